@@ -9,7 +9,7 @@
 One "step" = one complete evaluation: host packs the constrained parameters, one H2D copy, the HIP path for
 this rank's components (k -> rank k mod N), one all-reduce of the (P+1)-vector (RCCL) when N > 1, D2H, chain
 rule -- exactly what `LCGP.fit()` hands L-BFGS-B per function evaluation.  Inputs are resident in HBM before
-the timed region.  Rank 0 prints ONE JSON line.
+the timed region.  Rank 0 prints ONE JSON line; with --dump-outputs DIR it also writes what the last timed step returned.
 """
 import argparse
 import json
@@ -39,11 +39,18 @@ def parse():
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-stages', action='store_true')
     ap.add_argument('--no-fit', action='store_true', help='skip the wall-clock fit() leg')
-    ap.add_argument('--blocks', type=int, default=3, help='timed blocks of --steps evaluations (the first one is `value`)')
+    ap.add_argument('--blocks', type=int, default=1,
+                    help='timed blocks of --steps evaluations (the first one is `value`; more blocks show the spread and '
+                         'time blocks x --steps evaluations in all)')
     ap.add_argument('--cpu-repeats', type=int, default=5)
     ap.add_argument('--predict', type=int, default=2000, help='new inputs of the predict leg (K6); 0 = skip')
     ap.add_argument('--backend', default='nccl', help='process-group backend for --gpus > 1 (nccl = RCCL)')
-    return ap.parse_args()
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step returned (NLL and gradient, float64) as DIR/nll.npy and DIR/grad.npy')
+    args = ap.parse_args()
+    if args.steps < 1 or args.blocks < 1:
+        ap.error('--steps and --blocks must be at least 1')
+    return args
 
 
 def stage_times(m, reps=3):
@@ -232,11 +239,12 @@ def main():
         last = m.loss_and_grad(pts[i % len(pts)])
 
     def timed_block():
-        """EXACTLY --steps evaluations between two barrier + synchronize brackets; (local seconds, max over ranks)."""
+        """EXACTLY --steps evaluations between two barrier + synchronize brackets; (local seconds, max over ranks, what the
+        last evaluation returned)."""
         barrier()
         t0 = time.perf_counter()
         for i in range(args.steps):
-            m.loss_and_grad(pts[i % len(pts)])
+            last = m.loss_and_grad(pts[i % len(pts)])
         barrier()
         dt_local = time.perf_counter() - t0
         dt_max = dt_local
@@ -244,13 +252,20 @@ def main():
             tt = torch.tensor([dt_local], dtype=torch.float64, device='cuda' if args.backend == 'nccl' else 'cpu')
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
             dt_max = float(tt.item())
-        return dt_local, dt_max
+        return dt_local, dt_max, last
 
     # block 0 is the contract's measurement (`value`, `ms_per_step`); the further blocks only show the spread
-    blocks = [timed_block() for _ in range(max(1, args.blocks))]
-    dt_local, dt = blocks[0]
+    blocks = [timed_block() for _ in range(args.blocks)]
+    dt_local, dt, _ = blocks[0]
     per_block_ms = [1e3 * b[1] / args.steps for b in blocks]
     log('timed %d block(s) of %d steps: %s ms/step' % (len(blocks), args.steps, ['%.3f' % v for v in per_block_ms]))
+    if args.dump_outputs and rank == 0:
+        # the last timed step's result as its caller (L-BFGS-B) receives it; all-reduced, so every rank holds the same
+        nll, grad = blocks[-1][2]
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, 'nll.npy'), np.array([nll], np.float64))
+        np.save(os.path.join(args.dump_outputs, 'grad.npy'), np.asarray(grad, np.float64))
+        log('outputs of the last timed step written to %s (nll.npy, grad.npy)' % args.dump_outputs)
     n, d, p, q = int(m.n), int(m.d), int(m.p), int(m.q)
     flops_eval = float(q) * float(n) ** 3                       # potrf n^3/3 + inverse 2n^3/3 per component
     peak = FP64_MFMA_PEAK_TFLOPS if dtype == 'float64' else FP32_MFMA_PEAK_TFLOPS

@@ -3,7 +3,7 @@
 That file needs only numpy and scipy, so -- unlike lcgp.py / covmat.py, which need TensorFlow -- it can be
 loaded in the build container, by file path, without importing the `lcgp` package:
 
-    python tests/golden/make_eval_golden.py      # needs /root/reference; writes tests/golden/evaluation_golden.npz
+    python tests/golden/make_eval_golden.py <reference checkout>   # (or LCGP_REFERENCE=<dir>); writes evaluation_golden.npz
 
 Only numbers are stored (seeds of the inputs + the reference's outputs); no reference file travels anywhere.
 tests/test_evaluation_golden.py regenerates the inputs from the seeds and checks lcgp_amd/evaluation.py.
@@ -15,7 +15,6 @@ import sys
 import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-REF = os.environ.get('LCGP_REFERENCE', '/root/reference')
 
 # (seed, p, n): shapes cover p = 1, n = 1, and the KAT's (3, 400)
 CASES = [(1, 3, 400), (2, 1, 17), (3, 5, 1), (4, 8, 64), (5, 2, 1000)]
@@ -33,7 +32,10 @@ def case_inputs(seed, p, n):
 
 
 def main():
-    spec = importlib.util.spec_from_file_location('ref_evaluation', os.path.join(REF, 'src', 'lcgp', 'evaluation.py'))
+    ref_root = sys.argv[1] if len(sys.argv) > 1 else os.environ.get('LCGP_REFERENCE')
+    if not ref_root:
+        return 'usage: make_eval_golden.py <checkout of the reference LCGP package> (or set LCGP_REFERENCE)'
+    spec = importlib.util.spec_from_file_location('ref_evaluation', os.path.join(ref_root, 'src', 'lcgp', 'evaluation.py'))
     ref = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(ref)
     out = {'cases': np.array(CASES)}

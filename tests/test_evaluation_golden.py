@@ -32,6 +32,6 @@ def test_metrics_equal_the_reference_outputs(seed, p, n):
 
 
 def test_generator_is_not_needed_at_test_time():
-    """The fixture file is self-contained: nothing here reads /root/reference (absent on the GPU box)."""
+    """The fixture file is self-contained: nothing here reads the reference package (absent where the GPU tests run)."""
     src = open(os.path.join(HERE, 'test_evaluation_golden.py')).read()
     assert 'spec_from_file_location' not in src.split('def test_generator_is_not_needed_at_test_time')[0]

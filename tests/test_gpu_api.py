@@ -293,3 +293,30 @@ def test_bench_line_keeps_its_contract():
     assert r['clock_mhz'] is not None and r['clock_mhz'] > 0.0 and r['clock_window_us'] > 0.0
     assert r['traffic'] is None or r['traffic'] > 1e9
     assert set(d['roofline_stages']) == {'potrf', 'trtri', 'lauum'}
+
+
+def test_bench_dumps_what_its_last_timed_step_returned(tmp_path):
+    """`bench.py --dump-outputs DIR` writes the NLL and gradient of the LAST timed step (step --steps - 1 cycles through
+    synth.param_points): the same numbers an evaluation of that point in this process gives."""
+    import os
+    import subprocess
+    import sys
+    from lcgp_amd import synth
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    steps = 5
+    res = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', str(steps), '--warmup', '1',
+                          '--no-cpu-baseline', '--no-fit', '--no-stages', '--predict', '0', '--dump-outputs', str(tmp_path)],
+                         capture_output=True, text=True, timeout=600)
+    assert res.returncode == 0, res.stderr[-2000:]
+    assert sorted(os.listdir(tmp_path)) == ['grad.npy', 'nll.npy']
+    nll, grad = np.load(tmp_path / 'nll.npy'), np.load(tmp_path / 'grad.npy')
+    assert nll.dtype == np.float64 and grad.dtype == np.float64 and nll.shape == (1,)
+    x, y, cfg = synth.make_config(3)
+    m = LCGP(y=y, x=x, q=cfg['q'], submethod=cfg['submethod'], dtype='float64', device='cuda:0')
+    pts = synth.param_points(3, m._get_flat())
+    v, g = m.loss_and_grad(pts[(steps - 1) % len(pts)])
+    assert grad.shape == g.shape
+    assert abs(nll[0] - v) <= 1e-12 * abs(v), (nll[0], v)
+    np.testing.assert_allclose(grad, g, rtol=0, atol=1e-12 * np.max(np.abs(g)))
+    v0, _ = m.loss_and_grad(pts[0])
+    assert abs(nll[0] - v0) > 1e-6 * abs(v0)          # (the point of the last step, not the first)

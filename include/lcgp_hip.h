@@ -14,7 +14,10 @@
  *  - the library keeps NO mutable state (the only static is the thread-local text behind
  *    lcgp_last_error): schedule parameters travel with the call (lcgp_sched), so calls on different
  *    streams / devices / host threads are independent;
- *  - the caller owns all memory, including `workspace` (size from lcgp_workspace_bytes);
+ *  - the caller owns all memory, including `workspace` (size from lcgp_workspace_bytes);  the content of `workspace` and
+ *    of the `scratch` of lcgp_predict on entry is irrelevant: every value a call reads there was written earlier in the same
+ *    call or by the calls it documents as its input (lcgp_potrf_logdet -> lcgp_trtri -> lcgp_lauum, lcgp_nll_grad ->
+ *    lcgp_predict); tests/test_gpu_stage_bounds.py checks bitwise-equal results on zero, NaN and 0x5A-filled memory;
  *  - return value 0 = enqueued; < 0 = bad argument / HIP error (see lcgp_last_error()).
  *    A non positive-definite matrix is reported through the `info` word of the output block,
  *    not through the return value (the call is asynchronous).

@@ -1,0 +1,379 @@
+"""Stage-wise componentwise error bounds of the hot path (build, Cholesky, L^-1, A^-1, z, outputs, predict).
+
+Every check compares one stage of the library with a plain float64 reference computed from THE LIBRARY'S OWN INPUT TO THAT
+STAGE (the fetched A for the Cholesky, the fetched L for L^-1, ...), so no bound carries a condition number.  Entries are
+compared one by one (lower triangle for matrices): a wrong 64x64 tile of small far-off-diagonal entries is as visible as a
+wrong diagonal one, which a normwise max|error| / max|ref| is not.
+
+Every check returns a `Check`: the worst ratio |error| / bound over the entries (<= 1 passes; NaN counts as inf) and where
+it sits -- (row block, column block) of 64 for matrices, (block,) for vectors, the output slot name for scalars.
+
+Constants.  u is the unit roundoff of the stage's storage type (2^-53 float64, 2^-24 float32).  The standard model
+fl(a op b) = (a op b)(1 + e), |e| <= u, gives for an inner product of k terms, in ANY summation order (blocked, MFMA,
+tree), |fl(x^T y) - x^T y| <= gamma_k |x|^T |y|, gamma_k = k u / (1 - k u) <= 1.01 k u.  The library's error is bounded by
+that with one more rounding for the final subtraction / store (k + 1), and the float64 reference computed here from the
+fetched quantities commits at most the same again (for float64 stages) or a 2^-29 fraction of it (float32 stages).
+Everything below therefore uses C = 4 on top of "k + small": 2 for the library plus the reference, 2 of margin for the
+1.01 and the small additive terms.  Every bound also gets an absolute floor FLOOR_K x k x (smallest normal number of the
+dtype) for the entries that underflow (C0 cut-off, far tails of L^-1 and A^-1).
+
+The reference never calls the library.  It runs in torch float64 on the device of its inputs: numpy arrays are checked
+on the CPU, device tensors on the device (rocBLAS there, not this library's kernels).
+"""
+from __future__ import annotations
+
+import math
+from collections import namedtuple
+
+import numpy as np
+import torch
+
+TS = 64                  # tile size of the library (64 x 64 tiles): locations are reported in these blocks
+C = 4.0                  # see the module docstring
+FLOOR_K = 4.0
+EXP_FLOOR = {"float64": -708.0, "float32": -87.0}     # lcgp_hip.hip exp_floor<T>(): below, C0 is zero for the path
+
+Check = namedtuple("Check", "ratio where")
+
+
+def dname(dtype) -> str:
+    s = str(dtype)
+    return "float32" if ("32" in s) else "float64"
+
+
+def unit(dtype) -> float:
+    return 2.0 ** -24 if dname(dtype) == "float32" else 2.0 ** -53
+
+
+def tiny(dtype) -> float:
+    return float(np.finfo(np.float32 if dname(dtype) == "float32" else np.float64).tiny)
+
+
+def floor(dtype, k) -> float:
+    """absolute floor for an entry with inner dimension k"""
+    return FLOOR_K * max(int(k), 1) * tiny(dtype)
+
+
+def rounded(a, dtype):
+    """a rounded to the storage type (what the library holds after its upload), as float64 numpy"""
+    return np.asarray(np.asarray(a, np.float64).astype(np.float32 if dname(dtype) == "float32" else np.float64), np.float64)
+
+
+def _t(a, device=None):
+    if isinstance(a, torch.Tensor):
+        return a.to(device if device is not None else a.device, torch.float64)
+    return torch.as_tensor(np.asarray(a, np.float64), device=device)
+
+
+def _dev(*xs):
+    for a in xs:
+        if isinstance(a, torch.Tensor):
+            return a.device
+    return torch.device("cpu")
+
+
+def worst(err, bound, lower=True) -> Check:
+    """max over the entries of err / bound (lower triangle of a matrix when `lower`), with its 64-block location"""
+    r = err / bound
+    r = torch.where(torch.isnan(r), torch.full_like(r, math.inf), r)
+    if r.dim() == 2 and lower:
+        r = torch.tril(r)
+    if r.numel() == 0:
+        return Check(0.0, ())
+    idx = int(torch.argmax(r))
+    if r.dim() == 2:
+        i, j = divmod(idx, r.shape[1])
+        return Check(float(r.view(-1)[idx]), (i // TS, j // TS))
+    return Check(float(r.view(-1)[idx]), (idx // TS,))
+
+
+def combine(*checks) -> Check:
+    return max(checks, key=lambda c: c.ratio)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# covariance pieces in float64
+# ----------------------------------------------------------------------------------------------------------------------
+def kernel_parts(x1, x2, ell, kernel, dtype, device=None):
+    """C0 (n1 x n2) of the latent kernel in float64 from the ROUNDED inputs, the error magnification E of its evaluation in
+    the storage type, the mask of the entries past the library's C0 cut-off, and the lengthscale derivative factors
+    F_l = ell_l dC0/d ell_l (a list of d matrices, computed lazily by `dC0`).
+
+    E (units of u): the library stores x / ell rounded (|dS_l| <= u (|x1_l| + |x2_l|) / ell_l + u S_l), accumulates the
+    exponent in the storage type (d - 1 roundings of a sum bounded by its absolute value) and evaluates exp with an
+    error of at most one rounding of its argument's product with log2(e) plus one ulp (the float32 __expf: the sum-S term
+    accounts for it) and the Matern polynomial with d fused multiply-adds.
+      Matern32: d ln C0 / d S_l = -S_l / (1 + S_l), |.| <= 1:
+          E = sum_l (|x1_l| + |x2_l|) / ell_l + (d + 1) sum_l S_l + d + 3
+      SE: d ln C0 / d S_l = -S_l:
+          E = sum_l S_l ((|x1_l| + |x2_l|) / ell_l + S_l) + (d + 1) 1/2 sum_l S_l^2 + 3
+    """
+    dev = device if device is not None else _dev(x1, x2)
+    a = _t(x1, dev)
+    b = _t(x2, dev)
+    ell = np.asarray(ell, np.float64)
+    d = a.shape[1]
+    ssum = torch.zeros(a.shape[0], b.shape[0], dtype=torch.float64, device=dev)
+    poly = torch.ones_like(ssum)
+    mag = torch.zeros_like(ssum)
+    for l in range(d):
+        xa = a[:, l] / ell[l]
+        xb = b[:, l] / ell[l]
+        s = (xa[:, None] - xb[None, :]).abs()
+        m = xa.abs()[:, None] + xb.abs()[None, :]
+        if kernel == "se":
+            ssum += 0.5 * s * s
+            mag += s * (m + s)
+        else:
+            ssum += s
+            poly *= 1.0 + s
+            mag += m
+    if kernel == "se":
+        c0 = torch.exp(-ssum)
+        e = mag + (d + 1) * ssum + 3.0
+    else:
+        c0 = poly * torch.exp(-ssum)
+        e = mag + (d + 1) * ssum + d + 3.0
+    cut = ssum > -EXP_FLOOR[dname(dtype)]
+    return c0, e, cut
+
+
+def dC0(x1, x2, ell, kernel, device=None):
+    """ell_l d C0 / d ell_l for every l (Matern32: C0 S_l^2 / (1 + S_l); SE: C0 S_l^2), float64"""
+    dev = device if device is not None else _dev(x1, x2)
+    a, b = _t(x1, dev), _t(x2, dev)
+    ell = np.asarray(ell, np.float64)
+    c0 = kernel_parts(a, b, ell, kernel, "float64", dev)[0]
+    out = []
+    for l in range(a.shape[1]):
+        s = (a[:, l][:, None] / ell[l] - b[:, l][None, :] / ell[l]).abs()
+        out.append(c0 * s * s / (1.0 + s) if kernel != "se" else c0 * s * s)
+    return out
+
+
+def split_theta(th, d):
+    th = np.asarray(th, np.float64)
+    ell, scale, nug, D = th[:d], float(th[d]), float(th[d + 1]), float(th[d + 2])
+    return ell, scale, nug, D, th[d + 3:]
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# stage checks
+# ----------------------------------------------------------------------------------------------------------------------
+def reference_A(x, sr, th, kernel, dtype, device=None):
+    """A = I + D (C o sr sr^T) in float64 from the dtype-rounded x, sr (theta is float64 in both precisions)"""
+    d = np.asarray(x).shape[1]
+    ell, scale, nug, D, _ = split_theta(th, d)
+    c0, e, cut = kernel_parts(rounded(x, dtype), rounded(x, dtype), ell, kernel, dtype, device)
+    dev = c0.device
+    n = c0.shape[0]
+    s = _t(rounded(np.ones(n) if sr is None else sr, dtype), dev)
+    ss = s[:, None] * s[None, :]
+    nt = nug / (1.0 + nug)
+    eye = torch.eye(n, dtype=torch.float64, device=dev)
+    a = eye + D * scale * ss * ((1.0 - nt) * c0 + nt * eye)
+    return a, e, cut, ss
+
+
+def check_build(A, b, x, Y, sr, th, kernel, dtype) -> Check:
+    """A (the fetched matrix after lcgp_kernel_build) and b (fetch_vector 0) against their float64 definitions.
+
+    off the diagonal A_ij = ss_ij c_off C0_ij with c_off = D scale (1 - nt) rounded: relative error (E + 4) u (E of
+    kernel_parts; c_off, ss_ij and two products: four roundings).  The diagonal adds 1 + (c_diag - 1) ss_ii with
+    c_diag = 1 + D scale nt rounded: absolute error u ((1 + D scale nt) ss_ii + |A_ii|) -- the issue's bound
+    c (d + 3 + sum S) u |A_ij - delta_ij| misses exactly this term (it is not relative to A_ii - 1).  Past the C0 cut-off
+    (exponent below exp_floor) the library may return any value in [0, C0]: the bound there is |A_ij - delta_ij| itself.
+    b_i = sum_a Y_ai psi_a is accumulated in float64 and rounded once to storage: C p u64 (|Y|^T |psi|)_i + 2 u |b_i|
+    (the rounding to storage, with the margin factor 2 the other bounds carry in C).  b = None checks A alone (the
+    stand-alone lcgp_kernel_build, which has no Y, does not form b).
+    """
+    dev = _dev(A, b)
+    d = np.asarray(x).shape[1]
+    u = unit(dtype)
+    ell, scale, nug, D, psi = split_theta(th, d)
+    aref, e, cut, ss = reference_A(x, sr, th, kernel, dtype, dev)
+    n = aref.shape[0]
+    eye = torch.eye(n, dtype=torch.float64, device=dev)
+    off = (aref - eye).abs()
+    nt = nug / (1.0 + nug)
+    bound = C * (e + 4.0) * u * off + floor(dtype, d)
+    bound = bound + torch.where(cut, off, torch.zeros_like(off))
+    bound = bound + torch.diag(C * u * ((1.0 + abs(D * scale * nt)) * torch.diagonal(ss) + torch.diagonal(aref).abs()))
+    ca = worst((_t(A, dev) - aref).abs(), bound)
+    if b is None:
+        return ca
+    yr = _t(rounded(Y, dtype), dev)
+    ps = _t(psi, dev)
+    bref = yr.T @ ps
+    bb = C * yr.shape[0] * unit("float64") * (yr.abs().T @ ps.abs()) + 2.0 * u * bref.abs() + floor(dtype, 1)
+    cb = worst((_t(b, dev) - bref).abs(), bb)
+    return combine(ca, cb)
+
+
+def check_cholesky(A, L, dtype) -> Check:
+    """|A - L L^T|_ij <= C (min(i, j) + 2) u (|L| |L^T|)_ij: the componentwise backward error of any Cholesky variant
+    (blocked, right- or left-looking, MFMA) -- k = min(i, j) + 1 products plus the subtraction; independent of kappa(A)."""
+    dev = _dev(A, L)
+    a = _t(A, dev)
+    l = torch.tril(_t(L, dev))
+    n = a.shape[0]
+    r = (a - l @ l.T).abs()
+    idx = torch.arange(n, device=dev, dtype=torch.float64)
+    k = torch.minimum(idx[:, None], idx[None, :]) + 2.0
+    la = l.abs()
+    return worst(r, C * k * unit(dtype) * (la @ la.T) + floor(dtype, n))
+
+
+def check_half_logdet(L, half_logdet, dtype) -> Check:
+    """half_logdet (the library sums 1/2 log(pivot) in float64) against fsum(log L_ii) of the fetched factor:
+    C u (n sum |log L_ii| + n).  The second term is the rounding of each stored L_ii = sqrt(pivot): an absolute error of
+    u in log L_ii however close L_ii is to 1 (the issue's c n u sum |log L_ii| alone misses it for A near I)."""
+    dg = torch.diagonal(_t(L)).cpu().numpy()
+    n = dg.size
+    lg = np.log(dg)
+    ref = math.fsum(lg)
+    bound = C * unit(dtype) * (n * float(np.sum(np.abs(lg))) + n) + floor(dtype, n)
+    r = abs(float(half_logdet) - ref) / bound
+    return Check(r if np.isfinite(r) else math.inf, ("half_logdet",))
+
+
+def check_inverse_factor(L, W, dtype) -> Check:
+    """W = L^-1 against solve_triangular(L, I) in float64: 2 C n u (|W| |L| |W|)_ij.  Any method whose residual satisfies
+    |W L - I| <= c n u |W| |L| (or |L W - I| <= c n u |L| |W|) has W - L^-1 = (W L - I) L^-1, so this forward bound holds
+    for every blocked / level-parallel variant; the factor 2 covers W vs L^-1 on the right and the reference's own solve."""
+    dev = _dev(L, W)
+    l = torch.tril(_t(L, dev))
+    n = l.shape[0]
+    eye = torch.eye(n, dtype=torch.float64, device=dev)
+    wref = torch.linalg.solve_triangular(l, eye, upper=False)
+    wa = wref.abs()
+    bound = 2.0 * C * n * unit(dtype) * (wa @ (l.abs() @ wa)) + floor(dtype, n)
+    return worst((torch.tril(_t(W, dev)) - wref).abs(), bound)
+
+
+def check_inverse(W, V, dtype) -> Check:
+    """A^-1 = W^T W (lower triangle) against the float64 product of the fetched W: entry (i, j), i >= j, is an inner
+    product over k = i .. n-1, i.e. n - max(i, j) terms: C (n - max(i, j) + 2) u (|W|^T |W|)_ij"""
+    dev = _dev(W, V)
+    w = torch.tril(_t(W, dev))
+    n = w.shape[0]
+    vref = w.T @ w
+    idx = torch.arange(n, device=dev, dtype=torch.float64)
+    k = n - torch.maximum(idx[:, None], idx[None, :]) + 2.0
+    wa = w.abs()
+    return worst((_t(V, dev) - vref).abs(), C * k * unit(dtype) * (wa.T @ wa) + floor(dtype, n))
+
+
+def check_z(V, b, z, dtype) -> Check:
+    """z = A^-1 b against V b (V symmetric, as fetched): C n u (|V| |b|) + 2 u |z| (the last term: rounding to storage)"""
+    dev = _dev(V, b, z)
+    v, bb = _t(V, dev), _t(b, dev)
+    zref = v @ bb
+    n = zref.shape[0]
+    bound = C * n * unit(dtype) * (v.abs() @ bb.abs()) + 2.0 * unit(dtype) * zref.abs() + floor(dtype, n)
+    return worst((_t(z, dev) - zref).abs(), bound)
+
+
+def reference_outputs(x, Y, sr, th, V, b, z, kernel, dtype):
+    """(ref, bound) float64 tensors over the output row [quad, g_ell_0 .. g_ell_{d-1}, g_scale, g_nug, gsig_0 .. gsig_{p-1}]
+    from the library's V, b, z and the float64 kernel of the rounded x (see check_outputs)."""
+    dev = _dev(V, b, z)
+    d = np.asarray(x).shape[1]
+    u = unit("float64")               # the contraction runs in float64 in both precisions (check_outputs)
+    ell, scale, nug, D, psi = split_theta(th, d)
+    xr = rounded(x, dtype)
+    c0, e, cut = kernel_parts(xr, xr, ell, kernel, "float64", dev)
+    n = c0.shape[0]
+    s = _t(rounded(np.ones(n) if sr is None else sr, dtype), dev)
+    ss = s[:, None] * s[None, :]
+    nt = nug / (1.0 + nug)
+    v, bb, zz = _t(V, dev), _t(b, dev), _t(z, dev)
+    yr = _t(rounded(Y, dtype), dev)
+    eye = torch.eye(n, dtype=torch.float64, device=dev)
+    G = ss * (0.5 * D * v - 0.5 * zz[:, None] * zz[None, :])
+    Ga = ss * (0.5 * abs(D) * v.abs() + 0.5 * zz.abs()[:, None] * zz.abs()[None, :])
+    wgt = C * u * (n + d + e)
+    fl = floor("float64", n)
+    ref, bnd = [], []
+    if dname(dtype) == "float32":
+        # quad = D b^T (C o ss) z, gsig = D Y (C o ss) z: the cancellation-free forms the float32 path evaluates
+        cm = ss * scale * ((1.0 - nt) * c0 + nt * eye)
+        cz = cm @ zz
+        cz_b = (wgt * cm.abs()) @ zz.abs()
+        ref.append(D * torch.dot(bb, cz))
+        bnd.append(abs(D) * torch.dot(bb.abs(), cz_b) + fl)
+        gs_ref, gs_bnd = D * (yr @ cz), abs(D) * (yr.abs() @ cz_b) + fl
+    else:
+        ref.append(torch.dot(bb, bb - zz))
+        bnd.append(C * n * u * torch.dot(bb.abs(), bb.abs() + zz.abs()) + fl)
+        gs_ref = yr @ (bb - zz)
+        gs_bnd = C * n * u * (yr.abs() @ (bb.abs() + zz.abs())) + fl
+    for l, f in enumerate(dC0(xr, xr, ell, kernel, dev)):
+        k = scale * (1.0 - nt) / ell[l]
+        ref.append(k * (G * f).sum())
+        bnd.append(abs(k) * (wgt * Ga * f).sum() + fl)
+    sc0, trg = (G * c0).sum(), torch.trace(G)
+    asc0, atrg = (wgt * Ga * c0).sum(), torch.trace(wgt * Ga)
+    ref.append((1.0 - nt) * sc0 + nt * trg)
+    bnd.append((1.0 - nt) * asc0 + nt * atrg + fl)
+    ref.append(scale * (trg - sc0) / (1.0 + nug) ** 2)
+    bnd.append(abs(scale) * (atrg + asc0) / (1.0 + nug) ** 2 + fl)
+    ref = torch.cat([torch.stack(ref), gs_ref])
+    bnd = torch.cat([torch.stack(bnd), gs_bnd])
+    return ref, bnd
+
+
+def output_names(d, p):
+    return ["quad"] + ["g_ell%d" % l for l in range(d)] + ["g_scale", "g_nug"] + ["gsig%d" % a for a in range(p)]
+
+
+def check_outputs(out_row, x, Y, sr, th, V, b, z, kernel, dtype) -> Check:
+    """quad, gradients and gsig of one output row against the float64 contraction of the library's own V, b, z.
+
+    Precision.  In BOTH storage types the library does this stage in float64: grad_kernel / grad_kernel_wide convert the
+    stored x, sr, z and V to double, form x / ell, G, C0 and dC0 in double and accumulate in double; the c = (C o ss) z
+    partials of float32, cvec_reduce_kernel, gsig_c_kernel, gsig_body and finalize_kernel are double as well.  The only
+    float32 roundings are those of the stored inputs, and the reference uses exactly those (the fetched V, b, z and the
+    rounded x, Y, sr).  So u is the float64 unit roundoff here whatever the storage type, E is kernel_parts' float64
+    magnification and the floor is float64's.
+
+    Gradients: G = ss o (D/2 V - z z^T / 2) contracted with dC/dtheta (formulas of finalize_kernel): each term carries
+    (n + d + E_ij) u relative to |G|-with-absolute-values Ga = ss o (|D|/2 |V| + |z| |z|^T / 2) times |dC| (n: the
+    reduction over the tiles, d: the dimensions, E: the kernel evaluation).  quad and gsig: C n u (|b|^T (|b| + |z|)) in
+    float64 storage; in float32 storage the library evaluates D b^T (C o ss) z and D Y (C o ss) z (finalize_kernel /
+    gsig_c_kernel, the forms without the cancellation of b - z), bounded the same way as the gradients."""
+    d, p = np.asarray(x).shape[1], np.asarray(Y).shape[0]
+    ref, bnd = reference_outputs(x, Y, sr, th, V, b, z, kernel, dtype)
+    o = np.asarray(out_row, np.float64)
+    got = _t(np.concatenate([o[1:2], o[3:]]), ref.device)
+    r = (got - ref).abs() / bnd
+    r = torch.where(torch.isnan(r), torch.full_like(r, math.inf), r)
+    i = int(torch.argmax(r))
+    return Check(float(r[i]), (output_names(d, p)[i],))
+
+
+def check_predict(ghat, gvar, x0, x, sr, th, W, z, kernel, dtype) -> Check:
+    """predictions at x0 (not the training set: no nugget) against the float64 cross covariance X = scale (1 - nt)
+    C0(x0, x) o sr^T of the rounded inputs and the library's W, z:
+        ghat = X z             C (n + d + E) u |X| |z|
+        gvar = scale - D |W X_i^T|^2     C (n + d + E) u |D| || |W| |X_i| ||^2 + u scale"""
+    dev = _dev(W, z)
+    d = np.asarray(x).shape[1]
+    u = unit(dtype)
+    ell, scale, nug, D, _ = split_theta(th, d)
+    nt = nug / (1.0 + nug)
+    c0, e, cut = kernel_parts(rounded(x0, dtype), rounded(x, dtype), ell, kernel, dtype, dev)
+    n = c0.shape[1]
+    s = _t(rounded(np.ones(n) if sr is None else sr, dtype), dev)
+    X = scale * (1.0 - nt) * c0 * s[None, :]
+    Xa = X.abs() + torch.where(cut, X.abs(), torch.zeros_like(X))
+    wgt = C * u * (n + d + e.max(dim=1).values)
+    w = torch.tril(_t(W, dev))
+    zz = _t(z, dev)
+    gref = X @ zz
+    gb = wgt * (Xa @ zz.abs()) + floor(dtype, n)
+    U = X @ w.T
+    vref = scale - D * (U * U).sum(dim=1)
+    Ua = Xa @ w.abs().T
+    vb = wgt * abs(D) * (Ua * Ua).sum(dim=1) + u * abs(scale) + floor(dtype, n)
+    return combine(worst((_t(ghat, dev) - gref).abs(), gb), worst((_t(gvar, dev) - vref).abs(), vb))

@@ -230,6 +230,7 @@ def test_schedule_parameters_do_not_change_results():
                        dict(progressive_tiles=1 << 30, leaf_in_wide=0), dict(progressive_tiles=1 << 30, outer_blocks=3),
                        dict(progressive_tiles=1 << 30, progressive_lauum=0), dict(progressive_tiles=1 << 30, progressive_lauum=0, outer_blocks=2)):
             eng.sched = _sched(**fields)
+            eng.workspace.fill_(0xFF)        # NaN in both dtypes: a tile this schedule fails to write cannot pass for the last one's
             v, g = m.loss_and_grad(u)
             assert abs(v - ref_v) <= 1e-11 * abs(ref_v), fields
             assert np.max(np.abs(g - ref_g)) <= 1e-10 * np.max(np.abs(ref_g)), fields
@@ -259,6 +260,7 @@ def test_wide_tile_schedules_agree_at_medium_size():
                        dict(progressive_tiles=1 << 30, progressive_far=0, syrk_small_tiles=16),
                        dict(progressive_tiles=1 << 30, fill_leaf=40, fill_step=56), dict(progressive_tiles=1 << 30, outer_blocks=8)):
             eng.sched = _sched(**fields)
+            eng.workspace.fill_(0xFF)        # NaN in both dtypes: a tile this schedule fails to write cannot pass for the last one's
             v, g = m.loss_and_grad(u)
             assert abs(v - ref_v) <= 1e-11 * abs(ref_v), fields
             assert np.max(np.abs(g - ref_g)) <= 1e-10 * np.max(np.abs(ref_g)), fields
@@ -297,6 +299,7 @@ def test_progressive_inverse_with_jobs_split_over_launches():
                        dict(progressive_tiles=1 << 30, fill_leaf=6, fill_step=6), dict(progressive_tiles=1 << 30, progressive_far=0),
                        dict(progressive_tiles=1 << 30, progressive_lauum=0), dict(progressive_tiles=1 << 30, progressive_lauum=0, fill_leaf=30, fill_step=18)):
             eng.sched = _sched(**fields)
+            eng.workspace.fill_(0xFF)        # NaN in both dtypes: a tile this schedule fails to write cannot pass for the last one's
             v, g = m.loss_and_grad(u)
             assert abs(v - ref_v) <= 1e-11 * abs(ref_v), fields
             assert np.max(np.abs(g - ref_g)) <= 1e-10 * np.max(np.abs(ref_g)), fields

@@ -211,6 +211,7 @@ def test_cfg3_repeated_evaluations_are_bitwise_identical(cfg3):
     v0, g0 = m.loss_and_grad(u)
     for _ in range(4):
         m.loss_and_grad(m._get_flat() * 0 + synth.param_points(3, u)[0])      # another point in between
+        m._get_engine().workspace.fill_(0xFF)        # and a workspace of NaNs: every value read must be written in this call
         v, g = m.loss_and_grad(u)
         assert v == v0
         assert np.array_equal(g, g0)

@@ -2,7 +2,11 @@
 fields -- paired panels, filler capacities, panel widths, tile-size thresholds, the inverse behind the chain -- against the
 plainest schedule (no filler, no pairs, inverse after the factorisation) of the same problem.
 
-    python tools/sched_fuzz.py [cases] [seed] [big]
+    python tools/sched_fuzz.py [cases] [seed] [big] [--dtype float32]
+
+Every evaluation after the plainest one runs on a workspace filled with 0xFF bytes (NaN in both precisions), so a tile a
+schedule fails to write cannot pass for the one the previous schedule left behind.  The float32 engines are compared at
+1e-4 / 1e-3 (their own rounding differs by summation order), the float64 ones at 1e-10 / 1e-9.
 """
 import sys
 import numpy as np
@@ -20,9 +24,17 @@ def sched(**kw):
 
 
 def main():
-    cases = int(sys.argv[1]) if len(sys.argv) > 1 else 40
-    big = len(sys.argv) > 3 and sys.argv[3] == 'big'          # sizes around the headline configuration
-    rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 0)
+    argv = sys.argv[1:]
+    dtype = 'float64'
+    if '--dtype' in argv:
+        i = argv.index('--dtype')
+        dtype = argv[i + 1]
+        del argv[i:i + 2]
+    assert dtype in ('float64', 'float32'), dtype
+    tol_v, tol_g = (1e-10, 1e-9) if dtype == 'float64' else (1e-4, 1e-3)
+    cases = int(argv[0]) if len(argv) > 0 else 40
+    big = len(argv) > 2 and argv[2] == 'big'          # sizes around the headline configuration
+    rng = np.random.default_rng(int(argv[1]) if len(argv) > 1 else 0)
     worst = 0.0
     for case in range(cases):
         n = int(rng.integers(2600, 4300)) if big else int(rng.choice([rng.integers(65, 400), rng.integers(400, 1700), rng.integers(1700, 2600)]))
@@ -30,7 +42,8 @@ def main():
         d = int(rng.integers(1, 7))
         p = int(rng.integers(q, q + 6))
         x, y = synth.make_full(1000 + case, n, d, p, q)
-        m = LCGP(y=y, x=x, q=q)
+        m = LCGP(y=y, x=x, q=q, dtype=dtype)
+        m.float32_fallback = False                    # (a float64 repeat would compare float64 with itself)
         u = synth.param_points(1000 + case, m._get_flat())[1]
         eng = m._get_engine()
         eng.sched = sched(fill_leaf=0, fill_step=0, pair_tiles=0, progressive_tiles=0, leaf_in_wide=0)
@@ -42,12 +55,13 @@ def main():
                      progressive_tiles=int(rng.choice([0, 0, 600, 1 << 30])), trtri_level_small=int(rng.choice([0, 600, 100000])),
                      lauum_small_tiles=int(rng.choice([0, 2048, 100000])), trtri_small_tiles=int(rng.choice([0, 4200, 100000])))
             eng.sched = sched(**f)
+            eng.workspace.fill_(0xFF)
             v, g = m.loss_and_grad(u)
             ev = abs(v - v0) / abs(v0)
             eg = float(np.max(np.abs(g - g0)) / np.max(np.abs(g0)))
             worst = max(worst, ev, eg)
-            assert np.isfinite(v) and ev <= 1e-10 and eg <= 1e-9, (n, q, d, p, f, ev, eg)
-        print('case %2d  n=%4d q=%d d=%d p=%2d  ok' % (case, n, q, d, p), flush=True)
+            assert np.isfinite(v) and ev <= tol_v and eg <= tol_g, (n, q, d, p, f, ev, eg)
+        print('case %2d  %s n=%4d q=%d d=%d p=%2d  ok' % (case, dtype, n, q, d, p), flush=True)
     print('all schedules agree; worst relative difference %.2e' % worst)
 
 

@@ -218,6 +218,33 @@ int lcgp_predict(void* stream, int dtype, int kernel_id, int n, int d, int p, in
                  int n0, const void* x0, int same, void* scratch,
                  double* ghat /*q_local rows of n0*/, double* gvar /*q_local rows of n0*/, int out_stride);
 
+/* Joint posterior covariance over new inputs, and correlated draws (no counterpart in the reference: its predict is marginal
+ * only).  For local component k and n0 new inputs x0 (standardised), with c0k, sr, L_k^-1 exactly as in lcgp_predict:
+ *     Sigma_k = C00_k - D_k U_k U_k^T,   U_k = (c0k o sr^T) L_k^-T    (n0 x n),   diag(Sigma_k) = gvar[k, :] of lcgp_predict
+ *     C00_k   = the covariance kernel of x0 with itself, nugget on the diagonal (lcgp_covmat with same = 1)
+ * The result is written into a SECOND workspace, `cov_workspace`, of lcgp_workspace_bytes(dtype, n0, d, p, q_local) bytes:
+ * its matrix slot (lcgp_fetch_matrix(..., n0, ..., which = 0, k)) holds Sigma_k + tau_k I, tau_k = jitter * scale_k, lower
+ * tiles valid, identity on the padding -- exactly what lcgp_potrf_logdet(dtype, n0, d, p, q_local, cov_workspace, ...)
+ * factors in place (its info word reports a Sigma_k + tau_k I that is not numerically positive definite).
+ *   `same`: as in lcgp_predict (the nugget term of the cross covariance c0k; 0 = x0 is not the training set).
+ *   scratch: lcgp_predict_cov_scratch_bytes(dtype, n, q_local, n0) bytes.
+ * Flops per component: n0pad^2 npad (the lower tiles of U U^T, n0pad = n0 rounded up to 128) + n0pad npad^2 / 2 (U). */
+int lcgp_predict_cov_scratch_bytes(int dtype, int n, int q_local, int n0, size_t* bytes /*host out*/);
+int lcgp_predict_cov(void* stream, int dtype, int kernel_id, int n, int d, int p, int q_local,
+                     const void* x, const void* sr, const double* theta, const void* workspace,
+                     int n0, const void* x0, int same, void* scratch, void* cov_workspace, double jitter);
+
+/* Draws from the factor lcgp_potrf_logdet left in `cov_workspace` (L_k L_k^T = Sigma_k + tau_k I):
+ *     out[k, s, :] = ghat[k, :] + L_k eps[k, s, :]          s < S
+ * eps: q_local x S x n0 standard normals (dtype, dense); ghat: q_local rows of n0 doubles, `ldg` apart (0 = n0), e.g. the
+ * ghat of lcgp_predict; out: q_local x S x n0 doubles.  The call zeroes the unused strict upper triangle of the factor's
+ * diagonal tiles (the product reads whole tiles).  scratch: lcgp_sample_scratch_bytes(dtype, n0, q_local, S) bytes.
+ * Flops per component: S n0pad^2 (S rounded up to 128). */
+#define LCGP_SAMPLE_MAX 32768
+int lcgp_sample_scratch_bytes(int dtype, int n0, int q_local, int S, size_t* bytes /*host out*/);
+int lcgp_sample_latent(void* stream, int dtype, int n0, int d, int p, int q_local, int S, void* cov_workspace,
+                       const void* eps, const double* ghat, int ldg, void* scratch, double* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -23,7 +23,7 @@
 #include "../../include/lcgp_hip.h"
 #include "fill_sched.h"
 
-#define LCGP_VERSION 510
+#define LCGP_VERSION 520
 
 namespace {
 
@@ -719,7 +719,7 @@ __global__ __launch_bounds__(256, 2) void leaf_kernel(T* __restrict__ M, T* __re
 #ifndef LCGP_EXP
 #define LCGP_EXP 0      // destructive timing experiments (tools/build_variant.sh ... -DLCGP_EXP=n); 0 in every product build
 #endif
-enum GemmOp { OP_SYRK = 1, OP_TRTRI_T = 2, OP_TRTRI_W = 3, OP_LAUUM = 4, OP_PRED_U = 5 };
+enum GemmOp { OP_SYRK = 1, OP_TRTRI_T = 2, OP_TRTRI_W = 3, OP_LAUUM = 4, OP_PRED_U = 5, OP_PRED_COV = 6 };
 enum Lay { MK = 0, KM = 1 };
 
 struct GemmArgs {
@@ -736,6 +736,7 @@ struct GemmArgs {
     double* part = nullptr;                     // z = A^-1 b, [component][tile][2][128]; null = no fused product
     unsigned long long* clk = nullptr;          // OP_LAUUM: the first block (the longest K loop of the launch) leaves its duration
                                                 // in shader-clock cycles and in 10 ns ticks here: the clock the chip held (lcgp_lauum_clock)
+    const double* theta = nullptr;              // OP_PRED_COV: theta rows, p1 doubles apart; D_k is element p2 of row k
 };
 
 // one K-stage (KT = 16 k values) of a TM-row operand tile: global -> registers -> LDS [k][m], ld = TM + 16;
@@ -1075,6 +1076,15 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& g, const int lin /*blo
         nkt = g.nb - r;
         tri_b = r == c;
         Ct = Cb + (size_t)r * TM * g.ldC + (size_t)c * TM;
+    } else if constexpr (OP == OP_PRED_COV) {
+        // C[r, c] -= D_k sum_{kt < p0} U[r, kt] U[c, kt]^T over the lower tiles c <= r   (U = n0pad x npad, p0 = npad / TM)
+        int r, c;
+        tri_decode(bid, r, c);
+        A0 = Ab + (size_t)r * TM * g.ldA; dA = TM;
+        B0 = Bb + (size_t)c * TM * g.ldB; dB = TM;
+        nkt = g.p0;
+        Ct = Cb + (size_t)r * TM * g.ldC + (size_t)c * TM;
+        accumulate = true;          // (alpha = -D_k is read behind the k loop: nothing more lives across it than in OP_PRED_U)
     } else {
         // OP_PRED_U: U[m, r] = sum_{kt = 0}^{r} X[m, kt] W[r, kt]^T    (X = scaled cross covariance, n0pad x npad)
         const int r = g.nb - 1 - bid / g.p0, m = bid % g.p0;       // p0 = row tiles of X; longest k loops (large r) first
@@ -1131,7 +1141,7 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& g, const int lin /*blo
     // only add exact zeros: it skips the stage's fragment reads and MFMAs (one wave-uniform test per stage, nothing
     // else changes; bit-identical results: the zeros are stored zeros).  LAUUM / TRTRI_W: 24 of the 64 (wave, stage)
     // pairs of such a tile, TRTRI_T / PRED_U: 16.
-    constexpr bool HAS_TRI = OP != OP_SYRK;
+    constexpr bool HAS_TRI = OP != OP_SYRK && OP != OP_PRED_COV;
     const int tri_first = HAS_TRI ? (nkt - 1) * SPT : nst;
     // the wave is idle in the stages [dead_lo, dead_hi) of the k loop (two scalars per wave)
     int dead_lo = nst, dead_hi = nst;
@@ -1315,6 +1325,7 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& g, const int lin /*blo
         }
         }
     }
+    if constexpr (OP == OP_PRED_COV) alpha = -g.theta[(size_t)k * g.p1 + g.p2];
 #pragma unroll
     for (int mi = 0; mi < MIM; ++mi)
 #pragma unroll
@@ -2997,6 +3008,131 @@ int do_predict(hipStream_t st, const Ws& w, const void* x, const void* sr, const
     return 0;
 }
 
+// ---------------------------------------------------------------------------------------------------
+// Joint posterior covariance over new inputs and correlated draws (no counterpart in the reference, whose predict is
+// marginal only).  The covariance lives in the matrix slot of a SECOND workspace carved for n = n0 (n0pad = round_up(n0,
+// 128), the padding the factorisation expects), so lcgp_potrf_logdet factors it unchanged.
+// ---------------------------------------------------------------------------------------------------
+inline int cov_pad(int n0) { return round_up(n0, 2 * TS); }
+
+// diagonal of Sigma_k + tau_k I (tau_k = jitter scale_k) and the identity block of the padding (rows n0 .. n0pad: zero from
+// cross_kernel and from the zero rows of U, so only the diagonal needs a value)
+template <typename T>
+__global__ __launch_bounds__(256) void cov_diag_kernel(T* __restrict__ M, size_t mat, int n0, int n0pad,
+                                                       const double* __restrict__ theta, int tw, int d, double jitter) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x, k = blockIdx.y;
+    if (i >= n0pad) return;
+    T* e = M + (size_t)k * mat + (size_t)i * n0pad + i;
+    *e = i < n0 ? (T)((double)*e + jitter * theta[(size_t)k * tw + d]) : (T)1;
+}
+
+// zeroes the strict upper triangle of the 128x128 diagonal tiles of a factor: the draw product (OP_PRED_U) reads whole
+// diagonal tiles and relies on stored zeros there, which the factorisation leaves only inside its 64x64 diagonal blocks
+template <typename T>
+__global__ __launch_bounds__(256) void diag_tile_upper_zero_kernel(T* __restrict__ M, size_t mat, int ld) {
+    const int t = blockIdx.x, k = blockIdx.y;
+    T* base = M + (size_t)k * mat + (size_t)t * 2 * TS * ld + (size_t)t * 2 * TS;
+    for (int e = threadIdx.x; e < 4 * TS * TS; e += 256) {
+        const int i = e / (2 * TS), j = e - i * (2 * TS);
+        if (j > i) base[(size_t)i * ld + j] = (T)0;
+    }
+}
+
+// dense eps (q, S, n0) -> zero-padded (q, Spad, n0pad)
+template <typename T>
+__global__ __launch_bounds__(256) void eps_pack_kernel(const T* __restrict__ eps, int S, int n0, T* __restrict__ E, int n0pad,
+                                                       size_t slab) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x, s = blockIdx.y, k = blockIdx.z;
+    if (i >= n0pad) return;
+    E[(size_t)k * slab + (size_t)s * n0pad + i] = (s < S && i < n0) ? eps[((size_t)k * S + s) * n0 + i] : (T)0;
+}
+
+// out[k, s, i] = ghat[k, i] + (L_k E_k)^T[s, i]
+template <typename T>
+__global__ __launch_bounds__(256) void draw_out_kernel(const T* __restrict__ G, int n0pad, size_t slab, int S, int n0,
+                                                       const double* __restrict__ ghat, int ldg, double* __restrict__ out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x, s = blockIdx.y, k = blockIdx.z;
+    if (i >= n0) return;
+    out[((size_t)k * S + s) * n0 + i] = ghat[(size_t)k * ldg + i] + (double)G[(size_t)k * slab + (size_t)s * n0pad + i];
+}
+
+// Sigma_k + tau_k I for all local components:  C00_k = kernel(x0, x0) with the nugget on the diagonal (cross_kernel, same =
+// 1), X_k = c0k o sr^T and U_k = X_k W_k^T exactly as do_predict forms them, then ONE launch of the tile kernel
+// C00_k -= D_k U_k U_k^T over the lower tiles (K = npad), then the diagonal.
+template <typename T>
+int do_predict_cov(hipStream_t st, const Ws& w, const void* x, const void* sr, const double* theta, int n0, const void* x0,
+                   int same, void* scratch, const Ws& cw, double jitter) {
+    const int n0pad = cw.npad;
+    const size_t slab = (size_t)n0pad * w.npad;
+    T* X = (T*)scratch;
+    T* U = X + slab * w.q;
+    T* M = (T*)(cw.base + cw.off_M);
+    const int tw = w.d + 3 + w.p;
+    ThetaArg dummy;
+    memset(&dummy, 0, sizeof(dummy));
+    dim3 gx(w.nb, n0pad / TS, w.q), gc(n0pad / TS, n0pad / TS, w.q);
+    if (w.kern == 0) {
+        hipLaunchKernelGGL((cross_kernel<T, 0>), gx, dim3(256), 0, st, X, w.npad, n0, w.n, w.d, (const T*)x0, (const T*)x, dummy,
+                           theta, same, (const T*)sr, n0pad, w.npad, tw, slab);
+        hipLaunchKernelGGL((cross_kernel<T, 0>), gc, dim3(256), 0, st, M, n0pad, n0, n0, w.d, (const T*)x0, (const T*)x0, dummy,
+                           theta, 1, (const T*)nullptr, n0pad, n0pad, tw, cw.mat);
+    } else {
+        hipLaunchKernelGGL((cross_kernel<T, 1>), gx, dim3(256), 0, st, X, w.npad, n0, w.n, w.d, (const T*)x0, (const T*)x, dummy,
+                           theta, same, (const T*)sr, n0pad, w.npad, tw, slab);
+        hipLaunchKernelGGL((cross_kernel<T, 1>), gc, dim3(256), 0, st, M, n0pad, n0, n0, w.d, (const T*)x0, (const T*)x0, dummy,
+                           theta, 1, (const T*)nullptr, n0pad, n0pad, tw, cw.mat);
+    }
+    CHECK_LAUNCH("cross_kernel");
+    GemmArgs g;
+    g.A = X; g.B = (const T*)(w.base + w.off_W); g.C = U;
+    g.sA = slab; g.sB = w.mat; g.sC = slab; g.ldA = g.ldB = g.ldC = w.npad; g.p1 = g.p2 = g.p3 = 0;
+    g.nb = w.nb / 2; g.p0 = n0pad / (2 * TS);
+    int rc = launch_gemm<T, OP_PRED_U, 128>(st, g, g.p0 * g.nb, w.q);
+    if (rc) return rc;
+    GemmArgs h;
+    h.A = U; h.B = U; h.C = M;
+    h.sA = h.sB = slab; h.sC = cw.mat; h.ldA = h.ldB = w.npad; h.ldC = n0pad;
+    h.p1 = tw; h.p2 = w.d + 2; h.p3 = 0;
+    h.theta = theta;
+    // 64x64 tiles: the 128-tile instances of this op do not compile clean -- fp64 needs 12 registers more than the 128 a
+    // lane has at 4 waves per SIMD (a spill in the k loop; OP_PRED_U, the same loop, fits in 127), and in fp32 the compiler
+    // moves registers of the hand-counted prefetch before their wait (tools/check_counted_prefetch.py)
+    const int t64 = n0pad / TS;
+    h.nb = t64; h.p0 = w.npad / TS;
+    rc = launch_gemm<T, OP_PRED_COV, 64>(st, h, t64 * (t64 + 1) / 2, w.q);
+    if (rc) return rc;
+    hipLaunchKernelGGL((cov_diag_kernel<T>), dim3((n0pad + 255) / 256, w.q), dim3(256), 0, st, M, cw.mat, n0, n0pad, theta, tw,
+                       w.d, jitter);
+    CHECK_LAUNCH("cov_diag_kernel");
+    return 0;
+}
+
+// draws g_k = ghat_k + L_k eps_k for S draws per component, L_k the factor lcgp_potrf_logdet left in the cov workspace:
+// (L_k E_k)^T = E_k^T L_k^T is the product OP_PRED_U forms (X W^T with W lower triangular), X = E_k^T padded to whole tiles
+template <typename T>
+int do_sample(hipStream_t st, const Ws& cw, int S, const void* eps, const double* ghat, int ldg, void* scratch, double* out) {
+    const int n0pad = cw.npad, Spad = round_up(S, 2 * TS);
+    const size_t slab = (size_t)Spad * n0pad;
+    T* E = (T*)scratch;
+    T* G = E + slab * cw.q;
+    T* M = (T*)(cw.base + cw.off_M);
+    hipLaunchKernelGGL((diag_tile_upper_zero_kernel<T>), dim3(n0pad / (2 * TS), cw.q), dim3(256), 0, st, M, cw.mat, n0pad);
+    CHECK_LAUNCH("diag_tile_upper_zero_kernel");
+    hipLaunchKernelGGL((eps_pack_kernel<T>), dim3((n0pad + 255) / 256, Spad, cw.q), dim3(256), 0, st, (const T*)eps, S, cw.n, E,
+                       n0pad, slab);
+    CHECK_LAUNCH("eps_pack_kernel");
+    GemmArgs g;
+    g.A = E; g.B = M; g.C = G;
+    g.sA = slab; g.sB = cw.mat; g.sC = slab; g.ldA = g.ldB = g.ldC = n0pad; g.p1 = g.p2 = g.p3 = 0;
+    g.nb = n0pad / (2 * TS); g.p0 = Spad / (2 * TS);
+    int rc = launch_gemm<T, OP_PRED_U, 128>(st, g, g.p0 * g.nb, cw.q);
+    if (rc) return rc;
+    hipLaunchKernelGGL((draw_out_kernel<T>), dim3((cw.n + 255) / 256, S, cw.q), dim3(256), 0, st, (const T*)G, n0pad, slab, S,
+                       cw.n, ghat, ldg, out);
+    CHECK_LAUNCH("draw_out_kernel");
+    return 0;
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------------
@@ -3249,6 +3385,54 @@ int lcgp_predict(void* stream, int dtype, int kernel_id, int n, int d, int p, in
     hipStream_t st = (hipStream_t)stream;
     return dtype == LCGP_F64 ? do_predict<double>(st, w, x, sr, theta, n0, x0, same, scratch, ghat, gvar, ldo)
                              : do_predict<float>(st, w, x, sr, theta, n0, x0, same, scratch, ghat, gvar, ldo);
+}
+
+int lcgp_predict_cov_scratch_bytes(int dtype, int n, int q_local, int n0, size_t* bytes) {
+    if (dtype != LCGP_F64 && dtype != LCGP_F32) return bad("dtype must be 0 (f64) or 1 (f32)");
+    if (n < 1 || n0 < 1 || q_local < 1) return bad("n, n0, q_local must be >= 1");
+    if (!bytes) return bad("bytes is NULL");
+    *bytes = 2 * (size_t)q_local * cov_pad(n0) * round_up(n, 2 * TS) * (dtype == LCGP_F64 ? 8 : 4);
+    return 0;
+}
+
+int lcgp_sample_scratch_bytes(int dtype, int n0, int q_local, int S, size_t* bytes) {
+    if (dtype != LCGP_F64 && dtype != LCGP_F32) return bad("dtype must be 0 (f64) or 1 (f32)");
+    if (n0 < 1 || q_local < 1) return bad("n0, q_local must be >= 1");
+    if (S < 1 || S > LCGP_SAMPLE_MAX) return bad("S must be in [1, 32768]");
+    if (!bytes) return bad("bytes is NULL");
+    *bytes = 2 * (size_t)q_local * round_up(S, 2 * TS) * cov_pad(n0) * (dtype == LCGP_F64 ? 8 : 4);
+    return 0;
+}
+
+int lcgp_predict_cov(void* stream, int dtype, int kernel_id, int n, int d, int p, int q_local, const void* x, const void* sr,
+                     const double* theta, const void* workspace, int n0, const void* x0, int same, void* scratch,
+                     void* cov_workspace, double jitter) {
+    int rc = check_common(dtype, n, d, p, q_local, kernel_id);
+    if (rc) return rc;
+    if (n0 < 1) return bad("n0 < 1");
+    if (same < 0 || (same > 0 && same - 1 + n0 > n)) return bad("same must be 0 or 1 + the row offset of x0 within x");
+    if (!(jitter >= 0.0) || !__builtin_isfinite(jitter)) return bad("jitter must be finite and >= 0");
+    if (!x || !theta || !workspace || !x0 || !scratch || !cov_workspace) return bad("NULL pointer");
+    Ws w = carve(dtype, n, d, p, q_local, (void*)workspace);
+    w.kern = kernel_id;
+    Ws cw = carve(dtype, n0, d, p, q_local, cov_workspace);
+    hipStream_t st = (hipStream_t)stream;
+    return dtype == LCGP_F64 ? do_predict_cov<double>(st, w, x, sr, theta, n0, x0, same, scratch, cw, jitter)
+                             : do_predict_cov<float>(st, w, x, sr, theta, n0, x0, same, scratch, cw, jitter);
+}
+
+int lcgp_sample_latent(void* stream, int dtype, int n0, int d, int p, int q_local, int S, void* cov_workspace, const void* eps,
+                       const double* ghat, int ldg, void* scratch, double* out) {
+    int rc = check_common(dtype, n0, d, p, q_local);
+    if (rc) return rc;
+    if (S < 1 || S > LCGP_SAMPLE_MAX) return bad("S must be in [1, 32768]");
+    if (ldg != 0 && ldg < n0) return bad("ldg must be 0 (= n0) or >= n0");
+    if (!cov_workspace || !eps || !ghat || !scratch || !out) return bad("NULL pointer");
+    Ws cw = carve(dtype, n0, d, p, q_local, cov_workspace);
+    hipStream_t st = (hipStream_t)stream;
+    const int ld = ldg ? ldg : n0;
+    return dtype == LCGP_F64 ? do_sample<double>(st, cw, S, eps, ghat, ld, scratch, out)
+                             : do_sample<float>(st, cw, S, eps, ghat, ld, scratch, out);
 }
 
 }  // extern "C"

@@ -16,6 +16,8 @@ _DT = {"float64": _hip.F64, "f64": _hip.F64, "float32": _hip.F32, "f32": _hip.F3
 # rows of x0 handled per lcgp_predict call: bounds the scratch (2 * q_local * chunk * npad elements) however many
 # new inputs a caller passes (the reference has no limit on n0 either)
 PREDICT_CHUNK = 2048
+# draws per lcgp_sample_latent call (bounds its scratch, 2 * q_local * chunk * n0pad elements)
+SAMPLE_CHUNK = 4096
 
 
 class HotPathEngine:
@@ -79,6 +81,8 @@ class HotPathEngine:
             self.comp_dev = torch.as_tensor(np.asarray(comp_ids, np.int32)).to(self.device)
             self.partial_dev = torch.zeros(self.pw, dtype=torch.float64, device=self.device)
             self._scratch = None
+            self._cov_ws = None          # (n0, workspace) of the joint covariance (form_cov)
+            self._cov_plans = {}         # n0 -> launch plan of its factorisation
         self._theta_last = None
 
     # ------------------------------------------------------------------------------------------------
@@ -243,6 +247,132 @@ class HotPathEngine:
     def predict(self, x0s, same=False):
         ghat, gvar = self.predict_device(x0s, same)
         return ghat.cpu().numpy(), gvar.cpu().numpy()
+
+    # ------------------------------------------------------------------------------------------------
+    def _cov_workspace(self, n0):
+        """the second workspace, carved for n = n0, whose matrix slot receives Sigma_k + tau_k I (lcgp_predict_cov) and then
+        its factor (lcgp_potrf_logdet); cached per n0 like the predict scratch.  3 q_local n0pad^2 elements (n0pad = n0
+        rounded up to 128): at n0 = 4096, q_local = 8 in float64 that is 3.2 GB -- refused with ValueError beforehand when it
+        does not fit in the free device memory."""
+        torch = self.torch
+        if self._cov_ws is not None and self._cov_ws[0] == n0:
+            return self._cov_ws[1]
+        nbytes = C.c_size_t(0)
+        _hip.check(self.lib.lcgp_workspace_bytes(self.dtype, n0, self.d, self.p, self.q_local, C.byref(nbytes)),
+                   "lcgp_workspace_bytes")
+        self._cov_ws = None
+        self._require_memory(int(nbytes.value), "the joint covariance of %d new inputs" % n0)
+        ws = torch.empty(int(nbytes.value), dtype=torch.uint8, device=self.device)
+        self._cov_ws = (n0, ws)
+        return ws
+
+    def _require_memory(self, nbytes, what):
+        free, _ = self.torch.cuda.mem_get_info(self.device)
+        free += self.torch.cuda.memory_reserved(self.device) - self.torch.cuda.memory_allocated(self.device)
+        if nbytes > free:
+            raise ValueError("%s needs %.2f GB of device memory (%d components of n0 x n0, 3 matrices each), %.2f GB are "
+                             "free: pass fewer new inputs" % (what, nbytes / 1e9, self.q_local, free / 1e9))
+
+    def _grow_scratch(self, nbytes):
+        if self._scratch is None or self._scratch.numel() < nbytes:
+            self._scratch = None
+            self._require_memory(nbytes, "the scratch of the joint covariance")
+            self._scratch = self.torch.empty(int(nbytes), dtype=self.torch.uint8, device=self.device)
+        return self._scratch
+
+    def form_cov(self, x0s, same=False, jitter=0.0):
+        """Sigma_k + jitter scale_k I of the local components into the cov workspace for n0 = len(x0s) (lcgp_predict_cov);
+        returns the workspace (asynchronous)."""
+        torch = self.torch
+        if self._theta_last is None:
+            raise RuntimeError("predict_cov() needs a preceding evaluate() at the current parameters")
+        x0s = np.ascontiguousarray(x0s, np.float64)
+        n0 = x0s.shape[0]
+        assert x0s.ndim == 2 and x0s.shape[1] == self.d and n0 >= 1
+        with torch.cuda.device(self.device):
+            cws = self._cov_workspace(n0)
+            nbytes = C.c_size_t(0)
+            _hip.check(self.lib.lcgp_predict_cov_scratch_bytes(self.dtype, self.n, self.q_local, n0, C.byref(nbytes)),
+                       "lcgp_predict_cov_scratch_bytes")
+            scratch = self._grow_scratch(int(nbytes.value))
+            x0d = torch.as_tensor(x0s).to(self.device, self.tdtype).contiguous()
+            _hip.check(self.lib.lcgp_predict_cov(self._stream(), self.dtype, self.kernel_id, self.n, self.d, self.p, self.q_local,
+                                                 self._p(self.x), self._p(self.sr), self._p(self.theta_dev), self._p(self.workspace),
+                                                 n0, self._p(x0d), 1 if same else 0, self._p(scratch), self._p(cws), float(jitter)),
+                       "lcgp_predict_cov")
+            return cws
+
+    def fetch_cov(self, n0, which=0):
+        """(q_local, n0, n0) DEVICE tensor of the engine's dtype: matrix slot of the cov workspace, lower triangle mirrored"""
+        torch = self.torch
+        cws = self._cov_ws[1]
+        with torch.cuda.device(self.device):
+            out = torch.empty((self.q_local, n0, n0), dtype=self.tdtype, device=self.device)
+            for k in range(self.q_local):
+                _hip.check(self.lib.lcgp_fetch_matrix(self._stream(), self.dtype, n0, self.d, self.p, self.q_local, self._p(cws),
+                                                      int(which), k, self._p(out[k])), "lcgp_fetch_matrix")
+            return out
+
+    def predict_cov(self, x0s, same=False):
+        """(q_local, n0, n0) float64 DEVICE tensor Sigma_k = C00_k - D_k U_k U_k^T of the local components (before any jitter
+        or factorisation), from the factorisation of the last evaluate().  Memory: the cov workspace, 3 q_local n0pad^2
+        elements, and a scratch of 2 q_local n0pad npad elements."""
+        self.form_cov(x0s, same, 0.0)
+        return self.fetch_cov(len(x0s)).to(self.torch.float64)
+
+    def factor_cov(self, n0):
+        """factorises Sigma_k + tau_k I in the cov workspace in place (lcgp_potrf_logdet, plan with_inverse = 0); returns the
+        per-component info words on the host (0 = positive definite, else 1 + index of the first failing pivot)"""
+        torch = self.torch
+        if n0 not in self._cov_plans:
+            nbytes = C.c_size_t(0)
+            _hip.check(self.lib.lcgp_plan_bytes(self.dtype, n0, self.q_local, 0, None, C.byref(nbytes)), "lcgp_plan_bytes")
+            host = np.zeros(int(nbytes.value), dtype=np.uint8)
+            _hip.check(self.lib.lcgp_plan_build(self.dtype, n0, self.q_local, 0, None, C.c_void_p(host.ctypes.data), nbytes),
+                       "lcgp_plan_build")
+            self._cov_plans = {n0: host}
+        with torch.cuda.device(self.device):
+            info = torch.zeros(self.q_local, dtype=torch.int32, device=self.device)
+            _hip.check(self.lib.lcgp_potrf_logdet(self._stream(), self.dtype, n0, self.d, self.p, self.q_local,
+                                                  self._p(self._cov_ws[1]), None, self._p(info), None,
+                                                  C.c_void_p(self._cov_plans[n0].ctypes.data)), "lcgp_potrf_logdet")
+            return info.cpu().numpy()
+
+    def sample_latent(self, x0s, S, seeds, jitter=1e-10, same=False):
+        """(q_local, S, n0) float64 DEVICE tensor of draws g_k = ghat_k + L_k eps_k, L_k L_k^T = Sigma_k + jitter scale_k I.
+        eps_k (S x n0 standard normals) comes from numpy's default_rng(seeds[i]) for local component i, so a caller that
+        seeds by GLOBAL component gets draws independent of the sharding.  Raises numpy.linalg.LinAlgError naming the local
+        components whose Sigma_k + tau_k I is not numerically positive definite (the `info` words); never returns NaNs."""
+        torch = self.torch
+        x0s = np.ascontiguousarray(x0s, np.float64)
+        n0, S = x0s.shape[0], int(S)
+        assert len(seeds) == self.q_local and S >= 1
+        ghat = self.predict_block(x0s, same)[0]
+        self.form_cov(x0s, same, jitter)
+        info = self.factor_cov(n0)
+        if np.any(info != 0):
+            bad = [(i, int(v)) for i, v in enumerate(info) if v != 0]
+            err = np.linalg.LinAlgError("Sigma_k + jitter * scale_k I is not numerically positive definite for local components "
+                                        "(index, info) %s at jitter=%g" % (bad, jitter))
+            err.info = info
+            raise err
+        eps_all = np.stack([np.random.default_rng(s).standard_normal((S, n0)) for s in seeds])
+        with torch.cuda.device(self.device):
+            out = torch.empty((self.q_local, S, n0), dtype=torch.float64, device=self.device)
+            for lo in range(0, S, SAMPLE_CHUNK):
+                m = min(SAMPLE_CHUNK, S - lo)
+                nbytes = C.c_size_t(0)
+                _hip.check(self.lib.lcgp_sample_scratch_bytes(self.dtype, n0, self.q_local, m, C.byref(nbytes)),
+                           "lcgp_sample_scratch_bytes")
+                scratch = self._grow_scratch(int(nbytes.value))
+                eps = torch.as_tensor(np.ascontiguousarray(eps_all[:, lo:lo + m])).to(self.device, self.tdtype).contiguous()
+                dst = out if m == S else torch.empty((self.q_local, m, n0), dtype=torch.float64, device=self.device)
+                _hip.check(self.lib.lcgp_sample_latent(self._stream(), self.dtype, n0, self.d, self.p, self.q_local, m,
+                                                       self._p(self._cov_ws[1]), self._p(eps), self._p(ghat), n0,
+                                                       self._p(scratch), self._p(dst)), "lcgp_sample_latent")
+                if dst is not out:
+                    out[:, lo:lo + m].copy_(dst)
+            return out
 
     def fetch_vector(self, which, k):
         torch = self.torch

@@ -802,6 +802,141 @@ class LCGP:
             return _t(ypred), _t(ypredvar), _t(yconfvar), None
         return _t(ypred), _t(ypredvar), _t(yconfvar)
 
+    # =============================================================================================
+    # joint posterior covariance over new inputs and correlated draws (beyond the reference: its predict is marginal only)
+    # =============================================================================================
+    def _standardise_x0(self, x0):
+        """x0 on the raw scale -> standardised x0 and whether it IS the training set (the nugget of the cross covariance)"""
+        x0n = _np(self._verify_data_types(x0))
+        x0s = (x0n - _np(self.x_min)) / (_np(self.x_max) - _np(self.x_min))
+        xtrain = _np(self.x_unique_s if self.submethod == 'rep' else self.x)
+        same = (x0s.shape == xtrain.shape) and bool(np.all(x0s == xtrain))
+        return x0s, same
+
+    def _output_map(self):
+        """(W, noise, scale, offset) with which predict_full / predict_rep turn latent (ghat, gvar) into outputs:
+        mean_a = offset_a + scale_a sum_k W[k, a] g_k, noise variance scale_a^2 noise_a (same expressions as there)"""
+        ls2_b = _np(self.get_param()[2])
+        phi = _np(self.phi)
+        p = int(self.p)
+        if self.submethod == 'rep':
+            use_std = getattr(self, "rep_standardize_ybar", True)
+            std = _np(self.ybar_std)[:, 0] if use_std else np.ones(p, F64)
+            s_sqrt = np.sqrt(np.exp(ls2_b)) / std
+            W = (phi * s_sqrt[:, None]).T
+            noise = np.exp(ls2_b) / std ** 2
+            scale = _np(self.ybar_std)[:, 0] if use_std else np.ones(p, F64)
+            offset = _np(self.ybar_mean)[:, 0] if use_std else np.zeros(p, F64)
+        else:
+            W = phi.T * np.sqrt(np.exp(ls2_b))
+            noise = np.exp(ls2_b)
+            scale, offset = _np(self.ystd)[:, 0], _np(self.ymean)[:, 0]
+        return W, np.broadcast_to(noise, (p,)).astype(F64), scale, offset
+
+    def _agree(self, fn, jitter=None):
+        """runs this rank's share `fn()` and makes every rank raise together when any rank's share failed (a rank that raised
+        alone would leave the others waiting in the next collective): the q info words of the factorisations and a
+        ValueError flag are all-reduced first.  Returns fn()'s value."""
+        q = int(self.q)
+        status = np.zeros(q + 1, F64)
+        res, err = None, None
+        try:
+            res = fn()
+        except np.linalg.LinAlgError as e:
+            err = e
+            for i, v in enumerate(e.info):
+                status[self._local_ks[i]] = v
+        except ValueError as e:
+            err = e
+            status[q] = 1.0
+        if _dist.use_collectives(self._group):
+            status = _dist.all_reduce_sum(status, self._group, None if self._engine is None else self._engine.device)
+        if status[q] != 0:
+            raise err if err is not None else ValueError('another rank could not allocate the joint covariance')
+        bad = [k for k in range(q) if status[k] != 0]
+        if bad:
+            raise np.linalg.LinAlgError(
+                'the posterior covariance Sigma_k + jitter scale_k I of latent component(s) %s is not numerically positive '
+                'definite with jitter=%g (info %s): pass a larger jitter' % (bad, jitter, [int(status[k]) for k in bad]))
+        return res
+
+    def _gather_components(self, loc, shape):
+        """(q, *shape) numpy array from this rank's (q_local, *shape) device tensor: ONE reduction of a zero-padded block
+        (disjoint components: a sum is a gather), as _latent_predict does"""
+        if not _dist.use_collectives(self._group):
+            return loc.cpu().numpy()
+        full = self._zeros_on_device((int(self.q),) + tuple(shape))
+        if loc is not None:
+            idx = torch.as_tensor(self._local_ks, dtype=torch.long, device=full.device)
+            full.index_copy_(0, idx, loc.to(full.device))
+        return _dist.reduce_to_host(full, self._group)
+
+    def predict_latent_cov(self, x0):
+        """(q, n0, n0) posterior covariance of the latent components over the new inputs x0 (raw scale):
+            Sigma_k = C00_k - D_k (c0_k o sr) A_k^-1 (c0_k o sr)^T,   diag(Sigma_k) = gvar[k] of predict()
+        formed on the GPU from the factorisation of the current parameters (right after fit() no extra evaluation).
+        Memory: a second workspace of 3 q_local n0pad^2 elements per GPU (n0pad = n0 rounded up to 128; 3.2 GB at n0 = 4096,
+        8 local components, float64) -- ValueError when it does not fit.  float32 models compute in float32."""
+        x0s, same = self._standardise_x0(x0)
+        eng = self._ensure_aux()
+        loc = self._agree(lambda: None if eng is None else eng.predict_cov(x0s, same))
+        return _t(self._gather_components(loc, (x0s.shape[0], x0s.shape[0])))
+
+    def predict_jointcov(self, x0, outputs=None, include_noise=True):
+        """(len(outputs), n0, n0) posterior covariance of each selected output over the new inputs x0, on the raw output scale:
+            Cov(y_a(x0_i), y_a(x0_j)) = scale_a^2 (sum_k W[k, a]^2 Sigma_k[i, j] + [include_noise] noise_a delta_ij)
+        with W, noise, scale what predict() uses (psi / exp(lsigma2s) / ystd on the full path, Psi / s_var / ybar_std on
+        the rep path).  Its diagonal is predict()'s ypredvar (include_noise=True) or yconfvar (False).  outputs: indices
+        (default: all p).  Memory as predict_latent_cov."""
+        x0s, same = self._standardise_x0(x0)
+        n0 = x0s.shape[0]
+        outputs = list(range(int(self.p))) if outputs is None else [int(a) for a in np.atleast_1d(outputs)]
+        W, noise, scale, _ = self._output_map()
+        w2 = W[:, outputs] ** 2                                  # (q, P)
+        eng = self._ensure_aux()
+        sig = self._agree(lambda: None if eng is None else eng.predict_cov(x0s, same))
+        part = self._zeros_on_device((len(outputs), n0, n0))
+        if sig is not None:
+            wl = torch.as_tensor(w2[self._local_ks].T.copy(), device=sig.device)       # (P, q_local)
+            part = part.to(sig.device)
+            part += torch.tensordot(wl, sig, dims=1)
+            del sig
+        cov = _dist.reduce_to_host(part, self._group)           # one all-reduce: the sum over the ranks' components
+        if include_noise:
+            idx = np.arange(n0)
+            cov[:, idx, idx] += noise[outputs][:, None]
+        cov *= (scale[outputs] ** 2)[:, None, None]
+        return _t(cov)
+
+    def sample(self, x0, size=1, seed=None, include_noise=True, jitter=1e-10):
+        """(size, p, n0) draws of the outputs at the new inputs x0 (raw scale) from the joint posterior:
+            g_k = ghat_k + L_k eps_k,   L_k L_k^T = Sigma_k + jitter scale_k I,   y = offset + scale (W^T g + [include_noise] sqrt(noise) eta)
+        The normals of latent component k come from numpy's default_rng((seed, k)) with k the GLOBAL index, the observation
+        noise from default_rng((seed, q)): the draws do not depend on how the components are spread over ranks.  seed=None:
+        a fresh seed (rank 0's, on every rank).  A Sigma_k + tau I that is not numerically positive definite raises
+        numpy.linalg.LinAlgError naming the component and the jitter (never NaNs); a larger jitter helps, in float32 models
+        in particular (the factorisation runs in the dtype of the engine that holds the model's factorisation).
+        Memory as predict_latent_cov, plus 2 q_local min(size, 4096) n0pad elements of scratch."""
+        x0s, same = self._standardise_x0(x0)
+        n0, q, p, S = x0s.shape[0], int(self.q), int(self.p), int(size)
+        if S < 1:
+            raise ValueError('size must be >= 1')
+        if seed is None:
+            fresh = float(int(np.random.SeedSequence().generate_state(1, np.uint64)[0]) >> 12)     # exact in float64
+            seed = int(_dist.broadcast_array(np.array([fresh]), 0, self._group,
+                                             None if self._engine is None else self._engine.device)[0])
+        seed = int(seed)
+        W, noise, scale, offset = self._output_map()
+        eng = self._ensure_aux()
+        seeds = [(seed, k) for k in self._local_ks] if eng is not None else []
+        loc = self._agree(lambda: None if eng is None else eng.sample_latent(x0s, S, seeds, jitter, same), jitter)
+        g = self._gather_components(loc, (S, n0))
+        ys = np.einsum('ka,ksi->sai', W, g)
+        if include_noise:
+            eta = np.random.default_rng((seed, q)).standard_normal((S, p, n0))
+            ys += np.sqrt(noise)[None, :, None] * eta
+        return _t(ys * scale[None, :, None] + offset[None, :, None])
+
     # ---- cache views the reference keeps as attributes (materialised from the device only when read) ----
     def _fetch_all(self, fn, width):
         """(q, width) from per-component rows: every rank computes `fn` for the components IT holds (also any host-side

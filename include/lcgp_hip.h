@@ -228,6 +228,8 @@ int lcgp_predict(void* stream, int dtype, int kernel_id, int n, int d, int p, in
  * factors in place (its info word reports a Sigma_k + tau_k I that is not numerically positive definite).
  *   `same`: as in lcgp_predict (the nugget term of the cross covariance c0k; 0 = x0 is not the training set).
  *   scratch: lcgp_predict_cov_scratch_bytes(dtype, n, q_local, n0) bytes.
+ *   The content of `cov_workspace` and `scratch` on entry is irrelevant: the call writes every value it reads there
+ *   (tests/test_gpu_joint_bounds.py runs it on memory filled three ways and compares bitwise).
  * Flops per component: n0pad^2 npad (the lower tiles of U U^T, n0pad = n0 rounded up to 128) + n0pad npad^2 / 2 (U). */
 int lcgp_predict_cov_scratch_bytes(int dtype, int n, int q_local, int n0, size_t* bytes /*host out*/);
 int lcgp_predict_cov(void* stream, int dtype, int kernel_id, int n, int d, int p, int q_local,
@@ -239,6 +241,7 @@ int lcgp_predict_cov(void* stream, int dtype, int kernel_id, int n, int d, int p
  * eps: q_local x S x n0 standard normals (dtype, dense); ghat: q_local rows of n0 doubles, `ldg` apart (0 = n0), e.g. the
  * ghat of lcgp_predict; out: q_local x S x n0 doubles.  The call zeroes the unused strict upper triangle of the factor's
  * diagonal tiles (the product reads whole tiles).  scratch: lcgp_sample_scratch_bytes(dtype, n0, q_local, S) bytes.
+ * The content of `scratch` and `out` on entry is irrelevant; of `cov_workspace` only the factor in its matrix slot is read.
  * Flops per component: S n0pad^2 (S rounded up to 128). */
 #define LCGP_SAMPLE_MAX 32768
 int lcgp_sample_scratch_bytes(int dtype, int n0, int q_local, int S, size_t* bytes /*host out*/);

@@ -1,4 +1,5 @@
-"""Stage-wise componentwise error bounds of the hot path (build, Cholesky, L^-1, A^-1, z, outputs, predict).
+"""Stage-wise componentwise error bounds of the hot path (build, Cholesky, L^-1, A^-1, z, outputs, predict) and of the
+joint path (cross covariance X, U = X W^T, Sigma + tau I, its factor, the draws).
 
 Every check compares one stage of the library with a plain float64 reference computed from THE LIBRARY'S OWN INPUT TO THAT
 STAGE (the fetched A for the Cholesky, the fetched L for L^-1, ...), so no bound carries a condition number.  Entries are
@@ -224,6 +225,40 @@ def check_cholesky(A, L, dtype) -> Check:
     return worst(r, C * k * unit(dtype) * (la @ la.T) + floor(dtype, n))
 
 
+def check_cholesky_inverse_solve(A, L, dtype) -> Check:
+    """check_cholesky's residual bound plus the error of the library's panel solve, which is NOT a substitution: the
+    64-column panel tile is L_rc = A'_rc W_cc^T, a product with the explicit inverse W_cc of the diagonal block (chain_step,
+    DESIGN.md).  With the residual |W_cc L_cc - I| <= c TS u |W_cc| |L_cc| of the inverse, the tile's residual is
+        A'_rc - L_rc L_cc^T = A'_rc (I - W_cc L_cc)^T - E L_cc^T,   |E| <= TS u |A'_rc| |W_cc|^T,
+    and with |A'_rc| <= |L_rc| |L_cc|^T (to first order) both terms are within
+        C TS u |L_rc| (|L_cc|^T |W_cc|^T |L_cc|^T)        (entries of the strictly lower tiles (r, c), r > c)
+    on top of check_cholesky's bound, which still covers the trailing updates and the diagonal blocks.  The new term is of
+    the size of check_cholesky's when L_cc is well conditioned and grows with the componentwise condition of L_cc
+    otherwise: a substitution would not have it (check_cholesky then holds independently of kappa), this product does --
+    an ill-conditioned Sigma (a smooth prior over many new inputs, little data) exceeds check_cholesky's bound, this one
+    not.  W_cc is the float64 inverse of the fetched diagonal block."""
+    dev = _dev(A, L)
+    a = _t(A, dev)
+    l = torch.tril(_t(L, dev))
+    n = a.shape[0]
+    u = unit(dtype)
+    r = (a - l @ l.T).abs()
+    idx = torch.arange(n, device=dev, dtype=torch.float64)
+    k = torch.minimum(idx[:, None], idx[None, :]) + 2.0
+    la = l.abs()
+    bound = C * k * u * (la @ la.T) + floor(dtype, n)
+    extra = torch.zeros_like(bound)
+    for c in range(0, n, TS):
+        e = min(c + TS, n)
+        if e >= n:
+            break
+        lcc = l[c:e, c:e]
+        wcc = torch.linalg.solve_triangular(lcc, torch.eye(e - c, dtype=torch.float64, device=dev), upper=False)
+        m = lcc.abs().T @ wcc.abs().T @ lcc.abs().T
+        extra[e:, c:e] = C * TS * u * (la[e:, c:e] @ m)
+    return worst(r, bound + extra)
+
+
 def check_half_logdet(L, half_logdet, dtype) -> Check:
     """half_logdet (the library sums 1/2 log(pivot) in float64) against fsum(log L_ii) of the fetched factor:
     C u (n sum |log L_ii| + n).  The second term is the rounding of each stored L_ii = sqrt(pivot): an absolute error of
@@ -377,3 +412,98 @@ def check_predict(ghat, gvar, x0, x, sr, th, W, z, kernel, dtype) -> Check:
     Ua = Xa @ w.abs().T
     vb = wgt * abs(D) * (Ua * Ua).sum(dim=1) + u * abs(scale) + floor(dtype, n)
     return combine(worst((_t(ghat, dev) - gref).abs(), gb), worst((_t(gvar, dev) - vref).abs(), vb))
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# joint covariance over new inputs and correlated draws (lcgp_predict_cov, lcgp_potrf_logdet on the cov workspace,
+# lcgp_sample_latent).  The factor of the cov workspace goes through check_cholesky_inverse_solve(Sigma + tau I, L).
+# ----------------------------------------------------------------------------------------------------------------------
+def _pad128(n) -> int:
+    return -(-int(n) // (2 * TS)) * (2 * TS)
+
+
+def check_cov_cross(X, x0, x, sr, th, kernel, dtype, same=0) -> Check:
+    """X_k = scale ((1 - nt) C0(x0, x) + nt I[same]) o sr^T (n0 x n, the first slab of the lcgp_predict_cov scratch) against
+    its float64 definition from the rounded x0, x, sr.  `same` as in the C ABI: 0 = no nugget term, else x0 row i is x row
+    i + same - 1 and that entry carries scale nt sr.
+
+    cross_kernel forms x / ell, the exponent and the polynomial, scales by scale (1 - nt) and sr and stores once: relative
+    error (E + 4) u (E of kernel_parts: the evaluation; then the factors scale (1 - nt), sr and the store), entry by entry
+    (C = 4 on top).  A nugget entry adds scale nt sr_j, two roundings more: C u scale nt sr_j.  Past the C0 cut-off the
+    library may return any value in [0, C0]: the bound there is |X_ij| itself."""
+    dev = _dev(X)
+    d = np.asarray(x).shape[1]
+    u = unit(dtype)
+    ell, scale, nug, D, _ = split_theta(th, d)
+    nt = nug / (1.0 + nug)
+    c0, e, cut = kernel_parts(rounded(x0, dtype), rounded(x, dtype), ell, kernel, dtype, dev)
+    n0, n = c0.shape
+    s = _t(rounded(np.ones(n) if sr is None else sr, dtype), dev)
+    off = (scale * (1.0 - nt) * c0 * s[None, :]).abs()
+    dl = torch.zeros_like(c0)
+    if same:
+        i = torch.arange(n0, device=dev)
+        dl[i, i + same - 1] = 1.0
+    ref = scale * ((1.0 - nt) * c0 + nt * dl) * s[None, :]
+    bound = C * (e + 4.0) * u * off + C * u * abs(scale * nt) * dl * s[None, :].abs() + floor(dtype, d)
+    bound = bound + torch.where(cut, off, torch.zeros_like(off))
+    return worst((_t(X, dev) - ref).abs(), bound, lower=False)
+
+
+def check_cov_u(U, X, W, dtype) -> Check:
+    """U_k = X_k W_k^T (n0 x n, the second slab of the scratch) against the float64 product of the library's own X and
+    W = L^-1 (lower triangle of the fetched matrix): an inner product of K = npad terms (n rounded up to 128: the padding
+    adds stored zeros), C (npad + 2) u (|X| |W|^T)_ij."""
+    dev = _dev(U, X, W)
+    xx = _t(X, dev)
+    w = torch.tril(_t(W, dev))
+    k = _pad128(w.shape[0])
+    ref = xx @ w.T
+    bound = C * (k + 2.0) * unit(dtype) * (xx.abs() @ w.abs().T) + floor(dtype, k)
+    return worst((_t(U, dev) - ref).abs(), bound, lower=False)
+
+
+def check_sigma(S, U, x0, th, jitter, kernel, dtype) -> Check:
+    """Sigma_k + tau_k I (the matrix slot of the cov workspace after lcgp_predict_cov, lower triangle) against
+    C00 - D U U^T + tau I in float64, built from the library's own U (n0 x n) and the rounded x0; tau = jitter scale.
+
+    C00 = scale ((1 - nt) C0(x0, x0) + nt I) is evaluated like X in check_cov_cross: (E + 4) u relative.  The tile
+    kernel accumulates C00_ij - D sum_k U_ik U_jk over K = npad terms in the storage type, alpha = -D_k applied to the
+    product: (npad + 2) u (|C00| + |D| |U| |U|^T).  cov_diag_kernel adds tau to the stored diagonal in float64 and stores
+    once: u |tau| plus a rounding of the sum, which the previous term covers (|Sigma| <= |C00| + |D| |U| |U|^T).  Together,
+    with C = 4:  C (npad + d + E) u (|C00| + |D| |U| |U|^T) + u |tau|, and |C00| itself past the C0 cut-off.  The bound
+    starts from the library's U, so no condition number enters."""
+    dev = _dev(S, U)
+    d = np.asarray(x0).shape[1]
+    u = unit(dtype)
+    ell, scale, nug, D, _ = split_theta(th, d)
+    nt = nug / (1.0 + nug)
+    xr = rounded(x0, dtype)
+    c0, e, cut = kernel_parts(xr, xr, ell, kernel, dtype, dev)
+    n0 = c0.shape[0]
+    uu = _t(U, dev)
+    k = _pad128(uu.shape[1])
+    eye = torch.eye(n0, dtype=torch.float64, device=dev)
+    tau = jitter * scale
+    c00 = scale * ((1.0 - nt) * c0 + nt * eye)
+    ref = c00 - D * (uu @ uu.T) + tau * eye
+    ua = uu.abs()
+    bound = C * (k + d + e) * u * (c00.abs() + abs(D) * (ua @ ua.T)) + u * abs(tau) * eye + floor(dtype, k)
+    bound = bound + torch.where(cut, c00.abs(), torch.zeros_like(c00))
+    return worst((_t(S, dev) - ref).abs(), bound)
+
+
+def check_draws(out, L, eps, ghat, dtype) -> Check:
+    """draws out[s, i] = ghat_i + (L eps_s)_i (S x n0, float64, one component) against the float64 product of the library's
+    factor (lower triangle of the fetched matrix), eps rounded to the storage type (the library uploads it so) and the
+    library's ghat.  L eps_s is an inner product of at most n0 terms in the storage type, stored once: C (n0 + 1) u
+    (|eps| |L|^T); the final add to ghat is float64: C u64 (|ghat| + |L eps|).  Locations are (draw block, input block)."""
+    dev = _dev(out, L, ghat)
+    l = torch.tril(_t(L, dev))
+    n0 = l.shape[0]
+    ep = _t(rounded(eps, dtype), dev)
+    g = _t(ghat, dev)
+    le = ep @ l.T
+    ref = g[None, :] + le
+    bound = C * (n0 + 1.0) * unit(dtype) * (ep.abs() @ l.abs().T) + C * unit("float64") * (g.abs()[None, :] + le.abs())
+    return worst((_t(out, dev) - ref).abs(), bound + floor(dtype, n0), lower=False)

@@ -97,7 +97,7 @@ typedef struct lcgp_sched {
                                launch of lcgp_lauum after the factorisation (0 = always that) */
     int pair_tiles;         /* two consecutive panels share ONE trailing update with K = 2 panels on the columns between the
                                second panel and the far columns when that region holds at least this many 64x64 tiles (the
-                               first panel then only updates the second panel's own columns); 0 = never */
+                               first panel then only updates the second panel's own columns) (4000; 0 = never) */
 } lcgp_sched;
 int lcgp_sched_default(lcgp_sched* sched /*host out*/);
 

@@ -11,7 +11,7 @@ import subprocess
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_HERE)
-# (LCGP_HIP_LIB: tools only -- e.g. the stamped build of `make trace`; tests and the package use the in-tree library)
+# (LCGP_HIP_LIB: tools only -- the variant builds of tools/ab_builds.sh / trace_variants.sh; tests and the package use the in-tree library)
 LIB_PATH = os.environ.get("LCGP_HIP_LIB") or os.path.join(_HERE, "liblcgp_hip.so")
 SRC_PATH = os.path.join(_HERE, "csrc", "lcgp_hip.hip")
 HDR_PATH = os.path.join(_ROOT, "include", "lcgp_hip.h")

@@ -713,12 +713,6 @@ __global__ __launch_bounds__(256, 2) void leaf_kernel(T* __restrict__ M, T* __re
 //   MK : element (m, k) at P[m * ld + k]      KM : element (m, k) at P[k * ld + m]
 // and staged in LDS as [k][m] (KT = 16 k rows per stage, double buffered through registers).
 // ---------------------------------------------------------------------------------------------------
-#ifndef LCGP_PAIR_TILES_DEFAULT
-#define LCGP_PAIR_TILES_DEFAULT 4000
-#endif
-#ifndef LCGP_EXP
-#define LCGP_EXP 0      // destructive timing experiments (tools/build_variant.sh ... -DLCGP_EXP=n); 0 in every product build
-#endif
 enum GemmOp { OP_SYRK = 1, OP_TRTRI_T = 2, OP_TRTRI_W = 3, OP_LAUUM = 4, OP_PRED_U = 5, OP_PRED_COV = 6 };
 enum Lay { MK = 0, KM = 1 };
 
@@ -997,43 +991,35 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& g, const int lin /*blo
     bool tri_b = false;         // OP_LAUUM: the B operand of the last k tile is triangular too (diagonal tile)
     if constexpr (OP == OP_SYRK) {
         // M[r, c] -= sum_{kt in [p0, p1)} M[r, kt] M[c, kt]^T over the tiles c in [p2, p3), r in [c, nb)
-        // (p3 == nb: the whole trailing triangle; p3 < nb: the rest of the current panel), column-major
-#ifndef LCGP_SYRK_BAND
-#define LCGP_SYRK_BAND 8
-#endif
-        int t = bid + g.t0, c = g.p2, r;
-        if constexpr (LCGP_SYRK_BAND == 0) {
-            while (t >= g.nb - c) { t -= g.nb - c; ++c; }
-            r = c + t;
-        } else {
-            // Band-major: the rows p2 + i in bands of SB; inside a band column by column.  The workgroups resident on an XCD at
-            // one time (with eight components the component IS the XCD) then cover SB row tiles x a dozen column tiles instead
-            // of ~100 row tiles of one column: their operand panels (SB + a dozen of them) stay in the XCD's 4 MB L2, where the
-            // column-major order re-fetched a row panel per tile (profiles/r06_hbm_traffic_per_kernel.txt: 7.2 GB per
-            // evaluation through the fabric for 1.07 GB of matrix).  Same tiles, same arithmetic per tile.
-            constexpr int SB = LCGP_SYRK_BAND;
-            int i0 = 0;                                   // first row of the band, relative to p2
-            for (;;) {
-                // tiles of the band [i0, i0 + SB): row p2 + i holds the columns p2 .. min(p2 + i, p3 - 1)
-                const int rows = g.nb - g.p2 - i0 < SB ? g.nb - g.p2 - i0 : SB;
-                int cnt = 0;
-                for (int i = i0; i < i0 + rows; ++i) cnt += (i < g.p3 - g.p2 ? i : g.p3 - g.p2 - 1) + 1;
-                if (t < cnt) break;
-                t -= cnt;
-                i0 += SB;
-            }
+        // (p3 == nb: the whole trailing triangle; p3 < nb: the rest of the current panel)
+        // Band-major: the rows p2 + i in bands of SB; inside a band column by column.  The workgroups resident on an XCD at
+        // one time (with eight components the component IS the XCD) then cover SB row tiles x a dozen column tiles instead
+        // of ~100 row tiles of one column: their operand panels (SB + a dozen of them) stay in the XCD's 4 MB L2, where a
+        // column-major order re-fetched a row panel per tile (profiles/r06_hbm_traffic_per_kernel.txt: 7.2 GB per
+        // evaluation through the fabric for 1.07 GB of matrix).  Same tiles, same arithmetic per tile.
+        constexpr int SB = 8;
+        int t = bid + g.t0, r;
+        int i0 = 0;                                   // first row of the band, relative to p2
+        for (;;) {
+            // tiles of the band [i0, i0 + SB): row p2 + i holds the columns p2 .. min(p2 + i, p3 - 1)
             const int rows = g.nb - g.p2 - i0 < SB ? g.nb - g.p2 - i0 : SB;
-            // column j (relative) of the band holds the rows max(j, i0) .. i0 + rows - 1
-            int j = 0;
-            for (;;) {
-                const int lo = j > i0 ? j : i0;
-                const int cnt = i0 + rows - lo;
-                if (t < cnt) { r = g.p2 + lo + t; break; }
-                t -= cnt;
-                ++j;
-            }
-            c = g.p2 + j;
+            int cnt = 0;
+            for (int i = i0; i < i0 + rows; ++i) cnt += (i < g.p3 - g.p2 ? i : g.p3 - g.p2 - 1) + 1;
+            if (t < cnt) break;
+            t -= cnt;
+            i0 += SB;
         }
+        const int rows = g.nb - g.p2 - i0 < SB ? g.nb - g.p2 - i0 : SB;
+        // column j (relative) of the band holds the rows max(j, i0) .. i0 + rows - 1
+        int j = 0;
+        for (;;) {
+            const int lo = j > i0 ? j : i0;
+            const int cnt = i0 + rows - lo;
+            if (t < cnt) { r = g.p2 + lo + t; break; }
+            t -= cnt;
+            ++j;
+        }
+        const int c = g.p2 + j;
         A0 = Ab + (size_t)r * TM * g.ldA + (size_t)g.p0 * TM; dA = TM;
         B0 = Bb + (size_t)c * TM * g.ldB + (size_t)g.p0 * TM; dB = TM;
         nkt = g.p1 - g.p0;
@@ -1116,7 +1102,7 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& g, const int lin /*blo
         for (int j = 0; j < MIN; ++j)
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                if constexpr (PRELOAD_C && !(LCGP_EXP & 16)) {
+                if constexpr (PRELOAD_C) {
                     acc[i][j][e] = BufIo<T>::load(crs, cvoff + j * 16 * (unsigned)sizeof(T), c_soff(i, e));
                 } else {
                     acc[i][j][e] = 0;
@@ -1150,11 +1136,7 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& g, const int lin /*blo
     else if constexpr (OP == OP_TRTRI_W) dead_lo = tri_first + (wm0 + WTM) / KT;
     else if constexpr (OP == OP_PRED_U) dead_lo = tri_first + (wn0 + WTN) / KT;
     auto wave_live = [&](int sg) { return !HAS_TRI || sg < dead_lo || sg >= dead_hi; };
-#ifndef LCGP_NO_ROW_IMAGE
     constexpr bool ROWS_A = LA == MK && sizeof(T) == 8, ROWS_B = LB == MK && sizeof(T) == 8;     // (store_stage_rows)
-#else
-    constexpr bool ROWS_A = false, ROWS_B = false;
-#endif
     static_assert(TM * LDK <= KT * LD, "the row image fits the stage buffer");
     auto put_a = [&](T* S, const T (&reg)[EPT]) {
         if constexpr (ROWS_A) store_stage_rows<TM, NT>((double*)S, (const double (&)[EPT])reg, tid);
@@ -1218,21 +1200,9 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& g, const int lin /*blo
         // the k-contiguous operands to their row image (one fragment address instead of four): 119 registers at one stage,
         // 128 without a spill at two (profiles/r06_syrk_ab.txt: -0.09 ms per evaluation).  The hand-counted form of the loop
         // is not used for it: beside the 64 loads of the C tile the compiler spills accumulators around the loop.
-        constexpr bool F64 = sizeof(T) == 8;
-#ifndef LCGP_SYRK_PF
-#define LCGP_SYRK_PF 2
-#endif
-        constexpr int PF = OP == OP_SYRK ? (F64 ? LCGP_SYRK_PF : 2) : (TM == 64 ? (F64 ? 2 : 4) : 2);
+        constexpr int PF = OP != OP_SYRK && TM == 64 && sizeof(T) == 4 ? 4 : 2;     // fp32 64-tile products: a whole k tile
         constexpr int NPC = EPT * (int)sizeof(T) / 16;      // 16-byte pieces per lane, operand and stage
-#ifndef LCGP_NO_COUNTED_PREFETCH
-#ifdef LCGP_SYRK_COUNTED
-        constexpr bool COUNTED = PF == 2 && (NPC == 1 || NPC == 2) && (!PRELOAD_C || F64);
-#else
         constexpr bool COUNTED = PF == 2 && (NPC == 1 || NPC == 2 || NPC == 4) && !PRELOAD_C;
-#endif
-#else
-        constexpr bool COUNTED = false;
-#endif
         if constexpr (COUNTED) {
             // the hand-counted form of the loop below (see gload_piece): same stage images, same order of arithmetic
             typedef typename Piece<T>::v pc_t;
@@ -1265,20 +1235,13 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& g, const int lin /*blo
 #pragma unroll
                 for (int h = 0; h < PF; ++h) {
                     const int buf = (PF & 1) ? ((s + h) & 1) : (h & 1);
-                    // (LCGP_EXP: destructive timing experiments, never in a product build -- 1: no operand loads, 2: no LDS
-                    // stores / barrier, 8: no MFMA stage; results are garbage)
-                    if constexpr (!(LCGP_EXP & 1)) vm_wait_set<(PF - 1) * NL>(qa[h], qb[h]);
-                    if constexpr (!(LCGP_EXP & 2)) {
-                        put_ap(As + buf * KT * LD, qa[h]);
-                        put_bp(Bs + buf * KT * LD, qb[h]);
-                        __syncthreads();
-                    }
+                    vm_wait_set<(PF - 1) * NL>(qa[h], qb[h]);
+                    put_ap(As + buf * KT * LD, qa[h]);
+                    put_bp(Bs + buf * KT * LD, qb[h]);
+                    __syncthreads();
                     const int kt = (s + h + PF) / SPT, ks = ((s + h + PF) % SPT) * KT;
-                    if constexpr (!(LCGP_EXP & 1)) {
-                        load_stage_p<T, LA, TM, NT>(A0 + (ptrdiff_t)kt * dA, g.ldA, ks, qa[h], voffA);
-                        load_stage_p<T, LB, TM, NT>(B0 + (ptrdiff_t)kt * dB, g.ldB, ks, qb[h], voffB);
-                    }
-                    if constexpr (!(LCGP_EXP & 8))
+                    load_stage_p<T, LA, TM, NT>(A0 + (ptrdiff_t)kt * dA, g.ldA, ks, qa[h], voffA);
+                    load_stage_p<T, LB, TM, NT>(B0 + (ptrdiff_t)kt * dB, g.ldB, ks, qb[h], voffB);
                     if (wave_live(s + h)) compute_stage(buf);
                 }
             }
@@ -1294,35 +1257,33 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& g, const int lin /*blo
             }
             // (nothing the asm loaded is outstanding here: the last stored set was waited for with vmcnt(0))
         } else {
-        T ra[PF][EPT], rb[PF][EPT];
-        const unsigned uoffA = stage_lane_offset<T, LA, TM, NT>(g.ldA, tid), uoffB = stage_lane_offset<T, LB, TM, NT>(g.ldB, tid);
+            T ra[PF][EPT], rb[PF][EPT];
+            const unsigned uoffA = stage_lane_offset<T, LA, TM, NT>(g.ldA, tid), uoffB = stage_lane_offset<T, LB, TM, NT>(g.ldB, tid);
 #pragma unroll
-        for (int h = 0; h < PF; ++h) {
-            if (h < nst) {
-                const int kt = h / SPT, ks = (h % SPT) * KT;
-                load_stage_u<T, LA, TM, NT>(A0 + (ptrdiff_t)kt * dA, g.ldA, ks, ra[h], uoffA);
-                load_stage_u<T, LB, TM, NT>(B0 + (ptrdiff_t)kt * dB, g.ldB, ks, rb[h], uoffB);
-            }
-        }
-        for (int s = 0; s < nst; s += PF) {
-#pragma unroll
-            for (int h = 0; h < PF; ++h) {       // static register index h; LDS buffer (s + h) & 1
-                if (s + h < nst) {
-                    const int buf = (PF & 1) ? ((s + h) & 1) : (h & 1);
-                    if constexpr (!(LCGP_EXP & 128)) {
-                    put_a(As + buf * KT * LD, ra[h]);
-                    put_b(Bs + buf * KT * LD, rb[h]);
-                    __syncthreads();
-                    }
-                    if (!(LCGP_EXP & 64) && s + h + PF < nst) {
-                        const int kt = (s + h + PF) / SPT, ks = ((s + h + PF) % SPT) * KT;
-                        load_stage_u<T, LA, TM, NT>(A0 + (ptrdiff_t)kt * dA, g.ldA, ks, ra[h], uoffA);
-                        load_stage_u<T, LB, TM, NT>(B0 + (ptrdiff_t)kt * dB, g.ldB, ks, rb[h], uoffB);
-                    }
-                    if (wave_live(s + h)) compute_stage(buf);
+            for (int h = 0; h < PF; ++h) {
+                if (h < nst) {
+                    const int kt = h / SPT, ks = (h % SPT) * KT;
+                    load_stage_u<T, LA, TM, NT>(A0 + (ptrdiff_t)kt * dA, g.ldA, ks, ra[h], uoffA);
+                    load_stage_u<T, LB, TM, NT>(B0 + (ptrdiff_t)kt * dB, g.ldB, ks, rb[h], uoffB);
                 }
             }
-        }
+            for (int s = 0; s < nst; s += PF) {
+#pragma unroll
+                for (int h = 0; h < PF; ++h) {       // static register index h; LDS buffer (s + h) & 1
+                    if (s + h < nst) {
+                        const int buf = (PF & 1) ? ((s + h) & 1) : (h & 1);
+                        put_a(As + buf * KT * LD, ra[h]);
+                        put_b(Bs + buf * KT * LD, rb[h]);
+                        __syncthreads();
+                        if (s + h + PF < nst) {
+                            const int kt = (s + h + PF) / SPT, ks = ((s + h + PF) % SPT) * KT;
+                            load_stage_u<T, LA, TM, NT>(A0 + (ptrdiff_t)kt * dA, g.ldA, ks, ra[h], uoffA);
+                            load_stage_u<T, LB, TM, NT>(B0 + (ptrdiff_t)kt * dB, g.ldB, ks, rb[h], uoffB);
+                        }
+                        if (wave_live(s + h)) compute_stage(buf);
+                    }
+                }
+            }
         }
     }
     if constexpr (OP == OP_PRED_COV) alpha = -g.theta[(size_t)k * g.p1 + g.p2];
@@ -1338,7 +1299,6 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& g, const int lin /*blo
                         continue;
                 }
                 if constexpr (PRELOAD_C) {
-                    if constexpr (LCGP_EXP & 32) { if (acc[mi][ni][e] == (T)1.2345e-300) BufIo<T>::store((T)acc[mi][ni][e], crs, dvoff, dsoff); } else
                     BufIo<T>::store((T)acc[mi][ni][e], crs, dvoff, dsoff);
                 } else {
                     double v = alpha * (double)acc[mi][ni][e];
@@ -2544,7 +2504,7 @@ inline lcgp_sched default_sched() {
     s.progressive_lauum = 48;      // ... and A^-1 = W^T W accumulated behind the chain as well up to this many 64-blocks per side
                                    // (n = 2048: 1.12 -> 0.98 ms; at n = 4096 its tail is one ragged launch of long K loops
                                    // that loses to the one-launch W^T W: 2.54 vs 2.43 ms)
-    s.pair_tiles = LCGP_PAIR_TILES_DEFAULT;   // paired panels: one K = 2 ob update of the columns between the second panel and the far ones
+    s.pair_tiles = 4000;           // paired panels: one K = 2 ob update of the columns between the second panel and the far ones
     return s;
 }
 

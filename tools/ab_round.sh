@@ -1,6 +1,7 @@
 #!/bin/bash
 # One gpurun call: results of the builds build/libv_<name>.so compared bit for bit, then timed alternately on this box.
 #   usage: bash tools/ab_round.sh <tag> name1 name2 ...      (writes gpurun_out/<tag>_*.txt)
+set -eo pipefail
 TAG=$1; shift
 mkdir -p gpurun_out
 for v in "$@"; do

@@ -15,9 +15,10 @@
  *    lcgp_last_error): schedule parameters travel with the call (lcgp_sched), so calls on different
  *    streams / devices / host threads are independent;
  *  - the caller owns all memory, including `workspace` (size from lcgp_workspace_bytes);  the content of `workspace` and
- *    of the `scratch` of lcgp_predict on entry is irrelevant: every value a call reads there was written earlier in the same
- *    call or by the calls it documents as its input (lcgp_potrf_logdet -> lcgp_trtri -> lcgp_lauum, lcgp_nll_grad ->
- *    lcgp_predict); tests/test_gpu_stage_bounds.py checks bitwise-equal results on zero, NaN and 0x5A-filled memory;
+ *    of the `scratch` of lcgp_predict / lcgp_predict_grad on entry is irrelevant: every value a call reads there was
+ *    written earlier in the same call or by the calls it documents as its input (lcgp_potrf_logdet -> lcgp_trtri ->
+ *    lcgp_lauum, lcgp_nll_grad -> lcgp_predict); tests/test_gpu_stage_bounds.py checks bitwise-equal results on zero,
+ *    NaN and 0x5A-filled memory;
  *  - return value 0 = enqueued; < 0 = bad argument / HIP error (see lcgp_last_error()).
  *    A non positive-definite matrix is reported through the `info` word of the output block,
  *    not through the return value (the call is asynchronous).
@@ -217,6 +218,34 @@ int lcgp_predict(void* stream, int dtype, int kernel_id, int n, int d, int p, in
                  const void* x, const void* sr, const double* theta, const void* workspace,
                  int n0, const void* x0, int same, void* scratch,
                  double* ghat /*q_local rows of n0*/, double* gvar /*q_local rows of n0*/, int out_stride);
+
+/* Input gradients of the prediction (the reference gets them by a tf.GradientTape around predict, lcgp.py:808-930 with
+ * covmat.py:31-55; this entry point replaces that tape).  All derivatives are with respect to the STANDARDISED inputs x0s;
+ * output row i depends only on row i of x0, so the Jacobian is per point.  With X_k = c0k o sr^T, W_k = L_k^-1, U_k = X_k W_k^T,
+ * z_k = A_k^-1 b_k exactly as in lcgp_predict, for local component k, new input i and dimension l:
+ *     dghat[k, i, l] =        sum_j dc_l(i, j) sr_j z_k[j]
+ *     dgvar[k, i, l] = -2 D_k sum_j dc_l(i, j) sr_j V_k[i, j],      V_k = X_k A_k^-1 = U_k W_k
+ *     dc_l = -c0 dx_l / (ell_l^2 (1 + S_l))   (Matern-3/2; dx_l = x0_il - x_jl, S_l = |dx_l| / ell_l; 0 at dx_l = 0)
+ *     dc_l = -c0 dx_l / ell_l^2               (squared exponential)
+ *   c0 includes scale (1 - nug / (1 + nug)).  Nugget convention: the nugget term is a point mass the reference adds only when
+ *   x0 IS the training set; it has no derivative, so this is the gradient of the continuous prediction surface: same = 0
+ *   throughout, training inputs included.  ghat / gvar are written as well and are BITWISE those of
+ *   lcgp_predict(..., same = 0, ...) (the same launches).
+ * Input: the workspace of the last lcgp_nll_grad at the same theta, as for lcgp_predict.
+ * scratch: lcgp_predict_grad_scratch_bytes(dtype, n, q_local, n0) bytes (= lcgp_predict_scratch_bytes); its content on entry
+ *   is irrelevant.  V_k overwrites X_k in it once the row reductions have read X_k.
+ * Outputs: ghat / gvar q_local rows of n0, `out_stride` apart (0 = n0); dghat / dgvar q_local x n0 x d, row k at
+ *   k * out_stride * d (a caller that works in chunks passes the chunk's offset and the total as stride, as for lcgp_predict).
+ * Flops per component: n0pad npad^2 / 2 (U, as lcgp_predict) + n0pad npad^2 / 2 (V; n0pad = n0 rounded up to 128, or 64 below
+ * 128) + ~n0 n (12 d + 30) in the contraction, which never forms the n0 x n x d derivative tensor; the reduction order is fixed
+ * (no atomics): bitwise reproducible and independent of q_local. */
+int lcgp_predict_grad_scratch_bytes(int dtype, int n, int q_local, int n0, size_t* bytes /*host out*/);
+int lcgp_predict_grad(void* stream, int dtype, int kernel_id, int n, int d, int p, int q_local,
+                      const void* x, const void* sr, const double* theta, const void* workspace,
+                      int n0, const void* x0, void* scratch,
+                      double* ghat, double* gvar,        /* q_local rows of n0, `out_stride` apart */
+                      double* dghat, double* dgvar,      /* q_local x n0 x d, row k at k * out_stride * d */
+                      int out_stride);
 
 /* Joint posterior covariance over new inputs, and correlated draws (no counterpart in the reference: its predict is marginal
  * only).  For local component k and n0 new inputs x0 (standardised), with c0k, sr, L_k^-1 exactly as in lcgp_predict:

@@ -23,7 +23,7 @@
 #include "../../include/lcgp_hip.h"
 #include "fill_sched.h"
 
-#define LCGP_VERSION 520
+#define LCGP_VERSION 530
 
 namespace {
 
@@ -713,7 +713,7 @@ __global__ __launch_bounds__(256, 2) void leaf_kernel(T* __restrict__ M, T* __re
 //   MK : element (m, k) at P[m * ld + k]      KM : element (m, k) at P[k * ld + m]
 // and staged in LDS as [k][m] (KT = 16 k rows per stage, double buffered through registers).
 // ---------------------------------------------------------------------------------------------------
-enum GemmOp { OP_SYRK = 1, OP_TRTRI_T = 2, OP_TRTRI_W = 3, OP_LAUUM = 4, OP_PRED_U = 5, OP_PRED_COV = 6 };
+enum GemmOp { OP_SYRK = 1, OP_TRTRI_T = 2, OP_TRTRI_W = 3, OP_LAUUM = 4, OP_PRED_U = 5, OP_PRED_COV = 6, OP_PRED_V = 7 };
 enum Lay { MK = 0, KM = 1 };
 
 struct GemmArgs {
@@ -950,7 +950,7 @@ template <typename T, int OP, int TM, int NW>
 __device__ __forceinline__ void gemm_body(const GemmArgs& g, const int lin /*block index within this descriptor*/,
                                           unsigned char* lds) {
     constexpr int LA = (OP == OP_LAUUM) ? KM : MK;
-    constexpr int LB = (OP == OP_TRTRI_T || OP == OP_TRTRI_W || OP == OP_LAUUM) ? KM : MK;
+    constexpr int LB = (OP == OP_TRTRI_T || OP == OP_TRTRI_W || OP == OP_LAUUM || OP == OP_PRED_V) ? KM : MK;
     constexpr int NT = NW * 64;
     constexpr int LD = TM + 16;     // = 16 (mod 32): the two k rows a 32-lane group reads hit disjoint banks
     constexpr int WTM = TM / (NW / 2), WTN = TM / 2;   // per-wave sub-tile
@@ -1071,6 +1071,15 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& g, const int lin /*blo
         nkt = g.p0;
         Ct = Cb + (size_t)r * TM * g.ldC + (size_t)c * TM;
         accumulate = true;          // (alpha = -D_k is read behind the k loop: nothing more lives across it than in OP_PRED_U)
+    } else if constexpr (OP == OP_PRED_V) {
+        // V[m, c] = sum_{kt = c}^{nb-1} U[m, kt] W[kt, c]      (U = X W^T, n0pad x npad; W lower triangular)
+        // k tiles walked from nb-1 DOWN to c, as OP_LAUUM walks its B operand: every tile starts on the last block row of W,
+        // and the triangular diagonal tile W[c, c] comes last (its zero stages are skipped like OP_TRTRI_T's)
+        const int c = bid / g.p0, m = bid % g.p0;                  // p0 = row tiles of U; longest k loops (small c) first
+        A0 = Ab + (size_t)m * TM * g.ldA + (size_t)(g.nb - 1) * TM; dA = -(ptrdiff_t)TM;
+        B0 = Bb + (size_t)(g.nb - 1) * TM * g.ldB + (size_t)c * TM; dB = -(ptrdiff_t)TM * g.ldB;
+        nkt = g.nb - c;
+        Ct = Cb + (size_t)m * TM * g.ldC + (size_t)c * TM;
     } else {
         // OP_PRED_U: U[m, r] = sum_{kt = 0}^{r} X[m, kt] W[r, kt]^T    (X = scaled cross covariance, n0pad x npad)
         const int r = g.nb - 1 - bid / g.p0, m = bid % g.p0;       // p0 = row tiles of X; longest k loops (large r) first
@@ -1122,17 +1131,17 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& g, const int lin /*blo
         if (g.clk && lin == 0 && wave == 0) { clk0 = __builtin_amdgcn_s_memtime(); rt0 = __builtin_amdgcn_s_memrealtime(); }
     }
     // The LAST k tile of the triangular products holds a triangular TM x TM block of W (LAUUM: W[r,r] as A, and as B too
-    // on a diagonal tile; TRTRI_T: W11[cl,cl] as B; TRTRI_W: W22[rl,rl] as A; PRED_U: W[r,r] as B).  In the stage that
+    // on a diagonal tile; TRTRI_T: W11[cl,cl] as B; TRTRI_W: W22[rl,rl] as A; PRED_U: W[r,r] as B; PRED_V: W[c,c] as B).  In the stage that
     // covers its k rows [ks, ks + 16) a wave whose rows (columns) of that operand lie wholly on the zero side would
     // only add exact zeros: it skips the stage's fragment reads and MFMAs (one wave-uniform test per stage, nothing
     // else changes; bit-identical results: the zeros are stored zeros).  LAUUM / TRTRI_W: 24 of the 64 (wave, stage)
-    // pairs of such a tile, TRTRI_T / PRED_U: 16.
+    // pairs of such a tile, TRTRI_T / PRED_U / PRED_V: 16.
     constexpr bool HAS_TRI = OP != OP_SYRK && OP != OP_PRED_COV;
     const int tri_first = HAS_TRI ? (nkt - 1) * SPT : nst;
     // the wave is idle in the stages [dead_lo, dead_hi) of the k loop (two scalars per wave)
     int dead_lo = nst, dead_hi = nst;
     if constexpr (OP == OP_LAUUM) { dead_lo = tri_first; dead_hi = tri_first + (tri_b && wn0 > wm0 ? wn0 : wm0) / KT; }
-    else if constexpr (OP == OP_TRTRI_T) { dead_lo = tri_first; dead_hi = tri_first + wn0 / KT; }
+    else if constexpr (OP == OP_TRTRI_T || OP == OP_PRED_V) { dead_lo = tri_first; dead_hi = tri_first + wn0 / KT; }
     else if constexpr (OP == OP_TRTRI_W) dead_lo = tri_first + (wm0 + WTM) / KT;
     else if constexpr (OP == OP_PRED_U) dead_lo = tri_first + (wn0 + WTN) / KT;
     auto wave_live = [&](int sg) { return !HAS_TRI || sg < dead_lo || sg >= dead_hi; };
@@ -2432,6 +2441,118 @@ __global__ __launch_bounds__(64) void pred_reduce_kernel(const T* __restrict__ X
 }
 
 // ---------------------------------------------------------------------------------------------------
+// K7: input gradients of the prediction.  For local component k, new input i (standardised) and dimension l:
+//   dghat[k, i, l] =        sum_j dc_l(i, j) sr_j z_k[j]
+//   dgvar[k, i, l] = -2 D_k sum_j dc_l(i, j) sr_j V_k[i, j],      V_k = X_k A_k^-1 = U_k W_k   (OP_PRED_V)
+//   dc_l = -c0 s_l / (ell_l (1 + |s_l|))  (Matern-3/2),   -c0 s_l / ell_l  (SE),   s_l = (x0_il - x_jl) / ell_l
+// with c0 = scale (1 - nug / (1 + nug)) C0: the nugget term has no derivative (the gradient of the continuous surface).
+// The scaled distances and c0 are recomputed in registers as cross_kernel forms them; the n0 x n x d derivative tensor is
+// never written.  One workgroup per (32 rows of x0, component, chunk of DD dimensions): lane & 31 = row, the 8 half-waves
+// take every 8th training input of a stage of JT.  Accumulation in double (also for float32 inputs), per lane in ascending
+// j; the 8 slices are then summed in a fixed order -- no atomics: bitwise reproducible, independent of q_local.
+// DD < 32: d <= DD, the row of x0 held in registers.  DD = 32 serves every d in (16, 126]: c0 over all d from LDS, the
+// derivative for the 32 dimensions of chunk blockIdx.z (2 DD accumulators per lane, never 2 d).
+constexpr int PG_ROWS = 32, PG_SL = 8;
+template <typename T, int DD, int KERN>
+__global__ __launch_bounds__(256) void pgrad_kernel(const T* __restrict__ x0, int n0, const T* __restrict__ x,
+                                                    const T* __restrict__ sr, int n, int d, const double* __restrict__ theta,
+                                                    int tw, const T* __restrict__ z, int npad, const T* __restrict__ V,
+                                                    size_t slab, int ldo, double* __restrict__ dghat, double* __restrict__ dgvar) {
+    constexpr bool WIDE = DD == DMAX;
+    constexpr int JT = WIDE ? 16 : 32;                  // training inputs per LDS stage
+    constexpr int XW = WIDE ? DWIDE + 3 : DD + 1;       // odd row length: the per-row reads of x0sh hit distinct banks;
+                                                        // >= l0 + DD for every chunk (zeros beyond d)
+    __shared__ double x0sh[PG_ROWS][XW];
+    __shared__ double xsh[JT][XW];
+    __shared__ double vsh[PG_ROWS][JT + 1];
+    __shared__ double wz[JT], wsr[JT];
+    __shared__ double th[DWIDE + 3];
+    __shared__ double red[2][4][PG_ROWS];
+    const int k = blockIdx.y, i0 = blockIdx.x * PG_ROWS, l0 = WIDE ? blockIdx.z * DMAX : 0;
+    const int tid = threadIdx.x, r = tid & 31, sl = tid >> 5;
+    for (int e = tid; e < d + 3; e += 256) th[e] = theta[(size_t)k * tw + e];
+    __syncthreads();
+    const double scale = th[d], nug = th[d + 1], D = th[d + 2];
+    const double c_off = scale * (1.0 - nug / (1.0 + nug));
+    for (int e = tid; e < PG_ROWS * XW; e += 256) {
+        const int i = e / XW, m = e - i * XW;
+        x0sh[i][m] = (i0 + i < n0 && m < d) ? (double)x0[(size_t)(i0 + i) * d + m] / th[m] : 0.0;
+    }
+    const T* zk = z + (size_t)k * npad;
+    const T* Vk = V + (size_t)k * slab;
+    double am[DD], av[DD];
+#pragma unroll
+    for (int l = 0; l < DD; ++l) { am[l] = 0.0; av[l] = 0.0; }
+    double xi[WIDE ? 1 : DD];
+    __syncthreads();
+    if constexpr (!WIDE) {
+#pragma unroll
+        for (int m = 0; m < DD; ++m) xi[m] = x0sh[r][m];
+    }
+    for (int j0 = 0; j0 < n; j0 += JT) {
+        if (j0 > 0) __syncthreads();                    // every slice is done with the previous stage
+        for (int e = tid; e < JT * XW; e += 256) {
+            const int jj = e / XW, m = e - jj * XW;
+            xsh[jj][m] = (j0 + jj < n && m < d) ? (double)x[(size_t)(j0 + jj) * d + m] / th[m] : 0.0;
+        }
+        for (int e = tid; e < PG_ROWS * JT; e += 256) {
+            const int i = e / JT, jj = e - i * JT;
+            vsh[i][jj] = (i0 + i < n0 && j0 + jj < n) ? (double)Vk[(size_t)(i0 + i) * npad + j0 + jj] : 0.0;
+        }
+        if (tid < JT) {
+            const int j = j0 + tid;
+            const double s = j < n ? (sr ? (double)sr[j] : 1.0) : 0.0;      // (inputs beyond n weigh zero)
+            wsr[tid] = s;
+            wz[tid] = j < n ? s * (double)zk[j] : 0.0;
+        }
+        __syncthreads();
+        for (int jj = sl; jj < JT; jj += PG_SL) {
+            double poly = 1.0, ssum = 0.0;
+            auto acc_c0 = [&](double df) {
+                if constexpr (KERN == 0) {
+                    const double sd = fabs(df);
+                    poly *= 1.0 + sd;
+                    ssum -= sd;
+                } else {
+                    ssum = fma(-0.5 * df, df, ssum);
+                }
+            };
+            if constexpr (WIDE) {
+                for (int m = 0; m < d; ++m) acc_c0(x0sh[r][m] - xsh[jj][m]);
+            } else {
+#pragma unroll
+                for (int m = 0; m < DD; ++m) acc_c0(xi[m] - xsh[jj][m]);
+            }
+            const double c0 = c_off * (KERN == 0 ? fmin(poly, poly_cap<double>()) * exp_nonpos(ssum) : exp_nonpos(ssum));
+            const double a = c0 * wz[jj], b = c0 * wsr[jj] * vsh[r][jj];
+#pragma unroll
+            for (int l = 0; l < DD; ++l) {
+                const double s = WIDE ? x0sh[r][l0 + l] - xsh[jj][l0 + l] : xi[l] - xsh[jj][l];
+                const double h = KERN == 0 ? s * fast_rcp(1.0 + fabs(s)) : s;
+                am[l] = fma(a, h, am[l]);
+                av[l] = fma(b, h, av[l]);
+            }
+        }
+    }
+    // slices 2w and 2w + 1 share wave w (lanes r, r + 32), then the four waves through LDS: a fixed order
+    const int wave = tid >> 6, i = i0 + r;
+    const size_t orow = (size_t)k * ldo * d + (size_t)i * d;
+#pragma unroll
+    for (int l = 0; l < DD; ++l) {
+        const double sm = am[l] + __shfl_xor(am[l], 32), sv = av[l] + __shfl_xor(av[l], 32);
+        if ((tid & 63) < 32) { red[0][wave][r] = sm; red[1][wave][r] = sv; }
+        __syncthreads();
+        if (tid < PG_ROWS && i < n0 && l0 + l < d) {
+            const double tm = (red[0][0][r] + red[0][1][r]) + (red[0][2][r] + red[0][3][r]);
+            const double tv = (red[1][0][r] + red[1][1][r]) + (red[1][2][r] + red[1][3][r]);
+            dghat[orow + l0 + l] = -tm / th[l0 + l];
+            dgvar[orow + l0 + l] = 2.0 * D * tv / th[l0 + l];
+        }
+        __syncthreads();
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------
 // host-side drivers (enqueue only)
 // ---------------------------------------------------------------------------------------------------
 #define CHECK_LAUNCH(what)                                  \
@@ -2968,6 +3089,52 @@ int do_predict(hipStream_t st, const Ws& w, const void* x, const void* sr, const
     return 0;
 }
 
+template <typename T, int DD>
+void launch_pgrad(hipStream_t st, const Ws& w, dim3 grid, int n0, const void* x0, const void* x, const void* sr,
+                  const double* theta, const T* V, size_t slab, int ldo, double* dghat, double* dgvar) {
+    auto go = [&](auto kern) {
+        hipLaunchKernelGGL((pgrad_kernel<T, DD, decltype(kern)::value>), grid, dim3(256), 0, st, (const T*)x0, n0, (const T*)x,
+                           (const T*)sr, w.n, w.d, theta, w.d + 3 + w.p, (const T*)(w.base + w.off_z), w.npad, V, slab, ldo,
+                           dghat, dgvar);
+    };
+    if (w.kern == 0) go(std::integral_constant<int, 0>{}); else go(std::integral_constant<int, 1>{});
+}
+
+// K7 for all local components: do_predict with same = 0 (ghat / gvar bitwise those of lcgp_predict), then V_k = U_k W_k into
+// the X slab (free once the row reductions have read it; one launch of the tile kernel, k tiles from the diagonal of W
+// down), then the fused contraction (pgrad_kernel).  Scratch: that of lcgp_predict.
+template <typename T>
+int do_predict_grad(hipStream_t st, const Ws& w, const void* x, const void* sr, const double* theta, int n0, const void* x0,
+                    void* scratch, double* ghat, double* gvar, double* dghat, double* dgvar, int ldo) {
+    int rc = do_predict<T>(st, w, x, sr, theta, n0, x0, 0, scratch, ghat, gvar, ldo);
+    if (rc) return rc;
+    const int n0pad = predict_pad(n0);
+    const size_t slab = (size_t)n0pad * w.npad;
+    T* X = (T*)scratch;
+    T* U = X + slab * w.q;
+    GemmArgs g;
+    g.A = U; g.B = (const T*)(w.base + w.off_W); g.C = X;
+    g.sA = slab; g.sB = w.mat; g.sC = slab; g.ldA = g.ldB = g.ldC = w.npad; g.p1 = g.p2 = g.p3 = 0;
+    if (n0pad % (2 * TS) == 0) {
+        g.nb = w.nb / 2; g.p0 = n0pad / (2 * TS);
+        rc = launch_gemm<T, OP_PRED_V, 128>(st, g, g.p0 * g.nb, w.q);
+    } else {
+        g.nb = w.nb; g.p0 = n0pad / TS;
+        rc = launch_gemm<T, OP_PRED_V, 64>(st, g, g.p0 * g.nb, w.q);
+    }
+    if (rc) return rc;
+    const int wide = w.d > 16;
+    dim3 grid((n0 + PG_ROWS - 1) / PG_ROWS, w.q, wide ? (w.d + DMAX - 1) / DMAX : 1);
+    if (w.d <= 2) launch_pgrad<T, 2>(st, w, grid, n0, x0, x, sr, theta, X, slab, ldo, dghat, dgvar);
+    else if (w.d <= 4) launch_pgrad<T, 4>(st, w, grid, n0, x0, x, sr, theta, X, slab, ldo, dghat, dgvar);
+    else if (w.d <= 6) launch_pgrad<T, 6>(st, w, grid, n0, x0, x, sr, theta, X, slab, ldo, dghat, dgvar);
+    else if (w.d <= 10) launch_pgrad<T, 10>(st, w, grid, n0, x0, x, sr, theta, X, slab, ldo, dghat, dgvar);
+    else if (w.d <= 16) launch_pgrad<T, 16>(st, w, grid, n0, x0, x, sr, theta, X, slab, ldo, dghat, dgvar);
+    else launch_pgrad<T, DMAX>(st, w, grid, n0, x0, x, sr, theta, X, slab, ldo, dghat, dgvar);
+    CHECK_LAUNCH("pgrad_kernel");
+    return 0;
+}
+
 // ---------------------------------------------------------------------------------------------------
 // Joint posterior covariance over new inputs and correlated draws (no counterpart in the reference, whose predict is
 // marginal only).  The covariance lives in the matrix slot of a SECOND workspace carved for n = n0 (n0pad = round_up(n0,
@@ -3345,6 +3512,26 @@ int lcgp_predict(void* stream, int dtype, int kernel_id, int n, int d, int p, in
     hipStream_t st = (hipStream_t)stream;
     return dtype == LCGP_F64 ? do_predict<double>(st, w, x, sr, theta, n0, x0, same, scratch, ghat, gvar, ldo)
                              : do_predict<float>(st, w, x, sr, theta, n0, x0, same, scratch, ghat, gvar, ldo);
+}
+
+int lcgp_predict_grad_scratch_bytes(int dtype, int n, int q_local, int n0, size_t* bytes) {
+    return lcgp_predict_scratch_bytes(dtype, n, q_local, n0, bytes);
+}
+
+int lcgp_predict_grad(void* stream, int dtype, int kernel_id, int n, int d, int p, int q_local, const void* x, const void* sr,
+                      const double* theta, const void* workspace, int n0, const void* x0, void* scratch,
+                      double* ghat, double* gvar, double* dghat, double* dgvar, int out_stride) {
+    int rc = check_common(dtype, n, d, p, q_local, kernel_id);
+    if (rc) return rc;
+    if (n0 < 1) return bad("n0 < 1");
+    if (!x || !theta || !workspace || !x0 || !scratch || !ghat || !gvar || !dghat || !dgvar) return bad("NULL pointer");
+    if (out_stride != 0 && out_stride < n0) return bad("out_stride must be 0 (= n0) or >= n0");
+    const int ldo = out_stride ? out_stride : n0;
+    Ws w = carve(dtype, n, d, p, q_local, (void*)workspace);
+    w.kern = kernel_id;
+    hipStream_t st = (hipStream_t)stream;
+    return dtype == LCGP_F64 ? do_predict_grad<double>(st, w, x, sr, theta, n0, x0, scratch, ghat, gvar, dghat, dgvar, ldo)
+                             : do_predict_grad<float>(st, w, x, sr, theta, n0, x0, scratch, ghat, gvar, dghat, dgvar, ldo);
 }
 
 int lcgp_predict_cov_scratch_bytes(int dtype, int n, int q_local, int n0, size_t* bytes) {

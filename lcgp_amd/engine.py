@@ -239,6 +239,40 @@ class HotPathEngine:
                            "lcgp_predict")
             return out
 
+    def predict_grad_block(self, x0s):
+        """(block, jac) float64 DEVICE tensors for standardised x0s, from the factorisation of the last evaluate():
+        block (2, q_local, n0) = [ghat; gvar], bitwise predict_block(x0s, same=False); jac (2, q_local, n0, d) = [dghat; dgvar],
+        the derivatives with respect to x0s (lcgp_predict_grad: no nugget term, the gradient of the continuous surface).
+        Chunked like predict_block (PREDICT_CHUNK rows per call) and sharing its scratch."""
+        torch = self.torch
+        if self._theta_last is None:
+            raise RuntimeError("predict_grad() needs a preceding evaluate() at the current parameters")
+        x0s = np.ascontiguousarray(x0s, np.float64)
+        n0, d = x0s.shape[0], self.d
+        assert x0s.ndim == 2 and x0s.shape[1] == d and n0 >= 1
+        chunk = min(n0, PREDICT_CHUNK)
+        with torch.cuda.device(self.device):
+            x0d = torch.as_tensor(x0s).to(self.device, self.tdtype).contiguous()
+            nbytes = C.c_size_t(0)
+            _hip.check(self.lib.lcgp_predict_grad_scratch_bytes(self.dtype, self.n, self.q_local, chunk, C.byref(nbytes)),
+                       "lcgp_predict_grad_scratch_bytes")
+            if self._scratch is None or self._scratch.numel() < nbytes.value:
+                self._scratch = None
+                self._scratch = torch.empty(int(nbytes.value), dtype=torch.uint8, device=self.device)
+            out = torch.empty((2, self.q_local, n0), dtype=torch.float64, device=self.device)
+            jac = torch.empty((2, self.q_local, n0, d), dtype=torch.float64, device=self.device)
+            st, xp, srp, thp, wsp, scp = self._stream(), self._p(self.x), self._p(self.sr), self._p(self.theta_dev), \
+                self._p(self.workspace), self._p(self._scratch)
+            for lo in range(0, n0, chunk):
+                m = min(chunk, n0 - lo)
+                _hip.check(self.lib.lcgp_predict_grad(st, self.dtype, self.kernel_id, self.n, d, self.p, self.q_local, xp, srp, thp,
+                                                      wsp, m, C.c_void_p(x0d.data_ptr() + lo * d * x0d.element_size()), scp,
+                                                      C.c_void_p(out[0].data_ptr() + 8 * lo), C.c_void_p(out[1].data_ptr() + 8 * lo),
+                                                      C.c_void_p(jac[0].data_ptr() + 8 * lo * d),
+                                                      C.c_void_p(jac[1].data_ptr() + 8 * lo * d), n0),
+                           "lcgp_predict_grad")
+            return out, jac
+
     def predict_device(self, x0s, same=False):
         """ghat, gvar (q_local, n0): the two halves of predict_block()"""
         out = self.predict_block(x0s, same)

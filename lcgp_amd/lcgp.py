@@ -51,6 +51,34 @@ def _percentile50_nearest(a):
     return np.sort(a, axis=1)[:, idx:idx + 1]
 
 
+class _PredictFn(torch.autograd.Function):
+    """LCGP.predict_differentiable: forward = predict()'s outputs from one lcgp_predict_grad pass, backward = the per-point
+    vector-Jacobian product with the saved output Jacobians"""
+
+    @staticmethod
+    def forward(ctx, x0, model):
+        ghat, gvar, dghat, dgvar = model._latent_predict_grad(x0.detach().cpu().to(torch.float64))
+        outs = model._outputs_rep(ghat, gvar) if model.submethod == 'rep' else model._outputs_full(ghat, gvar)
+        dyp, dycv = model._output_jacobians(dghat, dgvar)
+        ctx.x0_dtype, ctx.x0_device, ctx.x0_shape = x0.dtype, x0.device, x0.shape
+        ctx.jac = (torch.as_tensor(dyp), torch.as_tensor(dycv))
+        return tuple(o.to(x0.device) for o in outs[:3])
+
+    @staticmethod
+    def backward(ctx, g_ypred, g_ypredvar, g_yconfvar):
+        if torch.is_grad_enabled():         # create_graph=True: the saved Jacobians are constants, not a graph
+            raise RuntimeError('LCGP.predict_differentiable supports first derivatives only: double backward '
+                               '(create_graph=True) is not available; use predict_grad() for the Jacobians')
+        dyp, dycv = ctx.jac
+        gx = torch.zeros(dyp.shape[1:], dtype=torch.float64)
+        if g_ypred is not None:
+            gx += torch.einsum('ai,ail->il', g_ypred.detach().cpu().to(torch.float64), dyp)
+        gv = [g.detach().cpu().to(torch.float64) for g in (g_ypredvar, g_yconfvar) if g is not None]
+        if gv:
+            gx += torch.einsum('ai,ail->il', sum(gv), dycv)
+        return gx.reshape(ctx.x0_shape).to(device=ctx.x0_device, dtype=ctx.x0_dtype), None
+
+
 class LCGP:
     """
     Latent Component Gaussian Process (LCGP), MI355X hot path.
@@ -762,6 +790,10 @@ class LCGP:
     def predict_full(self, x0, return_fullcov=False):
         """lcgp.py:808-859."""
         ghat, gvar = self._latent_predict(x0)
+        return self._outputs_full(ghat, gvar, return_fullcov)
+
+    def _outputs_full(self, ghat, gvar, return_fullcov=False):
+        """predict_full's map from latent (ghat, gvar) (q, n0) to (ypred, ypredvar, yconfvar[, cov])"""
         ls2_b = _np(self.get_param()[2])
         phi = _np(self.phi)
         ystd, ymean = _np(self.ystd), _np(self.ymean)
@@ -783,6 +815,10 @@ class LCGP:
     def predict_rep(self, x0, return_fullcov=False):
         """lcgp.py:864-930."""
         ghat, gvar = self._latent_predict(x0)
+        return self._outputs_rep(ghat, gvar, return_fullcov)
+
+    def _outputs_rep(self, ghat, gvar, return_fullcov=False):
+        """predict_rep's map from latent (ghat, gvar) (q, n0) to (ypred, ypredvar, yconfvar[, None])"""
         ls2_b = _np(self.get_param()[2])
         phi = _np(self.phi)
         use_std = getattr(self, "rep_standardize_ybar", True)
@@ -936,6 +972,58 @@ class LCGP:
             eta = np.random.default_rng((seed, q)).standard_normal((S, p, n0))
             ys += np.sqrt(noise)[None, :, None] * eta
         return _t(ys * scale[None, :, None] + offset[None, :, None])
+
+    # =============================================================================================
+    # input gradients of the prediction (the reference: a tf.GradientTape around predict)
+    # =============================================================================================
+    def _latent_predict_grad(self, x0):
+        """ghat, gvar (q, n0) and their Jacobians dghat, dgvar (q, n0, d) with respect to the STANDARDISED inputs, for raw-scale
+        x0: the local components on the device (lcgp_predict_grad), ONE reduction of the zero-padded block gathers them.
+        No nugget term (same = 0 even at training inputs): the gradient of the continuous prediction surface."""
+        x0s, _ = self._standardise_x0(x0)
+        n0, d = x0s.shape
+        eng = self._ensure_aux()
+        loc = None
+        if eng is not None:
+            blk, jac = eng.predict_grad_block(x0s)
+            loc = torch.cat([blk.permute(1, 0, 2).reshape(blk.shape[1], -1),
+                             jac.permute(1, 0, 2, 3).reshape(jac.shape[1], -1)], dim=1)
+        both = self._gather_components(loc, (2 * n0 + 2 * n0 * d,))
+        q = int(self.q)
+        ghat, gvar = both[:, :n0], both[:, n0:2 * n0]
+        jac = both[:, 2 * n0:].reshape(q, 2, n0, d)
+        self.ghat, self.gvar = _t(ghat), _t(gvar)
+        self.dghat, self.dgvar = _t(jac[:, 0]), _t(jac[:, 1])
+        return ghat, gvar, jac[:, 0], jac[:, 1]
+
+    def _output_jacobians(self, dghat, dgvar):
+        """latent Jacobians (q, n0, d) on the standardised scale -> (dypred, dyconfvar) (p, n0, d) on the raw input and output
+        scales, through _output_map():  dypred = scale_a sum_k W[k, a] dghat_k / range,  dyconfvar = scale_a^2 sum_k W[k, a]^2
+        dgvar_k / range  (range = x_max - x_min, x0s = (x0 - x_min) / range)"""
+        W, _, scale, _ = self._output_map()
+        rng = (_np(self.x_max) - _np(self.x_min)).reshape(-1)
+        dyp = np.einsum('ka,kil->ail', W, dghat) * scale[:, None, None] / rng[None, None, :]
+        dycv = np.einsum('ka,kil->ail', W ** 2, dgvar) * (scale ** 2)[:, None, None] / rng[None, None, :]
+        return dyp, dycv
+
+    def predict_grad(self, x0):
+        """Jacobians of predict()'s outputs with respect to the new inputs, per point (output row i depends only on x0[i]):
+            dypred[a, i, l] = d ypred[a, i] / d x0[i, l],   dypredvar, dyconfvar likewise      each (p, n0, d), CPU float64
+        on the raw input and output scales.  dypredvar = dyconfvar (the noise variance does not depend on x0).  Computed on
+        the GPU from the factorisation of the current parameters (lcgp_predict_grad; right after fit() no extra evaluation),
+        in the engine's dtype.  Nugget convention: the reference adds the nugget to the cross covariance only when x0 IS the
+        training set; that point mass has no derivative, so this is the gradient of the continuous prediction surface, also
+        at training inputs.  The latent Jacobians stay on the model as dghat / dgvar (q, n0, d), next to ghat / gvar."""
+        _, _, dghat, dgvar = self._latent_predict_grad(x0)
+        dyp, dycv = self._output_jacobians(dghat, dgvar)
+        return _t(dyp), _t(dycv.copy()), _t(dycv)
+
+    def predict_differentiable(self, x0):
+        """(ypred, ypredvar, yconfvar) (p, n0) as predict() returns them, float64 on x0's device, differentiable with respect to
+        a requires_grad x0 (any device) through torch.autograd: the backward pass is the vector-Jacobian product with the
+        Jacobians of predict_grad() saved by the forward pass (no second GPU pass).  The values equal predict(x0) whenever x0 is
+        not the training set (here the nugget term is never added: see predict_grad).  Double backward is not supported."""
+        return _PredictFn.apply(x0 if isinstance(x0, torch.Tensor) else torch.as_tensor(np.asarray(x0, F64)), self)
 
     # ---- cache views the reference keeps as attributes (materialised from the device only when read) ----
     def _fetch_all(self, fn, width):

@@ -277,6 +277,45 @@ int lcgp_sample_scratch_bytes(int dtype, int n0, int q_local, int S, size_t* byt
 int lcgp_sample_latent(void* stream, int dtype, int n0, int d, int p, int q_local, int S, void* cov_workspace,
                        const void* eps, const double* ghat, int ldg, void* scratch, double* out);
 
+/* Closed-form cross-validation at fixed parameters (no counterpart in the reference).  Input: the workspace of the last
+ * lcgp_nll_grad, whose V slot holds a = A_k^-1 (A_k = I + D_k (C_k o s s^T), s = sr, ones when sr is NULL) and whose vectors
+ * hold b_k and z_k = A_k^-1 b_k.  With K_k = C_k + (D_k S^2)^-1 (S = diag(s)), K_k^-1 = D_k S a S, so for a set B of m
+ * training inputs and M = a[B, B] (m x m) the model conditioned on the OTHER inputs -- same theta, D_k, psi_k, basis and
+ * standardisation, no nugget in the cross covariance (same = 0) -- predicts at x_B
+ *     ghat_B  = S_B^-1 (b_B - M^-1 z_B) / D_k
+ *     Sigma_B = S_B^-1 (M^-1 - I) S_B^-1 / D_k        (the prior variance scale_k, nugget included, on its diagonal)
+ * and leave-one-out (B = {i}) is
+ *     ghat_i = (b_i - z_i / a_ii) / (D_k s_i),   gvar_i = (1 / a_ii - 1) / (D_k s_i^2).
+ * These equal lcgp_predict of the conditioned model at x_B to rounding: no refit, no factorisation of size n.
+ *
+ * lcgp_loo: ghat / gvar for every training input, q_local rows of n doubles `out_stride` apart (0 = n).  Bitwise independent
+ * of q_local; accumulates in double.
+ *
+ * k-fold: the folds are given twice -- `folds_host` (host) and `folds` (device) hold the same F + 1 + n ints
+ *     [ fold_ptr_0 .. fold_ptr_F | fold_idx_0 .. fold_idx_{n-1} ],   fold f = fold_idx[fold_ptr_f .. fold_ptr_{f+1}),
+ * a partition of 0 .. n-1 into F non-empty folds, each sorted ascending.  The host copy is checked before anything is
+ * enqueued (an empty fold, an index out of range or repeated, fold_ptr not running from 0 to n, F * q_local > 65535 and
+ * NULL pointers are refused); the kernels read the device copy.  mmax = the largest fold.
+ *   1. lcgp_cv_gather writes M = a_k[B_f, B_f] into the matrix slot f * q_local + k of a SECOND workspace, `cv_workspace`,
+ *      of lcgp_cv_workspace_bytes bytes (= lcgp_workspace_bytes(dtype, mmax, d, p, q_local * F)): lower 64x64 tiles,
+ *      identity beyond m_f -- what lcgp_potrf_logdet(dtype, mmax, d, p, q_local * F, cv_workspace, ...) factors in place.
+ *   2. the caller factors and inverts with the existing entries: lcgp_potrf_logdet (a plan with with_inverse = 0; its info
+ *      word of slot f * q_local + k reports a fold matrix that is not numerically positive definite), then lcgp_potri.
+ *      M^-1 is then in the V slot (lcgp_fetch_matrix(..., which = 2, f * q_local + k) for Sigma_B).
+ *   3. lcgp_cv_apply forms t = M^-1 z_B and scatters ghat / gvar of every fold to the positions fold_idx of q_local rows of
+ *      n doubles, `out_stride` apart.  Fixed-order sums, no atomics: bitwise reproducible run to run (not across q_local:
+ *      the schedule of step 2 depends on the batch q_local * F).
+ * The content of `cv_workspace` on entry is irrelevant.  Memory: 3 q_local F mpad^2 elements (mpad = mmax rounded up to
+ * 128); flops per slot: mpad^3 / 3 (factor) + 2 mpad^3 / 3 (inverse) + 2 mmax^2 (apply). */
+int lcgp_loo(void* stream, int dtype, int n, int d, int p, int q_local, const void* sr, const double* theta,
+             const void* workspace, double* ghat, double* gvar, int out_stride);
+int lcgp_cv_workspace_bytes(int dtype, int n, int d, int p, int q_local, int F, const int* folds_host, size_t* bytes /*host out*/);
+int lcgp_cv_gather(void* stream, int dtype, int n, int d, int p, int q_local, const void* workspace, int F,
+                   const int* folds_host, const int* folds, void* cv_workspace);
+int lcgp_cv_apply(void* stream, int dtype, int n, int d, int p, int q_local, const void* sr, const double* theta,
+                  const void* workspace, int F, const int* folds_host, const int* folds, const void* cv_workspace,
+                  double* ghat, double* gvar, int out_stride);
+
 #ifdef __cplusplus
 }
 #endif

@@ -63,6 +63,10 @@ SIGNATURES = {
     "lcgp_predict_cov": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _d]),
     "lcgp_sample_scratch_bytes": (_i, [_i, _i, _i, _i, C.POINTER(C.c_size_t)]),
     "lcgp_sample_latent": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp]),
+    "lcgp_loo": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i]),
+    "lcgp_cv_workspace_bytes": (_i, [_i, _i, _i, _i, _i, _i, _vp, C.POINTER(C.c_size_t)]),
+    "lcgp_cv_gather": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp]),
+    "lcgp_cv_apply": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i]),
 }
 
 _lib = None

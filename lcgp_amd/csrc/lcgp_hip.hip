@@ -23,7 +23,7 @@
 #include "../../include/lcgp_hip.h"
 #include "fill_sched.h"
 
-#define LCGP_VERSION 530
+#define LCGP_VERSION 540
 
 namespace {
 
@@ -3260,6 +3260,176 @@ int do_sample(hipStream_t st, const Ws& cw, int S, const void* eps, const double
     return 0;
 }
 
+// ---------------------------------------------------------------------------------------------------
+// Closed-form cross-validation at fixed parameters (no counterpart in the reference).  With a = A_k^-1 (V slot), b_k, z_k
+// and s = sr of the last lcgp_nll_grad, the model conditioned on all inputs but a set B predicts at x_B
+//     ghat_B = S_B^-1 (b_B - M^-1 z_B) / D_k,   Sigma_B = S_B^-1 (M^-1 - I) S_B^-1 / D_k,   M = a[B, B]
+// (lcgp_hip.h).  Leave-one-out is the case |B| = 1.  The fold matrices M live in the matrix slots of a second workspace
+// carved for n = mmax (the largest fold) and q_local * F components, slot f * q_local + k; the unchanged lcgp_potrf_logdet
+// and lcgp_potri turn them into M^-1 in its V slot.  Folds: `folds` = [fold_ptr (F + 1) | fold_idx (n)] device ints.
+// ---------------------------------------------------------------------------------------------------
+
+// leave-one-out for every training input i and local component k: one thread per (i, k), double arithmetic
+template <typename T>
+__global__ __launch_bounds__(256) void loo_kernel(const T* __restrict__ V, size_t mat, int n, int npad, const T* __restrict__ b,
+                                                  const T* __restrict__ z, const T* __restrict__ sr,
+                                                  const double* __restrict__ theta, int tw, int d, int ldo,
+                                                  double* __restrict__ ghat, double* __restrict__ gvar) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x, k = blockIdx.y;
+    if (i >= n) return;
+    const double a = (double)V[(size_t)k * mat + (size_t)i * npad + i];
+    const double bi = (double)b[(size_t)k * npad + i], zi = (double)z[(size_t)k * npad + i];
+    const double s = sr ? (double)sr[i] : 1.0;
+    const double Dk = theta[(size_t)k * tw + d + 2];
+    const double ia = 1.0 / a;
+    ghat[(size_t)k * ldo + i] = (bi - zi * ia) / (Dk * s);
+    gvar[(size_t)k * ldo + i] = (ia - 1.0) / (Dk * s * s);
+}
+
+// slot s = f * q_local + k of the fold workspace <- a_k[B_f, B_f] in the form lcgp_kernel_build leaves for the factorisation:
+// one workgroup per lower 64x64 tile (written whole; the strict upper tiles are never read), identity beyond m_f (the fold's
+// own padding and that up to mpad).  a_k is read from its lower storage at (max, min).
+template <typename T>
+__global__ __launch_bounds__(256) void cv_gather_kernel(const T* __restrict__ V, size_t mat, int npad, const int* __restrict__ folds,
+                                                        int F, int q_local, T* __restrict__ M, size_t cmat, int mpad) {
+    const int s = blockIdx.y, f = s / q_local, k = s - f * q_local;
+    int r, c;
+    tri_decode(blockIdx.x, r, c);
+    const int lo = folds[f], m = folds[f + 1] - lo;
+    const int* __restrict__ idx = folds + F + 1 + lo;
+    __shared__ int ri[TS], ci[TS];
+    const int tid = threadIdx.x;
+    if (tid < TS) {
+        const int i = r * TS + tid;
+        ri[tid] = i < m ? idx[i] : -1;
+    } else if (tid < 2 * TS) {
+        const int j = c * TS + tid - TS;
+        ci[tid - TS] = j < m ? idx[j] : -1;
+    }
+    __syncthreads();
+    const T* __restrict__ A = V + (size_t)k * mat;
+    T* __restrict__ out = M + (size_t)s * cmat + (size_t)r * TS * mpad + (size_t)c * TS;
+    for (int e = tid; e < TS * TS; e += 256) {
+        const int ii = e / TS, jj = e - ii * TS;
+        const int gi = ri[ii], gj = ci[jj];
+        T v;
+        if (gi >= 0 && gj >= 0) v = A[(size_t)max(gi, gj) * npad + min(gi, gj)];
+        else v = (r == c && ii == jj) ? (T)1 : (T)0;
+        out[(size_t)ii * mpad + jj] = v;
+    }
+}
+
+// slot s = f * q_local + k: t = M^-1 z_B from the lower storage of M^-1 (V slot of the fold workspace), then ghat / gvar of the
+// fold's inputs scattered to their positions fold_idx.  One workgroup per 64-row strip of M^-1: the 64x64 tiles of the strip
+// pass through LDS (a tile above the diagonal is read as the transpose of its lower mirror), thread (row, g) sums the columns
+// g, g + 4, .. of each tile in order and the four partials are added in a fixed order: no atomics, bitwise reproducible.
+template <typename T>
+__global__ __launch_bounds__(256) void cv_apply_kernel(const T* __restrict__ Mi, size_t cmat, int mpad, const int* __restrict__ folds,
+                                                       int F, int q_local, const T* __restrict__ b, const T* __restrict__ z, int npad,
+                                                       const T* __restrict__ sr, const double* __restrict__ theta, int tw, int d,
+                                                       int ldo, double* __restrict__ ghat, double* __restrict__ gvar) {
+    const int s = blockIdx.y, f = s / q_local, k = s - f * q_local, I = blockIdx.x;
+    const int lo = folds[f], m = folds[f + 1] - lo;
+    if (I * TS >= m) return;                     // (uniform per workgroup)
+    const int* __restrict__ idx = folds + F + 1 + lo;
+    const T* __restrict__ Ms = Mi + (size_t)s * cmat;
+    const T* __restrict__ zk = z + (size_t)k * npad;
+    __shared__ double tile[TS][TS + 1];
+    __shared__ double zs[TS];
+    __shared__ double part[4][TS];
+    const int tid = threadIdx.x, row = tid & (TS - 1), g = tid >> 6;
+    const int nJ = (m + TS - 1) / TS;
+    double acc = 0.0;
+    for (int J = 0; J < nJ; ++J) {
+        const int tr = max(I, J), tc = min(I, J);        // the stored (lower) tile
+        const T* __restrict__ src = Ms + (size_t)tr * TS * mpad + (size_t)tc * TS;
+        for (int e = tid; e < TS * TS; e += 256) {
+            const int a = e / TS, bb = e - a * TS;
+            tile[a][bb] = (double)src[(size_t)a * mpad + bb];
+        }
+        if (tid < TS) {
+            const int j = J * TS + tid;
+            zs[tid] = j < m ? (double)zk[idx[j]] : 0.0;
+        }
+        __syncthreads();
+        const int jend = min(TS, m - J * TS);
+        for (int jj = g; jj < jend; jj += 4) {
+            double v;
+            if (J < I) v = tile[row][jj];
+            else if (J > I) v = tile[jj][row];
+            else v = row >= jj ? tile[row][jj] : tile[jj][row];
+            acc += v * zs[jj];
+        }
+        __syncthreads();
+    }
+    part[g][row] = acc;
+    __syncthreads();
+    const int i = I * TS + tid;
+    if (tid < TS && i < m) {
+        const double t = ((part[0][tid] + part[1][tid]) + part[2][tid]) + part[3][tid];
+        const int gi = idx[i];
+        const double mii = (double)Ms[(size_t)i * mpad + i];
+        const double sv = sr ? (double)sr[gi] : 1.0;
+        const double Dk = theta[(size_t)k * tw + d + 2];
+        ghat[(size_t)k * ldo + gi] = ((double)b[(size_t)k * npad + gi] - t) / (Dk * sv);
+        gvar[(size_t)k * ldo + gi] = (mii - 1.0) / (Dk * sv * sv);
+    }
+}
+
+template <typename T>
+int do_loo(hipStream_t st, const Ws& w, const void* sr, const double* theta, double* ghat, double* gvar, int ldo) {
+    hipLaunchKernelGGL((loo_kernel<T>), dim3((w.n + 255) / 256, w.q), dim3(256), 0, st, (const T*)(w.base + w.off_V), w.mat, w.n,
+                       w.npad, (const T*)(w.base + w.off_b), (const T*)(w.base + w.off_z), (const T*)sr, theta, w.d + 3 + w.p,
+                       w.d, ldo, ghat, gvar);
+    CHECK_LAUNCH("loo_kernel");
+    return 0;
+}
+
+template <typename T>
+int do_cv_gather(hipStream_t st, const Ws& w, const int* folds, int F, const Ws& cw) {
+    const int nbm = cw.npad / TS;
+    hipLaunchKernelGGL((cv_gather_kernel<T>), dim3(nbm * (nbm + 1) / 2, cw.q), dim3(256), 0, st, (const T*)(w.base + w.off_V),
+                       w.mat, w.npad, folds, F, w.q, (T*)(cw.base + cw.off_M), cw.mat, cw.npad);
+    CHECK_LAUNCH("cv_gather_kernel");
+    return 0;
+}
+
+template <typename T>
+int do_cv_apply(hipStream_t st, const Ws& w, const void* sr, const double* theta, const int* folds, int F, const Ws& cw,
+                double* ghat, double* gvar, int ldo) {
+    hipLaunchKernelGGL((cv_apply_kernel<T>), dim3((cw.n + TS - 1) / TS, cw.q), dim3(256), 0, st, (const T*)(cw.base + cw.off_V),
+                       cw.mat, cw.npad, folds, F, w.q, (const T*)(w.base + w.off_b), (const T*)(w.base + w.off_z), w.npad,
+                       (const T*)sr, theta, w.d + 3 + w.p, w.d, ldo, ghat, gvar);
+    CHECK_LAUNCH("cv_apply_kernel");
+    return 0;
+}
+
+// host-side checks of the folds (CSR over the n training inputs); returns the largest fold size in *mmax
+int check_folds(int n, int q_local, int F, const int* folds, int* mmax) {
+    if (F < 1) return bad("F must be >= 1");
+    if ((long long)F * q_local > 65535) return bad("F * q_local must be <= 65535");
+    if (!folds) return bad("NULL folds_host");
+    const int* ptr = folds;
+    const int* idx = folds + F + 1;
+    if (ptr[0] != 0 || ptr[F] != n) return bad("fold_ptr must start at 0 and end at n");
+    std::vector<char> seen((size_t)n, 0);
+    int mx = 0;
+    for (int f = 0; f < F; ++f) {
+        const int m = ptr[f + 1] - ptr[f];
+        if (m < 1) return bad("empty fold");
+        mx = max(mx, m);
+        for (int e = ptr[f]; e < ptr[f + 1]; ++e) {
+            const int v = idx[e];
+            if (v < 0 || v >= n) return bad("fold index out of range");
+            if (seen[v]) return bad("fold index repeated");
+            seen[v] = 1;
+            if (e > ptr[f] && v < idx[e - 1]) return bad("fold indices must be sorted ascending within a fold");
+        }
+    }
+    *mmax = mx;
+    return 0;
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------------
@@ -3580,6 +3750,58 @@ int lcgp_sample_latent(void* stream, int dtype, int n0, int d, int p, int q_loca
     const int ld = ldg ? ldg : n0;
     return dtype == LCGP_F64 ? do_sample<double>(st, cw, S, eps, ghat, ld, scratch, out)
                              : do_sample<float>(st, cw, S, eps, ghat, ld, scratch, out);
+}
+
+int lcgp_loo(void* stream, int dtype, int n, int d, int p, int q_local, const void* sr, const double* theta,
+             const void* workspace, double* ghat, double* gvar, int out_stride) {
+    int rc = check_common(dtype, n, d, p, q_local);
+    if (rc) return rc;
+    if (!theta || !workspace || !ghat || !gvar) return bad("NULL pointer");
+    if (out_stride != 0 && out_stride < n) return bad("out_stride must be 0 (= n) or >= n");
+    Ws w = carve(dtype, n, d, p, q_local, (void*)workspace);
+    hipStream_t st = (hipStream_t)stream;
+    const int ldo = out_stride ? out_stride : n;
+    return dtype == LCGP_F64 ? do_loo<double>(st, w, sr, theta, ghat, gvar, ldo) : do_loo<float>(st, w, sr, theta, ghat, gvar, ldo);
+}
+
+int lcgp_cv_workspace_bytes(int dtype, int n, int d, int p, int q_local, int F, const int* folds_host, size_t* bytes) {
+    int rc = check_common(dtype, n, d, p, q_local);
+    if (rc) return rc;
+    int mmax = 0;
+    if ((rc = check_folds(n, q_local, F, folds_host, &mmax))) return rc;
+    if (!bytes) return bad("bytes is NULL");
+    *bytes = carve(dtype, mmax, d, p, q_local * F, nullptr).total;
+    return 0;
+}
+
+int lcgp_cv_gather(void* stream, int dtype, int n, int d, int p, int q_local, const void* workspace, int F,
+                   const int* folds_host, const int* folds, void* cv_workspace) {
+    int rc = check_common(dtype, n, d, p, q_local);
+    if (rc) return rc;
+    int mmax = 0;
+    if ((rc = check_folds(n, q_local, F, folds_host, &mmax))) return rc;
+    if (!workspace || !folds || !cv_workspace) return bad("NULL pointer");
+    Ws w = carve(dtype, n, d, p, q_local, (void*)workspace);
+    Ws cw = carve(dtype, mmax, d, p, q_local * F, cv_workspace);
+    hipStream_t st = (hipStream_t)stream;
+    return dtype == LCGP_F64 ? do_cv_gather<double>(st, w, folds, F, cw) : do_cv_gather<float>(st, w, folds, F, cw);
+}
+
+int lcgp_cv_apply(void* stream, int dtype, int n, int d, int p, int q_local, const void* sr, const double* theta,
+                  const void* workspace, int F, const int* folds_host, const int* folds, const void* cv_workspace,
+                  double* ghat, double* gvar, int out_stride) {
+    int rc = check_common(dtype, n, d, p, q_local);
+    if (rc) return rc;
+    int mmax = 0;
+    if ((rc = check_folds(n, q_local, F, folds_host, &mmax))) return rc;
+    if (!theta || !workspace || !folds || !cv_workspace || !ghat || !gvar) return bad("NULL pointer");
+    if (out_stride != 0 && out_stride < n) return bad("out_stride must be 0 (= n) or >= n");
+    Ws w = carve(dtype, n, d, p, q_local, (void*)workspace);
+    Ws cw = carve(dtype, mmax, d, p, q_local * F, (void*)cv_workspace);
+    hipStream_t st = (hipStream_t)stream;
+    const int ldo = out_stride ? out_stride : n;
+    return dtype == LCGP_F64 ? do_cv_apply<double>(st, w, sr, theta, folds, F, cw, ghat, gvar, ldo)
+                             : do_cv_apply<float>(st, w, sr, theta, folds, F, cw, ghat, gvar, ldo);
 }
 
 }  // extern "C"

@@ -83,6 +83,8 @@ class HotPathEngine:
             self._scratch = None
             self._cov_ws = None          # (n0, workspace) of the joint covariance (form_cov)
             self._cov_plans = {}         # n0 -> launch plan of its factorisation
+            self._cv_ws = None           # ((mmax, F), workspace) of the fold matrices (cv_block)
+            self._cv_plans = {}          # (mmax, q_local F) -> launch plan of their factorisation
         self._theta_last = None
 
     # ------------------------------------------------------------------------------------------------
@@ -407,6 +409,119 @@ class HotPathEngine:
                 if dst is not out:
                     out[:, lo:lo + m].copy_(dst)
             return out
+
+    # ------------------------------------------------------------------------------------------------
+    # closed-form cross-validation at fixed parameters (lcgp_hip.h: lcgp_loo, lcgp_cv_gather / lcgp_cv_apply)
+    def loo_block(self):
+        """(2, q_local, n) float64 DEVICE tensor [ghat; gvar] of leave-one-out at every training input, from the factorisation
+        of the last evaluate() (lcgp_loo: reads A^-1's diagonal, b and z; one launch)."""
+        torch = self.torch
+        if self._theta_last is None:
+            raise RuntimeError("predict_loo() needs a preceding evaluate() at the current parameters")
+        with torch.cuda.device(self.device):
+            out = torch.empty((2, self.q_local, self.n), dtype=torch.float64, device=self.device)
+            _hip.check(self.lib.lcgp_loo(self._stream(), self.dtype, self.n, self.d, self.p, self.q_local, self._p(self.sr),
+                                         self._p(self.theta_dev), self._p(self.workspace), self._p(out[0]), self._p(out[1]),
+                                         self.n), "lcgp_loo")
+            self._raise_if_not_finite(out)
+            return out
+
+    def _raise_if_not_finite(self, out, info=None):
+        """LinAlgError carrying per-local-component info words when a fold factorisation failed (info) or a result is not
+        finite (never hand NaNs on)"""
+        bad = ~self.torch.isfinite(out).reshape(2, self.q_local, -1).all(dim=2).all(dim=0)
+        codes = bad.cpu().numpy().astype(np.int64)
+        if info is not None:
+            codes = np.where(info != 0, info, codes)
+        if np.any(codes != 0):
+            err = np.linalg.LinAlgError("cross-validation: a fold matrix of local components (index, info) %s is not numerically "
+                                        "positive definite" % [(i, int(v)) for i, v in enumerate(codes) if v != 0])
+            err.info = codes
+            raise err
+
+    def _cv_workspace(self, mmax, F, folds_host):
+        """the fold workspace (lcgp_cv_workspace_bytes: carved for n = mmax and q_local * F components), cached per (mmax, F)
+        like the joint-covariance workspace: 3 q_local F mpad^2 elements (mpad = mmax rounded up to 128) -- ValueError
+        beforehand when that does not fit in the free device memory"""
+        if self._cv_ws is not None and self._cv_ws[0] == (mmax, F):
+            return self._cv_ws[1]
+        nbytes = C.c_size_t(0)
+        _hip.check(self.lib.lcgp_cv_workspace_bytes(self.dtype, self.n, self.d, self.p, self.q_local, F,
+                                                    C.c_void_p(folds_host.ctypes.data), C.byref(nbytes)), "lcgp_cv_workspace_bytes")
+        self._cv_ws = None
+        free, _ = self.torch.cuda.mem_get_info(self.device)
+        free += self.torch.cuda.memory_reserved(self.device) - self.torch.cuda.memory_allocated(self.device)
+        if nbytes.value > free:
+            raise ValueError("cross-validation over %d folds of up to %d inputs needs %.2f GB of device memory (%d components x %d "
+                             "folds, 3 matrices each), %.2f GB are free: use fewer or smaller folds"
+                             % (F, mmax, nbytes.value / 1e9, self.q_local, F, free / 1e9))
+        ws = self.torch.empty(int(nbytes.value), dtype=self.torch.uint8, device=self.device)
+        self._cv_ws = ((mmax, F), ws)
+        return ws
+
+    def _cv_plan(self, mmax, qf):
+        key = (mmax, qf)
+        if key not in self._cv_plans:
+            nbytes = C.c_size_t(0)
+            _hip.check(self.lib.lcgp_plan_bytes(self.dtype, mmax, qf, 0, None, C.byref(nbytes)), "lcgp_plan_bytes")
+            host = np.zeros(int(nbytes.value), dtype=np.uint8)
+            _hip.check(self.lib.lcgp_plan_build(self.dtype, mmax, qf, 0, None, C.c_void_p(host.ctypes.data), nbytes),
+                       "lcgp_plan_build")
+            self._cv_plans = {key: host}
+        return C.c_void_p(self._cv_plans[key].ctypes.data)
+
+    def cv_block(self, fold_ptr, fold_idx, return_cov=False):
+        """(2, q_local, n) float64 DEVICE tensor [ghat; gvar]: the prediction at the inputs of each fold of the model conditioned
+        on the other folds (lcgp_cv_gather -> lcgp_potrf_logdet -> lcgp_potri -> lcgp_cv_apply).  fold_ptr (F + 1) / fold_idx
+        (n): CSR over the training inputs, each fold sorted ascending.  return_cov: also a list of F float64 DEVICE tensors
+        (q_local, m_f, m_f), the latent covariance of each fold.  Raises numpy.linalg.LinAlgError carrying per-local-component
+        info words when a fold matrix is not numerically positive definite."""
+        torch = self.torch
+        if self._theta_last is None:
+            raise RuntimeError("predict_cv() needs a preceding evaluate() at the current parameters")
+        fold_ptr = np.asarray(fold_ptr, np.int64)
+        F = len(fold_ptr) - 1
+        folds_host = np.ascontiguousarray(np.concatenate([fold_ptr, np.asarray(fold_idx, np.int64)]).astype(np.int32))
+        sizes = np.diff(fold_ptr)
+        mmax = int(sizes.max()) if F >= 1 else 0
+        qf = self.q_local * F
+        with torch.cuda.device(self.device):
+            cws = self._cv_workspace(mmax, F, folds_host)
+            folds = torch.as_tensor(folds_host).to(self.device)
+            hp = C.c_void_p(folds_host.ctypes.data)
+            st = self._stream()
+            _hip.check(self.lib.lcgp_cv_gather(st, self.dtype, self.n, self.d, self.p, self.q_local, self._p(self.workspace), F, hp,
+                                               self._p(folds), self._p(cws)), "lcgp_cv_gather")
+            info = torch.zeros(qf, dtype=torch.int32, device=self.device)
+            _hip.check(self.lib.lcgp_potrf_logdet(st, self.dtype, mmax, self.d, self.p, qf, self._p(cws), None, self._p(info), None,
+                                                  self._cv_plan(mmax, qf)), "lcgp_potrf_logdet")
+            _hip.check(self.lib.lcgp_potri(st, self.dtype, mmax, self.d, self.p, qf, self._p(cws), None), "lcgp_potri")
+            out = torch.empty((2, self.q_local, self.n), dtype=torch.float64, device=self.device)
+            _hip.check(self.lib.lcgp_cv_apply(st, self.dtype, self.n, self.d, self.p, self.q_local, self._p(self.sr),
+                                              self._p(self.theta_dev), self._p(self.workspace), F, hp, self._p(folds), self._p(cws),
+                                              self._p(out[0]), self._p(out[1]), self.n), "lcgp_cv_apply")
+            # a failed pivot of any fold of component k is reported on k (slot f * q_local + k)
+            inf = info.cpu().numpy().reshape(F, self.q_local)
+            self._raise_if_not_finite(out, np.where(inf != 0, inf, 0).max(axis=0))
+            if not return_cov:
+                return out
+            covs = []
+            mi = torch.empty((mmax, mmax), dtype=self.tdtype, device=self.device)
+            D = self.theta_dev[:, self.d + 2]
+            s = torch.ones(self.n, dtype=torch.float64, device=self.device) if self.sr is None else self.sr.to(torch.float64)
+            for f in range(F):
+                m = int(sizes[f])
+                idx = folds[F + 1 + int(fold_ptr[f]):F + 1 + int(fold_ptr[f + 1])].long()
+                sb = s[idx]
+                cov = torch.empty((self.q_local, m, m), dtype=torch.float64, device=self.device)
+                for k in range(self.q_local):
+                    _hip.check(self.lib.lcgp_fetch_matrix(st, self.dtype, mmax, self.d, self.p, qf, self._p(cws), 2,
+                                                          f * self.q_local + k, self._p(mi)), "lcgp_fetch_matrix")
+                    cov[k] = mi[:m, :m]
+                cov.diagonal(dim1=1, dim2=2).sub_(1.0)
+                cov /= D[:, None, None] * (sb[:, None] * sb[None, :])[None]
+                covs.append(cov)
+            return out, covs
 
     def fetch_vector(self, which, k):
         torch = self.torch

@@ -869,10 +869,11 @@ class LCGP:
             scale, offset = _np(self.ystd)[:, 0], _np(self.ymean)[:, 0]
         return W, np.broadcast_to(noise, (p,)).astype(F64), scale, offset
 
-    def _agree(self, fn, jitter=None):
+    def _agree(self, fn, jitter=None, failure=None):
         """runs this rank's share `fn()` and makes every rank raise together when any rank's share failed (a rank that raised
         alone would leave the others waiting in the next collective): the q info words of the factorisations and a
-        ValueError flag are all-reduced first.  Returns fn()'s value."""
+        ValueError flag are all-reduced first.  Returns fn()'s value.  `failure`: the message of the LinAlgError, formatted
+        with the failing components and their info words (default: that of the joint covariance)."""
         q = int(self.q)
         status = np.zeros(q + 1, F64)
         res, err = None, None
@@ -890,6 +891,8 @@ class LCGP:
         if status[q] != 0:
             raise err if err is not None else ValueError('another rank could not allocate the joint covariance')
         bad = [k for k in range(q) if status[k] != 0]
+        if bad and failure is not None:
+            raise np.linalg.LinAlgError(failure % (bad, [int(status[k]) for k in bad]))
         if bad:
             raise np.linalg.LinAlgError(
                 'the posterior covariance Sigma_k + jitter scale_k I of latent component(s) %s is not numerically positive '
@@ -972,6 +975,120 @@ class LCGP:
             eta = np.random.default_rng((seed, q)).standard_normal((S, p, n0))
             ys += np.sqrt(noise)[None, :, None] * eta
         return _t(ys * scale[None, :, None] + offset[None, :, None])
+
+    # =============================================================================================
+    # closed-form cross-validation at fixed parameters (beyond the reference)
+    # =============================================================================================
+    def _cv_labels(self, folds, seed):
+        """fold labels (n,) over the training inputs (the unique inputs on the rep path) -> (labels, fold_ptr, fold_idx)"""
+        n = int(self.x_unique_s.shape[0]) if self.submethod == 'rep' else int(self.n)
+        if np.ndim(folds) == 0:
+            if isinstance(folds, (bool, np.bool_)) or not float(folds).is_integer():
+                raise ValueError('folds must be an int F or an array of %d integer labels' % n)
+            F = int(folds)
+            if F < 1 or F > n:
+                raise ValueError('the number of folds must be in [1, %d], got %d' % (n, F))
+            labels = np.random.default_rng(seed).permutation(n) % F
+        else:
+            labels = np.asarray(folds)
+            if labels.shape != (n,):
+                raise ValueError('fold labels must have shape (%d,) (one per %s), got %s'
+                                 % (n, 'unique input' if self.submethod == 'rep' else 'training input', labels.shape))
+            if labels.dtype.kind not in 'iu' and not (labels.dtype.kind == 'f' and np.all(np.isfinite(labels))
+                                                      and np.all(labels == np.round(labels))):
+                raise ValueError('fold labels must be integers')
+            labels = labels.astype(np.int64)
+        _, inv = np.unique(labels, return_inverse=True)
+        inv = inv.reshape(-1)
+        F = int(inv.max()) + 1
+        if F * int(self.q) > 65535:
+            raise ValueError('at most %d folds with q = %d latent components' % (65535 // int(self.q), int(self.q)))
+        order = np.argsort(inv, kind='stable')          # ascending input index within each fold
+        fold_ptr = np.r_[0, np.cumsum(np.bincount(inv, minlength=F))]
+        return labels, fold_ptr, order
+
+    def _cv_latent(self, fn):
+        """runs the engine call `fn(eng)` -> (2, q_local, n) [ghat; gvar] (and extras) on the factorisation of the current
+        parameters, with the ranks agreeing on failures; a float32 model whose fold factorisation fails is evaluated again on
+        its float64 engine, as a failed float32 evaluation is"""
+        eng = self._ensure_aux()
+        failure = ('cross-validation: a fold matrix a_k[B, B] of latent component(s) %s is not numerically positive definite '
+                   'at the current parameters (info %s)')
+        try:
+            return self._agree(lambda: None if eng is None else fn(eng), failure=failure), eng
+        except np.linalg.LinAlgError:
+            if not (self._dtype == 'float32' and self.float32_fallback) or self._last_eval_float64:
+                raise
+        # float32 gave up: the float64 engine evaluates the current parameters (every rank: the failure was agreed on)
+        if self._engine64 is None and self._get_engine() is not None:
+            self._engine64 = self._make_engine('float64')
+        self.float32_fallbacks += 1
+        only = self._float64_only
+        self._float64_only = True
+        try:
+            self._run_path()
+        finally:
+            self._float64_only = only
+        eng = self._aux_engine if self._engine64 is not None else None
+        return self._agree(lambda: None if eng is None else fn(eng), failure=failure + ', in float64 either'), eng
+
+    def _cv_outputs(self, both):
+        """(q, 2, n) latent [ghat; gvar] per component -> predict's outputs (the same map, unchanged)"""
+        ghat, gvar = both[:, 0], both[:, 1]
+        if self.submethod == 'rep':
+            return self._outputs_rep(ghat, gvar)
+        return self._outputs_full(ghat, gvar)
+
+    def predict_loo(self):
+        """Leave-one-out predictions (ypred, ypredvar, yconfvar), each (p, n) -- (p, n_unique) on the rep path -- at FIXED
+        parameters: column i is what predict(x[i:i+1]) returns from the model conditioned on every other input, with the same
+        hyper-parameters, noise, basis phi and standardisation (no nugget in the cross covariance, as for a new input).  In
+        closed form from the factorisation of the current parameters (lcgp_loo; right after fit() or predict() no extra
+        evaluation), in the engine's dtype: ghat_i = (b_i - z_i / a_ii) / (D s_i), gvar_i = (1 / a_ii - 1) / (D s_i^2).
+        On the rep path input i is a unique input with all its replicates left out, and ypredvar is the variance of ONE new
+        replicate, as in predict(): compare against ybar[:, i] with yconfvar + noise / r_i.  On the full path duplicated rows
+        are left out one at a time (the copy stays in): group them with predict_cv labels, or use submethod='rep'.
+        self.ghat / self.gvar are left untouched."""
+        n = self._cv_n()
+        blk, _ = self._cv_latent(lambda e: e.loo_block())
+        loc = None if blk is None else blk.permute(1, 0, 2)              # (q_local, 2, n)
+        return self._cv_outputs(self._gather_components(loc, (2, n)))
+
+    def _cv_n(self):
+        return int(self.x_unique_s.shape[0]) if self.submethod == 'rep' else int(self.n)
+
+    def predict_cv(self, folds, seed=0, return_latent_cov=False):
+        """k-fold cross-validation predictions (ypred, ypredvar, yconfvar), each (p, n) -- (p, n_unique) on the rep path --
+        at FIXED parameters: the inputs of each fold are predicted by the model conditioned on all other folds, as
+        predict_loo() does for single inputs (same hyper-parameters, basis and standardisation; no refit).
+          folds: an int F (labels default_rng(seed).permutation(n) % F) or an array of n integer labels, one per training
+                 input (per unique input on the rep path).  The labels used are kept as self.cv_labels.
+          return_latent_cov: also a list of F tensors (q, m_f, m_f), the latent posterior covariance of each fold over its
+                 inputs in ascending order (the prior variance, nugget included, on the diagonal, as predict_latent_cov).
+        Folds of one input each reproduce predict_loo(); one fold holding every input gives the prior.  GPU memory: 3 q_local
+        F mpad^2 elements (mpad = the largest fold rounded up to 128) -- ValueError when it does not fit.  A float32 model
+        computes in float32 and repeats the call in float64 if a fold matrix is not numerically positive definite there.
+        self.ghat / self.gvar are left untouched."""
+        labels, fold_ptr, fold_idx = self._cv_labels(folds, seed)
+        n, q = len(labels), int(self.q)
+        sizes = np.diff(fold_ptr)
+        res, _ = self._cv_latent(lambda e: e.cv_block(fold_ptr, fold_idx, return_latent_cov))
+        loc = None
+        if res is not None:
+            blk, covs = res if return_latent_cov else (res, [])
+            # predictions and every fold's covariance in ONE reduction: (q_local, 2 n + sum m_f^2)
+            loc = torch.cat([blk.permute(1, 0, 2).reshape(blk.shape[1], -1)] + [c.reshape(c.shape[0], -1) for c in covs], dim=1)
+        width = 2 * n + (int(np.sum(sizes * sizes)) if return_latent_cov else 0)
+        flat = self._gather_components(loc, (width,))
+        self.cv_labels = labels
+        outs = self._cv_outputs(flat[:, :2 * n].reshape(q, 2, n))
+        if not return_latent_cov:
+            return outs
+        lat, off = [], 2 * n
+        for m in sizes:
+            lat.append(_t(flat[:, off:off + m * m].reshape(q, m, m)))
+            off += m * m
+        return (*outs, lat)
 
     # =============================================================================================
     # input gradients of the prediction (the reference: a tf.GradientTape around predict)

@@ -1,0 +1,60 @@
+"""Worker of tests/test_gpu_cv.py::test_two_ranks_reproduce_one_rank: one rank of a 2-rank gloo job in which both ranks
+drive the same GPU (component k -> rank k mod 2).  Every rank also builds the same model on a one-rank group of its own,
+which holds all components, and compares: leave-one-out bitwise, the folds to 1e-13 relative (the schedule of the fold
+factorisation depends on the batch q_local * F)."""
+import os
+import sys
+
+import numpy as np
+import torch
+import torch.distributed as dist
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from lcgp_amd import LCGP, synth  # noqa: E402
+from oracle import lcgp_oracle as orc  # noqa: E402
+
+
+def _rel(a, b):
+    return np.max(np.abs(a - b)) / max(np.max(np.abs(b)), 1e-300)
+
+
+def main():
+    torch.cuda.set_device(0)
+    dist.init_process_group("gloo")
+    rank, world = dist.get_rank(), dist.get_world_size()
+    assert world == 2
+    solo = [dist.new_group([r]) for r in range(world)][rank]
+    for mode, q, maker in (("full", 3, lambda: synth.make_full(81, 300, 2, 4, 3)),
+                           ("rep", 4, lambda: synth.make_rep(82, 90, 3, 2, 4, 4))):
+        x, y = maker()
+        m2 = LCGP(y=y, x=x, q=q, submethod=mode, device="cuda:0")
+        m1 = LCGP(y=y, x=x, q=q, submethod=mode, device="cuda:0", process_group=solo)
+        m1.phi = m2.phi.clone()
+        m1.g, m1.diag_D = m2.g.clone(), m2.diag_D.clone()
+        u = synth.param_points(81, orc.OracleLCGP(y=y, x=x, q=q, submethod=mode).get_unconstrained())[1]
+        m1._set_flat(u)
+        m2._set_flat(u)
+        for a, b in zip(m2.predict_loo(), m1.predict_loo()):
+            assert np.array_equal(a.numpy(), b.numpy()), (rank, mode, _rel(a.numpy(), b.numpy()))
+        r2 = m2.predict_cv(7, seed=3, return_latent_cov=True)
+        r1 = m1.predict_cv(7, seed=3, return_latent_cov=True)
+        assert len(m2._local_ks) == len(range(rank, q, world)) and len(m1._local_ks) == q
+        for a, b in zip(r2[:3], r1[:3]):
+            assert _rel(a.numpy(), b.numpy()) <= 1e-13, (rank, mode, _rel(a.numpy(), b.numpy()))
+        for a, b in zip(r2[3], r1[3]):
+            assert a.shape[0] == q and _rel(a.numpy(), b.numpy()) <= 1e-13, (rank, mode)
+    # q < world: rank 1 holds no component and still takes part in every collective
+    x, y = synth.make_full(83, 100, 2, 3, 1)
+    m = LCGP(y=y, x=x, q=1, device="cuda:0")
+    assert m.predict_loo()[0].shape == (3, 100)
+    assert m.predict_cv(4, return_latent_cov=True)[3][0].shape == (1, 25, 25)
+    assert (m._engine is None) == (rank == 1)
+    dist.barrier()
+    dist.destroy_process_group()
+    print("RANK %d OK" % rank)
+
+
+if __name__ == "__main__":
+    main()

@@ -2561,27 +2561,38 @@ __global__ __launch_bounds__(256) void pgrad_kernel(const T* __restrict__ x0, in
         if (e__ != hipSuccess) return fail(what, e__);      \
     } while (0)
 
-template <typename T, int DD>
-void launch_build(hipStream_t st, const Ws& w, dim3 grid, const void* x, const void* sr, const double* theta, const void* Y) {
-    // with Y (the NLL path) the launch also zeroes the log-determinant and status words of the components
-    auto go = [&](auto kern) {
-        hipLaunchKernelGGL((build_kernel<T, DD, decltype(kern)::value>), grid, dim3(256), 0, st, (T*)(w.base + w.off_M), w.mat, w.n,
-                           w.npad, w.d, w.p, (const T*)x, (const T*)sr, theta, w.ntile_lower, (const T*)Y, (T*)(w.base + w.off_b),
-                           Y ? (double*)(w.base + w.off_logdet) : nullptr, Y ? (int*)(w.base + w.off_info) : nullptr);
-    };
-    if (w.kern == 0) go(std::integral_constant<int, 0>{}); else go(std::integral_constant<int, 1>{});
+// f(std::integral_constant<int, KERN>{}) for the covariance kernel id w.kern (0 = Matern-3/2, 1 = squared exponential)
+template <typename F>
+inline void for_kern(int kern, F&& f) {
+    if (kern == 0) f(std::integral_constant<int, 0>{});
+    else f(std::integral_constant<int, 1>{});
+}
+
+// f(std::integral_constant<int, DD>{}) for the smallest input-dimension bound DD >= d the narrow kernels are built for
+// (DMAX beyond 16)
+template <typename F>
+inline void for_dim(int d, F&& f) {
+    if (d <= 2) f(std::integral_constant<int, 2>{});
+    else if (d <= 4) f(std::integral_constant<int, 4>{});
+    else if (d <= 6) f(std::integral_constant<int, 6>{});
+    else if (d <= 10) f(std::integral_constant<int, 10>{});
+    else if (d <= 16) f(std::integral_constant<int, 16>{});
+    else f(std::integral_constant<int, DMAX>{});
 }
 
 template <typename T>
 int do_build(hipStream_t st, const Ws& w, const void* x, const void* sr, const double* theta, const void* Y = nullptr) {
-    // with Y the launch also computes b_k = Y^T psi_k into the workspace (extra blocks past the tiles)
+    // with Y (the NLL path) the launch also computes b_k = Y^T psi_k into the workspace (extra blocks past the tiles) and
+    // zeroes the log-determinant and status words of the components
     dim3 grid(w.ntile_lower + (Y ? (w.npad + 255) / 256 : 0), w.q);
-    if (w.d <= 2) launch_build<T, 2>(st, w, grid, x, sr, theta, Y);
-    else if (w.d <= 4) launch_build<T, 4>(st, w, grid, x, sr, theta, Y);
-    else if (w.d <= 6) launch_build<T, 6>(st, w, grid, x, sr, theta, Y);
-    else if (w.d <= 10) launch_build<T, 10>(st, w, grid, x, sr, theta, Y);
-    else if (w.d <= 16) launch_build<T, 16>(st, w, grid, x, sr, theta, Y);
-    else launch_build<T, DMAX>(st, w, grid, x, sr, theta, Y);
+    for_dim(w.d, [&](auto dd) {
+        for_kern(w.kern, [&](auto kern) {
+            hipLaunchKernelGGL((build_kernel<T, decltype(dd)::value, decltype(kern)::value>), grid, dim3(256), 0, st,
+                               (T*)(w.base + w.off_M), w.mat, w.n, w.npad, w.d, w.p, (const T*)x, (const T*)sr, theta, w.ntile_lower,
+                               (const T*)Y, (T*)(w.base + w.off_b), Y ? (double*)(w.base + w.off_logdet) : nullptr,
+                               Y ? (int*)(w.base + w.off_info) : nullptr);
+        });
+    });
     CHECK_LAUNCH("build_kernel");
     return 0;
 }
@@ -2902,19 +2913,6 @@ int do_potri(hipStream_t st, const Ws& w, const lcgp_sched& sc, bool* z_partials
     return do_lauum<T>(st, w, sc, z_partials);
 }
 
-template <typename T, int DD>
-void launch_grad(hipStream_t st, const Ws& w, const void* x, const void* sr, const double* theta, const void* Y,
-                 double* out) {
-    // (float32: the noise gradient comes from c = (C o s s^T) z after this launch, so no extra blocks here)
-    auto go = [&](auto kern) {
-        hipLaunchKernelGGL((grad_kernel<T, DD, decltype(kern)::value>), dim3(w.ntile_lower + (sizeof(T) == 4 ? 0 : w.p), w.q),
-                           dim3(256), 0, st, (const T*)(w.base + w.off_V), w.mat, w.n, w.npad, w.d, w.p, (const T*)x, (const T*)sr,
-                           (const T*)(w.base + w.off_z), theta, (double*)(w.base + w.off_part), w.ntile_lower, (const T*)Y,
-                           (const T*)(w.base + w.off_b), out, (double*)(w.base + w.off_cpart));
-    };
-    if (w.kern == 0) go(std::integral_constant<int, 0>{}); else go(std::integral_constant<int, 1>{});
-}
-
 template <typename T>
 int do_nll_grad(hipStream_t st, const Ws& w, const lcgp_sched& sc, const void* x, const void* Y, const void* sr,
                 const double* theta, double* out, const void* plan_host) {
@@ -2941,21 +2939,17 @@ int do_nll_grad(hipStream_t st, const Ws& w, const lcgp_sched& sc, const void* x
                            (const double*)(w.base + w.off_part), w.ntile_lower, w.npad, w.nb, z);
     }
     CHECK_LAUNCH("symv_reduce_kernel");
-    if (w.d <= 2) launch_grad<T, 2>(st, w, x, sr, theta, Y, out);
-    else if (w.d <= 4) launch_grad<T, 4>(st, w, x, sr, theta, Y, out);
-    else if (w.d <= 6) launch_grad<T, 6>(st, w, x, sr, theta, Y, out);
-    else if (w.d <= 10) launch_grad<T, 10>(st, w, x, sr, theta, Y, out);
-    else if (w.d <= 16) launch_grad<T, 16>(st, w, x, sr, theta, Y, out);
-    else if (w.d <= DMAX) launch_grad<T, DMAX>(st, w, x, sr, theta, Y, out);
-    else {
-        auto go = [&](auto kern) {
-            hipLaunchKernelGGL((grad_kernel_wide<T, decltype(kern)::value>), dim3(w.ntile_lower + (sizeof(T) == 4 ? 0 : w.p), w.q),
-                               dim3(256), 0, st, (const T*)(w.base + w.off_V), w.mat, w.n, w.npad, w.d, w.p, (const T*)x,
-                               (const T*)sr, (const T*)(w.base + w.off_z), theta, (double*)(w.base + w.off_part), w.ntile_lower,
-                               (const T*)Y, (const T*)(w.base + w.off_b), out, (double*)(w.base + w.off_cpart));
+    // (float32: the noise gradient comes from c = (C o s s^T) z after this launch, so no extra blocks here)
+    for_kern(w.kern, [&](auto kern) {
+        auto go = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, dim3(w.ntile_lower + (sizeof(T) == 4 ? 0 : w.p), w.q), dim3(256), 0, st,
+                               (const T*)(w.base + w.off_V), w.mat, w.n, w.npad, w.d, w.p, (const T*)x, (const T*)sr,
+                               (const T*)(w.base + w.off_z), theta, (double*)(w.base + w.off_part), w.ntile_lower, (const T*)Y,
+                               (const T*)(w.base + w.off_b), out, (double*)(w.base + w.off_cpart));
         };
-        if (w.kern == 0) go(std::integral_constant<int, 0>{}); else go(std::integral_constant<int, 1>{});
-    }
+        if (w.d > DMAX) go(grad_kernel_wide<T, decltype(kern)::value>);
+        else for_dim(w.d, [&](auto dd) { go(grad_kernel<T, decltype(dd)::value, decltype(kern)::value>); });
+    });
     CHECK_LAUNCH("grad_kernel");
     const double* cvec = nullptr;
     if constexpr (sizeof(T) == 4) {
@@ -3037,12 +3031,10 @@ template <typename T>
 int do_matern(hipStream_t st, int kern, int n1, int n2, int d, const void* x1, const void* x2, const ThetaArg& th, int same,
               void* out) {
     dim3 grid((n2 + TS - 1) / TS, (n1 + TS - 1) / TS);
-    if (kern == 0)
-        hipLaunchKernelGGL((cross_kernel<T, 0>), grid, dim3(256), 0, st, (T*)out, n2, n1, n2, d, (const T*)x1, (const T*)x2, th,
-                           (const double*)nullptr, same, (const T*)nullptr, n1, n2, 0, (size_t)0);
-    else
-        hipLaunchKernelGGL((cross_kernel<T, 1>), grid, dim3(256), 0, st, (T*)out, n2, n1, n2, d, (const T*)x1, (const T*)x2, th,
-                           (const double*)nullptr, same, (const T*)nullptr, n1, n2, 0, (size_t)0);
+    for_kern(kern, [&](auto k) {
+        hipLaunchKernelGGL((cross_kernel<T, decltype(k)::value>), grid, dim3(256), 0, st, (T*)out, n2, n1, n2, d, (const T*)x1,
+                           (const T*)x2, th, (const double*)nullptr, same, (const T*)nullptr, n1, n2, 0, (size_t)0);
+    });
     CHECK_LAUNCH("cross_kernel");
     return 0;
 }
@@ -3051,8 +3043,38 @@ int do_matern(hipStream_t st, int kern, int n1, int n2, int d, const void* x1, c
 // then run on the 128x128 8-wave tile kernel), whole 64-tiles otherwise
 inline int predict_pad(int n0) { return n0 >= 128 ? round_up(n0, 2 * TS) : round_up(n0, TS); }
 
-// K6, all local components in every launch:  X_k = c0k o sr^T (one launch), U_k = X_k W_k^T (one launch of the tile
-// kernel, k tiles only up to the diagonal: W is lower triangular), then the row reductions.
+// C_k = A_k op B_k (an OP_PRED_* product of the tile kernel) for all local components: A and C are `rows` x ld slabs sA
+// apart, B_k ld x ld matrices sB apart, ld = nb 64-tiles.  128x128 tiles when rows is a multiple of 128, 64x64 tiles otherwise.
+template <typename T, int OP>
+int launch_pred(hipStream_t st, const T* A, const T* B, T* C, size_t sA, size_t sB, int ld, int rows, int nb, int q) {
+    GemmArgs g;
+    g.A = A; g.B = B; g.C = C;
+    g.sA = sA; g.sB = sB; g.sC = sA; g.ldA = g.ldB = g.ldC = ld; g.p1 = g.p2 = g.p3 = 0;
+    if (rows % (2 * TS) == 0) {
+        g.nb = nb / 2; g.p0 = rows / (2 * TS);
+        return launch_gemm<T, OP, 128>(st, g, g.p0 * g.nb, q);
+    }
+    g.nb = nb; g.p0 = rows / TS;
+    return launch_gemm<T, OP, 64>(st, g, g.p0 * g.nb, q);
+}
+
+// X_k = c0k o sr^T (one launch; zero padded to n0pad rows) and U_k = X_k W_k^T (one launch of the tile kernel, k tiles only
+// up to the diagonal: W is lower triangular) for all local components: q slabs n0pad x npad each
+template <typename T>
+int form_xu(hipStream_t st, const Ws& w, const void* x, const void* sr, const double* theta, int n0, int n0pad, const void* x0,
+            int same, T* X, T* U) {
+    const size_t slab = (size_t)n0pad * w.npad;
+    ThetaArg dummy;
+    memset(&dummy, 0, sizeof(dummy));
+    for_kern(w.kern, [&](auto kern) {
+        hipLaunchKernelGGL((cross_kernel<T, decltype(kern)::value>), dim3(w.nb, n0pad / TS, w.q), dim3(256), 0, st, X, w.npad, n0,
+                           w.n, w.d, (const T*)x0, (const T*)x, dummy, theta, same, (const T*)sr, n0pad, w.npad, w.d + 3 + w.p, slab);
+    });
+    CHECK_LAUNCH("cross_kernel");
+    return launch_pred<T, OP_PRED_U>(st, X, (const T*)(w.base + w.off_W), U, slab, w.mat, w.npad, n0pad, w.nb, w.q);
+}
+
+// K6, all local components in every launch: X_k and U_k (form_xu), then the row reductions.
 template <typename T>
 int do_predict(hipStream_t st, const Ws& w, const void* x, const void* sr, const double* theta, int n0, const void* x0,
                int same, void* scratch, double* ghat, double* gvar, int ldo) {
@@ -3060,44 +3082,12 @@ int do_predict(hipStream_t st, const Ws& w, const void* x, const void* sr, const
     const size_t slab = (size_t)n0pad * w.npad;
     T* X = (T*)scratch;                 // q slabs n0pad x npad : c0k o sr^T (zero padded)
     T* U = X + slab * w.q;              // q slabs n0pad x npad : X W^T = (L^-1 X^T)^T
-    const int tw = w.d + 3 + w.p;
-    ThetaArg dummy;
-    memset(&dummy, 0, sizeof(dummy));
-    dim3 grid(w.nb, n0pad / TS, w.q);
-    if (w.kern == 0)
-        hipLaunchKernelGGL((cross_kernel<T, 0>), grid, dim3(256), 0, st, X, w.npad, n0, w.n, w.d, (const T*)x0, (const T*)x, dummy,
-                           theta, same, (const T*)sr, n0pad, w.npad, tw, slab);
-    else
-        hipLaunchKernelGGL((cross_kernel<T, 1>), grid, dim3(256), 0, st, X, w.npad, n0, w.n, w.d, (const T*)x0, (const T*)x, dummy,
-                           theta, same, (const T*)sr, n0pad, w.npad, tw, slab);
-    CHECK_LAUNCH("cross_kernel");
-    GemmArgs g;
-    g.A = X; g.B = (const T*)(w.base + w.off_W); g.C = U;
-    g.sA = slab; g.sB = w.mat; g.sC = slab; g.ldA = g.ldB = g.ldC = w.npad; g.p1 = g.p2 = g.p3 = 0;
-    int rc;
-    if (n0pad % (2 * TS) == 0) {
-        g.nb = w.nb / 2; g.p0 = n0pad / (2 * TS);
-        rc = launch_gemm<T, OP_PRED_U, 128>(st, g, g.p0 * g.nb, w.q);
-    } else {
-        g.nb = w.nb; g.p0 = n0pad / TS;
-        rc = launch_gemm<T, OP_PRED_U, 64>(st, g, g.p0 * g.nb, w.q);
-    }
+    int rc = form_xu<T>(st, w, x, sr, theta, n0, n0pad, x0, same, X, U);
     if (rc) return rc;
     hipLaunchKernelGGL((pred_reduce_kernel<T>), dim3(n0, w.q), dim3(64), 0, st, (const T*)X, (const T*)U, slab, w.npad, w.n,
-                       (const T*)(w.base + w.off_z), w.npad, theta, tw, w.d, ldo, ghat, gvar);
+                       (const T*)(w.base + w.off_z), w.npad, theta, w.d + 3 + w.p, w.d, ldo, ghat, gvar);
     CHECK_LAUNCH("pred_reduce_kernel");
     return 0;
-}
-
-template <typename T, int DD>
-void launch_pgrad(hipStream_t st, const Ws& w, dim3 grid, int n0, const void* x0, const void* x, const void* sr,
-                  const double* theta, const T* V, size_t slab, int ldo, double* dghat, double* dgvar) {
-    auto go = [&](auto kern) {
-        hipLaunchKernelGGL((pgrad_kernel<T, DD, decltype(kern)::value>), grid, dim3(256), 0, st, (const T*)x0, n0, (const T*)x,
-                           (const T*)sr, w.n, w.d, theta, w.d + 3 + w.p, (const T*)(w.base + w.off_z), w.npad, V, slab, ldo,
-                           dghat, dgvar);
-    };
-    if (w.kern == 0) go(std::integral_constant<int, 0>{}); else go(std::integral_constant<int, 1>{});
 }
 
 // K7 for all local components: do_predict with same = 0 (ghat / gvar bitwise those of lcgp_predict), then V_k = U_k W_k into
@@ -3112,25 +3102,17 @@ int do_predict_grad(hipStream_t st, const Ws& w, const void* x, const void* sr, 
     const size_t slab = (size_t)n0pad * w.npad;
     T* X = (T*)scratch;
     T* U = X + slab * w.q;
-    GemmArgs g;
-    g.A = U; g.B = (const T*)(w.base + w.off_W); g.C = X;
-    g.sA = slab; g.sB = w.mat; g.sC = slab; g.ldA = g.ldB = g.ldC = w.npad; g.p1 = g.p2 = g.p3 = 0;
-    if (n0pad % (2 * TS) == 0) {
-        g.nb = w.nb / 2; g.p0 = n0pad / (2 * TS);
-        rc = launch_gemm<T, OP_PRED_V, 128>(st, g, g.p0 * g.nb, w.q);
-    } else {
-        g.nb = w.nb; g.p0 = n0pad / TS;
-        rc = launch_gemm<T, OP_PRED_V, 64>(st, g, g.p0 * g.nb, w.q);
-    }
+    rc = launch_pred<T, OP_PRED_V>(st, U, (const T*)(w.base + w.off_W), X, slab, w.mat, w.npad, n0pad, w.nb, w.q);
     if (rc) return rc;
     const int wide = w.d > 16;
     dim3 grid((n0 + PG_ROWS - 1) / PG_ROWS, w.q, wide ? (w.d + DMAX - 1) / DMAX : 1);
-    if (w.d <= 2) launch_pgrad<T, 2>(st, w, grid, n0, x0, x, sr, theta, X, slab, ldo, dghat, dgvar);
-    else if (w.d <= 4) launch_pgrad<T, 4>(st, w, grid, n0, x0, x, sr, theta, X, slab, ldo, dghat, dgvar);
-    else if (w.d <= 6) launch_pgrad<T, 6>(st, w, grid, n0, x0, x, sr, theta, X, slab, ldo, dghat, dgvar);
-    else if (w.d <= 10) launch_pgrad<T, 10>(st, w, grid, n0, x0, x, sr, theta, X, slab, ldo, dghat, dgvar);
-    else if (w.d <= 16) launch_pgrad<T, 16>(st, w, grid, n0, x0, x, sr, theta, X, slab, ldo, dghat, dgvar);
-    else launch_pgrad<T, DMAX>(st, w, grid, n0, x0, x, sr, theta, X, slab, ldo, dghat, dgvar);
+    for_dim(w.d, [&](auto dd) {
+        for_kern(w.kern, [&](auto kern) {
+            hipLaunchKernelGGL((pgrad_kernel<T, decltype(dd)::value, decltype(kern)::value>), grid, dim3(256), 0, st, (const T*)x0,
+                               n0, (const T*)x, (const T*)sr, w.n, w.d, theta, w.d + 3 + w.p, (const T*)(w.base + w.off_z), w.npad,
+                               (const T*)X, slab, ldo, dghat, dgvar);
+        });
+    });
     CHECK_LAUNCH("pgrad_kernel");
     return 0;
 }
@@ -3184,7 +3166,7 @@ __global__ __launch_bounds__(256) void draw_out_kernel(const T* __restrict__ G, 
 }
 
 // Sigma_k + tau_k I for all local components:  C00_k = kernel(x0, x0) with the nugget on the diagonal (cross_kernel, same =
-// 1), X_k = c0k o sr^T and U_k = X_k W_k^T exactly as do_predict forms them, then ONE launch of the tile kernel
+// 1), X_k = c0k o sr^T and U_k = X_k W_k^T exactly as do_predict forms them (form_xu), then ONE launch of the tile kernel
 // C00_k -= D_k U_k U_k^T over the lower tiles (K = npad), then the diagonal.
 template <typename T>
 int do_predict_cov(hipStream_t st, const Ws& w, const void* x, const void* sr, const double* theta, int n0, const void* x0,
@@ -3197,24 +3179,12 @@ int do_predict_cov(hipStream_t st, const Ws& w, const void* x, const void* sr, c
     const int tw = w.d + 3 + w.p;
     ThetaArg dummy;
     memset(&dummy, 0, sizeof(dummy));
-    dim3 gx(w.nb, n0pad / TS, w.q), gc(n0pad / TS, n0pad / TS, w.q);
-    if (w.kern == 0) {
-        hipLaunchKernelGGL((cross_kernel<T, 0>), gx, dim3(256), 0, st, X, w.npad, n0, w.n, w.d, (const T*)x0, (const T*)x, dummy,
-                           theta, same, (const T*)sr, n0pad, w.npad, tw, slab);
-        hipLaunchKernelGGL((cross_kernel<T, 0>), gc, dim3(256), 0, st, M, n0pad, n0, n0, w.d, (const T*)x0, (const T*)x0, dummy,
-                           theta, 1, (const T*)nullptr, n0pad, n0pad, tw, cw.mat);
-    } else {
-        hipLaunchKernelGGL((cross_kernel<T, 1>), gx, dim3(256), 0, st, X, w.npad, n0, w.n, w.d, (const T*)x0, (const T*)x, dummy,
-                           theta, same, (const T*)sr, n0pad, w.npad, tw, slab);
-        hipLaunchKernelGGL((cross_kernel<T, 1>), gc, dim3(256), 0, st, M, n0pad, n0, n0, w.d, (const T*)x0, (const T*)x0, dummy,
-                           theta, 1, (const T*)nullptr, n0pad, n0pad, tw, cw.mat);
-    }
+    for_kern(w.kern, [&](auto kern) {
+        hipLaunchKernelGGL((cross_kernel<T, decltype(kern)::value>), dim3(n0pad / TS, n0pad / TS, w.q), dim3(256), 0, st, M, n0pad,
+                           n0, n0, w.d, (const T*)x0, (const T*)x0, dummy, theta, 1, (const T*)nullptr, n0pad, n0pad, tw, cw.mat);
+    });
     CHECK_LAUNCH("cross_kernel");
-    GemmArgs g;
-    g.A = X; g.B = (const T*)(w.base + w.off_W); g.C = U;
-    g.sA = slab; g.sB = w.mat; g.sC = slab; g.ldA = g.ldB = g.ldC = w.npad; g.p1 = g.p2 = g.p3 = 0;
-    g.nb = w.nb / 2; g.p0 = n0pad / (2 * TS);
-    int rc = launch_gemm<T, OP_PRED_U, 128>(st, g, g.p0 * g.nb, w.q);
+    int rc = form_xu<T>(st, w, x, sr, theta, n0, n0pad, x0, same, X, U);
     if (rc) return rc;
     GemmArgs h;
     h.A = U; h.B = U; h.C = M;
@@ -3248,11 +3218,7 @@ int do_sample(hipStream_t st, const Ws& cw, int S, const void* eps, const double
     hipLaunchKernelGGL((eps_pack_kernel<T>), dim3((n0pad + 255) / 256, Spad, cw.q), dim3(256), 0, st, (const T*)eps, S, cw.n, E,
                        n0pad, slab);
     CHECK_LAUNCH("eps_pack_kernel");
-    GemmArgs g;
-    g.A = E; g.B = M; g.C = G;
-    g.sA = slab; g.sB = cw.mat; g.sC = slab; g.ldA = g.ldB = g.ldC = n0pad; g.p1 = g.p2 = g.p3 = 0;
-    g.nb = n0pad / (2 * TS); g.p0 = Spad / (2 * TS);
-    int rc = launch_gemm<T, OP_PRED_U, 128>(st, g, g.p0 * g.nb, cw.q);
+    int rc = launch_pred<T, OP_PRED_U>(st, E, M, G, slab, cw.mat, n0pad, Spad, n0pad / TS, cw.q);
     if (rc) return rc;
     hipLaunchKernelGGL((draw_out_kernel<T>), dim3((cw.n + 255) / 256, S, cw.q), dim3(256), 0, st, (const T*)G, n0pad, slab, S,
                        cw.n, ghat, ldg, out);

@@ -49,16 +49,15 @@ class HotPathEngine:
         assert all(0 <= k < self.q_total for k in comp_ids)
         self._sched_obj = None       # an _hip.Sched to override the launch schedule (tests / tools); None = defaults
         self.use_plan = True         # the launch plan is built once per schedule (lcgp_plan_build) and passed with every call
-        self._plan_cache = {}        # with_inverse -> host block
+        # slot -> ((n, q), host block): the evaluation's plans (slots True / False = with_inverse, at self.sched), the latest
+        # plan of the joint covariance ('cov') and of the CV folds ('cv') (default schedule)
+        self._plans = {}
         with torch.cuda.device(self.device):
             self.x = torch.as_tensor(x).to(self.device, self.tdtype).contiguous()
             self.Y = torch.as_tensor(Y).to(self.device, self.tdtype).contiguous()
             self.sr = None if sr is None else torch.as_tensor(np.ascontiguousarray(sr, np.float64)).to(
                 self.device, self.tdtype).contiguous()
-            nbytes = C.c_size_t(0)
-            _hip.check(self.lib.lcgp_workspace_bytes(self.dtype, self.n, self.d, self.p, self.q_local, C.byref(nbytes)),
-                       "lcgp_workspace_bytes")
-            self.workspace_bytes = int(nbytes.value)
+            self.workspace_bytes = self._nbytes("lcgp_workspace_bytes", self.dtype, self.n, self.d, self.p, self.q_local)
             # zero-filled, i.e. touched once here: the first evaluation of a fresh engine otherwise pays 30-70 ms of first-touch
             # page mapping for its 3 x q_local matrices inside the optimiser's first step (and the clock words start at zero)
             self.workspace = torch.zeros(self.workspace_bytes, dtype=torch.uint8, device=self.device)
@@ -82,9 +81,7 @@ class HotPathEngine:
             self.partial_dev = torch.zeros(self.pw, dtype=torch.float64, device=self.device)
             self._scratch = None
             self._cov_ws = None          # (n0, workspace) of the joint covariance (form_cov)
-            self._cov_plans = {}         # n0 -> launch plan of its factorisation
             self._cv_ws = None           # ((mmax, F), workspace) of the fold matrices (cv_block)
-            self._cv_plans = {}          # (mmax, q_local F) -> launch plan of their factorisation
         self._theta_last = None
 
     # ------------------------------------------------------------------------------------------------
@@ -101,22 +98,33 @@ class HotPathEngine:
     @sched.setter
     def sched(self, s):
         self._sched_obj = s
-        self._plan_cache = {}        # a plan carries the schedule it was built for
+        self._plans.pop(True, None)  # a plan carries the schedule it was built for (the 'cov' / 'cv' plans: the default one)
+        self._plans.pop(False, None)
 
     def _sched(self):
         return None if self._sched_obj is None else C.byref(self._sched_obj)
 
-    def _build_plan(self, with_inverse):
-        """the launch plan of the factorisation for the current schedule as a numpy byte block (lcgp_plan_build): host-only,
-        a function of (dtype, n, q_local, with_inverse, schedule) and nothing else"""
-        key = bool(with_inverse)
+    def _nbytes(self, entry, *args):
+        """the size one of the library's *_bytes queries (named `entry`) returns for args"""
         nbytes = C.c_size_t(0)
-        _hip.check(self.lib.lcgp_plan_bytes(self.dtype, self.n, self.q_local, int(key), self._sched(), C.byref(nbytes)),
-                   "lcgp_plan_bytes")
-        host = np.zeros(int(nbytes.value), dtype=np.uint8)
-        _hip.check(self.lib.lcgp_plan_build(self.dtype, self.n, self.q_local, int(key), self._sched(),
-                                            C.c_void_p(host.ctypes.data), nbytes), "lcgp_plan_build")
+        _hip.check(getattr(self.lib, entry)(*args, C.byref(nbytes)), entry)
+        return int(nbytes.value)
+
+    def _build_plan(self, n, q, with_inverse, sched):
+        """the launch plan of the factorisation of q matrices of order n as a numpy byte block (lcgp_plan_build): host-only,
+        a function of (dtype, n, q, with_inverse, schedule) and nothing else"""
+        nbytes = self._nbytes("lcgp_plan_bytes", self.dtype, n, q, int(with_inverse), sched)
+        host = np.zeros(nbytes, dtype=np.uint8)
+        _hip.check(self.lib.lcgp_plan_build(self.dtype, n, q, int(with_inverse), sched, C.c_void_p(host.ctypes.data), nbytes),
+                   "lcgp_plan_build")
         return host
+
+    def _cached_plan(self, slot, n, q, with_inverse=False, sched=None):
+        """the plan held in `slot`, rebuilt when (n, q) differ from those it was built for: one plan per slot"""
+        held = self._plans.get(slot)
+        if held is None or held[0] != (n, q):
+            held = self._plans[slot] = ((n, q), self._build_plan(n, q, with_inverse, sched))
+        return held[1]
 
     def plan(self, with_inverse=True):
         """host pointer of the launch plan of the factorisation for the current schedule: planned ONCE (lcgp_plan_build), the
@@ -125,18 +133,14 @@ class HotPathEngine:
         if not self.use_plan:
             return C.c_void_p(0)
         key = bool(with_inverse)
-        if key not in self._plan_cache:
-            self._plan_cache[key] = self._build_plan(key)
-        return C.c_void_p(self._plan_cache[key].ctypes.data)
+        return C.c_void_p(self._cached_plan(key, self.n, self.q_local, key, self._sched()).ctypes.data)
 
     def plan_info(self, with_inverse=True):
         """launches / what the plan leaves behind the factorisation (lcgp_plan_info)"""
         key = bool(with_inverse)
-        host = self._plan_cache.get(key) if self.use_plan else None
-        if host is None:
-            host = self._build_plan(key)        # (use_plan = False: a temporary plan, what the library would plan per call)
-            if self.use_plan:
-                self._plan_cache[key] = host
+        # (use_plan = False: a temporary plan, what the library would plan per call)
+        host = self._cached_plan(key, self.n, self.q_local, key, self._sched()) if self.use_plan else \
+            self._build_plan(self.n, self.q_local, key, self._sched())
         v = [C.c_int(0) for _ in range(2)]
         _hip.check(self.lib.lcgp_plan_info(C.c_void_p(host.ctypes.data), *[C.byref(x) for x in v]), "lcgp_plan_info")
         return dict(zip(("launches", "inverse_done"), (x.value for x in v)))
@@ -206,74 +210,51 @@ class HotPathEngine:
             self._theta_last, np.asarray(theta_rows, np.float64).reshape(self.q_local, self.tw))
 
     # ------------------------------------------------------------------------------------------------
-    def predict_block(self, x0s, same=False):
-        """(2, q_local, n0) float64 DEVICE tensor [ghat; gvar] for standardised x0s, from the factorisation of the last
-        evaluate().  x0 is processed in chunks of PREDICT_CHUNK rows with one engine-owned scratch buffer."""
+    def _predict_chunks(self, x0s, same, grad):
+        """lcgp_predict (grad = False) or lcgp_predict_grad over x0s in chunks of PREDICT_CHUNK rows with the engine's scratch:
+        returns the (2, q_local, n0) block [ghat; gvar] and, with grad, the (2, q_local, n0, d) block [dghat; dgvar].  Every
+        chunk writes its columns of the one result block in place (row stride = n0): no per-chunk temporaries, no
+        device-to-device copies"""
         torch = self.torch
         if self._theta_last is None:
-            raise RuntimeError("predict() needs a preceding evaluate() at the current parameters")
-        x0s = np.ascontiguousarray(x0s, np.float64)
-        n0 = x0s.shape[0]
-        assert x0s.shape[1] == self.d
-        chunk = min(n0, PREDICT_CHUNK)
-        with torch.cuda.device(self.device):
-            x0d = torch.as_tensor(x0s).to(self.device, self.tdtype).contiguous()
-            nbytes = C.c_size_t(0)
-            _hip.check(self.lib.lcgp_predict_scratch_bytes(self.dtype, self.n, self.q_local, chunk, C.byref(nbytes)),
-                       "lcgp_predict_scratch_bytes")
-            if self._scratch is None or self._scratch.numel() < nbytes.value:
-                self._scratch = None
-                self._scratch = torch.empty(int(nbytes.value), dtype=torch.uint8, device=self.device)
-            # ONE (2, q_local, n0) result block; every chunk writes its columns in place (row stride = n0): no per-chunk
-            # temporaries, no device-to-device copies
-            out = torch.empty((2, self.q_local, n0), dtype=torch.float64, device=self.device)
-            ghat, gvar = out[0], out[1]
-            st, xp, srp, thp, wsp, scp = self._stream(), self._p(self.x), self._p(self.sr), self._p(self.theta_dev), \
-                self._p(self.workspace), self._p(self._scratch)
-            for lo in range(0, n0, chunk):
-                m = min(chunk, n0 - lo)
-                # the nugget term only exists when x0 IS the training set (covmat.py:46-51): then n0 == n and the
-                # diagonal of the full cross matrix falls on rows lo .. lo+m of this chunk
-                _hip.check(self.lib.lcgp_predict(st, self.dtype, self.kernel_id, self.n, self.d, self.p, self.q_local, xp, srp, thp, wsp, m,
-                                                 C.c_void_p(x0d.data_ptr() + lo * self.d * x0d.element_size()),
-                                                 (1 + lo) if same else 0, scp,
-                                                 C.c_void_p(ghat.data_ptr() + 8 * lo), C.c_void_p(gvar.data_ptr() + 8 * lo), n0),
-                           "lcgp_predict")
-            return out
-
-    def predict_grad_block(self, x0s):
-        """(block, jac) float64 DEVICE tensors for standardised x0s, from the factorisation of the last evaluate():
-        block (2, q_local, n0) = [ghat; gvar], bitwise predict_block(x0s, same=False); jac (2, q_local, n0, d) = [dghat; dgvar],
-        the derivatives with respect to x0s (lcgp_predict_grad: no nugget term, the gradient of the continuous surface).
-        Chunked like predict_block (PREDICT_CHUNK rows per call) and sharing its scratch."""
-        torch = self.torch
-        if self._theta_last is None:
-            raise RuntimeError("predict_grad() needs a preceding evaluate() at the current parameters")
+            raise RuntimeError("%s() needs a preceding evaluate() at the current parameters" % ("predict_grad" if grad else "predict"))
         x0s = np.ascontiguousarray(x0s, np.float64)
         n0, d = x0s.shape[0], self.d
         assert x0s.ndim == 2 and x0s.shape[1] == d and n0 >= 1
         chunk = min(n0, PREDICT_CHUNK)
         with torch.cuda.device(self.device):
             x0d = torch.as_tensor(x0s).to(self.device, self.tdtype).contiguous()
-            nbytes = C.c_size_t(0)
-            _hip.check(self.lib.lcgp_predict_grad_scratch_bytes(self.dtype, self.n, self.q_local, chunk, C.byref(nbytes)),
-                       "lcgp_predict_grad_scratch_bytes")
-            if self._scratch is None or self._scratch.numel() < nbytes.value:
-                self._scratch = None
-                self._scratch = torch.empty(int(nbytes.value), dtype=torch.uint8, device=self.device)
+            # (lcgp_predict_grad_scratch_bytes is lcgp_predict_scratch_bytes; unchecked: PREDICT_CHUNK bounds it)
+            scp = self._p(self._grow_scratch(self._nbytes("lcgp_predict_scratch_bytes", self.dtype, self.n, self.q_local, chunk)))
             out = torch.empty((2, self.q_local, n0), dtype=torch.float64, device=self.device)
-            jac = torch.empty((2, self.q_local, n0, d), dtype=torch.float64, device=self.device)
-            st, xp, srp, thp, wsp, scp = self._stream(), self._p(self.x), self._p(self.sr), self._p(self.theta_dev), \
-                self._p(self.workspace), self._p(self._scratch)
+            jac = torch.empty((2, self.q_local, n0, d), dtype=torch.float64, device=self.device) if grad else None
+            st, xp, srp, thp, wsp = self._stream(), self._p(self.x), self._p(self.sr), self._p(self.theta_dev), self._p(self.workspace)
             for lo in range(0, n0, chunk):
                 m = min(chunk, n0 - lo)
-                _hip.check(self.lib.lcgp_predict_grad(st, self.dtype, self.kernel_id, self.n, d, self.p, self.q_local, xp, srp, thp,
-                                                      wsp, m, C.c_void_p(x0d.data_ptr() + lo * d * x0d.element_size()), scp,
-                                                      C.c_void_p(out[0].data_ptr() + 8 * lo), C.c_void_p(out[1].data_ptr() + 8 * lo),
-                                                      C.c_void_p(jac[0].data_ptr() + 8 * lo * d),
-                                                      C.c_void_p(jac[1].data_ptr() + 8 * lo * d), n0),
-                           "lcgp_predict_grad")
-            return out, jac
+                x0p = C.c_void_p(x0d.data_ptr() + lo * d * x0d.element_size())
+                gh, gv = C.c_void_p(out[0].data_ptr() + 8 * lo), C.c_void_p(out[1].data_ptr() + 8 * lo)
+                if grad:
+                    _hip.check(self.lib.lcgp_predict_grad(st, self.dtype, self.kernel_id, self.n, d, self.p, self.q_local, xp, srp,
+                                                          thp, wsp, m, x0p, scp, gh, gv, C.c_void_p(jac[0].data_ptr() + 8 * lo * d),
+                                                          C.c_void_p(jac[1].data_ptr() + 8 * lo * d), n0), "lcgp_predict_grad")
+                else:
+                    # the nugget term only exists when x0 IS the training set (covmat.py:46-51): then n0 == n and the
+                    # diagonal of the full cross matrix falls on rows lo .. lo+m of this chunk
+                    _hip.check(self.lib.lcgp_predict(st, self.dtype, self.kernel_id, self.n, d, self.p, self.q_local, xp, srp, thp,
+                                                     wsp, m, x0p, (1 + lo) if same else 0, scp, gh, gv, n0), "lcgp_predict")
+            return (out, jac) if grad else out
+
+    def predict_block(self, x0s, same=False):
+        """(2, q_local, n0) float64 DEVICE tensor [ghat; gvar] for standardised x0s, from the factorisation of the last
+        evaluate().  x0 is processed in chunks of PREDICT_CHUNK rows with one engine-owned scratch buffer."""
+        return self._predict_chunks(x0s, same, False)
+
+    def predict_grad_block(self, x0s):
+        """(block, jac) float64 DEVICE tensors for standardised x0s, from the factorisation of the last evaluate():
+        block (2, q_local, n0) = [ghat; gvar], bitwise predict_block(x0s, same=False); jac (2, q_local, n0, d) = [dghat; dgvar],
+        the derivatives with respect to x0s (lcgp_predict_grad: no nugget term, the gradient of the continuous surface).
+        Chunked like predict_block (PREDICT_CHUNK rows per call) and sharing its scratch."""
+        return self._predict_chunks(x0s, False, True)
 
     def predict_device(self, x0s, same=False):
         """ghat, gvar (q_local, n0): the two halves of predict_block()"""
@@ -285,36 +266,41 @@ class HotPathEngine:
         return ghat.cpu().numpy(), gvar.cpu().numpy()
 
     # ------------------------------------------------------------------------------------------------
-    def _cov_workspace(self, n0):
-        """the second workspace, carved for n = n0, whose matrix slot receives Sigma_k + tau_k I (lcgp_predict_cov) and then
-        its factor (lcgp_potrf_logdet); cached per n0 like the predict scratch.  3 q_local n0pad^2 elements (n0pad = n0
-        rounded up to 128): at n0 = 4096, q_local = 8 in float64 that is 3.2 GB -- refused with ValueError beforehand when it
-        does not fit in the free device memory."""
-        torch = self.torch
-        if self._cov_ws is not None and self._cov_ws[0] == n0:
-            return self._cov_ws[1]
-        nbytes = C.c_size_t(0)
-        _hip.check(self.lib.lcgp_workspace_bytes(self.dtype, n0, self.d, self.p, self.q_local, C.byref(nbytes)),
-                   "lcgp_workspace_bytes")
-        self._cov_ws = None
-        self._require_memory(int(nbytes.value), "the joint covariance of %d new inputs" % n0)
-        ws = torch.empty(int(nbytes.value), dtype=torch.uint8, device=self.device)
-        self._cov_ws = (n0, ws)
-        return ws
-
-    def _require_memory(self, nbytes, what):
+    def _require_memory(self, nbytes, what, detail, advice):
+        """ValueError before an allocation of nbytes that does not fit in the free device memory"""
         free, _ = self.torch.cuda.mem_get_info(self.device)
         free += self.torch.cuda.memory_reserved(self.device) - self.torch.cuda.memory_allocated(self.device)
         if nbytes > free:
-            raise ValueError("%s needs %.2f GB of device memory (%d components of n0 x n0, 3 matrices each), %.2f GB are "
-                             "free: pass fewer new inputs" % (what, nbytes / 1e9, self.q_local, free / 1e9))
+            raise ValueError("%s needs %.2f GB of device memory (%s), %.2f GB are free: %s"
+                             % (what, nbytes / 1e9, detail, free / 1e9, advice))
 
-    def _grow_scratch(self, nbytes):
+    def _cov_refusal(self, what):
+        """the free-memory check's text for the joint covariance's buffers"""
+        return what, "%d components of n0 x n0, 3 matrices each" % self.q_local, "pass fewer new inputs"
+
+    def _grow_scratch(self, nbytes, refusal=None):
+        """the engine's one scratch buffer, grown to at least nbytes; with refusal (what, detail, advice) checked against the
+        free device memory before it grows"""
         if self._scratch is None or self._scratch.numel() < nbytes:
             self._scratch = None
-            self._require_memory(nbytes, "the scratch of the joint covariance")
+            if refusal is not None:
+                self._require_memory(nbytes, *refusal)
             self._scratch = self.torch.empty(int(nbytes), dtype=self.torch.uint8, device=self.device)
         return self._scratch
+
+    def _workspace2(self, slot, key, nbytes, refusal):
+        """the second workspace cached in attribute `slot` ('_cov_ws' or '_cv_ws': a model can hold both) as (key, workspace);
+        a new key releases the old one, then nbytes() is checked against the free device memory (refusal: what, detail,
+        advice) and allocated"""
+        held = getattr(self, slot)
+        if held is not None and held[0] == key:
+            return held[1]
+        setattr(self, slot, None)
+        nb = nbytes()
+        self._require_memory(nb, *refusal)
+        ws = self.torch.empty(nb, dtype=self.torch.uint8, device=self.device)
+        setattr(self, slot, (key, ws))
+        return ws
 
     def form_cov(self, x0s, same=False, jitter=0.0):
         """Sigma_k + jitter scale_k I of the local components into the cov workspace for n0 = len(x0s) (lcgp_predict_cov);
@@ -326,11 +312,13 @@ class HotPathEngine:
         n0 = x0s.shape[0]
         assert x0s.ndim == 2 and x0s.shape[1] == self.d and n0 >= 1
         with torch.cuda.device(self.device):
-            cws = self._cov_workspace(n0)
-            nbytes = C.c_size_t(0)
-            _hip.check(self.lib.lcgp_predict_cov_scratch_bytes(self.dtype, self.n, self.q_local, n0, C.byref(nbytes)),
-                       "lcgp_predict_cov_scratch_bytes")
-            scratch = self._grow_scratch(int(nbytes.value))
+            # the second workspace, carved for n = n0, whose matrix slot receives Sigma_k + tau_k I and then its factor
+            # (lcgp_potrf_logdet): 3 q_local n0pad^2 elements (n0pad = n0 rounded up to 128), 3.2 GB at n0 = 4096, q_local = 8
+            # in float64
+            cws = self._workspace2('_cov_ws', n0, lambda: self._nbytes("lcgp_workspace_bytes", self.dtype, n0, self.d, self.p, self.q_local),
+                                   self._cov_refusal("the joint covariance of %d new inputs" % n0))
+            scratch = self._grow_scratch(self._nbytes("lcgp_predict_cov_scratch_bytes", self.dtype, self.n, self.q_local, n0),
+                                         self._cov_refusal("the scratch of the joint covariance"))
             x0d = torch.as_tensor(x0s).to(self.device, self.tdtype).contiguous()
             _hip.check(self.lib.lcgp_predict_cov(self._stream(), self.dtype, self.kernel_id, self.n, self.d, self.p, self.q_local,
                                                  self._p(self.x), self._p(self.sr), self._p(self.theta_dev), self._p(self.workspace),
@@ -360,18 +348,12 @@ class HotPathEngine:
         """factorises Sigma_k + tau_k I in the cov workspace in place (lcgp_potrf_logdet, plan with_inverse = 0); returns the
         per-component info words on the host (0 = positive definite, else 1 + index of the first failing pivot)"""
         torch = self.torch
-        if n0 not in self._cov_plans:
-            nbytes = C.c_size_t(0)
-            _hip.check(self.lib.lcgp_plan_bytes(self.dtype, n0, self.q_local, 0, None, C.byref(nbytes)), "lcgp_plan_bytes")
-            host = np.zeros(int(nbytes.value), dtype=np.uint8)
-            _hip.check(self.lib.lcgp_plan_build(self.dtype, n0, self.q_local, 0, None, C.c_void_p(host.ctypes.data), nbytes),
-                       "lcgp_plan_build")
-            self._cov_plans = {n0: host}
+        plan = self._cached_plan('cov', n0, self.q_local)
         with torch.cuda.device(self.device):
             info = torch.zeros(self.q_local, dtype=torch.int32, device=self.device)
             _hip.check(self.lib.lcgp_potrf_logdet(self._stream(), self.dtype, n0, self.d, self.p, self.q_local,
                                                   self._p(self._cov_ws[1]), None, self._p(info), None,
-                                                  C.c_void_p(self._cov_plans[n0].ctypes.data)), "lcgp_potrf_logdet")
+                                                  C.c_void_p(plan.ctypes.data)), "lcgp_potrf_logdet")
             return info.cpu().numpy()
 
     def sample_latent(self, x0s, S, seeds, jitter=1e-10, same=False):
@@ -397,10 +379,8 @@ class HotPathEngine:
             out = torch.empty((self.q_local, S, n0), dtype=torch.float64, device=self.device)
             for lo in range(0, S, SAMPLE_CHUNK):
                 m = min(SAMPLE_CHUNK, S - lo)
-                nbytes = C.c_size_t(0)
-                _hip.check(self.lib.lcgp_sample_scratch_bytes(self.dtype, n0, self.q_local, m, C.byref(nbytes)),
-                           "lcgp_sample_scratch_bytes")
-                scratch = self._grow_scratch(int(nbytes.value))
+                scratch = self._grow_scratch(self._nbytes("lcgp_sample_scratch_bytes", self.dtype, n0, self.q_local, m),
+                                             self._cov_refusal("the scratch of the joint covariance"))
                 eps = torch.as_tensor(np.ascontiguousarray(eps_all[:, lo:lo + m])).to(self.device, self.tdtype).contiguous()
                 dst = out if m == S else torch.empty((self.q_local, m, n0), dtype=torch.float64, device=self.device)
                 _hip.check(self.lib.lcgp_sample_latent(self._stream(), self.dtype, n0, self.d, self.p, self.q_local, m,
@@ -439,37 +419,6 @@ class HotPathEngine:
             err.info = codes
             raise err
 
-    def _cv_workspace(self, mmax, F, folds_host):
-        """the fold workspace (lcgp_cv_workspace_bytes: carved for n = mmax and q_local * F components), cached per (mmax, F)
-        like the joint-covariance workspace: 3 q_local F mpad^2 elements (mpad = mmax rounded up to 128) -- ValueError
-        beforehand when that does not fit in the free device memory"""
-        if self._cv_ws is not None and self._cv_ws[0] == (mmax, F):
-            return self._cv_ws[1]
-        nbytes = C.c_size_t(0)
-        _hip.check(self.lib.lcgp_cv_workspace_bytes(self.dtype, self.n, self.d, self.p, self.q_local, F,
-                                                    C.c_void_p(folds_host.ctypes.data), C.byref(nbytes)), "lcgp_cv_workspace_bytes")
-        self._cv_ws = None
-        free, _ = self.torch.cuda.mem_get_info(self.device)
-        free += self.torch.cuda.memory_reserved(self.device) - self.torch.cuda.memory_allocated(self.device)
-        if nbytes.value > free:
-            raise ValueError("cross-validation over %d folds of up to %d inputs needs %.2f GB of device memory (%d components x %d "
-                             "folds, 3 matrices each), %.2f GB are free: use fewer or smaller folds"
-                             % (F, mmax, nbytes.value / 1e9, self.q_local, F, free / 1e9))
-        ws = self.torch.empty(int(nbytes.value), dtype=self.torch.uint8, device=self.device)
-        self._cv_ws = ((mmax, F), ws)
-        return ws
-
-    def _cv_plan(self, mmax, qf):
-        key = (mmax, qf)
-        if key not in self._cv_plans:
-            nbytes = C.c_size_t(0)
-            _hip.check(self.lib.lcgp_plan_bytes(self.dtype, mmax, qf, 0, None, C.byref(nbytes)), "lcgp_plan_bytes")
-            host = np.zeros(int(nbytes.value), dtype=np.uint8)
-            _hip.check(self.lib.lcgp_plan_build(self.dtype, mmax, qf, 0, None, C.c_void_p(host.ctypes.data), nbytes),
-                       "lcgp_plan_build")
-            self._cv_plans = {key: host}
-        return C.c_void_p(self._cv_plans[key].ctypes.data)
-
     def cv_block(self, fold_ptr, fold_idx, return_cov=False):
         """(2, q_local, n) float64 DEVICE tensor [ghat; gvar]: the prediction at the inputs of each fold of the model conditioned
         on the other folds (lcgp_cv_gather -> lcgp_potrf_logdet -> lcgp_potri -> lcgp_cv_apply).  fold_ptr (F + 1) / fold_idx
@@ -486,7 +435,12 @@ class HotPathEngine:
         mmax = int(sizes.max()) if F >= 1 else 0
         qf = self.q_local * F
         with torch.cuda.device(self.device):
-            cws = self._cv_workspace(mmax, F, folds_host)
+            # the fold workspace (carved for n = mmax and q_local F components): 3 q_local F mpad^2 elements (mpad = mmax rounded
+            # up to 128)
+            cws = self._workspace2('_cv_ws', (mmax, F), lambda: self._nbytes("lcgp_cv_workspace_bytes", self.dtype, self.n, self.d, self.p,
+                                                                         self.q_local, F, C.c_void_p(folds_host.ctypes.data)),
+                                   ("cross-validation over %d folds of up to %d inputs" % (F, mmax),
+                                    "%d components x %d folds, 3 matrices each" % (self.q_local, F), "use fewer or smaller folds"))
             folds = torch.as_tensor(folds_host).to(self.device)
             hp = C.c_void_p(folds_host.ctypes.data)
             st = self._stream()
@@ -494,7 +448,7 @@ class HotPathEngine:
                                                self._p(folds), self._p(cws)), "lcgp_cv_gather")
             info = torch.zeros(qf, dtype=torch.int32, device=self.device)
             _hip.check(self.lib.lcgp_potrf_logdet(st, self.dtype, mmax, self.d, self.p, qf, self._p(cws), None, self._p(info), None,
-                                                  self._cv_plan(mmax, qf)), "lcgp_potrf_logdet")
+                                                  C.c_void_p(self._cached_plan('cv', mmax, qf).ctypes.data)), "lcgp_potrf_logdet")
             _hip.check(self.lib.lcgp_potri(st, self.dtype, mmax, self.d, self.p, qf, self._p(cws), None), "lcgp_potri")
             out = torch.empty((2, self.q_local, self.n), dtype=torch.float64, device=self.device)
             _hip.check(self.lib.lcgp_cv_apply(st, self.dtype, self.n, self.d, self.p, self.q_local, self._p(self.sr),

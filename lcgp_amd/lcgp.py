@@ -58,7 +58,7 @@ class _PredictFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x0, model):
         ghat, gvar, dghat, dgvar = model._latent_predict_grad(x0.detach().cpu().to(torch.float64))
-        outs = model._outputs_rep(ghat, gvar) if model.submethod == 'rep' else model._outputs_full(ghat, gvar)
+        outs = model._outputs(ghat, gvar)
         dyp, dycv = model._output_jacobians(dghat, dgvar)
         ctx.x0_dtype, ctx.x0_device, ctx.x0_shape = x0.dtype, x0.device, x0.shape
         ctx.jac = (torch.as_tensor(dyp), torch.as_tensor(dycv))
@@ -442,6 +442,11 @@ class LCGP:
             self._path_consts()
         return self._engine
 
+    def _ensure_engine64(self):
+        """creates the float64 engine behind a float32 model's fallback if it is missing (none on a rank without components)"""
+        if self._engine64 is None and self._get_engine() is not None:
+            self._engine64 = self._make_engine('float64')
+
     def _path_consts(self):
         """Parameter-independent pieces of the objective."""
         rank, world = _dist.rank_world(self._group)
@@ -570,8 +575,7 @@ class LCGP:
             # The float32 factorisation broke down (I + D_k C_k has a condition number beyond single precision somewhere
             # along a line search; the reference is float64 only).  The point is evaluated again in float64 -- on every
             # rank: info was all-reduced -- so the optimiser sees the objective there instead of an artificial value.
-            if self._engine64 is None and eng is not None:
-                self._engine64 = self._make_engine('float64')
+            self._ensure_engine64()
             self.float32_fallbacks += 1
             vec = reduced(self._engine64)
             self._last_eval_float64 = True
@@ -631,11 +635,10 @@ class LCGP:
         u0 = self._get_flat()
         last = []
         self._f32_consecutive = 0          # (a run of float64 repeats does not carry over from an earlier fit)
-        if self._dtype == 'float32' and self.float32_fallback and not self._float64_only and self._engine64 is None:
+        if self._dtype == 'float32' and self.float32_fallback and not self._float64_only:
             # the float64 engine behind the fallback is created BEFORE the optimiser starts: if its workspace does not fit,
             # that surfaces here, on every rank, and not in the middle of a run that has already made progress
-            self._get_engine()
-            self._engine64 = self._make_engine('float64')
+            self._ensure_engine64()
 
         def fun(u):
             try:
@@ -765,78 +768,44 @@ class LCGP:
 
     def _latent_predict(self, x0):
         """ghat, gvar (q, n0) for raw-scale x0 (lcgp.py:822-838 / 877-900): the local components' rows are computed
-        and placed on the device, ONE all-reduce of the zero-padded (2, q, n0) block gathers them, one D2H copy."""
+        on the device, ONE reduction of the zero-padded block gathers them (_gather_components)."""
+        x0s, same = self._standardise_x0(x0)
         eng = self._ensure_aux()
-        x0n = _np(x0)
-        x0s = (x0n - _np(self.x_min)) / (_np(self.x_max) - _np(self.x_min))
-        xtrain = _np(self.x_unique_s if self.submethod == 'rep' else self.x)
-        # the nugget is added iff x0 and the training inputs agree in shape and value (covmat.py:46-51)
-        same = (x0s.shape == xtrain.shape) and bool(np.all(x0s == xtrain))
-        n0, q = x0s.shape[0], int(self.q)
-        if eng is not None and not _dist.use_collectives(self._group):
-            both = eng.predict_block(x0s, same).cpu().numpy()
-        else:
-            full = self._zeros_on_device((2, q, n0))
-            if eng is not None:
-                gh, gv = eng.predict_device(x0s, same)
-                idx = torch.as_tensor(self._local_ks, dtype=torch.long, device=full.device)
-                full[0].index_copy_(0, idx, gh.to(full.device))
-                full[1].index_copy_(0, idx, gv.to(full.device))
-            both = _dist.reduce_to_host(full, self._group)      # disjoint rows: a sum is a gather
-        ghat, gvar = both[0], both[1]
+        loc = None if eng is None else eng.predict_block(x0s, same).permute(1, 0, 2)      # (q_local, 2, n0)
+        both = self._gather_components(loc, (2, x0s.shape[0]))
+        ghat, gvar = both[:, 0], both[:, 1]
         self.ghat, self.gvar = _t(ghat), _t(gvar)
         return ghat, gvar
 
     def predict_full(self, x0, return_fullcov=False):
         """lcgp.py:808-859."""
-        ghat, gvar = self._latent_predict(x0)
-        return self._outputs_full(ghat, gvar, return_fullcov)
-
-    def _outputs_full(self, ghat, gvar, return_fullcov=False):
-        """predict_full's map from latent (ghat, gvar) (q, n0) to (ypred, ypredvar, yconfvar[, cov])"""
-        ls2_b = _np(self.get_param()[2])
-        phi = _np(self.phi)
-        ystd, ymean = _np(self.ystd), _np(self.ymean)
-        psi = phi.T * np.sqrt(np.exp(ls2_b))
-        predmean = psi.T @ ghat
-        confvar = gvar.T @ psi ** 2
-        predvar = confvar + np.exp(ls2_b)
-        ypred = predmean * ystd + ymean
-        yconfvar = confvar.T * ystd ** 2
-        ypredvar = predvar.T * ystd ** 2
-        if return_fullcov:
-            ch = np.einsum('kn,kp->npk', np.sqrt(gvar), psi)
-            cov = ch @ np.transpose(ch, (0, 2, 1)) + np.diag(np.exp(ls2_b))[None, ...]
-            sv = ystd[:, 0]
-            cov = cov * (sv[:, None] * sv[None, :])[None, ...]
-            return _t(ypred), _t(ypredvar), _t(yconfvar), _t(cov)
-        return _t(ypred), _t(ypredvar), _t(yconfvar)
+        return self._outputs(*self._latent_predict(x0), return_fullcov)
 
     def predict_rep(self, x0, return_fullcov=False):
         """lcgp.py:864-930."""
-        ghat, gvar = self._latent_predict(x0)
-        return self._outputs_rep(ghat, gvar, return_fullcov)
+        return self._outputs(*self._latent_predict(x0), return_fullcov)
 
-    def _outputs_rep(self, ghat, gvar, return_fullcov=False):
-        """predict_rep's map from latent (ghat, gvar) (q, n0) to (ypred, ypredvar, yconfvar[, None])"""
-        ls2_b = _np(self.get_param()[2])
-        phi = _np(self.phi)
-        use_std = getattr(self, "rep_standardize_ybar", True)
-        std = _np(self.ybar_std)[:, 0] if use_std else np.ones(int(self.p), F64)
-        s_sqrt = np.sqrt(np.exp(ls2_b)) / std
-        s_var = np.exp(ls2_b) / std ** 2
-        Psi = phi * s_sqrt[:, None]
-        pm = Psi @ ghat
-        cv = (Psi ** 2) @ gvar
-        pv = cv + s_var[:, None]
-        if use_std:
-            ybs, ybm = _np(self.ybar_std), _np(self.ybar_mean)
-            ypred, yconfvar, ypredvar = pm * ybs + ybm, cv * ybs ** 2, pv * ybs ** 2
-        else:
-            ypred, yconfvar, ypredvar = pm, cv, pv
-        if return_fullcov:
+    def _outputs(self, ghat, gvar, return_fullcov=False):
+        """latent (ghat, gvar) (q, n0) -> (ypred, ypredvar, yconfvar[, cov]) through _output_map(); cov is the (n0, p, p)
+        output covariance on the full path and None on the rep path (lcgp.py:840-858 / 906-930)"""
+        W, noise, scale, offset = self._output_map()
+        predmean = W.T @ ghat
+        confvar = gvar.T @ W ** 2
+        predvar = confvar + noise
+        ypred = predmean * scale[:, None] + offset[:, None]
+        yconfvar = confvar.T * (scale ** 2)[:, None]
+        ypredvar = predvar.T * (scale ** 2)[:, None]
+        if not return_fullcov:
+            return _t(ypred), _t(ypredvar), _t(yconfvar)
+        if self.submethod == 'rep':
             return _t(ypred), _t(ypredvar), _t(yconfvar), None
-        return _t(ypred), _t(ypredvar), _t(yconfvar)
+        ch = np.einsum('kn,kp->npk', np.sqrt(gvar), W)
+        cov = ch @ np.transpose(ch, (0, 2, 1)) + np.diag(noise)[None, ...]
+        cov = cov * (scale[:, None] * scale[None, :])[None, ...]
+        return _t(ypred), _t(ypredvar), _t(yconfvar), _t(cov)
+
+    # the map's names per path, kept for callers of the earlier two-function form
+    _outputs_full = _outputs_rep = _outputs
 
     # =============================================================================================
     # joint posterior covariance over new inputs and correlated draws (beyond the reference: its predict is marginal only)
@@ -845,23 +814,25 @@ class LCGP:
         """x0 on the raw scale -> standardised x0 and whether it IS the training set (the nugget of the cross covariance)"""
         x0n = _np(self._verify_data_types(x0))
         x0s = (x0n - _np(self.x_min)) / (_np(self.x_max) - _np(self.x_min))
-        xtrain = _np(self.x_unique_s if self.submethod == 'rep' else self.x)
+        xtrain = self._x_train()
         same = (x0s.shape == xtrain.shape) and bool(np.all(x0s == xtrain))
         return x0s, same
 
+    def _x_train(self):
+        """the standardised training inputs the engine holds: the unique inputs on the rep path"""
+        return _np(self.x_unique_s if self.submethod == 'rep' else self.x)
+
     def _output_map(self):
-        """(W, noise, scale, offset) with which predict_full / predict_rep turn latent (ghat, gvar) into outputs:
-        mean_a = offset_a + scale_a sum_k W[k, a] g_k, noise variance scale_a^2 noise_a (same expressions as there)"""
+        """(W, noise, scale, offset) with which _outputs turns latent (ghat, gvar) into outputs, the one place that knows the
+        full / rep difference: mean_a = offset_a + scale_a sum_k W[k, a] g_k, noise variance scale_a^2 noise_a"""
         ls2_b = _np(self.get_param()[2])
         phi = _np(self.phi)
         p = int(self.p)
         if self.submethod == 'rep':
             use_std = getattr(self, "rep_standardize_ybar", True)
-            std = _np(self.ybar_std)[:, 0] if use_std else np.ones(p, F64)
-            s_sqrt = np.sqrt(np.exp(ls2_b)) / std
-            W = (phi * s_sqrt[:, None]).T
-            noise = np.exp(ls2_b) / std ** 2
             scale = _np(self.ybar_std)[:, 0] if use_std else np.ones(p, F64)
+            W = (phi * (np.sqrt(np.exp(ls2_b)) / scale)[:, None]).T
+            noise = np.exp(ls2_b) / scale ** 2
             offset = _np(self.ybar_mean)[:, 0] if use_std else np.zeros(p, F64)
         else:
             W = phi.T * np.sqrt(np.exp(ls2_b))
@@ -901,7 +872,7 @@ class LCGP:
 
     def _gather_components(self, loc, shape):
         """(q, *shape) numpy array from this rank's (q_local, *shape) device tensor: ONE reduction of a zero-padded block
-        (disjoint components: a sum is a gather), as _latent_predict does"""
+        (disjoint components: a sum is a gather)"""
         if not _dist.use_collectives(self._group):
             return loc.cpu().numpy()
         full = self._zeros_on_device((int(self.q),) + tuple(shape))
@@ -981,7 +952,7 @@ class LCGP:
     # =============================================================================================
     def _cv_labels(self, folds, seed):
         """fold labels (n,) over the training inputs (the unique inputs on the rep path) -> (labels, fold_ptr, fold_idx)"""
-        n = int(self.x_unique_s.shape[0]) if self.submethod == 'rep' else int(self.n)
+        n = self._cv_n()
         if np.ndim(folds) == 0:
             if isinstance(folds, (bool, np.bool_)) or not float(folds).is_integer():
                 raise ValueError('folds must be an int F or an array of %d integer labels' % n)
@@ -1020,8 +991,7 @@ class LCGP:
             if not (self._dtype == 'float32' and self.float32_fallback) or self._last_eval_float64:
                 raise
         # float32 gave up: the float64 engine evaluates the current parameters (every rank: the failure was agreed on)
-        if self._engine64 is None and self._get_engine() is not None:
-            self._engine64 = self._make_engine('float64')
+        self._ensure_engine64()
         self.float32_fallbacks += 1
         only = self._float64_only
         self._float64_only = True
@@ -1031,13 +1001,6 @@ class LCGP:
             self._float64_only = only
         eng = self._aux_engine if self._engine64 is not None else None
         return self._agree(lambda: None if eng is None else fn(eng), failure=failure + ', in float64 either'), eng
-
-    def _cv_outputs(self, both):
-        """(q, 2, n) latent [ghat; gvar] per component -> predict's outputs (the same map, unchanged)"""
-        ghat, gvar = both[:, 0], both[:, 1]
-        if self.submethod == 'rep':
-            return self._outputs_rep(ghat, gvar)
-        return self._outputs_full(ghat, gvar)
 
     def predict_loo(self):
         """Leave-one-out predictions (ypred, ypredvar, yconfvar), each (p, n) -- (p, n_unique) on the rep path -- at FIXED
@@ -1052,10 +1015,11 @@ class LCGP:
         n = self._cv_n()
         blk, _ = self._cv_latent(lambda e: e.loo_block())
         loc = None if blk is None else blk.permute(1, 0, 2)              # (q_local, 2, n)
-        return self._cv_outputs(self._gather_components(loc, (2, n)))
+        both = self._gather_components(loc, (2, n))
+        return self._outputs(both[:, 0], both[:, 1])
 
     def _cv_n(self):
-        return int(self.x_unique_s.shape[0]) if self.submethod == 'rep' else int(self.n)
+        return self._x_train().shape[0]
 
     def predict_cv(self, folds, seed=0, return_latent_cov=False):
         """k-fold cross-validation predictions (ypred, ypredvar, yconfvar), each (p, n) -- (p, n_unique) on the rep path --
@@ -1081,7 +1045,8 @@ class LCGP:
         width = 2 * n + (int(np.sum(sizes * sizes)) if return_latent_cov else 0)
         flat = self._gather_components(loc, (width,))
         self.cv_labels = labels
-        outs = self._cv_outputs(flat[:, :2 * n].reshape(q, 2, n))
+        both = flat[:, :2 * n].reshape(q, 2, n)
+        outs = self._outputs(both[:, 0], both[:, 1])
         if not return_latent_cov:
             return outs
         lat, off = [], 2 * n

@@ -316,6 +316,44 @@ int lcgp_cv_apply(void* stream, int dtype, int n, int d, int p, int q_local, con
                   const void* workspace, int F, const int* folds_host, const int* folds, const void* cv_workspace,
                   double* ghat, double* gvar, int out_stride);
 
+/* Integrated variance reduction at fixed parameters (the active-learning-Cohn criterion, ALC / IMSPE reduction; no counterpart
+ * in the reference).  Input: the workspace of the last lcgp_nll_grad, as for lcgp_predict.  With X_k = c0k o sr^T and
+ * U_k = X_k L_k^-T exactly as in lcgp_predict, for local component k, reference point t and candidate c (both standardised):
+ *     out[k, c]       = sum_t w_t Sigma_k(t, c)^2 / (max(Sigma_k^h(c, c), 0) + 1 / (D_k r))
+ *     Sigma_k(t, c)   = C_k(t, c) - D_k U_k(t) . U_k(c)      C_k without nugget: reference points are new inputs (same = 0)
+ *     Sigma_k^h(c, c) = scale_k - D_k |U_k(c)|^2             = lcgp_predict's gvar at c with the candidate's own cross row
+ * i.e. the drop of sum_t w_t gvar_k(t) if the training set were augmented by r replicates at c (same theta, A refactorised).
+ * A candidate's cross row has no nugget term unless match[c] = i >= 0: c IS training input i (the replicated path: it adds r
+ * replicates to input i) and the term scale_k nug sr_i goes to column i (lcgp_predict's `same` convention, per row).
+ * The caller normalises w; reference rows beyond n_ref count with weight 0.
+ *
+ *   1. lcgp_variance_reduction_prepare forms U_k and gvar_k of the n_ref reference points into `scratch` (the reference part).
+ *   2. lcgp_variance_reduction, once per chunk of candidates, reads that part: it forms U_k and gvar_k of the candidates (or,
+ *      with cand_row0 >= 0, takes rows cand_row0 .. cand_row0 + n_cand - 1 of the reference set's: the candidates ARE those
+ *      reference points; x_cand, match_host and match are then NULL), then runs ONE launch of the MFMA tile kernel over the
+ *      (reference tile, candidate tile) pairs whose epilogue recomputes C_k from x_ref / x_cand, forms Sigma_k and reduces
+ *      w_t Sigma_k^2 / den_c over the tile's rows (the n_ref x n_cand matrix never reaches memory), and a reduction over the
+ *      reference tiles in ascending order (no atomics).  out: q_local rows of n_cand doubles, `out_stride` apart (0 = n_cand).
+ *      Bitwise independent of q_local and of how candidates are split over calls.  Products in the dtype, sums in double.
+ *   match_host / match: the same n_cand ints (host, checked before anything is enqueued; device, read by the kernels), each -1
+ *      or a training index in [0, n); both NULL = no matches.  w_ref: n_ref doubles (device).  r >= 1.
+ * scratch: lcgp_variance_reduction_scratch_bytes(dtype, n, q_local, n_ref, n_cand) bytes -- q_local (n_ref + n_cand) npad
+ *   elements for the two U plus X work areas of at most 2048 rows each and q_local ceil(n_ref / 64) n_cand doubles of partial
+ *   sums; a scratch sized for n_cand serves calls with fewer candidates.  Its content on entry to step 1 is irrelevant; step 2
+ *   reads the reference part step 1 wrote (same n, q_local, theta, workspace, n_ref, x_ref) and writes everything else it reads.
+ * Flops per component: n_refpad npad^2 (U of the reference set, once; 2 per multiply-add over the lower triangle of L^-1) +
+ *   n_candpad npad^2 (U of the candidates, unless cand_row0 >= 0) + 2 n_ref64 n_cand64 npad (the fused product); n_refpad /
+ *   n_candpad: rounded up to 128 (to 64 below 128), n_ref64 / n_cand64: rounded up to 64. */
+int lcgp_variance_reduction_scratch_bytes(int dtype, int n, int q_local, int n_ref, int n_cand, size_t* bytes /*host out*/);
+int lcgp_variance_reduction_prepare(void* stream, int dtype, int kernel_id, int n, int d, int p, int q_local,
+                                    const void* x, const void* sr, const double* theta, const void* workspace,
+                                    int n_ref, const void* x_ref, void* scratch);
+int lcgp_variance_reduction(void* stream, int dtype, int kernel_id, int n, int d, int p, int q_local,
+                            const void* x, const void* sr, const double* theta, const void* workspace,
+                            int n_ref, const void* x_ref, const double* w_ref,
+                            int n_cand, const void* x_cand, const int* match_host /*host or NULL*/, const int* match,
+                            int cand_row0, int r, void* scratch, double* out, int out_stride);
+
 #ifdef __cplusplus
 }
 #endif

@@ -67,6 +67,10 @@ SIGNATURES = {
     "lcgp_cv_workspace_bytes": (_i, [_i, _i, _i, _i, _i, _i, _vp, C.POINTER(C.c_size_t)]),
     "lcgp_cv_gather": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp]),
     "lcgp_cv_apply": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i]),
+    "lcgp_variance_reduction_scratch_bytes": (_i, [_i, _i, _i, _i, _i, C.POINTER(C.c_size_t)]),
+    "lcgp_variance_reduction_prepare": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
+    "lcgp_variance_reduction": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _i,
+                                     _vp, _vp, _i]),
 }
 
 _lib = None

@@ -23,7 +23,7 @@
 #include "../../include/lcgp_hip.h"
 #include "fill_sched.h"
 
-#define LCGP_VERSION 540
+#define LCGP_VERSION 550
 
 namespace {
 
@@ -356,7 +356,9 @@ __global__ __launch_bounds__(256) void cross_kernel(T* __restrict__ out, int ldo
                                                     ThetaArg tv, const double* __restrict__ thp /*ell[d], scale, nug*/,
                                                     int same, const T* __restrict__ colscale, int n1pad, int n2pad,
                                                     int th_stride /*doubles between the theta rows of components*/,
-                                                    size_t out_stride /*elements between the output slabs*/) {
+                                                    size_t out_stride /*elements between the output slabs*/,
+                                                    const int* __restrict__ match /*per row of x1: the column of its nugget
+                                                                                    term, -1 = none; NULL: `same` decides*/) {
     __shared__ double xr[TS][DMAX + 1];
     __shared__ double xc[TS][DMAX + 1];
     __shared__ double cs[TS];
@@ -411,7 +413,9 @@ __global__ __launch_bounds__(256) void cross_kernel(T* __restrict__ out, int ldo
         double v = 0.0;
         if (gi < n1 && gj < n2) {
             double c0 = fmin(poly[m], poly_cap<double>()) * exp_nonpos(ssum[m]);
-            double dl = (same && gi + (same - 1) == gj) ? 1.0 : 0.0;   // same = 1 + row offset of x1 within x2
+            // same = 1 + row offset of x1 within x2; match: row gi is training input match[gi] (a replicate of it)
+            const bool on = match ? match[gi] == gj : (same && gi + (same - 1) == gj);
+            double dl = on ? 1.0 : 0.0;
             v = scale * ((1.0 - nt) * c0 + nt * dl) * cs[j];
         }
         out[(size_t)gi * ldo + gj] = (T)v;
@@ -713,7 +717,7 @@ __global__ __launch_bounds__(256, 2) void leaf_kernel(T* __restrict__ M, T* __re
 //   MK : element (m, k) at P[m * ld + k]      KM : element (m, k) at P[k * ld + m]
 // and staged in LDS as [k][m] (KT = 16 k rows per stage, double buffered through registers).
 // ---------------------------------------------------------------------------------------------------
-enum GemmOp { OP_SYRK = 1, OP_TRTRI_T = 2, OP_TRTRI_W = 3, OP_LAUUM = 4, OP_PRED_U = 5, OP_PRED_COV = 6, OP_PRED_V = 7 };
+enum GemmOp { OP_SYRK = 1, OP_TRTRI_T = 2, OP_TRTRI_W = 3, OP_LAUUM = 4, OP_PRED_U = 5, OP_PRED_COV = 6, OP_PRED_V = 7, OP_VR = 8 };
 enum Lay { MK = 0, KM = 1 };
 
 struct GemmArgs {
@@ -731,6 +735,16 @@ struct GemmArgs {
     unsigned long long* clk = nullptr;          // OP_LAUUM: the first block (the longest K loop of the launch) leaves its duration
                                                 // in shader-clock cycles and in 10 ns ticks here: the clock the chip held (lcgp_lauum_clock)
     const double* theta = nullptr;              // OP_PRED_COV: theta rows, p1 doubles apart; D_k is element p2 of row k
+                                                // (OP_VR: rows tw apart)
+    // OP_VR (the variance-reduction epilogue; see vr_epilogue): standardised inputs of the A rows (reference set) and of the
+    // B rows (candidates), d per row; the weights of the reference rows; the candidates' gvar (ldg per component); the covariance
+    // kernel, theta row width, replicates r and the row length of the partial sums (p0 = k tiles, p1 = candidate tiles,
+    // p2 = n_ref, p3 = n_cand)
+    const void* xa = nullptr;
+    const void* xb = nullptr;
+    const double* wref = nullptr;
+    const double* gvc = nullptr;
+    int ldg = 0, d = 0, kern = 0, tw = 0, nrep = 1, ldp = 0;
 };
 
 // one K-stage (KT = 16 k values) of a TM-row operand tile: global -> registers -> LDS [k][m], ld = TM + 16;
@@ -941,6 +955,112 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
     return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + i;
 }
 
+// ---- OP_VR epilogue: integrated variance reduction (lcgp_hip.h: lcgp_variance_reduction) ----
+// For reference tile rt, candidate tile ct and component k the accumulators hold acc[t, c] = U_k(t) . U_k(c); then
+//   sigma(t, c)    = C_k(t, c) - D_k acc[t, c]          C_k without nugget (reference points are new inputs)
+//   part[k, rt, c] = (sum_t w_t sigma^2) / den_c,       den_c = max(gvar_c, 0) + 1 / (D_k r)
+// C_k is recomputed in double from the standardised inputs of the tile's rows and columns, staged in LDS divided by ell
+// (the stage buffers are free behind the k loop) VR_DC dimensions at a time, as cross_kernel forms it.  Row sums in a fixed
+// order: per lane over its registers, then the four lanes 16 apart (they hold the same column: row = (lane >> 4) + 4 reg in
+// fp64, 4 (lane >> 4) + reg in fp32), then the lower pair of waves hands its sums to the upper pair through LDS.
+// Reference rows beyond n_ref carry weight 0; candidate columns beyond n_cand are not written.
+constexpr int VR_DC = 16;
+template <typename T, int KERN, int TM, int MIM, int MIN, typename Acc>
+__device__ __forceinline__ void vr_epilogue(const GemmArgs& g, const Acc (&acc)[MIM][MIN], int k, int rt, int ct, int tid, int wm0,
+                                            int wn0, unsigned char* lds) {
+    static_assert(TM == 64 && MIM == 2 && MIN == 2, "the OP_VR epilogue is written for the 64x64 tile on four waves");
+    constexpr int XL = VR_DC + 1;                   // odd row length: the 16 rows a lane group reads hit distinct banks
+    double* xa = (double*)lds;                      // [TM][XL] reference rows / ell
+    double* xb = xa + TM * XL;                      // [TM][XL] candidate rows / ell
+    double* wr = xb + TM * XL;                      // [TM] weights of the reference rows
+    double* red = wr + TM;                          // [TM] column sums of the waves that own rows 32 .. 63
+    static_assert((2 * TM * XL + 2 * TM) * sizeof(double) <= 4 * KT * (TM + 16) * sizeof(T), "fits the stage buffers");
+    const int lane = tid & 63, l15 = lane & 15, wave = tid >> 6;
+    const int d = g.d;
+    const double* th = g.theta + (size_t)k * g.tw;
+    const double scale = th[d], nug = th[d + 1], D = th[d + 2];
+    const double coff = scale * (1.0 - nug / (1.0 + nug));
+    const T* xra = (const T*)g.xa;
+    const T* xrb = (const T*)g.xb;
+    const int t0 = rt * TM, c0 = ct * TM;
+    __syncthreads();                                // every wave is done with the stage buffers
+    if (tid < TM) wr[tid] = t0 + tid < g.p2 ? g.wref[t0 + tid] : 0.0;
+    double s[MIN];
+#pragma unroll
+    for (int ni = 0; ni < MIN; ++ni) s[ni] = 0.0;
+    const int nch = (d + VR_DC - 1) / VR_DC;
+    // one 16 x 16 accumulator block at a time (four elements per lane): the kernel values of a block are accumulated over all
+    // dimension chunks before the next block starts, so only its four (poly, sum) pairs live beside the accumulators
+#pragma unroll
+    for (int mi = 0; mi < MIM; ++mi)
+#pragma unroll
+        for (int ni = 0; ni < MIN; ++ni) {
+            double pl[4], ss[4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) { pl[e] = 1.0; ss[e] = 0.0; }
+            // (loops over dimensions and staged elements kept rolled: unrolled, the compiler hoists their LDS reads and global
+            // loads ahead of the arithmetic and runs out of the 128 registers four waves per SIMD leave)
+#pragma unroll 1
+            for (int ch = 0; ch < nch; ++ch) {
+                const int d0 = ch * VR_DC, dc = d - d0 < VR_DC ? d - d0 : VR_DC;
+                if (nch > 1 || (mi == 0 && ni == 0)) {      // (one chunk: staged once for all blocks)
+                    if (ch > 0 || mi > 0 || ni > 0) __syncthreads();
+#pragma unroll 1
+                    for (int e = tid; e < TM * VR_DC; e += 256) {
+                        const int i = e / VR_DC, j = e - i * VR_DC;
+                        const int ta = t0 + i, cb = c0 + i;
+                        xa[i * XL + j] = (j < dc && ta < g.p2) ? (double)xra[(size_t)ta * d + d0 + j] / th[d0 + j] : 0.0;
+                        xb[i * XL + j] = (j < dc && cb < g.p3) ? (double)xrb[(size_t)cb * d + d0 + j] / th[d0 + j] : 0.0;
+                    }
+                    __syncthreads();
+                }
+                const double* pa = xa + (wm0 + mi * 16) * XL;
+                const double* pb = xb + (wn0 + ni * 16 + l15) * XL;
+#pragma unroll 1
+                for (int jj = 0; jj < dc; ++jj) {
+                    const double yv = pb[jj];
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const double xv = pa[Mfma<T>::row(lane, e) * XL + jj];
+                        if constexpr (KERN == 0) {
+                            const double sd = fabs(xv - yv);
+                            pl[e] = fma(pl[e], sd, pl[e]);
+                            ss[e] -= sd;
+                        } else {
+                            const double df = xv - yv;
+                            ss[e] = fma(-0.5 * df, df, ss[e]);
+                        }
+                    }
+                }
+            }
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const double c = KERN == 0 ? fmin(pl[e], poly_cap<double>()) * exp_nonpos(ss[e]) : exp_nonpos(ss[e]);
+                const double sg = fma(-D, (double)acc[mi][ni][e], coff * c);
+                s[ni] = fma(wr[wm0 + mi * 16 + Mfma<T>::row(lane, e)] * sg, sg, s[ni]);
+            }
+        }
+#pragma unroll
+    for (int ni = 0; ni < MIN; ++ni) {
+        s[ni] += __shfl_xor(s[ni], 16);
+        s[ni] += __shfl_xor(s[ni], 32);
+    }
+    if (wave >= 2 && lane < 16) {
+#pragma unroll
+        for (int ni = 0; ni < MIN; ++ni) red[wn0 + ni * 16 + l15] = s[ni];
+    }
+    __syncthreads();
+    if (wave < 2 && lane < 16) {
+        const double rd = 1.0 / (D * (double)g.nrep);
+        double* part = (double*)g.C + ((size_t)k * ((g.p2 + TM - 1) / TM) + rt) * g.ldp;
+#pragma unroll
+        for (int ni = 0; ni < MIN; ++ni) {
+            const int cl = wn0 + ni * 16 + l15, c = c0 + cl;
+            if (c < g.p3) part[c] = (s[ni] + red[cl]) / (fmax(g.gvc[(size_t)k * g.ldg + c], 0.0) + rd);
+        }
+    }
+}
+
 // TM x TM output tile per workgroup of NW waves arranged (NW/2) x 2:
 //   TM = 64,  NW = 4: 32x32 per wave (2x2 MFMA accumulators), 4 workgroups per CU
 //   TM = 128, NW = 8: 32x64 per wave (2x4 accumulators), 2 workgroups per CU = 4 waves per SIMD, half the
@@ -1071,6 +1191,14 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& g, const int lin /*blo
         nkt = g.p0;
         Ct = Cb + (size_t)r * TM * g.ldC + (size_t)c * TM;
         accumulate = true;          // (alpha = -D_k is read behind the k loop: nothing more lives across it than in OP_PRED_U)
+    } else if constexpr (OP == OP_VR) {
+        // acc = sum_{kt < p0} U_ref[rt, kt] U_cand[ct, kt]^T over all (reference tile rt, candidate tile ct); C is the partial
+        // buffer, written by the epilogue
+        const int ct = bid % g.p1, rt = bid / g.p1;
+        A0 = Ab + (size_t)rt * TM * g.ldA; dA = TM;
+        B0 = Bb + (size_t)ct * TM * g.ldB; dB = TM;
+        nkt = g.p0;
+        Ct = Cb;
     } else if constexpr (OP == OP_PRED_V) {
         // V[m, c] = sum_{kt = c}^{nb-1} U[m, kt] W[kt, c]      (U = X W^T, n0pad x npad; W lower triangular)
         // k tiles walked from nb-1 DOWN to c, as OP_LAUUM walks its B operand: every tile starts on the last block row of W,
@@ -1136,7 +1264,7 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& g, const int lin /*blo
     // only add exact zeros: it skips the stage's fragment reads and MFMAs (one wave-uniform test per stage, nothing
     // else changes; bit-identical results: the zeros are stored zeros).  LAUUM / TRTRI_W: 24 of the 64 (wave, stage)
     // pairs of such a tile, TRTRI_T / PRED_U / PRED_V: 16.
-    constexpr bool HAS_TRI = OP != OP_SYRK && OP != OP_PRED_COV;
+    constexpr bool HAS_TRI = OP != OP_SYRK && OP != OP_PRED_COV && OP != OP_VR;
     const int tri_first = HAS_TRI ? (nkt - 1) * SPT : nst;
     // the wave is idle in the stages [dead_lo, dead_hi) of the k loop (two scalars per wave)
     int dead_lo = nst, dead_hi = nst;
@@ -1295,6 +1423,12 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& g, const int lin /*blo
             }
         }
     }
+    if constexpr (OP == OP_VR) {
+        const int ct = bid % g.p1, rt = bid / g.p1;
+        if (g.kern == 0) vr_epilogue<T, 0, TM, MIM, MIN>(g, acc, k, rt, ct, tid, wm0, wn0, lds);
+        else vr_epilogue<T, 1, TM, MIM, MIN>(g, acc, k, rt, ct, tid, wm0, wn0, lds);
+        return;
+    }
     if constexpr (OP == OP_PRED_COV) alpha = -g.theta[(size_t)k * g.p1 + g.p2];
 #pragma unroll
     for (int mi = 0; mi < MIM; ++mi)
@@ -1377,8 +1511,10 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& g, const int lin /*blo
     }
 }
 
+// (OP_VR: two workgroups per CU.  Its epilogue -- kernel values, exponentials and row sums beside the accumulators -- needs
+// about 200 registers; at four workgroups per CU (128 registers) both dtypes spilled in it)
 template <typename T, int OP, int TM, int NW>
-__global__ __launch_bounds__(NW * 64, TM == 128 ? (NW == 8 ? 4 : 2) : 4) void tile_gemm(GemmArgs g) {
+__global__ __launch_bounds__(NW * 64, TM == 128 ? (NW == 8 ? 4 : 2) : (OP == OP_VR ? 2 : 4)) void tile_gemm(GemmArgs g) {
     __shared__ __align__(16) unsigned char lds[4 * KT * (TM + 16) * sizeof(T)];
     gemm_body<T, OP, TM, NW>(g, blockIdx.x, lds);
 }
@@ -2420,7 +2556,7 @@ __global__ void fetch_kernel(const T* __restrict__ src, int npad, int n, T* __re
 
 // ghat[k, m] = sum_i X_k[m, i] z_k[i] ;  gvar[k, m] = scale_k - D_k * sum_i U_k[m, i]^2        (one wave per row m)
 template <typename T>
-__global__ __launch_bounds__(64) void pred_reduce_kernel(const T* __restrict__ X, const T* __restrict__ U, size_t slab, int ld,
+__global__ __launch_bounds__(64) void pred_reduce_kernel(const T* __restrict__ X, const T* __restrict__ U, size_t slab, size_t uslab, int ld,
                                                          int n, const T* __restrict__ z, int npad,
                                                          const double* __restrict__ theta, int tw, int d, int ldo,
                                                          double* __restrict__ ghat, double* __restrict__ gvar) {
@@ -2428,7 +2564,7 @@ __global__ __launch_bounds__(64) void pred_reduce_kernel(const T* __restrict__ X
     const double* th = theta + (size_t)k * tw;
     const double scale = th[d], D = th[d + 2];
     const T* Xr = X + (size_t)k * slab + (size_t)m * ld;
-    const T* Ur = U + (size_t)k * slab + (size_t)m * ld;
+    const T* Ur = U + (size_t)k * uslab + (size_t)m * ld;
     const T* zk = z + (size_t)k * npad;
     double s1 = 0.0, s2 = 0.0;
     for (int i = lane; i < n; i += 64) {
@@ -3033,7 +3169,8 @@ int do_matern(hipStream_t st, int kern, int n1, int n2, int d, const void* x1, c
     dim3 grid((n2 + TS - 1) / TS, (n1 + TS - 1) / TS);
     for_kern(kern, [&](auto k) {
         hipLaunchKernelGGL((cross_kernel<T, decltype(k)::value>), grid, dim3(256), 0, st, (T*)out, n2, n1, n2, d, (const T*)x1,
-                           (const T*)x2, th, (const double*)nullptr, same, (const T*)nullptr, n1, n2, 0, (size_t)0);
+                           (const T*)x2, th, (const double*)nullptr, same, (const T*)nullptr, n1, n2, 0, (size_t)0,
+                           (const int*)nullptr);
     });
     CHECK_LAUNCH("cross_kernel");
     return 0;
@@ -3046,10 +3183,11 @@ inline int predict_pad(int n0) { return n0 >= 128 ? round_up(n0, 2 * TS) : round
 // C_k = A_k op B_k (an OP_PRED_* product of the tile kernel) for all local components: A and C are `rows` x ld slabs sA
 // apart, B_k ld x ld matrices sB apart, ld = nb 64-tiles.  128x128 tiles when rows is a multiple of 128, 64x64 tiles otherwise.
 template <typename T, int OP>
-int launch_pred(hipStream_t st, const T* A, const T* B, T* C, size_t sA, size_t sB, int ld, int rows, int nb, int q) {
+int launch_pred(hipStream_t st, const T* A, const T* B, T* C, size_t sA, size_t sB, int ld, int rows, int nb, int q,
+                size_t sC = 0 /*0 = sA*/) {
     GemmArgs g;
     g.A = A; g.B = B; g.C = C;
-    g.sA = sA; g.sB = sB; g.sC = sA; g.ldA = g.ldB = g.ldC = ld; g.p1 = g.p2 = g.p3 = 0;
+    g.sA = sA; g.sB = sB; g.sC = sC ? sC : sA; g.ldA = g.ldB = g.ldC = ld; g.p1 = g.p2 = g.p3 = 0;
     if (rows % (2 * TS) == 0) {
         g.nb = nb / 2; g.p0 = rows / (2 * TS);
         return launch_gemm<T, OP, 128>(st, g, g.p0 * g.nb, q);
@@ -3068,7 +3206,8 @@ int form_xu(hipStream_t st, const Ws& w, const void* x, const void* sr, const do
     memset(&dummy, 0, sizeof(dummy));
     for_kern(w.kern, [&](auto kern) {
         hipLaunchKernelGGL((cross_kernel<T, decltype(kern)::value>), dim3(w.nb, n0pad / TS, w.q), dim3(256), 0, st, X, w.npad, n0,
-                           w.n, w.d, (const T*)x0, (const T*)x, dummy, theta, same, (const T*)sr, n0pad, w.npad, w.d + 3 + w.p, slab);
+                           w.n, w.d, (const T*)x0, (const T*)x, dummy, theta, same, (const T*)sr, n0pad, w.npad, w.d + 3 + w.p, slab,
+                           (const int*)nullptr);
     });
     CHECK_LAUNCH("cross_kernel");
     return launch_pred<T, OP_PRED_U>(st, X, (const T*)(w.base + w.off_W), U, slab, w.mat, w.npad, n0pad, w.nb, w.q);
@@ -3084,7 +3223,7 @@ int do_predict(hipStream_t st, const Ws& w, const void* x, const void* sr, const
     T* U = X + slab * w.q;              // q slabs n0pad x npad : X W^T = (L^-1 X^T)^T
     int rc = form_xu<T>(st, w, x, sr, theta, n0, n0pad, x0, same, X, U);
     if (rc) return rc;
-    hipLaunchKernelGGL((pred_reduce_kernel<T>), dim3(n0, w.q), dim3(64), 0, st, (const T*)X, (const T*)U, slab, w.npad, w.n,
+    hipLaunchKernelGGL((pred_reduce_kernel<T>), dim3(n0, w.q), dim3(64), 0, st, (const T*)X, (const T*)U, slab, slab, w.npad, w.n,
                        (const T*)(w.base + w.off_z), w.npad, theta, w.d + 3 + w.p, w.d, ldo, ghat, gvar);
     CHECK_LAUNCH("pred_reduce_kernel");
     return 0;
@@ -3181,7 +3320,8 @@ int do_predict_cov(hipStream_t st, const Ws& w, const void* x, const void* sr, c
     memset(&dummy, 0, sizeof(dummy));
     for_kern(w.kern, [&](auto kern) {
         hipLaunchKernelGGL((cross_kernel<T, decltype(kern)::value>), dim3(n0pad / TS, n0pad / TS, w.q), dim3(256), 0, st, M, n0pad,
-                           n0, n0, w.d, (const T*)x0, (const T*)x0, dummy, theta, 1, (const T*)nullptr, n0pad, n0pad, tw, cw.mat);
+                           n0, n0, w.d, (const T*)x0, (const T*)x0, dummy, theta, 1, (const T*)nullptr, n0pad, n0pad, tw, cw.mat,
+                           (const int*)nullptr);
     });
     CHECK_LAUNCH("cross_kernel");
     int rc = form_xu<T>(st, w, x, sr, theta, n0, n0pad, x0, same, X, U);
@@ -3367,6 +3507,149 @@ int do_cv_apply(hipStream_t st, const Ws& w, const void* sr, const double* theta
                        cw.mat, cw.npad, folds, F, w.q, (const T*)(w.base + w.off_b), (const T*)(w.base + w.off_z), w.npad,
                        (const T*)sr, theta, w.d + 3 + w.p, w.d, ldo, ghat, gvar);
     CHECK_LAUNCH("cv_apply_kernel");
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------
+// Integrated variance reduction at fixed parameters (ALC / IMSPE reduction; no counterpart in the reference).  For
+// reference points t, candidates c (standardised) and local component k, with U_k = (c0k o sr^T) L_k^-T as lcgp_predict forms it:
+//     out[k, c] = sum_t w_t sigma_k(t, c)^2 / (max(gvar_k(c), 0) + 1 / (D_k r)),   sigma_k(t, c) = C_k(t, c) - D_k U_k(t) . U_k(c)
+// (lcgp_hip.h).  lcgp_variance_reduction_prepare forms U_k of the reference set once; lcgp_variance_reduction forms U_k and gvar
+// of a chunk of candidates (or takes them from the reference set), then ONE launch of the tile kernel (OP_VR: the n_ref x n_cand
+// products stay in registers, the epilogue reduces them to one partial per reference tile) and vr_reduce_kernel.
+// ---------------------------------------------------------------------------------------------------
+constexpr int VR_XBLK = 2048;       // rows of X = c0k o sr^T formed per pass: bounds the X work area however large a set is
+
+// scratch of the variance reduction: a reference part (offsets depend on n_ref only) followed by a candidate part (offsets
+// relative to cand, from the n_cand of the call): a scratch sized for n_cand serves every call with fewer candidates
+struct VrLay {
+    int rrows, nrt, ldp;
+    size_t uslab_r, xslab_r, uslab_c, xslab_c;
+    size_t off_uref, off_gvr, off_ghr, off_xr, cand;
+    size_t off_uc, off_gvc, off_ghc, off_xc, off_part, total;
+};
+
+inline VrLay vr_carve(int dtype, int n, int q, int n_ref, int n_cand) {
+    VrLay L;
+    const size_t esz = dtype == LCGP_F64 ? 8 : 4, npad = round_up(n, 2 * TS);
+    // U_ref rows: whole 128-row tiles plus one 64-row tile, so that a candidate tile taken from ANY row of the reference set
+    // (cand_row0 >= 0) stays inside the slab (its rows beyond the set only feed candidate columns that are never written)
+    L.rrows = round_up(n_ref, 2 * TS) + TS;
+    L.nrt = (n_ref + TS - 1) / TS;
+    L.ldp = round_up(n_cand, TS);
+    L.uslab_r = (size_t)L.rrows * npad;
+    L.xslab_r = (size_t)min(VR_XBLK, predict_pad(n_ref)) * npad;
+    size_t o = 0;
+    L.off_uref = o; o = align256(o + (size_t)q * L.uslab_r * esz);
+    L.off_gvr = o; o = align256(o + (size_t)q * n_ref * sizeof(double));
+    L.off_ghr = o; o = align256(o + (size_t)q * n_ref * sizeof(double));
+    L.off_xr = o; o = align256(o + (size_t)q * L.xslab_r * esz);
+    L.cand = o;
+    const int crows = predict_pad(n_cand);
+    L.uslab_c = (size_t)crows * npad;
+    L.xslab_c = (size_t)min(VR_XBLK, crows) * npad;
+    L.off_uc = o; o = align256(o + (size_t)q * L.uslab_c * esz);
+    L.off_gvc = o; o = align256(o + (size_t)q * n_cand * sizeof(double));
+    L.off_ghc = o; o = align256(o + (size_t)q * n_cand * sizeof(double));
+    L.off_xc = o; o = align256(o + (size_t)q * L.xslab_c * esz);
+    L.off_part = o; o = align256(o + (size_t)q * L.nrt * L.ldp * sizeof(double));
+    L.total = o;
+    return L;
+}
+
+// U_k and gvar_k (ld = ldv per component) of m0 inputs xs for all local components, in passes of VR_XBLK rows: X = c0k o sr^T
+// (cross_kernel, nugget term at column match[i] where given) into the X work area (q slabs xslab apart), U = X W^T (OP_PRED_U)
+// into rows lo .. of the U slabs (uslab apart), then the row reductions (pred_reduce_kernel; gh receives ghat, unused).
+// Per row the same arithmetic as lcgp_predict, whatever the pass.
+template <typename T>
+int vr_form(hipStream_t st, const Ws& w, const void* x, const void* sr, const double* theta, int m0, const void* xs,
+            const int* match, T* X, size_t xslab, T* U, size_t uslab, double* gh, double* gv, int ldv) {
+    const int tw = w.d + 3 + w.p;
+    ThetaArg dummy;
+    memset(&dummy, 0, sizeof(dummy));
+    for (int lo = 0; lo < m0; lo += VR_XBLK) {
+        const int m = min(VR_XBLK, m0 - lo), mpad = predict_pad(m);
+        const T* x0 = (const T*)xs + (size_t)lo * w.d;
+        const int* mt = match ? match + lo : nullptr;
+        for_kern(w.kern, [&](auto kern) {
+            hipLaunchKernelGGL((cross_kernel<T, decltype(kern)::value>), dim3(w.nb, mpad / TS, w.q), dim3(256), 0, st, X, w.npad, m,
+                               w.n, w.d, x0, (const T*)x, dummy, theta, 0, (const T*)sr, mpad, w.npad, tw, xslab, mt);
+        });
+        CHECK_LAUNCH("cross_kernel");
+        T* Ub = U + (size_t)lo * w.npad;
+        int rc = launch_pred<T, OP_PRED_U>(st, X, (const T*)(w.base + w.off_W), Ub, xslab, w.mat, w.npad, mpad, w.nb, w.q, uslab);
+        if (rc) return rc;
+        hipLaunchKernelGGL((pred_reduce_kernel<T>), dim3(m, w.q), dim3(64), 0, st, (const T*)X, (const T*)Ub, xslab, uslab, w.npad,
+                           w.n, (const T*)(w.base + w.off_z), w.npad, theta, tw, w.d, ldv, gh + lo, gv + lo);
+        CHECK_LAUNCH("pred_reduce_kernel");
+    }
+    return 0;
+}
+
+template <typename T>
+int do_vr_prepare(hipStream_t st, const Ws& w, const void* x, const void* sr, const double* theta, int n_ref, const void* x_ref,
+                  char* scratch) {
+    const VrLay L = vr_carve(w.esz == 8 ? LCGP_F64 : LCGP_F32, w.n, w.q, n_ref, 1);
+    return vr_form<T>(st, w, x, sr, theta, n_ref, x_ref, nullptr, (T*)(scratch + L.off_xr), L.xslab_r, (T*)(scratch + L.off_uref),
+                      L.uslab_r, (double*)(scratch + L.off_ghr), (double*)(scratch + L.off_gvr), n_ref);
+}
+
+// out[k, c] = sum over the reference tiles, in ascending order, of the partials the OP_VR epilogue left
+__global__ __launch_bounds__(256) void vr_reduce_kernel(const double* __restrict__ part, int nrt, int ldp, int n_cand, int ldo,
+                                                        double* __restrict__ out) {
+    const int c = blockIdx.x * blockDim.x + threadIdx.x, k = blockIdx.y;
+    if (c >= n_cand) return;
+    const double* pk = part + (size_t)k * nrt * ldp + c;
+    double s = 0.0;
+    for (int rt = 0; rt < nrt; ++rt) s += pk[(size_t)rt * ldp];
+    out[(size_t)k * ldo + c] = s;
+}
+
+template <typename T>
+int do_vr(hipStream_t st, const Ws& w, const void* x, const void* sr, const double* theta, int n_ref, const void* x_ref,
+          const double* w_ref, int n_cand, const void* x_cand, const int* match, int row0, int r, char* scratch, double* out,
+          int ldo) {
+    const VrLay L = vr_carve(w.esz == 8 ? LCGP_F64 : LCGP_F32, w.n, w.q, n_ref, n_cand);
+    const T* Ur = (const T*)(scratch + L.off_uref);
+    const T* Uc;
+    const double* gvc;
+    const void* xc;
+    size_t sB;
+    int ldg;
+    if (row0 >= 0) {                // the candidates are rows row0 .. of the reference set: its U and gvar serve
+        Uc = Ur + (size_t)row0 * w.npad; sB = L.uslab_r;
+        gvc = (const double*)(scratch + L.off_gvr) + row0; ldg = n_ref;
+        xc = (const T*)x_ref + (size_t)row0 * w.d;
+    } else {
+        T* U = (T*)(scratch + L.off_uc);
+        double* gv = (double*)(scratch + L.off_gvc);
+        int rc = vr_form<T>(st, w, x, sr, theta, n_cand, x_cand, match, (T*)(scratch + L.off_xc), L.xslab_c, U, L.uslab_c,
+                            (double*)(scratch + L.off_ghc), gv, n_cand);
+        if (rc) return rc;
+        Uc = U; sB = L.uslab_c; gvc = gv; ldg = n_cand; xc = x_cand;
+    }
+    GemmArgs h;
+    h.A = Ur; h.B = Uc; h.C = scratch + L.off_part;
+    h.sA = L.uslab_r; h.sB = sB; h.sC = 0;
+    h.ldA = h.ldB = w.npad; h.ldC = 0;
+    h.nb = 0;
+    h.p0 = w.npad / TS; h.p1 = (n_cand + TS - 1) / TS; h.p2 = n_ref; h.p3 = n_cand;
+    h.theta = theta; h.xa = x_ref; h.xb = xc; h.wref = w_ref; h.gvc = gvc; h.ldg = ldg;
+    h.d = w.d; h.kern = w.kern; h.tw = w.d + 3 + w.p; h.nrep = r; h.ldp = L.ldp;
+    // 64x64 tiles: the 128-tile instances of the U U^T product do not compile clean (OP_PRED_COV), and this
+    // epilogue holds more than that one's
+    int rc = launch_gemm<T, OP_VR, 64>(st, h, L.nrt * h.p1, w.q);
+    if (rc) return rc;
+    hipLaunchKernelGGL(vr_reduce_kernel, dim3((n_cand + 255) / 256, w.q), dim3(256), 0, st,
+                       (const double*)(scratch + L.off_part), L.nrt, L.ldp, n_cand, ldo, out);
+    CHECK_LAUNCH("vr_reduce_kernel");
+    return 0;
+}
+
+// host-side checks of the variance-reduction arguments shared by the two entries
+int check_vr(int n_ref, int n_cand) {
+    if (n_ref < 1) return bad("n_ref must be >= 1");
+    if (n_cand < 1) return bad("n_cand must be >= 1");
     return 0;
 }
 
@@ -3768,6 +4051,60 @@ int lcgp_cv_apply(void* stream, int dtype, int n, int d, int p, int q_local, con
     const int ldo = out_stride ? out_stride : n;
     return dtype == LCGP_F64 ? do_cv_apply<double>(st, w, sr, theta, folds, F, cw, ghat, gvar, ldo)
                              : do_cv_apply<float>(st, w, sr, theta, folds, F, cw, ghat, gvar, ldo);
+}
+
+int lcgp_variance_reduction_scratch_bytes(int dtype, int n, int q_local, int n_ref, int n_cand, size_t* bytes) {
+    int rc = check_common(dtype, n, 1, 1, q_local);
+    if (rc) return rc;
+    if ((rc = check_vr(n_ref, n_cand))) return rc;
+    if (!bytes) return bad("bytes is NULL");
+    *bytes = vr_carve(dtype, n, q_local, n_ref, n_cand).total;
+    return 0;
+}
+
+int lcgp_variance_reduction_prepare(void* stream, int dtype, int kernel_id, int n, int d, int p, int q_local, const void* x,
+                                    const void* sr, const double* theta, const void* workspace, int n_ref, const void* x_ref,
+                                    void* scratch) {
+    int rc = check_common(dtype, n, d, p, q_local, kernel_id);
+    if (rc) return rc;
+    if ((rc = check_vr(n_ref, 1))) return rc;
+    if (!x || !theta || !workspace || !x_ref || !scratch) return bad("NULL pointer");
+    Ws w = carve(dtype, n, d, p, q_local, (void*)workspace);
+    w.kern = kernel_id;
+    hipStream_t st = (hipStream_t)stream;
+    return dtype == LCGP_F64 ? do_vr_prepare<double>(st, w, x, sr, theta, n_ref, x_ref, (char*)scratch)
+                             : do_vr_prepare<float>(st, w, x, sr, theta, n_ref, x_ref, (char*)scratch);
+}
+
+int lcgp_variance_reduction(void* stream, int dtype, int kernel_id, int n, int d, int p, int q_local, const void* x, const void* sr,
+                            const double* theta, const void* workspace, int n_ref, const void* x_ref, const double* w_ref,
+                            int n_cand, const void* x_cand, const int* match_host, const int* match, int cand_row0, int r,
+                            void* scratch, double* out, int out_stride) {
+    int rc = check_common(dtype, n, d, p, q_local, kernel_id);
+    if (rc) return rc;
+    if ((rc = check_vr(n_ref, n_cand))) return rc;
+    if (r < 1) return bad("r must be >= 1");
+    if (cand_row0 < -1) return bad("cand_row0 must be -1 or a row of the reference set");
+    if (cand_row0 >= 0) {
+        if ((long long)cand_row0 + n_cand > n_ref) return bad("cand_row0 + n_cand must be <= n_ref");
+        if (x_cand || match_host || match) return bad("cand_row0 >= 0: x_cand and match must be NULL");
+    } else if (!x_cand) {
+        return bad("NULL pointer");
+    }
+    if ((match_host == nullptr) != (match == nullptr)) return bad("match_host and match must both be NULL or both be given");
+    if (match_host)
+        for (int i = 0; i < n_cand; ++i)
+            if (match_host[i] < -1 || match_host[i] >= n) return bad("match must be -1 or a training index in [0, n)");
+    if (!x || !theta || !workspace || !x_ref || !w_ref || !scratch || !out) return bad("NULL pointer");
+    if (out_stride != 0 && out_stride < n_cand) return bad("out_stride must be 0 (= n_cand) or >= n_cand");
+    const int ldo = out_stride ? out_stride : n_cand;
+    Ws w = carve(dtype, n, d, p, q_local, (void*)workspace);
+    w.kern = kernel_id;
+    hipStream_t st = (hipStream_t)stream;
+    return dtype == LCGP_F64 ? do_vr<double>(st, w, x, sr, theta, n_ref, x_ref, w_ref, n_cand, x_cand, match, cand_row0, r,
+                                             (char*)scratch, out, ldo)
+                             : do_vr<float>(st, w, x, sr, theta, n_ref, x_ref, w_ref, n_cand, x_cand, match, cand_row0, r,
+                                            (char*)scratch, out, ldo);
 }
 
 }  // extern "C"

@@ -477,6 +477,54 @@ class HotPathEngine:
                 covs.append(cov)
             return out, covs
 
+    # ------------------------------------------------------------------------------------------------
+    # integrated variance reduction at fixed parameters (lcgp_hip.h: lcgp_variance_reduction_prepare / lcgp_variance_reduction)
+    def variance_reduction_block(self, x_cand_s, x_ref_s, w, match, r):
+        """(q_local, n_cand) float64 DEVICE tensor R_k(c) = sum_t w_t Sigma_k(t, c)^2 / (max(Sigma_k^h(c, c), 0) + 1 / (D_k r)), from
+        the factorisation of the last evaluate().  x_cand_s (n_cand, d) / x_ref_s (n_ref, d): standardised; x_ref_s = None: the
+        reference set IS the candidate set.  w: n_ref weights (used as given).  match: None or n_cand ints, -1 or the training
+        input a candidate replicates (its cross row carries the nugget term there).  U of the reference set is formed once per
+        call; candidates go in chunks of PREDICT_CHUNK; with x_ref_s = None and no match one U serves both.  Raises ValueError
+        when the scratch does not fit in the free device memory."""
+        torch = self.torch
+        if self._theta_last is None:
+            raise RuntimeError("variance_reduction() needs a preceding evaluate() at the current parameters")
+        x_cand_s = np.ascontiguousarray(x_cand_s, np.float64)
+        n_cand, d = x_cand_s.shape[0], self.d
+        assert x_cand_s.ndim == 2 and x_cand_s.shape[1] == d and n_cand >= 1
+        match = None if match is None else np.ascontiguousarray(match, np.int32)
+        if match is not None and not np.any(match >= 0):
+            match = None
+        shared = x_ref_s is None and match is None
+        x_ref_s = x_cand_s if x_ref_s is None else np.ascontiguousarray(x_ref_s, np.float64)
+        n_ref = x_ref_s.shape[0]
+        assert x_ref_s.ndim == 2 and x_ref_s.shape[1] == d and n_ref >= 1 and len(w) == n_ref
+        chunk = min(n_cand, PREDICT_CHUNK)
+        with torch.cuda.device(self.device):
+            nbytes = self._nbytes("lcgp_variance_reduction_scratch_bytes", self.dtype, self.n, self.q_local, n_ref, chunk)
+            scratch = self._grow_scratch(nbytes, ("the variance reduction over %d reference points" % n_ref,
+                                                  "%d components of (n_ref + %d candidates) x n" % (self.q_local, chunk),
+                                                  "pass fewer reference points"))
+            xr = torch.as_tensor(x_ref_s).to(self.device, self.tdtype).contiguous()
+            xc = None if shared else torch.as_tensor(x_cand_s).to(self.device, self.tdtype).contiguous()
+            wd = torch.as_tensor(np.ascontiguousarray(w, np.float64)).to(self.device)
+            md = None if match is None else torch.as_tensor(match).to(self.device)
+            out = torch.empty((self.q_local, n_cand), dtype=torch.float64, device=self.device)
+            st, xp, srp, thp, wsp, scp = (self._stream(), self._p(self.x), self._p(self.sr), self._p(self.theta_dev),
+                                          self._p(self.workspace), self._p(scratch))
+            _hip.check(self.lib.lcgp_variance_reduction_prepare(st, self.dtype, self.kernel_id, self.n, d, self.p, self.q_local, xp, srp,
+                                                                thp, wsp, n_ref, self._p(xr), scp), "lcgp_variance_reduction_prepare")
+            for lo in range(0, n_cand, chunk):
+                m = min(chunk, n_cand - lo)
+                xcp = C.c_void_p(0) if shared else C.c_void_p(xc.data_ptr() + lo * d * xc.element_size())
+                mh = C.c_void_p(0) if match is None else C.c_void_p(match.ctypes.data + 4 * lo)
+                mdp = C.c_void_p(0) if match is None else C.c_void_p(md.data_ptr() + 4 * lo)
+                _hip.check(self.lib.lcgp_variance_reduction(st, self.dtype, self.kernel_id, self.n, d, self.p, self.q_local, xp, srp,
+                                                            thp, wsp, n_ref, self._p(xr), self._p(wd), m, xcp, mh, mdp,
+                                                            lo if shared else -1, int(r), scp, C.c_void_p(out.data_ptr() + 8 * lo),
+                                                            n_cand), "lcgp_variance_reduction")
+            return out
+
     def fetch_vector(self, which, k):
         torch = self.torch
         with torch.cuda.device(self.device):

@@ -1056,6 +1056,78 @@ class LCGP:
         return (*outs, lat)
 
     # =============================================================================================
+    # integrated variance reduction for choosing new design points (beyond the reference)
+    # =============================================================================================
+    def variance_reduction(self, x_cand, x_ref=None, weights=None, outputs=None, replicates=1, latent=False):
+        """Integrated variance reduction (the active-learning-Cohn criterion, ALC / IMSPE reduction): for each candidate input
+        the drop of the weighted predictive variance over a reference set if the simulator ran once more there, at FIXED
+        parameters (hyper-parameters, noise, basis phi, standardisation; no refit).  It does not depend on the simulator output.
+        With latent component k, reference point t, candidate c (standardised) and U_k as in predict():
+            R_k(c)     = sum_t w_t Sigma_k(t, c)^2 / (max(Sigma_k^h(c, c), 0) + 1 / (D_k r))
+            Sigma_k(t, c)   = C_k(t, c) - D_k U_k(t) . U_k(c)     (no nugget: reference points are new inputs)
+            Sigma_k^h(c, c) = scale_k - D_k |U_k(c)|^2           (predict()'s gvar at c, with the candidate's own cross row)
+            Delta_a(c) = scale_a^2 sum_k W[k, a]^2 R_k(c)         (W, scale: those of predict())
+        R_k(c) is gvar_k summed over the reference set before minus after adding the run to the training set; Delta_a(c) is the
+        drop of yconfvar, and of ypredvar (the noise does not change).
+          x_cand: (n_cand, d) raw-scale candidates.  x_ref: (n_ref, d) raw-scale reference points (default: x_cand).
+          weights: n_ref non-negative weights, normalised to sum 1 (default uniform).  outputs: output indices (default all p).
+          replicates: r runs at the candidate.  Full path: the candidate is one new training row with its own nugget, r = 1
+                 only; its cross row has no nugget term even where it equals a training input.  Rep path: a candidate equal
+                 (after standardisation, bitwise) to a unique training input adds r replicates to it (its cross row carries
+                 the nugget term at that input, as predict() does at the training set); otherwise it is a new unique input.
+          latent: return R (q, n_cand) instead of Delta (len(outputs), n_cand).
+        Computed on the GPU from the factorisation of the current parameters (right after fit() no extra evaluation), in the
+        engine's dtype (float32 models: float32 products, double sums).  GPU memory: q_local (n_ref + min(n_cand, 2048)) npad
+        elements of scratch and q_local ceil(n_ref / 64) min(n_cand, 2048) doubles (npad = n_train rounded up to 128); the
+        n_ref x n_cand matrix is never formed -- ValueError when it does not fit.  self.ghat / self.gvar are left untouched."""
+        d = int(self.d)
+        xc = _np(self._verify_data_types(x_cand))
+        if xc.ndim != 2 or xc.shape[1] != d or xc.shape[0] < 1:
+            raise ValueError('x_cand must have shape (n_cand, %d), got %s' % (d, tuple(xc.shape)))
+        xc_s, _ = self._standardise_x0(xc)
+        xr_s = None
+        n_ref = xc.shape[0]
+        if x_ref is not None:
+            xr = _np(self._verify_data_types(x_ref))
+            if xr.ndim != 2 or xr.shape[1] != d or xr.shape[0] < 1:
+                raise ValueError('x_ref must have shape (n_ref, %d), got %s' % (d, tuple(xr.shape)))
+            xr_s, _ = self._standardise_x0(xr)
+            n_ref = xr.shape[0]
+        if weights is None:
+            w = np.full(n_ref, 1.0 / n_ref)
+        else:
+            w = np.asarray(weights, F64).reshape(-1)
+            if w.shape != (n_ref,):
+                raise ValueError('weights must have length n_ref = %d, got %d' % (n_ref, w.size))
+            if not np.all(np.isfinite(w)) or np.any(w < 0):
+                raise ValueError('weights must be finite and non-negative')
+            if not np.any(w > 0):
+                raise ValueError('weights must not all be zero')
+            w = w / np.sum(w)
+        p = int(self.p)
+        outputs = list(range(p)) if outputs is None else [int(a) for a in np.atleast_1d(outputs)]
+        if any(a < 0 or a >= p for a in outputs):
+            raise ValueError('outputs must be indices in [0, %d)' % p)
+        if isinstance(replicates, (bool, np.bool_)) or int(replicates) != replicates or replicates < 1:
+            raise ValueError('replicates must be an integer >= 1')
+        r = int(replicates)
+        match = None
+        if self.submethod == 'rep':
+            xt = self._x_train()
+            lookup = {row.tobytes(): i for i, row in enumerate(np.ascontiguousarray(xt))}
+            match = np.array([lookup.get(row.tobytes(), -1) for row in np.ascontiguousarray(xc_s)], np.int32)
+        elif r != 1:
+            raise ValueError("replicates must be 1 on the full path (submethod='full'): a candidate is one new training row")
+        eng = self._ensure_aux()
+        loc = self._agree(lambda: None if eng is None else eng.variance_reduction_block(xc_s, xr_s, w, match, r))
+        R = self._gather_components(loc, (xc.shape[0],))
+        if latent:
+            return _t(R)
+        W, _, scale, _ = self._output_map()
+        delta = (W[:, outputs] ** 2).T @ R * (scale[outputs] ** 2)[:, None]
+        return _t(delta)
+
+    # =============================================================================================
     # input gradients of the prediction (the reference: a tf.GradientTape around predict)
     # =============================================================================================
     def _latent_predict_grad(self, x0):

@@ -1,5 +1,7 @@
-"""Stage-wise componentwise error bounds of the hot path (build, Cholesky, L^-1, A^-1, z, outputs, predict) and of the
-joint path (cross covariance X, U = X W^T, Sigma + tau I, its factor, the draws).
+"""Stage-wise componentwise error bounds of the hot path (build, Cholesky, L^-1, A^-1, z, outputs, predict), of the
+joint path (cross covariance X, U = X W^T, Sigma + tau I, its factor, the draws) and of the post-fit queries (V = U W and
+the input gradients of lcgp_predict_grad, leave-one-out, the k-fold gather / factor / inverse / apply, the integrated
+variance reduction).
 
 Every check compares one stage of the library with a plain float64 reference computed from THE LIBRARY'S OWN INPUT TO THAT
 STAGE (the fetched A for the Cholesky, the fetched L for L^-1, ...), so no bound carries a condition number.  Entries are
@@ -507,3 +509,240 @@ def check_draws(out, L, eps, ghat, dtype) -> Check:
     ref = g[None, :] + le
     bound = C * (n0 + 1.0) * unit(dtype) * (ep.abs() @ l.abs().T) + C * unit("float64") * (g.abs()[None, :] + le.abs())
     return worst((_t(out, dev) - ref).abs(), bound + floor(dtype, n0), lower=False)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# post-fit queries: input gradients of the prediction (lcgp_predict_grad), leave-one-out (lcgp_loo), k-fold cross-validation
+# (lcgp_cv_gather -> lcgp_potrf_logdet / lcgp_potri on the fold workspace -> lcgp_cv_apply) and the integrated variance
+# reduction (lcgp_variance_reduction_prepare / lcgp_variance_reduction).  The fold factor and inverse go through
+# check_cholesky_inverse_solve, check_inverse_factor and check_inverse on the fetched slot.
+# ----------------------------------------------------------------------------------------------------------------------
+def predict_pad(n0) -> int:
+    """rows of the lcgp_predict / lcgp_predict_grad scratch slabs: n0 rounded up to 128, or to 64 below 128"""
+    return _pad128(n0) if n0 >= 2 * TS else -(-int(n0) // TS) * TS
+
+
+def _worst_cols(err, bound, names) -> Check:
+    """worst(err / bound) over an (rows x columns) table, located as (row block, column name)"""
+    r = err / bound
+    r = torch.where(torch.isnan(r), torch.full_like(r, math.inf), r)
+    if r.numel() == 0:
+        return Check(0.0, ())
+    idx = int(torch.argmax(r))
+    i, j = divmod(idx, r.shape[1])
+    return Check(float(r.view(-1)[idx]), (i // TS, names[j]))
+
+
+def check_pgrad_v(V, U, W, dtype) -> Check:
+    """V_k = U_k W_k (n0 x n; OP_PRED_V, written over the X slabs of the lcgp_predict_grad scratch) against the float64 product
+    of the library's own U (the second slabs) and W = L^-1 (lower triangle of the fetched matrix).  Entry (i, j) is an inner
+    product over m = j .. npad - 1 (W is lower triangular, the padding adds stored zeros), accumulated in the storage type and
+    stored once: C (npad + 2) u (|U| |W|)_ij."""
+    dev = _dev(V, U, W)
+    uu = _t(U, dev)
+    w = torch.tril(_t(W, dev))
+    n = w.shape[0]
+    k = _pad128(n)
+    ref = uu @ w
+    bound = C * (k + 2.0) * unit(dtype) * (uu.abs() @ w.abs()) + floor(dtype, k)
+    return worst((_t(V, dev)[:, :n] - ref).abs(), bound, lower=False)
+
+
+def check_pgrad(dghat, dgvar, x0, x, sr, th, z, V, kernel, dtype) -> Check:
+    """dghat / dgvar (n0 x d) of lcgp_predict_grad against the contraction of include/lcgp_hip.h, in float64 from the rounded
+    x0, x, sr and the library's own z (fetched) and V = U W (check_pgrad_v's stage):
+        dghat[i, l] = -1/ell_l      sum_j c0_ij sr_j z_j    h_l(i, j)
+        dgvar[i, l] =  2 D / ell_l  sum_j c0_ij sr_j V_ij   h_l(i, j)
+        h_l = s / (1 + |s|) (Matern-3/2), s (SE),   s = x0_il / ell_l - x_jl / ell_l,   c0 = scale (1 - nt) C0.
+    Precision.  pgrad_kernel converts the stored x0, x, sr, z and V to double and does everything else in double, in both
+    storage types: u is the FLOAT64 unit roundoff for every factor below; the only storage-type roundings are those of the
+    inputs, which the reference shares (and of V and z, which it takes from the library).
+    Per term.  c0 carries kernel_parts' float64 magnification E (x / ell, the exponent, the polynomial; the cap and the
+    cut-off as in check_predict) plus the products by c_off, sr and z or V (three roundings).  s carries u (|x0_il| + |x_jl|)
+    / ell_l + u |s| (the two quotients and the difference); d h / d s = 1 / (1 + |s|)^2 <= 1 and h = s fast_rcp(1 + |s|)
+    (v_rcp_f64 with two Newton steps: within 2 u of 1 / (1 + |s|)) adds four roundings: |dh| <= u (m_l + 5 |h|),
+    m_l = (|x0_il| + |x_jl|) / ell_l.  The sum over j (fma per slice, then the fixed-order slice reduction) adds n roundings
+    of the absolute terms, the scaling by -1/ell_l or 2 D / ell_l two more.  Together, with C = 4 on top:
+        C u / ell_l sum_j |c0_ij sr_j z_j| ((n + d + E_ij + 4) |h_l| + m_l)          (|V_ij| and 2 |D| for dgvar)
+    plus the float64 floor.  m_l is not relative to |h_l|: x0 close to x_j (but not equal) leaves an absolute error of s.
+    At dx = 0 (a training input among x0) both sides have s = 0 exactly, so h = 0.  Past the C0 cut-off the term itself is
+    added (the library may return any c0 in [0, C0] there)."""
+    dev = _dev(dghat, dgvar, z, V)
+    u = unit("float64")
+    a = _t(rounded(x0, dtype), dev)
+    b = _t(rounded(x, dtype), dev)
+    n0, d = a.shape
+    n = b.shape[0]
+    ell, scale, nug, D, _ = split_theta(th, d)
+    nt = nug / (1.0 + nug)
+    c0, e, cut = kernel_parts(a, b, ell, kernel, "float64", dev)
+    c0 = scale * (1.0 - nt) * c0
+    s = _t(rounded(np.ones(n) if sr is None else sr, dtype), dev)
+    pz = c0 * (s * _t(z, dev)[:n])[None, :]
+    pv = c0 * s[None, :] * _t(V, dev)[:n0, :n]
+    cm = cut.to(torch.float64)
+    wgt = n + d + e + 4.0
+    gref, gbnd, vref, vbnd = (torch.zeros(n0, d, dtype=torch.float64, device=dev) for _ in range(4))
+    for l in range(d):
+        xa, xb = a[:, l] / ell[l], b[:, l] / ell[l]
+        sl = xa[:, None] - xb[None, :]
+        h = sl / (1.0 + sl.abs()) if kernel != "se" else sl
+        t = wgt * h.abs() + (xa.abs()[:, None] + xb.abs()[None, :])
+        gref[:, l] = -(pz * h).sum(dim=1) / ell[l]
+        gbnd[:, l] = (C * u * (pz.abs() * t).sum(dim=1) + (cm * (pz * h).abs()).sum(dim=1)) / ell[l]
+        vref[:, l] = 2.0 * D * (pv * h).sum(dim=1) / ell[l]
+        vbnd[:, l] = 2.0 * abs(D) * (C * u * (pv.abs() * t).sum(dim=1) + (cm * (pv * h).abs()).sum(dim=1)) / ell[l]
+    fl = floor("float64", n)
+    names = ["l%d" % l for l in range(d)]
+    cg = _worst_cols((_t(dghat, dev).reshape(n0, d) - gref).abs(), gbnd + fl, ["dghat " + s for s in names])
+    cv = _worst_cols((_t(dgvar, dev).reshape(n0, d) - vref).abs(), vbnd + fl, ["dgvar " + s for s in names])
+    return combine(cg, cv)
+
+
+def check_loo(ghat, gvar, V, b, z, sr, th, dtype, d) -> Check:
+    """leave-one-out (lcgp_loo) against the closed form of lcgp_hip.h from the library's own a_ii (diagonal of the fetched
+    A^-1), b and z and the rounded sr:
+        ghat_i = (b_i - z_i / a_ii) / (D s_i),     gvar_i = (1 / a_ii - 1) / (D s_i^2).
+    loo_kernel does this in double in both storage types, so u is float64's.  ghat: 1 / a_ii, the product with z_i, the
+    difference, D s_i and the quotient are five roundings, |error| <= u (3 |b_i| + 5 |z_i / a_ii|) / |D s_i|; gvar: 1 / a_ii,
+    the difference, D s_i, s_i once more and the quotient, |error| <= u (5 / |a_ii| + 4) / |D s_i^2|.  Bounds: 2 C u times
+    (|b_i| + |z_i / a_ii|) / |D s_i| and (1 / |a_ii| + 1) / |D s_i^2| (2 C = 8 >= 5), plus the float64 floor.  d: the input
+    dimension (it places D in the theta row)."""
+    dev = _dev(ghat, gvar, V, b, z)
+    u = unit("float64")
+    a = torch.diagonal(_t(V, dev))
+    n = a.shape[0]
+    D = split_theta(th, d)[3]
+    bb, zz = _t(b, dev)[:n], _t(z, dev)[:n]
+    s = _t(rounded(np.ones(n) if sr is None else sr, dtype), dev)
+    ia = 1.0 / a
+    gref = (bb - zz * ia) / (D * s)
+    gb = 2.0 * C * u * (bb.abs() + (zz * ia).abs()) / (abs(D) * s.abs()) + floor("float64", 1)
+    vref = (ia - 1.0) / (D * s * s)
+    vb = 2.0 * C * u * (ia.abs() + 1.0) / (abs(D) * s * s) + floor("float64", 1)
+    return combine(worst((_t(ghat, dev)[:n] - gref).abs(), gb), worst((_t(gvar, dev)[:n] - vref).abs(), vb))
+
+
+def check_cv_gather(M, V, fold_idx, mmax) -> Check:
+    """the matrix slot of one fold (M: the raw mpad x mpad slot of the fold workspace, mpad = mmax rounded up to 128) after
+    lcgp_cv_gather, BITWISE: on every lower 64-tile (whole tiles, the diagonal tiles' upper halves included, as the kernel
+    writes them) M[i, j] = A^-1[idx_i, idx_j] for i, j < m (V: the fetched A^-1, whose upper triangle mirrors the lower
+    storage the kernel reads at (max, min)) and the identity beyond m = len(fold_idx), up to mpad.  A copy has no rounding:
+    ratio 0 when every entry matches, inf otherwise, located at the first wrong (row block, column block)."""
+    dev = _dev(M, V)
+    m_ = _t(M, dev)
+    mpad = m_.shape[0]
+    assert mpad == _pad128(mmax) and m_.shape[1] == mpad, (m_.shape, mmax)
+    idx = torch.as_tensor(np.asarray(fold_idx, np.int64), device=dev)
+    m = idx.shape[0]
+    ref = torch.eye(mpad, dtype=torch.float64, device=dev)
+    ref[:m, :m] = _t(V, dev)[idx][:, idx]
+    blk = torch.arange(mpad, device=dev) // TS
+    lower = blk[:, None] >= blk[None, :]
+    bad = (m_.view(torch.int64) != ref.view(torch.int64)) & lower
+    if not bool(bad.any()):
+        return Check(0.0, ())
+    i, j = (int(v) for v in torch.nonzero(bad)[0])
+    return Check(math.inf, (i // TS, j // TS))
+
+
+def check_cv_apply(ghat, gvar, Minv, b, z, sr, th, fold_idx, dtype, d) -> Check:
+    """ghat / gvar at the positions of one fold (lcgp_cv_apply) against the closed form of lcgp_hip.h from the library's own
+    M^-1 (the fetched V slot of the fold's slot; its upper triangle mirrors the lower storage), b and z:
+        t = M^-1 z_B,   ghat_B = (b_B - t) / (D s_B),   gvar_B = (diag(M^-1) - 1) / (D s_B^2).
+    cv_apply_kernel works in double in both storage types (u = float64's): t is an inner product of m terms, |dt| <=
+    (m + 1) u (|M^-1| |z_B|); the difference, D s and the quotient add u (|b| + |t| + 2 |b - t|): together C u ((m + 2)
+    |M^-1| |z_B| + 2 |b_B|) / |D s_B|.  gvar: four roundings, 2 C u (|M^-1_ii| + 1) / |D s_B^2|.  Every position of the fold
+    is checked (locations: 64-blocks of the position within the fold).  d: the input dimension (places D in theta)."""
+    dev = _dev(ghat, gvar, Minv, b, z)
+    u = unit("float64")
+    idx = torch.as_tensor(np.asarray(fold_idx, np.int64), device=dev)
+    m = idx.shape[0]
+    D = split_theta(th, d)[3]
+    mi = _t(Minv, dev)[:m, :m]
+    zb, bb = _t(z, dev)[idx], _t(b, dev)[idx]
+    nfull = _t(b, dev).shape[0]
+    s = _t(rounded(np.ones(nfull) if sr is None else sr, dtype), dev)[idx]
+    t = mi @ zb
+    gref = (bb - t) / (D * s)
+    gb = C * u * ((m + 2.0) * (mi.abs() @ zb.abs()) + 2.0 * bb.abs()) / (abs(D) * s.abs()) + floor("float64", m)
+    dg = torch.diagonal(mi)
+    vref = (dg - 1.0) / (D * s * s)
+    vb = 2.0 * C * u * (dg.abs() + 1.0) / (abs(D) * s * s) + floor("float64", 1)
+    return combine(worst((_t(ghat, dev)[idx] - gref).abs(), gb), worst((_t(gvar, dev)[idx] - vref).abs(), vb))
+
+
+def check_vr(out, x_ref, w, x_cand, match, r, x, sr, th, W, kernel, dtype) -> Check:
+    """out[k, c] of lcgp_variance_reduction (one component, n_cand values) against its definition in float64 from the rounded
+    x_ref, x_cand, x, sr, the weights w (float64, as given), the library's W = L^-1 (lower triangle of the fetched matrix):
+        X_r = c_off C0(x_ref, x) o sr^T,   X_c = c_off C0(x_cand, x) o sr^T (+ scale nt sr_i at column i = match[c] >= 0)
+        U = X W^T,   Sigma(t, c) = c_off C0(x_ref_t, x_cand_c) - D U_r(t) . U_c(c),   gvar_c = scale - D |U_c(c)|^2
+        out_c = sum_t w_t Sigma(t, c)^2 / den_c,   den_c = max(gvar_c, 0) + 1 / (D r).
+    Sigma.  U of either set is lcgp_predict's U (cross_kernel, then the product in the storage type over npad terms): |dU| <=
+    g Ua with g = (npad + d + E) u and Ua = |X| |W|^T, |X| including the nugget entry (whose two extra roundings are within
+    the same relative bound).  The product U_r U_c^T adds npad terms in the storage type, and C(t, c) is recomputed in double
+    (E_tc).  Keeping the exact |U| on one side of each first-order term (|X| |W|^T alone is far larger than |U| where W
+    cancels, which in float32 swamps the denominator below):
+        |d(U_r . U_c)| <= g (Ua_t . |U_c| + |U_r| . Ua_c + |U_r| . |U_c|) + g^2 Ua_t . Ua_c
+        delta_tc = C g_tc (|C_tc| + |D| (that bracket)),   g_tc = (npad + d + E_t + E_c + E_tc) u     (+ |C_tc| past the cut-off)
+    with E_t, E_c the largest magnification of the row's cross covariance.  The nugget term never enters C(t, c): reference
+    points are new inputs; it enters only U_c (and so gvar_c) through X_c.
+    Denominator.  gvar_c = scale - D |U_c|^2 summed in double: delta_h = C |D| (g_c (2 |U_c| . Ua_c + |U_c|^2) + g_c^2
+    |Ua_c|^2) + u scale; max(., 0) is 1-Lipschitz, so it passes delta_h on unchanged (a gvar_c that cancels to a tiny or
+    negative value has den_c near 1 / (D r)); 1 / (D r) and the addition are three float64 roundings, C u64 den_c.
+    out.  The library's den' = max(gvar', 0) + 1 / (D r) is never below 1 / (D r), whatever gvar' is, so den' >= lo_c =
+    max(den_c - delta_h, 1 / (D r)) (the latter less a rounding).  With S = sum_t w_t Sigma^2, |S' - S| <= sum_t |w_t|
+    (2 |Sigma| delta + delta^2) and |1/den' - 1/den| <= delta_h / (den lo):
+        |out' - out| <= [sum_t |w_t| (2 |Sigma_tc| delta_tc + delta_tc^2) + |out_c| delta_h] / lo_c
+                        + C (n_ref + 2) u64 sum_t |w_t| Sigma_tc^2 / den_c          (the double sums and the quotient)
+    The clamp matters in float32 at large D: gvar_c of a candidate near the data cancels below its own error delta_h, and
+    without it den' (so out) would have no bound at all.  Locations: 64-blocks of the candidate."""
+    dev = _dev(out, W)
+    d = np.asarray(x).shape[1]
+    u, u64 = unit(dtype), unit("float64")
+    ell, scale, nug, D, _ = split_theta(th, d)
+    nt = nug / (1.0 + nug)
+    coff = scale * (1.0 - nt)
+    xr, xc, xt = (_t(rounded(a, dtype), dev) for a in (x_ref, x_cand, x))
+    n = xt.shape[0]
+    s = _t(rounded(np.ones(n) if sr is None else sr, dtype), dev)
+    w_ = torch.tril(_t(W, dev))
+    wa = w_.abs()
+    npad = _pad128(n)
+
+    def cross(x1, mt):
+        c0, e, cut = kernel_parts(x1, xt, ell, kernel, dtype, dev)
+        X = coff * c0 * s[None, :]
+        Xa = X.abs() + torch.where(cut, X.abs(), torch.zeros_like(X))
+        if mt is not None:
+            mt = np.asarray(mt, np.int64)
+            rows = np.nonzero(mt >= 0)[0]
+            if rows.size:
+                ri = torch.as_tensor(rows, device=dev)
+                ci = torch.as_tensor(mt[rows], device=dev)
+                X[ri, ci] += scale * nt * s[ci]
+                Xa[ri, ci] = X[ri, ci].abs() + torch.where(cut[ri, ci], (coff * c0 * s[None, :])[ri, ci].abs(), 0.0)
+        return X @ w_.T, Xa @ wa.T, e.max(dim=1).values
+
+    Ur, Ura, er = cross(xr, None)
+    Uc, Uca, ec = cross(xc, match)
+    ctc, etc_, cut_tc = kernel_parts(xr, xc, ell, kernel, dtype, dev)
+    ct = coff * ctc
+    sig = ct - D * (Ur @ Uc.T)
+    gt = (npad + d + er[:, None] + ec[None, :] + etc_) * u
+    ura, uca = Ur.abs(), Uc.abs()
+    prod = gt * (Ura @ uca.T + ura @ Uca.T + ura @ uca.T) + gt * gt * (Ura @ Uca.T)
+    delta = C * (gt * ct.abs() + abs(D) * prod)
+    delta = delta + torch.where(cut_tc, ct.abs(), torch.zeros_like(ct)) + floor(dtype, npad)
+    del ctc, etc_, cut_tc, gt, prod, Ura, ura
+    gc = (npad + d + ec) * u
+    gv = scale - D * (Uc * Uc).sum(dim=1)
+    den = torch.clamp(gv, min=0.0) + 1.0 / (D * r)
+    dh = C * abs(D) * (gc * (2.0 * (uca * Uca).sum(dim=1) + (uca * uca).sum(dim=1)) + gc * gc * (Uca * Uca).sum(dim=1))
+    dh = dh + u * abs(scale) + C * u64 * den + floor(dtype, npad)
+    wt = _t(w, dev)
+    ref = (wt[:, None] * sig * sig).sum(dim=0) / den
+    num = (wt.abs()[:, None] * (2.0 * sig.abs() * delta + delta * delta)).sum(dim=0)
+    lo = torch.clamp(den - dh, min=(1.0 - C * u64) / (D * r))
+    bound = (num + ref.abs() * dh) / lo + C * (wt.shape[0] + 2.0) * u64 * (wt.abs()[:, None] * sig * sig).sum(dim=0) / den
+    return worst((_t(out, dev) - ref).abs(), bound + floor("float64", wt.shape[0]))

@@ -376,3 +376,375 @@ def test_cov_factor_bound_covers_the_inverse_panel_solve():
         L[_tile(3, 1)] *= 1 + 1e-12
         ch = sb.check_cholesky_inverse_solve(c["sig"], L, "float64")
         assert ch.ratio > 1 and ch.where == (3, 1), (k, ch)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# post-fit queries: predict_grad (V = U W, the input gradients), leave-one-out, k-fold cross-validation, the integrated
+# variance reduction.  The emulated fit carries sr (the rep path) where a check depends on it; every post-fit stage is
+# computed in float64 from the previous stored stage and rounded to the storage type where the library stores it.
+# ----------------------------------------------------------------------------------------------------------------------
+def _normwise(got, ref):
+    got, ref = np.asarray(got, np.float64), np.asarray(ref, np.float64)
+    return np.max(np.abs(got - ref)) / np.max(np.abs(ref))
+
+
+def _fit(x, Y, sr, th, dtype, kernel="matern32"):
+    """the fitted workspace of the emulated path with sr: W = L^-1, V = A^-1, b, z (storage type)"""
+    d = x.shape[1]
+    A = _r(sb.reference_A(x, sr, th, kernel, dtype)[0].numpy(), dtype)
+    L = _r(np.linalg.cholesky(A), dtype)
+    W = np.tril(_r(np.linalg.solve(L, np.eye(x.shape[0])), dtype))
+    V = _r(W.T @ W, dtype)
+    b = _r(_r(Y, dtype).T @ th[d + 3:], dtype)
+    z = _r(V @ b, dtype)
+    return dict(W=W, V=V, b=b, z=z)
+
+
+def _theta(d, seed, ell=None, scale=1.3, nug=0.01, Dk=5.0):
+    rng = np.random.default_rng(seed)
+    ell = rng.uniform(0.3, 0.9, d) * np.sqrt(d) if ell is None else np.asarray(ell, np.float64)
+    return np.concatenate([ell, [scale, nug, Dk], rng.standard_normal(P)])
+
+
+def _cross(x0, x, sr, th, dtype, kernel="matern32", match=None):
+    """X = c_off C0(x0, x) o sr^T (+ the nugget term at column match[c]) in float64 from the rounded inputs"""
+    d = x.shape[1]
+    ell, scale, nug, Dk, _ = sb.split_theta(th, d)
+    nt = nug / (1 + nug)
+    s = np.ones(x.shape[0]) if sr is None else _r(sr, dtype)
+    X = scale * (1 - nt) * sb.kernel_parts(_r(x0, dtype), _r(x, dtype), ell, kernel, dtype)[0].numpy() * s[None, :]
+    if match is not None:
+        for c, i in enumerate(match):
+            if i >= 0:
+                X[c, i] += scale * nt * s[i]
+    return X
+
+
+def _pgrad(x0, x, sr, th, z, V, dtype, kernel="matern32", rcp=None, chunk_l0=None, drop=None):
+    """dghat, dgvar (n0 x d) of the contraction in float64; defects: rcp (the reciprocal in h), chunk_l0 (dimensions from
+    chunk_l0 on computed with the s of dimension l - chunk_l0), drop (training inputs left out of dgvar)"""
+    d = x.shape[1]
+    ell, scale, nug, Dk, _ = sb.split_theta(th, d)
+    s = np.ones(x.shape[0]) if sr is None else _r(sr, dtype)
+    c0 = _cross(x0, x, None, th, dtype, kernel)
+    a, b = _r(x0, dtype), _r(x, dtype)
+    pz = c0 * (s * z)[None, :]
+    pv = c0 * s[None, :] * V
+    if drop is not None:
+        pv = pv.copy()
+        pv[:, drop] = 0.0
+    gh, gv = np.zeros((x0.shape[0], d)), np.zeros((x0.shape[0], d))
+    for l in range(d):
+        ls = l - chunk_l0 if (chunk_l0 is not None and l >= chunk_l0) else l
+        sl = a[:, ls][:, None] / ell[ls] - b[:, ls][None, :] / ell[ls]
+        h = sl * (1.0 / (1.0 + np.abs(sl)) if rcp is None else rcp(1.0 + np.abs(sl))) if kernel != "se" else sl
+        gh[:, l] = -(pz * h).sum(axis=1) / ell[l]
+        gv[:, l] = 2 * Dk * (pv * h).sum(axis=1) / ell[l]
+    return gh, gv
+
+
+def _pgrad_problem(dtype, d=D_IN, n=N, n0=70, kernel="matern32", rep=False, seed=3):
+    rng = np.random.default_rng(seed)
+    x = rng.uniform(0.0, 1.0, (n, d))
+    Y = rng.standard_normal((P, n))
+    sr = np.sqrt(rng.integers(1, 6, n).astype(np.float64)) if rep else None
+    th = _theta(d, seed + 1)
+    e = _fit(x, Y, sr, th, dtype, kernel)
+    x0 = np.concatenate([x[:5], rng.uniform(-0.1, 1.1, (n0 - 5, d))])      # training inputs among x0: dx = 0
+    U = _r(_r(_cross(x0, x, sr, th, dtype, kernel), dtype) @ e["W"].T, dtype)
+    Vp = _r(U @ e["W"], dtype)                                               # V = U W of predict_grad (Vp here)
+    gh, gv = _pgrad(x0, x, sr, th, e["z"], Vp, dtype, kernel)
+    return dict(x=x, sr=sr, th=th, x0=x0, U=U, Vp=Vp, gh=gh, gv=gv, **e)
+
+
+@pytest.mark.parametrize("kernel", ["matern32", "se"])
+@pytest.mark.parametrize("dtype", ["float64", "float32"])
+def test_emulated_predict_grad_passes(dtype, kernel):
+    for rep in (False, True):
+        g = _pgrad_problem(dtype, kernel=kernel, rep=rep)
+        assert sb.check_pgrad_v(g["Vp"], g["U"], g["W"], dtype).ratio < 0.5
+        c = sb.check_pgrad(g["gh"], g["gv"], g["x0"], g["x"], g["sr"], g["th"], g["z"], g["Vp"], kernel, dtype)
+        assert c.ratio < 0.5, c
+
+
+@pytest.mark.parametrize("dtype", ["float64", "float32"])
+def test_pgrad_defect_1_v_block_from_the_wrong_component(dtype):
+    """rows 32 .. 63 of V (one PG_ROWS block) formed from the U of the next component"""
+    g = _pgrad_problem(dtype)
+    g2 = _pgrad_problem(dtype, seed=9)
+    V = g["Vp"].copy()
+    V[32:64] = g2["Vp"][32:64]
+    c = sb.check_pgrad_v(V, g["U"], g["W"], dtype)
+    assert c.ratio > 1 and c.where[0] == 0, c
+
+
+def test_pgrad_defect_2_wide_chunk_with_l0_zero():
+    """d = 40: the second 32-dimension chunk (blockIdx.z = 1) computed with l0 = 0 -- dimensions 32 .. 39 carry the scaled
+    distances of 0 .. 7, divided by their own lengthscales"""
+    for dtype in ("float64", "float32"):
+        g = _pgrad_problem(dtype, d=40, n=150, n0=40)
+        gh, gv = _pgrad(g["x0"], g["x"], None, g["th"], g["z"], g["Vp"], dtype, chunk_l0=32)
+        c = sb.check_pgrad(gh, gv, g["x0"], g["x"], None, g["th"], g["z"], g["Vp"], "matern32", dtype)
+        assert c.ratio > 1 and int(c.where[1].split("l")[-1]) >= 32, c
+
+
+def test_pgrad_defect_3_float32_reciprocal_in_h():
+    """h = s rcp(1 + |s|) with the reciprocal carrying float32 accuracy only (no Newton steps), in the float64 path"""
+    g = _pgrad_problem("float64")
+    gh, gv = _pgrad(g["x0"], g["x"], None, g["th"], g["z"], g["Vp"], "float64", rcp=lambda v: np.float32(1.0) / v.astype(np.float32))
+    c = sb.check_pgrad(gh, gv, g["x0"], g["x"], None, g["th"], g["z"], g["Vp"], "matern32", "float64")
+    assert c.ratio > 1, c
+
+
+@pytest.mark.parametrize("dtype", ["float64", "float32"])
+def test_pgrad_defect_4_stage_of_training_inputs_left_out_of_dgvar(dtype):
+    """one LDS stage of JT = 32 training inputs (64 .. 95) missing from the dgvar sum"""
+    g = _pgrad_problem(dtype, rep=True)
+    gh, gv = _pgrad(g["x0"], g["x"], g["sr"], g["th"], g["z"], g["Vp"], dtype, drop=slice(64, 96))
+    c = sb.check_pgrad(g["gh"], gv, g["x0"], g["x"], g["sr"], g["th"], g["z"], g["Vp"], "matern32", dtype)
+    assert c.ratio > 1 and c.where[1].startswith("dgvar"), c
+
+
+# ---- leave-one-out -----------------------------------------------------------------------------------------------------
+def _loo(V, b, z, sr, Dk):
+    a = np.diag(V)
+    s = np.ones_like(b) if sr is None else sr
+    return (b - z / a) / (Dk * s), (1 / a - 1) / (Dk * s * s)
+
+
+@pytest.mark.parametrize("dtype", ["float64", "float32"])
+def test_emulated_loo_passes_and_defects_fail(dtype):
+    for rep in (False, True):
+        g = _pgrad_problem(dtype, rep=rep)
+        sr = None if g["sr"] is None else _r(g["sr"], dtype)
+        Dk = g["th"][D_IN + 2]
+        gh, gv = _loo(g["V"], g["b"], g["z"], sr, Dk)
+        assert sb.check_loo(gh, gv, g["V"], g["b"], g["z"], g["sr"], g["th"], dtype, D_IN).ratio < 0.5
+        # defect 1: a_ii of component k + 1 (another theta, same inputs)
+        g2 = _fit(g["x"], np.random.default_rng(4).standard_normal((P, N)), g["sr"], _theta(D_IN, 11), dtype)
+        bad = _loo(np.diag(np.diag(g2["V"])), g["b"], g["z"], sr, Dk)
+        c = sb.check_loo(bad[0], bad[1], g["V"], g["b"], g["z"], g["sr"], g["th"], dtype, D_IN)
+        assert c.ratio > 1, c
+        # defect 2 (rep path): gvar divided by s_i instead of s_i^2
+        if rep:
+            c = sb.check_loo(gh, gv * sr, g["V"], g["b"], g["z"], g["sr"], g["th"], dtype, D_IN)
+            assert c.ratio > 1, c
+
+
+# ---- k-fold --------------------------------------------------------------------------------------------------------------
+FOLD_SIZES = (65, 129, 1, 105)          # mmax = 129: mpad = 256, four 64-tiles per side
+
+
+def _folds(n, sizes, seed):
+    perm = np.random.default_rng(seed).permutation(n)
+    out, lo = [], 0
+    for m in sizes:
+        out.append(np.sort(perm[lo:lo + m]))
+        lo += m
+    assert lo == n
+    return out
+
+
+def _raw_V(V, seed):
+    """lower storage of A^-1 as the library holds it: the strict upper triangle never written (garbage)"""
+    g = np.random.default_rng(seed).uniform(-1e3, 1e3, V.shape)
+    return np.tril(V) + np.triu(g, 1)
+
+
+def _gather(Vraw, idx, mpad, upper_bug=False):
+    M = np.eye(mpad)
+    ii, jj = np.meshgrid(idx, idx, indexing="ij")
+    m = len(idx)
+    M[:m, :m] = Vraw[ii, jj] if upper_bug else Vraw[np.maximum(ii, jj), np.minimum(ii, jj)]
+    return M
+
+
+def _sym(M):
+    return np.tril(M) + np.tril(M, -1).T
+
+
+def _cv_emulate(dtype, rep=True):
+    g = _pgrad_problem(dtype, rep=rep)
+    folds = _folds(N, FOLD_SIZES, 5)
+    mmax = max(FOLD_SIZES)
+    mpad = sb._pad128(mmax)
+    Vraw = _raw_V(g["V"], 6)
+    sr = None if g["sr"] is None else _r(g["sr"], dtype)
+    Dk = g["th"][D_IN + 2]
+    res = []
+    for idx in folds:
+        slot = _gather(Vraw, idx, mpad)
+        M = _sym(slot)[:mmax, :mmax]
+        L = _r(np.linalg.cholesky(M), dtype)
+        W = np.tril(_r(np.linalg.solve(L, np.eye(mmax)), dtype))
+        Mi = _r(W.T @ W, dtype)
+        m = len(idx)
+        s = np.ones(m) if sr is None else sr[idx]
+        t = Mi[:m, :m] @ g["z"][idx]
+        res.append(dict(idx=idx, slot=slot, M=M, L=L, W=W, Mi=Mi, t=t, s=s,
+                        gh=(g["b"][idx] - t) / (Dk * s), gv=(np.diag(Mi)[:m] - 1) / (Dk * s * s)))
+    return g, Vraw, mmax, res
+
+
+@pytest.fixture(scope="module", params=["float64", "float32"])
+def cv(request):
+    return (request.param,) + _cv_emulate(request.param)
+
+
+def _scatter(res, n):
+    gh, gv = np.full(n, np.nan), np.full(n, np.nan)
+    for f in res:
+        gh[f["idx"]], gv[f["idx"]] = f["gh"], f["gv"]
+    return gh, gv
+
+
+def test_emulated_cv_passes_every_stage(cv):
+    dtype, g, Vraw, mmax, res = cv
+    gh, gv = _scatter(res, N)
+    for f in res:
+        assert sb.check_cv_gather(f["slot"], g["V"], f["idx"], mmax).ratio == 0
+        assert sb.check_cholesky_inverse_solve(f["M"], f["L"], dtype).ratio < 0.5
+        assert sb.check_inverse_factor(f["L"], f["W"], dtype).ratio < 0.5
+        assert sb.check_inverse(f["W"], f["Mi"], dtype).ratio < 0.5
+        c = sb.check_cv_apply(gh, gv, f["Mi"], g["b"], g["z"], g["sr"], g["th"], f["idx"], dtype, D_IN)
+        assert c.ratio < 0.5, c
+
+
+def test_cv_defect_1_upper_tile_gathered_from_unwritten_storage(cv):
+    dtype, g, Vraw, mmax, res = cv
+    f = res[1]                                            # the 129-input fold: tiles (1, 0), (2, 0), (2, 1) and the diagonals
+    slot = _gather(Vraw, f["idx"], sb._pad128(mmax), upper_bug=True)
+    c = sb.check_cv_gather(slot, g["V"], f["idx"], mmax)
+    assert c.ratio > 1, c
+    slot = f["slot"].copy()
+    slot[200, 200] = 0.0                                  # the identity padding beyond m_f not written
+    assert sb.check_cv_gather(slot, g["V"], f["idx"], mmax).ratio > 1
+
+
+def test_cv_defect_2_fold_scattered_one_position_off(cv):
+    dtype, g, Vraw, mmax, res = cv
+    gh, gv = _scatter(res, N)
+    f = res[3]
+    gh[f["idx"][1:]] = f["gh"][:-1]
+    c = sb.check_cv_apply(gh, gv, f["Mi"], g["b"], g["z"], g["sr"], g["th"], f["idx"], dtype, D_IN)
+    assert c.ratio > 1, c
+
+
+def test_cv_defect_3_above_diagonal_tile_read_untransposed(cv):
+    """the apply reads the stored tile (1, 0) of M^-1 for the block (0, 1) without transposing it: t of the fold's first 64
+    positions is wrong"""
+    dtype, g, Vraw, mmax, res = cv
+    f = res[1]
+    m = len(f["idx"])
+    Mb = f["Mi"][:m, :m].copy()
+    Mb[0:64, 64:128] = f["Mi"][64:128, 0:64]
+    Dk = g["th"][D_IN + 2]
+    t = Mb @ g["z"][f["idx"]]
+    gh, gv = _scatter(res, N)
+    gh[f["idx"]] = (g["b"][f["idx"]] - t) / (Dk * f["s"])
+    c = sb.check_cv_apply(gh, gv, f["Mi"], g["b"], g["z"], g["sr"], g["th"], f["idx"], dtype, D_IN)
+    assert c.ratio > 1 and c.where == (0,), c
+
+
+# ---- integrated variance reduction -----------------------------------------------------------------------------------------
+N_REF, N_CAND, VR_XBLK = 2100, 70, 2048
+
+
+def _vr_out(Ur, Uc, xr, xc, w, th, r, dtype, kernel="matern32", den_r=None):
+    d = xr.shape[1]
+    ell, scale, nug, Dk, _ = sb.split_theta(th, d)
+    ct = scale * (1 - nug / (1 + nug)) * sb.kernel_parts(_r(xr, dtype), _r(xc, dtype), ell, kernel, dtype)[0].numpy()
+    sig = ct - Dk * _r(Ur @ Uc.T, dtype)
+    gv = scale - Dk * np.sum(Uc * Uc, axis=1)
+    den = np.maximum(gv, 0) + 1 / (Dk * (r if den_r is None else den_r))
+    return (w[:, None] * sig * sig).sum(axis=0) / den
+
+
+def _vr_emulate(dtype, kernel="matern32"):
+    g = _pgrad_problem(dtype, rep=True, kernel=kernel)
+    rng = np.random.default_rng(12)
+    xr = rng.uniform(-0.1, 1.1, (N_REF, D_IN))
+    xc = rng.uniform(-0.1, 1.1, (N_CAND, D_IN))
+    xc[:4] = g["x"][[7, 20, 33, 298]]                  # matched candidates: replicates of training inputs
+    match = -np.ones(N_CAND, np.int64)
+    match[:4] = [7, 20, 33, 298]
+    w = rng.uniform(0.0, 1.0, N_REF)
+    w[::7] = 0.0
+    w /= w.sum()
+    Ur = _r(_r(_cross(xr, g["x"], g["sr"], g["th"], dtype, kernel), dtype) @ g["W"].T, dtype)
+    Uc = _r(_r(_cross(xc, g["x"], g["sr"], g["th"], dtype, kernel, match), dtype) @ g["W"].T, dtype)
+    r = 3
+    out = _vr_out(Ur, Uc, xr, xc, w, g["th"], r, dtype, kernel)
+    return dict(g=g, xr=xr, xc=xc, match=match, w=w, Ur=Ur, Uc=Uc, r=r, out=out, kernel=kernel)
+
+
+@pytest.fixture(scope="module", params=["float64", "float32"])
+def vr(request):
+    return request.param, _vr_emulate(request.param)
+
+
+@pytest.fixture(scope="module")
+def vr64():
+    """float64 only, for the defects of a size the float32 bound cannot resolve: Sigma = C - D U_r . U_c cancels (the
+    posterior covariance is small against the prior), so in float32 its bound delta is of the size of Sigma itself and the
+    bound on out of the size of out (a dropped tile of 52 reference rows, a 1 % change of a matched U_c, den with r = 1)"""
+    return "float64", _vr_emulate("float64")
+
+
+def _check_vr(v, out, dtype, match="same", r=None):
+    g = v["g"]
+    return sb.check_vr(out, v["xr"], v["w"], v["xc"], v["match"] if match == "same" else match, v["r"] if r is None else r,
+                       g["x"], g["sr"], g["th"], g["W"], v["kernel"], dtype)
+
+
+def test_emulated_vr_passes(vr):
+    dtype, v = vr
+    assert _check_vr(v, v["out"], dtype).ratio < 0.5
+    v2 = _vr_emulate(dtype, "se")
+    assert _check_vr(v2, v2["out"], dtype).ratio < 0.5
+
+
+def test_vr_defect_1_last_reference_tile_left_out(vr64):
+    dtype, v = vr64
+    last = (N_REF - 1) // TS * TS
+    w = v["w"].copy()
+    w[last:] = 0.0
+    out = _vr_out(v["Ur"], v["Uc"], v["xr"], v["xc"], w, v["g"]["th"], v["r"], dtype)
+    assert _check_vr(v, out, dtype).ratio > 1
+
+
+def test_vr_defect_2_reference_row_beyond_n_ref_weighted(vr):
+    """a padding row of the last reference tile (x_ref staged as 0, U row 0) given the weight of row 1"""
+    dtype, v = vr
+    xr = np.concatenate([v["xr"], np.zeros((1, D_IN))])
+    Ur = np.concatenate([v["Ur"], np.zeros((1, v["Ur"].shape[1]))])
+    w = np.concatenate([v["w"], v["w"][1:2]])
+    out = _vr_out(Ur, v["Uc"], xr, v["xc"], w, v["g"]["th"], v["r"], dtype)
+    assert _check_vr(v, out, dtype).ratio > 1
+
+
+def test_vr_defect_3_nugget_term_of_a_match_on_the_wrong_column(vr64):
+    dtype, v = vr64
+    g = v["g"]
+    wrong = np.where(v["match"] >= 0, v["match"] + 1, -1)
+    Uc = _r(_r(_cross(v["xc"], g["x"], g["sr"], g["th"], dtype, "matern32", wrong), dtype) @ g["W"].T, dtype)
+    out = _vr_out(v["Ur"], Uc, v["xr"], v["xc"], v["w"], g["th"], v["r"], dtype)
+    c = _check_vr(v, out, dtype)
+    assert c.ratio > 1 and c.where == (0,), c
+
+
+def test_vr_defect_4_r_ignored_in_the_denominator(vr64):
+    dtype, v = vr64
+    out = _vr_out(v["Ur"], v["Uc"], v["xr"], v["xc"], v["w"], v["g"]["th"], v["r"], dtype, den_r=1)
+    assert _check_vr(v, out, dtype).ratio > 1
+
+
+def test_vr_defect_5_second_pass_written_at_row_zero(vr):
+    """n_ref = 2100 is formed in two passes of VR_XBLK = 2048 rows; the second pass's U lands on rows 0 .. 51 and rows
+    2048 .. 2099 keep what the scratch held (zeros here)"""
+    dtype, v = vr
+    Ur = v["Ur"].copy()
+    Ur[:N_REF - VR_XBLK] = v["Ur"][VR_XBLK:]
+    Ur[VR_XBLK:] = 0.0
+    out = _vr_out(Ur, v["Uc"], v["xr"], v["xc"], v["w"], v["g"]["th"], v["r"], dtype)
+    assert _check_vr(v, out, dtype).ratio > 1

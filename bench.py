@@ -10,6 +10,10 @@ One "step" = one complete evaluation: host packs the constrained parameters, one
 this rank's components (k -> rank k mod N), one all-reduce of the (P+1)-vector (RCCL) when N > 1, D2H, chain
 rule -- exactly what `LCGP.fit()` hands L-BFGS-B per function evaluation.  Inputs are resident in HBM before
 the timed region.  Rank 0 prints ONE JSON line; with --dump-outputs DIR it also writes what the last timed step returned.
+
+A plain run does only what the headline needs: set up, warm up, time the steps, print.  --full adds, after the timed
+steps, the legs the headline does not need: per-stage HIP-event times and the roofline of the dominant kernel, the
+predict leg, a wall-clock fit(), the CPU baseline with its parity gate, and the all-reduce timed alone (N > 1).
 """
 import argparse
 import json
@@ -36,14 +40,17 @@ def parse():
     ap.add_argument('--config', type=int, default=3, help='synthetic config id of lcgp_amd/synth.py (3 = headline)')
     ap.add_argument('--n', type=int, default=None, help='override n (debug only; invalidates the headline metric)')
     ap.add_argument('--q', type=int, default=None, help='override q (debug only: e.g. one rank\'s share of the components)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-stages', action='store_true')
-    ap.add_argument('--no-fit', action='store_true', help='skip the wall-clock fit() leg')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps, also run the stage timings + roofline, predict, fit(), CPU baseline + parity and '
+                         'all-reduce legs (the --no-* options and --predict 0 drop single legs of it)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline and parity leg')
+    ap.add_argument('--no-stages', action='store_true', help='with --full: skip the stage timings (and with them roofline and predict)')
+    ap.add_argument('--no-fit', action='store_true', help='with --full: skip the wall-clock fit() leg')
     ap.add_argument('--blocks', type=int, default=1,
                     help='timed blocks of --steps evaluations (the first one is `value`; more blocks show the spread and '
                          'time blocks x --steps evaluations in all)')
-    ap.add_argument('--cpu-repeats', type=int, default=5)
-    ap.add_argument('--predict', type=int, default=2000, help='new inputs of the predict leg (K6); 0 = skip')
+    ap.add_argument('--cpu-repeats', type=int, default=5, help='with --full: samples of each CPU baseline form')
+    ap.add_argument('--predict', type=int, default=2000, help='with --full: new inputs of the predict leg (K6); 0 = skip')
     ap.add_argument('--backend', default='nccl', help='process-group backend for --gpus > 1 (nccl = RCCL)')
     ap.add_argument('--dump-outputs', metavar='DIR', default=None,
                     help='write what the last timed step returned (NLL and gradient, float64) as DIR/nll.npy and DIR/grad.npy')
@@ -295,10 +302,11 @@ def main():
         mine['device_uuid'] = str(getattr(pr, 'uuid', ''))
     except Exception as e:      # never lose the line over a missing attribute
         mine['device_name'] = 'unknown (%s)' % e
-    if not args.no_stages:
+    stages = args.full and not args.no_stages
+    if stages:
         m.loss_and_grad(pts[0])          # collective: every rank takes part (leaves theta_0 resident)
     st = clock = None
-    if not args.no_stages and m._engine is not None:
+    if stages and m._engine is not None:
         st, clock = stage_times(m)
         mine['lauum_clock'] = clock
         esz = 8 if dtype == 'float64' else 4
@@ -311,7 +319,7 @@ def main():
 
     # ---- the collective on its own: the all-reduce of the (P+3)-vector, device-resident, timed alone ----
     allreduce_us = None
-    if world > 1:
+    if world > 1 and args.full:
         width = 3 + q * d + 2 * q + p
         t = torch.zeros(width, dtype=torch.float64, device='cuda' if args.backend == 'nccl' else 'cpu')
         for _ in range(20):
@@ -333,12 +341,12 @@ def main():
                        world_size=(dist.get_world_size() if world > 1 else 1), launched_gpus=args.gpus,
                        visible_devices=ndev, allreduce_us=allreduce_us,
                        allreduce_note='median of 5 x 100 in-place all_reduce(sum) of the %d-double vector, alone on the stream'
-                                      % (3 + q * d + 2 * q + p) if world > 1 else None,
+                                      % (3 + q * d + 2 * q + p) if allreduce_us is not None else None,
                        distinct_devices=len({(r.get('host'), r.get('pci_bus_id'), r.get('device_index')) for r in ranks}),
                        ranks=ranks)
 
     # ---- wall-clock fit() of the same configuration (the metric names it; lcgp.py:537-540), all ranks in lock-step ----
-    if not args.no_fit:
+    if args.full and not args.no_fit:
         mf = LCGP(y=y, x=x, q=cfg['q'], submethod=cfg['submethod'], dtype=dtype, device='cuda:%d' % dev_index)
         mf._get_engine()
         barrier()
@@ -412,7 +420,7 @@ def main():
             out['predict'] = pr
             log('predict leg: n0=%d %.3f ms = %.1f TFLOP/s' % (pr['n0'], pr['ms'], pr['tflops']))
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         log('cpu baseline (bounded sample) ...')
         base, pieces, ns = cpu_baseline(m, repeats=args.cpu_repeats)
         out['cpu_baseline'] = base

@@ -267,16 +267,16 @@ def test_the_inverse_launch_reports_the_clock_it_ran_at():
 
 
 def test_bench_line_keeps_its_contract():
-    """`python bench.py` prints ONE JSON line with the fields the driver reads (metric / value / unit / n_gpus / steps / warmup /
-    ms_per_step / higher_is_better / scaling / vs_baseline / dtype / data / config.workload) plus the `roofline` block of the
-    dominant kernel, measured live (HIP events, in-kernel clock).  Run as the driver runs it, in a process of its own."""
+    """`python bench.py --full` prints ONE JSON line with the fields the driver reads (metric / value / unit / n_gpus / steps /
+    warmup / ms_per_step / higher_is_better / scaling / vs_baseline / dtype / data / config.workload) plus the `roofline` block
+    of the dominant kernel, measured live (HIP events, in-kernel clock).  Run in a process of its own."""
     import json
     import os
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     res = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1',
-                          '--no-cpu-baseline', '--no-fit', '--predict', '0', '--blocks', '1'],
+                          '--full', '--no-cpu-baseline', '--no-fit', '--predict', '0', '--blocks', '1'],
                          capture_output=True, text=True, timeout=600)
     assert res.returncode == 0, res.stderr[-2000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith('{')]
@@ -293,6 +293,28 @@ def test_bench_line_keeps_its_contract():
     assert r['clock_mhz'] is not None and r['clock_mhz'] > 0.0 and r['clock_window_us'] > 0.0
     assert r['traffic'] is None or r['traffic'] > 1e9
     assert set(d['roofline_stages']) == {'potrf', 'trtri', 'lauum'}
+
+
+def test_plain_bench_line_is_the_headline_alone():
+    """A plain `bench.py --gpus 1 --steps N --warmup W`, as the driver runs it, prints the headline fields and none of the
+    legs that only `--full` runs (stage timings, roofline, predict, fit, CPU baseline, parity)."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    res = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1'],
+                         capture_output=True, text=True, timeout=600)
+    assert res.returncode == 0, res.stderr[-2000:]
+    lines = [ln for ln in res.stdout.splitlines() if ln.startswith('{')]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d['metric'] == 'NLL+grad evals/sec' and d['unit'] == 'evals/s' and d['higher_is_better'] is True
+    assert d['n_gpus'] == 1 and d['steps'] == 3 and d['warmup'] == 1 and d['dtype'] == 'f64'
+    assert abs(d['value'] - 1e3 / d['ms_per_step']) < 1e-6 * d['value'] and d['value'] > 0.0
+    full_only = {'stages_ms', 'stage_tflops', 'build_gbs', 'roofline', 'roofline_stages', 'predict', 'fit', 'cpu_baseline', 'parity'}
+    assert not full_only & set(d), sorted(full_only & set(d))
+    assert 'stages_ms' not in d['dist']['ranks'][0] and d['dist']['allreduce_us'] is None
 
 
 def test_bench_dumps_what_its_last_timed_step_returned(tmp_path):

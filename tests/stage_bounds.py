@@ -376,8 +376,10 @@ def check_outputs(out_row, x, Y, sr, th, V, b, z, kernel, dtype) -> Check:
 
     Gradients: G = ss o (D/2 V - z z^T / 2) contracted with dC/dtheta (formulas of finalize_kernel): each term carries
     (n + d + E_ij) u relative to |G|-with-absolute-values Ga = ss o (|D|/2 |V| + |z| |z|^T / 2) times |dC| (n: the
-    reduction over the tiles, d: the dimensions, E: the kernel evaluation).  quad and gsig: C n u (|b|^T (|b| + |z|)) in
-    float64 storage; in float32 storage the library evaluates D b^T (C o ss) z and D Y (C o ss) z (finalize_kernel /
+    reduction over the tiles, d: the dimensions, E: the kernel evaluation).  The d dimensions cover both forms of
+    C0 S_l^2 / (1 + S_l): grad_kernel's prefix / suffix products (d - 1 products) and grad_kernel_wide's prod / (1 + S_l)
+    (d products, the sum 1 + S_l and the quotient: d + 2 roundings, within d + E since E >= d + 3).  quad and gsig:
+    C n u (|b|^T (|b| + |z|)) in float64 storage; in float32 storage the library evaluates D b^T (C o ss) z and D Y (C o ss) z (finalize_kernel /
     gsig_c_kernel, the forms without the cancellation of b - z), bounded the same way as the gradients."""
     d, p = np.asarray(x).shape[1], np.asarray(Y).shape[0]
     ref, bnd = reference_outputs(x, Y, sr, th, V, b, z, kernel, dtype)
@@ -389,21 +391,29 @@ def check_outputs(out_row, x, Y, sr, th, V, b, z, kernel, dtype) -> Check:
     return Check(float(r[i]), (output_names(d, p)[i],))
 
 
-def check_predict(ghat, gvar, x0, x, sr, th, W, z, kernel, dtype) -> Check:
-    """predictions at x0 (not the training set: no nugget) against the float64 cross covariance X = scale (1 - nt)
-    C0(x0, x) o sr^T of the rounded inputs and the library's W, z:
+def check_predict(ghat, gvar, x0, x, sr, th, W, z, kernel, dtype, same=0) -> Check:
+    """predictions at x0 against the float64 cross covariance X = scale ((1 - nt) C0(x0, x) + nt I[same]) o sr^T of the
+    rounded inputs and the library's W, z:
         ghat = X z             C (n + d + E) u |X| |z|
-        gvar = scale - D |W X_i^T|^2     C (n + d + E) u |D| || |W| |X_i| ||^2 + u scale"""
+        gvar = scale - D |W X_i^T|^2     C (n + d + E) u |D| || |W| |X_i| ||^2 + u scale
+    `same` as in the C ABI (check_cov_cross): 0 = x0 are new inputs, no nugget term; else x0 row i is x row i + same - 1
+    and X carries scale nt sr_j at that column j, two roundings more, within the same relative bound of |X_ij|."""
     dev = _dev(W, z)
     d = np.asarray(x).shape[1]
     u = unit(dtype)
     ell, scale, nug, D, _ = split_theta(th, d)
     nt = nug / (1.0 + nug)
     c0, e, cut = kernel_parts(rounded(x0, dtype), rounded(x, dtype), ell, kernel, dtype, dev)
-    n = c0.shape[1]
+    n0, n = c0.shape
     s = _t(rounded(np.ones(n) if sr is None else sr, dtype), dev)
     X = scale * (1.0 - nt) * c0 * s[None, :]
     Xa = X.abs() + torch.where(cut, X.abs(), torch.zeros_like(X))
+    if same:
+        i = torch.arange(n0, device=dev)
+        j = i + same - 1
+        assert int(j[-1]) < n, (same, n0, n)
+        X[i, j] += scale * nt * s[j]
+        Xa[i, j] += abs(scale * nt) * s[j].abs()
     wgt = C * u * (n + d + e.max(dim=1).values)
     w = torch.tril(_t(W, dev))
     zz = _t(z, dev)

@@ -10,6 +10,25 @@ residual, half_logdet, L^-1, A^-1, z, quad / gradient / gsig, predictions.  (The
 only integer of the workspace is the info word, which the build launch -- or zero_stats_kernel when lcgp_potrf_logdet
 runs on its own -- resets before anything reads it.)
 
+Coverage of the input dimension.  build_kernel<T, DD, KERN> and grad_kernel<T, DD, KERN> are compiled per for_dim bucket
+DD = 2, 4, 6, 10, 16, 32; d > 32 runs build_kernel<T, 32, KERN> in chunks of 32 dimensions and grad_kernel_wide<T, KERN>.
+With T = double, float and KERN = Matern-3/2, SE that is 24 narrow (DD, KERN, T) instantiations and 4 wide (KERN, T) ones.
+  - test_every_dimension_bucket reaches all 28, both kernels and both storage types, at d = 1, 2 (DD = 2), 3, 4 (DD = 4),
+    5, 6 (DD = 6), 7, 9, 10 (DD = 10), 11, 15, 16 (DD = 16), 17, 31, 32 (DD = 32, one ragged or full chunk), and in the
+    wide kernels at 2 chunks (d = 33, 63 ragged; 64 full), 3 (65 ragged; 96 full) and 4 (97, 126 ragged), n = 130.
+  - test_wide_partials_over_many_tiles: 171 lower tiles of partials per component, q = 3: Matern-3/2 at DD = 16 (d = 16),
+    DD = 32 (17, 32) and wide at 2 and 4 chunks (33, 126); SE at DD = 32 (17) and wide at 4 chunks (126); both types.
+  - test_dimension_extremes: the wide kernels at 2 and 4 chunks (d = 33, 126), both kernels and types, with C0 past its
+    cut-off (collapsed lengthscales) and with S_j ~ 0 in every chunk (a third of the lengthscales at 1e3).
+  - test_replicated_path_dimensions: sr != 1 at DD = 6 (d = 5), DD = 32 (17) and wide at 4 chunks (126), both kernels
+    and types.
+  - test_tile_panel_and_pair_boundaries (Matern-3/2 at DD = 2, 4, 6, 10 and wide at 2 chunks) and
+    test_se_kernel_and_replicated_path (DD = 4) at the tile and panel edges of n.
+Predictions at the training inputs: test_predict_at_training_inputs calls lcgp_predict with x0 = x[lo : lo + m] and
+same = 1 + lo (lo at the 64-block and 128-pad edges and the last row; m = 1, 64, 65 and the whole set; n = 257 and 1025,
+full and rep paths) and the engine's predict_block(x, same=True) at PREDICT_CHUNK = 64 and 128, through
+check_predict(same).
+
 Run with -s to see the worst ratio per stage, dtype and case group."""
 import ctypes as C
 from collections import defaultdict
@@ -81,9 +100,10 @@ def _filled(shape, dtype, fill, device):
     return t
 
 
-def _predict(eng, x0, fill):
+def _predict(eng, x0, fill, same=0):
     """lcgp_predict (one call: n0 <= PREDICT_CHUNK) with its scratch AND its ghat / gvar rows filled with `fill`, so a
-    slot the library does not write keeps the poison and differs between the fills"""
+    slot the library does not write keeps the poison and differs between the fills.  same: as in the C ABI (0 = new
+    inputs; else x0 is x[same - 1 : same - 1 + n0])"""
     n0 = x0.shape[0]
     nbytes = C.c_size_t(0)
     _hip.check(eng.lib.lcgp_predict_scratch_bytes(eng.dtype, eng.n, eng.q_local, n0, C.byref(nbytes)), "scratch")
@@ -91,7 +111,7 @@ def _predict(eng, x0, fill):
     out = _filled((2, eng.q_local, n0), torch.float64, fill, eng.device)
     x0d = torch.as_tensor(np.ascontiguousarray(x0, np.float64)).to(eng.device, eng.tdtype).contiguous()
     _hip.check(eng.lib.lcgp_predict(eng._stream(), eng.dtype, eng.kernel_id, eng.n, eng.d, eng.p, eng.q_local, eng._p(eng.x),
-                                    eng._p(eng.sr), eng._p(eng.theta_dev), eng._p(eng.workspace), n0, eng._p(x0d), 0,
+                                    eng._p(eng.sr), eng._p(eng.theta_dev), eng._p(eng.workspace), n0, eng._p(x0d), int(same),
                                     eng._p(scratch), eng._p(out[0]), eng._p(out[1]), n0), "lcgp_predict")
     return out
 
@@ -176,7 +196,7 @@ def _check_all(group, eng, x, Y, sr, th, kernel, dtype, r, comps, x0):
     for k in comps:
         A, L, W, V, b, z = (r[s, k] for s in ("A", "L", "W", "V", "b", "z"))
         assert out[k, 2] == 0, ("info", k, out[k, 2])
-        tag = "k%d" % k
+        tag = "n%d d%d k%d" % (x.shape[0], x.shape[1], k)
         _record(group, dtype, "build", sb.check_build(A, b, x, Y, sr, th[k], kernel, dtype), tag)
         _record(group, dtype, "cholesky", sb.check_cholesky(A, L, dtype), tag)
         _record(group, dtype, "half_logdet", sb.check_half_logdet(L, out[k, 0], dtype), tag)
@@ -191,8 +211,11 @@ def _comps(n, q):
     return list(range(q)) if n <= 2000 else sorted({0, q - 1})
 
 
-def _case(group, dtype, n, d, p, q, seed, scheds, kernel="matern32", rep=False, **prob):
+def _case(group, dtype, n, d, p, q, seed, scheds, kernel="matern32", rep=False, theta=None, **prob):
+    """theta: a function th -> th applied to _problem's parameter rows (knobs _problem does not have)"""
     x, Y, sr, th = _problem(seed, n, d, p, q, rep=rep, **prob)
+    if theta is not None:
+        th = theta(th)
     x0 = np.random.default_rng(seed + 1).uniform(-0.1, 1.1, (37, d))
     eng = HotPathEngine(x, Y, sr=sr, q_local=q, dtype=dtype, kernel=kernel)
     comps = _comps(n, q)
@@ -361,3 +384,133 @@ def test_cfg3_full_size_float32():
         _record(g, dt, "z", sb.check_z(V, b, z, dt), k)
         del A, L, W, V, b, z
         torch.cuda.empty_cache()
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# input dimensions: every build_kernel / grad_kernel instantiation (for_dim: DD = 2, 4, 6, 10, 16, 32) and grad_kernel_wide
+# with one to four 32-dimension chunks, both kernels, both storage types
+# ----------------------------------------------------------------------------------------------------------------------
+BUCKET_DIMS = (1, 2, 3, 4, 5, 6, 7, 9, 10, 11, 15, 16, 17, 31, 32, 33, 63, 64, 65, 96, 97, 126)
+KERNELS = ("matern32", "se")
+GROUP = {"matern32": "m32", "se": "se"}
+
+
+@pytest.mark.parametrize("kernel", KERNELS)
+@pytest.mark.parametrize("dtype", ["float64", "float32"])
+def test_every_dimension_bucket(dtype, kernel):
+    """each for_dim bucket's edges and a padded interior point (DD = 2: 1, 2; 4: 3, 4; 6: 5, 6; 10: 7, 9, 10; 16: 11, 15,
+    16; 32: 17, 31, 32) and the wide gradient at 1 .. 4 chunks, full and ragged (33, 63, 64, 65, 96, 97, 126); n = 130
+    (three 64-blocks, the last ragged), q = 2, default and plainest schedule, every stage"""
+    for i, d in enumerate(BUCKET_DIMS):
+        _case("dim_" + GROUP[kernel], dtype, 130, d, 3, 2, 700 + i, ({}, PLAIN), kernel=kernel)
+
+
+@pytest.mark.parametrize("dtype", ["float64", "float32"])
+def test_wide_partials_over_many_tiles(dtype):
+    """n = 1025 (npad = 1152: 171 lower tiles), q = 3: the per-tile gradient partials (stride DMAX + 2 narrow, d + 2 wide, a
+    full 128-double slot at d = 126) of every component; a partial at the wrong stride or component offset lands in a
+    neighbour's slot and fails that component's outputs check"""
+    cases = [("matern32", d) for d in (16, 17, 32, 33, 126)] + [("se", d) for d in (17, 126)]
+    for i, (kernel, d) in enumerate(cases):
+        _case("tiles_" + GROUP[kernel], dtype, 1025, d, 3, 3, 800 + i, ({},), kernel=kernel)
+
+
+def _cut_ell(d, dtype, kernel):
+    """_problem's log-lengthscale band whose mean exponent is 1.1 times the C0 cut-off of the dtype (x uniform in the unit
+    box: E|dx| = 1/3, E dx^2 = 1/6): 75 - 93 % of the entries pass the cut-off (at d = 126 all of those only once a later
+    32-dimension chunk is summed, at d = 33 5 - 8 % only with dimension 32), and the rest sit close to it"""
+    f = 1.1 * abs(sb.EXP_FLOOR[dtype])
+    ell = d / (3.0 * f) if kernel == "matern32" else np.sqrt(d / (12.0 * f))
+    c = float(np.log(ell / np.sqrt(d)))
+    return (c - 0.15, c + 0.15)
+
+
+def _ard(th, d):
+    """every third lengthscale at 1e3 (S ~ 1e-3: those dimensions barely count), spread over the chunks"""
+    th = th.copy()
+    th[:, 0:d:3] = 1e3
+    return th
+
+
+@pytest.mark.parametrize("dtype", ["float64", "float32"])
+def test_dimension_extremes(dtype):
+    """d = 33 and 126, n = 257, both kernels: (a) collapsed lengthscales, most C0 entries past the exp cut-off, at d = 126
+    only across chunk boundaries (_cut_ell); (b) ARD-style lengthscales, a third of the dimensions at 1e3 and the rest short: the
+    wide kernel's prod / (1 + S_j) at S_j ~ 0 and exponent sums spread over every chunk.  A stays well conditioned (C0
+    small off the diagonal, the nugget on it)"""
+    for i, d in enumerate((33, 126)):
+        for j, kernel in enumerate(KERNELS):
+            seed = 900 + 10 * i + 2 * j
+            _case("collapse_" + GROUP[kernel], dtype, 257, d, 3, 2, seed, ({},), kernel=kernel, ell=_cut_ell(d, dtype, kernel))
+            _case("ard_" + GROUP[kernel], dtype, 257, d, 3, 2, seed + 1, ({},), kernel=kernel, ell=(-2.0, -0.5),
+                  theta=lambda th, d=d: _ard(th, d))
+
+
+@pytest.mark.parametrize("dtype", ["float64", "float32"])
+def test_replicated_path_dimensions(dtype):
+    """sr != 1 (replicates) at d = 5 (DD = 6), 17 (DD = 32) and 126 (four wide chunks), both kernels, n = 200"""
+    for i, d in enumerate((5, 17, 126)):
+        for j, kernel in enumerate(KERNELS):
+            _case("rep_" + GROUP[kernel], dtype, 200, d, 3, 2, 950 + 2 * i + j, ({}, PLAIN), kernel=kernel, rep=True)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# predictions at the training inputs: the nugget term of x0 row i on column i + same - 1
+# ----------------------------------------------------------------------------------------------------------------------
+PRED_LO = (0, 1, 63, 64, 127, 128)
+PRED_M = (1, 64, 65)
+
+
+def _train_slices(n):
+    """(lo, m): lo at 0, 1, 63, 64, 127, 128 and the last row, m = 1, 64, 65 where they fit, and the whole set"""
+    out = [(lo, m) for lo in PRED_LO + (n - 1,) for m in PRED_M if lo + m <= n]
+    return sorted(set(out)) + [(0, n)]
+
+
+def _fitted(seed, n, d, q, dtype, kernel, rep):
+    x, Y, sr, th = _problem(seed, n, d, 3, q, rep=rep)
+    eng = HotPathEngine(x, Y, sr=sr, q_local=q, dtype=dtype, kernel=kernel)
+    out = eng.evaluate(th)
+    assert np.all(out[:, 2] == 0), out[:, 2]
+    Wz = [(_fetch(eng, 1, k, True), _fetch(eng, 1, k, False)) for k in range(q)]
+    return eng, x, sr, th, Wz
+
+
+def _run_predict(eng, x0, fill, same):
+    return {"pred": _predict(eng, x0, fill, same)}
+
+
+def _run_predict_block(eng, x0, fill, chunk):
+    """engine.predict_block(x0, same=True) with PREDICT_CHUNK = chunk and the engine's scratch filled with `fill`"""
+    import lcgp_amd.engine as eng_mod
+    old = eng_mod.PREDICT_CHUNK
+    try:
+        eng_mod.PREDICT_CHUNK = chunk
+        nbytes = eng._nbytes("lcgp_predict_scratch_bytes", eng.dtype, eng.n, eng.q_local, min(chunk, x0.shape[0]))
+        eng._grow_scratch(nbytes).fill_(fill)
+        return {"pred": eng.predict_block(x0, same=True).clone()}
+    finally:
+        eng_mod.PREDICT_CHUNK = old
+
+
+@pytest.mark.parametrize("kernel", KERNELS)
+@pytest.mark.parametrize("dtype", ["float64", "float32"])
+def test_predict_at_training_inputs(dtype, kernel):
+    """lcgp_predict with x0 = x[lo : lo + m] and same = 1 + lo (the nugget term scale nt sr_j on column lo + i of row i)
+    at the 64-block and 128-pad edges, one row to the whole set, n = 257 and 1025, full and rep paths; then the engine's
+    chunked predict_block(x, same=True) with PREDICT_CHUNK = 64 and 128, whose chunks after the first pass same = 1 + lo.
+    Every call on the three fills (bitwise), every component through check_predict(same)."""
+    for i, (n, rep) in enumerate(((257, False), (257, True), (1025, False), (1025, True))):
+        group = "same_" + GROUP[kernel]
+        eng, x, sr, th, Wz = _fitted(1000 + i, n, 3, 2, dtype, kernel, rep)
+        for lo, m in _train_slices(n):
+            x0 = x[lo:lo + m]
+            r = _poisoned(_run_predict, eng, x0, 1 + lo)["pred"]
+            for k, (W, z) in enumerate(Wz):
+                c = sb.check_predict(r[0, k], r[1, k], x0, x, sr, th[k], W, z, kernel, dtype, same=1 + lo)
+                _record(group, dtype, "predict", c, "n%d rep%d lo%d m%d k%d" % (n, rep, lo, m, k))
+        for chunk in (64, 128):
+            r = _poisoned(_run_predict_block, eng, x, chunk)["pred"]
+            for k, (W, z) in enumerate(Wz):
+                c = sb.check_predict(r[0, k], r[1, k], x, x, sr, th[k], W, z, kernel, dtype, same=1)
+                _record(group, dtype, "predict_block", c, "n%d rep%d chunk%d k%d" % (n, rep, chunk, k))

@@ -6,7 +6,12 @@ end-to-end NLL within the 1e-6 parity bar: the bar the rest of the suite uses ca
 
 The joint path (X, U, Sigma + tau I, its factor, the draws) gets the same treatment on an emulated path with q = 3
 components: a perturbed tile of Sigma, a K-tile left out of D U U^T, tau of the wrong component, a draw through an
-upper triangle that was not zeroed, draws shifted at a chunk split and a float32-accurate Sigma each fail their check."""
+upper triangle that was not zeroed, draws shifted at a chunk split and a float32-accurate Sigma each fail their check.
+
+At the input dimensions of the d-templated kernels (d = 17, 33, 126) the emulated path passes as well, and a last chunk
+staged with the lengthscales of the chunk before it, stale padding dimensions, one lengthscale gradient 1e-8 off in the
+fourth 32-dimension chunk (which the oracle's normwise bar passes) and swapped g_scale / g_nug accumulators each fail;
+predictions at training rows fail check_predict when the nugget term sits one column off or is missing."""
 import numpy as np
 import pytest
 import torch
@@ -30,13 +35,14 @@ def _r(a, dtype):
 
 
 def _emulate(x, Y, th, dtype, kernel="matern32"):
-    """every stage computed in float64 from the previous stage's stored result and rounded to the storage type"""
+    """every stage computed in float64 from the previous stage's stored result and rounded to the storage type (any input
+    dimension: d = x.shape[1] places psi in th)"""
     A = _r(sb.reference_A(x, None, th, kernel, dtype)[0].numpy(), dtype)
     L = _r(np.linalg.cholesky(A), dtype)
     W = _r(np.linalg.solve(L, np.eye(x.shape[0])), dtype)
     W = np.tril(W)
     V = _r(W.T @ W, dtype)
-    psi = th[D_IN + 3:]
+    psi = th[x.shape[1] + 3:]
     b = _r(_r(Y, dtype).T @ psi, dtype)
     z = _r(V @ b, dtype)
     ref, _ = sb.reference_outputs(x, Y, None, th, V, b, z, kernel, dtype)
@@ -748,3 +754,142 @@ def test_vr_defect_5_second_pass_written_at_row_zero(vr):
     Ur[VR_XBLK:] = 0.0
     out = _vr_out(Ur, v["Uc"], v["xr"], v["xc"], v["w"], v["g"]["th"], v["r"], dtype)
     assert _check_vr(v, out, dtype).ratio > 1
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# input dimensions: the bounds at the widths of for_dim's last bucket (d = 17) and of four wide chunks (d = 126), and the
+# defects of the d-templated build and gradient kernels -- a chunk of lengthscales off by 32 dimensions, stale padding
+# dimensions, one lengthscale gradient off in the fourth chunk, swapped accumulator slots -- and of predict at training rows
+# ----------------------------------------------------------------------------------------------------------------------
+N_WIDE = 200
+
+
+def _wide_problem(d, seed=0, n=N_WIDE):
+    rng = np.random.default_rng(seed)
+    x = rng.uniform(0.0, 1.0, (n, d))
+    Y = rng.standard_normal((P, n))
+    return x, Y, _theta(d, seed + 1)
+
+
+@pytest.fixture(scope="module")
+def wide():
+    """d -> (x, Y, th) at d = 17, 33 and 126 (ell uniform in [0.3, 0.9] sqrt(d): every dimension distinct)"""
+    return {d: _wide_problem(d, seed=40 + d) for d in (17, 33, 126)}
+
+
+def _contraction(e, x, th, dtype, kernel="matern32"):
+    """the accumulators of grad_kernel in float64 from the emulated V, z: sum G F_l (l < d), sum G C0, trace G"""
+    d = x.shape[1]
+    ell, scale, nug, Dk, _ = sb.split_theta(th, d)
+    V, z = torch.as_tensor(e["V"]), torch.as_tensor(e["z"])
+    G = 0.5 * Dk * V - 0.5 * z[:, None] * z[None, :]
+    xr = sb.rounded(x, dtype)
+    c0 = sb.kernel_parts(xr, xr, ell, kernel, "float64")[0]
+    return [float((G * f).sum()) for f in sb.dC0(xr, xr, ell, kernel)] + [float((G * c0).sum()), float(torch.trace(G))]
+
+
+def _finalize(out, sums, th, d):
+    """the gradient slots of an output row from the accumulators, as finalize_kernel forms them"""
+    ell, scale, nug, Dk, _ = sb.split_theta(th, d)
+    nt = nug / (1 + nug)
+    out = out.copy()
+    for l in range(d):
+        out[3 + l] = scale * (1 - nt) / ell[l] * sums[l]
+    out[3 + d] = (1 - nt) * sums[d] + nt * sums[d + 1]
+    out[4 + d] = scale * (sums[d + 1] - sums[d]) / (1 + nug) ** 2
+    return out
+
+
+@pytest.mark.parametrize("kernel", ["matern32", "se"])
+@pytest.mark.parametrize("dtype", ["float64", "float32"])
+def test_emulated_path_passes_at_wide_dimensions(wide, dtype, kernel):
+    for d in (17, 126):
+        x, Y, th = wide[d]
+        e = _emulate(x, Y, th, dtype, kernel)
+        for stage, c in _checks(e, x, Y, th, dtype, kernel).items():
+            assert c.ratio < 0.5, (d, stage, c)
+        x0 = np.random.default_rng(d).uniform(-0.1, 1.1, (37, d))
+        X = _cross(x0, x, None, th, dtype, kernel)
+        gvar = th[d] - th[d + 2] * np.sum((X @ e["W"].T) ** 2, axis=1)
+        c = sb.check_predict(X @ e["z"], gvar, x0, x, None, th, e["W"], e["z"], kernel, dtype)
+        assert c.ratio < 0.5, (d, "predict", c)
+
+
+@pytest.mark.parametrize("kernel", ["matern32", "se"])
+@pytest.mark.parametrize("dtype", ["float64", "float32"])
+def test_wide_defect_1_last_chunk_with_the_lengthscales_of_the_previous_one(wide, dtype, kernel):
+    """d = 126: the dimensions 96 .. 125 of A staged with ell[64 .. 93] (d0 off by 32 in the last chunk)"""
+    x, Y, th = wide[126]
+    bad = th.copy()
+    bad[96:126] = th[64:94]
+    A = _r(sb.reference_A(x, None, bad, kernel, dtype)[0].numpy(), dtype)
+    b = _emulate(x, Y, th, dtype, kernel)["b"]
+    assert sb.check_build(_r(sb.reference_A(x, None, th, kernel, dtype)[0].numpy(), dtype), b, x, Y, None, th, kernel,
+                          dtype).ratio < 0.5
+    c = sb.check_build(A, b, x, Y, None, th, kernel, dtype)
+    assert c.ratio > 1, c
+
+
+@pytest.mark.parametrize("kernel", ["matern32", "se"])
+@pytest.mark.parametrize("dtype", ["float64", "float32"])
+def test_wide_defect_2_stale_padding_dimensions(wide, dtype, kernel):
+    """d = 33: the second chunk holds dimension 32 and 31 padding columns, which keep the first chunk's staged columns 1 ..
+    31 instead of zeros -- those dimensions count twice in the exponent (and in the Matern polynomial)"""
+    x, Y, th = wide[33]
+    ell, scale, nug, Dk, _ = sb.split_theta(th, 33)
+    nt = nug / (1 + nug)
+    xr = _r(x, dtype)
+    c0 = sb.kernel_parts(xr, xr, ell, kernel, "float64")[0].numpy()
+    extra = sb.kernel_parts(xr[:, 1:32], xr[:, 1:32], ell[1:32], kernel, "float64")[0].numpy()
+    A = _r(np.eye(N_WIDE) + Dk * scale * ((1 - nt) * c0 * extra + nt * np.eye(N_WIDE)), dtype)
+    b = _emulate(x, Y, th, dtype, kernel)["b"]
+    c = sb.check_build(A, b, x, Y, None, th, kernel, dtype)
+    assert c.ratio > 1, c
+
+
+def test_wide_defect_3_one_lengthscale_gradient_off_in_the_fourth_chunk(wide):
+    """d = 126, float64: g_ell_110 (fourth 32-dimension chunk) off by 1e-8 relative.  check_outputs names that entry; the
+    oracle bar max|dg| <= 1e-5 max|g| of the parity tests passes it"""
+    x, Y, th = wide[126]
+    e = _emulate(x, Y, th, "float64")
+    out = e["out"].copy()
+    out[3 + 110] *= 1 + 1e-8
+    c = sb.check_outputs(out, x, Y, None, th, e["V"], e["b"], e["z"], "matern32", "float64")
+    assert c.ratio > 1 and c.where == ("g_ell110",), c
+    g, gbad = e["out"][3:], out[3:]
+    assert np.max(np.abs(gbad - g)) <= 1e-5 * np.max(np.abs(g))
+
+
+@pytest.mark.parametrize("d", [5, 17, 126])
+@pytest.mark.parametrize("dtype", ["float64", "float32"])
+def test_wide_defect_4_swapped_accumulator_slots(wide, dtype, d):
+    """g_scale / g_nug formed from the wrong accumulators of the partial row (grad_kernel's e = tid < d ? tid : DD + tid - d
+    mapping): the two swapped, or each read one slot early (g_scale from the g_ell_{d-1} accumulator)"""
+    x, Y, th = wide[d] if d in wide else _wide_problem(d, seed=40 + d)
+    e = _emulate(x, Y, th, dtype)
+    sums = _contraction(e, x, th, dtype)
+    ok = _finalize(e["out"], sums, th, d)
+    assert sb.check_outputs(ok, x, Y, None, th, e["V"], e["b"], e["z"], "matern32", dtype).ratio < 0.5
+    swapped = sums[:d] + [sums[d + 1], sums[d]]
+    early = sums[:d] + [sums[d - 1], sums[d]]
+    for bad in (swapped, early):
+        c = sb.check_outputs(_finalize(e["out"], bad, th, d), x, Y, None, th, e["V"], e["b"], e["z"], "matern32", dtype)
+        assert c.ratio > 1 and c.where[0] in ("g_scale", "g_nug"), c
+
+
+@pytest.mark.parametrize("rep", [False, True])
+@pytest.mark.parametrize("dtype", ["float64", "float32"])
+def test_predict_defect_nugget_one_row_off(dtype, rep):
+    """x0 = the training rows 10 .. 109 (same = 11): check_predict(same = 11) passes the predictions and fails them with the
+    nugget term one column early (same = 10), one late (12) or missing (0)"""
+    g = _pgrad_problem(dtype, rep=rep)
+    x, sr, th = g["x"], g["sr"], g["th"]
+    lo, m = 10, 100
+    x0 = x[lo:lo + m]
+    X = _cross(x0, x, sr, th, dtype, match=np.arange(lo, lo + m))
+    ghat = X @ g["z"]
+    gvar = th[D_IN] - th[D_IN + 2] * np.sum((X @ g["W"].T) ** 2, axis=1)
+    assert sb.check_predict(ghat, gvar, x0, x, sr, th, g["W"], g["z"], "matern32", dtype, same=lo + 1).ratio < 0.5
+    for same in (lo, lo + 2, 0):
+        c = sb.check_predict(ghat, gvar, x0, x, sr, th, g["W"], g["z"], "matern32", dtype, same=same)
+        assert c.ratio > 1, (same, c)

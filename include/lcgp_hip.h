@@ -354,6 +354,52 @@ int lcgp_variance_reduction(void* stream, int dtype, int kernel_id, int n, int d
                             int n_cand, const void* x_cand, const int* match_host /*host or NULL*/, const int* match,
                             int cand_row0, int r, void* scratch, double* out, int out_stride);
 
+/* Greedy batch design by sequential ALC at fixed parameters (no counterpart in the reference): pick the candidate with the
+ * largest score, condition the posterior covariance on r runs there (ALC does not depend on the runs' outputs), score again.
+ * Per local component k, with Sigma, Sigma^h, den as in lcgp_variance_reduction and R_k = N_k / den_k its result:
+ *     score(c) = sum_k omega_k R_k(c)        over the local components in ascending order (rounded products and sums),
+ *                                            -inf at candidates already picked
+ *   pick j:  pcol = Sigma_k(cand, j),  scol = Sigma_k(ref, j)  of the CURRENT posterior:
+ *              C^x(., j) - D_k U_k(.) . U_k(j) - sum_{s<t} hist[s, .] V[s, j]          (C^x: kernel without nugget)
+ *            v = pcol / sqrt(den_k(j)),  u = scol / sqrt(den_k(j)),  V[t, :] = v,  Uh[t, :] = u
+ *            g = C^x(cand, ref) (w o u) - D_k U_cand (U_ref^T (w o u)) - sum_{s<t} V[s, :] (Uh[s, :] . (w o u))
+ *            N <- max(N - 2 v o g + v o v (u . (w o u)), 0),   h <- h - v o v,   R <- N / (max(h, 0) + 1 / (D_k r))
+ * a pivoted Cholesky of the posterior covariance over the candidates carried lazily: nothing of size n_ref x n_cand or
+ * n_cand x n_cand is stored.  Two different points never share a nugget: the caller refuses duplicate candidates.
+ *
+ *   1. lcgp_select_begin forms U_k / gvar_k of the reference set and of ALL candidates (resident in `scratch`; candidates pass
+ *      through the one X work area `pass_rows` <= 2048 rows at a time), then R_k with the launches of lcgp_variance_reduction:
+ *      bitwise what that entry writes for the same sets.  match_host / match, w_ref, r as there.  h_k = gvar_k of the candidates.
+ *   2. lcgp_select_score writes the score row of step `step` to out (n_cand doubles, device; NULL = not wanted) and the argmax
+ *      (lowest index wins ties) into the device word picks[step] of the scratch (lcgp_select_picks returns the address of picks).
+ *      omega: q_local doubles (device).
+ *   3. lcgp_select_condition performs the step above for the pick it reads from DEVICE memory (`pick`: picks + step, or any
+ *      device int the caller wrote), for all local components, and marks the candidate picked.  Steps 2 and 3 for step = 0 ..
+ *      size - 1 can be enqueued back to back without a host synchronisation.  Five launches: (i) one wave per row of
+ *      [U_cand; U_ref] . U_cand[j] (K = n) with the kernel value, the history correction and the scaling in its epilogue;
+ *      (ii) y = U_ref^T (w o u) over fixed chunks of 32 reference rows, the chunks' partials summed in ascending order (no
+ *      atomics), and the history dot products; (iii) one wave per candidate: U_cand y, the on-the-fly C^x(cand, ref) (w o u) and
+ *      the update of N / h.  16-byte loads, double accumulation in both dtypes (float32: U is float32, all else double).
+ *   lcgp_select_state copies R (which = 0) or h (which = 1), q_local rows of n_cand doubles, to `out` (device).
+ * Results are bitwise independent of the scratch content on entry to step 1, of q_local and of pass_rows.
+ * scratch: lcgp_select_scratch_bytes bytes -- q_local (n_ref + n_cand) npad elements for the two U, one X work area of at most
+ *   2048 rows, the partial sums of lcgp_variance_reduction for all candidates, and in double: R, h, V (size x n_cand), Uh (size x
+ *   n_ref), ceil(n_ref / 32) npad partials of y, the inputs divided by ell (q_local (n_ref + n_cand) d), the score state.
+ * Traffic per step and component: U_ref and U_cand twice each. */
+int lcgp_select_scratch_bytes(int dtype, int n, int d, int q_local, int n_ref, int n_cand, int size, size_t* bytes /*host out*/);
+int lcgp_select_begin(void* stream, int dtype, int kernel_id, int n, int d, int p, int q_local,
+                      const void* x, const void* sr, const double* theta, const void* workspace,
+                      int n_ref, const void* x_ref, const double* w_ref,
+                      int n_cand, const void* x_cand, const int* match_host /*host or NULL*/, const int* match,
+                      int r, int size, int pass_rows, void* scratch);
+int lcgp_select_score(void* stream, int dtype, int n, int d, int q_local, int n_ref, int n_cand, int size, int step,
+                      const double* omega, void* scratch, double* out /*device or NULL*/);
+int lcgp_select_picks(int dtype, int n, int d, int q_local, int n_ref, int n_cand, int size, void* scratch, int** picks /*host out*/);
+int lcgp_select_condition(void* stream, int dtype, int kernel_id, int n, int d, int p, int q_local, const double* theta,
+                          int n_ref, int n_cand, int size, int r, int step, const int* pick /*device*/, void* scratch);
+int lcgp_select_state(void* stream, int dtype, int n, int d, int q_local, int n_ref, int n_cand, int size, int which,
+                      const void* scratch, double* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -71,6 +71,12 @@ SIGNATURES = {
     "lcgp_variance_reduction_prepare": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
     "lcgp_variance_reduction": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _i,
                                      _vp, _vp, _i]),
+    "lcgp_select_scratch_bytes": (_i, [_i, _i, _i, _i, _i, _i, _i, C.POINTER(C.c_size_t)]),
+    "lcgp_select_begin": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "lcgp_select_score": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "lcgp_select_picks": (_i, [_i, _i, _i, _i, _i, _i, _i, _vp, C.POINTER(_vp)]),
+    "lcgp_select_condition": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    "lcgp_select_state": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
 }
 
 _lib = None

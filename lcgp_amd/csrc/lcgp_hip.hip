@@ -23,7 +23,7 @@
 #include "../../include/lcgp_hip.h"
 #include "fill_sched.h"
 
-#define LCGP_VERSION 550
+#define LCGP_VERSION 560
 
 namespace {
 
@@ -3653,6 +3653,423 @@ int check_vr(int n_ref, int n_cand) {
     return 0;
 }
 
+// ---------------------------------------------------------------------------------------------------
+// Greedy batch design by sequential ALC (lcgp_hip.h: lcgp_select_*; no counterpart in the reference).  The state per local
+// component is R(c) = N(c) / den(c) (what lcgp_variance_reduction writes), h(c) (the candidates' gvar) and the history rows
+// V[s, :] (candidates) / Uh[s, :] (reference points) of the picks made so far: a pivoted Cholesky of the posterior covariance
+// over the candidates carried lazily.  A step streams U_cand and U_ref twice each; nothing of size n_ref x n_cand is stored.
+// The step kernels are bandwidth-bound row passes: one wave per row of U, 16-byte loads, double sums in a fixed order.
+// ---------------------------------------------------------------------------------------------------
+constexpr int SEL_RB = 32;          // reference rows per partial of the transposed product (fixed: results do not depend on sizes)
+
+struct SelLay {
+    int rrows, crows, xrows, nrt, ldp, nchunk;
+    size_t uslab_r, uslab_c, xslab;
+    size_t off_uref, off_gvr, off_ghr, off_x, off_uc, off_ghc, off_h, off_part, off_R, off_V, off_Uh, off_ypart, off_y, off_b,
+        off_xsr, off_xsc, off_w, off_mask, off_picks, total;
+};
+
+inline SelLay sel_carve(int dtype, int n, int d, int q, int n_ref, int n_cand, int size) {
+    SelLay L;
+    const size_t esz = dtype == LCGP_F64 ? 8 : 4, npad = round_up(n, 2 * TS);
+    L.rrows = round_up(n_ref, 2 * TS) + TS;                 // as VrLay
+    L.crows = predict_pad(n_cand) + 2 * TS;                 // the last pass of lcgp_select_begin writes whole tiles past n_cand
+    L.xrows = min(VR_XBLK, max(predict_pad(n_ref), predict_pad(n_cand)));
+    L.nrt = (n_ref + TS - 1) / TS;
+    L.ldp = round_up(n_cand, TS);
+    L.nchunk = (n_ref + SEL_RB - 1) / SEL_RB;
+    L.uslab_r = (size_t)L.rrows * npad;
+    L.uslab_c = (size_t)L.crows * npad;
+    L.xslab = (size_t)L.xrows * npad;
+    const size_t D8 = sizeof(double);
+    size_t o = 0;
+    L.off_uref = o; o = align256(o + (size_t)q * L.uslab_r * esz);
+    L.off_uc = o; o = align256(o + (size_t)q * L.uslab_c * esz);
+    L.off_x = o; o = align256(o + (size_t)q * L.xslab * esz);
+    L.off_gvr = o; o = align256(o + (size_t)q * n_ref * D8);
+    L.off_ghr = o; o = align256(o + (size_t)q * n_ref * D8);
+    L.off_ghc = o; o = align256(o + (size_t)q * n_cand * D8);
+    L.off_h = o; o = align256(o + (size_t)q * n_cand * D8);
+    L.off_part = o; o = align256(o + (size_t)q * L.nrt * L.ldp * D8);
+    L.off_R = o; o = align256(o + (size_t)q * n_cand * D8);
+    L.off_V = o; o = align256(o + (size_t)q * size * n_cand * D8);
+    L.off_Uh = o; o = align256(o + (size_t)q * size * n_ref * D8);
+    L.off_ypart = o; o = align256(o + (size_t)q * L.nchunk * npad * D8);
+    L.off_y = o; o = align256(o + (size_t)q * npad * D8);
+    L.off_b = o; o = align256(o + (size_t)q * size * D8);
+    L.off_xsr = o; o = align256(o + (size_t)q * n_ref * d * D8);
+    L.off_xsc = o; o = align256(o + (size_t)q * n_cand * d * D8);
+    L.off_w = o; o = align256(o + (size_t)n_ref * D8);
+    L.off_mask = o; o = align256(o + (size_t)n_cand * sizeof(int));
+    L.off_picks = o; o = align256(o + (size_t)size * sizeof(int));
+    L.total = o;
+    return L;
+}
+
+// sums over the 64 lanes in a fixed order; every lane returns the total
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+
+// 16 bytes of a row: VEC = 2 doubles or 4 floats
+template <typename T> struct SelVec;
+template <> struct SelVec<double> { typedef double v __attribute__((ext_vector_type(2))); static constexpr int N = 2; };
+template <> struct SelVec<float> { typedef float v __attribute__((ext_vector_type(4))); static constexpr int N = 4; };
+
+// a . b over k < n for two rows of a U slab (16-byte aligned: rows are npad apart), double accumulation; one wave, every lane
+// returns the sum.  Lane l takes the 16-byte pieces l, l + 64, ..
+template <typename T>
+__device__ __forceinline__ double sel_row_dot(const T* __restrict__ a, const T* __restrict__ b, int n, int lane) {
+    constexpr int VN = SelVec<T>::N;
+    typedef typename SelVec<T>::v V;
+    double acc = 0.0;
+    const int nv = n / VN;
+#pragma unroll 4
+    for (int i = lane; i < nv; i += 64) {
+        const V x = *(const V*)(a + (size_t)i * VN), y = *(const V*)(b + (size_t)i * VN);
+#pragma unroll
+        for (int e = 0; e < VN; ++e) acc = fma((double)x[e], (double)y[e], acc);
+    }
+    const int tail = nv * VN + lane;
+    if (tail < n) acc = fma((double)a[tail], (double)b[tail], acc);
+    return wave_sum(acc);
+}
+
+// the same with a double vector y as the second operand
+template <typename T>
+__device__ __forceinline__ double sel_row_dot_y(const T* __restrict__ a, const double* __restrict__ y, int n, int lane) {
+    constexpr int VN = SelVec<T>::N;
+    typedef typename SelVec<T>::v V;
+    typedef SelVec<double>::v D2;
+    double acc = 0.0;
+    const int nv = n / VN;
+#pragma unroll 4
+    for (int i = lane; i < nv; i += 64) {
+        const V x = *(const V*)(a + (size_t)i * VN);
+#pragma unroll
+        for (int e = 0; e < VN; e += 2) {
+            const D2 yy = *(const D2*)(y + (size_t)i * VN + e);
+            acc = fma((double)x[e], yy[0], acc);
+            acc = fma((double)x[e + 1], yy[1], acc);
+        }
+    }
+    const int tail = nv * VN + lane;
+    if (tail < n) acc = fma((double)a[tail], y[tail], acc);
+    return wave_sum(acc);
+}
+
+// the product kernel (without scale and nugget) of two inputs already divided by ell, as cross_kernel forms it
+template <int KERN>
+__device__ __forceinline__ double sel_kern(const double* __restrict__ a, const double* __restrict__ b, int d) {
+    double pl = 1.0, ss = 0.0;
+    for (int l = 0; l < d; ++l) {
+        if constexpr (KERN == 0) {
+            const double sd = fabs(a[l] - b[l]);
+            pl = fma(pl, sd, pl);
+            ss -= sd;
+        } else {
+            const double df = a[l] - b[l];
+            ss = fma(-0.5 * df, df, ss);
+        }
+    }
+    return KERN == 0 ? fmin(pl, poly_cap<double>()) * exp_nonpos(ss) : exp_nonpos(ss);
+}
+
+// xs[k, i, l] = x[i, l] / ell_k[l] in double
+template <typename T>
+__global__ __launch_bounds__(256) void sel_scale_kernel(const T* __restrict__ x, int m, int d, const double* __restrict__ theta,
+                                                        int tw, double* __restrict__ xs) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x, k = blockIdx.y;
+    if (e >= m * d) return;
+    xs[(size_t)k * m * d + e] = (double)x[e] / theta[(size_t)k * tw + (e % d)];
+}
+
+__global__ __launch_bounds__(256) void sel_init_kernel(const double* __restrict__ w_in, int n_ref, double* __restrict__ w,
+                                                       int n_cand, int* __restrict__ mask, int size, int* __restrict__ picks) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n_ref) w[i] = w_in[i];
+    if (i < n_cand) mask[i] = 0;
+    if (i < size) picks[i] = 0;
+}
+
+// (i) the current covariance column of pick j over candidates and reference points, scaled:
+//   row c < n_cand:  V[t, c]  = (C^x(c, j) - D U_cand(c) . U_cand(j) - sum_{s<t} V[s, c]  V[s, j]) / sqrt(den_j)
+//   row n_cand + r:  Uh[t, r] = (C^x(r, j) - D U_ref(r)  . U_cand(j) - sum_{s<t} Uh[s, r] V[s, j]) / sqrt(den_j)
+// one wave per row, four rows per workgroup
+template <typename T, int KERN>
+__global__ __launch_bounds__(256) void sel_col_kernel(const T* __restrict__ Uc, size_t sUc, const T* __restrict__ Ur, size_t sUr,
+                                                      int npad, int n, int n_cand, int n_ref, const double* __restrict__ xsc,
+                                                      const double* __restrict__ xsr, int d, const double* __restrict__ theta,
+                                                      int tw, int nrep, const double* __restrict__ h, double* __restrict__ V,
+                                                      double* __restrict__ Uh, int size, int t, const int* __restrict__ pick) {
+    const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6), k = blockIdx.y;
+    if (row >= n_cand + n_ref) return;                      // (uniform per wave)
+    const int j = *pick;
+    const double* th = theta + (size_t)k * tw;
+    const double scale = th[d], nug = th[d + 1], D = th[d + 2];
+    const double coff = scale * (1.0 - nug / (1.0 + nug));
+    const bool isc = row < n_cand;
+    const int r = isc ? row : row - n_cand;
+    const T* __restrict__ a = isc ? Uc + (size_t)k * sUc + (size_t)r * npad : Ur + (size_t)k * sUr + (size_t)r * npad;
+    const T* __restrict__ b = Uc + (size_t)k * sUc + (size_t)j * npad;
+    const double dot = sel_row_dot<T>(a, b, n, lane);
+    const double* xr = isc ? xsc + ((size_t)k * n_cand + r) * d : xsr + ((size_t)k * n_ref + r) * d;
+    const double c = sel_kern<KERN>(xr, xsc + ((size_t)k * n_cand + j) * d, d);
+    double* __restrict__ H = isc ? V + (size_t)k * size * n_cand : Uh + (size_t)k * size * n_ref;
+    const int ldh = isc ? n_cand : n_ref;
+    const double* __restrict__ Vk = V + (size_t)k * size * n_cand;
+    double hs = 0.0;
+    for (int s = lane; s < t; s += 64) hs = fma(H[(size_t)s * ldh + r], Vk[(size_t)s * n_cand + j], hs);
+    hs = wave_sum(hs);
+    if (lane == 0) {
+        const double den = fmax(h[(size_t)k * n_cand + j], 0.0) + 1.0 / (D * (double)nrep);
+        H[(size_t)t * ldh + r] = (fma(-D, dot, coff * c) - hs) / sqrt(den);
+    }
+}
+
+// (ii) y = U_ref^T (w o u), first half: ypart[k, chunk, col] over the SEL_RB reference rows of the chunk, one 16-byte piece of
+// every row per thread
+template <typename T>
+__global__ __launch_bounds__(256) void sel_ty_part_kernel(const T* __restrict__ Ur, size_t sUr, int npad, int n, int n_ref,
+                                                          const double* __restrict__ w, const double* __restrict__ Uh, int size,
+                                                          int t, int nchunk, double* __restrict__ ypart) {
+    constexpr int VN = SelVec<T>::N;
+    typedef typename SelVec<T>::v V;
+    __shared__ double wu[SEL_RB];
+    const int ch = blockIdx.y, k = blockIdx.z, r0 = ch * SEL_RB;
+    const int rows = min(SEL_RB, n_ref - r0);
+    if (threadIdx.x < SEL_RB)
+        wu[threadIdx.x] = threadIdx.x < rows ? w[r0 + threadIdx.x] * Uh[((size_t)k * size + t) * n_ref + r0 + threadIdx.x] : 0.0;
+    __syncthreads();
+    const int col = (blockIdx.x * 256 + threadIdx.x) * VN;
+    if (col >= n) return;
+    const T* __restrict__ base = Ur + (size_t)k * sUr + (size_t)r0 * npad + col;
+    double acc[VN];
+#pragma unroll
+    for (int e = 0; e < VN; ++e) acc[e] = 0.0;
+    // (columns n .. npad of a row belong to the slab: a whole piece is always readable; only columns < n are written)
+#pragma unroll 8
+    for (int i = 0; i < rows; ++i) {
+        const V x = *(const V*)(base + (size_t)i * npad);
+#pragma unroll
+        for (int e = 0; e < VN; ++e) acc[e] = fma((double)x[e], wu[i], acc[e]);
+    }
+    double* out = ypart + ((size_t)k * nchunk + ch) * npad + col;
+#pragma unroll
+    for (int e = 0; e < VN; ++e)
+        if (col + e < n) out[e] = acc[e];
+}
+
+// second half: y[k, col] = sum of the chunks' partials in ascending order
+__global__ __launch_bounds__(256) void sel_ty_reduce_kernel(const double* __restrict__ ypart, int nchunk, int npad, int n,
+                                                            double* __restrict__ y) {
+    const int col = blockIdx.x * blockDim.x + threadIdx.x, k = blockIdx.y;
+    if (col >= npad) return;
+    double s = 0.0;
+    if (col < n) {
+        const double* p = ypart + (size_t)k * nchunk * npad + col;
+        for (int ch = 0; ch < nchunk; ++ch) s += p[(size_t)ch * npad];
+    }
+    y[(size_t)k * npad + col] = s;
+}
+
+// b[k, s] = Uh[s, :] . (w o u) for s <= t (s = t: u . (w o u)); one workgroup per (s, k), fixed-order sums
+__global__ __launch_bounds__(256) void sel_hdot_kernel(const double* __restrict__ w, const double* __restrict__ Uh, int size,
+                                                       int n_ref, int t, double* __restrict__ b) {
+    __shared__ double red[256];
+    const int s = blockIdx.x, k = blockIdx.y, tid = threadIdx.x;
+    const double* __restrict__ us = Uh + ((size_t)k * size + s) * n_ref;
+    const double* __restrict__ ut = Uh + ((size_t)k * size + t) * n_ref;
+    double acc = 0.0;
+    for (int i = tid; i < n_ref; i += 256) acc = fma(us[i], w[i] * ut[i], acc);
+    red[tid] = acc;
+    __syncthreads();
+    for (int o = 128; o >= 1; o >>= 1) {
+        if (tid < o) red[tid] += red[tid + o];
+        __syncthreads();
+    }
+    if (tid == 0) b[(size_t)k * size + s] = red[0];
+}
+
+// (iii) g(c) = C^x(c, ref) (w o u) - D U_cand(c) . y - sum_{s<t} V[s, c] b_s, then the update of the state of candidate c:
+//   N = R den;  N <- max(N - 2 v g + v^2 b_t, 0);  h <- h - v^2;  R <- N / den(h)          v = V[t, c]
+// one wave per candidate; the wave that holds the pick marks it
+template <typename T, int KERN>
+__global__ __launch_bounds__(256) void sel_update_kernel(const T* __restrict__ Uc, size_t sUc, int npad, int n, int n_cand, int n_ref,
+                                                         const double* __restrict__ xsc, const double* __restrict__ xsr, int d,
+                                                         const double* __restrict__ theta, int tw, int nrep,
+                                                         const double* __restrict__ w, const double* __restrict__ y,
+                                                         const double* __restrict__ b, const double* __restrict__ V,
+                                                         const double* __restrict__ Uh, double* __restrict__ h,
+                                                         double* __restrict__ R, int size, int t, const int* __restrict__ pick,
+                                                         int* __restrict__ mask) {
+    const int lane = threadIdx.x & 63, c = blockIdx.x * 4 + (threadIdx.x >> 6), k = blockIdx.y;
+    if (c >= n_cand) return;                                // (uniform per wave)
+    const double* th = theta + (size_t)k * tw;
+    const double scale = th[d], nug = th[d + 1], D = th[d + 2];
+    const double coff = scale * (1.0 - nug / (1.0 + nug));
+    const double dot = sel_row_dot_y<T>(Uc + (size_t)k * sUc + (size_t)c * npad, y + (size_t)k * npad, n, lane);
+    const double* xc = xsc + ((size_t)k * n_cand + c) * d;
+    const double* __restrict__ ut = Uh + ((size_t)k * size + t) * n_ref;
+    double g1 = 0.0;
+    for (int i = lane; i < n_ref; i += 64)
+        g1 = fma(sel_kern<KERN>(xc, xsr + ((size_t)k * n_ref + i) * d, d), w[i] * ut[i], g1);
+    g1 = wave_sum(g1);
+    const double* __restrict__ Vk = V + (size_t)k * size * n_cand;
+    const double* __restrict__ bk = b + (size_t)k * size;
+    double hs = 0.0;
+    for (int s = lane; s < t; s += 64) hs = fma(Vk[(size_t)s * n_cand + c], bk[s], hs);
+    hs = wave_sum(hs);
+    if (lane == 0) {
+        const double g = fma(-D, dot, coff * g1) - hs;
+        const double v = Vk[(size_t)t * n_cand + c], tau = 1.0 / (D * (double)nrep);
+        const size_t o = (size_t)k * n_cand + c;
+        const double h0 = h[o];
+        const double N0 = R[o] * (fmax(h0, 0.0) + tau);
+        const double N1 = fmax(fma(v * v, bk[t], fma(-2.0 * v, g, N0)), 0.0);
+        const double h1 = fma(-v, v, h0);
+        h[o] = h1;
+        R[o] = N1 / (fmax(h1, 0.0) + tau);
+        if (k == 0 && c == *pick) mask[c] = 1;
+    }
+}
+
+// out[c] = sum over the local components, ascending, of omega_k R_k(c) (rounded products, rounded sums: what a host loop
+// computes), -inf at picked candidates; then the argmax (lowest index wins ties) into *pick.  One workgroup.
+__global__ __launch_bounds__(1024) void sel_score_kernel(const double* __restrict__ R, int q, int n_cand,
+                                                         const double* __restrict__ omega, const int* __restrict__ mask,
+                                                         double* __restrict__ out, int* __restrict__ pick) {
+    __shared__ double bv[1024];
+    __shared__ int bi[1024];
+    const int tid = threadIdx.x;
+    double best = -INFINITY;
+    int at = 0x7fffffff;
+    for (int c = tid; c < n_cand; c += 1024) {
+        double s = -INFINITY;
+        if (!mask[c]) {
+            // (no contraction into fma: the product is rounded before it is added, as on the host)
+#pragma clang fp contract(off)
+            s = 0.0;
+            for (int k = 0; k < q; ++k) {
+                const double pr = omega[k] * R[(size_t)k * n_cand + c];
+                s = s + pr;
+            }
+        }
+        if (out) out[c] = s;
+        if (s > best || at == 0x7fffffff) { best = s; at = c; }       // (ascending c: the first maximum stays)
+    }
+    bv[tid] = best; bi[tid] = at;
+    __syncthreads();
+    for (int o = 512; o >= 1; o >>= 1) {
+        if (tid < o) {
+            const double v2 = bv[tid + o];
+            const int i2 = bi[tid + o];
+            if (i2 != 0x7fffffff && (bi[tid] == 0x7fffffff || v2 > bv[tid] || (v2 == bv[tid] && i2 < bi[tid]))) {
+                bv[tid] = v2; bi[tid] = i2;
+            }
+        }
+        __syncthreads();
+    }
+    if (tid == 0 && pick) *pick = bi[0];
+}
+
+template <typename T>
+int do_sel_begin(hipStream_t st, const Ws& w, const void* x, const void* sr, const double* theta, int n_ref, const void* x_ref,
+                 const double* w_ref, int n_cand, const void* x_cand, const int* match, int r, int size, int pass_rows,
+                 char* scratch) {
+    const SelLay L = sel_carve(w.esz == 8 ? LCGP_F64 : LCGP_F32, w.n, w.d, w.q, n_ref, n_cand, size);
+    const int tw = w.d + 3 + w.p;
+    T* X = (T*)(scratch + L.off_x);
+    T* Ur = (T*)(scratch + L.off_uref);
+    T* Uc = (T*)(scratch + L.off_uc);
+    double* hc = (double*)(scratch + L.off_h);
+    int rc = vr_form<T>(st, w, x, sr, theta, n_ref, x_ref, nullptr, X, L.xslab, Ur, L.uslab_r, (double*)(scratch + L.off_ghr),
+                        (double*)(scratch + L.off_gvr), n_ref);
+    if (rc) return rc;
+    for (int lo = 0; lo < n_cand; lo += pass_rows) {
+        const int m = min(pass_rows, n_cand - lo);
+        rc = vr_form<T>(st, w, x, sr, theta, m, (const T*)x_cand + (size_t)lo * w.d, match ? match + lo : nullptr, X, L.xslab,
+                        Uc + (size_t)lo * w.npad, L.uslab_c, (double*)(scratch + L.off_ghc) + lo, hc + lo, n_cand);
+        if (rc) return rc;
+    }
+    GemmArgs h;
+    h.A = Ur; h.B = Uc; h.C = scratch + L.off_part;
+    h.sA = L.uslab_r; h.sB = L.uslab_c; h.sC = 0;
+    h.ldA = h.ldB = w.npad; h.ldC = 0;
+    h.nb = 0;
+    h.p0 = w.npad / TS; h.p1 = (n_cand + TS - 1) / TS; h.p2 = n_ref; h.p3 = n_cand;
+    h.theta = theta; h.xa = x_ref; h.xb = x_cand; h.wref = w_ref; h.gvc = hc; h.ldg = n_cand;
+    h.d = w.d; h.kern = w.kern; h.tw = tw; h.nrep = r; h.ldp = L.ldp;
+    rc = launch_gemm<T, OP_VR, 64>(st, h, L.nrt * h.p1, w.q);
+    if (rc) return rc;
+    hipLaunchKernelGGL(vr_reduce_kernel, dim3((n_cand + 255) / 256, w.q), dim3(256), 0, st, (const double*)(scratch + L.off_part),
+                       L.nrt, L.ldp, n_cand, n_cand, (double*)(scratch + L.off_R));
+    CHECK_LAUNCH("vr_reduce_kernel");
+    hipLaunchKernelGGL((sel_scale_kernel<T>), dim3((n_ref * w.d + 255) / 256, w.q), dim3(256), 0, st, (const T*)x_ref, n_ref, w.d,
+                       theta, tw, (double*)(scratch + L.off_xsr));
+    CHECK_LAUNCH("sel_scale_kernel");
+    hipLaunchKernelGGL((sel_scale_kernel<T>), dim3((n_cand * w.d + 255) / 256, w.q), dim3(256), 0, st, (const T*)x_cand, n_cand,
+                       w.d, theta, tw, (double*)(scratch + L.off_xsc));
+    CHECK_LAUNCH("sel_scale_kernel");
+    const int mx = max(max(n_ref, n_cand), size);
+    hipLaunchKernelGGL(sel_init_kernel, dim3((mx + 255) / 256), dim3(256), 0, st, w_ref, n_ref, (double*)(scratch + L.off_w), n_cand,
+                       (int*)(scratch + L.off_mask), size, (int*)(scratch + L.off_picks));
+    CHECK_LAUNCH("sel_init_kernel");
+    return 0;
+}
+
+// one conditioning step on the pick *pick for all local components (w: n, d, p, q, kern, esz; no workspace is read)
+template <typename T>
+int do_sel_condition(hipStream_t st, const Ws& w, const double* theta, int n_ref, int n_cand, int size, int r, int t,
+                     const int* pick, char* scratch) {
+    const SelLay L = sel_carve(w.esz == 8 ? LCGP_F64 : LCGP_F32, w.n, w.d, w.q, n_ref, n_cand, size);
+    constexpr int VN = SelVec<T>::N;
+    const int tw = w.d + 3 + w.p;
+    const T* Ur = (const T*)(scratch + L.off_uref);
+    const T* Uc = (const T*)(scratch + L.off_uc);
+    double* h = (double*)(scratch + L.off_h);
+    double* R = (double*)(scratch + L.off_R);
+    double* V = (double*)(scratch + L.off_V);
+    double* Uh = (double*)(scratch + L.off_Uh);
+    double* yp = (double*)(scratch + L.off_ypart);
+    double* y = (double*)(scratch + L.off_y);
+    double* b = (double*)(scratch + L.off_b);
+    const double* xsr = (const double*)(scratch + L.off_xsr);
+    const double* xsc = (const double*)(scratch + L.off_xsc);
+    const double* wr = (const double*)(scratch + L.off_w);
+    int* mask = (int*)(scratch + L.off_mask);
+    for_kern(w.kern, [&](auto kern) {
+        hipLaunchKernelGGL((sel_col_kernel<T, decltype(kern)::value>), dim3((n_cand + n_ref + 3) / 4, w.q), dim3(256), 0, st, Uc,
+                           L.uslab_c, Ur, L.uslab_r, w.npad, w.n, n_cand, n_ref, xsc, xsr, w.d, theta, tw, r, (const double*)h, V, Uh,
+                           size, t, pick);
+    });
+    CHECK_LAUNCH("sel_col_kernel");
+    hipLaunchKernelGGL((sel_ty_part_kernel<T>), dim3((w.n + 256 * VN - 1) / (256 * VN), L.nchunk, w.q), dim3(256), 0, st, Ur,
+                       L.uslab_r, w.npad, w.n, n_ref, wr, (const double*)Uh, size, t, L.nchunk, yp);
+    CHECK_LAUNCH("sel_ty_part_kernel");
+    hipLaunchKernelGGL(sel_ty_reduce_kernel, dim3((w.npad + 255) / 256, w.q), dim3(256), 0, st, (const double*)yp, L.nchunk, w.npad,
+                       w.n, y);
+    CHECK_LAUNCH("sel_ty_reduce_kernel");
+    hipLaunchKernelGGL(sel_hdot_kernel, dim3(t + 1, w.q), dim3(256), 0, st, wr, (const double*)Uh, size, n_ref, t, b);
+    CHECK_LAUNCH("sel_hdot_kernel");
+    for_kern(w.kern, [&](auto kern) {
+        hipLaunchKernelGGL((sel_update_kernel<T, decltype(kern)::value>), dim3((n_cand + 3) / 4, w.q), dim3(256), 0, st, Uc,
+                           L.uslab_c, w.npad, w.n, n_cand, n_ref, xsc, xsr, w.d, theta, tw, r, wr, (const double*)y, (const double*)b,
+                           (const double*)V, (const double*)Uh, h, R, size, t, pick, mask);
+    });
+    CHECK_LAUNCH("sel_update_kernel");
+    return 0;
+}
+
+int check_sel(int n_ref, int n_cand, int size) {
+    int rc = check_vr(n_ref, n_cand);
+    if (rc) return rc;
+    if (size < 1 || size > n_cand) return bad("size must be in [1, n_cand]");
+    return 0;
+}
+
 // host-side checks of the folds (CSR over the n training inputs); returns the largest fold size in *mmax
 int check_folds(int n, int q_local, int F, const int* folds, int* mmax) {
     if (F < 1) return bad("F must be >= 1");
@@ -4105,6 +4522,92 @@ int lcgp_variance_reduction(void* stream, int dtype, int kernel_id, int n, int d
                                              (char*)scratch, out, ldo)
                              : do_vr<float>(st, w, x, sr, theta, n_ref, x_ref, w_ref, n_cand, x_cand, match, cand_row0, r,
                                             (char*)scratch, out, ldo);
+}
+
+int lcgp_select_scratch_bytes(int dtype, int n, int d, int q_local, int n_ref, int n_cand, int size, size_t* bytes) {
+    int rc = check_common(dtype, n, d, 1, q_local);
+    if (rc) return rc;
+    if ((rc = check_sel(n_ref, n_cand, size))) return rc;
+    if (!bytes) return bad("bytes is NULL");
+    *bytes = sel_carve(dtype, n, d, q_local, n_ref, n_cand, size).total;
+    return 0;
+}
+
+int lcgp_select_begin(void* stream, int dtype, int kernel_id, int n, int d, int p, int q_local, const void* x, const void* sr,
+                      const double* theta, const void* workspace, int n_ref, const void* x_ref, const double* w_ref, int n_cand,
+                      const void* x_cand, const int* match_host, const int* match, int r, int size, int pass_rows, void* scratch) {
+    int rc = check_common(dtype, n, d, p, q_local, kernel_id);
+    if (rc) return rc;
+    if ((rc = check_sel(n_ref, n_cand, size))) return rc;
+    if (r < 1) return bad("r must be >= 1");
+    if (pass_rows < 1 || pass_rows > VR_XBLK) return bad("pass_rows must be in [1, 2048]");
+    if ((match_host == nullptr) != (match == nullptr)) return bad("match_host and match must both be NULL or both be given");
+    if (match_host)
+        for (int i = 0; i < n_cand; ++i)
+            if (match_host[i] < -1 || match_host[i] >= n) return bad("match must be -1 or a training index in [0, n)");
+    if (!x || !theta || !workspace || !x_ref || !w_ref || !x_cand || !scratch) return bad("NULL pointer");
+    Ws w = carve(dtype, n, d, p, q_local, (void*)workspace);
+    w.kern = kernel_id;
+    hipStream_t st = (hipStream_t)stream;
+    return dtype == LCGP_F64 ? do_sel_begin<double>(st, w, x, sr, theta, n_ref, x_ref, w_ref, n_cand, x_cand, match, r, size,
+                                                    pass_rows, (char*)scratch)
+                             : do_sel_begin<float>(st, w, x, sr, theta, n_ref, x_ref, w_ref, n_cand, x_cand, match, r, size,
+                                                   pass_rows, (char*)scratch);
+}
+
+int lcgp_select_score(void* stream, int dtype, int n, int d, int q_local, int n_ref, int n_cand, int size, int step,
+                      const double* omega, void* scratch, double* out) {
+    int rc = check_common(dtype, n, d, 1, q_local);
+    if (rc) return rc;
+    if ((rc = check_sel(n_ref, n_cand, size))) return rc;
+    if (step < 0 || step >= size) return bad("step must be in [0, size)");
+    if (!omega || !scratch) return bad("NULL pointer");
+    const SelLay L = sel_carve(dtype, n, d, q_local, n_ref, n_cand, size);
+    char* sc = (char*)scratch;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(sel_score_kernel, dim3(1), dim3(1024), 0, st, (const double*)(sc + L.off_R), q_local, n_cand, omega,
+                       (const int*)(sc + L.off_mask), out, (int*)(sc + L.off_picks) + step);
+    CHECK_LAUNCH("sel_score_kernel");
+    return 0;
+}
+
+int lcgp_select_picks(int dtype, int n, int d, int q_local, int n_ref, int n_cand, int size, void* scratch, int** picks) {
+    int rc = check_common(dtype, n, d, 1, q_local);
+    if (rc) return rc;
+    if ((rc = check_sel(n_ref, n_cand, size))) return rc;
+    if (!scratch || !picks) return bad("NULL pointer");
+    *picks = (int*)((char*)scratch + sel_carve(dtype, n, d, q_local, n_ref, n_cand, size).off_picks);
+    return 0;
+}
+
+int lcgp_select_condition(void* stream, int dtype, int kernel_id, int n, int d, int p, int q_local, const double* theta,
+                          int n_ref, int n_cand, int size, int r, int step, const int* pick, void* scratch) {
+    int rc = check_common(dtype, n, d, p, q_local, kernel_id);
+    if (rc) return rc;
+    if ((rc = check_sel(n_ref, n_cand, size))) return rc;
+    if (r < 1) return bad("r must be >= 1");
+    if (step < 0 || step >= size) return bad("step must be in [0, size)");
+    if (!theta || !pick || !scratch) return bad("NULL pointer");
+    Ws w;
+    memset(&w, 0, sizeof(w));
+    w.n = n; w.npad = round_up(n, 2 * TS); w.d = d; w.p = p; w.q = q_local; w.kern = kernel_id;
+    w.esz = dtype == LCGP_F64 ? 8 : 4;
+    hipStream_t st = (hipStream_t)stream;
+    return dtype == LCGP_F64 ? do_sel_condition<double>(st, w, theta, n_ref, n_cand, size, r, step, pick, (char*)scratch)
+                             : do_sel_condition<float>(st, w, theta, n_ref, n_cand, size, r, step, pick, (char*)scratch);
+}
+
+int lcgp_select_state(void* stream, int dtype, int n, int d, int q_local, int n_ref, int n_cand, int size, int which,
+                      const void* scratch, double* out) {
+    int rc = check_common(dtype, n, d, 1, q_local);
+    if (rc) return rc;
+    if ((rc = check_sel(n_ref, n_cand, size))) return rc;
+    if (which != 0 && which != 1) return bad("which must be 0 (R) or 1 (h)");
+    if (!scratch || !out) return bad("NULL pointer");
+    const SelLay L = sel_carve(dtype, n, d, q_local, n_ref, n_cand, size);
+    hipError_t e = hipMemcpyAsync(out, (const char*)scratch + (which ? L.off_h : L.off_R), (size_t)q_local * n_cand * sizeof(double),
+                                  hipMemcpyDeviceToDevice, (hipStream_t)stream);
+    return e == hipSuccess ? 0 : fail("hipMemcpyAsync", e);
 }
 
 }  // extern "C"

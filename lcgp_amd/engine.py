@@ -82,6 +82,7 @@ class HotPathEngine:
             self._scratch = None
             self._cov_ws = None          # (n0, workspace) of the joint covariance (form_cov)
             self._cv_ws = None           # ((mmax, F), workspace) of the fold matrices (cv_block)
+            self._sel = None             # state of a running greedy selection (select_begin)
         self._theta_last = None
 
     # ------------------------------------------------------------------------------------------------
@@ -524,6 +525,96 @@ class HotPathEngine:
                                                             lo if shared else -1, int(r), scp, C.c_void_p(out.data_ptr() + 8 * lo),
                                                             n_cand), "lcgp_variance_reduction")
             return out
+
+    # ------------------------------------------------------------------------------------------------
+    # greedy batch design by sequential ALC (lcgp_hip.h: lcgp_select_begin / lcgp_select_score / lcgp_select_condition)
+    def select_begin(self, x_cand_s, x_ref_s, w, match, r, size):
+        """Starts a greedy selection of `size` of the candidates: U and gvar of the reference set and of ALL candidates into the
+        engine's scratch (candidates in passes of PREDICT_CHUNK rows) and the step-0 state R = variance_reduction_block(...) bitwise.
+        Arguments as variance_reduction_block.  Raises ValueError when the scratch does not fit in the free device memory.  The
+        state lives in the engine's scratch: no other query may run between select_begin and the last select_condition."""
+        torch = self.torch
+        if self._theta_last is None:
+            raise RuntimeError("select_batch() needs a preceding evaluate() at the current parameters")
+        x_cand_s = np.ascontiguousarray(x_cand_s, np.float64)
+        n_cand, d = x_cand_s.shape[0], self.d
+        assert x_cand_s.ndim == 2 and x_cand_s.shape[1] == d and 1 <= size <= n_cand
+        match = None if match is None else np.ascontiguousarray(match, np.int32)
+        if match is not None and not np.any(match >= 0):
+            match = None
+        x_ref_s = x_cand_s if x_ref_s is None else np.ascontiguousarray(x_ref_s, np.float64)
+        n_ref = x_ref_s.shape[0]
+        assert x_ref_s.ndim == 2 and x_ref_s.shape[1] == d and n_ref >= 1 and len(w) == n_ref
+        self._sel = None
+        with torch.cuda.device(self.device):
+            dims = (self.dtype, self.n, d, self.q_local, n_ref, n_cand, int(size))
+            nbytes = self._nbytes("lcgp_select_scratch_bytes", *dims)
+            scratch = self._grow_scratch(nbytes, ("the batch selection over %d candidates" % n_cand,
+                                                  "%d components of (%d reference points + %d candidates) x n, all resident"
+                                                  % (self.q_local, n_ref, n_cand), "pass fewer candidates"))
+            xr = torch.as_tensor(x_ref_s).to(self.device, self.tdtype).contiguous()
+            xc = torch.as_tensor(x_cand_s).to(self.device, self.tdtype).contiguous()
+            wd = torch.as_tensor(np.ascontiguousarray(w, np.float64)).to(self.device)
+            md = None if match is None else torch.as_tensor(match).to(self.device)
+            _hip.check(self.lib.lcgp_select_begin(self._stream(), self.dtype, self.kernel_id, self.n, d, self.p, self.q_local,
+                                                  self._p(self.x), self._p(self.sr), self._p(self.theta_dev), self._p(self.workspace),
+                                                  n_ref, self._p(xr), self._p(wd), n_cand, self._p(xc),
+                                                  C.c_void_p(0) if match is None else C.c_void_p(match.ctypes.data),
+                                                  C.c_void_p(0) if md is None else self._p(md), int(r), int(size),
+                                                  min(PREDICT_CHUNK, 2048), self._p(scratch)), "lcgp_select_begin")
+            picks = C.c_void_p(0)
+            _hip.check(self.lib.lcgp_select_picks(*dims, self._p(scratch), C.byref(picks)), "lcgp_select_picks")
+            self._sel = dict(dims=dims, scratch=scratch, n_ref=n_ref, n_cand=n_cand, size=int(size), r=int(r), step=0,
+                             picks=picks.value, keep=(xr, xc, wd, md))
+
+    def select_rows(self):
+        """(q_local, n_cand) float64 DEVICE tensor: R_k(c) of the model conditioned on the picks made so far"""
+        sel, torch = self._sel, self.torch
+        with torch.cuda.device(self.device):
+            out = torch.empty((self.q_local, sel['n_cand']), dtype=torch.float64, device=self.device)
+            _hip.check(self.lib.lcgp_select_state(self._stream(), *sel['dims'], 0, self._p(sel['scratch']), self._p(out)),
+                       "lcgp_select_state")
+            return out
+
+    def _select_condition(self, sel, pick_ptr):
+        _hip.check(self.lib.lcgp_select_condition(self._stream(), self.dtype, self.kernel_id, self.n, self.d, self.p, self.q_local,
+                                                  self._p(self.theta_dev), sel['n_ref'], sel['n_cand'], sel['size'], sel['r'],
+                                                  sel['step'], C.c_void_p(pick_ptr), self._p(sel['scratch'])),
+                   "lcgp_select_condition")
+        sel['step'] += 1
+
+    def select_condition(self, j):
+        """conditions the state on r runs at candidate j (a host int: the pick all ranks agreed on)"""
+        sel, torch = self._sel, self.torch
+        with torch.cuda.device(self.device):
+            jd = torch.full((1,), int(j), dtype=torch.int32, device=self.device)
+            self._select_condition(sel, jd.data_ptr())
+
+    def select_batch_block(self, x_cand_s, x_ref_s, w, match, r, size, omega):
+        """The whole greedy loop on the device for the engine's components (one rank holds them all): returns DEVICE tensors
+        idx (size,) int32 and scores (size, n_cand) float64, row t = sum_k omega_k R_k^t, -inf at candidates picked before step t.
+        All steps are enqueued without a host synchronisation (the kernels read each pick from device memory)."""
+        torch = self.torch
+        self.select_begin(x_cand_s, x_ref_s, w, match, r, size)
+        sel = self._sel
+        with torch.cuda.device(self.device):
+            om = torch.as_tensor(np.ascontiguousarray(omega, np.float64)).to(self.device)
+            scores = torch.empty((sel['size'], sel['n_cand']), dtype=torch.float64, device=self.device)
+            st, scp = self._stream(), self._p(sel['scratch'])
+            for t in range(sel['size']):
+                _hip.check(self.lib.lcgp_select_score(st, *sel['dims'], t, self._p(om), scp,
+                                                      C.c_void_p(scores.data_ptr() + 8 * t * sel['n_cand'])), "lcgp_select_score")
+                if t + 1 < sel['size']:
+                    self._select_condition(sel, sel['picks'] + 4 * t)
+            idx = torch.empty(sel['size'], dtype=torch.int32, device=self.device)
+            idx.copy_(self._select_picks_view(sel))
+            self._sel = None
+            return idx, scores
+
+    def _select_picks_view(self, sel):
+        """the picks word array of the scratch as an int32 view"""
+        off = sel['picks'] - sel['scratch'].data_ptr()
+        return sel['scratch'][off:off + 4 * sel['size']].view(self.torch.int32)
 
     def fetch_vector(self, which, k):
         torch = self.torch

@@ -1058,28 +1058,9 @@ class LCGP:
     # =============================================================================================
     # integrated variance reduction for choosing new design points (beyond the reference)
     # =============================================================================================
-    def variance_reduction(self, x_cand, x_ref=None, weights=None, outputs=None, replicates=1, latent=False):
-        """Integrated variance reduction (the active-learning-Cohn criterion, ALC / IMSPE reduction): for each candidate input
-        the drop of the weighted predictive variance over a reference set if the simulator ran once more there, at FIXED
-        parameters (hyper-parameters, noise, basis phi, standardisation; no refit).  It does not depend on the simulator output.
-        With latent component k, reference point t, candidate c (standardised) and U_k as in predict():
-            R_k(c)     = sum_t w_t Sigma_k(t, c)^2 / (max(Sigma_k^h(c, c), 0) + 1 / (D_k r))
-            Sigma_k(t, c)   = C_k(t, c) - D_k U_k(t) . U_k(c)     (no nugget: reference points are new inputs)
-            Sigma_k^h(c, c) = scale_k - D_k |U_k(c)|^2           (predict()'s gvar at c, with the candidate's own cross row)
-            Delta_a(c) = scale_a^2 sum_k W[k, a]^2 R_k(c)         (W, scale: those of predict())
-        R_k(c) is gvar_k summed over the reference set before minus after adding the run to the training set; Delta_a(c) is the
-        drop of yconfvar, and of ypredvar (the noise does not change).
-          x_cand: (n_cand, d) raw-scale candidates.  x_ref: (n_ref, d) raw-scale reference points (default: x_cand).
-          weights: n_ref non-negative weights, normalised to sum 1 (default uniform).  outputs: output indices (default all p).
-          replicates: r runs at the candidate.  Full path: the candidate is one new training row with its own nugget, r = 1
-                 only; its cross row has no nugget term even where it equals a training input.  Rep path: a candidate equal
-                 (after standardisation, bitwise) to a unique training input adds r replicates to it (its cross row carries
-                 the nugget term at that input, as predict() does at the training set); otherwise it is a new unique input.
-          latent: return R (q, n_cand) instead of Delta (len(outputs), n_cand).
-        Computed on the GPU from the factorisation of the current parameters (right after fit() no extra evaluation), in the
-        engine's dtype (float32 models: float32 products, double sums).  GPU memory: q_local (n_ref + min(n_cand, 2048)) npad
-        elements of scratch and q_local ceil(n_ref / 64) min(n_cand, 2048) doubles (npad = n_train rounded up to 128); the
-        n_ref x n_cand matrix is never formed -- ValueError when it does not fit.  self.ghat / self.gvar are left untouched."""
+    def _vr_arguments(self, x_cand, x_ref, weights, outputs, replicates):
+        """the checks and conventions variance_reduction() and select_batch() share: standardised candidates and reference points
+        (None: the candidates), normalised weights, output indices, r and the rep path's match of candidates to training inputs"""
         d = int(self.d)
         xc = _np(self._verify_data_types(x_cand))
         if xc.ndim != 2 or xc.shape[1] != d or xc.shape[0] < 1:
@@ -1118,14 +1099,100 @@ class LCGP:
             match = np.array([lookup.get(row.tobytes(), -1) for row in np.ascontiguousarray(xc_s)], np.int32)
         elif r != 1:
             raise ValueError("replicates must be 1 on the full path (submethod='full'): a candidate is one new training row")
+        return xc_s, xr_s, w, outputs, r, match
+
+    def variance_reduction(self, x_cand, x_ref=None, weights=None, outputs=None, replicates=1, latent=False):
+        """Integrated variance reduction (the active-learning-Cohn criterion, ALC / IMSPE reduction): for each candidate input
+        the drop of the weighted predictive variance over a reference set if the simulator ran once more there, at FIXED
+        parameters (hyper-parameters, noise, basis phi, standardisation; no refit).  It does not depend on the simulator output.
+        With latent component k, reference point t, candidate c (standardised) and U_k as in predict():
+            R_k(c)     = sum_t w_t Sigma_k(t, c)^2 / (max(Sigma_k^h(c, c), 0) + 1 / (D_k r))
+            Sigma_k(t, c)   = C_k(t, c) - D_k U_k(t) . U_k(c)     (no nugget: reference points are new inputs)
+            Sigma_k^h(c, c) = scale_k - D_k |U_k(c)|^2           (predict()'s gvar at c, with the candidate's own cross row)
+            Delta_a(c) = scale_a^2 sum_k W[k, a]^2 R_k(c)         (W, scale: those of predict())
+        R_k(c) is gvar_k summed over the reference set before minus after adding the run to the training set; Delta_a(c) is the
+        drop of yconfvar, and of ypredvar (the noise does not change).
+          x_cand: (n_cand, d) raw-scale candidates.  x_ref: (n_ref, d) raw-scale reference points (default: x_cand).
+          weights: n_ref non-negative weights, normalised to sum 1 (default uniform).  outputs: output indices (default all p).
+          replicates: r runs at the candidate.  Full path: the candidate is one new training row with its own nugget, r = 1
+                 only; its cross row has no nugget term even where it equals a training input.  Rep path: a candidate equal
+                 (after standardisation, bitwise) to a unique training input adds r replicates to it (its cross row carries
+                 the nugget term at that input, as predict() does at the training set); otherwise it is a new unique input.
+          latent: return R (q, n_cand) instead of Delta (len(outputs), n_cand).
+        Computed on the GPU from the factorisation of the current parameters (right after fit() no extra evaluation), in the
+        engine's dtype (float32 models: float32 products, double sums).  GPU memory: q_local (n_ref + min(n_cand, 2048)) npad
+        elements of scratch and q_local ceil(n_ref / 64) min(n_cand, 2048) doubles (npad = n_train rounded up to 128); the
+        n_ref x n_cand matrix is never formed -- ValueError when it does not fit.  self.ghat / self.gvar are left untouched."""
+        xc_s, xr_s, w, outputs, r, match = self._vr_arguments(x_cand, x_ref, weights, outputs, replicates)
         eng = self._ensure_aux()
         loc = self._agree(lambda: None if eng is None else eng.variance_reduction_block(xc_s, xr_s, w, match, r))
-        R = self._gather_components(loc, (xc.shape[0],))
+        R = self._gather_components(loc, (xc_s.shape[0],))
         if latent:
             return _t(R)
         W, _, scale, _ = self._output_map()
         delta = (W[:, outputs] ** 2).T @ R * (scale[outputs] ** 2)[:, None]
         return _t(delta)
+
+    def select_batch(self, x_cand, size, x_ref=None, weights=None, outputs=None, replicates=1, return_scores=False):
+        """Greedy batch design by sequential ALC: `size` of the candidates, chosen one after the other -- the candidate with the
+        largest integrated variance reduction is picked, the posterior variance is conditioned on `replicates` runs there (ALC
+        does not depend on the runs' outputs, so no simulator call is needed), and the remaining candidates are scored again.
+        Taking the `size` best candidates of ONE variance_reduction() call instead picks neighbours that duplicate information.
+            score_t(c) = sum_k omega_k R_k^t(c),   omega_k = mean over a in outputs of scale_a^2 W[k, a]^2
+        (the mean over the chosen outputs of variance_reduction()'s Delta), R_k^t: R_k of variance_reduction() for the model
+        conditioned on the t picks made so far, at FIXED parameters (hyper-parameters, noise, phi, standardisation; no refit).
+          x_cand, x_ref, weights, outputs, replicates: exactly as in variance_reduction() (same checks, same full / rep
+                 conventions, same matching of candidates to training inputs on the rep path).
+          size: 1 <= size <= n_cand; each candidate is picked at most once.
+        Bitwise-duplicate candidate rows (after standardisation) raise ValueError: two copies of one input would have to share
+        a nugget, a convention variance_reduction() does not define.
+        Returns idx (size,) int64, the picks in order, and gain (size,) float64, gain[t] = score_t(idx[t]); gain is
+        non-increasing up to rounding (ALC is submodular at fixed parameters).  With return_scores=True also scores
+        (size, n_cand) float64: the whole score row of every step, -inf at candidates already picked.  Ties go to the lowest index.
+        The posterior over the candidates is carried as a lazily evaluated pivoted Cholesky factor on the GPU:
+        per step two passes over U of the reference set and of the candidates; on one rank all steps are enqueued without a host
+        synchronisation.  GPU memory: q_local (n_ref + n_cand) npad elements (ALL candidates resident) plus q_local size
+        (n_ref + n_cand) doubles of history -- ValueError when it does not fit.  The model is left unchanged (ghat, gvar, the
+        factorisation and n untouched)."""
+        xc_s, xr_s, w, outputs, r, match = self._vr_arguments(x_cand, x_ref, weights, outputs, replicates)
+        n_cand = xc_s.shape[0]
+        if isinstance(size, (bool, np.bool_)) or int(size) != size or size < 1 or size > n_cand:
+            raise ValueError('size must be an integer in [1, n_cand = %d]' % n_cand)
+        size = int(size)
+        if len({row.tobytes() for row in np.ascontiguousarray(xc_s)}) != n_cand:
+            raise ValueError('x_cand holds duplicate rows (bitwise equal after standardisation): two copies of one input would '
+                             'have to share a nugget; pass each candidate once')
+        W, _, scale, _ = self._output_map()
+        q = int(self.q)
+        omega = np.mean((W[:, outputs] ** 2) * (scale[outputs] ** 2)[None, :], axis=1)
+        eng = self._ensure_aux()
+        if not _dist.use_collectives(self._group):
+            # one rank holds every component: the whole loop on the device, one copy back
+            idx_d, sc_d = self._agree(lambda: eng.select_batch_block(xc_s, xr_s, w, match, r, size, omega[self._local_ks]))
+            idx = idx_d.cpu().numpy().astype(np.int64)
+            scores = sc_d.cpu().numpy()
+        else:
+            # components sharded over ranks: per step the local rows are gathered (disjoint components: the sum is a gather, so
+            # every rank adds the q terms in the order one rank does), rank 0's argmax is broadcast
+            self._agree(lambda: None if eng is None else eng.select_begin(xc_s, xr_s, w, match, r, size))
+            dev = None if eng is None else eng.device
+            idx = np.zeros(size, np.int64)
+            scores = np.empty((size, n_cand), F64)
+            picked = np.zeros(n_cand, bool)
+            for t in range(size):
+                R = self._gather_components(None if eng is None else eng.select_rows(), (n_cand,))
+                s = np.zeros(n_cand, F64)
+                for k in range(q):
+                    s = s + omega[k] * R[k]
+                s[picked] = -np.inf
+                j = int(_dist.broadcast_array(np.array([np.argmax(s)], F64), 0, self._group, dev)[0])
+                idx[t], scores[t], picked[j] = j, s, True
+                if eng is not None and t + 1 < size:
+                    eng.select_condition(j)
+        gain = scores[np.arange(size), idx].copy()
+        if return_scores:
+            return torch.as_tensor(idx), _t(gain), _t(scores)
+        return torch.as_tensor(idx), _t(gain)
 
     # =============================================================================================
     # input gradients of the prediction (the reference: a tf.GradientTape around predict)

@@ -56,9 +56,15 @@ extern "C" {
  *                         (covmat.py holds Matern32 only); BASELINE.json's north star names it, so the path carries it as an
  *                         extension with the same nugget / scale structure.  Parity for it is UNPINNED: it is checked against
  *                         this repository's own oracle through identities only (gradient = finite differences = autograd,
- *                         eigendecomposition form = Cholesky form), never against the reference. */
+ *                         eigendecomposition form = Cholesky form), never against the reference.
+ *   LCGP_KERNEL_MATERN52  Matern-5/2 product kernel in the convention of LCGP_KERNEL_MATERN32 (no sqrt(5) factor):
+ *                         C0 = prod_j (1 + S_j + S_j^2 / 3) exp(-sum_j S_j), which is the textbook Matern-5/2 at lengthscale
+ *                         sqrt(5) ell_j per dimension.  Twice differentiable predictions (Matern-3/2: once).  The reference
+ *                         has no such kernel either: an extension like LCGP_KERNEL_SE, parity UNPINNED, tied to identities
+ *                         only.  Every call that takes a kernel_id accepts it. */
 #define LCGP_KERNEL_MATERN32 0
 #define LCGP_KERNEL_SE 1
+#define LCGP_KERNEL_MATERN52 2
 
 /* library version (major*100 + minor), hash of the sources the binary was built from
  * (sha256 of lcgp_hip.hip + lcgp_hip.h, first 16 hex digits; "unknown" if built without
@@ -113,7 +119,7 @@ int lcgp_predict_scratch_bytes(int dtype, int n, int q_local, int n0, size_t* by
 int lcgp_matern32(void* stream, int dtype, int n1, int n2, int d,
                   const void* x1, const void* x2,
                   const double* ell /*host, d*/, double scale, double nug, int same, void* out);
-/* the same for either kernel (lcgp_matern32 = lcgp_covmat with LCGP_KERNEL_MATERN32) */
+/* the same for any kernel_id (lcgp_matern32 = lcgp_covmat with LCGP_KERNEL_MATERN32) */
 int lcgp_covmat(void* stream, int dtype, int kernel_id, int n1, int n2, int d,
                 const void* x1, const void* x2,
                 const double* ell /*host, d*/, double scale, double nug, int same, void* out);

@@ -18,7 +18,8 @@ HDR_PATH = os.path.join(_ROOT, "include", "lcgp_hip.h")
 SCHED_PATH = os.path.join(_HERE, "csrc", "fill_sched.h")
 
 F64, F32 = 0, 1
-KERNELS = {"matern32": 0, "se": 1}      # include/lcgp_hip.h: LCGP_KERNEL_MATERN32 / LCGP_KERNEL_SE (an extension, parity unpinned)
+# include/lcgp_hip.h: LCGP_KERNEL_MATERN32 (the reference's) / LCGP_KERNEL_SE / LCGP_KERNEL_MATERN52 (extensions, parity unpinned)
+KERNELS = {"matern32": 0, "se": 1, "matern52": 2}
 
 
 class Sched(C.Structure):

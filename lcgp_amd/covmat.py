@@ -1,5 +1,6 @@
 """Matern32 with the reference's signature (covmat.py:5-55), evaluated by the HIP kernel `cross_kernel`; and the
-squared-exponential product kernel BASELINE.json's north star names (the reference has none: an extension, parity unpinned)."""
+squared-exponential product kernel BASELINE.json's north star names and the Matern-5/2 product kernel (the reference has neither:
+extensions, parity unpinned)."""
 from __future__ import annotations
 
 import numpy as np
@@ -47,3 +48,13 @@ def SquaredExponential(x1, x2, llmb, llmb0, lnug, diag_only: bool = False):
     The reference has no such kernel (covmat.py:5-55 holds Matern32 only); `LCGP(..., kernel='se')` uses it.
     """
     return Matern32(x1, x2, llmb, llmb0, lnug, diag_only, _kernel='se')
+
+
+def Matern52(x1, x2, llmb, llmb0, lnug, diag_only: bool = False):
+    """
+    The Matern-5/2 product kernel with Matern32's signature, nugget / scale structure and convention (no sqrt(5) factor):
+        C = scale ((1 - nt) prod_j (1 + S_j + S_j^2 / 3) exp(-sum_j S_j) + nt [x1 is x2]),   S_j = |x1_j - x2_j| / llmb_j,
+    nt = lnug / (1 + lnug).  This is the textbook Matern-5/2, (1 + sqrt(5) r / l + 5 r^2 / (3 l^2)) exp(-sqrt(5) r / l) per
+    dimension, at lengthscale l = sqrt(5) llmb_j.  The reference has no such kernel; `LCGP(..., kernel='matern52')` uses it.
+    """
+    return Matern32(x1, x2, llmb, llmb0, lnug, diag_only, _kernel='matern52')

@@ -23,7 +23,7 @@
 #include "../../include/lcgp_hip.h"
 #include "fill_sched.h"
 
-#define LCGP_VERSION 560
+#define LCGP_VERSION 570
 
 namespace {
 
@@ -54,7 +54,7 @@ inline int round_up(int a, int b) { return (a + b - 1) / b * b; }
 // ---------------------------------------------------------------------------------------------------
 struct Ws {
     int n, npad, nb, d, p, q;
-    int kern = 0;        // covariance kernel (lcgp_hip.h: LCGP_KERNEL_MATERN32 / LCGP_KERNEL_SE)
+    int kern = 0;        // covariance kernel (lcgp_hip.h: LCGP_KERNEL_MATERN32 / LCGP_KERNEL_SE / LCGP_KERNEL_MATERN52)
     size_t esz;
     size_t mat;          // elements per matrix
     char* base;
@@ -212,6 +212,26 @@ template <typename T> __device__ __forceinline__ constexpr T exp_floor();
 template <> __device__ __forceinline__ constexpr double exp_floor<double>() { return -708.0; }
 template <> __device__ __forceinline__ constexpr float exp_floor<float>() { return -87.0f; }
 
+// Covariance kernel ids (lcgp_hip.h): every device function templated on KERN spells out all three; a site that only
+// told "0" from "not 0" would silently evaluate the squared exponential for a new id.
+template <int KERN> struct kern_known { static constexpr bool value = KERN == 0 || KERN == 1 || KERN == 2; };
+// Matern-5/2 (KERN == 2), the reference's Matern-3/2 convention carried over (no sqrt(5)): per dimension the factor
+//   f(S) = 1 + S + S^2 / 3   beside exp(-S),     C0 = prod_j f(S_j) exp(-sum_j S_j),
+// i.e. the textbook Matern-5/2 at lengthscale sqrt(5) ell_j.  f(S) <= exp(S), so the guards of the 3/2 path carry over
+// unchanged: a product beyond poly_cap (or inf, or the NaN of inf x 0 -- fmin returns its other operand) meets an
+// exponential that has underflowed to zero.  m52_fm1 = f - 1 (the form `poly = fma(poly, f - 1, poly)` of the 3/2 path);
+//   dC0/d ell_j  = C0 m52_wl(S_j) / (f(S_j) ell_j),     m52_wl(S) = S^2 (1 + S) / 3
+//   dC0/d x1_j   = -C0 m52_wx(s_j) / ell_j,             m52_wx(s) = s (1 + |s|) / (3 + 3 |s| + s^2)  (|m52_wx| < 1)
+template <typename T> __device__ __forceinline__ T m52_fm1(T sd) { return fma(sd * (T)(1.0 / 3.0), sd, sd); }
+__device__ __forceinline__ double m52_wl(double sd) { return (sd * sd) * fma(sd, 1.0 / 3.0, 1.0 / 3.0); }
+// the value of the product kernel from its two accumulated parts (SE carries no polynomial)
+template <int KERN>
+__device__ __forceinline__ double kern_c0(double poly, double ssum) {
+    static_assert(kern_known<KERN>::value, "unknown covariance kernel id");
+    if constexpr (KERN == 1) return exp_nonpos(ssum);
+    else return fmin(poly, poly_cap<double>()) * exp_nonpos(ssum);
+}
+
 // ---------------------------------------------------------------------------------------------------
 // K1: kernel build.   A_ij = delta_ij + D sr_i sr_j s ((1 - nt) C0_ij + nt delta_ij)
 //   C0 = prod_j (1 + S_j) exp(-sum_j S_j),  S_j = |x_i,j/ell_j - x_i',j/ell_j|      (covmat.py:35-53)
@@ -302,9 +322,14 @@ __global__ __launch_bounds__(256) void build_kernel(T* __restrict__ M, size_t ma
                         const T sd = fabs(xa[a] - xb[b]);
                         poly[a][b] = fma(poly[a][b], sd, poly[a][b]);
                         ssum[a][b] -= sd;
-                    } else {
+                    } else if constexpr (KERN == 1) {
                         const T df = xa[a] - xb[b];
                         ssum[a][b] = fma((T)-0.5 * df, df, ssum[a][b]);
+                    } else {
+                        static_assert(KERN == 2, "unknown covariance kernel id");
+                        const T sd = fabs(xa[a] - xb[b]);
+                        poly[a][b] = fma(poly[a][b], m52_fm1(sd), poly[a][b]);
+                        ssum[a][b] -= sd;
                     }
                 }
         }
@@ -398,9 +423,14 @@ __global__ __launch_bounds__(256) void cross_kernel(T* __restrict__ out, int ldo
                     double sd = fabs(xr[i][jj] - xc[j][jj]);
                     poly[m] *= 1.0 + sd;
                     ssum[m] -= sd;
-                } else {
+                } else if constexpr (KERN == 1) {
                     const double df = xr[i][jj] - xc[j][jj];
                     ssum[m] = fma(-0.5 * df, df, ssum[m]);
+                } else {
+                    static_assert(KERN == 2, "unknown covariance kernel id");
+                    const double sd = fabs(xr[i][jj] - xc[j][jj]);
+                    poly[m] = fma(poly[m], m52_fm1(sd), poly[m]);
+                    ssum[m] -= sd;
                 }
             }
         }
@@ -1026,16 +1056,21 @@ __device__ __forceinline__ void vr_epilogue(const GemmArgs& g, const Acc (&acc)[
                             const double sd = fabs(xv - yv);
                             pl[e] = fma(pl[e], sd, pl[e]);
                             ss[e] -= sd;
-                        } else {
+                        } else if constexpr (KERN == 1) {
                             const double df = xv - yv;
                             ss[e] = fma(-0.5 * df, df, ss[e]);
+                        } else {
+                            static_assert(KERN == 2, "unknown covariance kernel id");
+                            const double sd = fabs(xv - yv);
+                            pl[e] = fma(pl[e], m52_fm1(sd), pl[e]);
+                            ss[e] -= sd;
                         }
                     }
                 }
             }
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                const double c = KERN == 0 ? fmin(pl[e], poly_cap<double>()) * exp_nonpos(ss[e]) : exp_nonpos(ss[e]);
+                const double c = kern_c0<KERN>(pl[e], ss[e]);
                 const double sg = fma(-D, (double)acc[mi][ni][e], coff * c);
                 s[ni] = fma(wr[wm0 + mi * 16 + Mfma<T>::row(lane, e)] * sg, sg, s[ni]);
             }
@@ -1426,7 +1461,8 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& g, const int lin /*blo
     if constexpr (OP == OP_VR) {
         const int ct = bid % g.p1, rt = bid / g.p1;
         if (g.kern == 0) vr_epilogue<T, 0, TM, MIM, MIN>(g, acc, k, rt, ct, tid, wm0, wn0, lds);
-        else vr_epilogue<T, 1, TM, MIM, MIN>(g, acc, k, rt, ct, tid, wm0, wn0, lds);
+        else if (g.kern == 1) vr_epilogue<T, 1, TM, MIM, MIN>(g, acc, k, rt, ct, tid, wm0, wn0, lds);
+        else vr_epilogue<T, 2, TM, MIM, MIN>(g, acc, k, rt, ct, tid, wm0, wn0, lds);
         return;
     }
     if constexpr (OP == OP_PRED_COV) alpha = -g.theta[(size_t)k * g.p1 + g.p2];
@@ -2209,15 +2245,23 @@ __global__ __launch_bounds__(256) void grad_kernel(const T* __restrict__ V, size
                     pre[jj] = prod;
                     prod = fma(prod, s, prod);
                     ssum -= s;
-                } else {            // squared exponential: dC0/d ell_j = C0 S_j^2 / ell_j, no polynomial factor
+                } else if constexpr (KERN == 1) {   // squared exponential: dC0/d ell_j = C0 S_j^2 / ell_j, no polynomial factor
                     const double s = xr[i][jj] - xcj;
                     sv[jj] = s;
                     ssum = fma(-0.5 * s, s, ssum);
+                } else {            // Matern-5/2: as 3/2 with the factor f(S) = 1 + S + S^2 / 3
+                    static_assert(KERN == 2, "unknown covariance kernel id");
+                    const double s = fabs(xr[i][jj] - xcj);
+                    sv[jj] = s;
+                    pre[jj] = prod;
+                    prod = fma(prod, m52_fm1(s), prod);
+                    ssum -= s;
                 }
             }
             // C0 = 0 where its exponential underflows, and the polynomial beside it may have overflowed (inf x 0): no contribution.
-            // (Only the widest instantiation can get there: (1 + S)^16 stays finite for every S below 1e19.)
-            if constexpr (DD > 16) { if (ssum < exp_floor<double>()) continue; }
+            // (Only the widest instantiation can get there: (1 + S)^16 stays finite for every S below 1e19; the Matern-5/2
+            // factor grows with S^2, so there the same holds up to 8 dimensions.)
+            if constexpr (DD > (KERN == 2 ? 8 : 16)) { if (ssum < exp_floor<double>()) continue; }
             const double ex = exp_nonpos(ssum);
             const double ge = G * ex;
             if constexpr (CZ) {
@@ -2231,8 +2275,12 @@ __global__ __launch_bounds__(256) void grad_kernel(const T* __restrict__ V, size
                 if constexpr (KERN == 0) {
                     acc[jj] = fma(ge * (sv[jj] * sv[jj]), pre[jj] * suf, acc[jj]);
                     suf = fma(suf, sv[jj], suf);
-                } else {
+                } else if constexpr (KERN == 1) {
                     acc[jj] = fma(ge, sv[jj] * sv[jj], acc[jj]);
+                } else {            // C0 S^2 (1 + S) / (3 f(S_j)) = exp(-sum S) m52_wl(S_j) prod_{i != j} f(S_i)
+                    static_assert(KERN == 2, "unknown covariance kernel id");
+                    acc[jj] = fma(ge * m52_wl(sv[jj]), pre[jj] * suf, acc[jj]);
+                    suf = fma(suf, m52_fm1(sv[jj]), suf);
                 }
             }
             acc[DD] = fma(ge, prod, acc[DD]);
@@ -2347,9 +2395,14 @@ __global__ __launch_bounds__(256) void grad_kernel_wide(const T* __restrict__ V,
                         const double s = fabs(xr[i][jj] - xc[j][jj]);
                         pr = fma(pr, s, pr);
                         ss -= s;
-                    } else {
+                    } else if constexpr (KERN == 1) {
                         const double s = xr[i][jj] - xc[j][jj];
                         ss = fma(-0.5 * s, s, ss);
+                    } else {
+                        static_assert(KERN == 2, "unknown covariance kernel id");
+                        const double s = fabs(xr[i][jj] - xc[j][jj]);
+                        pr = fma(pr, m52_fm1(s), pr);
+                        ss -= s;
                     }
                 }
                 prodT[2 * m + h] = pr;
@@ -2384,6 +2437,11 @@ __global__ __launch_bounds__(256) void grad_kernel_wide(const T* __restrict__ V,
                     cz1[m] = fma(cs, zc[j], cz1[m]);
                     if (gi != gj) cz2[h] = fma(cs, zr[i], cz2[h]);
                 }
+            } else {
+                // not part of the sum (padding, the upper half of a diagonal tile): its weight ge is zero, but its product may
+                // have overflowed, and 0 x inf in the sweep below would be a NaN (Matern-5/2 at collapsed lengthscales gets
+                // there from about 27 dimensions on, Matern-3/2 from about 52)
+                prodT[2 * m + h] = 0.0;
             }
             geT[2 * m + h] = ge;
         }
@@ -2402,7 +2460,11 @@ __global__ __launch_bounds__(256) void grad_kernel_wide(const T* __restrict__ V,
                 for (int h = 0; h < 2; ++h) {
                     const double s = fabs(xr[(tid >> 5) * 8 + m][jj] - xc[j0 + h][jj]);
                     if constexpr (KERN == 0) a = fma(geT[2 * m + h] * (s * s), prodT[2 * m + h] / (1.0 + s), a);
-                    else a = fma(geT[2 * m + h], s * s, a);
+                    else if constexpr (KERN == 1) a = fma(geT[2 * m + h], s * s, a);
+                    else {
+                        static_assert(KERN == 2, "unknown covariance kernel id");
+                        a = fma(geT[2 * m + h] * m52_wl(s), prodT[2 * m + h] / (1.0 + m52_fm1(s)), a);
+                    }
                 }
             a = wave_sum(a);
             if (lane == 0) red[wave][d0 + jj] = a;
@@ -2580,7 +2642,8 @@ __global__ __launch_bounds__(64) void pred_reduce_kernel(const T* __restrict__ X
 // K7: input gradients of the prediction.  For local component k, new input i (standardised) and dimension l:
 //   dghat[k, i, l] =        sum_j dc_l(i, j) sr_j z_k[j]
 //   dgvar[k, i, l] = -2 D_k sum_j dc_l(i, j) sr_j V_k[i, j],      V_k = X_k A_k^-1 = U_k W_k   (OP_PRED_V)
-//   dc_l = -c0 s_l / (ell_l (1 + |s_l|))  (Matern-3/2),   -c0 s_l / ell_l  (SE),   s_l = (x0_il - x_jl) / ell_l
+//   dc_l = -c0 s_l / (ell_l (1 + |s_l|))  (Matern-3/2),   -c0 s_l / ell_l  (SE),   s_l = (x0_il - x_jl) / ell_l,
+//          -c0 s_l (1 + |s_l|) / (ell_l (3 + 3 |s_l| + s_l^2))  (Matern-5/2)
 // with c0 = scale (1 - nug / (1 + nug)) C0: the nugget term has no derivative (the gradient of the continuous surface).
 // The scaled distances and c0 are recomputed in registers as cross_kernel forms them; the n0 x n x d derivative tensor is
 // never written.  One workgroup per (32 rows of x0, component, chunk of DD dimensions): lane & 31 = row, the 8 half-waves
@@ -2649,8 +2712,13 @@ __global__ __launch_bounds__(256) void pgrad_kernel(const T* __restrict__ x0, in
                     const double sd = fabs(df);
                     poly *= 1.0 + sd;
                     ssum -= sd;
-                } else {
+                } else if constexpr (KERN == 1) {
                     ssum = fma(-0.5 * df, df, ssum);
+                } else {
+                    static_assert(KERN == 2, "unknown covariance kernel id");
+                    const double sd = fabs(df);
+                    poly = fma(poly, m52_fm1(sd), poly);
+                    ssum -= sd;
                 }
             };
             if constexpr (WIDE) {
@@ -2659,12 +2727,19 @@ __global__ __launch_bounds__(256) void pgrad_kernel(const T* __restrict__ x0, in
 #pragma unroll
                 for (int m = 0; m < DD; ++m) acc_c0(xi[m] - xsh[jj][m]);
             }
-            const double c0 = c_off * (KERN == 0 ? fmin(poly, poly_cap<double>()) * exp_nonpos(ssum) : exp_nonpos(ssum));
+            const double c0 = c_off * kern_c0<KERN>(poly, ssum);
             const double a = c0 * wz[jj], b = c0 * wsr[jj] * vsh[r][jj];
 #pragma unroll
             for (int l = 0; l < DD; ++l) {
                 const double s = WIDE ? x0sh[r][l0 + l] - xsh[jj][l0 + l] : xi[l] - xsh[jj][l];
-                const double h = KERN == 0 ? s * fast_rcp(1.0 + fabs(s)) : s;
+                double h;
+                if constexpr (KERN == 0) h = s * fast_rcp(1.0 + fabs(s));
+                else if constexpr (KERN == 1) h = s;
+                else {              // m52_wx(s) = s (1 + |s|) / (3 + 3 |s| + s^2)
+                    static_assert(KERN == 2, "unknown covariance kernel id");
+                    const double sa = fabs(s);
+                    h = fma(s, sa, s) * fast_rcp(fma(sa, sa + 3.0, 3.0));
+                }
                 am[l] = fma(a, h, am[l]);
                 av[l] = fma(b, h, av[l]);
             }
@@ -2697,11 +2772,13 @@ __global__ __launch_bounds__(256) void pgrad_kernel(const T* __restrict__ x0, in
         if (e__ != hipSuccess) return fail(what, e__);      \
     } while (0)
 
-// f(std::integral_constant<int, KERN>{}) for the covariance kernel id w.kern (0 = Matern-3/2, 1 = squared exponential)
+// f(std::integral_constant<int, KERN>{}) for the covariance kernel id w.kern (0 = Matern-3/2, 1 = squared exponential,
+// 2 = Matern-5/2; validated at the C ABI)
 template <typename F>
 inline void for_kern(int kern, F&& f) {
     if (kern == 0) f(std::integral_constant<int, 0>{});
-    else f(std::integral_constant<int, 1>{});
+    else if (kern == 1) f(std::integral_constant<int, 1>{});
+    else f(std::integral_constant<int, 2>{});
 }
 
 // f(std::integral_constant<int, DD>{}) for the smallest input-dimension bound DD >= d the narrow kernels are built for
@@ -3150,7 +3227,8 @@ __global__ __launch_bounds__(256) void pack_partial_kernel(int d, int p, int q_l
 
 int check_common(int dtype, int n, int d, int p, int q, int kernel_id = 0) {
     if (dtype != LCGP_F64 && dtype != LCGP_F32) return bad("dtype must be 0 (f64) or 1 (f32)");
-    if (kernel_id != LCGP_KERNEL_MATERN32 && kernel_id != LCGP_KERNEL_SE) return bad("kernel_id must be 0 (Matern-3/2) or 1 (squared exponential)");
+    if (kernel_id != LCGP_KERNEL_MATERN32 && kernel_id != LCGP_KERNEL_SE && kernel_id != LCGP_KERNEL_MATERN52)
+        return bad("kernel_id must be 0 (Matern-3/2), 1 (squared exponential) or 2 (Matern-5/2)");
     if (n < 1) return bad("n < 1");
     if (d < 1 || d > DWIDE) return bad("d must be in [1, 126]");
     if (p < 1) return bad("p < 1");
@@ -3769,12 +3847,17 @@ __device__ __forceinline__ double sel_kern(const double* __restrict__ a, const d
             const double sd = fabs(a[l] - b[l]);
             pl = fma(pl, sd, pl);
             ss -= sd;
-        } else {
+        } else if constexpr (KERN == 1) {
             const double df = a[l] - b[l];
             ss = fma(-0.5 * df, df, ss);
+        } else {
+            static_assert(KERN == 2, "unknown covariance kernel id");
+            const double sd = fabs(a[l] - b[l]);
+            pl = fma(pl, m52_fm1(sd), pl);
+            ss -= sd;
         }
     }
-    return KERN == 0 ? fmin(pl, poly_cap<double>()) * exp_nonpos(ss) : exp_nonpos(ss);
+    return kern_c0<KERN>(pl, ss);
 }
 
 // xs[k, i, l] = x[i, l] / ell_k[l] in double
@@ -4140,7 +4223,8 @@ int lcgp_predict_scratch_bytes(int dtype, int n, int q_local, int n0, size_t* by
 int lcgp_covmat(void* stream, int dtype, int kernel_id, int n1, int n2, int d, const void* x1, const void* x2, const double* ell,
                 double scale, double nug, int same, void* out) {
     if (dtype != LCGP_F64 && dtype != LCGP_F32) return bad("dtype must be 0 (f64) or 1 (f32)");
-    if (kernel_id != LCGP_KERNEL_MATERN32 && kernel_id != LCGP_KERNEL_SE) return bad("kernel_id must be 0 (Matern-3/2) or 1 (squared exponential)");
+    if (kernel_id != LCGP_KERNEL_MATERN32 && kernel_id != LCGP_KERNEL_SE && kernel_id != LCGP_KERNEL_MATERN52)
+        return bad("kernel_id must be 0 (Matern-3/2), 1 (squared exponential) or 2 (Matern-5/2)");
     if (n1 < 1 || n2 < 1) return bad("n1/n2 < 1");
     if (d < 1 || d > DWIDE) return bad("d must be in [1, 126]");
     if (!x1 || !x2 || !ell || !out) return bad("NULL pointer");

@@ -636,8 +636,9 @@ class HotPathEngine:
 
 
 def matern32_device(x1, x2, ell, scale, nug, same, dtype="float64", kernel="matern32"):
-    """covmat.py:31-55 on the GPU: returns the (n1, n2) matrix as a numpy float64 array (kernel = "se": the squared-exponential
-    product kernel with the same scale / nugget structure, an extension the reference does not have)."""
+    """covmat.py:31-55 on the GPU: returns the (n1, n2) matrix as a numpy float64 array (kernel = "se" / "matern52":
+    the squared-exponential and Matern-5/2 product kernels with the same scale / nugget structure, extensions the reference does
+    not have)."""
     import torch
     _hip.require_gpu()
     lib = _hip.load()

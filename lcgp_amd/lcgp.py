@@ -95,9 +95,11 @@ class LCGP:
                  verbose=False, *, device=None, dtype='float64', process_group=None, kernel='matern32'):
         self.verbose = verbose
         # covariance kernel of the latent components: 'matern32' is the reference's only kernel (covmat.py:5-55); 'se', the
-        # squared-exponential product kernel, is an extension (BASELINE.json's north star names it; parity unpinned)
-        if kernel not in ('matern32', 'se'):
-            raise ValueError("kernel must be 'matern32' or 'se', got %r" % (kernel,))
+        # squared-exponential product kernel, is an extension (BASELINE.json's north star names it; parity unpinned), and so is
+        # 'matern52': prod_j (1 + S_j + S_j^2 / 3) exp(-sum_j S_j) in the reference's convention for Matern-3/2 (no sqrt(5):
+        # the textbook Matern-5/2 at lengthscale sqrt(5) ell_j), whose predictions are twice differentiable in x0
+        if kernel not in ('matern32', 'se', 'matern52'):
+            raise ValueError("kernel must be 'matern32', 'se' or 'matern52', got %r" % (kernel,))
         self.kernel = kernel
         self.robust_mean = robust_mean
         self.rep_standardize_ybar = rep_standardize_ybar

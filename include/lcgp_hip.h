@@ -59,7 +59,8 @@ extern "C" {
  *                         eigendecomposition form = Cholesky form), never against the reference.
  *   LCGP_KERNEL_MATERN52  Matern-5/2 product kernel in the convention of LCGP_KERNEL_MATERN32 (no sqrt(5) factor):
  *                         C0 = prod_j (1 + S_j + S_j^2 / 3) exp(-sum_j S_j), which is the textbook Matern-5/2 at lengthscale
- *                         sqrt(5) ell_j per dimension.  Twice differentiable predictions (Matern-3/2: once).  The reference
+ *                         sqrt(5) ell_j per dimension.  Twice differentiable sample paths (Matern-3/2: once; the PREDICTIONS of all three
+ *                         kernels have the input Hessians of lcgp_predict_hess).  The reference
  *                         has no such kernel either: an extension like LCGP_KERNEL_SE, parity UNPINNED, tied to identities
  *                         only.  Every call that takes a kernel_id accepts it. */
 #define LCGP_KERNEL_MATERN32 0
@@ -251,6 +252,40 @@ int lcgp_predict_grad(void* stream, int dtype, int kernel_id, int n, int d, int 
                       int n0, const void* x0, void* scratch,
                       double* ghat, double* gvar,        /* q_local rows of n0, `out_stride` apart */
                       double* dghat, double* dgvar,      /* q_local x n0 x d, row k at k * out_stride * d */
+                      int out_stride);
+
+/* Input Hessians of the prediction (the reference gets them by nesting two gradient tapes around predict; this entry point
+ * replaces both).  Derivatives with respect to the STANDARDISED inputs, per point, same = 0 throughout as in lcgp_predict_grad.
+ * With X_k, W_k, U_k, V_k, z_k as there, s_l = (x0_il - x_jl) / ell_l, a = |s_l|, for local component k, new input i and
+ * dimensions l, m:
+ *     d_l c     = c phi_l,  phi_l = -h(s_l) / ell_l      d2_lm c = c phi_l phi_m  (l != m)      d2_ll c = c psi(s_l) / ell_l^2
+ *       Matern-3/2: h = s / (1 + a)                 psi = -(1 - a) / (1 + a)        (continuous at 0, with a kink there)
+ *       SE        : h = s                           psi = s^2 - 1
+ *       Matern-5/2: h = s (1 + a) / (3 + 3 a + a^2) psi = -(1 + a - a^2) / (3 + 3 a + a^2)
+ *     d2ghat[k, i, l, m] =        sum_j d2_lm c(i, j) sr_j z_k[j]
+ *     d2gvar[k, i, l, m] = -2 D_k (sum_j d2_lm c(i, j) sr_j V_k[i, j] + P_il . P_im),   P_il = (d_l X_i) W_k^T  (n elements)
+ * ghat, gvar, dghat, dgvar are written as well and are BITWISE those of lcgp_predict_grad (the same launches, enqueued first).
+ * Then: one launch writes the rows d_l X_i (row i d + l, without their factor -1 / ell_l, zero padded to whole tiles), the
+ * tile kernel forms P (the product of lcgp_predict's U on n0 d rows), one wave per point and 4 x 4 block of dimension pairs
+ * forms the dot products P_il . P_im, and a fused contraction (c recomputed in registers, V staged through LDS, the n0 x n x d x
+ * d tensor never written) adds the sums over j and applies -2 D_k / (ell_l ell_m).
+ * Input: the workspace of the last lcgp_nll_grad at the same theta, as for lcgp_predict.
+ * scratch: lcgp_predict_hess_scratch_bytes(dtype, n, d, q_local, n0) bytes = 2 q_local (n0pad + rpad) npad elements, n0pad as in
+ *   lcgp_predict, rpad = n0 d rounded up to 128 (to 64 below 128); its content on entry is irrelevant.
+ *   n0 d <= LCGP_HESS_MAX_ROWS (a caller with more passes the new inputs in chunks, as for lcgp_predict).
+ * Outputs: the four of lcgp_predict_grad; d2ghat / d2gvar q_local x n0 x d (d + 1) / 2, the packed lower triangle, entry
+ *   (l, m <= l) at l (l + 1) / 2 + m, row k at k * out_stride * d (d + 1) / 2.
+ * Flops per component: those of lcgp_predict_grad + rpad npad^2 / 2 (P) + 2 n0 n d (d + 1) / 2-ish in the dot products and the
+ * contraction; the reduction order is fixed (no atomics): bitwise reproducible, independent of q_local, of how a caller splits
+ * the new inputs over calls and of the scratch content on entry. */
+#define LCGP_HESS_MAX_ROWS 4194304
+int lcgp_predict_hess_scratch_bytes(int dtype, int n, int d, int q_local, int n0, size_t* bytes /*host out*/);
+int lcgp_predict_hess(void* stream, int dtype, int kernel_id, int n, int d, int p, int q_local,
+                      const void* x, const void* sr, const double* theta, const void* workspace,
+                      int n0, const void* x0, void* scratch,
+                      double* ghat, double* gvar,        /* q_local rows of n0, `out_stride` apart */
+                      double* dghat, double* dgvar,      /* q_local x n0 x d, row k at k * out_stride * d */
+                      double* d2ghat, double* d2gvar,    /* q_local x n0 x d (d + 1) / 2, row k at k * out_stride * d (d + 1) / 2 */
                       int out_stride);
 
 /* Joint posterior covariance over new inputs, and correlated draws (no counterpart in the reference: its predict is marginal

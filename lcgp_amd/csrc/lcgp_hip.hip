@@ -23,7 +23,7 @@
 #include "../../include/lcgp_hip.h"
 #include "fill_sched.h"
 
-#define LCGP_VERSION 570
+#define LCGP_VERSION 580
 
 namespace {
 
@@ -4146,6 +4146,325 @@ int do_sel_condition(hipStream_t st, const Ws& w, const double* theta, int n_ref
     return 0;
 }
 
+// ---------------------------------------------------------------------------------------------------
+// K8: input Hessians of the prediction.  For local component k, new input i (standardised) and dimensions m <= l, with
+// s_l = (x0_il - x_jl) / ell_l, h = -(d/ds) log f and psi = f'' / f of the 1-D factor f (kern_h / kern_psi):
+//   kap_lm(i, j) = h(s_l) h(s_m)  (l != m),   psi(s_l)  (l == m)              d2c_lm = c0 kap_lm / (ell_l ell_m)
+//   d2ghat[k, i, lm] =         sum_j c0 kap_lm sr_j z_k[j]                  / (ell_l ell_m)
+//   d2gvar[k, i, lm] = -2 D_k (sum_j c0 kap_lm sr_j V_k[i, j] + G_i[l, m]) / (ell_l ell_m)
+//   G_i[l, m] = P[i d + l] . P[i d + m],   P = DX W^T,   DX[i d + l, j] = c0(i, j) sr_j h(s_l)     (the 1 / ell and the two signs
+//   of d c0 / d x0_l = -c0 h / ell_l leave the rows and meet in the last step)
+// Launches behind do_predict_grad: pdx_kernel (DX), OP_PRED_U of the tile kernel (P), phess_gram_kernel (G, into d2gvar),
+// phess_kernel (the fused contraction, which reads G back and finishes both outputs).  The dimension pairs are worked in
+// PH_B x PH_B blocks (lb >= mb) selected by blockIdx.z, so the accumulators per lane do not grow with d.  Fixed summation
+// order, no atomics.
+// ---------------------------------------------------------------------------------------------------
+constexpr int PH_B = 4;        // dimensions per block of a block pair
+constexpr int PH_PTS = 16;     // new inputs per workgroup of pdx_kernel
+
+template <int KERN>
+__device__ __forceinline__ double kern_h(double s) {
+    if constexpr (KERN == 0) return s * fast_rcp(1.0 + fabs(s));
+    else if constexpr (KERN == 1) return s;
+    else {
+        static_assert(KERN == 2, "unknown covariance kernel id");
+        const double sa = fabs(s);
+        return fma(s, sa, s) * fast_rcp(fma(sa, sa + 3.0, 3.0));
+    }
+}
+
+template <int KERN>
+__device__ __forceinline__ double kern_psi(double s) {
+    const double sa = fabs(s);
+    if constexpr (KERN == 0) return (sa - 1.0) * fast_rcp(1.0 + sa);
+    else if constexpr (KERN == 1) return fma(s, s, -1.0);
+    else {
+        static_assert(KERN == 2, "unknown covariance kernel id");
+        return fma(sa, sa - 1.0, -1.0) * fast_rcp(fma(sa, sa + 3.0, 3.0));
+    }
+}
+
+template <int KERN>
+__device__ __forceinline__ void kern_acc(double df, double& poly, double& ssum) {
+    if constexpr (KERN == 0) {
+        const double sd = fabs(df);
+        poly *= 1.0 + sd;
+        ssum -= sd;
+    } else if constexpr (KERN == 1) {
+        ssum = fma(-0.5 * df, df, ssum);
+    } else {
+        static_assert(KERN == 2, "unknown covariance kernel id");
+        const double sd = fabs(df);
+        poly = fma(poly, m52_fm1(sd), poly);
+        ssum -= sd;
+    }
+}
+
+// DX[k][i d + l, j] = c0(i, j) sr_j h(s_l) for i < n0, j < n; zero in the columns n .. npad and the rows n0 d .. rows_pad.
+// One workgroup per (64 columns, PH_PTS new inputs, component): lane & 63 = column, each wave four inputs; c0 over all d
+// in chunks of DMAX dimensions through LDS as cross_kernel forms it, then the d rows of each input (64 consecutive elements
+// per wave and row).
+template <typename T, int KERN>
+__global__ __launch_bounds__(256) void pdx_kernel(T* __restrict__ DX, size_t slab, int ld, int n0, int n, int d, int rows_pad,
+                                                  const T* __restrict__ x0, const T* __restrict__ x, const T* __restrict__ sr,
+                                                  const double* __restrict__ theta, int tw) {
+    __shared__ double xr[PH_PTS][DMAX + 1];
+    __shared__ double xc[TS][DMAX + 1];
+    __shared__ double cs[TS];
+    __shared__ double th[DWIDE + 2];
+    const int c = blockIdx.x, i0 = blockIdx.y * PH_PTS, k = blockIdx.z;
+    const int tid = threadIdx.x, j = tid & 63, wv = tid >> 6, gj = c * TS + j;
+    T* out = DX + (size_t)k * slab;
+    for (int e = tid; e < d + 2; e += 256) th[e] = theta[(size_t)k * tw + e];
+    if (tid < TS) cs[tid] = gj < n ? (sr ? (double)sr[gj] : 1.0) : 0.0;
+    __syncthreads();
+    const double scale = th[d], nug = th[d + 1];
+    const double c_off = scale * (1.0 - nug / (1.0 + nug));
+    auto stage = [&](int d0, int dc) {
+        for (int e = tid; e < TS * dc; e += 256) {
+            const int jj = e / dc, m = e - jj * dc, gjj = c * TS + jj;
+            xc[jj][m] = gjj < n ? (double)x[(size_t)gjj * d + d0 + m] / th[d0 + m] : 0.0;
+        }
+        for (int e = tid; e < PH_PTS * dc; e += 256) {
+            const int ii = e / dc, m = e - ii * dc;
+            xr[ii][m] = i0 + ii < n0 ? (double)x0[(size_t)(i0 + ii) * d + d0 + m] / th[d0 + m] : 0.0;
+        }
+    };
+    double poly[4], ssum[4];
+#pragma unroll
+    for (int a = 0; a < 4; ++a) { poly[a] = 1.0; ssum[a] = 0.0; }
+    for (int d0 = 0; d0 < d; d0 += DMAX) {
+        const int dc = d - d0 < DMAX ? d - d0 : DMAX;
+        if (d0 > 0) __syncthreads();
+        stage(d0, dc);
+        __syncthreads();
+#pragma unroll
+        for (int a = 0; a < 4; ++a)
+            for (int m = 0; m < dc; ++m) kern_acc<KERN>(xr[wv * 4 + a][m] - xc[j][m], poly[a], ssum[a]);
+    }
+    double v[4];
+#pragma unroll
+    for (int a = 0; a < 4; ++a) v[a] = c_off * kern_c0<KERN>(poly[a], ssum[a]) * cs[j];      // (zero in the columns beyond n)
+    for (int d0 = 0; d0 < d; d0 += DMAX) {
+        const int dc = d - d0 < DMAX ? d - d0 : DMAX;
+        if (d > DMAX) {                                  // (a single chunk is still resident)
+            __syncthreads();
+            stage(d0, dc);
+            __syncthreads();
+        }
+#pragma unroll
+        for (int a = 0; a < 4; ++a) {
+            const int i = i0 + wv * 4 + a;
+            if (i >= n0) continue;
+            T* row = out + ((size_t)i * d + d0) * ld + gj;
+            for (int m = 0; m < dc; ++m) row[(size_t)m * ld] = (T)(v[a] * kern_h<KERN>(xr[wv * 4 + a][m] - xc[j][m]));
+        }
+    }
+    if (blockIdx.y == gridDim.y - 1)
+        for (int r = n0 * d + wv; r < rows_pad; r += 4) out[(size_t)r * ld + gj] = (T)0;
+}
+
+// G_i[l, m] = P[i d + l] . P[i d + m] over the n columns for the block pair blockIdx.z = (lb, mb), into the packed lower
+// triangle of d2gvar (entries with m <= l < d).  One wave per new input: 16-byte loads of the 2 PH_B rows, PH_B^2
+// accumulators in double, the fixed butterfly of wave_sum.
+template <typename T>
+__global__ __launch_bounds__(256) void phess_gram_kernel(const T* __restrict__ P, size_t slab, int ld, int n, int n0, int d,
+                                                         int ldo, double* __restrict__ d2gvar) {
+    constexpr int VN = SelVec<T>::N;
+    typedef typename SelVec<T>::v V;
+    const int lane = threadIdx.x & 63, i = blockIdx.x * 4 + (threadIdx.x >> 6), k = blockIdx.y;
+    if (i >= n0) return;
+    int lb, mb;
+    tri_decode(blockIdx.z, lb, mb);
+    const int l0 = lb * PH_B, m0 = mb * PH_B;
+    const T* base = P + (size_t)k * slab + (size_t)i * d * ld;
+    const T* ra[PH_B];
+    const T* rb[PH_B];
+#pragma unroll
+    for (int a = 0; a < PH_B; ++a) {                    // (dimensions beyond d: row d - 1 again, never written out)
+        ra[a] = base + (size_t)min(l0 + a, d - 1) * ld;
+        rb[a] = base + (size_t)min(m0 + a, d - 1) * ld;
+    }
+    double acc[PH_B][PH_B];
+#pragma unroll
+    for (int a = 0; a < PH_B; ++a)
+#pragma unroll
+        for (int b = 0; b < PH_B; ++b) acc[a][b] = 0.0;
+    const int nv = n / VN;
+    for (int p = lane; p < nv; p += 64) {
+        V xa[PH_B], xb[PH_B];
+#pragma unroll
+        for (int a = 0; a < PH_B; ++a) {
+            xa[a] = *(const V*)(ra[a] + (size_t)p * VN);
+            xb[a] = *(const V*)(rb[a] + (size_t)p * VN);
+        }
+#pragma unroll
+        for (int a = 0; a < PH_B; ++a)
+#pragma unroll
+            for (int b = 0; b < PH_B; ++b)
+#pragma unroll
+                for (int e = 0; e < VN; ++e) acc[a][b] = fma((double)xa[a][e], (double)xb[b][e], acc[a][b]);
+    }
+    const int tail = nv * VN + lane;
+    if (tail < n) {
+#pragma unroll
+        for (int a = 0; a < PH_B; ++a)
+#pragma unroll
+            for (int b = 0; b < PH_B; ++b) acc[a][b] = fma((double)ra[a][tail], (double)rb[b][tail], acc[a][b]);
+    }
+    double* o = d2gvar + ((size_t)k * ldo + i) * ((size_t)d * (d + 1) / 2);
+#pragma unroll
+    for (int a = 0; a < PH_B; ++a)
+#pragma unroll
+        for (int b = 0; b < PH_B; ++b) {
+            const double s = wave_sum(acc[a][b]);
+            const int l = l0 + a, m = m0 + b;
+            if (lane == 0 && l < d && m <= l) o[l * (l + 1) / 2 + m] = s;
+        }
+}
+
+// The fused second-derivative contraction, modelled on pgrad_kernel: one workgroup per (32 rows of x0, component, block
+// pair): lane & 31 = row, the 8 half-waves take every 8th training input of a stage of JT.  c0 over all d from LDS, kap for
+// the PH_B x PH_B entries of the block pair (2 PH_B^2 accumulators per lane whatever d), V staged through LDS; the n0 x n x
+// d x d tensor is never written.  Per lane in ascending j, then the 8 slices in a fixed order.  The last step adds the Gram
+// term phess_gram_kernel left in d2gvar and applies -2 D_k / (ell_l ell_m).  WIDE: d > 16 (rows of DWIDE + 3 doubles in LDS).
+template <typename T, int KERN, bool WIDE>
+__global__ __launch_bounds__(256) void phess_kernel(const T* __restrict__ x0, int n0, const T* __restrict__ x,
+                                                    const T* __restrict__ sr, int n, int d, const double* __restrict__ theta,
+                                                    int tw, const T* __restrict__ z, int npad, const T* __restrict__ V,
+                                                    size_t slab, int ldo, double* __restrict__ d2ghat,
+                                                    double* __restrict__ d2gvar) {
+    constexpr int JT = WIDE ? 16 : 32;                  // training inputs per LDS stage
+    constexpr int XW = WIDE ? DWIDE + 3 : 16 + PH_B + 1; // odd row length >= l0 + PH_B for every block (zeros beyond d)
+    __shared__ double x0sh[PG_ROWS][XW];
+    __shared__ double xsh[JT][XW];
+    __shared__ double vsh[PG_ROWS][JT + 1];
+    __shared__ double wz[JT], wsr[JT];
+    __shared__ double th[DWIDE + 3];
+    __shared__ double red[2][4][PG_ROWS];
+    const int k = blockIdx.y, i0 = blockIdx.x * PG_ROWS;
+    int lb, mb;
+    tri_decode(blockIdx.z, lb, mb);
+    const int l0 = lb * PH_B, m0 = mb * PH_B;
+    const bool diag = lb == mb;
+    const int tid = threadIdx.x, r = tid & 31, sl = tid >> 5;
+    for (int e = tid; e < d + 3; e += 256) th[e] = theta[(size_t)k * tw + e];
+    __syncthreads();
+    const double scale = th[d], nug = th[d + 1], D = th[d + 2];
+    const double c_off = scale * (1.0 - nug / (1.0 + nug));
+    for (int e = tid; e < PG_ROWS * XW; e += 256) {
+        const int i = e / XW, m = e - i * XW;
+        x0sh[i][m] = (i0 + i < n0 && m < d) ? (double)x0[(size_t)(i0 + i) * d + m] / th[m] : 0.0;
+    }
+    const T* zk = z + (size_t)k * npad;
+    const T* Vk = V + (size_t)k * slab;
+    double am[PH_B][PH_B], av[PH_B][PH_B];
+#pragma unroll
+    for (int a = 0; a < PH_B; ++a)
+#pragma unroll
+        for (int b = 0; b < PH_B; ++b) { am[a][b] = 0.0; av[a][b] = 0.0; }
+    for (int j0 = 0; j0 < n; j0 += JT) {
+        __syncthreads();                                // x0sh is written; every slice is done with the previous stage
+        for (int e = tid; e < JT * XW; e += 256) {
+            const int jj = e / XW, m = e - jj * XW;
+            xsh[jj][m] = (j0 + jj < n && m < d) ? (double)x[(size_t)(j0 + jj) * d + m] / th[m] : 0.0;
+        }
+        for (int e = tid; e < PG_ROWS * JT; e += 256) {
+            const int i = e / JT, jj = e - i * JT;
+            vsh[i][jj] = (i0 + i < n0 && j0 + jj < n) ? (double)Vk[(size_t)(i0 + i) * npad + j0 + jj] : 0.0;
+        }
+        if (tid < JT) {
+            const int j = j0 + tid;
+            const double s = j < n ? (sr ? (double)sr[j] : 1.0) : 0.0;      // (inputs beyond n weigh zero)
+            wsr[tid] = s;
+            wz[tid] = j < n ? s * (double)zk[j] : 0.0;
+        }
+        __syncthreads();
+        for (int jj = sl; jj < JT; jj += PG_SL) {
+            double poly = 1.0, ssum = 0.0;
+            for (int m = 0; m < d; ++m) kern_acc<KERN>(x0sh[r][m] - xsh[jj][m], poly, ssum);
+            const double c0 = c_off * kern_c0<KERN>(poly, ssum);
+            const double ca = c0 * wz[jj], cb = c0 * wsr[jj] * vsh[r][jj];
+            double hl[PH_B], hm[PH_B];
+#pragma unroll
+            for (int a = 0; a < PH_B; ++a) {
+                hl[a] = kern_h<KERN>(x0sh[r][l0 + a] - xsh[jj][l0 + a]);
+                hm[a] = kern_h<KERN>(x0sh[r][m0 + a] - xsh[jj][m0 + a]);
+            }
+#pragma unroll
+            for (int a = 0; a < PH_B; ++a)
+#pragma unroll
+                for (int b = 0; b < PH_B; ++b) {
+                    double kap = hl[a] * hm[b];
+                    if (a == b && diag) kap = kern_psi<KERN>(x0sh[r][l0 + a] - xsh[jj][l0 + a]);
+                    am[a][b] = fma(ca, kap, am[a][b]);
+                    av[a][b] = fma(cb, kap, av[a][b]);
+                }
+        }
+    }
+    // slices 2w and 2w + 1 share wave w (lanes r, r + 32), then the four waves through LDS: a fixed order
+    const int wave = tid >> 6, i = i0 + r;
+    const size_t orow = ((size_t)k * ldo + i) * ((size_t)d * (d + 1) / 2);
+#pragma unroll
+    for (int a = 0; a < PH_B; ++a)
+#pragma unroll
+        for (int b = 0; b < PH_B; ++b) {
+            const double sm = am[a][b] + __shfl_xor(am[a][b], 32), sv = av[a][b] + __shfl_xor(av[a][b], 32);
+            if ((tid & 63) < 32) { red[0][wave][r] = sm; red[1][wave][r] = sv; }
+            __syncthreads();
+            const int l = l0 + a, m = m0 + b;
+            if (tid < PG_ROWS && i < n0 && l < d && m <= l) {
+                const double tm = (red[0][0][r] + red[0][1][r]) + (red[0][2][r] + red[0][3][r]);
+                const double tv = (red[1][0][r] + red[1][1][r]) + (red[1][2][r] + red[1][3][r]);
+                const double inv = 1.0 / (th[l] * th[m]);
+                const size_t o = orow + (size_t)(l * (l + 1) / 2 + m);
+                d2ghat[o] = tm * inv;
+                d2gvar[o] = -2.0 * D * (tv + d2gvar[o]) * inv;
+            }
+            __syncthreads();
+        }
+}
+
+inline int hess_rows_pad(int n0, int d) { return predict_pad(n0 * d); }
+
+// K8 for all local components: do_predict_grad (its four outputs bitwise those of lcgp_predict_grad; V_k stays in the X
+// slab), then DX and P = DX W^T in the second half of the scratch, the Gram terms and the fused contraction.
+template <typename T>
+int do_predict_hess(hipStream_t st, const Ws& w, const void* x, const void* sr, const double* theta, int n0, const void* x0,
+                    void* scratch, double* ghat, double* gvar, double* dghat, double* dgvar, double* d2ghat, double* d2gvar,
+                    int ldo) {
+    int rc = do_predict_grad<T>(st, w, x, sr, theta, n0, x0, scratch, ghat, gvar, dghat, dgvar, ldo);
+    if (rc) return rc;
+    const int n0pad = predict_pad(n0), rows_pad = hess_rows_pad(n0, w.d), tw = w.d + 3 + w.p;
+    const size_t slab = (size_t)n0pad * w.npad, dslab = (size_t)rows_pad * w.npad;
+    const T* V = (const T*)scratch;                     // q slabs n0pad x npad : X A^-1 (do_predict_grad)
+    T* DX = (T*)scratch + 2 * slab * w.q;               // q slabs rows_pad x npad : c0 sr h(s_l), row i d + l
+    T* P = DX + dslab * w.q;                            // q slabs rows_pad x npad : DX W^T
+    for_kern(w.kern, [&](auto kern) {
+        hipLaunchKernelGGL((pdx_kernel<T, decltype(kern)::value>), dim3(w.nb, (n0 + PH_PTS - 1) / PH_PTS, w.q), dim3(256), 0, st,
+                           DX, dslab, w.npad, n0, w.n, w.d, rows_pad, (const T*)x0, (const T*)x, (const T*)sr, theta, tw);
+    });
+    CHECK_LAUNCH("pdx_kernel");
+    rc = launch_pred<T, OP_PRED_U>(st, DX, (const T*)(w.base + w.off_W), P, dslab, w.mat, w.npad, rows_pad, w.nb, w.q);
+    if (rc) return rc;
+    const int nblk = (w.d + PH_B - 1) / PH_B, npair = nblk * (nblk + 1) / 2;
+    hipLaunchKernelGGL((phess_gram_kernel<T>), dim3((n0 + 3) / 4, w.q, npair), dim3(256), 0, st, (const T*)P, dslab, w.npad, w.n,
+                       n0, w.d, ldo, d2gvar);
+    CHECK_LAUNCH("phess_gram_kernel");
+    dim3 grid((n0 + PG_ROWS - 1) / PG_ROWS, w.q, npair);
+    for_kern(w.kern, [&](auto kern) {
+        auto go = [&](auto wide) {
+            hipLaunchKernelGGL((phess_kernel<T, decltype(kern)::value, decltype(wide)::value>), grid, dim3(256), 0, st,
+                               (const T*)x0, n0, (const T*)x, (const T*)sr, w.n, w.d, theta, tw, (const T*)(w.base + w.off_z),
+                               w.npad, V, slab, ldo, d2ghat, d2gvar);
+        };
+        if (w.d > 16) go(std::true_type{});
+        else go(std::false_type{});
+    });
+    CHECK_LAUNCH("phess_kernel");
+    return 0;
+}
+
 int check_sel(int n_ref, int n_cand, int size) {
     int rc = check_vr(n_ref, n_cand);
     if (rc) return rc;
@@ -4452,6 +4771,36 @@ int lcgp_predict_grad(void* stream, int dtype, int kernel_id, int n, int d, int 
     hipStream_t st = (hipStream_t)stream;
     return dtype == LCGP_F64 ? do_predict_grad<double>(st, w, x, sr, theta, n0, x0, scratch, ghat, gvar, dghat, dgvar, ldo)
                              : do_predict_grad<float>(st, w, x, sr, theta, n0, x0, scratch, ghat, gvar, dghat, dgvar, ldo);
+}
+
+int lcgp_predict_hess_scratch_bytes(int dtype, int n, int d, int q_local, int n0, size_t* bytes) {
+    if (dtype != LCGP_F64 && dtype != LCGP_F32) return bad("dtype must be 0 (f64) or 1 (f32)");
+    if (n < 1 || n0 < 1 || q_local < 1) return bad("n, n0, q_local must be >= 1");
+    if (d < 1 || d > DWIDE) return bad("d must be in [1, 126]");
+    if ((long long)n0 * d > LCGP_HESS_MAX_ROWS) return bad("n0 * d must be <= LCGP_HESS_MAX_ROWS: pass the new inputs in chunks");
+    if (!bytes) return bad("bytes is NULL");
+    const size_t npad = round_up(n, 2 * TS), n0pad = predict_pad(n0), rows_pad = hess_rows_pad(n0, d);
+    *bytes = 2 * (size_t)q_local * (n0pad + rows_pad) * npad * (dtype == LCGP_F64 ? 8 : 4);
+    return 0;
+}
+
+int lcgp_predict_hess(void* stream, int dtype, int kernel_id, int n, int d, int p, int q_local, const void* x, const void* sr,
+                      const double* theta, const void* workspace, int n0, const void* x0, void* scratch,
+                      double* ghat, double* gvar, double* dghat, double* dgvar, double* d2ghat, double* d2gvar, int out_stride) {
+    int rc = check_common(dtype, n, d, p, q_local, kernel_id);
+    if (rc) return rc;
+    if (n0 < 1) return bad("n0 < 1");
+    if ((long long)n0 * d > LCGP_HESS_MAX_ROWS) return bad("n0 * d must be <= LCGP_HESS_MAX_ROWS: pass the new inputs in chunks");
+    if (!x || !theta || !workspace || !x0 || !scratch || !ghat || !gvar || !dghat || !dgvar || !d2ghat || !d2gvar)
+        return bad("NULL pointer");
+    if (out_stride != 0 && out_stride < n0) return bad("out_stride must be 0 (= n0) or >= n0");
+    const int ldo = out_stride ? out_stride : n0;
+    Ws w = carve(dtype, n, d, p, q_local, (void*)workspace);
+    w.kern = kernel_id;
+    hipStream_t st = (hipStream_t)stream;
+    return dtype == LCGP_F64
+               ? do_predict_hess<double>(st, w, x, sr, theta, n0, x0, scratch, ghat, gvar, dghat, dgvar, d2ghat, d2gvar, ldo)
+               : do_predict_hess<float>(st, w, x, sr, theta, n0, x0, scratch, ghat, gvar, dghat, dgvar, d2ghat, d2gvar, ldo);
 }
 
 int lcgp_predict_cov_scratch_bytes(int dtype, int n, int q_local, int n0, size_t* bytes) {

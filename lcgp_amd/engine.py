@@ -257,6 +257,44 @@ class HotPathEngine:
         Chunked like predict_block (PREDICT_CHUNK rows per call) and sharing its scratch."""
         return self._predict_chunks(x0s, False, True)
 
+    def predict_hess_block(self, x0s):
+        """(block, jac, hess) float64 DEVICE tensors for standardised x0s, from the factorisation of the last evaluate():
+        block (2, q_local, n0) and jac (2, q_local, n0, d) bitwise those of predict_grad_block(x0s); hess (2, q_local, n0,
+        d (d + 1) / 2) = [d2ghat; d2gvar], the packed lower triangles (entry (l, m <= l) at l (l + 1) / 2 + m) of the Hessians
+        with respect to x0s (lcgp_predict_hess).  Chunked so that one call forms at most PREDICT_CHUNK rows of P (chunk * d <=
+        PREDICT_CHUNK) but never fewer than 128 new inputs while n0 has them: the library forms V on 128-row tiles from 128 new
+        inputs on and on 64-row tiles below, in different summation orders, so a last pass of fewer than 128 inputs is moved
+        back to overlap its predecessor (the same values again).  All results are therefore bitwise independent of
+        PREDICT_CHUNK.  The scratch holds 2 q_local (chunk_pad + (chunk d)_pad) npad elements, chunk = max(128, PREDICT_CHUNK //
+        d); raises ValueError when it does not fit in the free device memory."""
+        torch = self.torch
+        if self._theta_last is None:
+            raise RuntimeError("predict_hess() needs a preceding evaluate() at the current parameters")
+        x0s = np.ascontiguousarray(x0s, np.float64)
+        n0, d = x0s.shape[0], self.d
+        assert x0s.ndim == 2 and x0s.shape[1] == d and n0 >= 1
+        tri = d * (d + 1) // 2
+        chunk = min(n0, max(128, PREDICT_CHUNK // d))
+        with torch.cuda.device(self.device):
+            x0d = torch.as_tensor(x0s).to(self.device, self.tdtype).contiguous()
+            nbytes = self._nbytes("lcgp_predict_hess_scratch_bytes", self.dtype, self.n, d, self.q_local, chunk)
+            scp = self._p(self._grow_scratch(nbytes, ("the Hessians of %d new inputs per pass" % chunk,
+                                                      "%d components of %d x n, twice" % (self.q_local, chunk * (d + 1)),
+                                                      "lower lcgp_amd.engine.PREDICT_CHUNK")))
+            out = torch.empty((2, self.q_local, n0), dtype=torch.float64, device=self.device)
+            jac = torch.empty((2, self.q_local, n0, d), dtype=torch.float64, device=self.device)
+            hess = torch.empty((2, self.q_local, n0, tri), dtype=torch.float64, device=self.device)
+            st, xp, srp, thp, wsp = self._stream(), self._p(self.x), self._p(self.sr), self._p(self.theta_dev), self._p(self.workspace)
+            for lo in range(0, n0, chunk):
+                m = min(chunk, n0 - lo)
+                if m < 128 <= n0:
+                    lo, m = n0 - 128, 128
+                x0p = C.c_void_p(x0d.data_ptr() + lo * d * x0d.element_size())
+                ptrs = [C.c_void_p(t[h].data_ptr() + 8 * lo * w) for t, w in ((out, 1), (jac, d), (hess, tri)) for h in (0, 1)]
+                _hip.check(self.lib.lcgp_predict_hess(st, self.dtype, self.kernel_id, self.n, d, self.p, self.q_local, xp, srp, thp,
+                                                      wsp, m, x0p, scp, *ptrs, n0), "lcgp_predict_hess")
+            return out, jac, hess
+
     def predict_device(self, x0s, same=False):
         """ghat, gvar (q_local, n0): the two halves of predict_block()"""
         out = self.predict_block(x0s, same)

@@ -79,6 +79,72 @@ class _PredictFn(torch.autograd.Function):
         return gx.reshape(ctx.x0_shape).to(device=ctx.x0_device, dtype=ctx.x0_dtype), None
 
 
+def _vjp_first(g_ypred, g_ypredvar, g_yconfvar, dyp, dycv):
+    """(n0, d) CPU float64: sum_a g_ypred[a, i] dyp[a, i, l] + (g_ypredvar + g_yconfvar)[a, i] dycv[a, i, l]"""
+    gp, gv = _cpu64(g_ypred), _cpu64(g_ypredvar) + _cpu64(g_yconfvar)
+    return torch.einsum('ai,ail->il', gp, dyp) + torch.einsum('ai,ail->il', gv, dycv)
+
+
+def _cpu64(t):
+    return t.detach().cpu().to(torch.float64)
+
+
+class _PredictFn2(torch.autograd.Function):
+    """LCGP.predict_differentiable(order=2): _PredictFn whose backward pass is itself a differentiable function
+    (_PredictVjpFn) of x0 and of the incoming gradients"""
+
+    @staticmethod
+    def forward(ctx, x0, model):
+        x0c = _cpu64(x0)
+        ghat, gvar, dghat, dgvar = model._latent_predict_grad(x0c)
+        outs = model._outputs(ghat, gvar)
+        dyp, dycv = model._output_jacobians(dghat, dgvar)
+        ctx.model, ctx.x0c = model, x0c
+        ctx.jac = (torch.as_tensor(dyp), torch.as_tensor(dycv))
+        ctx.save_for_backward(x0)
+        return tuple(o.to(x0.device) for o in outs[:3])
+
+    @staticmethod
+    def backward(ctx, g_ypred, g_ypredvar, g_yconfvar):
+        (x0,) = ctx.saved_tensors
+        return _PredictVjpFn.apply(x0, g_ypred, g_ypredvar, g_yconfvar, ctx.model, ctx.x0c, ctx.jac), None
+
+
+class _PredictVjpFn(torch.autograd.Function):
+    """gx[i, l] = sum_a g_ypred[a, i] dypred[a, i, l] + (g_ypredvar + g_yconfvar)[a, i] dyconfvar[a, i, l] as a function of x0
+    (through the Jacobians) and of the three incoming gradients.  Its backward contracts the Hessians of predict_hess(), fetched
+    by ONE lcgp_predict_hess pass, and only here: a first-order use of predict_differentiable(order=2) never pays for them."""
+
+    @staticmethod
+    def forward(ctx, x0, g_ypred, g_ypredvar, g_yconfvar, model, x0c, jac):
+        ctx.model, ctx.x0c, ctx.jac = model, x0c, jac
+        ctx.x0_meta = (x0.dtype, x0.device, x0.shape)
+        ctx.g_meta = [(g.dtype, g.device) for g in (g_ypred, g_ypredvar, g_yconfvar)]
+        ctx.save_for_backward(g_ypred, g_ypredvar, g_yconfvar)
+        gx = _vjp_first(g_ypred, g_ypredvar, g_yconfvar, *jac)
+        return gx.reshape(x0.shape).to(device=x0.device, dtype=x0.dtype)
+
+    @staticmethod
+    def backward(ctx, gg):
+        if torch.is_grad_enabled():         # a third derivative: the Hessians are constants, not a graph
+            raise RuntimeError('LCGP.predict_differentiable(order=2) supports first and second derivatives only: triple '
+                               'backward is not available; use predict_hess() for the Hessians')
+        g_ypred, g_ypredvar, g_yconfvar = ctx.saved_tensors
+        dyp, dycv = ctx.jac
+        ggc = _cpu64(gg).reshape(dyp.shape[1:])
+        gx0 = None
+        if ctx.needs_input_grad[0]:
+            d2yp, _, d2ycv = ctx.model.predict_hess(ctx.x0c)
+            gp, gv = _cpu64(g_ypred), _cpu64(g_ypredvar) + _cpu64(g_yconfvar)
+            gx0 = torch.einsum('ai,ailm,im->il', gp, d2yp, ggc) + torch.einsum('ai,ailm,im->il', gv, d2ycv, ggc)
+            dt, dev, shape = ctx.x0_meta
+            gx0 = gx0.reshape(shape).to(device=dev, dtype=dt)
+        gp = torch.einsum('ail,il->ai', dyp, ggc)
+        gv = torch.einsum('ail,il->ai', dycv, ggc)
+        gouts = [v.to(device=dev, dtype=dt) for v, (dt, dev) in zip((gp, gv, gv), ctx.g_meta)]
+        return (gx0, *gouts, None, None, None)
+
+
 class LCGP:
     """
     Latent Component Gaussian Process (LCGP), MI355X hot path.
@@ -1241,12 +1307,73 @@ class LCGP:
         dyp, dycv = self._output_jacobians(dghat, dgvar)
         return _t(dyp), _t(dycv.copy()), _t(dycv)
 
-    def predict_differentiable(self, x0):
+    def predict_differentiable(self, x0, order=1):
         """(ypred, ypredvar, yconfvar) (p, n0) as predict() returns them, float64 on x0's device, differentiable with respect to
         a requires_grad x0 (any device) through torch.autograd: the backward pass is the vector-Jacobian product with the
         Jacobians of predict_grad() saved by the forward pass (no second GPU pass).  The values equal predict(x0) whenever x0 is
-        not the training set (here the nugget term is never added: see predict_grad).  Double backward is not supported."""
-        return _PredictFn.apply(x0 if isinstance(x0, torch.Tensor) else torch.as_tensor(np.asarray(x0, F64)), self)
+        not the training set (here the nugget term is never added: see predict_grad).
+        order=1: first derivatives only; a double backward (create_graph=True) raises.  order=2: the backward pass is itself
+        differentiable, so torch.autograd.grad(..., create_graph=True), torch.autograd.functional.hessian and gradgradcheck
+        work; the Hessians come from one predict_hess() pass, made only when a double backward actually runs.  A third
+        derivative raises."""
+        if order not in (1, 2):
+            raise ValueError('predict_differentiable: order must be 1 or 2, got %r' % (order,))
+        x0 = x0 if isinstance(x0, torch.Tensor) else torch.as_tensor(np.asarray(x0, F64))
+        return (_PredictFn if order == 1 else _PredictFn2).apply(x0, self)
+
+    # =============================================================================================
+    # input Hessians of the prediction (the reference: two nested tf.GradientTapes around predict)
+    # =============================================================================================
+    def _latent_predict_hess(self, x0):
+        """ghat, gvar (q, n0), dghat, dgvar (q, n0, d) and the Hessians d2ghat, d2gvar (q, n0, d, d) with respect to the
+        STANDARDISED inputs, for raw-scale x0: the local components on the device (lcgp_predict_hess), ONE reduction of the
+        zero-padded block gathers them; the packed lower triangles are mirrored here, so the Hessians are exactly symmetric.
+        No nugget term, as in _latent_predict_grad."""
+        x0s, _ = self._standardise_x0(x0)
+        n0, d = x0s.shape
+        tri = d * (d + 1) // 2
+        eng = self._ensure_aux()
+        loc = None
+        if eng is not None:
+            blk, jac, hess = eng.predict_hess_block(x0s)
+            loc = torch.cat([t.movedim(1, 0).reshape(t.shape[1], -1) for t in (blk, jac, hess)], dim=1)
+        both = self._gather_components(loc, (2 * n0 * (1 + d + tri),))
+        q = int(self.q)
+        ghat, gvar = both[:, :n0], both[:, n0:2 * n0]
+        jac = both[:, 2 * n0:2 * n0 * (1 + d)].reshape(q, 2, n0, d)
+        packed = both[:, 2 * n0 * (1 + d):].reshape(q, 2, n0, tri)
+        il, im = np.tril_indices(d)                       # row-major over the lower triangle: entry (l, m) at l (l + 1) / 2 + m
+        full = np.empty((q, 2, n0, d, d), F64)
+        full[..., il, im] = packed
+        full[..., im, il] = packed
+        self.ghat, self.gvar = _t(ghat), _t(gvar)
+        self.dghat, self.dgvar = _t(jac[:, 0]), _t(jac[:, 1])
+        self.d2ghat, self.d2gvar = _t(full[:, 0]), _t(full[:, 1])
+        return ghat, gvar, jac[:, 0], jac[:, 1], full[:, 0], full[:, 1]
+
+    def _output_hessians(self, d2ghat, d2gvar):
+        """latent Hessians (q, n0, d, d) on the standardised scale -> (d2ypred, d2yconfvar) (p, n0, d, d) on the raw input and
+        output scales, as _output_jacobians:  d2ypred = scale_a sum_k W[k, a] d2ghat_k / (range_l range_m),  d2yconfvar with
+        W^2, scale_a^2"""
+        W, _, scale, _ = self._output_map()
+        rng = (_np(self.x_max) - _np(self.x_min)).reshape(-1)
+        rr = rng[:, None] * rng[None, :]
+        d2yp = np.einsum('ka,kilm->ailm', W, d2ghat) * scale[:, None, None, None] / rr
+        d2ycv = np.einsum('ka,kilm->ailm', W ** 2, d2gvar) * (scale ** 2)[:, None, None, None] / rr
+        return d2yp, d2ycv
+
+    def predict_hess(self, x0):
+        """Hessians of predict()'s outputs with respect to the new inputs, per point (output row i depends only on x0[i]):
+            d2ypred[a, i, l, m] = d^2 ypred[a, i] / d x0[i, l] d x0[i, m],   d2ypredvar, d2yconfvar likewise
+        each (p, n0, d, d), CPU float64, exactly symmetric in the last two axes, on the raw input and output scales;
+        d2ypredvar = d2yconfvar.  One pass on the GPU from the factorisation of the current parameters (lcgp_predict_hess),
+        in the engine's dtype; every kernel has them (Matern-3/2: continuous, with a kink where x0[i, l] equals a training
+        input's coordinate).  Nugget convention of predict_grad: the Hessian of the continuous prediction surface, also at
+        training inputs.  The latent Hessians stay on the model as d2ghat / d2gvar (q, n0, d, d), beside dghat / dgvar (which,
+        like ghat / gvar, this call sets to what predict_grad(x0) sets)."""
+        _, _, _, _, d2ghat, d2gvar = self._latent_predict_hess(x0)
+        d2yp, d2ycv = self._output_hessians(d2ghat, d2gvar)
+        return _t(d2yp), _t(d2ycv.copy()), _t(d2ycv)
 
     # ---- cache views the reference keeps as attributes (materialised from the device only when read) ----
     def _fetch_all(self, fn, width):

@@ -395,6 +395,31 @@ int lcgp_variance_reduction(void* stream, int dtype, int kernel_id, int n, int d
                             int n_cand, const void* x_cand, const int* match_host /*host or NULL*/, const int* match,
                             int cand_row0, int r, void* scratch, double* out, int out_stride);
 
+/* Gradient of the integrated variance reduction with respect to the candidate's location (standardised scale; no counterpart in
+ * the reference).  Every candidate is a NEW input (no match): with R = N / den the result of lcgp_variance_reduction,
+ *     dout[k, c, l] = (d_l N - R d_l h) / den
+ *     d_l h(c) = -2 D_k sum_j dc_l(c, j) sr_j V_k[c, j],   V_k = U_cand W_k      (lcgp_predict_grad's dgvar; taken as 0 where h <= 0)
+ *     d_l N(c) = 2 [ sum_t dC_l(c, t) S[c, t] - D_k sum_j dc_l(c, j) sr_j Q[c, j] ],   S[c, t] = w_t Sigma_k(t, c),  Q = (S U_ref) W_k
+ * with dc_l the first kernel derivative of lcgp_predict_grad (no nugget term).  x_ref and w_ref are constants, also where the
+ * candidates are rows of the reference set (cand_row0 >= 0).
+ * Runs behind lcgp_variance_reduction_prepare (same scratch, sized by lcgp_variance_reduction_grad_scratch_bytes), once per
+ * chunk of candidates: the launches of lcgp_variance_reduction (out: bitwise its result), then P = U_cand U_ref^T and G = S U_ref
+ * on the MFMA tile kernel, S from P in place (C recomputed in double), Q and V (the product of lcgp_predict_grad), the fused
+ * contraction of lcgp_predict_grad over the reference points (S) and over the training inputs (Q beside V), and one combining
+ * launch.  Products in the dtype; Sigma, sums and contractions in double, in a fixed order, no atomics: bitwise independent of
+ * q_local, of the scratch content and of how the candidates are split over calls.
+ * out: q_local rows of n_cand doubles, out_stride apart (0 = n_cand); dout: [q_local][out_stride][d] doubles.
+ * scratch: that of lcgp_variance_reduction plus q_local n_candpad (n_refpad + 2 npad) elements (S, G / V, Q) and 3 q_local
+ *   n_cand d doubles; n_candpad / n_refpad rounded up to 128 (n_candpad to 64 below 128).  n_cand <= 65407 per call.
+ * Flops per component beyond lcgp_variance_reduction: 4 n_candpad n_refpad npad (P, G) + 2 n_candpad npad^2 (Q, V). */
+int lcgp_variance_reduction_grad_scratch_bytes(int dtype, int n, int d, int q_local, int n_ref, int n_cand,
+                                               size_t* bytes /*host out*/);
+int lcgp_variance_reduction_grad(void* stream, int dtype, int kernel_id, int n, int d, int p, int q_local,
+                                 const void* x, const void* sr, const double* theta, const void* workspace,
+                                 int n_ref, const void* x_ref, const double* w_ref,
+                                 int n_cand, const void* x_cand, int cand_row0, int r, void* scratch,
+                                 double* out, int out_stride, double* dout);
+
 /* Greedy batch design by sequential ALC at fixed parameters (no counterpart in the reference): pick the candidate with the
  * largest score, condition the posterior covariance on r runs there (ALC does not depend on the runs' outputs), score again.
  * Per local component k, with Sigma, Sigma^h, den as in lcgp_variance_reduction and R_k = N_k / den_k its result:

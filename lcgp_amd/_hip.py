@@ -74,6 +74,9 @@ SIGNATURES = {
     "lcgp_variance_reduction_prepare": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
     "lcgp_variance_reduction": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _i,
                                      _vp, _vp, _i]),
+    "lcgp_variance_reduction_grad_scratch_bytes": (_i, [_i, _i, _i, _i, _i, _i, C.POINTER(C.c_size_t)]),
+    "lcgp_variance_reduction_grad": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _i, _i, _vp, _vp, _i,
+                                          _vp]),
     "lcgp_select_scratch_bytes": (_i, [_i, _i, _i, _i, _i, _i, _i, C.POINTER(C.c_size_t)]),
     "lcgp_select_begin": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "lcgp_select_score": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),

@@ -23,7 +23,7 @@
 #include "../../include/lcgp_hip.h"
 #include "fill_sched.h"
 
-#define LCGP_VERSION 580
+#define LCGP_VERSION 590
 
 namespace {
 
@@ -747,7 +747,8 @@ __global__ __launch_bounds__(256, 2) void leaf_kernel(T* __restrict__ M, T* __re
 //   MK : element (m, k) at P[m * ld + k]      KM : element (m, k) at P[k * ld + m]
 // and staged in LDS as [k][m] (KT = 16 k rows per stage, double buffered through registers).
 // ---------------------------------------------------------------------------------------------------
-enum GemmOp { OP_SYRK = 1, OP_TRTRI_T = 2, OP_TRTRI_W = 3, OP_LAUUM = 4, OP_PRED_U = 5, OP_PRED_COV = 6, OP_PRED_V = 7, OP_VR = 8 };
+enum GemmOp { OP_SYRK = 1, OP_TRTRI_T = 2, OP_TRTRI_W = 3, OP_LAUUM = 4, OP_PRED_U = 5, OP_PRED_COV = 6, OP_PRED_V = 7, OP_VR = 8,
+              OP_VG_P = 9, OP_VG_G = 10 };
 enum Lay { MK = 0, KM = 1 };
 
 struct GemmArgs {
@@ -1105,7 +1106,7 @@ template <typename T, int OP, int TM, int NW>
 __device__ __forceinline__ void gemm_body(const GemmArgs& g, const int lin /*block index within this descriptor*/,
                                           unsigned char* lds) {
     constexpr int LA = (OP == OP_LAUUM) ? KM : MK;
-    constexpr int LB = (OP == OP_TRTRI_T || OP == OP_TRTRI_W || OP == OP_LAUUM || OP == OP_PRED_V) ? KM : MK;
+    constexpr int LB = (OP == OP_TRTRI_T || OP == OP_TRTRI_W || OP == OP_LAUUM || OP == OP_PRED_V || OP == OP_VG_G) ? KM : MK;
     constexpr int NT = NW * 64;
     constexpr int LD = TM + 16;     // = 16 (mod 32): the two k rows a 32-lane group reads hit disjoint banks
     constexpr int WTM = TM / (NW / 2), WTN = TM / 2;   // per-wave sub-tile
@@ -1234,6 +1235,21 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& g, const int lin /*blo
         B0 = Bb + (size_t)ct * TM * g.ldB; dB = TM;
         nkt = g.p0;
         Ct = Cb;
+    } else if constexpr (OP == OP_VG_P) {
+        // P[c, t] = sum_{kt < p0} U_cand[ct, kt] U_ref[rt, kt]^T over all (candidate tile ct, reference tile rt), p1 reference
+        // tiles per candidate tile: the product OP_VR keeps in registers, stored (lcgp_variance_reduction_grad)
+        const int rt = bid % g.p1, ct = bid / g.p1;
+        A0 = Ab + (size_t)ct * TM * g.ldA; dA = TM;
+        B0 = Bb + (size_t)rt * TM * g.ldB; dB = TM;
+        nkt = g.p0;
+        Ct = Cb + (size_t)ct * TM * g.ldC + (size_t)rt * TM;
+    } else if constexpr (OP == OP_VG_G) {
+        // G[m, c] = sum_{kt < p1} S[m, kt] U_ref[kt, c]      (S = n_candpad x n_refpad, U_ref = n_refpad x npad: no triangle)
+        const int c = bid / g.p0, m = bid % g.p0;                  // p0 = row tiles of S
+        A0 = Ab + (size_t)m * TM * g.ldA; dA = TM;
+        B0 = Bb + (size_t)c * TM; dB = (ptrdiff_t)TM * g.ldB;
+        nkt = g.p1;
+        Ct = Cb + (size_t)m * TM * g.ldC + (size_t)c * TM;
     } else if constexpr (OP == OP_PRED_V) {
         // V[m, c] = sum_{kt = c}^{nb-1} U[m, kt] W[kt, c]      (U = X W^T, n0pad x npad; W lower triangular)
         // k tiles walked from nb-1 DOWN to c, as OP_LAUUM walks its B operand: every tile starts on the last block row of W,
@@ -1299,7 +1315,7 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& g, const int lin /*blo
     // only add exact zeros: it skips the stage's fragment reads and MFMAs (one wave-uniform test per stage, nothing
     // else changes; bit-identical results: the zeros are stored zeros).  LAUUM / TRTRI_W: 24 of the 64 (wave, stage)
     // pairs of such a tile, TRTRI_T / PRED_U / PRED_V: 16.
-    constexpr bool HAS_TRI = OP != OP_SYRK && OP != OP_PRED_COV && OP != OP_VR;
+    constexpr bool HAS_TRI = OP != OP_SYRK && OP != OP_PRED_COV && OP != OP_VR && OP != OP_VG_P && OP != OP_VG_G;
     const int tri_first = HAS_TRI ? (nkt - 1) * SPT : nst;
     // the wave is idle in the stages [dead_lo, dead_hi) of the k loop (two scalars per wave)
     int dead_lo = nst, dead_hi = nst;
@@ -2652,7 +2668,8 @@ __global__ __launch_bounds__(64) void pred_reduce_kernel(const T* __restrict__ X
 // DD < 32: d <= DD, the row of x0 held in registers.  DD = 32 serves every d in (16, 126]: c0 over all d from LDS, the
 // derivative for the 32 dimensions of chunk blockIdx.z (2 DD accumulators per lane, never 2 d).
 constexpr int PG_ROWS = 32, PG_SL = 8;
-template <typename T, int DD, int KERN>
+// ZMAT (lcgp_variance_reduction_grad): z is a matrix laid out as V is (row i0 + i of slab k, row length npad), not the vector z_k.
+template <typename T, int DD, int KERN, bool ZMAT = false>
 __global__ __launch_bounds__(256) void pgrad_kernel(const T* __restrict__ x0, int n0, const T* __restrict__ x,
                                                     const T* __restrict__ sr, int n, int d, const double* __restrict__ theta,
                                                     int tw, const T* __restrict__ z, int npad, const T* __restrict__ V,
@@ -2664,6 +2681,7 @@ __global__ __launch_bounds__(256) void pgrad_kernel(const T* __restrict__ x0, in
     __shared__ double x0sh[PG_ROWS][XW];
     __shared__ double xsh[JT][XW];
     __shared__ double vsh[PG_ROWS][JT + 1];
+    __shared__ double zsh[ZMAT ? PG_ROWS : 1][JT + 1];
     __shared__ double wz[JT], wsr[JT];
     __shared__ double th[DWIDE + 3];
     __shared__ double red[2][4][PG_ROWS];
@@ -2677,7 +2695,7 @@ __global__ __launch_bounds__(256) void pgrad_kernel(const T* __restrict__ x0, in
         const int i = e / XW, m = e - i * XW;
         x0sh[i][m] = (i0 + i < n0 && m < d) ? (double)x0[(size_t)(i0 + i) * d + m] / th[m] : 0.0;
     }
-    const T* zk = z + (size_t)k * npad;
+    const T* zk = z + (size_t)k * (ZMAT ? slab : (size_t)npad);
     const T* Vk = V + (size_t)k * slab;
     double am[DD], av[DD];
 #pragma unroll
@@ -2697,12 +2715,14 @@ __global__ __launch_bounds__(256) void pgrad_kernel(const T* __restrict__ x0, in
         for (int e = tid; e < PG_ROWS * JT; e += 256) {
             const int i = e / JT, jj = e - i * JT;
             vsh[i][jj] = (i0 + i < n0 && j0 + jj < n) ? (double)Vk[(size_t)(i0 + i) * npad + j0 + jj] : 0.0;
+            if constexpr (ZMAT) zsh[i][jj] = (i0 + i < n0 && j0 + jj < n) ? (double)zk[(size_t)(i0 + i) * npad + j0 + jj] : 0.0;
         }
         if (tid < JT) {
             const int j = j0 + tid;
             const double s = j < n ? (sr ? (double)sr[j] : 1.0) : 0.0;      // (inputs beyond n weigh zero)
             wsr[tid] = s;
-            wz[tid] = j < n ? s * (double)zk[j] : 0.0;
+            if constexpr (ZMAT) wz[tid] = s;
+            else wz[tid] = j < n ? s * (double)zk[j] : 0.0;
         }
         __syncthreads();
         for (int jj = sl; jj < JT; jj += PG_SL) {
@@ -2728,7 +2748,7 @@ __global__ __launch_bounds__(256) void pgrad_kernel(const T* __restrict__ x0, in
                 for (int m = 0; m < DD; ++m) acc_c0(xi[m] - xsh[jj][m]);
             }
             const double c0 = c_off * kern_c0<KERN>(poly, ssum);
-            const double a = c0 * wz[jj], b = c0 * wsr[jj] * vsh[r][jj];
+            const double a = ZMAT ? c0 * wz[jj] * zsh[r][jj] : c0 * wz[jj], b = c0 * wsr[jj] * vsh[r][jj];
 #pragma unroll
             for (int l = 0; l < DD; ++l) {
                 const double s = WIDE ? x0sh[r][l0 + l] - xsh[jj][l0 + l] : xi[l] - xsh[jj][l];
@@ -3262,11 +3282,11 @@ inline int predict_pad(int n0) { return n0 >= 128 ? round_up(n0, 2 * TS) : round
 // apart, B_k ld x ld matrices sB apart, ld = nb 64-tiles.  128x128 tiles when rows is a multiple of 128, 64x64 tiles otherwise.
 template <typename T, int OP>
 int launch_pred(hipStream_t st, const T* A, const T* B, T* C, size_t sA, size_t sB, int ld, int rows, int nb, int q,
-                size_t sC = 0 /*0 = sA*/) {
+                size_t sC = 0 /*0 = sA*/, bool small = false /*64x64 tiles whatever rows is*/) {
     GemmArgs g;
     g.A = A; g.B = B; g.C = C;
     g.sA = sA; g.sB = sB; g.sC = sC ? sC : sA; g.ldA = g.ldB = g.ldC = ld; g.p1 = g.p2 = g.p3 = 0;
-    if (rows % (2 * TS) == 0) {
+    if (rows % (2 * TS) == 0 && !small) {
         g.nb = nb / 2; g.p0 = rows / (2 * TS);
         return launch_gemm<T, OP, 128>(st, g, g.p0 * g.nb, q);
     }
@@ -3728,6 +3748,184 @@ int do_vr(hipStream_t st, const Ws& w, const void* x, const void* sr, const doub
 int check_vr(int n_ref, int n_cand) {
     if (n_ref < 1) return bad("n_ref must be >= 1");
     if (n_cand < 1) return bad("n_cand must be >= 1");
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------
+// Gradient of the integrated variance reduction with respect to the candidate (lcgp_hip.h: lcgp_variance_reduction_grad; no
+// counterpart in the reference).  With R = N / den as above, every candidate a new input, S[c, t] = w_t sigma(t, c):
+//     d_l R(c) = (d_l N - R d_l h) / den          d_l h = -2 D sum_j dc_l(c, j) sr_j V[c, j]   (pgrad_kernel's dgvar; 0 where h <= 0)
+//     d_l N(c) = 2 [ sum_t dC_l(c, t) S[c, t]  -  D sum_j dc_l(c, j) sr_j Q[c, j] ],      Q = (S U_ref) W,   V = U_cand W
+// R comes from do_vr itself (bitwise lcgp_variance_reduction).  Then P = U_cand U_ref^T (OP_VG_P, the product OP_VR keeps in
+// registers), S from P in place (vrg_sigma_kernel: C recomputed in double as the OP_VR epilogue forms it), the first sum by the
+// fused contraction over the REFERENCE points (pgrad_kernel<ZMAT> with z = S), G = S U_ref (OP_VG_G), Q and V (OP_PRED_V), the
+// other two sums by ONE contraction over the training inputs (pgrad_kernel<ZMAT> with z = Q beside V), and vrg_combine_kernel.
+// Every row of every product depends on its candidate only, every sum has a fixed order: bitwise independent of q_local, of
+// the scratch content and of how the candidates are split over calls.
+// ---------------------------------------------------------------------------------------------------
+struct VrgLay {
+    int crows, lds;                 // rows of the candidate slabs; row length of S (n_ref rounded up to 128)
+    size_t sslab, gslab;
+    size_t off_s, off_g, off_q, off_t, off_a, off_h, total;       // relative to the end of the variance reduction's own scratch
+};
+
+inline VrgLay vrg_carve(int dtype, int n, int d, int q, int n_ref, int n_cand) {
+    VrgLay G;
+    const size_t esz = dtype == LCGP_F64 ? 8 : 4, npad = round_up(n, 2 * TS);
+    G.crows = predict_pad(n_cand);
+    G.lds = round_up(n_ref, 2 * TS);
+    G.sslab = (size_t)G.crows * G.lds;
+    G.gslab = (size_t)G.crows * npad;
+    size_t o = 0;
+    G.off_s = o; o = align256(o + (size_t)q * G.sslab * esz);
+    G.off_g = o; o = align256(o + (size_t)q * G.gslab * esz);
+    G.off_q = o; o = align256(o + (size_t)q * G.gslab * esz);
+    G.off_t = o; o = align256(o + (size_t)q * n_cand * d * sizeof(double));
+    G.off_a = o; o = align256(o + (size_t)q * n_cand * d * sizeof(double));
+    G.off_h = o; o = align256(o + (size_t)q * n_cand * d * sizeof(double));
+    G.total = o;
+    return G;
+}
+
+// S[k, c, t] = w_t (C_k(c, t) - D_k P[k, c, t]) in place over P (row length lds), zero beyond n_cand rows / n_ref columns (the
+// k padding of S U_ref).  C_k in double from the standardised inputs divided by ell, the arithmetic of the OP_VR epilogue.
+template <typename T, int KERN>
+__global__ __launch_bounds__(256) void vrg_sigma_kernel(T* __restrict__ S, size_t sslab, int lds, int n_cand, int n_ref, int d,
+                                                        const T* __restrict__ xc, const T* __restrict__ xr,
+                                                        const double* __restrict__ wref, const double* __restrict__ theta, int tw) {
+    const int t = blockIdx.x * 256 + threadIdx.x, c = blockIdx.y, k = blockIdx.z;
+    if (t >= lds) return;
+    T* p = S + (size_t)k * sslab + (size_t)c * lds + t;
+    if (c >= n_cand || t >= n_ref) { *p = (T)0; return; }
+    const double* th = theta + (size_t)k * tw;
+    const double scale = th[d], nug = th[d + 1], D = th[d + 2];
+    const double coff = scale * (1.0 - nug / (1.0 + nug));
+    double poly = 1.0, ssum = 0.0;
+    for (int l = 0; l < d; ++l) {
+        const double xv = (double)xr[(size_t)t * d + l] / th[l], yv = (double)xc[(size_t)c * d + l] / th[l];
+        if constexpr (KERN == 0) {
+            const double sd = fabs(xv - yv);
+            poly = fma(poly, sd, poly);
+            ssum -= sd;
+        } else if constexpr (KERN == 1) {
+            const double df = xv - yv;
+            ssum = fma(-0.5 * df, df, ssum);
+        } else {
+            static_assert(KERN == 2, "unknown covariance kernel id");
+            const double sd = fabs(xv - yv);
+            poly = fma(poly, m52_fm1(sd), poly);
+            ssum -= sd;
+        }
+    }
+    const double sg = fma(-D, (double)*p, coff * kern_c0<KERN>(poly, ssum));
+    *p = (T)(wref[t] * sg);
+}
+
+// dR[k, c, l] = (2 (t1 - D_k a1) - R_k(c) dh) / den_c; dh counts only where the candidate's gvar is positive
+__global__ __launch_bounds__(256) void vrg_combine_kernel(const double* __restrict__ R, int ldo, const double* __restrict__ gvc, int ldg,
+                                                          const double* __restrict__ theta, int tw, int d, int nrep, int n_cand,
+                                                          const double* __restrict__ t1, const double* __restrict__ a1,
+                                                          const double* __restrict__ dh, double* __restrict__ dR) {
+    const int e = blockIdx.x * 256 + threadIdx.x, k = blockIdx.y;
+    if (e >= n_cand * d) return;
+    const int c = e / d;
+    const double D = theta[(size_t)k * tw + d + 2];
+    const double h = gvc[(size_t)k * ldg + c];
+    const double den = fmax(h, 0.0) + 1.0 / (D * (double)nrep);
+    const size_t io = (size_t)k * ldo * d + e, is = (size_t)k * n_cand * d + e;
+    const double dhv = h > 0.0 ? dh[is] : 0.0;
+    dR[io] = (2.0 * fma(-D, a1[is], t1[is]) - R[(size_t)k * ldo + c] * dhv) / den;
+}
+
+// the fused contraction with a matrix in the place of z (outputs n0 rows apart per component)
+template <typename T>
+int launch_pgrad_mat(hipStream_t st, const Ws& w, const void* x0, int n0, const void* x, const void* sr, int n,
+                     const double* theta, const T* Z, const T* V, int ld, size_t slab, double* dz, double* dv) {
+    const int wide = w.d > 16;
+    dim3 grid((n0 + PG_ROWS - 1) / PG_ROWS, w.q, wide ? (w.d + DMAX - 1) / DMAX : 1);
+    for_dim(w.d, [&](auto dd) {
+        for_kern(w.kern, [&](auto kern) {
+            hipLaunchKernelGGL((pgrad_kernel<T, decltype(dd)::value, decltype(kern)::value, true>), grid, dim3(256), 0, st,
+                               (const T*)x0, n0, (const T*)x, (const T*)sr, n, w.d, theta, w.d + 3 + w.p, Z, ld, V, slab, n0, dz, dv);
+        });
+    });
+    CHECK_LAUNCH("pgrad_kernel");
+    return 0;
+}
+
+template <typename T>
+int do_vr_grad(hipStream_t st, const Ws& w, const void* x, const void* sr, const double* theta, int n_ref, const void* x_ref,
+               const double* w_ref, int n_cand, const void* x_cand, int row0, int r, char* scratch, double* out, int ldo,
+               double* dout) {
+    const int dt = w.esz == 8 ? LCGP_F64 : LCGP_F32;
+    const VrLay L = vr_carve(dt, w.n, w.q, n_ref, n_cand);
+    const VrgLay G = vrg_carve(dt, w.n, w.d, w.q, n_ref, n_cand);
+    int rc = do_vr<T>(st, w, x, sr, theta, n_ref, x_ref, w_ref, n_cand, x_cand, nullptr, row0, r, scratch, out, ldo);
+    if (rc) return rc;
+    // U, gvar and inputs of the candidates, where do_vr left or found them
+    T* Ur = (T*)(scratch + L.off_uref);
+    const T* Uc;
+    const double* gvc;
+    const void* xc;
+    size_t sUc;
+    int ldg, rows;
+    if (row0 >= 0) {
+        // rows of the reference set: whole 64-tiles only, which stay inside its slab (vr_carve)
+        Uc = Ur + (size_t)row0 * w.npad; sUc = L.uslab_r; rows = round_up(n_cand, TS);
+        gvc = (const double*)(scratch + L.off_gvr) + row0; ldg = n_ref;
+        xc = (const T*)x_ref + (size_t)row0 * w.d;
+    } else {
+        Uc = (const T*)(scratch + L.off_uc); sUc = L.uslab_c; rows = G.crows;
+        gvc = (const double*)(scratch + L.off_gvc); ldg = n_cand; xc = x_cand;
+    }
+    char* ex = scratch + L.total;
+    T* S = (T*)(ex + G.off_s);
+    T* Gb = (T*)(ex + G.off_g);
+    T* Qb = (T*)(ex + G.off_q);
+    double* t1 = (double*)(ex + G.off_t);
+    double* a1 = (double*)(ex + G.off_a);
+    double* dh = (double*)(ex + G.off_h);
+    // the rows of U_ref between the set and the k padding of S U_ref: zeros (those up to the padding of the passes that formed
+    // the set are zeros already; the rest has never been written)
+    if (G.lds > n_ref) {
+        hipError_t e = hipMemset2DAsync(Ur + (size_t)n_ref * w.npad, L.uslab_r * w.esz, 0,
+                                        (size_t)(G.lds - n_ref) * w.npad * w.esz, w.q, st);
+        if (e != hipSuccess) return fail("hipMemset2DAsync", e);
+    }
+    GemmArgs h;
+    h.A = Uc; h.B = Ur; h.C = S;
+    h.sA = sUc; h.sB = L.uslab_r; h.sC = G.sslab;
+    h.ldA = h.ldB = w.npad; h.ldC = G.lds;
+    h.nb = 0; h.p0 = w.npad / TS; h.p1 = G.lds / TS; h.p2 = h.p3 = 0;
+    rc = launch_gemm<T, OP_VG_P, 64>(st, h, (rows / TS) * h.p1, w.q);
+    if (rc) return rc;
+    for_kern(w.kern, [&](auto kern) {
+        hipLaunchKernelGGL((vrg_sigma_kernel<T, decltype(kern)::value>), dim3((G.lds + 255) / 256, rows, w.q), dim3(256), 0, st, S,
+                           G.sslab, G.lds, n_cand, n_ref, w.d, (const T*)xc, (const T*)x_ref, w_ref, theta, w.d + 3 + w.p);
+    });
+    CHECK_LAUNCH("vrg_sigma_kernel");
+    // t1[c, l] = sum_t dC_l(c, t) S[c, t]   (a1 receives the same sum scaled: overwritten below)
+    rc = launch_pgrad_mat<T>(st, w, xc, n_cand, x_ref, nullptr, n_ref, theta, S, S, G.lds, G.sslab, t1, a1);
+    if (rc) return rc;
+    GemmArgs g;
+    g.A = S; g.B = Ur; g.C = Gb;
+    g.sA = G.sslab; g.sB = L.uslab_r; g.sC = G.gslab;
+    g.ldA = G.lds; g.ldB = g.ldC = w.npad; g.p2 = g.p3 = 0;
+    // 64x64 tiles for G, Q and V whatever the number of candidates: OP_PRED_V sums in a different order on 128-row tiles
+    // (DESIGN 4.2), and a call's candidates may be any rows of a larger set
+    g.nb = w.nb; g.p0 = rows / TS; g.p1 = G.lds / TS;
+    rc = launch_gemm<T, OP_VG_G, 64>(st, g, g.p0 * g.nb, w.q);
+    if (rc) return rc;
+    const T* W = (const T*)(w.base + w.off_W);
+    rc = launch_pred<T, OP_PRED_V>(st, Gb, W, Qb, G.gslab, w.mat, w.npad, rows, w.nb, w.q, 0, true);
+    if (rc) return rc;
+    rc = launch_pred<T, OP_PRED_V>(st, Uc, W, Gb, sUc, w.mat, w.npad, rows, w.nb, w.q, G.gslab, true);     // (G is free: V = U_cand W)
+    if (rc) return rc;
+    rc = launch_pgrad_mat<T>(st, w, xc, n_cand, x, sr, w.n, theta, Qb, Gb, w.npad, G.gslab, a1, dh);
+    if (rc) return rc;
+    hipLaunchKernelGGL(vrg_combine_kernel, dim3((n_cand * w.d + 255) / 256, w.q), dim3(256), 0, st, (const double*)out, ldo, gvc, ldg,
+                       theta, w.d + 3 + w.p, w.d, r, n_cand, (const double*)t1, (const double*)a1, (const double*)dh, dout);
+    CHECK_LAUNCH("vrg_combine_kernel");
     return 0;
 }
 
@@ -4955,6 +5153,50 @@ int lcgp_variance_reduction(void* stream, int dtype, int kernel_id, int n, int d
                                              (char*)scratch, out, ldo)
                              : do_vr<float>(st, w, x, sr, theta, n_ref, x_ref, w_ref, n_cand, x_cand, match, cand_row0, r,
                                             (char*)scratch, out, ldo);
+}
+
+// the candidates of one call are rows of a launch grid
+static int check_vr_grad(int n_cand) {
+    if (n_cand > 65535 - 2 * TS) return bad("n_cand must be <= 65407 per call (pass the candidates in chunks)");
+    return 0;
+}
+
+int lcgp_variance_reduction_grad_scratch_bytes(int dtype, int n, int d, int q_local, int n_ref, int n_cand, size_t* bytes) {
+    int rc = check_common(dtype, n, d, 1, q_local);
+    if (rc) return rc;
+    if ((rc = check_vr(n_ref, n_cand))) return rc;
+    if ((rc = check_vr_grad(n_cand))) return rc;
+    if (!bytes) return bad("bytes is NULL");
+    *bytes = vr_carve(dtype, n, q_local, n_ref, n_cand).total + vrg_carve(dtype, n, d, q_local, n_ref, n_cand).total;
+    return 0;
+}
+
+int lcgp_variance_reduction_grad(void* stream, int dtype, int kernel_id, int n, int d, int p, int q_local, const void* x,
+                                 const void* sr, const double* theta, const void* workspace, int n_ref, const void* x_ref,
+                                 const double* w_ref, int n_cand, const void* x_cand, int cand_row0, int r, void* scratch,
+                                 double* out, int out_stride, double* dout) {
+    int rc = check_common(dtype, n, d, p, q_local, kernel_id);
+    if (rc) return rc;
+    if ((rc = check_vr(n_ref, n_cand))) return rc;
+    if ((rc = check_vr_grad(n_cand))) return rc;
+    if (r < 1) return bad("r must be >= 1");
+    if (cand_row0 < -1) return bad("cand_row0 must be -1 or a row of the reference set");
+    if (cand_row0 >= 0) {
+        if ((long long)cand_row0 + n_cand > n_ref) return bad("cand_row0 + n_cand must be <= n_ref");
+        if (x_cand) return bad("cand_row0 >= 0: x_cand must be NULL");
+    } else if (!x_cand) {
+        return bad("NULL pointer");
+    }
+    if (!x || !theta || !workspace || !x_ref || !w_ref || !scratch || !out || !dout) return bad("NULL pointer");
+    if (out_stride != 0 && out_stride < n_cand) return bad("out_stride must be 0 (= n_cand) or >= n_cand");
+    const int ldo = out_stride ? out_stride : n_cand;
+    Ws w = carve(dtype, n, d, p, q_local, (void*)workspace);
+    w.kern = kernel_id;
+    hipStream_t st = (hipStream_t)stream;
+    return dtype == LCGP_F64 ? do_vr_grad<double>(st, w, x, sr, theta, n_ref, x_ref, w_ref, n_cand, x_cand, cand_row0, r,
+                                                  (char*)scratch, out, ldo, dout)
+                             : do_vr_grad<float>(st, w, x, sr, theta, n_ref, x_ref, w_ref, n_cand, x_cand, cand_row0, r,
+                                                 (char*)scratch, out, ldo, dout);
 }
 
 int lcgp_select_scratch_bytes(int dtype, int n, int d, int q_local, int n_ref, int n_cand, int size, size_t* bytes) {

@@ -564,6 +564,47 @@ class HotPathEngine:
                                                             n_cand), "lcgp_variance_reduction")
             return out
 
+    def variance_reduction_grad_block(self, x_cand_s, x_ref_s, w, r):
+        """R (q_local, n_cand) and dR (q_local, n_cand, d) float64 DEVICE tensors: variance_reduction_block's R_k(c) with every
+        candidate a new input (no match) and its gradient with respect to the candidate's standardised location, x_ref_s and
+        w held constant (also with x_ref_s = None, where the reference set is a copy of the candidates)
+        (lcgp_variance_reduction_prepare once, lcgp_variance_reduction_grad per chunk of PREDICT_CHUNK candidates).  Raises
+        ValueError when the scratch does not fit in the free device memory."""
+        torch = self.torch
+        if self._theta_last is None:
+            raise RuntimeError("variance_reduction_grad() needs a preceding evaluate() at the current parameters")
+        x_cand_s = np.ascontiguousarray(x_cand_s, np.float64)
+        n_cand, d = x_cand_s.shape[0], self.d
+        assert x_cand_s.ndim == 2 and x_cand_s.shape[1] == d and n_cand >= 1
+        shared = x_ref_s is None
+        x_ref_s = x_cand_s if shared else np.ascontiguousarray(x_ref_s, np.float64)
+        n_ref = x_ref_s.shape[0]
+        assert x_ref_s.ndim == 2 and x_ref_s.shape[1] == d and n_ref >= 1 and len(w) == n_ref
+        chunk = min(n_cand, PREDICT_CHUNK)
+        with torch.cuda.device(self.device):
+            nbytes = self._nbytes("lcgp_variance_reduction_grad_scratch_bytes", self.dtype, self.n, d, self.q_local, n_ref, chunk)
+            scratch = self._grow_scratch(nbytes, ("the variance reduction gradient over %d reference points" % n_ref,
+                                                  "%d components of n_ref x n and %d candidates x (n_ref + 3 n)" % (self.q_local, chunk),
+                                                  "pass fewer reference points"))
+            xr = torch.as_tensor(x_ref_s).to(self.device, self.tdtype).contiguous()
+            xc = None if shared else torch.as_tensor(x_cand_s).to(self.device, self.tdtype).contiguous()
+            wd = torch.as_tensor(np.ascontiguousarray(w, np.float64)).to(self.device)
+            out = torch.empty((self.q_local, n_cand), dtype=torch.float64, device=self.device)
+            dout = torch.empty((self.q_local, n_cand, d), dtype=torch.float64, device=self.device)
+            st, xp, srp, thp, wsp, scp = (self._stream(), self._p(self.x), self._p(self.sr), self._p(self.theta_dev),
+                                          self._p(self.workspace), self._p(scratch))
+            _hip.check(self.lib.lcgp_variance_reduction_prepare(st, self.dtype, self.kernel_id, self.n, d, self.p, self.q_local, xp, srp,
+                                                                thp, wsp, n_ref, self._p(xr), scp), "lcgp_variance_reduction_prepare")
+            for lo in range(0, n_cand, chunk):
+                m = min(chunk, n_cand - lo)
+                xcp = C.c_void_p(0) if shared else C.c_void_p(xc.data_ptr() + lo * d * xc.element_size())
+                _hip.check(self.lib.lcgp_variance_reduction_grad(st, self.dtype, self.kernel_id, self.n, d, self.p, self.q_local, xp,
+                                                                 srp, thp, wsp, n_ref, self._p(xr), self._p(wd), m, xcp,
+                                                                 lo if shared else -1, int(r), scp,
+                                                                 C.c_void_p(out.data_ptr() + 8 * lo), n_cand,
+                                                                 C.c_void_p(dout.data_ptr() + 8 * lo * d)), "lcgp_variance_reduction_grad")
+            return out, dout
+
     # ------------------------------------------------------------------------------------------------
     # greedy batch design by sequential ALC (lcgp_hip.h: lcgp_select_begin / lcgp_select_score / lcgp_select_condition)
     def select_begin(self, x_cand_s, x_ref_s, w, match, r, size):

@@ -145,6 +145,27 @@ class _PredictVjpFn(torch.autograd.Function):
         return (gx0, *gouts, None, None, None)
 
 
+class _VrFn(torch.autograd.Function):
+    """LCGP.variance_reduction_differentiable: forward = variance_reduction_grad()'s gain, backward = the per-candidate
+    vector-Jacobian product with the saved gradient"""
+
+    @staticmethod
+    def forward(ctx, x_cand, model, kwargs):
+        gain, dgain = model.variance_reduction_grad(x_cand.detach().cpu().to(torch.float64), **kwargs)
+        ctx.meta = (x_cand.dtype, x_cand.device, x_cand.shape)
+        ctx.dgain = dgain
+        return gain.to(x_cand.device)
+
+    @staticmethod
+    def backward(ctx, g):
+        if torch.is_grad_enabled():         # create_graph=True: the saved gradient is a constant, not a graph
+            raise RuntimeError('LCGP.variance_reduction_differentiable supports first derivatives only: double backward '
+                               '(create_graph=True) is not available; use variance_reduction_grad() for the gradient')
+        dt, dev, shape = ctx.meta
+        gx = torch.einsum('ac,acl->cl', _cpu64(g), ctx.dgain)
+        return gx.reshape(shape).to(device=dev, dtype=dt), None, None
+
+
 class LCGP:
     """
     Latent Component Gaussian Process (LCGP), MI355X hot path.
@@ -1200,6 +1221,53 @@ class LCGP:
         W, _, scale, _ = self._output_map()
         delta = (W[:, outputs] ** 2).T @ R * (scale[outputs] ** 2)[:, None]
         return _t(delta)
+
+    def variance_reduction_grad(self, x_cand, x_ref=None, weights=None, outputs=None, replicates=1, latent=False):
+        """variance_reduction() and its gradient with respect to the candidates' locations (the analytic derivative a continuous
+        ALC / IMSPE search needs; laGP's alcopt): returns (gain, dgain), CPU float64,
+            gain[a, c]     = Delta_a(c)  (latent=True: R_k(c)),   shape (len(outputs) | q, n_cand)
+            dgain[a, c, l] = d gain[a, c] / d x_cand[c, l]        on the RAW input scale, shape (len(outputs) | q, n_cand, d)
+        Arguments, checks and the full / rep rules for `replicates` exactly as in variance_reduction().  x_ref and weights are
+        CONSTANTS: the gradient is with respect to the candidate's location only, also when x_ref=None makes the reference set a
+        copy of the candidates.
+        Every candidate is a NEW input: on the rep path a candidate bitwise equal to a unique training input gets the value and
+        gradient of the continuous surface (a new unique input at that location), NOT variance_reduction()'s
+        add-replicates-to-that-input value -- the rule of predict_grad() / predict_differentiable(); the point mass of the nugget
+        has no derivative.  Away from such candidates gain is bitwise variance_reduction()'s.  All three kernels have a continuous
+        first derivative everywhere, so there is no kink convention.
+        Computed on the GPU from the factorisation of the current parameters (lcgp_variance_reduction_grad), in the engine's
+        dtype (float32 models: float32 products; Sigma, sums and contractions in double).  GPU memory: variance_reduction()'s plus
+        q_local min(n_cand, 2048) (n_ref + 2 npad) elements -- ValueError when it does not fit.  self.ghat / self.gvar are left
+        untouched."""
+        xc_s, xr_s, w, outputs, r, _ = self._vr_arguments(x_cand, x_ref, weights, outputs, replicates)
+        n_cand, d = xc_s.shape
+        eng = self._ensure_aux()
+
+        def local():
+            if eng is None:
+                return None
+            R, dR = eng.variance_reduction_grad_block(xc_s, xr_s, w, r)
+            return torch.cat([R, dR.reshape(dR.shape[0], -1)], dim=1)
+        both = self._gather_components(self._agree(local), (n_cand + n_cand * d,))
+        rng = (_np(self.x_max) - _np(self.x_min)).reshape(-1)
+        R = both[:, :n_cand]
+        dR = both[:, n_cand:].reshape(-1, n_cand, d) / rng[None, None, :]
+        if latent:
+            return _t(R.copy()), _t(dR)
+        W, _, scale, _ = self._output_map()
+        delta = (W[:, outputs] ** 2).T @ R * (scale[outputs] ** 2)[:, None]
+        ddelta = np.einsum('ka,kcl->acl', W[:, outputs] ** 2, dR) * (scale[outputs] ** 2)[:, None, None]
+        return _t(delta), _t(ddelta)
+
+    def variance_reduction_differentiable(self, x_cand, x_ref=None, weights=None, outputs=None, replicates=1, latent=False):
+        """variance_reduction_grad()'s gain as a tensor on x_cand's device, differentiable with respect to a requires_grad x_cand
+        through torch.autograd (the backward pass is the vector-Jacobian product with the gradient the forward pass saved: no
+        second GPU pass), so any torch or SciPy optimiser can search a box for the best next run.  x_ref and weights are
+        constants (no gradient flows to them, nor through the reference copy of the candidates made by x_ref=None).  First
+        derivatives only: a double backward (create_graph=True) raises."""
+        x_cand = x_cand if isinstance(x_cand, torch.Tensor) else torch.as_tensor(np.asarray(x_cand, F64))
+        kwargs = dict(x_ref=x_ref, weights=weights, outputs=outputs, replicates=replicates, latent=latent)
+        return _VrFn.apply(x_cand, self, kwargs)
 
     def select_batch(self, x_cand, size, x_ref=None, weights=None, outputs=None, replicates=1, return_scores=False):
         """Greedy batch design by sequential ALC: `size` of the candidates, chosen one after the other -- the candidate with the

@@ -186,6 +186,42 @@ int lcgp_nll_grad(void* stream, int dtype, int kernel_id, int n, int d, int p, i
                   const double* theta, void* workspace, double* out, const lcgp_sched* sched,
                   const void* plan /*host, or NULL*/);
 
+/* Exact Hessian of the objective in the parameters (the reference would nest two gradient tapes around neglpost, lcgp.py:635-666
+ * / 554-630; this entry replaces them).  float64 only: LCGP_F32 is refused with an error text (the kernel block is the
+ * difference of two traces that cancel heavily, and the call is made once per fit).
+ * Runs behind lcgp_nll_grad at the same theta and only READS its workspace (A_k^-1 lower tiles, b_k, z_k): lcgp_predict and the
+ * other post-fit entries stay valid after it.  Per local component k, with A = I + D (C o s s^T), C = scale ((1 - w) C0 + w I),
+ * w = nug / (1 + nug), z = A^-1 b, b = sum_a psi_a Y_a, c_a = psi_a Y_a, the component's share of the objective is
+ * f_k = 1/2 log det A - b^T (b - z) / (2 D), and for the m = d + 2 kernel parameters theta_i in [ell_0 .. ell_{d-1}, scale, nug],
+ * G_i = A^-1 d_iA, y_i = d_iA z, and the built noise parameters t_a (psi_a = phi_ak / sig_a, sig_a = exp(t_a / 2) / std_a):
+ *     hk[i, j] = 1/2 sum (A^-1 o d_ijA) - 1/2 tr(G_i G_j) - z^T d_ijA z / (2 D) + y_i^T A^-1 y_j / D          (m x m, symmetric)
+ *     hx[i, a] = c_a^T A^-1 y_i / (2 D)                                                                       (m x p)
+ *     hn[a, b] = -[ delta_ab c_a^T (b - z) + c_a^T (I - A^-1) c_b ] / (4 D)                                   (p x p)
+ *   kernel derivatives in ell with S_i = |dx_i| / ell_i: d_i C0 = C0 phi_i, d_ij C0 = C0 (phi_i phi_j + delta_ij d phi_i / d ell_i),
+ *       Matern-3/2: phi = S^2 / ((1 + S) ell)      SE: phi = S^2 / ell      Matern-5/2: phi = S^2 (1 + S) / (ell (3 + 3 S + S^2))
+ *   d_scale A and d_nug A are combinations of A, I and diag(s^2): G_scale, G_nug, y_scale, y_nug need no matrix product.
+ * Output: row k of `out` (q_local rows of lcgp_nll_hess_width(d, p) = m^2 + m p + p^2 doubles) = [ hk | hx | hn ], row-major
+ * blocks.  The caller sums hn over the components, adds the term of the objective outside the components
+ * (delta_ab ysq_a / (2 sig_a^2)), folds both noise blocks through the error-structure groups and applies the 1 / n of the
+ * replicated path.  Kernel blocks of different components are exactly zero and are not written.
+ * The call handles the components k0 .. k0 + q_group - 1 of the workspace (carved for q_local) and writes their rows of
+ * `out`: a caller bounds the scratch by processing the local components in groups.  Launches: A^-1 mirrored to a full matrix
+ * with G_scale / G_nug beside it; per dimension i one launch that materialises d_iA (one buffer, reused: the tile kernel then
+ * stages plain dense operands, and the same buffer gives y_i = d_iA z), and G_i = A^-1 d_iA on the fp64 MFMA tile kernel
+ * (operand mode OP_HESS_G, 128 x 128 tiles); the pairwise traces tr(G_i G_j) by a tile-transposing reduction; a second-order
+ * fused contraction that recomputes C0, phi_i and d phi_i / d ell_i in registers (no n x n x d x d tensor is written);
+ * u_i = A^-1 y_i; Q = Y A^-1 on the tile kernel; the dot products of the three blocks.
+ * scratch: lcgp_nll_hess_scratch_bytes(dtype, n, d, p, q_group) bytes = q_group (d + 4) npad^2 doubles (A^-1, d_iA, the d + 2
+ *   G_i) plus q_group (3 d + 4 + ppad) npad and ppad npad doubles of vectors, Q and the padded Y (ppad = p rounded up to 128) and
+ *   the per-band partial sums; its content on entry is irrelevant.
+ * Flops per component: 2 d npad^3 (the products G_i) + 2 ppad npad^2 (Q) + (d + 2)(d + 3) npad^2 (the traces); every sum has a
+ * fixed order, no atomics: bitwise reproducible, independent of q_local, of q_group and of the scratch content on entry. */
+int lcgp_nll_hess_width(int d, int p);
+int lcgp_nll_hess_scratch_bytes(int dtype, int n, int d, int p, int q_group, size_t* bytes /*host out*/);
+int lcgp_nll_hess(void* stream, int dtype, int kernel_id, int n, int d, int p, int q_local,
+                  const void* x, const void* Y, const void* sr, const double* theta, const void* workspace,
+                  int k0, int q_group, void* scratch, double* out /*q_local rows of lcgp_nll_hess_width(d, p)*/);
+
 /* The launch plan of the factorisation, computed ONCE by the caller instead of in every evaluation (it depends on
  * dtype, n, q_local, the schedule and on whether the inverse follows -- with_inverse = 1 for lcgp_nll_grad, 0 for
  * lcgp_potrf_logdet -- and on nothing else).  The plan is a position-independent block of `bytes` bytes in HOST memory

@@ -23,7 +23,7 @@
 #include "../../include/lcgp_hip.h"
 #include "fill_sched.h"
 
-#define LCGP_VERSION 590
+#define LCGP_VERSION 600
 
 namespace {
 
@@ -748,7 +748,7 @@ __global__ __launch_bounds__(256, 2) void leaf_kernel(T* __restrict__ M, T* __re
 // and staged in LDS as [k][m] (KT = 16 k rows per stage, double buffered through registers).
 // ---------------------------------------------------------------------------------------------------
 enum GemmOp { OP_SYRK = 1, OP_TRTRI_T = 2, OP_TRTRI_W = 3, OP_LAUUM = 4, OP_PRED_U = 5, OP_PRED_COV = 6, OP_PRED_V = 7, OP_VR = 8,
-              OP_VG_P = 9, OP_VG_G = 10 };
+              OP_VG_P = 9, OP_VG_G = 10, OP_HESS_G = 11 };
 enum Lay { MK = 0, KM = 1 };
 
 struct GemmArgs {
@@ -1106,7 +1106,7 @@ template <typename T, int OP, int TM, int NW>
 __device__ __forceinline__ void gemm_body(const GemmArgs& g, const int lin /*block index within this descriptor*/,
                                           unsigned char* lds) {
     constexpr int LA = (OP == OP_LAUUM) ? KM : MK;
-    constexpr int LB = (OP == OP_TRTRI_T || OP == OP_TRTRI_W || OP == OP_LAUUM || OP == OP_PRED_V || OP == OP_VG_G) ? KM : MK;
+    constexpr int LB = (OP == OP_TRTRI_T || OP == OP_TRTRI_W || OP == OP_LAUUM || OP == OP_PRED_V || OP == OP_VG_G || OP == OP_HESS_G) ? KM : MK;
     constexpr int NT = NW * 64;
     constexpr int LD = TM + 16;     // = 16 (mod 32): the two k rows a 32-lane group reads hit disjoint banks
     constexpr int WTM = TM / (NW / 2), WTN = TM / 2;   // per-wave sub-tile
@@ -1243,8 +1243,10 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& g, const int lin /*blo
         B0 = Bb + (size_t)rt * TM * g.ldB; dB = TM;
         nkt = g.p0;
         Ct = Cb + (size_t)ct * TM * g.ldC + (size_t)rt * TM;
-    } else if constexpr (OP == OP_VG_G) {
+    } else if constexpr (OP == OP_VG_G || OP == OP_HESS_G) {
         // G[m, c] = sum_{kt < p1} S[m, kt] U_ref[kt, c]      (S = n_candpad x n_refpad, U_ref = n_refpad x npad: no triangle)
+        // OP_HESS_G: the same dense product with dense square operands, G_i = A^-1 d_iA and Q = Y A^-1 of lcgp_nll_hess (A^-1
+        // mirrored to a full matrix, d_iA materialised: neither operand has a triangle to skip)
         const int c = bid / g.p0, m = bid % g.p0;                  // p0 = row tiles of S
         A0 = Ab + (size_t)m * TM * g.ldA; dA = TM;
         B0 = Bb + (size_t)c * TM; dB = (ptrdiff_t)TM * g.ldB;
@@ -1315,7 +1317,7 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& g, const int lin /*blo
     // only add exact zeros: it skips the stage's fragment reads and MFMAs (one wave-uniform test per stage, nothing
     // else changes; bit-identical results: the zeros are stored zeros).  LAUUM / TRTRI_W: 24 of the 64 (wave, stage)
     // pairs of such a tile, TRTRI_T / PRED_U / PRED_V: 16.
-    constexpr bool HAS_TRI = OP != OP_SYRK && OP != OP_PRED_COV && OP != OP_VR && OP != OP_VG_P && OP != OP_VG_G;
+    constexpr bool HAS_TRI = OP != OP_SYRK && OP != OP_PRED_COV && OP != OP_VR && OP != OP_VG_P && OP != OP_VG_G && OP != OP_HESS_G;
     const int tri_first = HAS_TRI ? (nkt - 1) * SPT : nst;
     // the wave is idle in the stages [dead_lo, dead_hi) of the k loop (two scalars per wave)
     int dead_lo = nst, dead_hi = nst;
@@ -4663,6 +4665,489 @@ int do_predict_hess(hipStream_t st, const Ws& w, const void* x, const void* sr, 
     return 0;
 }
 
+// ---------------------------------------------------------------------------------------------------
+// Hessian of the objective in the parameters (lcgp_hip.h: lcgp_nll_hess; no counterpart in the reference, whose
+// users would nest two gradient tapes around neglpost).  float64 only.  Runs behind lcgp_nll_grad at the same theta and only
+// READS the workspace (A^-1 lower tiles, b, z).  Per component, m = d + 2 kernel parameters [ell_0 .. ell_{d-1}, scale, nug]:
+//   AI = A^-1 mirrored to a full matrix; G_scale, G_nug elementwise from it (d_scale A and d_nug A are combinations of A, I and
+//   diag(s^2));  for every dimension i: E = d_iA materialised (one buffer, reused), y_i = E z, G_i = AI E on the tile kernel
+//   (OP_HESS_G);  tr(G_i G_j) by a tile-transposing reduction;  sum gmat o d_ijC by a fused contraction that recomputes C0,
+//   phi_i and d phi_i / d ell_i in registers;  u_i = AI y_i, Q = Y AI (tile kernel), and the small dot products.
+// Every sum has a fixed order (per-thread ascending, butterflies, per-band partials summed ascending), no atomics: bitwise
+// reproducible, independent of the number of components in the call and of the scratch content on entry.
+// ---------------------------------------------------------------------------------------------------
+constexpr int HS_B = 4;            // dimensions per block of a block pair of the second-order contraction
+constexpr int HS_SLOTS = 22;       // 16 second-order sums, 4 first-order sums, sum gmat o C0, trace gmat
+constexpr int HS_JC = 8;           // G_j tiles multiplied against one staged G_i tile
+
+struct HessLay {
+    int m, npad, nb, ppad, npair, nbk, npb;
+    size_t mat;
+    size_t off_ai, off_e, off_g, off_xs, off_yv, off_uv, off_yp, off_q, off_tp, off_cp, off_dot, total;
+};
+
+inline HessLay hess_carve(int n, int d, int p, int qg) {
+    HessLay H;
+    H.m = d + 2;
+    H.npad = round_up(n, 2 * TS);
+    H.nb = H.npad / TS;
+    H.ppad = round_up(p, 2 * TS);
+    H.npair = H.m * (H.m + 1) / 2;
+    H.nbk = (d + HS_B - 1) / HS_B;
+    H.npb = H.nbk * (H.nbk + 1) / 2;
+    H.mat = (size_t)H.npad * H.npad;
+    size_t o = 0;
+    const size_t e = sizeof(double);
+    H.off_ai = o; o = align256(o + (size_t)qg * H.mat * e);
+    H.off_e = o; o = align256(o + (size_t)qg * H.mat * e);
+    H.off_g = o; o = align256(o + (size_t)qg * H.m * H.mat * e);
+    H.off_xs = o; o = align256(o + (size_t)qg * d * H.npad * e);
+    H.off_yv = o; o = align256(o + (size_t)qg * H.m * H.npad * e);
+    H.off_uv = o; o = align256(o + (size_t)qg * H.m * H.npad * e);
+    H.off_yp = o; o = align256(o + (size_t)H.ppad * H.npad * e);
+    H.off_q = o; o = align256(o + (size_t)qg * H.ppad * H.npad * e);
+    H.off_tp = o; o = align256(o + (size_t)qg * H.npair * H.nb * e);
+    H.off_cp = o; o = align256(o + (size_t)qg * H.npb * H.nb * HS_SLOTS * e);
+    H.off_dot = o; o = align256(o + (size_t)qg * H.m * H.m * e);
+    H.total = o;
+    return H;
+}
+
+inline int hess_out_width(int d, int p) { return (d + 2) * (d + 2) + (d + 2) * p + p * p; }
+
+// phi = d log C0 / d ell and d phi / d ell of one dimension at S = |dx| / ell
+template <int KERN>
+__device__ __forceinline__ void hess_phi(double S, double ell, double& phi, double& dphi) {
+    static_assert(kern_known<KERN>::value, "unknown covariance kernel id");
+    const double ie = 1.0 / ell, S2 = S * S;
+    if constexpr (KERN == 0) {
+        const double r = 1.0 / (1.0 + S);
+        phi = S2 * r * ie;
+        dphi = -S2 * fma(2.0, S, 3.0) * (r * r) * (ie * ie);
+    } else if constexpr (KERN == 1) {
+        phi = S2 * ie;
+        dphi = -3.0 * S2 * (ie * ie);
+    } else {
+        const double r = 1.0 / fma(S, S, fma(3.0, S, 3.0));
+        const double N = S2 * (1.0 + S);
+        phi = N * r * ie;
+        dphi = -(S2 * fma(3.0, S, 2.0) * r + N * (3.0 - S2) * (r * r)) * (ie * ie);
+    }
+}
+
+// C0(a, b) from the inputs divided by ell, stored dimension-major (xs[l * npad + i])
+template <int KERN>
+__device__ __forceinline__ double hess_c0(const double* __restrict__ xs, int npad, int d, int a, int b) {
+    double poly = 1.0, ssum = 0.0;
+    for (int l = 0; l < d; ++l) {
+        const double df = xs[(size_t)l * npad + a] - xs[(size_t)l * npad + b];
+        if constexpr (KERN == 0) {
+            const double sd = fabs(df);
+            poly = fma(poly, sd, poly);
+            ssum -= sd;
+        } else if constexpr (KERN == 1) {
+            ssum = fma(-0.5 * df, df, ssum);
+        } else {
+            static_assert(KERN == 2, "unknown covariance kernel id");
+            const double sd = fabs(df);
+            poly = fma(poly, m52_fm1(sd), poly);
+            ssum -= sd;
+        }
+    }
+    return kern_c0<KERN>(poly, ssum);
+}
+
+// sum over the 256 threads of a workgroup in a fixed order (butterflies inside a wave, then the four waves); sh: 4 doubles
+__device__ __forceinline__ double hess_block_sum(double v, double* sh, int tid) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
+    __syncthreads();
+    if ((tid & 63) == 0) sh[tid >> 6] = v;
+    __syncthreads();
+    return (sh[0] + sh[1]) + (sh[2] + sh[3]);
+}
+
+// xs = x / ell (dimension-major, zero beyond n) and the two vectors that need no matrix: y_scale = d_scale A z = (b - z) / scale,
+// y_nug = d_nug A z = [D scale s^2 o z - (b - z)] / ((1 - w) (1 + nug)^2)        (A z = b)
+__global__ __launch_bounds__(256) void hess_prep_kernel(const double* __restrict__ x, const double* __restrict__ sr, int n, int npad,
+                                                        int d, const double* __restrict__ theta, int tw,
+                                                        const double* __restrict__ bvec, const double* __restrict__ zvec,
+                                                        double* __restrict__ xs, double* __restrict__ yv) {
+    const int i = blockIdx.x * 256 + threadIdx.x, k = blockIdx.y;
+    if (i >= npad) return;
+    const double* th = theta + (size_t)k * tw;
+    const double scale = th[d], nug = th[d + 1], D = th[d + 2];
+    double* xk = xs + (size_t)k * d * npad;
+    for (int l = 0; l < d; ++l) xk[(size_t)l * npad + i] = i < n ? x[(size_t)i * d + l] / th[l] : 0.0;
+    double* yk = yv + (size_t)k * (d + 2) * npad;
+    double ys = 0.0, yn = 0.0;
+    if (i < n) {
+        const double z = zvec[(size_t)k * npad + i], bz = bvec[(size_t)k * npad + i] - z;
+        const double s = sr ? sr[i] : 1.0;
+        ys = bz / scale;
+        yn = (D * scale * (s * s) * z - bz) / (1.0 + nug);      // 1 / ((1 - w) (1 + nug)^2) = 1 / (1 + nug)
+    }
+    yk[(size_t)d * npad + i] = ys;
+    yk[(size_t)(d + 1) * npad + i] = yn;
+}
+
+// AI = A^-1 as a full symmetric matrix (identity on the padding) from the lower tiles of the workspace, and beside it
+//   G_scale = A^-1 d_scale A = (I - A^-1) / scale,     G_nug = A^-1 d_nug A = [D scale A^-1 diag(s^2) - I + A^-1] / (1 + nug)
+// (zero on the padding)
+__global__ __launch_bounds__(256) void hess_mirror_kernel(const double* __restrict__ V, size_t mat, int n, int npad, int d,
+                                                          const double* __restrict__ sr, const double* __restrict__ theta, int tw,
+                                                          double* __restrict__ AI, double* __restrict__ G) {
+    const int b = blockIdx.x * 256 + threadIdx.x, a = blockIdx.y, k = blockIdx.z;
+    if (b >= npad) return;
+    const double* th = theta + (size_t)k * tw;
+    const double scale = th[d], nug = th[d + 1], D = th[d + 2];
+    const bool in = a < n && b < n;
+    const double* Vk = V + (size_t)k * mat;
+    const double dl = a == b ? 1.0 : 0.0;
+    const double v = in ? (b <= a ? Vk[(size_t)a * npad + b] : Vk[(size_t)b * npad + a]) : dl;
+    const size_t e = (size_t)a * npad + b;
+    AI[(size_t)k * mat + e] = v;
+    double* Gk = G + (size_t)k * (d + 2) * mat;
+    const double sb = (sr && b < n) ? sr[b] : 1.0;
+    Gk[(size_t)d * mat + e] = in ? (dl - v) / scale : 0.0;
+    Gk[(size_t)(d + 1) * mat + e] = in ? (fma(D * scale * (sb * sb), v, v) - dl) / (1.0 + nug) : 0.0;
+}
+
+// E = d A / d ell_i = D scale (1 - w) (s s^T) o C0 o phi_i as a full matrix, zero on the padding
+template <int KERN>
+__global__ __launch_bounds__(256) void hess_da_kernel(double* __restrict__ E, size_t mat, int n, int npad, int d, int i,
+                                                      const double* __restrict__ xs, const double* __restrict__ sr,
+                                                      const double* __restrict__ theta, int tw) {
+    const int b = blockIdx.x * 256 + threadIdx.x, a = blockIdx.y, k = blockIdx.z;
+    if (b >= npad) return;
+    double v = 0.0;
+    if (a < n && b < n) {
+        const double* th = theta + (size_t)k * tw;
+        const double scale = th[d], nug = th[d + 1], D = th[d + 2];
+        const double* xk = xs + (size_t)k * d * npad;
+        const double c0 = hess_c0<KERN>(xk, npad, d, a, b);
+        double phi, dphi;
+        hess_phi<KERN>(fabs(xk[(size_t)i * npad + a] - xk[(size_t)i * npad + b]), th[i], phi, dphi);
+        const double ss = sr ? sr[a] * sr[b] : 1.0;
+        v = (D * scale / (1.0 + nug)) * ss * c0 * phi;
+    }
+    E[(size_t)k * mat + (size_t)a * npad + b] = v;
+}
+
+// O[v][r] = sum_c M[r, c] X[v][c]: one wave per row, the lanes stride the columns, butterflies at the end
+__global__ __launch_bounds__(256) void hess_matvec_kernel(const double* __restrict__ M, size_t sM, int n, int npad,
+                                                          const double* __restrict__ X, size_t sXk, double* __restrict__ O, size_t sOk) {
+    const int lane = threadIdx.x & 63, r = blockIdx.x * 4 + (threadIdx.x >> 6), v = blockIdx.y, k = blockIdx.z;
+    const double* row = M + (size_t)k * sM + (size_t)r * npad;
+    const double* xv = X + (size_t)k * sXk + (size_t)v * npad;
+    double s = 0.0;
+    for (int c = lane; c < n; c += 64) s = fma(row[c], xv[c], s);      // (columns beyond n hold the padding: exact zeros in M)
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) s += __shfl_xor(s, o);
+    if (lane == 0) O[(size_t)k * sOk + (size_t)v * npad + r] = s;
+}
+
+// partial traces: tp[k][pair(i, j <= i)][rb] = sum_{a in band rb} sum_b G_i[a, b] G_j[b, a].  One workgroup per (band, i, chunk of
+// HS_JC values of j): the 64 x 64 tile G_i[rb, tb] is staged in LDS and read transposed against the tiles G_j[tb, rb]
+__global__ __launch_bounds__(256) void hess_trace_kernel(const double* __restrict__ G, size_t mat, int npad, int nb, int m, int npair,
+                                                         double* __restrict__ tp) {
+    __shared__ double T[TS][TS + 1];
+    __shared__ double sh[4];
+    const int njc = (m + HS_JC - 1) / HS_JC;
+    const int rb = blockIdx.x, i = blockIdx.y / njc, j0 = (blockIdx.y % njc) * HS_JC, k = blockIdx.z;
+    if (j0 > i) return;
+    const int tid = threadIdx.x, c = tid & 63, r0 = tid >> 6;
+    const double* Gk = G + (size_t)k * m * mat;
+    const double* Gi = Gk + (size_t)i * mat;
+    double acc[HS_JC];
+#pragma unroll
+    for (int jj = 0; jj < HS_JC; ++jj) acc[jj] = 0.0;
+    for (int tb = 0; tb < nb; ++tb) {
+        __syncthreads();
+#pragma unroll
+        for (int e = 0; e < 16; ++e) T[r0 + 4 * e][c] = Gi[(size_t)(rb * TS + r0 + 4 * e) * npad + tb * TS + c];
+        __syncthreads();
+#pragma unroll
+        for (int jj = 0; jj < HS_JC; ++jj) {
+            if (j0 + jj <= i) {
+                const double* Gj = Gk + (size_t)(j0 + jj) * mat + (size_t)(tb * TS) * npad + rb * TS + c;
+                double s = acc[jj];
+#pragma unroll
+                for (int e = 0; e < 16; ++e) s = fma(Gj[(size_t)(r0 + 4 * e) * npad], T[c][r0 + 4 * e], s);
+                acc[jj] = s;
+            }
+        }
+    }
+#pragma unroll
+    for (int jj = 0; jj < HS_JC; ++jj) {
+        if (j0 + jj <= i) {          // (uniform over the workgroup)
+            const double s = hess_block_sum(acc[jj], sh, tid);
+            if (tid == 0) tp[((size_t)k * npair + (size_t)i * (i + 1) / 2 + j0 + jj) * nb + rb] = s;
+        }
+    }
+}
+
+// The second-order fused contraction: with gmat = s s^T o (D/2 A^-1 - z z^T / 2) (the weight of the gradient contraction) and
+// w0 = gmat o C0, for the band rb of 64 rows and the block pair (bi, bj <= bi) of HS_B dimensions each
+//   slot ii * 4 + jj : sum w0 (phi_i phi_j + [i == j] d phi_i / d ell_i),   i = 4 bi + ii, j = 4 bj + jj
+//   slot 16 + ii     : sum w0 phi_i        (bj == 0 only)
+//   slot 20, 21      : sum w0, trace gmat  (block pair 0 only)
+// C0, phi and d phi are recomputed in registers from the scaled inputs: no n x n x d x d tensor is written
+template <int KERN>
+__global__ __launch_bounds__(256) void hess_contract_kernel(const double* __restrict__ AI, size_t mat, int n, int npad, int nb, int d,
+                                                            const double* __restrict__ xs, const double* __restrict__ sr,
+                                                            const double* __restrict__ zvec, const double* __restrict__ theta, int tw,
+                                                            int npb, double* __restrict__ cp) {
+    __shared__ double sh[4];
+    const int rb = blockIdx.x, pb = blockIdx.y, k = blockIdx.z;
+    int bi, bj;
+    tri_decode(pb, bi, bj);
+    const int tid = threadIdx.x, cl = tid & 63, r0 = tid >> 6;
+    const double* th = theta + (size_t)k * tw;
+    const double D = th[d + 2];
+    const double* xk = xs + (size_t)k * d * npad;
+    const double* zk = zvec + (size_t)k * npad;
+    const double* Ak = AI + (size_t)k * mat;
+    double a2[HS_B][HS_B], a1[HS_B], a0 = 0.0, ad = 0.0;
+#pragma unroll
+    for (int ii = 0; ii < HS_B; ++ii) {
+        a1[ii] = 0.0;
+#pragma unroll
+        for (int jj = 0; jj < HS_B; ++jj) a2[ii][jj] = 0.0;
+    }
+    for (int tb = 0; tb < nb; ++tb) {
+        const int b = tb * TS + cl;
+        if (b >= n) continue;
+        const double zb = zk[b], sb = sr ? sr[b] : 1.0;
+        for (int e = 0; e < 16; ++e) {
+            const int a = rb * TS + r0 + 4 * e;
+            if (a >= n) continue;
+            const double sa = sr ? sr[a] : 1.0;
+            const double g = (sa * sb) * (0.5 * D * Ak[(size_t)a * npad + b] - 0.5 * (zk[a] * zb));
+            const double w0 = g * hess_c0<KERN>(xk, npad, d, a, b);
+            a0 += w0;
+            if (a == b) ad += g;
+            double pi[HS_B], dpi[HS_B], pj[HS_B];
+#pragma unroll
+            for (int ii = 0; ii < HS_B; ++ii) {
+                const int li = bi * HS_B + ii, lj = bj * HS_B + ii;
+                pi[ii] = dpi[ii] = pj[ii] = 0.0;
+                if (li < d) hess_phi<KERN>(fabs(xk[(size_t)li * npad + a] - xk[(size_t)li * npad + b]), th[li], pi[ii], dpi[ii]);
+                if (bi == bj) pj[ii] = pi[ii];
+                else if (lj < d) {
+                    double unused;
+                    hess_phi<KERN>(fabs(xk[(size_t)lj * npad + a] - xk[(size_t)lj * npad + b]), th[lj], pj[ii], unused);
+                }
+            }
+#pragma unroll
+            for (int ii = 0; ii < HS_B; ++ii) {
+                a1[ii] = fma(w0, pi[ii], a1[ii]);
+#pragma unroll
+                for (int jj = 0; jj < HS_B; ++jj) {
+                    const double k2 = (bi == bj && ii == jj) ? fma(pi[ii], pj[jj], dpi[ii]) : pi[ii] * pj[jj];
+                    a2[ii][jj] = fma(w0, k2, a2[ii][jj]);
+                }
+            }
+        }
+    }
+    double* out = cp + (((size_t)k * npb + pb) * nb + rb) * HS_SLOTS;
+#pragma unroll
+    for (int ii = 0; ii < HS_B; ++ii)
+#pragma unroll
+        for (int jj = 0; jj < HS_B; ++jj) {
+            const double s = hess_block_sum(a2[ii][jj], sh, tid);
+            if (tid == 0) out[ii * HS_B + jj] = s;
+        }
+#pragma unroll
+    for (int ii = 0; ii < HS_B; ++ii) {
+        const double s = hess_block_sum(a1[ii], sh, tid);
+        if (tid == 0) out[16 + ii] = s;
+    }
+    const double s0 = hess_block_sum(a0, sh, tid), sd = hess_block_sum(ad, sh, tid);
+    if (tid == 0) { out[20] = s0; out[21] = sd; }
+}
+
+// dot[k][i * m + j] = y_i . u_j  (u_j = A^-1 y_j): one wave per pair
+__global__ __launch_bounds__(64) void hess_dot_kernel(const double* __restrict__ yv, const double* __restrict__ uv, int n, int npad, int m,
+                                                      double* __restrict__ dot) {
+    const int i = blockIdx.x / m, j = blockIdx.x % m, k = blockIdx.y, lane = threadIdx.x;
+    const double* y = yv + ((size_t)k * m + i) * npad;
+    const double* u = uv + ((size_t)k * m + j) * npad;
+    double s = 0.0;
+    for (int c = lane; c < n; c += 64) s = fma(y[c], u[c], s);
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) s += __shfl_xor(s, o);
+    if (lane == 0) dot[(size_t)k * m * m + blockIdx.x] = s;
+}
+
+// Y (p x n) zero padded to ppad x npad: the A operand of Q = Y A^-1
+__global__ __launch_bounds__(256) void hess_pack_y_kernel(const double* __restrict__ Y, int p, int n, int npad, double* __restrict__ YP) {
+    const int i = blockIdx.x * 256 + threadIdx.x, a = blockIdx.y;
+    if (i >= npad) return;
+    YP[(size_t)a * npad + i] = (a < p && i < n) ? Y[(size_t)a * n + i] : 0.0;
+}
+
+// cross block: hx[i * p + a] = psi_a (Y_a . u_i) / (2 D): one wave per entry
+__global__ __launch_bounds__(64) void hess_cross_kernel(const double* __restrict__ YP, const double* __restrict__ uv, int n, int npad, int m,
+                                                        int p, int d, const double* __restrict__ theta, int tw, double* __restrict__ out,
+                                                        int ow) {
+    const int i = blockIdx.x / p, a = blockIdx.x % p, k = blockIdx.y, lane = threadIdx.x;
+    const double* th = theta + (size_t)k * tw;
+    const double* y = YP + (size_t)a * npad;
+    const double* u = uv + ((size_t)k * m + i) * npad;
+    double s = 0.0;
+    for (int c = lane; c < n; c += 64) s = fma(y[c], u[c], s);
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) s += __shfl_xor(s, o);
+    if (lane == 0) out[(size_t)k * ow + m * m + blockIdx.x] = th[d + 3 + a] * s / (2.0 * th[d + 2]);
+}
+
+// noise block: hn[a * p + b] = -[ delta_ab psi_a Y_a . (b - z) + psi_a psi_b Y_a . (Y_b - Q_b) ] / (4 D),  Q_b = A^-1 Y_b
+__global__ __launch_bounds__(64) void hess_noise_kernel(const double* __restrict__ YP, const double* __restrict__ Q, size_t sQ, int n, int npad,
+                                                        int m, int p, int d, const double* __restrict__ bvec,
+                                                        const double* __restrict__ zvec, const double* __restrict__ theta, int tw,
+                                                        double* __restrict__ out, int ow) {
+    const int a = blockIdx.x / p, b = blockIdx.x % p, k = blockIdx.y, lane = threadIdx.x;
+    const double* th = theta + (size_t)k * tw;
+    const double* ya = YP + (size_t)a * npad;
+    const double* yb = YP + (size_t)b * npad;
+    const double* qb = Q + (size_t)k * sQ + (size_t)b * npad;
+    const double* bk = bvec + (size_t)k * npad;
+    const double* zk = zvec + (size_t)k * npad;
+    double s = 0.0, t = 0.0;
+    for (int c = lane; c < n; c += 64) {
+        s = fma(ya[c], yb[c] - qb[c], s);
+        if (a == b) t = fma(ya[c], bk[c] - zk[c], t);
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) { s += __shfl_xor(s, o); t += __shfl_xor(t, o); }
+    if (lane == 0) {
+        const double pa = th[d + 3 + a], pb = th[d + 3 + b];
+        out[(size_t)k * ow + m * m + m * p + blockIdx.x] = -(pa * t + pa * pb * s) / (4.0 * th[d + 2]);
+    }
+}
+
+// kernel block: hk[i][j] = T_ij - tr(G_i G_j) / 2 + y_i . u_j / D, one thread per pair i >= j, written to both triangles.
+// T_ij = sum gmat o d_ij C from the slots of hess_contract_kernel, the bands summed in ascending order
+__global__ __launch_bounds__(256) void hess_final_kernel(const double* __restrict__ tp, const double* __restrict__ cp,
+                                                         const double* __restrict__ dot, int nb, int m, int npair, int npb, int d,
+                                                         const double* __restrict__ theta, int tw, double* __restrict__ out, int ow) {
+    const int t = blockIdx.x * 256 + threadIdx.x, k = blockIdx.y;
+    if (t >= npair) return;
+    int i, j;
+    tri_decode(t, i, j);
+    const double* th = theta + (size_t)k * tw;
+    const double scale = th[d], nug = th[d + 1], D = th[d + 2];
+    const double w1 = 1.0 / ((1.0 + nug) * (1.0 + nug)), omw = 1.0 / (1.0 + nug);      // dw / dnug, 1 - w
+    const double* cpk = cp + (size_t)k * npb * nb * HS_SLOTS;
+    auto slot_sum = [&](int pb, int slot) {
+        double s = 0.0;
+        for (int rb = 0; rb < nb; ++rb) s += cpk[((size_t)pb * nb + rb) * HS_SLOTS + slot];
+        return s;
+    };
+    double T;
+    if (i < d) {                       // (j <= i < d)
+        const int bi = i / HS_B, bj = j / HS_B;
+        T = scale * omw * slot_sum(bi * (bi + 1) / 2 + bj, (i % HS_B) * HS_B + j % HS_B);
+    } else if (j < d) {                // (scale | nug) x ell_j
+        const int bj = j / HS_B;
+        const double s1 = slot_sum(bj * (bj + 1) / 2, 16 + j % HS_B);
+        T = i == d ? omw * s1 : -scale * w1 * s1;
+    } else {
+        const double dd = slot_sum(0, 21) - slot_sum(0, 20);       // sum gmat o (I - C0)
+        T = (i == d) ? 0.0 : (j == d ? w1 * dd : -2.0 * scale * w1 * omw * dd);
+    }
+    double tr = 0.0;
+    const double* tpk = tp + ((size_t)k * npair + t) * nb;
+    for (int rb = 0; rb < nb; ++rb) tr += tpk[rb];
+    const double v = (T - 0.5 * tr) + dot[(size_t)k * m * m + (size_t)i * m + j] / D;
+    out[(size_t)k * ow + (size_t)i * m + j] = v;
+    out[(size_t)k * ow + (size_t)j * m + i] = v;
+}
+
+// enqueues the pass for the components [k0, k0 + qg) of the workspace; `out` rows are those of the q_local components
+int do_nll_hess(hipStream_t st, const Ws& w, const void* x, const double* Y, const void* sr, const double* theta, int k0, int qg,
+                char* scratch, double* out) {
+    const int n = w.n, d = w.d, p = w.p, npad = w.npad, tw = d + 3 + p, ow = hess_out_width(d, p);
+    const HessLay H = hess_carve(n, d, p, qg);
+    const int m = H.m, nb = H.nb;
+    double* AI = (double*)(scratch + H.off_ai);
+    double* E = (double*)(scratch + H.off_e);
+    double* G = (double*)(scratch + H.off_g);
+    double* XS = (double*)(scratch + H.off_xs);
+    double* YV = (double*)(scratch + H.off_yv);
+    double* UV = (double*)(scratch + H.off_uv);
+    double* YP = (double*)(scratch + H.off_yp);
+    double* Q = (double*)(scratch + H.off_q);
+    double* TP = (double*)(scratch + H.off_tp);
+    double* CP = (double*)(scratch + H.off_cp);
+    double* DOT = (double*)(scratch + H.off_dot);
+    const double* V = (const double*)(w.base + w.off_V) + (size_t)k0 * w.mat;
+    const double* bv = (const double*)(w.base + w.off_b) + (size_t)k0 * npad;
+    const double* zv = (const double*)(w.base + w.off_z) + (size_t)k0 * npad;
+    const double* th = theta + (size_t)k0 * tw;
+    const double* xd = (const double*)x;
+    const double* srd = (const double*)sr;
+    double* o = out + (size_t)k0 * ow;
+    const dim3 full((npad + 255) / 256, npad, qg);
+
+    hipLaunchKernelGGL(hess_prep_kernel, dim3((npad + 255) / 256, qg), dim3(256), 0, st, xd, srd, n, npad, d, th, tw, bv, zv, XS, YV);
+    CHECK_LAUNCH("hess_prep_kernel");
+    hipLaunchKernelGGL(hess_mirror_kernel, full, dim3(256), 0, st, V, w.mat, n, npad, d, srd, th, tw, AI, G);
+    CHECK_LAUNCH("hess_mirror_kernel");
+    GemmArgs g;
+    g.A = AI; g.B = E; g.ldA = g.ldB = g.ldC = npad;
+    g.sA = H.mat; g.sB = H.mat; g.sC = (size_t)m * H.mat;
+    g.nb = nb / 2; g.p0 = nb / 2; g.p1 = nb / 2; g.p2 = g.p3 = 0;
+    for (int i = 0; i < d; ++i) {
+        for_kern(w.kern, [&](auto kern) {
+            hipLaunchKernelGGL((hess_da_kernel<decltype(kern)::value>), full, dim3(256), 0, st, E, H.mat, n, npad, d, i,
+                               (const double*)XS, srd, th, tw);
+        });
+        CHECK_LAUNCH("hess_da_kernel");
+        // y_i = d_iA z
+        hipLaunchKernelGGL(hess_matvec_kernel, dim3(npad / 4, 1, qg), dim3(256), 0, st, (const double*)E, H.mat, n, npad, zv, (size_t)npad,
+                           YV + (size_t)i * npad, (size_t)m * npad);
+        CHECK_LAUNCH("hess_matvec_kernel");
+        g.C = G + (size_t)i * H.mat;
+        int rc = launch_gemm<double, OP_HESS_G, 128>(st, g, g.p0 * g.nb, qg);
+        if (rc) return rc;
+    }
+    hipLaunchKernelGGL(hess_trace_kernel, dim3(nb, m * ((m + HS_JC - 1) / HS_JC), qg), dim3(256), 0, st, (const double*)G, H.mat, npad,
+                       nb, m, H.npair, TP);
+    CHECK_LAUNCH("hess_trace_kernel");
+    for_kern(w.kern, [&](auto kern) {
+        hipLaunchKernelGGL((hess_contract_kernel<decltype(kern)::value>), dim3(nb, H.npb, qg), dim3(256), 0, st, (const double*)AI, H.mat,
+                           n, npad, nb, d, (const double*)XS, srd, zv, th, tw, H.npb, CP);
+    });
+    CHECK_LAUNCH("hess_contract_kernel");
+    // u_i = A^-1 y_i for all m vectors
+    hipLaunchKernelGGL(hess_matvec_kernel, dim3(npad / 4, m, qg), dim3(256), 0, st, (const double*)AI, H.mat, n, npad, (const double*)YV,
+                       (size_t)m * npad, UV, (size_t)m * npad);
+    CHECK_LAUNCH("hess_matvec_kernel");
+    hipLaunchKernelGGL(hess_dot_kernel, dim3(m * m, qg), dim3(64), 0, st, (const double*)YV, (const double*)UV, n, npad, m, DOT);
+    CHECK_LAUNCH("hess_dot_kernel");
+    // Q = Y A^-1 (Y zero padded to whole tiles; A^-1 symmetric: row b of Q is A^-1 Y_b)
+    hipLaunchKernelGGL(hess_pack_y_kernel, dim3((npad + 255) / 256, H.ppad), dim3(256), 0, st, Y, p, n, npad, YP);
+    CHECK_LAUNCH("hess_pack_y_kernel");
+    GemmArgs gq;
+    gq.A = YP; gq.B = AI; gq.C = Q; gq.ldA = gq.ldB = gq.ldC = npad;
+    gq.sA = 0; gq.sB = H.mat; gq.sC = (size_t)H.ppad * npad;
+    gq.nb = nb / 2; gq.p0 = H.ppad / (2 * TS); gq.p1 = nb / 2; gq.p2 = gq.p3 = 0;
+    int rc = launch_gemm<double, OP_HESS_G, 128>(st, gq, gq.p0 * gq.nb, qg);
+    if (rc) return rc;
+    hipLaunchKernelGGL(hess_cross_kernel, dim3(m * p, qg), dim3(64), 0, st, (const double*)YP, (const double*)UV, n, npad, m, p, d, th, tw,
+                       o, ow);
+    CHECK_LAUNCH("hess_cross_kernel");
+    hipLaunchKernelGGL(hess_noise_kernel, dim3(p * p, qg), dim3(64), 0, st, (const double*)YP, (const double*)Q, (size_t)H.ppad * npad, n,
+                       npad, m, p, d, bv, zv, th, tw, o, ow);
+    CHECK_LAUNCH("hess_noise_kernel");
+    hipLaunchKernelGGL(hess_final_kernel, dim3((H.npair + 255) / 256, qg), dim3(256), 0, st, (const double*)TP, (const double*)CP,
+                       (const double*)DOT, nb, m, H.npair, H.npb, d, th, tw, o, ow);
+    CHECK_LAUNCH("hess_final_kernel");
+    return 0;
+}
+
 int check_sel(int n_ref, int n_cand, int size) {
     int rc = check_vr(n_ref, n_cand);
     if (rc) return rc;
@@ -4891,6 +5376,35 @@ int lcgp_nll_grad(void* stream, int dtype, int kernel_id, int n, int d, int p, i
     w.kern = kernel_id;
     return dtype == LCGP_F64 ? do_nll_grad<double>((hipStream_t)stream, w, sc, x, Y, sr, theta, out, plan_host)
                              : do_nll_grad<float>((hipStream_t)stream, w, sc, x, Y, sr, theta, out, plan_host);
+}
+
+int lcgp_nll_hess_width(int d, int p) { return hess_out_width(d, p); }
+
+static int check_nll_hess(int dtype) {
+    if (dtype == LCGP_F32) return bad("lcgp_nll_hess is float64 only (the trace difference of the kernel block cancels heavily): "
+                                      "evaluate on a float64 workspace");
+    return 0;
+}
+
+int lcgp_nll_hess_scratch_bytes(int dtype, int n, int d, int p, int q_group, size_t* bytes) {
+    int rc = check_common(dtype, n, d, p, q_group);
+    if (rc) return rc;
+    if ((rc = check_nll_hess(dtype))) return rc;
+    if (!bytes) return bad("bytes is NULL");
+    *bytes = hess_carve(n, d, p, q_group).total;
+    return 0;
+}
+
+int lcgp_nll_hess(void* stream, int dtype, int kernel_id, int n, int d, int p, int q_local, const void* x, const void* Y,
+                  const void* sr, const double* theta, const void* workspace, int k0, int q_group, void* scratch, double* out) {
+    int rc = check_common(dtype, n, d, p, q_local, kernel_id);
+    if (rc) return rc;
+    if ((rc = check_nll_hess(dtype))) return rc;
+    if (k0 < 0 || q_group < 1 || k0 + q_group > q_local) return bad("k0 / q_group must select components inside [0, q_local)");
+    if (!x || !Y || !theta || !workspace || !scratch || !out) return bad("NULL pointer");
+    Ws w = carve(dtype, n, d, p, q_local, (void*)workspace);
+    w.kern = kernel_id;
+    return do_nll_hess((hipStream_t)stream, w, x, (const double*)Y, sr, theta, k0, q_group, (char*)scratch, out);
 }
 
 int lcgp_plan_bytes(int dtype, int n, int q_local, int with_inverse, const lcgp_sched* sched, size_t* bytes) {

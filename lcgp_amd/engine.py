@@ -695,6 +695,42 @@ class HotPathEngine:
         off = sel['picks'] - sel['scratch'].data_ptr()
         return sel['scratch'][off:off + 4 * sel['size']].view(self.torch.int32)
 
+    # ------------------------------------------------------------------------------------------------
+    # exact Hessian of the objective in the parameters (lcgp_hip.h: lcgp_nll_hess)
+    def nll_hess_block(self):
+        """(q_local, (d + 2)^2 + (d + 2) p + p^2) float64 DEVICE tensor: per local component the kernel block, the kernel x built
+        noise block and the component's share of the built noise block of the Hessian of the objective in the CONSTRAINED
+        parameters (lcgp_nll_hess), from the factorisation of the last evaluate() -- which it only reads.  float64 engines only.
+        The scratch holds (d + 4) npad^2 doubles per component processed at once: the local components go in groups as large
+        as the free device memory allows (results are bitwise independent of the grouping); raises ValueError when even one
+        component does not fit."""
+        torch = self.torch
+        if self._theta_last is None:
+            raise RuntimeError("loss_hessian() needs a preceding evaluate() at the current parameters")
+        if self.dtype != _hip.F64:
+            raise RuntimeError("the Hessian of the objective is float64 only: evaluate on a float64 engine")
+        with torch.cuda.device(self.device):
+            width = self.lib.lcgp_nll_hess_width(self.d, self.p)
+            free, _ = torch.cuda.mem_get_info(self.device)
+            free += torch.cuda.memory_reserved(self.device) - torch.cuda.memory_allocated(self.device)
+            free += 0 if self._scratch is None else self._scratch.numel()
+            group = self.q_local
+            while True:
+                nbytes = self._nbytes("lcgp_nll_hess_scratch_bytes", self.dtype, self.n, self.d, self.p, group)
+                if group == 1 or nbytes <= free:
+                    break
+                group = (group + 1) // 2
+            scp = self._p(self._grow_scratch(nbytes, ("the Hessian of the objective", "%d matrices of n x n per component"
+                                                      % (self.d + 4), "use fewer training inputs per GPU")))
+            out = torch.empty((self.q_local, width), dtype=torch.float64, device=self.device)
+            st = self._stream()
+            for k0 in range(0, self.q_local, group):
+                _hip.check(self.lib.lcgp_nll_hess(st, self.dtype, self.kernel_id, self.n, self.d, self.p, self.q_local,
+                                                  self._p(self.x), self._p(self.Y), self._p(self.sr), self._p(self.theta_dev),
+                                                  self._p(self.workspace), k0, min(group, self.q_local - k0), scp, self._p(out)),
+                           "lcgp_nll_hess")
+            return out
+
     def fetch_vector(self, which, k):
         torch = self.torch
         with torch.cuda.device(self.device):

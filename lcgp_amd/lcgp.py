@@ -25,7 +25,7 @@ import torch
 
 from . import dist as _dist
 from .params import Parameter, SoftClip
-from .params import softclip_flat
+from .params import softclip_flat, softclip_flat2
 
 F64 = np.float64
 
@@ -164,6 +164,17 @@ class _VrFn(torch.autograd.Function):
         dt, dev, shape = ctx.meta
         gx = torch.einsum('ac,acl->cl', _cpu64(g), ctx.dgain)
         return gx.reshape(shape).to(device=dev, dtype=dt), None, None
+
+
+class LaplaceResult:
+    """What LCGP.laplace() returns: `hessian` (the unconstrained Hessian of the objective), its `eigenvalues` (ascending),
+    `cov` = hessian^-1 and `stderr`, the delta-method standard errors of the constrained parameters shaped like get_param()."""
+
+    def __init__(self, hessian, eigenvalues, cov, stderr):
+        self.hessian, self.eigenvalues, self.cov, self.stderr = hessian, eigenvalues, cov, stderr
+
+    def __repr__(self):
+        return "LaplaceResult(P=%d, eigenvalues in [%.3e, %.3e])" % (len(self.eigenvalues), self.eigenvalues[0], self.eigenvalues[-1])
 
 
 class LCGP:
@@ -691,7 +702,8 @@ class LCGP:
         g_ls2 = np.add.reduceat(g_b, es_starts)
         grad = np.concatenate([vec[2:2 + q * d + 2 * q], g_ls2])
         if self.submethod == 'rep':
-            return float(nll / n), grad / n
+            nll, grad = nll / n, grad / n
+        self._gc_last = grad             # (the constrained gradient at _u_last: the curvature term of loss_hessian's chain rule)
         return float(nll), grad
 
     def loss_and_grad(self, u=None):
@@ -708,6 +720,125 @@ class LCGP:
                               self.lnugGPs.transform.dforward(self.lnugGPs.unconstrained),
                               np.ones(self.lsigma2s.size, F64)])
         return val, g * jac
+
+    # =============================================================================================
+    # exact Hessian of the objective in the parameters (beyond the reference, which would nest two tapes around neglpost)
+    # =============================================================================================
+    def _hessian_blocks(self):
+        """((q, (d + 2)^2 + (d + 2) p + p^2) numpy array of the per-component blocks of lcgp_nll_hess, constrained gradient)
+        at the current parameters.  The factorisation in the workspace is reused when it is the current one and float64;
+        otherwise one evaluation runs first (a float32 model: on its float64 engine).  Every rank computes its components'
+        rows; one reduction of the zero-padded block gathers them (_gather_components), failures go through _agree."""
+        eng = self._get_engine()
+        if not (self._aux_valid and (self._dtype == 'float64' or self._last_eval_float64)):
+            if self._dtype == 'float64' or self._float64_only:
+                self._run_path()
+            else:
+                self._ensure_engine64()
+                self._float64_only = True          # one evaluation on the float64 engine at the current parameters
+                try:
+                    self._run_path()
+                finally:
+                    self._float64_only = False
+        aux = self._aux_engine if eng is not None else None
+        d, p = int(self.d), int(self.p)
+        width = (d + 2) * (d + 2) + (d + 2) * p + p * p
+        blocks = self._gather_components(self._agree(lambda: None if aux is None else aux.nll_hess_block()), (width,))
+        return np.asarray(blocks, F64), self._gc_last
+
+    def _hessian_constrained(self, blocks):
+        """(P, P) Hessian in the constrained parameters from the per-component blocks: the q dense kernel blocks, the border
+        and the noise corner (a sum over the components in ascending order, plus the term of the objective outside the
+        components), both noise blocks folded through the error-structure groups; rep: the 1 / n of the objective."""
+        n, d, p, q = int(self.n), int(self.d), int(self.p), int(self.q)
+        m = d + 2
+        es = np.asarray(self.diag_error_structure, int)
+        starts = np.r_[0, np.cumsum(es)[:-1]]
+        ns = len(es)
+        o = q * m
+        H = np.zeros((o + ns, o + ns), F64)
+        sig_eff = np.exp(0.5 * np.repeat(self.lsigma2s.numpy(), es)) / self._std
+        corner = np.diag(0.5 * self._ysq / sig_eff ** 2)
+        for k in range(q):
+            row = blocks[k]
+            idx = np.r_[k * d + np.arange(d), q * d + k, q * d + q + k]
+            H[np.ix_(idx, idx)] = row[:m * m].reshape(m, m)
+            H[idx, o:] = border = np.add.reduceat(row[m * m:m * m + m * p].reshape(m, p), starts, axis=1)
+            H[o:, idx] = border.T
+            corner = corner + row[m * m + m * p:].reshape(p, p)
+        H[o:, o:] = np.add.reduceat(np.add.reduceat(corner, starts, axis=0), starts, axis=1)
+        if self.submethod == 'rep':
+            H /= n
+        return H
+
+    def _flat_jacobians(self):
+        """d constrained / d unconstrained and its derivative, in flat order (1 and 0 on lsigma2s, which has no bijector)"""
+        pars = (self.lLmb, self.lLmb0, self.lnugGPs)
+        ns = self.lsigma2s.size
+        if self._flat_transform() is not None:
+            _, lo, hi, w, cc, _ = self._bounds_cache
+            u = np.concatenate([par.unconstrained.reshape(-1) for par in pars])
+            j, j2 = softclip_flat2(u, lo, hi, w, cc)
+        else:
+            for par in pars:
+                if not hasattr(par.transform, 'd2forward'):
+                    raise NotImplementedError(
+                        "loss_hessian(space='unconstrained') needs the second derivative of the bijector of %s: give %s a "
+                        "d2forward(u) beside dforward(u), or ask for space='constrained'" % (par.name, type(par.transform).__name__))
+            j = np.concatenate([par.transform.dforward(par.unconstrained).reshape(-1) for par in pars])
+            j2 = np.concatenate([np.asarray(par.transform.d2forward(par.unconstrained), F64).reshape(-1) for par in pars])
+        return np.concatenate([j, np.ones(ns, F64)]), np.concatenate([j2, np.zeros(ns, F64)])
+
+    def loss_hessian(self, u=None, space='unconstrained'):
+        """Exact Hessian of the objective (`loss()`) in the parameters: a (P, P) float64 numpy array in the flat order of
+        loss_and_grad (lLmb, lLmb0, lnugGPs, lsigma2s), evaluated at `u` if given (the parameters are set to it, as
+        loss_and_grad does).  space='unconstrained' (default): in the vector the optimiser sees, H_u = J H_c J + diag(g_c o
+        d2forward), the matrix that goes with loss_and_grad's gradient; space='constrained': in the constrained values
+        get_param() returns (lsigma2s per error-structure group).
+        One GPU pass (lcgp_nll_hess) behind the factorisation of the current parameters, which is reused when the workspace
+        holds it (right after fit() or loss_and_grad(u)) and only read: predict() stays valid.  Always float64: a
+        dtype='float32' model evaluates once on its float64 engine at the current parameters and computes there, so its
+        result is the float64 model's.  The result is exactly symmetric (one triangle mirrored, not averaged); kernel
+        blocks of different components are exactly zero.  Multi-rank: each rank computes its components, one reduction
+        assembles them, every rank returns the same matrix.  GPU memory: (d + 4) npad^2 doubles per component processed at a
+        time -- ValueError when not even one fits."""
+        if space not in ('unconstrained', 'constrained'):
+            raise ValueError("space must be 'unconstrained' or 'constrained', not %r" % (space,))
+        if u is not None:
+            self._set_flat(u)
+        if space == 'unconstrained':
+            jac, jac2 = self._flat_jacobians()          # (before the GPU pass: a bijector without d2forward fails at once)
+        blocks, g_c = self._hessian_blocks()
+        H = self._hessian_constrained(blocks)
+        if space == 'unconstrained':
+            H = jac[:, None] * H * jac[None, :]
+            H[np.diag_indices_from(H)] += g_c * jac2
+        low = np.tril(H)
+        return low + np.tril(H, -1).T
+
+    def laplace(self):
+        """Laplace approximation at the current parameters (call it after fit()): a LaplaceResult with
+            hessian      (P, P) loss_hessian() in the unconstrained vector       eigenvalues  (P,) ascending
+            cov          (P, P) its inverse, the covariance of the unconstrained vector
+            stderr       standard errors of the CONSTRAINED parameters by the delta method (|d forward| sqrt(diag cov)), a
+                         tuple shaped like get_param(): (lLmb (q, d), lLmb0 (q,), built lsigma2s (p,), lnugGPs (q,))
+        On the rep path the objective carries 1 / n, so cov is n times the covariance of the parameters' posterior mode
+        approximation of the unnormalised objective.  Raises numpy.linalg.LinAlgError naming the smallest eigenvalue when the
+        Hessian is not positive definite (a flat valley or a point that is no minimum); nothing is jittered."""
+        H = self.loss_hessian(space='unconstrained')
+        ev, vec = np.linalg.eigh(H)
+        if not np.all(np.isfinite(ev)) or ev[0] <= 0.0:
+            raise np.linalg.LinAlgError('the Hessian of the objective is not positive definite at the current parameters: '
+                                        'smallest eigenvalue %.6e (largest %.6e)' % (ev[0], ev[-1]))
+        cov = (vec / ev[None, :]) @ vec.T
+        cov = np.tril(cov) + np.tril(cov, -1).T
+        jac, _ = self._flat_jacobians()
+        se = np.abs(jac) * np.sqrt(np.diag(cov))
+        q, d = int(self.q), int(self.d)
+        es = np.asarray(self.diag_error_structure, int)
+        stderr = (_t(se[:q * d].reshape(q, d)), _t(se[q * d:q * d + q]), _t(np.repeat(se[q * d + 2 * q:], es)),
+                  _t(se[q * d + q:q * d + 2 * q]))
+        return LaplaceResult(H, ev, cov, stderr)
 
     def fit(self, verbose=False):
         """scipy L-BFGS-B with default options on the unconstrained vector (lcgp.py:537-540).

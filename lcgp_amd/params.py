@@ -43,6 +43,13 @@ class SoftClip:
         u = np.asarray(u, F64)
         return self._c * _sigmoid(self._w - _softplus(u - self.low)) * _sigmoid(u - self.low)
 
+    def d2forward(self, u):
+        """second derivative of forward(): with t = u - low, a = w - softplus(t), dforward = c sigmoid(a) sigmoid(t) and
+        d2forward = dforward ((1 - sigmoid(t)) - (1 - sigmoid(a)) sigmoid(t))   (the chain rule of the parameter Hessian)"""
+        u = np.asarray(u, F64)
+        st, sa = _sigmoid(u - self.low), _sigmoid(self._w - _softplus(u - self.low))
+        return self._c * sa * st * ((1.0 - st) - (1.0 - sa) * st)
+
 
 def softclip_flat(u, lo, hi, w, c):
     """SoftClip.forward and SoftClip.dforward of a FLAT vector whose elements have their own bounds (arrays lo, hi, w = hi - lo,
@@ -51,6 +58,16 @@ def softclip_flat(u, lo, hi, w, c):
     t = u - lo
     a = w - _softplus(t)
     return hi - c * _softplus(a), c * _sigmoid(a) * _sigmoid(t)
+
+
+def softclip_flat2(u, lo, hi, w, c):
+    """SoftClip.dforward and SoftClip.d2forward of a flat vector with per-element bounds (the arrays of softclip_flat): the
+    Jacobian and the curvature of the constrained -> unconstrained map of LCGP.loss_hessian.  Element by element the same
+    operations as the two methods."""
+    t = u - lo
+    st, sa = _sigmoid(t), _sigmoid(w - _softplus(t))
+    j = c * sa * st
+    return j, j * ((1.0 - st) - (1.0 - sa) * st)
 
 
 class Identity:
@@ -65,6 +82,9 @@ class Identity:
 
     def dforward(self, u):
         return np.ones_like(np.asarray(u, F64))
+
+    def d2forward(self, u):
+        return np.zeros_like(np.asarray(u, F64))
 
 
 class _Variable:

@@ -324,6 +324,37 @@ int lcgp_predict_hess(void* stream, int dtype, int kernel_id, int n, int d, int 
                       double* d2ghat, double* d2gvar,    /* q_local x n0 x d (d + 1) / 2, row k at k * out_stride * d (d + 1) / 2 */
                       int out_stride);
 
+/* Posterior covariance of the latent GRADIENT at new inputs, and its weighted sum over them (no counterpart in the reference).
+ * With X_k, W_k as above and the rows P_il of lcgp_predict_hess, for local component k, new input i (standardised) and
+ * dimensions l, m: the posterior covariance function Sigma_k(x, x') = c_k(x, x') - D_k X_k(x) W_k^T W_k X_k(x')^T of the
+ * continuous surface (no nugget term: a point mass has no derivative, as in lcgp_predict_grad) differentiated once in each
+ * argument at x = x' = x0_i:
+ *     Gamma[k, i, l, m] = delta_lm c_k kappa / ell_l^2 - D_k (P_il . P_im) / (ell_l ell_m)
+ *     c_k = scale_k (1 - nug_k / (1 + nug_k)), the continuous part of the prior variance;  kappa = -f''(0) of the 1-D factor:
+ *     1 (Matern-3/2), 1 (SE), 1 / 3 (Matern-5/2).  f'(0) = 0 for all three, so the prior part is diagonal.
+ *     dghat[k, i, l] BITWISE that of lcgp_predict_grad (its contraction without the variance half; V_k is not formed).
+ *     M[k, l, m]    += sum_i w_i Gamma[k, i, l, m]            when w is given
+ * Launches: the mean half of lcgp_predict_grad's contraction, the rows d_l X_i and P as in lcgp_predict_hess, then one wave per
+ * (new input, 4 x 4 block of dimension pairs) for the dot products and Gamma; with w, every workgroup leaves its weighted
+ * sum in the scratch and a second launch adds them to M in index order (no atomics).
+ * scratch: lcgp_predict_gradcov_scratch_bytes(dtype, n, d, q_local, n0) bytes = 2 q_local rpad npad elements, rpad = n0 d rounded
+ *   up to 128 (to 64 below 128): less than lcgp_predict_hess_scratch_bytes.  n0 d <= LCGP_HESS_MAX_ROWS.
+ * Outputs: dghat as in lcgp_predict_grad; gamma q_local x n0 x d (d + 1) / 2 packed as d2gvar is, or NULL with w given: the
+ *   per-point tensor is then never written.  w: n0 doubles on the device or NULL.  M: q_local x d (d + 1) / 2, contiguous,
+ *   ADDED to (a caller that passes the new inputs in chunks carries it across calls and zeroes it first); required with w.
+ * dghat and gamma are bitwise reproducible, independent of q_local, of w, of the scratch content on entry and, between calls
+ * that use the same tile size for P (rpad a multiple of 128 or not), of how a caller splits the new inputs; M is bitwise
+ * reproducible for the same split and does not depend on whether gamma is written. */
+int lcgp_predict_gradcov_scratch_bytes(int dtype, int n, int d, int q_local, int n0, size_t* bytes /*host out*/);
+int lcgp_predict_gradcov(void* stream, int dtype, int kernel_id, int n, int d, int p, int q_local,
+                         const void* x, const void* sr, const double* theta, const void* workspace,
+                         int n0, const void* x0, void* scratch,
+                         double* dghat,                  /* q_local x n0 x d, row k at k * out_stride * d */
+                         double* gamma,                  /* q_local x n0 x d (d + 1) / 2, row k at k * out_stride * d (d + 1) / 2; or NULL */
+                         const double* w,                /* n0 weights, or NULL */
+                         double* M,                      /* q_local x d (d + 1) / 2, added to; NULL without w */
+                         int out_stride);
+
 /* Joint posterior covariance over new inputs, and correlated draws (no counterpart in the reference: its predict is marginal
  * only).  For local component k and n0 new inputs x0 (standardised), with c0k, sr, L_k^-1 exactly as in lcgp_predict:
  *     Sigma_k = C00_k - D_k U_k U_k^T,   U_k = (c0k o sr^T) L_k^-T    (n0 x n),   diag(Sigma_k) = gvar[k, :] of lcgp_predict

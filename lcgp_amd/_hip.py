@@ -65,6 +65,8 @@ SIGNATURES = {
     "lcgp_predict_grad": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i]),
     "lcgp_predict_hess_scratch_bytes": (_i, [_i, _i, _i, _i, _i, C.POINTER(C.c_size_t)]),
     "lcgp_predict_hess": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i]),
+    "lcgp_predict_gradcov_scratch_bytes": (_i, [_i, _i, _i, _i, _i, C.POINTER(C.c_size_t)]),
+    "lcgp_predict_gradcov": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i]),
     "lcgp_predict_cov_scratch_bytes": (_i, [_i, _i, _i, _i, C.POINTER(C.c_size_t)]),
     "lcgp_predict_cov": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _d]),
     "lcgp_sample_scratch_bytes": (_i, [_i, _i, _i, _i, C.POINTER(C.c_size_t)]),

@@ -23,7 +23,7 @@
 #include "../../include/lcgp_hip.h"
 #include "fill_sched.h"
 
-#define LCGP_VERSION 600
+#define LCGP_VERSION 610
 
 namespace {
 
@@ -2671,7 +2671,8 @@ __global__ __launch_bounds__(64) void pred_reduce_kernel(const T* __restrict__ X
 // derivative for the 32 dimensions of chunk blockIdx.z (2 DD accumulators per lane, never 2 d).
 constexpr int PG_ROWS = 32, PG_SL = 8;
 // ZMAT (lcgp_variance_reduction_grad): z is a matrix laid out as V is (row i0 + i of slab k, row length npad), not the vector z_k.
-template <typename T, int DD, int KERN, bool ZMAT = false>
+// MEAN (lcgp_predict_gradcov): dghat alone, by the same operations in the same order; V and dgvar are not touched.
+template <typename T, int DD, int KERN, bool ZMAT = false, bool MEAN = false>
 __global__ __launch_bounds__(256) void pgrad_kernel(const T* __restrict__ x0, int n0, const T* __restrict__ x,
                                                     const T* __restrict__ sr, int n, int d, const double* __restrict__ theta,
                                                     int tw, const T* __restrict__ z, int npad, const T* __restrict__ V,
@@ -2682,7 +2683,7 @@ __global__ __launch_bounds__(256) void pgrad_kernel(const T* __restrict__ x0, in
                                                         // >= l0 + DD for every chunk (zeros beyond d)
     __shared__ double x0sh[PG_ROWS][XW];
     __shared__ double xsh[JT][XW];
-    __shared__ double vsh[PG_ROWS][JT + 1];
+    __shared__ double vsh[MEAN ? 1 : PG_ROWS][JT + 1];
     __shared__ double zsh[ZMAT ? PG_ROWS : 1][JT + 1];
     __shared__ double wz[JT], wsr[JT];
     __shared__ double th[DWIDE + 3];
@@ -2716,7 +2717,7 @@ __global__ __launch_bounds__(256) void pgrad_kernel(const T* __restrict__ x0, in
         }
         for (int e = tid; e < PG_ROWS * JT; e += 256) {
             const int i = e / JT, jj = e - i * JT;
-            vsh[i][jj] = (i0 + i < n0 && j0 + jj < n) ? (double)Vk[(size_t)(i0 + i) * npad + j0 + jj] : 0.0;
+            if constexpr (!MEAN) vsh[i][jj] = (i0 + i < n0 && j0 + jj < n) ? (double)Vk[(size_t)(i0 + i) * npad + j0 + jj] : 0.0;
             if constexpr (ZMAT) zsh[i][jj] = (i0 + i < n0 && j0 + jj < n) ? (double)zk[(size_t)(i0 + i) * npad + j0 + jj] : 0.0;
         }
         if (tid < JT) {
@@ -2750,7 +2751,7 @@ __global__ __launch_bounds__(256) void pgrad_kernel(const T* __restrict__ x0, in
                 for (int m = 0; m < DD; ++m) acc_c0(xi[m] - xsh[jj][m]);
             }
             const double c0 = c_off * kern_c0<KERN>(poly, ssum);
-            const double a = ZMAT ? c0 * wz[jj] * zsh[r][jj] : c0 * wz[jj], b = c0 * wsr[jj] * vsh[r][jj];
+            const double a = ZMAT ? c0 * wz[jj] * zsh[r][jj] : c0 * wz[jj], b = MEAN ? 0.0 : c0 * wsr[jj] * vsh[r][jj];
 #pragma unroll
             for (int l = 0; l < DD; ++l) {
                 const double s = WIDE ? x0sh[r][l0 + l] - xsh[jj][l0 + l] : xi[l] - xsh[jj][l];
@@ -2763,7 +2764,7 @@ __global__ __launch_bounds__(256) void pgrad_kernel(const T* __restrict__ x0, in
                     h = fma(s, sa, s) * fast_rcp(fma(sa, sa + 3.0, 3.0));
                 }
                 am[l] = fma(a, h, am[l]);
-                av[l] = fma(b, h, av[l]);
+                if constexpr (!MEAN) av[l] = fma(b, h, av[l]);
             }
         }
     }
@@ -2779,7 +2780,7 @@ __global__ __launch_bounds__(256) void pgrad_kernel(const T* __restrict__ x0, in
             const double tm = (red[0][0][r] + red[0][1][r]) + (red[0][2][r] + red[0][3][r]);
             const double tv = (red[1][0][r] + red[1][1][r]) + (red[1][2][r] + red[1][3][r]);
             dghat[orow + l0 + l] = -tm / th[l0 + l];
-            dgvar[orow + l0 + l] = 2.0 * D * tv / th[l0 + l];
+            if constexpr (!MEAN) dgvar[orow + l0 + l] = 2.0 * D * tv / th[l0 + l];
         }
         __syncthreads();
     }
@@ -4666,6 +4667,149 @@ int do_predict_hess(hipStream_t st, const Ws& w, const void* x, const void* sr, 
 }
 
 // ---------------------------------------------------------------------------------------------------
+// K9: posterior covariance of the latent gradient (lcgp_hip.h: lcgp_predict_gradcov).  For local component k,
+// new input i and dimensions m <= l, with the rows P of K8 (their factors -1 / ell left out):
+//   Gamma[k, i, lm] = (delta_lm c_k kappa - D_k P[i d + l] . P[i d + m]) / (ell_l ell_m),   c_k = scale (1 - nug / (1 + nug))
+//   M[k, lm]       += sum_i w_i Gamma[k, i, lm]
+// Launches: pgrad_kernel<MEAN> (dghat, bitwise that of K7), pdx_kernel, OP_PRED_U of the tile kernel, gradcov_kernel, and with
+// weights gradcov_reduce_kernel.  V_k = U_k W_k and the contractions over the training inputs of K8 are not needed.
+// ---------------------------------------------------------------------------------------------------
+
+// phess_gram_kernel's dot products for the block pair blockIdx.z, finished to Gamma: one wave per new input, the packed
+// lower triangle to `gamma` unless it is NULL.  With weights the four waves' w_i Gamma go through LDS and are summed in wave
+// order into part[k][blockIdx.x][lm]: every entry of the triangle by exactly one block pair.
+template <typename T>
+__global__ __launch_bounds__(256) void gradcov_kernel(const T* __restrict__ P, size_t slab, int ld, int n, int n0, int d,
+                                                      const double* __restrict__ theta, int tw, double kappa, int ldo,
+                                                      double* __restrict__ gamma, const double* __restrict__ w,
+                                                      double* __restrict__ part) {
+    constexpr int VN = SelVec<T>::N;
+    typedef typename SelVec<T>::v V;
+    __shared__ double red[4][PH_B * PH_B];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, i = blockIdx.x * 4 + wv, k = blockIdx.y;
+    const bool live = i < n0;                           // (uniform over the wave)
+    int lb, mb;
+    tri_decode(blockIdx.z, lb, mb);
+    const int l0 = lb * PH_B, m0 = mb * PH_B;
+    const size_t tri = (size_t)d * (d + 1) / 2;
+    const double* th = theta + (size_t)k * tw;
+    double acc[PH_B][PH_B];
+#pragma unroll
+    for (int a = 0; a < PH_B; ++a)
+#pragma unroll
+        for (int b = 0; b < PH_B; ++b) acc[a][b] = 0.0;
+    if (live) {
+        const T* base = P + (size_t)k * slab + (size_t)i * d * ld;
+        const T* ra[PH_B];
+        const T* rb[PH_B];
+#pragma unroll
+        for (int a = 0; a < PH_B; ++a) {                // (dimensions beyond d: row d - 1 again, never written out)
+            ra[a] = base + (size_t)min(l0 + a, d - 1) * ld;
+            rb[a] = base + (size_t)min(m0 + a, d - 1) * ld;
+        }
+        const int nv = n / VN;
+        for (int p = lane; p < nv; p += 64) {
+            V xa[PH_B], xb[PH_B];
+#pragma unroll
+            for (int a = 0; a < PH_B; ++a) {
+                xa[a] = *(const V*)(ra[a] + (size_t)p * VN);
+                xb[a] = *(const V*)(rb[a] + (size_t)p * VN);
+            }
+#pragma unroll
+            for (int a = 0; a < PH_B; ++a)
+#pragma unroll
+                for (int b = 0; b < PH_B; ++b)
+#pragma unroll
+                    for (int e = 0; e < VN; ++e) acc[a][b] = fma((double)xa[a][e], (double)xb[b][e], acc[a][b]);
+        }
+        const int tail = nv * VN + lane;
+        if (tail < n) {
+#pragma unroll
+            for (int a = 0; a < PH_B; ++a)
+#pragma unroll
+                for (int b = 0; b < PH_B; ++b) acc[a][b] = fma((double)ra[a][tail], (double)rb[b][tail], acc[a][b]);
+        }
+    }
+    const double scale = th[d], nug = th[d + 1], D = th[d + 2];
+    const double prior = scale * (1.0 - nug / (1.0 + nug)) * kappa;
+    const double wi = (w && live) ? w[i] : 0.0;
+    double* o = gamma ? gamma + ((size_t)k * ldo + (live ? i : 0)) * tri : nullptr;
+#pragma unroll
+    for (int a = 0; a < PH_B; ++a)
+#pragma unroll
+        for (int b = 0; b < PH_B; ++b) {
+            const double s = wave_sum(acc[a][b]);
+            const int l = l0 + a, m = m0 + b;
+            double g = 0.0;
+            if (live && l < d && m <= l) {
+                g = ((l == m ? prior : 0.0) - D * s) / (th[l] * th[m]);
+                if (lane == 0 && o) o[l * (l + 1) / 2 + m] = g;
+            }
+            if (lane == 0) red[wv][a * PH_B + b] = wi * g;
+        }
+    if (!w) return;                                     // (uniform over the launch)
+    __syncthreads();
+    const int t = threadIdx.x;
+    if (t < PH_B * PH_B) {
+        const int l = l0 + t / PH_B, m = m0 + t % PH_B;
+        if (l < d && m <= l)
+            part[((size_t)k * gridDim.x + blockIdx.x) * tri + (size_t)(l * (l + 1) / 2 + m)] =
+                ((red[0][t] + red[1][t]) + red[2][t]) + red[3][t];
+    }
+}
+
+// M[k][e] += the nwg partial sums of gradcov_kernel in ascending workgroup order
+__global__ __launch_bounds__(256) void gradcov_reduce_kernel(const double* __restrict__ part, int nwg, int tri,
+                                                             double* __restrict__ M) {
+    const int e = blockIdx.x * 256 + threadIdx.x, k = blockIdx.y;
+    if (e >= tri) return;
+    const double* p = part + (size_t)k * nwg * tri + e;
+    double s = 0.0;
+    for (int g = 0; g < nwg; ++g) s += p[(size_t)g * tri];
+    M[(size_t)k * tri + e] += s;
+}
+
+inline double gradcov_kappa(int kern) { return kern == LCGP_KERNEL_MATERN52 ? 1.0 / 3.0 : 1.0; }
+
+// K9 for all local components.  Scratch: DX and P (q slabs rows_pad x npad each); once P is formed the DX slabs are free
+// and take the per-workgroup partial sums (q ceil(n0 / 4) tri doubles <= 508 q n0 d bytes < q rows_pad npad elements).
+template <typename T>
+int do_predict_gradcov(hipStream_t st, const Ws& w, const void* x, const void* sr, const double* theta, int n0, const void* x0,
+                       void* scratch, double* dghat, double* gamma, const double* wt, double* M, int ldo) {
+    const int rows_pad = hess_rows_pad(n0, w.d), tw = w.d + 3 + w.p;
+    const size_t dslab = (size_t)rows_pad * w.npad;
+    T* DX = (T*)scratch;
+    T* P = DX + dslab * w.q;
+    const int wide = w.d > 16;
+    dim3 pgrid((n0 + PG_ROWS - 1) / PG_ROWS, w.q, wide ? (w.d + DMAX - 1) / DMAX : 1);
+    for_dim(w.d, [&](auto dd) {
+        for_kern(w.kern, [&](auto kern) {
+            hipLaunchKernelGGL((pgrad_kernel<T, decltype(dd)::value, decltype(kern)::value, false, true>), pgrid, dim3(256), 0, st,
+                               (const T*)x0, n0, (const T*)x, (const T*)sr, w.n, w.d, theta, tw, (const T*)(w.base + w.off_z),
+                               w.npad, (const T*)nullptr, (size_t)0, ldo, dghat, (double*)nullptr);
+        });
+    });
+    CHECK_LAUNCH("pgrad_kernel");
+    for_kern(w.kern, [&](auto kern) {
+        hipLaunchKernelGGL((pdx_kernel<T, decltype(kern)::value>), dim3(w.nb, (n0 + PH_PTS - 1) / PH_PTS, w.q), dim3(256), 0, st,
+                           DX, dslab, w.npad, n0, w.n, w.d, rows_pad, (const T*)x0, (const T*)x, (const T*)sr, theta, tw);
+    });
+    CHECK_LAUNCH("pdx_kernel");
+    int rc = launch_pred<T, OP_PRED_U>(st, DX, (const T*)(w.base + w.off_W), P, dslab, w.mat, w.npad, rows_pad, w.nb, w.q);
+    if (rc) return rc;
+    const int nblk = (w.d + PH_B - 1) / PH_B, npair = nblk * (nblk + 1) / 2, nwg = (n0 + 3) / 4, tri = w.d * (w.d + 1) / 2;
+    double* part = (double*)scratch;
+    hipLaunchKernelGGL((gradcov_kernel<T>), dim3(nwg, w.q, npair), dim3(256), 0, st, (const T*)P, dslab, w.npad, w.n, n0, w.d,
+                       theta, tw, gradcov_kappa(w.kern), ldo, gamma, wt, part);
+    CHECK_LAUNCH("gradcov_kernel");
+    if (wt) {
+        hipLaunchKernelGGL(gradcov_reduce_kernel, dim3((tri + 255) / 256, w.q), dim3(256), 0, st, (const double*)part, nwg, tri, M);
+        CHECK_LAUNCH("gradcov_reduce_kernel");
+    }
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------
 // Hessian of the objective in the parameters (lcgp_hip.h: lcgp_nll_hess; no counterpart in the reference, whose
 // users would nest two gradient tapes around neglpost).  float64 only.  Runs behind lcgp_nll_grad at the same theta and only
 // READS the workspace (A^-1 lower tiles, b, z).  Per component, m = d + 2 kernel parameters [ell_0 .. ell_{d-1}, scale, nug]:
@@ -5513,6 +5657,35 @@ int lcgp_predict_hess(void* stream, int dtype, int kernel_id, int n, int d, int 
     return dtype == LCGP_F64
                ? do_predict_hess<double>(st, w, x, sr, theta, n0, x0, scratch, ghat, gvar, dghat, dgvar, d2ghat, d2gvar, ldo)
                : do_predict_hess<float>(st, w, x, sr, theta, n0, x0, scratch, ghat, gvar, dghat, dgvar, d2ghat, d2gvar, ldo);
+}
+
+int lcgp_predict_gradcov_scratch_bytes(int dtype, int n, int d, int q_local, int n0, size_t* bytes) {
+    if (dtype != LCGP_F64 && dtype != LCGP_F32) return bad("dtype must be 0 (f64) or 1 (f32)");
+    if (n < 1 || n0 < 1 || q_local < 1) return bad("n, n0, q_local must be >= 1");
+    if (d < 1 || d > DWIDE) return bad("d must be in [1, 126]");
+    if ((long long)n0 * d > LCGP_HESS_MAX_ROWS) return bad("n0 * d must be <= LCGP_HESS_MAX_ROWS: pass the new inputs in chunks");
+    if (!bytes) return bad("bytes is NULL");
+    *bytes = 2 * (size_t)q_local * hess_rows_pad(n0, d) * round_up(n, 2 * TS) * (dtype == LCGP_F64 ? 8 : 4);
+    return 0;
+}
+
+int lcgp_predict_gradcov(void* stream, int dtype, int kernel_id, int n, int d, int p, int q_local, const void* x, const void* sr,
+                         const double* theta, const void* workspace, int n0, const void* x0, void* scratch, double* dghat,
+                         double* gamma, const double* w, double* M, int out_stride) {
+    int rc = check_common(dtype, n, d, p, q_local, kernel_id);
+    if (rc) return rc;
+    if (n0 < 1) return bad("n0 < 1");
+    if ((long long)n0 * d > LCGP_HESS_MAX_ROWS) return bad("n0 * d must be <= LCGP_HESS_MAX_ROWS: pass the new inputs in chunks");
+    if (!x || !theta || !workspace || !x0 || !scratch || !dghat) return bad("NULL pointer");
+    if (!gamma && !w) return bad("NULL pointer: gamma may only be NULL when w is given");
+    if ((w != nullptr) != (M != nullptr)) return bad("w and M go together: both or neither");
+    if (out_stride != 0 && out_stride < n0) return bad("out_stride must be 0 (= n0) or >= n0");
+    const int ldo = out_stride ? out_stride : n0;
+    Ws ws = carve(dtype, n, d, p, q_local, (void*)workspace);
+    ws.kern = kernel_id;
+    hipStream_t st = (hipStream_t)stream;
+    return dtype == LCGP_F64 ? do_predict_gradcov<double>(st, ws, x, sr, theta, n0, x0, scratch, dghat, gamma, w, M, ldo)
+                             : do_predict_gradcov<float>(st, ws, x, sr, theta, n0, x0, scratch, dghat, gamma, w, M, ldo);
 }
 
 int lcgp_predict_cov_scratch_bytes(int dtype, int n, int q_local, int n0, size_t* bytes) {

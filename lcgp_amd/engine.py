@@ -295,6 +295,58 @@ class HotPathEngine:
                                                       wsp, m, x0p, scp, *ptrs, n0), "lcgp_predict_hess")
             return out, jac, hess
 
+    def grad_cov_block(self, x0s, w=None, per_point=True):
+        """(dghat, gamma, M) float64 DEVICE tensors for standardised x0s, from the factorisation of the last evaluate()
+        (lcgp_predict_gradcov): dghat (q_local, n0, d) bitwise that of predict_grad_block(x0s); gamma (q_local, n0, d (d + 1)
+        / 2), the packed lower triangles (entry (l, m <= l) at l (l + 1) / 2 + m) of the posterior covariance of the latent
+        gradient at each new input, or None with per_point=False (w is then required and the per-point tensor is never
+        formed); M (q_local, d (d + 1) / 2) = sum_i w_i gamma[:, i] for n0 weights w, reduced on the device in a fixed order,
+        or None without w.  Chunked as predict_hess_block is (at most PREDICT_CHUNK rows of P per pass, never fewer than 128
+        new inputs while n0 has them, a short last pass moved back so that P is formed on 128-row tiles in every pass of a
+        call with several): dghat and gamma are bitwise independent of PREDICT_CHUNK.  The rows a moved-back pass repeats
+        weigh zero in it.  The scratch holds 2 q_local (chunk d)_pad npad elements; raises ValueError when it does not fit in
+        the free device memory."""
+        torch = self.torch
+        if self._theta_last is None:
+            raise RuntimeError("predict_grad_cov() needs a preceding evaluate() at the current parameters")
+        x0s = np.ascontiguousarray(x0s, np.float64)
+        n0, d = x0s.shape[0], self.d
+        assert x0s.ndim == 2 and x0s.shape[1] == d and n0 >= 1
+        if w is None and not per_point:
+            raise ValueError("grad_cov_block: per_point=False needs weights")
+        tri = d * (d + 1) // 2
+        chunk = min(n0, max(128, PREDICT_CHUNK // d))
+        with torch.cuda.device(self.device):
+            x0d = torch.as_tensor(x0s).to(self.device, self.tdtype).contiguous()
+            nbytes = self._nbytes("lcgp_predict_gradcov_scratch_bytes", self.dtype, self.n, d, self.q_local, chunk)
+            scp = self._p(self._grow_scratch(nbytes, ("the gradient covariances of %d new inputs per pass" % chunk,
+                                                      "%d components of %d x n, twice" % (self.q_local, chunk * d),
+                                                      "lower lcgp_amd.engine.PREDICT_CHUNK")))
+            dghat = torch.empty((self.q_local, n0, d), dtype=torch.float64, device=self.device)
+            gamma = torch.empty((self.q_local, n0, tri), dtype=torch.float64, device=self.device) if per_point else None
+            M = wd = None
+            if w is not None:
+                w = np.ascontiguousarray(w, np.float64).reshape(-1)
+                assert w.shape == (n0,)
+                wd = torch.as_tensor(w).to(self.device)
+                M = torch.zeros((self.q_local, tri), dtype=torch.float64, device=self.device)
+            st, xp, srp, thp, wsp = self._stream(), self._p(self.x), self._p(self.sr), self._p(self.theta_dev), self._p(self.workspace)
+            for lo in range(0, n0, chunk):
+                m = min(chunk, n0 - lo)
+                wp = None if wd is None else C.c_void_p(wd.data_ptr() + 8 * lo)
+                if m < 128 <= n0:
+                    if wd is not None:                  # the rows n0 - 128 .. lo were summed by the pass before
+                        wl = wd[n0 - 128:].clone()
+                        wl[:lo - (n0 - 128)] = 0.0
+                        wp = self._p(wl)
+                    lo, m = n0 - 128, 128
+                x0p = C.c_void_p(x0d.data_ptr() + lo * d * x0d.element_size())
+                _hip.check(self.lib.lcgp_predict_gradcov(
+                    st, self.dtype, self.kernel_id, self.n, d, self.p, self.q_local, xp, srp, thp, wsp, m, x0p, scp,
+                    C.c_void_p(dghat.data_ptr() + 8 * lo * d), None if gamma is None else C.c_void_p(gamma.data_ptr() + 8 * lo * tri),
+                    wp, None if M is None else self._p(M), n0), "lcgp_predict_gradcov")
+            return dghat, gamma, M
+
     def predict_device(self, x0s, same=False):
         """ghat, gvar (q_local, n0): the two halves of predict_block()"""
         out = self.predict_block(x0s, same)

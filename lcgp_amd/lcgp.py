@@ -177,6 +177,21 @@ class LaplaceResult:
         return "LaplaceResult(P=%d, eigenvalues in [%.3e, %.3e])" % (len(self.eigenvalues), self.eigenvalues[0], self.eigenvalues[-1])
 
 
+class ActiveSubspace:
+    """What LCGP.active_subspace() returns, per selected output a (CPU float64 tensors): `matrix` (p_sel, d, d), the posterior
+    expectation of sum_i w_i grad f_a grad f_a^T over the reference points, = `mean_part` (the gradients of the predictive
+    mean) + `cov_part` (the emulator's own uncertainty about the gradient); `activity` (p_sel, d), its diagonal: the
+    posterior-expected derivative-based sensitivity nu_l = E[(d f_a / d x_l)^2]; `eigenvalues` (p_sel, d), descending, and
+    `eigenvectors` (p_sel, d, d) in columns, the largest-magnitude entry of each positive."""
+
+    def __init__(self, matrix, mean_part, cov_part, activity, eigenvalues, eigenvectors):
+        self.matrix, self.mean_part, self.cov_part = matrix, mean_part, cov_part
+        self.activity, self.eigenvalues, self.eigenvectors = activity, eigenvalues, eigenvectors
+
+    def __repr__(self):
+        return "ActiveSubspace(outputs=%d, d=%d)" % tuple(self.activity.shape)
+
+
 class LCGP:
     """
     Latent Component Gaussian Process (LCGP), MI355X hot path.
@@ -1573,6 +1588,110 @@ class LCGP:
         _, _, _, _, d2ghat, d2gvar = self._latent_predict_hess(x0)
         d2yp, d2ycv = self._output_hessians(d2ghat, d2gvar)
         return _t(d2yp), _t(d2ycv.copy()), _t(d2ycv)
+
+    # =============================================================================================
+    # posterior covariance of the gradient and active subspaces (no counterpart in the reference)
+    # =============================================================================================
+    @staticmethod
+    def _unpack_lower(packed, d):
+        """(..., d (d + 1) / 2) packed lower triangles -> (..., d, d), mirrored: exactly symmetric"""
+        il, im = np.tril_indices(d)
+        full = np.empty(packed.shape[:-1] + (d, d), F64)
+        full[..., il, im] = packed
+        full[..., im, il] = packed
+        return full
+
+    def _x0_2d(self, x0, name):
+        x0n = _np(self._verify_data_types(x0))
+        if x0n.ndim != 2 or x0n.shape[1] != int(self.d) or x0n.shape[0] < 1:
+            raise ValueError('%s must have shape (n, %d), got %s' % (name, int(self.d), tuple(x0n.shape)))
+        return self._standardise_x0(x0n)[0]
+
+    def predict_grad_cov(self, x0, latent=False):
+        """Posterior covariance of the gradient of the noise-free output at each new input, the counterpart of yconfvar for
+        predict_grad()'s dypred:
+            cov[a, i, l, m] = Cov(d y_a / d x0[i, l], d y_a / d x0[i, m])
+                            = scale_a^2 sum_k W[k, a]^2 Gamma_k[i, l, m] / (range_l range_m)          (p, n0, d, d)
+            Gamma_k[i, l, m] = delta_lm c_k kappa / ell_l^2 - D_k (P_il . P_im) / (ell_l ell_m)
+        on the raw input and output scales (W, scale: those of predict(); range = x_max - x_min), CPU float64, exactly
+        symmetric.  Gamma_k is the posterior covariance function of latent component k differentiated once in each argument:
+        c_k = scale_k (1 - nug_k / (1 + nug_k)) is the continuous part of the prior variance (the nugget is a point mass with
+        no derivative: the convention of predict_grad), kappa = 1 (Matern-3/2, SE) or 1 / 3 (Matern-5/2), P_il the rows of
+        predict_hess().  latent=True returns Gamma (q, n0, d, d) in standardised inputs.  One pass on the GPU from the
+        factorisation of the current parameters (lcgp_predict_gradcov), in the engine's dtype.  Sets self.dghat to what
+        predict_grad(x0) sets."""
+        x0s = self._x0_2d(x0, 'x0')
+        n0, d = x0s.shape
+        tri = d * (d + 1) // 2
+        eng = self._ensure_aux()
+        loc = None
+        if eng is not None:
+            dghat, gamma, _ = eng.grad_cov_block(x0s)
+            loc = torch.cat([dghat.reshape(dghat.shape[0], -1), gamma.reshape(gamma.shape[0], -1)], dim=1)
+        both = self._gather_components(loc, (n0 * (d + tri),))
+        q = int(self.q)
+        self.dghat = _t(both[:, :n0 * d].reshape(q, n0, d))
+        G = self._unpack_lower(both[:, n0 * d:].reshape(q, n0, tri), d)
+        if latent:
+            return _t(G)
+        W, _, scale, _ = self._output_map()
+        rng = (_np(self.x_max) - _np(self.x_min)).reshape(-1)
+        cov = np.einsum('ka,kilm->ailm', W ** 2, G) * (scale ** 2)[:, None, None, None] / (rng[:, None] * rng[None, :])
+        return _t(cov)
+
+    def active_subspace(self, x_ref, weights=None, outputs=None):
+        """Active-subspace matrix of each selected output over a reference sample, with the emulator's uncertainty included:
+            C_a = sum_i w_i E[grad y_a grad y_a^T at x_ref[i]] = sum_i w_i grad ypred_a grad ypred_a^T + sum_i w_i predict_grad_cov
+        (the posterior expectation of an outer product is the outer product of the means plus the covariance).  Returns an
+        ActiveSubspace: matrix = mean_part + cov_part (p_sel, d, d), activity = its diagonal (the expected derivative-based
+        global sensitivity measures nu_l, which bound the total Sobol indices from above), eigenvalues (descending) and
+        eigenvectors (columns).  A cov_part that is not small beside mean_part says more runs may change the ranking.
+          x_ref: (n_ref, d) raw-scale sample of the input distribution.  weights: n_ref non-negative weights, normalised to
+          sum 1 (default uniform), as in variance_reduction().  outputs: output indices (default all p).
+        The weighted sum of the covariances is reduced on the GPU (the n_ref x d x d tensor is never formed); the mean part is
+        formed on the host from the gathered latent gradients, n_ref x d per component."""
+        x0s = self._x0_2d(x_ref, 'x_ref')
+        n0, d = x0s.shape
+        if weights is None:
+            w = np.full(n0, 1.0 / n0)
+        else:
+            w = np.asarray(weights, F64).reshape(-1)
+            if w.shape != (n0,):
+                raise ValueError('weights must have length n_ref = %d, got %d' % (n0, w.size))
+            if not np.all(np.isfinite(w)) or np.any(w < 0):
+                raise ValueError('weights must be finite and non-negative')
+            if not np.any(w > 0):
+                raise ValueError('weights must not all be zero')
+            w = w / np.sum(w)
+        p = int(self.p)
+        outputs = list(range(p)) if outputs is None else [int(a) for a in np.atleast_1d(outputs)]
+        if any(a < 0 or a >= p for a in outputs):
+            raise ValueError('outputs must be indices in [0, %d)' % p)
+        tri = d * (d + 1) // 2
+        eng = self._ensure_aux()
+        loc = None
+        if eng is not None:
+            dghat, _, M = eng.grad_cov_block(x0s, w, per_point=False)
+            loc = torch.cat([dghat.reshape(dghat.shape[0], -1), M], dim=1)
+        both = self._gather_components(loc, (n0 * d + tri,))
+        q = int(self.q)
+        dghat = both[:, :n0 * d].reshape(q, n0, d)
+        Mk = self._unpack_lower(both[:, n0 * d:], d)
+        W, _, scale, _ = self._output_map()
+        W, scale = W[:, outputs], scale[outputs]
+        rng = (_np(self.x_max) - _np(self.x_min)).reshape(-1)
+        grad = np.einsum('ka,kil->ail', W, dghat) * scale[:, None, None] / rng[None, None, :]
+        mean_part = np.einsum('i,ail,aim->alm', w, grad, grad)
+        mean_part = 0.5 * (mean_part + np.swapaxes(mean_part, -1, -2))
+        cov_part = np.einsum('ka,klm->alm', W ** 2, Mk) * (scale ** 2)[:, None, None] / (rng[:, None] * rng[None, :])
+        matrix = mean_part + cov_part
+        lam, vec = np.linalg.eigh(matrix)
+        lam, vec = lam[:, ::-1].copy(), vec[:, :, ::-1].copy()
+        big = np.argmax(np.abs(vec), axis=1)                            # (p_sel, d): row of the largest entry per column
+        sign = np.sign(np.take_along_axis(vec, big[:, None, :], axis=1))
+        vec = vec * np.where(sign == 0, 1.0, sign)
+        activity = np.diagonal(matrix, axis1=-2, axis2=-1).copy()
+        return ActiveSubspace(_t(matrix), _t(mean_part), _t(cov_part), _t(activity), _t(lam), _t(vec))
 
     # ---- cache views the reference keeps as attributes (materialised from the device only when read) ----
     def _fetch_all(self, fn, width):

@@ -262,6 +262,30 @@ int lcgp_predict(void* stream, int dtype, int kernel_id, int n, int d, int p, in
                  int n0, const void* x0, int same, void* scratch,
                  double* ghat /*q_local rows of n0*/, double* gvar /*q_local rows of n0*/, int out_stride);
 
+/* Box-averaged predictions (no counterpart in the reference): the posterior mean and variance of latent component k AVERAGED
+ * over a subset of the inputs, uniform on the box [lo_l, hi_l] (standardised inputs, hi_l > lo_l).  Row i of x0 carries a mask
+ * (mask[i d + l] != 0: dimension l is integrated out; the entry x0[i, l] is then never read, a NaN there does not matter).
+ * For the three product kernels the average of the cross-covariance row is a product of 1-D integrals of the kernel factor
+ * kappa(u), u = |t - x| / ell (F(b) = int_0^b kappa, G(b) = int_0^b u kappa(u) du, in closed form):
+ *     I1[k, l, j] = (ell / w) [sgn(x_jl - lo) F(|x_jl - lo| / ell) + sgn(hi - x_jl) F(|hi - x_jl| / ell)]     (w = hi_l - lo_l)
+ *     I2[k, l]    = 2 ell [w F(a) - ell G(a)] / w^2,   a = w / ell                                        (ell = ell_kl)
+ *     Xbar_k[i, j] = scale_k (1 - nt_k) prod_{l not in mask_i} kappa(|x0_il - x_jl| / ell_kl) prod_{l in mask_i} I1[k, l, j] sr_j
+ *     ghat[k, i] = Xbar_k[i, :] z_k          gvar[k, i] = prior_ki - D_k |Xbar_k[i, :] W_k^T|^2
+ *     prior_ki = scale_k (1 - nt_k) prod_{l in mask_i} I2[k, l]  (ascending l; nt = nug / (1 + nug): the nugget is white noise
+ *     whose average over a set of positive measure vanishes);  a row with an EMPTY mask has prior scale_k and is bitwise the
+ *     row of lcgp_predict(..., same = 0, ...) when both are formed on the same tile size (n0 below 128 in both, or not).
+ * Launches: one writes the table I1 (q_local d npad doubles) and I2 into the scratch, the rows are formed by the kernel of
+ * lcgp_predict compiled with the mask and table as extra inputs, then U = Xbar W^T on the tile kernel and the row reductions
+ * as in lcgp_predict.  Summation order fixed, no atomics: results are bitwise reproducible and independent of q_local, of the
+ * scratch content on entry and, between calls that use the same tile size, of how a caller splits the rows.
+ * mask: device, n0 x d bytes.  box: device, 2 d doubles, lo then hi.
+ * scratch: lcgp_predict_marginal_scratch_bytes(dtype, n, d, q_local, n0) = lcgp_predict_scratch_bytes + 8 q_local d (npad + 1). */
+int lcgp_predict_marginal_scratch_bytes(int dtype, int n, int d, int q_local, int n0, size_t* bytes /*host out*/);
+int lcgp_predict_marginal(void* stream, int dtype, int kernel_id, int n, int d, int p, int q_local,
+                          const void* x, const void* sr, const double* theta, const void* workspace,
+                          int n0, const void* x0, const unsigned char* mask, const double* box, void* scratch,
+                          double* ghat /*q_local rows of n0*/, double* gvar /*q_local rows of n0*/, int out_stride);
+
 /* Input gradients of the prediction (the reference gets them by a tf.GradientTape around predict, lcgp.py:808-930 with
  * covmat.py:31-55; this entry point replaces that tape).  All derivatives are with respect to the STANDARDISED inputs x0s;
  * output row i depends only on row i of x0, so the Jacobian is per point.  With X_k = c0k o sr^T, W_k = L_k^-1, U_k = X_k W_k^T,

@@ -375,7 +375,18 @@ __global__ __launch_bounds__(256) void build_kernel(T* __restrict__ M, size_t ma
 // Parameters come either by value (host call, lcgp_matern32) or from a device theta row (predict).
 struct ThetaArg { double v[DWIDE + 2]; };
 
-template <typename T, int KERN>
+// MARG (lcgp_predict_marginal; the instances with the two extra arguments mask and tab): row i of x1 carries a mask of
+// INTEGRATED dimensions (mask[i d + l] != 0, n1 x d bytes).  Such a dimension's entry of x1 is never loaded; its factor is
+// the box average of the 1-D kernel factor at the training input, read from the table tab[(k d + l) n2pad + j]
+// (marg_table_kernel) and multiplied into poly; ssum is left alone.  Rows with an empty mask go through exactly the operations
+// of the plain kernel.  Every MARG statement sits behind `if constexpr`, and the plain instances have an empty pack: the
+// signature and the code lcgp_predict and the others launch are those of the kernel without the variant.
+__device__ __forceinline__ void marg_args(const unsigned char*& mask, const double*& tab, const unsigned char* m, const double* t) {
+    mask = m;
+    tab = t;
+}
+
+template <typename T, int KERN, typename... EX>
 __global__ __launch_bounds__(256) void cross_kernel(T* __restrict__ out, int ldo, int n1, int n2, int d,
                                                     const T* __restrict__ x1, const T* __restrict__ x2,
                                                     ThetaArg tv, const double* __restrict__ thp /*ell[d], scale, nug*/,
@@ -383,11 +394,18 @@ __global__ __launch_bounds__(256) void cross_kernel(T* __restrict__ out, int ldo
                                                     int th_stride /*doubles between the theta rows of components*/,
                                                     size_t out_stride /*elements between the output slabs*/,
                                                     const int* __restrict__ match /*per row of x1: the column of its nugget
-                                                                                    term, -1 = none; NULL: `same` decides*/) {
+                                                                                    term, -1 = none; NULL: `same` decides*/,
+                                                    EX... ex /*MARG: const unsigned char* mask, const double* tab*/) {
+    constexpr bool MARG = sizeof...(EX) != 0;
+    const unsigned char* mask = nullptr;
+    const double* tab = nullptr;
+    if constexpr (MARG) marg_args(mask, tab, ex...);
     __shared__ double xr[TS][DMAX + 1];
     __shared__ double xc[TS][DMAX + 1];
     __shared__ double cs[TS];
     __shared__ double th[DWIDE + 2];
+    __shared__ double tb[MARG ? DMAX : 1][MARG ? TS : 1];            // the table's entries of this chunk and column tile
+    __shared__ unsigned char mr[MARG ? TS : 1][MARG ? DMAX : 1];     // the masks of this row tile, this chunk
     const int r = blockIdx.y, c = blockIdx.x;
     const int tid = threadIdx.x;
     if (thp) thp += (size_t)blockIdx.z * th_stride;
@@ -411,14 +429,29 @@ __global__ __launch_bounds__(256) void cross_kernel(T* __restrict__ out, int ldo
         for (int e = tid; e < TS * dc; e += 256) {
             int i = e / dc, jj = e - i * dc;
             int gi = r * TS + i, gjj = c * TS + i;
-            xr[i][jj] = gi < n1 ? (double)x1[(size_t)gi * d + d0 + jj] / th[d0 + jj] : 0.0;
+            if constexpr (MARG) {
+                const bool mk = gi < n1 && mask[(size_t)gi * d + d0 + jj] != 0;
+                mr[i][jj] = mk;
+                xr[i][jj] = (gi < n1 && !mk) ? (double)x1[(size_t)gi * d + d0 + jj] / th[d0 + jj] : 0.0;
+            } else {
+                xr[i][jj] = gi < n1 ? (double)x1[(size_t)gi * d + d0 + jj] / th[d0 + jj] : 0.0;
+            }
             xc[i][jj] = gjj < n2 ? (double)x2[(size_t)gjj * d + d0 + jj] / th[d0 + jj] : 0.0;
+        }
+        if constexpr (MARG) {
+            for (int e = tid; e < TS * dc; e += 256) {       // (c TS + t < n2pad: the grid has n2pad / TS column tiles)
+                const int jj = e / TS, t = e - jj * TS;
+                tb[jj][t] = tab[((size_t)blockIdx.z * d + d0 + jj) * n2pad + c * TS + t];
+            }
         }
         __syncthreads();
 #pragma unroll
         for (int m = 0; m < 16; ++m) {
             const int i = (tid >> 6) * 16 + m;
             for (int jj = 0; jj < dc; ++jj) {
+                if constexpr (MARG) {
+                    if (mr[i][jj]) { poly[m] *= tb[jj][j]; continue; }      // (uniform over the wave: i is)
+                }
                 if constexpr (KERN == 0) {
                     double sd = fabs(xr[i][jj] - xc[j][jj]);
                     poly[m] *= 1.0 + sd;
@@ -450,6 +483,95 @@ __global__ __launch_bounds__(256) void cross_kernel(T* __restrict__ out, int ldo
         }
         out[(size_t)gi * ldo + gj] = (T)v;
     }
+}
+
+// ---------------------------------------------------------------------------------------------------
+// Box averages of the 1-D kernel factors (lcgp_predict_marginal).  kappa(u), u = |t - x| / ell:  (1 + u) e^-u (Matern-3/2),
+// e^(-u^2 / 2) (SE), (1 + u + u^2 / 3) e^-u (Matern-5/2).  F(b) = int_0^b kappa, G(b) = int_0^b u kappa(u) du, Fc(b) =
+// int_b^inf kappa.  The closed forms of the Matern pair subtract O(1) terms that cancel for small b (G ~ b^2 / 2), so below
+// b = 1/2 both are summed from the Taylor series of kappa, kappa(u) = sum_m f(m) (-u)^m / m! with f(m) = 1 - m (Matern-3/2)
+// and (m - 1)(m - 3) / 3 (Matern-5/2): 20 terms, the first one left out is below 1e-24.  SE: erf and expm1, no cancellation.
+// ---------------------------------------------------------------------------------------------------
+constexpr double MARG_SERIES_BELOW = 0.5;
+constexpr int MARG_SERIES_TERMS = 20;
+
+template <int KERN>
+__device__ __forceinline__ void marg_series(double b, double& F, double& G) {
+    double t = 1.0, sf = 0.0, sg = 0.0;                    // t = (-b)^m / m!
+    for (int m = 0; m < MARG_SERIES_TERMS; ++m) {
+        const double f = KERN == 0 ? 1.0 - m : (m - 1.0) * (m - 3.0) / 3.0;
+        sf += t * f / (m + 1.0);
+        sg += t * f / (m + 2.0);
+        t *= -b / (m + 1.0);
+    }
+    F = b * sf;
+    G = b * b * sg;
+}
+
+template <int KERN>
+__device__ __forceinline__ double marg_F(double b) {
+    if constexpr (KERN == 1) {
+        return 1.2533141373155003 * erf(b * 0.70710678118654752);            // sqrt(pi / 2), 1 / sqrt(2)
+    } else {
+        if (b < MARG_SERIES_BELOW) { double F, G; marg_series<KERN>(b, F, G); return F; }
+        const double e = exp(-b), em = -expm1(-b);
+        if constexpr (KERN == 0) return 2.0 * em - b * e;
+        else return (8.0 / 3.0) * em - b * (5.0 + b) / 3.0 * e;
+    }
+}
+
+template <int KERN>
+__device__ __forceinline__ double marg_G(double b) {
+    if constexpr (KERN == 1) {
+        return -expm1(-0.5 * b * b);
+    } else {
+        if (b < MARG_SERIES_BELOW) { double F, G; marg_series<KERN>(b, F, G); return G; }
+        const double e = exp(-b), em = -expm1(-b);
+        if constexpr (KERN == 0) return 3.0 * em - b * (3.0 + b) * e;
+        else return 5.0 * em - b * (5.0 + b * (2.0 + b / 3.0)) * e;
+    }
+}
+
+template <int KERN>
+__device__ __forceinline__ double marg_Fc(double b) {
+    if constexpr (KERN == 0) return (2.0 + b) * exp(-b);
+    else if constexpr (KERN == 1) return 1.2533141373155003 * erfc(b * 0.70710678118654752);
+    else return (8.0 + b * (5.0 + b)) / 3.0 * exp(-b);
+}
+
+// I1[k, l, j] = (1 / w_l) int_lo^hi kappa(|t - x_jl| / ell_kl) dt  for every training input (columns n .. npad - 1: 1), and
+// I2[k, l] = (1 / w_l^2) int int kappa(|t - t'| / ell_kl) dt dt' = 2 [F(a) / a - G(a) / a^2], a = w_l / ell_kl.
+// x inside the box: (ell / w) [F(b1) + F(b2)], b = the scaled distances to the two ends.  Outside: the difference of the two,
+// taken between the tails Fc once the nearer end is more than one length scale away (F saturates there and the difference
+// of two saturated values would lose the small result).  grid (npad / 256, d, q); everything in double.
+template <typename T, int KERN>
+__global__ __launch_bounds__(256) void marg_table_kernel(const T* __restrict__ x, int n, int npad, int d,
+                                                         const double* __restrict__ theta, int tw,
+                                                         const double* __restrict__ box /*lo[d], hi[d]*/,
+                                                         double* __restrict__ tab, double* __restrict__ i2) {
+    const int j = blockIdx.x * 256 + threadIdx.x, l = blockIdx.y, k = blockIdx.z;
+    const double ell = theta[(size_t)k * tw + l];
+    const double lo = box[l], hi = box[d + l], w = hi - lo;
+    if (j == 0) {
+        const double a = w / ell;
+        i2[(size_t)k * d + l] = 2.0 * (marg_F<KERN>(a) / a - marg_G<KERN>(a) / (a * a));
+    }
+    if (j >= npad) return;
+    double v = 1.0;
+    if (j < n) {
+        const double xv = (double)x[(size_t)j * d + l];
+        const double a1 = xv - lo, a2 = hi - xv;
+        const double b1 = fabs(a1) / ell, b2 = fabs(a2) / ell;
+        double r;
+        if (a1 >= 0.0 && a2 >= 0.0) {
+            r = marg_F<KERN>(b1) + marg_F<KERN>(b2);
+        } else {
+            const double bn = fmin(b1, b2), bf = fmax(b1, b2);
+            r = bn > 1.0 ? marg_Fc<KERN>(bn) - marg_Fc<KERN>(bf) : marg_F<KERN>(bf) - marg_F<KERN>(bn);
+        }
+        v = ell / w * r;
+    }
+    tab[((size_t)k * d + l) * npad + j] = v;
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -2656,6 +2778,39 @@ __global__ __launch_bounds__(64) void pred_reduce_kernel(const T* __restrict__ X
     if (lane == 0) { ghat[(size_t)k * ldo + m] = s1; gvar[(size_t)k * ldo + m] = scale - D * s2; }
 }
 
+// pred_reduce_kernel with the prior of a box average: scale_k (1 - nt_k) prod_{l in the row's mask} I2[k, l] (ascending l;
+// the nugget is white noise, its average over a set of positive measure vanishes); a row with an empty mask keeps scale_k
+// and is bitwise pred_reduce_kernel's
+template <typename T>
+__global__ __launch_bounds__(64) void marg_reduce_kernel(const T* __restrict__ X, const T* __restrict__ U, size_t slab, int ld, int n,
+                                                         const T* __restrict__ z, int npad, const double* __restrict__ theta, int tw,
+                                                         int d, const unsigned char* __restrict__ mask,
+                                                         const double* __restrict__ i2, int ldo, double* __restrict__ ghat,
+                                                         double* __restrict__ gvar) {
+    const int m = blockIdx.x, k = blockIdx.y, lane = threadIdx.x;
+    const double* th = theta + (size_t)k * tw;
+    const double scale = th[d], nug = th[d + 1], D = th[d + 2];
+    const T* Xr = X + (size_t)k * slab + (size_t)m * ld;
+    const T* Ur = U + (size_t)k * slab + (size_t)m * ld;
+    const T* zk = z + (size_t)k * npad;
+    double s1 = 0.0, s2 = 0.0;
+    for (int i = lane; i < n; i += 64) {
+        const double u = (double)Ur[i];
+        s1 += (double)Xr[i] * (double)zk[i];
+        s2 += u * u;
+    }
+    for (int off = 32; off > 0; off >>= 1) { s1 += __shfl_xor(s1, off); s2 += __shfl_xor(s2, off); }
+    if (lane == 0) {
+        double pr = scale * (1.0 - nug / (1.0 + nug));
+        bool any = false;
+        for (int l = 0; l < d; ++l)
+            if (mask[(size_t)m * d + l]) { pr *= i2[(size_t)k * d + l]; any = true; }
+        const double prior = any ? pr : scale;
+        ghat[(size_t)k * ldo + m] = s1;
+        gvar[(size_t)k * ldo + m] = prior - D * s2;
+    }
+}
+
 // ---------------------------------------------------------------------------------------------------
 // K7: input gradients of the prediction.  For local component k, new input i (standardised) and dimension l:
 //   dghat[k, i, l] =        sum_j dc_l(i, j) sr_j z_k[j]
@@ -3327,6 +3482,40 @@ int do_predict(hipStream_t st, const Ws& w, const void* x, const void* sr, const
     hipLaunchKernelGGL((pred_reduce_kernel<T>), dim3(n0, w.q), dim3(64), 0, st, (const T*)X, (const T*)U, slab, slab, w.npad, w.n,
                        (const T*)(w.base + w.off_z), w.npad, theta, w.d + 3 + w.p, w.d, ldo, ghat, gvar);
     CHECK_LAUNCH("pred_reduce_kernel");
+    return 0;
+}
+
+// Box-averaged predictions, all local components in every launch: the table of 1-D averages (marg_table_kernel), the rows
+// (cross_kernel with the masks), U = X W^T (the launch of form_xu) and the row reductions with the per-row prior.
+// Scratch: X and U as in do_predict, then the table (q d npad doubles) and I2 (q d doubles).
+template <typename T>
+int do_predict_marginal(hipStream_t st, const Ws& w, const void* x, const void* sr, const double* theta, int n0, const void* x0,
+                        const unsigned char* mask, const double* box, void* scratch, double* ghat, double* gvar, int ldo) {
+    const int n0pad = predict_pad(n0);
+    const size_t slab = (size_t)n0pad * w.npad;
+    const int tw = w.d + 3 + w.p;
+    T* X = (T*)scratch;
+    T* U = X + slab * w.q;
+    double* tab = (double*)(U + slab * w.q);
+    double* i2 = tab + (size_t)w.q * w.d * w.npad;
+    ThetaArg dummy;
+    memset(&dummy, 0, sizeof(dummy));
+    for_kern(w.kern, [&](auto kern) {
+        hipLaunchKernelGGL((marg_table_kernel<T, decltype(kern)::value>), dim3((w.npad + 255) / 256, w.d, w.q), dim3(256), 0, st,
+                           (const T*)x, w.n, w.npad, w.d, theta, tw, box, tab, i2);
+    });
+    CHECK_LAUNCH("marg_table_kernel");
+    for_kern(w.kern, [&](auto kern) {
+        hipLaunchKernelGGL((cross_kernel<T, decltype(kern)::value, const unsigned char*, const double*>), dim3(w.nb, n0pad / TS, w.q),
+                           dim3(256), 0, st, X, w.npad, n0, w.n, w.d, (const T*)x0, (const T*)x, dummy, theta, 0, (const T*)sr, n0pad,
+                           w.npad, tw, slab, (const int*)nullptr, mask, (const double*)tab);
+    });
+    CHECK_LAUNCH("cross_kernel (marginal rows)");
+    int rc = launch_pred<T, OP_PRED_U>(st, X, (const T*)(w.base + w.off_W), U, slab, w.mat, w.npad, n0pad, w.nb, w.q);
+    if (rc) return rc;
+    hipLaunchKernelGGL((marg_reduce_kernel<T>), dim3(n0, w.q), dim3(64), 0, st, (const T*)X, (const T*)U, slab, w.npad, w.n,
+                       (const T*)(w.base + w.off_z), w.npad, theta, tw, w.d, mask, (const double*)i2, ldo, ghat, gvar);
+    CHECK_LAUNCH("marg_reduce_kernel");
     return 0;
 }
 
@@ -5607,6 +5796,30 @@ int lcgp_predict(void* stream, int dtype, int kernel_id, int n, int d, int p, in
     hipStream_t st = (hipStream_t)stream;
     return dtype == LCGP_F64 ? do_predict<double>(st, w, x, sr, theta, n0, x0, same, scratch, ghat, gvar, ldo)
                              : do_predict<float>(st, w, x, sr, theta, n0, x0, same, scratch, ghat, gvar, ldo);
+}
+
+int lcgp_predict_marginal_scratch_bytes(int dtype, int n, int d, int q_local, int n0, size_t* bytes) {
+    if (d < 1 || d > DWIDE) return bad("d must be in [1, 126]");
+    int rc = lcgp_predict_scratch_bytes(dtype, n, q_local, n0, bytes);
+    if (rc) return rc;
+    *bytes += (size_t)q_local * d * (round_up(n, 2 * TS) + 1) * sizeof(double);
+    return 0;
+}
+
+int lcgp_predict_marginal(void* stream, int dtype, int kernel_id, int n, int d, int p, int q_local, const void* x, const void* sr,
+                          const double* theta, const void* workspace, int n0, const void* x0, const unsigned char* mask,
+                          const double* box, void* scratch, double* ghat, double* gvar, int out_stride) {
+    int rc = check_common(dtype, n, d, p, q_local, kernel_id);
+    if (rc) return rc;
+    if (n0 < 1) return bad("n0 < 1");
+    if (!x || !theta || !workspace || !x0 || !mask || !box || !scratch || !ghat || !gvar) return bad("NULL pointer");
+    if (out_stride != 0 && out_stride < n0) return bad("out_stride must be 0 (= n0) or >= n0");
+    const int ldo = out_stride ? out_stride : n0;
+    Ws w = carve(dtype, n, d, p, q_local, (void*)workspace);
+    w.kern = kernel_id;
+    hipStream_t st = (hipStream_t)stream;
+    return dtype == LCGP_F64 ? do_predict_marginal<double>(st, w, x, sr, theta, n0, x0, mask, box, scratch, ghat, gvar, ldo)
+                             : do_predict_marginal<float>(st, w, x, sr, theta, n0, x0, mask, box, scratch, ghat, gvar, ldo);
 }
 
 int lcgp_predict_grad_scratch_bytes(int dtype, int n, int q_local, int n0, size_t* bytes) {

@@ -347,6 +347,43 @@ class HotPathEngine:
                     wp, None if M is None else self._p(M), n0), "lcgp_predict_gradcov")
             return dghat, gamma, M
 
+    def predict_marginal_block(self, x0s, mask, box):
+        """(2, q_local, n0) float64 DEVICE tensor [ghat; gvar] of the latent components AVERAGED over the dimensions mask marks
+        (mask (n0, d), non-zero = integrated out), uniformly over box (2, d) = [lo; hi] in standardised inputs, from the
+        factorisation of the last evaluate() (lcgp_predict_marginal).  Entries of x0s under the mask are never read on the
+        device (they are uploaded as zeros: NaN is allowed there).  A row with an empty mask is bitwise predict_block(x0s,
+        same=False)'s while both take one pass.  Chunked like predict_block with the engine's scratch, a pass never below 128
+        rows while n0 has them and a short last pass moved back over its predecessor (the same values again), so that every
+        pass forms U on the same tile size: results are bitwise independent of PREDICT_CHUNK."""
+        torch = self.torch
+        if self._theta_last is None:
+            raise RuntimeError("predict_marginal() needs a preceding evaluate() at the current parameters")
+        n0, d = np.shape(x0s)[0], self.d
+        mask = np.ascontiguousarray(np.asarray(mask) != 0, np.uint8)
+        box = np.ascontiguousarray(box, np.float64)
+        assert np.shape(x0s) == (n0, d) and mask.shape == (n0, d) and box.shape == (2, d) and n0 >= 1
+        if not np.all(box[1] > box[0]):
+            raise ValueError("predict_marginal_block: the box needs hi > lo in every dimension")
+        x0s = np.ascontiguousarray(np.where(mask != 0, 0.0, np.asarray(x0s, np.float64)))
+        chunk = min(n0, max(128, PREDICT_CHUNK))
+        with torch.cuda.device(self.device):
+            x0d = torch.as_tensor(x0s).to(self.device, self.tdtype).contiguous()
+            md = torch.as_tensor(mask).to(self.device)
+            bd = torch.as_tensor(box).to(self.device)
+            scp = self._p(self._grow_scratch(self._nbytes("lcgp_predict_marginal_scratch_bytes", self.dtype, self.n, d,
+                                                          self.q_local, chunk)))
+            out = torch.empty((2, self.q_local, n0), dtype=torch.float64, device=self.device)
+            st, xp, srp, thp, wsp = self._stream(), self._p(self.x), self._p(self.sr), self._p(self.theta_dev), self._p(self.workspace)
+            for lo in range(0, n0, chunk):
+                m = min(chunk, n0 - lo)
+                if m < 128 <= n0:
+                    lo, m = n0 - 128, 128
+                _hip.check(self.lib.lcgp_predict_marginal(
+                    st, self.dtype, self.kernel_id, self.n, d, self.p, self.q_local, xp, srp, thp, wsp, m,
+                    C.c_void_p(x0d.data_ptr() + lo * d * x0d.element_size()), C.c_void_p(md.data_ptr() + lo * d), self._p(bd), scp,
+                    C.c_void_p(out[0].data_ptr() + 8 * lo), C.c_void_p(out[1].data_ptr() + 8 * lo), n0), "lcgp_predict_marginal")
+            return out
+
     def predict_device(self, x0s, same=False):
         """ghat, gvar (q_local, n0): the two halves of predict_block()"""
         out = self.predict_block(x0s, same)

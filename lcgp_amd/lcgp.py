@@ -192,6 +192,20 @@ class ActiveSubspace:
         return "ActiveSubspace(outputs=%d, d=%d)" % tuple(self.activity.shape)
 
 
+class MainEffects:
+    """main_effects(): grid (d, G) on the raw input scale; mean, var (p_sel, d, G), the output as a function of input l alone,
+    averaged over the others, and the posterior variance of that average; overall, overall_var (p_sel,), the average over all
+    inputs (the Bayesian-quadrature mean of the output over the box); effect = mean - overall (no variance: that needs the
+    covariance between rows)."""
+
+    def __init__(self, grid, mean, var, overall, overall_var):
+        self.grid, self.mean, self.var, self.overall, self.overall_var = grid, mean, var, overall, overall_var
+        self.effect = mean - overall[:, None, None]
+
+    def __repr__(self):
+        return 'MainEffects(outputs=%d, d=%d, grid=%d)' % (self.mean.shape[0], self.mean.shape[1], self.mean.shape[2])
+
+
 class LCGP:
     """
     Latent Component Gaussian Process (LCGP), MI355X hot path.
@@ -1692,6 +1706,97 @@ class LCGP:
         vec = vec * np.where(sign == 0, 1.0, sign)
         activity = np.diagonal(matrix, axis1=-2, axis2=-1).copy()
         return ActiveSubspace(_t(matrix), _t(mean_part), _t(cov_part), _t(activity), _t(lam), _t(vec))
+
+    # =============================================================================================
+    # box-averaged predictions (beyond the reference): closed-form averages of the product kernels
+    # =============================================================================================
+    def _marginal_box(self, box):
+        """box (2, d) on the raw scale (default: the training inputs' bounding box) -> standardised [lo; hi]"""
+        d = int(self.d)
+        if box is None:
+            return np.stack([np.zeros(d, F64), np.ones(d, F64)])
+        b = np.asarray(_np(self._verify_data_types(box)), F64)
+        if b.shape != (2, d):
+            raise ValueError('box must have shape (2, %d) = [lower; upper], got %s' % (d, tuple(b.shape)))
+        xmin, xmax = _np(self.x_min).reshape(-1), _np(self.x_max).reshape(-1)
+        bs = (b - xmin[None, :]) / (xmax - xmin)[None, :]
+        if not np.all(np.isfinite(bs)) or not np.all(bs[1] > bs[0]):
+            raise ValueError('box must be finite with upper > lower in every dimension')
+        return bs
+
+    def predict_marginal(self, x0, integrate, box=None, latent=False):
+        """Predictions AVERAGED over some of the inputs: (ypred, yconfvar), each (p, n0), the output at the kept inputs of each
+        row of x0 averaged over the integrated inputs, uniformly over `box`, and the posterior variance of that average (of
+        the noise-free surface; no ypredvar: observation noise does not average).
+          integrate: a sequence of dimension indices, the same for every row, or a boolean (n0, d) array, one mask per row
+                     (True = integrated out).  Values of x0 in integrated columns are ignored; NaN is allowed there.
+          box:       (2, d) = [lower; upper] on the raw input scale (default: the training inputs' bounding box).  Training
+                     inputs may lie outside it.
+          latent:    return (ghat, gvar), each (q, n0), of the latent components instead.
+        For the product kernels the average is exact: a prediction whose cross-covariance row holds the box average of the
+        1-D kernel factor in the integrated dimensions and whose prior variance holds its double average (the nugget, white
+        noise, averages to zero).  One pass on the GPU at the cost of predict() on n0 rows (lcgp_predict_marginal); a row that
+        integrates nothing is predict()'s at a new input.  Rows are treated one by one: their covariance is not formed."""
+        x0n = np.array(_np(self._verify_data_types(x0)), F64)
+        d = int(self.d)
+        if x0n.ndim != 2 or x0n.shape[1] != d or x0n.shape[0] < 1:
+            raise ValueError('x0 must have shape (n, %d), got %s' % (d, tuple(x0n.shape)))
+        n0 = x0n.shape[0]
+        integ = np.asarray(integrate)
+        if integ.dtype == bool and integ.ndim == 2:
+            if integ.shape != (n0, d):
+                raise ValueError('a boolean integrate must have shape (%d, %d), got %s' % (n0, d, tuple(integ.shape)))
+            mask = integ.copy()
+        else:
+            idx = integ.reshape(-1)
+            if idx.size and not np.issubdtype(idx.dtype, np.integer):
+                raise ValueError('integrate must be dimension indices or a boolean (n0, d) array')
+            if np.any(idx < 0) or np.any(idx >= d):
+                raise ValueError('integrate must hold dimension indices in [0, %d)' % d)
+            mask = np.zeros((n0, d), bool)
+            mask[:, idx.astype(int)] = True
+        bs = self._marginal_box(box)
+        if not np.all(np.isfinite(x0n[~mask])):
+            raise ValueError('x0 must be finite in the columns that are kept')
+        x0n[mask] = 0.0                                  # (never read: the engine passes zeros under the mask)
+        x0s = self._standardise_x0(x0n)[0]
+        eng = self._ensure_aux()
+        loc = None if eng is None else eng.predict_marginal_block(x0s, mask, bs).permute(1, 0, 2)        # (q_local, 2, n0)
+        both = self._gather_components(loc, (2, n0))
+        ghat, gvar = both[:, 0], both[:, 1]
+        if latent:
+            return _t(ghat), _t(gvar)
+        ypred, _, yconfvar = self._outputs(ghat, gvar)
+        return ypred, yconfvar
+
+    def main_effects(self, grid=33, box=None, outputs=None):
+        """Main effects of every input: the output as a function of input l alone, averaged over all the others uniformly over
+        `box` ((2, d) raw scale, default the training inputs' bounding box), on `grid` equally spaced values of input l
+        between the box's ends, with the posterior variance of each average; and the average over all inputs.  One
+        predict_marginal() pass of d grid + 1 rows.  Returns a MainEffects (grid, mean, var, overall, overall_var, effect);
+        outputs: output indices (default all p)."""
+        d, G = int(self.d), int(grid)
+        if G < 1:
+            raise ValueError('grid must be at least 1')
+        p = int(self.p)
+        outputs = list(range(p)) if outputs is None else [int(a) for a in np.atleast_1d(outputs)]
+        if any(a < 0 or a >= p for a in outputs):
+            raise ValueError('outputs must be indices in [0, %d)' % p)
+        self._marginal_box(box)                                 # (its checks, before any work)
+        xmin, xmax = _np(self.x_min).reshape(-1), _np(self.x_max).reshape(-1)
+        raw = np.stack([xmin, xmax]) if box is None else np.asarray(_np(self._verify_data_types(box)), F64)
+        t = np.linspace(0.0, 1.0, G) if G > 1 else np.array([0.5])
+        grid_raw = raw[0][:, None] + (raw[1] - raw[0])[:, None] * t[None, :]                   # (d, G)
+        x0 = np.full((d * G + 1, d), np.nan)
+        mask = np.ones((d * G + 1, d), bool)
+        for l in range(d):
+            x0[l * G:(l + 1) * G, l] = grid_raw[l]
+            mask[l * G:(l + 1) * G, l] = False
+        ypred, yconfvar = self.predict_marginal(x0, mask, box=box)
+        ypred, yconfvar = _np(ypred)[outputs], _np(yconfvar)[outputs]
+        ns = len(outputs)
+        return MainEffects(_t(grid_raw), _t(ypred[:, :-1].reshape(ns, d, G)), _t(yconfvar[:, :-1].reshape(ns, d, G)),
+                           _t(ypred[:, -1]), _t(yconfvar[:, -1]))
 
     # ---- cache views the reference keeps as attributes (materialised from the device only when read) ----
     def _fetch_all(self, fn, width):

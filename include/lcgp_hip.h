@@ -222,6 +222,44 @@ int lcgp_nll_hess(void* stream, int dtype, int kernel_id, int n, int d, int p, i
                   const void* x, const void* Y, const void* sr, const double* theta, const void* workspace,
                   int k0, int q_group, void* scratch, double* out /*q_local rows of lcgp_nll_hess_width(d, p)*/);
 
+/* Parameter derivatives of the prediction (the reference gets them by a tf.GradientTape around predict, lcgp.py:808-930, over
+ * the trainable variables; this entry replaces that tape).  float64 only: LCGP_F32 is refused with an error text (the variance
+ * derivatives are differences that cancel).  Runs behind lcgp_nll_grad at the same theta and only READS its workspace (L_k^-1,
+ * b_k, z_k): every other post-fit entry stays valid after it.  Per local component k, in the notation of lcgp_nll_hess, with
+ * X_i the cross-covariance row of lcgp_predict for new input i (standardised; `same` as there: the row's nugget entry),
+ * V_i = X_i A^-1, ghat_i = X_i . z, gvar_i = scale - D X_i . V_i, y_t = d_tA z and t in [ell_0 .. ell_{d-1}, scale, nug]:
+ *     dghat[k, i, t]       = (d_t X_i) . z - V_i . y_t
+ *     dgvar[k, i, t]       = d_t scale - D [ 2 (d_t X_i) . V_i - V_i (d_tA) V_i^T ]
+ *     dghat_noise[k, i, a] = -1/2 psi_a V_i . Y_a          (the built noise parameters t_a of lcgp_nll_hess; d gvar / d t_a = 0)
+ *   d_ell_j X_i = Xc_i o phi_j(x0_i, .) with Xc the continuous part of the row (phi_j = 0 at the nugget entry) and the phi of
+ *   lcgp_nll_hess; d_scale X_i = X_i / scale; d_nug X_i = -Xc_i / (1 + nug) + scale s e_c* / (1 + nug)^2 at the nugget entry c*.
+ *   d_scale A = (A - I) / scale and d_nug A = [D scale diag(s^2) - (A - I)] / (1 + nug) need no product: V_i A = X_i, so
+ *   V_i (A - I) V_i^T = X_i . V_i - |V_i|^2.  Only the d terms V_i (d_jA) V_i^T do.
+ * The call handles the components k0 .. k0 + q_group - 1 of the workspace (carved for q_local) and writes their rows of the
+ * outputs: a caller bounds the scratch by processing the local components in groups and the new inputs in chunks.
+ * Launches: x / ell, y_scale, y_nug (the first launch of lcgp_nll_hess); X, U = X W^T, ghat / gvar and V = U W by the launches
+ * of lcgp_predict_grad (ghat / gvar are BITWISE those of lcgp_predict with the same `same`; V overwrites X); per dimension j:
+ * d_jA materialised into one reused buffer, y_j = d_jA z, T_j = V d_jA on the fp64 MFMA tile kernel (operand mode OP_HESS_G, 128 x
+ * 128 tiles, over U) and one wave per new input for T_j[i, :] . V_i; a fused row kernel, one workgroup per (new input, block of 16
+ * dimensions), that recomputes C0 and phi_j in registers and accumulates every remaining sum in one sweep over the row (no n0 x n
+ * x d tensor is written); V Y^T on the tile kernel (Y^T zero padded); one combining launch.
+ * Outputs: ghat / gvar q_local rows of n0, `out_stride` apart (0 = n0); dghat / dgvar [q_local][out_stride][d + 2];
+ *   dghat_noise [q_local][out_stride][p] (a caller that works in chunks passes the chunk's offset and the total as stride).
+ * scratch: lcgp_predict_paramgrad_scratch_bytes(dtype, n, d, p, q_group, n0) bytes = q_group (2 n0pad npad + npad^2) doubles (X / V,
+ *   U / T_j, d_jA; n0pad = n0 rounded up to 128) plus q_group ((2 d + 2) npad + n0pad (ppad + 4 d + 8)) and npad ppad doubles of
+ *   vectors, V Y^T, the sums and the padded Y^T (ppad = p rounded up to 128); its content on entry is irrelevant.  n0 <= 65535.
+ * Flops per component: 2 d n0pad npad^2 (the products T_j) + n0pad npad^2 (U, V) + 2 n0pad ppad npad (V Y^T) + d npad^2 (d + 30)-ish
+ * (d_jA) + n0 n (d + 40) ceil(d / 16)-ish in the row kernel; every sum has a fixed order, no atomics: bitwise reproducible,
+ * independent of q_local, of q_group and of the scratch content on entry. */
+int lcgp_predict_paramgrad_scratch_bytes(int dtype, int n, int d, int p, int q_group, int n0, size_t* bytes /*host out*/);
+int lcgp_predict_paramgrad(void* stream, int dtype, int kernel_id, int n, int d, int p, int q_local,
+                           const void* x, const void* Y, const void* sr, const double* theta, const void* workspace,
+                           int k0, int q_group, int n0, const void* x0, int same, void* scratch,
+                           double* ghat, double* gvar,            /* q_local rows of n0, `out_stride` apart */
+                           double* dghat, double* dgvar,          /* [q_local][out_stride][d + 2] */
+                           double* dghat_noise,                   /* [q_local][out_stride][p] */
+                           int out_stride);
+
 /* The launch plan of the factorisation, computed ONCE by the caller instead of in every evaluation (it depends on
  * dtype, n, q_local, the schedule and on whether the inverse follows -- with_inverse = 1 for lcgp_nll_grad, 0 for
  * lcgp_potrf_logdet -- and on nothing else).  The plan is a position-independent block of `bytes` bytes in HOST memory

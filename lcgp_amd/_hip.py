@@ -56,6 +56,9 @@ SIGNATURES = {
     "lcgp_nll_hess_width": (_i, [_i, _i]),
     "lcgp_nll_hess_scratch_bytes": (_i, [_i, _i, _i, _i, _i, C.POINTER(C.c_size_t)]),
     "lcgp_nll_hess": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp]),
+    "lcgp_predict_paramgrad_scratch_bytes": (_i, [_i, _i, _i, _i, _i, _i, C.POINTER(C.c_size_t)]),
+    "lcgp_predict_paramgrad": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp,
+                                    _vp, _i]),
     "lcgp_plan_bytes": (_i, [_i, _i, _i, _i, _sp, C.POINTER(C.c_size_t)]),
     "lcgp_plan_build": (_i, [_i, _i, _i, _i, _sp, _vp, C.c_size_t]),
     "lcgp_plan_info": (_i, [_vp, C.POINTER(_i), C.POINTER(_i)]),

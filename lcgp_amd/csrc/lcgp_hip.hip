@@ -5481,6 +5481,283 @@ int do_nll_hess(hipStream_t st, const Ws& w, const void* x, const double* Y, con
     return 0;
 }
 
+// ---------------------------------------------------------------------------------------------------
+// Parameter derivatives of the prediction (lcgp_hip.h: lcgp_predict_paramgrad; the reference would put a gradient
+// tape around predict over the trainable variables).  float64 only.  Runs behind lcgp_nll_grad at the same theta and only
+// READS the workspace (L^-1, b, z).  Per component and new input i, with X_i the cross-covariance row of lcgp_predict,
+// V_i = X_i A^-1, y_t = d_tA z and the m = d + 2 kernel parameters t in [ell_0 .. ell_{d-1}, scale, nug]:
+//     d_t ghat_i = (d_t X_i) . z - V_i . y_t          d_t gvar_i = d_t scale - D [2 (d_t X_i) . V_i - V_i (d_tA) V_i^T]
+// Launches: hess_prep_kernel (x / ell, y_scale, y_nug); X, U = X W^T, ghat / gvar and V = U W exactly as lcgp_predict_grad forms
+// them (V over X); per dimension j: d_jA materialised (hess_da_kernel, one buffer), y_j = d_jA z, T_j = V d_jA on the tile kernel
+// (OP_HESS_G, over U) and its row dots with V; the fused row kernel (C0 and phi_j recomputed in registers, every other sum of
+// the formulas in one sweep over the row); V Y^T on the tile kernel; the combining kernel.
+// Every sum has a fixed order, no atomics: bitwise reproducible, independent of the number of components in the call and of
+// the scratch content on entry.
+// ---------------------------------------------------------------------------------------------------
+constexpr int PP_DB = 16;          // dimensions per workgroup of the row kernel: 3 accumulators each, 48 of the 56 per thread
+
+struct PgradLay {
+    int m, npad, nb, ppad, n0p, n0r, nsum;
+    size_t mat, slab;
+    size_t off_x, off_u, off_e, off_xs, off_yv, off_yt, off_vy, off_rd, off_sum, total;
+};
+
+inline PgradLay pgrad_carve(int n, int d, int p, int qg, int n0) {
+    PgradLay L;
+    L.m = d + 2;
+    L.npad = round_up(n, 2 * TS);
+    L.nb = L.npad / TS;
+    L.ppad = round_up(p, 2 * TS);
+    L.n0p = predict_pad(n0);                // rows of X / U / V the launches of lcgp_predict form
+    L.n0r = round_up(n0, 2 * TS);           // rows of a slab: the dense products run on 128 x 128 tiles
+    L.nsum = 3 * d + 8;                     // [ dz_j (d) | dv_j (d) | Xc.z, Xc.V, rz, rv, |V|^2, sum s^2 V^2 | V . y_t (d + 2) ]
+    L.mat = (size_t)L.npad * L.npad;
+    L.slab = (size_t)L.n0r * L.npad;
+    size_t o = 0;
+    const size_t e = sizeof(double);
+    L.off_x = o; o = align256(o + (size_t)qg * L.slab * e);
+    L.off_u = o; o = align256(o + (size_t)qg * L.slab * e);
+    L.off_e = o; o = align256(o + (size_t)qg * L.mat * e);
+    L.off_xs = o; o = align256(o + (size_t)qg * d * L.npad * e);
+    L.off_yv = o; o = align256(o + (size_t)qg * L.m * L.npad * e);
+    L.off_yt = o; o = align256(o + (size_t)L.npad * L.ppad * e);
+    L.off_vy = o; o = align256(o + (size_t)qg * L.n0r * L.ppad * e);
+    L.off_rd = o; o = align256(o + (size_t)qg * d * L.n0r * e);
+    L.off_sum = o; o = align256(o + (size_t)qg * L.n0r * L.nsum * e);
+    L.total = o;
+    return L;
+}
+
+// Y^T (n x p) zero padded to npad x ppad: the B operand of V Y^T
+__global__ __launch_bounds__(256) void pgrad_pack_yt_kernel(const double* __restrict__ Y, int p, int n, int ppad, double* __restrict__ YT) {
+    const int a = blockIdx.x * 256 + threadIdx.x, i = blockIdx.y;
+    if (a >= ppad) return;
+    YT[(size_t)i * ppad + a] = (a < p && i < n) ? Y[(size_t)a * n + i] : 0.0;
+}
+
+// rd[k][j][i] = T_j[i, :] . V[i, :] = V_i (d_jA) V_i^T: one wave per new input
+__global__ __launch_bounds__(64) void pgrad_rowdot_kernel(const double* __restrict__ T, const double* __restrict__ V, size_t slab, int ld,
+                                                          int n, double* __restrict__ rd, size_t srd) {
+    const int i = blockIdx.x, k = blockIdx.y, lane = threadIdx.x;
+    const double* t = T + (size_t)k * slab + (size_t)i * ld;
+    const double* v = V + (size_t)k * slab + (size_t)i * ld;
+    double s = 0.0;
+    for (int c = lane; c < n; c += 64) s = fma(t[c], v[c], s);
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) s += __shfl_xor(s, o);
+    if (lane == 0) rd[(size_t)k * srd + i] = s;
+}
+
+// The fused row kernel: one workgroup per (new input i, component, block of PP_DB dimensions).  With Xc = scale (1 - w) C0 o s
+// the continuous part of the cross-covariance row (C0 and phi_j recomputed in registers from x / ell), v = V_i and c* the
+// column of the row's nugget entry (same > 0: c* = i + same - 1), one sweep over the n columns accumulates
+//   dz_j = sum Xc phi_j z      dv_j = sum Xc phi_j v      vy_j = sum v y_j             for the block's dimensions j
+//   Xc . z, Xc . v, rz = s z at c*, rv = s v at c*, |v|^2, sum s^2 v^2, v . y_scale, v . y_nug       (dimension block 0 only)
+// into row (k, i) of `sums` (PgradLay::nsum doubles).  No n0 x n x d tensor is written.
+template <int KERN>
+__global__ __launch_bounds__(256) void pgrad_row_kernel(const double* __restrict__ x0, int n0, int same, const double* __restrict__ xs,
+                                                        const double* __restrict__ sr, int n, int npad, int d,
+                                                        const double* __restrict__ theta, int tw, const double* __restrict__ zvec,
+                                                        const double* __restrict__ V, size_t slab, const double* __restrict__ yv,
+                                                        double* __restrict__ sums, int n0r, int nsum) {
+    __shared__ double x0l[DWIDE];
+    __shared__ double sh[4];
+    const int i = blockIdx.x, k = blockIdx.y, j0 = blockIdx.z * PP_DB, tid = threadIdx.x;
+    const double* th = theta + (size_t)k * tw;
+    if (tid < d) x0l[tid] = x0[(size_t)i * d + tid] / th[tid];
+    __syncthreads();
+    const double cc = th[d] / (1.0 + th[d + 1]);          // scale (1 - w)
+    const double* xk = xs + (size_t)k * d * npad;
+    const double* zk = zvec + (size_t)k * npad;
+    const double* vr = V + (size_t)k * slab + (size_t)i * npad;
+    const double* yk = yv + (size_t)k * (d + 2) * npad;
+    const int cstar = same > 0 ? i + same - 1 : -1;
+    const bool first = j0 == 0;
+    double dz[PP_DB], dv[PP_DB], vy[PP_DB];
+#pragma unroll
+    for (int jj = 0; jj < PP_DB; ++jj) dz[jj] = dv[jj] = vy[jj] = 0.0;
+    double xz = 0.0, xv = 0.0, rz = 0.0, rv = 0.0, vv = 0.0, s2vv = 0.0, vys = 0.0, vyn = 0.0;
+    for (int c = tid; c < n; c += 256) {
+        double poly = 1.0, ssum = 0.0;
+        for (int l = 0; l < d; ++l) {
+            const double df = x0l[l] - xk[(size_t)l * npad + c];
+            if constexpr (KERN == 0) {
+                const double sd = fabs(df);
+                poly = fma(poly, sd, poly);
+                ssum -= sd;
+            } else if constexpr (KERN == 1) {
+                ssum = fma(-0.5 * df, df, ssum);
+            } else {
+                static_assert(KERN == 2, "unknown covariance kernel id");
+                const double sd = fabs(df);
+                poly = fma(poly, m52_fm1(sd), poly);
+                ssum -= sd;
+            }
+        }
+        const double s = sr ? sr[c] : 1.0, z = zk[c], v = vr[c];
+        const double xc = cc * kern_c0<KERN>(poly, ssum) * s;
+#pragma unroll
+        for (int jj = 0; jj < PP_DB; ++jj) {
+            const int j = j0 + jj;
+            if (j < d) {
+                double phi, dphi;
+                hess_phi<KERN>(fabs(x0l[j] - xk[(size_t)j * npad + c]), th[j], phi, dphi);
+                const double t = xc * phi;
+                dz[jj] = fma(t, z, dz[jj]);
+                dv[jj] = fma(t, v, dv[jj]);
+                vy[jj] = fma(v, yk[(size_t)j * npad + c], vy[jj]);
+            }
+        }
+        if (first) {
+            xz = fma(xc, z, xz);
+            xv = fma(xc, v, xv);
+            vv = fma(v, v, vv);
+            s2vv = fma((s * s) * v, v, s2vv);
+            vys = fma(v, yk[(size_t)d * npad + c], vys);
+            vyn = fma(v, yk[(size_t)(d + 1) * npad + c], vyn);
+            if (c == cstar) { rz = s * z; rv = s * v; }
+        }
+    }
+    double* out = sums + ((size_t)k * n0r + i) * nsum;
+#pragma unroll
+    for (int jj = 0; jj < PP_DB; ++jj) {
+        const int j = j0 + jj;
+        if (j < d) {                 // (uniform over the workgroup)
+            const double a = hess_block_sum(dz[jj], sh, tid), b = hess_block_sum(dv[jj], sh, tid), c = hess_block_sum(vy[jj], sh, tid);
+            if (tid == 0) { out[j] = a; out[d + j] = b; out[2 * d + 6 + j] = c; }
+        }
+    }
+    if (first) {
+        const double a0 = hess_block_sum(xz, sh, tid), a1 = hess_block_sum(xv, sh, tid), a2 = hess_block_sum(rz, sh, tid),
+                     a3 = hess_block_sum(rv, sh, tid), a4 = hess_block_sum(vv, sh, tid), a5 = hess_block_sum(s2vv, sh, tid),
+                     a6 = hess_block_sum(vys, sh, tid), a7 = hess_block_sum(vyn, sh, tid);
+        if (tid == 0) {
+            double* o6 = out + 2 * d;
+            o6[0] = a0; o6[1] = a1; o6[2] = a2; o6[3] = a3; o6[4] = a4; o6[5] = a5;
+            out[3 * d + 6] = a6; out[3 * d + 7] = a7;
+        }
+    }
+}
+
+// combines the sums into dghat / dgvar (n0 x (d + 2), order [ell_0 .. ell_{d-1}, scale, nug]) and dghat_noise (n0 x p):
+// one thread per (new input, component)
+__global__ __launch_bounds__(256) void pgrad_final_kernel(const double* __restrict__ sums, int n0r, int nsum, const double* __restrict__ rd,
+                                                          const double* __restrict__ vy, int ppad, int n0, int d, int p,
+                                                          const double* __restrict__ theta, int tw, int ldo,
+                                                          double* __restrict__ dghat, double* __restrict__ dgvar,
+                                                          double* __restrict__ dnoise) {
+    const int i = blockIdx.x * 256 + threadIdx.x, k = blockIdx.y;
+    if (i >= n0) return;
+    const double* th = theta + (size_t)k * tw;
+    const double scale = th[d], nug = th[d + 1], D = th[d + 2];
+    const double omw = 1.0 / (1.0 + nug), nt = nug * omw, w1 = omw * omw;      // 1 - w, w, dw / dnug
+    const double* s = sums + ((size_t)k * n0r + i) * nsum;
+    const double* rdk = rd + (size_t)k * d * n0r;
+    const int m = d + 2;
+    double* dg = dghat + ((size_t)k * ldo + i) * m;
+    double* dv = dgvar + ((size_t)k * ldo + i) * m;
+    for (int j = 0; j < d; ++j) {
+        dg[j] = s[j] - s[2 * d + 6 + j];
+        dv[j] = -D * (2.0 * s[d + j] - rdk[(size_t)j * n0r + i]);
+    }
+    const double xcz = s[2 * d], xcv = s[2 * d + 1], rz = s[2 * d + 2], rv = s[2 * d + 3], vv = s[2 * d + 4], s2vv = s[2 * d + 5];
+    const double xz = fma(scale * nt, rz, xcz), xv = fma(scale * nt, rv, xcv);        // X . z, X . V with the nugget entry
+    dg[d] = xz / scale - s[3 * d + 6];
+    dv[d] = 1.0 - D * (xv + vv) / scale;
+    dg[d + 1] = fma(scale * w1, rz, -xcz * omw) - s[3 * d + 7];
+    dv[d + 1] = -D * (2.0 * fma(scale * w1, rv, -xcv * omw) - (D * scale * s2vv - (xv - vv)) * omw);
+    const double* vyr = vy + ((size_t)k * n0r + i) * ppad;
+    double* dn = dnoise + ((size_t)k * ldo + i) * p;
+    for (int a = 0; a < p; ++a) dn[a] = -0.5 * th[d + 3 + a] * vyr[a];
+}
+
+// enqueues the pass for the components [k0, k0 + qg) of the workspace; the outputs are those of the q_local components
+int do_predict_paramgrad(hipStream_t st, const Ws& w, const void* x, const double* Y, const void* sr, const double* theta, int k0,
+                         int qg, int n0, const void* x0, int same, char* scratch, double* ghat, double* gvar, double* dghat,
+                         double* dgvar, double* dnoise, int ldo) {
+    const int n = w.n, d = w.d, p = w.p, npad = w.npad, tw = d + 3 + p;
+    const PgradLay L = pgrad_carve(n, d, p, qg, n0);
+    const int m = L.m;
+    double* X = (double*)(scratch + L.off_x);          // X, then V
+    double* U = (double*)(scratch + L.off_u);          // U, then T_j
+    double* E = (double*)(scratch + L.off_e);
+    double* XS = (double*)(scratch + L.off_xs);
+    double* YV = (double*)(scratch + L.off_yv);
+    double* YT = (double*)(scratch + L.off_yt);
+    double* VY = (double*)(scratch + L.off_vy);
+    double* RD = (double*)(scratch + L.off_rd);
+    double* SUM = (double*)(scratch + L.off_sum);
+    const double* W = (const double*)(w.base + w.off_W) + (size_t)k0 * w.mat;
+    const double* bv = (const double*)(w.base + w.off_b) + (size_t)k0 * npad;
+    const double* zv = (const double*)(w.base + w.off_z) + (size_t)k0 * npad;
+    const double* th = theta + (size_t)k0 * tw;
+    const double* xd = (const double*)x;
+    const double* srd = (const double*)sr;
+    const double* x0d = (const double*)x0;
+    double* gh = ghat + (size_t)k0 * ldo;
+    double* gv = gvar + (size_t)k0 * ldo;
+
+    hipLaunchKernelGGL(hess_prep_kernel, dim3((npad + 255) / 256, qg), dim3(256), 0, st, xd, srd, n, npad, d, th, tw, bv, zv, XS, YV);
+    CHECK_LAUNCH("hess_prep_kernel");
+    // X, U = X W^T, ghat / gvar, V = U W: the launches of lcgp_predict_grad on the group's components
+    ThetaArg dummy;
+    memset(&dummy, 0, sizeof(dummy));
+    for_kern(w.kern, [&](auto kern) {
+        hipLaunchKernelGGL((cross_kernel<double, decltype(kern)::value>), dim3(w.nb, L.n0p / TS, qg), dim3(256), 0, st, X, npad, n0, n, d,
+                           x0d, xd, dummy, th, same, srd, L.n0p, npad, tw, L.slab, (const int*)nullptr);
+    });
+    CHECK_LAUNCH("cross_kernel");
+    int rc = launch_pred<double, OP_PRED_U>(st, X, W, U, L.slab, w.mat, npad, L.n0p, w.nb, qg);
+    if (rc) return rc;
+    hipLaunchKernelGGL((pred_reduce_kernel<double>), dim3(n0, qg), dim3(64), 0, st, (const double*)X, (const double*)U, L.slab, L.slab,
+                       npad, n, zv, npad, th, tw, d, ldo, gh, gv);
+    CHECK_LAUNCH("pred_reduce_kernel");
+    rc = launch_pred<double, OP_PRED_V>(st, U, W, X, L.slab, w.mat, npad, L.n0p, w.nb, qg);
+    if (rc) return rc;
+    const double* V = X;
+    // per dimension: d_jA, y_j = d_jA z, T_j = V d_jA (rows beyond n0p of a slab are never written: their products are never read)
+    const dim3 full((npad + 255) / 256, npad, qg);
+    GemmArgs g;
+    g.A = V; g.B = E; g.C = U; g.ldA = g.ldB = g.ldC = npad;
+    g.sA = L.slab; g.sB = L.mat; g.sC = L.slab;
+    g.nb = L.nb / 2; g.p0 = L.n0r / (2 * TS); g.p1 = L.nb / 2; g.p2 = g.p3 = 0;
+    for (int j = 0; j < d; ++j) {
+        for_kern(w.kern, [&](auto kern) {
+            hipLaunchKernelGGL((hess_da_kernel<decltype(kern)::value>), full, dim3(256), 0, st, E, L.mat, n, npad, d, j,
+                               (const double*)XS, srd, th, tw);
+        });
+        CHECK_LAUNCH("hess_da_kernel");
+        hipLaunchKernelGGL(hess_matvec_kernel, dim3(npad / 4, 1, qg), dim3(256), 0, st, (const double*)E, L.mat, n, npad, zv, (size_t)npad,
+                           YV + (size_t)j * npad, (size_t)m * npad);
+        CHECK_LAUNCH("hess_matvec_kernel");
+        rc = launch_gemm<double, OP_HESS_G, 128>(st, g, g.p0 * g.nb, qg);
+        if (rc) return rc;
+        hipLaunchKernelGGL(pgrad_rowdot_kernel, dim3(n0, qg), dim3(64), 0, st, (const double*)U, V, L.slab, npad, n,
+                           RD + (size_t)j * L.n0r, (size_t)d * L.n0r);
+        CHECK_LAUNCH("pgrad_rowdot_kernel");
+    }
+    for_kern(w.kern, [&](auto kern) {
+        hipLaunchKernelGGL((pgrad_row_kernel<decltype(kern)::value>), dim3(n0, qg, (d + PP_DB - 1) / PP_DB), dim3(256), 0, st, x0d, n0,
+                           same, (const double*)XS, srd, n, npad, d, th, tw, zv, V, L.slab, (const double*)YV, SUM, L.n0r, L.nsum);
+    });
+    CHECK_LAUNCH("pgrad_row_kernel");
+    // V Y^T (Y^T zero padded to whole tiles)
+    hipLaunchKernelGGL(pgrad_pack_yt_kernel, dim3((L.ppad + 255) / 256, npad), dim3(256), 0, st, Y, p, n, L.ppad, YT);
+    CHECK_LAUNCH("pgrad_pack_yt_kernel");
+    GemmArgs gy;
+    gy.A = V; gy.B = YT; gy.C = VY; gy.ldA = npad; gy.ldB = gy.ldC = L.ppad;
+    gy.sA = L.slab; gy.sB = 0; gy.sC = (size_t)L.n0r * L.ppad;
+    gy.nb = L.ppad / (2 * TS); gy.p0 = L.n0r / (2 * TS); gy.p1 = L.nb / 2; gy.p2 = gy.p3 = 0;
+    rc = launch_gemm<double, OP_HESS_G, 128>(st, gy, gy.p0 * gy.nb, qg);
+    if (rc) return rc;
+    const size_t ko = (size_t)k0 * ldo;
+    hipLaunchKernelGGL(pgrad_final_kernel, dim3((n0 + 255) / 256, qg), dim3(256), 0, st, (const double*)SUM, L.n0r, L.nsum,
+                       (const double*)RD, (const double*)VY, L.ppad, n0, d, p, th, tw, ldo, dghat + ko * m, dgvar + ko * m,
+                       dnoise + ko * p);
+    CHECK_LAUNCH("pgrad_final_kernel");
+    return 0;
+}
+
 int check_sel(int n_ref, int n_cand, int size) {
     int rc = check_vr(n_ref, n_cand);
     if (rc) return rc;
@@ -5738,6 +6015,40 @@ int lcgp_nll_hess(void* stream, int dtype, int kernel_id, int n, int d, int p, i
     Ws w = carve(dtype, n, d, p, q_local, (void*)workspace);
     w.kern = kernel_id;
     return do_nll_hess((hipStream_t)stream, w, x, (const double*)Y, sr, theta, k0, q_group, (char*)scratch, out);
+}
+
+static int check_predict_paramgrad(int dtype, int n0) {
+    if (dtype == LCGP_F32) return bad("lcgp_predict_paramgrad is float64 only (the variance derivatives are differences that cancel): "
+                                      "evaluate on a float64 workspace");
+    if (n0 < 1 || n0 > 65535) return bad("n0 must be in [1, 65535]: pass the new inputs in chunks");
+    return 0;
+}
+
+int lcgp_predict_paramgrad_scratch_bytes(int dtype, int n, int d, int p, int q_group, int n0, size_t* bytes) {
+    int rc = check_common(dtype, n, d, p, q_group);
+    if (rc) return rc;
+    if ((rc = check_predict_paramgrad(dtype, n0))) return rc;
+    if (!bytes) return bad("bytes is NULL");
+    *bytes = pgrad_carve(n, d, p, q_group, n0).total;
+    return 0;
+}
+
+int lcgp_predict_paramgrad(void* stream, int dtype, int kernel_id, int n, int d, int p, int q_local, const void* x, const void* Y,
+                           const void* sr, const double* theta, const void* workspace, int k0, int q_group, int n0, const void* x0,
+                           int same, void* scratch, double* ghat, double* gvar, double* dghat, double* dgvar, double* dghat_noise,
+                           int out_stride) {
+    int rc = check_common(dtype, n, d, p, q_local, kernel_id);
+    if (rc) return rc;
+    if ((rc = check_predict_paramgrad(dtype, n0))) return rc;
+    if (k0 < 0 || q_group < 1 || k0 + q_group > q_local) return bad("k0 / q_group must select components inside [0, q_local)");
+    if (!x || !Y || !theta || !workspace || !x0 || !scratch || !ghat || !gvar || !dghat || !dgvar || !dghat_noise)
+        return bad("NULL pointer");
+    if (out_stride != 0 && out_stride < n0) return bad("out_stride must be 0 (= n0) or >= n0");
+    if (same < 0 || (same > 0 && (long long)same - 1 + n0 > n)) return bad("same: the rows of x0 must be training inputs same - 1 .. same - 2 + n0");
+    Ws w = carve(dtype, n, d, p, q_local, (void*)workspace);
+    w.kern = kernel_id;
+    return do_predict_paramgrad((hipStream_t)stream, w, x, (const double*)Y, sr, theta, k0, q_group, n0, x0, same, (char*)scratch,
+                                ghat, gvar, dghat, dgvar, dghat_noise, out_stride ? out_stride : n0);
 }
 
 int lcgp_plan_bytes(int dtype, int n, int q_local, int with_inverse, const lcgp_sched* sched, size_t* bytes) {

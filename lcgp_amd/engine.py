@@ -257,6 +257,54 @@ class HotPathEngine:
         Chunked like predict_block (PREDICT_CHUNK rows per call) and sharing its scratch."""
         return self._predict_chunks(x0s, False, True)
 
+    def predict_paramgrad_block(self, x0s, same=False, q_group=None):
+        """(block, dk, dn) float64 DEVICE tensors for standardised x0s, from the factorisation of the last evaluate() -- which
+        is only read (lcgp_predict_paramgrad): block (2, q_local, n0) = [ghat; gvar], bitwise predict_block(x0s, same) while both
+        take one pass; dk (2, q_local, n0, d + 2) = [dghat; dgvar], the derivatives in the component's CONSTRAINED kernel
+        parameters [ell_0 .. ell_{d-1}, scale, nug]; dn (q_local, n0, p) = d ghat / d built noise parameters (gvar has none).
+        float64 engines only.  x0s goes in chunks of PREDICT_CHUNK rows, the local components in groups as large as the free
+        device memory allows (q_group: at most that many, for tests; results are bitwise independent of the grouping): the
+        scratch holds 2 chunk_pad npad + npad^2 doubles per component processed at once.  Raises ValueError when even one
+        component does not fit."""
+        torch = self.torch
+        if self._theta_last is None:
+            raise RuntimeError("predict_param_grad() needs a preceding evaluate() at the current parameters")
+        if self.dtype != _hip.F64:
+            raise RuntimeError("the parameter derivatives of the prediction are float64 only: evaluate on a float64 engine")
+        x0s = np.ascontiguousarray(x0s, np.float64)
+        n0, d, m = x0s.shape[0], self.d, self.d + 2
+        assert x0s.ndim == 2 and x0s.shape[1] == d and n0 >= 1
+        chunk = min(n0, PREDICT_CHUNK)
+        with torch.cuda.device(self.device):
+            free, _ = torch.cuda.mem_get_info(self.device)
+            free += torch.cuda.memory_reserved(self.device) - torch.cuda.memory_allocated(self.device)
+            free += 0 if self._scratch is None else self._scratch.numel()
+            group = self.q_local if q_group is None else max(1, min(int(q_group), self.q_local))
+            while True:
+                nbytes = self._nbytes("lcgp_predict_paramgrad_scratch_bytes", self.dtype, self.n, d, self.p, group, chunk)
+                if group == 1 or nbytes <= free:
+                    break
+                group = (group + 1) // 2
+            scp = self._p(self._grow_scratch(nbytes, ("the parameter derivatives of %d new inputs per pass" % chunk,
+                                                      "one n x n matrix and two of %d x n per component" % chunk,
+                                                      "use fewer training inputs per GPU or lower lcgp_amd.engine.PREDICT_CHUNK")))
+            x0d = torch.as_tensor(x0s).to(self.device).contiguous()
+            out = torch.empty((2, self.q_local, n0), dtype=torch.float64, device=self.device)
+            dk = torch.empty((2, self.q_local, n0, m), dtype=torch.float64, device=self.device)
+            dn = torch.empty((self.q_local, n0, self.p), dtype=torch.float64, device=self.device)
+            st = self._stream()
+            for lo in range(0, n0, chunk):
+                rows = min(chunk, n0 - lo)
+                for k0 in range(0, self.q_local, group):
+                    _hip.check(self.lib.lcgp_predict_paramgrad(
+                        st, self.dtype, self.kernel_id, self.n, d, self.p, self.q_local, self._p(self.x), self._p(self.Y),
+                        self._p(self.sr), self._p(self.theta_dev), self._p(self.workspace), k0, min(group, self.q_local - k0), rows,
+                        C.c_void_p(x0d.data_ptr() + 8 * lo * d), (1 + lo) if same else 0, scp,
+                        C.c_void_p(out[0].data_ptr() + 8 * lo), C.c_void_p(out[1].data_ptr() + 8 * lo),
+                        C.c_void_p(dk[0].data_ptr() + 8 * lo * m), C.c_void_p(dk[1].data_ptr() + 8 * lo * m),
+                        C.c_void_p(dn.data_ptr() + 8 * lo * self.p), n0), "lcgp_predict_paramgrad")
+            return out, dk, dn
+
     def predict_hess_block(self, x0s):
         """(block, jac, hess) float64 DEVICE tensors for standardised x0s, from the factorisation of the last evaluate():
         block (2, q_local, n0) and jac (2, q_local, n0, d) bitwise those of predict_grad_block(x0s); hess (2, q_local, n0,

@@ -166,6 +166,77 @@ class _VrFn(torch.autograd.Function):
         return gx.reshape(shape).to(device=dev, dtype=dt), None, None
 
 
+# rows of new inputs per pass of param_variance: bounds the (p, rows, P) Jacobian it holds (p P LAPLACE_CHUNK doubles)
+LAPLACE_CHUNK = 256
+
+
+def param_jacobians(ghat, gvar, dghat, dgvar, dnoise, W, noise, scale, offset, error_structure, jac=None, latent=False,
+                    mean_only=False):
+    """The host map of predict_param_grad, a pure function of the latent arrays: ghat, gvar (q, n0); dghat, dgvar (q, n0, d + 2)
+    in each component's constrained [ell_0 .. ell_{d-1}, scale, nug]; dnoise (q, n0, p) = d ghat / d built noise parameters t_b;
+    (W, noise, scale, offset) of LCGP._output_map() (W[k, a] ~ exp(t_a / 2), noise_a ~ exp(t_a)); error_structure: the sizes of
+    the groups of outputs that share one lsigma2s.  Returns (dypred, dypredvar, dyconfvar), each (p, n0, P), P = q (d + 2) +
+    groups, in the flat order [ell (q d, component-major), scale (q), nug (q), lsigma2s]:
+        d ypred_a / d theta_k = scale_a W[k, a] d ghat_k       d yconfvar_a / d theta_k = scale_a^2 W[k, a]^2 d gvar_k
+        d ypred_a / d t_b     = scale_a sum_k W[k, a] d_tb ghat_k + delta_ab (ypred_a - offset_a) / 2
+        d yconfvar_a / d t_b  = delta_ab yconfvar_a            d ypredvar_a / d t_b adds delta_ab scale_a^2 noise_a
+    the t_b folded through the groups.  jac (P,): d constrained / d unconstrained, multiplied onto the last axis (None: the
+    constrained space).  latent=True: (dghat, dgvar) (q, n0, P) instead.  mean_only=True: dypred alone."""
+    ghat, gvar, dghat, dgvar, dnoise = (np.asarray(a, F64) for a in (ghat, gvar, dghat, dgvar, dnoise))
+    q, n0, m = dghat.shape
+    d = m - 2
+    es = np.asarray(error_structure, int)
+    starts = np.r_[0, np.cumsum(es)[:-1]]
+    o = q * m
+    P = o + len(es)
+    p = W.shape[1]
+    cols = [np.r_[k * d + np.arange(d), q * d + k, q * d + q + k] for k in range(q)]
+
+    def finish(*arrays):
+        return tuple(a if jac is None else a * jac for a in arrays)
+
+    if latent:
+        lg, lv = np.zeros((q, n0, P), F64), np.zeros((q, n0, P), F64)
+        for k in range(q):
+            lg[k][:, cols[k]] = dghat[k]
+            lv[k][:, cols[k]] = dgvar[k]
+        lg[:, :, o:] = np.add.reduceat(dnoise, starts, axis=2)
+        return finish(lg, lv)
+    dyp = np.zeros((p, n0, P), F64)
+    for k in range(q):
+        dyp[:, :, cols[k]] = (scale * W[k])[:, None, None] * dghat[k][None]
+    tb = np.einsum('ka,kib->aib', W, dnoise) * scale[:, None, None]
+    half = 0.5 * scale[:, None] * (W.T @ ghat)                       # (ypred - offset) / 2
+    tb[np.arange(p), :, np.arange(p)] += half
+    dyp[:, :, o:] = np.add.reduceat(tb, starts, axis=2)
+    if mean_only:
+        return finish(dyp)[0]
+    dyc = np.zeros((p, n0, P), F64)
+    for k in range(q):
+        dyc[:, :, cols[k]] = (scale * W[k])[:, None, None] ** 2 * dgvar[k][None]
+    yconfvar = (W.T ** 2 @ gvar) * (scale ** 2)[:, None]
+    group = np.repeat(np.arange(len(es)), es)                        # the group of output a
+    dyv = dyc.copy()
+    dyc[np.arange(p), :, o + group] = yconfvar
+    dyv[np.arange(p), :, o + group] = yconfvar + (scale ** 2 * noise)[:, None]
+    return finish(dyp, dyv, dyc)
+
+
+def param_variance(ghat, dghat, dnoise, W, scale, error_structure, jac, cov):
+    """yparamvar (p, n0) of predict_laplace: J cov J^T per output and new input, J = d ypred / d unconstrained vector
+    (param_jacobians), formed over LAPLACE_CHUNK new inputs at a time"""
+    p, n0 = W.shape[1], np.shape(ghat)[1]
+    out = np.empty((p, n0), F64)
+    zero = np.zeros(p, F64)
+    for lo in range(0, n0, LAPLACE_CHUNK):
+        hi = min(n0, lo + LAPLACE_CHUNK)
+        # (gvar, dgvar, noise and offset do not enter the mean's Jacobian)
+        J = param_jacobians(ghat[:, lo:hi], ghat[:, lo:hi], dghat[:, lo:hi], dghat[:, lo:hi], dnoise[:, lo:hi], W, zero, scale, zero,
+                            error_structure, jac, mean_only=True)
+        out[:, lo:hi] = np.einsum('aip,aip->ai', J @ cov, J)
+    return out
+
+
 class LaplaceResult:
     """What LCGP.laplace() returns: `hessian` (the unconstrained Hessian of the objective), its `eigenvalues` (ascending),
     `cov` = hessian^-1 and `stderr`, the delta-method standard errors of the constrained parameters shaped like get_param()."""
@@ -753,11 +824,10 @@ class LCGP:
     # =============================================================================================
     # exact Hessian of the objective in the parameters (beyond the reference, which would nest two tapes around neglpost)
     # =============================================================================================
-    def _hessian_blocks(self):
-        """((q, (d + 2)^2 + (d + 2) p + p^2) numpy array of the per-component blocks of lcgp_nll_hess, constrained gradient)
-        at the current parameters.  The factorisation in the workspace is reused when it is the current one and float64;
-        otherwise one evaluation runs first (a float32 model: on its float64 engine).  Every rank computes its components'
-        rows; one reduction of the zero-padded block gathers them (_gather_components), failures go through _agree."""
+    def _ensure_aux64(self):
+        """the engine whose workspace holds the FLOAT64 factorisation of the current parameters (None on a rank without
+        components): the one in the workspace when it is current and float64, otherwise one evaluation runs first (a float32
+        model: on its float64 engine)"""
         eng = self._get_engine()
         if not (self._aux_valid and (self._dtype == 'float64' or self._last_eval_float64)):
             if self._dtype == 'float64' or self._float64_only:
@@ -769,7 +839,14 @@ class LCGP:
                     self._run_path()
                 finally:
                     self._float64_only = False
-        aux = self._aux_engine if eng is not None else None
+        return self._aux_engine if eng is not None else None
+
+    def _hessian_blocks(self):
+        """((q, (d + 2)^2 + (d + 2) p + p^2) numpy array of the per-component blocks of lcgp_nll_hess, constrained gradient)
+        at the current parameters.  The factorisation in the workspace is reused when it is the current one and float64;
+        otherwise one evaluation runs first (a float32 model: on its float64 engine).  Every rank computes its components'
+        rows; one reduction of the zero-padded block gathers them (_gather_components), failures go through _agree."""
+        aux = self._ensure_aux64()
         d, p = int(self.d), int(self.p)
         width = (d + 2) * (d + 2) + (d + 2) * p + p * p
         blocks = self._gather_components(self._agree(lambda: None if aux is None else aux.nll_hess_block()), (width,))
@@ -868,6 +945,75 @@ class LCGP:
         stderr = (_t(se[:q * d].reshape(q, d)), _t(se[q * d:q * d + q]), _t(np.repeat(se[q * d + 2 * q:], es)),
                   _t(se[q * d + q:q * d + 2 * q]))
         return LaplaceResult(H, ev, cov, stderr)
+
+    # =============================================================================================
+    # parameter derivatives of the prediction and the Laplace-propagated parameter uncertainty (the reference: a gradient tape
+    # around predict over the trainable variables)
+    # =============================================================================================
+    def _latent_param_grad(self, x0):
+        """(ghat, gvar (q, n0), dghat, dgvar (q, n0, d + 2), dnoise (q, n0, p)) for raw-scale x0: the latent prediction and its
+        derivatives in each component's CONSTRAINED kernel parameters [ell, scale, nug] and in the built noise parameters, from
+        the float64 factorisation of the current parameters (lcgp_predict_paramgrad on the local components, ONE reduction of
+        the zero-padded block gathers them, failures go through _agree).  x0 equal to the training set carries predict()'s
+        nugget entry."""
+        x0s, same = self._standardise_x0(x0)
+        n0, m, p = x0s.shape[0], int(self.d) + 2, int(self.p)
+        aux = self._ensure_aux64()
+
+        def local():
+            if aux is None:
+                return None
+            blk, dk, dn = aux.predict_paramgrad_block(x0s, same)
+            return torch.cat([blk.permute(1, 2, 0), dk.permute(1, 2, 0, 3).reshape(blk.shape[1], n0, 2 * m), dn], dim=2)
+
+        both = np.asarray(self._gather_components(self._agree(local), (n0, 2 + 2 * m + p)), F64)
+        return both[:, :, 0], both[:, :, 1], both[:, :, 2:2 + m], both[:, :, 2 + m:2 + 2 * m], both[:, :, 2 + 2 * m:]
+
+    def _param_grad_space(self, space):
+        """d constrained / d unconstrained in flat order for space='unconstrained', None for 'constrained'"""
+        if space not in ('unconstrained', 'constrained'):
+            raise ValueError("space must be 'unconstrained' or 'constrained', not %r" % (space,))
+        return self._flat_jacobians()[0] if space == 'unconstrained' else None
+
+    def predict_param_grad(self, x0, space='unconstrained', latent=False):
+        """Jacobians of predict()'s outputs with respect to the parameters, per new input:
+            dypred[a, i, :] = d ypred[a, i] / d flat vector,   dypredvar, dyconfvar likewise      each (p, n0, P), CPU float64
+        in the flat order of loss_and_grad (lLmb, lLmb0, lnugGPs, lsigma2s) and with loss_hessian's `space` convention:
+        'unconstrained' (default) is the vector the optimiser sees, 'constrained' the values get_param() returns (lsigma2s per
+        error-structure group).  latent=True: (dghat, dgvar) (q, n0, P) of the latent components instead, zero in the kernel
+        parameters of the other components.
+        One GPU pass (lcgp_predict_paramgrad) behind the factorisation of the current parameters, which is reused when the
+        workspace holds it (right after fit() no extra evaluation) and only read.  Always float64: a dtype='float32' model
+        evaluates once on its float64 engine and computes there.  x0 equal to the training set follows predict()'s branch
+        (the nugget entry of the cross covariance).  Multi-rank: each rank computes its components, one reduction assembles
+        them, every rank returns the same arrays.  GPU memory: one n x n matrix and two of min(n0, 2048) x n per component
+        processed at a time -- ValueError when not even one fits."""
+        jac = self._param_grad_space(space)
+        ghat, gvar, dghat, dgvar, dnoise = self._latent_param_grad(x0)
+        W, noise, scale, offset = self._output_map()
+        out = param_jacobians(ghat, gvar, dghat, dgvar, dnoise, W, noise, scale, offset, self.diag_error_structure, jac, latent)
+        return tuple(_t(a) for a in out)
+
+    def predict_laplace(self, x0, cov=None):
+        """predict() with the uncertainty of the fitted parameters propagated to first order:
+            (ypred, ypredvar, yconfvar, yparamvar), each (p, n0), CPU float64
+        yparamvar[a, i] = J Sigma J^T with J = d ypred[a, i] / d unconstrained vector (predict_param_grad) and Sigma the
+        covariance of that vector: laplace().cov by default, or `cov`, a symmetric (P, P) array in the unconstrained space
+        (from MCMC, say).  yparamvar is ADDED to both variances -- the first-order law of total variance, Var ~ E[var | theta] +
+        Var[E | theta]; ypred is predict()'s, bit for bit.  A Hessian that is not positive definite raises laplace()'s
+        LinAlgError.  The quadratic form is taken over chunks of new inputs: the (p, n0, P) Jacobian is never held whole."""
+        ypred, ypredvar, yconfvar = self.predict(x0)          # (first: a float32 model predicts on its own engine)
+        if cov is None:
+            cov = self.laplace().cov
+        cov = np.asarray(cov, F64)
+        jac = self._param_grad_space('unconstrained')
+        if cov.shape != (jac.size, jac.size):
+            raise ValueError('predict_laplace: cov must be (%d, %d) in the unconstrained space, not %r' % (jac.size, jac.size, cov.shape))
+        ghat, gvar, dghat, dgvar, dnoise = self._latent_param_grad(x0)
+        W, noise, scale, offset = self._output_map()
+        yparamvar = param_variance(ghat, dghat, dnoise, W, scale, self.diag_error_structure, jac, cov)
+        pv = _t(yparamvar)
+        return ypred, ypredvar + pv, yconfvar + pv, pv
 
     def fit(self, verbose=False):
         """scipy L-BFGS-B with default options on the unconstrained vector (lcgp.py:537-540).

@@ -447,6 +447,53 @@ int lcgp_sample_scratch_bytes(int dtype, int n0, int q_local, int S, size_t* byt
 int lcgp_sample_latent(void* stream, int dtype, int n0, int d, int p, int q_local, int S, void* cov_workspace,
                        const void* eps, const double* ghat, int ldg, void* scratch, double* out);
 
+/* Conditioning on new runs without refactorising (no counterpart in the reference; what BoTorch calls
+ * condition_on_observations).  Input: the workspace of the last lcgp_nll_grad, which is only READ -- every other post-fit
+ * entry stays valid.  For local component k, m new UNIQUE inputs xn (standardised, none of them a training input) with
+ * replicate counts r_i and latent observations t_i, in the notation of lcgp_predict (W_k = L_k^-1):
+ *     U_n  = (c(xn, x) o sr^T) W_k^T                      (m x npad; cross rows without nugget: lcgp_predict, same = 0)
+ *     S    = C(xn, xn) - D_k U_n U_n^T + diag(tau),       C(xn, xn) with the nugget on its diagonal (lcgp_predict_cov's C00),
+ *            tau_i = 1 / (D_k r_i)                        (the tau of lcgp_variance_reduction)
+ *     L_S L_S^T = S,   v = L_S^-1 (t - ghat_k(xn))
+ *   t[k, i] = psi_k . y_i / D_k with y_i the standardised output (the replicate mean on the replicated path): the entry of b_k
+ *   that lcgp_nll_grad would form for that input as a training column, divided by D_k sr_i.
+ * and for n0 new inputs x0:
+ *     Sigma_0n = C^x(x0, xn) - D_k U_0 U_n^T   (n0 x m, no nugget),   T = Sigma_0n L_S^-T
+ *     ghat'[k, :] = ghat[k, :] + T v           gvar'[k, :] = gvar[k, :] - rowsum(T o T)
+ * which equals lcgp_predict(same = 0) of a model built on the augmented data at the same theta, to rounding.
+ *
+ *   1. lcgp_condition_prepare: the launches of lcgp_predict for xn (U_n into `state`, ghat(xn)), those of lcgp_predict_cov for
+ *      S (into the matrix slot of `cond_workspace`, lcgp_workspace_bytes(dtype, m, d, p, q_local) bytes, with tau_i on the
+ *      diagonal instead of a jitter), the unchanged factorisation and triangular inverse there, a dense copy of L_S^-1 into
+ *      `state` with zeros above the diagonal (the product that forms T reads whole tiles), and v by one wave per row.
+ *      info: q_local device ints, 0 or 1 + the first failing pivot of S (nothing is jittered; the state is then unusable).
+ *      t: q_local x m doubles (device).  r: m doubles (device) or NULL (all ones).
+ *   2. lcgp_condition_predict, once per chunk of new inputs: ghat / gvar by the launches of lcgp_predict(same = 0), the kernel
+ *      values C^x(x0, xn), ONE launch of the MFMA tile kernel on all n0pad / 64 x mpad / 64 tiles with K = npad (operand mode
+ *      OP_COND_CROSS, 64 x 64 tiles), T by the product of lcgp_predict's U, and a row reduction in lcgp_predict's order.
+ * `state`: lcgp_condition_state_bytes bytes = q_local (mpad npad + mpad^2) elements + q_local mpad doubles (mpad = m rounded
+ *   up to 128).  `scratch`: lcgp_condition_scratch_bytes(dtype, n, q_local, m, n0) bytes, n0 = 0 for the preparation alone
+ *   (q_local mpad npad elements), otherwise the larger of that and 2 q_local n0pad (npad + mpad) elements (n0pad as in
+ *   lcgp_predict); `scratch_bytes` is what the caller allocated and is checked.
+ * Products in the dtype, the reductions in double, fixed order, no atomics: results are bitwise independent of the content of
+ * scratch, state and cond_workspace on entry and, between calls on the same tile size (n0 below 128 in both, or not), of how a
+ * caller splits the rows of x0.  They are independent of q_local as far as the factorisation and inverse of S are: those are
+ * scheduled for q_local matrices of order m, and the default schedule picks 64- or 128-row tiles from q_local x the tile count
+ * (lcgp_sched: syrk_small_tiles, trtri_small_tiles, trtri_level_small).  Up to mpad = 128 there is one schedule; beyond it two
+ * values of q_local agree bitwise where they pick the same tile sizes, as lcgp_cv_* documents for its batch.
+ * Flops per component: preparation mpad npad^2 (U_n) + mpad^2 npad (S) + mpad^3 (factor and inverse); prediction: those of
+ * lcgp_predict plus 2 n0pad mpad npad (Sigma_0n) + n0pad mpad^2 (T). */
+int lcgp_condition_scratch_bytes(int dtype, int n, int q_local, int m, int n0, size_t* bytes /*host out*/);
+int lcgp_condition_state_bytes(int dtype, int n, int d, int q_local, int m, size_t* bytes /*host out*/);
+int lcgp_condition_prepare(void* stream, int dtype, int kernel_id, int n, int d, int p, int q_local,
+                           const void* x, const void* sr, const double* theta, const void* workspace,
+                           int m, const void* xn, const double* t, const double* r /*or NULL*/,
+                           void* scratch, size_t scratch_bytes, void* cond_workspace, void* state, int* info);
+int lcgp_condition_predict(void* stream, int dtype, int kernel_id, int n, int d, int p, int q_local,
+                           const void* x, const void* sr, const double* theta, const void* workspace,
+                           const void* state, int m, const void* xn, int n0, const void* x0,
+                           void* scratch, size_t scratch_bytes, double* ghat, double* gvar, int out_stride);
+
 /* Closed-form cross-validation at fixed parameters (no counterpart in the reference).  Input: the workspace of the last
  * lcgp_nll_grad, whose V slot holds a = A_k^-1 (A_k = I + D_k (C_k o s s^T), s = sr, ones when sr is NULL) and whose vectors
  * hold b_k and z_k = A_k^-1 b_k.  With K_k = C_k + (D_k S^2)^-1 (S = diag(s)), K_k^-1 = D_k S a S, so for a set B of m

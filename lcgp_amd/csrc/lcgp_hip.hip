@@ -870,7 +870,7 @@ __global__ __launch_bounds__(256, 2) void leaf_kernel(T* __restrict__ M, T* __re
 // and staged in LDS as [k][m] (KT = 16 k rows per stage, double buffered through registers).
 // ---------------------------------------------------------------------------------------------------
 enum GemmOp { OP_SYRK = 1, OP_TRTRI_T = 2, OP_TRTRI_W = 3, OP_LAUUM = 4, OP_PRED_U = 5, OP_PRED_COV = 6, OP_PRED_V = 7, OP_VR = 8,
-              OP_VG_P = 9, OP_VG_G = 10, OP_HESS_G = 11 };
+              OP_VG_P = 9, OP_VG_G = 10, OP_HESS_G = 11, OP_COND_CROSS = 12 };
 enum Lay { MK = 0, KM = 1 };
 
 struct GemmArgs {
@@ -888,7 +888,7 @@ struct GemmArgs {
     unsigned long long* clk = nullptr;          // OP_LAUUM: the first block (the longest K loop of the launch) leaves its duration
                                                 // in shader-clock cycles and in 10 ns ticks here: the clock the chip held (lcgp_lauum_clock)
     const double* theta = nullptr;              // OP_PRED_COV: theta rows, p1 doubles apart; D_k is element p2 of row k
-                                                // (OP_VR: rows tw apart)
+                                                // (OP_VR: rows tw apart; OP_COND_CROSS: rows p2 apart, D_k element p3)
     // OP_VR (the variance-reduction epilogue; see vr_epilogue): standardised inputs of the A rows (reference set) and of the
     // B rows (candidates), d per row; the weights of the reference rows; the candidates' gvar (ldg per component); the covariance
     // kernel, theta row width, replicates r and the row length of the partial sums (p0 = k tiles, p1 = candidate tiles,
@@ -1365,6 +1365,16 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& g, const int lin /*blo
         B0 = Bb + (size_t)rt * TM * g.ldB; dB = TM;
         nkt = g.p0;
         Ct = Cb + (size_t)ct * TM * g.ldC + (size_t)rt * TM;
+    } else if constexpr (OP == OP_COND_CROSS) {
+        // C[r, c] -= D_k sum_{kt < p0} U_0[r, kt] U_n[c, kt]^T over ALL (row tile r of the new inputs, column tile c of the
+        // conditioning inputs), p1 column tiles per row tile: the rectangular two-set sibling of OP_PRED_COV
+        // (lcgp_condition_predict; C holds the kernel values C^x(x0, xn) on entry)
+        const int c = bid % g.p1, r = bid / g.p1;
+        A0 = Ab + (size_t)r * TM * g.ldA; dA = TM;
+        B0 = Bb + (size_t)c * TM * g.ldB; dB = TM;
+        nkt = g.p0;
+        Ct = Cb + (size_t)r * TM * g.ldC + (size_t)c * TM;
+        accumulate = true;          // (alpha = -D_k is read behind the k loop, as in OP_PRED_COV)
     } else if constexpr (OP == OP_VG_G || OP == OP_HESS_G) {
         // G[m, c] = sum_{kt < p1} S[m, kt] U_ref[kt, c]      (S = n_candpad x n_refpad, U_ref = n_refpad x npad: no triangle)
         // OP_HESS_G: the same dense product with dense square operands, G_i = A^-1 d_iA and Q = Y A^-1 of lcgp_nll_hess (A^-1
@@ -1439,7 +1449,8 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& g, const int lin /*blo
     // only add exact zeros: it skips the stage's fragment reads and MFMAs (one wave-uniform test per stage, nothing
     // else changes; bit-identical results: the zeros are stored zeros).  LAUUM / TRTRI_W: 24 of the 64 (wave, stage)
     // pairs of such a tile, TRTRI_T / PRED_U / PRED_V: 16.
-    constexpr bool HAS_TRI = OP != OP_SYRK && OP != OP_PRED_COV && OP != OP_VR && OP != OP_VG_P && OP != OP_VG_G && OP != OP_HESS_G;
+    constexpr bool HAS_TRI = OP != OP_SYRK && OP != OP_PRED_COV && OP != OP_VR && OP != OP_VG_P && OP != OP_VG_G && OP != OP_HESS_G &&
+                             OP != OP_COND_CROSS;
     const int tri_first = HAS_TRI ? (nkt - 1) * SPT : nst;
     // the wave is idle in the stages [dead_lo, dead_hi) of the k loop (two scalars per wave)
     int dead_lo = nst, dead_hi = nst;
@@ -1606,6 +1617,7 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& g, const int lin /*blo
         return;
     }
     if constexpr (OP == OP_PRED_COV) alpha = -g.theta[(size_t)k * g.p1 + g.p2];
+    if constexpr (OP == OP_COND_CROSS) alpha = -g.theta[(size_t)k * g.p2 + g.p3];
 #pragma unroll
     for (int mi = 0; mi < MIM; ++mi)
 #pragma unroll
@@ -3653,6 +3665,201 @@ int do_sample(hipStream_t st, const Ws& cw, int S, const void* eps, const double
     hipLaunchKernelGGL((draw_out_kernel<T>), dim3((cw.n + 255) / 256, S, cw.q), dim3(256), 0, st, (const T*)G, n0pad, slab, S,
                        cw.n, ghat, ldg, out);
     CHECK_LAUNCH("draw_out_kernel");
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------
+// Conditioning on new runs without refactorising (no counterpart in the reference): lcgp_condition_prepare /
+// lcgp_condition_predict (lcgp_hip.h).  The fitted workspace is only read.  Per local component, for m new unique inputs xn:
+//     U_n = (c(xn, x) o sr^T) W^T,  S = C(xn, xn) - D U_n U_n^T + diag(1 / (D r_i)),  L_S L_S^T = S,  v = L_S^-1 (t - ghat(xn))
+// and for new inputs x0:  Sigma_0n = C^x(x0, xn) - D U_0 U_n^T,  T = Sigma_0n L_S^-T,  ghat += T v,  gvar -= rowsum(T o T).
+// S lives in the matrix slot of a SECOND workspace carved for n = m (as the joint covariance's); the state keeps U_n, a dense
+// copy of L_S^-1 with its strict upper triangle zeroed (the product that forms T reads whole tiles) and v.
+// ---------------------------------------------------------------------------------------------------
+struct CondLay {
+    int npad, mpad;
+    size_t off_U, off_W, off_v, total;      // state: U_n (q mpad npad elements), L_S^-1 (q mpad^2 elements), v (q mpad doubles)
+};
+
+inline CondLay cond_carve(int dtype, int n, int q, int m) {
+    CondLay L;
+    const size_t esz = dtype == LCGP_F64 ? 8 : 4;
+    L.npad = round_up(n, 2 * TS);
+    L.mpad = cov_pad(m);
+    size_t o = 0;
+    L.off_U = o; o = align256(o + (size_t)q * L.mpad * L.npad * esz);
+    L.off_W = o; o = align256(o + (size_t)q * L.mpad * L.mpad * esz);
+    L.off_v = o; o = align256(o + (size_t)q * L.mpad * sizeof(double));
+    L.total = o;
+    return L;
+}
+
+// scratch of the preparation: X of the conditioning inputs (q mpad npad elements), then ghat / gvar there (2 q mpad doubles)
+inline size_t cond_prepare_scratch(int dtype, int n, int q, int m) {
+    const size_t esz = dtype == LCGP_F64 ? 8 : 4;
+    const size_t mpad = cov_pad(m), npad = round_up(n, 2 * TS);
+    return align256((size_t)q * mpad * npad * esz) + align256(2 * (size_t)q * mpad * sizeof(double));
+}
+
+// scratch of a prediction pass: X and U of the new inputs (2 q n0pad npad elements), Sigma_0n and T (2 q n0pad mpad elements)
+inline size_t cond_predict_scratch(int dtype, int n, int q, int m, int n0) {
+    const size_t esz = dtype == LCGP_F64 ? 8 : 4;
+    const size_t mpad = cov_pad(m), npad = round_up(n, 2 * TS), n0pad = predict_pad(n0);
+    return align256(2 * (size_t)q * n0pad * npad * esz) + align256(2 * (size_t)q * n0pad * mpad * esz);
+}
+
+// diagonal of S = Sigma_nn + diag(tau), tau_i = 1 / (D_k r_i) (r = NULL: ones), and the identity of the padding
+template <typename T>
+__global__ __launch_bounds__(256) void cond_diag_kernel(T* __restrict__ M, size_t mat, int m, int mpad,
+                                                        const double* __restrict__ theta, int tw, int d,
+                                                        const double* __restrict__ r) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x, k = blockIdx.y;
+    if (i >= mpad) return;
+    T* e = M + (size_t)k * mat + (size_t)i * mpad + i;
+    const double D = theta[(size_t)k * tw + d + 2];
+    *e = i < m ? (T)((double)*e + 1.0 / (D * (r ? r[i] : 1.0))) : (T)1;
+}
+
+// dense copy of the lower triangle of L_S^-1 (W slot of the cond workspace) into the state, zeros above the diagonal
+template <typename T>
+__global__ __launch_bounds__(256) void cond_copy_kernel(const T* __restrict__ W, size_t mat, int mpad, T* __restrict__ dst) {
+    const int i = blockIdx.x, j = blockIdx.y * blockDim.x + threadIdx.x, k = blockIdx.z;     // (rows on grid.x: no 65535 limit)
+    if (j >= mpad) return;
+    const size_t at = (size_t)k * mat + (size_t)i * mpad + j;
+    dst[at] = j <= i ? W[at] : (T)0;
+}
+
+// v[k, i] = sum_{j <= i} L_S^-1[i, j] (t[k, j] - ghat_n[k, j])    (one wave per row i; zero on the padding)
+template <typename T>
+__global__ __launch_bounds__(64) void cond_v_kernel(const T* __restrict__ Wi, size_t mat, int m, int mpad,
+                                                    const double* __restrict__ t, const double* __restrict__ gh, int ldg,
+                                                    double* __restrict__ v) {
+    const int i = blockIdx.x, k = blockIdx.y, lane = threadIdx.x;
+    double s = 0.0;
+    if (i < m) {
+        const T* row = Wi + (size_t)k * mat + (size_t)i * mpad;
+        for (int j = lane; j <= i; j += 64) s += (double)row[j] * (t[(size_t)k * m + j] - gh[(size_t)k * ldg + j]);
+        for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
+    }
+    if (lane == 0) v[(size_t)k * mpad + i] = s;
+}
+
+// ghat[k, r] += sum_j T[r, j] v[k, j] ;  gvar[k, r] -= sum_j T[r, j]^2        (one wave per row, pred_reduce_kernel's order)
+template <typename T>
+__global__ __launch_bounds__(64) void cond_reduce_kernel(const T* __restrict__ Tm, size_t slab, int ld, int m,
+                                                         const double* __restrict__ v, int mpad, int ldo,
+                                                         double* __restrict__ ghat, double* __restrict__ gvar) {
+    const int r = blockIdx.x, k = blockIdx.y, lane = threadIdx.x;
+    const T* Tr = Tm + (size_t)k * slab + (size_t)r * ld;
+    const double* vk = v + (size_t)k * mpad;
+    double s1 = 0.0, s2 = 0.0;
+    for (int j = lane; j < m; j += 64) {
+        const double u = (double)Tr[j];
+        s1 += u * vk[j];
+        s2 += u * u;
+    }
+    for (int off = 32; off > 0; off >>= 1) { s1 += __shfl_xor(s1, off); s2 += __shfl_xor(s2, off); }
+    if (lane == 0) { ghat[(size_t)k * ldo + r] += s1; gvar[(size_t)k * ldo + r] -= s2; }
+}
+
+template <typename T>
+int do_condition_prepare(hipStream_t st, const Ws& w, const void* x, const void* sr, const double* theta, int m, const void* xn,
+                         const double* t, const double* r, void* scratch, const Ws& cw, void* state, int* info) {
+    const int dtype = sizeof(T) == 4 ? LCGP_F32 : LCGP_F64;
+    const CondLay L = cond_carve(dtype, w.n, w.q, m);
+    const int mpad = L.mpad, tw = w.d + 3 + w.p;
+    const size_t slab = (size_t)mpad * w.npad;
+    T* X = (T*)scratch;
+    double* gh = (double*)((char*)scratch + align256((size_t)w.q * slab * sizeof(T)));
+    double* gv = gh + (size_t)w.q * mpad;
+    T* Un = (T*)((char*)state + L.off_U);
+    T* Wi = (T*)((char*)state + L.off_W);
+    double* v = (double*)((char*)state + L.off_v);
+    T* M = (T*)(cw.base + cw.off_M);
+    // U_n and ghat(xn): the launches of lcgp_predict with same = 0 (a conditioning input is a new input)
+    int rc = form_xu<T>(st, w, x, sr, theta, m, mpad, xn, 0, X, Un);
+    if (rc) return rc;
+    hipLaunchKernelGGL((pred_reduce_kernel<T>), dim3(m, w.q), dim3(64), 0, st, (const T*)X, (const T*)Un, slab, slab, w.npad, w.n,
+                       (const T*)(w.base + w.off_z), w.npad, theta, tw, w.d, mpad, gh, gv);
+    CHECK_LAUNCH("pred_reduce_kernel");
+    // S: C(xn, xn) with the nugget on the diagonal, minus D U_n U_n^T over the lower tiles (the launch of lcgp_predict_cov),
+    // plus tau_i on the diagonal
+    ThetaArg dummy;
+    memset(&dummy, 0, sizeof(dummy));
+    for_kern(w.kern, [&](auto kern) {
+        hipLaunchKernelGGL((cross_kernel<T, decltype(kern)::value>), dim3(mpad / TS, mpad / TS, w.q), dim3(256), 0, st, M, mpad, m,
+                           m, w.d, (const T*)xn, (const T*)xn, dummy, theta, 1, (const T*)nullptr, mpad, mpad, tw, cw.mat,
+                           (const int*)nullptr);
+    });
+    CHECK_LAUNCH("cross_kernel");
+    GemmArgs h;
+    h.A = Un; h.B = Un; h.C = M;
+    h.sA = h.sB = slab; h.sC = cw.mat; h.ldA = h.ldB = w.npad; h.ldC = mpad;
+    h.p1 = tw; h.p2 = w.d + 2; h.p3 = 0;
+    h.theta = theta;
+    const int t64 = mpad / TS;
+    h.nb = t64; h.p0 = w.npad / TS;
+    rc = launch_gemm<T, OP_PRED_COV, 64>(st, h, t64 * (t64 + 1) / 2, w.q);
+    if (rc) return rc;
+    hipLaunchKernelGGL((cond_diag_kernel<T>), dim3((mpad + 255) / 256, w.q), dim3(256), 0, st, M, cw.mat, m, mpad, theta, tw, w.d, r);
+    CHECK_LAUNCH("cond_diag_kernel");
+    // L_S and L_S^-1 by the unchanged factorisation and triangular inverse on the second workspace
+    const lcgp_sched sc = default_sched();
+    rc = do_potrf<T>(st, cw, sc);
+    if (rc) return rc;
+    rc = do_trtri<T>(st, cw, sc);
+    if (rc) return rc;
+    hipLaunchKernelGGL(copy_stats_kernel, dim3((w.q + 63) / 64), dim3(64), 0, st, (const double*)(cw.base + cw.off_logdet),
+                       (const int*)(cw.base + cw.off_info), (double*)nullptr, info, w.q);
+    CHECK_LAUNCH("copy_stats");
+    hipLaunchKernelGGL((cond_copy_kernel<T>), dim3(mpad, (mpad + 255) / 256, w.q), dim3(256), 0, st,
+                       (const T*)(cw.base + cw.off_W), cw.mat, mpad, Wi);
+    CHECK_LAUNCH("cond_copy_kernel");
+    hipLaunchKernelGGL((cond_v_kernel<T>), dim3(mpad, w.q), dim3(64), 0, st, (const T*)Wi, (size_t)mpad * mpad, m, mpad, t,
+                       (const double*)gh, mpad, v);
+    CHECK_LAUNCH("cond_v_kernel");
+    return 0;
+}
+
+template <typename T>
+int do_condition_predict(hipStream_t st, const Ws& w, const void* x, const void* sr, const double* theta, const void* state, int m,
+                         const void* xn, int n0, const void* x0, void* scratch, double* ghat, double* gvar, int ldo) {
+    const int dtype = sizeof(T) == 4 ? LCGP_F32 : LCGP_F64;
+    const CondLay L = cond_carve(dtype, w.n, w.q, m);
+    const int mpad = L.mpad, tw = w.d + 3 + w.p, n0pad = predict_pad(n0);
+    const size_t slab = (size_t)n0pad * w.npad, cslab = (size_t)n0pad * mpad;
+    const T* Un = (const T*)((const char*)state + L.off_U);
+    const T* Wi = (const T*)((const char*)state + L.off_W);
+    const double* v = (const double*)((const char*)state + L.off_v);
+    T* U0 = (T*)scratch + slab * w.q;
+    T* Sg = (T*)((char*)scratch + align256(2 * (size_t)w.q * slab * sizeof(T)));
+    T* Tm = Sg + cslab * w.q;
+    // U_0, ghat, gvar exactly as lcgp_predict(same = 0)
+    int rc = do_predict<T>(st, w, x, sr, theta, n0, x0, 0, scratch, ghat, gvar, ldo);
+    if (rc) return rc;
+    // Sigma_0n = C^x(x0, xn) - D U_0 U_n^T on all tiles (zero on the padding rows and columns)
+    ThetaArg dummy;
+    memset(&dummy, 0, sizeof(dummy));
+    for_kern(w.kern, [&](auto kern) {
+        hipLaunchKernelGGL((cross_kernel<T, decltype(kern)::value>), dim3(mpad / TS, n0pad / TS, w.q), dim3(256), 0, st, Sg, mpad, n0,
+                           m, w.d, (const T*)x0, (const T*)xn, dummy, theta, 0, (const T*)nullptr, n0pad, mpad, tw, cslab,
+                           (const int*)nullptr);
+    });
+    CHECK_LAUNCH("cross_kernel");
+    GemmArgs h;
+    h.A = U0; h.B = Un; h.C = Sg;
+    h.sA = slab; h.sB = (size_t)mpad * w.npad; h.sC = cslab; h.ldA = h.ldB = w.npad; h.ldC = mpad;
+    h.nb = 0; h.p0 = w.npad / TS; h.p1 = mpad / TS; h.p2 = tw; h.p3 = w.d + 2;
+    h.theta = theta;
+    // (64x64 tiles, the instance OP_PRED_COV runs on; a 128x128 instance of this op has not been compiled or measured)
+    rc = launch_gemm<T, OP_COND_CROSS, 64>(st, h, (n0pad / TS) * (mpad / TS), w.q);
+    if (rc) return rc;
+    // T = Sigma_0n L_S^-T: the product of lcgp_predict's U with X := Sigma_0n, W := L_S^-1
+    rc = launch_pred<T, OP_PRED_U>(st, Sg, Wi, Tm, cslab, (size_t)mpad * mpad, mpad, n0pad, mpad / TS, w.q);
+    if (rc) return rc;
+    hipLaunchKernelGGL((cond_reduce_kernel<T>), dim3(n0, w.q), dim3(64), 0, st, (const T*)Tm, cslab, mpad, m, v, mpad, ldo, ghat,
+                       gvar);
+    CHECK_LAUNCH("cond_reduce_kernel");
     return 0;
 }
 
@@ -6258,6 +6465,64 @@ int lcgp_sample_latent(void* stream, int dtype, int n0, int d, int p, int q_loca
     const int ld = ldg ? ldg : n0;
     return dtype == LCGP_F64 ? do_sample<double>(st, cw, S, eps, ghat, ld, scratch, out)
                              : do_sample<float>(st, cw, S, eps, ghat, ld, scratch, out);
+}
+
+int lcgp_condition_scratch_bytes(int dtype, int n, int q_local, int m, int n0, size_t* bytes) {
+    if (dtype != LCGP_F64 && dtype != LCGP_F32) return bad("dtype must be 0 (f64) or 1 (f32)");
+    if (n < 1 || q_local < 1) return bad("n, q_local must be >= 1");
+    if (m < 1) return bad("m < 1");
+    if (n0 < 0) return bad("n0 < 0");
+    if (!bytes) return bad("bytes is NULL");
+    const size_t a = cond_prepare_scratch(dtype, n, q_local, m);
+    const size_t b = n0 ? cond_predict_scratch(dtype, n, q_local, m, n0) : 0;
+    *bytes = a > b ? a : b;
+    return 0;
+}
+
+int lcgp_condition_state_bytes(int dtype, int n, int d, int q_local, int m, size_t* bytes) {
+    if (dtype != LCGP_F64 && dtype != LCGP_F32) return bad("dtype must be 0 (f64) or 1 (f32)");
+    if (n < 1 || q_local < 1) return bad("n, q_local must be >= 1");
+    if (d < 1 || d > DWIDE) return bad("d must be in [1, 126]");
+    if (m < 1) return bad("m < 1");
+    if (!bytes) return bad("bytes is NULL");
+    *bytes = cond_carve(dtype, n, q_local, m).total;
+    return 0;
+}
+
+int lcgp_condition_prepare(void* stream, int dtype, int kernel_id, int n, int d, int p, int q_local, const void* x, const void* sr,
+                           const double* theta, const void* workspace, int m, const void* xn, const double* t, const double* r,
+                           void* scratch, size_t scratch_bytes, void* cond_workspace, void* state, int* info) {
+    int rc = check_common(dtype, n, d, p, q_local, kernel_id);
+    if (rc) return rc;
+    if (m < 1) return bad("m < 1");
+    if (!x || !theta || !workspace || !xn || !t || !scratch || !cond_workspace || !state || !info) return bad("NULL pointer");
+    if (scratch_bytes < cond_prepare_scratch(dtype, n, q_local, m))
+        return bad("scratch is smaller than lcgp_condition_scratch_bytes(dtype, n, q_local, m, 0)");
+    Ws w = carve(dtype, n, d, p, q_local, (void*)workspace);
+    w.kern = kernel_id;
+    Ws cw = carve(dtype, m, d, p, q_local, cond_workspace);
+    hipStream_t st = (hipStream_t)stream;
+    return dtype == LCGP_F64 ? do_condition_prepare<double>(st, w, x, sr, theta, m, xn, t, r, scratch, cw, state, info)
+                             : do_condition_prepare<float>(st, w, x, sr, theta, m, xn, t, r, scratch, cw, state, info);
+}
+
+int lcgp_condition_predict(void* stream, int dtype, int kernel_id, int n, int d, int p, int q_local, const void* x, const void* sr,
+                           const double* theta, const void* workspace, const void* state, int m, const void* xn, int n0,
+                           const void* x0, void* scratch, size_t scratch_bytes, double* ghat, double* gvar, int out_stride) {
+    int rc = check_common(dtype, n, d, p, q_local, kernel_id);
+    if (rc) return rc;
+    if (m < 1) return bad("m < 1");
+    if (n0 < 1) return bad("n0 < 1");
+    if (!x || !theta || !workspace || !state || !xn || !x0 || !scratch || !ghat || !gvar) return bad("NULL pointer");
+    if (out_stride != 0 && out_stride < n0) return bad("out_stride must be 0 (= n0) or >= n0");
+    if (scratch_bytes < cond_predict_scratch(dtype, n, q_local, m, n0))
+        return bad("scratch is smaller than lcgp_condition_scratch_bytes(dtype, n, q_local, m, n0)");
+    const int ldo = out_stride ? out_stride : n0;
+    Ws w = carve(dtype, n, d, p, q_local, (void*)workspace);
+    w.kern = kernel_id;
+    hipStream_t st = (hipStream_t)stream;
+    return dtype == LCGP_F64 ? do_condition_predict<double>(st, w, x, sr, theta, state, m, xn, n0, x0, scratch, ghat, gvar, ldo)
+                             : do_condition_predict<float>(st, w, x, sr, theta, state, m, xn, n0, x0, scratch, ghat, gvar, ldo);
 }
 
 int lcgp_loo(void* stream, int dtype, int n, int d, int p, int q_local, const void* sr, const double* theta,

@@ -82,6 +82,7 @@ class HotPathEngine:
             self._scratch = None
             self._cov_ws = None          # (n0, workspace) of the joint covariance (form_cov)
             self._cv_ws = None           # ((mmax, F), workspace) of the fold matrices (cv_block)
+            self._cond_ws = None         # (m, workspace) of the conditioning matrices S_k (condition_begin)
             self._sel = None             # state of a running greedy selection (select_begin)
         self._theta_last = None
 
@@ -465,7 +466,7 @@ class HotPathEngine:
         return self._scratch
 
     def _workspace2(self, slot, key, nbytes, refusal):
-        """the second workspace cached in attribute `slot` ('_cov_ws' or '_cv_ws': a model can hold both) as (key, workspace);
+        """the second workspace cached in attribute `slot` ('_cov_ws', '_cv_ws' or '_cond_ws': a model can hold all) as (key, workspace);
         a new key releases the old one, then nbytes() is checked against the free device memory (refusal: what, detail,
         advice) and allocated"""
         held = getattr(self, slot)
@@ -564,6 +565,78 @@ class HotPathEngine:
                                                        self._p(scratch), self._p(dst)), "lcgp_sample_latent")
                 if dst is not out:
                     out[:, lo:lo + m].copy_(dst)
+            return out
+
+    # ------------------------------------------------------------------------------------------------
+    # conditioning on new runs without refactorising (lcgp_hip.h: lcgp_condition_prepare / lcgp_condition_predict)
+    def condition_begin(self, xn_s, t, r=None):
+        """The state of a view conditioned on m new unique inputs xn_s (m, d; standardised, none of them a training input) with
+        latent observations t (q_local, m) and replicate counts r (m; None = ones), from the factorisation of the last
+        evaluate(), which is only read (lcgp_condition_prepare): a dict holding the device state (U_n, L_S^-1 and v per local
+        component), the inputs on the device and the theta rows it belongs to.  The conditioning matrices are factorised in a
+        second workspace carved for n = m (3 q_local mpad^2 elements, mpad = m rounded up to 128); the state holds q_local mpad
+        (npad + mpad) elements.  Raises ValueError when they do not fit in the free device memory, and
+        numpy.linalg.LinAlgError carrying the per-local-component info words when an S_k is not numerically positive definite."""
+        torch = self.torch
+        if self._theta_last is None:
+            raise RuntimeError("condition() needs a preceding evaluate() at the current parameters")
+        xn_s = np.ascontiguousarray(xn_s, np.float64)
+        m, d = xn_s.shape[0], self.d
+        t = np.ascontiguousarray(t, np.float64)
+        assert xn_s.ndim == 2 and xn_s.shape[1] == d and m >= 1 and t.shape == (self.q_local, m)
+        assert r is None or np.shape(r) == (m,)
+        refusal = ("conditioning on %d new inputs" % m, "%d components of %d x (n + 4 m)" % (self.q_local, m),
+                   "condition on fewer new inputs at a time")
+        with torch.cuda.device(self.device):
+            cws = self._workspace2('_cond_ws', m, lambda: self._nbytes("lcgp_workspace_bytes", self.dtype, m, d, self.p, self.q_local),
+                                   refusal)
+            scratch = self._grow_scratch(self._nbytes("lcgp_condition_scratch_bytes", self.dtype, self.n, self.q_local, m, 0), refusal)
+            nstate = self._nbytes("lcgp_condition_state_bytes", self.dtype, self.n, d, self.q_local, m)
+            self._require_memory(nstate, *refusal)
+            state = torch.empty(nstate, dtype=torch.uint8, device=self.device)
+            xnd = torch.as_tensor(xn_s).to(self.device, self.tdtype).contiguous()
+            td = torch.as_tensor(t).to(self.device)
+            rd = None if r is None else torch.as_tensor(np.ascontiguousarray(r, np.float64)).to(self.device)
+            info = torch.zeros(self.q_local, dtype=torch.int32, device=self.device)
+            _hip.check(self.lib.lcgp_condition_prepare(
+                self._stream(), self.dtype, self.kernel_id, self.n, d, self.p, self.q_local, self._p(self.x), self._p(self.sr),
+                self._p(self.theta_dev), self._p(self.workspace), m, self._p(xnd), self._p(td), self._p(rd), self._p(scratch),
+                scratch.numel(), self._p(cws), self._p(state), self._p(info)), "lcgp_condition_prepare")
+            info = info.cpu().numpy()
+        if np.any(info != 0):
+            err = np.linalg.LinAlgError("condition(): S_k is not numerically positive definite for local components (index, info) %s"
+                                        % [(i, int(v)) for i, v in enumerate(info) if v != 0])
+            err.info = info
+            raise err
+        return {'m': m, 'xn': xnd, 'state': state, 'theta': self._theta_last.copy()}
+
+    def condition_predict_block(self, state, x0s):
+        """(2, q_local, n0) float64 DEVICE tensor [ghat; gvar] of the view `state` (condition_begin) at standardised x0s
+        (lcgp_condition_predict: lcgp_predict's launches with same = 0, then the rank-m correction).  Chunked as predict_block
+        is: passes of at most PREDICT_CHUNK rows that write their columns of the one result block in place.  The base
+        factorisation must still be the one the state was built from."""
+        torch = self.torch
+        if not self.is_current(state['theta']):
+            raise RuntimeError("the conditioned view does not belong to the factorisation in the workspace")
+        x0s = np.ascontiguousarray(x0s, np.float64)
+        n0, d, m = x0s.shape[0], self.d, state['m']
+        assert x0s.ndim == 2 and x0s.shape[1] == d and n0 >= 1
+        chunk = min(n0, PREDICT_CHUNK)
+        with torch.cuda.device(self.device):
+            x0d = torch.as_tensor(x0s).to(self.device, self.tdtype).contiguous()
+            scratch = self._grow_scratch(self._nbytes("lcgp_condition_scratch_bytes", self.dtype, self.n, self.q_local, m, chunk),
+                                         ("the conditioned prediction of %d new inputs per pass" % chunk,
+                                          "%d components of %d x (n + m), twice" % (self.q_local, chunk),
+                                          "lower lcgp_amd.engine.PREDICT_CHUNK"))
+            out = torch.empty((2, self.q_local, n0), dtype=torch.float64, device=self.device)
+            st, xp, srp, thp, wsp = self._stream(), self._p(self.x), self._p(self.sr), self._p(self.theta_dev), self._p(self.workspace)
+            for lo in range(0, n0, chunk):
+                rows = min(chunk, n0 - lo)
+                _hip.check(self.lib.lcgp_condition_predict(
+                    st, self.dtype, self.kernel_id, self.n, d, self.p, self.q_local, xp, srp, thp, wsp, self._p(state['state']), m,
+                    self._p(state['xn']), rows, C.c_void_p(x0d.data_ptr() + lo * d * x0d.element_size()), self._p(scratch),
+                    scratch.numel(), C.c_void_p(out[0].data_ptr() + 8 * lo), C.c_void_p(out[1].data_ptr() + 8 * lo), n0),
+                    "lcgp_condition_predict")
             return out
 
     # ------------------------------------------------------------------------------------------------

@@ -277,6 +277,49 @@ class MainEffects:
         return 'MainEffects(outputs=%d, d=%d, grid=%d)' % (self.mean.shape[0], self.mean.shape[1], self.mean.shape[2])
 
 
+class ConditionedLCGP:
+    """What LCGP.condition() returns: a read-only view of the fitted model `base` conditioned on `m` new unique inputs
+    `x_new` (raw scale, (m, d)) at the FIXED parameters, basis and standardisation of the fit.  It holds device state only
+    (per local component U_n, L_S^-1 and v of DESIGN.md 4.13); the fitted model, its workspace and its plans are only read.
+    predict(x0) equals, to rounding, predict(x0) of a model built on the augmented data at the same parameters.  The view
+    goes stale when the base model's parameters change or the model is evaluated elsewhere: using it then raises RuntimeError."""
+
+    def __init__(self, base, x_new, engine, state):
+        self.base, self.x_new, self.m = base, x_new, int(x_new.shape[0])
+        self._engine, self._state = engine, state
+        # (the view of a float32 model may live on its float64 engine, which does not follow the model's later evaluations:
+        # the parameter vector itself is part of the check)
+        self._u = base._get_flat().copy()
+
+    def __repr__(self):
+        return "ConditionedLCGP(m=%d, d=%d, base=%s n=%d)" % (self.m, int(self.base.d), self.base.submethod, int(self.base.n))
+
+    def _require_current(self):
+        base = self.base
+        ok = base._aux_valid and np.array_equal(self._u, base._get_flat()) and \
+            (self._engine is None or self._engine.is_current(self._state['theta']))
+        if not ok:
+            raise RuntimeError('this ConditionedLCGP is stale: the parameters of its base model changed (or the model was refit) '
+                               'after condition(); call condition() again')
+
+    def predict(self, x0, latent=False):
+        """(ypred, ypredvar, yconfvar), each (p, n0) CPU float64 as LCGP.predict returns them, of the conditioned model at the
+        raw-scale inputs x0; latent=True: (ghat, gvar), each (q, n0).  Rows of x0 that equal training inputs follow
+        predict_grad()'s rule: the continuous prediction surface, no nugget term in the cross covariance (same = 0), also
+        when x0 IS the training set.  Computed on the GPU in the dtype of the engine that holds the view's state (float32
+        models: float32 products, ghat / gvar in double)."""
+        base = self.base
+        x0s = base._x0_2d(x0, 'x0')
+        self._require_current()
+        eng = self._engine
+        loc = None if eng is None else eng.condition_predict_block(self._state, x0s).permute(1, 0, 2)      # (q_local, 2, n0)
+        both = base._gather_components(loc, (2, x0s.shape[0]))
+        ghat, gvar = both[:, 0], both[:, 1]
+        if latent:
+            return _t(ghat.copy()), _t(gvar.copy())
+        return tuple(r.detach() for r in base._outputs(ghat, gvar))
+
+
 class LCGP:
     """
     Latent Component Gaussian Process (LCGP), MI355X hot path.
@@ -1235,11 +1278,12 @@ class LCGP:
             scale, offset = _np(self.ystd)[:, 0], _np(self.ymean)[:, 0]
         return W, np.broadcast_to(noise, (p,)).astype(F64), scale, offset
 
-    def _agree(self, fn, jitter=None, failure=None):
+    def _agree(self, fn, jitter=None, failure=None, what='the joint covariance'):
         """runs this rank's share `fn()` and makes every rank raise together when any rank's share failed (a rank that raised
         alone would leave the others waiting in the next collective): the q info words of the factorisations and a
         ValueError flag are all-reduced first.  Returns fn()'s value.  `failure`: the message of the LinAlgError, formatted
-        with the failing components and their info words (default: that of the joint covariance)."""
+        with the failing components and their info words (default: that of the joint covariance); `what`: what a rank that
+        reports another rank's memory refusal says could not be allocated."""
         q = int(self.q)
         status = np.zeros(q + 1, F64)
         res, err = None, None
@@ -1255,7 +1299,7 @@ class LCGP:
         if _dist.use_collectives(self._group):
             status = _dist.all_reduce_sum(status, self._group, None if self._engine is None else self._engine.device)
         if status[q] != 0:
-            raise err if err is not None else ValueError('another rank could not allocate the joint covariance')
+            raise err if err is not None else ValueError('another rank could not allocate %s' % what)
         bad = [k for k in range(q) if status[k] != 0]
         if bad and failure is not None:
             raise np.linalg.LinAlgError(failure % (bad, [int(status[k]) for k in bad]))
@@ -1341,6 +1385,85 @@ class LCGP:
             eta = np.random.default_rng((seed, q)).standard_normal((S, p, n0))
             ys += np.sqrt(noise)[None, :, None] * eta
         return _t(ys * scale[None, :, None] + offset[None, :, None])
+
+    # =============================================================================================
+    # conditioning on new runs without refactorising (beyond the reference)
+    # =============================================================================================
+    def condition(self, x_new, y_new):
+        """A read-only view of this model conditioned on new runs: x_new (N, d) on the raw input scale, y_new (p, N) on the raw
+        output scale.  Returns a ConditionedLCGP whose predict(x0) equals, to rounding, predict(x0) of a model built on the
+        augmented data at the same parameters, basis phi and standardisation (no refit, no factorisation of size n): per
+        latent component a rank-m correction from a block factorisation.  y_new goes through the stored
+        standardisation (on the rep path the one of the replicate means).  Full path: every row is one run.  Rep path:
+        bitwise-equal rows of x_new are grouped into m unique inputs with their counts and means.
+        Raises ValueError for wrong shapes, non-finite values, N = 0, a new input bitwise equal (after standardisation) to a
+        training input -- it would have to share a nugget with it -- and, on the full path, bitwise-duplicate rows inside
+        x_new: refit for those.  A conditioning matrix S_k that is not numerically positive definite raises
+        numpy.linalg.LinAlgError naming the component (nothing is jittered); a float32 model builds the view once more on
+        its float64 engine first (counted in float32_fallbacks, the one thing condition() changes on the model).  The fitted model, its workspace and its plans are only read: every other query keeps
+        working on the base model, and predict() of the base model is bitwise unchanged."""
+        self._require_mode(self.submethod)
+        d, p = int(self.d), int(self.p)
+        xn = _np(self._verify_data_types(x_new))
+        if isinstance(y_new, torch.Tensor):
+            yn = y_new.detach().to('cpu', torch.float64).numpy()
+        else:
+            yn = np.asarray(y_new, F64)
+        if xn.ndim != 2 or xn.shape[1] != d:
+            raise ValueError('x_new must have shape (N, %d), got %s' % (d, tuple(xn.shape)))
+        if xn.shape[0] < 1:
+            raise ValueError('x_new holds no rows (N = 0)')
+        if yn.ndim != 2 or yn.shape != (p, xn.shape[0]):
+            raise ValueError('y_new must have shape (%d, N = %d), got %s' % (p, xn.shape[0], tuple(yn.shape)))
+        if not np.all(np.isfinite(xn)) or not np.all(np.isfinite(yn)):
+            raise ValueError('x_new and y_new must be finite')
+        if self.submethod == 'rep':
+            xu, inverse, counts = self._group_unique_rows_np(xn)
+            ybar = self._compute_ybar_np(yn, inverse, xu.shape[0])
+            if self.rep_standardize_ybar:
+                ybar = (ybar - _np(self.ybar_mean)) / _np(self.ybar_std)
+            ys, r = ybar, counts.astype(F64)
+        else:
+            xu, r = xn, None
+            ys = (yn - _np(self.ymean)) / _np(self.ystd)
+        xu_s = self._standardise_x0(xu)[0]
+        if r is None and len({row.tobytes() for row in np.ascontiguousarray(xu_s)}) != xu_s.shape[0]:
+            raise ValueError('x_new holds duplicate rows (bitwise equal after standardisation): two copies of one input would '
+                             'have to share a nugget; refit with the new runs instead')
+        train = {row.tobytes() for row in np.ascontiguousarray(self._x_train())}
+        if any(row.tobytes() in train for row in np.ascontiguousarray(xu_s)):
+            raise ValueError('a row of x_new equals a training input (bitwise after standardisation): it would have to share a '
+                             'nugget with it; refit with the new runs instead')
+        eng = self._ensure_aux()
+        failure = ('condition(): the conditioning matrix S_k of latent component(s) %s is not numerically positive definite at '
+                   'the current parameters (info %s)')
+
+        def begin(e):
+            if e is None:
+                return None
+            rows = e._theta_last
+            # the latent observation of each new input: the entry of b_k the evaluation would form for it, over D_k sr_i
+            # (one product per component: a row's sum must not depend on how many components the rank holds)
+            t = np.stack([(row[d + 3:] @ ys) / row[d + 2] for row in rows])
+            return e.condition_begin(xu_s, t, r)
+        try:
+            state = self._agree(lambda: begin(eng), failure=failure, what='the conditioned view')
+        except np.linalg.LinAlgError:
+            if not (self._dtype == 'float32' and self.float32_fallback) or self._last_eval_float64:
+                raise
+            # float32 gave up (every rank: the failure was agreed on): the view is built once on the float64 engine, evaluated
+            # at the current parameters; the base model keeps answering from its own float32 factorisation
+            keep = (self._aux_engine, self._last_eval_float64, self._gc_last, self._float64_only)
+            self._ensure_engine64()
+            self.float32_fallbacks += 1
+            self._float64_only = True
+            try:
+                self._run_path()
+                eng = self._aux_engine if self._engine64 is not None else None
+            finally:
+                self._aux_engine, self._last_eval_float64, self._gc_last, self._float64_only = keep
+            state = self._agree(lambda: begin(eng), failure=failure + ', in float64 either', what='the conditioned view')
+        return ConditionedLCGP(self, _t(xu), eng, state)
 
     # =============================================================================================
     # closed-form cross-validation at fixed parameters (beyond the reference)

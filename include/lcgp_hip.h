@@ -642,6 +642,71 @@ int lcgp_select_condition(void* stream, int dtype, int kernel_id, int n, int d, 
 int lcgp_select_state(void* stream, int dtype, int n, int d, int q_local, int n_ref, int n_cand, int size, int which,
                       const void* scratch, double* out);
 
+/* Variance reduction and greedy selection on a CONDITIONED VIEW (no counterpart in the reference): lcgp_variance_reduction and
+ * lcgp_select_* of the model lcgp_condition_prepare conditioned on m new inputs xn, without refactorising -- what closes the
+ * loop pick a batch / run the simulator / lcgp_condition_prepare / pick the next batch.  `state`, m, xn: as
+ * lcgp_condition_predict takes them; the workspace and the state are only read.  For any input a, with U_a as in lcgp_predict
+ * and the notation of lcgp_condition_*:
+ *     Sigma_an = C^x(a, xn) - D_k U_a U_n^T,   T_a = Sigma_an L_S^-T         (1 x mpad, zero beyond m)
+ *     Sigma'_k(t, c)   = C_k(t, c) - D_k U_t . U_c - T_t . T_c                 (the view's posterior covariance)
+ *     Sigma'^h_k(c, c) = gvar_k(c) - |T_c|^2                                   (lcgp_condition_predict's gvar)
+ * With the WIDENED ROW U^_a = [U_a | T_a / sqrt(D_k)] of length K' = npad + mpad (mpad = m rounded up to 128) these are
+ * C_k - D_k U^_t . U^_c and scale_k - D_k |U^_c|^2: the forms lcgp_variance_reduction and lcgp_select_* consume, so
+ *     out[k, c] = sum_t w_t Sigma'_k(t, c)^2 / (max(Sigma'^h_k(c, c), 0) + 1 / (D_k r))
+ * equals lcgp_variance_reduction of a model built on the augmented data at the same theta, to rounding, and the selection is
+ * lcgp_select_* on widened rows.  A candidate must not equal a conditioning input (the caller refuses it); match, w_ref, r,
+ * cand_row0, pass_rows, omega, step, pick, which and the outputs are those of the entry each one mirrors.
+ *
+ * The row former, for a block of at most 2048 inputs: the launches of lcgp_variance_reduction's (cross rows with the match
+ * term, U into rows K' apart, gvar), then those of lcgp_condition_predict on the block (the kernel values C^x(., xn), Sigma_an by
+ * OP_COND_CROSS, T by the product of lcgp_predict's U on the dense L_S^-1), and one launch that writes T / sqrt(D_k) behind the
+ * row's U -- zeros in columns m .. mpad - 1 and in the rows of the padding, whatever the scratch held -- and takes rowsum(T o T)
+ * off gvar in lcgp_condition_predict's order: for a row without a match gvar is bitwise lcgp_condition_predict's.  The fused
+ * product (OP_VR) then runs with K = K', the selection's row kernels with row length and dot length K'.
+ *
+ * scratch (`scratch_bytes` is what the caller allocated and is checked by every entry), with esz the element size, npad / mpad
+ * n / m rounded up to 128, pad(v) = v rounded up to 128 (to 64 below 128) and every part rounded up to 256 bytes:
+ *   lcgp_condition_vr_scratch_bytes:  reference part  q (pad128(n_ref) + 64) K' esz + 2 q n_ref 8 + q X_r npad esz + 2 q X_r mpad esz,
+ *        X_r = min(2048, pad(n_ref));  candidate part  q pad(n_cand) K' esz + 2 q n_cand 8 + q X_c npad esz + 2 q X_c mpad esz
+ *        + q ceil(n_ref / 64) pad64(n_cand) 8,  X_c = min(2048, pad(n_cand))       (pad128 / pad64: rounded up to 128 / 64)
+ *   lcgp_condition_select_scratch_bytes:  q (pad128(n_ref) + 64) K' esz + q (pad(n_cand) + 128) K' esz + q X npad esz + 2 q X mpad esz
+ *        (X = min(2048, max(pad(n_ref), pad(n_cand)))) + doubles: q (2 n_ref + 2 n_cand) + q ceil(n_ref / 64) pad64(n_cand) + q n_cand
+ *        + q size (n_cand + n_ref) + q ceil(n_ref / 32) K' + q K' + q size + q (n_ref + n_cand) d + n_ref, and n_cand + size ints.
+ *   A scratch sized for n_cand serves lcgp_condition_vr calls with fewer candidates.
+ * Numerics follow lcgp_variance_reduction: products in the dtype, Sigma, sums and reductions in double, fixed order, no
+ * atomics.  Results are bitwise independent of the content of scratch on entry, of q_local, of how candidates are split over
+ * calls and of pass_rows.  The entries of the fitted model run the same code with K = npad and are bitwise what they were.
+ * Flops per component beyond the base entries', per row of either set: 2 mpad npad (Sigma_an) + mpad^2 (T); the fused product
+ * is 2 n_ref64 n_cand64 K'. */
+int lcgp_condition_vr_scratch_bytes(int dtype, int n, int q_local, int m, int n_ref, int n_cand, size_t* bytes /*host out*/);
+int lcgp_condition_vr_prepare(void* stream, int dtype, int kernel_id, int n, int d, int p, int q_local,
+                              const void* x, const void* sr, const double* theta, const void* workspace,
+                              const void* state, int m, const void* xn,
+                              int n_ref, const void* x_ref, void* scratch, size_t scratch_bytes);
+int lcgp_condition_vr(void* stream, int dtype, int kernel_id, int n, int d, int p, int q_local,
+                      const void* x, const void* sr, const double* theta, const void* workspace,
+                      const void* state, int m, const void* xn,
+                      int n_ref, const void* x_ref, const double* w_ref,
+                      int n_cand, const void* x_cand, const int* match_host /*host or NULL*/, const int* match,
+                      int cand_row0, int r, void* scratch, size_t scratch_bytes, double* out, int out_stride);
+int lcgp_condition_select_scratch_bytes(int dtype, int n, int d, int q_local, int m, int n_ref, int n_cand, int size,
+                                        size_t* bytes /*host out*/);
+int lcgp_condition_select_begin(void* stream, int dtype, int kernel_id, int n, int d, int p, int q_local,
+                                const void* x, const void* sr, const double* theta, const void* workspace,
+                                const void* state, int m, const void* xn,
+                                int n_ref, const void* x_ref, const double* w_ref,
+                                int n_cand, const void* x_cand, const int* match_host /*host or NULL*/, const int* match,
+                                int r, int size, int pass_rows, void* scratch, size_t scratch_bytes);
+int lcgp_condition_select_score(void* stream, int dtype, int n, int d, int q_local, int m, int n_ref, int n_cand, int size,
+                                int step, const double* omega, void* scratch, size_t scratch_bytes, double* out /*device or NULL*/);
+int lcgp_condition_select_picks(int dtype, int n, int d, int q_local, int m, int n_ref, int n_cand, int size, void* scratch,
+                                size_t scratch_bytes, int** picks /*host out*/);
+int lcgp_condition_select_condition(void* stream, int dtype, int kernel_id, int n, int d, int p, int q_local, const double* theta,
+                                    int m, int n_ref, int n_cand, int size, int r, int step, const int* pick /*device*/,
+                                    void* scratch, size_t scratch_bytes);
+int lcgp_condition_select_state(void* stream, int dtype, int n, int d, int q_local, int m, int n_ref, int n_cand, int size,
+                                int which, const void* scratch, size_t scratch_bytes, double* out);
+
 #ifdef __cplusplus
 }
 #endif

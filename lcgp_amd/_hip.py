@@ -98,6 +98,17 @@ SIGNATURES = {
     "lcgp_select_picks": (_i, [_i, _i, _i, _i, _i, _i, _i, _vp, C.POINTER(_vp)]),
     "lcgp_select_condition": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "lcgp_select_state": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "lcgp_condition_vr_scratch_bytes": (_i, [_i, _i, _i, _i, _i, _i, C.POINTER(C.c_size_t)]),
+    "lcgp_condition_vr_prepare": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, C.c_size_t]),
+    "lcgp_condition_vr": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _i,
+                               _vp, C.c_size_t, _vp, _i]),
+    "lcgp_condition_select_scratch_bytes": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, C.POINTER(C.c_size_t)]),
+    "lcgp_condition_select_begin": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp,
+                                         _i, _i, _i, _vp, C.c_size_t]),
+    "lcgp_condition_select_score": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, C.c_size_t, _vp]),
+    "lcgp_condition_select_picks": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _vp, C.c_size_t, C.POINTER(_vp)]),
+    "lcgp_condition_select_condition": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, C.c_size_t]),
+    "lcgp_condition_select_state": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, C.c_size_t, _vp]),
 }
 
 _lib = None

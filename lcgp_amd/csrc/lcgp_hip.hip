@@ -2773,12 +2773,13 @@ template <typename T>
 __global__ __launch_bounds__(64) void pred_reduce_kernel(const T* __restrict__ X, const T* __restrict__ U, size_t slab, size_t uslab, int ld,
                                                          int n, const T* __restrict__ z, int npad,
                                                          const double* __restrict__ theta, int tw, int d, int ldo,
-                                                         double* __restrict__ ghat, double* __restrict__ gvar) {
+                                                         double* __restrict__ ghat, double* __restrict__ gvar,
+                                                         int ldu = 0 /*row length of U; 0 = ld*/) {
     const int m = blockIdx.x, k = blockIdx.y, lane = threadIdx.x;
     const double* th = theta + (size_t)k * tw;
     const double scale = th[d], D = th[d + 2];
     const T* Xr = X + (size_t)k * slab + (size_t)m * ld;
-    const T* Ur = U + (size_t)k * uslab + (size_t)m * ld;
+    const T* Ur = U + (size_t)k * uslab + (size_t)m * (ldu ? ldu : ld);
     const T* zk = z + (size_t)k * npad;
     double s1 = 0.0, s2 = 0.0;
     for (int i = lane; i < n; i += 64) {
@@ -3452,10 +3453,10 @@ inline int predict_pad(int n0) { return n0 >= 128 ? round_up(n0, 2 * TS) : round
 // apart, B_k ld x ld matrices sB apart, ld = nb 64-tiles.  128x128 tiles when rows is a multiple of 128, 64x64 tiles otherwise.
 template <typename T, int OP>
 int launch_pred(hipStream_t st, const T* A, const T* B, T* C, size_t sA, size_t sB, int ld, int rows, int nb, int q,
-                size_t sC = 0 /*0 = sA*/, bool small = false /*64x64 tiles whatever rows is*/) {
+                size_t sC = 0 /*0 = sA*/, bool small = false /*64x64 tiles whatever rows is*/, int ldc = 0 /*row length of C; 0 = ld*/) {
     GemmArgs g;
     g.A = A; g.B = B; g.C = C;
-    g.sA = sA; g.sB = sB; g.sC = sC ? sC : sA; g.ldA = g.ldB = g.ldC = ld; g.p1 = g.p2 = g.p3 = 0;
+    g.sA = sA; g.sB = sB; g.sC = sC ? sC : sA; g.ldA = g.ldB = ld; g.ldC = ldc ? ldc : ld; g.p1 = g.p2 = g.p3 = 0;
     if (rows % (2 * TS) == 0 && !small) {
         g.nb = nb / 2; g.p0 = rows / (2 * TS);
         return launch_gemm<T, OP, 128>(st, g, g.p0 * g.nb, q);
@@ -4020,35 +4021,48 @@ constexpr int VR_XBLK = 2048;       // rows of X = c0k o sr^T formed per pass: b
 // scratch of the variance reduction: a reference part (offsets depend on n_ref only) followed by a candidate part (offsets
 // relative to cand, from the n_cand of the call): a scratch sized for n_cand serves every call with fewer candidates
 struct VrLay {
-    int rrows, nrt, ldp;
+    int rrows, nrt, ldp, kp;
     size_t uslab_r, xslab_r, uslab_c, xslab_c;
-    size_t off_uref, off_gvr, off_ghr, off_xr, cand;
-    size_t off_uc, off_gvc, off_ghc, off_xc, off_part, total;
+    size_t off_uref, off_gvr, off_ghr, off_xr, off_str, cand;
+    size_t off_uc, off_gvc, off_ghc, off_xc, off_stc, off_part, total;
 };
 
-inline VrLay vr_carve(int dtype, int n, int q, int n_ref, int n_cand) {
+// A conditioned view (lcgp_condition_prepare's state) the variance reduction and the selection run on instead of the fitted
+// model (lcgp_condition_vr_* / lcgp_condition_select_*): rows of U are widened to K' = npad + mpad, [U_a | T_a / sqrt(D_k)],
+// and gvar is the view's.  Everything behind the row former is the base model's code with K' as the row length.
+struct VrView {
+    const void* Un; const void* Wi; const void* xn;     // U_n and L_S^-1 of the state, the conditioning inputs
+    int m, mpad;
+};
+
+// mpad > 0: the layout of a conditioned view -- rows of the two U are npad + mpad long, and each X work area is followed by
+// the work area of Sigma_an and T (2 q rows mpad elements).  mpad = 0 is the base model's layout, byte for byte.
+inline VrLay vr_carve(int dtype, int n, int q, int n_ref, int n_cand, int mpad = 0) {
     VrLay L;
-    const size_t esz = dtype == LCGP_F64 ? 8 : 4, npad = round_up(n, 2 * TS);
+    const size_t esz = dtype == LCGP_F64 ? 8 : 4, npad = round_up(n, 2 * TS), kp = npad + mpad;
+    L.kp = (int)kp;
     // U_ref rows: whole 128-row tiles plus one 64-row tile, so that a candidate tile taken from ANY row of the reference set
     // (cand_row0 >= 0) stays inside the slab (its rows beyond the set only feed candidate columns that are never written)
     L.rrows = round_up(n_ref, 2 * TS) + TS;
     L.nrt = (n_ref + TS - 1) / TS;
     L.ldp = round_up(n_cand, TS);
-    L.uslab_r = (size_t)L.rrows * npad;
+    L.uslab_r = (size_t)L.rrows * kp;
     L.xslab_r = (size_t)min(VR_XBLK, predict_pad(n_ref)) * npad;
     size_t o = 0;
     L.off_uref = o; o = align256(o + (size_t)q * L.uslab_r * esz);
     L.off_gvr = o; o = align256(o + (size_t)q * n_ref * sizeof(double));
     L.off_ghr = o; o = align256(o + (size_t)q * n_ref * sizeof(double));
     L.off_xr = o; o = align256(o + (size_t)q * L.xslab_r * esz);
+    L.off_str = o; o = align256(o + 2 * (size_t)q * min(VR_XBLK, predict_pad(n_ref)) * mpad * esz);
     L.cand = o;
     const int crows = predict_pad(n_cand);
-    L.uslab_c = (size_t)crows * npad;
+    L.uslab_c = (size_t)crows * kp;
     L.xslab_c = (size_t)min(VR_XBLK, crows) * npad;
     L.off_uc = o; o = align256(o + (size_t)q * L.uslab_c * esz);
     L.off_gvc = o; o = align256(o + (size_t)q * n_cand * sizeof(double));
     L.off_ghc = o; o = align256(o + (size_t)q * n_cand * sizeof(double));
     L.off_xc = o; o = align256(o + (size_t)q * L.xslab_c * esz);
+    L.off_stc = o; o = align256(o + 2 * (size_t)q * min(VR_XBLK, crows) * mpad * esz);
     L.off_part = o; o = align256(o + (size_t)q * L.nrt * L.ldp * sizeof(double));
     L.total = o;
     return L;
@@ -4058,10 +4072,39 @@ inline VrLay vr_carve(int dtype, int n, int q, int n_ref, int n_cand) {
 // (cross_kernel, nugget term at column match[i] where given) into the X work area (q slabs xslab apart), U = X W^T (OP_PRED_U)
 // into rows lo .. of the U slabs (uslab apart), then the row reductions (pred_reduce_kernel; gh receives ghat, unused).
 // Per row the same arithmetic as lcgp_predict, whatever the pass.
+// On a conditioned view (cv; ST: its work area of 2 q rows mpad elements) the rows of U are npad + mpad long, and each pass
+// goes on with the launches of lcgp_condition_predict on its rows: the kernel values C^x(., xn), Sigma_an (OP_COND_CROSS, A rows
+// npad + mpad apart), T = Sigma_an L_S^-T (OP_PRED_U on the dense L_S^-1), and cond_tail_kernel, which writes T / sqrt(D_k) behind
+// the row's U and takes rowsum(T o T) off gvar: per row the arithmetic of lcgp_condition_predict.
+template <typename T>
+__global__ __launch_bounds__(64) void cond_tail_kernel(const T* __restrict__ Tm, size_t slab, int ld, int m, int mpad, int n0,
+                                                       const double* __restrict__ theta, int tw, int d, T* __restrict__ Ut,
+                                                       size_t uslab, int ldu, int ldo, double* __restrict__ gvar) {
+    const int r = blockIdx.x, k = blockIdx.y, lane = threadIdx.x;
+    T* out = Ut + (size_t)k * uslab + (size_t)r * ldu;
+    if (r >= n0) {                                  // (uniform per block) padding rows: zeros, whatever the scratch held
+        for (int j = lane; j < mpad; j += 64) out[j] = (T)0;
+        return;
+    }
+    const T* Tr = Tm + (size_t)k * slab + (size_t)r * ld;
+    const double is = 1.0 / sqrt(theta[(size_t)k * tw + d + 2]);
+    double s2 = 0.0;
+    for (int j = lane; j < m; j += 64) {            // (cond_reduce_kernel's order)
+        const double u = (double)Tr[j];
+        s2 += u * u;
+        out[j] = (T)(u * is);
+    }
+    for (int j = (m & ~63) + lane; j < mpad; j += 64)
+        if (j >= m) out[j] = (T)0;                  // columns m .. mpad - 1: zeros, whatever T's padding held
+    for (int off = 32; off > 0; off >>= 1) s2 += __shfl_xor(s2, off);
+    if (lane == 0) gvar[(size_t)k * ldo + r] -= s2;
+}
+
 template <typename T>
 int vr_form(hipStream_t st, const Ws& w, const void* x, const void* sr, const double* theta, int m0, const void* xs,
-            const int* match, T* X, size_t xslab, T* U, size_t uslab, double* gh, double* gv, int ldv) {
-    const int tw = w.d + 3 + w.p;
+            const int* match, T* X, size_t xslab, T* U, size_t uslab, double* gh, double* gv, int ldv,
+            const VrView* cv = nullptr, T* ST = nullptr) {
+    const int tw = w.d + 3 + w.p, ldu = w.npad + (cv ? cv->mpad : 0);
     ThetaArg dummy;
     memset(&dummy, 0, sizeof(dummy));
     for (int lo = 0; lo < m0; lo += VR_XBLK) {
@@ -4073,22 +4116,47 @@ int vr_form(hipStream_t st, const Ws& w, const void* x, const void* sr, const do
                                w.n, w.d, x0, (const T*)x, dummy, theta, 0, (const T*)sr, mpad, w.npad, tw, xslab, mt);
         });
         CHECK_LAUNCH("cross_kernel");
-        T* Ub = U + (size_t)lo * w.npad;
-        int rc = launch_pred<T, OP_PRED_U>(st, X, (const T*)(w.base + w.off_W), Ub, xslab, w.mat, w.npad, mpad, w.nb, w.q, uslab);
+        T* Ub = U + (size_t)lo * ldu;
+        int rc = launch_pred<T, OP_PRED_U>(st, X, (const T*)(w.base + w.off_W), Ub, xslab, w.mat, w.npad, mpad, w.nb, w.q, uslab,
+                                           false, ldu);
         if (rc) return rc;
         hipLaunchKernelGGL((pred_reduce_kernel<T>), dim3(m, w.q), dim3(64), 0, st, (const T*)X, (const T*)Ub, xslab, uslab, w.npad,
-                           w.n, (const T*)(w.base + w.off_z), w.npad, theta, tw, w.d, ldv, gh + lo, gv + lo);
+                           w.n, (const T*)(w.base + w.off_z), w.npad, theta, tw, w.d, ldv, gh + lo, gv + lo, ldu);
         CHECK_LAUNCH("pred_reduce_kernel");
+        if (!cv) continue;
+        const int cm = cv->mpad;
+        const size_t cslab = (size_t)mpad * cm;
+        T* Sg = ST;
+        T* Tm = ST + cslab * w.q;
+        for_kern(w.kern, [&](auto kern) {
+            hipLaunchKernelGGL((cross_kernel<T, decltype(kern)::value>), dim3(cm / TS, mpad / TS, w.q), dim3(256), 0, st, Sg, cm, m,
+                               cv->m, w.d, x0, (const T*)cv->xn, dummy, theta, 0, (const T*)nullptr, mpad, cm, tw, cslab,
+                               (const int*)nullptr);
+        });
+        CHECK_LAUNCH("cross_kernel");
+        GemmArgs h;
+        h.A = Ub; h.B = cv->Un; h.C = Sg;
+        h.sA = uslab; h.sB = (size_t)cm * w.npad; h.sC = cslab; h.ldA = ldu; h.ldB = w.npad; h.ldC = cm;
+        h.nb = 0; h.p0 = w.npad / TS; h.p1 = cm / TS; h.p2 = tw; h.p3 = w.d + 2;
+        h.theta = theta;
+        rc = launch_gemm<T, OP_COND_CROSS, 64>(st, h, (mpad / TS) * (cm / TS), w.q);
+        if (rc) return rc;
+        rc = launch_pred<T, OP_PRED_U>(st, Sg, (const T*)cv->Wi, Tm, cslab, (size_t)cm * cm, cm, mpad, cm / TS, w.q);
+        if (rc) return rc;
+        hipLaunchKernelGGL((cond_tail_kernel<T>), dim3(mpad, w.q), dim3(64), 0, st, (const T*)Tm, cslab, cm, cv->m, cm, m, theta, tw,
+                           w.d, Ub + w.npad, uslab, ldu, ldv, gv + lo);
+        CHECK_LAUNCH("cond_tail_kernel");
     }
     return 0;
 }
 
 template <typename T>
 int do_vr_prepare(hipStream_t st, const Ws& w, const void* x, const void* sr, const double* theta, int n_ref, const void* x_ref,
-                  char* scratch) {
-    const VrLay L = vr_carve(w.esz == 8 ? LCGP_F64 : LCGP_F32, w.n, w.q, n_ref, 1);
+                  char* scratch, const VrView* cv = nullptr) {
+    const VrLay L = vr_carve(w.esz == 8 ? LCGP_F64 : LCGP_F32, w.n, w.q, n_ref, 1, cv ? cv->mpad : 0);
     return vr_form<T>(st, w, x, sr, theta, n_ref, x_ref, nullptr, (T*)(scratch + L.off_xr), L.xslab_r, (T*)(scratch + L.off_uref),
-                      L.uslab_r, (double*)(scratch + L.off_ghr), (double*)(scratch + L.off_gvr), n_ref);
+                      L.uslab_r, (double*)(scratch + L.off_ghr), (double*)(scratch + L.off_gvr), n_ref, cv,
+                      (T*)(scratch + L.off_str));
 }
 
 // out[k, c] = sum over the reference tiles, in ascending order, of the partials the OP_VR epilogue left
@@ -4105,8 +4173,8 @@ __global__ __launch_bounds__(256) void vr_reduce_kernel(const double* __restrict
 template <typename T>
 int do_vr(hipStream_t st, const Ws& w, const void* x, const void* sr, const double* theta, int n_ref, const void* x_ref,
           const double* w_ref, int n_cand, const void* x_cand, const int* match, int row0, int r, char* scratch, double* out,
-          int ldo) {
-    const VrLay L = vr_carve(w.esz == 8 ? LCGP_F64 : LCGP_F32, w.n, w.q, n_ref, n_cand);
+          int ldo, const VrView* cv = nullptr) {
+    const VrLay L = vr_carve(w.esz == 8 ? LCGP_F64 : LCGP_F32, w.n, w.q, n_ref, n_cand, cv ? cv->mpad : 0);
     const T* Ur = (const T*)(scratch + L.off_uref);
     const T* Uc;
     const double* gvc;
@@ -4114,23 +4182,23 @@ int do_vr(hipStream_t st, const Ws& w, const void* x, const void* sr, const doub
     size_t sB;
     int ldg;
     if (row0 >= 0) {                // the candidates are rows row0 .. of the reference set: its U and gvar serve
-        Uc = Ur + (size_t)row0 * w.npad; sB = L.uslab_r;
+        Uc = Ur + (size_t)row0 * L.kp; sB = L.uslab_r;
         gvc = (const double*)(scratch + L.off_gvr) + row0; ldg = n_ref;
         xc = (const T*)x_ref + (size_t)row0 * w.d;
     } else {
         T* U = (T*)(scratch + L.off_uc);
         double* gv = (double*)(scratch + L.off_gvc);
         int rc = vr_form<T>(st, w, x, sr, theta, n_cand, x_cand, match, (T*)(scratch + L.off_xc), L.xslab_c, U, L.uslab_c,
-                            (double*)(scratch + L.off_ghc), gv, n_cand);
+                            (double*)(scratch + L.off_ghc), gv, n_cand, cv, (T*)(scratch + L.off_stc));
         if (rc) return rc;
         Uc = U; sB = L.uslab_c; gvc = gv; ldg = n_cand; xc = x_cand;
     }
     GemmArgs h;
     h.A = Ur; h.B = Uc; h.C = scratch + L.off_part;
     h.sA = L.uslab_r; h.sB = sB; h.sC = 0;
-    h.ldA = h.ldB = w.npad; h.ldC = 0;
+    h.ldA = h.ldB = L.kp; h.ldC = 0;                // (a conditioned view: the widened rows, K = npad + mpad)
     h.nb = 0;
-    h.p0 = w.npad / TS; h.p1 = (n_cand + TS - 1) / TS; h.p2 = n_ref; h.p3 = n_cand;
+    h.p0 = L.kp / TS; h.p1 = (n_cand + TS - 1) / TS; h.p2 = n_ref; h.p3 = n_cand;
     h.theta = theta; h.xa = x_ref; h.xb = xc; h.wref = w_ref; h.gvc = gvc; h.ldg = ldg;
     h.d = w.d; h.kern = w.kern; h.tw = w.d + 3 + w.p; h.nrep = r; h.ldp = L.ldp;
     // 64x64 tiles: the 128-tile instances of the U U^T product do not compile clean (OP_PRED_COV), and this
@@ -4338,29 +4406,32 @@ int do_vr_grad(hipStream_t st, const Ws& w, const void* x, const void* sr, const
 constexpr int SEL_RB = 32;          // reference rows per partial of the transposed product (fixed: results do not depend on sizes)
 
 struct SelLay {
-    int rrows, crows, xrows, nrt, ldp, nchunk;
+    int rrows, crows, xrows, nrt, ldp, nchunk, kp;
     size_t uslab_r, uslab_c, xslab;
-    size_t off_uref, off_gvr, off_ghr, off_x, off_uc, off_ghc, off_h, off_part, off_R, off_V, off_Uh, off_ypart, off_y, off_b,
+    size_t off_uref, off_gvr, off_ghr, off_x, off_st, off_uc, off_ghc, off_h, off_part, off_R, off_V, off_Uh, off_ypart, off_y, off_b,
         off_xsr, off_xsc, off_w, off_mask, off_picks, total;
 };
 
-inline SelLay sel_carve(int dtype, int n, int d, int q, int n_ref, int n_cand, int size) {
+// (mpad > 0: the layout of a conditioned view, as vr_carve's -- rows of npad + mpad, the Sigma_an / T work area behind X)
+inline SelLay sel_carve(int dtype, int n, int d, int q, int n_ref, int n_cand, int size, int mpad = 0) {
     SelLay L;
-    const size_t esz = dtype == LCGP_F64 ? 8 : 4, npad = round_up(n, 2 * TS);
+    const size_t esz = dtype == LCGP_F64 ? 8 : 4, npad = round_up(n, 2 * TS), kp = npad + mpad;
+    L.kp = (int)kp;
     L.rrows = round_up(n_ref, 2 * TS) + TS;                 // as VrLay
     L.crows = predict_pad(n_cand) + 2 * TS;                 // the last pass of lcgp_select_begin writes whole tiles past n_cand
     L.xrows = min(VR_XBLK, max(predict_pad(n_ref), predict_pad(n_cand)));
     L.nrt = (n_ref + TS - 1) / TS;
     L.ldp = round_up(n_cand, TS);
     L.nchunk = (n_ref + SEL_RB - 1) / SEL_RB;
-    L.uslab_r = (size_t)L.rrows * npad;
-    L.uslab_c = (size_t)L.crows * npad;
+    L.uslab_r = (size_t)L.rrows * kp;
+    L.uslab_c = (size_t)L.crows * kp;
     L.xslab = (size_t)L.xrows * npad;
     const size_t D8 = sizeof(double);
     size_t o = 0;
     L.off_uref = o; o = align256(o + (size_t)q * L.uslab_r * esz);
     L.off_uc = o; o = align256(o + (size_t)q * L.uslab_c * esz);
     L.off_x = o; o = align256(o + (size_t)q * L.xslab * esz);
+    L.off_st = o; o = align256(o + 2 * (size_t)q * L.xrows * mpad * esz);
     L.off_gvr = o; o = align256(o + (size_t)q * n_ref * D8);
     L.off_ghr = o; o = align256(o + (size_t)q * n_ref * D8);
     L.off_ghc = o; o = align256(o + (size_t)q * n_cand * D8);
@@ -4369,8 +4440,8 @@ inline SelLay sel_carve(int dtype, int n, int d, int q, int n_ref, int n_cand, i
     L.off_R = o; o = align256(o + (size_t)q * n_cand * D8);
     L.off_V = o; o = align256(o + (size_t)q * size * n_cand * D8);
     L.off_Uh = o; o = align256(o + (size_t)q * size * n_ref * D8);
-    L.off_ypart = o; o = align256(o + (size_t)q * L.nchunk * npad * D8);
-    L.off_y = o; o = align256(o + (size_t)q * npad * D8);
+    L.off_ypart = o; o = align256(o + (size_t)q * L.nchunk * kp * D8);
+    L.off_y = o; o = align256(o + (size_t)q * kp * D8);
     L.off_b = o; o = align256(o + (size_t)q * size * D8);
     L.off_xsr = o; o = align256(o + (size_t)q * n_ref * d * D8);
     L.off_xsc = o; o = align256(o + (size_t)q * n_cand * d * D8);
@@ -4658,28 +4729,29 @@ __global__ __launch_bounds__(1024) void sel_score_kernel(const double* __restric
 template <typename T>
 int do_sel_begin(hipStream_t st, const Ws& w, const void* x, const void* sr, const double* theta, int n_ref, const void* x_ref,
                  const double* w_ref, int n_cand, const void* x_cand, const int* match, int r, int size, int pass_rows,
-                 char* scratch) {
-    const SelLay L = sel_carve(w.esz == 8 ? LCGP_F64 : LCGP_F32, w.n, w.d, w.q, n_ref, n_cand, size);
+                 char* scratch, const VrView* cv = nullptr) {
+    const SelLay L = sel_carve(w.esz == 8 ? LCGP_F64 : LCGP_F32, w.n, w.d, w.q, n_ref, n_cand, size, cv ? cv->mpad : 0);
     const int tw = w.d + 3 + w.p;
     T* X = (T*)(scratch + L.off_x);
+    T* ST = (T*)(scratch + L.off_st);
     T* Ur = (T*)(scratch + L.off_uref);
     T* Uc = (T*)(scratch + L.off_uc);
     double* hc = (double*)(scratch + L.off_h);
     int rc = vr_form<T>(st, w, x, sr, theta, n_ref, x_ref, nullptr, X, L.xslab, Ur, L.uslab_r, (double*)(scratch + L.off_ghr),
-                        (double*)(scratch + L.off_gvr), n_ref);
+                        (double*)(scratch + L.off_gvr), n_ref, cv, ST);
     if (rc) return rc;
     for (int lo = 0; lo < n_cand; lo += pass_rows) {
         const int m = min(pass_rows, n_cand - lo);
         rc = vr_form<T>(st, w, x, sr, theta, m, (const T*)x_cand + (size_t)lo * w.d, match ? match + lo : nullptr, X, L.xslab,
-                        Uc + (size_t)lo * w.npad, L.uslab_c, (double*)(scratch + L.off_ghc) + lo, hc + lo, n_cand);
+                        Uc + (size_t)lo * L.kp, L.uslab_c, (double*)(scratch + L.off_ghc) + lo, hc + lo, n_cand, cv, ST);
         if (rc) return rc;
     }
     GemmArgs h;
     h.A = Ur; h.B = Uc; h.C = scratch + L.off_part;
     h.sA = L.uslab_r; h.sB = L.uslab_c; h.sC = 0;
-    h.ldA = h.ldB = w.npad; h.ldC = 0;
+    h.ldA = h.ldB = L.kp; h.ldC = 0;
     h.nb = 0;
-    h.p0 = w.npad / TS; h.p1 = (n_cand + TS - 1) / TS; h.p2 = n_ref; h.p3 = n_cand;
+    h.p0 = L.kp / TS; h.p1 = (n_cand + TS - 1) / TS; h.p2 = n_ref; h.p3 = n_cand;
     h.theta = theta; h.xa = x_ref; h.xb = x_cand; h.wref = w_ref; h.gvc = hc; h.ldg = n_cand;
     h.d = w.d; h.kern = w.kern; h.tw = tw; h.nrep = r; h.ldp = L.ldp;
     rc = launch_gemm<T, OP_VR, 64>(st, h, L.nrt * h.p1, w.q);
@@ -4700,13 +4772,15 @@ int do_sel_begin(hipStream_t st, const Ws& w, const void* x, const void* sr, con
     return 0;
 }
 
-// one conditioning step on the pick *pick for all local components (w: n, d, p, q, kern, esz; no workspace is read)
+// one conditioning step on the pick *pick for all local components (w: n, d, p, q, kern, esz; no workspace is read).
+// The row kernels take the row length ld and the length of the dot products kn: npad and n on the fitted model; on a
+// conditioned view (mpad > 0) both are npad + mpad, the widened rows (zeros in their two paddings).
 template <typename T>
 int do_sel_condition(hipStream_t st, const Ws& w, const double* theta, int n_ref, int n_cand, int size, int r, int t,
-                     const int* pick, char* scratch) {
-    const SelLay L = sel_carve(w.esz == 8 ? LCGP_F64 : LCGP_F32, w.n, w.d, w.q, n_ref, n_cand, size);
+                     const int* pick, char* scratch, int mpad = 0) {
+    const SelLay L = sel_carve(w.esz == 8 ? LCGP_F64 : LCGP_F32, w.n, w.d, w.q, n_ref, n_cand, size, mpad);
     constexpr int VN = SelVec<T>::N;
-    const int tw = w.d + 3 + w.p;
+    const int tw = w.d + 3 + w.p, ld = L.kp, kn = mpad ? L.kp : w.n;
     const T* Ur = (const T*)(scratch + L.off_uref);
     const T* Uc = (const T*)(scratch + L.off_uc);
     double* h = (double*)(scratch + L.off_h);
@@ -4722,21 +4796,21 @@ int do_sel_condition(hipStream_t st, const Ws& w, const double* theta, int n_ref
     int* mask = (int*)(scratch + L.off_mask);
     for_kern(w.kern, [&](auto kern) {
         hipLaunchKernelGGL((sel_col_kernel<T, decltype(kern)::value>), dim3((n_cand + n_ref + 3) / 4, w.q), dim3(256), 0, st, Uc,
-                           L.uslab_c, Ur, L.uslab_r, w.npad, w.n, n_cand, n_ref, xsc, xsr, w.d, theta, tw, r, (const double*)h, V, Uh,
+                           L.uslab_c, Ur, L.uslab_r, ld, kn, n_cand, n_ref, xsc, xsr, w.d, theta, tw, r, (const double*)h, V, Uh,
                            size, t, pick);
     });
     CHECK_LAUNCH("sel_col_kernel");
-    hipLaunchKernelGGL((sel_ty_part_kernel<T>), dim3((w.n + 256 * VN - 1) / (256 * VN), L.nchunk, w.q), dim3(256), 0, st, Ur,
-                       L.uslab_r, w.npad, w.n, n_ref, wr, (const double*)Uh, size, t, L.nchunk, yp);
+    hipLaunchKernelGGL((sel_ty_part_kernel<T>), dim3((kn + 256 * VN - 1) / (256 * VN), L.nchunk, w.q), dim3(256), 0, st, Ur,
+                       L.uslab_r, ld, kn, n_ref, wr, (const double*)Uh, size, t, L.nchunk, yp);
     CHECK_LAUNCH("sel_ty_part_kernel");
-    hipLaunchKernelGGL(sel_ty_reduce_kernel, dim3((w.npad + 255) / 256, w.q), dim3(256), 0, st, (const double*)yp, L.nchunk, w.npad,
-                       w.n, y);
+    hipLaunchKernelGGL(sel_ty_reduce_kernel, dim3((ld + 255) / 256, w.q), dim3(256), 0, st, (const double*)yp, L.nchunk, ld,
+                       kn, y);
     CHECK_LAUNCH("sel_ty_reduce_kernel");
     hipLaunchKernelGGL(sel_hdot_kernel, dim3(t + 1, w.q), dim3(256), 0, st, wr, (const double*)Uh, size, n_ref, t, b);
     CHECK_LAUNCH("sel_hdot_kernel");
     for_kern(w.kern, [&](auto kern) {
         hipLaunchKernelGGL((sel_update_kernel<T, decltype(kern)::value>), dim3((n_cand + 3) / 4, w.q), dim3(256), 0, st, Uc,
-                           L.uslab_c, w.npad, w.n, n_cand, n_ref, xsc, xsr, w.d, theta, tw, r, wr, (const double*)y, (const double*)b,
+                           L.uslab_c, ld, kn, n_cand, n_ref, xsc, xsr, w.d, theta, tw, r, wr, (const double*)y, (const double*)b,
                            (const double*)V, (const double*)Uh, h, R, size, t, pick, mask);
     });
     CHECK_LAUNCH("sel_update_kernel");
@@ -6756,6 +6830,188 @@ int lcgp_select_state(void* stream, int dtype, int n, int d, int q_local, int n_
     if (which != 0 && which != 1) return bad("which must be 0 (R) or 1 (h)");
     if (!scratch || !out) return bad("NULL pointer");
     const SelLay L = sel_carve(dtype, n, d, q_local, n_ref, n_cand, size);
+    hipError_t e = hipMemcpyAsync(out, (const char*)scratch + (which ? L.off_h : L.off_R), (size_t)q_local * n_cand * sizeof(double),
+                                  hipMemcpyDeviceToDevice, (hipStream_t)stream);
+    return e == hipSuccess ? 0 : fail("hipMemcpyAsync", e);
+}
+
+// ---- variance reduction and greedy selection on a conditioned view (lcgp_hip.h: lcgp_condition_vr_* / lcgp_condition_select_*) ----
+// the base model's code on widened rows (VrView); every entry checks its arguments and scratch_bytes before anything is enqueued
+static int check_view(int m) {
+    if (m < 1) return bad("m < 1");
+    return 0;
+}
+
+static VrView view_of(int dtype, int n, int q_local, const void* state, int m, const void* xn) {
+    const CondLay L = cond_carve(dtype, n, q_local, m);
+    VrView v;
+    v.Un = (const char*)state + L.off_U; v.Wi = (const char*)state + L.off_W; v.xn = xn;
+    v.m = m; v.mpad = L.mpad;
+    return v;
+}
+
+int lcgp_condition_vr_scratch_bytes(int dtype, int n, int q_local, int m, int n_ref, int n_cand, size_t* bytes) {
+    int rc = check_common(dtype, n, 1, 1, q_local);
+    if (rc) return rc;
+    if ((rc = check_view(m))) return rc;
+    if ((rc = check_vr(n_ref, n_cand))) return rc;
+    if (!bytes) return bad("bytes is NULL");
+    *bytes = vr_carve(dtype, n, q_local, n_ref, n_cand, cov_pad(m)).total;
+    return 0;
+}
+
+int lcgp_condition_vr_prepare(void* stream, int dtype, int kernel_id, int n, int d, int p, int q_local, const void* x, const void* sr,
+                              const double* theta, const void* workspace, const void* state, int m, const void* xn, int n_ref,
+                              const void* x_ref, void* scratch, size_t scratch_bytes) {
+    int rc = check_common(dtype, n, d, p, q_local, kernel_id);
+    if (rc) return rc;
+    if ((rc = check_view(m))) return rc;
+    if ((rc = check_vr(n_ref, 1))) return rc;
+    if (!x || !theta || !workspace || !state || !xn || !x_ref || !scratch) return bad("NULL pointer");
+    if (scratch_bytes < vr_carve(dtype, n, q_local, n_ref, 1, cov_pad(m)).total)
+        return bad("scratch is smaller than lcgp_condition_vr_scratch_bytes(dtype, n, q_local, m, n_ref, 1)");
+    Ws w = carve(dtype, n, d, p, q_local, (void*)workspace);
+    w.kern = kernel_id;
+    const VrView cv = view_of(dtype, n, q_local, state, m, xn);
+    hipStream_t st = (hipStream_t)stream;
+    return dtype == LCGP_F64 ? do_vr_prepare<double>(st, w, x, sr, theta, n_ref, x_ref, (char*)scratch, &cv)
+                             : do_vr_prepare<float>(st, w, x, sr, theta, n_ref, x_ref, (char*)scratch, &cv);
+}
+
+int lcgp_condition_vr(void* stream, int dtype, int kernel_id, int n, int d, int p, int q_local, const void* x, const void* sr,
+                      const double* theta, const void* workspace, const void* state, int m, const void* xn, int n_ref,
+                      const void* x_ref, const double* w_ref, int n_cand, const void* x_cand, const int* match_host, const int* match,
+                      int cand_row0, int r, void* scratch, size_t scratch_bytes, double* out, int out_stride) {
+    int rc = check_common(dtype, n, d, p, q_local, kernel_id);
+    if (rc) return rc;
+    if ((rc = check_view(m))) return rc;
+    if ((rc = check_vr(n_ref, n_cand))) return rc;
+    if (r < 1) return bad("r must be >= 1");
+    if (cand_row0 < -1) return bad("cand_row0 must be -1 or a row of the reference set");
+    if (cand_row0 >= 0) {
+        if ((long long)cand_row0 + n_cand > n_ref) return bad("cand_row0 + n_cand must be <= n_ref");
+        if (x_cand || match_host || match) return bad("cand_row0 >= 0: x_cand and match must be NULL");
+    } else if (!x_cand) {
+        return bad("NULL pointer");
+    }
+    if ((match_host == nullptr) != (match == nullptr)) return bad("match_host and match must both be NULL or both be given");
+    if (match_host)
+        for (int i = 0; i < n_cand; ++i)
+            if (match_host[i] < -1 || match_host[i] >= n) return bad("match must be -1 or a training index in [0, n)");
+    if (!x || !theta || !workspace || !state || !xn || !x_ref || !w_ref || !scratch || !out) return bad("NULL pointer");
+    if (out_stride != 0 && out_stride < n_cand) return bad("out_stride must be 0 (= n_cand) or >= n_cand");
+    if (scratch_bytes < vr_carve(dtype, n, q_local, n_ref, n_cand, cov_pad(m)).total)
+        return bad("scratch is smaller than lcgp_condition_vr_scratch_bytes(dtype, n, q_local, m, n_ref, n_cand)");
+    const int ldo = out_stride ? out_stride : n_cand;
+    Ws w = carve(dtype, n, d, p, q_local, (void*)workspace);
+    w.kern = kernel_id;
+    const VrView cv = view_of(dtype, n, q_local, state, m, xn);
+    hipStream_t st = (hipStream_t)stream;
+    return dtype == LCGP_F64 ? do_vr<double>(st, w, x, sr, theta, n_ref, x_ref, w_ref, n_cand, x_cand, match, cand_row0, r,
+                                             (char*)scratch, out, ldo, &cv)
+                             : do_vr<float>(st, w, x, sr, theta, n_ref, x_ref, w_ref, n_cand, x_cand, match, cand_row0, r,
+                                            (char*)scratch, out, ldo, &cv);
+}
+
+// the checks the five selection entries on a view share; *L receives the layout
+static int check_view_sel(int dtype, int n, int d, int p, int q_local, int kernel_id, int m, int n_ref, int n_cand, int size,
+                          const void* scratch, size_t scratch_bytes, SelLay* L) {
+    int rc = check_common(dtype, n, d, p, q_local, kernel_id);
+    if (rc) return rc;
+    if ((rc = check_view(m))) return rc;
+    if ((rc = check_sel(n_ref, n_cand, size))) return rc;
+    if (!scratch) return bad("NULL pointer");
+    *L = sel_carve(dtype, n, d, q_local, n_ref, n_cand, size, cov_pad(m));
+    if (scratch_bytes < L->total)
+        return bad("scratch is smaller than lcgp_condition_select_scratch_bytes(dtype, n, d, q_local, m, n_ref, n_cand, size)");
+    return 0;
+}
+
+int lcgp_condition_select_scratch_bytes(int dtype, int n, int d, int q_local, int m, int n_ref, int n_cand, int size, size_t* bytes) {
+    int rc = check_common(dtype, n, d, 1, q_local);
+    if (rc) return rc;
+    if ((rc = check_view(m))) return rc;
+    if ((rc = check_sel(n_ref, n_cand, size))) return rc;
+    if (!bytes) return bad("bytes is NULL");
+    *bytes = sel_carve(dtype, n, d, q_local, n_ref, n_cand, size, cov_pad(m)).total;
+    return 0;
+}
+
+int lcgp_condition_select_begin(void* stream, int dtype, int kernel_id, int n, int d, int p, int q_local, const void* x,
+                                const void* sr, const double* theta, const void* workspace, const void* state, int m, const void* xn,
+                                int n_ref, const void* x_ref, const double* w_ref, int n_cand, const void* x_cand,
+                                const int* match_host, const int* match, int r, int size, int pass_rows, void* scratch,
+                                size_t scratch_bytes) {
+    SelLay L;
+    int rc = check_view_sel(dtype, n, d, p, q_local, kernel_id, m, n_ref, n_cand, size, scratch, scratch_bytes, &L);
+    if (rc) return rc;
+    if (r < 1) return bad("r must be >= 1");
+    if (pass_rows < 1 || pass_rows > VR_XBLK) return bad("pass_rows must be in [1, 2048]");
+    if ((match_host == nullptr) != (match == nullptr)) return bad("match_host and match must both be NULL or both be given");
+    if (match_host)
+        for (int i = 0; i < n_cand; ++i)
+            if (match_host[i] < -1 || match_host[i] >= n) return bad("match must be -1 or a training index in [0, n)");
+    if (!x || !theta || !workspace || !state || !xn || !x_ref || !w_ref || !x_cand) return bad("NULL pointer");
+    Ws w = carve(dtype, n, d, p, q_local, (void*)workspace);
+    w.kern = kernel_id;
+    const VrView cv = view_of(dtype, n, q_local, state, m, xn);
+    hipStream_t st = (hipStream_t)stream;
+    return dtype == LCGP_F64 ? do_sel_begin<double>(st, w, x, sr, theta, n_ref, x_ref, w_ref, n_cand, x_cand, match, r, size,
+                                                    pass_rows, (char*)scratch, &cv)
+                             : do_sel_begin<float>(st, w, x, sr, theta, n_ref, x_ref, w_ref, n_cand, x_cand, match, r, size,
+                                                   pass_rows, (char*)scratch, &cv);
+}
+
+int lcgp_condition_select_score(void* stream, int dtype, int n, int d, int q_local, int m, int n_ref, int n_cand, int size, int step,
+                                const double* omega, void* scratch, size_t scratch_bytes, double* out) {
+    SelLay L;
+    int rc = check_view_sel(dtype, n, d, 1, q_local, 0, m, n_ref, n_cand, size, scratch, scratch_bytes, &L);
+    if (rc) return rc;
+    if (step < 0 || step >= size) return bad("step must be in [0, size)");
+    if (!omega) return bad("NULL pointer");
+    char* sc = (char*)scratch;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(sel_score_kernel, dim3(1), dim3(1024), 0, st, (const double*)(sc + L.off_R), q_local, n_cand, omega,
+                       (const int*)(sc + L.off_mask), out, (int*)(sc + L.off_picks) + step);
+    CHECK_LAUNCH("sel_score_kernel");
+    return 0;
+}
+
+int lcgp_condition_select_picks(int dtype, int n, int d, int q_local, int m, int n_ref, int n_cand, int size, void* scratch,
+                                size_t scratch_bytes, int** picks) {
+    SelLay L;
+    int rc = check_view_sel(dtype, n, d, 1, q_local, 0, m, n_ref, n_cand, size, scratch, scratch_bytes, &L);
+    if (rc) return rc;
+    if (!picks) return bad("NULL pointer");
+    *picks = (int*)((char*)scratch + L.off_picks);
+    return 0;
+}
+
+int lcgp_condition_select_condition(void* stream, int dtype, int kernel_id, int n, int d, int p, int q_local, const double* theta,
+                                    int m, int n_ref, int n_cand, int size, int r, int step, const int* pick, void* scratch,
+                                    size_t scratch_bytes) {
+    SelLay L;
+    int rc = check_view_sel(dtype, n, d, p, q_local, kernel_id, m, n_ref, n_cand, size, scratch, scratch_bytes, &L);
+    if (rc) return rc;
+    if (r < 1) return bad("r must be >= 1");
+    if (step < 0 || step >= size) return bad("step must be in [0, size)");
+    if (!theta || !pick) return bad("NULL pointer");
+    Ws w;
+    memset(&w, 0, sizeof(w));
+    w.n = n; w.npad = round_up(n, 2 * TS); w.d = d; w.p = p; w.q = q_local; w.kern = kernel_id;
+    w.esz = dtype == LCGP_F64 ? 8 : 4;
+    hipStream_t st = (hipStream_t)stream;
+    return dtype == LCGP_F64 ? do_sel_condition<double>(st, w, theta, n_ref, n_cand, size, r, step, pick, (char*)scratch, cov_pad(m))
+                             : do_sel_condition<float>(st, w, theta, n_ref, n_cand, size, r, step, pick, (char*)scratch, cov_pad(m));
+}
+
+int lcgp_condition_select_state(void* stream, int dtype, int n, int d, int q_local, int m, int n_ref, int n_cand, int size, int which,
+                                const void* scratch, size_t scratch_bytes, double* out) {
+    SelLay L;
+    int rc = check_view_sel(dtype, n, d, 1, q_local, 0, m, n_ref, n_cand, size, scratch, scratch_bytes, &L);
+    if (rc) return rc;
+    if (which != 0 && which != 1) return bad("which must be 0 (R) or 1 (h)");
+    if (!out) return bad("NULL pointer");
     hipError_t e = hipMemcpyAsync(out, (const char*)scratch + (which ? L.off_h : L.off_R), (size_t)q_local * n_cand * sizeof(double),
                                   hipMemcpyDeviceToDevice, (hipStream_t)stream);
     return e == hipSuccess ? 0 : fail("hipMemcpyAsync", e);

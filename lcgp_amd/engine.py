@@ -728,7 +728,27 @@ class HotPathEngine:
 
     # ------------------------------------------------------------------------------------------------
     # integrated variance reduction at fixed parameters (lcgp_hip.h: lcgp_variance_reduction_prepare / lcgp_variance_reduction)
+    def _view_args(self, state):
+        """what the entries on a conditioned view take beyond those of the fitted model: (m, (state, m, xn) pointers, K' = npad +
+        mpad), after the staleness check of condition_predict_block; state = None (the fitted model): (0, (), npad)"""
+        npad = -(-self.n // 128) * 128
+        if state is None:
+            return 0, (), npad
+        if not self.is_current(state['theta']):
+            raise RuntimeError("the conditioned view does not belong to the factorisation in the workspace")
+        m = state['m']
+        return m, (self._p(state['state']), m, self._p(state['xn'])), npad + -(-m // 128) * 128
+
     def variance_reduction_block(self, x_cand_s, x_ref_s, w, match, r):
+        return self._vr_block(None, x_cand_s, x_ref_s, w, match, r)
+
+    def condition_variance_reduction_block(self, state, x_cand_s, x_ref_s, w, match, r):
+        """variance_reduction_block of the view `state` (condition_begin): R'_k(c) of the model conditioned on the view's runs
+        (lcgp_condition_vr_prepare / lcgp_condition_vr: the same launches on rows widened to K' = npad + mpad).  The base
+        factorisation must still be the one the state was built from."""
+        return self._vr_block(state, x_cand_s, x_ref_s, w, match, r)
+
+    def _vr_block(self, state, x_cand_s, x_ref_s, w, match, r):
         """(q_local, n_cand) float64 DEVICE tensor R_k(c) = sum_t w_t Sigma_k(t, c)^2 / (max(Sigma_k^h(c, c), 0) + 1 / (D_k r)), from
         the factorisation of the last evaluate().  x_cand_s (n_cand, d) / x_ref_s (n_ref, d): standardised; x_ref_s = None: the
         reference set IS the candidate set.  w: n_ref weights (used as given).  match: None or n_cand ints, -1 or the training
@@ -749,10 +769,15 @@ class HotPathEngine:
         n_ref = x_ref_s.shape[0]
         assert x_ref_s.ndim == 2 and x_ref_s.shape[1] == d and n_ref >= 1 and len(w) == n_ref
         chunk = min(n_cand, PREDICT_CHUNK)
+        m, view, kp = self._view_args(state)
         with torch.cuda.device(self.device):
-            nbytes = self._nbytes("lcgp_variance_reduction_scratch_bytes", self.dtype, self.n, self.q_local, n_ref, chunk)
-            scratch = self._grow_scratch(nbytes, ("the variance reduction over %d reference points" % n_ref,
-                                                  "%d components of (n_ref + %d candidates) x n" % (self.q_local, chunk),
+            if state is None:
+                nbytes = self._nbytes("lcgp_variance_reduction_scratch_bytes", self.dtype, self.n, self.q_local, n_ref, chunk)
+                detail = "%d components of (n_ref + %d candidates) x n" % (self.q_local, chunk)
+            else:
+                nbytes = self._nbytes("lcgp_condition_vr_scratch_bytes", self.dtype, self.n, self.q_local, m, n_ref, chunk)
+                detail = "%d components of (n_ref + %d candidates) x K', K' = npad + mpad = %d" % (self.q_local, chunk, kp)
+            scratch = self._grow_scratch(nbytes, ("the variance reduction over %d reference points" % n_ref, detail,
                                                   "pass fewer reference points"))
             xr = torch.as_tensor(x_ref_s).to(self.device, self.tdtype).contiguous()
             xc = None if shared else torch.as_tensor(x_cand_s).to(self.device, self.tdtype).contiguous()
@@ -761,17 +786,20 @@ class HotPathEngine:
             out = torch.empty((self.q_local, n_cand), dtype=torch.float64, device=self.device)
             st, xp, srp, thp, wsp, scp = (self._stream(), self._p(self.x), self._p(self.sr), self._p(self.theta_dev),
                                           self._p(self.workspace), self._p(scratch))
-            _hip.check(self.lib.lcgp_variance_reduction_prepare(st, self.dtype, self.kernel_id, self.n, d, self.p, self.q_local, xp, srp,
-                                                                thp, wsp, n_ref, self._p(xr), scp), "lcgp_variance_reduction_prepare")
+            # (the entries on a view take the view behind the workspace and the scratch size behind the scratch)
+            prepare, entry = (("lcgp_variance_reduction_prepare", "lcgp_variance_reduction") if state is None else
+                              ("lcgp_condition_vr_prepare", "lcgp_condition_vr"))
+            scs = (scp,) if state is None else (scp, scratch.numel())
+            head = (st, self.dtype, self.kernel_id, self.n, d, self.p, self.q_local, xp, srp, thp, wsp) + view
+            _hip.check(getattr(self.lib, prepare)(*head, n_ref, self._p(xr), *scs), prepare)
             for lo in range(0, n_cand, chunk):
-                m = min(chunk, n_cand - lo)
+                rows = min(chunk, n_cand - lo)
                 xcp = C.c_void_p(0) if shared else C.c_void_p(xc.data_ptr() + lo * d * xc.element_size())
                 mh = C.c_void_p(0) if match is None else C.c_void_p(match.ctypes.data + 4 * lo)
                 mdp = C.c_void_p(0) if match is None else C.c_void_p(md.data_ptr() + 4 * lo)
-                _hip.check(self.lib.lcgp_variance_reduction(st, self.dtype, self.kernel_id, self.n, d, self.p, self.q_local, xp, srp,
-                                                            thp, wsp, n_ref, self._p(xr), self._p(wd), m, xcp, mh, mdp,
-                                                            lo if shared else -1, int(r), scp, C.c_void_p(out.data_ptr() + 8 * lo),
-                                                            n_cand), "lcgp_variance_reduction")
+                _hip.check(getattr(self.lib, entry)(*head, n_ref, self._p(xr), self._p(wd), rows, xcp, mh, mdp,
+                                                    lo if shared else -1, int(r), *scs, C.c_void_p(out.data_ptr() + 8 * lo),
+                                                    n_cand), entry)
             return out
 
     def variance_reduction_grad_block(self, x_cand_s, x_ref_s, w, r):
@@ -818,6 +846,14 @@ class HotPathEngine:
     # ------------------------------------------------------------------------------------------------
     # greedy batch design by sequential ALC (lcgp_hip.h: lcgp_select_begin / lcgp_select_score / lcgp_select_condition)
     def select_begin(self, x_cand_s, x_ref_s, w, match, r, size):
+        return self._select_begin(None, x_cand_s, x_ref_s, w, match, r, size)
+
+    def condition_select_begin(self, state, x_cand_s, x_ref_s, w, match, r, size):
+        """select_begin on the view `state` (condition_begin): the selection starts from the model conditioned on the view's
+        runs (lcgp_condition_select_begin).  condition_select_rows / condition_select_condition carry it on."""
+        return self._select_begin(state, x_cand_s, x_ref_s, w, match, r, size)
+
+    def _select_begin(self, state, x_cand_s, x_ref_s, w, match, r, size):
         """Starts a greedy selection of `size` of the candidates: U and gvar of the reference set and of ALL candidates into the
         engine's scratch (candidates in passes of PREDICT_CHUNK rows) and the step-0 state R = variance_reduction_block(...) bitwise.
         Arguments as variance_reduction_block.  Raises ValueError when the scratch does not fit in the free device memory.  The
@@ -835,41 +871,47 @@ class HotPathEngine:
         n_ref = x_ref_s.shape[0]
         assert x_ref_s.ndim == 2 and x_ref_s.shape[1] == d and n_ref >= 1 and len(w) == n_ref
         self._sel = None
+        m, view, kp = self._view_args(state)
         with torch.cuda.device(self.device):
-            dims = (self.dtype, self.n, d, self.q_local, n_ref, n_cand, int(size))
-            nbytes = self._nbytes("lcgp_select_scratch_bytes", *dims)
-            scratch = self._grow_scratch(nbytes, ("the batch selection over %d candidates" % n_cand,
-                                                  "%d components of (%d reference points + %d candidates) x n, all resident"
-                                                  % (self.q_local, n_ref, n_cand), "pass fewer candidates"))
+            # (dims: what every entry of the family takes; on a view m goes behind q_local)
+            dims = (self.dtype, self.n, d, self.q_local) + ((m,) if view else ()) + (n_ref, n_cand, int(size))
+            pre = "lcgp_condition_select_" if view else "lcgp_select_"
+            nbytes = self._nbytes(pre + "scratch_bytes", *dims)
+            detail = ("%d components of (%d reference points + %d candidates) x %s, all resident"
+                      % (self.q_local, n_ref, n_cand, "K', K' = npad + mpad = %d" % kp if view else "n"))
+            scratch = self._grow_scratch(nbytes, ("the batch selection over %d candidates" % n_cand, detail, "pass fewer candidates"))
             xr = torch.as_tensor(x_ref_s).to(self.device, self.tdtype).contiguous()
             xc = torch.as_tensor(x_cand_s).to(self.device, self.tdtype).contiguous()
             wd = torch.as_tensor(np.ascontiguousarray(w, np.float64)).to(self.device)
             md = None if match is None else torch.as_tensor(match).to(self.device)
-            _hip.check(self.lib.lcgp_select_begin(self._stream(), self.dtype, self.kernel_id, self.n, d, self.p, self.q_local,
-                                                  self._p(self.x), self._p(self.sr), self._p(self.theta_dev), self._p(self.workspace),
-                                                  n_ref, self._p(xr), self._p(wd), n_cand, self._p(xc),
-                                                  C.c_void_p(0) if match is None else C.c_void_p(match.ctypes.data),
-                                                  C.c_void_p(0) if md is None else self._p(md), int(r), int(size),
-                                                  min(PREDICT_CHUNK, 2048), self._p(scratch)), "lcgp_select_begin")
+            scs = (self._p(scratch), scratch.numel()) if view else (self._p(scratch),)
+            _hip.check(getattr(self.lib, pre + "begin")(
+                self._stream(), self.dtype, self.kernel_id, self.n, d, self.p, self.q_local,
+                self._p(self.x), self._p(self.sr), self._p(self.theta_dev), self._p(self.workspace), *view,
+                n_ref, self._p(xr), self._p(wd), n_cand, self._p(xc),
+                C.c_void_p(0) if match is None else C.c_void_p(match.ctypes.data),
+                C.c_void_p(0) if md is None else self._p(md), int(r), int(size),
+                min(PREDICT_CHUNK, 2048), *scs), pre + "begin")
             picks = C.c_void_p(0)
-            _hip.check(self.lib.lcgp_select_picks(*dims, self._p(scratch), C.byref(picks)), "lcgp_select_picks")
-            self._sel = dict(dims=dims, scratch=scratch, n_ref=n_ref, n_cand=n_cand, size=int(size), r=int(r), step=0,
-                             picks=picks.value, keep=(xr, xc, wd, md))
+            _hip.check(getattr(self.lib, pre + "picks")(*dims, *scs, C.byref(picks)), pre + "picks")
+            self._sel = dict(dims=dims, scratch=scratch, scs=scs, pre=pre, m=m, n_ref=n_ref, n_cand=n_cand, size=int(size), r=int(r),
+                             step=0, picks=picks.value, keep=(xr, xc, wd, md, state))
 
     def select_rows(self):
         """(q_local, n_cand) float64 DEVICE tensor: R_k(c) of the model conditioned on the picks made so far"""
         sel, torch = self._sel, self.torch
         with torch.cuda.device(self.device):
             out = torch.empty((self.q_local, sel['n_cand']), dtype=torch.float64, device=self.device)
-            _hip.check(self.lib.lcgp_select_state(self._stream(), *sel['dims'], 0, self._p(sel['scratch']), self._p(out)),
-                       "lcgp_select_state")
+            _hip.check(getattr(self.lib, sel['pre'] + "state")(self._stream(), *sel['dims'], 0, *sel['scs'], self._p(out)),
+                       sel['pre'] + "state")
             return out
 
     def _select_condition(self, sel, pick_ptr):
-        _hip.check(self.lib.lcgp_select_condition(self._stream(), self.dtype, self.kernel_id, self.n, self.d, self.p, self.q_local,
-                                                  self._p(self.theta_dev), sel['n_ref'], sel['n_cand'], sel['size'], sel['r'],
-                                                  sel['step'], C.c_void_p(pick_ptr), self._p(sel['scratch'])),
-                   "lcgp_select_condition")
+        view = (sel['m'],) if sel['m'] else ()
+        _hip.check(getattr(self.lib, sel['pre'] + "condition")(
+            self._stream(), self.dtype, self.kernel_id, self.n, self.d, self.p, self.q_local, self._p(self.theta_dev), *view,
+            sel['n_ref'], sel['n_cand'], sel['size'], sel['r'], sel['step'], C.c_void_p(pick_ptr), *sel['scs']),
+            sel['pre'] + "condition")
         sel['step'] += 1
 
     def select_condition(self, j):
@@ -879,20 +921,36 @@ class HotPathEngine:
             jd = torch.full((1,), int(j), dtype=torch.int32, device=self.device)
             self._select_condition(sel, jd.data_ptr())
 
+    # (the view's selection lives in the same scratch and the same state record: these carry on whichever began)
+    def condition_select_rows(self):
+        """select_rows of a selection begun by condition_select_begin"""
+        return self.select_rows()
+
+    def condition_select_condition(self, j):
+        """select_condition of a selection begun by condition_select_begin"""
+        return self.select_condition(j)
+
     def select_batch_block(self, x_cand_s, x_ref_s, w, match, r, size, omega):
+        return self._select_batch_block(None, x_cand_s, x_ref_s, w, match, r, size, omega)
+
+    def condition_select_batch_block(self, state, x_cand_s, x_ref_s, w, match, r, size, omega):
+        """select_batch_block on the view `state` (condition_begin)"""
+        return self._select_batch_block(state, x_cand_s, x_ref_s, w, match, r, size, omega)
+
+    def _select_batch_block(self, state, x_cand_s, x_ref_s, w, match, r, size, omega):
         """The whole greedy loop on the device for the engine's components (one rank holds them all): returns DEVICE tensors
         idx (size,) int32 and scores (size, n_cand) float64, row t = sum_k omega_k R_k^t, -inf at candidates picked before step t.
         All steps are enqueued without a host synchronisation (the kernels read each pick from device memory)."""
         torch = self.torch
-        self.select_begin(x_cand_s, x_ref_s, w, match, r, size)
+        self._select_begin(state, x_cand_s, x_ref_s, w, match, r, size)
         sel = self._sel
         with torch.cuda.device(self.device):
             om = torch.as_tensor(np.ascontiguousarray(omega, np.float64)).to(self.device)
             scores = torch.empty((sel['size'], sel['n_cand']), dtype=torch.float64, device=self.device)
-            st, scp = self._stream(), self._p(sel['scratch'])
+            st, score = self._stream(), getattr(self.lib, sel['pre'] + "score")
             for t in range(sel['size']):
-                _hip.check(self.lib.lcgp_select_score(st, *sel['dims'], t, self._p(om), scp,
-                                                      C.c_void_p(scores.data_ptr() + 8 * t * sel['n_cand'])), "lcgp_select_score")
+                _hip.check(score(st, *sel['dims'], t, self._p(om), *sel['scs'],
+                                 C.c_void_p(scores.data_ptr() + 8 * t * sel['n_cand'])), sel['pre'] + "score")
                 if t + 1 < sel['size']:
                     self._select_condition(sel, sel['picks'] + 4 * t)
             idx = torch.empty(sel['size'], dtype=torch.int32, device=self.device)

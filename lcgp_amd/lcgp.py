@@ -319,6 +319,56 @@ class ConditionedLCGP:
             return _t(ghat.copy()), _t(gvar.copy())
         return tuple(r.detach() for r in base._outputs(ghat, gvar))
 
+    def _design_arguments(self, xc_s, match):
+        """what the design queries check beyond the base model's: the view is current, and on the rep path no candidate equals
+        one of the view's new inputs"""
+        self._require_current()
+        base = self.base
+        if match is not None:
+            new = {row.tobytes() for row in np.ascontiguousarray(base._standardise_x0(_np(self.x_new))[0])}
+            if any(row.tobytes() in new for row in np.ascontiguousarray(xc_s)):
+                raise ValueError('a candidate equals one of the new inputs of this view (bitwise after standardisation): it would '
+                                 'have to share a nugget with that run, and the view has no column to add replicates to; refit '
+                                 'with the new runs instead')
+
+    def variance_reduction(self, x_cand, x_ref=None, weights=None, outputs=None, replicates=1, latent=False):
+        """LCGP.variance_reduction() of the conditioned model: for each candidate the drop of the weighted predictive variance
+        over the reference set if the simulator ran there once more, GIVEN the base model's data and this view's new runs, at
+        the fixed parameters.  Equal, to rounding, to variance_reduction() of a model built on the augmented data at the same
+        parameters; nothing is refactorised (the base model's kernels on rows widened by the view's m columns).
+        Arguments, checks, the output map and the full / rep rules are exactly LCGP.variance_reduction()'s; on the rep path a
+        candidate equal to a BASE training input adds `replicates` runs to it.  A candidate bitwise equal (after
+        standardisation) to one of the view's new inputs raises ValueError on the rep path (it would share a nugget with that
+        run; refit for it); on the full path it is one more new row with its own nugget.  RuntimeError when the view is stale.
+        GPU memory: the base method's with rows of K' = npad + mpad instead of npad (mpad = m rounded up to 128)."""
+        base = self.base
+        xc_s, xr_s, w, outputs, r, match = base._vr_arguments(x_cand, x_ref, weights, outputs, replicates)
+        self._design_arguments(xc_s, match)
+        eng = self._engine
+        loc = base._agree(lambda: None if eng is None else
+                          eng.condition_variance_reduction_block(self._state, xc_s, xr_s, w, match, r))
+        R = base._gather_components(loc, (xc_s.shape[0],))
+        if latent:
+            return _t(R)
+        W, _, scale, _ = base._output_map()
+        delta = (W[:, outputs] ** 2).T @ R * (scale[outputs] ** 2)[:, None]
+        return _t(delta)
+
+    def select_batch(self, x_cand, size, x_ref=None, weights=None, outputs=None, replicates=1, return_scores=False):
+        """LCGP.select_batch() of the conditioned model: the next batch GIVEN the base model's data and this view's new runs --
+        same contract, same returns (idx, gain[, scores]), same checks as there and as variance_reduction() of this view.  On
+        one rank the whole loop runs on the device; on several ranks each step is gathered and rank 0's argmax broadcast, as
+        on the base model.  To go on after the batch has been run, condition the base model on all new runs so far."""
+        base = self.base
+        xc_s, xr_s, w, r, match, size, omega = base._select_arguments(x_cand, size, x_ref, weights, outputs, replicates)
+        self._design_arguments(xc_s, match)
+        eng, st = self._engine, self._state
+        return base._select_run(
+            eng, xc_s.shape[0], size, omega, return_scores,
+            block=lambda: eng.condition_select_batch_block(st, xc_s, xr_s, w, match, r, size, omega[base._local_ks]),
+            begin=lambda: eng.condition_select_begin(st, xc_s, xr_s, w, match, r, size),
+            rows=lambda: eng.condition_select_rows(), condition=lambda j: eng.condition_select_condition(j))
+
 
 class LCGP:
     """
@@ -1719,6 +1769,17 @@ class LCGP:
         synchronisation.  GPU memory: q_local (n_ref + n_cand) npad elements (ALL candidates resident) plus q_local size
         (n_ref + n_cand) doubles of history -- ValueError when it does not fit.  The model is left unchanged (ghat, gvar, the
         factorisation and n untouched)."""
+        xc_s, xr_s, w, r, match, size, omega = self._select_arguments(x_cand, size, x_ref, weights, outputs, replicates)
+        eng = self._ensure_aux()
+        return self._select_run(
+            eng, xc_s.shape[0], size, omega, return_scores,
+            block=lambda: eng.select_batch_block(xc_s, xr_s, w, match, r, size, omega[self._local_ks]),
+            begin=lambda: eng.select_begin(xc_s, xr_s, w, match, r, size),
+            rows=lambda: eng.select_rows(), condition=lambda j: eng.select_condition(j))
+
+    def _select_arguments(self, x_cand, size, x_ref, weights, outputs, replicates):
+        """_vr_arguments plus what select_batch() of the model and of a conditioned view check and form beyond it: size, no
+        duplicate candidates, the score weights omega (q,)"""
         xc_s, xr_s, w, outputs, r, match = self._vr_arguments(x_cand, x_ref, weights, outputs, replicates)
         n_cand = xc_s.shape[0]
         if isinstance(size, (bool, np.bool_)) or int(size) != size or size < 1 or size > n_cand:
@@ -1728,24 +1789,28 @@ class LCGP:
             raise ValueError('x_cand holds duplicate rows (bitwise equal after standardisation): two copies of one input would '
                              'have to share a nugget; pass each candidate once')
         W, _, scale, _ = self._output_map()
-        q = int(self.q)
         omega = np.mean((W[:, outputs] ** 2) * (scale[outputs] ** 2)[None, :], axis=1)
-        eng = self._ensure_aux()
+        return xc_s, xr_s, w, r, match, size, omega
+
+    def _select_run(self, eng, n_cand, size, omega, return_scores, block, begin, rows, condition):
+        """the greedy loop of select_batch(), of the model and of a conditioned view: `block` runs it whole on the device,
+        `begin` / `rows` / `condition` are its steps on this rank's engine (eng = None: a rank without components)"""
+        q = int(self.q)
         if not _dist.use_collectives(self._group):
             # one rank holds every component: the whole loop on the device, one copy back
-            idx_d, sc_d = self._agree(lambda: eng.select_batch_block(xc_s, xr_s, w, match, r, size, omega[self._local_ks]))
+            idx_d, sc_d = self._agree(block)
             idx = idx_d.cpu().numpy().astype(np.int64)
             scores = sc_d.cpu().numpy()
         else:
             # components sharded over ranks: per step the local rows are gathered (disjoint components: the sum is a gather, so
             # every rank adds the q terms in the order one rank does), rank 0's argmax is broadcast
-            self._agree(lambda: None if eng is None else eng.select_begin(xc_s, xr_s, w, match, r, size))
+            self._agree(lambda: None if eng is None else begin())
             dev = None if eng is None else eng.device
             idx = np.zeros(size, np.int64)
             scores = np.empty((size, n_cand), F64)
             picked = np.zeros(n_cand, bool)
             for t in range(size):
-                R = self._gather_components(None if eng is None else eng.select_rows(), (n_cand,))
+                R = self._gather_components(None if eng is None else rows(), (n_cand,))
                 s = np.zeros(n_cand, F64)
                 for k in range(q):
                     s = s + omega[k] * R[k]
@@ -1753,7 +1818,7 @@ class LCGP:
                 j = int(_dist.broadcast_array(np.array([np.argmax(s)], F64), 0, self._group, dev)[0])
                 idx[t], scores[t], picked[j] = j, s, True
                 if eng is not None and t + 1 < size:
-                    eng.select_condition(j)
+                    condition(j)
         gain = scores[np.arange(size), idx].copy()
         if return_scores:
             return torch.as_tensor(idx), _t(gain), _t(scores)

@@ -707,6 +707,32 @@ int lcgp_condition_select_condition(void* stream, int dtype, int kernel_id, int 
 int lcgp_condition_select_state(void* stream, int dtype, int n, int d, int q_local, int m, int n_ref, int n_cand, int size,
                                 int which, const void* scratch, size_t scratch_bytes, double* out);
 
+/* Calibration rows (no counterpart in the reference): the log density of ONE observation vector of the outputs given the
+ * latent prediction of each of n0 inputs, and its derivatives.  With Phi_s the (scaled) output map restricted to the observed
+ * outputs, t the centred observation and Lambda the input-independent part of the covariance (noise + observation covariance),
+ * the caller folds everything output-sized ONCE into
+ *     M = Phi_s^T Lambda^-1 Phi_s (q x q, symmetric),  b = Phi_s^T Lambda^-1 t,  c0 = t^T Lambda^-1 t,
+ *     lognorm = logdet Lambda + |O| log 2 pi
+ * and per row i, with g = ghat[:, i] and h = sqrt(max(gvar[:, i], 0)):
+ *     w = b - M g,   K = I + diag(h) M diag(h) = L L^T   (eigenvalues >= 1: never fails for finite input),   u = L^-1 (h o w)
+ *     ll[i] = -1/2 (c0 - 2 b.g + g^T M g - u.u + 2 sum_k log L_kk + lognorm)
+ *           = log N(y_obs; Phi_s g, Phi_s diag(gvar) Phi_s^T + Lambda)
+ *     s = w - M (h o L^-T u) = d ll / d ghat,   R = L^-1 diag(h) M,   v_k = 1/2 s_k^2 - 1/2 (M_kk - sum_j R_jk^2) = d ll / d gvar_k
+ *     dll[i, l] = inv_range[l] sum_k (s_k dghat[k, i, l] + v_k dgvar[k, i, l])
+ * (no division by gvar anywhere: rows with gvar = 0 are ordinary).  ghat, gvar, dghat, dgvar are the double arrays lcgp_predict /
+ * lcgp_predict_grad write, for models of either precision; q is the TOTAL number of components (the q x q system couples them).
+ * One launch: q <= 8 one thread per row with every component loop unrolled, 8 < q <= 64 one wavefront per row with the factor
+ * in 16 q^2 bytes of LDS.  float64, no atomics, fixed summation order: a row's results are bitwise reproducible, independent of
+ * the content of the outputs on entry and of how a caller splits the rows over calls.  Arguments are checked before any launch. */
+#define LCGP_CALIB_MAX_Q 64
+int lcgp_calib_rows(void* stream, int q, int d, int n0,
+                    const double* ghat, const double* gvar,      /* q rows of n0, in_stride apart (0 = n0) */
+                    const double* dghat, const double* dgvar,    /* q x n0 x d, row k at k * in_stride * d; both NULL: no gradient */
+                    int in_stride,
+                    const double* M /* q x q, device */, const double* b /* q, device */, double c0, double lognorm,
+                    const double* inv_range /* d, device; NULL = ones */,
+                    double* ll /* n0 */, double* dll /* n0 x d or NULL */, double* sens /* 2 x q x n0 (s then v) or NULL */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6072,6 +6072,233 @@ int check_folds(int n, int q_local, int F, const int* folds, int* mmax) {
     return 0;
 }
 
+// ---------------------------------------------------------------------------------------------------
+// calibration rows (lcgp_calib_rows): per row i the Gaussian log density of one observation vector given the row's latent
+// prediction, folded to q-space (include/lcgp_hip.h), with its sensitivities s = d ll / d ghat, v = d ll / d gvar and the
+// contraction with the latent Jacobians.  float64; one launch; no atomics; every row is computed from its own inputs in a
+// fixed order, so a row's result does not depend on which call or which position it is in.
+// M is symmetric (the host symmetrises it): both kernels read M[j * q + k] for M_kj.
+// The formulas are evaluated as the header states them (a by back substitution, s = w - M a): the kernels differ from a plain
+// float64 evaluation in summation order and fused multiply-adds only.
+// ---------------------------------------------------------------------------------------------------
+
+// q <= 8: one thread per row, Q a template parameter and every loop over components unrolled (K, L, the vectors: registers;
+// no runtime-indexed array).  M and b are staged once per workgroup in LDS and read as broadcasts.
+template <int Q, bool GRAD>
+__global__ __launch_bounds__(64) void calib_rows_small_kernel(int d, int n0, const double* __restrict__ ghat,
+                                                               const double* __restrict__ gvar, const double* __restrict__ dghat,
+                                                               const double* __restrict__ dgvar, size_t ld,
+                                                               const double* __restrict__ M, const double* __restrict__ b, double c0,
+                                                               double lognorm, const double* __restrict__ inv_range,
+                                                               double* __restrict__ ll, double* __restrict__ dll,
+                                                               double* __restrict__ sens) {
+    __shared__ double sM[Q * Q];
+    __shared__ double sb[Q];
+    for (int t = threadIdx.x; t < Q * Q; t += 64) sM[t] = M[t];
+    if (threadIdx.x < Q) sb[threadIdx.x] = b[threadIdx.x];
+    __syncthreads();
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= n0) return;
+    double g[Q], h[Q], w[Q], u[Q];
+#pragma unroll
+    for (int k = 0; k < Q; ++k) {
+        g[k] = ghat[(size_t)k * ld + i];
+        h[k] = sqrt(fmax(gvar[(size_t)k * ld + i], 0.0));
+    }
+    double bg = 0.0, gmg = 0.0;
+#pragma unroll
+    for (int k = 0; k < Q; ++k) {
+        double mg = 0.0;
+#pragma unroll
+        for (int j = 0; j < Q; ++j) mg += sM[j * Q + k] * g[j];
+        w[k] = sb[k] - mg;
+        bg += sb[k] * g[k];
+        gmg += g[k] * mg;
+    }
+    // K = I + diag(h) M diag(h) = L L^T, row by row (only the lower triangle of L is ever touched)
+    double L[Q][Q];
+    double sumlog = 0.0, uu = 0.0;
+#pragma unroll
+    for (int r = 0; r < Q; ++r) {
+#pragma unroll
+        for (int j = 0; j <= r; ++j) {
+            double acc = h[r] * sM[j * Q + r] * h[j] + (j == r ? 1.0 : 0.0);
+#pragma unroll
+            for (int m = 0; m < j; ++m) acc -= L[r][m] * L[j][m];
+            L[r][j] = j == r ? sqrt(acc) : acc / L[j][j];
+        }
+        sumlog += log(L[r][r]);
+        double acc = h[r] * w[r];
+#pragma unroll
+        for (int m = 0; m < r; ++m) acc -= L[r][m] * u[m];
+        u[r] = acc / L[r][r];
+        uu += u[r] * u[r];
+    }
+    ll[i] = -0.5 * (c0 - 2.0 * bg + gmg - uu + 2.0 * sumlog + lognorm);
+    if (!GRAD && !sens) return;
+    // a = h o L^-T u (u is overwritten), then per component s_k = w_k - (M a)_k and column k of R = L^-1 diag(h) M for its
+    // squared norm (T_kk = M_kk - |R_k|^2)
+#pragma unroll
+    for (int j = Q - 1; j >= 0; --j) {
+        double acc = u[j];
+#pragma unroll
+        for (int m = j + 1; m < Q; ++m) acc -= L[m][j] * u[m];
+        u[j] = acc / L[j][j];
+    }
+#pragma unroll
+    for (int j = 0; j < Q; ++j) u[j] *= h[j];
+    double s[Q], v[Q];
+#pragma unroll
+    for (int k = 0; k < Q; ++k) {
+        double y[Q];
+        double tk = 0.0, ma = 0.0;
+#pragma unroll
+        for (int j = 0; j < Q; ++j) {
+            double acc = h[j] * sM[j * Q + k];
+#pragma unroll
+            for (int m = 0; m < j; ++m) acc -= L[j][m] * y[m];
+            y[j] = acc / L[j][j];
+            tk += y[j] * y[j];
+            ma += sM[j * Q + k] * u[j];
+        }
+        s[k] = w[k] - ma;
+        v[k] = 0.5 * s[k] * s[k] - 0.5 * (sM[k * Q + k] - tk);
+    }
+    if (sens) {
+#pragma unroll
+        for (int k = 0; k < Q; ++k) {
+            sens[(size_t)k * n0 + i] = s[k];
+            sens[(size_t)(Q + k) * n0 + i] = v[k];
+        }
+    }
+    if (GRAD) {
+        for (int l = 0; l < d; ++l) {
+            double acc = 0.0;
+#pragma unroll
+            for (int k = 0; k < Q; ++k) {
+                const size_t at = ((size_t)k * ld + i) * d + l;
+                acc += s[k] * dghat[at] + v[k] * dgvar[at];
+            }
+            dll[(size_t)i * d + l] = inv_range ? inv_range[l] * acc : acc;
+        }
+    }
+}
+
+// v of lane `lane` (the same lane for the whole wave) in every lane
+__device__ __forceinline__ double calib_lane(double v, int lane) {
+    const int lo = __builtin_amdgcn_readlane(__double2loint(v), lane);
+    const int hi = __builtin_amdgcn_readlane(__double2hiint(v), lane);
+    return __hiloint2double(hi, lo);
+}
+
+// 8 < q <= 64: one wavefront (= one workgroup) per row, lane k owns component k: row k of the left-looking Cholesky, then
+// column k of R.  Dynamic LDS, 2 q^2 doubles: LT[m * q + k] = L[k][m] (the factor stored transposed: lanes read consecutive
+// addresses, the pivot row is a broadcast, so no padding is needed) and R[j * q + k] (diag(h) M, solved in place, each lane
+// its own column).  The forward substitution for u rides on the factorisation's steps.
+__global__ __launch_bounds__(64) void calib_rows_wave_kernel(int q, int d, int n0, const double* __restrict__ ghat,
+                                                              const double* __restrict__ gvar, const double* __restrict__ dghat,
+                                                              const double* __restrict__ dgvar, size_t ld,
+                                                              const double* __restrict__ M, const double* __restrict__ b, double c0,
+                                                              double lognorm, const double* __restrict__ inv_range,
+                                                              double* __restrict__ ll, double* __restrict__ dll,
+                                                              double* __restrict__ sens) {
+    extern __shared__ __attribute__((aligned(16))) char calib_lds[];
+    double* LT = (double*)calib_lds;
+    double* R = LT + q * q;
+    const int k = threadIdx.x;
+    const int i = blockIdx.x;
+    const bool on = k < q;
+    const double g = on ? ghat[(size_t)k * ld + i] : 0.0;
+    const double h = on ? sqrt(fmax(gvar[(size_t)k * ld + i], 0.0)) : 0.0;
+    const double bk = on ? b[k] : 0.0;
+    double mg = 0.0, mkk = 0.0;
+    for (int j = 0; j < q; ++j) {
+        const double gj = calib_lane(g, j), hj = calib_lane(h, j);
+        if (on) {
+            const double m = M[j * q + k];
+            mg += m * gj;
+            R[j * q + k] = hj * m;
+            if (j == k) mkk = m;
+        }
+    }
+    const double w = bk - mg;
+    const double bg = wave_sum(bk * g), gmg = wave_sum(g * mg);
+    double rhs = h * w, u = 0.0, sumlog = 0.0, uu = 0.0;
+    for (int j = 0; j < q; ++j) {
+        double acc = 0.0;
+        if (on && k >= j) {
+            acc = h * R[j * q + k] + (j == k ? 1.0 : 0.0);
+            for (int m = 0; m < j; ++m) acc -= LT[m * q + k] * LT[m * q + j];
+        }
+        const double piv = sqrt(calib_lane(acc, j));
+        const double lkj = k == j ? piv : acc / piv;
+        if (on && k >= j) LT[j * q + k] = lkj;
+        sumlog += log(piv);
+        const double uj = calib_lane(rhs, j) / piv;
+        if (k == j) u = uj;
+        if (k > j) rhs -= lkj * uj;
+        uu += uj * uj;
+        __syncthreads();        // (one wave per workgroup) row j of LT is read by every lane from the next step on
+    }
+    if (k == 0) ll[i] = -0.5 * (c0 - 2.0 * bg + gmg - uu + 2.0 * sumlog + lognorm);
+    if (!dll && !sens) return;
+    // x = L^-T u, one wave sum per step: lane m > j holds its final x_m and reads L[m][j] = LT[j * q + m] (consecutive addresses)
+    double xk = 0.0;
+    for (int j = q - 1; j >= 0; --j) {
+        const double rest = wave_sum(on && k > j ? LT[j * q + k] * xk : 0.0);
+        const double xj = (calib_lane(u, j) - rest) / LT[j * q + j];
+        if (k == j) xk = xj;
+    }
+    const double a = h * xk;
+    double tk = 0.0, ma = 0.0;
+    for (int j = 0; j < q; ++j) {
+        const double aj = calib_lane(a, j);
+        if (on) {
+            ma += M[j * q + k] * aj;
+            double acc = R[j * q + k];
+            for (int m = 0; m < j; ++m) acc -= LT[m * q + j] * R[m * q + k];
+            const double y = acc / LT[j * q + j];
+            R[j * q + k] = y;
+            tk += y * y;
+        }
+    }
+    const double s = w - ma;
+    const double v = 0.5 * s * s - 0.5 * (mkk - tk);
+    if (sens && on) {
+        sens[(size_t)k * n0 + i] = s;
+        sens[(size_t)(q + k) * n0 + i] = v;
+    }
+    if (dll) {
+        for (int l0 = 0; l0 < d; l0 += 64) {
+            const int l = l0 + k;
+            double acc = 0.0;
+            for (int c = 0; c < q; ++c) {
+                const double sc = calib_lane(s, c), vc = calib_lane(v, c);
+                if (l < d) {
+                    const size_t at = ((size_t)c * ld + i) * d + l;
+                    acc += sc * dghat[at] + vc * dgvar[at];
+                }
+            }
+            if (l < d) dll[(size_t)i * d + l] = inv_range ? inv_range[l] * acc : acc;
+        }
+    }
+}
+
+template <int Q>
+int launch_calib_small(hipStream_t st, int d, int n0, const double* ghat, const double* gvar, const double* dghat,
+                       const double* dgvar, size_t ld, const double* M, const double* b, double c0, double lognorm,
+                       const double* inv_range, double* ll, double* dll, double* sens) {
+    const dim3 grid((n0 + 63) / 64), block(64);
+    if (dll)
+        hipLaunchKernelGGL((calib_rows_small_kernel<Q, true>), grid, block, 0, st, d, n0, ghat, gvar, dghat, dgvar, ld, M, b, c0,
+                           lognorm, inv_range, ll, dll, sens);
+    else
+        hipLaunchKernelGGL((calib_rows_small_kernel<Q, false>), grid, block, 0, st, d, n0, ghat, gvar, dghat, dgvar, ld, M, b, c0,
+                           lognorm, inv_range, ll, dll, sens);
+    CHECK_LAUNCH("calib_rows_small");
+    return 0;
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------------
@@ -7015,6 +7242,32 @@ int lcgp_condition_select_state(void* stream, int dtype, int n, int d, int q_loc
     hipError_t e = hipMemcpyAsync(out, (const char*)scratch + (which ? L.off_h : L.off_R), (size_t)q_local * n_cand * sizeof(double),
                                   hipMemcpyDeviceToDevice, (hipStream_t)stream);
     return e == hipSuccess ? 0 : fail("hipMemcpyAsync", e);
+}
+
+int lcgp_calib_rows(void* stream, int q, int d, int n0, const double* ghat, const double* gvar, const double* dghat,
+                    const double* dgvar, int in_stride, const double* M, const double* b, double c0, double lognorm,
+                    const double* inv_range, double* ll, double* dll, double* sens) {
+    if (q < 1 || q > LCGP_CALIB_MAX_Q) return bad("q must be in [1, LCGP_CALIB_MAX_Q = 64]");
+    if (d < 1 || d > DWIDE) return bad("d must be in [1, 126]");
+    if (n0 < 1) return bad("n0 < 1");
+    if (!ghat || !gvar || !M || !b || !ll) return bad("NULL pointer");
+    if ((dghat == nullptr) != (dgvar == nullptr)) return bad("dghat and dgvar must both be given or both be NULL");
+    if (dll && !dghat) return bad("dll needs the Jacobians dghat and dgvar");
+    if (in_stride != 0 && in_stride < n0) return bad("in_stride must be 0 (= n0) or >= n0");
+    const size_t ld = in_stride ? in_stride : n0;
+    hipStream_t st = (hipStream_t)stream;
+    switch (q) {
+#define LCGP_CALIB_CASE(Q) \
+    case Q: return launch_calib_small<Q>(st, d, n0, ghat, gvar, dghat, dgvar, ld, M, b, c0, lognorm, inv_range, ll, dll, sens);
+        LCGP_CALIB_CASE(1) LCGP_CALIB_CASE(2) LCGP_CALIB_CASE(3) LCGP_CALIB_CASE(4)
+        LCGP_CALIB_CASE(5) LCGP_CALIB_CASE(6) LCGP_CALIB_CASE(7) LCGP_CALIB_CASE(8)
+#undef LCGP_CALIB_CASE
+        default: break;
+    }
+    hipLaunchKernelGGL(calib_rows_wave_kernel, dim3(n0), dim3(64), 2 * (size_t)q * q * sizeof(double), st, q, d, n0, ghat, gvar,
+                       dghat, dgvar, ld, M, b, c0, lognorm, inv_range, ll, dll, sens);
+    CHECK_LAUNCH("calib_rows_wave");
+    return 0;
 }
 
 }  // extern "C"

@@ -1039,3 +1039,28 @@ def matern32_device(x1, x2, ell, scale, nug, same, dtype="float64", kernel="mate
                                  ell.ctypes.data_as(C.POINTER(C.c_double)), float(scale), float(nug), int(bool(same)),
                                  C.c_void_p(out.data_ptr())), "lcgp_covmat")
     return out.cpu().numpy().astype(np.float64)
+
+
+def calib_rows_device(blk, jac, M, b, c0, lognorm, inv_range=None, want_sens=False):
+    """lcgp_calib_rows on the device that holds `blk`: blk (2, q, n0) float64 DEVICE tensor [ghat; gvar] of ALL q components (a
+    block of predict_block / predict_grad_block, read in place), jac (2, q, n0, d) = [dghat; dgvar] or None (no gradient),
+    M (q, q), b (q,) and inv_range (d,) float64 tensors on the same device.  Returns device tensors (ll (n0,), dll (n0, d) or
+    None, sens (2, q, n0) or None).  One launch; there is no torch formulation behind it."""
+    import torch
+    _hip.require_gpu()
+    lib = _hip.load()
+    dev = blk.device
+    assert blk.dtype == torch.float64 and blk.is_contiguous() and blk.dim() == 3 and blk.shape[0] == 2
+    _, q, n0 = blk.shape
+    d = 1 if jac is None else int(jac.shape[3])
+    assert jac is None or (jac.dtype == torch.float64 and jac.is_contiguous() and tuple(jac.shape) == (2, q, n0, d))
+    assert M.is_contiguous() and tuple(M.shape) == (q, q) and tuple(b.shape) == (q,)
+    p = lambda t: C.c_void_p(0 if t is None else t.data_ptr())   # noqa: E731
+    with torch.cuda.device(dev):
+        ll = torch.empty(n0, dtype=torch.float64, device=dev)
+        dll = None if jac is None else torch.empty((n0, d), dtype=torch.float64, device=dev)
+        sens = torch.empty((2, q, n0), dtype=torch.float64, device=dev) if want_sens else None
+        _hip.check(lib.lcgp_calib_rows(C.c_void_p(torch.cuda.current_stream(dev).cuda_stream), q, d, n0, p(blk[0]), p(blk[1]),
+                                       p(None if jac is None else jac[0]), p(None if jac is None else jac[1]), n0, p(M), p(b),
+                                       float(c0), float(lognorm), p(inv_range), p(ll), p(dll), p(sens)), "lcgp_calib_rows")
+    return ll, dll, sens

@@ -370,6 +370,86 @@ class ConditionedLCGP:
             rows=lambda: eng.condition_select_rows(), condition=lambda j: eng.condition_select_condition(j))
 
 
+class _CalibFn(torch.autograd.Function):
+    """CalibrationTarget.loglik_differentiable: forward = loglik_grad()'s log likelihood, backward = the per-row product with
+    the saved gradient"""
+
+    @staticmethod
+    def forward(ctx, theta, target):
+        ll, dll = target.loglik_grad(theta.detach().cpu().to(torch.float64))
+        ctx.meta = (theta.dtype, theta.device, theta.shape)
+        ctx.dll = dll
+        return ll.to(theta.device)
+
+    @staticmethod
+    def backward(ctx, g):
+        if torch.is_grad_enabled():         # create_graph=True: the saved gradient is a constant, not a graph
+            raise RuntimeError('CalibrationTarget.loglik_differentiable supports first derivatives only: double backward '
+                               '(create_graph=True) is not available; use loglik_grad() for the gradient')
+        dt, dev, shape = ctx.meta
+        gx = _cpu64(g)[:, None] * ctx.dll
+        return gx.reshape(shape).to(device=dev, dtype=dt), None
+
+
+class CalibrationTarget:
+    """What LCGP.calibration() returns: the log likelihood of ONE field observation y_obs of the p outputs as a function of the
+    inputs theta, under the fitted emulator `model` at its current parameters,
+        log p(y_obs | theta) = log N(y_obs; ypred(theta), Phi_s diag(gvar(theta)) Phi_s^T + noise + Sigma_obs),
+    over the observed outputs.  Read-only: it holds the q x q matrix M, the q-vector b and two scalars into
+    which everything output-sized was folded once, and a reference to the model, whose factorisation it reads.  It goes stale
+    when the model's parameters change: every method then raises RuntimeError.  Nugget convention: predict_grad()'s (the
+    continuous prediction surface, same = 0, training inputs included)."""
+
+    def __init__(self, model, observed, M, b, c0, lognorm):
+        self.model, self.observed = model, observed
+        self.M, self.b, self.c0, self.lognorm = M, b, float(c0), float(lognorm)
+        self._u = model._get_flat().copy()
+        self._consts = {}               # device -> (M, b, 1 / input range) as tensors there
+
+    def __repr__(self):
+        return "CalibrationTarget(observed=%d of p=%d, q=%d)" % (int(self.observed.sum()), int(self.model.p), int(self.model.q))
+
+    def _require_current(self):
+        if not np.array_equal(self._u, self.model._get_flat()):
+            raise RuntimeError('this CalibrationTarget is stale: the parameters of its model changed (or the model was refit) '
+                               'after calibration(); call calibration() again')
+
+    def _device_consts(self, dev):
+        hit = self._consts.get(dev)
+        if hit is None:
+            m = self.model
+            inv_range = 1.0 / (_np(m.x_max) - _np(m.x_min)).reshape(-1)
+            hit = self._consts[dev] = tuple(torch.as_tensor(np.ascontiguousarray(a, F64)).to(dev)
+                                            for a in (self.M, self.b, inv_range))
+        return hit
+
+    def _rows(self, theta, grad, want_sens=False):
+        m = self.model
+        x0s = m._x0_2d(theta, 'theta')
+        self._require_current()
+        blk, jac = m._calib_latent(x0s, grad)
+        return m._calib_rows_device(blk, jac, *self._device_consts(blk.device), self.c0, self.lognorm, want_sens)
+
+    def loglik(self, theta):
+        """(n0,) CPU float64: log p(y_obs | theta[i]) for the rows of theta (n0, d) on the raw input scale"""
+        return _t(self._rows(theta, False)[0])
+
+    def loglik_grad(self, theta, latent=False):
+        """(ll (n0,), dll (n0, d)), CPU float64: dll[i, l] = d ll[i] / d theta[i, l] on the raw input scale; ll is bitwise
+        loglik(theta).  latent=True: additionally s, v (q, n0), the sensitivities d ll / d ghat and d ll / d gvar."""
+        ll, dll, sens = self._rows(theta, True, latent)
+        if latent:
+            return _t(ll), _t(dll), _t(sens[0]), _t(sens[1])
+        return _t(ll), _t(dll)
+
+    def loglik_differentiable(self, theta):
+        """(n0,) float64 on theta's device, differentiable with respect to a requires_grad theta (any device) through
+        torch.autograd to first order: the backward pass multiplies with the gradient of loglik_grad() saved by the forward pass.
+        A double backward (create_graph=True) raises."""
+        theta = theta if isinstance(theta, torch.Tensor) else torch.as_tensor(np.asarray(theta, F64))
+        return _CalibFn.apply(theta, self)
+
+
 class LCGP:
     """
     Latent Component Gaussian Process (LCGP), MI355X hot path.
@@ -1882,6 +1962,99 @@ class LCGP:
             raise ValueError('predict_differentiable: order must be 1 or 2, got %r' % (order,))
         x0 = x0 if isinstance(x0, torch.Tensor) else torch.as_tensor(np.asarray(x0, F64))
         return (_PredictFn if order == 1 else _PredictFn2).apply(x0, self)
+
+    # =============================================================================================
+    # calibration: the log likelihood of a field observation as a function of the inputs (beyond the reference)
+    # =============================================================================================
+    def calibration(self, y_obs, obs_var, include_noise=True):
+        """A CalibrationTarget for one field observation: y_obs (p,) on the raw output scale, NaN marking an output that was not
+        observed (at least one must be; fewer than q is fine), and obs_var, the observation (plus discrepancy) covariance on
+        the raw output scale as a scalar, (p,) variances or a symmetric (p, p) matrix; rows and columns of unobserved outputs
+        are ignored.  include_noise=True adds the fitted noise variance, as ypredvar does.  The target's loglik(theta) is
+            log N(y_obs; ypred(theta), Phi_s diag(gvar(theta)) Phi_s^T + noise + Sigma_obs)
+        restricted to the observed outputs, exactly (no diagonal approximation of the emulator's covariance), on the full and
+        rep paths; loglik_grad(theta) adds its gradient in theta.  Everything p-sized is folded here, once, into a q x q
+        matrix and a q-vector (host float64; a diagonal obs_var never forms a p x p matrix); per row of theta the GPU then
+        factorises a q x q matrix on top of lcgp_predict_grad's outputs (lcgp_calib_rows).
+        Raises ValueError for wrong shapes, non-finite observed values, negative variances and an asymmetric (p, p) obs_var,
+        numpy.linalg.LinAlgError when noise + Sigma_obs over the observed outputs is not positive definite."""
+        p = int(self.p)
+        y = _np(y_obs)
+        if y.shape != (p,):
+            raise ValueError('y_obs must have shape (%d,), got %s' % (p, tuple(y.shape)))
+        obs = ~np.isnan(y)
+        if not obs.any():
+            raise ValueError('y_obs holds no observed output (all NaN)')
+        if not np.all(np.isfinite(y[obs])):
+            raise ValueError('the observed entries of y_obs must be finite')
+        ov = _np(obs_var)
+        if ov.ndim == 0:
+            ov = np.full(p, float(ov), F64)
+        if ov.shape not in ((p,), (p, p)):
+            raise ValueError('obs_var must be a scalar, (%d,) variances or a (%d, %d) covariance, got shape %s'
+                             % (p, p, p, tuple(ov.shape)))
+        W, noise, scale, offset = self._output_map()
+        phi_s = (W[:, obs] * scale[obs][None, :]).T                          # (|O|, q)
+        t = (y - offset)[obs]
+        lam = (scale ** 2 * noise)[obs] if include_noise else np.zeros(int(obs.sum()), F64)
+        if ov.ndim == 1:
+            var = ov[obs]
+            if not np.all(np.isfinite(var)) or np.any(var < 0):
+                raise ValueError('obs_var must be finite and non-negative on the observed outputs')
+            lam = lam + var
+            if not np.all(lam > 0):
+                raise np.linalg.LinAlgError('noise + obs_var is not positive on every observed output')
+            M = phi_s.T @ (phi_s / lam[:, None])
+            b = phi_s.T @ (t / lam)
+            c0 = float(t @ (t / lam))
+            logdet = float(np.sum(np.log(lam)))
+        else:
+            S = ov[np.ix_(obs, obs)]
+            if not np.all(np.isfinite(S)) or np.any(np.diag(S) < 0):
+                raise ValueError('obs_var must be finite with a non-negative diagonal on the observed outputs')
+            if np.max(np.abs(S - S.T)) > 1e-12 * max(np.max(np.abs(S)), np.finfo(F64).tiny):
+                raise ValueError('a (p, p) obs_var must be symmetric')
+            low = np.linalg.cholesky(0.5 * (S + S.T) + np.diag(lam))         # LinAlgError when not positive definite
+            import scipy.linalg as sla
+            A = sla.solve_triangular(low, phi_s, lower=True)
+            z = sla.solve_triangular(low, t, lower=True)
+            M, b, c0 = A.T @ A, A.T @ z, float(z @ z)
+            logdet = 2.0 * float(np.sum(np.log(np.diag(low))))
+        lognorm = logdet + int(obs.sum()) * float(np.log(2.0 * np.pi))
+        return CalibrationTarget(self, obs, 0.5 * (M + M.T), b, c0, lognorm)
+
+    def _calib_latent(self, x0s, grad):
+        """(blk (2, q, n0), jac (2, q, n0, d) or None): [ghat; gvar] and [dghat; dgvar] of ALL q components at the standardised
+        inputs x0s, float64 tensors where the row kernel runs.  One rank: the engine's blocks, read in place.  Several ranks:
+        the zero-padded blocks are summed over the ranks (disjoint components: exact) and copied back to every rank's device."""
+        eng = self._ensure_aux()
+        if not _dist.use_collectives(self._group):
+            return eng.predict_grad_block(x0s) if grad else (eng.predict_block(x0s, False), None)
+        n0, d = x0s.shape
+        q = int(self.q)
+        loc = None
+        if eng is not None and grad:
+            blk, jac = eng.predict_grad_block(x0s)
+            loc = torch.cat([blk.permute(1, 0, 2).reshape(blk.shape[1], -1),
+                             jac.permute(1, 0, 2, 3).reshape(jac.shape[1], -1)], dim=1)
+        elif eng is not None:
+            loc = eng.predict_block(x0s, False).permute(1, 0, 2).reshape(-1, 2 * n0)
+        both = self._gather_components(loc, (2 * n0 + (2 * n0 * d if grad else 0),))
+        if eng is not None:
+            dev = eng.device
+        else:
+            dev = torch.device(self._device) if self._device is not None else torch.device('cuda', torch.cuda.current_device())
+        both = torch.as_tensor(np.ascontiguousarray(both, F64)).to(dev)
+        blk = both[:, :2 * n0].reshape(q, 2, n0).permute(1, 0, 2).contiguous()
+        jac = both[:, 2 * n0:].reshape(q, 2, n0, d).permute(1, 0, 2, 3).contiguous() if grad else None
+        return blk, jac
+
+    def _calib_rows_device(self, blk, jac, M, b, inv_range, c0, lognorm, want_sens):
+        """the one call into the row kernel (lcgp_calib_rows; there is no other implementation in the package): device
+        tensors in, numpy (ll (n0,), dll (n0, d) or None, sens (2, q, n0) or None) out"""
+        from .engine import calib_rows_device
+        out = calib_rows_device(blk, jac, M, b, c0, lognorm, inv_range, want_sens)
+        return tuple(None if t is None else t.cpu().numpy() for t in out)
 
     # =============================================================================================
     # input Hessians of the prediction (the reference: two nested tf.GradientTapes around predict)

@@ -97,6 +97,14 @@ def combine(*checks) -> Check:
 # ----------------------------------------------------------------------------------------------------------------------
 # covariance pieces in float64
 # ----------------------------------------------------------------------------------------------------------------------
+KERNEL_NAMES = ("matern32", "se", "matern52")
+
+
+def _known(kernel):
+    if kernel not in KERNEL_NAMES:
+        raise ValueError("unknown covariance kernel %r (one of %s)" % (kernel, ", ".join(KERNEL_NAMES)))
+
+
 def kernel_parts(x1, x2, ell, kernel, dtype, device=None):
     """C0 (n1 x n2) of the latent kernel in float64 from the ROUNDED inputs, the error magnification E of its evaluation in
     the storage type, the mask of the entries past the library's C0 cut-off, and the lengthscale derivative factors
@@ -110,7 +118,20 @@ def kernel_parts(x1, x2, ell, kernel, dtype, device=None):
           E = sum_l (|x1_l| + |x2_l|) / ell_l + (d + 1) sum_l S_l + d + 3
       SE: d ln C0 / d S_l = -S_l:
           E = sum_l S_l ((|x1_l| + |x2_l|) / ell_l + S_l) + (d + 1) 1/2 sum_l S_l^2 + 3
+      Matern52: C0 = prod_l f(S_l) exp(-sum_l S_l), f(S) = 1 + S + S^2 / 3; d ln C0 / d S_l = -S_l (1 + S_l) / (3 f(S_l)),
+      |.| = w(S_l) < 1, so the input and the exponent terms are those of Matern32 and the cut-off is the same (the exponent
+      is sum S).  The polynomial: per dimension build_kernel does m52_fm1 = fma(sd * (1/3), sd, sd), then poly = fma(poly,
+      fm1, poly).  Recounted from the code that is FOUR sources of error per dimension, not three: the constant 1/3 rounded
+      to the storage type (u / 2 in both types), the product sd * (1/3), the inner fma, the outer fma.  The first two act on
+      a = S^2 / 3 alone, the third on f - 1 = a + S, the fourth on the running product: relative to f they weigh
+      1 + (2.5 a + S) / f(S) -- below 3 for S <= 7.5, and below 3.5 always.  The half beyond 3 is covered by the input term:
+      it is counted with weight 1 where its true weight is w(S_l), and (1 - w(S)) 2 S = 2 S (3 + 2 S) / (3 f(S)) >= 3.3
+      from S = 7.5 on (m_l >= S_l).  So three per dimension stand, where Matern32 has one:
+          E = sum_l (|x1_l| + |x2_l|) / ell_l + (d + 1) sum_l S_l + 3 d + 3
+      (cross_kernel, pgrad_kernel and the others evaluate the same two fmas per dimension in double.)
+    Any other kernel name is a ValueError: no branch stands for "some Matern".
     """
+    _known(kernel)
     dev = device if device is not None else _dev(x1, x2)
     a = _t(x1, dev)
     b = _t(x2, dev)
@@ -127,22 +148,33 @@ def kernel_parts(x1, x2, ell, kernel, dtype, device=None):
         if kernel == "se":
             ssum += 0.5 * s * s
             mag += s * (m + s)
-        else:
+        elif kernel == "matern32":
             ssum += s
             poly *= 1.0 + s
+            mag += m
+        elif kernel == "matern52":
+            ssum += s
+            poly *= 1.0 + s + s * s / 3.0
             mag += m
     if kernel == "se":
         c0 = torch.exp(-ssum)
         e = mag + (d + 1) * ssum + 3.0
-    else:
+    elif kernel == "matern32":
         c0 = poly * torch.exp(-ssum)
         e = mag + (d + 1) * ssum + d + 3.0
+    elif kernel == "matern52":
+        c0 = poly * torch.exp(-ssum)
+        e = mag + (d + 1) * ssum + 3.0 * d + 3.0
     cut = ssum > -EXP_FLOOR[dname(dtype)]
     return c0, e, cut
 
 
 def dC0(x1, x2, ell, kernel, device=None):
-    """ell_l d C0 / d ell_l for every l (Matern32: C0 S_l^2 / (1 + S_l); SE: C0 S_l^2), float64"""
+    """ell_l d C0 / d ell_l for every l (Matern32: C0 S_l^2 / (1 + S_l); SE: C0 S_l^2; Matern52: C0 S_l^2 (1 + S_l) /
+    (3 f(S_l)), f(S) = 1 + S + S^2 / 3), float64.  This is the reference's own form: a product, a sum and a quotient on top
+    of C0 in every kernel.  The library never divides in its narrow kernels: for Matern52 it forms m52_wl(S_l) = (S_l S_l)
+    fma(S_l, 1/3, 1/3) (three roundings) times the product of the other dimensions' f (check_outputs counts them)."""
+    _known(kernel)
     dev = device if device is not None else _dev(x1, x2)
     a, b = _t(x1, dev), _t(x2, dev)
     ell = np.asarray(ell, np.float64)
@@ -150,7 +182,12 @@ def dC0(x1, x2, ell, kernel, device=None):
     out = []
     for l in range(a.shape[1]):
         s = (a[:, l][:, None] / ell[l] - b[:, l][None, :] / ell[l]).abs()
-        out.append(c0 * s * s / (1.0 + s) if kernel != "se" else c0 * s * s)
+        if kernel == "se":
+            out.append(c0 * s * s)
+        elif kernel == "matern32":
+            out.append(c0 * s * s / (1.0 + s))
+        elif kernel == "matern52":
+            out.append(c0 * s * s * (1.0 + s) / (3.0 + 3.0 * s + s * s))
     return out
 
 
@@ -378,7 +415,13 @@ def check_outputs(out_row, x, Y, sr, th, V, b, z, kernel, dtype) -> Check:
     (n + d + E_ij) u relative to |G|-with-absolute-values Ga = ss o (|D|/2 |V| + |z| |z|^T / 2) times |dC| (n: the
     reduction over the tiles, d: the dimensions, E: the kernel evaluation).  The d dimensions cover both forms of
     C0 S_l^2 / (1 + S_l): grad_kernel's prefix / suffix products (d - 1 products) and grad_kernel_wide's prod / (1 + S_l)
-    (d products, the sum 1 + S_l and the quotient: d + 2 roundings, within d + E since E >= d + 3).  quad and gsig:
+    (d products, the sum 1 + S_l and the quotient: d + 2 roundings, within d + E since E >= d + 3).  Matern52, C0 S_l^2
+    (1 + S_l) / (3 f(S_l)) = exp(-sum S) m52_wl(S_l) prod_{i != l} f(S_i): m52_wl = (S S) fma(S, 1/3, 1/3) costs three
+    roundings (the square, the fma, the product; the two constants 1/3 half a rounding each); every factor f(S_i) of a
+    prefix / suffix product costs three (kernel_parts), so grad_kernel's pre_l suf has 3 (d - 1) and one more for the product
+    of the two, and the products with ge and into the accumulator two: 3 d + 3 together, within d + E since E >= 3 d + 3.
+    grad_kernel_wide (d > 32 only) has the whole product (3 d), m52_fm1 again (three), the sum 1 + fm1, the quotient, m52_wl
+    (three) and the same two products: 3 d + 10, within d + E from d = 7 on, i.e. wherever that kernel runs.  quad and gsig:
     C n u (|b|^T (|b| + |z|)) in float64 storage; in float32 storage the library evaluates D b^T (C o ss) z and D Y (C o ss) z (finalize_kernel /
     gsig_c_kernel, the forms without the cancellation of b - z), bounded the same way as the gradients."""
     d, p = np.asarray(x).shape[1], np.asarray(Y).shape[0]
@@ -558,12 +601,23 @@ def check_pgrad_v(V, U, W, dtype) -> Check:
     return worst((_t(V, dev)[:, :n] - ref).abs(), bound, lower=False)
 
 
+def pgrad_h(s, kernel):
+    """h_l of check_pgrad from the signed scaled distance s (a float64 tensor): dC0 / dx0_l = -C0 h_l / ell_l"""
+    _known(kernel)
+    if kernel == "se":
+        return s
+    if kernel == "matern32":
+        return s / (1.0 + s.abs())
+    return s * (1.0 + s.abs()) / (3.0 + 3.0 * s.abs() + s * s)
+
+
 def check_pgrad(dghat, dgvar, x0, x, sr, th, z, V, kernel, dtype) -> Check:
     """dghat / dgvar (n0 x d) of lcgp_predict_grad against the contraction of include/lcgp_hip.h, in float64 from the rounded
     x0, x, sr and the library's own z (fetched) and V = U W (check_pgrad_v's stage):
         dghat[i, l] = -1/ell_l      sum_j c0_ij sr_j z_j    h_l(i, j)
         dgvar[i, l] =  2 D / ell_l  sum_j c0_ij sr_j V_ij   h_l(i, j)
-        h_l = s / (1 + |s|) (Matern-3/2), s (SE),   s = x0_il / ell_l - x_jl / ell_l,   c0 = scale (1 - nt) C0.
+        h_l = s / (1 + |s|) (Matern-3/2), s (SE), s (1 + |s|) / (3 + 3 |s| + s^2) (Matern-5/2),
+        s = x0_il / ell_l - x_jl / ell_l,   c0 = scale (1 - nt) C0             (h is defined by dC0/dx0_l = -C0 h_l / ell_l).
     Precision.  pgrad_kernel converts the stored x0, x, sr, z and V to double and does everything else in double, in both
     storage types: u is the FLOAT64 unit roundoff for every factor below; the only storage-type roundings are those of the
     inputs, which the reference shares (and of V and z, which it takes from the library).
@@ -571,12 +625,18 @@ def check_pgrad(dghat, dgvar, x0, x, sr, th, z, V, kernel, dtype) -> Check:
     cut-off as in check_predict) plus the products by c_off, sr and z or V (three roundings).  s carries u (|x0_il| + |x_jl|)
     / ell_l + u |s| (the two quotients and the difference); d h / d s = 1 / (1 + |s|)^2 <= 1 and h = s fast_rcp(1 + |s|)
     (v_rcp_f64 with two Newton steps: within 2 u of 1 / (1 + |s|)) adds four roundings: |dh| <= u (m_l + 5 |h|),
-    m_l = (|x0_il| + |x_jl|) / ell_l.  The sum over j (fma per slice, then the fixed-order slice reduction) adds n roundings
+    m_l = (|x0_il| + |x_jl|) / ell_l.  Matern-5/2: h = fma(s, |s|, s) fast_rcp(fma(|s|, |s| + 3, 3)) -- two fmas, the add
+    |s| + 3, fast_rcp within 2 u and the product: six roundings; d h / d s = (3 + 6 |s| + 2 s^2) / (3 + 3 |s| + s^2)^2 <= 1/3
+    and |s| d h / d s <= |h|, so |dh| <= u (m_l / 3 + 7 |h|).  That is two roundings of |h| more than Matern-3/2 and a third
+    of its m_l: with c0's E + 3, the n of the sum and the two of the scaling the library's count is (n + E + 12) |h| + m_l / 3,
+    and twice that (the reference) sits within C = 4 times the existing (n + d + E + 4) |h| + m_l, since E >= 3 d + 3 >= 6.
+    The sum over j (fma per slice, then the fixed-order slice reduction) adds n roundings
     of the absolute terms, the scaling by -1/ell_l or 2 D / ell_l two more.  Together, with C = 4 on top:
         C u / ell_l sum_j |c0_ij sr_j z_j| ((n + d + E_ij + 4) |h_l| + m_l)          (|V_ij| and 2 |D| for dgvar)
     plus the float64 floor.  m_l is not relative to |h_l|: x0 close to x_j (but not equal) leaves an absolute error of s.
     At dx = 0 (a training input among x0) both sides have s = 0 exactly, so h = 0.  Past the C0 cut-off the term itself is
     added (the library may return any c0 in [0, C0] there)."""
+    _known(kernel)
     dev = _dev(dghat, dgvar, z, V)
     u = unit("float64")
     a = _t(rounded(x0, dtype), dev)
@@ -596,7 +656,7 @@ def check_pgrad(dghat, dgvar, x0, x, sr, th, z, V, kernel, dtype) -> Check:
     for l in range(d):
         xa, xb = a[:, l] / ell[l], b[:, l] / ell[l]
         sl = xa[:, None] - xb[None, :]
-        h = sl / (1.0 + sl.abs()) if kernel != "se" else sl
+        h = pgrad_h(sl, kernel)
         t = wgt * h.abs() + (xa.abs()[:, None] + xb.abs()[None, :])
         gref[:, l] = -(pz * h).sum(dim=1) / ell[l]
         gbnd[:, l] = (C * u * (pz.abs() * t).sum(dim=1) + (cm * (pz * h).abs()).sum(dim=1)) / ell[l]

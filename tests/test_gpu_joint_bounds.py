@@ -46,7 +46,7 @@ def _report():
     print("\nworst ratio |error| / bound per case group, dtype and stage of the joint path (<= 1 passes)")
     for key in sorted(WORST):
         c = WORST[key]
-        print("  %-12s %-8s %-11s %.3e  at %s" % (key + (c.ratio, c.where)))
+        print("  %-15s %-8s %-11s %.3e  at %s" % (key + (c.ratio, c.where)))
 
 
 def _record(group, dtype, stage, c, where_extra=None):
@@ -200,6 +200,17 @@ def test_se_kernel_and_replicated_path(dtype):
     _joint_case("se", eng, x, sr, th, "se", dtype, _x0(905, 257, 3), 129)
     eng, x, sr, th = _engine(906, 500, 3, 3, dtype, rep=True)
     _joint_case("rep", eng, x, sr, th, "matern32", dtype, _x0(907, 257, 3), 129)
+
+
+@pytest.mark.parametrize("dtype", ["float64", "float32"])
+def test_matern52_kernel(dtype):
+    """Matern-5/2: one pass of the `boundary` case list (n = 129, every n0 of BOUNDARY_N0) and one of `training_x0` (n = 257,
+    same = 1), q_local = 3; cross, u, sigma, cov_factor and draws of every component"""
+    eng, x, sr, th = _engine(915, 129, 3, 3, dtype, kernel="matern52")
+    for i, n0 in enumerate(BOUNDARY_N0):
+        _joint_case("boundary_m52", eng, x, sr, th, "matern52", dtype, _x0(920 + i, n0, 3), 5, seed=i)
+    eng, x, sr, th = _engine(916, 257, 3, 3, dtype, kernel="matern52")
+    _joint_case("training_x0_m52", eng, x, sr, th, "matern52", dtype, x, 130, same=1)
 
 
 @pytest.mark.parametrize("dtype", ["float64", "float32"])

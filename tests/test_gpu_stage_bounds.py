@@ -12,18 +12,24 @@ runs on its own -- resets before anything reads it.)
 
 Coverage of the input dimension.  build_kernel<T, DD, KERN> and grad_kernel<T, DD, KERN> are compiled per for_dim bucket
 DD = 2, 4, 6, 10, 16, 32; d > 32 runs build_kernel<T, 32, KERN> in chunks of 32 dimensions and grad_kernel_wide<T, KERN>.
-With T = double, float and KERN = Matern-3/2, SE that is 24 narrow (DD, KERN, T) instantiations and 4 wide (KERN, T) ones.
-  - test_every_dimension_bucket reaches all 28, both kernels and both storage types, at d = 1, 2 (DD = 2), 3, 4 (DD = 4),
+With T = double, float and KERN = Matern-3/2, SE, Matern-5/2 that is 36 narrow (DD, KERN, T) instantiations and 6 wide
+(KERN, T) ones.
+  - test_every_dimension_bucket reaches all 42, the three kernels and both storage types, at d = 1, 2 (DD = 2), 3, 4 (DD = 4),
     5, 6 (DD = 6), 7, 9, 10 (DD = 10), 11, 15, 16 (DD = 16), 17, 31, 32 (DD = 32, one ragged or full chunk), and in the
     wide kernels at 2 chunks (d = 33, 63 ragged; 64 full), 3 (65 ragged; 96 full) and 4 (97, 126 ragged), n = 130.
   - test_wide_partials_over_many_tiles: 171 lower tiles of partials per component, q = 3: Matern-3/2 at DD = 16 (d = 16),
-    DD = 32 (17, 32) and wide at 2 and 4 chunks (33, 126); SE at DD = 32 (17) and wide at 4 chunks (126); both types.
-  - test_dimension_extremes: the wide kernels at 2 and 4 chunks (d = 33, 126), both kernels and types, with C0 past its
+    DD = 32 (17, 32) and wide at 2 and 4 chunks (33, 126); SE at DD = 32 (17) and wide at 4 chunks (126); Matern-5/2 at
+    DD = 10 (d = 10), 16 (16), 32 (17) and wide at 4 chunks (126); both types.
+  - test_dimension_extremes: the wide kernels at 2 and 4 chunks (d = 33, 126), the three kernels, both types, with C0 past its
     cut-off (collapsed lengthscales) and with S_j ~ 0 in every chunk (a third of the lengthscales at 1e3).
-  - test_replicated_path_dimensions: sr != 1 at DD = 6 (d = 5), DD = 32 (17) and wide at 4 chunks (126), both kernels
-    and types.
-  - test_tile_panel_and_pair_boundaries (Matern-3/2 at DD = 2, 4, 6, 10 and wide at 2 chunks) and
-    test_se_kernel_and_replicated_path (DD = 4) at the tile and panel edges of n.
+  - test_matern52_cutoff_in_the_narrow_buckets: grad_kernel skips an entry whose exponent is below exp_floor only where
+    DD > (KERN == 2 ? 8 : 16), so the buckets DD = 10 and 16 take that branch for Matern-5/2 alone: C0 around its cut-off
+    at d = 6 (DD = 6, no skip), 7, 10 (DD = 10) and 16 (DD = 16), and every lengthscale at 1e-6 at d = 6, 10, 16 (the
+    polynomial overflows float32, the exponential is zero: A is diagonal, the gradient finite).
+  - test_replicated_path_dimensions: sr != 1 at DD = 6 (d = 5), DD = 32 (17) and wide at 4 chunks (126), the three kernels,
+    both types.
+  - test_tile_panel_and_pair_boundaries (Matern-3/2 at DD = 2, 4, 6, 10 and wide at 2 chunks),
+    test_se_kernel_and_replicated_path and test_matern52_kernel (DD = 4) at the tile and panel edges of n.
 Predictions at the training inputs: test_predict_at_training_inputs calls lcgp_predict with x0 = x[lo : lo + m] and
 same = 1 + lo (lo at the 64-block and 128-pad edges and the last row; m = 1, 64, 65 and the whole set; n = 257 and 1025,
 full and rep paths) and the engine's predict_block(x, same=True) at PREDICT_CHUNK = 64 and 128, through
@@ -57,7 +63,7 @@ def _report():
     print("\nworst ratio |error| / bound per case group, dtype and stage (<= 1 passes)")
     for key in sorted(WORST):
         c = WORST[key]
-        print("  %-12s %-8s %-15s %.3e  at %s" % (key + (c.ratio, c.where)))
+        print("  %-13s %-8s %-15s %.3e  at %s" % (key + (c.ratio, c.where)))
 
 
 def _sched(**fields):
@@ -335,6 +341,12 @@ def test_se_kernel_and_replicated_path(dtype, n):
     _case("rep", dtype, n, 3, 4, 2, 600 + n, ({}, PLAIN), rep=True)
 
 
+@pytest.mark.parametrize("dtype", ["float64", "float32"])
+@pytest.mark.parametrize("n", [200, 1025])
+def test_matern52_kernel(dtype, n):
+    _case("m52", dtype, n, 3, 4, 2, 650 + n, ({}, PLAIN), kernel="matern52")
+
+
 def _config_problem(c, dtype, n=None):
     """configs[c - 1] of the benchmark (synth.make_config(c): its own data, q and standardisation) at the second parameter
     point of synth.param_points, optionally cut to its first n points: the model's engine and its theta rows"""
@@ -391,8 +403,8 @@ def test_cfg3_full_size_float32():
 # with one to four 32-dimension chunks, both kernels, both storage types
 # ----------------------------------------------------------------------------------------------------------------------
 BUCKET_DIMS = (1, 2, 3, 4, 5, 6, 7, 9, 10, 11, 15, 16, 17, 31, 32, 33, 63, 64, 65, 96, 97, 126)
-KERNELS = ("matern32", "se")
-GROUP = {"matern32": "m32", "se": "se"}
+KERNELS = ("matern32", "se", "matern52")
+GROUP = {"matern32": "m32", "se": "se", "matern52": "m52"}
 
 
 @pytest.mark.parametrize("kernel", KERNELS)
@@ -410,7 +422,8 @@ def test_wide_partials_over_many_tiles(dtype):
     """n = 1025 (npad = 1152: 171 lower tiles), q = 3: the per-tile gradient partials (stride DMAX + 2 narrow, d + 2 wide, a
     full 128-double slot at d = 126) of every component; a partial at the wrong stride or component offset lands in a
     neighbour's slot and fails that component's outputs check"""
-    cases = [("matern32", d) for d in (16, 17, 32, 33, 126)] + [("se", d) for d in (17, 126)]
+    cases = ([("matern32", d) for d in (16, 17, 32, 33, 126)] + [("se", d) for d in (17, 126)] +
+             [("matern52", d) for d in (10, 16, 17, 126)])
     for i, (kernel, d) in enumerate(cases):
         _case("tiles_" + GROUP[kernel], dtype, 1025, d, 3, 3, 800 + i, ({},), kernel=kernel)
 
@@ -420,7 +433,12 @@ def _cut_ell(d, dtype, kernel):
     box: E|dx| = 1/3, E dx^2 = 1/6): 75 - 93 % of the entries pass the cut-off (at d = 126 all of those only once a later
     32-dimension chunk is summed, at d = 33 5 - 8 % only with dimension 32), and the rest sit close to it"""
     f = 1.1 * abs(sb.EXP_FLOOR[dtype])
-    ell = d / (3.0 * f) if kernel == "matern32" else np.sqrt(d / (12.0 * f))
+    if kernel in ("matern32", "matern52"):          # the exponent is sum S in both
+        ell = d / (3.0 * f)
+    elif kernel == "se":
+        ell = np.sqrt(d / (12.0 * f))
+    else:
+        raise ValueError(kernel)
     c = float(np.log(ell / np.sqrt(d)))
     return (c - 0.15, c + 0.15)
 
@@ -434,7 +452,7 @@ def _ard(th, d):
 
 @pytest.mark.parametrize("dtype", ["float64", "float32"])
 def test_dimension_extremes(dtype):
-    """d = 33 and 126, n = 257, both kernels: (a) collapsed lengthscales, most C0 entries past the exp cut-off, at d = 126
+    """d = 33 and 126, n = 257, every kernel: (a) collapsed lengthscales, most C0 entries past the exp cut-off, at d = 126
     only across chunk boundaries (_cut_ell); (b) ARD-style lengthscales, a third of the dimensions at 1e3 and the rest short: the
     wide kernel's prod / (1 + S_j) at S_j ~ 0 and exponent sums spread over every chunk.  A stays well conditioned (C0
     small off the diagonal, the nugget on it)"""
@@ -447,8 +465,35 @@ def test_dimension_extremes(dtype):
 
 
 @pytest.mark.parametrize("dtype", ["float64", "float32"])
+def test_matern52_cutoff_in_the_narrow_buckets(dtype):
+    """grad_kernel<T, DD, 2> leaves an entry out (`continue`) when its exponent is below exp_floor only for DD > 8, where
+    Matern-3/2 and SE do so for DD > 16: DD = 10 and 16 have that branch for this kernel alone.  n = 257, q = 2.
+    (a) C0 around its cut-off (_cut_ell) at d = 6 (DD = 6: no skip), 7 and 10 (DD = 10) and 16 (DD = 16);
+    (b) every lengthscale at 1e-6 at d = 6, 10, 16 with D <= 2: S ~ 1e6 per dimension, f(S)^d overflows float32 (poly_cap and
+    fmin must hold it) while the exponential is zero, so the off-diagonal of A is zero exactly and A the nugget diagonal;
+    the output row is finite and within check_outputs (a NaN counts as inf there)."""
+    n, q, p = 257, 2, 3
+    for i, d in enumerate((6, 7, 10, 16)):
+        _case("cutoff_m52", dtype, n, d, p, q, 960 + i, ({},), kernel="matern52", ell=_cut_ell(d, dtype, "matern52"))
+    for i, d in enumerate((6, 10, 16)):
+        x, Y, sr, th = _problem(970 + i, n, d, p, q, D=(1.0, 2.0))
+        th[:, :d] = 1e-6
+        x0 = np.random.default_rng(980 + i).uniform(-0.1, 1.1, (37, d))
+        eng = HotPathEngine(x, Y, sr=sr, q_local=q, dtype=dtype, kernel="matern52")
+        eng.sched = _sched()
+        r = _poisoned(_run_nll, eng, th, [0, 1], x0)
+        out = r["out"].cpu().numpy()
+        assert np.all(np.isfinite(out)), (d, out)
+        for k in range(q):
+            A = r["A", k]
+            assert torch.all(torch.isfinite(A)), (d, k)
+            assert torch.count_nonzero(A - torch.diag(torch.diagonal(A))) == 0, (d, k)
+        _check_all("collapsed_m52", eng, x, Y, sr, th, "matern52", dtype, r, [0, 1], x0)
+
+
+@pytest.mark.parametrize("dtype", ["float64", "float32"])
 def test_replicated_path_dimensions(dtype):
-    """sr != 1 (replicates) at d = 5 (DD = 6), 17 (DD = 32) and 126 (four wide chunks), both kernels, n = 200"""
+    """sr != 1 (replicates) at d = 5 (DD = 6), 17 (DD = 32) and 126 (four wide chunks), every kernel, n = 200"""
     for i, d in enumerate((5, 17, 126)):
         for j, kernel in enumerate(KERNELS):
             _case("rep_" + GROUP[kernel], dtype, 200, d, 3, 2, 950 + 2 * i + j, ({}, PLAIN), kernel=kernel, rep=True)

@@ -11,7 +11,12 @@ upper triangle that was not zeroed, draws shifted at a chunk split and a float32
 At the input dimensions of the d-templated kernels (d = 17, 33, 126) the emulated path passes as well, and a last chunk
 staged with the lengthscales of the chunk before it, stale padding dimensions, one lengthscale gradient 1e-8 off in the
 fourth 32-dimension chunk (which the oracle's normwise bar passes) and swapped g_scale / g_nug accumulators each fail;
-predictions at training rows fail check_predict when the nugget term sits one column off or is missing."""
+predictions at training rows fail check_predict when the nugget term sits one column off or is missing.
+
+Matern-5/2.  The emulated paths build their matrices from sb.kernel_parts, so its Matern-5/2 branches are pinned without
+going through them: C0 against tests/matern52_oracle.py, dC0 and h against torch autograd of a C0 restated here, and the
+magnification E against an emulation of build_kernel's float32 operation order.  Three wrong-kernel defects (a far tile of
+A, one g_ell slot, dghat: each with the Matern-3/2 formula) fail their stage."""
 import numpy as np
 import pytest
 import torch
@@ -20,6 +25,7 @@ from tests import stage_bounds as sb
 
 N, D_IN, P = 300, 3, 4
 TS = sb.TS
+KERNELS = ["matern32", "se", "matern52"]
 
 
 def _problem(seed=0, ell=(0.3, 0.5, 0.8), n=N):
@@ -81,7 +87,7 @@ def prob2048():
     return _problem(1, n=2048)
 
 
-@pytest.mark.parametrize("kernel", ["matern32", "se"])
+@pytest.mark.parametrize("kernel", KERNELS)
 @pytest.mark.parametrize("dtype", ["float64", "float32"])
 def test_emulated_path_passes_every_stage(prob, dtype, kernel):
     x, Y, th = prob
@@ -260,6 +266,13 @@ def test_emulated_joint_path_se_kernel():
             assert ch.ratio < 0.5, (k, stage, ch)
 
 
+def test_emulated_joint_path_matern52_kernel():
+    x, x0, jit, comps = _emulate_joint("float64", "matern52")
+    for k, c in enumerate(comps):
+        for stage, ch in _joint_checks(c, x, x0, jit, "float64", "matern52").items():
+            assert ch.ratio < 0.5, (k, stage, ch)
+
+
 def test_cov_cross_honours_the_nugget_of_the_training_set():
     """x0 = the training rows 10 .. 109 (same = 11): the nugget term belongs on the shifted diagonal and nowhere else"""
     x, _, _ = _problem()
@@ -426,9 +439,23 @@ def _cross(x0, x, sr, th, dtype, kernel="matern32", match=None):
     return X
 
 
-def _pgrad(x0, x, sr, th, z, V, dtype, kernel="matern32", rcp=None, chunk_l0=None, drop=None):
+def _h(sl, kernel, rcp=None):
+    """h of the input gradient, every kernel spelled out (numpy; rcp: the reciprocal the library's fast_rcp stands for)"""
+    rcp = (lambda v: 1.0 / v) if rcp is None else rcp
+    a = np.abs(sl)
+    if kernel == "se":
+        return sl
+    if kernel == "matern32":
+        return sl * rcp(1.0 + a)
+    if kernel == "matern52":
+        return (sl * a + sl) * rcp(a * (a + 3.0) + 3.0)
+    raise ValueError(kernel)
+
+
+def _pgrad(x0, x, sr, th, z, V, dtype, kernel="matern32", rcp=None, chunk_l0=None, drop=None, h_kernel=None):
     """dghat, dgvar (n0 x d) of the contraction in float64; defects: rcp (the reciprocal in h), chunk_l0 (dimensions from
-    chunk_l0 on computed with the s of dimension l - chunk_l0), drop (training inputs left out of dgvar)"""
+    chunk_l0 on computed with the s of dimension l - chunk_l0), drop (training inputs left out of dgvar), h_kernel (dghat
+    formed with the h of another kernel)"""
     d = x.shape[1]
     ell, scale, nug, Dk, _ = sb.split_theta(th, d)
     s = np.ones(x.shape[0]) if sr is None else _r(sr, dtype)
@@ -443,8 +470,8 @@ def _pgrad(x0, x, sr, th, z, V, dtype, kernel="matern32", rcp=None, chunk_l0=Non
     for l in range(d):
         ls = l - chunk_l0 if (chunk_l0 is not None and l >= chunk_l0) else l
         sl = a[:, ls][:, None] / ell[ls] - b[:, ls][None, :] / ell[ls]
-        h = sl * (1.0 / (1.0 + np.abs(sl)) if rcp is None else rcp(1.0 + np.abs(sl))) if kernel != "se" else sl
-        gh[:, l] = -(pz * h).sum(axis=1) / ell[l]
+        h = _h(sl, kernel, rcp)
+        gh[:, l] = -(pz * (h if h_kernel is None else _h(sl, h_kernel, rcp))).sum(axis=1) / ell[l]
         gv[:, l] = 2 * Dk * (pv * h).sum(axis=1) / ell[l]
     return gh, gv
 
@@ -463,7 +490,7 @@ def _pgrad_problem(dtype, d=D_IN, n=N, n0=70, kernel="matern32", rep=False, seed
     return dict(x=x, sr=sr, th=th, x0=x0, U=U, Vp=Vp, gh=gh, gv=gv, **e)
 
 
-@pytest.mark.parametrize("kernel", ["matern32", "se"])
+@pytest.mark.parametrize("kernel", KERNELS)
 @pytest.mark.parametrize("dtype", ["float64", "float32"])
 def test_emulated_predict_grad_passes(dtype, kernel):
     for rep in (False, True):
@@ -706,8 +733,9 @@ def _check_vr(v, out, dtype, match="same", r=None):
 def test_emulated_vr_passes(vr):
     dtype, v = vr
     assert _check_vr(v, v["out"], dtype).ratio < 0.5
-    v2 = _vr_emulate(dtype, "se")
-    assert _check_vr(v2, v2["out"], dtype).ratio < 0.5
+    for kernel in ("se", "matern52"):
+        v2 = _vr_emulate(dtype, kernel)
+        assert _check_vr(v2, v2["out"], dtype).ratio < 0.5, kernel
 
 
 def test_vr_defect_1_last_reference_tile_left_out(vr64):
@@ -800,7 +828,7 @@ def _finalize(out, sums, th, d):
     return out
 
 
-@pytest.mark.parametrize("kernel", ["matern32", "se"])
+@pytest.mark.parametrize("kernel", KERNELS)
 @pytest.mark.parametrize("dtype", ["float64", "float32"])
 def test_emulated_path_passes_at_wide_dimensions(wide, dtype, kernel):
     for d in (17, 126):
@@ -815,7 +843,7 @@ def test_emulated_path_passes_at_wide_dimensions(wide, dtype, kernel):
         assert c.ratio < 0.5, (d, "predict", c)
 
 
-@pytest.mark.parametrize("kernel", ["matern32", "se"])
+@pytest.mark.parametrize("kernel", KERNELS)
 @pytest.mark.parametrize("dtype", ["float64", "float32"])
 def test_wide_defect_1_last_chunk_with_the_lengthscales_of_the_previous_one(wide, dtype, kernel):
     """d = 126: the dimensions 96 .. 125 of A staged with ell[64 .. 93] (d0 off by 32 in the last chunk)"""
@@ -830,7 +858,7 @@ def test_wide_defect_1_last_chunk_with_the_lengthscales_of_the_previous_one(wide
     assert c.ratio > 1, c
 
 
-@pytest.mark.parametrize("kernel", ["matern32", "se"])
+@pytest.mark.parametrize("kernel", KERNELS)
 @pytest.mark.parametrize("dtype", ["float64", "float32"])
 def test_wide_defect_2_stale_padding_dimensions(wide, dtype, kernel):
     """d = 33: the second chunk holds dimension 32 and 31 padding columns, which keep the first chunk's staged columns 1 ..
@@ -893,3 +921,206 @@ def test_predict_defect_nugget_one_row_off(dtype, rep):
     for same in (lo, lo + 2, 0):
         c = sb.check_predict(ghat, gvar, x0, x, sr, th, g["W"], g["z"], "matern32", dtype, same=same)
         assert c.ratio > 1, (same, c)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# Matern-5/2: pins of kernel_parts / dC0 / pgrad_h that do not go through them, the magnification E against build_kernel's
+# float32 operation order, and the wrong-kernel defects
+# ----------------------------------------------------------------------------------------------------------------------
+M52_DIMS = (1, 3, 17, 40)
+
+
+def _m52_points(d, seed):
+    """x1 (23 x d) and x2 (31 x d) in the unit box; rows 0 .. 4 of x1 coincide with rows 7 .. 11 of x2"""
+    rng = np.random.default_rng(seed)
+    x1, x2 = rng.uniform(0.0, 1.0, (23, d)), rng.uniform(0.0, 1.0, (31, d))
+    x1[:5] = x2[7:12]
+    ell = rng.uniform(0.3, 0.9, d) * np.sqrt(d)
+    return x1, x2, ell
+
+
+def _c0_m52_torch(a, b, logell):
+    """prod_l (1 + S_l + S_l^2 / 3) exp(-sum_l S_l) restated from the oracle's definition, differentiable in a and log ell"""
+    s = ((a[:, None, :] - b[None, :, :]) / torch.exp(logell)).abs()
+    return torch.prod(1.0 + s + s * s / 3.0, dim=2) * torch.exp(-s.sum(dim=2))
+
+
+def test_unknown_kernel_name_is_an_error():
+    x = np.zeros((2, 1))
+    for name in ("matern", "matern12", "rbf", None):
+        with pytest.raises(ValueError):
+            sb.kernel_parts(x, x, [1.0], name, "float64")
+        with pytest.raises(ValueError):
+            sb.dC0(x, x, [1.0], name)
+        with pytest.raises(ValueError):
+            sb.pgrad_h(torch.zeros(2, dtype=torch.float64), name)
+        with pytest.raises(ValueError):
+            sb.check_pgrad(np.zeros((2, 1)), np.zeros((2, 1)), x, x, None, [1.0, 1.0, 0.01, 1.0], np.zeros(2), np.zeros((2, 2)),
+                           name, "float64")
+
+
+@pytest.mark.parametrize("d", M52_DIMS)
+def test_matern52_c0_against_the_oracle(d):
+    """kernel_parts' Matern-5/2 C0 against tests/matern52_oracle.c0_matern52 (pinned by the identities of
+    tests/test_matern52_oracle.py), float64, 1e-14 relative: rectangular x1 != x2 with coincident rows, and x1 = x2"""
+    from tests import matern52_oracle as m52
+    x1, x2, ell = _m52_points(d, 60 + d)
+    for a, b in ((x1, x2), (x2, x2)):
+        c0, e, cut = sb.kernel_parts(a, b, ell, "matern52", "float64")
+        ref = m52.c0_matern52(a / ell, b / ell)
+        assert np.all(np.abs(c0.numpy() - ref) <= 1e-14 * np.abs(ref))
+        assert not bool(cut.any())
+    assert np.all(sb.kernel_parts(x1, x2, ell, "matern52", "float64")[0].numpy()[np.arange(5), np.arange(7, 12)] == 1.0)
+    assert np.all(np.diag(sb.kernel_parts(x2, x2, ell, "matern52", "float64")[0].numpy()) == 1.0)
+    # the restatement the autograd pins below differentiate is the same function
+    t = _c0_m52_torch(torch.as_tensor(x1), torch.as_tensor(x2), torch.as_tensor(np.log(ell))).numpy()
+    ref = m52.c0_matern52(x1 / ell, x2 / ell)
+    assert np.all(np.abs(t - ref) <= 1e-14 * np.abs(ref))
+
+
+@pytest.mark.parametrize("d", M52_DIMS)
+def test_matern52_dc0_and_h_against_autograd(d):
+    """dC0 = ell_l dC0 / d ell_l against autograd of C0 in log ell, and h, defined by dC0 / dx0_l = -C0 h_l / ell_l, against
+    autograd of C0 in x0: float64, 1e-10 of the largest entry per dimension"""
+    x1, x2, ell = _m52_points(d, 70 + d)
+    a, b = torch.as_tensor(x1), torch.as_tensor(x2)
+    le = torch.as_tensor(np.log(ell))
+    J = torch.autograd.functional.jacobian(lambda t: _c0_m52_torch(a, b, t), le)             # (n1, n2, d)
+    F = sb.dC0(x1, x2, ell, "matern52")
+    assert len(F) == d
+    for l in range(d):
+        ref = J[:, :, l]
+        assert float((F[l] - ref).abs().max()) <= 1e-10 * float(ref.abs().max()), l
+    c0 = sb.kernel_parts(x1, x2, ell, "matern52", "float64")[0]
+    Jx = torch.autograd.functional.jacobian(lambda t: _c0_m52_torch(t, b, le), a)            # (n1, n2, n1, d)
+    i = torch.arange(a.shape[0])
+    Jx = Jx[i, :, i, :]                                                                      # (n1, n2, d): row i by x0_i
+    for l in range(d):
+        sl = a[:, l][:, None] / ell[l] - b[:, l][None, :] / ell[l]
+        got = -c0 * sb.pgrad_h(sl, "matern52") / ell[l]
+        ref = Jx[:, :, l]
+        assert float((got - ref).abs().max()) <= 1e-10 * float(ref.abs().max()), l
+        assert float(sb.pgrad_h(sl, "matern52").abs().max()) < 1.0
+        assert bool(torch.all(sb.pgrad_h(sl, "matern52")[:5][i[:5], i[:5] + 7] == 0.0))      # coincident points: h = 0
+
+
+def _f32(v):
+    return np.asarray(v, np.float32)
+
+
+def _fma32(a, b, c):
+    """fma in float32: the product of two float32 is exact in float64 (48 bits), the sum is rounded to float64 and then to
+    float32 -- a single rounding but for the rare double-rounding ties"""
+    with np.errstate(over="ignore", invalid="ignore"):
+        return _f32(a.astype(np.float64) * b.astype(np.float64) + c.astype(np.float64))
+
+
+def _build_kernel_f32_matern52(x, th):
+    """A of build_kernel<float, DD, 2> (sr = 1), operation by operation in float32: x / ell formed in double and rounded;
+    per dimension sd = |xa - xb|, m52_fm1 = fma(sd * (1/3), sd, sd), poly = fma(poly, fm1, poly), ssum -= sd; then
+    c0 = min(poly, 1e38) exp(ssum) with __expf = exp2 of the float32 product with log2(e), v = (ss c_off) c0 and, on the
+    diagonal, v += 1 + (c_diag - 1) ss.  Written from lcgp_hip.hip, independent of stage_bounds."""
+    n, d = x.shape
+    ell, scale, nug, Dk = th[:d], th[d], th[d + 1], th[d + 2]
+    nt = nug / (1.0 + nug)
+    xs = _f32(_f32(x).astype(np.float64) / ell)
+    third = np.float32(1.0 / 3.0)
+    poly = np.ones((n, n), np.float32)
+    ssum = np.zeros((n, n), np.float32)
+    with np.errstate(over="ignore", invalid="ignore", under="ignore"):
+        for l in range(d):
+            sd = np.abs(xs[:, l][:, None] - xs[:, l][None, :])
+            fm1 = _fma32(sd * third, sd, sd)
+            poly = _fma32(poly, fm1, poly)
+            ssum = ssum - sd
+        arg = ssum * np.float32(1.4426950408889634)
+        ex = _f32(np.exp2(arg.astype(np.float64)))
+        c0 = np.fmin(poly, np.float32(1e38)) * ex
+        c_off, c_diag = np.float32(Dk * scale * (1.0 - nt)), np.float32(1.0 + Dk * scale * nt)
+        ss = np.float32(1.0) * np.float32(1.0)
+        v = (ss * c_off) * c0
+        v[np.diag_indices(n)] += np.float32(1.0) + (c_diag - np.float32(1.0)) * ss
+    assert v.dtype == np.float32
+    return v.astype(np.float64)
+
+
+@pytest.mark.parametrize("ells", ["collapsed", "long"])
+@pytest.mark.parametrize("d", [1, 6, 10, 33, 126])
+def test_matern52_magnification_against_build_kernel_order(d, ells):
+    """the constant 3 d + 3 of kernel_parts' Matern-5/2 E: an emulation of build_kernel's float32 operation order passes
+    check_build below 0.5.  collapsed: the mean exponent at 0.9 times the float32 cut-off (entries on both sides of it, S_l
+    up to ~ 250 / d per dimension); long: S_l ~ 0.03, the polynomial's roundings are all there is.  Past the cut-off
+    check_build's bound is |A_ij| itself (the exponential is a denormal or zero there, whatever the polynomial): the whole
+    matrix is held to ratio <= 1, and to < 0.5 with the entries past the cut-off taken from the reference, so that E alone
+    is what the 0.5 measures."""
+    rng = np.random.default_rng(80 + d)
+    n = 130
+    x = rng.uniform(0.0, 1.0, (n, d))
+    Y = rng.standard_normal((P, n))
+    if ells == "collapsed":
+        ell = d / (3.0 * 0.9 * abs(sb.EXP_FLOOR["float32"])) * np.exp(rng.uniform(-0.15, 0.15, d))
+    else:
+        ell = 10.0 * np.exp(rng.uniform(-0.15, 0.15, d))
+    th = _theta(d, 81 + d, ell=ell)
+    A = _build_kernel_f32_matern52(x, th)
+    assert np.all(np.isfinite(A))
+    cut = sb.kernel_parts(_r(x, "float32"), _r(x, "float32"), ell, "matern52", "float32")[2].numpy()
+    if ells == "collapsed":
+        assert 0.05 < cut.mean() < 0.95, cut.mean()
+        assert sb.check_build(A, None, x, Y, None, th, "matern52", "float32").ratio <= 1.0
+        A = np.where(cut, _r(sb.reference_A(x, None, th, "matern52", "float32")[0].numpy(), "float32"), A)
+    else:
+        assert not cut.any()
+    c = sb.check_build(A, None, x, Y, None, th, "matern52", "float32")
+    assert c.ratio < 0.5, c
+    # teeth: the same matrix with one far tile's polynomial evaluated as Matern-3/2 fails (long lengthscales: inside the cut)
+    if ells == "long":
+        bad = A.copy()
+        bad[_tile(1, 0)] = _r(sb.reference_A(x, None, th, "matern32", "float32")[0].numpy(), "float32")[_tile(1, 0)]
+        c = sb.check_build(bad, None, x, Y, None, th, "matern52", "float32")
+        assert c.ratio > 1 and c.where == (1, 0), c
+
+
+@pytest.mark.parametrize("dtype", ["float64", "float32"])
+def test_matern52_defect_1_far_tile_of_A_with_matern32_values(prob, dtype):
+    """the far-off-diagonal 64-tile (4, 0) of A holds the Matern-3/2 kernel"""
+    x, Y, th = prob
+    e = _emulate(x, Y, th, dtype, "matern52")
+    assert sb.check_build(e["A"], e["b"], x, Y, None, th, "matern52", dtype).ratio < 0.5
+    A = e["A"].copy()
+    A[_tile(4, 0)] = _emulate(x, Y, th, dtype, "matern32")["A"][_tile(4, 0)]
+    c = sb.check_build(A, e["b"], x, Y, None, th, "matern52", dtype)
+    assert c.ratio > 1 and c.where == (4, 0), c
+
+
+@pytest.mark.parametrize("dtype", ["float64", "float32"])
+def test_matern52_defect_2_one_lengthscale_slot_with_the_matern32_weight(wide, dtype):
+    """d = 126: g_ell_100 (fourth 32-dimension chunk) contracted with S^2 / (1 + S) in place of S^2 (1 + S) / (3 f(S))"""
+    d, l = 126, 100
+    x, Y, th = wide[d]
+    e = _emulate(x, Y, th, dtype, "matern52")
+    sums = _contraction(e, x, th, dtype, "matern52")
+    ok = _finalize(e["out"], sums, th, d)
+    assert sb.check_outputs(ok, x, Y, None, th, e["V"], e["b"], e["z"], "matern52", dtype).ratio < 0.5
+    ell, scale, nug, Dk, _ = sb.split_theta(th, d)
+    V, z = torch.as_tensor(e["V"]), torch.as_tensor(e["z"])
+    G = 0.5 * Dk * V - 0.5 * z[:, None] * z[None, :]
+    xr = torch.as_tensor(sb.rounded(x, dtype))
+    c0 = sb.kernel_parts(xr, xr, ell, "matern52", "float64")[0]
+    s = (xr[:, l][:, None] / ell[l] - xr[:, l][None, :] / ell[l]).abs()
+    bad = list(sums)
+    bad[l] = float((G * c0 * s * s / (1.0 + s)).sum())
+    c = sb.check_outputs(_finalize(e["out"], bad, th, d), x, Y, None, th, e["V"], e["b"], e["z"], "matern52", dtype)
+    assert c.ratio > 1 and c.where == ("g_ell%d" % l,), c
+
+
+@pytest.mark.parametrize("dtype", ["float64", "float32"])
+def test_matern52_defect_3_dghat_with_the_matern32_h(dtype):
+    """dghat formed with h = s / (1 + |s|); dgvar with the right one"""
+    g = _pgrad_problem(dtype, kernel="matern52", rep=True)
+    args = (g["x0"], g["x"], g["sr"], g["th"], g["z"], g["Vp"])
+    assert sb.check_pgrad(g["gh"], g["gv"], *args, "matern52", dtype).ratio < 0.5
+    gh, gv = _pgrad(*args, dtype, "matern52", h_kernel="matern32")
+    assert np.array_equal(gv, g["gv"])
+    c = sb.check_pgrad(gh, gv, *args, "matern52", dtype)
+    assert c.ratio > 1 and c.where[1].startswith("dghat"), c

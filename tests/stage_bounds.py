@@ -1,7 +1,8 @@
 """Stage-wise componentwise error bounds of the hot path (build, Cholesky, L^-1, A^-1, z, outputs, predict), of the
 joint path (cross covariance X, U = X W^T, Sigma + tau I, its factor, the draws) and of the post-fit queries (V = U W and
 the input gradients of lcgp_predict_grad, leave-one-out, the k-fold gather / factor / inverse / apply, the integrated
-variance reduction).
+variance reduction) and of the conditioned view (lcgp_condition_prepare / lcgp_condition_predict: S and its factor, the dense
+L_S^-1, v, Sigma_0n, T and the corrected outputs).
 
 Every check compares one stage of the library with a plain float64 reference computed from THE LIBRARY'S OWN INPUT TO THAT
 STAGE (the fetched A for the Cholesky, the fetched L for L^-1, ...), so no bound carries a condition number.  Entries are
@@ -279,9 +280,16 @@ def check_cholesky_inverse_solve(A, L, dtype) -> Check:
     dev = _dev(A, L)
     a = _t(A, dev)
     l = torch.tril(_t(L, dev))
-    n = a.shape[0]
-    u = unit(dtype)
     r = (a - l @ l.T).abs()
+    return worst(r, inverse_solve_bound(l, dtype))
+
+
+def inverse_solve_bound(l, dtype):
+    """the bound of check_cholesky_inverse_solve on |A - L L^T| (n x n float64 tensor) from the factor alone: l is the lower
+    triangle of the fetched factor, float64.  check_cond_s adds it to the bound of the matrix the factor is held to."""
+    dev = l.device
+    n = l.shape[0]
+    u = unit(dtype)
     idx = torch.arange(n, device=dev, dtype=torch.float64)
     k = torch.minimum(idx[:, None], idx[None, :]) + 2.0
     la = l.abs()
@@ -295,7 +303,7 @@ def check_cholesky_inverse_solve(A, L, dtype) -> Check:
         wcc = torch.linalg.solve_triangular(lcc, torch.eye(e - c, dtype=torch.float64, device=dev), upper=False)
         m = lcc.abs().T @ wcc.abs().T @ lcc.abs().T
         extra[e:, c:e] = C * TS * u * (la[e:, c:e] @ m)
-    return worst(r, bound + extra)
+    return bound + extra
 
 
 def check_half_logdet(L, half_logdet, dtype) -> Check:
@@ -529,6 +537,15 @@ def check_sigma(S, U, x0, th, jitter, kernel, dtype) -> Check:
     with C = 4:  C (npad + d + E) u (|C00| + |D| |U| |U|^T) + u |tau|, and |C00| itself past the C0 cut-off.  The bound
     starts from the library's U, so no condition number enters."""
     dev = _dev(S, U)
+    ell, scale, nug, D, _ = split_theta(th, np.asarray(x0).shape[1])
+    ref, bound = sigma_ref_bound(U, x0, th, jitter * scale, kernel, dtype, dev)
+    return worst((_t(S, dev) - ref).abs(), bound)
+
+
+def sigma_ref_bound(U, x0, th, tau, kernel, dtype, dev):
+    """(reference, bound) of check_sigma, float64 n0 x n0 tensors: C00 - D U U^T + diag(tau) from the library's own U and the
+    rounded x0.  tau: a float (check_sigma's jitter scale) or a vector of n0 diagonal terms (check_cond_s: 1 / (D r_i)), which
+    enter the bound as u |tau_i|."""
     d = np.asarray(x0).shape[1]
     u = unit(dtype)
     ell, scale, nug, D, _ = split_theta(th, d)
@@ -539,13 +556,14 @@ def check_sigma(S, U, x0, th, jitter, kernel, dtype) -> Check:
     uu = _t(U, dev)
     k = _pad128(uu.shape[1])
     eye = torch.eye(n0, dtype=torch.float64, device=dev)
-    tau = jitter * scale
+    if not isinstance(tau, float):
+        tau = _t(tau, dev)
     c00 = scale * ((1.0 - nt) * c0 + nt * eye)
     ref = c00 - D * (uu @ uu.T) + tau * eye
     ua = uu.abs()
     bound = C * (k + d + e) * u * (c00.abs() + abs(D) * (ua @ ua.T)) + u * abs(tau) * eye + floor(dtype, k)
     bound = bound + torch.where(cut, c00.abs(), torch.zeros_like(c00))
-    return worst((_t(S, dev) - ref).abs(), bound)
+    return ref, bound
 
 
 def check_draws(out, L, eps, ghat, dtype) -> Check:
@@ -816,3 +834,151 @@ def check_vr(out, x_ref, w, x_cand, match, r, x, sr, th, W, kernel, dtype) -> Ch
     lo = torch.clamp(den - dh, min=(1.0 - C * u64) / (D * r))
     bound = (num + ref.abs() * dh) / lo + C * (wt.shape[0] + 2.0) * u64 * (wt.abs()[:, None] * sig * sig).sum(dim=0) / den
     return worst((_t(out, dev) - ref).abs(), bound + floor("float64", wt.shape[0]))
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# the conditioned view (lcgp_condition_prepare / lcgp_condition_predict).  Per component, for m new unique inputs xn with
+# latent observations t and replicate counts r, and n0 new inputs x0:
+#     preparation   X_n, U_n = X_n W^T, ghat_n / gvar_n       check_cov_cross(same=0), check_cov_u, check_predict(same=0)
+#                   L_S L_S^T = S                              check_cond_s
+#                   L_S^-1 (W slot of the cond workspace), its dense copy in the state
+#                                                              check_inverse_factor, check_cond_dense_inverse (bitwise)
+#                   v = L_S^-1 (t - ghat_n)                    check_cond_v
+#     prediction    X_0, U_0, ghat_0 / gvar_0                  check_cov_cross(same=0), check_cov_u, lcgp_predict's output
+#                   Sigma_0n = C^x(x0, xn) - D U_0 U_n^T       check_cond_cross
+#                   T = Sigma_0n L_S^-T                        check_cov_u(T, Sigma_0n, dense L_S^-1)
+#                   ghat_0 + T v,  gvar_0 - rowsum(T o T)      check_cond_out
+# Every check starts from the library's own input to its stage, so tau = 1 / (D r) -- which can make S ill-conditioned --
+# enters no bound as a condition number.
+# ----------------------------------------------------------------------------------------------------------------------
+def cond_tau(th, r, m, d):
+    """tau_i = 1 / (D r_i) (m values, float64 numpy; r = None: ones), as cond_diag_kernel forms it"""
+    D = split_theta(th, d)[3]
+    rr = np.ones(m) if r is None else np.asarray(r, np.float64)
+    return 1.0 / (D * rr)
+
+
+def cond_s_ref_bound(L, Un, xn, r, th, kernel, dtype):
+    """(S_ref, bound, residual) of check_cond_s: float64 m x m tensors on the device of L / Un"""
+    dev = _dev(L, Un)
+    xn = np.asarray(xn)
+    tau = cond_tau(th, r, xn.shape[0], xn.shape[1])
+    ref, b1 = sigma_ref_bound(Un, xn, th, tau, kernel, dtype, dev)
+    l = torch.tril(_t(L, dev))
+    return ref, b1 + inverse_solve_bound(l, dtype), (ref - l @ l.T).abs()
+
+
+def check_cond_s(L, Un, xn, r, th, kernel, dtype) -> Check:
+    """L_S (the fetched matrix slot of the cond workspace after lcgp_condition_prepare, n = m) against
+        S_ref = C(xn, xn) with the nugget on the diagonal - D U_n U_n^T + diag(tau),   tau_i = 1 / (D r_i),
+    in float64 from the library's own U_n (m x n, the state's first slabs), the rounded xn and the counts r (float64, as given;
+    None: ones).  S itself is factorised in place and cannot be read back, so the factor is held to S_ref directly:
+        |L_S L_S^T - S_ref| <= |S - S_ref| + |L_S L_S^T - S|
+    with the sum of two existing bounds (lower triangle):
+      - check_sigma's for the first term.  cross_kernel (same = 1: the nugget on the diagonal), OP_PRED_COV over K = npad
+        terms with alpha = -D on the product: C (npad + d + E) u (|C00| + |D| |U_n| |U_n|^T), |C00| itself past the C0 cut-off.
+        cond_diag_kernel forms tau_i = 1 / (D r_i) in double (two roundings of u64), adds it to the stored diagonal in double
+        and stores once: u |S_ii + tau_i| <= u |tau_i| + u |S_ii|; the second part is within the previous term, the first is
+        the u |tau_i| on the diagonal.  (Operation count of the diagonal entry: npad products, the alpha product, the
+        subtraction, the store, then one addition and one store more.  The double roundings of tau and the reference's own
+        are within the margin of C on the first term as long as tau_i <= npad (|C00_ii| + |D| |U_n|_i^2), i.e. D r_i scale >=
+        1 / npad: every case of the suite.)
+      - check_cholesky_inverse_solve's for the second, on |L_S| |L_S|^T: min(i, j) + 2 terms per entry, plus the panel solve
+        by the explicit inverse of the 64 x 64 diagonal block, which is what an ill-conditioned S (small tau, new inputs
+        close together) needs -- that function's docstring.
+    Both are independent of the condition number of S, so their sum is."""
+    ref, bound, res = cond_s_ref_bound(L, Un, xn, r, th, kernel, dtype)
+    return worst(res, bound)
+
+
+def _first_bad(bad) -> Check:
+    if not bool(bad.any()):
+        return Check(0.0, ())
+    i, j = (int(v) for v in torch.nonzero(bad)[0])
+    return Check(math.inf, (i // TS, j // TS))
+
+
+def cond_dense_mismatch(Wd, W, m):
+    """the mask (mpad x mpad, bool) of the entries of the state's dense L_S^-1 that check_cond_dense_inverse rejects"""
+    dev = _dev(Wd, W)
+    wd = _t(Wd, dev).contiguous()
+    mpad = wd.shape[0]
+    assert mpad == _pad128(m) and wd.shape[1] == mpad, (wd.shape, m)
+    ref = torch.eye(mpad, dtype=torch.float64, device=dev)
+    ref[:m, :m] = torch.tril(_t(W, dev)[:m, :m])
+    low = torch.zeros(mpad, mpad, dtype=torch.bool, device=dev)
+    low[:m, :m] = torch.tril(torch.ones(m, m, dtype=torch.bool, device=dev))
+    return torch.where(low, wd.view(torch.int64) != ref.view(torch.int64), wd != ref)
+
+
+def check_cond_dense_inverse(Wd, W, m) -> Check:
+    """the dense copy of L_S^-1 in the state (Wd: the raw mpad x mpad slab) after lcgp_condition_prepare, EXACTLY: bitwise equal to
+    the fetched W slot of the cond workspace (W, m x m) on the lower triangle of the first m rows; zero above the diagonal over
+    the whole mpad x mpad (the product that forms T reads whole tiles); the identity's rows from m on.  Off the copied triangle
+    the comparison is by value: a NaN or any non-zero is rejected, a zero of either sign is a zero -- the triangular inverse of
+    the identity padding leaves -0 = -(1 x 0 x w) below the diagonal of those rows, which adds nothing to any product.  A copy
+    has no rounding: ratio 0 when every entry matches, inf otherwise, located at the first wrong (row block, column block)."""
+    return _first_bad(cond_dense_mismatch(Wd, W, m))
+
+
+def check_cond_v(v, Wd, t, ghat_n, m) -> Check:
+    """v = L_S^-1 (t - ghat_n) (the state's m doubles) against the float64 product of the state's own dense L_S^-1 (lower
+    triangle of its first m rows), the observations t (float64, as given) and ghat(xn) as the preparation left it in its
+    scratch.  cond_v_kernel converts the stored row to double and accumulates in double in both storage types: per row the
+    subtraction, at most m products and m - 1 additions (64 lanes, then the butterfly):
+        C (m + 2) u64 (|L_S^-1| (|t| + |ghat_n|))_i + floor."""
+    dev = _dev(v, Wd, ghat_n)
+    w = torch.tril(_t(Wd, dev)[:m, :m])
+    tt, gh = _t(t, dev)[:m], _t(ghat_n, dev)[:m]
+    ref = w @ (tt - gh)
+    bound = C * (m + 2.0) * unit("float64") * (w.abs() @ (tt.abs() + gh.abs())) + floor("float64", m)
+    return worst((_t(v, dev)[:m] - ref).abs(), bound)
+
+
+def check_cond_cross(Sg, U0, Un, x0, xn, th, kernel, dtype) -> Check:
+    """Sigma_0n (n0 x m, the third slabs of the lcgp_condition_predict scratch) against
+        scale (1 - nt) C0(x0, xn) - D U_0 U_n^T,
+    never a nugget term (a row of x0 that equals a row of xn is still a new input of the continuous surface), in float64 from
+    the library's own U_0 (n0 x n, the scratch's second slabs) and U_n (m x n, the state) and the rounded x0, xn.
+    cross_kernel evaluates C^x like X in check_cov_cross ((E + 4) u relative, any value in [0, C0] past the cut-off);
+    OP_COND_CROSS accumulates sum_k U_0[i, k] U_n[j, k] over K = npad terms in the storage type on 64 x 64 tiles, applies
+    alpha = -D to the product, adds the C tile and stores once: npad products, the alpha product, the addition and the store,
+        C (npad + d + E) u (|C^x| + |D| |U_0| |U_n|^T)  (+ |C^x| past the cut-off)  + floor,
+    on ALL entries (the output is rectangular and has no symmetry to lean on)."""
+    dev = _dev(Sg, U0, Un)
+    d = np.asarray(x0).shape[1]
+    u = unit(dtype)
+    ell, scale, nug, D, _ = split_theta(th, d)
+    nt = nug / (1.0 + nug)
+    c0, e, cut = kernel_parts(rounded(x0, dtype), rounded(xn, dtype), ell, kernel, dtype, dev)
+    u0, un = _t(U0, dev), _t(Un, dev)
+    k = _pad128(un.shape[1])
+    cx = scale * (1.0 - nt) * c0
+    ref = cx - D * (u0 @ un.T)
+    bound = C * (k + d + e) * u * (cx.abs() + abs(D) * (u0.abs() @ un.abs().T)) + floor(dtype, k)
+    bound = bound + torch.where(cut, cx.abs(), torch.zeros_like(cx))
+    return worst((_t(Sg, dev) - ref).abs(), bound, lower=False)
+
+
+def check_cond_out(ghat, gvar, T, v, ghat0, gvar0, m) -> Check:
+    """the outputs of lcgp_condition_predict (n0 doubles each, one component) against
+        ghat_0 + T v,    gvar_0 - rowsum(T o T)
+    in float64 from the library's own T (n0 x m, the scratch's fourth slabs), v (the state) and the ghat_0 / gvar_0 of a
+    separate lcgp_predict(same = 0) call on the same rows, which the view's own first stage must equal bitwise.
+    cond_reduce_kernel converts T to double and sums m terms in double (64 lanes, then the butterfly), then one addition to
+    the stored output: m products, m additions:
+        C (m + 2) u64 (|ghat_0| + |T| |v|) + floor,    C (m + 2) u64 (|gvar_0| + sum_j T_ij^2) + floor.
+    The bound of gvar is relative to gvar_0 + sum T^2, not to the result: where a row of x0 equals a row of xn the result
+    cancels to about tau."""
+    dev = _dev(ghat, gvar, T, v)
+    tm = _t(T, dev)[:, :m]
+    vv = _t(v, dev)[:m]
+    g0, v0 = _t(ghat0, dev), _t(gvar0, dev)
+    w = C * (m + 2.0) * unit("float64")
+    fl = floor("float64", m)
+    gref = g0 + tm @ vv
+    gb = w * (g0.abs() + tm.abs() @ vv.abs()) + fl
+    t2 = (tm * tm).sum(dim=1)
+    vref = v0 - t2
+    vb = w * (v0.abs() + t2) + fl
+    return combine(worst((_t(ghat, dev) - gref).abs(), gb), worst((_t(gvar, dev) - vref).abs(), vb))

@@ -16,7 +16,14 @@ predictions at training rows fail check_predict when the nugget term sits one co
 Matern-5/2.  The emulated paths build their matrices from sb.kernel_parts, so its Matern-5/2 branches are pinned without
 going through them: C0 against tests/matern52_oracle.py, dC0 and h against torch autograd of a C0 restated here, and the
 magnification E against an emulation of build_kernel's float32 operation order.  Three wrong-kernel defects (a far tile of
-A, one g_ell slot, dghat: each with the Matern-3/2 formula) fail their stage."""
+A, one g_ell slot, dghat: each with the Matern-3/2 formula) fail their stage.
+
+The conditioned view (lcgp_condition_prepare / lcgp_condition_predict) is emulated in the storage type with q = 3 components,
+the three kernels, the full and the replicated path: every stage from X_n to the corrected outputs is at or below 1, and tau of
+the wrong component or without the replicate counts, a K-stage left out of a far tile of Sigma_0n, a nugget term where a row of
+x0 equals a row of xn, an upper triangle of the dense L_S^-1 that was not zeroed, v of the wrong component, row sums over a
+non-zero padding column of T and a float32-accurate Sigma_0n each fail their own stage and none upstream of it.  A far tile of
+Sigma_0n off by 1e-6 relative, invisible in the units of the end-to-end test, fails cond_cross."""
 import numpy as np
 import pytest
 import torch
@@ -1124,3 +1131,268 @@ def test_matern52_defect_3_dghat_with_the_matern32_h(dtype):
     assert np.array_equal(gv, g["gv"])
     c = sb.check_pgrad(gh, gv, *args, "matern52", dtype)
     assert c.ratio > 1 and c.where[1].startswith("dghat"), c
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# the conditioned view: an emulated lcgp_condition_prepare / lcgp_condition_predict with q = 3 components that differ in
+# every parameter, in the storage type (numpy float32 / float64 arrays; the tile kernel's products in 64-stages on one
+# accumulator, the reductions in double).  n = 300 (npad 384), m = 150 (mpad 256: 106 padding columns), n0 = 130 (n0pad
+# 256).  Rows 0 .. 3 of x0 equal rows of xn; rows 64 .. 127 of x0 lie nine units outside the data, so the row block 1 of
+# Sigma_0n is made of far tiles (entries ~1e-14 of the largest).
+# ----------------------------------------------------------------------------------------------------------------------
+COND_M, COND_N0 = 150, 130
+COND_EQUAL = (0, 63, 64, 149)                 # x0 row i equals xn row COND_EQUAL[i]
+COND_FAR = (1, 1)                             # a far tile of Sigma_0n: x0 rows 64 .. 127, xn rows 64 .. 127
+COND_STAGES = ("cross_n", "u_n", "pred_n", "cond_s", "cond_winv", "cond_dense", "cond_v", "cross_0", "u_0", "cond_cross",
+               "cond_t", "cond_out")
+
+
+def _np_t(dtype):
+    return np.float32 if dtype == "float32" else np.float64
+
+
+def _mm(A, B, dtype):
+    """A B^T as the tile kernel forms it: operands and accumulator in the storage type, K in 64-stages"""
+    T = _np_t(dtype)
+    A, B = np.asarray(A, T), np.asarray(B, T)
+    acc = np.zeros((A.shape[0], B.shape[0]), T)
+    for k in range(0, A.shape[1], TS):
+        acc += A[:, k:k + TS] @ B[:, k:k + TS].T
+    return acc
+
+
+def _axpy(Cm, alpha, acc, dtype):
+    """C + alpha acc in the storage type (the epilogue of OP_PRED_COV / OP_COND_CROSS), as float64"""
+    T = _np_t(dtype)
+    return np.asarray(np.asarray(Cm, T) + T(alpha) * np.asarray(acc, T), np.float64)
+
+
+def _cond_problem(dtype, kernel="matern32", rep=False):
+    import scipy.linalg  # noqa: F401  (the triangular solves of the emulation)
+    rng = np.random.default_rng(50)
+    x = rng.uniform(0.0, 1.0, (N, D_IN))
+    Y = rng.standard_normal((P, N))
+    sr = np.sqrt(rng.integers(1, 6, N).astype(np.float64)) if rep else None
+    xn = rng.uniform(0.0, 1.0, (COND_M, D_IN))
+    r = (1.0 + np.arange(COND_M) % 3) if rep else None
+    x0 = rng.uniform(-0.1, 1.1, (COND_N0, D_IN))
+    x0[:len(COND_EQUAL)] = xn[list(COND_EQUAL)]
+    x0[64:128] += 9.0
+    t = rng.standard_normal((len(JOINT_TH), COND_M))
+    ths, fits = [], []
+    for k, (ell, scale, nug, Dk) in enumerate(JOINT_TH):
+        th = np.concatenate([ell, [scale, nug, Dk], np.random.default_rng(60 + k).standard_normal(P)])
+        ths.append(th)
+        fits.append(_fit(x, Y, sr, th, dtype, kernel))
+    return dict(x=x, sr=sr, xn=xn, r=r, x0=x0, t=t, th=ths, fit=fits, dtype=dtype, kernel=kernel)
+
+
+def _cond_prepare(p, k, tau_D=None, use_r=True, upper=None):
+    """the preparation of component k.  Defects: tau_D (the D that tau is formed with), use_r = False (tau = 1 / D), upper (a
+    value left above the diagonal of the dense L_S^-1)"""
+    import scipy.linalg as sla
+    dtype, kernel, th, f = p["dtype"], p["kernel"], p["th"][k], p["fit"][k]
+    T = _np_t(dtype)
+    ell, scale, nug, Dk, _ = sb.split_theta(th, D_IN)
+    nt = nug / (1 + nug)
+    m, mpad = COND_M, sb._pad128(COND_M)
+    Xn = _r(_cross(p["xn"], p["x"], p["sr"], th, dtype, kernel), dtype)
+    Un = np.asarray(_mm(Xn, f["W"], dtype), np.float64)
+    ghat_n = Xn @ f["z"]
+    gvar_n = scale - Dk * np.sum(Un * Un, axis=1)
+    xr = _r(p["xn"], dtype)
+    cnn = scale * ((1 - nt) * sb.kernel_parts(xr, xr, ell, kernel, dtype)[0].numpy() + nt * np.eye(m))
+    S = _axpy(_r(cnn, dtype), -Dk, _mm(Un, Un, dtype), dtype)
+    rr = p["r"] if (use_r and p["r"] is not None) else np.ones(m)
+    tau = 1.0 / ((Dk if tau_D is None else tau_D) * rr)
+    S[np.arange(m), np.arange(m)] = _r(np.diag(S) + tau, dtype)
+    L = np.linalg.cholesky(np.asarray(S, T))
+    Wn = np.tril(sla.solve_triangular(L, np.eye(m, dtype=T), lower=True))
+    assert L.dtype == T and Wn.dtype == T
+    L, Wn = np.asarray(L, np.float64), np.asarray(Wn, np.float64)
+    Wd = np.eye(mpad)
+    Wd[:m, :m] = Wn
+    if upper is not None:
+        Wd[np.triu_indices(mpad, 1)] = upper
+    v = np.zeros(mpad)
+    v[:m] = np.tril(Wd[:m, :m]) @ (p["t"][k] - ghat_n)         # (cond_v_kernel sums j <= i only)
+    return dict(Xn=Xn, Un=Un, ghat_n=ghat_n, gvar_n=gvar_n, L=L, Wn=Wn, Wd=Wd, v=v)
+
+
+def _cond_sigma(p, k, e, drop=None, nugget=False, as32=False):
+    """Sigma_0n of component k, padded to n0pad x mpad with zeros, and what it is made from.  Defects: drop = (tile, stage): that
+    64-tile misses that 64-wide K-stage of U_0 U_n^T; nugget: scale nt added where a row of x0 equals a row of xn; as32: the
+    result carries float32 accuracy"""
+    dtype, kernel, th, f = p["dtype"], p["kernel"], p["th"][k], p["fit"][k]
+    ell, scale, nug, Dk, _ = sb.split_theta(th, D_IN)
+    nt = nug / (1 + nug)
+    n0, m = COND_N0, COND_M
+    X0 = _r(_cross(p["x0"], p["x"], p["sr"], th, dtype, kernel), dtype)
+    U0 = np.asarray(_mm(X0, f["W"], dtype), np.float64)
+    g0 = X0 @ f["z"]
+    v0 = scale - Dk * np.sum(U0 * U0, axis=1)
+    cx = scale * (1 - nt) * sb.kernel_parts(_r(p["x0"], dtype), _r(p["xn"], dtype), ell, kernel, dtype)[0].numpy()
+    if nugget:
+        cx = cx.copy()
+        cx[np.arange(len(COND_EQUAL)), list(COND_EQUAL)] += scale * nt
+    acc = np.asarray(_mm(U0, e["Un"], dtype), np.float64)
+    if drop is not None:
+        (i, j), s = drop
+        rows, cols = _tile(i, j)
+        ks = slice(s * TS, (s + 1) * TS)
+        acc[rows, cols] = _r(acc[rows, cols] - U0[rows, ks] @ e["Un"][cols, ks].T, dtype)[:n0 - rows.start]
+    Sg = np.zeros((sb.predict_pad(n0), sb._pad128(m)))
+    Sg[:n0, :m] = _axpy(_r(cx, dtype), -Dk, acc, dtype)
+    if as32:
+        Sg = _r(Sg, "float32")
+    return dict(X0=X0, U0=U0, g0=g0, v0=v0, Sg=Sg)
+
+
+def _cond_output(p, e, s, v=None, pad_column=False):
+    """T and the corrected outputs from the dense L_S^-1 (read whole, as the tile kernel does), v and Sigma_0n.  Defects: v (the v
+    of another component); pad_column: column m of T holds what column 0 does and the row sums run to mpad"""
+    n0, m = COND_N0, COND_M
+    Tm = np.asarray(_mm(s["Sg"], e["Wd"], p["dtype"]), np.float64)
+    vv = e["v"] if v is None else v
+    hi = m
+    if pad_column:
+        Tm[:, m] = Tm[:, 0]
+        hi = Tm.shape[1]
+    gh = s["g0"] + Tm[:n0, :hi] @ vv[:hi]
+    gv = s["v0"] - np.sum(Tm[:n0, :hi] ** 2, axis=1)
+    return dict(Tm=Tm, gh=gh, gv=gv)
+
+
+def _cond_checks(p, k, e, s, o):
+    dtype, kernel, th, f = p["dtype"], p["kernel"], p["th"][k], p["fit"][k]
+    x, sr, xn, x0, n0, m = p["x"], p["sr"], p["xn"], p["x0"], COND_N0, COND_M
+    return dict(
+        cross_n=sb.check_cov_cross(e["Xn"], xn, x, sr, th, kernel, dtype),
+        u_n=sb.check_cov_u(e["Un"], e["Xn"], f["W"], dtype),
+        pred_n=sb.check_predict(e["ghat_n"], e["gvar_n"], xn, x, sr, th, f["W"], f["z"], kernel, dtype),
+        cond_s=sb.check_cond_s(e["L"], e["Un"], xn, p["r"], th, kernel, dtype),
+        cond_winv=sb.check_inverse_factor(e["L"], e["Wn"], dtype),
+        cond_dense=sb.check_cond_dense_inverse(e["Wd"], e["Wn"], m),
+        cond_v=sb.check_cond_v(e["v"], e["Wd"], p["t"][k], e["ghat_n"], m),
+        cross_0=sb.check_cov_cross(s["X0"], x0, x, sr, th, kernel, dtype),
+        u_0=sb.check_cov_u(s["U0"], s["X0"], f["W"], dtype),
+        cond_cross=sb.check_cond_cross(s["Sg"][:n0, :m], s["U0"], e["Un"], x0, xn, th, kernel, dtype),
+        cond_t=sb.check_cov_u(o["Tm"][:n0, :m], s["Sg"][:n0, :m], e["Wd"][:m, :m], dtype),
+        cond_out=sb.check_cond_out(o["gh"], o["gv"], o["Tm"][:n0], e["v"], s["g0"], s["v0"], m))
+
+
+def _cond_run(p, k, prepare=None, sigma=None, output=None):
+    e = _cond_prepare(p, k, **(prepare or {}))
+    s = _cond_sigma(p, k, e, **(sigma or {}))
+    o = _cond_output(p, e, s, **(output or {}))
+    return e, s, o, _cond_checks(p, k, e, s, o)
+
+
+def _only(checks, *failing):
+    """every stage listed in `failing` is above 1, every stage upstream of the first of them at or below 1"""
+    assert tuple(checks) == COND_STAGES
+    first = min(COND_STAGES.index(f) for f in failing)
+    for stage in COND_STAGES[:first]:
+        assert checks[stage].ratio <= 1.0, ("upstream", stage, checks[stage])
+    for stage in failing:
+        assert checks[stage].ratio > 1.0, (stage, checks[stage])
+
+
+@pytest.fixture(scope="module", params=["float64", "float32"])
+def cond(request):
+    return _cond_problem(request.param)
+
+
+@pytest.fixture(scope="module")
+def cond64():
+    return _cond_problem("float64")
+
+
+@pytest.mark.parametrize("rep", [False, True], ids=["full", "rep"])
+@pytest.mark.parametrize("kernel", KERNELS)
+@pytest.mark.parametrize("dtype", ["float64", "float32"])
+def test_emulated_conditioned_view_passes_every_stage(dtype, kernel, rep):
+    p = _cond_problem(dtype, kernel, rep)
+    for k in range(len(JOINT_TH)):
+        e, s, o, checks = _cond_run(p, k)
+        print("conditioned view, emulated, %s %s %s k%d: %s"
+              % (dtype, kernel, "rep" if rep else "full", k, "  ".join("%s %.2e" % (st, c.ratio) for st, c in checks.items())))
+        for stage, c in checks.items():
+            assert c.ratio <= 1.0, (k, stage, c)
+        # the far tile is far: below 1e-8 of the largest entry, and not all zero in float64
+        far = np.abs(s["Sg"][_tile(*COND_FAR)])
+        assert far.max() < 1e-8 * np.abs(s["Sg"]).max()
+        assert dtype == "float32" or kernel == "se" or far.min() > 0
+
+
+def test_cond_defect_1_tau_of_the_next_component_or_without_r():
+    """tau = 1 / (D_{k+1} r) and, on the rep path, tau = 1 / D_k: S, so its factor and everything behind it, belong to another
+    problem; cond_s fails and nothing before it"""
+    for dtype in ("float64", "float32"):
+        p = _cond_problem(dtype, rep=True)
+        for k in range(len(JOINT_TH)):
+            other = p["th"][(k + 1) % len(JOINT_TH)][D_IN + 2]
+            _only(_cond_run(p, k, prepare=dict(tau_D=other))[3], "cond_s")
+            _only(_cond_run(p, k, prepare=dict(use_r=False))[3], "cond_s")
+
+
+def test_cond_defect_2_k_stage_left_out_of_a_far_tile(cond):
+    """the far tile (1, 1) of Sigma_0n misses the 64-wide K-stage 2 of U_0 U_n^T"""
+    for k in range(len(JOINT_TH)):
+        checks = _cond_run(cond, k, sigma=dict(drop=(COND_FAR, 2)))[3]
+        _only(checks, "cond_cross")
+        assert checks["cond_cross"].where == COND_FAR, checks["cond_cross"]
+
+
+def test_cond_defect_3_nugget_where_a_row_of_x0_equals_a_row_of_xn(cond):
+    for k in range(len(JOINT_TH)):
+        checks = _cond_run(cond, k, sigma=dict(nugget=True))[3]
+        _only(checks, "cond_cross")
+        assert checks["cond_cross"].where[0] == 0, checks["cond_cross"]
+
+
+def test_cond_defect_4_upper_triangle_of_the_dense_inverse_not_zeroed(cond):
+    """the strict upper triangle of the state's L_S^-1 holds 0.25: the bitwise check sees it, and T, which the tile kernel forms
+    from whole tiles of it, fails cond_t; the stages between (v sums j <= i only) and Sigma_0n do not"""
+    for k in range(len(JOINT_TH)):
+        checks = _cond_run(cond, k, prepare=dict(upper=0.25))[3]
+        _only(checks, "cond_dense", "cond_t")
+        for stage in ("cond_winv", "cond_v", "cross_0", "u_0", "cond_cross"):
+            assert checks[stage].ratio <= 1.0, (stage, checks[stage])
+
+
+def test_cond_defect_5_v_of_the_next_component(cond):
+    for k in range(len(JOINT_TH)):
+        v = _cond_prepare(cond, (k + 1) % len(JOINT_TH))["v"]
+        _only(_cond_run(cond, k, output=dict(v=v))[3], "cond_out")
+
+
+def test_cond_defect_6_row_sums_over_a_nonzero_padding_column_of_t(cond):
+    for k in range(len(JOINT_TH)):
+        _only(_cond_run(cond, k, output=dict(pad_column=True))[3], "cond_out")
+
+
+def test_cond_defect_7_float32_sigma0n_in_the_float64_check(cond64):
+    for k in range(len(JOINT_TH)):
+        _only(_cond_run(cond64, k, sigma=dict(as32=True))[3], "cond_cross")
+
+
+def test_cond_gap_far_tile_off_by_1e_6_is_invisible_end_to_end(cond64):
+    """what the stage bound closes: the far tile (1, 1) of Sigma_0n off by 1e-6 relative.  In the units of tests/test_gpu_condition.py
+    -- the largest gvar of the base model and the largest |ghat| over the 130 points -- the outputs move by far less than its
+    1e-10; cond_cross is above 1 at that tile"""
+    p = cond64
+    for k in range(len(JOINT_TH)):
+        e, s, o, checks = _cond_run(p, k)
+        assert checks["cond_cross"].ratio <= 1.0
+        bad = dict(s, Sg=s["Sg"].copy())
+        tile = _tile(*COND_FAR)
+        assert np.abs(bad["Sg"][tile]).max() < 1e-8 * np.abs(s["Sg"]).max()
+        bad["Sg"][tile] *= 1 + 1e-6
+        ob = _cond_output(p, e, bad)
+        eh = np.max(np.abs(ob["gh"] - o["gh"])) / np.max(np.abs(o["gh"]))
+        ev = np.max(np.abs(ob["gv"] - o["gv"])) / np.max(s["v0"])
+        print("gap k%d: end-to-end change ghat %.3e gvar %.3e (bar 1e-10)" % (k, eh, ev))
+        assert eh < 1e-10 and ev < 1e-10
+        c = _cond_checks(p, k, e, bad, ob)["cond_cross"]
+        assert c.ratio > 1 and c.where == COND_FAR, c

@@ -494,6 +494,44 @@ int lcgp_condition_predict(void* stream, int dtype, int kernel_id, int n, int d,
                            const void* state, int m, const void* xn, int n0, const void* x0,
                            void* scratch, size_t scratch_bytes, double* ghat, double* gvar, int out_stride);
 
+/* Input gradients of a conditioned view's prediction (what lcgp_predict_grad is to lcgp_predict): per local component k and
+ * new input i the outputs of lcgp_condition_predict and their derivatives with respect to the standardised x0, in
+ * lcgp_predict_grad's layout (dghat, dgvar: q_local x out_stride x d doubles).  `state`, m, xn: as lcgp_condition_predict takes
+ * them; the workspace and the state are only read.  With T = Sigma_0n L_S^-T as there:
+ *     w   = L_S^-T v                                  (m)          once per view
+ *     z'  = z - D_k W^T (U_n^T w)                     (npad)       once per view        ghat' = X_0 z' + C^x(x0, xn) w
+ *     R   = T L_S^-1  (= Sigma_0n S^-1)               (n0 x m)     per pass
+ *     U'  = U_0 - R U_n,   V' = U' W                  (n0 x npad)  per pass
+ *     dghat'[i, l] =        sum_j dc_l(x0_i, x_j) sr_j z'_j       +   sum_a dc^x_l(x0_i, xn_a) w_a
+ *     dgvar'[i, l] = -2 D_k sum_j dc_l(x0_i, x_j) sr_j V'[i, j]   - 2 sum_a dc^x_l(x0_i, xn_a) R[i, a]
+ * dc_l as in lcgp_predict_grad for the three kernels (0 at dx_l = 0); same = 0 throughout: the gradient of the continuous
+ * surface, also at training inputs and at the view's own new inputs.
+ *   1. lcgp_condition_grad_prepare, once per view: w and z' of every local component into `grad_state`
+ *      (lcgp_condition_grad_state_bytes bytes = q_local (mpad + 2 npad) doubles, the second npad a work area), by three
+ *      bandwidth-bound products with the transposes of L_S^-1, U_n and W, read along their rows; sums in double, the rows
+ *      of a column shared among four waves in a fixed order.
+ *   2. lcgp_condition_predict_grad, once per chunk of new inputs: the launches of lcgp_condition_predict (ghat' / gvar' are
+ *      bitwise that function's), R over Sigma_0n by lcgp_predict_grad's product V = U W with W := L_S^-1 (64 x 64 tiles), U' in place over U_0
+ *      by ONE launch of the tile kernel (operand mode OP_COND_U: K = mpad, C -= A B; 64 x 64 tiles, as OP_COND_CROSS: the 128-row
+ *      instances spill in float64 and fail the counted-prefetch check in float32), V' over X as lcgp_predict_grad forms V, and lcgp_predict_grad's fused contraction over the n + m columns
+ *      (pgrad_cond_kernel: the conditioning inputs are a second segment behind the training inputs, weight 1, w for z, R for
+ *      V; same lane / slice / wave order, double accumulators; nothing of size n0 (n + m) d is written).
+ * `scratch`: lcgp_condition_predict_grad_scratch_bytes = lcgp_condition_scratch_bytes(dtype, n, q_local, m, n0) of a pass, checked
+ * against `scratch_bytes`.  Fixed order, no atomics, one stream: results are bitwise independent of the content of scratch
+ * and grad_state on entry, of q_local in lcgp_condition_predict's sense, and of how a caller splits the rows of x0: R and V' are
+ * formed on 64 x 64 tiles whatever n0 is (the product V = U W walks its k tiles downwards in units of the tile, so its 128-row
+ * instance adds in another order; lcgp_variance_reduction_grad makes the same choice), U' likewise.
+ * Flops per component beyond lcgp_condition_predict's: n0pad mpad^2 (R) + 2 n0pad mpad npad (U') + n0pad npad^2 (V'). */
+int lcgp_condition_grad_state_bytes(int dtype, int n, int q_local, int m, size_t* bytes /*host out*/);
+int lcgp_condition_grad_prepare(void* stream, int dtype, int n, int d, int p, int q_local, const double* theta,
+                                const void* workspace, const void* state, int m, void* grad_state);
+int lcgp_condition_predict_grad_scratch_bytes(int dtype, int n, int q_local, int m, int n0, size_t* bytes /*host out*/);
+int lcgp_condition_predict_grad(void* stream, int dtype, int kernel_id, int n, int d, int p, int q_local,
+                                const void* x, const void* sr, const double* theta, const void* workspace,
+                                const void* state, int m, const void* xn, const void* grad_state, int n0, const void* x0,
+                                void* scratch, size_t scratch_bytes, double* ghat, double* gvar, double* dghat, double* dgvar,
+                                int out_stride);
+
 /* Closed-form cross-validation at fixed parameters (no counterpart in the reference).  Input: the workspace of the last
  * lcgp_nll_grad, whose V slot holds a = A_k^-1 (A_k = I + D_k (C_k o s s^T), s = sr, ones when sr is NULL) and whose vectors
  * hold b_k and z_k = A_k^-1 b_k.  With K_k = C_k + (D_k S^2)^-1 (S = diag(s)), K_k^-1 = D_k S a S, so for a set B of m

@@ -870,7 +870,7 @@ __global__ __launch_bounds__(256, 2) void leaf_kernel(T* __restrict__ M, T* __re
 // and staged in LDS as [k][m] (KT = 16 k rows per stage, double buffered through registers).
 // ---------------------------------------------------------------------------------------------------
 enum GemmOp { OP_SYRK = 1, OP_TRTRI_T = 2, OP_TRTRI_W = 3, OP_LAUUM = 4, OP_PRED_U = 5, OP_PRED_COV = 6, OP_PRED_V = 7, OP_VR = 8,
-              OP_VG_P = 9, OP_VG_G = 10, OP_HESS_G = 11, OP_COND_CROSS = 12 };
+              OP_VG_P = 9, OP_VG_G = 10, OP_HESS_G = 11, OP_COND_CROSS = 12, OP_COND_U = 13 };
 enum Lay { MK = 0, KM = 1 };
 
 struct GemmArgs {
@@ -1228,7 +1228,8 @@ template <typename T, int OP, int TM, int NW>
 __device__ __forceinline__ void gemm_body(const GemmArgs& g, const int lin /*block index within this descriptor*/,
                                           unsigned char* lds) {
     constexpr int LA = (OP == OP_LAUUM) ? KM : MK;
-    constexpr int LB = (OP == OP_TRTRI_T || OP == OP_TRTRI_W || OP == OP_LAUUM || OP == OP_PRED_V || OP == OP_VG_G || OP == OP_HESS_G) ? KM : MK;
+    constexpr int LB = (OP == OP_TRTRI_T || OP == OP_TRTRI_W || OP == OP_LAUUM || OP == OP_PRED_V || OP == OP_VG_G || OP == OP_HESS_G ||
+                        OP == OP_COND_U) ? KM : MK;
     constexpr int NT = NW * 64;
     constexpr int LD = TM + 16;     // = 16 (mod 32): the two k rows a 32-lane group reads hit disjoint banks
     constexpr int WTM = TM / (NW / 2), WTN = TM / 2;   // per-wave sub-tile
@@ -1384,6 +1385,16 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& g, const int lin /*blo
         B0 = Bb + (size_t)c * TM; dB = (ptrdiff_t)TM * g.ldB;
         nkt = g.p1;
         Ct = Cb + (size_t)m * TM * g.ldC + (size_t)c * TM;
+    } else if constexpr (OP == OP_COND_U) {
+        // U'[m, c] = U_0[m, c] - sum_{kt < p1} R[m, kt] U_n[kt, c]      (R = n0pad x mpad, U_n = mpad x npad, C = U_0 in place: the
+        // rectangular product of OP_VG_G with K = mpad and the accumulating epilogue of OP_COND_CROSS, alpha = -1;
+        // lcgp_condition_predict_grad).  Ascending k on either tile size.
+        const int c = bid / g.p0, m = bid % g.p0;                  // p0 = row tiles of R
+        A0 = Ab + (size_t)m * TM * g.ldA; dA = TM;
+        B0 = Bb + (size_t)c * TM; dB = (ptrdiff_t)TM * g.ldB;
+        nkt = g.p1;
+        Ct = Cb + (size_t)m * TM * g.ldC + (size_t)c * TM;
+        alpha = -1.0; accumulate = true;
     } else if constexpr (OP == OP_PRED_V) {
         // V[m, c] = sum_{kt = c}^{nb-1} U[m, kt] W[kt, c]      (U = X W^T, n0pad x npad; W lower triangular)
         // k tiles walked from nb-1 DOWN to c, as OP_LAUUM walks its B operand: every tile starts on the last block row of W,
@@ -1450,7 +1461,7 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& g, const int lin /*blo
     // else changes; bit-identical results: the zeros are stored zeros).  LAUUM / TRTRI_W: 24 of the 64 (wave, stage)
     // pairs of such a tile, TRTRI_T / PRED_U / PRED_V: 16.
     constexpr bool HAS_TRI = OP != OP_SYRK && OP != OP_PRED_COV && OP != OP_VR && OP != OP_VG_P && OP != OP_VG_G && OP != OP_HESS_G &&
-                             OP != OP_COND_CROSS;
+                             OP != OP_COND_CROSS && OP != OP_COND_U;
     const int tri_first = HAS_TRI ? (nkt - 1) * SPT : nst;
     // the wave is idle in the stages [dead_lo, dead_hi) of the k loop (two scalars per wave)
     int dead_lo = nst, dead_hi = nst;
@@ -2840,11 +2851,25 @@ __global__ __launch_bounds__(64) void marg_reduce_kernel(const T* __restrict__ X
 constexpr int PG_ROWS = 32, PG_SL = 8;
 // ZMAT (lcgp_variance_reduction_grad): z is a matrix laid out as V is (row i0 + i of slab k, row length npad), not the vector z_k.
 // MEAN (lcgp_predict_gradcov): dghat alone, by the same operations in the same order; V and dgvar are not touched.
-template <typename T, int DD, int KERN, bool ZMAT = false, bool MEAN = false>
-__global__ __launch_bounds__(256) void pgrad_kernel(const T* __restrict__ x0, int n0, const T* __restrict__ x,
-                                                    const T* __restrict__ sr, int n, int d, const double* __restrict__ theta,
-                                                    int tw, const T* __restrict__ z, int npad, const T* __restrict__ V,
-                                                    size_t slab, int ldo, double* __restrict__ dghat, double* __restrict__ dgvar) {
+// COND (lcgp_condition_predict_grad): the contraction runs over a SECOND segment of columns behind the training inputs, the m
+// conditioning inputs xn of a view -- weight 1 instead of sr_j, w in place of z, R (rows mpad long) in place of V, the factor
+// -2 in place of -2 D (D rides on the weights of the first segment) -- and z is the view's z' in double.  Same stages, same
+// lane / slice / wave order; per lane the training inputs in ascending j, then the conditioning inputs in ascending j.
+template <typename T>
+struct PgradCond {
+    const double* zd;           // z' (q x npad doubles)
+    const T* xn; int m;         // the conditioning inputs (m x d)
+    const double* wv; int mpad; // w = L_S^-T v (q x mpad doubles)
+    const T* R; size_t rslab;   // R = T L_S^-1 (q slabs of rows mpad long)
+};
+
+template <typename T, int DD, int KERN, bool ZMAT, bool MEAN, bool COND>
+__device__ __forceinline__ void pgrad_body(const T* __restrict__ x0, int n0, const T* __restrict__ x,
+                                           const T* __restrict__ sr, int n, int d, const double* __restrict__ theta,
+                                           int tw, const T* __restrict__ z, int npad, const T* __restrict__ V,
+                                           size_t slab, int ldo, double* __restrict__ dghat, double* __restrict__ dgvar,
+                                           const PgradCond<T>& cs) {
+    static_assert(!COND || (!ZMAT && !MEAN), "the second segment belongs to the plain contraction");
     constexpr bool WIDE = DD == DMAX;
     constexpr int JT = WIDE ? 16 : 32;                  // training inputs per LDS stage
     constexpr int XW = WIDE ? DWIDE + 3 : DD + 1;       // odd row length: the per-row reads of x0sh hit distinct banks;
@@ -2877,23 +2902,39 @@ __global__ __launch_bounds__(256) void pgrad_kernel(const T* __restrict__ x0, in
 #pragma unroll
         for (int m = 0; m < DD; ++m) xi[m] = x0sh[r][m];
     }
-    for (int j0 = 0; j0 < n; j0 += JT) {
+    // (COND: the stages of the second segment follow those of the first, whose last stage may be short)
+    const int n1 = (n + JT - 1) / JT * JT, jend = COND ? n1 + (cs.m + JT - 1) / JT * JT : n;
+    for (int j0 = 0; j0 < jend; j0 += JT) {
         if (j0 > 0) __syncthreads();                    // every slice is done with the previous stage
+        const bool seg2 = COND && j0 >= n1;
+        const int jb = seg2 ? j0 - n1 : j0;             // first input of the stage within its segment
+        const T* xs = seg2 ? cs.xn : x;
+        const int ns = seg2 ? cs.m : n;
         for (int e = tid; e < JT * XW; e += 256) {
             const int jj = e / XW, m = e - jj * XW;
-            xsh[jj][m] = (j0 + jj < n && m < d) ? (double)x[(size_t)(j0 + jj) * d + m] / th[m] : 0.0;
+            xsh[jj][m] = (jb + jj < ns && m < d) ? (double)xs[(size_t)(jb + jj) * d + m] / th[m] : 0.0;
         }
         for (int e = tid; e < PG_ROWS * JT; e += 256) {
             const int i = e / JT, jj = e - i * JT;
-            if constexpr (!MEAN) vsh[i][jj] = (i0 + i < n0 && j0 + jj < n) ? (double)Vk[(size_t)(i0 + i) * npad + j0 + jj] : 0.0;
+            if constexpr (COND) {
+                const bool in = i0 + i < n0 && jb + jj < ns;
+                vsh[i][jj] = !in ? 0.0 : seg2 ? (double)cs.R[(size_t)k * cs.rslab + (size_t)(i0 + i) * cs.mpad + jb + jj]
+                                              : (double)Vk[(size_t)(i0 + i) * npad + jb + jj];
+            } else if constexpr (!MEAN) vsh[i][jj] = (i0 + i < n0 && j0 + jj < n) ? (double)Vk[(size_t)(i0 + i) * npad + j0 + jj] : 0.0;
             if constexpr (ZMAT) zsh[i][jj] = (i0 + i < n0 && j0 + jj < n) ? (double)zk[(size_t)(i0 + i) * npad + j0 + jj] : 0.0;
         }
         if (tid < JT) {
-            const int j = j0 + tid;
-            const double s = j < n ? (sr ? (double)sr[j] : 1.0) : 0.0;      // (inputs beyond n weigh zero)
-            wsr[tid] = s;
-            if constexpr (ZMAT) wz[tid] = s;
-            else wz[tid] = j < n ? s * (double)zk[j] : 0.0;
+            const int j = jb + tid;
+            if constexpr (COND) {
+                const double s = j < ns ? (seg2 ? 1.0 : (sr ? (double)sr[j] : 1.0)) : 0.0;
+                wsr[tid] = seg2 ? s : s * D;
+                wz[tid] = j < ns ? s * (seg2 ? cs.wv[(size_t)k * cs.mpad + j] : cs.zd[(size_t)k * npad + j]) : 0.0;
+            } else {
+                const double s = j < n ? (sr ? (double)sr[j] : 1.0) : 0.0;      // (inputs beyond n weigh zero)
+                wsr[tid] = s;
+                if constexpr (ZMAT) wz[tid] = s;
+                else wz[tid] = j < n ? s * (double)zk[j] : 0.0;
+            }
         }
         __syncthreads();
         for (int jj = sl; jj < JT; jj += PG_SL) {
@@ -2948,10 +2989,28 @@ __global__ __launch_bounds__(256) void pgrad_kernel(const T* __restrict__ x0, in
             const double tm = (red[0][0][r] + red[0][1][r]) + (red[0][2][r] + red[0][3][r]);
             const double tv = (red[1][0][r] + red[1][1][r]) + (red[1][2][r] + red[1][3][r]);
             dghat[orow + l0 + l] = -tm / th[l0 + l];
-            if constexpr (!MEAN) dgvar[orow + l0 + l] = 2.0 * D * tv / th[l0 + l];
+            if constexpr (COND) dgvar[orow + l0 + l] = 2.0 * tv / th[l0 + l];      // (D rode on the first segment's weights)
+            else if constexpr (!MEAN) dgvar[orow + l0 + l] = 2.0 * D * tv / th[l0 + l];
         }
         __syncthreads();
     }
+}
+
+template <typename T, int DD, int KERN, bool ZMAT = false, bool MEAN = false>
+__global__ __launch_bounds__(256) void pgrad_kernel(const T* __restrict__ x0, int n0, const T* __restrict__ x,
+                                                    const T* __restrict__ sr, int n, int d, const double* __restrict__ theta,
+                                                    int tw, const T* __restrict__ z, int npad, const T* __restrict__ V,
+                                                    size_t slab, int ldo, double* __restrict__ dghat, double* __restrict__ dgvar) {
+    pgrad_body<T, DD, KERN, ZMAT, MEAN, false>(x0, n0, x, sr, n, d, theta, tw, z, npad, V, slab, ldo, dghat, dgvar, PgradCond<T>{});
+}
+
+// the contraction of lcgp_condition_predict_grad over the n training inputs and the m conditioning inputs of a view
+template <typename T, int DD, int KERN>
+__global__ __launch_bounds__(256) void pgrad_cond_kernel(const T* __restrict__ x0, int n0, const T* __restrict__ x,
+                                                         const T* __restrict__ sr, int n, int d, const double* __restrict__ theta,
+                                                         int tw, int npad, const T* __restrict__ V, size_t slab, int ldo,
+                                                         double* __restrict__ dghat, double* __restrict__ dgvar, PgradCond<T> cs) {
+    pgrad_body<T, DD, KERN, false, false, true>(x0, n0, x, sr, n, d, theta, tw, (const T*)nullptr, npad, V, slab, ldo, dghat, dgvar, cs);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -3861,6 +3920,135 @@ int do_condition_predict(hipStream_t st, const Ws& w, const void* x, const void*
     hipLaunchKernelGGL((cond_reduce_kernel<T>), dim3(n0, w.q), dim3(64), 0, st, (const T*)Tm, cslab, mpad, m, v, mpad, ldo, ghat,
                        gvar);
     CHECK_LAUNCH("cond_reduce_kernel");
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------
+// Input gradients on a conditioned view (lcgp_condition_grad_prepare / lcgp_condition_predict_grad, lcgp_hip.h).  With
+// w = L_S^-T v and z' = z - D W^T (U_n^T w) (once per view, the grad state) the view's mean is X_0 z' + C^x(x0, xn) w; with
+// R = T L_S^-1, U' = U_0 - R U_n and V' = U' W (per pass) its variance has the gradient -2 D sum_j dc sr_j V' - 2 sum_a dc^x R:
+// pgrad_kernel's contraction over n + m columns (pgrad_cond_kernel).
+// ---------------------------------------------------------------------------------------------------
+struct CondGradLay {
+    size_t off_w, off_z, off_a, total;      // w (q mpad doubles), z' (q npad doubles), a = U_n^T w (q npad doubles; work area)
+};
+
+inline CondGradLay cond_grad_carve(int n, int q, int m) {
+    CondGradLay L;
+    const size_t mpad = cov_pad(m), npad = round_up(n, 2 * TS);
+    size_t o = 0;
+    L.off_w = o; o = align256(o + (size_t)q * mpad * sizeof(double));
+    L.off_z = o; o = align256(o + (size_t)q * npad * sizeof(double));
+    L.off_a = o; o = align256(o + (size_t)q * npad * sizeof(double));
+    L.total = o;
+    return L;
+}
+
+// out[k, c] = (zs ? zs[k, c] - D_k sum : sum),  sum = sum_{i < nrows, tri: i >= c} M_k[i, c] vec[k, i]   for c < ncols: the
+// product with the TRANSPOSE of a row-major matrix, read along its rows (64 adjacent columns per wave, coalesced).  The four
+// waves of a workgroup take the rows i = wave (mod 4) in ascending order, in double; their sums are added in a fixed order.
+template <typename T>
+__global__ __launch_bounds__(256) void cond_tmatvec_kernel(const T* __restrict__ M, size_t mat, int ld, int nrows, int ncols,
+                                                           int tri, const double* __restrict__ vec, int ldv,
+                                                           const T* __restrict__ zs, const double* __restrict__ theta, int tw,
+                                                           int d, double* __restrict__ out, int ldo) {
+    __shared__ double part[4][64];
+    const int k = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6, c = blockIdx.x * 64 + lane;
+    const T* Mk = M + (size_t)k * mat;
+    const double* vk = vec + (size_t)k * ldv;
+    double s = 0.0;
+    if (c < ncols) {
+        int i = tri ? (blockIdx.x * 64) / 4 * 4 + wave : wave;         // (rows above the block's first column hold nothing)
+        for (; i < nrows; i += 4)
+            if (!tri || i >= c) s = fma((double)Mk[(size_t)i * ld + c], vk[i], s);
+    }
+    part[wave][lane] = s;
+    __syncthreads();
+    if (wave == 0 && c < ncols) {
+        const double t = (part[0][lane] + part[1][lane]) + (part[2][lane] + part[3][lane]);
+        out[(size_t)k * ldo + c] = zs ? (double)zs[(size_t)k * ldo + c] - theta[(size_t)k * tw + d + 2] * t : t;
+    }
+}
+
+template <typename T>
+int do_condition_grad_prepare(hipStream_t st, const Ws& w, const double* theta, const void* state, int m, void* gstate) {
+    const int dtype = sizeof(T) == 4 ? LCGP_F32 : LCGP_F64;
+    const CondLay L = cond_carve(dtype, w.n, w.q, m);
+    const CondGradLay G = cond_grad_carve(w.n, w.q, m);
+    const int mpad = L.mpad, tw = w.d + 3 + w.p;
+    const T* Un = (const T*)((const char*)state + L.off_U);
+    const T* Wi = (const T*)((const char*)state + L.off_W);
+    const double* v = (const double*)((const char*)state + L.off_v);
+    double* wv = (double*)((char*)gstate + G.off_w);
+    double* zd = (double*)((char*)gstate + G.off_z);
+    double* a = (double*)((char*)gstate + G.off_a);
+    // w = L_S^-T v (zero on the padding: no row below m is read)
+    hipLaunchKernelGGL((cond_tmatvec_kernel<T>), dim3(mpad / 64, w.q), dim3(256), 0, st, Wi, (size_t)mpad * mpad, mpad, m, mpad, 1,
+                       v, mpad, (const T*)nullptr, theta, tw, w.d, wv, mpad);
+    CHECK_LAUNCH("cond_tmatvec_kernel (w)");
+    // a = U_n^T w
+    hipLaunchKernelGGL((cond_tmatvec_kernel<T>), dim3(w.npad / 64, w.q), dim3(256), 0, st, Un, (size_t)mpad * w.npad, w.npad, m,
+                       w.npad, 0, (const double*)wv, mpad, (const T*)nullptr, theta, tw, w.d, a, w.npad);
+    CHECK_LAUNCH("cond_tmatvec_kernel (a)");
+    // z' = z - D W^T a (W = L^-1 of the fitted workspace, lower triangular: the rows from the column down, below n)
+    hipLaunchKernelGGL((cond_tmatvec_kernel<T>), dim3(w.npad / 64, w.q), dim3(256), 0, st, (const T*)(w.base + w.off_W), w.mat,
+                       w.npad, w.n, w.npad, 1, (const double*)a, w.npad, (const T*)(w.base + w.off_z), theta, tw, w.d, zd, w.npad);
+    CHECK_LAUNCH("cond_tmatvec_kernel (z')");
+    return 0;
+}
+
+// One pass: the launches of lcgp_condition_predict (ghat' / gvar' bitwise its; they leave U_0 in the U slab and T behind
+// Sigma_0n), R = T L_S^-1 over Sigma_0n (OP_PRED_V on the state's dense L_S^-1), U' = U_0 - R U_n in place (OP_COND_U), V' = U' W
+// into the X slab (OP_PRED_V, as lcgp_predict_grad's V but on 64-row tiles) and the contraction over the n + m columns.
+// Scratch: that of lcgp_condition_predict.
+template <typename T>
+int do_condition_predict_grad(hipStream_t st, const Ws& w, const void* x, const void* sr, const double* theta, const void* state,
+                              int m, const void* xn, const void* gstate, int n0, const void* x0, void* scratch, double* ghat,
+                              double* gvar, double* dghat, double* dgvar, int ldo) {
+    int rc = do_condition_predict<T>(st, w, x, sr, theta, state, m, xn, n0, x0, scratch, ghat, gvar, ldo);
+    if (rc) return rc;
+    const int dtype = sizeof(T) == 4 ? LCGP_F32 : LCGP_F64;
+    const CondLay L = cond_carve(dtype, w.n, w.q, m);
+    const CondGradLay G = cond_grad_carve(w.n, w.q, m);
+    const int mpad = L.mpad, n0pad = predict_pad(n0);
+    const size_t slab = (size_t)n0pad * w.npad, cslab = (size_t)n0pad * mpad;
+    const T* Un = (const T*)((const char*)state + L.off_U);
+    const T* Wi = (const T*)((const char*)state + L.off_W);
+    T* X = (T*)scratch;
+    T* U0 = X + slab * w.q;
+    T* Rm = (T*)((char*)scratch + align256(2 * (size_t)w.q * slab * sizeof(T)));      // (Sigma_0n has been consumed)
+    T* Tm = Rm + cslab * w.q;
+    // 64x64 tiles for R and V' whatever the number of rows (as lcgp_variance_reduction_grad's G, Q and V): OP_PRED_V sums in a
+    // different order on 128-row tiles, and a caller's split of the rows must not show in the Jacobians
+    rc = launch_pred<T, OP_PRED_V>(st, Tm, Wi, Rm, cslab, (size_t)mpad * mpad, mpad, n0pad, mpad / TS, w.q, 0, true);
+    if (rc) return rc;
+    GemmArgs g;
+    g.A = Rm; g.B = Un; g.C = U0;
+    g.sA = cslab; g.sB = (size_t)mpad * w.npad; g.sC = slab; g.ldA = mpad; g.ldB = g.ldC = w.npad;
+    g.p2 = g.p3 = 0;
+    // 64x64 tiles, as OP_PRED_COV and OP_COND_CROSS: the 128-row instances of this op do not compile clean -- fp64 needs 15
+    // registers more than the 128 a lane has at 4 waves per SIMD (spills), and in fp32 (106 registers) the compiler moves
+    // registers of the hand-counted prefetch before their wait (tools/check_counted_prefetch.py)
+    g.nb = w.nb; g.p0 = n0pad / TS; g.p1 = mpad / TS;
+    rc = launch_gemm<T, OP_COND_U, 64>(st, g, g.p0 * g.nb, w.q);
+    if (rc) return rc;
+    rc = launch_pred<T, OP_PRED_V>(st, U0, (const T*)(w.base + w.off_W), X, slab, w.mat, w.npad, n0pad, w.nb, w.q, 0, true);
+    if (rc) return rc;
+    PgradCond<T> cs;
+    cs.zd = (const double*)((const char*)gstate + G.off_z);
+    cs.xn = (const T*)xn; cs.m = m;
+    cs.wv = (const double*)((const char*)gstate + G.off_w); cs.mpad = mpad;
+    cs.R = Rm; cs.rslab = cslab;
+    const int wide = w.d > 16;
+    dim3 grid((n0 + PG_ROWS - 1) / PG_ROWS, w.q, wide ? (w.d + DMAX - 1) / DMAX : 1);
+    for_dim(w.d, [&](auto dd) {
+        for_kern(w.kern, [&](auto kern) {
+            hipLaunchKernelGGL((pgrad_cond_kernel<T, decltype(dd)::value, decltype(kern)::value>), grid, dim3(256), 0, st,
+                               (const T*)x0, n0, (const T*)x, (const T*)sr, w.n, w.d, theta, w.d + 3 + w.p, w.npad, (const T*)X, slab,
+                               ldo, dghat, dgvar, cs);
+        });
+    });
+    CHECK_LAUNCH("pgrad_cond_kernel");
     return 0;
 }
 
@@ -6824,6 +7012,61 @@ int lcgp_condition_predict(void* stream, int dtype, int kernel_id, int n, int d,
     hipStream_t st = (hipStream_t)stream;
     return dtype == LCGP_F64 ? do_condition_predict<double>(st, w, x, sr, theta, state, m, xn, n0, x0, scratch, ghat, gvar, ldo)
                              : do_condition_predict<float>(st, w, x, sr, theta, state, m, xn, n0, x0, scratch, ghat, gvar, ldo);
+}
+
+int lcgp_condition_grad_state_bytes(int dtype, int n, int q_local, int m, size_t* bytes) {
+    if (dtype != LCGP_F64 && dtype != LCGP_F32) return bad("dtype must be 0 (f64) or 1 (f32)");
+    if (n < 1 || q_local < 1) return bad("n, q_local must be >= 1");
+    if (m < 1) return bad("m < 1");
+    if (!bytes) return bad("bytes is NULL");
+    *bytes = cond_grad_carve(n, q_local, m).total;
+    return 0;
+}
+
+int lcgp_condition_grad_prepare(void* stream, int dtype, int n, int d, int p, int q_local, const double* theta,
+                                const void* workspace, const void* state, int m, void* grad_state) {
+    int rc = check_common(dtype, n, d, p, q_local);
+    if (rc) return rc;
+    if (m < 1) return bad("m < 1");
+    if (!theta || !workspace || !state || !grad_state) return bad("NULL pointer");
+    Ws w = carve(dtype, n, d, p, q_local, (void*)workspace);
+    hipStream_t st = (hipStream_t)stream;
+    return dtype == LCGP_F64 ? do_condition_grad_prepare<double>(st, w, theta, state, m, grad_state)
+                             : do_condition_grad_prepare<float>(st, w, theta, state, m, grad_state);
+}
+
+int lcgp_condition_predict_grad_scratch_bytes(int dtype, int n, int q_local, int m, int n0, size_t* bytes) {
+    if (dtype != LCGP_F64 && dtype != LCGP_F32) return bad("dtype must be 0 (f64) or 1 (f32)");
+    if (n < 1 || q_local < 1) return bad("n, q_local must be >= 1");
+    if (m < 1) return bad("m < 1");
+    if (n0 < 1) return bad("n0 < 1");
+    if (!bytes) return bad("bytes is NULL");
+    *bytes = cond_predict_scratch(dtype, n, q_local, m, n0);
+    return 0;
+}
+
+int lcgp_condition_predict_grad(void* stream, int dtype, int kernel_id, int n, int d, int p, int q_local, const void* x,
+                                const void* sr, const double* theta, const void* workspace, const void* state, int m,
+                                const void* xn, const void* grad_state, int n0, const void* x0, void* scratch, size_t scratch_bytes,
+                                double* ghat, double* gvar, double* dghat, double* dgvar, int out_stride) {
+    int rc = check_common(dtype, n, d, p, q_local, kernel_id);
+    if (rc) return rc;
+    if (m < 1) return bad("m < 1");
+    if (n0 < 1) return bad("n0 < 1");
+    if (!x || !theta || !workspace || !state || !xn || !grad_state || !x0 || !scratch || !ghat || !gvar || !dghat || !dgvar)
+        return bad("NULL pointer");
+    if (out_stride != 0 && out_stride < n0) return bad("out_stride must be 0 (= n0) or >= n0");
+    if (scratch_bytes < cond_predict_scratch(dtype, n, q_local, m, n0))
+        return bad("scratch is smaller than lcgp_condition_predict_grad_scratch_bytes(dtype, n, q_local, m, n0)");
+    const int ldo = out_stride ? out_stride : n0;
+    Ws w = carve(dtype, n, d, p, q_local, (void*)workspace);
+    w.kern = kernel_id;
+    hipStream_t st = (hipStream_t)stream;
+    return dtype == LCGP_F64
+               ? do_condition_predict_grad<double>(st, w, x, sr, theta, state, m, xn, grad_state, n0, x0, scratch, ghat, gvar, dghat,
+                                                   dgvar, ldo)
+               : do_condition_predict_grad<float>(st, w, x, sr, theta, state, m, xn, grad_state, n0, x0, scratch, ghat, gvar, dghat,
+                                                  dgvar, ldo);
 }
 
 int lcgp_loo(void* stream, int dtype, int n, int d, int p, int q_local, const void* sr, const double* theta,

@@ -639,6 +639,54 @@ class HotPathEngine:
                     "lcgp_condition_predict")
             return out
 
+    def _condition_grad_state(self, state):
+        """the grad state of the view `state` (w = L_S^-T v and z' per local component: lcgp_condition_grad_prepare), built on
+        first use and kept with the view's state"""
+        torch = self.torch
+        gs = state.get('grad')
+        if gs is None:
+            m = state['m']
+            gs = torch.empty(self._nbytes("lcgp_condition_grad_state_bytes", self.dtype, self.n, self.q_local, m),
+                             dtype=torch.uint8, device=self.device)
+            _hip.check(self.lib.lcgp_condition_grad_prepare(
+                self._stream(), self.dtype, self.n, self.d, self.p, self.q_local, self._p(self.theta_dev), self._p(self.workspace),
+                self._p(state['state']), m, self._p(gs)), "lcgp_condition_grad_prepare")
+            state['grad'] = gs
+        return gs
+
+    def condition_predict_grad_block(self, state, x0s):
+        """(block, jac) float64 DEVICE tensors of the view `state` (condition_begin) at standardised x0s: block (2, q_local, n0)
+        = [ghat; gvar], bitwise condition_predict_block(state, x0s); jac (2, q_local, n0, d) = [dghat; dgvar], their
+        derivatives with respect to x0s (lcgp_condition_predict_grad: no nugget term, the gradient of the continuous surface,
+        also at the view's own new inputs).  Chunked as predict_grad_block is; the scratch is condition_predict_block's.  The
+        base factorisation must still be the one the state was built from."""
+        torch = self.torch
+        if not self.is_current(state['theta']):
+            raise RuntimeError("the conditioned view does not belong to the factorisation in the workspace")
+        x0s = np.ascontiguousarray(x0s, np.float64)
+        n0, d, m = x0s.shape[0], self.d, state['m']
+        assert x0s.ndim == 2 and x0s.shape[1] == d and n0 >= 1
+        chunk = min(n0, PREDICT_CHUNK)
+        with torch.cuda.device(self.device):
+            gs = self._condition_grad_state(state)
+            x0d = torch.as_tensor(x0s).to(self.device, self.tdtype).contiguous()
+            scratch = self._grow_scratch(
+                self._nbytes("lcgp_condition_predict_grad_scratch_bytes", self.dtype, self.n, self.q_local, m, chunk),
+                ("the conditioned gradient of %d new inputs per pass" % chunk,
+                 "%d components of %d x (n + m), twice" % (self.q_local, chunk), "lower lcgp_amd.engine.PREDICT_CHUNK"))
+            out = torch.empty((2, self.q_local, n0), dtype=torch.float64, device=self.device)
+            jac = torch.empty((2, self.q_local, n0, d), dtype=torch.float64, device=self.device)
+            st, xp, srp, thp, wsp = self._stream(), self._p(self.x), self._p(self.sr), self._p(self.theta_dev), self._p(self.workspace)
+            for lo in range(0, n0, chunk):
+                rows = min(chunk, n0 - lo)
+                _hip.check(self.lib.lcgp_condition_predict_grad(
+                    st, self.dtype, self.kernel_id, self.n, d, self.p, self.q_local, xp, srp, thp, wsp, self._p(state['state']), m,
+                    self._p(state['xn']), self._p(gs), rows, C.c_void_p(x0d.data_ptr() + lo * d * x0d.element_size()),
+                    self._p(scratch), scratch.numel(), C.c_void_p(out[0].data_ptr() + 8 * lo), C.c_void_p(out[1].data_ptr() + 8 * lo),
+                    C.c_void_p(jac[0].data_ptr() + 8 * lo * d), C.c_void_p(jac[1].data_ptr() + 8 * lo * d), n0),
+                    "lcgp_condition_predict_grad")
+            return out, jac
+
     # ------------------------------------------------------------------------------------------------
     # closed-form cross-validation at fixed parameters (lcgp_hip.h: lcgp_loo, lcgp_cv_gather / lcgp_cv_apply)
     def loo_block(self):

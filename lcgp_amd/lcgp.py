@@ -319,6 +319,53 @@ class ConditionedLCGP:
             return _t(ghat.copy()), _t(gvar.copy())
         return tuple(r.detach() for r in base._outputs(ghat, gvar))
 
+    def _latent_predict_grad(self, x0):
+        """ghat, gvar (q, n0) of the view and their Jacobians dghat, dgvar (q, n0, d) with respect to the STANDARDISED inputs,
+        for raw-scale x0: LCGP._latent_predict_grad on the view (one reduction gathers the components over the ranks)"""
+        base = self.base
+        x0s = base._x0_2d(x0, 'x0')
+        self._require_current()
+        n0, d = x0s.shape
+        loc = None
+        if self._engine is not None:
+            blk, jac = self._engine.condition_predict_grad_block(self._state, x0s)
+            loc = torch.cat([blk.permute(1, 0, 2).reshape(blk.shape[1], -1),
+                             jac.permute(1, 0, 2, 3).reshape(jac.shape[1], -1)], dim=1)
+        both = base._gather_components(loc, (2 * n0 + 2 * n0 * d,))
+        jac = both[:, 2 * n0:].reshape(int(base.q), 2, n0, d)
+        return both[:, :n0], both[:, n0:2 * n0], jac[:, 0], jac[:, 1]
+
+    def predict_grad(self, x0, latent=False):
+        """LCGP.predict_grad() of the conditioned model: (dypred, dypredvar, dyconfvar), each (p, n0, d) CPU float64 on the raw
+        input and output scales, the Jacobians of predict()'s outputs per point; dypredvar = dyconfvar.  latent=True:
+        (ghat, gvar, dghat, dgvar), (q, n0) and (q, n0, d), on the standardised scale (ghat / gvar are predict(latent=True)'s).
+        Equal, to rounding, to predict_grad() of a model built on the augmented data at the same parameters; nothing is
+        refactorised.  The gradient of the continuous prediction surface (same = 0), also at training inputs
+        and at the view's own new inputs.  RuntimeError when the view is stale."""
+        ghat, gvar, dghat, dgvar = self._latent_predict_grad(x0)
+        if latent:
+            return _t(ghat.copy()), _t(gvar.copy()), _t(dghat.copy()), _t(dgvar.copy())
+        dyp, dycv = self.base._output_jacobians(dghat, dgvar)
+        return _t(dyp), _t(dycv.copy()), _t(dycv)
+
+    def predict_differentiable(self, x0):
+        """(ypred, ypredvar, yconfvar) (p, n0) as predict() returns them, float64 on x0's device, differentiable with respect to
+        a requires_grad x0 (any device) through torch.autograd to first order, as LCGP.predict_differentiable(order=1): the
+        backward pass multiplies with the Jacobians of predict_grad() saved by the forward pass.  A double backward
+        (create_graph=True) raises."""
+        x0 = x0 if isinstance(x0, torch.Tensor) else torch.as_tensor(np.asarray(x0, F64))
+        return _ViewPredictFn.apply(x0, self)
+
+    def calibration(self, y_obs, obs_var, include_noise=True):
+        """LCGP.calibration() of the conditioned model: a CalibrationTarget for one field observation whose loglik(theta),
+        loglik_grad(theta) and loglik_differentiable(theta) draw ghat, gvar and their Jacobians from this view.  The output
+        map is the base model's, so arguments, checks, errors and the folding into M, b, c0 and lognorm are exactly
+        LCGP.calibration()'s.  The target is stale when the view is."""
+        self._require_current()
+        target = self.base.calibration(y_obs, obs_var, include_noise)
+        target._view = self
+        return target
+
     def _design_arguments(self, xc_s, match):
         """what the design queries check beyond the base model's: the view is current, and on the rep path no candidate equals
         one of the view's new inputs"""
@@ -370,6 +417,28 @@ class ConditionedLCGP:
             rows=lambda: eng.condition_select_rows(), condition=lambda j: eng.condition_select_condition(j))
 
 
+class _ViewPredictFn(torch.autograd.Function):
+    """ConditionedLCGP.predict_differentiable: _PredictFn on the view's latents -- forward = view.predict()'s outputs from one
+    lcgp_condition_predict_grad pass, backward = the per-point vector-Jacobian product with the saved output Jacobians"""
+
+    @staticmethod
+    def forward(ctx, x0, view):
+        base = view.base
+        ghat, gvar, dghat, dgvar = view._latent_predict_grad(x0.detach().cpu().to(torch.float64))
+        outs = base._outputs(ghat, gvar)
+        dyp, dycv = base._output_jacobians(dghat, dgvar)
+        ctx.x0_dtype, ctx.x0_device, ctx.x0_shape = x0.dtype, x0.device, x0.shape
+        ctx.jac = (torch.as_tensor(dyp), torch.as_tensor(dycv))
+        return tuple(o.to(x0.device) for o in outs[:3])
+
+    @staticmethod
+    def backward(ctx, g_ypred, g_ypredvar, g_yconfvar):
+        if torch.is_grad_enabled():         # create_graph=True: the saved Jacobians are constants, not a graph
+            raise RuntimeError('ConditionedLCGP.predict_differentiable supports first derivatives only: double backward '
+                               '(create_graph=True) is not available; use predict_grad() for the Jacobians')
+        return _PredictFn.backward(ctx, g_ypred, g_ypredvar, g_yconfvar)
+
+
 class _CalibFn(torch.autograd.Function):
     """CalibrationTarget.loglik_differentiable: forward = loglik_grad()'s log likelihood, backward = the per-row product with
     the saved gradient"""
@@ -405,11 +474,14 @@ class CalibrationTarget:
         self.M, self.b, self.c0, self.lognorm = M, b, float(c0), float(lognorm)
         self._u = model._get_flat().copy()
         self._consts = {}               # device -> (M, b, 1 / input range) as tensors there
+        self._view = None               # the ConditionedLCGP the latents are drawn from (ConditionedLCGP.calibration)
 
     def __repr__(self):
         return "CalibrationTarget(observed=%d of p=%d, q=%d)" % (int(self.observed.sum()), int(self.model.p), int(self.model.q))
 
     def _require_current(self):
+        if self._view is not None:
+            self._view._require_current()
         if not np.array_equal(self._u, self.model._get_flat()):
             raise RuntimeError('this CalibrationTarget is stale: the parameters of its model changed (or the model was refit) '
                                'after calibration(); call calibration() again')
@@ -427,7 +499,7 @@ class CalibrationTarget:
         m = self.model
         x0s = m._x0_2d(theta, 'theta')
         self._require_current()
-        blk, jac = m._calib_latent(x0s, grad)
+        blk, jac = m._calib_latent(x0s, grad, view=self._view)
         return m._calib_rows_device(blk, jac, *self._device_consts(blk.device), self.c0, self.lognorm, want_sens)
 
     def loglik(self, theta):
@@ -2023,22 +2095,30 @@ class LCGP:
         lognorm = logdet + int(obs.sum()) * float(np.log(2.0 * np.pi))
         return CalibrationTarget(self, obs, 0.5 * (M + M.T), b, c0, lognorm)
 
-    def _calib_latent(self, x0s, grad):
+    def _calib_latent(self, x0s, grad, view=None):
         """(blk (2, q, n0), jac (2, q, n0, d) or None): [ghat; gvar] and [dghat; dgvar] of ALL q components at the standardised
-        inputs x0s, float64 tensors where the row kernel runs.  One rank: the engine's blocks, read in place.  Several ranks:
-        the zero-padded blocks are summed over the ranks (disjoint components: exact) and copied back to every rank's device."""
-        eng = self._ensure_aux()
+        inputs x0s, float64 tensors where the row kernel runs; view: a ConditionedLCGP of this model whose latents are taken
+        instead of the fitted model's.  One rank: the engine's blocks, read in place.  Several ranks: the zero-padded blocks
+        are summed over the ranks (disjoint components: exact) and copied back to every rank's device."""
+        if view is None:
+            eng = self._ensure_aux()
+            grad_block = lambda x: eng.predict_grad_block(x)
+            block = lambda x: eng.predict_block(x, False)
+        else:
+            eng, st = view._engine, view._state
+            grad_block = lambda x: eng.condition_predict_grad_block(st, x)
+            block = lambda x: eng.condition_predict_block(st, x)
         if not _dist.use_collectives(self._group):
-            return eng.predict_grad_block(x0s) if grad else (eng.predict_block(x0s, False), None)
+            return grad_block(x0s) if grad else (block(x0s), None)
         n0, d = x0s.shape
         q = int(self.q)
         loc = None
         if eng is not None and grad:
-            blk, jac = eng.predict_grad_block(x0s)
+            blk, jac = grad_block(x0s)
             loc = torch.cat([blk.permute(1, 0, 2).reshape(blk.shape[1], -1),
                              jac.permute(1, 0, 2, 3).reshape(jac.shape[1], -1)], dim=1)
         elif eng is not None:
-            loc = eng.predict_block(x0s, False).permute(1, 0, 2).reshape(-1, 2 * n0)
+            loc = block(x0s).permute(1, 0, 2).reshape(-1, 2 * n0)
         both = self._gather_components(loc, (2 * n0 + (2 * n0 * d if grad else 0),))
         if eng is not None:
             dev = eng.device

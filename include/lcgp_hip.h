@@ -745,6 +745,41 @@ int lcgp_condition_select_condition(void* stream, int dtype, int kernel_id, int 
 int lcgp_condition_select_state(void* stream, int dtype, int n, int d, int q_local, int m, int n_ref, int n_cand, int size,
                                 int which, const void* scratch, size_t scratch_bytes, double* out);
 
+/* Joint posterior covariance of a conditioned view over new inputs (no counterpart in the reference): lcgp_predict_cov of the
+ * model lcgp_condition_prepare conditioned on m new inputs xn, without refactorising.  `state`, m, xn: as lcgp_condition_predict
+ * takes them; the workspace and the state are only read.  With the widened row U^_a = [U_a | T_a / sqrt(D_k)] of length
+ * K' = npad + mpad (lcgp_condition_vr above), for local component k and n0 new inputs x0 (standardised):
+ *     Sigma'_k = C00_k - D_k U^ U^^T  =  C00_k - D_k U_0 U_0^T - T T^T          (n0 x n0),   T = Sigma_0n L_S^-T
+ *     diag(Sigma'_k) = gvar'[k, :] of lcgp_condition_predict, to rounding
+ *     C00_k = the covariance kernel of x0 with itself, nugget on the diagonal (lcgp_predict_cov's)
+ * which equals lcgp_predict_cov(same = 0) of a model built on the augmented data at the same theta, to rounding.  Rows of x0
+ * that equal training inputs or conditioning inputs get the continuous surface (no match term, same = 0: lcgp_condition_predict's
+ * rule).  The result goes where lcgp_predict_cov puts it: the matrix slot of `cov_workspace`
+ * (lcgp_workspace_bytes(dtype, n0, d, p, q_local) bytes) holds Sigma'_k + tau_k I, tau_k = jitter * scale_k, lower tiles valid,
+ * identity on the padding; lcgp_potrf_logdet factors it there and lcgp_sample_latent draws from the factor, both unchanged (the
+ * mean of the draws: ghat' of lcgp_condition_predict).
+ * Launches, all local components each, one stream:
+ *   1. the row former of lcgp_condition_vr (no match) on blocks of at most 2048 rows of x0, into a slab of n0pad x K' elements
+ *      per component (n0pad = n0 rounded up to 128).  A last block of fewer than 128 rows is padded to 64 by the row former: the
+ *      up to 64 rows of the slab behind it are zeroed by one small launch (the product reads whole tiles);
+ *   2. C00_k into the matrix slot (the launch of lcgp_predict_cov);
+ *   3. ONE launch of the tile kernel over the lower tiles, C00_k -= D_k U^ U^^T (operand mode OP_PRED_COV, 64 x 64 tiles, rows
+ *      K' apart, K = K': the instance lcgp_predict_cov runs with K = npad);
+ *   4. the diagonal: + tau_k on rows below n0, 1 on the padding (the launch of lcgp_predict_cov).
+ * scratch: lcgp_condition_predict_cov_scratch_bytes(dtype, n, q_local, m, n0) bytes =
+ *     q n0pad K' esz  +  q X npad esz  +  2 q X mpad esz  +  2 roundup256(q n0 8),      X = min(2048, pad(n0)),
+ * esz the element size, pad(v) = v rounded up to 128 (to 64 below 128), every part rounded up to 256 bytes; `scratch_bytes` is
+ * what the caller allocated and is checked before anything is enqueued.
+ * Products in the dtype, the row sums in double, fixed order, no atomics: the result is bitwise independent of the content of
+ * scratch and cov_workspace on entry, and of q_local in lcgp_condition_predict's sense (the state is what depends on it).
+ * Flops per component: those of lcgp_predict_cov (n0pad^2 npad + n0pad npad^2 / 2) plus 2 n0pad mpad npad + n0pad mpad^2 for
+ * the rows (Sigma_0n and T) and n0pad^2 mpad for the wider product. */
+int lcgp_condition_predict_cov_scratch_bytes(int dtype, int n, int q_local, int m, int n0, size_t* bytes /*host out*/);
+int lcgp_condition_predict_cov(void* stream, int dtype, int kernel_id, int n, int d, int p, int q_local,
+                               const void* x, const void* sr, const double* theta, const void* workspace,
+                               const void* state, int m, const void* xn, int n0, const void* x0,
+                               void* scratch, size_t scratch_bytes, void* cov_workspace, double jitter);
+
 /* Calibration rows (no counterpart in the reference): the log density of ONE observation vector of the outputs given the
  * latent prediction of each of n0 inputs, and its derivatives.  With Phi_s the (scaled) output map restricted to the observed
  * outputs, t the centred observation and Lambda the input-independent part of the covariance (noise + observation covariance),

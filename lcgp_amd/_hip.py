@@ -114,6 +114,9 @@ SIGNATURES = {
     "lcgp_condition_select_picks": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _vp, C.c_size_t, C.POINTER(_vp)]),
     "lcgp_condition_select_condition": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, C.c_size_t]),
     "lcgp_condition_select_state": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, C.c_size_t, _vp]),
+    "lcgp_condition_predict_cov_scratch_bytes": (_i, [_i, _i, _i, _i, _i, C.POINTER(C.c_size_t)]),
+    "lcgp_condition_predict_cov": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, C.c_size_t,
+                                        _vp, _d]),
     "lcgp_calib_rows": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _d, _d, _vp, _vp, _vp, _vp]),
 }
 

@@ -4347,6 +4347,87 @@ int do_vr_prepare(hipStream_t st, const Ws& w, const void* x, const void* sr, co
                       (T*)(scratch + L.off_str));
 }
 
+// ---- joint posterior covariance of a conditioned view (lcgp_hip.h: lcgp_condition_predict_cov) ----
+// Sigma'_k = C00_k - D_k U^ U^^T on the widened rows U^_a = [U_a | T_a / sqrt(D_k)] of all n0 new inputs: the row former above on a
+// slab of n0pad x K' elements per component (n0pad = cov_pad(n0), what the factorisation expects), lcgp_predict_cov's prior,
+// product (K = K') and diagonal.  scratch: the slab, the row former's two work areas, and the ghat / gvar it writes.
+struct CondCovLay {
+    int n0pad, mpad, kp, xb;        // xb: rows of a pass of the row former
+    size_t uslab, xslab;
+    size_t off_U, off_X, off_ST, off_gh, off_gv, total;
+};
+
+inline CondCovLay cond_cov_carve(int dtype, int n, int q, int m, int n0) {
+    CondCovLay L;
+    const size_t esz = dtype == LCGP_F64 ? 8 : 4, npad = round_up(n, 2 * TS);
+    L.n0pad = cov_pad(n0);
+    L.mpad = cov_pad(m);
+    L.kp = (int)npad + L.mpad;
+    L.xb = min(VR_XBLK, predict_pad(n0));
+    L.uslab = (size_t)L.n0pad * L.kp;
+    L.xslab = (size_t)L.xb * npad;
+    size_t o = 0;
+    L.off_U = o; o = align256(o + (size_t)q * L.uslab * esz);
+    L.off_X = o; o = align256(o + (size_t)q * L.xslab * esz);
+    L.off_ST = o; o = align256(o + 2 * (size_t)q * L.xb * L.mpad * esz);
+    L.off_gh = o; o = align256(o + (size_t)q * n0 * sizeof(double));
+    L.off_gv = o; o = align256(o + (size_t)q * n0 * sizeof(double));
+    L.total = o;
+    return L;
+}
+
+// zeroes count elements at U + k slab for every component k: the rows of the slab behind the last pass of the row former
+template <typename T>
+__global__ __launch_bounds__(256) void cond_cov_zero_kernel(T* __restrict__ U, size_t slab, size_t count) {
+    const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e < count) U[(size_t)blockIdx.y * slab + e] = (T)0;
+}
+
+template <typename T>
+int do_condition_predict_cov(hipStream_t st, const Ws& w, const void* x, const void* sr, const double* theta, const VrView& cv,
+                             int n0, const void* x0, char* scratch, const Ws& cw, double jitter) {
+    const CondCovLay L = cond_cov_carve(sizeof(T) == 4 ? LCGP_F32 : LCGP_F64, w.n, w.q, cv.m, n0);
+    const int n0pad = L.n0pad, tw = w.d + 3 + w.p;
+    T* U = (T*)(scratch + L.off_U);
+    T* M = (T*)(cw.base + cw.off_M);
+    // the widened rows of all n0 inputs, no match term (same = 0: the continuous surface, also at training inputs and at the
+    // view's own inputs)
+    int rc = vr_form<T>(st, w, x, sr, theta, n0, x0, nullptr, (T*)(scratch + L.off_X), L.xslab, U, L.uslab,
+                        (double*)(scratch + L.off_gh), (double*)(scratch + L.off_gv), n0, &cv, (T*)(scratch + L.off_ST));
+    if (rc) return rc;
+    // the row former pads a last pass of fewer than 128 rows to 64, the slab is padded to 128: up to 64 rows behind it were not
+    // written, and the product reads them
+    const int rem = n0 % VR_XBLK, done = n0 - rem + (rem ? predict_pad(rem) : 0);
+    if (done < n0pad) {
+        const size_t count = (size_t)(n0pad - done) * L.kp;
+        hipLaunchKernelGGL((cond_cov_zero_kernel<T>), dim3((unsigned)((count + 255) / 256), w.q), dim3(256), 0, st,
+                           U + (size_t)done * L.kp, L.uslab, count);
+        CHECK_LAUNCH("cond_cov_zero_kernel");
+    }
+    // the prior C00 with the nugget on its diagonal, as do_predict_cov writes it
+    ThetaArg dummy;
+    memset(&dummy, 0, sizeof(dummy));
+    for_kern(w.kern, [&](auto kern) {
+        hipLaunchKernelGGL((cross_kernel<T, decltype(kern)::value>), dim3(n0pad / TS, n0pad / TS, w.q), dim3(256), 0, st, M, n0pad,
+                           n0, n0, w.d, (const T*)x0, (const T*)x0, dummy, theta, 1, (const T*)nullptr, n0pad, n0pad, tw, cw.mat,
+                           (const int*)nullptr);
+    });
+    CHECK_LAUNCH("cross_kernel");
+    GemmArgs h;
+    h.A = U; h.B = U; h.C = M;
+    h.sA = h.sB = L.uslab; h.sC = cw.mat; h.ldA = h.ldB = L.kp; h.ldC = n0pad;
+    h.p1 = tw; h.p2 = w.d + 2; h.p3 = 0;
+    h.theta = theta;
+    const int t64 = n0pad / TS;         // (64x64 tiles: do_predict_cov)
+    h.nb = t64; h.p0 = L.kp / TS;
+    rc = launch_gemm<T, OP_PRED_COV, 64>(st, h, t64 * (t64 + 1) / 2, w.q);
+    if (rc) return rc;
+    hipLaunchKernelGGL((cov_diag_kernel<T>), dim3((n0pad + 255) / 256, w.q), dim3(256), 0, st, M, cw.mat, n0, n0pad, theta, tw,
+                       w.d, jitter);
+    CHECK_LAUNCH("cov_diag_kernel");
+    return 0;
+}
+
 // out[k, c] = sum over the reference tiles, in ascending order, of the partials the OP_VR epilogue left
 __global__ __launch_bounds__(256) void vr_reduce_kernel(const double* __restrict__ part, int nrt, int ldp, int n_cand, int ldo,
                                                         double* __restrict__ out) {
@@ -7381,6 +7462,37 @@ int lcgp_condition_vr(void* stream, int dtype, int kernel_id, int n, int d, int 
                                              (char*)scratch, out, ldo, &cv)
                              : do_vr<float>(st, w, x, sr, theta, n_ref, x_ref, w_ref, n_cand, x_cand, match, cand_row0, r,
                                             (char*)scratch, out, ldo, &cv);
+}
+
+// ---- joint posterior covariance of a conditioned view (lcgp_hip.h) ----
+int lcgp_condition_predict_cov_scratch_bytes(int dtype, int n, int q_local, int m, int n0, size_t* bytes) {
+    int rc = check_common(dtype, n, 1, 1, q_local);
+    if (rc) return rc;
+    if ((rc = check_view(m))) return rc;
+    if (n0 < 1) return bad("n0 < 1");
+    if (!bytes) return bad("bytes is NULL");
+    *bytes = cond_cov_carve(dtype, n, q_local, m, n0).total;
+    return 0;
+}
+
+int lcgp_condition_predict_cov(void* stream, int dtype, int kernel_id, int n, int d, int p, int q_local, const void* x,
+                               const void* sr, const double* theta, const void* workspace, const void* state, int m, const void* xn,
+                               int n0, const void* x0, void* scratch, size_t scratch_bytes, void* cov_workspace, double jitter) {
+    int rc = check_common(dtype, n, d, p, q_local, kernel_id);
+    if (rc) return rc;
+    if ((rc = check_view(m))) return rc;
+    if (n0 < 1) return bad("n0 < 1");
+    if (!(jitter >= 0.0) || !__builtin_isfinite(jitter)) return bad("jitter must be finite and >= 0");
+    if (!x || !theta || !workspace || !state || !xn || !x0 || !scratch || !cov_workspace) return bad("NULL pointer");
+    if (scratch_bytes < cond_cov_carve(dtype, n, q_local, m, n0).total)
+        return bad("scratch is smaller than lcgp_condition_predict_cov_scratch_bytes(dtype, n, q_local, m, n0)");
+    Ws w = carve(dtype, n, d, p, q_local, (void*)workspace);
+    w.kern = kernel_id;
+    Ws cw = carve(dtype, n0, d, p, q_local, cov_workspace);
+    const VrView cv = view_of(dtype, n, q_local, state, m, xn);
+    hipStream_t st = (hipStream_t)stream;
+    return dtype == LCGP_F64 ? do_condition_predict_cov<double>(st, w, x, sr, theta, cv, n0, x0, (char*)scratch, cw, jitter)
+                             : do_condition_predict_cov<float>(st, w, x, sr, theta, cv, n0, x0, (char*)scratch, cw, jitter);
 }
 
 // the checks the five selection entries on a view share; *L receives the layout

@@ -482,25 +482,45 @@ class HotPathEngine:
     def form_cov(self, x0s, same=False, jitter=0.0):
         """Sigma_k + jitter scale_k I of the local components into the cov workspace for n0 = len(x0s) (lcgp_predict_cov);
         returns the workspace (asynchronous)."""
+        return self._form_cov(None, x0s, same, jitter)
+
+    def _form_cov(self, state, x0s, same, jitter):
+        """form_cov of the fitted model (state = None) or of the view `state` (condition_begin; lcgp_condition_predict_cov:
+        the same launches on rows widened to K' = npad + mpad, same = 0)"""
         torch = self.torch
         if self._theta_last is None:
             raise RuntimeError("predict_cov() needs a preceding evaluate() at the current parameters")
+        m, view, kp = self._view_args(state)
         x0s = np.ascontiguousarray(x0s, np.float64)
         n0 = x0s.shape[0]
         assert x0s.ndim == 2 and x0s.shape[1] == self.d and n0 >= 1
+        if state is None:
+            refusal = self._cov_refusal
+        else:
+            def refusal(what):
+                return (what + " on a conditioned view",
+                        "%d components of n0 x n0, 3 matrices each, and of n0 x K', K' = npad + mpad = %d" % (self.q_local, kp),
+                        "pass fewer new inputs")
         with torch.cuda.device(self.device):
             # the second workspace, carved for n = n0, whose matrix slot receives Sigma_k + tau_k I and then its factor
             # (lcgp_potrf_logdet): 3 q_local n0pad^2 elements (n0pad = n0 rounded up to 128), 3.2 GB at n0 = 4096, q_local = 8
             # in float64
             cws = self._workspace2('_cov_ws', n0, lambda: self._nbytes("lcgp_workspace_bytes", self.dtype, n0, self.d, self.p, self.q_local),
-                                   self._cov_refusal("the joint covariance of %d new inputs" % n0))
-            scratch = self._grow_scratch(self._nbytes("lcgp_predict_cov_scratch_bytes", self.dtype, self.n, self.q_local, n0),
-                                         self._cov_refusal("the scratch of the joint covariance"))
+                                   refusal("the joint covariance of %d new inputs" % n0))
+            if state is None:
+                nbytes = self._nbytes("lcgp_predict_cov_scratch_bytes", self.dtype, self.n, self.q_local, n0)
+            else:
+                nbytes = self._nbytes("lcgp_condition_predict_cov_scratch_bytes", self.dtype, self.n, self.q_local, m, n0)
+            scratch = self._grow_scratch(nbytes, refusal("the scratch of the joint covariance"))
             x0d = torch.as_tensor(x0s).to(self.device, self.tdtype).contiguous()
-            _hip.check(self.lib.lcgp_predict_cov(self._stream(), self.dtype, self.kernel_id, self.n, self.d, self.p, self.q_local,
-                                                 self._p(self.x), self._p(self.sr), self._p(self.theta_dev), self._p(self.workspace),
-                                                 n0, self._p(x0d), 1 if same else 0, self._p(scratch), self._p(cws), float(jitter)),
-                       "lcgp_predict_cov")
+            head = (self._stream(), self.dtype, self.kernel_id, self.n, self.d, self.p, self.q_local, self._p(self.x),
+                    self._p(self.sr), self._p(self.theta_dev), self._p(self.workspace))
+            if state is None:
+                _hip.check(self.lib.lcgp_predict_cov(*head, n0, self._p(x0d), 1 if same else 0, self._p(scratch), self._p(cws),
+                                                     float(jitter)), "lcgp_predict_cov")
+            else:
+                _hip.check(self.lib.lcgp_condition_predict_cov(*head, *view, n0, self._p(x0d), self._p(scratch), scratch.numel(),
+                                                               self._p(cws), float(jitter)), "lcgp_condition_predict_cov")
             return cws
 
     def fetch_cov(self, n0, which=0):
@@ -518,7 +538,16 @@ class HotPathEngine:
         """(q_local, n0, n0) float64 DEVICE tensor Sigma_k = C00_k - D_k U_k U_k^T of the local components (before any jitter
         or factorisation), from the factorisation of the last evaluate().  Memory: the cov workspace, 3 q_local n0pad^2
         elements, and a scratch of 2 q_local n0pad npad elements."""
-        self.form_cov(x0s, same, 0.0)
+        return self._predict_cov(None, x0s, same)
+
+    def condition_predict_cov(self, state, x0s):
+        """predict_cov of the view `state` (condition_begin): Sigma'_k = C00_k - D_k U^ U^^T on rows widened to K' = npad + mpad
+        (lcgp_condition_predict_cov), same = 0.  Memory: the cov workspace and a scratch of q_local n0pad K' elements plus the
+        row former's work areas.  The base factorisation must still be the one the state was built from."""
+        return self._predict_cov(state, x0s, False)
+
+    def _predict_cov(self, state, x0s, same):
+        self._form_cov(state, x0s, same, 0.0)
         return self.fetch_cov(len(x0s)).to(self.torch.float64)
 
     def factor_cov(self, n0):
@@ -538,12 +567,21 @@ class HotPathEngine:
         eps_k (S x n0 standard normals) comes from numpy's default_rng(seeds[i]) for local component i, so a caller that
         seeds by GLOBAL component gets draws independent of the sharding.  Raises numpy.linalg.LinAlgError naming the local
         components whose Sigma_k + tau_k I is not numerically positive definite (the `info` words); never returns NaNs."""
+        return self._sample_latent(None, x0s, S, seeds, jitter, same)
+
+    def condition_sample_latent(self, state, x0s, S, seeds, jitter=1e-10):
+        """sample_latent of the view `state` (condition_begin): draws ghat'_k + L_k eps_k, L_k L_k^T = Sigma'_k + jitter scale_k I,
+        with ghat' condition_predict_block's and Sigma' condition_predict_cov's; the factorisation, the seeding and the draws
+        are sample_latent's.  The base factorisation must still be the one the state was built from."""
+        return self._sample_latent(state, x0s, S, seeds, jitter, False)
+
+    def _sample_latent(self, state, x0s, S, seeds, jitter, same):
         torch = self.torch
         x0s = np.ascontiguousarray(x0s, np.float64)
         n0, S = x0s.shape[0], int(S)
         assert len(seeds) == self.q_local and S >= 1
-        ghat = self.predict_block(x0s, same)[0]
-        self.form_cov(x0s, same, jitter)
+        ghat = (self.predict_block(x0s, same) if state is None else self.condition_predict_block(state, x0s))[0]
+        self._form_cov(state, x0s, same, jitter)
         info = self.factor_cov(n0)
         if np.any(info != 0):
             bad = [(i, int(v)) for i, v in enumerate(info) if v != 0]

@@ -366,6 +366,43 @@ class ConditionedLCGP:
         target._view = self
         return target
 
+    def predict_latent_cov(self, x0):
+        """LCGP.predict_latent_cov() of the conditioned model: (q, n0, n0) CPU float64, the posterior covariance of the latent
+        components over the raw-scale inputs x0 GIVEN the base model's data and this view's new runs,
+            Sigma'_k = C00_k - D_k U_0 U_0^T - T T^T,   diag(Sigma'_k) = gvar'[k] of predict(latent=True)
+        (the base model's kernels on rows widened by the view's m columns; nothing is refactorised).  Equal, to
+        rounding, to predict_latent_cov() of a model built on the augmented data at the same parameters.  Rows of x0 that equal
+        training inputs or the view's own inputs follow predict()'s rule (same = 0).  RuntimeError when the view is stale;
+        ValueError when the buffers do not fit.  GPU memory: the base method's plus q_local n0pad K' elements, K' = npad + mpad."""
+        base = self.base
+        x0s = base._x0_2d(x0, 'x0')
+        self._require_current()
+        st = self._state
+        return base._latent_cov(x0s, lambda: self._engine, lambda eng: eng.condition_predict_cov(st, x0s))
+
+    def predict_jointcov(self, x0, outputs=None, include_noise=True):
+        """LCGP.predict_jointcov() of the conditioned model: (len(outputs), n0, n0) CPU float64 on the raw output scale, with
+        the base model's output map; its diagonal is this view's ypredvar (include_noise=True) or yconfvar (False).
+        RuntimeError when the view is stale.  Memory as predict_latent_cov."""
+        base = self.base
+        x0s = base._x0_2d(x0, 'x0')
+        self._require_current()
+        st = self._state
+        return base._jointcov(x0s, outputs, include_noise, lambda: self._engine, lambda eng: eng.condition_predict_cov(st, x0s))
+
+    def sample(self, x0, size=1, seed=None, include_noise=True, jitter=1e-10):
+        """LCGP.sample() of the conditioned model: (size, p, n0) CPU float64 draws of the outputs at x0 from the joint posterior
+        given the base model's data and this view's new runs, g_k = ghat'_k + L_k eps_k with L_k L_k^T = Sigma'_k + jitter scale_k I.
+        Seeding, the noise, the LinAlgError for a Sigma'_k + tau I that is not numerically positive definite and the memory
+        beyond predict_latent_cov's are LCGP.sample()'s: the draws do not depend on how the components are spread over ranks.
+        The factorisation runs in the dtype of the engine that holds the view's state.  RuntimeError when the view is stale."""
+        base = self.base
+        x0s = base._x0_2d(x0, 'x0')
+        self._require_current()
+        st = self._state
+        return base._sample(x0s, size, seed, include_noise, jitter, lambda: self._engine,
+                            lambda eng, S, seeds: eng.condition_sample_latent(st, x0s, S, seeds, jitter))
+
     def _design_arguments(self, xc_s, match):
         """what the design queries check beyond the base model's: the view is current, and on the rep path no candidate equals
         one of the view's new inputs"""
@@ -1529,8 +1566,13 @@ class LCGP:
         Memory: a second workspace of 3 q_local n0pad^2 elements per GPU (n0pad = n0 rounded up to 128; 3.2 GB at n0 = 4096,
         8 local components, float64) -- ValueError when it does not fit.  float32 models compute in float32."""
         x0s, same = self._standardise_x0(x0)
-        eng = self._ensure_aux()
-        loc = self._agree(lambda: None if eng is None else eng.predict_cov(x0s, same))
+        return self._latent_cov(x0s, self._ensure_aux, lambda eng: eng.predict_cov(x0s, same))
+
+    def _latent_cov(self, x0s, engine, cov):
+        """predict_latent_cov of this model or of a view of it: engine() is the engine that answers (None on a rank without
+        components), cov(engine) this rank's (q_local, n0, n0) share"""
+        eng = engine()
+        loc = self._agree(lambda: None if eng is None else cov(eng))
         return _t(self._gather_components(loc, (x0s.shape[0], x0s.shape[0])))
 
     def predict_jointcov(self, x0, outputs=None, include_noise=True):
@@ -1540,12 +1582,17 @@ class LCGP:
         the rep path).  Its diagonal is predict()'s ypredvar (include_noise=True) or yconfvar (False).  outputs: indices
         (default: all p).  Memory as predict_latent_cov."""
         x0s, same = self._standardise_x0(x0)
+        return self._jointcov(x0s, outputs, include_noise, self._ensure_aux, lambda eng: eng.predict_cov(x0s, same))
+
+    def _jointcov(self, x0s, outputs, include_noise, engine, cov):
+        """predict_jointcov of this model or of a view of it (engine, cov: as _latent_cov takes them): the output projection of
+        the local components' covariances, one all-reduce, the noise on the diagonal"""
         n0 = x0s.shape[0]
         outputs = list(range(int(self.p))) if outputs is None else [int(a) for a in np.atleast_1d(outputs)]
         W, noise, scale, _ = self._output_map()
         w2 = W[:, outputs] ** 2                                  # (q, P)
-        eng = self._ensure_aux()
-        sig = self._agree(lambda: None if eng is None else eng.predict_cov(x0s, same))
+        eng = engine()
+        sig = self._agree(lambda: None if eng is None else cov(eng))
         part = self._zeros_on_device((len(outputs), n0, n0))
         if sig is not None:
             wl = torch.as_tensor(w2[self._local_ks].T.copy(), device=sig.device)       # (P, q_local)
@@ -1569,6 +1616,12 @@ class LCGP:
         in particular (the factorisation runs in the dtype of the engine that holds the model's factorisation).
         Memory as predict_latent_cov, plus 2 q_local min(size, 4096) n0pad elements of scratch."""
         x0s, same = self._standardise_x0(x0)
+        return self._sample(x0s, size, seed, include_noise, jitter, self._ensure_aux,
+                            lambda eng, S, seeds: eng.sample_latent(x0s, S, seeds, jitter, same))
+
+    def _sample(self, x0s, size, seed, include_noise, jitter, engine, draw):
+        """sample of this model or of a view of it: engine() as _latent_cov takes it, draw(engine, S, seeds) this rank's
+        (q_local, S, n0) latent draws; the seed broadcast, the seeding by GLOBAL component, the output map and the noise"""
         n0, q, p, S = x0s.shape[0], int(self.q), int(self.p), int(size)
         if S < 1:
             raise ValueError('size must be >= 1')
@@ -1578,9 +1631,9 @@ class LCGP:
                                              None if self._engine is None else self._engine.device)[0])
         seed = int(seed)
         W, noise, scale, offset = self._output_map()
-        eng = self._ensure_aux()
+        eng = engine()
         seeds = [(seed, k) for k in self._local_ks] if eng is not None else []
-        loc = self._agree(lambda: None if eng is None else eng.sample_latent(x0s, S, seeds, jitter, same), jitter)
+        loc = self._agree(lambda: None if eng is None else draw(eng, S, seeds), jitter)
         g = self._gather_components(loc, (S, n0))
         ys = np.einsum('ka,ksi->sai', W, g)
         if include_noise:

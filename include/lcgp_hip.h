@@ -745,6 +745,47 @@ int lcgp_condition_select_condition(void* stream, int dtype, int kernel_id, int 
 int lcgp_condition_select_state(void* stream, int dtype, int n, int d, int q_local, int m, int n_ref, int n_cand, int size,
                                 int which, const void* scratch, size_t scratch_bytes, double* out);
 
+/* Gradient of the variance reduction on a CONDITIONED VIEW with respect to the candidate's location (standardised scale; no
+ * counterpart in the reference): lcgp_variance_reduction_grad of the model lcgp_condition_prepare conditioned on m new inputs
+ * xn, without refactorising.  `state`, m, xn as lcgp_condition_vr takes them; every other argument as
+ * lcgp_variance_reduction_grad's; the workspace and the state are only read.  Every candidate is a NEW input (no match).  With
+ * the widened rows U^_a = [U_a | T_a / sqrt(D_k)] of length K' = npad + mpad, Sigma', h' = Sigma'^h and den' as in lcgp_condition_vr,
+ * R' = N' / den' its result and S'[c, t] = w_t Sigma'_k(t, c):
+ *     t1[c, l]  = sum_t dC_l(c, t) S'[c, t]
+ *     G^        = S' U^_ref = [G_U | G_T / sqrt(D_k)]                           (n_cand x K')
+ *     Q_n       = G_T L_S^-1,      Q'   = (G_U - Q_n U_n) W_k
+ *     R_c       = T_c L_S^-1,      V'_c = (U_c - R_c U_n) W_k                   (lcgp_condition_predict_grad's R and V')
+ *     a1[c, l]  = D_k sum_j dc_l(c, j) sr_j Q'[c, j] + sum_a dc^x_l(c, xn_a) Q_n[c, a]
+ *     d_l h'(c) = -2 D_k sum_j dc_l(c, j) sr_j V'_c[c, j] - 2 sum_a dc^x_l(c, xn_a) R_c[c, a]        (taken as 0 where h' <= 0)
+ *     dout[k, c, l] = (2 (t1 - a1) - R' d_l h') / den'
+ * which equals lcgp_variance_reduction_grad of a model built on the augmented data at the same theta, to rounding.
+ * Runs behind lcgp_condition_vr_prepare (same scratch, sized by lcgp_condition_vr_grad_scratch_bytes), once per chunk of
+ * candidates: the launches of lcgp_condition_vr without a match (out: bitwise its result), P' = U^_cand U^_ref^T (K = K') and S'
+ * from it in place, t1 by the fused contraction over the reference points, G^ over K' columns, Q_n and R_c by the product of
+ * lcgp_condition_predict_grad's R on the dense L_S^-1 (rows K' apart in, mpad apart out) and one scaling launch each (the tails
+ * carry 1 / sqrt(D_k)), G_U - Q_n U_n in place and U_c - R_c U_n in a buffer of its own (the candidates' rows may be rows of
+ * U^_ref), Q' and V'_c by the product of lcgp_predict_grad, ONE fused contraction over the n + m columns with a matrix in the
+ * place of z in both segments (Q' beside V'_c over the training inputs, Q_n beside R_c over the conditioning inputs), and the
+ * combining launch.  64-row tiles for every product whose rows are candidates.  Products in the dtype; Sigma', sums and
+ * contractions in double, in a fixed order, no atomics, one stream: bitwise independent of q_local, of the scratch content and
+ * of how the candidates are split over calls.  lcgp_variance_reduction_grad runs the same code with K = npad and is bitwise what
+ * it was.
+ * scratch (`scratch_bytes` is checked before anything is enqueued): lcgp_condition_vr_scratch_bytes(dtype, n, q_local, m, n_ref,
+ *   n_cand) plus, with C = pad(n_cand), esz, npad, mpad, pad() as there and every part rounded up to 256 bytes:
+ *     q C pad128(n_ref) esz (S')  +  q C K' esz (G^ / V'_c)  +  q C npad esz (Q')  +  3 q n_cand d 8 (t1, a1, d h')
+ *     +  q C npad esz (U_c - R_c U_n)  +  2 q C mpad esz (Q_n, R_c)
+ *   With mpad = 0 the two sums are lcgp_variance_reduction_grad_scratch_bytes.  n_cand <= 65407 per call.
+ * Flops per component beyond lcgp_condition_vr: 4 C pad128(n_ref) K' (P', G^) + 2 C npad^2 (Q', V'_c) + 2 C mpad^2 (Q_n, R_c)
+ *   + 4 C mpad npad (the two products with U_n). */
+int lcgp_condition_vr_grad_scratch_bytes(int dtype, int n, int d, int q_local, int m, int n_ref, int n_cand,
+                                         size_t* bytes /*host out*/);
+int lcgp_condition_vr_grad(void* stream, int dtype, int kernel_id, int n, int d, int p, int q_local,
+                           const void* x, const void* sr, const double* theta, const void* workspace,
+                           const void* state, int m, const void* xn,
+                           int n_ref, const void* x_ref, const double* w_ref,
+                           int n_cand, const void* x_cand, int cand_row0, int r, void* scratch, size_t scratch_bytes,
+                           double* out, int out_stride, double* dout);
+
 /* Joint posterior covariance of a conditioned view over new inputs (no counterpart in the reference): lcgp_predict_cov of the
  * model lcgp_condition_prepare conditioned on m new inputs xn, without refactorising.  `state`, m, xn: as lcgp_condition_predict
  * takes them; the workspace and the state are only read.  With the widened row U^_a = [U_a | T_a / sqrt(D_k)] of length

@@ -107,6 +107,9 @@ SIGNATURES = {
     "lcgp_condition_vr_prepare": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, C.c_size_t]),
     "lcgp_condition_vr": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _i,
                                _vp, C.c_size_t, _vp, _i]),
+    "lcgp_condition_vr_grad_scratch_bytes": (_i, [_i, _i, _i, _i, _i, _i, _i, C.POINTER(C.c_size_t)]),
+    "lcgp_condition_vr_grad": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _i, _i,
+                                    _vp, C.c_size_t, _vp, _i, _vp]),
     "lcgp_condition_select_scratch_bytes": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, C.POINTER(C.c_size_t)]),
     "lcgp_condition_select_begin": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp,
                                          _i, _i, _i, _vp, C.c_size_t]),

@@ -2855,6 +2855,9 @@ constexpr int PG_ROWS = 32, PG_SL = 8;
 // conditioning inputs xn of a view -- weight 1 instead of sr_j, w in place of z, R (rows mpad long) in place of V, the factor
 // -2 in place of -2 D (D rides on the weights of the first segment) -- and z is the view's z' in double.  Same stages, same
 // lane / slice / wave order; per lane the training inputs in ascending j, then the conditioning inputs in ascending j.
+// COND + ZMAT (lcgp_condition_vr_grad): both segments carry a matrix in the place of z -- z (rows npad long, beside V) over
+// the training inputs with the weight D sr_j, zn (rows mpad long, laid out as R is) over the conditioning inputs with the
+// weight 1; zd and wv are not read.
 template <typename T>
 struct PgradCond {
     const double* zd;           // z' (q x npad doubles)
@@ -2868,8 +2871,8 @@ __device__ __forceinline__ void pgrad_body(const T* __restrict__ x0, int n0, con
                                            const T* __restrict__ sr, int n, int d, const double* __restrict__ theta,
                                            int tw, const T* __restrict__ z, int npad, const T* __restrict__ V,
                                            size_t slab, int ldo, double* __restrict__ dghat, double* __restrict__ dgvar,
-                                           const PgradCond<T>& cs) {
-    static_assert(!COND || (!ZMAT && !MEAN), "the second segment belongs to the plain contraction");
+                                           const PgradCond<T>& cs, const T* __restrict__ zn = nullptr) {
+    static_assert(!COND || !MEAN, "the second segment belongs to the contractions that carry the variance");
     constexpr bool WIDE = DD == DMAX;
     constexpr int JT = WIDE ? 16 : 32;                  // training inputs per LDS stage
     constexpr int XW = WIDE ? DWIDE + 3 : DD + 1;       // odd row length: the per-row reads of x0sh hit distinct banks;
@@ -2920,15 +2923,19 @@ __device__ __forceinline__ void pgrad_body(const T* __restrict__ x0, int n0, con
                 const bool in = i0 + i < n0 && jb + jj < ns;
                 vsh[i][jj] = !in ? 0.0 : seg2 ? (double)cs.R[(size_t)k * cs.rslab + (size_t)(i0 + i) * cs.mpad + jb + jj]
                                               : (double)Vk[(size_t)(i0 + i) * npad + jb + jj];
+                if constexpr (ZMAT)
+                    zsh[i][jj] = !in ? 0.0 : seg2 ? (double)zn[(size_t)k * cs.rslab + (size_t)(i0 + i) * cs.mpad + jb + jj]
+                                                  : (double)zk[(size_t)(i0 + i) * npad + jb + jj];
             } else if constexpr (!MEAN) vsh[i][jj] = (i0 + i < n0 && j0 + jj < n) ? (double)Vk[(size_t)(i0 + i) * npad + j0 + jj] : 0.0;
-            if constexpr (ZMAT) zsh[i][jj] = (i0 + i < n0 && j0 + jj < n) ? (double)zk[(size_t)(i0 + i) * npad + j0 + jj] : 0.0;
+            if constexpr (ZMAT && !COND) zsh[i][jj] = (i0 + i < n0 && j0 + jj < n) ? (double)zk[(size_t)(i0 + i) * npad + j0 + jj] : 0.0;
         }
         if (tid < JT) {
             const int j = jb + tid;
             if constexpr (COND) {
                 const double s = j < ns ? (seg2 ? 1.0 : (sr ? (double)sr[j] : 1.0)) : 0.0;
                 wsr[tid] = seg2 ? s : s * D;
-                wz[tid] = j < ns ? s * (seg2 ? cs.wv[(size_t)k * cs.mpad + j] : cs.zd[(size_t)k * npad + j]) : 0.0;
+                if constexpr (ZMAT) wz[tid] = seg2 ? s : s * D;
+                else wz[tid] = j < ns ? s * (seg2 ? cs.wv[(size_t)k * cs.mpad + j] : cs.zd[(size_t)k * npad + j]) : 0.0;
             } else {
                 const double s = j < n ? (sr ? (double)sr[j] : 1.0) : 0.0;      // (inputs beyond n weigh zero)
                 wsr[tid] = s;
@@ -3011,6 +3018,17 @@ __global__ __launch_bounds__(256) void pgrad_cond_kernel(const T* __restrict__ x
                                                          int tw, int npad, const T* __restrict__ V, size_t slab, int ldo,
                                                          double* __restrict__ dghat, double* __restrict__ dgvar, PgradCond<T> cs) {
     pgrad_body<T, DD, KERN, false, false, true>(x0, n0, x, sr, n, d, theta, tw, (const T*)nullptr, npad, V, slab, ldo, dghat, dgvar, cs);
+}
+
+// the contraction of lcgp_condition_vr_grad over the n + m columns with a matrix in the place of z in both segments: z beside V
+// (slabs `slab` apart, rows npad long), zn beside cs.R (slabs cs.rslab apart, rows cs.mpad long)
+template <typename T, int DD, int KERN>
+__global__ __launch_bounds__(256) void pgrad_cond_mat_kernel(const T* __restrict__ x0, int n0, const T* __restrict__ x,
+                                                             const T* __restrict__ sr, int n, int d, const double* __restrict__ theta,
+                                                             int tw, const T* __restrict__ z, int npad, const T* __restrict__ V,
+                                                             size_t slab, int ldo, double* __restrict__ dghat,
+                                                             double* __restrict__ dgvar, PgradCond<T> cs, const T* __restrict__ zn) {
+    pgrad_body<T, DD, KERN, true, false, true>(x0, n0, x, sr, n, d, theta, tw, z, npad, V, slab, ldo, dghat, dgvar, cs, zn);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -4501,24 +4519,33 @@ int check_vr(int n_ref, int n_cand) {
 // ---------------------------------------------------------------------------------------------------
 struct VrgLay {
     int crows, lds;                 // rows of the candidate slabs; row length of S (n_ref rounded up to 128)
-    size_t sslab, gslab;
-    size_t off_s, off_g, off_q, off_t, off_a, off_h, total;       // relative to the end of the variance reduction's own scratch
+    size_t sslab, gslab, qslab, nslab;
+    size_t off_s, off_g, off_q, off_t, off_a, off_h, off_u, off_qn, off_rc, total;    // relative to the end of the variance
+                                                                                      // reduction's own scratch
 };
 
-inline VrgLay vrg_carve(int dtype, int n, int d, int q, int n_ref, int n_cand) {
+// mpad > 0: the layout of a conditioned view (lcgp_condition_vr_grad) -- the rows of G are npad + mpad long (gslab), and behind
+// the base layout lie U' (rows npad long, qslab) and Q_n, R_c (rows mpad long, nslab).  mpad = 0 is the base model's layout,
+// byte for byte.
+inline VrgLay vrg_carve(int dtype, int n, int d, int q, int n_ref, int n_cand, int mpad = 0) {
     VrgLay G;
     const size_t esz = dtype == LCGP_F64 ? 8 : 4, npad = round_up(n, 2 * TS);
     G.crows = predict_pad(n_cand);
     G.lds = round_up(n_ref, 2 * TS);
     G.sslab = (size_t)G.crows * G.lds;
-    G.gslab = (size_t)G.crows * npad;
+    G.gslab = (size_t)G.crows * (npad + mpad);
+    G.qslab = (size_t)G.crows * npad;
+    G.nslab = (size_t)G.crows * mpad;
     size_t o = 0;
     G.off_s = o; o = align256(o + (size_t)q * G.sslab * esz);
     G.off_g = o; o = align256(o + (size_t)q * G.gslab * esz);
-    G.off_q = o; o = align256(o + (size_t)q * G.gslab * esz);
+    G.off_q = o; o = align256(o + (size_t)q * G.qslab * esz);
     G.off_t = o; o = align256(o + (size_t)q * n_cand * d * sizeof(double));
     G.off_a = o; o = align256(o + (size_t)q * n_cand * d * sizeof(double));
     G.off_h = o; o = align256(o + (size_t)q * n_cand * d * sizeof(double));
+    G.off_u = o; o = align256(o + (mpad ? (size_t)q * G.qslab * esz : 0));
+    G.off_qn = o; o = align256(o + (size_t)q * G.nslab * esz);
+    G.off_rc = o; o = align256(o + (size_t)q * G.nslab * esz);
     G.total = o;
     return G;
 }
@@ -4558,6 +4585,8 @@ __global__ __launch_bounds__(256) void vrg_sigma_kernel(T* __restrict__ S, size_
 }
 
 // dR[k, c, l] = (2 (t1 - D_k a1) - R_k(c) dh) / den_c; dh counts only where the candidate's gvar is positive
+// COND (a conditioned view): a1 arrives with D_k on its first segment's weights, 2 (t1 - a1)
+template <bool COND>
 __global__ __launch_bounds__(256) void vrg_combine_kernel(const double* __restrict__ R, int ldo, const double* __restrict__ gvc, int ldg,
                                                           const double* __restrict__ theta, int tw, int d, int nrep, int n_cand,
                                                           const double* __restrict__ t1, const double* __restrict__ a1,
@@ -4570,7 +4599,20 @@ __global__ __launch_bounds__(256) void vrg_combine_kernel(const double* __restri
     const double den = fmax(h, 0.0) + 1.0 / (D * (double)nrep);
     const size_t io = (size_t)k * ldo * d + e, is = (size_t)k * n_cand * d + e;
     const double dhv = h > 0.0 ? dh[is] : 0.0;
-    dR[io] = (2.0 * fma(-D, a1[is], t1[is]) - R[(size_t)k * ldo + c] * dhv) / den;
+    const double num = COND ? t1[is] - a1[is] : fma(-D, a1[is], t1[is]);
+    dR[io] = (2.0 * num - R[(size_t)k * ldo + c] * dhv) / den;
+}
+
+// a conditioned view: dst[k, r, j] = f_k src[k, r, j] for r < rows, j < cols (rows lds / ldd apart, slabs sslab / dslab apart),
+// f_k = sqrt(D_k) (scale: the tails T / sqrt(D_k) of the widened rows back to T's scale) or 1 (a copy)
+template <typename T>
+__global__ __launch_bounds__(256) void vrg_rows_kernel(const T* __restrict__ src, size_t sslab, int lds, T* __restrict__ dst,
+                                                       size_t dslab, int ldd, int cols, int scale,
+                                                       const double* __restrict__ theta, int tw, int d) {
+    const int j = blockIdx.x * 256 + threadIdx.x, r = blockIdx.y, k = blockIdx.z;
+    if (j >= cols) return;
+    const T v = src[(size_t)k * sslab + (size_t)r * lds + j];
+    dst[(size_t)k * dslab + (size_t)r * ldd + j] = scale ? (T)((double)v * sqrt(theta[(size_t)k * tw + d + 2])) : v;
 }
 
 // the fused contraction with a matrix in the place of z (outputs n0 rows apart per component)
@@ -4589,14 +4631,46 @@ int launch_pgrad_mat(hipStream_t st, const Ws& w, const void* x0, int n0, const 
     return 0;
 }
 
+// the same contraction on a conditioned view: over the n + m columns, Z beside V (rows npad long, slabs `slab` apart) and Zn
+// beside Rn (rows mpad long, slabs `nslab` apart)
+template <typename T>
+int launch_pgrad_cond_mat(hipStream_t st, const Ws& w, const void* x0, int n0, const void* x, const void* sr, const double* theta,
+                          const T* Z, const T* V, size_t slab, const VrView& cv, const T* Zn, const T* Rn, size_t nslab,
+                          double* dz, double* dv) {
+    PgradCond<T> cs;
+    cs.zd = nullptr; cs.wv = nullptr;
+    cs.xn = (const T*)cv.xn; cs.m = cv.m; cs.mpad = cv.mpad;
+    cs.R = Rn; cs.rslab = nslab;
+    const int wide = w.d > 16;
+    dim3 grid((n0 + PG_ROWS - 1) / PG_ROWS, w.q, wide ? (w.d + DMAX - 1) / DMAX : 1);
+    for_dim(w.d, [&](auto dd) {
+        for_kern(w.kern, [&](auto kern) {
+            hipLaunchKernelGGL((pgrad_cond_mat_kernel<T, decltype(dd)::value, decltype(kern)::value>), grid, dim3(256), 0, st,
+                               (const T*)x0, n0, (const T*)x, (const T*)sr, w.n, w.d, theta, w.d + 3 + w.p, Z, w.npad, V, slab, n0,
+                               dz, dv, cs, Zn);
+        });
+    });
+    CHECK_LAUNCH("pgrad_cond_mat_kernel");
+    return 0;
+}
+
+// On a conditioned view (cv; lcgp_condition_vr_grad) the rows of the two U are the widened rows U^ = [U | T / sqrt(D)] of length
+// K' = npad + mpad: P' = U^_cand U^_ref^T and S' as above, G^ = S' U^_ref = [G_U | G_T / sqrt(D)] over K' columns, then with the
+// state's dense L_S^-1 and U_n (the notation of lcgp_condition_predict_grad)
+//     Q_n = G_T L_S^-1,   Q' = (G_U - Q_n U_n) W,   R_c = T_c L_S^-1,   V'_c = (U_c - R_c U_n) W
+//     a1 = D sum_j dc_l sr_j Q' + sum_a dc^x_l Q_n,     d_l h' = -2 D sum_j dc_l sr_j V'_c - 2 sum_a dc^x_l R_c,
+//     d_l R' = (2 (t1 - a1) - R' d_l h') / den'
+// by ONE contraction over the n + m columns (pgrad_cond_mat_kernel).  U_c - R_c U_n goes into a buffer of its own: the
+// candidates' rows may be rows of U^_ref.
 template <typename T>
 int do_vr_grad(hipStream_t st, const Ws& w, const void* x, const void* sr, const double* theta, int n_ref, const void* x_ref,
                const double* w_ref, int n_cand, const void* x_cand, int row0, int r, char* scratch, double* out, int ldo,
-               double* dout) {
-    const int dt = w.esz == 8 ? LCGP_F64 : LCGP_F32;
-    const VrLay L = vr_carve(dt, w.n, w.q, n_ref, n_cand);
-    const VrgLay G = vrg_carve(dt, w.n, w.d, w.q, n_ref, n_cand);
-    int rc = do_vr<T>(st, w, x, sr, theta, n_ref, x_ref, w_ref, n_cand, x_cand, nullptr, row0, r, scratch, out, ldo);
+               double* dout, const VrView* cv = nullptr) {
+    const int dt = w.esz == 8 ? LCGP_F64 : LCGP_F32, mpad = cv ? cv->mpad : 0;
+    const VrLay L = vr_carve(dt, w.n, w.q, n_ref, n_cand, mpad);
+    const VrgLay G = vrg_carve(dt, w.n, w.d, w.q, n_ref, n_cand, mpad);
+    const int kp = L.kp, tw = w.d + 3 + w.p;
+    int rc = do_vr<T>(st, w, x, sr, theta, n_ref, x_ref, w_ref, n_cand, x_cand, nullptr, row0, r, scratch, out, ldo, cv);
     if (rc) return rc;
     // U, gvar and inputs of the candidates, where do_vr left or found them
     T* Ur = (T*)(scratch + L.off_uref);
@@ -4607,7 +4681,7 @@ int do_vr_grad(hipStream_t st, const Ws& w, const void* x, const void* sr, const
     int ldg, rows;
     if (row0 >= 0) {
         // rows of the reference set: whole 64-tiles only, which stay inside its slab (vr_carve)
-        Uc = Ur + (size_t)row0 * w.npad; sUc = L.uslab_r; rows = round_up(n_cand, TS);
+        Uc = Ur + (size_t)row0 * kp; sUc = L.uslab_r; rows = round_up(n_cand, TS);
         gvc = (const double*)(scratch + L.off_gvr) + row0; ldg = n_ref;
         xc = (const T*)x_ref + (size_t)row0 * w.d;
     } else {
@@ -4624,20 +4698,20 @@ int do_vr_grad(hipStream_t st, const Ws& w, const void* x, const void* sr, const
     // the rows of U_ref between the set and the k padding of S U_ref: zeros (those up to the padding of the passes that formed
     // the set are zeros already; the rest has never been written)
     if (G.lds > n_ref) {
-        hipError_t e = hipMemset2DAsync(Ur + (size_t)n_ref * w.npad, L.uslab_r * w.esz, 0,
-                                        (size_t)(G.lds - n_ref) * w.npad * w.esz, w.q, st);
+        hipError_t e = hipMemset2DAsync(Ur + (size_t)n_ref * kp, L.uslab_r * w.esz, 0,
+                                        (size_t)(G.lds - n_ref) * kp * w.esz, w.q, st);
         if (e != hipSuccess) return fail("hipMemset2DAsync", e);
     }
     GemmArgs h;
     h.A = Uc; h.B = Ur; h.C = S;
     h.sA = sUc; h.sB = L.uslab_r; h.sC = G.sslab;
-    h.ldA = h.ldB = w.npad; h.ldC = G.lds;
-    h.nb = 0; h.p0 = w.npad / TS; h.p1 = G.lds / TS; h.p2 = h.p3 = 0;
+    h.ldA = h.ldB = kp; h.ldC = G.lds;
+    h.nb = 0; h.p0 = kp / TS; h.p1 = G.lds / TS; h.p2 = h.p3 = 0;
     rc = launch_gemm<T, OP_VG_P, 64>(st, h, (rows / TS) * h.p1, w.q);
     if (rc) return rc;
     for_kern(w.kern, [&](auto kern) {
         hipLaunchKernelGGL((vrg_sigma_kernel<T, decltype(kern)::value>), dim3((G.lds + 255) / 256, rows, w.q), dim3(256), 0, st, S,
-                           G.sslab, G.lds, n_cand, n_ref, w.d, (const T*)xc, (const T*)x_ref, w_ref, theta, w.d + 3 + w.p);
+                           G.sslab, G.lds, n_cand, n_ref, w.d, (const T*)xc, (const T*)x_ref, w_ref, theta, tw);
     });
     CHECK_LAUNCH("vrg_sigma_kernel");
     // t1[c, l] = sum_t dC_l(c, t) S[c, t]   (a1 receives the same sum scaled: overwritten below)
@@ -4646,21 +4720,74 @@ int do_vr_grad(hipStream_t st, const Ws& w, const void* x, const void* sr, const
     GemmArgs g;
     g.A = S; g.B = Ur; g.C = Gb;
     g.sA = G.sslab; g.sB = L.uslab_r; g.sC = G.gslab;
-    g.ldA = G.lds; g.ldB = g.ldC = w.npad; g.p2 = g.p3 = 0;
+    g.ldA = G.lds; g.ldB = g.ldC = kp; g.p2 = g.p3 = 0;
     // 64x64 tiles for G, Q and V whatever the number of candidates: OP_PRED_V sums in a different order on 128-row tiles
     // (DESIGN 4.2), and a call's candidates may be any rows of a larger set
-    g.nb = w.nb; g.p0 = rows / TS; g.p1 = G.lds / TS;
+    g.nb = kp / TS; g.p0 = rows / TS; g.p1 = G.lds / TS;
     rc = launch_gemm<T, OP_VG_G, 64>(st, g, g.p0 * g.nb, w.q);
     if (rc) return rc;
     const T* W = (const T*)(w.base + w.off_W);
-    rc = launch_pred<T, OP_PRED_V>(st, Gb, W, Qb, G.gslab, w.mat, w.npad, rows, w.nb, w.q, 0, true);
+    if (!cv) {
+        rc = launch_pred<T, OP_PRED_V>(st, Gb, W, Qb, G.gslab, w.mat, w.npad, rows, w.nb, w.q, 0, true);
+        if (rc) return rc;
+        rc = launch_pred<T, OP_PRED_V>(st, Uc, W, Gb, sUc, w.mat, w.npad, rows, w.nb, w.q, G.gslab, true); // (G is free: V = U_cand W)
+        if (rc) return rc;
+        rc = launch_pgrad_mat<T>(st, w, xc, n_cand, x, sr, w.n, theta, Qb, Gb, w.npad, G.gslab, a1, dh);
+        if (rc) return rc;
+        hipLaunchKernelGGL(vrg_combine_kernel<false>, dim3((n_cand * w.d + 255) / 256, w.q), dim3(256), 0, st, (const double*)out,
+                           ldo, gvc, ldg, theta, tw, w.d, r, n_cand, (const double*)t1, (const double*)a1, (const double*)dh, dout);
+        CHECK_LAUNCH("vrg_combine_kernel");
+        return 0;
+    }
+    T* Up = (T*)(ex + G.off_u);
+    T* Qn = (T*)(ex + G.off_qn);
+    T* Rc = (T*)(ex + G.off_rc);
+    const T* Wi = (const T*)cv->Wi;
+    const T* Un = (const T*)cv->Un;
+    const size_t wimat = (size_t)mpad * mpad, unmat = (size_t)mpad * w.npad;
+    const dim3 tgrid((mpad + 255) / 256, rows, w.q), ugrid((w.npad + 255) / 256, rows, w.q);
+    // `tails` = the mpad columns behind the npad of a widened row, times L_S^-1 (OP_PRED_V on the dense L_S^-1, rows K' apart in,
+    // mpad apart out), then to T's scale; `minus_un` = C - A U_n in place (OP_COND_U, K = mpad); `times_w` = A W (OP_PRED_V)
+    auto tails = [&](const T* A, size_t sA, T* C) -> int {
+        GemmArgs a;
+        a.A = A + w.npad; a.B = Wi; a.C = C;
+        a.sA = sA; a.sB = wimat; a.sC = G.nslab; a.ldA = kp; a.ldB = a.ldC = mpad; a.p1 = a.p2 = a.p3 = 0;
+        a.nb = mpad / TS; a.p0 = rows / TS;
+        int e = launch_gemm<T, OP_PRED_V, 64>(st, a, a.p0 * a.nb, w.q);
+        if (e) return e;
+        hipLaunchKernelGGL((vrg_rows_kernel<T>), tgrid, dim3(256), 0, st, (const T*)C, G.nslab, mpad, C, G.nslab, mpad, mpad, 1, theta,
+                           tw, w.d);
+        CHECK_LAUNCH("vrg_rows_kernel");
+        return 0;
+    };
+    auto minus_un = [&](const T* A, T* C, size_t sC, int ldC) -> int {
+        GemmArgs a;
+        a.A = A; a.B = Un; a.C = C;
+        a.sA = G.nslab; a.sB = unmat; a.sC = sC; a.ldA = mpad; a.ldB = w.npad; a.ldC = ldC; a.p2 = a.p3 = 0;
+        a.nb = w.nb; a.p0 = rows / TS; a.p1 = mpad / TS;
+        return launch_gemm<T, OP_COND_U, 64>(st, a, a.p0 * a.nb, w.q);
+    };
+    auto times_w = [&](const T* A, size_t sA, int ldA, T* C) -> int {
+        GemmArgs a;
+        a.A = A; a.B = W; a.C = C;
+        a.sA = sA; a.sB = w.mat; a.sC = G.qslab; a.ldA = ldA; a.ldB = a.ldC = w.npad; a.p1 = a.p2 = a.p3 = 0;
+        a.nb = w.nb; a.p0 = rows / TS;
+        return launch_gemm<T, OP_PRED_V, 64>(st, a, a.p0 * a.nb, w.q);
+    };
+    // Q_n = G_T L_S^-1,  Q' = (G_U - Q_n U_n) W
+    if ((rc = tails(Gb, G.gslab, Qn))) return rc;
+    if ((rc = minus_un(Qn, Gb, G.gslab, kp))) return rc;
+    if ((rc = times_w(Gb, G.gslab, kp, Qb))) return rc;
+    // R_c = T_c L_S^-1,  V'_c = (U_c - R_c U_n) W into the slab of G (free now; rows npad long)
+    if ((rc = tails(Uc, sUc, Rc))) return rc;
+    hipLaunchKernelGGL((vrg_rows_kernel<T>), ugrid, dim3(256), 0, st, Uc, sUc, kp, Up, G.qslab, w.npad, w.npad, 0, theta, tw, w.d);
+    CHECK_LAUNCH("vrg_rows_kernel");
+    if ((rc = minus_un(Rc, Up, G.qslab, w.npad))) return rc;
+    if ((rc = times_w(Up, G.qslab, w.npad, Gb))) return rc;
+    rc = launch_pgrad_cond_mat<T>(st, w, xc, n_cand, x, sr, theta, Qb, Gb, G.qslab, *cv, Qn, Rc, G.nslab, a1, dh);
     if (rc) return rc;
-    rc = launch_pred<T, OP_PRED_V>(st, Uc, W, Gb, sUc, w.mat, w.npad, rows, w.nb, w.q, G.gslab, true);     // (G is free: V = U_cand W)
-    if (rc) return rc;
-    rc = launch_pgrad_mat<T>(st, w, xc, n_cand, x, sr, w.n, theta, Qb, Gb, w.npad, G.gslab, a1, dh);
-    if (rc) return rc;
-    hipLaunchKernelGGL(vrg_combine_kernel, dim3((n_cand * w.d + 255) / 256, w.q), dim3(256), 0, st, (const double*)out, ldo, gvc, ldg,
-                       theta, w.d + 3 + w.p, w.d, r, n_cand, (const double*)t1, (const double*)a1, (const double*)dh, dout);
+    hipLaunchKernelGGL(vrg_combine_kernel<true>, dim3((n_cand * w.d + 255) / 256, w.q), dim3(256), 0, st, (const double*)out, ldo,
+                       gvc, ldg, theta, tw, w.d, r, n_cand, (const double*)t1, (const double*)a1, (const double*)dh, dout);
     CHECK_LAUNCH("vrg_combine_kernel");
     return 0;
 }
@@ -7462,6 +7589,52 @@ int lcgp_condition_vr(void* stream, int dtype, int kernel_id, int n, int d, int 
                                              (char*)scratch, out, ldo, &cv)
                              : do_vr<float>(st, w, x, sr, theta, n_ref, x_ref, w_ref, n_cand, x_cand, match, cand_row0, r,
                                             (char*)scratch, out, ldo, &cv);
+}
+
+// ---- gradient of the variance reduction on a conditioned view (lcgp_hip.h: lcgp_condition_vr_grad) ----
+int lcgp_condition_vr_grad_scratch_bytes(int dtype, int n, int d, int q_local, int m, int n_ref, int n_cand, size_t* bytes) {
+    int rc = check_common(dtype, n, d, 1, q_local);
+    if (rc) return rc;
+    if ((rc = check_view(m))) return rc;
+    if ((rc = check_vr(n_ref, n_cand))) return rc;
+    if ((rc = check_vr_grad(n_cand))) return rc;
+    if (!bytes) return bad("bytes is NULL");
+    const int mpad = cov_pad(m);
+    *bytes = vr_carve(dtype, n, q_local, n_ref, n_cand, mpad).total + vrg_carve(dtype, n, d, q_local, n_ref, n_cand, mpad).total;
+    return 0;
+}
+
+int lcgp_condition_vr_grad(void* stream, int dtype, int kernel_id, int n, int d, int p, int q_local, const void* x, const void* sr,
+                           const double* theta, const void* workspace, const void* state, int m, const void* xn, int n_ref,
+                           const void* x_ref, const double* w_ref, int n_cand, const void* x_cand, int cand_row0, int r,
+                           void* scratch, size_t scratch_bytes, double* out, int out_stride, double* dout) {
+    int rc = check_common(dtype, n, d, p, q_local, kernel_id);
+    if (rc) return rc;
+    if ((rc = check_view(m))) return rc;
+    if ((rc = check_vr(n_ref, n_cand))) return rc;
+    if ((rc = check_vr_grad(n_cand))) return rc;
+    if (r < 1) return bad("r must be >= 1");
+    if (cand_row0 < -1) return bad("cand_row0 must be -1 or a row of the reference set");
+    if (cand_row0 >= 0) {
+        if ((long long)cand_row0 + n_cand > n_ref) return bad("cand_row0 + n_cand must be <= n_ref");
+        if (x_cand) return bad("cand_row0 >= 0: x_cand must be NULL");
+    } else if (!x_cand) {
+        return bad("NULL pointer");
+    }
+    if (!x || !theta || !workspace || !state || !xn || !x_ref || !w_ref || !scratch || !out || !dout) return bad("NULL pointer");
+    if (out_stride != 0 && out_stride < n_cand) return bad("out_stride must be 0 (= n_cand) or >= n_cand");
+    const int mpad = cov_pad(m);
+    if (scratch_bytes < vr_carve(dtype, n, q_local, n_ref, n_cand, mpad).total + vrg_carve(dtype, n, d, q_local, n_ref, n_cand, mpad).total)
+        return bad("scratch is smaller than lcgp_condition_vr_grad_scratch_bytes(dtype, n, d, q_local, m, n_ref, n_cand)");
+    const int ldo = out_stride ? out_stride : n_cand;
+    Ws w = carve(dtype, n, d, p, q_local, (void*)workspace);
+    w.kern = kernel_id;
+    const VrView cv = view_of(dtype, n, q_local, state, m, xn);
+    hipStream_t st = (hipStream_t)stream;
+    return dtype == LCGP_F64 ? do_vr_grad<double>(st, w, x, sr, theta, n_ref, x_ref, w_ref, n_cand, x_cand, cand_row0, r,
+                                                  (char*)scratch, out, ldo, dout, &cv)
+                             : do_vr_grad<float>(st, w, x, sr, theta, n_ref, x_ref, w_ref, n_cand, x_cand, cand_row0, r,
+                                                 (char*)scratch, out, ldo, dout, &cv);
 }
 
 // ---- joint posterior covariance of a conditioned view (lcgp_hip.h) ----

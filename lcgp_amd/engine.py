@@ -889,11 +889,21 @@ class HotPathEngine:
             return out
 
     def variance_reduction_grad_block(self, x_cand_s, x_ref_s, w, r):
+        return self._vr_grad_block(None, x_cand_s, x_ref_s, w, r)
+
+    def condition_variance_reduction_grad_block(self, state, x_cand_s, x_ref_s, w, r):
+        """variance_reduction_grad_block of the view `state` (condition_begin): R'_k(c) of the model conditioned on the view's runs
+        and its gradient (lcgp_condition_vr_prepare once, lcgp_condition_vr_grad per chunk: the same launches on rows widened to
+        K' = npad + mpad, and the contraction over the n + m columns).  The base factorisation must still be the one the state
+        was built from."""
+        return self._vr_grad_block(state, x_cand_s, x_ref_s, w, r)
+
+    def _vr_grad_block(self, state, x_cand_s, x_ref_s, w, r):
         """R (q_local, n_cand) and dR (q_local, n_cand, d) float64 DEVICE tensors: variance_reduction_block's R_k(c) with every
         candidate a new input (no match) and its gradient with respect to the candidate's standardised location, x_ref_s and
         w held constant (also with x_ref_s = None, where the reference set is a copy of the candidates)
-        (lcgp_variance_reduction_prepare once, lcgp_variance_reduction_grad per chunk of PREDICT_CHUNK candidates).  Raises
-        ValueError when the scratch does not fit in the free device memory."""
+        (lcgp_variance_reduction_prepare once, lcgp_variance_reduction_grad per chunk of PREDICT_CHUNK candidates; on a view
+        their lcgp_condition_vr_* siblings).  Raises ValueError when the scratch does not fit in the free device memory."""
         torch = self.torch
         if self._theta_last is None:
             raise RuntimeError("variance_reduction_grad() needs a preceding evaluate() at the current parameters")
@@ -905,10 +915,16 @@ class HotPathEngine:
         n_ref = x_ref_s.shape[0]
         assert x_ref_s.ndim == 2 and x_ref_s.shape[1] == d and n_ref >= 1 and len(w) == n_ref
         chunk = min(n_cand, PREDICT_CHUNK)
+        m, view, kp = self._view_args(state)
         with torch.cuda.device(self.device):
-            nbytes = self._nbytes("lcgp_variance_reduction_grad_scratch_bytes", self.dtype, self.n, d, self.q_local, n_ref, chunk)
-            scratch = self._grow_scratch(nbytes, ("the variance reduction gradient over %d reference points" % n_ref,
-                                                  "%d components of n_ref x n and %d candidates x (n_ref + 3 n)" % (self.q_local, chunk),
+            if state is None:
+                nbytes = self._nbytes("lcgp_variance_reduction_grad_scratch_bytes", self.dtype, self.n, d, self.q_local, n_ref, chunk)
+                detail = "%d components of n_ref x n and %d candidates x (n_ref + 3 n)" % (self.q_local, chunk)
+            else:
+                nbytes = self._nbytes("lcgp_condition_vr_grad_scratch_bytes", self.dtype, self.n, d, self.q_local, m, n_ref, chunk)
+                detail = ("%d components of n_ref x K' and %d candidates x (n_ref + 2 K' + 2 n), K' = npad + mpad = %d"
+                          % (self.q_local, chunk, kp))
+            scratch = self._grow_scratch(nbytes, ("the variance reduction gradient over %d reference points" % n_ref, detail,
                                                   "pass fewer reference points"))
             xr = torch.as_tensor(x_ref_s).to(self.device, self.tdtype).contiguous()
             xc = None if shared else torch.as_tensor(x_cand_s).to(self.device, self.tdtype).contiguous()
@@ -917,16 +933,18 @@ class HotPathEngine:
             dout = torch.empty((self.q_local, n_cand, d), dtype=torch.float64, device=self.device)
             st, xp, srp, thp, wsp, scp = (self._stream(), self._p(self.x), self._p(self.sr), self._p(self.theta_dev),
                                           self._p(self.workspace), self._p(scratch))
-            _hip.check(self.lib.lcgp_variance_reduction_prepare(st, self.dtype, self.kernel_id, self.n, d, self.p, self.q_local, xp, srp,
-                                                                thp, wsp, n_ref, self._p(xr), scp), "lcgp_variance_reduction_prepare")
+            # (the entries on a view take the view behind the workspace and the scratch size behind the scratch)
+            prepare, entry = (("lcgp_variance_reduction_prepare", "lcgp_variance_reduction_grad") if state is None else
+                              ("lcgp_condition_vr_prepare", "lcgp_condition_vr_grad"))
+            scs = (scp,) if state is None else (scp, scratch.numel())
+            head = (st, self.dtype, self.kernel_id, self.n, d, self.p, self.q_local, xp, srp, thp, wsp) + view
+            _hip.check(getattr(self.lib, prepare)(*head, n_ref, self._p(xr), *scs), prepare)
             for lo in range(0, n_cand, chunk):
-                m = min(chunk, n_cand - lo)
+                rows = min(chunk, n_cand - lo)
                 xcp = C.c_void_p(0) if shared else C.c_void_p(xc.data_ptr() + lo * d * xc.element_size())
-                _hip.check(self.lib.lcgp_variance_reduction_grad(st, self.dtype, self.kernel_id, self.n, d, self.p, self.q_local, xp,
-                                                                 srp, thp, wsp, n_ref, self._p(xr), self._p(wd), m, xcp,
-                                                                 lo if shared else -1, int(r), scp,
-                                                                 C.c_void_p(out.data_ptr() + 8 * lo), n_cand,
-                                                                 C.c_void_p(dout.data_ptr() + 8 * lo * d)), "lcgp_variance_reduction_grad")
+                _hip.check(getattr(self.lib, entry)(*head, n_ref, self._p(xr), self._p(wd), rows, xcp, lo if shared else -1, int(r),
+                                                    *scs, C.c_void_p(out.data_ptr() + 8 * lo), n_cand,
+                                                    C.c_void_p(dout.data_ptr() + 8 * lo * d)), entry)
             return out, dout
 
     # ------------------------------------------------------------------------------------------------

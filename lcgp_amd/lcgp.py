@@ -438,6 +438,35 @@ class ConditionedLCGP:
         delta = (W[:, outputs] ** 2).T @ R * (scale[outputs] ** 2)[:, None]
         return _t(delta)
 
+    def variance_reduction_grad(self, x_cand, x_ref=None, weights=None, outputs=None, replicates=1, latent=False):
+        """LCGP.variance_reduction_grad() of the conditioned model: (gain, dgain), CPU float64, this view's variance_reduction()
+        and its gradient with respect to the candidates' locations on the RAW input scale -- what a continuous ALC search needs
+        after condition().  Equal, to rounding, to variance_reduction_grad() of a model built on the augmented data at the same
+        parameters; nothing of size n is factorised (lcgp_condition_vr_grad).  Arguments, checks, shapes, the
+        output map and the full / rep rule for `replicates` are LCGP.variance_reduction_grad()'s.  x_ref and weights are
+        CONSTANTS, also with x_ref=None.  Every candidate is a NEW input (predict_grad()'s rule): on the rep path a candidate
+        equal to a base training input or to one of this view's own inputs gets the value and gradient of the continuous
+        surface and is not refused; away from such candidates gain is bitwise variance_reduction()'s.  RuntimeError when the
+        view is stale.  GPU memory: this view's variance_reduction()'s plus q_local min(n_cand, 2048) (n_ref + K' + 2 npad + 2 mpad)
+        elements, K' = npad + mpad -- ValueError when it does not fit."""
+        base = self.base
+        xc_s, xr_s, w, outputs, r, _ = base._vr_arguments(x_cand, x_ref, weights, outputs, replicates)
+        self._require_current()
+        n_cand, d = xc_s.shape
+        eng, st = self._engine, self._state
+        return base._vr_grad_result(None if eng is None else
+                                    lambda: eng.condition_variance_reduction_grad_block(st, xc_s, xr_s, w, r),
+                                    n_cand, d, outputs, latent)
+
+    def variance_reduction_differentiable(self, x_cand, x_ref=None, weights=None, outputs=None, replicates=1, latent=False):
+        """LCGP.variance_reduction_differentiable() of the conditioned model: variance_reduction_grad()'s gain as a tensor on
+        x_cand's device, differentiable with respect to a requires_grad x_cand through torch.autograd to first order (the
+        backward pass multiplies with the gradient the forward pass saved); x_ref and weights are constants.  A double backward
+        (create_graph=True) raises."""
+        x_cand = x_cand if isinstance(x_cand, torch.Tensor) else torch.as_tensor(np.asarray(x_cand, F64))
+        kwargs = dict(x_ref=x_ref, weights=weights, outputs=outputs, replicates=replicates, latent=latent)
+        return _VrFn.apply(x_cand, self, kwargs)
+
     def select_batch(self, x_cand, size, x_ref=None, weights=None, outputs=None, replicates=1, return_scores=False):
         """LCGP.select_batch() of the conditioned model: the next batch GIVEN the base model's data and this view's new runs --
         same contract, same returns (idx, gain[, scores]), same checks as there and as variance_reduction() of this view.  On
@@ -1927,10 +1956,16 @@ class LCGP:
         n_cand, d = xc_s.shape
         eng = self._ensure_aux()
 
+        return self._vr_grad_result(None if eng is None else lambda: eng.variance_reduction_grad_block(xc_s, xr_s, w, r),
+                                    n_cand, d, outputs, latent)
+
+    def _vr_grad_result(self, block, n_cand, d, outputs, latent):
+        """(gain, dgain) of variance_reduction_grad() from block() = (R, dR) of the local components (None: a rank without any):
+        one reduction gathers both, the gradient goes to the raw input scale, the output map folds the components"""
         def local():
-            if eng is None:
+            if block is None:
                 return None
-            R, dR = eng.variance_reduction_grad_block(xc_s, xr_s, w, r)
+            R, dR = block()
             return torch.cat([R, dR.reshape(dR.shape[0], -1)], dim=1)
         both = self._gather_components(self._agree(local), (n_cand + n_cand * d,))
         rng = (_np(self.x_max) - _np(self.x_min)).reshape(-1)

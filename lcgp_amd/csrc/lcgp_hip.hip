@@ -5312,6 +5312,7 @@ __global__ __launch_bounds__(256) void pdx_kernel(T* __restrict__ DX, size_t sla
     double v[4];
 #pragma unroll
     for (int a = 0; a < 4; ++a) v[a] = c_off * kern_c0<KERN>(poly[a], ssum[a]) * cs[j];      // (zero in the columns beyond n)
+    const bool incol = gj < n;                           // (beyond n: +0, not v h = -0 where h < 0)
     for (int d0 = 0; d0 < d; d0 += DMAX) {
         const int dc = d - d0 < DMAX ? d - d0 : DMAX;
         if (d > DMAX) {                                  // (a single chunk is still resident)
@@ -5324,7 +5325,8 @@ __global__ __launch_bounds__(256) void pdx_kernel(T* __restrict__ DX, size_t sla
             const int i = i0 + wv * 4 + a;
             if (i >= n0) continue;
             T* row = out + ((size_t)i * d + d0) * ld + gj;
-            for (int m = 0; m < dc; ++m) row[(size_t)m * ld] = (T)(v[a] * kern_h<KERN>(xr[wv * 4 + a][m] - xc[j][m]));
+            for (int m = 0; m < dc; ++m)
+                row[(size_t)m * ld] = incol ? (T)(v[a] * kern_h<KERN>(xr[wv * 4 + a][m] - xc[j][m])) : (T)0;
         }
     }
     if (blockIdx.y == gridDim.y - 1)

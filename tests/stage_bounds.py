@@ -2,7 +2,8 @@
 joint path (cross covariance X, U = X W^T, Sigma + tau I, its factor, the draws) and of the post-fit queries (V = U W and
 the input gradients of lcgp_predict_grad, leave-one-out, the k-fold gather / factor / inverse / apply, the integrated
 variance reduction) and of the conditioned view (lcgp_condition_prepare / lcgp_condition_predict: S and its factor, the dense
-L_S^-1, v, Sigma_0n, T and the corrected outputs).
+L_S^-1, v, Sigma_0n, T and the corrected outputs) and of the two second-order input queries (lcgp_predict_hess: DX, P = DX W^T,
+the packed Hessians; lcgp_predict_gradcov: dghat, Gamma and its weighted sum M).
 
 Every check compares one stage of the library with a plain float64 reference computed from THE LIBRARY'S OWN INPUT TO THAT
 STAGE (the fetched A for the Cholesky, the fetched L for L^-1, ...), so no bound carries a condition number.  Entries are
@@ -629,6 +630,38 @@ def pgrad_h(s, kernel):
     return s * (1.0 + s.abs()) / (3.0 + 3.0 * s.abs() + s * s)
 
 
+def pgrad_psi(s, kernel):
+    """psi = f'' / f of the 1-D factor f at the signed scaled distance s (a float64 tensor): d2 C0 / d x0_l^2 = C0 psi(s_l) /
+    ell_l^2 (include/lcgp_hip.h).  Matern-3/2: (|s| - 1) / (1 + |s|), -1 at s = 0 with a kink there; SE: s^2 - 1; Matern-5/2:
+    (s^2 - |s| - 1) / (3 + 3 |s| + s^2), -1/3 at s = 0."""
+    _known(kernel)
+    a = s.abs()
+    if kernel == "se":
+        return s * s - 1.0
+    if kernel == "matern32":
+        return (a - 1.0) / (1.0 + a)
+    return (s * s - a - 1.0) / (3.0 + 3.0 * a + s * s)
+
+
+def pgrad_psi_err(s, kernel):
+    """(|d psi / d s|, k, abs) of the evaluation of psi in kern_psi, so that |d psi| <= u (|psi'| (m_l + |s|) + k |psi| + abs)
+    with m_l = (|x0_il| + |x_jl|) / ell_l and |ds| <= u (m_l + |s|) as in check_pgrad.
+      Matern-3/2: (a - 1) fast_rcp(1 + a): psi' = 2 / (1 + a)^2 (<= 2); the difference, the sum, fast_rcp within 2 u and the
+        product are five roundings, each relative to psi: k = 5.
+      SE: fma(s, s, -1): psi' = 2 s (NOT bounded by 1: the m_l weight is 2 |s|); one rounding: k = 1.
+      Matern-5/2: fma(a, a - 1, -1) fast_rcp(fma(a, a + 3, 3)): psi' = 4 a (a + 2) / (3 + 3 a + a^2)^2 (<= 0.26); the two fmas,
+        the sum a + 3, fast_rcp and the product are six roundings relative to psi (k = 6); the rounding of a - 1 is multiplied by
+        a and is relative to a |a - 1|, not to the numerator a^2 - a - 1, which vanishes at a = 1.618: abs = a |a - 1| / q."""
+    _known(kernel)
+    a = s.abs()
+    if kernel == "se":
+        return 2.0 * a, 1.0, torch.zeros_like(a)
+    if kernel == "matern32":
+        return 2.0 / (1.0 + a) ** 2, 5.0, torch.zeros_like(a)
+    q = 3.0 + 3.0 * a + a * a
+    return 4.0 * a * (a + 2.0) / (q * q), 6.0, a * (a - 1.0).abs() / q
+
+
 def check_pgrad(dghat, dgvar, x0, x, sr, th, z, V, kernel, dtype) -> Check:
     """dghat / dgvar (n0 x d) of lcgp_predict_grad against the contraction of include/lcgp_hip.h, in float64 from the rounded
     x0, x, sr and the library's own z (fetched) and V = U W (check_pgrad_v's stage):
@@ -654,8 +687,28 @@ def check_pgrad(dghat, dgvar, x0, x, sr, th, z, V, kernel, dtype) -> Check:
     plus the float64 floor.  m_l is not relative to |h_l|: x0 close to x_j (but not equal) leaves an absolute error of s.
     At dx = 0 (a training input among x0) both sides have s = 0 exactly, so h = 0.  Past the C0 cut-off the term itself is
     added (the library may return any c0 in [0, C0] there)."""
-    _known(kernel)
     dev = _dev(dghat, dgvar, z, V)
+    n0, d = np.asarray(x0).shape
+    gref, gbnd, vref, vbnd = _pgrad_tables(x0, x, sr, th, z, V, kernel, dtype, dev)
+    names = ["l%d" % l for l in range(d)]
+    cg = _worst_cols((_t(dghat, dev).reshape(n0, d) - gref).abs(), gbnd, ["dghat " + s for s in names])
+    cv = _worst_cols((_t(dgvar, dev).reshape(n0, d) - vref).abs(), vbnd, ["dgvar " + s for s in names])
+    return combine(cg, cv)
+
+
+def check_pgrad_mean(dghat, x0, x, sr, th, z, kernel, dtype) -> Check:
+    """the mean half of check_pgrad alone: dghat (n0 x d) of lcgp_predict_gradcov, whose pgrad_kernel<MEAN> launch runs the
+    same contraction without V.  Reference, bound and locations are check_pgrad's (one table, _pgrad_tables)."""
+    dev = _dev(dghat, z)
+    n0, d = np.asarray(x0).shape
+    gref, gbnd, _, _ = _pgrad_tables(x0, x, sr, th, z, None, kernel, dtype, dev)
+    return _worst_cols((_t(dghat, dev).reshape(n0, d) - gref).abs(), gbnd, ["dghat l%d" % l for l in range(d)])
+
+
+def _pgrad_tables(x0, x, sr, th, z, V, kernel, dtype, dev):
+    """(reference, bound) of dghat and of dgvar as check_pgrad's docstring derives them: four n0 x d float64 tensors, the
+    floor included in the bounds.  V = None leaves the variance half out (its two tensors are None)."""
+    _known(kernel)
     u = unit("float64")
     a = _t(rounded(x0, dtype), dev)
     b = _t(rounded(x, dtype), dev)
@@ -667,7 +720,7 @@ def check_pgrad(dghat, dgvar, x0, x, sr, th, z, V, kernel, dtype) -> Check:
     c0 = scale * (1.0 - nt) * c0
     s = _t(rounded(np.ones(n) if sr is None else sr, dtype), dev)
     pz = c0 * (s * _t(z, dev)[:n])[None, :]
-    pv = c0 * s[None, :] * _t(V, dev)[:n0, :n]
+    pv = None if V is None else c0 * s[None, :] * _t(V, dev)[:n0, :n]
     cm = cut.to(torch.float64)
     wgt = n + d + e + 4.0
     gref, gbnd, vref, vbnd = (torch.zeros(n0, d, dtype=torch.float64, device=dev) for _ in range(4))
@@ -678,13 +731,13 @@ def check_pgrad(dghat, dgvar, x0, x, sr, th, z, V, kernel, dtype) -> Check:
         t = wgt * h.abs() + (xa.abs()[:, None] + xb.abs()[None, :])
         gref[:, l] = -(pz * h).sum(dim=1) / ell[l]
         gbnd[:, l] = (C * u * (pz.abs() * t).sum(dim=1) + (cm * (pz * h).abs()).sum(dim=1)) / ell[l]
-        vref[:, l] = 2.0 * D * (pv * h).sum(dim=1) / ell[l]
-        vbnd[:, l] = 2.0 * abs(D) * (C * u * (pv.abs() * t).sum(dim=1) + (cm * (pv * h).abs()).sum(dim=1)) / ell[l]
+        if pv is not None:
+            vref[:, l] = 2.0 * D * (pv * h).sum(dim=1) / ell[l]
+            vbnd[:, l] = 2.0 * abs(D) * (C * u * (pv.abs() * t).sum(dim=1) + (cm * (pv * h).abs()).sum(dim=1)) / ell[l]
     fl = floor("float64", n)
-    names = ["l%d" % l for l in range(d)]
-    cg = _worst_cols((_t(dghat, dev).reshape(n0, d) - gref).abs(), gbnd + fl, ["dghat " + s for s in names])
-    cv = _worst_cols((_t(dgvar, dev).reshape(n0, d) - vref).abs(), vbnd + fl, ["dgvar " + s for s in names])
-    return combine(cg, cv)
+    if pv is None:
+        return gref, gbnd + fl, None, None
+    return gref, gbnd + fl, vref, vbnd + fl
 
 
 def check_loo(ghat, gvar, V, b, z, sr, th, dtype, d) -> Check:
@@ -982,3 +1035,195 @@ def check_cond_out(ghat, gvar, T, v, ghat0, gvar0, m) -> Check:
     vref = v0 - t2
     vb = w * (v0.abs() + t2) + fl
     return combine(worst((_t(ghat, dev) - gref).abs(), gb), worst((_t(gvar, dev) - vref).abs(), vb))
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# second-order input queries: lcgp_predict_hess (pdx_kernel -> OP_PRED_U on n0 d rows -> phess_gram_kernel -> phess_kernel) and
+# lcgp_predict_gradcov (pgrad_kernel<MEAN> -> pdx_kernel -> the same product -> gradcov_kernel -> gradcov_reduce_kernel).
+# P = DX W^T goes through check_cov_u(P, DX, W): its inner dimension is npad whatever the number of rows, so the rows_pad rows
+# of DX (n0 d rounded up to 64 / 128) need no wider count.  dghat of the second goes through check_pgrad_mean.
+# ----------------------------------------------------------------------------------------------------------------------
+def tri_names(d, prefix):
+    """names of the packed lower triangle: entry (l, m <= l) at l (l + 1) / 2 + m"""
+    return ["%s l%d m%d" % (prefix, l, m) for l in range(d) for m in range(l + 1)]
+
+
+def _second_order_parts(x0, x, sr, th, kernel, dev):
+    """shared float64 pieces from the ROUNDED x0, x, sr: c = c_off C0 (n0 x n), E, the cut-off mask (float64's: these kernels
+    evaluate c0 in double in both storage types), sr, and per dimension the signed scaled distances S, the absolute terms
+    Mx = (|x0_il| + |x_jl|) / ell_l and H = h(S): three n0 x n x d tensors (the largest objects; no n0 x n x d x d one)."""
+    a, b = _t(x0, dev), _t(x, dev)
+    n0, d = a.shape
+    n = b.shape[0]
+    ell, scale, nug, D, _ = split_theta(th, d)
+    nt = nug / (1.0 + nug)
+    c0, e, cut = kernel_parts(a, b, ell, kernel, "float64", dev)
+    c0 = scale * (1.0 - nt) * c0
+    s = _t(np.ones(n) if sr is None else sr, dev)
+    le = _t(ell, dev)
+    xa, xb = a / le, b / le
+    S = xa[:, None, :] - xb[None, :, :]
+    Mx = xa.abs()[:, None, :] + xb.abs()[None, :, :]
+    return c0, e, cut.to(torch.float64), s, S, Mx, pgrad_h(S, kernel), ell, scale * (1.0 - nt), D
+
+
+def check_pdx(DX, x0, x, sr, th, kernel, dtype) -> Check:
+    """DX (n0 d x n, one slab of the lcgp_predict_hess / lcgp_predict_gradcov scratch, row i d + l) against
+        DX[i d + l, j] = c_off C0_ij sr_j h_l(s_l),   s_l = x0_il / ell_l - x_jl / ell_l
+    in float64 from the rounded x0, x, sr.  Precision: pdx_kernel converts the stored inputs to double, forms everything in
+    double and rounds ONCE to the storage type at the store, in both storage types.  Counted from the source:
+      v = c_off kern_c0(poly, ssum) cs_j: C0 carries kernel_parts' float64 magnification E; c_off = scale (1 - nug / (1 + nug))
+        is four roundings, the two products two: (E + 6) u64 relative;
+      h: u64 (m_l + 5 |h|) (Matern-3/2), u64 (m_l / 3 + 7 |h|) (Matern-5/2), u64 (m_l + |h|) (SE: h = s), m_l = (|x0_il| + |x_jl|)
+        / ell_l the absolute term of check_pgrad (x0 close to x_j leaves an absolute error of s);
+      the product v h in double: one more; the store (T): one rounding of the storage type.
+    Library: u64 |v| ((E + 14) |h| + m_l) + u |DX|; the reference commits the float64 part again.  With C = 4 on top:
+        C u64 |v| ((E + 14) |h| + m_l) + 2 u |DX_ref| + floor(dtype, d),      and |DX_ref| itself past the C0 cut-off.
+    At a training input among x0, s = 0 exactly on both sides (the same two quotients), h = 0 and DX = 0 exactly: the bound
+    there is the floor alone.  (The padding -- columns n .. npad, rows n0 d .. rows_pad -- is asserted bitwise zero by the GPU
+    test: an exact statement, not a bound.)  Locations: (64-block of the row i d + l, 64-block of the column)."""
+    _known(kernel)
+    dev = _dev(DX)
+    n0, d = np.asarray(x0).shape
+    c0, e, cm, s, S, Mx, H, ell, _, _ = _second_order_parts(rounded(x0, dtype), rounded(x, dtype),
+                                                            None if sr is None else rounded(sr, dtype), th, kernel, dev)
+    n = c0.shape[1]
+    v = c0 * s[None, :]
+    ref = (v[:, :, None] * H).permute(0, 2, 1).reshape(n0 * d, n)
+    t = (v.abs()[:, :, None] * ((e[:, :, None] + 14.0) * H.abs() + Mx)).permute(0, 2, 1).reshape(n0 * d, n)
+    bound = C * unit("float64") * t + 2.0 * unit(dtype) * ref.abs() + floor(dtype, d)
+    bound = bound + cm[:, None, :].expand(n0, d, n).reshape(n0 * d, n) * ref.abs()
+    return worst((_t(DX, dev)[:n0 * d, :n] - ref).abs(), bound, lower=False)
+
+
+def check_phess(d2ghat, d2gvar, x0, x, sr, th, z, V, P, kernel, dtype) -> Check:
+    """d2ghat / d2gvar (n0 x d (d + 1) / 2, the packed lower triangles, entry (l, m <= l) at l (l + 1) / 2 + m) of
+    lcgp_predict_hess against include/lcgp_hip.h, in float64 from the rounded x0, x, sr and the library's own z (fetched),
+    V = U W (n0 x n, the first slabs of the scratch) and P = DX W^T (n0 d x n, row i d + l; the last slabs):
+        d2ghat[i, lm] =        sum_j c_ij kap_lm(i, j) sr_j z_j                     / (ell_l ell_m)
+        d2gvar[i, lm] = -2 D (sum_j c_ij kap_lm(i, j) sr_j V_ij + P_il . P_im)       / (ell_l ell_m)
+        kap_lm = h(s_l) h(s_m)  (l != m),   psi(s_l)  (l == m);   c = c_off C0.
+    Precision.  phess_kernel and phess_gram_kernel convert the stored x0, x, sr, z, V and P to double and compute in double in
+    both storage types: u is the FLOAT64 unit roundoff throughout; the storage-type roundings are those of the inputs, which the
+    reference shares or takes from the library.  Counted from the source, per term of the sum over j:
+      c0 = c_off kern_c0: E (kernel_parts, float64) + 4 (c_off) + 1; times wz_j = sr_j z_j or wsr_j V_ij: 2 more: E + 7;
+      l != m: kap = h_l h_m with |dh| <= u (m + 7 |h|) (check_pgrad; the largest of the three kernels) and the product:
+          |d kap| <= u (m_l |h_m| + m_m |h_l| + 15 |kap|);
+      l == m: kap = psi(s_l), |d psi| <= u (|psi'| (m_l + |s_l|) + k |psi| + abs), k <= 6 (pgrad_psi_err: the m_l weight of psi
+          is |psi'|, which is 2 |s| for SE and not bounded by 1);
+      the fma into the accumulator, the per-lane sums in ascending j, the half-wave shuffle and the four waves: at most n
+      roundings of the absolute terms; 1 / (ell_l ell_m) two roundings and its product one; d2gvar adds the Gram term, -2 D and
+      the same scaling: five.  Library: (n + E + 28) |term| + the m terms; the reference the same again; within C = 4 times
+          (n + d + E + 16) |c kap w_j| + |c w_j| (m_l |h_m| + m_m |h_l|)                          (l != m)
+          (n + d + E + 16) |c psi w_j| + |c w_j| (|psi'| (m_l + |s_l|) + abs)                     (l == m).
+      Past the C0 cut-off the term itself is added, as in check_pgrad.
+    The Gram term G_i[l, m] = P_il . P_im: n fmas in double from the storage-type P (16-byte loads and a tail, then the
+    butterfly of wave_sum: any order) -- C (n + 2) u64 |P_il| . |P_im|, scaled by 2 |D| / (ell_l ell_m) like the rest (the five
+    roundings behind it are within C (n + 2) for n >= 2 on top of the library's n + 6 and the reference's n).
+    Locations: (64-block of the new input, "d2ghat l<l> m<m>" / "d2gvar l<l> m<m>").  Loops over l, vectorised over m <= l."""
+    _known(kernel)
+    dev = _dev(d2ghat, d2gvar, z, V, P)
+    u = unit("float64")
+    n0, d = np.asarray(x0).shape
+    c0, e, cm, s, S, Mx, H, ell, _, D = _second_order_parts(rounded(x0, dtype), rounded(x, dtype),
+                                                            None if sr is None else rounded(sr, dtype), th, kernel, dev)
+    n = c0.shape[1]
+    tri = d * (d + 1) // 2
+    pz = c0 * (s * _t(z, dev)[:n])[None, :]
+    pv = c0 * s[None, :] * _t(V, dev)[:n0, :n]
+    Pr = _t(P, dev)[:n0 * d, :n].reshape(n0, d, n)
+    Pa = Pr.abs()
+    wgt = (n + d + e + 16.0)[:, :, None]
+    Ha = H.abs()
+    gref, gbnd, vref, vbnd = (torch.zeros(n0, tri, dtype=torch.float64, device=dev) for _ in range(4))
+    for l in range(d):
+        m1 = l + 1
+        kap = H[:, :, l:m1] * H[:, :, :m1]
+        t = wgt * kap.abs() + Mx[:, :, l:m1] * Ha[:, :, :m1] + Mx[:, :, :m1] * Ha[:, :, l:m1]
+        sl = S[:, :, l]
+        psi = pgrad_psi(sl, kernel)
+        dpsi, _, apsi = pgrad_psi_err(sl, kernel)
+        kap[:, :, l] = psi
+        t[:, :, l] = wgt[:, :, 0] * psi.abs() + dpsi * (Mx[:, :, l] + sl.abs()) + apsi
+        inv = 1.0 / (ell[l] * _t(ell[:m1], dev))
+        o = slice(l * (l + 1) // 2, l * (l + 1) // 2 + m1)
+        cz = torch.einsum("ij,ijm->im", pz, kap)
+        bz = C * u * torch.einsum("ij,ijm->im", pz.abs(), t) + torch.einsum("ij,ijm->im", cm * pz.abs(), kap.abs())
+        cv = torch.einsum("ij,ijm->im", pv, kap)
+        bv = C * u * torch.einsum("ij,ijm->im", pv.abs(), t) + torch.einsum("ij,ijm->im", cm * pv.abs(), kap.abs())
+        G = torch.einsum("ij,imj->im", Pr[:, l], Pr[:, :m1])
+        Gb = C * (n + 2.0) * u * torch.einsum("ij,imj->im", Pa[:, l], Pa[:, :m1])
+        gref[:, o] = cz * inv
+        gbnd[:, o] = bz * inv
+        vref[:, o] = -2.0 * D * (cv + G) * inv
+        vbnd[:, o] = 2.0 * abs(D) * (bv + Gb) * inv
+    fl = floor("float64", n)
+    cg = _worst_cols((_t(d2ghat, dev).reshape(n0, tri) - gref).abs(), gbnd + fl, tri_names(d, "d2ghat"))
+    cv = _worst_cols((_t(d2gvar, dev).reshape(n0, tri) - vref).abs(), vbnd + fl, tri_names(d, "d2gvar"))
+    return combine(cg, cv)
+
+
+GRADCOV_KAPPA = {"matern32": 1.0, "se": 1.0, "matern52": 1.0 / 3.0}      # -f''(0) of the 1-D factor
+
+
+def check_gradcov(gamma, dghat, x0, x, sr, th, z, P, kernel, dtype) -> Check:
+    """gamma (n0 x d (d + 1) / 2 packed as d2gvar is) and dghat (n0 x d) of lcgp_predict_gradcov.  dghat goes through
+    check_pgrad_mean (the mean half of check_pgrad: the same launch without V).  gamma against
+        Gamma[i, lm] = (delta_lm c_k kappa - D P_il . P_im) / (ell_l ell_m),   c_k = scale (1 - nt),   kappa = 1, 1, 1/3
+    in float64 from the library's own P (n0 d x n, the second slabs of the scratch).  gradcov_kernel works in double from the
+    storage-type P in both storage types (u = float64's).  Counted from the source: the dot product is n fmas and the
+    butterfly (n roundings, any order); D s, the difference, ell_l ell_m and the quotient four more; the prior c_k kappa is
+    scale (1 - nug / (1 + nug)) kappa, five roundings (the constant 1/3 half of one), and shares the last three.  Library:
+    (n + 4) |D| |P_il| . |P_im| + 8 c_k kappa; the reference the same in float64; with C = 4:
+        C u64 ((n + 2) |D| |P_il| . |P_im| + 5 delta_lm c_k kappa) / (ell_l ell_m) + floor.
+    Locations: (64-block of the new input, "gamma l<l> m<m>"), or check_pgrad's for dghat."""
+    _known(kernel)
+    dev = _dev(gamma, dghat, z, P)
+    u = unit("float64")
+    n0, d = np.asarray(x0).shape
+    n = np.asarray(x).shape[0]
+    ell, scale, nug, D, _ = split_theta(th, d)
+    prior = scale * (1.0 - nug / (1.0 + nug)) * GRADCOV_KAPPA[kernel]
+    tri = d * (d + 1) // 2
+    Pr = _t(P, dev)[:n0 * d, :n].reshape(n0, d, n)
+    Pa = Pr.abs()
+    ref, bnd = (torch.zeros(n0, tri, dtype=torch.float64, device=dev) for _ in range(2))
+    for l in range(d):
+        m1 = l + 1
+        inv = 1.0 / (ell[l] * _t(ell[:m1], dev))
+        dl = torch.zeros(m1, dtype=torch.float64, device=dev)
+        dl[l] = 1.0
+        o = slice(l * (l + 1) // 2, l * (l + 1) // 2 + m1)
+        G = torch.einsum("ij,imj->im", Pr[:, l], Pr[:, :m1])
+        Ga = torch.einsum("ij,imj->im", Pa[:, l], Pa[:, :m1])
+        ref[:, o] = (dl * prior - D * G) * inv
+        bnd[:, o] = C * u * ((n + 2.0) * abs(D) * Ga + 5.0 * dl * abs(prior)) * inv
+    cg = _worst_cols((_t(gamma, dev).reshape(n0, tri) - ref).abs(), bnd + floor("float64", n), tri_names(d, "gamma"))
+    return combine(cg, check_pgrad_mean(dghat, x0, x, sr, th, z, kernel, dtype))
+
+
+def check_gradcov_sum(M_after, M_before, gamma, w) -> Check:
+    """M (d (d + 1) / 2, one component) after lcgp_predict_gradcov with weights against M_before + sum_i w_i Gamma_i, from the
+    library's OWN gamma (n0 x d (d + 1) / 2) and the weights w (n0 float64).  gradcov_kernel multiplies w_i Gamma_i (one
+    rounding), sums the four waves of a workgroup, gradcov_reduce_kernel the workgroups in ascending order and adds the sum to
+    M: n0 + 1 roundings of the absolute terms in any order, and the last addition, relative to |M_after| <= |M_before| + sum:
+        C (n0 + 2) u64 sum_i |w_i Gamma_i| + u64 |M_before| + floor.
+    The last term is ONE rounding, so the reference may not commit one of its own there: the sum is formed in float64 (its
+    error is within the first term) and M_after - M_before by an error-free TwoSum, so only sum-sized quantities are rounded."""
+    dev = _dev(M_after, M_before, gamma)
+    u = unit("float64")
+    g, ww = _t(gamma, dev), _t(w, dev)
+    n0 = g.shape[0]
+    ma, mb = _t(M_after, dev).reshape(-1), _t(M_before, dev).reshape(-1)
+    sref = (ww[:, None] * g).sum(dim=0)
+    sabs = (ww[:, None] * g).abs().sum(dim=0)
+    hi = ma - mb                                   # TwoSum(ma, -mb): hi + lo = ma - mb exactly
+    bv = hi - ma
+    lo = (ma - (hi - bv)) + (-mb - bv)
+    err = ((hi - sref) + lo).abs()
+    bound = C * (n0 + 2.0) * u * sabs + u * mb.abs() + floor("float64", n0)
+    r = err / bound
+    r = torch.where(torch.isnan(r), torch.full_like(r, math.inf), r)
+    i = int(torch.argmax(r))
+    d = int(round((math.sqrt(8 * r.numel() + 1) - 1) / 2))
+    return Check(float(r[i]), (tri_names(d, "M")[i],))

@@ -23,7 +23,15 @@ the three kernels, the full and the replicated path: every stage from X_n to the
 the wrong component or without the replicate counts, a K-stage left out of a far tile of Sigma_0n, a nugget term where a row of
 x0 equals a row of xn, an upper triangle of the dense L_S^-1 that was not zeroed, v of the wrong component, row sums over a
 non-zero padding column of T and a float32-accurate Sigma_0n each fail their own stage and none upstream of it.  A far tile of
-Sigma_0n off by 1e-6 relative, invisible in the units of the end-to-end test, fails cond_cross."""
+Sigma_0n off by 1e-6 relative, invisible in the units of the end-to-end test, fails cond_cross.
+
+The second-order input queries (lcgp_predict_hess, lcgp_predict_gradcov) are emulated in the kernels' blocked order (4 x 4 blocks
+of dimension pairs, 32-dimension chunks, four waves per workgroup), DX and P in the storage type: the three kernels, both
+precisions, the full and the replicated path pass pdx, p, phess, gradcov and gradcov_sum at d = 6 and d = 33.  psi on an
+off-diagonal block pair, a block past d written into a valid slot, a transposed packed index, the tail of the vector loads left
+out of the Gram term, a stale 32-dimension chunk in DX, the Matern-3/2 psi or kappa under Matern-5/2, a float32 reciprocal, the D
+of another component, M overwritten or a dead wave weighted, and a float32-accurate P each fail the check they name and no other.
+One small off-diagonal Hessian entry off by 1e-3 relative, invisible to max|err| / max|ref|, fails check_phess."""
 import numpy as np
 import pytest
 import torch
@@ -1396,3 +1404,350 @@ def test_cond_gap_far_tile_off_by_1e_6_is_invisible_end_to_end(cond64):
         assert eh < 1e-10 and ev < 1e-10
         c = _cond_checks(p, k, e, bad, ob)["cond_cross"]
         assert c.ratio > 1 and c.where == COND_FAR, c
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# second-order input queries (lcgp_predict_hess, lcgp_predict_gradcov): DX, P = DX W^T, the packed Hessians, Gamma and its
+# weighted sum M, emulated in the kernels' blocked order -- PH_B x PH_B block pairs (lb >= mb) with psi where lb == mb and
+# a == b, the DMAX chunks of pdx_kernel, four waves per workgroup and the workgroups ascending for M.  DX and P are stored in
+# the storage type (the product through _mm), everything else is float64, as in the library.  n = 303: odd (VN = 2 leaves a
+# tail of one column in float64) and 3 mod 4 (VN = 4 leaves three in float32).
+# ----------------------------------------------------------------------------------------------------------------------
+SO_N, SO_N0 = 303, 21                         # 21 = 5 workgroups of four waves + one: three dead waves in the last
+PH_B, DMAX = 4, 32
+SO_STAGES = ("pdx", "p", "phess", "gradcov", "gradcov_sum")
+_SO_CACHE = {}
+
+
+def _psi(sl, kernel, rcp=None):
+    """psi of the input Hessian, every kernel spelled out (numpy; rcp as in _h)"""
+    rcp = (lambda v: 1.0 / v) if rcp is None else rcp
+    a = np.abs(sl)
+    if kernel == "se":
+        return sl * sl - 1.0
+    if kernel == "matern32":
+        return (a - 1.0) * rcp(1.0 + a)
+    if kernel == "matern52":
+        return (a * (a - 1.0) - 1.0) * rcp(a * (a + 3.0) + 3.0)
+    raise ValueError(kernel)
+
+
+def _so_problem(dtype, d=6, kernel="matern32", rep=False, n0=SO_N0, seed=11, far=False):
+    key = (dtype, d, kernel, rep, n0, seed, far)
+    if key in _SO_CACHE:
+        return _SO_CACHE[key]
+    rng = np.random.default_rng(seed + d)
+    n = SO_N
+    x = rng.uniform(0.0, 1.0, (n, d))
+    Y = rng.standard_normal((P, n))
+    sr = np.sqrt(rng.integers(1, 6, n).astype(np.float64)) if rep else None
+    th = _theta(d, seed + 1)
+    e = _fit(x, Y, sr, th, dtype, kernel)
+    x0 = np.concatenate([x[:3], rng.uniform(-0.1, 1.1, (n0 - 3, d))])      # training inputs among x0: s = 0
+    if far:
+        x0[-1] = 12.0                                                         # one new input far outside the data
+    U = _r(_r(_cross(x0, x, sr, th, dtype, kernel), dtype) @ e["W"].T, dtype)
+    Vp = _r(U @ e["W"], dtype)
+    w = rng.uniform(0.0, 1.0, n0)
+    w[::4] = 0.0
+    w[1] = -0.3
+    Mb = rng.standard_normal(d * (d + 1) // 2)
+    p = dict(x=x, sr=sr, th=th, x0=x0, Vp=Vp, w=w, Mb=Mb, dtype=dtype, kernel=kernel, d=d, n=n, n0=n0, **e)
+    _SO_CACHE[key] = p
+    return p
+
+
+def _so_s(p, l, ell_of=None):
+    ell = sb.split_theta(p["th"], p["d"])[0]
+    le = ell[l if ell_of is None else ell_of]
+    a, b = _r(p["x0"], p["dtype"]), _r(p["x"], p["dtype"])
+    return a[:, l][:, None] / le - b[:, l][None, :] / le
+
+
+def _so_pdx(p, rcp=None, stale_chunk=False):
+    """DX (n0 d x n), rounded once to the storage type.  Defects: rcp (the reciprocal in h), stale_chunk (the chunks of DMAX
+    dimensions after the first are staged with the lengthscales of the chunk before them)"""
+    d, n0, n, dtype, kernel = p["d"], p["n0"], p["n"], p["dtype"], p["kernel"]
+    X = _cross(p["x0"], p["x"], p["sr"], p["th"], dtype, kernel)
+    DX = np.zeros((n0, d, n))
+    for d0 in range(0, d, DMAX):
+        for l in range(d0, min(d0 + DMAX, d)):
+            s = _so_s(p, l, l - DMAX if (stale_chunk and d0 > 0) else None)
+            DX[:, l, :] = X * _h(s, kernel, rcp)
+    return _r(DX.reshape(n0 * d, n), dtype)
+
+
+def _so_p(p, DX, as32=False):
+    """P = DX W^T on the tile kernel (storage type); defect as32: stored with float32 accuracy"""
+    Pm = np.asarray(_mm(DX, p["W"], p["dtype"]), np.float64)
+    return _r(Pm, "float32") if as32 else Pm
+
+
+def _so_pairs(d):
+    nblk = -(-d // PH_B)
+    return [(lb, mb) for lb in range(nblk) for mb in range(lb + 1)]
+
+
+def _so_gram(p, P, i_l, i_m, drop_tail):
+    """P_il . P_im for row-index arrays; drop_tail: the n % VN columns behind the 16-byte loads left out"""
+    n = p["n"]
+    vn = 4 if p["dtype"] == "float32" else 2
+    cols = n - n % vn if drop_tail else n
+    return np.einsum("ij,ij->i", P[i_l, :cols], P[i_m, :cols])
+
+
+def _so_phess(p, P, diag_ignored=False, past_d=False, transposed=False, drop_tail=False, psi_kernel=None, rcp=None):
+    """d2ghat, d2gvar (n0 x tri) block pair by block pair.  Defects: diag_ignored (psi on a == b of every block pair),
+    past_d (the guard l < d missing: the dimensions beyond d, which re-read row d - 1, are written at l (l + 1) / 2 + m, which
+    lies in the next input's row), transposed (the packed index m (m + 1) / 2 + l), drop_tail, psi_kernel (psi of another
+    kernel), rcp (the reciprocal in h and psi)"""
+    d, n0, dtype, kernel, th = p["d"], p["n0"], p["dtype"], p["kernel"], p["th"]
+    ell, scale, nug, Dk, _ = sb.split_theta(th, d)
+    s = np.ones(p["n"]) if p["sr"] is None else _r(p["sr"], dtype)
+    c0 = _cross(p["x0"], p["x"], None, th, dtype, kernel)
+    pz, pv = c0 * (s * p["z"])[None, :], c0 * s[None, :] * p["Vp"]
+    S = [_so_s(p, l) for l in range(d)]
+    Hh = [_h(S[l], kernel, rcp) for l in range(d)]
+    Ps = [_psi(S[l], psi_kernel or kernel, rcp) for l in range(d)]
+    tri = d * (d + 1) // 2
+    gh, gv = np.full((n0, tri), np.nan), np.full((n0, tri), np.nan)
+    rows = np.arange(n0) * d
+
+    def entry(l, m, use_psi):
+        kap = Ps[l] if use_psi else Hh[l] * Hh[m]
+        inv = 1.0 / (ell[l] * ell[m])
+        G = _so_gram(p, P, rows + l, rows + m, drop_tail)
+        return (pz * kap).sum(axis=1) * inv, -2.0 * Dk * ((pv * kap).sum(axis=1) + G) * inv
+
+    for lb, mb in _so_pairs(d):
+        for a in range(PH_B):
+            for b in range(PH_B):
+                l, m = lb * PH_B + a, mb * PH_B + b
+                use_psi = a == b and (lb == mb or diag_ignored)
+                if l < d and m <= l:
+                    o = m * (m + 1) // 2 + l if transposed else l * (l + 1) // 2 + m
+                    gh[:, o], gv[:, o] = entry(l, m, use_psi)
+                elif past_d and l >= d and m <= l:
+                    o = l * (l + 1) // 2 + m - tri
+                    if o < tri:
+                        vh, vv = entry(d - 1, min(m, d - 1), use_psi and m >= d - 1)
+                        gh[1:, o], gv[1:, o] = vh[:-1], vv[:-1]
+    return gh, gv
+
+
+def _so_gradcov(p, P, kappa=None, Dk=None, drop_tail=False):
+    """Gamma (n0 x tri); defects: kappa, Dk (the D of another component), drop_tail"""
+    d, n0, th = p["d"], p["n0"], p["th"]
+    ell, scale, nug, D, _ = sb.split_theta(th, d)
+    D = D if Dk is None else Dk
+    prior = scale * (1.0 - nug / (1.0 + nug)) * (sb.GRADCOV_KAPPA[p["kernel"]] if kappa is None else kappa)
+    g = np.zeros((n0, d * (d + 1) // 2))
+    rows = np.arange(n0) * d
+    for lb, mb in _so_pairs(d):
+        for a in range(PH_B):
+            for b in range(PH_B):
+                l, m = lb * PH_B + a, mb * PH_B + b
+                if l < d and m <= l:
+                    G = _so_gram(p, P, rows + l, rows + m, drop_tail)
+                    g[:, l * (l + 1) // 2 + m] = ((prior if l == m else 0.0) - D * G) / (ell[l] * ell[m])
+    return g
+
+
+def _so_sum(p, gamma, overwrite=False, dead_weight=False):
+    """M after the weighted call: four waves per workgroup, the workgroups ascending, then M += sum.  Defects: overwrite,
+    dead_weight (a wave beyond n0 in the last workgroup adds the last input once more, with weight 1)"""
+    n0, w = p["n0"], p["w"]
+    s = np.zeros(gamma.shape[1])
+    for g0 in range(0, n0, 4):
+        red = []
+        for i in range(g0, g0 + 4):
+            if i < n0:
+                red.append(w[i] * gamma[i])
+            else:
+                red.append(1.0 * gamma[n0 - 1] if dead_weight else 0.0 * gamma[0])
+        s = s + (((red[0] + red[1]) + red[2]) + red[3])
+    return s if overwrite else p["Mb"] + s
+
+
+def _so_run(p, pdx=None, pp=None, phess=None, gradcov=None, gsum=None):
+    dtype, kernel = p["dtype"], p["kernel"]
+    a = (p["x0"], p["x"], p["sr"], p["th"])
+    DX = _so_pdx(p, **(pdx or {}))
+    Pm = _so_p(p, DX, **(pp or {}))
+    gh, gv = _so_phess(p, Pm, **(phess or {}))
+    gamma = _so_gradcov(p, Pm, **(gradcov or {}))
+    dghat = _pgrad(p["x0"], p["x"], p["sr"], p["th"], p["z"], p["Vp"], dtype, kernel)[0]
+    Ma = _so_sum(p, gamma, **(gsum or {}))
+    checks = dict(pdx=sb.check_pdx(DX, *a, kernel, dtype),
+                  p=sb.check_cov_u(Pm, DX, p["W"], dtype),
+                  phess=sb.check_phess(gh, gv, *a, p["z"], p["Vp"], Pm, kernel, dtype),
+                  gradcov=sb.check_gradcov(gamma, dghat, *a, p["z"], Pm, kernel, dtype),
+                  gradcov_sum=sb.check_gradcov_sum(Ma, p["Mb"], gamma, p["w"]))
+    return dict(DX=DX, P=Pm, gh=gh, gv=gv, gamma=gamma, dghat=dghat, Ma=Ma), checks
+
+
+def _so_only(checks, *failing):
+    """the stages listed in `failing` are above 1 and EVERY other stage is at or below 1"""
+    assert tuple(checks) == SO_STAGES
+    for stage in SO_STAGES:
+        if stage in failing:
+            assert checks[stage].ratio > 1.0, (stage, checks[stage])
+        else:
+            assert checks[stage].ratio <= 1.0, ("not named", stage, checks[stage])
+
+
+@pytest.mark.parametrize("d", [6, 33])
+@pytest.mark.parametrize("rep", [False, True], ids=["full", "rep"])
+@pytest.mark.parametrize("kernel", KERNELS)
+@pytest.mark.parametrize("dtype", ["float64", "float32"])
+def test_emulated_second_order_paths_pass_every_stage(dtype, kernel, rep, d):
+    p = _so_problem(dtype, d=d, kernel=kernel, rep=rep, n0=SO_N0 if d == 6 else 10)
+    r, checks = _so_run(p)
+    print("second order, emulated, %s %s %s d=%d: %s"
+          % (dtype, kernel, "rep" if rep else "full", d, "  ".join("%s %.2e" % (st, c.ratio) for st, c in checks.items())))
+    for stage, c in checks.items():
+        assert c.ratio <= 1.0, (stage, c)
+    for i in range(3):                                       # x0 row i IS x row i: s = 0 and DX = 0 exactly at column i
+        assert np.all(r["DX"][i * d:(i + 1) * d, i] == 0.0)
+
+
+@pytest.mark.parametrize("kernel", KERNELS)
+def test_psi_and_h_against_autograd_of_the_1d_factor(kernel):
+    """pgrad_psi = f'' / f and pgrad_h = -f' / f of the 1-D factor f(s) = g(|s|), against torch autograd of g in a = |s| (g is
+    smooth on a >= 0; f'' (s) = g''(|s|) away from 0 and psi(0) is its one-sided limit: -1 for Matern-3/2, where f has a kink
+    in its second derivative), and the |psi'| of pgrad_psi_err against autograd of psi: float64, 1e-12"""
+    g = {"matern32": lambda a: (1.0 + a) * torch.exp(-a), "se": lambda a: torch.exp(-0.5 * a * a),
+         "matern52": lambda a: (1.0 + a + a * a / 3.0) * torch.exp(-a)}[kernel]
+    s = torch.as_tensor(np.concatenate([[0.0, 1e-300, -1e-300, 1.0, -1.0, 1.618033988749895],
+                                        np.random.default_rng(5).uniform(-9.0, 9.0, 200)]))
+    a = s.abs().clone().requires_grad_(True)
+    f = g(a)
+    f1, = torch.autograd.grad(f.sum(), a, create_graph=True)
+    f2, = torch.autograd.grad(f1.sum(), a)
+    psi, h = sb.pgrad_psi(s, kernel), sb.pgrad_h(s, kernel)
+    assert float((psi - (f2 / f).detach()).abs().max()) <= 1e-12
+    assert float((h + torch.sign(s) * (f1 / f).detach()).abs().max()) <= 1e-12
+    assert float(psi[0]) == {"matern32": -1.0, "se": -1.0, "matern52": -1.0 / 3.0}[kernel]
+    assert float((psi[1:3] - psi[0]).abs().max()) <= 1e-15    # continuous at 0 from both sides
+    sv = s.clone().requires_grad_(True)
+    dpsi, = torch.autograd.grad(sb.pgrad_psi(sv, kernel).sum(), sv)
+    got, k, ab = sb.pgrad_psi_err(s, kernel)
+    nz = s != 0
+    assert float((got - dpsi.abs())[nz].abs().max()) <= 1e-12
+    assert 1.0 <= k <= 6.0 and float(ab.min()) >= 0.0
+
+
+def test_unknown_kernel_name_is_an_error_in_the_second_order_checks():
+    p = _so_problem("float64")
+    r, _ = _so_run(p)
+    a = (p["x0"], p["x"], p["sr"], p["th"])
+    with pytest.raises(ValueError):
+        sb.pgrad_psi(torch.zeros(1, dtype=torch.float64), "matern")
+    with pytest.raises(ValueError):
+        sb.check_pdx(r["DX"], *a, "matern", "float64")
+    with pytest.raises(ValueError):
+        sb.check_phess(r["gh"], r["gv"], *a, p["z"], p["Vp"], r["P"], "matern", "float64")
+    with pytest.raises(ValueError):
+        sb.check_gradcov(r["gamma"], r["dghat"], *a, p["z"], r["P"], "matern", "float64")
+
+
+@pytest.mark.parametrize("dtype", ["float64", "float32"])
+def test_second_order_defect_1_psi_on_an_off_diagonal_block_pair(dtype):
+    """the diag flag ignored: block pair (1, 0) at d = 6 puts psi(s_4), psi(s_5) at (4, 0) and (5, 1)"""
+    checks = _so_run(_so_problem(dtype), phess=dict(diag_ignored=True))[1]
+    _so_only(checks, "phess")
+    assert checks["phess"].where[1].split(" ", 1)[1] in ("l4 m0", "l5 m1"), checks["phess"]
+
+
+@pytest.mark.parametrize("dtype", ["float64", "float32"])
+def test_second_order_defect_2_block_past_d_written_into_a_valid_slot(dtype):
+    """d = 6: block 1 reaches dimensions 6 and 7, which re-read row 5; without l < d they land in the next input's row"""
+    _so_only(_so_run(_so_problem(dtype), phess=dict(past_d=True))[1], "phess")
+
+
+@pytest.mark.parametrize("dtype", ["float64", "float32"])
+def test_second_order_defect_3_transposed_packed_index(dtype):
+    _so_only(_so_run(_so_problem(dtype), phess=dict(transposed=True))[1], "phess")
+
+
+@pytest.mark.parametrize("dtype", ["float64", "float32"])
+def test_second_order_defect_4_vector_load_tail_left_out_of_the_gram_term(dtype):
+    """n = 303: the last column (float64, VN = 2) or the last three (float32, VN = 4) missing from P_il . P_im"""
+    assert SO_N % 2 == 1 and SO_N % 4 == 3
+    p = _so_problem(dtype)
+    checks = _so_run(p, phess=dict(drop_tail=True), gradcov=dict(drop_tail=True))[1]
+    _so_only(checks, "phess", "gradcov")
+    assert checks["phess"].where[1].startswith("d2gvar") and checks["gradcov"].where[1].startswith("gamma")
+    _so_only(_so_run(p, phess=dict(drop_tail=True))[1], "phess")
+    _so_only(_so_run(p, gradcov=dict(drop_tail=True))[1], "gradcov")
+
+
+@pytest.mark.parametrize("dtype", ["float64", "float32"])
+def test_second_order_defect_5_second_pdx_chunk_with_the_lengthscales_of_the_first(dtype):
+    checks = _so_run(_so_problem(dtype, d=33, n0=10), pdx=dict(stale_chunk=True))[1]
+    _so_only(checks, "pdx")
+
+
+@pytest.mark.parametrize("dtype", ["float64", "float32"])
+def test_second_order_defect_6_matern52_with_the_matern32_psi_or_kappa(dtype):
+    p = _so_problem(dtype, kernel="matern52")
+    checks = _so_run(p, phess=dict(psi_kernel="matern32"))[1]
+    _so_only(checks, "phess")
+    l, m = (int(v[1:]) for v in checks["phess"].where[1].split(" ")[1:])
+    assert l == m, checks["phess"]
+    checks = _so_run(p, gradcov=dict(kappa=1.0))[1]
+    _so_only(checks, "gradcov")
+    assert checks["gradcov"].where[1].startswith("gamma"), checks["gradcov"]
+
+
+def test_second_order_defect_7_float32_reciprocal_in_h_and_psi():
+    """fast_rcp without its Newton steps, in the float64 path: in pdx_kernel (DX, and nothing behind it: P, G and Gamma are
+    checked from the library's own DX and P), and in phess_kernel"""
+    rcp32 = lambda v: np.float32(1.0) / v.astype(np.float32)      # noqa: E731
+    p = _so_problem("float64")
+    _so_only(_so_run(p, pdx=dict(rcp=rcp32))[1], "pdx")
+    _so_only(_so_run(p, phess=dict(rcp=rcp32))[1], "phess")
+    p = _so_problem("float64", kernel="matern52")
+    _so_only(_so_run(p, pdx=dict(rcp=rcp32))[1], "pdx")
+    _so_only(_so_run(p, phess=dict(rcp=rcp32))[1], "phess")
+
+
+@pytest.mark.parametrize("dtype", ["float64", "float32"])
+def test_second_order_defect_8_gamma_with_the_d_of_the_next_component(dtype):
+    p = _so_problem(dtype)
+    other = sb.split_theta(p["th"], p["d"])[3] * 1.7
+    _so_only(_so_run(p, gradcov=dict(Dk=other))[1], "gradcov")
+
+
+@pytest.mark.parametrize("dtype", ["float64", "float32"])
+def test_second_order_defect_9_m_overwritten_or_a_dead_wave_weighted(dtype):
+    p = _so_problem(dtype)
+    assert p["n0"] % 4 != 0 and np.any(p["Mb"] != 0)
+    _so_only(_so_run(p, gsum=dict(overwrite=True))[1], "gradcov_sum")
+    _so_only(_so_run(p, gsum=dict(dead_weight=True))[1], "gradcov_sum")
+
+
+def test_second_order_defect_10_float32_p_in_the_float64_check():
+    _so_only(_so_run(_so_problem("float64"), pp=dict(as32=True))[1], "p")
+
+
+def test_second_order_gap_small_hessian_entry_is_invisible_normwise():
+    """what the entry-by-entry bound closes: tests/test_gpu_predict_hess.py measures max|err| / max|ref| over the whole output
+    against LATENT_BAR = 1e-10.  An off-diagonal entry (l = 3, m = 1) of the Hessians of a new input far from the data, off by
+    1e-3 RELATIVE, stays far below that bar; check_phess is above 1 at that entry"""
+    LATENT_BAR = 1e-10
+    p = _so_problem("float64", far=True)
+    r, checks = _so_run(p)
+    for c in checks.values():
+        assert c.ratio <= 1.0, checks
+    i, o = p["n0"] - 1, 3 * 4 // 2 + 1
+    a = (p["x0"], p["x"], p["sr"], p["th"])
+    for name in ("gh", "gv"):
+        bad = dict(r, **{name: r[name].copy()})
+        assert abs(bad[name][i, o]) < 1e-8 * np.abs(r[name]).max() and bad[name][i, o] != 0
+        bad[name][i, o] *= 1 + 1e-3
+        nw = _normwise(bad[name], r[name])
+        print("gap %s: normwise %.3e (bar %.0e)" % (name, nw, LATENT_BAR))
+        assert nw < 1e-3 * LATENT_BAR
+        c = sb.check_phess(bad["gh"], bad["gv"], *a, p["z"], p["Vp"], r["P"], "matern32", "float64")
+        assert c.ratio > 1 and c.where == (i // TS, "%s l3 m1" % ("d2ghat" if name == "gh" else "d2gvar")), c

@@ -494,6 +494,43 @@ int lcgp_condition_predict(void* stream, int dtype, int kernel_id, int n, int d,
                            const void* state, int m, const void* xn, int n0, const void* x0,
                            void* scratch, size_t scratch_bytes, double* ghat, double* gvar, int out_stride);
 
+/* Box-averaged predictions of a conditioned view, and the covariance of every row's average with that of one reference row
+ * (what lcgp_predict_marginal is to lcgp_predict, on the view or on the fitted model).  `state`, m, xn: as
+ * lcgp_condition_predict takes them, or state = NULL, m = 0, xn = NULL for the fitted model; x0, mask, box: as
+ * lcgp_predict_marginal takes them.  Averaging over a box is linear, so it commutes with conditioning: with Xbar the masked
+ * cross rows against the training inputs and Cbar^x(x0, xn) the same masked rows against the view's inputs (no sr, no nugget
+ * term; their table I1 evaluated at xn, q_local d mpad doubles),
+ *     Ubar_0 = Xbar W^T        ghat, gvar: those of lcgp_predict_marginal, bitwise
+ *     Sigma_0n = Cbar^x(x0, xn) - D Ubar_0 U_n^T        Tbar = Sigma_0n L_S^-T
+ *     ghat' = ghat + Tbar v                             gvar' = gvar - rowsum(Tbar o Tbar)
+ * Launches without a view and without a reference row: exactly those of lcgp_predict_marginal.  On a view: the table kernel
+ * a second time over xn, then the masked rows against xn, OP_COND_CROSS, T and the row reduction as lcgp_condition_predict
+ * enqueues them.  A row with an EMPTY mask is bitwise the row of lcgp_condition_predict on the same tile size.
+ * Reference row (optional; it adds launches behind the pass and changes nothing in ghat / gvar):
+ *   ref_out != NULL: the widened row [Ubar_r | Tbar_r] of pass row ref_row (0 <= ref_row < n0) is copied to ref_out,
+ *     q_local x (npad + mpad) elements of the dtype (mpad = 0 without a view).
+ *   ref_in != NULL: such a widened row, with the row's d values ref_x (dtype; entries under its mask are never read) and mask
+ *     ref_mask (d bytes), all on the device.  gcov (q_local rows, out_stride apart as ghat) receives
+ *         gcov[k, i] = prior_k(i, r) - D_k Ubar_i . Ubar_r - Tbar_i . Tbar_r
+ *         prior_k(i, r) = scale_k (1 - nt_k) prod_l f_l  (ascending l):  f_l = kappa(|x0_il - ref_x_l| / ell_kl) where both rows
+ *         keep l, the box average of kappa at the kept value where one of them integrates l, I2[k, l] where both do
+ *     -- the covariance of the two averages of the CONTINUOUS surface (no nugget term, also between two rows with empty masks
+ *     at the same input).  One wave per row (marg_refcov_kernel): lanes stride the n columns of U, then the m columns of T,
+ *     sums in double in the fixed order of the row reductions; the prior is formed by lane 0 in double.
+ * A caller runs a one-row pass with ref_out first and its chunked passes with ref_in afterwards; both may be given at once.
+ * `scratch`: lcgp_condition_predict_marginal_scratch_bytes(dtype, n, d, q_local, m, n0) = with m = 0 that of
+ * lcgp_predict_marginal, otherwise lcgp_condition_scratch_bytes of a pass + 8 q_local d (npad + 1 + mpad); checked against
+ * `scratch_bytes`.  Fixed order, no atomics, one stream: bitwise independent of the scratch content on entry, of q_local in
+ * lcgp_condition_predict's sense and, between calls on the same tile size, of how a caller splits the rows. */
+int lcgp_condition_predict_marginal_scratch_bytes(int dtype, int n, int d, int q_local, int m, int n0, size_t* bytes /*host out*/);
+int lcgp_condition_predict_marginal(void* stream, int dtype, int kernel_id, int n, int d, int p, int q_local,
+                                    const void* x, const void* sr, const double* theta, const void* workspace,
+                                    const void* state /*or NULL*/, int m, const void* xn /*or NULL*/, int n0, const void* x0,
+                                    const unsigned char* mask, const double* box, void* scratch, size_t scratch_bytes,
+                                    double* ghat, double* gvar, int out_stride,
+                                    int ref_row, void* ref_out /*or NULL*/, const void* ref_in /*or NULL*/,
+                                    const void* ref_x, const unsigned char* ref_mask, double* gcov);
+
 /* Input gradients of a conditioned view's prediction (what lcgp_predict_grad is to lcgp_predict): per local component k and
  * new input i the outputs of lcgp_condition_predict and their derivatives with respect to the standardised x0, in
  * lcgp_predict_grad's layout (dghat, dgvar: q_local x out_stride x d doubles).  `state`, m, xn: as lcgp_condition_predict takes

@@ -81,6 +81,9 @@ SIGNATURES = {
     "lcgp_condition_prepare": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, C.c_size_t, _vp, _vp, _vp]),
     "lcgp_condition_predict": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, C.c_size_t, _vp, _vp,
                                     _i]),
+    "lcgp_condition_predict_marginal_scratch_bytes": (_i, [_i, _i, _i, _i, _i, _i, C.POINTER(C.c_size_t)]),
+    "lcgp_condition_predict_marginal": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp,
+                                             C.c_size_t, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "lcgp_condition_grad_state_bytes": (_i, [_i, _i, _i, _i, C.POINTER(C.c_size_t)]),
     "lcgp_condition_grad_prepare": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp]),
     "lcgp_condition_predict_grad_scratch_bytes": (_i, [_i, _i, _i, _i, _i, C.POINTER(C.c_size_t)]),

@@ -539,6 +539,23 @@ __device__ __forceinline__ double marg_Fc(double b) {
     else return (8.0 + b * (5.0 + b)) / 3.0 * exp(-b);
 }
 
+// (1 / w) int_lo^hi kappa(|t - xv| / ell) dt, w = hi - lo: the box average of the 1-D kernel factor at the value xv (a training
+// input's in marg_table_kernel, a query row's in marg_refcov_kernel; the cases are spelt out below)
+template <int KERN>
+__device__ __forceinline__ double marg_I1(double xv, double lo, double hi, double ell) {
+    const double w = hi - lo;
+    const double a1 = xv - lo, a2 = hi - xv;
+    const double b1 = fabs(a1) / ell, b2 = fabs(a2) / ell;
+    double r;
+    if (a1 >= 0.0 && a2 >= 0.0) {
+        r = marg_F<KERN>(b1) + marg_F<KERN>(b2);
+    } else {
+        const double bn = fmin(b1, b2), bf = fmax(b1, b2);
+        r = bn > 1.0 ? marg_Fc<KERN>(bn) - marg_Fc<KERN>(bf) : marg_F<KERN>(bf) - marg_F<KERN>(bn);
+    }
+    return ell / w * r;
+}
+
 // I1[k, l, j] = (1 / w_l) int_lo^hi kappa(|t - x_jl| / ell_kl) dt  for every training input (columns n .. npad - 1: 1), and
 // I2[k, l] = (1 / w_l^2) int int kappa(|t - t'| / ell_kl) dt dt' = 2 [F(a) / a - G(a) / a^2], a = w_l / ell_kl.
 // x inside the box: (ell / w) [F(b1) + F(b2)], b = the scaled distances to the two ends.  Outside: the difference of the two,
@@ -559,17 +576,7 @@ __global__ __launch_bounds__(256) void marg_table_kernel(const T* __restrict__ x
     if (j >= npad) return;
     double v = 1.0;
     if (j < n) {
-        const double xv = (double)x[(size_t)j * d + l];
-        const double a1 = xv - lo, a2 = hi - xv;
-        const double b1 = fabs(a1) / ell, b2 = fabs(a2) / ell;
-        double r;
-        if (a1 >= 0.0 && a2 >= 0.0) {
-            r = marg_F<KERN>(b1) + marg_F<KERN>(b2);
-        } else {
-            const double bn = fmin(b1, b2), bf = fmax(b1, b2);
-            r = bn > 1.0 ? marg_Fc<KERN>(bn) - marg_Fc<KERN>(bf) : marg_F<KERN>(bf) - marg_F<KERN>(bn);
-        }
-        v = ell / w * r;
+        v = marg_I1<KERN>((double)x[(size_t)j * d + l], lo, hi, ell);
     }
     tab[((size_t)k * d + l) * npad + j] = v;
 }
@@ -2835,6 +2842,67 @@ __global__ __launch_bounds__(64) void marg_reduce_kernel(const T* __restrict__ X
     }
 }
 
+// the widened row [U_r | T_r] of pass row r (lcgp_condition_predict_marginal, ref_out): ref[k, 0 .. npad) = U_k[r, :],
+// ref[k, npad .. npad + mpad) = T_k[r, :] (mpad = 0 without a view).  grid ((npad + mpad) / 256 rounded up, q)
+template <typename T>
+__global__ __launch_bounds__(256) void marg_refrow_kernel(const T* __restrict__ U, size_t slab, int npad, const T* __restrict__ Tm,
+                                                          size_t cslab, int mpad, int r, T* __restrict__ ref) {
+    const int j = blockIdx.x * 256 + threadIdx.x, k = blockIdx.y;
+    if (j >= npad + mpad) return;
+    ref[(size_t)k * (npad + mpad) + j] = j < npad ? U[(size_t)k * slab + (size_t)r * npad + j]
+                                                  : Tm[(size_t)k * cslab + (size_t)r * mpad + (j - npad)];
+}
+
+// gcov[k, i] = prior_k(i, r) - D_k U_k[i, :] . U_r - T_k[i, :] . T_r: the posterior covariance of the box average of row i with
+// that of a reference row r given as its widened row ref = [U_r | T_r] (marg_refrow_kernel), its values xr and its mask mr.
+// prior_k(i, r) = scale_k (1 - nt_k) prod_l f_l in ascending l, f_l = kappa(|x0_il - xr_l| / ell_kl) where both rows keep l,
+// the box average of kappa at the kept value where one row integrates l, I2[k, l] where both do; no nugget term (the
+// continuous surface).  One wave per row: the lanes stride the n columns of U and then the m columns of T (m = 0: no view),
+// butterfly sums as in pred_reduce_kernel and cond_reduce_kernel; lane 0 forms the prior.  An entry of x0 or xr under its
+// row's mask is never loaded.
+template <typename T, int KERN>
+__global__ __launch_bounds__(64) void marg_refcov_kernel(const T* __restrict__ U, size_t slab, int npad, int n,
+                                                         const T* __restrict__ Tm, size_t cslab, int mpad, int m,
+                                                         const T* __restrict__ ref, const double* __restrict__ theta, int tw,
+                                                         int d, const T* __restrict__ x0, const unsigned char* __restrict__ mask,
+                                                         const T* __restrict__ xr, const unsigned char* __restrict__ mr,
+                                                         const double* __restrict__ box, const double* __restrict__ i2, int ldo,
+                                                         double* __restrict__ gcov) {
+    const int i = blockIdx.x, k = blockIdx.y, lane = threadIdx.x;
+    const double* th = theta + (size_t)k * tw;
+    const T* Ui = U + (size_t)k * slab + (size_t)i * npad;
+    const T* rf = ref + (size_t)k * (npad + mpad);
+    double s1 = 0.0, s2 = 0.0;
+    for (int j = lane; j < n; j += 64) s1 += (double)Ui[j] * (double)rf[j];
+    if (m > 0) {
+        const T* Ti = Tm + (size_t)k * cslab + (size_t)i * mpad;
+        for (int j = lane; j < m; j += 64) s2 += (double)Ti[j] * (double)rf[npad + j];
+    }
+    for (int off = 32; off > 0; off >>= 1) { s1 += __shfl_xor(s1, off); s2 += __shfl_xor(s2, off); }
+    if (lane == 0) {
+        const double scale = th[d], nug = th[d + 1], D = th[d + 2];
+        double pr = scale * (1.0 - nug / (1.0 + nug));
+        for (int l = 0; l < d; ++l) {
+            const bool mi = mask[(size_t)i * d + l] != 0, mj = mr[l] != 0;
+            const double ell = th[l];
+            double f;
+            if (mi && mj) {
+                f = i2[(size_t)k * d + l];
+            } else if (mi || mj) {
+                const double xv = mi ? (double)xr[l] : (double)x0[(size_t)i * d + l];
+                f = marg_I1<KERN>(xv, box[l], box[d + l], ell);
+            } else {
+                const double u = fabs((double)x0[(size_t)i * d + l] - (double)xr[l]) / ell;
+                if constexpr (KERN == 0) f = (1.0 + u) * exp(-u);
+                else if constexpr (KERN == 1) f = exp(-0.5 * u * u);
+                else f = (1.0 + u + u * u / 3.0) * exp(-u);
+            }
+            pr *= f;
+        }
+        gcov[(size_t)k * ldo + i] = pr - D * s1 - s2;
+    }
+}
+
 // ---------------------------------------------------------------------------------------------------
 // K7: input gradients of the prediction.  For local component k, new input i (standardised) and dimension l:
 //   dghat[k, i, l] =        sum_j dc_l(i, j) sr_j z_k[j]
@@ -3575,40 +3643,6 @@ int do_predict(hipStream_t st, const Ws& w, const void* x, const void* sr, const
     return 0;
 }
 
-// Box-averaged predictions, all local components in every launch: the table of 1-D averages (marg_table_kernel), the rows
-// (cross_kernel with the masks), U = X W^T (the launch of form_xu) and the row reductions with the per-row prior.
-// Scratch: X and U as in do_predict, then the table (q d npad doubles) and I2 (q d doubles).
-template <typename T>
-int do_predict_marginal(hipStream_t st, const Ws& w, const void* x, const void* sr, const double* theta, int n0, const void* x0,
-                        const unsigned char* mask, const double* box, void* scratch, double* ghat, double* gvar, int ldo) {
-    const int n0pad = predict_pad(n0);
-    const size_t slab = (size_t)n0pad * w.npad;
-    const int tw = w.d + 3 + w.p;
-    T* X = (T*)scratch;
-    T* U = X + slab * w.q;
-    double* tab = (double*)(U + slab * w.q);
-    double* i2 = tab + (size_t)w.q * w.d * w.npad;
-    ThetaArg dummy;
-    memset(&dummy, 0, sizeof(dummy));
-    for_kern(w.kern, [&](auto kern) {
-        hipLaunchKernelGGL((marg_table_kernel<T, decltype(kern)::value>), dim3((w.npad + 255) / 256, w.d, w.q), dim3(256), 0, st,
-                           (const T*)x, w.n, w.npad, w.d, theta, tw, box, tab, i2);
-    });
-    CHECK_LAUNCH("marg_table_kernel");
-    for_kern(w.kern, [&](auto kern) {
-        hipLaunchKernelGGL((cross_kernel<T, decltype(kern)::value, const unsigned char*, const double*>), dim3(w.nb, n0pad / TS, w.q),
-                           dim3(256), 0, st, X, w.npad, n0, w.n, w.d, (const T*)x0, (const T*)x, dummy, theta, 0, (const T*)sr, n0pad,
-                           w.npad, tw, slab, (const int*)nullptr, mask, (const double*)tab);
-    });
-    CHECK_LAUNCH("cross_kernel (marginal rows)");
-    int rc = launch_pred<T, OP_PRED_U>(st, X, (const T*)(w.base + w.off_W), U, slab, w.mat, w.npad, n0pad, w.nb, w.q);
-    if (rc) return rc;
-    hipLaunchKernelGGL((marg_reduce_kernel<T>), dim3(n0, w.q), dim3(64), 0, st, (const T*)X, (const T*)U, slab, w.npad, w.n,
-                       (const T*)(w.base + w.off_z), w.npad, theta, tw, w.d, mask, (const double*)i2, ldo, ghat, gvar);
-    CHECK_LAUNCH("marg_reduce_kernel");
-    return 0;
-}
-
 // K7 for all local components: do_predict with same = 0 (ghat / gvar bitwise those of lcgp_predict), then V_k = U_k W_k into
 // the X slab (free once the row reductions have read it; one launch of the tile kernel, k tiles from the diagonal of W
 // down), then the fused contraction (pgrad_kernel).  Scratch: that of lcgp_predict.
@@ -3938,6 +3972,109 @@ int do_condition_predict(hipStream_t st, const Ws& w, const void* x, const void*
     hipLaunchKernelGGL((cond_reduce_kernel<T>), dim3(n0, w.q), dim3(64), 0, st, (const T*)Tm, cslab, mpad, m, v, mpad, ldo, ghat,
                        gvar);
     CHECK_LAUNCH("cond_reduce_kernel");
+    return 0;
+}
+
+// Box-averaged predictions of the fitted model (state = NULL, m = 0) or of a conditioned view, all local components in every
+// launch (lcgp_predict_marginal, lcgp_condition_predict_marginal).  Fitted model: the table of 1-D averages (marg_table_kernel),
+// the rows (cross_kernel with the masks), U = X W^T (the launch of form_xu) and the row reductions with the per-row prior.
+// View: averaging commutes with conditioning, so the pass is do_condition_predict's with both row kernels replaced by their
+// masked instances -- a second table over the view's inputs xn (marg_table_kernel with x := xn, n := m, npad := mpad), the
+// masked rows against xn (no sr, no nugget) into Sigma_0n, then OP_COND_CROSS, T and cond_reduce_kernel as there.
+// The reference row (MargRef) adds launches BEHIND those and changes none of them: ref_out copies the widened row [U_r | T_r] of
+// pass row ref_row out, ref_in gives gcov = the covariance of every row's average with that of the row ref_in belongs to.
+// Scratch: X and U as in do_predict, then the table (q d npad doubles) and I2 (q d doubles); on a view that of
+// do_condition_predict, then the table and I2, then the table over xn (q d mpad doubles).
+struct MargRef {
+    int row = 0;                                  // pass row written to out
+    void* out = nullptr;                          // q (npad + mpad) elements, or NULL
+    const void* in = nullptr;                     // the widened row of the reference row, or NULL
+    const void* x = nullptr;                      // its d values (entries under its mask are never read)
+    const unsigned char* mask = nullptr;          // its d mask bytes
+    double* gcov = nullptr;                       // q rows of ldo
+};
+
+template <typename T>
+int do_predict_marginal(hipStream_t st, const Ws& w, const void* x, const void* sr, const double* theta, const void* state, int m,
+                        const void* xn, int n0, const void* x0, const unsigned char* mask, const double* box, void* scratch,
+                        double* ghat, double* gvar, int ldo, const MargRef& ref) {
+    const int dtype = sizeof(T) == 4 ? LCGP_F32 : LCGP_F64;
+    const int n0pad = predict_pad(n0);
+    const size_t slab = (size_t)n0pad * w.npad;
+    const int tw = w.d + 3 + w.p;
+    const int mpad = state ? cov_pad(m) : 0;
+    const size_t cslab = (size_t)n0pad * mpad;
+    T* X = (T*)scratch;
+    T* U = X + slab * w.q;
+    T* Sg = state ? (T*)((char*)scratch + align256(2 * (size_t)w.q * slab * sizeof(T))) : nullptr;
+    T* Tm = state ? Sg + cslab * w.q : nullptr;
+    double* tab = state ? (double*)((char*)scratch + cond_predict_scratch(dtype, w.n, w.q, m, n0)) : (double*)(U + slab * w.q);
+    double* i2 = tab + (size_t)w.q * w.d * w.npad;
+    double* tabn = i2 + (size_t)w.q * w.d;
+    ThetaArg dummy;
+    memset(&dummy, 0, sizeof(dummy));
+    for_kern(w.kern, [&](auto kern) {
+        hipLaunchKernelGGL((marg_table_kernel<T, decltype(kern)::value>), dim3((w.npad + 255) / 256, w.d, w.q), dim3(256), 0, st,
+                           (const T*)x, w.n, w.npad, w.d, theta, tw, box, tab, i2);
+    });
+    CHECK_LAUNCH("marg_table_kernel");
+    if (state) {
+        for_kern(w.kern, [&](auto kern) {
+            hipLaunchKernelGGL((marg_table_kernel<T, decltype(kern)::value>), dim3((mpad + 255) / 256, w.d, w.q), dim3(256), 0, st,
+                               (const T*)xn, m, mpad, w.d, theta, tw, box, tabn, i2);      // (I2 again: the same values)
+        });
+        CHECK_LAUNCH("marg_table_kernel (view inputs)");
+    }
+    for_kern(w.kern, [&](auto kern) {
+        hipLaunchKernelGGL((cross_kernel<T, decltype(kern)::value, const unsigned char*, const double*>), dim3(w.nb, n0pad / TS, w.q),
+                           dim3(256), 0, st, X, w.npad, n0, w.n, w.d, (const T*)x0, (const T*)x, dummy, theta, 0, (const T*)sr, n0pad,
+                           w.npad, tw, slab, (const int*)nullptr, mask, (const double*)tab);
+    });
+    CHECK_LAUNCH("cross_kernel (marginal rows)");
+    int rc = launch_pred<T, OP_PRED_U>(st, X, (const T*)(w.base + w.off_W), U, slab, w.mat, w.npad, n0pad, w.nb, w.q);
+    if (rc) return rc;
+    hipLaunchKernelGGL((marg_reduce_kernel<T>), dim3(n0, w.q), dim3(64), 0, st, (const T*)X, (const T*)U, slab, w.npad, w.n,
+                       (const T*)(w.base + w.off_z), w.npad, theta, tw, w.d, mask, (const double*)i2, ldo, ghat, gvar);
+    CHECK_LAUNCH("marg_reduce_kernel");
+    if (state) {
+        const CondLay L = cond_carve(dtype, w.n, w.q, m);
+        const T* Un = (const T*)((const char*)state + L.off_U);
+        const T* Wi = (const T*)((const char*)state + L.off_W);
+        const double* v = (const double*)((const char*)state + L.off_v);
+        // Sigma_0n = Cbar^x(x0, xn) - D U_0 U_n^T: the masked rows against the view's inputs (table rows mpad long, m columns)
+        for_kern(w.kern, [&](auto kern) {
+            hipLaunchKernelGGL((cross_kernel<T, decltype(kern)::value, const unsigned char*, const double*>),
+                               dim3(mpad / TS, n0pad / TS, w.q), dim3(256), 0, st, Sg, mpad, n0, m, w.d, (const T*)x0, (const T*)xn,
+                               dummy, theta, 0, (const T*)nullptr, n0pad, mpad, tw, cslab, (const int*)nullptr, mask,
+                               (const double*)tabn);
+        });
+        CHECK_LAUNCH("cross_kernel (marginal rows, view inputs)");
+        GemmArgs h;
+        h.A = U; h.B = Un; h.C = Sg;
+        h.sA = slab; h.sB = (size_t)mpad * w.npad; h.sC = cslab; h.ldA = h.ldB = w.npad; h.ldC = mpad;
+        h.nb = 0; h.p0 = w.npad / TS; h.p1 = mpad / TS; h.p2 = tw; h.p3 = w.d + 2;
+        h.theta = theta;
+        rc = launch_gemm<T, OP_COND_CROSS, 64>(st, h, (n0pad / TS) * (mpad / TS), w.q);
+        if (rc) return rc;
+        rc = launch_pred<T, OP_PRED_U>(st, Sg, Wi, Tm, cslab, (size_t)mpad * mpad, mpad, n0pad, mpad / TS, w.q);
+        if (rc) return rc;
+        hipLaunchKernelGGL((cond_reduce_kernel<T>), dim3(n0, w.q), dim3(64), 0, st, (const T*)Tm, cslab, mpad, m, v, mpad, ldo, ghat,
+                           gvar);
+        CHECK_LAUNCH("cond_reduce_kernel");
+    }
+    if (ref.out) {
+        hipLaunchKernelGGL((marg_refrow_kernel<T>), dim3((w.npad + mpad + 255) / 256, w.q), dim3(256), 0, st, (const T*)U, slab, w.npad,
+                           (const T*)Tm, cslab, mpad, ref.row, (T*)ref.out);
+        CHECK_LAUNCH("marg_refrow_kernel");
+    }
+    if (ref.in) {
+        for_kern(w.kern, [&](auto kern) {
+            hipLaunchKernelGGL((marg_refcov_kernel<T, decltype(kern)::value>), dim3(n0, w.q), dim3(64), 0, st, (const T*)U, slab,
+                               w.npad, w.n, (const T*)Tm, cslab, mpad, state ? m : 0, (const T*)ref.in, theta, tw, w.d,
+                               (const T*)x0, mask, (const T*)ref.x, ref.mask, box, (const double*)i2, ldo, ref.gcov);
+        });
+        CHECK_LAUNCH("marg_refcov_kernel");
+    }
     return 0;
 }
 
@@ -7035,8 +7172,10 @@ int lcgp_predict_marginal(void* stream, int dtype, int kernel_id, int n, int d, 
     Ws w = carve(dtype, n, d, p, q_local, (void*)workspace);
     w.kern = kernel_id;
     hipStream_t st = (hipStream_t)stream;
-    return dtype == LCGP_F64 ? do_predict_marginal<double>(st, w, x, sr, theta, n0, x0, mask, box, scratch, ghat, gvar, ldo)
-                             : do_predict_marginal<float>(st, w, x, sr, theta, n0, x0, mask, box, scratch, ghat, gvar, ldo);
+    const MargRef none;
+    return dtype == LCGP_F64
+               ? do_predict_marginal<double>(st, w, x, sr, theta, nullptr, 0, nullptr, n0, x0, mask, box, scratch, ghat, gvar, ldo, none)
+               : do_predict_marginal<float>(st, w, x, sr, theta, nullptr, 0, nullptr, n0, x0, mask, box, scratch, ghat, gvar, ldo, none);
 }
 
 int lcgp_predict_grad_scratch_bytes(int dtype, int n, int q_local, int n0, size_t* bytes) {
@@ -7222,6 +7361,49 @@ int lcgp_condition_predict(void* stream, int dtype, int kernel_id, int n, int d,
     hipStream_t st = (hipStream_t)stream;
     return dtype == LCGP_F64 ? do_condition_predict<double>(st, w, x, sr, theta, state, m, xn, n0, x0, scratch, ghat, gvar, ldo)
                              : do_condition_predict<float>(st, w, x, sr, theta, state, m, xn, n0, x0, scratch, ghat, gvar, ldo);
+}
+
+int lcgp_condition_predict_marginal_scratch_bytes(int dtype, int n, int d, int q_local, int m, int n0, size_t* bytes) {
+    if (m < 0) return bad("m < 0");
+    if (m == 0) return lcgp_predict_marginal_scratch_bytes(dtype, n, d, q_local, n0, bytes);
+    if (d < 1 || d > DWIDE) return bad("d must be in [1, 126]");
+    if (dtype != LCGP_F64 && dtype != LCGP_F32) return bad("dtype must be 0 (f64) or 1 (f32)");
+    if (n < 1 || n0 < 1 || q_local < 1) return bad("n, n0, q_local must be >= 1");
+    if (!bytes) return bad("bytes is NULL");
+    *bytes = cond_predict_scratch(dtype, n, q_local, m, n0)
+             + (size_t)q_local * d * (round_up(n, 2 * TS) + 1 + cov_pad(m)) * sizeof(double);
+    return 0;
+}
+
+int lcgp_condition_predict_marginal(void* stream, int dtype, int kernel_id, int n, int d, int p, int q_local, const void* x,
+                                    const void* sr, const double* theta, const void* workspace, const void* state, int m,
+                                    const void* xn, int n0, const void* x0, const unsigned char* mask, const double* box,
+                                    void* scratch, size_t scratch_bytes, double* ghat, double* gvar, int out_stride, int ref_row,
+                                    void* ref_out, const void* ref_in, const void* ref_x, const unsigned char* ref_mask,
+                                    double* gcov) {
+    int rc = check_common(dtype, n, d, p, q_local, kernel_id);
+    if (rc) return rc;
+    if (state ? m < 1 : m != 0) return bad("m must be >= 1 with a state and 0 without one");
+    if (n0 < 1) return bad("n0 < 1");
+    if (!x || !theta || !workspace || !x0 || !mask || !box || !scratch || !ghat || !gvar) return bad("NULL pointer");
+    if (state && !xn) return bad("NULL pointer");
+    if (ref_out && (ref_row < 0 || ref_row >= n0)) return bad("ref_row must be a row of the pass");
+    if (ref_in && (!ref_x || !ref_mask || !gcov)) return bad("ref_in needs ref_x, ref_mask and gcov");
+    if (out_stride != 0 && out_stride < n0) return bad("out_stride must be 0 (= n0) or >= n0");
+    size_t need = 0;
+    rc = lcgp_condition_predict_marginal_scratch_bytes(dtype, n, d, q_local, m, n0, &need);
+    if (rc) return rc;
+    if (scratch_bytes < need)
+        return bad("scratch is smaller than lcgp_condition_predict_marginal_scratch_bytes(dtype, n, d, q_local, m, n0)");
+    const int ldo = out_stride ? out_stride : n0;
+    Ws w = carve(dtype, n, d, p, q_local, (void*)workspace);
+    w.kern = kernel_id;
+    hipStream_t st = (hipStream_t)stream;
+    MargRef ref;
+    ref.row = ref_row; ref.out = ref_out; ref.in = ref_in; ref.x = ref_x; ref.mask = ref_mask; ref.gcov = gcov;
+    return dtype == LCGP_F64
+               ? do_predict_marginal<double>(st, w, x, sr, theta, state, m, xn, n0, x0, mask, box, scratch, ghat, gvar, ldo, ref)
+               : do_predict_marginal<float>(st, w, x, sr, theta, state, m, xn, n0, x0, mask, box, scratch, ghat, gvar, ldo, ref);
 }
 
 int lcgp_condition_grad_state_bytes(int dtype, int n, int q_local, int m, size_t* bytes) {

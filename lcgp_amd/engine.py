@@ -396,14 +396,21 @@ class HotPathEngine:
                     wp, None if M is None else self._p(M), n0), "lcgp_predict_gradcov")
             return dghat, gamma, M
 
-    def predict_marginal_block(self, x0s, mask, box):
+    def predict_marginal_block(self, x0s, mask, box, state=None, ref=None):
         """(2, q_local, n0) float64 DEVICE tensor [ghat; gvar] of the latent components AVERAGED over the dimensions mask marks
         (mask (n0, d), non-zero = integrated out), uniformly over box (2, d) = [lo; hi] in standardised inputs, from the
         factorisation of the last evaluate() (lcgp_predict_marginal).  Entries of x0s under the mask are never read on the
         device (they are uploaded as zeros: NaN is allowed there).  A row with an empty mask is bitwise predict_block(x0s,
         same=False)'s while both take one pass.  Chunked like predict_block with the engine's scratch, a pass never below 128
         rows while n0 has them and a short last pass moved back over its predecessor (the same values again), so that every
-        pass forms U on the same tile size: results are bitwise independent of PREDICT_CHUNK."""
+        pass forms U on the same tile size: results are bitwise independent of PREDICT_CHUNK.
+          state: a view's state (condition_begin): the averages of the conditioned model (lcgp_condition_predict_marginal); a
+                 row with an empty mask is then bitwise condition_predict_block's while both take one pass.  The base
+                 factorisation must still be the one the state was built from.
+          ref:   (x_ref_s (d,), mask_ref (d,)), one more row: the result is (3, q_local, n0) with gcov third, the posterior
+                 covariance of every row's average with that row's (continuous surface, no nugget term).  A one-row pass
+                 writes the reference row's widened row [U_r | T_r] out first; the chunked passes then read it.  The first two
+                 rows are bitwise those without ref."""
         torch = self.torch
         if self._theta_last is None:
             raise RuntimeError("predict_marginal() needs a preceding evaluate() at the current parameters")
@@ -415,22 +422,53 @@ class HotPathEngine:
             raise ValueError("predict_marginal_block: the box needs hi > lo in every dimension")
         x0s = np.ascontiguousarray(np.where(mask != 0, 0.0, np.asarray(x0s, np.float64)))
         chunk = min(n0, max(128, PREDICT_CHUNK))
+        m, view, kp = self._view_args(state)
         with torch.cuda.device(self.device):
             x0d = torch.as_tensor(x0s).to(self.device, self.tdtype).contiguous()
             md = torch.as_tensor(mask).to(self.device)
             bd = torch.as_tensor(box).to(self.device)
-            scp = self._p(self._grow_scratch(self._nbytes("lcgp_predict_marginal_scratch_bytes", self.dtype, self.n, d,
-                                                          self.q_local, chunk)))
-            out = torch.empty((2, self.q_local, n0), dtype=torch.float64, device=self.device)
+            out = torch.empty((2 if ref is None else 3, self.q_local, n0), dtype=torch.float64, device=self.device)
             st, xp, srp, thp, wsp = self._stream(), self._p(self.x), self._p(self.sr), self._p(self.theta_dev), self._p(self.workspace)
+            plain = state is None and ref is None
+            if plain:
+                scratch = self._grow_scratch(self._nbytes("lcgp_predict_marginal_scratch_bytes", self.dtype, self.n, d,
+                                                          self.q_local, chunk))
+            else:
+                scratch = self._grow_scratch(
+                    self._nbytes("lcgp_condition_predict_marginal_scratch_bytes", self.dtype, self.n, d, self.q_local, m, chunk),
+                    ("the box-averaged prediction of %d rows per pass" % chunk,
+                     "%d components of %d x K', K' = npad + mpad = %d, twice" % (self.q_local, chunk, kp),
+                     "lower lcgp_amd.engine.PREDICT_CHUNK"))
+            scp = self._p(scratch)
+            head = (st, self.dtype, self.kernel_id, self.n, d, self.p, self.q_local, xp, srp, thp, wsp) + \
+                (view if view else (None, 0, None))
+            refs = (0, None, None, None, None)          # ref_row, ref_out, ref_in, ref_x, ref_mask
+            if ref is not None:
+                mr = np.ascontiguousarray(np.asarray(ref[1]) != 0, np.uint8).reshape(1, d)
+                xr = np.ascontiguousarray(np.where(mr != 0, 0.0, np.asarray(ref[0], np.float64).reshape(1, d)))
+                xrd = torch.as_tensor(xr).to(self.device, self.tdtype).contiguous()
+                mrd = torch.as_tensor(mr).to(self.device)
+                row = torch.empty((self.q_local, kp), dtype=self.tdtype, device=self.device)
+                one = torch.empty((2, self.q_local, 1), dtype=torch.float64, device=self.device)
+                _hip.check(self.lib.lcgp_condition_predict_marginal(
+                    *head, 1, self._p(xrd), self._p(mrd), self._p(bd), scp, scratch.numel(), self._p(one[0]), self._p(one[1]), 1,
+                    0, self._p(row), None, None, None, None), "lcgp_condition_predict_marginal")
+                refs = (0, None, self._p(row), self._p(xrd), self._p(mrd))
             for lo in range(0, n0, chunk):
-                m = min(chunk, n0 - lo)
-                if m < 128 <= n0:
-                    lo, m = n0 - 128, 128
-                _hip.check(self.lib.lcgp_predict_marginal(
-                    st, self.dtype, self.kernel_id, self.n, d, self.p, self.q_local, xp, srp, thp, wsp, m,
-                    C.c_void_p(x0d.data_ptr() + lo * d * x0d.element_size()), C.c_void_p(md.data_ptr() + lo * d), self._p(bd), scp,
-                    C.c_void_p(out[0].data_ptr() + 8 * lo), C.c_void_p(out[1].data_ptr() + 8 * lo), n0), "lcgp_predict_marginal")
+                rows = min(chunk, n0 - lo)
+                if rows < 128 <= n0:
+                    lo, rows = n0 - 128, 128
+                x0p, mp = C.c_void_p(x0d.data_ptr() + lo * d * x0d.element_size()), C.c_void_p(md.data_ptr() + lo * d)
+                ghp, gvp = C.c_void_p(out[0].data_ptr() + 8 * lo), C.c_void_p(out[1].data_ptr() + 8 * lo)
+                if plain:
+                    _hip.check(self.lib.lcgp_predict_marginal(
+                        st, self.dtype, self.kernel_id, self.n, d, self.p, self.q_local, xp, srp, thp, wsp, rows, x0p, mp,
+                        self._p(bd), scp, ghp, gvp, n0), "lcgp_predict_marginal")
+                else:
+                    gcp = None if ref is None else C.c_void_p(out[2].data_ptr() + 8 * lo)
+                    _hip.check(self.lib.lcgp_condition_predict_marginal(
+                        *head, rows, x0p, mp, self._p(bd), scp, scratch.numel(), ghp, gvp, n0, *refs, gcp),
+                        "lcgp_condition_predict_marginal")
             return out
 
     def predict_device(self, x0s, same=False):

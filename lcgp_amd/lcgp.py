@@ -266,12 +266,15 @@ class ActiveSubspace:
 class MainEffects:
     """main_effects(): grid (d, G) on the raw input scale; mean, var (p_sel, d, G), the output as a function of input l alone,
     averaged over the others, and the posterior variance of that average; overall, overall_var (p_sel,), the average over all
-    inputs (the Bayesian-quadrature mean of the output over the box); effect = mean - overall (no variance: that needs the
-    covariance between rows)."""
+    inputs (the Bayesian-quadrature mean of the output over the box); effect = mean - overall, the curve of a main-effect plot;
+    effect_var (p_sel, d, G) its posterior variance var + overall_var - 2 cov(row, overall row) -- mean and overall are strongly
+    correlated, so this is far below var + overall_var -- or None when main_effects() was not asked for it.  Small negative
+    values from rounding are not clamped."""
 
-    def __init__(self, grid, mean, var, overall, overall_var):
+    def __init__(self, grid, mean, var, overall, overall_var, effect_var=None):
         self.grid, self.mean, self.var, self.overall, self.overall_var = grid, mean, var, overall, overall_var
         self.effect = mean - overall[:, None, None]
+        self.effect_var = effect_var
 
     def __repr__(self):
         return 'MainEffects(outputs=%d, d=%d, grid=%d)' % (self.mean.shape[0], self.mean.shape[1], self.mean.shape[2])
@@ -402,6 +405,26 @@ class ConditionedLCGP:
         st = self._state
         return base._sample(x0s, size, seed, include_noise, jitter, lambda: self._engine,
                             lambda eng, S, seeds: eng.condition_sample_latent(st, x0s, S, seeds, jitter))
+
+    def predict_marginal(self, x0, integrate, box=None, latent=False, cov_with=None):
+        """LCGP.predict_marginal() of the conditioned model: (ypred, yconfvar[, ycov]), each (p, n0) CPU float64 (latent=True:
+        (q, n0)), the box averages of the outputs GIVEN the base model's data and this view's new runs.  Averaging is linear, so
+        it commutes with conditioning: the pass is predict()'s of this view with both row kernels replaced by their box-averaged
+        instances (lcgp_condition_predict_marginal); nothing is refactorised.  Equal, to rounding, to
+        predict_marginal() of a model built on the augmented data at the same parameters.  Arguments, defaults, checks, errors
+        and shapes are LCGP.predict_marginal()'s; the default box is the bounding box of the BASE model's training inputs (the
+        view's inputs may lie outside it).  RuntimeError when the view is stale."""
+        base = self.base
+        x0s, mask, bs, ref = base._marginal_arguments(x0, integrate, box, cov_with)
+        self._require_current()
+        eng = self._engine
+        loc = None if eng is None else eng.predict_marginal_block(x0s, mask, bs, state=self._state, ref=ref).permute(1, 0, 2)
+        return base._marginal_result(loc, x0s.shape[0], latent, ref is not None)
+
+    def main_effects(self, grid=33, box=None, outputs=None, effect_var=False):
+        """LCGP.main_effects() of the conditioned model: the main-effect curves after the view's new runs, from one
+        predict_marginal() pass of this view.  Arguments, defaults, checks and the MainEffects returned are the model's."""
+        return self.base._main_effects(self.predict_marginal, grid, box, outputs, effect_var)
 
     def _design_arguments(self, xc_s, match):
         """what the design queries check beyond the base model's: the view is current, and on the rep path no candidate equals
@@ -2399,23 +2422,13 @@ class LCGP:
             raise ValueError('box must be finite with upper > lower in every dimension')
         return bs
 
-    def predict_marginal(self, x0, integrate, box=None, latent=False):
-        """Predictions AVERAGED over some of the inputs: (ypred, yconfvar), each (p, n0), the output at the kept inputs of each
-        row of x0 averaged over the integrated inputs, uniformly over `box`, and the posterior variance of that average (of
-        the noise-free surface; no ypredvar: observation noise does not average).
-          integrate: a sequence of dimension indices, the same for every row, or a boolean (n0, d) array, one mask per row
-                     (True = integrated out).  Values of x0 in integrated columns are ignored; NaN is allowed there.
-          box:       (2, d) = [lower; upper] on the raw input scale (default: the training inputs' bounding box).  Training
-                     inputs may lie outside it.
-          latent:    return (ghat, gvar), each (q, n0), of the latent components instead.
-        For the product kernels the average is exact: a prediction whose cross-covariance row holds the box average of the
-        1-D kernel factor in the integrated dimensions and whose prior variance holds its double average (the nugget, white
-        noise, averages to zero).  One pass on the GPU at the cost of predict() on n0 rows (lcgp_predict_marginal); a row that
-        integrates nothing is predict()'s at a new input.  Rows are treated one by one: their covariance is not formed."""
+    def _marginal_rows(self, x0, integrate, name='x0'):
+        """x0 (n0, d) raw scale and `integrate` (dimension indices for every row, or a boolean (n0, d) array) -> (x0n, mask): a
+        float64 copy and the boolean mask of integrated entries, after predict_marginal()'s shape and index checks"""
         x0n = np.array(_np(self._verify_data_types(x0)), F64)
         d = int(self.d)
         if x0n.ndim != 2 or x0n.shape[1] != d or x0n.shape[0] < 1:
-            raise ValueError('x0 must have shape (n, %d), got %s' % (d, tuple(x0n.shape)))
+            raise ValueError('%s must have shape (n, %d), got %s' % (name, d, tuple(x0n.shape)))
         n0 = x0n.shape[0]
         integ = np.asarray(integrate)
         if integ.dtype == bool and integ.ndim == 2:
@@ -2430,26 +2443,90 @@ class LCGP:
                 raise ValueError('integrate must hold dimension indices in [0, %d)' % d)
             mask = np.zeros((n0, d), bool)
             mask[:, idx.astype(int)] = True
+        return x0n, mask
+
+    def _marginal_arguments(self, x0, integrate, box, cov_with):
+        """predict_marginal()'s checks, for the model and its views: (x0s (n0, d) standardised with zeros under the mask, mask,
+        box (2, d) standardised, ref) with ref = None or (x_ref_s (d,), mask_ref (d,)) from cov_with"""
+        x0n, mask = self._marginal_rows(x0, integrate)
+        row = None
+        if cov_with is not None:
+            if not isinstance(cov_with, (tuple, list)) or len(cov_with) != 2:
+                raise ValueError('cov_with must be (x_row, integrate_row): one raw-scale row (d,) and its integrated dimensions')
+            xr = np.array(_np(cov_with[0]), F64)                  # (a vector: _verify_data_types would make it a column)
+            d = int(self.d)
+            if xr.shape != (d,):
+                raise ValueError('the row of cov_with must have shape (%d,), got %s' % (d, tuple(xr.shape)))
+            ir = np.asarray(cov_with[1])
+            if ir.dtype == bool and ir.ndim == 1:
+                if ir.shape != (d,):
+                    raise ValueError('a boolean integrate_row of cov_with must have shape (%d,), got %s' % (d, tuple(ir.shape)))
+                ir = ir[None, :]
+            row = self._marginal_rows(xr[None, :], ir, 'the row of cov_with')
         bs = self._marginal_box(box)
         if not np.all(np.isfinite(x0n[~mask])):
             raise ValueError('x0 must be finite in the columns that are kept')
         x0n[mask] = 0.0                                  # (never read: the engine passes zeros under the mask)
         x0s = self._standardise_x0(x0n)[0]
-        eng = self._ensure_aux()
-        loc = None if eng is None else eng.predict_marginal_block(x0s, mask, bs).permute(1, 0, 2)        # (q_local, 2, n0)
-        both = self._gather_components(loc, (2, n0))
+        ref = None
+        if row is not None:
+            xr, mr = row
+            if not np.all(np.isfinite(xr[~mr])):
+                raise ValueError('the row of cov_with must be finite in the columns that are kept')
+            xr[mr] = 0.0
+            ref = (self._standardise_x0(xr)[0][0], mr[0])
+        return x0s, mask, bs, ref
+
+    def _marginal_result(self, loc, n0, latent, with_cov):
+        """this rank's (q_local, 2 or 3, n0) block [ghat; gvar[; gcov]] (None without components) -> what predict_marginal()
+        returns; a covariance maps to the outputs as a variance does (W^2, scale^2, no additive term)"""
+        both = self._gather_components(loc, (3 if with_cov else 2, n0))
         ghat, gvar = both[:, 0], both[:, 1]
         if latent:
-            return _t(ghat), _t(gvar)
+            return (_t(ghat), _t(gvar)) + ((_t(both[:, 2]),) if with_cov else ())
         ypred, _, yconfvar = self._outputs(ghat, gvar)
-        return ypred, yconfvar
+        if not with_cov:
+            return ypred, yconfvar
+        W, _, scale, _ = self._output_map()
+        return ypred, yconfvar, _t((both[:, 2].T @ W ** 2).T * (scale ** 2)[:, None])
 
-    def main_effects(self, grid=33, box=None, outputs=None):
+    def predict_marginal(self, x0, integrate, box=None, latent=False, cov_with=None):
+        """Predictions AVERAGED over some of the inputs: (ypred, yconfvar), each (p, n0), the output at the kept inputs of each
+        row of x0 averaged over the integrated inputs, uniformly over `box`, and the posterior variance of that average (of
+        the noise-free surface; no ypredvar: observation noise does not average).
+          integrate: a sequence of dimension indices, the same for every row, or a boolean (n0, d) array, one mask per row
+                     (True = integrated out).  Values of x0 in integrated columns are ignored; NaN is allowed there.
+          box:       (2, d) = [lower; upper] on the raw input scale (default: the training inputs' bounding box).  Training
+                     inputs may lie outside it.
+          latent:    return (ghat, gvar), each (q, n0), of the latent components instead.
+          cov_with:  (x_row, integrate_row): one more raw-scale row (d,) with its dimension indices or boolean (d,) mask, checked
+                     as x0 and integrate are (NaN allowed under the mask).  A third result ycov (p, n0) is appended (latent:
+                     gcov (q, n0)): the posterior covariance of each row's average with that row's average, for the same
+                     output, of the continuous surface (no nugget term, also for two rows that integrate nothing).  The first
+                     two results are bitwise those without it.
+        For the product kernels the average is exact: a prediction whose cross-covariance row holds the box average of the
+        1-D kernel factor in the integrated dimensions and whose prior variance holds its double average (the nugget, white
+        noise, averages to zero).  One pass on the GPU at the cost of predict() on n0 rows (lcgp_predict_marginal); a row that
+        integrates nothing is predict()'s at a new input.  Rows are treated one by one: beyond cov_with's row their covariance
+        is not formed."""
+        x0s, mask, bs, ref = self._marginal_arguments(x0, integrate, box, cov_with)
+        eng = self._ensure_aux()
+        extra = {} if ref is None else {'ref': ref}
+        loc = None if eng is None else eng.predict_marginal_block(x0s, mask, bs, **extra).permute(1, 0, 2)      # (q_local, 2 | 3, n0)
+        return self._marginal_result(loc, x0s.shape[0], latent, ref is not None)
+
+    def main_effects(self, grid=33, box=None, outputs=None, effect_var=False):
         """Main effects of every input: the output as a function of input l alone, averaged over all the others uniformly over
         `box` ((2, d) raw scale, default the training inputs' bounding box), on `grid` equally spaced values of input l
         between the box's ends, with the posterior variance of each average; and the average over all inputs.  One
-        predict_marginal() pass of d grid + 1 rows.  Returns a MainEffects (grid, mean, var, overall, overall_var, effect);
-        outputs: output indices (default all p)."""
+        predict_marginal() pass of d grid + 1 rows.  Returns a MainEffects (grid, mean, var, overall, overall_var, effect,
+        effect_var); outputs: output indices (default all p).  effect_var=True: the same pass takes the overall row as
+        cov_with's and fills MainEffects.effect_var, the variance of the plotted curve `effect` (otherwise None; the other
+        fields are bitwise the same either way)."""
+        return self._main_effects(self.predict_marginal, grid, box, outputs, effect_var)
+
+    def _main_effects(self, marginal, grid, box, outputs, effect_var):
+        """main_effects() through `marginal`, the model's predict_marginal or a view's"""
         d, G = int(self.d), int(grid)
         if G < 1:
             raise ValueError('grid must be at least 1')
@@ -2467,11 +2544,18 @@ class LCGP:
         for l in range(d):
             x0[l * G:(l + 1) * G, l] = grid_raw[l]
             mask[l * G:(l + 1) * G, l] = False
-        ypred, yconfvar = self.predict_marginal(x0, mask, box=box)
-        ypred, yconfvar = _np(ypred)[outputs], _np(yconfvar)[outputs]
         ns = len(outputs)
+        if effect_var:
+            ypred, yconfvar, ycov = marginal(x0, mask, box=box, cov_with=(x0[-1], mask[-1]))
+            ycov = _np(ycov)[outputs]
+        else:
+            ypred, yconfvar = marginal(x0, mask, box=box)
+        ypred, yconfvar = _np(ypred)[outputs], _np(yconfvar)[outputs]
+        ev = None
+        if effect_var:
+            ev = _t((yconfvar[:, :-1] + yconfvar[:, -1:] - 2.0 * ycov[:, :-1]).reshape(ns, d, G))
         return MainEffects(_t(grid_raw), _t(ypred[:, :-1].reshape(ns, d, G)), _t(yconfvar[:, :-1].reshape(ns, d, G)),
-                           _t(ypred[:, -1]), _t(yconfvar[:, -1]))
+                           _t(ypred[:, -1]), _t(yconfvar[:, -1]), ev)
 
     # ---- cache views the reference keeps as attributes (materialised from the device only when read) ----
     def _fetch_all(self, fn, width):

@@ -569,6 +569,51 @@ int lcgp_condition_predict_grad(void* stream, int dtype, int kernel_id, int n, i
                                 void* scratch, size_t scratch_bytes, double* ghat, double* gvar, double* dghat, double* dgvar,
                                 int out_stride);
 
+/* Input Hessians and the posterior covariance of the gradient on a conditioned view (what lcgp_predict_hess and
+ * lcgp_predict_gradcov are to the fitted model).  `state`, m, xn, `grad_state`: as lcgp_condition_predict_grad takes
+ * them; workspace, state and grad state are only read.  Per local component k, with X_0, U_0, T, R, U', V', w, z' as there, the
+ * derivative rows of lcgp_predict_hess on both column sets (their factors -1 / ell_l left out) and the row they give in the
+ * augmented factor (K' = npad + mpad, the widening of lcgp_condition_vr_*):
+ *     P_il   = (d_l X_i) W^T                                            (npad)
+ *     Q_il   = (d_l c^x(x0_i, xn) - D_k P_il U_n^T) L_S^-T                (mpad; the launches that make T out of X_0)
+ *     P'_il  = [ P_il | Q_il / sqrt(D_k) ]                              (K')
+ *     d2ghat'[i, lm] =           sum_j d2c_lm(x0_i, x_j) sr_j z'_j       +   sum_a d2c^x_lm(x0_i, xn_a) w_a
+ *     d2gvar'[i, lm] = -2 [ D_k sum_j d2c_lm(x0_i, x_j) sr_j V'[i, j]    +   sum_a d2c^x_lm(x0_i, xn_a) R[i, a]
+ *                           + D_k P'_il . P'_im / (ell_l ell_m) ]
+ *     Gamma'[i, lm]  = delta_lm c_k kappa / ell_l^2  -  D_k P'_il . P'_im / (ell_l ell_m)
+ * d2c_lm, c_k, kappa as in lcgp_predict_hess / lcgp_predict_gradcov; same = 0 throughout (the Matern-3/2 psi has its kink where
+ * a coordinate of x0 equals a training input's or one of the view's inputs').  Outputs in the layouts of those two functions.
+ *   lcgp_condition_predict_hess: the launches of lcgp_condition_predict_grad (ghat', gvar', dghat', dgvar' are bitwise that
+ *     function's; V' stays in its slab, R over Sigma_0n), then behind that pass's scratch pdx_kernel on (x0, x, sr) and on (x0, xn),
+ *     P into rows K' apart (OP_PRED_U), -D P U_n^T (OP_COND_CROSS, 64 x 64 tiles), Q (OP_PRED_U on the dense L_S^-1), the tails
+ *     Q / sqrt(D) behind each P row (zeros in the columns m .. mpad - 1 and in the padding rows), phess_gram_kernel over npad + m
+ *     columns (the columns n .. npad - 1 of P are zero) and the two-segment contraction phess_cond_kernel (a second segment of
+ *     stages over the view's inputs: weight 1, w for z, R for V; D rides on the first segment; same lane / slice / wave order,
+ *     double accumulators, no atomics; nothing of size n0 (n + m) d^2 is written).
+ *   lcgp_condition_predict_gradcov: dghat' by the mean-only instance of lcgp_condition_predict_grad's contraction (bitwise that
+ *     function's; R, U' and V' are not formed), the rows P' as above, then gradcov_kernel and with weights gradcov_reduce_kernel
+ *     over the widened rows.  gamma may be NULL when w is given; M is accumulated into (the caller carries it across passes).
+ *     The per-workgroup partial sums go into the freed DX slabs: q ceil(n0 / 4) d (d + 1) / 2 doubles <= 508 q n0 d bytes, less
+ *     than the q rows_pad npad elements there, as in lcgp_predict_gradcov.
+ * `scratch`: lcgp_condition_predict_hess_scratch_bytes = that of lcgp_condition_predict_grad + q rows_pad (2 K' + mpad) elements
+ * (P', DX, the derivative rows against xn and Q); lcgp_condition_predict_gradcov_scratch_bytes = q rows_pad (2 K' + mpad)
+ * elements (rows_pad = n0 d padded as in lcgp_predict_hess); both
+ * checked against `scratch_bytes`.  n0 d <= LCGP_HESS_MAX_ROWS.  Fixed order, one stream: results are bitwise independent of the
+ * content of scratch on entry and of q_local.
+ * Flops per component beyond lcgp_predict_hess's: rows_pad mpad (2 npad + mpad) for Q. */
+int lcgp_condition_predict_hess_scratch_bytes(int dtype, int n, int d, int q_local, int m, int n0, size_t* bytes /*host out*/);
+int lcgp_condition_predict_hess(void* stream, int dtype, int kernel_id, int n, int d, int p, int q_local,
+                                const void* x, const void* sr, const double* theta, const void* workspace,
+                                const void* state, int m, const void* xn, const void* grad_state, int n0, const void* x0,
+                                void* scratch, size_t scratch_bytes, double* ghat, double* gvar, double* dghat, double* dgvar,
+                                double* d2ghat, double* d2gvar, int out_stride);
+int lcgp_condition_predict_gradcov_scratch_bytes(int dtype, int n, int d, int q_local, int m, int n0, size_t* bytes /*host out*/);
+int lcgp_condition_predict_gradcov(void* stream, int dtype, int kernel_id, int n, int d, int p, int q_local,
+                                   const void* x, const void* sr, const double* theta, const void* workspace,
+                                   const void* state, int m, const void* xn, const void* grad_state, int n0, const void* x0,
+                                   void* scratch, size_t scratch_bytes, double* dghat, double* gamma /*or NULL*/,
+                                   const double* w /*or NULL*/, double* M /*or NULL*/, int out_stride);
+
 /* Closed-form cross-validation at fixed parameters (no counterpart in the reference).  Input: the workspace of the last
  * lcgp_nll_grad, whose V slot holds a = A_k^-1 (A_k = I + D_k (C_k o s s^T), s = sr, ones when sr is NULL) and whose vectors
  * hold b_k and z_k = A_k^-1 b_k.  With K_k = C_k + (D_k S^2)^-1 (S = diag(s)), K_k^-1 = D_k S a S, so for a set B of m

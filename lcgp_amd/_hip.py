@@ -89,6 +89,12 @@ SIGNATURES = {
     "lcgp_condition_predict_grad_scratch_bytes": (_i, [_i, _i, _i, _i, _i, C.POINTER(C.c_size_t)]),
     "lcgp_condition_predict_grad": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, C.c_size_t,
                                          _vp, _vp, _vp, _vp, _i]),
+    "lcgp_condition_predict_hess_scratch_bytes": (_i, [_i, _i, _i, _i, _i, _i, C.POINTER(C.c_size_t)]),
+    "lcgp_condition_predict_hess": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, C.c_size_t,
+                                         _vp, _vp, _vp, _vp, _vp, _vp, _i]),
+    "lcgp_condition_predict_gradcov_scratch_bytes": (_i, [_i, _i, _i, _i, _i, _i, C.POINTER(C.c_size_t)]),
+    "lcgp_condition_predict_gradcov": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp,
+                                            C.c_size_t, _vp, _vp, _vp, _vp, _i]),
     "lcgp_loo": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i]),
     "lcgp_cv_workspace_bytes": (_i, [_i, _i, _i, _i, _i, _i, _vp, C.POINTER(C.c_size_t)]),
     "lcgp_cv_gather": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp]),

@@ -2923,6 +2923,7 @@ constexpr int PG_ROWS = 32, PG_SL = 8;
 // conditioning inputs xn of a view -- weight 1 instead of sr_j, w in place of z, R (rows mpad long) in place of V, the factor
 // -2 in place of -2 D (D rides on the weights of the first segment) -- and z is the view's z' in double.  Same stages, same
 // lane / slice / wave order; per lane the training inputs in ascending j, then the conditioning inputs in ascending j.
+// COND + MEAN (lcgp_condition_predict_gradcov): dghat' alone over both segments; V', R and dgvar are not touched.
 // COND + ZMAT (lcgp_condition_vr_grad): both segments carry a matrix in the place of z -- z (rows npad long, beside V) over
 // the training inputs with the weight D sr_j, zn (rows mpad long, laid out as R is) over the conditioning inputs with the
 // weight 1; zd and wv are not read.
@@ -2940,7 +2941,7 @@ __device__ __forceinline__ void pgrad_body(const T* __restrict__ x0, int n0, con
                                            int tw, const T* __restrict__ z, int npad, const T* __restrict__ V,
                                            size_t slab, int ldo, double* __restrict__ dghat, double* __restrict__ dgvar,
                                            const PgradCond<T>& cs, const T* __restrict__ zn = nullptr) {
-    static_assert(!COND || !MEAN, "the second segment belongs to the contractions that carry the variance");
+    static_assert(!ZMAT || !MEAN, "the mean-only contraction carries the vector z");
     constexpr bool WIDE = DD == DMAX;
     constexpr int JT = WIDE ? 16 : 32;                  // training inputs per LDS stage
     constexpr int XW = WIDE ? DWIDE + 3 : DD + 1;       // odd row length: the per-row reads of x0sh hit distinct banks;
@@ -2989,8 +2990,9 @@ __device__ __forceinline__ void pgrad_body(const T* __restrict__ x0, int n0, con
             const int i = e / JT, jj = e - i * JT;
             if constexpr (COND) {
                 const bool in = i0 + i < n0 && jb + jj < ns;
-                vsh[i][jj] = !in ? 0.0 : seg2 ? (double)cs.R[(size_t)k * cs.rslab + (size_t)(i0 + i) * cs.mpad + jb + jj]
-                                              : (double)Vk[(size_t)(i0 + i) * npad + jb + jj];
+                if constexpr (!MEAN)
+                    vsh[i][jj] = !in ? 0.0 : seg2 ? (double)cs.R[(size_t)k * cs.rslab + (size_t)(i0 + i) * cs.mpad + jb + jj]
+                                                  : (double)Vk[(size_t)(i0 + i) * npad + jb + jj];
                 if constexpr (ZMAT)
                     zsh[i][jj] = !in ? 0.0 : seg2 ? (double)zn[(size_t)k * cs.rslab + (size_t)(i0 + i) * cs.mpad + jb + jj]
                                                   : (double)zk[(size_t)(i0 + i) * npad + jb + jj];
@@ -3064,8 +3066,9 @@ __device__ __forceinline__ void pgrad_body(const T* __restrict__ x0, int n0, con
             const double tm = (red[0][0][r] + red[0][1][r]) + (red[0][2][r] + red[0][3][r]);
             const double tv = (red[1][0][r] + red[1][1][r]) + (red[1][2][r] + red[1][3][r]);
             dghat[orow + l0 + l] = -tm / th[l0 + l];
-            if constexpr (COND) dgvar[orow + l0 + l] = 2.0 * tv / th[l0 + l];      // (D rode on the first segment's weights)
-            else if constexpr (!MEAN) dgvar[orow + l0 + l] = 2.0 * D * tv / th[l0 + l];
+            if constexpr (MEAN) (void)tv;
+            else if constexpr (COND) dgvar[orow + l0 + l] = 2.0 * tv / th[l0 + l];      // (D rode on the first segment's weights)
+            else dgvar[orow + l0 + l] = 2.0 * D * tv / th[l0 + l];
         }
         __syncthreads();
     }
@@ -3086,6 +3089,16 @@ __global__ __launch_bounds__(256) void pgrad_cond_kernel(const T* __restrict__ x
                                                          int tw, int npad, const T* __restrict__ V, size_t slab, int ldo,
                                                          double* __restrict__ dghat, double* __restrict__ dgvar, PgradCond<T> cs) {
     pgrad_body<T, DD, KERN, false, false, true>(x0, n0, x, sr, n, d, theta, tw, (const T*)nullptr, npad, V, slab, ldo, dghat, dgvar, cs);
+}
+
+// its MEAN instance (lcgp_condition_predict_gradcov): dghat' alone, by the same operations in the same order; V', R and dgvar
+// are not touched
+template <typename T, int DD, int KERN>
+__global__ __launch_bounds__(256) void pgrad_cond_mean_kernel(const T* __restrict__ x0, int n0, const T* __restrict__ x,
+                                                              const T* __restrict__ sr, int n, int d, const double* __restrict__ theta,
+                                                              int tw, int npad, int ldo, double* __restrict__ dghat, PgradCond<T> cs) {
+    pgrad_body<T, DD, KERN, false, true, true>(x0, n0, x, sr, n, d, theta, tw, (const T*)nullptr, npad, (const T*)nullptr, (size_t)0,
+                                               ldo, dghat, (double*)nullptr, cs);
 }
 
 // the contraction of lcgp_condition_vr_grad over the n + m columns with a matrix in the place of z in both segments: z beside V
@@ -5534,12 +5547,17 @@ __global__ __launch_bounds__(256) void phess_gram_kernel(const T* __restrict__ P
 // the PH_B x PH_B entries of the block pair (2 PH_B^2 accumulators per lane whatever d), V staged through LDS; the n0 x n x
 // d x d tensor is never written.  Per lane in ascending j, then the 8 slices in a fixed order.  The last step adds the Gram
 // term phess_gram_kernel left in d2gvar and applies -2 D_k / (ell_l ell_m).  WIDE: d > 16 (rows of DWIDE + 3 doubles in LDS).
-template <typename T, int KERN, bool WIDE>
-__global__ __launch_bounds__(256) void phess_kernel(const T* __restrict__ x0, int n0, const T* __restrict__ x,
-                                                    const T* __restrict__ sr, int n, int d, const double* __restrict__ theta,
-                                                    int tw, const T* __restrict__ z, int npad, const T* __restrict__ V,
-                                                    size_t slab, int ldo, double* __restrict__ d2ghat,
-                                                    double* __restrict__ d2gvar) {
+// COND (lcgp_condition_predict_hess): a SECOND segment of stages over the m conditioning inputs xn of a view behind the n
+// training inputs, as in pgrad_body -- weight 1 instead of sr_j, w in place of z, R (rows mpad long) in place of V; z is the
+// view's z' in double, and D rides on the weights of the first segment, so the last step applies -2 / (ell_l ell_m) to
+// tv + D G.  Same stages, same lane / slice / wave order; per lane the training inputs in ascending j, then the conditioning
+// inputs in ascending j.
+template <typename T, int KERN, bool WIDE, bool COND>
+__device__ __forceinline__ void phess_body(const T* __restrict__ x0, int n0, const T* __restrict__ x,
+                                           const T* __restrict__ sr, int n, int d, const double* __restrict__ theta,
+                                           int tw, const T* __restrict__ z, int npad, const T* __restrict__ V,
+                                           size_t slab, int ldo, double* __restrict__ d2ghat,
+                                           double* __restrict__ d2gvar, const PgradCond<T>& cs) {
     constexpr int JT = WIDE ? 16 : 32;                  // training inputs per LDS stage
     constexpr int XW = WIDE ? DWIDE + 3 : 16 + PH_B + 1; // odd row length >= l0 + PH_B for every block (zeros beyond d)
     __shared__ double x0sh[PG_ROWS][XW];
@@ -5562,28 +5580,53 @@ __global__ __launch_bounds__(256) void phess_kernel(const T* __restrict__ x0, in
         const int i = e / XW, m = e - i * XW;
         x0sh[i][m] = (i0 + i < n0 && m < d) ? (double)x0[(size_t)(i0 + i) * d + m] / th[m] : 0.0;
     }
-    const T* zk = z + (size_t)k * npad;
+    const T* zk = COND ? z : z + (size_t)k * npad;       // (COND: z' comes in double through cs.zd)
     const T* Vk = V + (size_t)k * slab;
     double am[PH_B][PH_B], av[PH_B][PH_B];
 #pragma unroll
     for (int a = 0; a < PH_B; ++a)
 #pragma unroll
         for (int b = 0; b < PH_B; ++b) { am[a][b] = 0.0; av[a][b] = 0.0; }
-    for (int j0 = 0; j0 < n; j0 += JT) {
+    // (COND: the stages of the second segment follow those of the first, whose last stage may be short)
+    const int n1 = (n + JT - 1) / JT * JT, jend = COND ? n1 + (cs.m + JT - 1) / JT * JT : n;
+    for (int j0 = 0; j0 < jend; j0 += JT) {
         __syncthreads();                                // x0sh is written; every slice is done with the previous stage
-        for (int e = tid; e < JT * XW; e += 256) {
-            const int jj = e / XW, m = e - jj * XW;
-            xsh[jj][m] = (j0 + jj < n && m < d) ? (double)x[(size_t)(j0 + jj) * d + m] / th[m] : 0.0;
-        }
-        for (int e = tid; e < PG_ROWS * JT; e += 256) {
-            const int i = e / JT, jj = e - i * JT;
-            vsh[i][jj] = (i0 + i < n0 && j0 + jj < n) ? (double)Vk[(size_t)(i0 + i) * npad + j0 + jj] : 0.0;
-        }
-        if (tid < JT) {
-            const int j = j0 + tid;
-            const double s = j < n ? (sr ? (double)sr[j] : 1.0) : 0.0;      // (inputs beyond n weigh zero)
-            wsr[tid] = s;
-            wz[tid] = j < n ? s * (double)zk[j] : 0.0;
+        if constexpr (COND) {
+            const bool seg2 = j0 >= n1;
+            const int jb = seg2 ? j0 - n1 : j0;         // first input of the stage within its segment
+            const T* xs = seg2 ? cs.xn : x;
+            const int ns = seg2 ? cs.m : n;
+            for (int e = tid; e < JT * XW; e += 256) {
+                const int jj = e / XW, m = e - jj * XW;
+                xsh[jj][m] = (jb + jj < ns && m < d) ? (double)xs[(size_t)(jb + jj) * d + m] / th[m] : 0.0;
+            }
+            for (int e = tid; e < PG_ROWS * JT; e += 256) {
+                const int i = e / JT, jj = e - i * JT;
+                const bool in = i0 + i < n0 && jb + jj < ns;
+                vsh[i][jj] = !in ? 0.0 : seg2 ? (double)cs.R[(size_t)k * cs.rslab + (size_t)(i0 + i) * cs.mpad + jb + jj]
+                                              : (double)Vk[(size_t)(i0 + i) * npad + jb + jj];
+            }
+            if (tid < JT) {
+                const int j = jb + tid;
+                const double s = j < ns ? (seg2 ? 1.0 : (sr ? (double)sr[j] : 1.0)) : 0.0;
+                wsr[tid] = seg2 ? s : s * D;
+                wz[tid] = j < ns ? s * (seg2 ? cs.wv[(size_t)k * cs.mpad + j] : cs.zd[(size_t)k * npad + j]) : 0.0;
+            }
+        } else {
+            for (int e = tid; e < JT * XW; e += 256) {
+                const int jj = e / XW, m = e - jj * XW;
+                xsh[jj][m] = (j0 + jj < n && m < d) ? (double)x[(size_t)(j0 + jj) * d + m] / th[m] : 0.0;
+            }
+            for (int e = tid; e < PG_ROWS * JT; e += 256) {
+                const int i = e / JT, jj = e - i * JT;
+                vsh[i][jj] = (i0 + i < n0 && j0 + jj < n) ? (double)Vk[(size_t)(i0 + i) * npad + j0 + jj] : 0.0;
+            }
+            if (tid < JT) {
+                const int j = j0 + tid;
+                const double s = j < n ? (sr ? (double)sr[j] : 1.0) : 0.0;      // (inputs beyond n weigh zero)
+                wsr[tid] = s;
+                wz[tid] = j < n ? s * (double)zk[j] : 0.0;
+            }
         }
         __syncthreads();
         for (int jj = sl; jj < JT; jj += PG_SL) {
@@ -5625,10 +5668,30 @@ __global__ __launch_bounds__(256) void phess_kernel(const T* __restrict__ x0, in
                 const double inv = 1.0 / (th[l] * th[m]);
                 const size_t o = orow + (size_t)(l * (l + 1) / 2 + m);
                 d2ghat[o] = tm * inv;
-                d2gvar[o] = -2.0 * D * (tv + d2gvar[o]) * inv;
+                if constexpr (COND) d2gvar[o] = -2.0 * (tv + D * d2gvar[o]) * inv;      // (D rode on the first segment's weights)
+                else d2gvar[o] = -2.0 * D * (tv + d2gvar[o]) * inv;
             }
             __syncthreads();
         }
+}
+
+template <typename T, int KERN, bool WIDE>
+__global__ __launch_bounds__(256) void phess_kernel(const T* __restrict__ x0, int n0, const T* __restrict__ x,
+                                                    const T* __restrict__ sr, int n, int d, const double* __restrict__ theta,
+                                                    int tw, const T* __restrict__ z, int npad, const T* __restrict__ V,
+                                                    size_t slab, int ldo, double* __restrict__ d2ghat,
+                                                    double* __restrict__ d2gvar) {
+    phess_body<T, KERN, WIDE, false>(x0, n0, x, sr, n, d, theta, tw, z, npad, V, slab, ldo, d2ghat, d2gvar, PgradCond<T>{});
+}
+
+// the second-derivative contraction of lcgp_condition_predict_hess over the n training inputs and the m conditioning inputs
+template <typename T, int KERN, bool WIDE>
+__global__ __launch_bounds__(256) void phess_cond_kernel(const T* __restrict__ x0, int n0, const T* __restrict__ x,
+                                                         const T* __restrict__ sr, int n, int d, const double* __restrict__ theta,
+                                                         int tw, int npad, const T* __restrict__ V, size_t slab, int ldo,
+                                                         double* __restrict__ d2ghat, double* __restrict__ d2gvar,
+                                                         PgradCond<T> cs) {
+    phess_body<T, KERN, WIDE, true>(x0, n0, x, sr, n, d, theta, tw, (const T*)nullptr, npad, V, slab, ldo, d2ghat, d2gvar, cs);
 }
 
 inline int hess_rows_pad(int n0, int d) { return predict_pad(n0 * d); }
@@ -5805,6 +5868,170 @@ int do_predict_gradcov(hipStream_t st, const Ws& w, const void* x, const void* s
     const int nblk = (w.d + PH_B - 1) / PH_B, npair = nblk * (nblk + 1) / 2, nwg = (n0 + 3) / 4, tri = w.d * (w.d + 1) / 2;
     double* part = (double*)scratch;
     hipLaunchKernelGGL((gradcov_kernel<T>), dim3(nwg, w.q, npair), dim3(256), 0, st, (const T*)P, dslab, w.npad, w.n, n0, w.d,
+                       theta, tw, gradcov_kappa(w.kern), ldo, gamma, wt, part);
+    CHECK_LAUNCH("gradcov_kernel");
+    if (wt) {
+        hipLaunchKernelGGL(gradcov_reduce_kernel, dim3((tri + 255) / 256, w.q), dim3(256), 0, st, (const double*)part, nwg, tri, M);
+        CHECK_LAUNCH("gradcov_reduce_kernel");
+    }
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------
+// K8 / K9 on a conditioned view (lcgp_hip.h: lcgp_condition_predict_hess / lcgp_condition_predict_gradcov).  The
+// derivative rows of K8 are formed on both column sets and widened to K' = npad + mpad as the rows of the design criteria
+// are (vr_form):
+//   P_il  = DX_il W^T                                            (npad; pdx_kernel on (x0, x, sr), OP_PRED_U)
+//   Q_il  = (DX^n_il - D P_il U_n^T) L_S^-T                        (mpad; pdx_kernel on (x0, xn, no sr), OP_COND_CROSS, OP_PRED_U
+//                                                                 on the dense L_S^-1: the launches that make T out of X_0)
+//   P'_il = [ P_il | Q_il / sqrt(D) ]                            (cond_rows_tail_kernel: zeros in the columns m .. mpad - 1)
+// so that D P'_il . P'_im is the Gram term of the augmented factor; the columns n .. npad - 1 of P are zero, and the unchanged
+// Gram kernels sum npad + m columns of rows K' apart.
+//   d2ghat'[i, lm] =     (sum_j c0 kap sr_j z'_j      + sum_a c0^x kap w_a)                       / (ell_l ell_m)
+//   d2gvar'[i, lm] = -2 (D sum_j c0 kap sr_j V'[i, j] + sum_a c0^x kap R[i, a] + D P'_il . P'_im) / (ell_l ell_m)
+//   Gamma'[i, lm]  = (delta_lm c_k kappa - D P'_il . P'_im) / (ell_l ell_m)
+// ---------------------------------------------------------------------------------------------------
+
+// out[r, 0 .. mpad) = Q[r, :] / sqrt(D_k) behind column npad of the widened row r (ldu apart) for r < rows; zeros in the columns
+// m .. mpad - 1 and in the rows rows .. gridDim.x - 1, whatever the scratch held: cond_tail_kernel without the gvar update
+template <typename T>
+__global__ __launch_bounds__(64) void cond_rows_tail_kernel(const T* __restrict__ Q, size_t slab, int m, int mpad, int rows,
+                                                            const double* __restrict__ theta, int tw, int d, T* __restrict__ Pt,
+                                                            size_t pslab, int ldu) {
+    const int r = blockIdx.x, k = blockIdx.y, lane = threadIdx.x;
+    T* out = Pt + (size_t)k * pslab + (size_t)r * ldu;
+    if (r >= rows) {                                // (uniform per block)
+        for (int j = lane; j < mpad; j += 64) out[j] = (T)0;
+        return;
+    }
+    const T* Qr = Q + (size_t)k * slab + (size_t)r * mpad;
+    const double is = 1.0 / sqrt(theta[(size_t)k * tw + d + 2]);
+    for (int j = lane; j < mpad; j += 64) out[j] = j < m ? (T)((double)Qr[j] * is) : (T)0;
+}
+
+// scratch of the widened derivative rows of one pass: P' (q slabs rows_pad x K'), DX (q rows_pad x npad), DX^n and Q (q rows_pad x
+// mpad each) = q rows_pad (2 K' + mpad) elements, carved in this order by cond_rows_form
+inline size_t cond_rows_scratch(int dtype, int n, int d, int q, int m, int n0) {
+    const size_t mpad = cov_pad(m), kp = (size_t)round_up(n, 2 * TS) + mpad;
+    return align256((size_t)q * hess_rows_pad(n0, d) * (2 * kp + mpad) * (dtype == LCGP_F64 ? 8 : 4));
+}
+
+// P' for all local components into Pw (q slabs rows_pad x K'); DX, DX^n and Q behind it
+template <typename T>
+int cond_rows_form(hipStream_t st, const Ws& w, const void* x, const void* sr, const double* theta, const T* Un, const T* Wi, int m,
+                   int mpad, const void* xn, int n0, const void* x0, T* Pw) {
+    const int rows_pad = hess_rows_pad(n0, w.d), tw = w.d + 3 + w.p, kp = w.npad + mpad;
+    const size_t pslab = (size_t)rows_pad * kp, dslab = (size_t)rows_pad * w.npad, cslab = (size_t)rows_pad * mpad;
+    T* DX = Pw + pslab * w.q;
+    T* Sd = DX + dslab * w.q;
+    T* Qm = Sd + cslab * w.q;
+    // (the carve above against the size the entries check the caller's scratch with: a mismatch is an error, not a fault)
+    if ((size_t)(Qm + cslab * w.q - Pw) * sizeof(T) > cond_rows_scratch(sizeof(T) == 4 ? LCGP_F32 : LCGP_F64, w.n, w.d, w.q, m, n0))
+        return bad("internal: the widened derivative rows do not fit lcgp_condition_predict_gradcov_scratch_bytes");
+    for_kern(w.kern, [&](auto kern) {
+        hipLaunchKernelGGL((pdx_kernel<T, decltype(kern)::value>), dim3(w.nb, (n0 + PH_PTS - 1) / PH_PTS, w.q), dim3(256), 0, st,
+                           DX, dslab, w.npad, n0, w.n, w.d, rows_pad, (const T*)x0, (const T*)x, (const T*)sr, theta, tw);
+    });
+    CHECK_LAUNCH("pdx_kernel");
+    for_kern(w.kern, [&](auto kern) {
+        hipLaunchKernelGGL((pdx_kernel<T, decltype(kern)::value>), dim3(mpad / TS, (n0 + PH_PTS - 1) / PH_PTS, w.q), dim3(256), 0, st,
+                           Sd, cslab, mpad, n0, m, w.d, rows_pad, (const T*)x0, (const T*)xn, (const T*)nullptr, theta, tw);
+    });
+    CHECK_LAUNCH("pdx_kernel (view inputs)");
+    int rc = launch_pred<T, OP_PRED_U>(st, DX, (const T*)(w.base + w.off_W), Pw, dslab, w.mat, w.npad, rows_pad, w.nb, w.q, pslab,
+                                       false, kp);
+    if (rc) return rc;
+    GemmArgs h;
+    h.A = Pw; h.B = Un; h.C = Sd;
+    h.sA = pslab; h.sB = (size_t)mpad * w.npad; h.sC = cslab; h.ldA = kp; h.ldB = w.npad; h.ldC = mpad;
+    h.nb = 0; h.p0 = w.npad / TS; h.p1 = mpad / TS; h.p2 = tw; h.p3 = w.d + 2;
+    h.theta = theta;
+    rc = launch_gemm<T, OP_COND_CROSS, 64>(st, h, (rows_pad / TS) * (mpad / TS), w.q);
+    if (rc) return rc;
+    rc = launch_pred<T, OP_PRED_U>(st, Sd, Wi, Qm, cslab, (size_t)mpad * mpad, mpad, rows_pad, mpad / TS, w.q);
+    if (rc) return rc;
+    hipLaunchKernelGGL((cond_rows_tail_kernel<T>), dim3(rows_pad, w.q), dim3(64), 0, st, (const T*)Qm, cslab, m, mpad, n0 * w.d, theta,
+                       tw, w.d, Pw + w.npad, pslab, kp);
+    CHECK_LAUNCH("cond_rows_tail_kernel");
+    return 0;
+}
+
+// K8 on a view: do_condition_predict_grad (its four outputs bitwise those of lcgp_condition_predict_grad; V' stays in the X slab,
+// R over Sigma_0n), then the widened rows behind that pass's scratch, the Gram terms and the two-segment contraction.
+template <typename T>
+int do_condition_predict_hess(hipStream_t st, const Ws& w, const void* x, const void* sr, const double* theta, const void* state,
+                              int m, const void* xn, const void* gstate, int n0, const void* x0, void* scratch, double* ghat,
+                              double* gvar, double* dghat, double* dgvar, double* d2ghat, double* d2gvar, int ldo) {
+    int rc = do_condition_predict_grad<T>(st, w, x, sr, theta, state, m, xn, gstate, n0, x0, scratch, ghat, gvar, dghat, dgvar, ldo);
+    if (rc) return rc;
+    const int dtype = sizeof(T) == 4 ? LCGP_F32 : LCGP_F64;
+    const CondLay L = cond_carve(dtype, w.n, w.q, m);
+    const CondGradLay G = cond_grad_carve(w.n, w.q, m);
+    const int mpad = L.mpad, n0pad = predict_pad(n0), rows_pad = hess_rows_pad(n0, w.d), tw = w.d + 3 + w.p, kp = w.npad + mpad;
+    const size_t slab = (size_t)n0pad * w.npad, cslab = (size_t)n0pad * mpad;
+    const T* Un = (const T*)((const char*)state + L.off_U);
+    const T* Wi = (const T*)((const char*)state + L.off_W);
+    const T* V = (const T*)scratch;                     // V' = U' W (do_condition_predict_grad)
+    const T* Rm = (const T*)((const char*)scratch + align256(2 * (size_t)w.q * slab * sizeof(T)));
+    T* Pw = (T*)((char*)scratch + cond_predict_scratch(dtype, w.n, w.q, m, n0));
+    rc = cond_rows_form<T>(st, w, x, sr, theta, Un, Wi, m, mpad, xn, n0, x0, Pw);
+    if (rc) return rc;
+    const int nblk = (w.d + PH_B - 1) / PH_B, npair = nblk * (nblk + 1) / 2;
+    hipLaunchKernelGGL((phess_gram_kernel<T>), dim3((n0 + 3) / 4, w.q, npair), dim3(256), 0, st, (const T*)Pw,
+                       (size_t)rows_pad * kp, kp, w.npad + m, n0, w.d, ldo, d2gvar);
+    CHECK_LAUNCH("phess_gram_kernel");
+    PgradCond<T> cs;
+    cs.zd = (const double*)((const char*)gstate + G.off_z);
+    cs.xn = (const T*)xn; cs.m = m;
+    cs.wv = (const double*)((const char*)gstate + G.off_w); cs.mpad = mpad;
+    cs.R = Rm; cs.rslab = cslab;
+    dim3 grid((n0 + PG_ROWS - 1) / PG_ROWS, w.q, npair);
+    for_kern(w.kern, [&](auto kern) {
+        auto go = [&](auto wide) {
+            hipLaunchKernelGGL((phess_cond_kernel<T, decltype(kern)::value, decltype(wide)::value>), grid, dim3(256), 0, st,
+                               (const T*)x0, n0, (const T*)x, (const T*)sr, w.n, w.d, theta, tw, w.npad, V, slab, ldo, d2ghat,
+                               d2gvar, cs);
+        };
+        if (w.d > 16) go(std::true_type{});
+        else go(std::false_type{});
+    });
+    CHECK_LAUNCH("phess_cond_kernel");
+    return 0;
+}
+
+// K9 on a view.  Scratch: cond_rows_scratch; once P is formed the DX slabs are free and take the per-workgroup partial sums
+// exactly as in do_predict_gradcov (the same q ceil(n0 / 4) tri doubles in the same q rows_pad npad elements: they still fit).
+template <typename T>
+int do_condition_predict_gradcov(hipStream_t st, const Ws& w, const void* x, const void* sr, const double* theta, const void* state,
+                                 int m, const void* xn, const void* gstate, int n0, const void* x0, void* scratch, double* dghat,
+                                 double* gamma, const double* wt, double* M, int ldo) {
+    const int dtype = sizeof(T) == 4 ? LCGP_F32 : LCGP_F64;
+    const CondLay L = cond_carve(dtype, w.n, w.q, m);
+    const CondGradLay G = cond_grad_carve(w.n, w.q, m);
+    const int mpad = L.mpad, rows_pad = hess_rows_pad(n0, w.d), tw = w.d + 3 + w.p, kp = w.npad + mpad;
+    const T* Un = (const T*)((const char*)state + L.off_U);
+    const T* Wi = (const T*)((const char*)state + L.off_W);
+    PgradCond<T> cs;
+    cs.zd = (const double*)((const char*)gstate + G.off_z);
+    cs.xn = (const T*)xn; cs.m = m;
+    cs.wv = (const double*)((const char*)gstate + G.off_w); cs.mpad = mpad;
+    cs.R = nullptr; cs.rslab = 0;
+    const int wide = w.d > 16;
+    dim3 pgrid((n0 + PG_ROWS - 1) / PG_ROWS, w.q, wide ? (w.d + DMAX - 1) / DMAX : 1);
+    for_dim(w.d, [&](auto dd) {
+        for_kern(w.kern, [&](auto kern) {
+            hipLaunchKernelGGL((pgrad_cond_mean_kernel<T, decltype(dd)::value, decltype(kern)::value>), pgrid, dim3(256), 0, st,
+                               (const T*)x0, n0, (const T*)x, (const T*)sr, w.n, w.d, theta, tw, w.npad, ldo, dghat, cs);
+        });
+    });
+    CHECK_LAUNCH("pgrad_cond_mean_kernel");
+    T* Pw = (T*)scratch;
+    int rc = cond_rows_form<T>(st, w, x, sr, theta, Un, Wi, m, mpad, xn, n0, x0, Pw);
+    if (rc) return rc;
+    const size_t pslab = (size_t)rows_pad * kp;
+    const int nblk = (w.d + PH_B - 1) / PH_B, npair = nblk * (nblk + 1) / 2, nwg = (n0 + 3) / 4, tri = w.d * (w.d + 1) / 2;
+    double* part = (double*)(Pw + pslab * w.q);         // the DX slabs
+    hipLaunchKernelGGL((gradcov_kernel<T>), dim3(nwg, w.q, npair), dim3(256), 0, st, (const T*)Pw, pslab, kp, w.npad + m, n0, w.d,
                        theta, tw, gradcov_kappa(w.kern), ldo, gamma, wt, part);
     CHECK_LAUNCH("gradcov_kernel");
     if (wt) {
@@ -7459,6 +7686,83 @@ int lcgp_condition_predict_grad(void* stream, int dtype, int kernel_id, int n, i
                                                    dgvar, ldo)
                : do_condition_predict_grad<float>(st, w, x, sr, theta, state, m, xn, grad_state, n0, x0, scratch, ghat, gvar, dghat,
                                                   dgvar, ldo);
+}
+
+static int check_cond_rows(int dtype, int n, int d, int q_local, int m, int n0) {
+    if (dtype != LCGP_F64 && dtype != LCGP_F32) return bad("dtype must be 0 (f64) or 1 (f32)");
+    if (n < 1 || q_local < 1) return bad("n, q_local must be >= 1");
+    if (d < 1 || d > DWIDE) return bad("d must be in [1, 126]");
+    if (m < 1) return bad("m < 1");
+    if (n0 < 1) return bad("n0 < 1");
+    if ((long long)n0 * d > LCGP_HESS_MAX_ROWS) return bad("n0 * d must be <= LCGP_HESS_MAX_ROWS: pass the new inputs in chunks");
+    return 0;
+}
+
+int lcgp_condition_predict_hess_scratch_bytes(int dtype, int n, int d, int q_local, int m, int n0, size_t* bytes) {
+    int rc = check_cond_rows(dtype, n, d, q_local, m, n0);
+    if (rc) return rc;
+    if (!bytes) return bad("bytes is NULL");
+    *bytes = cond_predict_scratch(dtype, n, q_local, m, n0) + cond_rows_scratch(dtype, n, d, q_local, m, n0);
+    return 0;
+}
+
+int lcgp_condition_predict_hess(void* stream, int dtype, int kernel_id, int n, int d, int p, int q_local, const void* x,
+                                const void* sr, const double* theta, const void* workspace, const void* state, int m,
+                                const void* xn, const void* grad_state, int n0, const void* x0, void* scratch, size_t scratch_bytes,
+                                double* ghat, double* gvar, double* dghat, double* dgvar, double* d2ghat, double* d2gvar,
+                                int out_stride) {
+    int rc = check_common(dtype, n, d, p, q_local, kernel_id);
+    if (rc) return rc;
+    rc = check_cond_rows(dtype, n, d, q_local, m, n0);
+    if (rc) return rc;
+    if (!x || !theta || !workspace || !state || !xn || !grad_state || !x0 || !scratch || !ghat || !gvar || !dghat || !dgvar ||
+        !d2ghat || !d2gvar)
+        return bad("NULL pointer");
+    if (out_stride != 0 && out_stride < n0) return bad("out_stride must be 0 (= n0) or >= n0");
+    if (scratch_bytes < cond_predict_scratch(dtype, n, q_local, m, n0) + cond_rows_scratch(dtype, n, d, q_local, m, n0))
+        return bad("scratch is smaller than lcgp_condition_predict_hess_scratch_bytes(dtype, n, d, q_local, m, n0)");
+    const int ldo = out_stride ? out_stride : n0;
+    Ws w = carve(dtype, n, d, p, q_local, (void*)workspace);
+    w.kern = kernel_id;
+    hipStream_t st = (hipStream_t)stream;
+    return dtype == LCGP_F64
+               ? do_condition_predict_hess<double>(st, w, x, sr, theta, state, m, xn, grad_state, n0, x0, scratch, ghat, gvar, dghat,
+                                                   dgvar, d2ghat, d2gvar, ldo)
+               : do_condition_predict_hess<float>(st, w, x, sr, theta, state, m, xn, grad_state, n0, x0, scratch, ghat, gvar, dghat,
+                                                  dgvar, d2ghat, d2gvar, ldo);
+}
+
+int lcgp_condition_predict_gradcov_scratch_bytes(int dtype, int n, int d, int q_local, int m, int n0, size_t* bytes) {
+    int rc = check_cond_rows(dtype, n, d, q_local, m, n0);
+    if (rc) return rc;
+    if (!bytes) return bad("bytes is NULL");
+    *bytes = cond_rows_scratch(dtype, n, d, q_local, m, n0);
+    return 0;
+}
+
+int lcgp_condition_predict_gradcov(void* stream, int dtype, int kernel_id, int n, int d, int p, int q_local, const void* x,
+                                   const void* sr, const double* theta, const void* workspace, const void* state, int m,
+                                   const void* xn, const void* grad_state, int n0, const void* x0, void* scratch,
+                                   size_t scratch_bytes, double* dghat, double* gamma, const double* w, double* M, int out_stride) {
+    int rc = check_common(dtype, n, d, p, q_local, kernel_id);
+    if (rc) return rc;
+    rc = check_cond_rows(dtype, n, d, q_local, m, n0);
+    if (rc) return rc;
+    if (!x || !theta || !workspace || !state || !xn || !grad_state || !x0 || !scratch || !dghat) return bad("NULL pointer");
+    if (!gamma && !w) return bad("NULL pointer: gamma may only be NULL when w is given");
+    if ((w != nullptr) != (M != nullptr)) return bad("w and M go together: both or neither");
+    if (out_stride != 0 && out_stride < n0) return bad("out_stride must be 0 (= n0) or >= n0");
+    if (scratch_bytes < cond_rows_scratch(dtype, n, d, q_local, m, n0))
+        return bad("scratch is smaller than lcgp_condition_predict_gradcov_scratch_bytes(dtype, n, d, q_local, m, n0)");
+    const int ldo = out_stride ? out_stride : n0;
+    Ws ws = carve(dtype, n, d, p, q_local, (void*)workspace);
+    ws.kern = kernel_id;
+    hipStream_t st = (hipStream_t)stream;
+    return dtype == LCGP_F64
+               ? do_condition_predict_gradcov<double>(st, ws, x, sr, theta, state, m, xn, grad_state, n0, x0, scratch, dghat, gamma, w,
+                                                      M, ldo)
+               : do_condition_predict_gradcov<float>(st, ws, x, sr, theta, state, m, xn, grad_state, n0, x0, scratch, dghat, gamma, w,
+                                                     M, ldo);
 }
 
 int lcgp_loo(void* stream, int dtype, int n, int d, int p, int q_local, const void* sr, const double* theta,

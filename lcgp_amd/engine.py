@@ -763,6 +763,95 @@ class HotPathEngine:
                     "lcgp_condition_predict_grad")
             return out, jac
 
+    def condition_predict_hess_block(self, state, x0s):
+        """(block, jac, hess) float64 DEVICE tensors of the view `state` (condition_begin) at standardised x0s: block and jac
+        bitwise those of condition_predict_grad_block(state, x0s); hess (2, q_local, n0, d (d + 1) / 2) = [d2ghat'; d2gvar'], the
+        packed lower triangles of the Hessians with respect to x0s in predict_hess_block's layout
+        (lcgp_condition_predict_hess).  Chunked as predict_hess_block is: max(128, PREDICT_CHUNK // d) inputs per pass, a short
+        last pass moved back over its predecessor, so the results do not depend on PREDICT_CHUNK.  The scratch holds that of
+        condition_predict_grad_block and q_local (chunk d)_pad (2 npad + 3 mpad) elements; raises ValueError when it does not fit
+        in the free device memory.  The base factorisation must still be the one the state was built from."""
+        torch = self.torch
+        if not self.is_current(state['theta']):
+            raise RuntimeError("the conditioned view does not belong to the factorisation in the workspace")
+        x0s = np.ascontiguousarray(x0s, np.float64)
+        n0, d, m = x0s.shape[0], self.d, state['m']
+        assert x0s.ndim == 2 and x0s.shape[1] == d and n0 >= 1
+        tri = d * (d + 1) // 2
+        chunk = min(n0, max(128, PREDICT_CHUNK // d))
+        with torch.cuda.device(self.device):
+            gs = self._condition_grad_state(state)
+            x0d = torch.as_tensor(x0s).to(self.device, self.tdtype).contiguous()
+            scratch = self._grow_scratch(
+                self._nbytes("lcgp_condition_predict_hess_scratch_bytes", self.dtype, self.n, d, self.q_local, m, chunk),
+                ("the conditioned Hessians of %d new inputs per pass" % chunk,
+                 "%d components of %d x (n + m), twice" % (self.q_local, chunk * (d + 1)), "lower lcgp_amd.engine.PREDICT_CHUNK"))
+            out = torch.empty((2, self.q_local, n0), dtype=torch.float64, device=self.device)
+            jac = torch.empty((2, self.q_local, n0, d), dtype=torch.float64, device=self.device)
+            hess = torch.empty((2, self.q_local, n0, tri), dtype=torch.float64, device=self.device)
+            st, xp, srp, thp, wsp = self._stream(), self._p(self.x), self._p(self.sr), self._p(self.theta_dev), self._p(self.workspace)
+            for lo in range(0, n0, chunk):
+                rows = min(chunk, n0 - lo)
+                if rows < 128 <= n0:
+                    lo, rows = n0 - 128, 128
+                x0p = C.c_void_p(x0d.data_ptr() + lo * d * x0d.element_size())
+                ptrs = [C.c_void_p(t[h].data_ptr() + 8 * lo * w) for t, w in ((out, 1), (jac, d), (hess, tri)) for h in (0, 1)]
+                _hip.check(self.lib.lcgp_condition_predict_hess(
+                    st, self.dtype, self.kernel_id, self.n, d, self.p, self.q_local, xp, srp, thp, wsp, self._p(state['state']), m,
+                    self._p(state['xn']), self._p(gs), rows, x0p, self._p(scratch), scratch.numel(), *ptrs, n0),
+                    "lcgp_condition_predict_hess")
+            return out, jac, hess
+
+    def condition_grad_cov_block(self, state, x0s, w=None, per_point=True):
+        """(dghat, gamma, M) float64 DEVICE tensors of the view `state` (condition_begin) at standardised x0s, in grad_cov_block's
+        layout and with its arguments (lcgp_condition_predict_gradcov): dghat (q_local, n0, d) bitwise that of
+        condition_predict_grad_block(state, x0s); gamma the packed posterior covariance of the latent gradient given the
+        view's runs, or None with per_point=False; M = sum_i w_i gamma[:, i], reduced on the device in a fixed order, or None
+        without w.  Chunked as grad_cov_block is; the rows a moved-back pass repeats weigh zero in it.  The scratch holds
+        q_local (chunk d)_pad (2 npad + 3 mpad) elements; raises ValueError when it does not fit in the free device memory."""
+        torch = self.torch
+        if not self.is_current(state['theta']):
+            raise RuntimeError("the conditioned view does not belong to the factorisation in the workspace")
+        x0s = np.ascontiguousarray(x0s, np.float64)
+        n0, d, m = x0s.shape[0], self.d, state['m']
+        assert x0s.ndim == 2 and x0s.shape[1] == d and n0 >= 1
+        if w is None and not per_point:
+            raise ValueError("condition_grad_cov_block: per_point=False needs weights")
+        tri = d * (d + 1) // 2
+        chunk = min(n0, max(128, PREDICT_CHUNK // d))
+        with torch.cuda.device(self.device):
+            gs = self._condition_grad_state(state)
+            x0d = torch.as_tensor(x0s).to(self.device, self.tdtype).contiguous()
+            scratch = self._grow_scratch(
+                self._nbytes("lcgp_condition_predict_gradcov_scratch_bytes", self.dtype, self.n, d, self.q_local, m, chunk),
+                ("the conditioned gradient covariances of %d new inputs per pass" % chunk,
+                 "%d components of %d x (n + m), twice" % (self.q_local, chunk * d), "lower lcgp_amd.engine.PREDICT_CHUNK"))
+            dghat = torch.empty((self.q_local, n0, d), dtype=torch.float64, device=self.device)
+            gamma = torch.empty((self.q_local, n0, tri), dtype=torch.float64, device=self.device) if per_point else None
+            M = wd = None
+            if w is not None:
+                w = np.ascontiguousarray(w, np.float64).reshape(-1)
+                assert w.shape == (n0,)
+                wd = torch.as_tensor(w).to(self.device)
+                M = torch.zeros((self.q_local, tri), dtype=torch.float64, device=self.device)
+            st, xp, srp, thp, wsp = self._stream(), self._p(self.x), self._p(self.sr), self._p(self.theta_dev), self._p(self.workspace)
+            for lo in range(0, n0, chunk):
+                rows = min(chunk, n0 - lo)
+                wp = None if wd is None else C.c_void_p(wd.data_ptr() + 8 * lo)
+                if rows < 128 <= n0:
+                    if wd is not None:                  # the rows n0 - 128 .. lo were summed by the pass before
+                        wl = wd[n0 - 128:].clone()
+                        wl[:lo - (n0 - 128)] = 0.0
+                        wp = self._p(wl)
+                    lo, rows = n0 - 128, 128
+                x0p = C.c_void_p(x0d.data_ptr() + lo * d * x0d.element_size())
+                _hip.check(self.lib.lcgp_condition_predict_gradcov(
+                    st, self.dtype, self.kernel_id, self.n, d, self.p, self.q_local, xp, srp, thp, wsp, self._p(state['state']), m,
+                    self._p(state['xn']), self._p(gs), rows, x0p, self._p(scratch), scratch.numel(),
+                    C.c_void_p(dghat.data_ptr() + 8 * lo * d), None if gamma is None else C.c_void_p(gamma.data_ptr() + 8 * lo * tri),
+                    wp, None if M is None else self._p(M), n0), "lcgp_condition_predict_gradcov")
+            return dghat, gamma, M
+
     # ------------------------------------------------------------------------------------------------
     # closed-form cross-validation at fixed parameters (lcgp_hip.h: lcgp_loo, lcgp_cv_gather / lcgp_cv_apply)
     def loo_block(self):

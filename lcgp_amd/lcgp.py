@@ -96,9 +96,10 @@ class _PredictFn2(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x0, model):
         x0c = _cpu64(x0)
+        host = getattr(model, 'base', model)        # (a ConditionedLCGP: the output map is its base model's)
         ghat, gvar, dghat, dgvar = model._latent_predict_grad(x0c)
-        outs = model._outputs(ghat, gvar)
-        dyp, dycv = model._output_jacobians(dghat, dgvar)
+        outs = host._outputs(ghat, gvar)
+        dyp, dycv = host._output_jacobians(dghat, dgvar)
         ctx.model, ctx.x0c = model, x0c
         ctx.jac = (torch.as_tensor(dyp), torch.as_tensor(dycv))
         ctx.save_for_backward(x0)
@@ -351,13 +352,61 @@ class ConditionedLCGP:
         dyp, dycv = self.base._output_jacobians(dghat, dgvar)
         return _t(dyp), _t(dycv.copy()), _t(dycv)
 
-    def predict_differentiable(self, x0):
+    def predict_differentiable(self, x0, order=1):
         """(ypred, ypredvar, yconfvar) (p, n0) as predict() returns them, float64 on x0's device, differentiable with respect to
-        a requires_grad x0 (any device) through torch.autograd to first order, as LCGP.predict_differentiable(order=1): the
-        backward pass multiplies with the Jacobians of predict_grad() saved by the forward pass.  A double backward
-        (create_graph=True) raises."""
+        a requires_grad x0 (any device) through torch.autograd, as LCGP.predict_differentiable: the backward pass multiplies
+        with the Jacobians of predict_grad() saved by the forward pass.  order=1: a double backward (create_graph=True)
+        raises.  order=2: the backward pass is itself differentiable (torch.autograd.functional.hessian, gradgradcheck); the
+        Hessians come from one predict_hess() pass of this view, made only when a double backward runs.  A third derivative
+        raises."""
+        if order not in (1, 2):
+            raise ValueError('predict_differentiable: order must be 1 or 2, got %r' % (order,))
         x0 = x0 if isinstance(x0, torch.Tensor) else torch.as_tensor(np.asarray(x0, F64))
-        return _ViewPredictFn.apply(x0, self)
+        return (_ViewPredictFn if order == 1 else _PredictFn2).apply(x0, self)
+
+    def _latent_predict_hess(self, x0):
+        """ghat, gvar, dghat, dgvar and the Hessians d2ghat, d2gvar (q, n0, d, d) of the view with respect to the STANDARDISED
+        inputs, exactly symmetric: LCGP._latent_predict_hess on the view (lcgp_condition_predict_hess)"""
+        base = self.base
+        x0s = base._x0_2d(x0, 'x0')
+        self._require_current()
+        eng, st = self._engine, self._state
+        return base._latent_hess_result(x0s, None if eng is None else lambda: eng.condition_predict_hess_block(st, x0s))
+
+    def predict_hess(self, x0):
+        """LCGP.predict_hess() of the conditioned model: (d2ypred, d2ypredvar, d2yconfvar), each (p, n0, d, d) CPU float64,
+        exactly symmetric, on the raw input and output scales; d2ypredvar = d2yconfvar.  Equal, to rounding, to predict_hess()
+        of a model built on the augmented data at the same parameters; nothing is refactorised.  The Hessian
+        of the continuous prediction surface (same = 0), also at training inputs and at the view's own new inputs; the
+        Matern-3/2 kernel has its kinks where a coordinate of x0 equals a training input's or one of the view's inputs'.
+        RuntimeError when the view is stale."""
+        _, _, _, _, d2ghat, d2gvar = self._latent_predict_hess(x0)
+        d2yp, d2ycv = self.base._output_hessians(d2ghat, d2gvar)
+        return _t(d2yp), _t(d2ycv.copy()), _t(d2ycv)
+
+    def predict_grad_cov(self, x0, latent=False):
+        """LCGP.predict_grad_cov() of the conditioned model: (p, n0, d, d) CPU float64, exactly symmetric, the posterior
+        covariance of the gradient of the noise-free output at each new input GIVEN the base model's data and this view's new
+        runs; latent=True: Gamma' (q, n0, d, d) in standardised inputs,
+            Gamma'_k[i, l, m] = delta_lm c_k kappa / ell_l^2 - D_k (P'_il . P'_im) / (ell_l ell_m)
+        with the rows P' of predict_hess() widened by the view's m columns (lcgp_condition_predict_gradcov).
+        Gamma of the base model minus Gamma' is positive semidefinite: conditioning cannot add gradient uncertainty.
+        RuntimeError when the view is stale."""
+        base = self.base
+        x0s = base._x0_2d(x0, 'x0')
+        self._require_current()
+        eng, st = self._engine, self._state
+        return base._grad_cov_result(x0s, None if eng is None else lambda: eng.condition_grad_cov_block(st, x0s), latent)[1]
+
+    def active_subspace(self, x_ref, weights=None, outputs=None):
+        """LCGP.active_subspace() of the conditioned model: the ActiveSubspace over x_ref after the view's new runs; cov_part
+        shrinks by what the runs settled.  Arguments, defaults, checks and the result are the model's."""
+        def engine():
+            self._require_current()
+            return self._engine
+        st = self._state
+        return self.base._active_subspace(x_ref, weights, outputs, engine,
+                                          lambda eng, x0s, w: eng.condition_grad_cov_block(st, x0s, w, per_point=False))
 
     def calibration(self, y_obs, obs_var, include_noise=True):
         """LCGP.calibration() of the conditioned model: a CalibrationTarget for one field observation whose loglik(theta),
@@ -2256,12 +2305,22 @@ class LCGP:
         zero-padded block gathers them; the packed lower triangles are mirrored here, so the Hessians are exactly symmetric.
         No nugget term, as in _latent_predict_grad."""
         x0s, _ = self._standardise_x0(x0)
+        eng = self._ensure_aux()
+        res = self._latent_hess_result(x0s, None if eng is None else lambda: eng.predict_hess_block(x0s))
+        ghat, gvar, dghat, dgvar, d2ghat, d2gvar = res
+        self.ghat, self.gvar = _t(ghat), _t(gvar)
+        self.dghat, self.dgvar = _t(dghat), _t(dgvar)
+        self.d2ghat, self.d2gvar = _t(d2ghat), _t(d2gvar)
+        return res
+
+    def _latent_hess_result(self, x0s, block):
+        """_latent_predict_hess's gather and mirroring for this rank's (blk, jac, hess) = block() (None on a rank without
+        components): shared with ConditionedLCGP"""
         n0, d = x0s.shape
         tri = d * (d + 1) // 2
-        eng = self._ensure_aux()
         loc = None
-        if eng is not None:
-            blk, jac, hess = eng.predict_hess_block(x0s)
+        if block is not None:
+            blk, jac, hess = block()
             loc = torch.cat([t.movedim(1, 0).reshape(t.shape[1], -1) for t in (blk, jac, hess)], dim=1)
         both = self._gather_components(loc, (2 * n0 * (1 + d + tri),))
         q = int(self.q)
@@ -2272,9 +2331,6 @@ class LCGP:
         full = np.empty((q, 2, n0, d, d), F64)
         full[..., il, im] = packed
         full[..., im, il] = packed
-        self.ghat, self.gvar = _t(ghat), _t(gvar)
-        self.dghat, self.dgvar = _t(jac[:, 0]), _t(jac[:, 1])
-        self.d2ghat, self.d2gvar = _t(full[:, 0]), _t(full[:, 1])
         return ghat, gvar, jac[:, 0], jac[:, 1], full[:, 0], full[:, 1]
 
     def _output_hessians(self, d2ghat, d2gvar):
@@ -2333,23 +2389,30 @@ class LCGP:
         factorisation of the current parameters (lcgp_predict_gradcov), in the engine's dtype.  Sets self.dghat to what
         predict_grad(x0) sets."""
         x0s = self._x0_2d(x0, 'x0')
+        eng = self._ensure_aux()
+        dghat, cov = self._grad_cov_result(x0s, None if eng is None else lambda: eng.grad_cov_block(x0s), latent)
+        self.dghat = _t(dghat)
+        return cov
+
+    def _grad_cov_result(self, x0s, block, latent):
+        """predict_grad_cov's gather and output map for this rank's (dghat, gamma, _) = block() (None on a rank without
+        components) -> (dghat (q, n0, d), the result): shared with ConditionedLCGP"""
         n0, d = x0s.shape
         tri = d * (d + 1) // 2
-        eng = self._ensure_aux()
         loc = None
-        if eng is not None:
-            dghat, gamma, _ = eng.grad_cov_block(x0s)
+        if block is not None:
+            dghat, gamma, _ = block()
             loc = torch.cat([dghat.reshape(dghat.shape[0], -1), gamma.reshape(gamma.shape[0], -1)], dim=1)
         both = self._gather_components(loc, (n0 * (d + tri),))
         q = int(self.q)
-        self.dghat = _t(both[:, :n0 * d].reshape(q, n0, d))
+        dghat = both[:, :n0 * d].reshape(q, n0, d)
         G = self._unpack_lower(both[:, n0 * d:].reshape(q, n0, tri), d)
         if latent:
-            return _t(G)
+            return dghat, _t(G)
         W, _, scale, _ = self._output_map()
         rng = (_np(self.x_max) - _np(self.x_min)).reshape(-1)
         cov = np.einsum('ka,kilm->ailm', W ** 2, G) * (scale ** 2)[:, None, None, None] / (rng[:, None] * rng[None, :])
-        return _t(cov)
+        return dghat, _t(cov)
 
     def active_subspace(self, x_ref, weights=None, outputs=None):
         """Active-subspace matrix of each selected output over a reference sample, with the emulator's uncertainty included:
@@ -2362,6 +2425,12 @@ class LCGP:
           sum 1 (default uniform), as in variance_reduction().  outputs: output indices (default all p).
         The weighted sum of the covariances is reduced on the GPU (the n_ref x d x d tensor is never formed); the mean part is
         formed on the host from the gathered latent gradients, n_ref x d per component."""
+        return self._active_subspace(x_ref, weights, outputs, self._ensure_aux,
+                                     lambda eng, x0s, w: eng.grad_cov_block(x0s, w, per_point=False))
+
+    def _active_subspace(self, x_ref, weights, outputs, engine, block):
+        """active_subspace's checks, gather and assembly; engine() is called behind the checks and gives this rank's engine
+        (None on a rank without components), block(engine, x0s, w) its (dghat, _, M): shared with ConditionedLCGP"""
         x0s = self._x0_2d(x_ref, 'x_ref')
         n0, d = x0s.shape
         if weights is None:
@@ -2380,10 +2449,10 @@ class LCGP:
         if any(a < 0 or a >= p for a in outputs):
             raise ValueError('outputs must be indices in [0, %d)' % p)
         tri = d * (d + 1) // 2
-        eng = self._ensure_aux()
+        eng = engine()
         loc = None
         if eng is not None:
-            dghat, _, M = eng.grad_cov_block(x0s, w, per_point=False)
+            dghat, _, M = block(eng, x0s, w)
             loc = torch.cat([dghat.reshape(dghat.shape[0], -1), M], dim=1)
         both = self._gather_components(loc, (n0 * d + tri,))
         q = int(self.q)

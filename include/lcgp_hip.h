@@ -929,6 +929,31 @@ int lcgp_calib_rows(void* stream, int q, int d, int n0,
                     const double* inv_range /* d, device; NULL = ones */,
                     double* ll /* n0 */, double* dll /* n0 x d or NULL */, double* sens /* 2 x q x n0 (s then v) or NULL */);
 
+/* Calibration rows to second order: lcgp_calib_rows plus the Hessian of ll[i] in the row's input.  With
+ *     B = M - R^T R     (= Phi_s^T Sigma_i^-1 Phi_s, q x q symmetric; v_k = 1/2 s_k^2 - 1/2 B_kk)
+ * the second derivatives of ll in the latents are
+ *     d2 ll / d ghat_k d ghat_j = -B_kj,   d2 ll / d ghat_k d gvar_j = -B_kj s_j,   d2 ll / d gvar_k d gvar_j = 1/2 B_kj^2 - s_k s_j B_kj
+ * and with P = dghat[:, i, :], V = dgvar[:, i, :] (q x d) and the packed Hessians of lcgp_predict_hess (entry (l, m <= l) at
+ * l (l + 1) / 2 + m, tri = d (d + 1) / 2 per row)
+ *     d2ll[i, lm] = inv_range_l inv_range_m ( sum_k s_k d2ghat[k, i, lm] + v_k d2gvar[k, i, lm]
+ *                     - (P^T B P)_lm - (P^T B diag(s) V)_lm - (P^T B diag(s) V)_ml + (V^T (1/2 B o B - (s s^T) o B) V)_lm )
+ * packed the same way.  No division by gvar: rows with gvar = 0 or slightly below are ordinary rows.
+ * Two launches on one stream: lcgp_calib_rows' own launch writes ll, dll and sens, so these are BITWISE lcgp_calib_rows' for
+ * every q; then one wavefront per row (any q in [1, 64], 16 q^2 bytes of LDS) refactorises K, forms R, s, v and B (in L's
+ * place) and contracts column by column of the triangle: O(q^3 + q^2 d + q d^2) per row.  The second launch reads none of the
+ * first one's outputs and runs when d2ll or Bout is given.  float64, no atomics, fixed summation order: a row's results are
+ * bitwise independent of the content of the outputs on entry, of how a caller splits the rows over calls and of which optional
+ * outputs are requested.  Limits and checks are lcgp_calib_rows'; arguments are checked before any launch. */
+int lcgp_calib_hess_rows(void* stream, int q, int d, int n0,
+                         const double* ghat, const double* gvar,      /* q rows of n0, in_stride apart (0 = n0) */
+                         const double* dghat, const double* dgvar,    /* q x n0 x d, row k at k * in_stride * d */
+                         const double* d2ghat, const double* d2gvar,  /* q x n0 x tri, row k at k * in_stride * tri; needed for d2ll */
+                         int in_stride,
+                         const double* M /* q x q, device */, const double* b /* q, device */, double c0, double lognorm,
+                         const double* inv_range /* d, device; NULL = ones */,
+                         double* ll /* n0 */, double* dll /* n0 x d or NULL */, double* d2ll /* n0 x tri or NULL */,
+                         double* sens /* 2 x q x n0 (s then v) or NULL */, double* Bout /* n0 x q x q or NULL */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -130,6 +130,8 @@ SIGNATURES = {
     "lcgp_condition_predict_cov": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, C.c_size_t,
                                         _vp, _d]),
     "lcgp_calib_rows": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _d, _d, _vp, _vp, _vp, _vp]),
+    "lcgp_calib_hess_rows": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _d, _d, _vp, _vp, _vp, _vp, _vp,
+                                  _vp]),
 }
 
 _lib = None

@@ -6953,17 +6953,44 @@ __device__ __forceinline__ double calib_lane(double v, int lane) {
     return __hiloint2double(hi, lo);
 }
 
+// acc - sum_{m < n} a[m * q] b[m * q] in four partial sums over m mod 4: chains of n / 4 roundings, not n.  The second launch
+// of lcgp_calib_hess_rows solves for R and forms B with it: at q = 64 single chains leave B's tolerance, 4 eps (|M| + |R|^T |R|),
+// by a tenth on some rows.  Symmetric in a and b bit for bit.
+__device__ __forceinline__ double calib_sub_dot4(double acc, const double* a, const double* b, int q, int n) {
+    double a1 = 0.0, a2 = 0.0, a3 = 0.0;
+    int m = 0;
+    for (; m + 3 < n; m += 4) {
+        acc -= a[m * q] * b[m * q];
+        a1 -= a[(m + 1) * q] * b[(m + 1) * q];
+        a2 -= a[(m + 2) * q] * b[(m + 2) * q];
+        a3 -= a[(m + 3) * q] * b[(m + 3) * q];
+    }
+    for (; m < n; ++m) acc -= a[m * q] * b[m * q];
+    return (acc + a1) + (a2 + a3);
+}
+
 // 8 < q <= 64: one wavefront (= one workgroup) per row, lane k owns component k: row k of the left-looking Cholesky, then
 // column k of R.  Dynamic LDS, 2 q^2 doubles: LT[m * q + k] = L[k][m] (the factor stored transposed: lanes read consecutive
 // addresses, the pivot row is a broadcast, so no padding is needed) and R[j * q + k] (diag(h) M, solved in place, each lane
 // its own column).  The forward substitution for u rides on the factorisation's steps.
-__global__ __launch_bounds__(64) void calib_rows_wave_kernel(int q, int d, int n0, const double* __restrict__ ghat,
-                                                              const double* __restrict__ gvar, const double* __restrict__ dghat,
-                                                              const double* __restrict__ dgvar, size_t ld,
-                                                              const double* __restrict__ M, const double* __restrict__ b, double c0,
-                                                              double lognorm, const double* __restrict__ inv_range,
-                                                              double* __restrict__ ll, double* __restrict__ dll,
-                                                              double* __restrict__ sens) {
+// HESS (lcgp_calib_hess_rows' second launch): the same steps to s, v and R, nothing written to ll / dll / sens; then B = M - R^T R
+// takes L's place in LDS (B[j * q + k] = B_kj, lane k its own column; the products R_mk R_mj commute and M is symmetric, so B
+// is bitwise symmetric) and per column c <= l of the packed triangle
+//     x1 = B P[:, c],  x2 = B (s o V[:, c]),  x3 = (B o B) V[:, c]          (lane k owns entry k; P = dghat, V = dgvar of the row)
+//     alpha = -(x1 + x2),  beta = 1/2 x3 - s o (x1 + x2)
+//     d2ll[l, c] = inv_range_l inv_range_c sum_k (s_k d2ghat[k, l, c] + v_k d2gvar[k, l, c] + P_kl alpha_k + V_kl beta_k)
+// with the lanes striding over l >= c: the four matrix terms of the header folded into two q-vectors per column by B's
+// symmetry.  O(q^3) for B, O(q^2 d + q d^2) for the contraction, nothing of size d x d x q^2.
+template <bool HESS>
+__device__ __forceinline__ void calib_wave_row(int q, int d, int n0, const double* __restrict__ ghat,
+                                               const double* __restrict__ gvar, const double* __restrict__ dghat,
+                                               const double* __restrict__ dgvar, size_t ld,
+                                               const double* __restrict__ M, const double* __restrict__ b, double c0,
+                                               double lognorm, const double* __restrict__ inv_range,
+                                               double* __restrict__ ll, double* __restrict__ dll,
+                                               double* __restrict__ sens, const double* __restrict__ d2ghat,
+                                               const double* __restrict__ d2gvar, double* __restrict__ d2ll,
+                                               double* __restrict__ Bout) {
     extern __shared__ __attribute__((aligned(16))) char calib_lds[];
     double* LT = (double*)calib_lds;
     double* R = LT + q * q;
@@ -7002,8 +7029,10 @@ __global__ __launch_bounds__(64) void calib_rows_wave_kernel(int q, int d, int n
         uu += uj * uj;
         __syncthreads();        // (one wave per workgroup) row j of LT is read by every lane from the next step on
     }
-    if (k == 0) ll[i] = -0.5 * (c0 - 2.0 * bg + gmg - uu + 2.0 * sumlog + lognorm);
-    if (!dll && !sens) return;
+    if (!HESS) {
+        if (k == 0) ll[i] = -0.5 * (c0 - 2.0 * bg + gmg - uu + 2.0 * sumlog + lognorm);
+        if (!dll && !sens) return;
+    }
     // x = L^-T u, one wave sum per step: lane m > j holds its final x_m and reads L[m][j] = LT[j * q + m] (consecutive addresses)
     double xk = 0.0;
     for (int j = q - 1; j >= 0; --j) {
@@ -7018,7 +7047,11 @@ __global__ __launch_bounds__(64) void calib_rows_wave_kernel(int q, int d, int n
         if (on) {
             ma += M[j * q + k] * aj;
             double acc = R[j * q + k];
-            for (int m = 0; m < j; ++m) acc -= LT[m * q + j] * R[m * q + k];
+            if (HESS) {
+                acc = calib_sub_dot4(acc, LT + j, R + k, q, j);
+            } else {
+                for (int m = 0; m < j; ++m) acc -= LT[m * q + j] * R[m * q + k];
+            }
             const double y = acc / LT[j * q + j];
             R[j * q + k] = y;
             tk += y * y;
@@ -7026,24 +7059,101 @@ __global__ __launch_bounds__(64) void calib_rows_wave_kernel(int q, int d, int n
     }
     const double s = w - ma;
     const double v = 0.5 * s * s - 0.5 * (mkk - tk);
-    if (sens && on) {
-        sens[(size_t)k * n0 + i] = s;
-        sens[(size_t)(q + k) * n0 + i] = v;
-    }
-    if (dll) {
-        for (int l0 = 0; l0 < d; l0 += 64) {
-            const int l = l0 + k;
-            double acc = 0.0;
-            for (int c = 0; c < q; ++c) {
-                const double sc = calib_lane(s, c), vc = calib_lane(v, c);
-                if (l < d) {
-                    const size_t at = ((size_t)c * ld + i) * d + l;
-                    acc += sc * dghat[at] + vc * dgvar[at];
+    if (!HESS) {
+        if (sens && on) {
+            sens[(size_t)k * n0 + i] = s;
+            sens[(size_t)(q + k) * n0 + i] = v;
+        }
+        if (dll) {
+            for (int l0 = 0; l0 < d; l0 += 64) {
+                const int l = l0 + k;
+                double acc = 0.0;
+                for (int c = 0; c < q; ++c) {
+                    const double sc = calib_lane(s, c), vc = calib_lane(v, c);
+                    if (l < d) {
+                        const size_t at = ((size_t)c * ld + i) * d + l;
+                        acc += sc * dghat[at] + vc * dgvar[at];
+                    }
                 }
+                if (l < d) dll[(size_t)i * d + l] = inv_range ? inv_range[l] * acc : acc;
             }
-            if (l < d) dll[(size_t)i * d + l] = inv_range ? inv_range[l] * acc : acc;
+        }
+        return;
+    }
+    __syncthreads();            // R is complete and L is dead: B takes L's place
+    double* B = LT;
+    if (on) {
+        for (int j = 0; j < q; ++j) {
+            const double acc = calib_sub_dot4(M[j * q + k], R + k, R + j, q, q);
+            B[j * q + k] = acc;
+            if (Bout) Bout[((size_t)i * q + j) * q + k] = acc;
         }
     }
+    __syncthreads();
+    if (!d2ll) return;
+    const int tri = d * (d + 1) / 2;
+    for (int c = 0; c < d; ++c) {
+        const size_t at = ((size_t)k * ld + i) * d + c;
+        const double pc = on ? dghat[at] : 0.0, vc = on ? dgvar[at] : 0.0;
+        const double sv = s * vc;
+        double x1 = 0.0, x2 = 0.0, x3 = 0.0;
+        for (int j = 0; j < q; ++j) {
+            const double pj = calib_lane(pc, j), svj = calib_lane(sv, j), vj = calib_lane(vc, j);
+            if (on) {
+                const double bkj = B[j * q + k];
+                x1 += bkj * pj;
+                x2 += bkj * svj;
+                x3 += bkj * bkj * vj;
+            }
+        }
+        const double alpha = -(x1 + x2);
+        const double beta = 0.5 * x3 - s * (x1 + x2);
+        const double irc = inv_range ? inv_range[c] : 1.0;
+        for (int l0 = c; l0 < d; l0 += 64) {
+            const int l = l0 + k;
+            const bool in = l < d;
+            const size_t pk = (size_t)l * (l + 1) / 2 + c;
+            double acc = 0.0;
+            for (int j = 0; j < q; ++j) {
+                const double sj = calib_lane(s, j), vj = calib_lane(v, j);
+                if (in) {
+                    const size_t ah = ((size_t)j * ld + i) * tri + pk;
+                    acc += sj * d2ghat[ah] + vj * d2gvar[ah];
+                }
+            }
+            for (int j = 0; j < q; ++j) {
+                const double aj = calib_lane(alpha, j), bj = calib_lane(beta, j);
+                if (in) {
+                    const size_t aj1 = ((size_t)j * ld + i) * d + l;
+                    acc += dghat[aj1] * aj + dgvar[aj1] * bj;
+                }
+            }
+            if (in) d2ll[(size_t)i * tri + pk] = (inv_range ? inv_range[l] * irc : 1.0) * acc;
+        }
+    }
+}
+
+__global__ __launch_bounds__(64) void calib_rows_wave_kernel(int q, int d, int n0, const double* __restrict__ ghat,
+                                                              const double* __restrict__ gvar, const double* __restrict__ dghat,
+                                                              const double* __restrict__ dgvar, size_t ld,
+                                                              const double* __restrict__ M, const double* __restrict__ b, double c0,
+                                                              double lognorm, const double* __restrict__ inv_range,
+                                                              double* __restrict__ ll, double* __restrict__ dll,
+                                                              double* __restrict__ sens) {
+    calib_wave_row<false>(q, d, n0, ghat, gvar, dghat, dgvar, ld, M, b, c0, lognorm, inv_range, ll, dll, sens, nullptr, nullptr,
+                          nullptr, nullptr);
+}
+
+// lcgp_calib_hess_rows' second launch: one wavefront per row for every q in [1, 64]
+__global__ __launch_bounds__(64) void calib_hess_wave_kernel(int q, int d, int n0, const double* __restrict__ ghat,
+                                                              const double* __restrict__ gvar, const double* __restrict__ dghat,
+                                                              const double* __restrict__ dgvar, size_t ld,
+                                                              const double* __restrict__ M, const double* __restrict__ b,
+                                                              const double* __restrict__ inv_range,
+                                                              const double* __restrict__ d2ghat, const double* __restrict__ d2gvar,
+                                                              double* __restrict__ d2ll, double* __restrict__ Bout) {
+    calib_wave_row<true>(q, d, n0, ghat, gvar, dghat, dgvar, ld, M, b, 0.0, 0.0, inv_range, nullptr, nullptr, nullptr, d2ghat,
+                         d2gvar, d2ll, Bout);
 }
 
 template <int Q>
@@ -8283,6 +8393,23 @@ int lcgp_calib_rows(void* stream, int q, int d, int n0, const double* ghat, cons
     hipLaunchKernelGGL(calib_rows_wave_kernel, dim3(n0), dim3(64), 2 * (size_t)q * q * sizeof(double), st, q, d, n0, ghat, gvar,
                        dghat, dgvar, ld, M, b, c0, lognorm, inv_range, ll, dll, sens);
     CHECK_LAUNCH("calib_rows_wave");
+    return 0;
+}
+
+int lcgp_calib_hess_rows(void* stream, int q, int d, int n0, const double* ghat, const double* gvar, const double* dghat,
+                         const double* dgvar, const double* d2ghat, const double* d2gvar, int in_stride, const double* M,
+                         const double* b, double c0, double lognorm, const double* inv_range, double* ll, double* dll,
+                         double* d2ll, double* sens, double* Bout) {
+    if ((d2ghat == nullptr) != (d2gvar == nullptr)) return bad("d2ghat and d2gvar must both be given or both be NULL");
+    if (d2ll && !d2ghat) return bad("d2ll needs the Hessians d2ghat and d2gvar");
+    if (d2ll && !dghat) return bad("d2ll needs the Jacobians dghat and dgvar");
+    // (every other check is lcgp_calib_rows', made there before its launch; the second launch adds no condition of its own)
+    int rc = lcgp_calib_rows(stream, q, d, n0, ghat, gvar, dghat, dgvar, in_stride, M, b, c0, lognorm, inv_range, ll, dll, sens);
+    if (rc || (!d2ll && !Bout)) return rc;
+    const size_t ld = in_stride ? in_stride : n0;
+    hipLaunchKernelGGL(calib_hess_wave_kernel, dim3(n0), dim3(64), 2 * (size_t)q * q * sizeof(double), (hipStream_t)stream, q, d, n0,
+                       ghat, gvar, dghat, dgvar, ld, M, b, inv_range, d2ghat, d2gvar, d2ll, Bout);
+    CHECK_LAUNCH("calib_hess_wave");
     return 0;
 }
 

@@ -1295,3 +1295,34 @@ def calib_rows_device(blk, jac, M, b, c0, lognorm, inv_range=None, want_sens=Fal
                                        p(None if jac is None else jac[0]), p(None if jac is None else jac[1]), n0, p(M), p(b),
                                        float(c0), float(lognorm), p(inv_range), p(ll), p(dll), p(sens)), "lcgp_calib_rows")
     return ll, dll, sens
+
+
+def calib_hess_rows_device(blk, jac, hess, M, b, c0, lognorm, inv_range=None, want_sens=False, want_B=False):
+    """lcgp_calib_hess_rows on the device that holds `blk`: blk (2, q, n0), jac (2, q, n0, d) and hess (2, q, n0, d (d + 1) / 2)
+    = [d2ghat; d2gvar] (packed lower triangles) float64 DEVICE tensors of ALL q components (the blocks of predict_hess_block,
+    read in place), M (q, q), b (q,) and inv_range (d,) float64 tensors on the same device.  Returns device tensors (ll (n0,),
+    dll (n0, d), d2ll (n0, d (d + 1) / 2) packed, sens (2, q, n0) or None, B (n0, q, q) or None).  ll, dll and sens are bitwise
+    calib_rows_device's.  Two launches; there is no torch formulation behind it."""
+    import torch
+    _hip.require_gpu()
+    lib = _hip.load()
+    dev = blk.device
+    assert blk.dtype == torch.float64 and blk.is_contiguous() and blk.dim() == 3 and blk.shape[0] == 2
+    _, q, n0 = blk.shape
+    d = int(jac.shape[3])
+    tri = d * (d + 1) // 2
+    assert jac.dtype == torch.float64 and jac.is_contiguous() and tuple(jac.shape) == (2, q, n0, d)
+    assert hess.dtype == torch.float64 and hess.is_contiguous() and tuple(hess.shape) == (2, q, n0, tri)
+    assert M.is_contiguous() and tuple(M.shape) == (q, q) and tuple(b.shape) == (q,)
+    p = lambda t: C.c_void_p(0 if t is None else t.data_ptr())   # noqa: E731
+    with torch.cuda.device(dev):
+        ll = torch.empty(n0, dtype=torch.float64, device=dev)
+        dll = torch.empty((n0, d), dtype=torch.float64, device=dev)
+        d2ll = torch.empty((n0, tri), dtype=torch.float64, device=dev)
+        sens = torch.empty((2, q, n0), dtype=torch.float64, device=dev) if want_sens else None
+        B = torch.empty((n0, q, q), dtype=torch.float64, device=dev) if want_B else None
+        _hip.check(lib.lcgp_calib_hess_rows(C.c_void_p(torch.cuda.current_stream(dev).cuda_stream), q, d, n0, p(blk[0]), p(blk[1]),
+                                            p(jac[0]), p(jac[1]), p(hess[0]), p(hess[1]), n0, p(M), p(b), float(c0),
+                                            float(lognorm), p(inv_range), p(ll), p(dll), p(d2ll), p(sens), p(B)),
+                   "lcgp_calib_hess_rows")
+    return ll, dll, d2ll, sens, B

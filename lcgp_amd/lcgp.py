@@ -410,7 +410,8 @@ class ConditionedLCGP:
 
     def calibration(self, y_obs, obs_var, include_noise=True):
         """LCGP.calibration() of the conditioned model: a CalibrationTarget for one field observation whose loglik(theta),
-        loglik_grad(theta) and loglik_differentiable(theta) draw ghat, gvar and their Jacobians from this view.  The output
+        loglik_grad(theta), loglik_hess(theta) and loglik_differentiable(theta) draw ghat, gvar, their Jacobians and their
+        Hessians from this view.  The output
         map is the base model's, so arguments, checks, errors and the folding into M, b, c0 and lognorm are exactly
         LCGP.calibration()'s.  The target is stale when the view is."""
         self._require_current()
@@ -598,6 +599,54 @@ class _CalibFn(torch.autograd.Function):
         return gx.reshape(shape).to(device=dev, dtype=dt), None
 
 
+class _CalibFn2(torch.autograd.Function):
+    """CalibrationTarget.loglik_differentiable(order=2): _CalibFn whose backward pass is itself a differentiable function
+    (_CalibVjpFn) of theta and of the incoming gradient"""
+
+    @staticmethod
+    def forward(ctx, theta, target):
+        thc = _cpu64(theta)
+        ll, dll = target.loglik_grad(thc)
+        ctx.target, ctx.thc, ctx.dll = target, thc, dll
+        ctx.save_for_backward(theta)
+        return ll.to(theta.device)
+
+    @staticmethod
+    def backward(ctx, g):
+        (theta,) = ctx.saved_tensors
+        return _CalibVjpFn.apply(theta, g, ctx.target, ctx.thc, ctx.dll), None
+
+
+class _CalibVjpFn(torch.autograd.Function):
+    """gx[i, l] = g[i] dll[i, l] as a function of theta (through the gradient) and of the incoming gradient g.  Its backward
+    contracts the Hessian of loglik_hess(), fetched by ONE lcgp_predict_hess + lcgp_calib_hess_rows pass, and only here: a
+    first-order use of loglik_differentiable(order=2) never pays for it."""
+
+    @staticmethod
+    def forward(ctx, theta, g, target, thc, dll):
+        ctx.target, ctx.thc, ctx.dll = target, thc, dll
+        ctx.meta = (theta.dtype, theta.device, theta.shape)
+        ctx.g_meta = (g.dtype, g.device)
+        ctx.save_for_backward(g)
+        gx = _cpu64(g)[:, None] * dll
+        return gx.reshape(theta.shape).to(device=theta.device, dtype=theta.dtype)
+
+    @staticmethod
+    def backward(ctx, gg):
+        if torch.is_grad_enabled():         # a third derivative: the Hessian is a constant, not a graph
+            raise RuntimeError('CalibrationTarget.loglik_differentiable(order=2) supports first and second derivatives only: '
+                               'triple backward is not available; use loglik_hess() for the Hessian')
+        (g,) = ctx.saved_tensors
+        ggc = _cpu64(gg).reshape(ctx.dll.shape)
+        gth = None
+        if ctx.needs_input_grad[0]:
+            d2ll = ctx.target.loglik_hess(ctx.thc)[2]
+            dt, dev, shape = ctx.meta
+            gth = (_cpu64(g)[:, None] * torch.einsum('ilm,im->il', d2ll, ggc)).reshape(shape).to(device=dev, dtype=dt)
+        dt, dev = ctx.g_meta
+        return gth, torch.einsum('il,il->i', ctx.dll, ggc).to(device=dev, dtype=dt), None, None, None
+
+
 class CalibrationTarget:
     """What LCGP.calibration() returns: the log likelihood of ONE field observation y_obs of the p outputs as a function of the
     inputs theta, under the fitted emulator `model` at its current parameters,
@@ -652,12 +701,34 @@ class CalibrationTarget:
             return _t(ll), _t(dll), _t(sens[0]), _t(sens[1])
         return _t(ll), _t(dll)
 
-    def loglik_differentiable(self, theta):
+    def loglik_hess(self, theta, latent=False):
+        """(ll (n0,), dll (n0, d), d2ll (n0, d, d)), CPU float64 on the raw input scale: d2ll[i, l, m] = d^2 ll[i] / d theta[i, l]
+        d theta[i, m], exact and EXACTLY symmetric (the packed triangle of lcgp_calib_hess_rows, mirrored
+        here); ll and dll are bitwise loglik_grad(theta)'s.  One lcgp_predict_hess pass (of the view for a view's target) and
+        the row kernels.  latent=True: additionally s, v (q, n0) and B (n0, q, q) = Phi_s^T Sigma_i^-1 Phi_s, minus the Hessian
+        of ll in ghat.  Nugget convention of predict_hess(): the continuous surface, also at training inputs and at a view's
+        own inputs; the Matern-3/2 kernel has its kinks there."""
+        m = self.model
+        x0s = m._x0_2d(theta, 'theta')
+        self._require_current()
+        blk, jac, hess = m._calib_latent(x0s, 2, view=self._view)
+        ll, dll, packed, sens, B = m._calib_hess_rows_device(blk, jac, hess, *self._device_consts(blk.device), self.c0,
+                                                             self.lognorm, latent, latent)
+        d2ll = m._unpack_lower(packed, x0s.shape[1])
+        if latent:
+            return _t(ll), _t(dll), _t(d2ll), _t(sens[0]), _t(sens[1]), _t(B)
+        return _t(ll), _t(dll), _t(d2ll)
+
+    def loglik_differentiable(self, theta, order=1):
         """(n0,) float64 on theta's device, differentiable with respect to a requires_grad theta (any device) through
-        torch.autograd to first order: the backward pass multiplies with the gradient of loglik_grad() saved by the forward pass.
-        A double backward (create_graph=True) raises."""
+        torch.autograd: the backward pass multiplies with the gradient of loglik_grad() saved by the forward pass.
+        order=1: first derivatives only; a double backward (create_graph=True) raises.  order=2: the backward pass is itself
+        differentiable (torch.autograd.functional.hessian, gradgradcheck); the Hessian comes from one loglik_hess() pass, made
+        only when a double backward actually runs.  A third derivative raises."""
+        if order not in (1, 2):
+            raise ValueError('loglik_differentiable: order must be 1 or 2, got %r' % (order,))
         theta = theta if isinstance(theta, torch.Tensor) else torch.as_tensor(np.asarray(theta, F64))
-        return _CalibFn.apply(theta, self)
+        return (_CalibFn if order == 1 else _CalibFn2).apply(theta, self)
 
 
 class LCGP:
@@ -2205,7 +2276,7 @@ class LCGP:
         are ignored.  include_noise=True adds the fitted noise variance, as ypredvar does.  The target's loglik(theta) is
             log N(y_obs; ypred(theta), Phi_s diag(gvar(theta)) Phi_s^T + noise + Sigma_obs)
         restricted to the observed outputs, exactly (no diagonal approximation of the emulator's covariance), on the full and
-        rep paths; loglik_grad(theta) adds its gradient in theta.  Everything p-sized is folded here, once, into a q x q
+        rep paths; loglik_grad(theta) adds its gradient in theta, loglik_hess(theta) its Hessian.  Everything p-sized is folded here, once, into a q x q
         matrix and a q-vector (host float64; a diagonal obs_var never forms a p x p matrix); per row of theta the GPU then
         factorises a q x q matrix on top of lcgp_predict_grad's outputs (lcgp_calib_rows).
         Raises ValueError for wrong shapes, non-finite observed values, negative variances and an asymmetric (p, p) obs_var,
@@ -2258,35 +2329,44 @@ class LCGP:
     def _calib_latent(self, x0s, grad, view=None):
         """(blk (2, q, n0), jac (2, q, n0, d) or None): [ghat; gvar] and [dghat; dgvar] of ALL q components at the standardised
         inputs x0s, float64 tensors where the row kernel runs; view: a ConditionedLCGP of this model whose latents are taken
-        instead of the fitted model's.  One rank: the engine's blocks, read in place.  Several ranks: the zero-padded blocks
+        instead of the fitted model's.  grad=2 (second order): (blk, jac, hess), hess (2, q, n0, d (d + 1) / 2) = [d2ghat;
+        d2gvar] as packed lower triangles, from predict_hess_block / condition_predict_hess_block, whose blk and jac are
+        bitwise the first-order ones.  One rank: the engine's blocks, read in place.  Several ranks: the zero-padded blocks
         are summed over the ranks (disjoint components: exact) and copied back to every rank's device."""
         if view is None:
             eng = self._ensure_aux()
+            hess_block = lambda x: eng.predict_hess_block(x)
             grad_block = lambda x: eng.predict_grad_block(x)
             block = lambda x: eng.predict_block(x, False)
         else:
             eng, st = view._engine, view._state
+            hess_block = lambda x: eng.condition_predict_hess_block(st, x)
             grad_block = lambda x: eng.condition_predict_grad_block(st, x)
             block = lambda x: eng.condition_predict_block(st, x)
         if not _dist.use_collectives(self._group):
+            if grad == 2:
+                return hess_block(x0s)
             return grad_block(x0s) if grad else (block(x0s), None)
         n0, d = x0s.shape
         q = int(self.q)
+        tri = d * (d + 1) // 2
+        widths = [2 * n0] + ([2 * n0 * d] if grad else []) + ([2 * n0 * tri] if grad == 2 else [])
         loc = None
         if eng is not None and grad:
-            blk, jac = grad_block(x0s)
-            loc = torch.cat([blk.permute(1, 0, 2).reshape(blk.shape[1], -1),
-                             jac.permute(1, 0, 2, 3).reshape(jac.shape[1], -1)], dim=1)
+            parts = hess_block(x0s) if grad == 2 else grad_block(x0s)
+            loc = torch.cat([t.movedim(1, 0).reshape(t.shape[1], -1) for t in parts], dim=1)
         elif eng is not None:
             loc = block(x0s).permute(1, 0, 2).reshape(-1, 2 * n0)
-        both = self._gather_components(loc, (2 * n0 + (2 * n0 * d if grad else 0),))
+        both = self._gather_components(loc, (sum(widths),))
         if eng is not None:
             dev = eng.device
         else:
             dev = torch.device(self._device) if self._device is not None else torch.device('cuda', torch.cuda.current_device())
         both = torch.as_tensor(np.ascontiguousarray(both, F64)).to(dev)
         blk = both[:, :2 * n0].reshape(q, 2, n0).permute(1, 0, 2).contiguous()
-        jac = both[:, 2 * n0:].reshape(q, 2, n0, d).permute(1, 0, 2, 3).contiguous() if grad else None
+        jac = both[:, 2 * n0:2 * n0 * (1 + d)].reshape(q, 2, n0, d).permute(1, 0, 2, 3).contiguous() if grad else None
+        if grad == 2:
+            return blk, jac, both[:, 2 * n0 * (1 + d):].reshape(q, 2, n0, tri).permute(1, 0, 2, 3).contiguous()
         return blk, jac
 
     def _calib_rows_device(self, blk, jac, M, b, inv_range, c0, lognorm, want_sens):
@@ -2294,6 +2374,14 @@ class LCGP:
         tensors in, numpy (ll (n0,), dll (n0, d) or None, sens (2, q, n0) or None) out"""
         from .engine import calib_rows_device
         out = calib_rows_device(blk, jac, M, b, c0, lognorm, inv_range, want_sens)
+        return tuple(None if t is None else t.cpu().numpy() for t in out)
+
+    def _calib_hess_rows_device(self, blk, jac, hess, M, b, inv_range, c0, lognorm, want_sens, want_B):
+        """the one call into the second-order row entry (lcgp_calib_hess_rows; there is no other implementation in the
+        package): device tensors in, numpy (ll (n0,), dll (n0, d), d2ll (n0, d (d + 1) / 2) packed, sens (2, q, n0) or None,
+        B (n0, q, q) or None) out"""
+        from .engine import calib_hess_rows_device
+        out = calib_hess_rows_device(blk, jac, hess, M, b, c0, lognorm, inv_range, want_sens, want_B)
         return tuple(None if t is None else t.cpu().numpy() for t in out)
 
     # =============================================================================================

@@ -20,6 +20,39 @@ PREDICT_CHUNK = 2048
 SAMPLE_CHUNK = 4096
 
 
+def point_passes(n0, chunk, keep_tiles):
+    """The passes of a chunked per-point query over n0 rows, chunk rows at a time, as a list of (lo, rows, fresh): the pass
+    hands rows lo .. lo + rows to the library, and fresh is the first of them that no earlier pass produced.  keep_tiles: a
+    pass never runs below 128 rows while n0 has them -- the library forms its rows on 128-row tiles from 128 rows on and on
+    64-row tiles below, in different summation orders -- so a short last pass is moved back over its predecessor (the same
+    values again; fresh > lo then, else fresh == lo).  That makes results bitwise independent of the chunk."""
+    passes = []
+    for fresh in range(0, n0, chunk):
+        lo, rows = fresh, min(chunk, n0 - fresh)
+        if keep_tiles and rows < 128 <= n0:
+            lo, rows = n0 - 128, 128
+        passes.append((lo, rows, fresh))
+    return passes
+
+
+# the chunked per-point queries: the public name in the error text, (entry, scratch query) of the fitted model and of a
+# conditioned view, whether a pass keeps 128-row tiles (point_passes; these also pass d to the scratch query and check the
+# fitted model's scratch against the free memory), and for the memory refusal what a pass forms and its rows of width n per
+# new input
+_POINT_QUERIES = {
+    'predict': ("predict", ("lcgp_predict", "lcgp_predict_scratch_bytes"),
+                ("lcgp_condition_predict", "lcgp_condition_scratch_bytes"), False, "prediction", lambda d: 1),
+    # (lcgp_predict_grad_scratch_bytes is lcgp_predict_scratch_bytes)
+    'grad': ("predict_grad", ("lcgp_predict_grad", "lcgp_predict_scratch_bytes"),
+             ("lcgp_condition_predict_grad", "lcgp_condition_predict_grad_scratch_bytes"), False, "gradient", lambda d: 1),
+    'hess': ("predict_hess", ("lcgp_predict_hess", "lcgp_predict_hess_scratch_bytes"),
+             ("lcgp_condition_predict_hess", "lcgp_condition_predict_hess_scratch_bytes"), True, "Hessians", lambda d: d + 1),
+    'gradcov': ("predict_grad_cov", ("lcgp_predict_gradcov", "lcgp_predict_gradcov_scratch_bytes"),
+                ("lcgp_condition_predict_gradcov", "lcgp_condition_predict_gradcov_scratch_bytes"), True,
+                "gradient covariances", lambda d: d),
+}
+
+
 class HotPathEngine:
     """Holds x (n,d), Y (p,n), optional sr (n) and the workspace for the local components on one GPU.
 
@@ -92,6 +125,18 @@ class HotPathEngine:
 
     def _p(self, t):
         return C.c_void_p(0 if t is None else t.data_ptr())
+
+    def _head(self, Y=False):
+        """what the entries that read the fitted model begin with: (stream, dtype, kernel_id, n, d, p, q_local, x, sr, theta,
+        workspace); Y: with Y behind x (the entries that differentiate in the parameters)"""
+        held = (self.x, self.Y, self.sr, self.theta_dev, self.workspace) if Y else (self.x, self.sr, self.theta_dev, self.workspace)
+        return (self._stream(), self.dtype, self.kernel_id, self.n, self.d, self.p, self.q_local) + tuple(self._p(t) for t in held)
+
+    def _upload_x0(self, x0s):
+        """(n0, x0s on the device in the engine's dtype) for n0 >= 1 standardised new inputs x0s (n0, d)"""
+        x0s = np.ascontiguousarray(x0s, np.float64)
+        assert x0s.ndim == 2 and x0s.shape[1] == self.d and x0s.shape[0] >= 1
+        return x0s.shape[0], self.torch.as_tensor(x0s).to(self.device, self.tdtype).contiguous()
 
     @property
     def sched(self):
@@ -212,51 +257,77 @@ class HotPathEngine:
             self._theta_last, np.asarray(theta_rows, np.float64).reshape(self.q_local, self.tw))
 
     # ------------------------------------------------------------------------------------------------
-    def _predict_chunks(self, x0s, same, grad):
-        """lcgp_predict (grad = False) or lcgp_predict_grad over x0s in chunks of PREDICT_CHUNK rows with the engine's scratch:
-        returns the (2, q_local, n0) block [ghat; gvar] and, with grad, the (2, q_local, n0, d) block [dghat; dgvar].  Every
-        chunk writes its columns of the one result block in place (row stride = n0): no per-chunk temporaries, no
-        device-to-device copies"""
-        torch = self.torch
-        if self._theta_last is None:
-            raise RuntimeError("%s() needs a preceding evaluate() at the current parameters" % ("predict_grad" if grad else "predict"))
-        x0s = np.ascontiguousarray(x0s, np.float64)
-        n0, d = x0s.shape[0], self.d
-        assert x0s.ndim == 2 and x0s.shape[1] == d and n0 >= 1
-        chunk = min(n0, PREDICT_CHUNK)
+    def _point_check(self, query, state):
+        """_view_args(state) after the check that an evaluation stands behind the query (a view: that it is still the view's)"""
+        if state is None and self._theta_last is None:
+            raise RuntimeError("%s() needs a preceding evaluate() at the current parameters" % _POINT_QUERIES[query][0])
+        return self._view_args(state)
+
+    def _point_query(self, query, x0s, state, same=False):
+        """What the chunked per-point queries (_POINT_QUERIES) share, for the fitted model (state = None) or the view `state`
+        (condition_begin), inside the device context: the checks, the view's grad state where the entry takes one, x0s on the
+        device and the engine's scratch grown for one pass.  Returns (n0, passes, run): passes = point_passes(...), and
+        run(lo, rows, *outs) calls the entry on rows lo .. lo + rows of x0s with the output pointers outs.  The entries on a
+        view take the view behind the workspace and the scratch size behind the scratch; same goes to lcgp_predict only."""
+        _, base, on_view, keep_tiles, what, per_input = _POINT_QUERIES[query]
+        m, view, _ = self._point_check(query, state)
+        assert state is None or not same
+        entry, sizer = base if state is None else on_view
+        d, q = self.d, self.q_local
+        if state is not None and query != 'predict':
+            view += (self._p(self._condition_grad_state(state)),)
+        n0, x0d = self._upload_x0(x0s)
+        chunk = min(n0, max(128, PREDICT_CHUNK // d) if keep_tiles else PREDICT_CHUNK)
+        dims = (self.dtype, self.n) + ((d,) if keep_tiles else ()) + (q,) + (() if state is None else (m,)) + (chunk,)
+        refusal = None                                  # (the fitted model's predict and predict_grad: PREDICT_CHUNK bounds it)
+        if keep_tiles or state is not None:
+            refusal = ("the %s%s of %d new inputs per pass" % ("" if state is None else "conditioned ", what, chunk),
+                       "%d components of %d x %s, twice" % (q, chunk * per_input(d), "n" if state is None else "(n + m)"),
+                       "lower lcgp_amd.engine.PREDICT_CHUNK")
+        scratch = self._grow_scratch(self._nbytes(sizer, *dims), refusal)
+        scs = (self._p(scratch),) if state is None else (self._p(scratch), scratch.numel())
+        head, fn = self._head() + view, getattr(self.lib, entry)
+
+        def run(lo, rows, *outs):
+            x0p = C.c_void_p(x0d.data_ptr() + lo * d * x0d.element_size())
+            # the nugget term only exists when x0 IS the training set (covmat.py:46-51): then n0 == n and the diagonal of
+            # the full cross matrix falls on rows lo .. lo + rows of this pass
+            sm = ((1 + lo) if same else 0,) if entry == "lcgp_predict" else ()
+            _hip.check(fn(*head, rows, x0p, *sm, *scs, *outs, n0), entry)
+        return n0, point_passes(n0, chunk, keep_tiles), run
+
+    def _predict_chunks(self, query, x0s, state, same=False):
+        """predict_block, predict_grad_block or predict_hess_block (query = 'predict', 'grad', 'hess'): the list of the (2,
+        q_local, n0[, width]) result blocks: the values, the Jacobians of width d, the Hessians of width d (d + 1) / 2.  Every
+        pass writes its rows of the result blocks in place (row stride = n0): no per-pass temporaries, no device-to-device
+        copies"""
+        torch, d = self.torch, self.d
+        tails = {'predict': [()], 'grad': [(), (d,)], 'hess': [(), (d,), (d * (d + 1) // 2,)]}[query]
         with torch.cuda.device(self.device):
-            x0d = torch.as_tensor(x0s).to(self.device, self.tdtype).contiguous()
-            # (lcgp_predict_grad_scratch_bytes is lcgp_predict_scratch_bytes; unchecked: PREDICT_CHUNK bounds it)
-            scp = self._p(self._grow_scratch(self._nbytes("lcgp_predict_scratch_bytes", self.dtype, self.n, self.q_local, chunk)))
-            out = torch.empty((2, self.q_local, n0), dtype=torch.float64, device=self.device)
-            jac = torch.empty((2, self.q_local, n0, d), dtype=torch.float64, device=self.device) if grad else None
-            st, xp, srp, thp, wsp = self._stream(), self._p(self.x), self._p(self.sr), self._p(self.theta_dev), self._p(self.workspace)
-            for lo in range(0, n0, chunk):
-                m = min(chunk, n0 - lo)
-                x0p = C.c_void_p(x0d.data_ptr() + lo * d * x0d.element_size())
-                gh, gv = C.c_void_p(out[0].data_ptr() + 8 * lo), C.c_void_p(out[1].data_ptr() + 8 * lo)
-                if grad:
-                    _hip.check(self.lib.lcgp_predict_grad(st, self.dtype, self.kernel_id, self.n, d, self.p, self.q_local, xp, srp,
-                                                          thp, wsp, m, x0p, scp, gh, gv, C.c_void_p(jac[0].data_ptr() + 8 * lo * d),
-                                                          C.c_void_p(jac[1].data_ptr() + 8 * lo * d), n0), "lcgp_predict_grad")
-                else:
-                    # the nugget term only exists when x0 IS the training set (covmat.py:46-51): then n0 == n and the
-                    # diagonal of the full cross matrix falls on rows lo .. lo+m of this chunk
-                    _hip.check(self.lib.lcgp_predict(st, self.dtype, self.kernel_id, self.n, d, self.p, self.q_local, xp, srp, thp,
-                                                     wsp, m, x0p, (1 + lo) if same else 0, scp, gh, gv, n0), "lcgp_predict")
-            return (out, jac) if grad else out
+            n0, passes, run = self._point_query(query, x0s, state, same)
+            blocks = [torch.empty((2, self.q_local, n0) + tail, dtype=torch.float64, device=self.device) for tail in tails]
+            for lo, rows, _ in passes:
+                run(lo, rows, *[C.c_void_p(t[h].data_ptr() + 8 * lo * t.stride(2)) for t in blocks for h in (0, 1)])
+            return blocks
 
-    def predict_block(self, x0s, same=False):
+    def predict_block(self, x0s, same=False, state=None):
         """(2, q_local, n0) float64 DEVICE tensor [ghat; gvar] for standardised x0s, from the factorisation of the last
-        evaluate().  x0 is processed in chunks of PREDICT_CHUNK rows with one engine-owned scratch buffer."""
-        return self._predict_chunks(x0s, same, False)
+        evaluate() (lcgp_predict).  x0 is processed in chunks of PREDICT_CHUNK rows with one engine-owned scratch buffer:
+        passes that write their columns of the one result block in place.
+          state: a view's state (condition_begin): the prediction of the conditioned model (lcgp_condition_predict:
+                 lcgp_predict's launches with same = 0, then the rank-m correction; same must be False).  The base
+                 factorisation must still be the one the state was built from."""
+        return self._predict_chunks('predict', x0s, state, same)[0]
 
-    def predict_grad_block(self, x0s):
+    def predict_grad_block(self, x0s, state=None):
         """(block, jac) float64 DEVICE tensors for standardised x0s, from the factorisation of the last evaluate():
         block (2, q_local, n0) = [ghat; gvar], bitwise predict_block(x0s, same=False); jac (2, q_local, n0, d) = [dghat; dgvar],
         the derivatives with respect to x0s (lcgp_predict_grad: no nugget term, the gradient of the continuous surface).
-        Chunked like predict_block (PREDICT_CHUNK rows per call) and sharing its scratch."""
-        return self._predict_chunks(x0s, False, True)
+        Chunked like predict_block (PREDICT_CHUNK rows per call) and sharing its scratch.
+          state: a view's state (condition_begin): block bitwise predict_block(x0s, state=state) and its derivatives
+                 (lcgp_condition_predict_grad: the continuous surface also at the view's own new inputs); the scratch is that
+                 of predict_block on the view.  The base factorisation must still be the one the state was built from."""
+        return tuple(self._predict_chunks('grad', x0s, state))
 
     def predict_paramgrad_block(self, x0s, same=False, q_group=None):
         """(block, dk, dn) float64 DEVICE tensors for standardised x0s, from the factorisation of the last evaluate() -- which
@@ -293,58 +364,34 @@ class HotPathEngine:
             out = torch.empty((2, self.q_local, n0), dtype=torch.float64, device=self.device)
             dk = torch.empty((2, self.q_local, n0, m), dtype=torch.float64, device=self.device)
             dn = torch.empty((self.q_local, n0, self.p), dtype=torch.float64, device=self.device)
-            st = self._stream()
-            for lo in range(0, n0, chunk):
-                rows = min(chunk, n0 - lo)
+            head = self._head(Y=True)
+            for lo, rows, _ in point_passes(n0, chunk, False):
                 for k0 in range(0, self.q_local, group):
                     _hip.check(self.lib.lcgp_predict_paramgrad(
-                        st, self.dtype, self.kernel_id, self.n, d, self.p, self.q_local, self._p(self.x), self._p(self.Y),
-                        self._p(self.sr), self._p(self.theta_dev), self._p(self.workspace), k0, min(group, self.q_local - k0), rows,
+                        *head, k0, min(group, self.q_local - k0), rows,
                         C.c_void_p(x0d.data_ptr() + 8 * lo * d), (1 + lo) if same else 0, scp,
                         C.c_void_p(out[0].data_ptr() + 8 * lo), C.c_void_p(out[1].data_ptr() + 8 * lo),
                         C.c_void_p(dk[0].data_ptr() + 8 * lo * m), C.c_void_p(dk[1].data_ptr() + 8 * lo * m),
                         C.c_void_p(dn.data_ptr() + 8 * lo * self.p), n0), "lcgp_predict_paramgrad")
             return out, dk, dn
 
-    def predict_hess_block(self, x0s):
+    def predict_hess_block(self, x0s, state=None):
         """(block, jac, hess) float64 DEVICE tensors for standardised x0s, from the factorisation of the last evaluate():
         block (2, q_local, n0) and jac (2, q_local, n0, d) bitwise those of predict_grad_block(x0s); hess (2, q_local, n0,
         d (d + 1) / 2) = [d2ghat; d2gvar], the packed lower triangles (entry (l, m <= l) at l (l + 1) / 2 + m) of the Hessians
         with respect to x0s (lcgp_predict_hess).  Chunked so that one call forms at most PREDICT_CHUNK rows of P (chunk * d <=
         PREDICT_CHUNK) but never fewer than 128 new inputs while n0 has them: the library forms V on 128-row tiles from 128 new
         inputs on and on 64-row tiles below, in different summation orders, so a last pass of fewer than 128 inputs is moved
-        back to overlap its predecessor (the same values again).  All results are therefore bitwise independent of
-        PREDICT_CHUNK.  The scratch holds 2 q_local (chunk_pad + (chunk d)_pad) npad elements, chunk = max(128, PREDICT_CHUNK //
-        d); raises ValueError when it does not fit in the free device memory."""
-        torch = self.torch
-        if self._theta_last is None:
-            raise RuntimeError("predict_hess() needs a preceding evaluate() at the current parameters")
-        x0s = np.ascontiguousarray(x0s, np.float64)
-        n0, d = x0s.shape[0], self.d
-        assert x0s.ndim == 2 and x0s.shape[1] == d and n0 >= 1
-        tri = d * (d + 1) // 2
-        chunk = min(n0, max(128, PREDICT_CHUNK // d))
-        with torch.cuda.device(self.device):
-            x0d = torch.as_tensor(x0s).to(self.device, self.tdtype).contiguous()
-            nbytes = self._nbytes("lcgp_predict_hess_scratch_bytes", self.dtype, self.n, d, self.q_local, chunk)
-            scp = self._p(self._grow_scratch(nbytes, ("the Hessians of %d new inputs per pass" % chunk,
-                                                      "%d components of %d x n, twice" % (self.q_local, chunk * (d + 1)),
-                                                      "lower lcgp_amd.engine.PREDICT_CHUNK")))
-            out = torch.empty((2, self.q_local, n0), dtype=torch.float64, device=self.device)
-            jac = torch.empty((2, self.q_local, n0, d), dtype=torch.float64, device=self.device)
-            hess = torch.empty((2, self.q_local, n0, tri), dtype=torch.float64, device=self.device)
-            st, xp, srp, thp, wsp = self._stream(), self._p(self.x), self._p(self.sr), self._p(self.theta_dev), self._p(self.workspace)
-            for lo in range(0, n0, chunk):
-                m = min(chunk, n0 - lo)
-                if m < 128 <= n0:
-                    lo, m = n0 - 128, 128
-                x0p = C.c_void_p(x0d.data_ptr() + lo * d * x0d.element_size())
-                ptrs = [C.c_void_p(t[h].data_ptr() + 8 * lo * w) for t, w in ((out, 1), (jac, d), (hess, tri)) for h in (0, 1)]
-                _hip.check(self.lib.lcgp_predict_hess(st, self.dtype, self.kernel_id, self.n, d, self.p, self.q_local, xp, srp, thp,
-                                                      wsp, m, x0p, scp, *ptrs, n0), "lcgp_predict_hess")
-            return out, jac, hess
+        back to overlap its predecessor (the same values again; point_passes).  All results are therefore bitwise independent
+        of PREDICT_CHUNK.  The scratch holds 2 q_local (chunk_pad + (chunk d)_pad) npad elements, chunk = max(128,
+        PREDICT_CHUNK // d); raises ValueError when it does not fit in the free device memory.
+          state: a view's state (condition_begin): block and jac bitwise those of predict_grad_block(x0s, state=state), hess
+                 [d2ghat'; d2gvar'] of the conditioned model (lcgp_condition_predict_hess), chunked the same way.  The scratch
+                 holds that of predict_grad_block on the view and q_local (chunk d)_pad (2 npad + 3 mpad) elements.  The base
+                 factorisation must still be the one the state was built from."""
+        return tuple(self._predict_chunks('hess', x0s, state))
 
-    def grad_cov_block(self, x0s, w=None, per_point=True):
+    def grad_cov_block(self, x0s, w=None, per_point=True, state=None):
         """(dghat, gamma, M) float64 DEVICE tensors for standardised x0s, from the factorisation of the last evaluate()
         (lcgp_predict_gradcov): dghat (q_local, n0, d) bitwise that of predict_grad_block(x0s); gamma (q_local, n0, d (d + 1)
         / 2), the packed lower triangles (entry (l, m <= l) at l (l + 1) / 2 + m) of the posterior covariance of the latent
@@ -354,23 +401,18 @@ class HotPathEngine:
         new inputs while n0 has them, a short last pass moved back so that P is formed on 128-row tiles in every pass of a
         call with several): dghat and gamma are bitwise independent of PREDICT_CHUNK.  The rows a moved-back pass repeats
         weigh zero in it.  The scratch holds 2 q_local (chunk d)_pad npad elements; raises ValueError when it does not fit in
-        the free device memory."""
-        torch = self.torch
-        if self._theta_last is None:
-            raise RuntimeError("predict_grad_cov() needs a preceding evaluate() at the current parameters")
-        x0s = np.ascontiguousarray(x0s, np.float64)
-        n0, d = x0s.shape[0], self.d
-        assert x0s.ndim == 2 and x0s.shape[1] == d and n0 >= 1
+        the free device memory.
+          state: a view's state (condition_begin): dghat bitwise that of predict_grad_block(x0s, state=state), gamma the
+                 covariance of the latent gradient given the view's runs too (lcgp_condition_predict_gradcov), chunked and
+                 weighted the same way.  The scratch holds q_local (chunk d)_pad (2 npad + 3 mpad) elements.  The base
+                 factorisation must still be the one the state was built from."""
+        torch, d = self.torch, self.d
         if w is None and not per_point:
-            raise ValueError("grad_cov_block: per_point=False needs weights")
+            self._point_check('gradcov', state)         # (an engine never evaluated or a stale view is reported first)
+            raise ValueError("%sgrad_cov_block: per_point=False needs weights" % ("" if state is None else "condition_"))
         tri = d * (d + 1) // 2
-        chunk = min(n0, max(128, PREDICT_CHUNK // d))
         with torch.cuda.device(self.device):
-            x0d = torch.as_tensor(x0s).to(self.device, self.tdtype).contiguous()
-            nbytes = self._nbytes("lcgp_predict_gradcov_scratch_bytes", self.dtype, self.n, d, self.q_local, chunk)
-            scp = self._p(self._grow_scratch(nbytes, ("the gradient covariances of %d new inputs per pass" % chunk,
-                                                      "%d components of %d x n, twice" % (self.q_local, chunk * d),
-                                                      "lower lcgp_amd.engine.PREDICT_CHUNK")))
+            n0, passes, run = self._point_query('gradcov', x0s, state)
             dghat = torch.empty((self.q_local, n0, d), dtype=torch.float64, device=self.device)
             gamma = torch.empty((self.q_local, n0, tri), dtype=torch.float64, device=self.device) if per_point else None
             M = wd = None
@@ -379,21 +421,14 @@ class HotPathEngine:
                 assert w.shape == (n0,)
                 wd = torch.as_tensor(w).to(self.device)
                 M = torch.zeros((self.q_local, tri), dtype=torch.float64, device=self.device)
-            st, xp, srp, thp, wsp = self._stream(), self._p(self.x), self._p(self.sr), self._p(self.theta_dev), self._p(self.workspace)
-            for lo in range(0, n0, chunk):
-                m = min(chunk, n0 - lo)
-                wp = None if wd is None else C.c_void_p(wd.data_ptr() + 8 * lo)
-                if m < 128 <= n0:
-                    if wd is not None:                  # the rows n0 - 128 .. lo were summed by the pass before
-                        wl = wd[n0 - 128:].clone()
-                        wl[:lo - (n0 - 128)] = 0.0
-                        wp = self._p(wl)
-                    lo, m = n0 - 128, 128
-                x0p = C.c_void_p(x0d.data_ptr() + lo * d * x0d.element_size())
-                _hip.check(self.lib.lcgp_predict_gradcov(
-                    st, self.dtype, self.kernel_id, self.n, d, self.p, self.q_local, xp, srp, thp, wsp, m, x0p, scp,
-                    C.c_void_p(dghat.data_ptr() + 8 * lo * d), None if gamma is None else C.c_void_p(gamma.data_ptr() + 8 * lo * tri),
-                    wp, None if M is None else self._p(M), n0), "lcgp_predict_gradcov")
+            for lo, rows, fresh in passes:
+                wl = None if wd is None else wd[lo:lo + rows]
+                if wd is not None and fresh > lo:       # the rows lo .. fresh were summed by the pass before
+                    wl = wl.clone()
+                    wl[:fresh - lo] = 0.0
+                run(lo, rows, C.c_void_p(dghat.data_ptr() + 8 * lo * d),
+                    None if gamma is None else C.c_void_p(gamma.data_ptr() + 8 * lo * tri), self._p(wl),
+                    None if M is None else self._p(M))
             return dghat, gamma, M
 
     def predict_marginal_block(self, x0s, mask, box, state=None, ref=None):
@@ -420,15 +455,14 @@ class HotPathEngine:
         assert np.shape(x0s) == (n0, d) and mask.shape == (n0, d) and box.shape == (2, d) and n0 >= 1
         if not np.all(box[1] > box[0]):
             raise ValueError("predict_marginal_block: the box needs hi > lo in every dimension")
-        x0s = np.ascontiguousarray(np.where(mask != 0, 0.0, np.asarray(x0s, np.float64)))
         chunk = min(n0, max(128, PREDICT_CHUNK))
         m, view, kp = self._view_args(state)
         with torch.cuda.device(self.device):
-            x0d = torch.as_tensor(x0s).to(self.device, self.tdtype).contiguous()
+            _, x0d = self._upload_x0(np.where(mask != 0, 0.0, np.asarray(x0s, np.float64)))
             md = torch.as_tensor(mask).to(self.device)
             bd = torch.as_tensor(box).to(self.device)
             out = torch.empty((2 if ref is None else 3, self.q_local, n0), dtype=torch.float64, device=self.device)
-            st, xp, srp, thp, wsp = self._stream(), self._p(self.x), self._p(self.sr), self._p(self.theta_dev), self._p(self.workspace)
+            base = self._head()
             plain = state is None and ref is None
             if plain:
                 scratch = self._grow_scratch(self._nbytes("lcgp_predict_marginal_scratch_bytes", self.dtype, self.n, d,
@@ -440,8 +474,7 @@ class HotPathEngine:
                      "%d components of %d x K', K' = npad + mpad = %d, twice" % (self.q_local, chunk, kp),
                      "lower lcgp_amd.engine.PREDICT_CHUNK"))
             scp = self._p(scratch)
-            head = (st, self.dtype, self.kernel_id, self.n, d, self.p, self.q_local, xp, srp, thp, wsp) + \
-                (view if view else (None, 0, None))
+            head = base + (view if view else (None, 0, None))
             refs = (0, None, None, None, None)          # ref_row, ref_out, ref_in, ref_x, ref_mask
             if ref is not None:
                 mr = np.ascontiguousarray(np.asarray(ref[1]) != 0, np.uint8).reshape(1, d)
@@ -454,16 +487,12 @@ class HotPathEngine:
                     *head, 1, self._p(xrd), self._p(mrd), self._p(bd), scp, scratch.numel(), self._p(one[0]), self._p(one[1]), 1,
                     0, self._p(row), None, None, None, None), "lcgp_condition_predict_marginal")
                 refs = (0, None, self._p(row), self._p(xrd), self._p(mrd))
-            for lo in range(0, n0, chunk):
-                rows = min(chunk, n0 - lo)
-                if rows < 128 <= n0:
-                    lo, rows = n0 - 128, 128
+            for lo, rows, _ in point_passes(n0, chunk, True):
                 x0p, mp = C.c_void_p(x0d.data_ptr() + lo * d * x0d.element_size()), C.c_void_p(md.data_ptr() + lo * d)
                 ghp, gvp = C.c_void_p(out[0].data_ptr() + 8 * lo), C.c_void_p(out[1].data_ptr() + 8 * lo)
                 if plain:
-                    _hip.check(self.lib.lcgp_predict_marginal(
-                        st, self.dtype, self.kernel_id, self.n, d, self.p, self.q_local, xp, srp, thp, wsp, rows, x0p, mp,
-                        self._p(bd), scp, ghp, gvp, n0), "lcgp_predict_marginal")
+                    _hip.check(self.lib.lcgp_predict_marginal(*base, rows, x0p, mp, self._p(bd), scp, ghp, gvp, n0),
+                               "lcgp_predict_marginal")
                 else:
                     gcp = None if ref is None else C.c_void_p(out[2].data_ptr() + 8 * lo)
                     _hip.check(self.lib.lcgp_condition_predict_marginal(
@@ -551,8 +580,7 @@ class HotPathEngine:
                 nbytes = self._nbytes("lcgp_condition_predict_cov_scratch_bytes", self.dtype, self.n, self.q_local, m, n0)
             scratch = self._grow_scratch(nbytes, refusal("the scratch of the joint covariance"))
             x0d = torch.as_tensor(x0s).to(self.device, self.tdtype).contiguous()
-            head = (self._stream(), self.dtype, self.kernel_id, self.n, self.d, self.p, self.q_local, self._p(self.x),
-                    self._p(self.sr), self._p(self.theta_dev), self._p(self.workspace))
+            head = self._head()
             if state is None:
                 _hip.check(self.lib.lcgp_predict_cov(*head, n0, self._p(x0d), 1 if same else 0, self._p(scratch), self._p(cws),
                                                      float(jitter)), "lcgp_predict_cov")
@@ -675,9 +703,8 @@ class HotPathEngine:
             rd = None if r is None else torch.as_tensor(np.ascontiguousarray(r, np.float64)).to(self.device)
             info = torch.zeros(self.q_local, dtype=torch.int32, device=self.device)
             _hip.check(self.lib.lcgp_condition_prepare(
-                self._stream(), self.dtype, self.kernel_id, self.n, d, self.p, self.q_local, self._p(self.x), self._p(self.sr),
-                self._p(self.theta_dev), self._p(self.workspace), m, self._p(xnd), self._p(td), self._p(rd), self._p(scratch),
-                scratch.numel(), self._p(cws), self._p(state), self._p(info)), "lcgp_condition_prepare")
+                *self._head(), m, self._p(xnd), self._p(td), self._p(rd), self._p(scratch), scratch.numel(), self._p(cws),
+                self._p(state), self._p(info)), "lcgp_condition_prepare")
             info = info.cpu().numpy()
         if np.any(info != 0):
             err = np.linalg.LinAlgError("condition(): S_k is not numerically positive definite for local components (index, info) %s"
@@ -685,35 +712,6 @@ class HotPathEngine:
             err.info = info
             raise err
         return {'m': m, 'xn': xnd, 'state': state, 'theta': self._theta_last.copy()}
-
-    def condition_predict_block(self, state, x0s):
-        """(2, q_local, n0) float64 DEVICE tensor [ghat; gvar] of the view `state` (condition_begin) at standardised x0s
-        (lcgp_condition_predict: lcgp_predict's launches with same = 0, then the rank-m correction).  Chunked as predict_block
-        is: passes of at most PREDICT_CHUNK rows that write their columns of the one result block in place.  The base
-        factorisation must still be the one the state was built from."""
-        torch = self.torch
-        if not self.is_current(state['theta']):
-            raise RuntimeError("the conditioned view does not belong to the factorisation in the workspace")
-        x0s = np.ascontiguousarray(x0s, np.float64)
-        n0, d, m = x0s.shape[0], self.d, state['m']
-        assert x0s.ndim == 2 and x0s.shape[1] == d and n0 >= 1
-        chunk = min(n0, PREDICT_CHUNK)
-        with torch.cuda.device(self.device):
-            x0d = torch.as_tensor(x0s).to(self.device, self.tdtype).contiguous()
-            scratch = self._grow_scratch(self._nbytes("lcgp_condition_scratch_bytes", self.dtype, self.n, self.q_local, m, chunk),
-                                         ("the conditioned prediction of %d new inputs per pass" % chunk,
-                                          "%d components of %d x (n + m), twice" % (self.q_local, chunk),
-                                          "lower lcgp_amd.engine.PREDICT_CHUNK"))
-            out = torch.empty((2, self.q_local, n0), dtype=torch.float64, device=self.device)
-            st, xp, srp, thp, wsp = self._stream(), self._p(self.x), self._p(self.sr), self._p(self.theta_dev), self._p(self.workspace)
-            for lo in range(0, n0, chunk):
-                rows = min(chunk, n0 - lo)
-                _hip.check(self.lib.lcgp_condition_predict(
-                    st, self.dtype, self.kernel_id, self.n, d, self.p, self.q_local, xp, srp, thp, wsp, self._p(state['state']), m,
-                    self._p(state['xn']), rows, C.c_void_p(x0d.data_ptr() + lo * d * x0d.element_size()), self._p(scratch),
-                    scratch.numel(), C.c_void_p(out[0].data_ptr() + 8 * lo), C.c_void_p(out[1].data_ptr() + 8 * lo), n0),
-                    "lcgp_condition_predict")
-            return out
 
     def _condition_grad_state(self, state):
         """the grad state of the view `state` (w = L_S^-T v and z' per local component: lcgp_condition_grad_prepare), built on
@@ -730,127 +728,18 @@ class HotPathEngine:
             state['grad'] = gs
         return gs
 
+    # (the per-point queries of the view `state`: the fitted model's methods with state)
+    def condition_predict_block(self, state, x0s):
+        return self.predict_block(x0s, state=state)
+
     def condition_predict_grad_block(self, state, x0s):
-        """(block, jac) float64 DEVICE tensors of the view `state` (condition_begin) at standardised x0s: block (2, q_local, n0)
-        = [ghat; gvar], bitwise condition_predict_block(state, x0s); jac (2, q_local, n0, d) = [dghat; dgvar], their
-        derivatives with respect to x0s (lcgp_condition_predict_grad: no nugget term, the gradient of the continuous surface,
-        also at the view's own new inputs).  Chunked as predict_grad_block is; the scratch is condition_predict_block's.  The
-        base factorisation must still be the one the state was built from."""
-        torch = self.torch
-        if not self.is_current(state['theta']):
-            raise RuntimeError("the conditioned view does not belong to the factorisation in the workspace")
-        x0s = np.ascontiguousarray(x0s, np.float64)
-        n0, d, m = x0s.shape[0], self.d, state['m']
-        assert x0s.ndim == 2 and x0s.shape[1] == d and n0 >= 1
-        chunk = min(n0, PREDICT_CHUNK)
-        with torch.cuda.device(self.device):
-            gs = self._condition_grad_state(state)
-            x0d = torch.as_tensor(x0s).to(self.device, self.tdtype).contiguous()
-            scratch = self._grow_scratch(
-                self._nbytes("lcgp_condition_predict_grad_scratch_bytes", self.dtype, self.n, self.q_local, m, chunk),
-                ("the conditioned gradient of %d new inputs per pass" % chunk,
-                 "%d components of %d x (n + m), twice" % (self.q_local, chunk), "lower lcgp_amd.engine.PREDICT_CHUNK"))
-            out = torch.empty((2, self.q_local, n0), dtype=torch.float64, device=self.device)
-            jac = torch.empty((2, self.q_local, n0, d), dtype=torch.float64, device=self.device)
-            st, xp, srp, thp, wsp = self._stream(), self._p(self.x), self._p(self.sr), self._p(self.theta_dev), self._p(self.workspace)
-            for lo in range(0, n0, chunk):
-                rows = min(chunk, n0 - lo)
-                _hip.check(self.lib.lcgp_condition_predict_grad(
-                    st, self.dtype, self.kernel_id, self.n, d, self.p, self.q_local, xp, srp, thp, wsp, self._p(state['state']), m,
-                    self._p(state['xn']), self._p(gs), rows, C.c_void_p(x0d.data_ptr() + lo * d * x0d.element_size()),
-                    self._p(scratch), scratch.numel(), C.c_void_p(out[0].data_ptr() + 8 * lo), C.c_void_p(out[1].data_ptr() + 8 * lo),
-                    C.c_void_p(jac[0].data_ptr() + 8 * lo * d), C.c_void_p(jac[1].data_ptr() + 8 * lo * d), n0),
-                    "lcgp_condition_predict_grad")
-            return out, jac
+        return self.predict_grad_block(x0s, state=state)
 
     def condition_predict_hess_block(self, state, x0s):
-        """(block, jac, hess) float64 DEVICE tensors of the view `state` (condition_begin) at standardised x0s: block and jac
-        bitwise those of condition_predict_grad_block(state, x0s); hess (2, q_local, n0, d (d + 1) / 2) = [d2ghat'; d2gvar'], the
-        packed lower triangles of the Hessians with respect to x0s in predict_hess_block's layout
-        (lcgp_condition_predict_hess).  Chunked as predict_hess_block is: max(128, PREDICT_CHUNK // d) inputs per pass, a short
-        last pass moved back over its predecessor, so the results do not depend on PREDICT_CHUNK.  The scratch holds that of
-        condition_predict_grad_block and q_local (chunk d)_pad (2 npad + 3 mpad) elements; raises ValueError when it does not fit
-        in the free device memory.  The base factorisation must still be the one the state was built from."""
-        torch = self.torch
-        if not self.is_current(state['theta']):
-            raise RuntimeError("the conditioned view does not belong to the factorisation in the workspace")
-        x0s = np.ascontiguousarray(x0s, np.float64)
-        n0, d, m = x0s.shape[0], self.d, state['m']
-        assert x0s.ndim == 2 and x0s.shape[1] == d and n0 >= 1
-        tri = d * (d + 1) // 2
-        chunk = min(n0, max(128, PREDICT_CHUNK // d))
-        with torch.cuda.device(self.device):
-            gs = self._condition_grad_state(state)
-            x0d = torch.as_tensor(x0s).to(self.device, self.tdtype).contiguous()
-            scratch = self._grow_scratch(
-                self._nbytes("lcgp_condition_predict_hess_scratch_bytes", self.dtype, self.n, d, self.q_local, m, chunk),
-                ("the conditioned Hessians of %d new inputs per pass" % chunk,
-                 "%d components of %d x (n + m), twice" % (self.q_local, chunk * (d + 1)), "lower lcgp_amd.engine.PREDICT_CHUNK"))
-            out = torch.empty((2, self.q_local, n0), dtype=torch.float64, device=self.device)
-            jac = torch.empty((2, self.q_local, n0, d), dtype=torch.float64, device=self.device)
-            hess = torch.empty((2, self.q_local, n0, tri), dtype=torch.float64, device=self.device)
-            st, xp, srp, thp, wsp = self._stream(), self._p(self.x), self._p(self.sr), self._p(self.theta_dev), self._p(self.workspace)
-            for lo in range(0, n0, chunk):
-                rows = min(chunk, n0 - lo)
-                if rows < 128 <= n0:
-                    lo, rows = n0 - 128, 128
-                x0p = C.c_void_p(x0d.data_ptr() + lo * d * x0d.element_size())
-                ptrs = [C.c_void_p(t[h].data_ptr() + 8 * lo * w) for t, w in ((out, 1), (jac, d), (hess, tri)) for h in (0, 1)]
-                _hip.check(self.lib.lcgp_condition_predict_hess(
-                    st, self.dtype, self.kernel_id, self.n, d, self.p, self.q_local, xp, srp, thp, wsp, self._p(state['state']), m,
-                    self._p(state['xn']), self._p(gs), rows, x0p, self._p(scratch), scratch.numel(), *ptrs, n0),
-                    "lcgp_condition_predict_hess")
-            return out, jac, hess
+        return self.predict_hess_block(x0s, state=state)
 
     def condition_grad_cov_block(self, state, x0s, w=None, per_point=True):
-        """(dghat, gamma, M) float64 DEVICE tensors of the view `state` (condition_begin) at standardised x0s, in grad_cov_block's
-        layout and with its arguments (lcgp_condition_predict_gradcov): dghat (q_local, n0, d) bitwise that of
-        condition_predict_grad_block(state, x0s); gamma the packed posterior covariance of the latent gradient given the
-        view's runs, or None with per_point=False; M = sum_i w_i gamma[:, i], reduced on the device in a fixed order, or None
-        without w.  Chunked as grad_cov_block is; the rows a moved-back pass repeats weigh zero in it.  The scratch holds
-        q_local (chunk d)_pad (2 npad + 3 mpad) elements; raises ValueError when it does not fit in the free device memory."""
-        torch = self.torch
-        if not self.is_current(state['theta']):
-            raise RuntimeError("the conditioned view does not belong to the factorisation in the workspace")
-        x0s = np.ascontiguousarray(x0s, np.float64)
-        n0, d, m = x0s.shape[0], self.d, state['m']
-        assert x0s.ndim == 2 and x0s.shape[1] == d and n0 >= 1
-        if w is None and not per_point:
-            raise ValueError("condition_grad_cov_block: per_point=False needs weights")
-        tri = d * (d + 1) // 2
-        chunk = min(n0, max(128, PREDICT_CHUNK // d))
-        with torch.cuda.device(self.device):
-            gs = self._condition_grad_state(state)
-            x0d = torch.as_tensor(x0s).to(self.device, self.tdtype).contiguous()
-            scratch = self._grow_scratch(
-                self._nbytes("lcgp_condition_predict_gradcov_scratch_bytes", self.dtype, self.n, d, self.q_local, m, chunk),
-                ("the conditioned gradient covariances of %d new inputs per pass" % chunk,
-                 "%d components of %d x (n + m), twice" % (self.q_local, chunk * d), "lower lcgp_amd.engine.PREDICT_CHUNK"))
-            dghat = torch.empty((self.q_local, n0, d), dtype=torch.float64, device=self.device)
-            gamma = torch.empty((self.q_local, n0, tri), dtype=torch.float64, device=self.device) if per_point else None
-            M = wd = None
-            if w is not None:
-                w = np.ascontiguousarray(w, np.float64).reshape(-1)
-                assert w.shape == (n0,)
-                wd = torch.as_tensor(w).to(self.device)
-                M = torch.zeros((self.q_local, tri), dtype=torch.float64, device=self.device)
-            st, xp, srp, thp, wsp = self._stream(), self._p(self.x), self._p(self.sr), self._p(self.theta_dev), self._p(self.workspace)
-            for lo in range(0, n0, chunk):
-                rows = min(chunk, n0 - lo)
-                wp = None if wd is None else C.c_void_p(wd.data_ptr() + 8 * lo)
-                if rows < 128 <= n0:
-                    if wd is not None:                  # the rows n0 - 128 .. lo were summed by the pass before
-                        wl = wd[n0 - 128:].clone()
-                        wl[:lo - (n0 - 128)] = 0.0
-                        wp = self._p(wl)
-                    lo, rows = n0 - 128, 128
-                x0p = C.c_void_p(x0d.data_ptr() + lo * d * x0d.element_size())
-                _hip.check(self.lib.lcgp_condition_predict_gradcov(
-                    st, self.dtype, self.kernel_id, self.n, d, self.p, self.q_local, xp, srp, thp, wsp, self._p(state['state']), m,
-                    self._p(state['xn']), self._p(gs), rows, x0p, self._p(scratch), scratch.numel(),
-                    C.c_void_p(dghat.data_ptr() + 8 * lo * d), None if gamma is None else C.c_void_p(gamma.data_ptr() + 8 * lo * tri),
-                    wp, None if M is None else self._p(M), n0), "lcgp_condition_predict_gradcov")
-            return dghat, gamma, M
+        return self.grad_cov_block(x0s, w, per_point, state=state)
 
     # ------------------------------------------------------------------------------------------------
     # closed-form cross-validation at fixed parameters (lcgp_hip.h: lcgp_loo, lcgp_cv_gather / lcgp_cv_apply)
@@ -997,13 +886,11 @@ class HotPathEngine:
             wd = torch.as_tensor(np.ascontiguousarray(w, np.float64)).to(self.device)
             md = None if match is None else torch.as_tensor(match).to(self.device)
             out = torch.empty((self.q_local, n_cand), dtype=torch.float64, device=self.device)
-            st, xp, srp, thp, wsp, scp = (self._stream(), self._p(self.x), self._p(self.sr), self._p(self.theta_dev),
-                                          self._p(self.workspace), self._p(scratch))
             # (the entries on a view take the view behind the workspace and the scratch size behind the scratch)
             prepare, entry = (("lcgp_variance_reduction_prepare", "lcgp_variance_reduction") if state is None else
                               ("lcgp_condition_vr_prepare", "lcgp_condition_vr"))
-            scs = (scp,) if state is None else (scp, scratch.numel())
-            head = (st, self.dtype, self.kernel_id, self.n, d, self.p, self.q_local, xp, srp, thp, wsp) + view
+            scs = (self._p(scratch),) if state is None else (self._p(scratch), scratch.numel())
+            head = self._head() + view
             _hip.check(getattr(self.lib, prepare)(*head, n_ref, self._p(xr), *scs), prepare)
             for lo in range(0, n_cand, chunk):
                 rows = min(chunk, n_cand - lo)
@@ -1058,13 +945,11 @@ class HotPathEngine:
             wd = torch.as_tensor(np.ascontiguousarray(w, np.float64)).to(self.device)
             out = torch.empty((self.q_local, n_cand), dtype=torch.float64, device=self.device)
             dout = torch.empty((self.q_local, n_cand, d), dtype=torch.float64, device=self.device)
-            st, xp, srp, thp, wsp, scp = (self._stream(), self._p(self.x), self._p(self.sr), self._p(self.theta_dev),
-                                          self._p(self.workspace), self._p(scratch))
             # (the entries on a view take the view behind the workspace and the scratch size behind the scratch)
             prepare, entry = (("lcgp_variance_reduction_prepare", "lcgp_variance_reduction_grad") if state is None else
                               ("lcgp_condition_vr_prepare", "lcgp_condition_vr_grad"))
-            scs = (scp,) if state is None else (scp, scratch.numel())
-            head = (st, self.dtype, self.kernel_id, self.n, d, self.p, self.q_local, xp, srp, thp, wsp) + view
+            scs = (self._p(scratch),) if state is None else (self._p(scratch), scratch.numel())
+            head = self._head() + view
             _hip.check(getattr(self.lib, prepare)(*head, n_ref, self._p(xr), *scs), prepare)
             for lo in range(0, n_cand, chunk):
                 rows = min(chunk, n_cand - lo)
@@ -1117,9 +1002,7 @@ class HotPathEngine:
             md = None if match is None else torch.as_tensor(match).to(self.device)
             scs = (self._p(scratch), scratch.numel()) if view else (self._p(scratch),)
             _hip.check(getattr(self.lib, pre + "begin")(
-                self._stream(), self.dtype, self.kernel_id, self.n, d, self.p, self.q_local,
-                self._p(self.x), self._p(self.sr), self._p(self.theta_dev), self._p(self.workspace), *view,
-                n_ref, self._p(xr), self._p(wd), n_cand, self._p(xc),
+                *self._head(), *view, n_ref, self._p(xr), self._p(wd), n_cand, self._p(xc),
                 C.c_void_p(0) if match is None else C.c_void_p(match.ctypes.data),
                 C.c_void_p(0) if md is None else self._p(md), int(r), int(size),
                 min(PREDICT_CHUNK, 2048), *scs), pre + "begin")
@@ -1222,12 +1105,9 @@ class HotPathEngine:
             scp = self._p(self._grow_scratch(nbytes, ("the Hessian of the objective", "%d matrices of n x n per component"
                                                       % (self.d + 4), "use fewer training inputs per GPU")))
             out = torch.empty((self.q_local, width), dtype=torch.float64, device=self.device)
-            st = self._stream()
+            head = self._head(Y=True)
             for k0 in range(0, self.q_local, group):
-                _hip.check(self.lib.lcgp_nll_hess(st, self.dtype, self.kernel_id, self.n, self.d, self.p, self.q_local,
-                                                  self._p(self.x), self._p(self.Y), self._p(self.sr), self._p(self.theta_dev),
-                                                  self._p(self.workspace), k0, min(group, self.q_local - k0), scp, self._p(out)),
-                           "lcgp_nll_hess")
+                _hip.check(self.lib.lcgp_nll_hess(*head, k0, min(group, self.q_local - k0), scp, self._p(out)), "lcgp_nll_hess")
             return out
 
     def fetch_vector(self, which, k):

@@ -329,15 +329,8 @@ class ConditionedLCGP:
         base = self.base
         x0s = base._x0_2d(x0, 'x0')
         self._require_current()
-        n0, d = x0s.shape
-        loc = None
-        if self._engine is not None:
-            blk, jac = self._engine.condition_predict_grad_block(self._state, x0s)
-            loc = torch.cat([blk.permute(1, 0, 2).reshape(blk.shape[1], -1),
-                             jac.permute(1, 0, 2, 3).reshape(jac.shape[1], -1)], dim=1)
-        both = base._gather_components(loc, (2 * n0 + 2 * n0 * d,))
-        jac = both[:, 2 * n0:].reshape(int(base.q), 2, n0, d)
-        return both[:, :n0], both[:, n0:2 * n0], jac[:, 0], jac[:, 1]
+        eng, st = self._engine, self._state
+        return base._latent_grad_result(x0s, None if eng is None else lambda: eng.condition_predict_grad_block(st, x0s))
 
     def predict_grad(self, x0, latent=False):
         """LCGP.predict_grad() of the conditioned model: (dypred, dypredvar, dyconfvar), each (p, n0, d) CPU float64 on the raw
@@ -2215,20 +2208,24 @@ class LCGP:
         x0: the local components on the device (lcgp_predict_grad), ONE reduction of the zero-padded block gathers them.
         No nugget term (same = 0 even at training inputs): the gradient of the continuous prediction surface."""
         x0s, _ = self._standardise_x0(x0)
-        n0, d = x0s.shape
         eng = self._ensure_aux()
-        loc = None
-        if eng is not None:
-            blk, jac = eng.predict_grad_block(x0s)
-            loc = torch.cat([blk.permute(1, 0, 2).reshape(blk.shape[1], -1),
-                             jac.permute(1, 0, 2, 3).reshape(jac.shape[1], -1)], dim=1)
-        both = self._gather_components(loc, (2 * n0 + 2 * n0 * d,))
-        q = int(self.q)
-        ghat, gvar = both[:, :n0], both[:, n0:2 * n0]
-        jac = both[:, 2 * n0:].reshape(q, 2, n0, d)
+        res = self._latent_grad_result(x0s, None if eng is None else lambda: eng.predict_grad_block(x0s))
+        ghat, gvar, dghat, dgvar = res
         self.ghat, self.gvar = _t(ghat), _t(gvar)
-        self.dghat, self.dgvar = _t(jac[:, 0]), _t(jac[:, 1])
-        return ghat, gvar, jac[:, 0], jac[:, 1]
+        self.dghat, self.dgvar = _t(dghat), _t(dgvar)
+        return res
+
+    def _latent_grad_result(self, x0s, block):
+        """_latent_predict_grad's gather for this rank's (blk, jac) = block() (None on a rank without components): shared with
+        ConditionedLCGP"""
+        n0, d = x0s.shape
+        loc = None
+        if block is not None:
+            blk, jac = block()
+            loc = torch.cat([t.movedim(1, 0).reshape(t.shape[1], -1) for t in (blk, jac)], dim=1)
+        both = self._gather_components(loc, (2 * n0 + 2 * n0 * d,))
+        jac = both[:, 2 * n0:].reshape(int(self.q), 2, n0, d)
+        return both[:, :n0], both[:, n0:2 * n0], jac[:, 0], jac[:, 1]
 
     def _output_jacobians(self, dghat, dgvar):
         """latent Jacobians (q, n0, d) on the standardised scale -> (dypred, dyconfvar) (p, n0, d) on the raw input and output

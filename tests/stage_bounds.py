@@ -3,7 +3,9 @@ joint path (cross covariance X, U = X W^T, Sigma + tau I, its factor, the draws)
 the input gradients of lcgp_predict_grad, leave-one-out, the k-fold gather / factor / inverse / apply, the integrated
 variance reduction) and of the conditioned view (lcgp_condition_prepare / lcgp_condition_predict: S and its factor, the dense
 L_S^-1, v, Sigma_0n, T and the corrected outputs) and of the two second-order input queries (lcgp_predict_hess: DX, P = DX W^T,
-the packed Hessians; lcgp_predict_gradcov: dghat, Gamma and its weighted sum M).
+the packed Hessians; lcgp_predict_gradcov: dghat, Gamma and its weighted sum M) and of the box-averaged predictions
+(lcgp_predict_marginal / lcgp_condition_predict_marginal: the table of 1-D averages against mpmath, the masked rows, the outputs
+with the averaged prior, the view's stages and gcov).
 
 Every check compares one stage of the library with a plain float64 reference computed from THE LIBRARY'S OWN INPUT TO THAT
 STAGE (the fetched A for the Cholesky, the fetched L for L^-1, ...), so no bound carries a condition number.  Entries are
@@ -30,7 +32,9 @@ from __future__ import annotations
 import math
 from collections import namedtuple
 
+import mpmath as mp
 import numpy as np
+import scipy.special
 import torch
 
 TS = 64                  # tile size of the library (64 x 64 tiles): locations are reported in these blocks
@@ -1227,3 +1231,456 @@ def check_gradcov_sum(M_after, M_before, gamma, w) -> Check:
     i = int(torch.argmax(r))
     d = int(round((math.sqrt(8 * r.numel() + 1) - 1) / 2))
     return Check(float(r[i]), (tri_names(d, "M")[i],))
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# box-averaged predictions (lcgp_predict_marginal, lcgp_condition_predict_marginal): marg_table_kernel -> the masked instance of
+# cross_kernel -> U = X W^T (check_cov_u) -> marg_reduce_kernel; on a view the second table over xn, the masked rows against
+# xn, OP_COND_CROSS, T (check_cov_u) and cond_reduce_kernel (check_cond_out, from an m = 0 call); marg_refcov_kernel (gcov).
+#
+# The table is the one stage of the library whose reference cannot be a float64 restatement: its formulas (a 20-term series
+# below b = 1/2, closed forms with expm1 / erf / erfc above, three branches of I1) lose accuracy in places, and a restatement
+# with the same switches loses it in the same places.  marg_exact / marg_exact2 are mpmath references with one formula per
+# region and no switch; the bounds below FOLLOW the library's branches, the references do not.
+# ----------------------------------------------------------------------------------------------------------------------
+MARG_DPS = 50                   # digits of the mpmath references (guard digits are added where a closed form cancels)
+MARG_ULP = 4.0                  # ASSUMED error of one device exp / expm1 / erf / erfc call, in ulp: no ulp table of ROCm's device
+#                                 maths ships with the toolchain this suite runs on, so the largest figure the public tables of
+#                                 comparable device libraries give for these four in double (1, 1, 2, 4..5) is taken for all
+MARG_SERIES_BELOW = 0.5         # lcgp_hip.hip MARG_SERIES_BELOW / MARG_SERIES_TERMS: for the BOUND only (which terms are summed)
+MARG_SERIES_TERMS = 20
+# roundings of the closed forms beyond the special-function call, counted from marg_F / marg_G / marg_Fc:
+#   Matern-3/2  F = 2 em - b e: the product b e, the difference (2 em is exact): 2, kept at 3 (one of margin)           3
+#               G = 3 em - b (3 + b) e: 3 + b, two products, 3 em, the difference                                        5
+#               Fc = (2 + b) e: the sum, the product                                                                      2
+#   Matern-5/2  F = (8/3) em - b (5 + b) / 3 e: the constant (1/2), its product, 5 + b, b *, / 3, * e, the difference     7
+#               G = 5 em - b (5 + b (2 + b / 3)) e: b / 3, 2 +, b *, 5 +, b *, * e, 5 em, the difference                   8
+#               Fc = (8 + b (5 + b)) / 3 e: 5 + b, b *, 8 +, / 3, * e                                                     5
+#   SE          F, Fc = c erf|erfc(b s): the constant c (1/2) and its product (the product b s and the constant s act on the
+#               ARGUMENT: MARG_ARG)                                                                                        2
+#               G = -expm1(-(b / 2) b): the product, whose error u b^2 / 2 moves G by at most u G (x e^-x <= 1 - e^-x)       1
+# each on the sum of the absolute values of the terms of that form (_marg_terms)
+MARG_ROUNDINGS = {("matern32", "F"): 3, ("matern32", "G"): 5, ("matern32", "Fc"): 2,
+                  ("matern52", "F"): 7, ("matern52", "G"): 8, ("matern52", "Fc"): 5,
+                  ("se", "F"): 2, ("se", "G"): 1, ("se", "Fc"): 2}
+# the series: term m is t_m f(m) / (m + 1 | m + 2) with t_m = (-b)^m / m! built by m products and m quotients: 2 m + 3 roundings
+# (the product with f, the quotient, f = (m - 1)(m - 3) / 3 itself for Matern-5/2) on a term that is below 1/2^m / m! of the
+# first, so sum_m (2 m + 3) |term_m| <= 4 sum_m |term_m| (m = 0: 3; m = 2: 7/24; m = 3: 9/192; ...); the 20 additions add at most
+# u times the largest partial sum each (<= sum |term_m|), the products b sf / b b sg one / two more: 4 + 20 + 2, and one of margin
+MARG_SERIES_ROUNDINGS = 27.0
+# roundings of the ARGUMENT b = |xv - lo| / ell (the difference and the quotient: 2), for SE also b s and the constant s (1.5),
+# rounded up; they act through dF / db = kappa(b), dFc / db = -kappa(b): |dF| <= MARG_ARG u b kappa(b)
+MARG_ARG = {"matern32": 2.0, "matern52": 2.0, "se": 4.0}
+_MARG_CACHE = {}
+
+
+def _kappa(kernel, b):
+    """the 1-D factor of the product kernel at the scaled distance b >= 0 (float64 numpy)"""
+    _known(kernel)
+    if kernel == "se":
+        return np.exp(-0.5 * b * b)
+    if kernel == "matern32":
+        return (1.0 + b) * np.exp(-b)
+    return (1.0 + b + b * b / 3.0) * np.exp(-b)
+
+
+def _marg_mp(kernel, which, b):
+    """F(b) = int_0^b kappa, Fc(b) = int_b^inf kappa or G(b) = int_0^b u kappa(u) du in mpmath, MARG_DPS digits AFTER the
+    cancellation of the closed form at small b (F ~ b, G ~ b^2 / 2 from terms of order one: two, three decimal guard digits
+    per decade of 1 / b).  The tails go through erfc and the exact Matern tails, never through 1 - F."""
+    _known(kernel)
+    guard = 0 if (b == 0 or b >= 1) else 3 * (int(-mp.log10(b)) + 1)
+    with mp.workdps(MARG_DPS + 10 + guard):
+        if kernel == "se":
+            if which == "F":
+                return mp.sqrt(mp.pi / 2) * mp.erf(b / mp.sqrt(2))
+            if which == "Fc":
+                return mp.sqrt(mp.pi / 2) * mp.erfc(b / mp.sqrt(2))
+            return -mp.expm1(-b * b / 2)
+        e = mp.exp(-b)
+        if kernel == "matern32":
+            if which == "F":
+                return -2 * mp.expm1(-b) - b * e
+            if which == "Fc":
+                return (2 + b) * e
+            return -3 * mp.expm1(-b) - b * (3 + b) * e
+        if which == "F":
+            return -mp.mpf(8) / 3 * mp.expm1(-b) - b * (5 + b) / 3 * e
+        if which == "Fc":
+            return (8 + b * (5 + b)) / 3 * e
+        return -5 * mp.expm1(-b) - b * (5 + b * (2 + b / 3)) * e
+
+
+def marg_exact(kernel, x, lo, hi, ell):
+    """I1 = (1 / w) int_lo^hi kappa(|t - x| / ell) dt, w = hi - lo, for every value of the float64 array x (lo, hi, ell: float64
+    scalars, taken as exact), as an object array of mpmath numbers of MARG_DPS digits.  One formula per region:
+        x inside [lo, hi] (ends included):   (ell / w) [F(b1) + F(b2)],      b1 = (x - lo) / ell, b2 = (hi - x) / ell
+        x outside:                           (ell / w) [Fc(bn) - Fc(bf)],    bn < bf the scaled distances to the two ends
+    with Fc through erfc (SE) or the exact Matern tails -- F(bf) - F(bn) is wrong in the far tails at ANY working precision that
+    does not grow with b, which is how a 60-digit reference of that form went wrong in the SE tails.  No series, no switch at
+    b = 1/2, none at bn = 1; nothing from tests/marginal_ref.py.  b1, b2 are formed exactly (the differences of floats are exact
+    in mpmath).  Cached per (kernel, ell, lo, hi, x value): a case costs at most q d n evaluations."""
+    _known(kernel)
+    xs = np.asarray(x, np.float64)
+    key = (kernel, float(ell), float(lo), float(hi))
+    cache = _MARG_CACHE.setdefault(key, {})
+    out = np.empty(xs.shape, object)
+    flat = out.reshape(-1)
+    with mp.workdps(MARG_DPS + 10):
+        le, l0, h0 = mp.mpf(float(ell)), mp.mpf(float(lo)), mp.mpf(float(hi))
+        w = h0 - l0
+        for i, v in enumerate(xs.reshape(-1).tolist()):
+            got = cache.get(v)
+            if got is None:
+                xv = mp.mpf(v)
+                a1, a2 = xv - l0, h0 - xv
+                b1, b2 = abs(a1) / le, abs(a2) / le
+                if a1 >= 0 and a2 >= 0:
+                    r = _marg_mp(kernel, "F", b1) + _marg_mp(kernel, "F", b2)
+                else:
+                    r = _marg_mp(kernel, "Fc", min(b1, b2)) - _marg_mp(kernel, "Fc", max(b1, b2))
+                got = cache[v] = le / w * r
+            flat[i] = got
+    return out
+
+
+def marg_exact2(kernel, w, ell):
+    """I2 = (1 / w^2) int int kappa(|t - t'| / ell) dt dt' over [0, w]^2 = 2 [F(a) / a - G(a) / a^2], a = w / ell, in mpmath
+    (MARG_DPS digits; w: a float or an mpmath number -- the exact hi - lo)"""
+    _known(kernel)
+    key = (kernel, float(ell), "i2", str(w))
+    if key not in _MARG_CACHE:
+        with mp.workdps(MARG_DPS + 10):
+            a = mp.mpf(w) / mp.mpf(float(ell))
+            _MARG_CACHE[key] = 2 * (_marg_mp(kernel, "F", a) / a - _marg_mp(kernel, "G", a) / (a * a))
+    return _MARG_CACHE[key]
+
+
+def _mp_err(got, exact):
+    """|got - exact| as float64: got a float64 array, exact an object array of mpmath numbers (NaN in got: inf)"""
+    g = np.asarray(got, np.float64)
+    out = np.empty(g.shape, np.float64)
+    with mp.workdps(MARG_DPS + 10):
+        for i, (a, b) in enumerate(zip(g.reshape(-1).tolist(), np.asarray(exact, object).reshape(-1))):
+            out.reshape(-1)[i] = float(abs(mp.mpf(a) - b)) if math.isfinite(a) else math.inf
+    return out
+
+
+def _marg_terms(kernel, which, b):
+    """K A of one evaluation of marg_F / marg_G / marg_Fc at b (a float64 array) IN THE BRANCH THE LIBRARY TAKES: A the sum of the
+    absolute values of the terms that form adds or subtracts, K its count of roundings in units of u (MARG_ULP per special
+    function call plus MARG_ROUNDINGS, or MARG_SERIES_ROUNDINGS).  |error of the evaluation| <= u K A."""
+    _known(kernel)
+    b = np.asarray(b, np.float64)
+    k = MARG_ULP + MARG_ROUNDINGS[kernel, which]
+    if kernel == "se":
+        s = math.sqrt(0.5)
+        c = math.sqrt(0.5 * math.pi)
+        if which == "G":
+            return k * -np.expm1(-0.5 * b * b)
+        return k * c * (scipy.special.erf(b * s) if which == "F" else scipy.special.erfc(b * s))
+    e, em = np.exp(-b), -np.expm1(-b)
+    if which == "Fc":
+        return k * ((2.0 + b) * e if kernel == "matern32" else (8.0 + b * (5.0 + b)) / 3.0 * e)
+    if kernel == "matern32":
+        closed = 2.0 * em + b * e if which == "F" else 3.0 * em + b * (3.0 + b) * e
+    else:
+        closed = (8.0 / 3.0) * em + b * (5.0 + b) / 3.0 * e if which == "F" else 5.0 * em + b * (5.0 + b * (2.0 + b / 3.0)) * e
+    bs = np.minimum(b, MARG_SERIES_BELOW)
+    t, sa = np.ones_like(bs), np.zeros_like(bs)
+    for m in range(MARG_SERIES_TERMS):
+        f = abs(1.0 - m) if kernel == "matern32" else abs((m - 1.0) * (m - 3.0)) / 3.0
+        sa = sa + t * f / (m + (1.0 if which == "F" else 2.0))
+        t = t * bs / (m + 1.0)
+    series = bs * sa if which == "F" else bs * bs * sa
+    return np.where(b < MARG_SERIES_BELOW, MARG_SERIES_ROUNDINGS * series, k * closed)
+
+
+def marg_table_bound(kernel, xv, lo, hi, ell):
+    """the bound of check_marg_table on |I1 - exact| for the values xv (float64 array; lo, hi, ell float64 scalars), without C:
+        u (ell / w) [ K1 A1 + K2 A2 + 3 (A1 + A2) + MARG_ARG (b1 kappa(b1) + b2 kappa(b2)) ]
+    marg_I1 forms w = hi - lo, a1 = xv - lo, a2 = hi - xv, b = |a| / ell (one rounding each) and takes one of three branches:
+    F(b1) + F(b2) inside (a1, a2 >= 0: the sign of a rounded difference is the exact one, so the library and the reference
+    agree on it), otherwise with bn <= bf: Fc(bn) - Fc(bf) if bn > 1, else F(bf) - F(bn).  The b are recomputed here with the same
+    three IEEE operations, so this follows the library's branch also at bn = 1 and b = 1/2 to the last bit.
+      - K A: the evaluation of each of the two terms (_marg_terms).  The two are then added or subtracted and the result is
+        scaled: the sum, w, ell / w and the product are four roundings of |r| <= A1 + A2, counted as 3 (w and ell / w act on the
+        factor alone; half of each is in the margin of C).  Outside the box the result is (ell / w) kappa(.) (bf - bn) while the
+        terms stay of order one: the error relative to the RESULT grows like ell / w -- the narrow-box loss, a property of the
+        formula, which this bound admits and profiles/stage_bounds_marginal.txt records.
+      - the argument: b carries two roundings and F' = kappa, Fc' = -kappa: u MARG_ARG b kappa(b) per end.  Relative to a tail
+        Fc(b) ~ kappa(b) / b (SE) this is u MARG_ARG b^2: the argument magnification of the far SE tails."""
+    _known(kernel)
+    xv = np.asarray(xv, np.float64)
+    lo, hi, ell = float(lo), float(hi), float(ell)
+    w = hi - lo
+    a1, a2 = xv - lo, hi - xv
+    b1, b2 = np.abs(a1) / ell, np.abs(a2) / ell
+    inside = (a1 >= 0.0) & (a2 >= 0.0)
+    far = ~inside & (np.minimum(b1, b2) > 1.0)
+    t1 = np.where(far, _marg_terms(kernel, "Fc", b1), _marg_terms(kernel, "F", b1))
+    t2 = np.where(far, _marg_terms(kernel, "Fc", b2), _marg_terms(kernel, "F", b2))
+    k1 = MARG_ULP + np.where(far, MARG_ROUNDINGS[kernel, "Fc"], MARG_ROUNDINGS[kernel, "F"])
+    # 3 (A1 + A2) <= 3 (K1 A1 + K2 A2) / min K: expressed through the K A already formed
+    extra = 3.0 * (t1 + t2) / np.minimum(k1, MARG_SERIES_ROUNDINGS)
+    arg = MARG_ARG[kernel] * (b1 * _kappa(kernel, b1) + b2 * _kappa(kernel, b2))
+    return unit("float64") * (ell / w) * (t1 + t2 + extra + arg)
+
+
+def marg_i2_bound(kernel, w, ell):
+    """the bound of check_marg_table on |I2 - exact|, without C.  marg_table_kernel: a = w / ell (w = hi - lo: two roundings),
+    2 (F(a) / a - G(a) / (a a)): the evaluations (K_F A_F, K_G A_G of _marg_terms), one / two roundings for the quotients, one
+    for the difference, and the argument through d/da [F / a - G / a^2] = -F / a^2 + 2 G / a^3 (the kappa terms cancel) with
+    |da| <= 2 u a:      2 u [ (K_F A_F + F) / a + (K_G A_G + 2 G) / a^2 + (F / a + G / a^2) + 2 (F / a + 2 G / a^2) ]
+    with F <= A_F, G <= A_G used for the values."""
+    a = (float(w)) / float(ell)
+    kf, kg = float(_marg_terms(kernel, "F", a)), float(_marg_terms(kernel, "G", a))
+    kmin = MARG_ULP + 1.0
+    f, g = kf / kmin, kg / kmin                      # upper bounds of A_F >= F and A_G >= G (every K is at least MARG_ULP + 1)
+    return 2.0 * unit("float64") * ((kf + 4.0 * f) / a + (kg + 7.0 * g) / (a * a))
+
+
+def check_marg_table(tab, i2, x, th, box, kernel, dtype, n, npad) -> Check:
+    """the table of 1-D box averages (tab: q x d x npad doubles, i2: q x d doubles; double in BOTH storage types) after
+    marg_table_kernel, entry by entry against marg_exact at the ROUNDED x (the library converts the stored x to double) and
+    marg_exact2 at the exact hi - lo, for the theta rows th (q x tw) and box (2 x d):
+        |tab - I1| <= C marg_table_bound + floor (1 + ell / w),        |i2 - I2| <= C marg_i2_bound + floor
+    (the floor: the tails underflow to denormals and to zero where the exact value is 1e-320 or less; it scales with the factor
+    ell / w that multiplies the underflowed difference).  Columns n .. npad - 1 must be BITWISE 1.0 (the masked cross_kernel
+    multiplies whole 64-column tiles into poly; their products are discarded, but a NaN there must not be relied on to vanish).
+    Locations: (component, dimension, 64-block of the column), or (component, dimension, "i2")."""
+    _known(kernel)
+    tb = np.asarray(tab.cpu() if isinstance(tab, torch.Tensor) else tab, np.float64)
+    ii = np.asarray(i2.cpu() if isinstance(i2, torch.Tensor) else i2, np.float64)
+    th = np.atleast_2d(np.asarray(th, np.float64))
+    box = np.asarray(box, np.float64)
+    q, d = ii.shape
+    assert tb.shape == (q, d, npad) and th.shape[0] == q and box.shape == (2, d), (tb.shape, ii.shape, th.shape, box.shape)
+    xr = rounded(x, dtype)[:n]
+    one = np.float64(1.0).view(np.int64)
+    best = Check(0.0, ())
+    for k in range(q):
+        for l in range(d):
+            lo, hi, ell = box[0, l], box[1, l], th[k, l]
+            pad = tb[k, l, n:].view(np.int64) != one
+            if pad.any():
+                return Check(math.inf, (k, l, (n + int(np.argmax(pad))) // TS))
+            r = marg_table_ratios(kernel, tb[k, l, :n], xr[:, l], lo, hi, ell)
+            j = int(np.argmax(r))
+            if r[j] > best.ratio:
+                best = Check(float(r[j]), (k, l, j // TS))
+            with mp.workdps(MARG_DPS + 10):
+                e2 = float(abs(mp.mpf(float(ii[k, l])) - marg_exact2(kernel, mp.mpf(float(hi)) - mp.mpf(float(lo)), ell))) \
+                    if math.isfinite(ii[k, l]) else math.inf
+            r2 = e2 / (C * marg_i2_bound(kernel, hi - lo, ell) + floor("float64", 1))
+            if r2 > best.ratio:
+                best = Check(float(r2), (k, l, "i2"))
+    return best
+
+
+def marg_table_ratios(kernel, got, xv, lo, hi, ell):
+    """|got - I1| / (C marg_table_bound + floor (1 + ell / w)) per value of xv (float64 arrays; NaN counts as inf): the ratios of
+    check_marg_table for one (component, dimension), also for a restatement evaluated on a grid"""
+    err = _mp_err(got, marg_exact(kernel, xv, lo, hi, ell))
+    bound = C * marg_table_bound(kernel, xv, lo, hi, ell) + floor("float64", 1) * (1.0 + float(ell) / (float(hi) - float(lo)))
+    r = err / bound
+    r[np.isnan(r)] = math.inf
+    return r
+
+
+def marg_floor_fraction(x, th, box, kernel, dtype):
+    """the fraction of the table entries (n x d, one theta row) whose bound is set by the absolute floor, not by the terms of
+    marg_table_bound (the CPU tests hold it below 1 % in the default-box and sub-box cases)"""
+    xr = rounded(x, dtype)
+    th = np.asarray(th, np.float64)
+    cnt = 0
+    for l in range(xr.shape[1]):
+        lo, hi, ell = box[0][l], box[1][l], th[l]
+        cnt += int(np.sum(C * marg_table_bound(kernel, xr[:, l], lo, hi, ell) < floor("float64", 1) * (1.0 + ell / (hi - lo))))
+    return cnt / xr.size
+
+
+def _marg_cross_ref(tab, x0, mask, x2, colscale, th, kernel, dtype, dev):
+    """(ref, bound weight E', cut) of the masked rows: ref_ij = scale (1 - nt) C0_kept(x0_i, x2_j) prod_{l in mask_i} tab[l, j]
+    cs_j in float64 from the LIBRARY'S table (d x n2pad) and the rounded x0, x2, colscale; E' = E of kernel_parts over the KEPT
+    dimensions of the row + 4 + the number of masked dimensions.  x0 under the mask is never read (np.where first)."""
+    mask = np.asarray(mask) != 0
+    n0, d = mask.shape
+    x2r = rounded(x2, dtype)
+    n2 = x2r.shape[0]
+    x0r = rounded(np.where(mask, 0.0, np.asarray(x0, np.float64)), dtype)
+    ell, scale, nug, D, _ = split_theta(th, d)
+    nt = nug / (1.0 + nug)
+    tb = _t(tab, dev)[:, :n2]
+    cs = _t(rounded(np.ones(n2) if colscale is None else colscale, dtype), dev)
+    ref = torch.zeros(n0, n2, dtype=torch.float64, device=dev)
+    ew = torch.zeros_like(ref)
+    cut = torch.zeros(n0, n2, dtype=torch.bool, device=dev)
+    pats, inv = np.unique(mask, axis=0, return_inverse=True)
+    inv = np.asarray(inv).reshape(-1)
+    for pi, pat in enumerate(pats):
+        rows = np.nonzero(inv == pi)[0]
+        keep = np.nonzero(~pat)[0]
+        c0, e, ct = kernel_parts(x0r[rows][:, keep], x2r[:, keep], ell[keep], kernel, dtype, dev)
+        prod = torch.ones(n2, dtype=torch.float64, device=dev)
+        for l in np.nonzero(pat)[0]:
+            prod = prod * tb[int(l)]
+        ri = torch.as_tensor(rows, device=dev)
+        ref[ri] = scale * (1.0 - nt) * c0 * (prod * cs)[None, :]
+        ew[ri] = e + 4.0 + float(pat.sum())
+        cut[ri] = ct
+    return ref, ew, cut
+
+
+def check_marg_cross(X, tab, x0, mask, x2, colscale, th, kernel, dtype, plain=None) -> Check:
+    """the masked rows (X: n0 x n2, one component; the first slabs of the scratch against the training inputs with colscale = sr,
+    or -- before OP_COND_CROSS overwrites them -- the view's rows against xn with colscale = None; never a nugget term) against
+        X_ij = scale (1 - nt) [prod_{l kept} kappa(|x0_il - x2_jl| / ell_l)] [prod_{l in mask_i} tab[l, j]] cs_j
+    in float64 from the library's OWN table tab (d x n2pad doubles of this component), the rounded x0, x2, colscale.  The kept
+    dimensions go through kernel_parts restricted to them (E of its docstring with d := the number kept; the exponent is summed
+    over kept dimensions only, and so is the cut-off); each masked dimension multiplies one table entry into poly: one rounding.
+    Then scale (1 - nt), cs and the store as in check_cov_cross:      C (E_kept + 4 + #masked) u |X_ij|  (+ |X_ij| past the cut-off).
+    Entries of x0 under the mask are never read here either: the tests pass NaN there, and a library that loads them returns NaN
+    (ratio inf).  plain: the same rows from the plain path (lcgp_predict's X on x0 with zeros under the mask); every row with an
+    EMPTY mask must equal it bitwise (ratio inf otherwise).  Locations: (row block, column block)."""
+    dev = _dev(X)
+    ref, ew, cut = _marg_cross_ref(tab, x0, mask, x2, colscale, th, kernel, dtype, dev)
+    d = np.asarray(mask).shape[1]
+    bound = C * ew * unit(dtype) * ref.abs() + torch.where(cut, ref.abs(), torch.zeros_like(ref)) + floor(dtype, d)
+    got = _t(X, dev)
+    c = worst((got - ref).abs(), bound, lower=False)
+    if plain is not None:
+        empty = torch.as_tensor(~(np.asarray(mask) != 0).any(axis=1), device=dev)
+        a, b = got[empty].contiguous(), _t(plain, dev)[empty].contiguous()
+        bad = a.view(torch.int64) != b.view(torch.int64)
+        if bool(bad.any()):
+            i, j = (int(v) for v in torch.nonzero(bad)[0])
+            return Check(math.inf, (int(torch.nonzero(empty)[i]) // TS, j // TS))
+    return c
+
+
+def marg_prior(i2, mask, th):
+    """the prior of marg_reduce_kernel per row (float64 numpy): scale (1 - nt) prod_{l in mask_i} i2[l] in ascending l from the
+    library's own i2 (d doubles), or scale for a row with an empty mask"""
+    mask = np.asarray(mask) != 0
+    d = mask.shape[1]
+    ell, scale, nug, D, _ = split_theta(th, d)
+    pr = np.full(mask.shape[0], scale * (1.0 - nug / (1.0 + nug)))
+    ii = np.asarray(i2, np.float64)
+    for l in range(d):
+        pr = np.where(mask[:, l], pr * ii[l], pr)
+    return np.where(mask.any(axis=1), pr, scale)
+
+
+def check_marg_out(ghat, gvar, X, U, z, i2, mask, th, dtype) -> Check:
+    """ghat / gvar of lcgp_predict_marginal (n0 doubles each, one component) against
+        ghat = X z,     gvar = prior - D rowsum(U o U),     prior = marg_prior (the nugget averages out; an empty mask: scale)
+    in float64 from the library's own X, U (n0 x n), z (fetched) and i2.  marg_reduce_kernel converts the stored rows to double
+    and sums n terms in double (64 lanes, then the butterfly); the prior is d products at most, the scaling by 1 - nug / (1 + nug)
+    three roundings, D s2 and the difference two: gamma_{n + d} on the absolute terms, u = float64's in both storage types:
+        C (n + d + 2) u64 (|X| |z|)_i + floor,      C (n + d + 2) u64 (|prior_i| + |D| |U_i|^2) + floor."""
+    dev = _dev(ghat, gvar, X, U, z)
+    xx, uu = _t(X, dev), _t(U, dev)
+    n = xx.shape[1]
+    zz = _t(z, dev)[:n]
+    d = np.asarray(mask).shape[1]
+    D = split_theta(th, d)[3]
+    pr = _t(marg_prior(i2.cpu() if isinstance(i2, torch.Tensor) else i2, mask, th), dev)
+    w = C * (n + d + 2.0) * unit("float64")
+    fl = floor("float64", n)
+    gref = xx @ zz
+    gb = w * (xx.abs() @ zz.abs()) + fl
+    u2 = (uu * uu).sum(dim=1)
+    vref = pr - D * u2
+    vb = w * (pr.abs() + abs(D) * u2) + fl
+    return combine(worst((_t(ghat, dev) - gref).abs(), gb), worst((_t(gvar, dev) - vref).abs(), vb))
+
+
+def check_marg_cond_cross(Sg, U0, Un, tabn, x0, mask, xn, th, kernel, dtype) -> Check:
+    """check_cond_cross for the box-averaged view: Sigma_0n (n0 x m) after OP_COND_CROSS against
+        Cbar^x(x0, xn) - D U_0 U_n^T
+    with Cbar^x the reference of check_marg_cross from the FETCHED table over xn (tabn: d x mpad doubles), no colscale and no
+    nugget, and the library's own U_0, U_n.  Bound as check_cond_cross with E' of the masked rows (E_kept + 4 + #masked):
+        C (npad + d + E') u (|Cbar^x| + |D| |U_0| |U_n|^T)  (+ |Cbar^x| past the cut-off) + floor, on all entries."""
+    dev = _dev(Sg, U0, Un)
+    d = np.asarray(mask).shape[1]
+    D = split_theta(th, d)[3]
+    cx, ew, cut = _marg_cross_ref(tabn, x0, mask, xn, None, th, kernel, dtype, dev)
+    u0, un = _t(U0, dev), _t(Un, dev)
+    k = _pad128(un.shape[1])
+    ref = cx - D * (u0 @ un.T)
+    bound = C * (k + d + ew) * unit(dtype) * (cx.abs() + abs(D) * (u0.abs() @ un.abs().T)) + floor(dtype, k)
+    bound = bound + torch.where(cut, cx.abs(), torch.zeros_like(cx))
+    return worst((_t(Sg, dev) - ref).abs(), bound, lower=False)
+
+
+def check_marg_refcov(gcov, U, T, ref, x0, mask, xr, mr, box, i2, th, kernel, dtype, n, m, ref_rows=None) -> Check:
+    """gcov (n0 doubles, one component) of marg_refcov_kernel against
+        gcov_i = prior(i, r) - D U_i . U_r - T_i . T_r,       [U_r | T_r] = ref (npad + mpad values; m = 0: no view, T ignored)
+    in float64 from the library's own U (n0 x >= n), T (n0 x >= m), the widened row ref and i2 (d doubles), the rounded x0, xr
+    (entries under their masks never read) and box (2 x d).  ref_rows = (U_r, T_r): the rows the widened row was copied from
+    (padded as stored; T_r None without a view) -- ref must equal them BITWISE (ratio inf at ("ref",) otherwise).
+    prior(i, r) = scale (1 - nt) prod_l f_l in ascending l: f_l = kappa(|x0_il - xr_l| / ell_l) where both rows keep l, the
+    mpmath I1 (marg_exact) at the kept value where exactly one integrates l, the FETCHED i2[l] where both do.
+    Counted from the source (double throughout): the two dot products are n and m fmas and the butterfly; D s1 and the two
+    differences three; the prior d products and the three roundings of scale (1 - nt):
+        C (n + m + d + 4) u64 (|prior| + |D| |U_i| . |U_r| + |T_i| . |T_r|)
+    plus the factors' own errors, relative to |prior|: a mixed dimension carries marg_table_bound / I1 (the same marg_I1, on
+    a query row's value); a kept-kept dimension the difference, the quotient, exp (MARG_ULP) and the polynomial (four), and the
+    argument through b |kappa'(b)| / kappa(b) (b^2 / (1 + b), b^2, b^2 (1 + b) / (3 + 3 b + b^2)) with three roundings of b:
+        C |prior| sum_l rel_l,     rel_l = u64 (MARG_ULP + 4 + 3 b |kappa'| / kappa)   or   marg_table_bound_l / I1_l.
+    Locations: (64-block of the row,)."""
+    _known(kernel)
+    dev = _dev(gcov, U, T, ref)
+    mask = np.asarray(mask) != 0
+    mr = np.asarray(mr).reshape(-1) != 0
+    n0, d = mask.shape
+    npad = _pad128(n)
+    rf = _t(ref, dev).reshape(-1)
+    if ref_rows is not None:
+        want = _t(ref_rows[0], dev).reshape(-1)[:npad]
+        if m > 0:
+            want = torch.cat([want, _t(ref_rows[1], dev).reshape(-1)[:_pad128(m)]])
+        if want.shape != rf.shape or bool((want.contiguous().view(torch.int64) != rf.contiguous().view(torch.int64)).any()):
+            return Check(math.inf, ("ref",))
+    ell, scale, nug, D, _ = split_theta(th, d)
+    u64 = unit("float64")
+    x0r = rounded(np.where(mask, 0.0, np.asarray(x0, np.float64)), dtype)
+    xrr = rounded(np.where(mr, 0.0, np.asarray(xr, np.float64).reshape(-1)), dtype)
+    ii = np.asarray(i2.cpu() if isinstance(i2, torch.Tensor) else i2, np.float64)
+    pr = np.full(n0, scale * (1.0 - nug / (1.0 + nug)))
+    rel = np.zeros(n0)
+    for l in range(d):
+        both = mask[:, l] & mr[l]
+        mixed = mask[:, l] ^ mr[l]
+        kept = ~mask[:, l] & ~mr[l]
+        f = np.ones(n0)
+        f[both] = ii[l]
+        if mixed.any():
+            xv = np.full(n0, xrr[l]) if not mr[l] else x0r[:, l]
+            i1 = marg_exact(kernel, xv[mixed], box[0][l], box[1][l], ell[l])
+            f[mixed] = np.array([float(v) for v in i1])
+            with np.errstate(divide="ignore", invalid="ignore"):
+                r = marg_table_bound(kernel, xv[mixed], box[0][l], box[1][l], ell[l]) / f[mixed]
+            rel[mixed] += np.where(np.isfinite(r), r, 0.0)
+        if kept.any():
+            b = np.abs(x0r[kept, l] - xrr[l]) / ell[l]
+            f[kept] = _kappa(kernel, b)
+            mag = b * b / (1.0 + b) if kernel == "matern32" else b * b if kernel == "se" \
+                else b * b * (1.0 + b) / (3.0 + 3.0 * b + b * b)
+            rel[kept] += u64 * (MARG_ULP + 4.0 + 3.0 * mag)
+        pr = pr * f
+    uu = _t(U, dev)[:, :n]
+    ur = rf[:n]
+    dots = uu @ ur
+    adots = uu.abs() @ ur.abs()
+    if m > 0:
+        tt, tr = _t(T, dev)[:, :m], rf[npad:npad + m]
+        tdot, atdot = tt @ tr, tt.abs() @ tr.abs()
+    else:
+        tdot = atdot = torch.zeros_like(dots)
+    prt = _t(pr, dev)
+    gref = prt - D * dots - tdot
+    bound = C * (n + m + d + 4.0) * u64 * (prt.abs() + abs(D) * adots + atdot) + C * prt.abs() * _t(rel, dev) \
+        + floor("float64", n + m)
+    return worst((_t(gcov, dev) - gref).abs(), bound)

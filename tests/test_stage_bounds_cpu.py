@@ -31,7 +31,17 @@ precisions, the full and the replicated path pass pdx, p, phess, gradcov and gra
 off-diagonal block pair, a block past d written into a valid slot, a transposed packed index, the tail of the vector loads left
 out of the Gram term, a stale 32-dimension chunk in DX, the Matern-3/2 psi or kappa under Matern-5/2, a float32 reciprocal, the D
 of another component, M overwritten or a dead wave weighted, and a float32-accurate P each fail the check they name and no other.
-One small off-diagonal Hessian entry off by 1e-3 relative, invisible to max|err| / max|ref|, fails check_phess."""
+One small off-diagonal Hessian entry off by 1e-3 relative, invisible to max|err| / max|ref|, fails check_phess.
+
+The box-averaged predictions (lcgp_predict_marginal, lcgp_condition_predict_marginal) are emulated from the float64 restatement
+tests/marginal_ref.py (the table), the masked rows, U, the outputs with the averaged prior, the view's stages and gcov: the three
+kernels, both precisions, full and rep, d = 3 and 34, the default box and a sub-box pass every check, at most 1 % of the table
+entries have a bound set by the absolute floor and the median ratio of the table stays above 1e-3.  The restatement itself -- which
+shares its series, switches and closed forms with the kernel -- meets the table bound against mpmath on a grid that sits on every
+switch.  A wrong Matern-5/2 coefficient, ten series terms, the near-branch formula (erf differences for SE) in the far tail, a
+padding column that is not 1, the table row of the next dimension or component, a stale table chunk, x0 read under the mask, a
+prior left at scale or with the nugget, I2 of the wrong dimension or T_i . T_r dropped in gcov and float32-accurate rows each fail
+their stage.  Small table entries or one far tile of masked rows off by 1e-9, invisible to the normwise 1e-10, fail theirs."""
 import numpy as np
 import pytest
 import torch
@@ -1751,3 +1761,454 @@ def test_second_order_gap_small_hessian_entry_is_invisible_normwise():
         assert nw < 1e-3 * LATENT_BAR
         c = sb.check_phess(bad["gh"], bad["gv"], *a, p["z"], p["Vp"], r["P"], "matern32", "float64")
         assert c.ratio > 1 and c.where == (i // TS, "%s l3 m1" % ("d2ghat" if name == "gh" else "d2gvar")), c
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# box-averaged predictions (lcgp_predict_marginal, lcgp_condition_predict_marginal): the table of 1-D averages (the restatement
+# tests/marginal_ref.py in float64: the same series, switches and closed forms as marg_table_kernel), the masked rows, U, the
+# outputs with the averaged prior, the view's stages (the table over xn, the masked rows against xn, Sigma_0n, T, the corrected
+# outputs) and gcov, emulated with q = 2 components whose lengthscales run from 0.02 to 30 within a row.  n = 130 (npad 256:
+# 126 padding columns of the table), n0 = 70, m = 70; d = 3 and d = 34 (two 32-dimension chunks of the masked cross_kernel).
+# The inputs are float32-representable so that both precisions share the mpmath values (stage_bounds caches them per value).
+# ----------------------------------------------------------------------------------------------------------------------
+from tests import marginal_ref as mref  # noqa: E402
+
+MG_N, MG_N0, MG_M, MG_Q = 130, 70, 70, 2
+MG_BOXES = {"default": (0.0, 1.0), "sub": (0.3, 0.75)}
+MG_STAGES = ("table", "cross", "u", "out", "table_n", "cross_n", "cond_cross", "cond_t", "cond_out", "gcov")
+MG_REF_ROWS = (0, 3, 4)                       # rows of _mg_rows with an empty, a full and a random mask: the reference rows of gcov
+_MG_CACHE = {}
+
+
+def _mg_rows(d, n0, seed, shift=0):
+    """x0 (NaN under the mask) and masks of the kinds tests/test_gpu_marginal.py::_rows makes: empty, one dimension, all but one,
+    all, random (never empty); with d > 32 the single / kept dimension walks over 30 .. 33 and the random masks straddle 31 / 32.
+    Row i is of kind (i + shift) % 5"""
+    rng = np.random.default_rng(seed)
+    x0 = np.asarray(rng.uniform(-0.1, 1.1, (n0, d)), np.float32).astype(np.float64)
+    mask = np.zeros((n0, d), bool)
+    edge = [l for l in (0, 30, 31, 32, 33, d - 1) if l < d]
+    for i in range(n0):
+        l = edge[(i // 5) % len(edge)]
+        kind = (i + shift) % 5
+        if kind == 1:
+            mask[i, l] = True
+        elif kind == 2:
+            mask[i] = True
+            mask[i, l] = False
+        elif kind == 3:
+            mask[i] = True
+        elif kind == 4:
+            mask[i] = rng.uniform(0, 1, d) < 0.5
+            if d > 32:
+                mask[i, 31], mask[i, 32] = True, False
+            if not mask[i].any() or (mask[i].all() and d > 1):
+                mask[i, d - 1], mask[i, 0] = False, True
+    x0[mask] = np.nan
+    return x0, mask
+
+
+def _mg_theta(d, kernel, k):
+    """theta row of component k: lengthscales from 0.02 (0.1 for SE at d > 3, whose C0 would otherwise be past its cut-off for
+    nearly every pair) to 30 within the row, 0.7 in between so that b straddles 1/2 and 1 at the box edges; the components
+    share the other lengthscales at d > 3 (the mpmath cache is keyed on them)"""
+    rng = np.random.default_rng(900 + d)
+    ell = np.sqrt(d) * rng.uniform(0.3, 0.9, d)
+    small = 0.02 if (kernel != "se" or d <= 3) else 0.1
+    if d <= 3:
+        ell = np.array([[small, 0.7, 30.0], [30.0, 0.3, small]][k][:d])
+    else:
+        ell[0], ell[1], ell[d // 2], ell[d - 1] = (small, 30.0, 0.7, 2.0) if k == 0 else (30.0, small, 0.7, 2.0)
+    rk = np.random.default_rng(910 + k)
+    return np.concatenate([ell, [(1.3, 0.7)[k], (0.01, 0.002)[k], (5.0, 12.0)[k]], rk.standard_normal(P)])
+
+
+def _mg_problem(dtype, kernel="matern32", rep=False, d=3, box="default", sort0=False):
+    key = (dtype, kernel, rep, d, box, sort0)
+    if key in _MG_CACHE:
+        return _MG_CACHE[key]
+    rng = np.random.default_rng(70 + d)
+    x = np.asarray(rng.uniform(0.0, 1.0, (MG_N, d)), np.float32).astype(np.float64)
+    if sort0:
+        x = x[np.argsort(x[:, 0])]
+    Y = rng.standard_normal((P, MG_N))
+    sr = np.sqrt(rng.integers(1, 6, MG_N).astype(np.float64)) if rep else None
+    xn = np.asarray(rng.uniform(-0.2, 1.2, (MG_M, d)), np.float32).astype(np.float64)       # inside and outside the box
+    r = (1.0 + np.arange(MG_M) % 3) if rep else None
+    x0, mask = _mg_rows(d, MG_N0, 71 + d)
+    for i, j in ((0, 5), (6, 64), (9, 69)):                    # rows of x0 equal to rows of xn where they keep the dimension
+        x0[i] = np.where(mask[i], np.nan, xn[j])
+    if sort0:
+        x0[:64, 0] = np.where(mask[:64, 0], np.nan, 0.5 * np.abs(np.nan_to_num(x0[:64, 0])) / 1.1)
+        x0 = np.where(mask, np.nan, np.asarray(np.nan_to_num(x0), np.float32).astype(np.float64))
+    t = rng.standard_normal((MG_Q, MG_M))
+    lo, hi = MG_BOXES[box]
+    bx = np.stack([np.full(d, lo), np.full(d, hi)])
+    ths = [_mg_theta(d, kernel, k) for k in range(MG_Q)]
+    fits = [_fit(x, Y, sr, th, dtype, kernel) for th in ths]
+    p = dict(x=x, sr=sr, xn=xn, r=r, x0=x0, mask=mask, t=t, th=ths, fit=fits, dtype=dtype, kernel=kernel, d=d, box=bx)
+    _MG_CACHE[key] = p
+    return p
+
+
+def _mg_table(p, k, x2, n2pad, i1=None, pad=1.0, shift=0):
+    """the table (d x n2pad doubles, padding 1.0) and i2 (d) of component k over the inputs x2 from the restatement.  Defects:
+    i1 (another I1), pad (the padding value), shift (row l holds the values of dimension l + shift)"""
+    d, th, kernel = p["d"], p["th"][k], p["kernel"]
+    x2r = _r(x2, p["dtype"])
+    f = mref.I1 if i1 is None else i1
+    tab = np.full((d, n2pad), pad)
+    for l in range(d):
+        ls = (l + shift) % d
+        tab[l, :x2r.shape[0]] = f(kernel, x2r[:, ls], p["box"][0][ls], p["box"][1][ls], th[ls])
+    i2 = np.array([float(mref.I2(kernel, p["box"][1][l] - p["box"][0][l], th[l])) for l in range(d)])
+    return tab, i2
+
+
+def _mg_X(p, k, tab, x2, cs, stale_chunk=False, read_masked=False):
+    """the masked rows of component k against x2 (float64 from the rounded inputs, rounded once to the storage type): kept
+    dimensions kappa(|x0 - x2| / ell), masked ones the table entry.  Defects: stale_chunk (the dimensions of the second
+    32-dimension chunk take the table rows of the first), read_masked (x0 is loaded under the mask)"""
+    d, th, kernel, dtype, mask = p["d"], p["th"][k], p["kernel"], p["dtype"], p["mask"]
+    ell, scale, nug, Dk, _ = sb.split_theta(th, d)
+    x2r = _r(x2, dtype)
+    n2 = x2r.shape[0]
+    x0r = _r(np.where(mask & (not read_masked), 0.0, p["x0"]), dtype)
+    s = np.ones(n2) if cs is None else _r(cs, dtype)
+    poly = np.ones((x0r.shape[0], n2))
+    for l in range(d):
+        ls = l - 32 if (stale_chunk and l >= 32) else l
+        kept = mref.kappa(kernel, np.abs(x0r[:, l][:, None] - x2r[:, l][None, :]) / ell[l])
+        use_tab = mask[:, l] & (not read_masked)
+        poly = poly * np.where(use_tab[:, None], tab[ls, :n2][None, :], kept)
+    return _r(scale * (1.0 - nug / (1.0 + nug)) * poly * s[None, :], dtype)
+
+
+def _mg_prior(p, k, i2, keep_scale=False, nugget=False):
+    d, th, mask = p["d"], p["th"][k], p["mask"]
+    ell, scale, nug, Dk, _ = sb.split_theta(th, d)
+    pr = np.full(mask.shape[0], scale if nugget else scale * (1.0 - nug / (1.0 + nug)))
+    for l in range(d):
+        pr = np.where(mask[:, l], pr * i2[l], pr)
+    return np.where(mask.any(axis=1) & (not keep_scale), pr, scale)
+
+
+def _mg_view(p, k):
+    """a valid state of the view for component k (U_n, the dense L_S^-1, v), as lcgp_condition_prepare leaves it; its own stages are
+    held by the conditioned-view tests above"""
+    import scipy.linalg as sla
+    dtype, kernel, th, f, d = p["dtype"], p["kernel"], p["th"][k], p["fit"][k], p["d"]
+    T = _np_t(dtype)
+    ell, scale, nug, Dk, _ = sb.split_theta(th, d)
+    nt = nug / (1 + nug)
+    m, mpad = MG_M, sb._pad128(MG_M)
+    Xn = _r(_cross(p["xn"], p["x"], p["sr"], th, dtype, kernel), dtype)
+    Un = np.asarray(_mm(Xn, f["W"], dtype), np.float64)
+    xr = _r(p["xn"], dtype)
+    cnn = scale * ((1 - nt) * sb.kernel_parts(xr, xr, ell, kernel, dtype)[0].numpy() + nt * np.eye(m))
+    S = _axpy(_r(cnn, dtype), -Dk, _mm(Un, Un, dtype), dtype)
+    rr = p["r"] if p["r"] is not None else np.ones(m)
+    S[np.arange(m), np.arange(m)] = _r(np.diag(S) + 1.0 / (Dk * rr), dtype)
+    L = np.linalg.cholesky(np.asarray(S, T))
+    Wn = np.asarray(np.tril(sla.solve_triangular(L, np.eye(m, dtype=T), lower=True)), np.float64)
+    Wd = np.eye(mpad)
+    Wd[:m, :m] = Wn
+    v = np.zeros(mpad)
+    v[:m] = Wn @ (p["t"][k] - Xn @ f["z"])
+    return dict(Un=Un, Wd=Wd, v=v)
+
+
+def _mg_gcov(p, k, e, r, wrong_i2=False, drop_t=False):
+    """gcov of every row against the reference row r of the same pass: the widened row [U_r | T_r] and the prior from the
+    restatement.  Defects: wrong_i2 (I2 of dimension l + 1 where both rows integrate l), drop_t (T_i . T_r left out)"""
+    d, th, kernel, dtype, mask = p["d"], p["th"][k], p["kernel"], p["dtype"], p["mask"]
+    ell, scale, nug, Dk, _ = sb.split_theta(th, d)
+    n, m, npad, mpad = MG_N, MG_M, sb._pad128(MG_N), sb._pad128(MG_M)
+    ref = np.zeros(npad + mpad)
+    ref[:n] = e["U"][r]
+    ref[npad:npad + mpad] = e["Tm"][r]
+    x0r = _r(np.where(mask, 0.0, p["x0"]), dtype)
+    xr, mr = x0r[r], mask[r]
+    pr = np.full(mask.shape[0], scale * (1.0 - nug / (1.0 + nug)))
+    for l in range(d):
+        lo, hi = p["box"][0][l], p["box"][1][l]
+        kept = mref.kappa(kernel, np.abs(x0r[:, l] - xr[l]) / ell[l])
+        if mr[l]:
+            f = np.where(mask[:, l], e["i2"][(l + 1) % d if wrong_i2 else l], mref.I1(kernel, x0r[:, l], lo, hi, ell[l]))
+        else:
+            f = np.where(mask[:, l], float(mref.I1(kernel, xr[l], lo, hi, ell[l])), kept)
+        pr = pr * f
+    g = pr - Dk * (e["U"] @ e["U"][r])
+    if not drop_t:
+        g = g - e["Tm"][:, :m] @ e["Tm"][r, :m]
+    return dict(ref=ref, xr=p["x0"][r], mr=mr, gcov=g)
+
+
+def _mg_emulate(p, k, table=None, cross=None, prior=None, tab_of=None, as32=False):
+    """every stage of component k.  Defects: table / cross / prior (keywords of _mg_table / _mg_X / _mg_prior), tab_of (the masked
+    rows read the table of that component), as32 (X carries float32 accuracy)"""
+    dtype, th, f, d = p["dtype"], p["th"][k], p["fit"][k], p["d"]
+    Dk = sb.split_theta(th, d)[3]
+    n0, n, m = MG_N0, MG_N, MG_M
+    npad, mpad, n0pad = sb._pad128(n), sb._pad128(m), sb.predict_pad(n0)
+    tab, i2 = _mg_table(p, k, p["x"], npad, **(table or {}))
+    rd = tab if tab_of is None else _mg_table(p, tab_of, p["x"], npad)[0]
+    X = _mg_X(p, k, rd, p["x"], p["sr"], **(cross or {}))
+    if as32:
+        X = _r(X, "float32")
+    U = np.asarray(_mm(X, f["W"], dtype), np.float64)
+    pr = _mg_prior(p, k, i2, **(prior or {}))
+    gh, gv = X @ f["z"], pr - Dk * np.sum(U * U, axis=1)
+    v = _mg_view(p, k)
+    tabn, _ = _mg_table(p, k, p["xn"], mpad)
+    Cn = _mg_X(p, k, tabn, p["xn"], None, **(cross or {}))
+    Sg = np.zeros((n0pad, mpad))
+    Sg[:n0, :m] = _axpy(Cn, -Dk, _mm(U, v["Un"], dtype), dtype)
+    Tm = np.asarray(_mm(Sg, v["Wd"], dtype), np.float64)[:n0]
+    gh1 = gh + Tm[:, :m] @ v["v"][:m]
+    gv1 = gv - np.sum(Tm[:, :m] ** 2, axis=1)
+    return dict(tab=tab, i2=i2, X=X, U=U, gh=gh, gv=gv, tabn=tabn, Cn=Cn, Sg=Sg[:n0, :m], Tm=Tm, gh1=gh1, gv1=gv1, **v)
+
+
+def _mg_checks(p, k, e, gc=None, r=MG_REF_ROWS[2], stages=MG_STAGES):
+    dtype, kernel, th, f, d = p["dtype"], p["kernel"], p["th"][k], p["fit"][k], p["d"]
+    x, sr, xn, x0, mask, box = p["x"], p["sr"], p["xn"], p["x0"], p["mask"], p["box"]
+    n, m, npad, mpad = MG_N, MG_M, sb._pad128(MG_N), sb._pad128(MG_M)
+    out = {}
+    for st in stages:
+        if st == "table":
+            out[st] = sb.check_marg_table(e["tab"][None], e["i2"][None], x, th[None], box, kernel, dtype, n, npad)
+        elif st == "cross":
+            out[st] = sb.check_marg_cross(e["X"], e["tab"], x0, mask, x, sr, th, kernel, dtype)
+        elif st == "u":
+            out[st] = sb.check_cov_u(e["U"], e["X"], f["W"], dtype)
+        elif st == "out":
+            out[st] = sb.check_marg_out(e["gh"], e["gv"], e["X"], e["U"], f["z"], e["i2"], mask, th, dtype)
+        elif st == "table_n":
+            out[st] = sb.check_marg_table(e["tabn"][None], e["i2"][None], xn, th[None], box, kernel, dtype, m, mpad)
+        elif st == "cross_n":
+            out[st] = sb.check_marg_cross(e["Cn"], e["tabn"], x0, mask, xn, None, th, kernel, dtype)
+        elif st == "cond_cross":
+            out[st] = sb.check_marg_cond_cross(e["Sg"], e["U"], e["Un"], e["tabn"], x0, mask, xn, th, kernel, dtype)
+        elif st == "cond_t":
+            out[st] = sb.check_cov_u(e["Tm"][:, :m], e["Sg"], e["Wd"][:m, :m], dtype)
+        elif st == "cond_out":
+            out[st] = sb.check_cond_out(e["gh1"], e["gv1"], e["Tm"], e["v"], e["gh"], e["gv"], m)
+        elif st == "gcov":
+            g = _mg_gcov(p, k, e, r) if gc is None else gc
+            out[st] = sb.check_marg_refcov(g["gcov"], e["U"], e["Tm"], g["ref"], x0, mask, g["xr"], g["mr"], box, e["i2"], th,
+                                           kernel, dtype, n, m, ref_rows=(np.pad(e["U"][r], (0, npad - n)), e["Tm"][r]))
+    return out
+
+
+def _mg_only(checks, *failing):
+    first = min(MG_STAGES.index(f) for f in failing)
+    for stage in MG_STAGES[:first]:
+        if stage in checks:
+            assert checks[stage].ratio <= 1.0, ("upstream", stage, checks[stage])
+    for stage in failing:
+        assert checks[stage].ratio > 1.0, (stage, checks[stage])
+
+
+def _mg_table_ratios(p, k, e):
+    """every ratio of the table entries of component k (n d values)"""
+    xr = _r(p["x"], p["dtype"])
+    return np.concatenate([sb.marg_table_ratios(p["kernel"], e["tab"][l, :MG_N], xr[:, l], p["box"][0][l], p["box"][1][l], p["th"][k][l])
+                           for l in range(p["d"])])
+
+
+@pytest.mark.parametrize("d,box", [(3, "default"), (3, "sub"), (34, "default"), (34, "sub")])
+@pytest.mark.parametrize("rep", [False, True], ids=["full", "rep"])
+@pytest.mark.parametrize("kernel", KERNELS)
+@pytest.mark.parametrize("dtype", ["float64", "float32"])
+def test_emulated_marginal_path_passes_every_stage(dtype, kernel, rep, d, box):
+    """every stage at or below 1, with every kind of reference row for gcov; and the two conditions that keep the table bound
+    honest: at most 1 % of its entries have a bound set by the absolute floor, and the median ratio of the emulation is above
+    1e-3 (the bound is within three orders of what correct code does)"""
+    p = _mg_problem(dtype, kernel, rep, d, box)
+    for k in range(MG_Q):
+        e = _mg_emulate(p, k)
+        checks = _mg_checks(p, k, e)
+        for r in MG_REF_ROWS[:2]:
+            checks["gcov r%d" % r] = _mg_checks(p, k, e, r=r, stages=("gcov",))["gcov"]
+        med = float(np.median(_mg_table_ratios(p, k, e)))
+        fl = sb.marg_floor_fraction(p["x"], p["th"][k], p["box"], kernel, dtype)
+        print("marginal, emulated, %s %s %s d=%d %s k%d: %s  table median %.2e floor fraction %.4f"
+              % (dtype, kernel, "rep" if rep else "full", d, box, k, "  ".join("%s %.2e" % (s, c.ratio) for s, c in checks.items()),
+                 med, fl))
+        for stage, c in checks.items():
+            assert c.ratio <= 1.0, (k, stage, c)
+        assert med > 1e-3, (k, med)
+        assert fl <= 0.01, (k, fl)
+
+
+# the restatement against mpmath, on every switch: b = 1/2 and bn = 1 with their float64 neighbours, x on lo, on hi and one ulp
+# either side, w / ell from 1e-4 to 50, ell from 0.02 to 30.  With lo = 0 the difference x - lo is exact and b = x / ell sits on the
+# switch (ell = 1: exactly, with both neighbours); with lo = 0.25 it is rounded first.  The neighbours are taken in x and b is
+# recomputed from x as the library does
+MG_GRID_ELL = (0.02, 0.3, 1.0, 7.0, 30.0)
+MG_GRID_WL = (1e-4, 1e-3, 1e-2, 0.1, 0.5, 1.0, 3.0, 50.0)
+
+
+def _mg_grid(ell, w, lo):
+    hi = lo + w
+    xs = []
+    for b in (0.0, 1e-9, 1e-3, 0.1, 0.25, 0.5, 0.75, 1.0, 1.5, 3.0, 8.0, 20.0, 40.0):
+        for base in (lo - b * ell, hi + b * ell, lo + b * ell, hi - b * ell):
+            xs += [np.nextafter(base, -np.inf), base, np.nextafter(base, np.inf)]
+    for base in (lo, hi):
+        xs += [np.nextafter(base, -np.inf), base, np.nextafter(base, np.inf)]
+    return lo, hi, np.unique(np.asarray(xs, np.float64))
+
+
+@pytest.mark.parametrize("kernel", KERNELS)
+def test_marginal_restatement_meets_the_table_bound_against_mpmath(kernel):
+    """tests/marginal_ref.py's I1 (through its F and Fc in all three branches) and I2 (F and G) against marg_exact / marg_exact2
+    within the bound of check_marg_table: the structure the restatement shares with the kernel is itself held to an
+    independent reference.  The worst relative error per class is printed (the narrow-box loss ~ u ell / w among them)"""
+    worst, relw = 0.0, {}
+    for ell in MG_GRID_ELL:
+        for wl, lo0 in [(w_, l_) for w_ in MG_GRID_WL for l_ in (0.0, 0.25)]:
+            lo, hi, xs = _mg_grid(ell, wl * ell, lo0)
+            got = mref.I1(kernel, xs, lo, hi, ell)
+            r = sb.marg_table_ratios(kernel, got, xs, lo, hi, ell)
+            assert np.all(r <= 1.0), (kernel, ell, wl, float(r.max()), float(xs[int(np.argmax(r))]))
+            worst = max(worst, float(r.max()))
+            ex = np.array([float(v) for v in sb.marg_exact(kernel, xs, lo, hi, ell)])
+            ok = ex > 1e-300
+            relw[wl] = max(relw.get(wl, 0.0), float(np.max(np.abs(got[ok] - ex[ok]) / ex[ok])) / sb.unit("float64"))
+            i2 = float(mref.I2(kernel, hi - lo, ell))
+            with sb.mp.workdps(60):
+                e2 = float(abs(sb.mp.mpf(i2) - sb.marg_exact2(kernel, sb.mp.mpf(hi) - sb.mp.mpf(lo), ell)))
+            r2 = e2 / (sb.C * sb.marg_i2_bound(kernel, hi - lo, ell) + sb.floor("float64", 1))
+            assert r2 <= 1.0, (kernel, ell, wl, r2)
+            for which in ("F", "G", "Fc"):
+                for b in (np.nextafter(0.5, 0), 0.5, np.nextafter(0.5, 1), np.nextafter(1.0, 0), 1.0, np.nextafter(1.0, 2), wl):
+                    g = float(getattr(mref, which)(kernel, b))
+                    with sb.mp.workdps(60):
+                        eb = float(abs(sb.mp.mpf(g) - sb._marg_mp(kernel, which, sb.mp.mpf(float(b)))))
+                    assert eb <= sb.C * sb.unit("float64") * float(sb._marg_terms(kernel, which, b)), (kernel, which, b, eb)
+    print("restatement against mpmath, %s: worst ratio %.3f; worst relative error of I1 in u per w / ell: %s"
+          % (kernel, worst, "  ".join("%g: %.3g" % kv for kv in sorted(relw.items()))))
+
+
+def _i1_variant(near_always=False, erf_tail=False):
+    """I1 of the restatement with a wrong branch: the near-branch formula F(bf) - F(bn) also beyond bn = 1"""
+    def i1(kernel, x, lo, hi, ell):
+        x, lo, hi, ell = np.broadcast_arrays(*(np.asarray(v, np.float64) for v in (x, lo, hi, ell)))
+        a1, a2 = x - lo, hi - x
+        b1, b2 = np.abs(a1) / ell, np.abs(a2) / ell
+        inside = (a1 >= 0.0) & (a2 >= 0.0)
+        bn, bf = np.minimum(b1, b2), np.maximum(b1, b2)
+        r = np.where(inside, mref.F(kernel, b1) + mref.F(kernel, b2), mref.F(kernel, bf) - mref.F(kernel, bn))
+        return ell / (hi - lo) * r
+    return i1
+
+
+def test_marginal_defects_of_the_table(monkeypatch):
+    """a wrong Matern-5/2 coefficient in F; 10 series terms at b just below 1/2; the near-branch formula far out in the tail
+    (Matern) and erf differences in place of erfc (SE: the same mistake in its kernel); a padding column that is not 1; the row
+    of the next dimension.  Each fails check_marg_table, and the untouched table passes"""
+    # (1) 8/3 -> 8/3 (1 + 1e-12) in the closed form of F
+    p = _mg_problem("float64", "matern52", False, 3, "default")
+    good = _mg_emulate(p, 0)
+    assert _mg_checks(p, 0, good, stages=("table",))["table"].ratio <= 1.0
+    closed = mref._closed
+
+    def wrong_closed(kernel, b):
+        f, g = closed(kernel, b)
+        return f + (8.0 / 3.0) * 1e-12 * -np.expm1(-b), g
+    monkeypatch.setattr(mref, "_closed", wrong_closed)
+    _mg_only(_mg_checks(p, 0, _mg_emulate(p, 0), stages=("table",)), "table")
+    monkeypatch.setattr(mref, "_closed", closed)
+    # (2) ten terms of the series: seen on the grid, at the first b below 1/2
+    for kernel in ("matern32", "matern52"):
+        lo, hi, ell = 0.0, 1.0, 1.0
+        xs = np.array([np.nextafter(0.5, 0), 0.49])
+        monkeypatch.setattr(mref, "SERIES_TERMS", 10)
+        bad = mref.I1(kernel, xs, lo, hi, ell)
+        monkeypatch.setattr(mref, "SERIES_TERMS", 20)
+        assert np.all(sb.marg_table_ratios(kernel, bad, xs, lo, hi, ell) > 1.0)
+        assert np.all(sb.marg_table_ratios(kernel, mref.I1(kernel, xs, lo, hi, ell), xs, lo, hi, ell) <= 1.0)
+    # (3), (4) the near-branch formula beyond bn = 1, in the sub-box problem whose inputs lie up to 15 lengthscales outside
+    for kernel in KERNELS:
+        p = _mg_problem("float64", kernel, False, 3, "sub")
+        c = _mg_checks(p, 0, _mg_emulate(p, 0, table=dict(i1=_i1_variant())), stages=("table",))["table"]
+        assert c.ratio > 1.0 and c.where[1] == 0, (kernel, c)                  # (dimension 0: ell = 0.02)
+    # (5) the padding, (6) the next dimension's row
+    p = _mg_problem("float32", "matern32", True, 3, "sub")
+    for defect in (dict(pad=0.0), dict(pad=np.nextafter(1.0, 2.0)), dict(pad=np.nan), dict(shift=1)):
+        _mg_only(_mg_checks(p, 1, _mg_emulate(p, 1, table=defect), stages=("table",)), "table")
+
+
+@pytest.mark.parametrize("dtype", ["float64", "float32"])
+def test_marginal_defects_of_the_masked_rows_and_outputs(dtype):
+    """the table of the next component read; the second 32-dimension chunk staged with the first chunk's table rows; x0 read under
+    the mask (NaN there); the prior of a masked row left at scale; the nugget kept in the prior; I2 of the wrong dimension and
+    T_i . T_r dropped in gcov: each fails its own stage and nothing upstream"""
+    front = ("table", "cross", "u", "out")
+    p = _mg_problem(dtype, "matern52", True, 3, "sub")
+    _mg_only(_mg_checks(p, 0, _mg_emulate(p, 0, tab_of=1), stages=front), "cross")
+    p34 = _mg_problem(dtype, "matern32", False, 34, "default")
+    c = _mg_checks(p34, 0, _mg_emulate(p34, 0, cross=dict(stale_chunk=True)), stages=front + ("table_n", "cross_n"))
+    _mg_only(c, "cross", "cross_n")
+    for q in (p, p34):
+        c = _mg_checks(q, 1, _mg_emulate(q, 1, cross=dict(read_masked=True)), stages=("table", "cross"))
+        _mg_only(c, "cross")
+        assert c["cross"].ratio == np.inf
+    _mg_only(_mg_checks(p, 0, _mg_emulate(p, 0, prior=dict(keep_scale=True)), stages=front), "out")
+    _mg_only(_mg_checks(p, 0, _mg_emulate(p, 0, prior=dict(nugget=True)), stages=front), "out")
+    e = _mg_emulate(p, 0)
+    for r in (MG_REF_ROWS[1], MG_REF_ROWS[2]):
+        for defect in (dict(wrong_i2=True), dict(drop_t=True)):
+            assert _mg_checks(p, 0, e, r=r, stages=("gcov",))["gcov"].ratio <= 1.0
+            c = _mg_checks(p, 0, e, gc=_mg_gcov(p, 0, e, r, **defect), r=r, stages=("gcov",))["gcov"]
+            assert c.ratio > 1.0, (r, defect, c)
+    g = _mg_gcov(p, 0, e, 4)
+    g["ref"] = g["ref"].copy()
+    g["ref"][1] = np.nextafter(g["ref"][1], 1.0)
+    assert _mg_checks(p, 0, e, gc=g, r=4, stages=("gcov",))["gcov"] == sb.Check(np.inf, ("ref",))
+
+
+def test_marginal_defect_float32_rows_in_the_float64_check():
+    p = _mg_problem("float64", "se", False, 3, "default")
+    _mg_only(_mg_checks(p, 0, _mg_emulate(p, 0, as32=True), stages=("table", "cross")), "cross")
+
+
+def test_marginal_gap_small_table_entries_and_a_far_tile_are_invisible_normwise():
+    """what the stage bounds close.  (a) the table entries of the inputs far outside the sub-box (below 1e-3 of the row's largest)
+    off by 1e-9 relative; (b) one 64-tile of the masked rows, whose entries are small, off by 1e-9 relative.  Both leave ghat and
+    gvar within the 1e-10 of max|err| / max|ref| that tests/test_gpu_marginal.py holds them to -- computed here -- and both fail
+    their stage check.  The training inputs are sorted along dimension 0 (lengthscale 0.02) and rows 0 .. 63 of x0 keep to its
+    lower half where they keep it, so the last column tile is far from the first row tile"""
+    p = _mg_problem("float64", "matern32", False, 3, "sub", sort0=True)
+    k = 0
+    e = _mg_emulate(p, k)
+    assert all(c.ratio <= 1.0 for c in _mg_checks(p, k, e, stages=("table", "cross", "u", "out")).values())
+    f, Dk = p["fit"][k], p["th"][k][p["d"] + 2]
+
+    def outputs(X):
+        U = np.asarray(_mm(X, f["W"], "float64"), np.float64)
+        return X @ f["z"], _mg_prior(p, k, e["i2"]) - Dk * np.sum(U * U, axis=1)
+    # (a)
+    tab = e["tab"].copy()
+    small = tab[0, :MG_N] < 1e-3 * tab[0, :MG_N].max()
+    assert 10 <= small.sum() < MG_N
+    tab[0, :MG_N][small] *= 1 + 1e-9
+    gh, gv = outputs(_mg_X(p, k, tab, p["x"], p["sr"]))
+    eh, ev = _normwise(gh, e["gh"]), _normwise(gv, e["gv"])
+    print("gap (a): end-to-end change ghat %.3e gvar %.3e (bar 1e-10)" % (eh, ev))
+    assert eh < 1e-10 and ev < 1e-10
+    c = sb.check_marg_table(tab[None], e["i2"][None], p["x"], p["th"][k][None], p["box"], "matern32", "float64", MG_N, 256)
+    assert c.ratio > 1.0 and c.where[:2] == (0, 0), c
+    # (b)
+    rows, cols = _tile(0, (MG_N - 1) // TS)
+    X = e["X"].copy()
+    assert np.abs(X[rows, cols]).max() < 1e-2 * np.abs(X).max() and np.abs(X[rows, cols]).max() > 0
+    X[rows, cols] *= 1 + 1e-9
+    gh, gv = outputs(X)
+    eh, ev = _normwise(gh, e["gh"]), _normwise(gv, e["gv"])
+    print("gap (b): end-to-end change ghat %.3e gvar %.3e (bar 1e-10)" % (eh, ev))
+    assert eh < 1e-10 and ev < 1e-10
+    c = sb.check_marg_cross(X, e["tab"], p["x0"], p["mask"], p["x"], p["sr"], p["th"][k], "matern32", "float64")
+    assert c.ratio > 1.0 and c.where == (0, (MG_N - 1) // TS), c

@@ -954,6 +954,32 @@ int lcgp_calib_hess_rows(void* stream, int q, int d, int n0,
                          double* ll /* n0 */, double* dll /* n0 x d or NULL */, double* d2ll /* n0 x tri or NULL */,
                          double* sens /* 2 x q x n0 (s then v) or NULL */, double* Bout /* n0 x q x q or NULL */);
 
+/* Pair sums behind the closed-form Sobol indices of the posterior mean surface.  Component k's surface is
+ *     ghat_k(t) = sum_i w[k, i] prod_l kappa(|t_l - x[i, l]| / ell[k, l])
+ * (w = scale (1 - nt) sr o z, what the box-averaged prediction multiplies its rows by).  With, per input dimension l,
+ *     a_l[i]     = (1 / w_l) int_box kappa(|t - x_il| / ell_kl) dt                                    (component k;  a'_l: k')
+ *     J_l[i, i'] = (1 / w_l) int_box kappa(|t - x_il| / ell_kl) kappa(|t - x_i'l| / ell_k'l) dt
+ *     M_u[i, i'] = prod_{l in u} J_l[i, i'] prod_{l not in u} a_l[i] a'_l[i']                         (M_0: u empty)
+ * row r of `out` holds, for the pair (k, k') = (pairs[2 r], pairs[2 r + 1]),
+ *     D_u = sum_{i, i'} w[k, i] w[k', i'] (M_u - M_0)[i, i']
+ * for u = {l} in columns l = 0 .. d - 1 (first-order), u = all but l in columns d .. 2 d - 1, u = all inputs in column 2 d: the
+ * covariance over the box, under the uniform measure, of the conditional means of ghat_k and ghat_k' given the inputs in u.
+ * Column 2 d + 1: the box mean sum_i w[k, i] prod_l a_l[i] of component k in the rows with k = k', 0 elsewhere.
+ * The difference M_u - M_0 is taken per element; no subset product is formed by a division.  J for two different length scales
+ * comes without a division by their difference (the recipe is in DESIGN.md 4.22 and above sobol_moments in the source).
+ * Always float64; the factorisation workspace is not touched.  x, w, ell, box, scratch and out are device pointers, pairs is a
+ * HOST array.  Three launches per batch of 64 pairs (the table of the a_l and the means once per call): 64 x 64 tiles of the
+ * (i, i') plane, a pair k = k' over the lower tiles only; the tile sums go through the scratch and are added in a fixed order:
+ * no atomics, two calls agree bit for bit and nothing depends on the scratch content on entry.  d <= 16: d pair integrals per
+ * element; beyond: d^2.
+ * scratch: lcgp_sobol_scratch_bytes(n, d, q_all, npairs) = 8 (q_all d n + q_all + min(npairs, 64) ceil(n / 64)^2 (2 d + 1)). */
+int lcgp_sobol_scratch_bytes(int n, int d, int q_all, int npairs, size_t* bytes /*host out*/);
+int lcgp_sobol_pairs(void* stream, int kernel_id, int n, int d, int q_all,
+                     const double* x /* n x d, standardised */, const double* w /* q_all x n */,
+                     const double* ell /* q_all x d */, const double* box /* lo[d], hi[d] */,
+                     const int* pairs /* npairs x 2, host */, int npairs, void* scratch,
+                     double* out /* npairs x (2 d + 2) */);
+
 #ifdef __cplusplus
 }
 #endif

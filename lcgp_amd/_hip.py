@@ -132,6 +132,8 @@ SIGNATURES = {
     "lcgp_calib_rows": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _d, _d, _vp, _vp, _vp, _vp]),
     "lcgp_calib_hess_rows": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _d, _d, _vp, _vp, _vp, _vp, _vp,
                                   _vp]),
+    "lcgp_sobol_scratch_bytes": (_i, [_i, _i, _i, _i, C.POINTER(C.c_size_t)]),
+    "lcgp_sobol_pairs": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, C.POINTER(_i), _i, _vp, _vp]),
 }
 
 _lib = None

@@ -7171,6 +7171,361 @@ int launch_calib_small(hipStream_t st, int d, int n0, const double* ghat, const 
     return 0;
 }
 
+// ---------------------------------------------------------------------------------------------------
+// Sobol indices of the posterior mean surface in closed form (lcgp_sobol_pairs).  For two components k, k' with
+// weight vectors w, w' and one input dimension l, besides the box average a_l[i] of the 1-D factor (marg_I1) the PAIR average
+//   J_l[i, i'] = (1 / w_l) int_box kappa(|t - x_il| / ell_kl) kappa(|t - x_i'l| / ell_k'l) dt
+// of two factors with different centres and length scales.  SE: the product of two Gaussians is a Gaussian (erf / erfc as in
+// marg_I1).  Matern: kappa(s) = P(s) e^-s; the centres are ordered (u <= v), the box split at those inside it into (at most)
+// three segments, and on a segment neither t - u nor t - v changes sign, so the integrand is a polynomial times e^(c t).  Each
+// segment is anchored at the end where the exponent is largest (t = t0 +- tau) and integrated as
+//   e^(-s0a - s0b) sum_n q_n m_n(|c|, L),     m_n(g, L) = int_0^L tau^n e^(-g tau) dtau,
+// s0a, s0b the scaled distances at the anchor, q the product of the two polynomials P(s0 +- tau / ell) in powers of tau.  On
+// the middle segment g = |1 / a - 1 / b|, which is 0 for equal length scales (every pair k = k'): m_n never divides by g where
+// g L is small.  Below g L = 4 the TOP moment comes from the all-positive series
+//   m_N = e^(-g L) L^(N + 1) / (N + 1) (1 + x / (N + 2) (1 + x / (N + 3) (1 + ...))),   x = g L,   30 terms (the first one left
+// out is below 1e-18 of the sum), the lower ones from the backward recurrence m_(n-1) = (g m_n + L^n e^(-g L)) / n (all
+// positive as well, exact at g = 0); from 4 on m_0 = -expm1(-g L) / g and the forward recurrence m_n = (n m_(n-1) - L^n
+// e^(-g L)) / g, whose error amplification n / (g L) stays below 1 there (n <= 4).
+// ---------------------------------------------------------------------------------------------------
+constexpr double SOBOL_SERIES_BELOW = 4.0;
+constexpr int SOBOL_SERIES_TERMS = 30;
+constexpr int SOBOL_BATCH = 64;               // pairs per launch (their component indices travel as kernel arguments)
+
+struct SobolPairs { int k[SOBOL_BATCH], kp[SOBOL_BATCH]; };
+
+// what one input dimension contributes to every J of a pair: the box and per kernel the constants of the two length scales
+//   Matern: c0 = 1 / a, c1 = 1 / b.   SE (s2 = a^2 + b^2): c0 = -1 / (2 s2), c1 = sigma = a b / sqrt(s2), c2 = 1 / sigma,
+//   c3 = b^2 / s2, c4 = a^2 / s2 (the centre of the product is c3 u + c4 v)
+struct SobolDim { double lo, hi, rw, c0, c1, c2, c3, c4; };
+
+template <int KERN>
+__device__ __forceinline__ SobolDim sobol_dim(double a, double b, double lo, double hi) {
+    static_assert(kern_known<KERN>::value, "unknown covariance kernel id");
+    SobolDim c;
+    c.lo = lo; c.hi = hi; c.rw = 1.0 / (hi - lo);
+    if constexpr (KERN == 1) {
+        const double s2 = a * a + b * b;
+        c.c0 = -0.5 / s2;
+        c.c1 = a * b / sqrt(s2);
+        c.c2 = 1.0 / c.c1;
+        c.c3 = b * b / s2;
+        c.c4 = a * a / s2;
+    } else {
+        c.c0 = 1.0 / a; c.c1 = 1.0 / b; c.c2 = c.c3 = c.c4 = 0.0;
+    }
+    return c;
+}
+
+// m[n] = int_0^L tau^n e^(-g tau) dtau, n = 0 .. NT (g >= 0, L >= 0)
+template <int NT>
+__device__ __forceinline__ void sobol_moments(double g, double L, double (&m)[NT + 1]) {
+    const double x = g * L;
+    const double eL = exp(-x);
+    double Ln[NT + 2];                                     // L^n
+    Ln[0] = 1.0;
+#pragma unroll
+    for (int n = 1; n <= NT + 1; ++n) Ln[n] = Ln[n - 1] * L;
+    if (x < SOBOL_SERIES_BELOW) {
+        double s = 1.0;
+#pragma unroll
+        for (int j = SOBOL_SERIES_TERMS; j >= 1; --j) s = fma(s * x, 1.0 / (NT + 1 + j), 1.0);
+        m[NT] = eL * Ln[NT + 1] * s * (1.0 / (NT + 1));
+#pragma unroll
+        for (int n = NT; n >= 1; --n) m[n - 1] = fma(g, m[n], Ln[n] * eL) * (1.0 / n);
+    } else {
+        const double rg = fast_rcp(g);
+        m[0] = -expm1(-x) * rg;
+#pragma unroll
+        for (int n = 1; n <= NT; ++n) m[n] = fma((double)n, m[n - 1], -Ln[n] * eL) * rg;
+    }
+}
+
+// one segment of length L: e^(-s0a - s0b) sum_n q_n m_n(al + be, L), with P(s0a + al tau) P(s0b + be tau) = sum_n q_n tau^n
+template <int KERN>
+__device__ __forceinline__ double sobol_segment(double L, double s0a, double s0b, double al, double be) {
+    constexpr int NT = KERN == 0 ? 2 : 4;
+    double m[NT + 1];
+    sobol_moments<NT>(al + be, L, m);
+    double sum;
+    if constexpr (KERN == 0) {
+        const double a0 = 1.0 + s0a, b0 = 1.0 + s0b;
+        sum = a0 * b0 * m[0] + fma(a0, be, al * b0) * m[1] + al * be * m[2];
+    } else {
+        const double a0 = 1.0 + fma(s0a * (1.0 / 3.0), s0a, s0a), a1 = al * fma(s0a, 2.0 / 3.0, 1.0), a2 = al * al * (1.0 / 3.0);
+        const double b0 = 1.0 + fma(s0b * (1.0 / 3.0), s0b, s0b), b1 = be * fma(s0b, 2.0 / 3.0, 1.0), b2 = be * be * (1.0 / 3.0);
+        sum = a0 * b0 * m[0] + fma(a0, b1, a1 * b0) * m[1] + (fma(a0, b2, a2 * b0) + a1 * b1) * m[2] + fma(a1, b2, a2 * b1) * m[3] +
+              a2 * b2 * m[4];
+    }
+    return exp(-(s0a + s0b)) * sum;
+}
+
+// J = (1 / w) int_lo^hi kappa(|t - u| / a) kappa(|t - v| / b) dt
+template <int KERN>
+__device__ __forceinline__ double sobol_J(double u, double v, const SobolDim& c) {
+    if constexpr (KERN == 1) {
+        const double df = u - v;
+        const double pref = exp(c.c0 * df * df);
+        const double mu = fma(c.c3, u, c.c4 * v);
+        const double z1 = (mu - c.lo) * c.c2, z2 = (c.hi - mu) * c.c2;
+        const double b1 = fabs(z1), b2 = fabs(z2);
+        double r;
+        if (z1 >= 0.0 && z2 >= 0.0) {
+            r = marg_F<1>(b1) + marg_F<1>(b2);
+        } else {
+            const double bn = fmin(b1, b2), bf = fmax(b1, b2);
+            r = bn > 1.0 ? marg_Fc<1>(bn) - marg_Fc<1>(bf) : marg_F<1>(bf) - marg_F<1>(bn);
+        }
+        return pref * c.c1 * r * c.rw;
+    } else {
+        double ra = c.c0, rb = c.c1;
+        if (u > v) {
+            const double t = u; u = v; v = t;
+            ra = c.c1; rb = c.c0;
+        }
+        const double cu = fmin(fmax(u, c.lo), c.hi), cv = fmin(fmax(v, c.lo), c.hi);
+        // (a centre outside the box leaves segments of length 0: their moments are 0, and the distances below are taken as
+        // absolute values so that the factor in front stays finite)
+        // left of both centres: anchored at its right end, both distances grow with tau
+        double tot = sobol_segment<KERN>(cu - c.lo, fabs(u - cu) * ra, fabs(v - cu) * rb, ra, rb);
+        // between the centres: anchored at the end with the larger exponent, the centre with the shorter length scale
+        if (rb <= ra) tot += sobol_segment<KERN>(cv - cu, fabs(cu - u) * ra, fabs(v - cu) * rb, ra, -rb);
+        else tot += sobol_segment<KERN>(cv - cu, fabs(cv - u) * ra, fabs(v - cv) * rb, -ra, rb);
+        // right of both: anchored at its left end
+        tot += sobol_segment<KERN>(c.hi - cv, fabs(cv - u) * ra, fabs(cv - v) * rb, ra, rb);
+        return tot * c.rw;
+    }
+}
+
+__device__ __forceinline__ double sobol_wave_sum(double v) {          // lane 0 holds the sum; a fixed order
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v += __shfl_down(v, o, 64);
+    return v;
+}
+
+// launch 1: tab[k, l, i] = the box average of the 1-D factor of component k at training input i (marg_I1), and the box mean
+// means[k] = sum_i w_ki prod_l tab[k, l, i] of the component's surface, reduced in a fixed order.  One workgroup per component.
+template <int KERN>
+__global__ __launch_bounds__(256) void sobol_table_kernel(const double* __restrict__ x, int n, int d, const double* __restrict__ w,
+                                                          const double* __restrict__ ell, const double* __restrict__ box,
+                                                          double* __restrict__ tab, double* __restrict__ means) {
+    __shared__ double red[4];
+    const int k = blockIdx.x, tid = threadIdx.x;
+    double acc = 0.0;
+    for (int i = tid; i < n; i += 256) {
+        double pr = 1.0;
+        for (int l = 0; l < d; ++l) {
+            const double v = marg_I1<KERN>(x[(size_t)i * d + l], box[l], box[d + l], ell[(size_t)k * d + l]);
+            tab[((size_t)k * d + l) * n + i] = v;
+            pr *= v;
+        }
+        acc = fma(w[(size_t)k * n + i], pr, acc);
+    }
+    acc = sobol_wave_sum(acc);
+    if ((tid & 63) == 0) red[tid >> 6] = acc;
+    __syncthreads();
+    if (tid == 0) means[k] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+// launch 2: one 64 x 64 tile of the (i, i') plane of one pair per workgroup, 16 elements per thread, one after the other.  Per
+// element the d pair averages J_l (a rolled loop: the code of one J is long) go through the thread's own LDS column into
+// registers, the d products A_l = a_l[i] a'_l[i'] beside them; prefix and suffix products then give the 2 d + 1 subset products
+// M_u without a division (factors underflow to zero), and w_i w'_i' (M_u - M_0) is accumulated per subset: the difference is
+// taken per element, never between two large sums.  Rows and columns beyond n are skipped.  A pair k = k' visits the tiles with
+// column tile <= row tile and counts the strictly lower ones twice.  The block sums go to part[pair, tile, subset] (wave
+// shuffles, then the four waves in order): no atomics.  DD >= d bounds the unrolled loops.
+template <int KERN, int DD>
+__global__ __launch_bounds__(256) void sobol_pair_kernel(const double* __restrict__ x, int n, int d, const double* __restrict__ w,
+                                                         const double* __restrict__ ell, const double* __restrict__ box,
+                                                         const double* __restrict__ tab, SobolPairs pr, int ntile,
+                                                         double* __restrict__ part) {
+    __shared__ double xr[TS][DD + 1], xc[TS][DD + 1], ar[TS][DD + 1], ac[TS][DD + 1];
+    __shared__ double wr[TS], wc[TS];
+    __shared__ double Js[DD][256];
+    __shared__ SobolDim cst[DD];
+    __shared__ double red[4][2 * DD + 1];
+    const int r = blockIdx.x, c = blockIdx.y, z = blockIdx.z;
+    const int k = pr.k[z], kp = pr.kp[z];
+    if (k == kp && c > r) return;
+    const int tid = threadIdx.x;
+    for (int e = tid; e < TS * DD; e += 256) {
+        const int i = e / DD, l = e - i * DD;
+        const int gi = r * TS + i, gj = c * TS + i;
+        const bool vi = gi < n && l < d, vj = gj < n && l < d;
+        xr[i][l] = vi ? x[(size_t)gi * d + l] : 0.0;
+        xc[i][l] = vj ? x[(size_t)gj * d + l] : 0.0;
+        ar[i][l] = vi ? tab[((size_t)k * d + l) * n + gi] : 1.0;
+        ac[i][l] = vj ? tab[((size_t)kp * d + l) * n + gj] : 1.0;
+    }
+    if (tid < TS) {
+        const int gi = r * TS + tid, gj = c * TS + tid;
+        wr[tid] = gi < n ? w[(size_t)k * n + gi] : 0.0;
+        wc[tid] = gj < n ? w[(size_t)kp * n + gj] : 0.0;
+    }
+    if (tid < DD) {
+        if (tid < d) cst[tid] = sobol_dim<KERN>(ell[(size_t)k * d + tid], ell[(size_t)kp * d + tid], box[tid], box[d + tid]);
+    }
+#pragma unroll
+    for (int l = 0; l < DD; ++l) Js[l][tid] = 1.0;         // (dimensions d .. DD - 1 stay neutral)
+    __syncthreads();
+    const double twice = (k == kp && c < r) ? 2.0 : 1.0;
+    const int tx = tid & 15, ty = tid >> 4;
+    double accF[DD], accC[DD], accA = 0.0;
+#pragma unroll
+    for (int l = 0; l < DD; ++l) accF[l] = accC[l] = 0.0;
+#pragma unroll 1
+    for (int e = 0; e < 16; ++e) {
+        const int i = ty * 4 + (e >> 2), j = tx + 16 * (e & 3);
+        if (r * TS + i >= n || c * TS + j >= n) continue;
+#pragma unroll 1
+        for (int l = 0; l < d; ++l) Js[l][tid] = sobol_J<KERN>(xr[i][l], xc[j][l], cst[l]);
+        // the weight of the element: ONE place (a matrix entry can take the product's place)
+        const double wgt = twice * (wr[i] * wc[j]);
+        double J[DD], A[DD], F[DD], Cl[DD];
+        double pa = 1.0, pj = 1.0;
+#pragma unroll
+        for (int l = 0; l < DD; ++l) {
+            J[l] = Js[l][tid];
+            A[l] = ar[i][l] * ac[j][l];
+            F[l] = pa * J[l];
+            Cl[l] = pj * A[l];
+            pa *= A[l];
+            pj *= J[l];
+        }
+        const double m0 = pa;
+        accA = fma(wgt, pj - m0, accA);
+        double sa = 1.0, sj = 1.0;
+#pragma unroll
+        for (int l = DD - 1; l >= 0; --l) {
+            accF[l] = fma(wgt, F[l] * sa - m0, accF[l]);
+            accC[l] = fma(wgt, Cl[l] * sj - m0, accC[l]);
+            sa *= A[l];
+            sj *= J[l];
+        }
+    }
+    const int wave = tid >> 6, lane = tid & 63;
+#pragma unroll
+    for (int l = 0; l < DD; ++l) {
+        const double f = sobol_wave_sum(accF[l]), g = sobol_wave_sum(accC[l]);
+        if (lane == 0 && l < d) { red[wave][l] = f; red[wave][d + l] = g; }
+    }
+    accA = sobol_wave_sum(accA);
+    if (lane == 0) red[wave][2 * d] = accA;
+    __syncthreads();
+    if (tid < 2 * d + 1)
+        part[(((size_t)z * ntile + r) * ntile + c) * (2 * d + 1) + tid] = (red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid]);
+}
+
+// launch 2 for d > 16: the same tiles, elements and sums, one input l at a time, its three products recomputed from the inputs
+// (O(d^2) pair averages per element), nothing staged
+template <int KERN>
+__global__ __launch_bounds__(256) void sobol_pair_wide_kernel(const double* __restrict__ x, int n, int d, const double* __restrict__ w,
+                                                              const double* __restrict__ ell, const double* __restrict__ box,
+                                                              const double* __restrict__ tab, SobolPairs pr, int ntile,
+                                                              double* __restrict__ part) {
+    __shared__ double red[4][3];
+    const int r = blockIdx.x, c = blockIdx.y, z = blockIdx.z;
+    const int k = pr.k[z], kp = pr.kp[z];
+    if (k == kp && c > r) return;
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const double twice = (k == kp && c < r) ? 2.0 : 1.0;
+    const int tx = tid & 15, ty = tid >> 4;
+    double* dst = part + (((size_t)z * ntile + r) * ntile + c) * (2 * d + 1);
+    for (int l = 0; l < d; ++l) {
+        double accF = 0.0, accC = 0.0, accA = 0.0;
+        for (int e = 0; e < 16; ++e) {
+            const int gi = r * TS + ty * 4 + (e >> 2), gj = c * TS + tx + 16 * (e & 3);
+            if (gi >= n || gj >= n) continue;
+            double m0 = 1.0, ax = 1.0, jx = 1.0, Al = 1.0, Jl = 1.0;       // prod A, prod over m != l of A and of J, A_l, J_l
+            for (int m = 0; m < d; ++m) {
+                const SobolDim cm = sobol_dim<KERN>(ell[(size_t)k * d + m], ell[(size_t)kp * d + m], box[m], box[d + m]);
+                const double Jm = sobol_J<KERN>(x[(size_t)gi * d + m], x[(size_t)gj * d + m], cm);
+                const double Am = tab[((size_t)k * d + m) * n + gi] * tab[((size_t)kp * d + m) * n + gj];
+                m0 *= Am;
+                if (m == l) { Al = Am; Jl = Jm; }
+                else { ax *= Am; jx *= Jm; }
+            }
+            const double wgt = twice * (w[(size_t)k * n + gi] * w[(size_t)kp * n + gj]);
+            accF = fma(wgt, Jl * ax - m0, accF);
+            accC = fma(wgt, Al * jx - m0, accC);
+            accA = fma(wgt, Jl * jx - m0, accA);
+        }
+        accF = sobol_wave_sum(accF);
+        accC = sobol_wave_sum(accC);
+        accA = sobol_wave_sum(accA);
+        __syncthreads();                                   // (the previous round's sums have been read)
+        if (lane == 0) { red[wave][0] = accF; red[wave][1] = accC; red[wave][2] = accA; }
+        __syncthreads();
+        if (tid < 3 && (tid < 2 || l == 0))
+            dst[tid == 0 ? l : tid == 1 ? d + l : 2 * d] = (red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid]);
+    }
+}
+
+// launch 3: out[pair, s] = the sum over the pair's tiles of part[pair, tile, s] in a fixed order (thread t adds tiles t, t + 256,
+// ..., then a tree over the threads), s = 0 .. 2 d; out[pair, 2 d + 1] = the box mean of component k where k = k', else 0.
+// grid (2 d + 2, pairs of the launch)
+__global__ __launch_bounds__(256) void sobol_reduce_kernel(const double* __restrict__ part, int ntile, int d, SobolPairs pr,
+                                                           const double* __restrict__ means, double* __restrict__ out) {
+    __shared__ double red[256];
+    const int s = blockIdx.x, z = blockIdx.y, tid = threadIdx.x;
+    const int k = pr.k[z], kp = pr.kp[z];
+    double* dst = out + (size_t)z * (2 * d + 2);
+    if (s == 2 * d + 1) {
+        if (tid == 0) dst[s] = k == kp ? means[k] : 0.0;
+        return;
+    }
+    double acc = 0.0;
+    for (int t = tid; t < ntile * ntile; t += 256) {
+        const int r = t / ntile, c = t - r * ntile;
+        if (k == kp && c > r) continue;
+        acc += part[((size_t)z * ntile * ntile + t) * (2 * d + 1) + s];
+    }
+    red[tid] = acc;
+    __syncthreads();
+    for (int o = 128; o >= 1; o >>= 1) {
+        if (tid < o) red[tid] += red[tid + o];
+        __syncthreads();
+    }
+    if (tid == 0) dst[s] = red[0];
+}
+
+inline size_t sobol_part_doubles(int n, int d, int npairs) {
+    const size_t ntile = (n + TS - 1) / TS;
+    return (size_t)(npairs < SOBOL_BATCH ? npairs : SOBOL_BATCH) * ntile * ntile * (2 * d + 1);
+}
+
+int do_sobol_pairs(hipStream_t st, int kern, int n, int d, int q_all, const double* x, const double* w, const double* ell,
+                   const double* box, const int* pairs, int npairs, void* scratch, double* out) {
+    double* tab = (double*)scratch;
+    double* means = tab + (size_t)q_all * d * n;
+    double* part = means + q_all;
+    const int ntile = (n + TS - 1) / TS;
+    for_kern(kern, [&](auto kn) {
+        hipLaunchKernelGGL((sobol_table_kernel<decltype(kn)::value>), dim3(q_all), dim3(256), 0, st, x, n, d, w, ell, box, tab, means);
+    });
+    CHECK_LAUNCH("sobol_table_kernel");
+    for (int p0 = 0; p0 < npairs; p0 += SOBOL_BATCH) {
+        const int nb = npairs - p0 < SOBOL_BATCH ? npairs - p0 : SOBOL_BATCH;
+        SobolPairs pr;
+        for (int i = 0; i < SOBOL_BATCH; ++i) {
+            pr.k[i] = i < nb ? pairs[2 * (p0 + i)] : 0;
+            pr.kp[i] = i < nb ? pairs[2 * (p0 + i) + 1] : 0;
+        }
+        const dim3 grid(ntile, ntile, nb);
+        for_kern(kern, [&](auto kn) {
+            constexpr int K = decltype(kn)::value;
+            if (d <= 8) hipLaunchKernelGGL((sobol_pair_kernel<K, 8>), grid, dim3(256), 0, st, x, n, d, w, ell, box, tab, pr, ntile, part);
+            else if (d <= 16) hipLaunchKernelGGL((sobol_pair_kernel<K, 16>), grid, dim3(256), 0, st, x, n, d, w, ell, box, tab, pr, ntile, part);
+            else hipLaunchKernelGGL((sobol_pair_wide_kernel<K>), grid, dim3(256), 0, st, x, n, d, w, ell, box, tab, pr, ntile, part);
+        });
+        CHECK_LAUNCH("sobol_pair_kernel");
+        hipLaunchKernelGGL(sobol_reduce_kernel, dim3(2 * d + 2, nb), dim3(256), 0, st, part, ntile, d, pr, means,
+                           out + (size_t)p0 * (2 * d + 2));
+        CHECK_LAUNCH("sobol_reduce_kernel");
+    }
+    return 0;
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------------
@@ -8411,6 +8766,35 @@ int lcgp_calib_hess_rows(void* stream, int q, int d, int n0, const double* ghat,
                        ghat, gvar, dghat, dgvar, ld, M, b, inv_range, d2ghat, d2gvar, d2ll, Bout);
     CHECK_LAUNCH("calib_hess_wave");
     return 0;
+}
+
+static int sobol_check(int n, int d, int q_all, int npairs) {
+    if (n < 1) return bad("n < 1");
+    if (d < 1 || d > DWIDE) return bad("d must be in [1, 126]");
+    if (q_all < 1 || q_all > 65535) return bad("q_all must be in [1, 65535]");
+    if (npairs < 1) return bad("npairs < 1");
+    if ((n + TS - 1) / TS > 65535) return bad("n must be at most 64 * 65535");
+    return 0;
+}
+
+int lcgp_sobol_scratch_bytes(int n, int d, int q_all, int npairs, size_t* bytes) {
+    int rc = sobol_check(n, d, q_all, npairs);
+    if (rc) return rc;
+    if (!bytes) return bad("bytes is NULL");
+    *bytes = ((size_t)q_all * d * n + q_all + sobol_part_doubles(n, d, npairs)) * sizeof(double);
+    return 0;
+}
+
+int lcgp_sobol_pairs(void* stream, int kernel_id, int n, int d, int q_all, const double* x, const double* w, const double* ell,
+                     const double* box, const int* pairs, int npairs, void* scratch, double* out) {
+    if (kernel_id != LCGP_KERNEL_MATERN32 && kernel_id != LCGP_KERNEL_SE && kernel_id != LCGP_KERNEL_MATERN52)
+        return bad("kernel_id must be 0 (Matern-3/2), 1 (squared exponential) or 2 (Matern-5/2)");
+    int rc = sobol_check(n, d, q_all, npairs);
+    if (rc) return rc;
+    if (!x || !w || !ell || !box || !pairs || !scratch || !out) return bad("NULL pointer");
+    for (int i = 0; i < 2 * npairs; ++i)
+        if (pairs[i] < 0 || pairs[i] >= q_all) return bad("pairs must hold component indices in [0, q_all)");
+    return do_sobol_pairs((hipStream_t)stream, kernel_id, n, d, q_all, x, w, ell, box, pairs, npairs, scratch, out);
 }
 
 }  // extern "C"

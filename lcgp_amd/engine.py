@@ -500,6 +500,36 @@ class HotPathEngine:
                         "lcgp_condition_predict_marginal")
             return out
 
+    def sobol_pairs(self, x, w, ell, box, pairs):
+        """The pair sums behind the closed-form Sobol indices (lcgp_sobol_pairs), always float64: x (n, d) standardised inputs,
+        w (q_all, n) the weight vectors of ALL components (scale (1 - nt) sr o z), ell (q_all, d) their length scales, box
+        (2, d) = [lo; hi] standardised, pairs (npairs, 2) component indices.  Returns host arrays (D (npairs, 2 d + 1), means
+        (npairs,)): row r = D_u of the pair for u = {l} (l = 0 .. d - 1), all but l, all inputs; means[r] = the box mean of
+        component k where the pair is (k, k), 0 elsewhere.  Nothing of the factorisation is read; the tile sums go through the
+        engine's scratch and are added in a fixed order (two calls agree bit for bit)."""
+        torch = self.torch
+        x = np.ascontiguousarray(x, np.float64)
+        w = np.ascontiguousarray(w, np.float64)
+        ell = np.ascontiguousarray(ell, np.float64)
+        box = np.ascontiguousarray(box, np.float64)
+        pairs = np.ascontiguousarray(pairs, np.int32)
+        n, d = x.shape
+        q_all, npairs = w.shape[0], pairs.shape[0]
+        assert w.shape == (q_all, n) and ell.shape == (q_all, d) and box.shape == (2, d) and pairs.shape == (npairs, 2)
+        if not np.all(box[1] > box[0]):
+            raise ValueError("sobol_pairs: the box needs hi > lo in every dimension")
+        with torch.cuda.device(self.device):
+            dev = [torch.as_tensor(a).to(self.device) for a in (x, w, ell, box)]
+            scratch = self._grow_scratch(self._nbytes("lcgp_sobol_scratch_bytes", n, d, q_all, npairs),
+                                         ("the Sobol pair sums", "%d tile sums of %d pairs at a time" % ((-(-n // 64)) ** 2, min(npairs, 64)),
+                                          "use fewer training inputs"))
+            out = torch.empty((npairs, 2 * d + 2), dtype=torch.float64, device=self.device)
+            _hip.check(self.lib.lcgp_sobol_pairs(self._stream(), self.kernel_id, n, d, q_all, *[self._p(t) for t in dev],
+                                                 pairs.ctypes.data_as(C.POINTER(C.c_int)), npairs, self._p(scratch), self._p(out)),
+                       "lcgp_sobol_pairs")
+            res = out.cpu().numpy()
+        return res[:, :2 * d + 1].copy(), res[:, 2 * d + 1].copy()
+
     def predict_device(self, x0s, same=False):
         """ghat, gvar (q_local, n0): the two halves of predict_block()"""
         out = self.predict_block(x0s, same)

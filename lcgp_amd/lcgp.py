@@ -281,6 +281,22 @@ class MainEffects:
         return 'MainEffects(outputs=%d, d=%d, grid=%d)' % (self.mean.shape[0], self.mean.shape[1], self.mean.shape[2])
 
 
+class SobolIndices:
+    """sobol_indices(): first, total (p_sel, d), the first-order and total Sobol indices of every selected output (latent=True:
+    of every latent component) for each input, of the posterior mean surface under the uniform measure on the box; variance
+    (p_sel,), the variance V of that surface over the box, and mean (p_sel,), its average (main_effects().overall), on the raw
+    output scale; first_variance = V_l (p_sel, d), the variance of the main effect of input l (first = V_l / V), and
+    closed_variance = V_~l, the variance explained by all inputs but l (total = 1 - V_~l / V).  A surface that is constant over
+    the box (V exactly 0) has NaN indices.  Rounding is not clamped: an index may leave [0, 1] by rounding error."""
+
+    def __init__(self, first, total, variance, mean, first_variance, closed_variance):
+        self.first, self.total, self.variance, self.mean = first, total, variance, mean
+        self.first_variance, self.closed_variance = first_variance, closed_variance
+
+    def __repr__(self):
+        return 'SobolIndices(outputs=%d, d=%d)' % tuple(self.first.shape)
+
+
 class ConditionedLCGP:
     """What LCGP.condition() returns: a read-only view of the fitted model `base` conditioned on `m` new unique inputs
     `x_new` (raw scale, (m, d)) at the FIXED parameters, basis and standardisation of the fit.  It holds device state only
@@ -2710,6 +2726,64 @@ class LCGP:
             ev = _t((yconfvar[:, :-1] + yconfvar[:, -1:] - 2.0 * ycov[:, :-1]).reshape(ns, d, G))
         return MainEffects(_t(grid_raw), _t(ypred[:, :-1].reshape(ns, d, G)), _t(yconfvar[:, :-1].reshape(ns, d, G)),
                            _t(ypred[:, -1]), _t(yconfvar[:, -1]), ev)
+
+    # =============================================================================================
+    # Sobol indices of the posterior mean surface in closed form (beyond the reference)
+    # =============================================================================================
+    def sobol_indices(self, box=None, outputs=None, latent=False):
+        """First-order and total Sobol indices of every output with respect to every input: the share of the output's variance
+        over `box` ((2, d) raw scale, default the training inputs' bounding box; uniform measure) that input l explains alone
+        (first) and together with all its interactions (total).  They are those of the posterior mean surface at the fitted
+        parameters (the plug-in estimator; the emulator's own uncertainty does not enter), exact for the product kernels: no
+        sampling, so an index that is zero comes out as rounding error, not as Monte Carlo noise.  Returns a SobolIndices
+        (first, total, variance, mean, first_variance, closed_variance); outputs: output indices (default all p); latent=True:
+        the same for the q latent components (outputs then selects components).
+        One pass on the GPU over the n x n pairs of training inputs per pair of components k <= k' (lcgp_sobol_pairs; latent=True:
+        the q pairs k = k' only), always in float64 -- a float32 model evaluates once on its float64 engine for the weight
+        vectors.  With several ranks the pairs are dealt round-robin over the ranks that hold components and one reduction
+        assembles them: the result does not depend on the number of ranks."""
+        d, p, q = int(self.d), int(self.p), int(self.q)
+        rows = q if latent else p
+        outputs = list(range(rows)) if outputs is None else [int(a) for a in np.atleast_1d(outputs)]
+        if any(a < 0 or a >= rows for a in outputs):
+            raise ValueError('outputs must be indices in [0, %d)' % rows)
+        bs = self._marginal_box(box)
+        eng = self._ensure_aux64()
+        n = int(self.n)
+        sr = np.sqrt(_np(self.r)) if self.submethod == 'rep' else np.ones(n, F64)
+        z = self._fetch_all(lambda e, i: e.fetch_vector(1, i), n)
+        ell, scale_k, nug = self.lLmb.numpy(), self.lLmb0.numpy(), self.lnugGPs.numpy()
+        w = (scale_k * (1.0 - nug / (1.0 + nug)))[:, None] * sr[None, :] * z
+        pairs = np.array([(k, k) for k in range(q)] if latent else [(k, kp) for k in range(q) for kp in range(k, q)], np.int32)
+        rank, world = _dist.rank_world(self._group)
+        mine = np.arange(rank, len(pairs), min(world, q)) if eng is not None else np.zeros(0, int)
+        full = np.zeros((len(pairs), 2 * d + 2), F64)
+
+        def share():
+            if len(mine):
+                full[mine, :2 * d + 1], full[mine, 2 * d + 1] = eng.sobol_pairs(self._x_train(), w, ell, bs, pairs[mine])
+
+        self._agree(share, what='the Sobol pair sums')
+        if _dist.use_collectives(self._group):
+            full = _dist.all_reduce_sum(full.reshape(-1), self._group, None if eng is None else eng.device).reshape(full.shape)
+        D = np.zeros((q, q, 2 * d + 1), F64)
+        means = np.zeros(q, F64)
+        for (k, kp), row in zip(pairs, full):
+            D[k, kp] = D[kp, k] = row[:2 * d + 1]
+            if k == kp:
+                means[k] = row[2 * d + 1]
+        if latent:
+            V, mean = D[np.arange(q), np.arange(q)], means
+        else:
+            W, _, scale, offset = self._output_map()
+            V = np.einsum('ka,la,klu->au', W, W, D) * (scale ** 2)[:, None]
+            mean = offset + scale * (W.T @ means)
+        V, mean = V[outputs], mean[outputs]
+        var = V[:, 2 * d]
+        with np.errstate(divide='ignore', invalid='ignore'):
+            first = np.where(var[:, None] == 0.0, np.nan, V[:, :d] / var[:, None])
+            total = np.where(var[:, None] == 0.0, np.nan, 1.0 - V[:, d:2 * d] / var[:, None])
+        return SobolIndices(_t(first), _t(total), _t(var.copy()), _t(mean.copy()), _t(V[:, :d].copy()), _t(V[:, d:2 * d].copy()))
 
     # ---- cache views the reference keeps as attributes (materialised from the device only when read) ----
     def _fetch_all(self, fn, width):

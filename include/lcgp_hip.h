@@ -980,6 +980,27 @@ int lcgp_sobol_pairs(void* stream, int kernel_id, int n, int d, int q_all,
                      const int* pairs /* npairs x 2, host */, int npairs, void* scratch,
                      double* out /* npairs x (2 d + 2) */);
 
+/* The same pass weighted by a matrix: what the posterior uncertainty of the emulator adds to the Sobol variances, and the
+ * exact box-integrated posterior variance.  For each LOCAL component k in `ks` of a float64 workspace whose
+ * A^-1 slot is filled (what lcgp_fetch_matrix(which = 2) reads), with
+ *     Q[i, i'] = v[k, i] v[k, i'] A_k^-1[i, i'],      v[k, i] = c_k sr_i sqrt(D_k),  c_k = scale_k (1 - nt_k)
+ * and a_l, J_l, M_u, M_0 of lcgp_sobol_pairs for the pair (k, k), row r of `out` holds for k = ks[r]
+ *     sum_{i, i'} Q[i, i'] (M_u - M_0)[i, i']   in columns 0 .. 2 d (u = {l}, all but l, all inputs), and
+ *     S0 = sum_{i, i'} Q[i, i'] M_0[i, i']      in column 2 d + 1.
+ * A^-1 is read IN PLACE, tile by tile (no n x n copy); only its lower triangle is read: the tiles with column tile <= row tile,
+ * the strictly lower ones counted twice, and in a diagonal tile an element above the diagonal takes the mirrored entry.  The
+ * element loop, its pair integrals and the order of every sum are those of lcgp_sobol_pairs, whose results do not change.
+ * v and ell are (q_local, n) and (q_local, d), rows of the LOCAL components; x, v, ell, box, workspace, scratch and out are
+ * device pointers, ks is a HOST array.  float64 only (a float32 workspace is refused), d <= 126, n >= 1, nks >= 1.  No atomics:
+ * two calls agree bit for bit and nothing depends on the scratch content on entry.
+ * scratch: lcgp_sobol_matrix_scratch_bytes(n, d, q_local, nks) = 8 (q_local d n + q_local + min(nks, 64) ceil(n / 64)^2 (2 d + 2)). */
+int lcgp_sobol_matrix_scratch_bytes(int n, int d, int q_local, int nks, size_t* bytes /*host out*/);
+int lcgp_sobol_matrix_pairs(void* stream, int dtype, int kernel_id, int n, int d, int p, int q_local,
+                            const double* x /* n x d, standardised */, const double* v /* q_local x n */,
+                            const double* ell /* q_local x d */, const double* box /* lo[d], hi[d] */,
+                            const void* workspace, const int* ks /* nks, host */, int nks, void* scratch,
+                            double* out /* nks x (2 d + 2) */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -134,6 +134,8 @@ SIGNATURES = {
                                   _vp]),
     "lcgp_sobol_scratch_bytes": (_i, [_i, _i, _i, _i, C.POINTER(C.c_size_t)]),
     "lcgp_sobol_pairs": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, C.POINTER(_i), _i, _vp, _vp]),
+    "lcgp_sobol_matrix_scratch_bytes": (_i, [_i, _i, _i, _i, C.POINTER(C.c_size_t)]),
+    "lcgp_sobol_matrix_pairs": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, C.POINTER(_i), _i, _vp, _vp]),
 }
 
 _lib = None

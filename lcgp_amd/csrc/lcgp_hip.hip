@@ -7303,6 +7303,26 @@ __device__ __forceinline__ double sobol_wave_sum(double v) {          // lane 0 
     return v;
 }
 
+// the matrix a matrix-weighted pair launch reads its weights from: component k's at base + k * mat, rows of npad doubles, the
+// lower triangle valid (the A^-1 slot of a float64 workspace); all zero in the launches of lcgp_sobol_pairs, which never read it
+struct SobolQ { const double* base; size_t mat; int npad; };
+
+// tile (r, c), c <= r, of component k's matrix into qt[i * (TS + 1) + j], for the 256 threads of a workgroup: thread e reads
+// row e / 64, column e % 64, so a wavefront reads 64 consecutive doubles of one row.  In a diagonal tile only j <= i is read
+// and written to both (i, j) and (j, i): an element above the diagonal takes the mirrored entry.  Rows and columns beyond n
+// (never used by the element loop) are zero.  The caller's barrier follows.
+__device__ __forceinline__ void sobol_stage_q(double* qt, const SobolQ& qm, int k, int n, int r, int c, int tid) {
+    const double* src = qm.base + (size_t)k * qm.mat;
+    for (int e = tid; e < TS * TS; e += 256) {
+        const int i = e >> 6, j = e & 63;
+        const int gi = r * TS + i, gj = c * TS + j;
+        if (r == c && j > i) continue;
+        const double v = (gi < n && gj < n) ? src[(size_t)gi * qm.npad + gj] : 0.0;
+        qt[i * (TS + 1) + j] = v;
+        if (r == c) qt[j * (TS + 1) + i] = v;
+    }
+}
+
 // launch 1: tab[k, l, i] = the box average of the 1-D factor of component k at training input i (marg_I1), and the box mean
 // means[k] = sum_i w_ki prod_l tab[k, l, i] of the component's surface, reduced in a fixed order.  One workgroup per component.
 template <int KERN>
@@ -7334,16 +7354,20 @@ __global__ __launch_bounds__(256) void sobol_table_kernel(const double* __restri
 // taken per element, never between two large sums.  Rows and columns beyond n are skipped.  A pair k = k' visits the tiles with
 // column tile <= row tile and counts the strictly lower ones twice.  The block sums go to part[pair, tile, subset] (wave
 // shuffles, then the four waves in order): no atomics.  DD >= d bounds the unrolled loops.
-template <int KERN, int DD>
+// MAT (lcgp_sobol_matrix_pairs): pairs k = k' of LOCAL components only, and the weight of an element is
+// w_i w_i' Q[i, i'] with Q the component's matrix in `qm` (A^-1 in place: qmat elements per component, rows of npad, its lower
+// triangle valid).  The tile of Q goes through LDS (sobol_stage_q); one more sum per tile, S0 = sum w_i w_i' Q M_0, follows the
+// 2 d + 1 others in part.  Nothing of MAT is instantiated in the instances without it.
+template <int KERN, int DD, bool MAT>
 __global__ __launch_bounds__(256) void sobol_pair_kernel(const double* __restrict__ x, int n, int d, const double* __restrict__ w,
                                                          const double* __restrict__ ell, const double* __restrict__ box,
                                                          const double* __restrict__ tab, SobolPairs pr, int ntile,
-                                                         double* __restrict__ part) {
+                                                         double* __restrict__ part, SobolQ qm) {
     __shared__ double xr[TS][DD + 1], xc[TS][DD + 1], ar[TS][DD + 1], ac[TS][DD + 1];
     __shared__ double wr[TS], wc[TS];
     __shared__ double Js[DD][256];
     __shared__ SobolDim cst[DD];
-    __shared__ double red[4][2 * DD + 1];
+    __shared__ double red[4][2 * DD + (MAT ? 2 : 1)];
     const int r = blockIdx.x, c = blockIdx.y, z = blockIdx.z;
     const int k = pr.k[z], kp = pr.kp[z];
     if (k == kp && c > r) return;
@@ -7367,10 +7391,17 @@ __global__ __launch_bounds__(256) void sobol_pair_kernel(const double* __restric
     }
 #pragma unroll
     for (int l = 0; l < DD; ++l) Js[l][tid] = 1.0;         // (dimensions d .. DD - 1 stay neutral)
+    const double* qs = nullptr;
+    if constexpr (MAT) {
+        __shared__ double qtile[TS * (TS + 1)];
+        sobol_stage_q(qtile, qm, k, n, r, c, tid);
+        qs = qtile;
+    }
     __syncthreads();
     const double twice = (k == kp && c < r) ? 2.0 : 1.0;
     const int tx = tid & 15, ty = tid >> 4;
     double accF[DD], accC[DD], accA = 0.0;
+    [[maybe_unused]] double accS = 0.0;
 #pragma unroll
     for (int l = 0; l < DD; ++l) accF[l] = accC[l] = 0.0;
 #pragma unroll 1
@@ -7380,7 +7411,8 @@ __global__ __launch_bounds__(256) void sobol_pair_kernel(const double* __restric
 #pragma unroll 1
         for (int l = 0; l < d; ++l) Js[l][tid] = sobol_J<KERN>(xr[i][l], xc[j][l], cst[l]);
         // the weight of the element: ONE place (a matrix entry can take the product's place)
-        const double wgt = twice * (wr[i] * wc[j]);
+        double wgt = twice * (wr[i] * wc[j]);
+        if constexpr (MAT) wgt *= qs[i * (TS + 1) + j];
         double J[DD], A[DD], F[DD], Cl[DD];
         double pa = 1.0, pj = 1.0;
 #pragma unroll
@@ -7394,6 +7426,7 @@ __global__ __launch_bounds__(256) void sobol_pair_kernel(const double* __restric
         }
         const double m0 = pa;
         accA = fma(wgt, pj - m0, accA);
+        if constexpr (MAT) accS = fma(wgt, m0, accS);
         double sa = 1.0, sj = 1.0;
 #pragma unroll
         for (int l = DD - 1; l >= 0; --l) {
@@ -7411,28 +7444,42 @@ __global__ __launch_bounds__(256) void sobol_pair_kernel(const double* __restric
     }
     accA = sobol_wave_sum(accA);
     if (lane == 0) red[wave][2 * d] = accA;
+    if constexpr (MAT) {
+        accS = sobol_wave_sum(accS);
+        if (lane == 0) red[wave][2 * d + 1] = accS;
+    }
     __syncthreads();
-    if (tid < 2 * d + 1)
-        part[(((size_t)z * ntile + r) * ntile + c) * (2 * d + 1) + tid] = (red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid]);
+    constexpr int EX = MAT ? 1 : 0;
+    if (tid < 2 * d + 1 + EX)
+        part[(((size_t)z * ntile + r) * ntile + c) * (2 * d + 1 + EX) + tid] = (red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid]);
 }
 
 // launch 2 for d > 16: the same tiles, elements and sums, one input l at a time, its three products recomputed from the inputs
 // (O(d^2) pair averages per element), nothing staged
-template <int KERN>
+template <int KERN, bool MAT>
 __global__ __launch_bounds__(256) void sobol_pair_wide_kernel(const double* __restrict__ x, int n, int d, const double* __restrict__ w,
                                                               const double* __restrict__ ell, const double* __restrict__ box,
                                                               const double* __restrict__ tab, SobolPairs pr, int ntile,
-                                                              double* __restrict__ part) {
-    __shared__ double red[4][3];
+                                                              double* __restrict__ part, SobolQ qm) {
+    constexpr int NR = MAT ? 4 : 3;                        // sums per round: F, C, all[, S0]
+    __shared__ double red[4][NR];
     const int r = blockIdx.x, c = blockIdx.y, z = blockIdx.z;
     const int k = pr.k[z], kp = pr.kp[z];
     if (k == kp && c > r) return;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const double twice = (k == kp && c < r) ? 2.0 : 1.0;
     const int tx = tid & 15, ty = tid >> 4;
-    double* dst = part + (((size_t)z * ntile + r) * ntile + c) * (2 * d + 1);
+    double* dst = part + (((size_t)z * ntile + r) * ntile + c) * (2 * d + NR - 2);
+    const double* qs = nullptr;
+    if constexpr (MAT) {                                   // (the one thing staged: every round reads the same weights)
+        __shared__ double qtile[TS * (TS + 1)];
+        sobol_stage_q(qtile, qm, k, n, r, c, tid);
+        qs = qtile;
+        __syncthreads();
+    }
     for (int l = 0; l < d; ++l) {
         double accF = 0.0, accC = 0.0, accA = 0.0;
+        [[maybe_unused]] double accS = 0.0;
         for (int e = 0; e < 16; ++e) {
             const int gi = r * TS + ty * 4 + (e >> 2), gj = c * TS + tx + 16 * (e & 3);
             if (gi >= n || gj >= n) continue;
@@ -7445,40 +7492,49 @@ __global__ __launch_bounds__(256) void sobol_pair_wide_kernel(const double* __re
                 if (m == l) { Al = Am; Jl = Jm; }
                 else { ax *= Am; jx *= Jm; }
             }
-            const double wgt = twice * (w[(size_t)k * n + gi] * w[(size_t)kp * n + gj]);
+            double wgt = twice * (w[(size_t)k * n + gi] * w[(size_t)kp * n + gj]);
+            if constexpr (MAT) wgt *= qs[(ty * 4 + (e >> 2)) * (TS + 1) + tx + 16 * (e & 3)];
             accF = fma(wgt, Jl * ax - m0, accF);
             accC = fma(wgt, Al * jx - m0, accC);
             accA = fma(wgt, Jl * jx - m0, accA);
+            if constexpr (MAT) accS = fma(wgt, m0, accS);
         }
         accF = sobol_wave_sum(accF);
         accC = sobol_wave_sum(accC);
         accA = sobol_wave_sum(accA);
+        if constexpr (MAT) accS = sobol_wave_sum(accS);
         __syncthreads();                                   // (the previous round's sums have been read)
         if (lane == 0) { red[wave][0] = accF; red[wave][1] = accC; red[wave][2] = accA; }
+        if constexpr (MAT) {
+            if (lane == 0) red[wave][3] = accS;
+        }
         __syncthreads();
-        if (tid < 3 && (tid < 2 || l == 0))
-            dst[tid == 0 ? l : tid == 1 ? d + l : 2 * d] = (red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid]);
+        if (tid < NR && (tid < 2 || l == 0))
+            dst[tid == 0 ? l : tid == 1 ? d + l : 2 * d + tid - 2] = (red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid]);
     }
 }
 
 // launch 3: out[pair, s] = the sum over the pair's tiles of part[pair, tile, s] in a fixed order (thread t adds tiles t, t + 256,
 // ..., then a tree over the threads), s = 0 .. 2 d; out[pair, 2 d + 1] = the box mean of component k where k = k', else 0.
-// grid (2 d + 2, pairs of the launch)
+// grid (2 d + 2, pairs of the launch).  MAT: part holds 2 d + 2 sums per tile and out[pair, 2 d + 1] is the last one's sum, S0.
+template <bool MAT>
 __global__ __launch_bounds__(256) void sobol_reduce_kernel(const double* __restrict__ part, int ntile, int d, SobolPairs pr,
                                                            const double* __restrict__ means, double* __restrict__ out) {
     __shared__ double red[256];
     const int s = blockIdx.x, z = blockIdx.y, tid = threadIdx.x;
     const int k = pr.k[z], kp = pr.kp[z];
     double* dst = out + (size_t)z * (2 * d + 2);
-    if (s == 2 * d + 1) {
-        if (tid == 0) dst[s] = k == kp ? means[k] : 0.0;
-        return;
+    if constexpr (!MAT) {
+        if (s == 2 * d + 1) {
+            if (tid == 0) dst[s] = k == kp ? means[k] : 0.0;
+            return;
+        }
     }
     double acc = 0.0;
     for (int t = tid; t < ntile * ntile; t += 256) {
         const int r = t / ntile, c = t - r * ntile;
         if (k == kp && c > r) continue;
-        acc += part[((size_t)z * ntile * ntile + t) * (2 * d + 1) + s];
+        acc += part[((size_t)z * ntile * ntile + t) * (2 * d + (MAT ? 2 : 1)) + s];
     }
     red[tid] = acc;
     __syncthreads();
@@ -7489,13 +7545,16 @@ __global__ __launch_bounds__(256) void sobol_reduce_kernel(const double* __restr
     if (tid == 0) dst[s] = red[0];
 }
 
-inline size_t sobol_part_doubles(int n, int d, int npairs) {
+inline size_t sobol_part_doubles(int n, int d, int npairs, int per_tile_extra = 0) {
     const size_t ntile = (n + TS - 1) / TS;
-    return (size_t)(npairs < SOBOL_BATCH ? npairs : SOBOL_BATCH) * ntile * ntile * (2 * d + 1);
+    return (size_t)(npairs < SOBOL_BATCH ? npairs : SOBOL_BATCH) * ntile * ntile * (2 * d + 1 + per_tile_extra);
 }
 
+// MAT = false: lcgp_sobol_pairs (qm unused).  MAT = true: lcgp_sobol_matrix_pairs, `pairs` holds (k, k) of local components,
+// w their row vectors v and out[pair, 2 d + 1] is S0
+template <bool MAT>
 int do_sobol_pairs(hipStream_t st, int kern, int n, int d, int q_all, const double* x, const double* w, const double* ell,
-                   const double* box, const int* pairs, int npairs, void* scratch, double* out) {
+                   const double* box, const int* pairs, int npairs, void* scratch, double* out, SobolQ qm) {
     double* tab = (double*)scratch;
     double* means = tab + (size_t)q_all * d * n;
     double* part = means + q_all;
@@ -7514,12 +7573,15 @@ int do_sobol_pairs(hipStream_t st, int kern, int n, int d, int q_all, const doub
         const dim3 grid(ntile, ntile, nb);
         for_kern(kern, [&](auto kn) {
             constexpr int K = decltype(kn)::value;
-            if (d <= 8) hipLaunchKernelGGL((sobol_pair_kernel<K, 8>), grid, dim3(256), 0, st, x, n, d, w, ell, box, tab, pr, ntile, part);
-            else if (d <= 16) hipLaunchKernelGGL((sobol_pair_kernel<K, 16>), grid, dim3(256), 0, st, x, n, d, w, ell, box, tab, pr, ntile, part);
-            else hipLaunchKernelGGL((sobol_pair_wide_kernel<K>), grid, dim3(256), 0, st, x, n, d, w, ell, box, tab, pr, ntile, part);
+            if (d <= 8)
+                hipLaunchKernelGGL((sobol_pair_kernel<K, 8, MAT>), grid, dim3(256), 0, st, x, n, d, w, ell, box, tab, pr, ntile, part, qm);
+            else if (d <= 16)
+                hipLaunchKernelGGL((sobol_pair_kernel<K, 16, MAT>), grid, dim3(256), 0, st, x, n, d, w, ell, box, tab, pr, ntile, part, qm);
+            else
+                hipLaunchKernelGGL((sobol_pair_wide_kernel<K, MAT>), grid, dim3(256), 0, st, x, n, d, w, ell, box, tab, pr, ntile, part, qm);
         });
         CHECK_LAUNCH("sobol_pair_kernel");
-        hipLaunchKernelGGL(sobol_reduce_kernel, dim3(2 * d + 2, nb), dim3(256), 0, st, part, ntile, d, pr, means,
+        hipLaunchKernelGGL((sobol_reduce_kernel<MAT>), dim3(2 * d + 2, nb), dim3(256), 0, st, part, ntile, d, pr, means,
                            out + (size_t)p0 * (2 * d + 2));
         CHECK_LAUNCH("sobol_reduce_kernel");
     }
@@ -8794,7 +8856,36 @@ int lcgp_sobol_pairs(void* stream, int kernel_id, int n, int d, int q_all, const
     if (!x || !w || !ell || !box || !pairs || !scratch || !out) return bad("NULL pointer");
     for (int i = 0; i < 2 * npairs; ++i)
         if (pairs[i] < 0 || pairs[i] >= q_all) return bad("pairs must hold component indices in [0, q_all)");
-    return do_sobol_pairs((hipStream_t)stream, kernel_id, n, d, q_all, x, w, ell, box, pairs, npairs, scratch, out);
+    return do_sobol_pairs<false>((hipStream_t)stream, kernel_id, n, d, q_all, x, w, ell, box, pairs, npairs, scratch, out,
+                                 SobolQ{nullptr, 0, 0});
+}
+
+int lcgp_sobol_matrix_scratch_bytes(int n, int d, int q_local, int nks, size_t* bytes) {
+    int rc = sobol_check(n, d, q_local, 1);
+    if (rc) return rc;
+    if (nks < 1) return bad("nks < 1");
+    if (!bytes) return bad("bytes is NULL");
+    *bytes = ((size_t)q_local * d * n + q_local + sobol_part_doubles(n, d, nks, 1)) * sizeof(double);
+    return 0;
+}
+
+int lcgp_sobol_matrix_pairs(void* stream, int dtype, int kernel_id, int n, int d, int p, int q_local, const double* x,
+                            const double* v, const double* ell, const double* box, const void* workspace, const int* ks,
+                            int nks, void* scratch, double* out) {
+    if (dtype != LCGP_F64) return bad("lcgp_sobol_matrix_pairs reads a float64 workspace");
+    int rc = check_common(dtype, n, d, p, q_local, kernel_id);
+    if (rc) return rc;
+    if ((rc = sobol_check(n, d, q_local, 1))) return rc;
+    if (nks < 1) return bad("nks < 1");
+    if (!x || !v || !ell || !box || !workspace || !ks || !scratch || !out) return bad("NULL pointer");
+    std::vector<int> pairs(2 * (size_t)nks);
+    for (int i = 0; i < nks; ++i) {
+        if (ks[i] < 0 || ks[i] >= q_local) return bad("ks must hold local component indices in [0, q_local)");
+        pairs[2 * i] = pairs[2 * i + 1] = ks[i];
+    }
+    Ws w = carve(dtype, n, d, p, q_local, (void*)workspace);
+    const SobolQ qm{(const double*)(w.base + w.off_V), w.mat, w.npad};
+    return do_sobol_pairs<true>((hipStream_t)stream, kernel_id, n, d, q_local, x, v, ell, box, pairs.data(), nks, scratch, out, qm);
 }
 
 }  // extern "C"

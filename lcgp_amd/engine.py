@@ -530,6 +530,41 @@ class HotPathEngine:
             res = out.cpu().numpy()
         return res[:, :2 * d + 1].copy(), res[:, 2 * d + 1].copy()
 
+    def sobol_matrix_sums(self, x, v, ell, box, ks):
+        """The pair sums of sobol_pairs for the pairs (k, k) of the LOCAL components ks, weighted by the matrix
+        Q[i, i'] = v[k, i] v[k, i'] A_k^-1[i, i'] instead of a product of two vectors (lcgp_sobol_matrix_pairs):
+        x (n, d) standardised inputs, v (q_local, n) the row vectors c sr sqrt(D) and ell (q_local, d) the length scales of the
+        local components, box (2, d) standardised, ks local component indices.  Returns host arrays (sums (len(ks), 2 d + 1),
+        s0 (len(ks),)): sum Q (M_u - M_0) for u = {l}, all but l, all inputs, and S0 = sum Q M_0.  A^-1 is read in place from the
+        float64 workspace of the last evaluate(); the tile sums go through the engine's scratch in a fixed order."""
+        torch = self.torch
+        assert self.dtype == _hip.F64, "sobol_matrix_sums reads the A^-1 of a float64 engine"
+        if self._theta_last is None:
+            raise RuntimeError("sobol_matrix_sums() needs a preceding evaluate() at the current parameters")
+        x = np.ascontiguousarray(x, np.float64)
+        v = np.ascontiguousarray(v, np.float64)
+        ell = np.ascontiguousarray(ell, np.float64)
+        box = np.ascontiguousarray(box, np.float64)
+        ks = np.ascontiguousarray(ks, np.int32).reshape(-1)
+        n, d = x.shape
+        nks = ks.shape[0]
+        assert n == self.n and d == self.d and v.shape == (self.q_local, n) and ell.shape == (self.q_local, d) and box.shape == (2, d)
+        if not np.all(box[1] > box[0]):
+            raise ValueError("sobol_matrix_sums: the box needs hi > lo in every dimension")
+        with torch.cuda.device(self.device):
+            dev = [torch.as_tensor(a).to(self.device) for a in (x, v, ell, box)]
+            scratch = self._grow_scratch(self._nbytes("lcgp_sobol_matrix_scratch_bytes", n, d, self.q_local, nks),
+                                         ("the matrix-weighted Sobol pair sums",
+                                          "%d tile sums of %d components at a time" % ((-(-n // 64)) ** 2, min(nks, 64)),
+                                          "use fewer training inputs"))
+            out = torch.empty((nks, 2 * d + 2), dtype=torch.float64, device=self.device)
+            _hip.check(self.lib.lcgp_sobol_matrix_pairs(self._stream(), self.dtype, self.kernel_id, n, d, self.p, self.q_local,
+                                                        *[self._p(t) for t in dev], self._p(self.workspace),
+                                                        ks.ctypes.data_as(C.POINTER(C.c_int)), nks, self._p(scratch), self._p(out)),
+                       "lcgp_sobol_matrix_pairs")
+            res = out.cpu().numpy()
+        return res[:, :2 * d + 1].copy(), res[:, 2 * d + 1].copy()
+
     def predict_device(self, x0s, same=False):
         """ghat, gvar (q_local, n0): the two halves of predict_block()"""
         out = self.predict_block(x0s, same)

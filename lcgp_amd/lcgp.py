@@ -43,6 +43,30 @@ def _np(a):
     return np.asarray(a, dtype=F64)
 
 
+def _box_double_average(kernel, a):
+    """I2 = (1 / w^2) int int kappa(|t - t'| / ell) dt dt' over [0, w]^2 = 2 [F(a) / a - G(a) / a^2], a = w / ell, of the 1-D
+    factor of the product kernel (a scalar, host side: q d values per call).  Matern below a = 1/2: F and G from
+    the Taylor series of kappa, as the device does, because their closed forms cancel there."""
+    import math
+    if kernel == 'se':
+        Fa, Ga = math.sqrt(0.5 * math.pi) * math.erf(a * math.sqrt(0.5)), -math.expm1(-0.5 * a * a)
+    elif a < 0.5:
+        t, sf, sg = 1.0, 0.0, 0.0
+        for m in range(20):
+            f = 1.0 - m if kernel == 'matern32' else (m - 1.0) * (m - 3.0) / 3.0
+            sf += t * f / (m + 1.0)
+            sg += t * f / (m + 2.0)
+            t *= -a / (m + 1.0)
+        Fa, Ga = a * sf, a * a * sg
+    else:
+        e, em = math.exp(-a), -math.expm1(-a)
+        if kernel == 'matern32':
+            Fa, Ga = 2.0 * em - a * e, 3.0 * em - a * (3.0 + a) * e
+        else:
+            Fa, Ga = (8.0 / 3.0) * em - a * (5.0 + a) / 3.0 * e, 5.0 * em - a * (5.0 + a * (2.0 + a / 3.0)) * e
+    return 2.0 * (Fa / a - Ga / (a * a))
+
+
 def _percentile50_nearest(a):
     """tfp.stats.percentile(a, 50.0, axis=1, keepdims=True) with its default 'nearest' interpolation
     (lcgp.py:317-318, 388-389): ascending sort, index round-half-even(0.5 (m-1)).  Not np.median."""
@@ -287,11 +311,21 @@ class SobolIndices:
     (p_sel,), the variance V of that surface over the box, and mean (p_sel,), its average (main_effects().overall), on the raw
     output scale; first_variance = V_l (p_sel, d), the variance of the main effect of input l (first = V_l / V), and
     closed_variance = V_~l, the variance explained by all inputs but l (total = 1 - V_~l / V).  A surface that is constant over
-    the box (V exactly 0) has NaN indices.  Rounding is not clamped: an index may leave [0, 1] by rounding error."""
+    the box (V exactly 0) has NaN indices.  Rounding is not clamped: an index may leave [0, 1] by rounding error.
+    With uncertainty=True also (None otherwise) the posterior EXPECTATIONS of the same variances under the emulator's own
+    uncertainty at the fitted parameters: expected_variance (p_sel,) = E[V], expected_first_variance = E[V_l] and
+    expected_closed_variance = E[V_~l] (p_sel, d), each the plug-in value plus a correction >= 0; first_expected = E[V_l] /
+    E[V] and total_expected = 1 - E[V_~l] / E[V], ratios of expectations (NaN where E[V] is exactly 0); and
+    integrated_variance (p_sel,), the posterior variance of the continuous surface averaged over the box."""
 
-    def __init__(self, first, total, variance, mean, first_variance, closed_variance):
+    def __init__(self, first, total, variance, mean, first_variance, closed_variance, expected_variance=None,
+                 expected_first_variance=None, expected_closed_variance=None, first_expected=None, total_expected=None,
+                 integrated_variance=None):
         self.first, self.total, self.variance, self.mean = first, total, variance, mean
         self.first_variance, self.closed_variance = first_variance, closed_variance
+        self.expected_variance, self.integrated_variance = expected_variance, integrated_variance
+        self.expected_first_variance, self.expected_closed_variance = expected_first_variance, expected_closed_variance
+        self.first_expected, self.total_expected = first_expected, total_expected
 
     def __repr__(self):
         return 'SobolIndices(outputs=%d, d=%d)' % tuple(self.first.shape)
@@ -2730,7 +2764,7 @@ class LCGP:
     # =============================================================================================
     # Sobol indices of the posterior mean surface in closed form (beyond the reference)
     # =============================================================================================
-    def sobol_indices(self, box=None, outputs=None, latent=False):
+    def sobol_indices(self, box=None, outputs=None, latent=False, uncertainty=False):
         """First-order and total Sobol indices of every output with respect to every input: the share of the output's variance
         over `box` ((2, d) raw scale, default the training inputs' bounding box; uniform measure) that input l explains alone
         (first) and together with all its interactions (total).  They are those of the posterior mean surface at the fitted
@@ -2741,12 +2775,15 @@ class LCGP:
         One pass on the GPU over the n x n pairs of training inputs per pair of components k <= k' (lcgp_sobol_pairs; latent=True:
         the q pairs k = k' only), always in float64 -- a float32 model evaluates once on its float64 engine for the weight
         vectors.  With several ranks the pairs are dealt round-robin over the ranks that hold components and one reduction
-        assembles them: the result does not depend on the number of ranks."""
+        assembles them: the result does not depend on the number of ranks.
+        uncertainty=True: the SobolIndices also carries the posterior expectations of the variances (Oakley and O'Hagan 2004)
+        and the integrated variance (expected_variance, expected_first_variance, expected_closed_variance, first_expected,
+        total_expected, integrated_variance): with few runs the plug-in indices understate the variance, and an
+        input the data say nothing about gets a plug-in index of exactly zero.  One more pass over the pairs k = k' (on the rank
+        that owns the component, weighted by its A^-1 in place: lcgp_sobol_matrix_pairs) and one more reduction; the fields
+        above are bitwise the same with and without it."""
         d, p, q = int(self.d), int(self.p), int(self.q)
-        rows = q if latent else p
-        outputs = list(range(rows)) if outputs is None else [int(a) for a in np.atleast_1d(outputs)]
-        if any(a < 0 or a >= rows for a in outputs):
-            raise ValueError('outputs must be indices in [0, %d)' % rows)
+        outputs = self._sobol_rows(outputs, latent)
         bs = self._marginal_box(box)
         eng = self._ensure_aux64()
         n = int(self.n)
@@ -2783,7 +2820,84 @@ class LCGP:
         with np.errstate(divide='ignore', invalid='ignore'):
             first = np.where(var[:, None] == 0.0, np.nan, V[:, :d] / var[:, None])
             total = np.where(var[:, None] == 0.0, np.nan, 1.0 - V[:, d:2 * d] / var[:, None])
-        return SobolIndices(_t(first), _t(total), _t(var.copy()), _t(mean.copy()), _t(V[:, :d].copy()), _t(V[:, d:2 * d].copy()))
+        plug = (_t(first), _t(total), _t(var.copy()), _t(mean.copy()), _t(V[:, :d].copy()), _t(V[:, d:2 * d].copy()))
+        if not uncertainty:
+            return SobolIndices(*plug)
+        corr, iv, _ = self._sobol_matrix(bs)
+        E = V + self._latent_variance_to_rows(corr, latent)[outputs]
+        ev = E[:, 2 * d]
+        with np.errstate(divide='ignore', invalid='ignore'):
+            first_e = np.where(ev[:, None] == 0.0, np.nan, E[:, :d] / ev[:, None])
+            total_e = np.where(ev[:, None] == 0.0, np.nan, 1.0 - E[:, d:2 * d] / ev[:, None])
+        return SobolIndices(*plug, _t(ev.copy()), _t(E[:, :d].copy()), _t(E[:, d:2 * d].copy()), _t(first_e), _t(total_e),
+                            _t(self._latent_variance_to_rows(iv, latent)[outputs]))
+
+    def integrated_variance(self, box=None, outputs=None, latent=False):
+        """(p_sel,) the posterior variance of every selected output averaged over `box` ((2, d) raw scale, default the training
+        inputs' bounding box; uniform measure), exact for the product kernels: IMSPE, the number a design is judged by, without
+        a Monte Carlo mean of predict().  It is the variance of the CONTINUOUS surface (no nugget, as in predict_marginal): the
+        box mean of predict()'s yconfvar at new inputs exceeds it by the constant scale_a^2 sum_k W_ka^2 scale_k nt_k.
+        outputs: output indices (default all p); latent=True: per latent component (outputs then selects components).  The
+        matrix-weighted pass of sobol_indices(uncertainty=True) alone -- none of the q (q + 1) / 2 pairs of the mean surface
+        -- and bitwise that call's integrated_variance; float64 always, any number of ranks."""
+        outputs = self._sobol_rows(outputs, latent)
+        _, iv, _ = self._sobol_matrix(self._marginal_box(box))
+        return _t(self._latent_variance_to_rows(iv, latent)[outputs])
+
+    def _sobol_rows(self, outputs, latent):
+        """the checked list of rows `outputs` selects: of the p outputs, latent: of the q components"""
+        rows = int(self.q) if latent else int(self.p)
+        outputs = list(range(rows)) if outputs is None else [int(a) for a in np.atleast_1d(outputs)]
+        if any(a < 0 or a >= rows for a in outputs):
+            raise ValueError('outputs must be indices in [0, %d)' % rows)
+        return outputs
+
+    def _latent_variance_to_rows(self, lat, latent):
+        """per-component variances lat (q, ...) -> per output: scale_a^2 sum_k W_ka^2 lat[k] (latent: unchanged)"""
+        if latent:
+            return lat
+        W, _, scale, _ = self._output_map()
+        return np.tensordot((W ** 2).T, lat, axes=(1, 0)) * (scale ** 2).reshape((-1,) + (1,) * (lat.ndim - 1))
+
+    def _sobol_matrix(self, bs):
+        """What the posterior covariance of the continuous surface adds, per latent component, over the standardised box bs
+        (DESIGN.md 4.23): (C (q, 2 d + 1), IV (q,), overall_var (q,)) with
+            C_u = c (prod_{l not in u} I2_l - prod_l I2_l) - sum Q (M_u - M_0)      E[V_u] - V_u(mean), u as in sobol_indices
+            IV  = c - S0 - sum Q (M_all - M_0)                                        the box mean of the posterior variance
+            overall_var = c prod_l I2_l - S0                                          the variance of the box mean
+        c = scale (1 - nt), Q = D c^2 sr sr^T o A^-1.  Every rank evaluates the components it holds on its float64 engine
+        (lcgp_sobol_matrix_pairs), fills their rows of a zero array, and one reduction completes it."""
+        d, q, n = int(self.d), int(self.q), int(self.n)
+        eng = self._ensure_aux64()
+        sr = np.sqrt(_np(self.r)) if self.submethod == 'rep' else np.ones(n, F64)
+        ell, scale_k, nug = self.lLmb.numpy(), self.lLmb0.numpy(), self.lnugGPs.numpy()
+        c = scale_k * (1.0 - nug / (1.0 + nug))
+        Dk = _np(self.diag_D).reshape(-1)
+        full = np.zeros((q, 2 * d + 2), F64)
+
+        def share():
+            if eng is not None:
+                loc = [int(k) for k in self._local_ks]
+                v = (c[loc] * np.sqrt(Dk[loc]))[:, None] * sr[None, :]
+                full[loc, :2 * d + 1], full[loc, 2 * d + 1] = eng.sobol_matrix_sums(self._x_train(), v, ell[loc], bs,
+                                                                                    np.arange(len(loc)))
+
+        self._agree(share, what='the matrix-weighted Sobol pair sums')
+        if _dist.use_collectives(self._group):
+            full = _dist.all_reduce_sum(full.reshape(-1), self._group, None if eng is None else eng.device).reshape(full.shape)
+        width = bs[1] - bs[0]
+        prior = np.zeros((q, 2 * d + 1), F64)                  # prod of I2 over the inputs NOT in u (u = all: the empty product)
+        i2all = np.ones(q, F64)
+        for k in range(q):
+            i2 = [_box_double_average(self.kernel, float(width[l] / ell[k, l])) for l in range(d)]
+            for l in range(d):
+                prior[k, l] = float(np.prod([i2[m] for m in range(d) if m != l]))
+                prior[k, d + l] = i2[l]
+            prior[k, 2 * d] = 1.0
+            i2all[k] = float(np.prod(i2))
+        sums, s0 = full[:, :2 * d + 1], full[:, 2 * d + 1]
+        C = c[:, None] * (prior - i2all[:, None]) - sums
+        return C, c - s0 - sums[:, 2 * d], c * i2all - s0
 
     # ---- cache views the reference keeps as attributes (materialised from the device only when read) ----
     def _fetch_all(self, fn, width):

@@ -5,7 +5,10 @@ variance reduction) and of the conditioned view (lcgp_condition_prepare / lcgp_c
 L_S^-1, v, Sigma_0n, T and the corrected outputs) and of the two second-order input queries (lcgp_predict_hess: DX, P = DX W^T,
 the packed Hessians; lcgp_predict_gradcov: dghat, Gamma and its weighted sum M) and of the box-averaged predictions
 (lcgp_predict_marginal / lcgp_condition_predict_marginal: the table of 1-D averages against mpmath, the masked rows, the outputs
-with the averaged prior, the view's stages and gcov).
+with the averaged prior, the view's stages and gcov) and of the two parameter-space queries (lcgp_nll_hess: xs and the two
+closed-form vectors, the mirrored A^-1 with G_scale and G_nug, d_iA, y_i, G_i, the trace partials, the contraction slots, u_i / dot
+/ YP / Q, the three output blocks; lcgp_predict_paramgrad: y_j, T, the row dots, the 3 d + 8 row sums, YT and V YT, the three
+outputs -- with hess_layout / pgrad_layout restating the scratch layouts).
 
 Every check compares one stage of the library with a plain float64 reference computed from THE LIBRARY'S OWN INPUT TO THAT
 STAGE (the fetched A for the Cholesky, the fetched L for L^-1, ...), so no bound carries a condition number.  Entries are
@@ -1684,3 +1687,620 @@ def check_marg_refcov(gcov, U, T, ref, x0, mask, xr, mr, box, i2, th, kernel, dt
     bound = C * (n + m + d + 4.0) * u64 * (prt.abs() + abs(D) * adots + atdot) + C * prt.abs() * _t(rel, dev) \
         + floor("float64", n + m)
     return worst((_t(gcov, dev) - gref).abs(), bound)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# the two parameter-space queries: lcgp_nll_hess and lcgp_predict_paramgrad.  float64 only, so
+# u = 2^-53 throughout.  Both leave every intermediate in their scratch (HessLay / PgradLay of lcgp_hip.hip, restated by
+# hess_layout / pgrad_layout), so every stage is checked from the library's own input to it.  The references start from the
+# library's own xs = x / ell (checked bitwise against one IEEE division in check_hess_prep).
+#
+# Evaluation constants, counted from the kernel text (units of u, relative unless stated):
+#   C0 from xs (hess_c0, the row loop of pgrad_row_kernel): kernel_parts' E with the input-rounding term dropped -- xs is an
+#     input here.  What is left: the difference df (one rounding of S_l, weight |d ln C0 / d ln S_l| <= S_l, S_l^2 for SE), the
+#     d - 1 roundings of the exponent, the argument of exp and its ulp, the polynomial, the product:
+#       matern32 (d + 1) sum S + d + 3,   matern52 (d + 1) sum S + 3 d + 3   (kernel_parts' counts),
+#       se: 2 ssum (the differences) + d ssum (the fmas) + ssum + 1 (exp) <= (d + 3) ssum + 3,   ssum = 1/2 sum S^2.
+#   phi (hess_phi), every factor positive, S carries the rounding of df with weight d ln phi / d ln S:
+#       matern32  ie, S2, r = 1 / (1 + S) (2), S2 r ie (2), S (<= 2)                                              8
+#       se        ie, S2, the product, S (2)                                                                      5
+#       matern52  r = 1 / fma(fma) (3), N = S2 (1 + S) (3), N r ie (2), ie, S (<= 3)                             12
+#   d phi (absolute, in units of u):
+#       matern32  S2, fma, r r (5), ie ie (3), three products, S (<= 2)                         15 |dphi|
+#       se        S2, 3 S2, ie ie (3), the product, S (2)                                         8 |dphi|
+#       matern52  dphi = -(A + B) ie^2, A = S2 fma(3, S, 2) r > 0, B = N (3 - S2) r^2 changes sign at S = sqrt(3):
+#                 A: S2, fma, r (4), two products, S (<= 3), the sum, ie ie and its product (4)        16 A ie^2
+#                 B: N (3), its S (<= 3), r r (9) and its S (<= 4), 3 - S2 (absolute: 4 u (3 + S2)), two products, the
+#                 sum, ie ie (4): 30 relative to N (3 + S2) r^2 -- the cancellation in 3 - S2 is not charged to B
+#   d_iA = (D scale / (1 + nug)) (s_a s_b) C0 phi_i: the coefficient (3), s_a s_b, three products: E0 + PHI + 7.
+# ----------------------------------------------------------------------------------------------------------------------
+HS_B, HS_SLOTS, HS_JC, PP_DB = 4, 22, 8, 16            # lcgp_hip.hip
+PHI_ROUND = {"matern32": 8.0, "se": 5.0, "matern52": 12.0}
+DA_ROUND = 7.0
+FLOOR_LOG = None          # a list while a test counts the entries whose bound the absolute floor sets: (stage, floored, entries)
+_U64 = 2.0 ** -53
+
+
+def gamma(k) -> float:
+    """gamma_k = k u / (1 - k u) of the module docstring, u = 2^-53"""
+    return k * _U64 / (1.0 - k * _U64)
+
+
+def _align256(o) -> int:
+    return (int(o) + 255) // 256 * 256
+
+
+def _carve(sizes):
+    """offsets in doubles, in order, each aligned to 256 bytes; 'total' in bytes"""
+    lay, o = {}, 0
+    for name, count in sizes:
+        lay[name] = o // 8
+        o = _align256(o + 8 * int(count))
+    lay["total"] = o
+    return lay
+
+
+def hess_layout(n, d, p, qg):
+    """hess_carve of lcgp_hip.hip: the element offsets of AI, E, G, xs, yv, uv, YP, Q, tp, cp, dot in the scratch of
+    lcgp_nll_hess (doubles) and `total` in bytes (= lcgp_nll_hess_scratch_bytes)"""
+    m, npad, ppad = d + 2, _pad128(n), _pad128(p)
+    nb, nbk = npad // TS, -(-d // HS_B)
+    npair, npb, mat = m * (m + 1) // 2, nbk * (nbk + 1) // 2, npad * npad
+    lay = _carve([("ai", qg * mat), ("e", qg * mat), ("g", qg * m * mat), ("xs", qg * d * npad), ("yv", qg * m * npad),
+                  ("uv", qg * m * npad), ("yp", ppad * npad), ("q", qg * ppad * npad), ("tp", qg * npair * nb),
+                  ("cp", qg * npb * nb * HS_SLOTS), ("dot", qg * m * m)])
+    lay.update(m=m, npad=npad, ppad=ppad, nb=nb, npair=npair, npb=npb, mat=mat)
+    return lay
+
+
+def pgrad_layout(n, d, p, qg, n0):
+    """pgrad_carve of lcgp_hip.hip: X (then V), U (then T_j), E, xs, yv, YT, VY, rd, sums of lcgp_predict_paramgrad"""
+    m, npad, ppad, n0p, n0r, nsum = d + 2, _pad128(n), _pad128(p), predict_pad(n0), _pad128(n0), 3 * d + 8
+    lay = _carve([("x", qg * n0r * npad), ("u", qg * n0r * npad), ("e", qg * npad * npad), ("xs", qg * d * npad),
+                  ("yv", qg * m * npad), ("yt", npad * ppad), ("vy", qg * n0r * ppad), ("rd", qg * d * n0r),
+                  ("sum", qg * n0r * nsum)])
+    lay.update(m=m, npad=npad, ppad=ppad, n0p=n0p, n0r=n0r, nsum=nsum, nb=npad // TS, mat=npad * npad, slab=n0r * npad)
+    return lay
+
+
+def tri_decode(t):
+    r = int((math.sqrt(8.0 * t + 1.0) - 1.0) * 0.5)
+    while (r + 1) * (r + 2) // 2 <= t:
+        r += 1
+    while r * (r + 1) // 2 > t:
+        r -= 1
+    return r, t - r * (r + 1) // 2
+
+
+def _same_bits(a, b) -> bool:
+    a, b = a.contiguous(), b.contiguous()
+    return a.shape == b.shape and bool(torch.equal(a.view(torch.int64), b.view(torch.int64)))
+
+
+def _zero_bits(a) -> bool:
+    return not bool(a.contiguous().view(torch.int64).any())
+
+
+def _exact(ok, where) -> Check:
+    return Check(0.0 if ok else math.inf, (where,))
+
+
+def _blocks(pos):
+    return tuple(int(v) // TS for v in pos)
+
+
+def _pworst(stage, err, core, k, name=_blocks) -> Check:
+    """worst err / (core + floor(k)) over every entry, located by name(index tuple)"""
+    fl = floor("float64", k)
+    if FLOOR_LOG is not None:
+        FLOOR_LOG.append((stage, int((core < fl).sum()), int(core.numel())))
+    if err.numel() == 0:
+        return Check(0.0, ())
+    r = err / (core + fl)
+    r = torch.where(torch.isnan(r), torch.full_like(r, math.inf), r)
+    idx = int(torch.argmax(r))
+    return Check(float(r.reshape(-1)[idx]), name(np.unravel_index(idx, tuple(r.shape))))
+
+
+def _phi_parts(S, ell, kernel):
+    """phi = d log C0 / d ell, d phi / d ell of one dimension at S = |dx| / ell (hess_phi) and the ABSOLUTE error bounds of
+    the library's evaluation of each in units of u (see the section comment)"""
+    _known(kernel)
+    ie, S2 = 1.0 / ell, S * S
+    if kernel == "matern32":
+        r = 1.0 / (1.0 + S)
+        phi, dphi = S2 * r * ie, -S2 * (2.0 * S + 3.0) * r * r * ie * ie
+        return phi, dphi, PHI_ROUND[kernel] * phi, 15.0 * dphi.abs()
+    if kernel == "se":
+        phi, dphi = S2 * ie, -3.0 * S2 * ie * ie
+        return phi, dphi, PHI_ROUND[kernel] * phi, 8.0 * dphi.abs()
+    r = 1.0 / (S2 + 3.0 * S + 3.0)
+    N = S2 * (1.0 + S)
+    A, B = S2 * (3.0 * S + 2.0) * r, N * (3.0 - S2) * r * r
+    return N * r * ie, -(A + B) * ie * ie, PHI_ROUND[kernel] * N * r * ie, (16.0 * A + 30.0 * N * (3.0 + S2) * r * r) * ie * ie
+
+
+def param_parts(xa, xb, ell, kernel):
+    """C0 (na x nb), its evaluation magnification E0, and per dimension phi, dphi and their absolute error bounds (units of
+    u), all from the SCALED inputs xa (d x na), xb (d x nb) -- the library's x / ell -- in float64 on their device"""
+    _known(kernel)
+    d = xa.shape[0]
+    ssum = torch.zeros(xa.shape[1], xb.shape[1], dtype=torch.float64, device=xa.device)
+    poly = torch.ones_like(ssum)
+    S = []
+    for l in range(d):
+        s = (xa[l][:, None] - xb[l][None, :]).abs()
+        S.append(s)
+        if kernel == "se":
+            ssum += 0.5 * s * s
+        elif kernel == "matern32":
+            ssum += s
+            poly *= 1.0 + s
+        else:
+            ssum += s
+            poly *= 1.0 + s + s * s / 3.0
+    c0 = poly * torch.exp(-ssum)
+    e0 = (d + 3.0) * ssum + 3.0 if kernel == "se" else (d + 1.0) * ssum + (d if kernel == "matern32" else 3.0 * d) + 3.0
+    parts = [_phi_parts(S[l], float(ell[l]), kernel) for l in range(d)]
+    return dict(c0=c0, e0=e0, phi=[q[0] for q in parts], dphi=[q[1] for q in parts], ephi=[q[2] for q in parts],
+                edphi=[q[3] for q in parts])
+
+
+def hess_parts(xs, sr, th, kernel, n):
+    """what the checks of both queries share, from the library's xs (d x npad) of one component: param_parts on the n training
+    inputs, s s^T, the coefficient of d_iA and dA(i) -> (d_iA, its relative evaluation error in units of u), n x n"""
+    xs = _t(xs)
+    d = xs.shape[0]
+    ell, scale, nug, D, _ = split_theta(th, d)
+    R = param_parts(xs[:, :n], xs[:, :n], ell, kernel)
+    s = _t(np.ones(n) if sr is None else np.asarray(sr, np.float64), xs.device)
+    R.update(n=n, d=d, npad=xs.shape[1], s=s, ss=s[:, None] * s[None, :], coef=D * scale / (1.0 + nug), kernel=kernel)
+    R["dA"] = lambda i: (R["coef"] * R["ss"] * R["c0"] * R["phi"][i], R["e0"] + PHI_ROUND[kernel] + DA_ROUND)
+    return R
+
+
+def _padded(a, npad):
+    out = torch.zeros(npad, npad, dtype=torch.float64, device=a.device)
+    out[:a.shape[0], :a.shape[1]] = a
+    return out
+
+
+# ---- lcgp_nll_hess ---------------------------------------------------------------------------------------------------
+def check_hess_prep(xs, yv, x, sr, th, b, z) -> Check:
+    """hess_prep_kernel, from x, sr, theta and the fetched b, z of the component.  xs (d x npad): bitwise x / ell -- one IEEE
+    division, so numpy gives the same bits -- dimension-major, bitwise zero on n .. npad.  yv rows d, d + 1:
+        y_scale = (b - z) / scale: the difference and the quotient, 2 u (|b| + |z|) / scale;
+        y_nug = (D scale s^2 z - (b - z)) / (1 + nug): D scale, s s, two products (4) on T1 = D scale s^2 |z|, the difference
+        b - z (1) on |b| + |z|, then the subtraction, 1 + nug and the quotient (3) on both: u (7 T1 + 4 (|b| + |z|)) / (1 + nug);
+    both bitwise zero on the padding.  Locations: the name of what failed, or (row, 64-block)."""
+    x = np.asarray(x, np.float64)
+    n, d = x.shape
+    ell, scale, nug, D, _ = split_theta(th, d)
+    xs, yv = _t(xs), _t(yv)
+    dev, npad = xs.device, xs.shape[1]
+    want = np.zeros((d, npad))
+    want[:, :n] = (x / ell[None, :]).T
+    if not _same_bits(xs.cpu(), torch.as_tensor(want)):
+        return Check(math.inf, ("xs",))
+    if not _zero_bits(yv[d:, n:]):
+        return Check(math.inf, ("y padding",))
+    bt, zt = _t(b, dev), _t(z, dev)
+    s = _t(np.ones(n) if sr is None else np.asarray(sr, np.float64), dev)
+    bz, mag = bt - zt, bt.abs() + zt.abs()
+    t1 = D * scale * (s * s) * zt
+    ref = torch.stack([bz / scale, (t1 - bz) / (1.0 + nug)])
+    core = C * _U64 * torch.stack([2.0 * mag / scale, (7.0 * t1.abs() + 4.0 * mag) / (1.0 + nug)])
+    return _pworst("hess_prep", (yv[d:, :n] - ref).abs(), core, 1, lambda pos: (("y_scale", "y_nug")[pos[0]], int(pos[1]) // TS))
+
+
+def check_hess_mirror(AI, Gs, Gn, V, sr, th, n, d) -> Check:
+    """hess_mirror_kernel.  AI (npad x npad): bitwise the mirror of the lower triangle of the fetched A^-1 (V, n x n), exactly
+    symmetric, the identity on the padding.  From that AI, entry by entry (v = AI[a, b], dl = delta_ab):
+        G_scale = (dl - v) / scale: two roundings, 2 u (dl + |v|) / scale;
+        G_nug = (fma(c, v, v) - dl) / (1 + nug), c = D scale s_b^2 (three roundings), the fma, the subtraction, 1 + nug, the
+        quotient: at most 7 u (dl + |v| (1 + c)) / (1 + nug) -- on the sum of the absolute terms, which does not shrink where
+        A^-1 is close to I.  s_b is the COLUMN's s (G_nug = A^-1 d_nug A is not symmetric on the rep path).
+    Both bitwise zero on the padding."""
+    AI, Gs, Gn = _t(AI), _t(Gs), _t(Gn)
+    dev, npad = AI.device, AI.shape[0]
+    _, scale, nug, D, _ = split_theta(th, d)
+    v = torch.tril(_t(V, dev))
+    want = torch.eye(npad, dtype=torch.float64, device=dev)
+    want[:n, :n] = v + torch.tril(v, -1).T
+    if not _same_bits(AI, want) or not _same_bits(AI, AI.T):
+        return Check(math.inf, ("AI",))
+    for g in (Gs, Gn):
+        if not (_zero_bits(g[n:, :]) and _zero_bits(g[:, n:])):
+            return Check(math.inf, ("G padding",))
+    v = AI[:n, :n]
+    dl = torch.eye(n, dtype=torch.float64, device=dev)
+    s = _t(np.ones(n) if sr is None else np.asarray(sr, np.float64), dev)
+    c = (D * scale * s * s)[None, :]
+    mag = dl + v.abs() * (1.0 + c)
+    c1 = _pworst("hess_mirror", (Gs[:n, :n] - (dl - v) / scale).abs(), C * 2.0 * _U64 * (dl + v.abs()) / scale, 1,
+                 lambda pos: ("G_scale",) + _blocks(pos))
+    c2 = _pworst("hess_mirror", (Gn[:n, :n] - (c * v + v - dl) / (1.0 + nug)).abs(), C * 7.0 * _U64 * mag / (1.0 + nug), 1,
+                 lambda pos: ("G_nug",) + _blocks(pos))
+    return combine(c1, c2)
+
+
+def check_hess_da(E, R, i) -> Check:
+    """hess_da_kernel: E (npad x npad) = d_iA against coef s s^T o C0 o phi_i from xs, relative error (E0 + PHI + 7) u entry
+    by entry over the FULL matrix; E exactly symmetric (df and -df give the same |df|; s_a s_b commutes) and bitwise zero on
+    the padding.  (Its diagonal is exactly zero -- phi(0) = 0 -- and stands on the floor.)"""
+    E = _t(E)
+    n = R["n"]
+    if not _same_bits(E, E.T):
+        return Check(math.inf, ("E symmetry",))
+    if not (_zero_bits(E[n:, :]) and _zero_bits(E[:, n:])):
+        return Check(math.inf, ("E padding",))
+    ref, e = R["dA"](i)
+    return _pworst("hess_da", (E[:n, :n] - ref).abs(), C * _U64 * e * ref.abs(), 1)
+
+
+def check_hess_y(yv, R, z, stage="hess_y") -> Check:
+    """hess_matvec_kernel over d_iA: every y_i = d_iA z, i < d (yv: m x npad), against the reference d_iA from xs times the
+    fetched z.  n fmas and the butterfly in some order (gamma_n, with the store n + 1) and the evaluation of d_iA:
+        u sum_b (n + 1 + E0 + PHI + 7) |d_iA[a, b]| |z_b|.
+    The rows n .. npad are bitwise zero (the rows of E there are).  Locations: (i, 64-block)."""
+    yv = _t(yv)
+    n, d = R["n"], R["d"]
+    if not _zero_bits(yv[:d, n:]):
+        return Check(math.inf, ("y padding",))
+    zt = _t(z, yv.device)
+    err, core = [], []
+    for i in range(d):
+        ref, e = R["dA"](i)
+        err.append((yv[i, :n] - ref @ zt).abs())
+        core.append(C * _U64 * (((n + 1.0) + e) * ref.abs()) @ zt.abs())
+    return _pworst(stage, torch.stack(err), torch.stack(core), n, lambda pos: (int(pos[0]), int(pos[1]) // TS))
+
+
+def check_hess_g(G, AI, E, R) -> Check:
+    """OP_HESS_G: G_i = AI d_iA, i < d (G: >= d matrices npad x npad), entry by entry over the FULL matrix -- G is not symmetric.
+    For i = d - 1 the operand is the fetched E (what the buffer holds after the call) and the bound is the product's alone,
+    gamma_{n+1} |AI| |E| (the zero padding adds nothing, in any order of the k loop); for i < d - 1 the operand is the
+    reference d_iA from xs and its evaluation error goes through |AI|: + u |AI| ((E0 + PHI + 7) |d_iA|).  The padding rows and
+    columns are bitwise zero.  Locations: (i, row block, column block)."""
+    G, AI, E = _t(G), _t(AI), _t(E)
+    n, d, npad = R["n"], R["d"], R["npad"]
+    worst_c = Check(0.0, ())
+    aa = AI.abs()
+    for i in range(d):
+        if not (_zero_bits(G[i][n:, :]) and _zero_bits(G[i][:, n:])):
+            return Check(math.inf, ("G padding", i))
+        if i == d - 1:
+            op, extra = E, None
+        else:
+            ref, e = R["dA"](i)
+            op, extra = _padded(ref, npad), _padded(e * ref.abs(), npad)
+        core = C * gamma(n + 1.0) * (aa @ op.abs())
+        if extra is not None:
+            core = core + C * _U64 * (aa @ extra)
+        c = _pworst("hess_g", (G[i][:n, :n] - (AI @ op)[:n, :n]).abs(), core[:n, :n], n, lambda pos: (i,) + _blocks(pos))
+        worst_c = combine(worst_c, c)
+    return worst_c
+
+
+def check_hess_trace(tp, G, n) -> Check:
+    """hess_trace_kernel: every tp[pair(i, j <= i)][rb] = sum_{a in band rb} sum_b G_i[a, b] G_j[b, a] from the fetched G (all
+    m matrices), pair(i, j) = i (i + 1) / 2 + j.  64 npad fmas and the workgroup sum in some order:
+        gamma_{64 npad} sum_{a in rb, b} |G_i[a, b]| |G_j[b, a]|.
+    A band entirely past n is exactly zero.  Locations: (i, j, rb)."""
+    tp, G = _t(tp), _t(G)
+    m, npad = G.shape[0], G.shape[1]
+    nb, nlive = npad // TS, -(-n // TS)
+    worst_c = Check(0.0, ())
+    for i in range(m):
+        prod = G[:i + 1].transpose(1, 2) * G[i][None]                     # [j, a, b] = G_i[a, b] G_j[b, a]
+        ref = prod.reshape(i + 1, nb, TS * npad).sum(dim=2)
+        ab = prod.abs().reshape(i + 1, nb, TS * npad).sum(dim=2)
+        got = tp[i * (i + 1) // 2:i * (i + 1) // 2 + i + 1]
+        if bool((got[:, nlive:] != 0).any()):
+            return Check(math.inf, ("trace padding band", i))
+        c = _pworst("hess_trace", (got - ref).abs()[:, :nlive], C * gamma(64.0 * npad) * ab[:, :nlive], 64 * npad,
+                    lambda pos: (i, int(pos[0]), int(pos[1])))
+        worst_c = combine(worst_c, c)
+    return worst_c
+
+
+def _bands(M, nb):
+    """sums over the 64-row bands of an n x n matrix -> nb values (the bands past n are zero)"""
+    out = torch.zeros(nb * TS, dtype=torch.float64, device=M.device)
+    out[:M.shape[0]] = M.sum(dim=1)
+    return out.reshape(nb, TS).sum(dim=1)
+
+
+def check_hess_contract(cp, AI, R, z, th) -> Check:
+    """hess_contract_kernel: the slots of cp (npb x nb x 22) per block pair pb = (bi, bj <= bi) and band rb, from AI, xs, the
+    fetched z, sr and theta.  With g = s_a s_b (D/2 AI - z_a z_b / 2), |g|_abs = s_a s_b (D/2 |AI| + |z_a z_b| / 2) (the
+    product s_a s_b, D/2 AI, z_a z_b, the subtraction: 4), w0 = g C0 (E0 + 1) and K = 64 n + 8 (the 64 n fmas of a band and
+    the workgroup sum in some order, the 4 + 1 of w0, the product / fma of k2 and the fma into the accumulator):
+        slot ii 4 + jj, i = 4 bi + ii, j = 4 bj + jj < d:   sum w0 (phi_i phi_j + [i = j] dphi_i)
+            u sum |g|_abs C0 [ (K + E0) |phi_i phi_j| + ephi_i |phi_j| + |phi_i| ephi_j + [i = j] ((K + E0) |dphi_i| + edphi_i) ]
+        slot 16 + ii (bj = 0, what hess_final_kernel reads), slot 20 (pb = 0): sum w0 phi_i, sum w0, likewise
+        slot 21 (pb = 0): trace g, K u sum |g|_abs on the diagonal.
+    On the diagonal block pair the slots jj > ii, which hess_final_kernel does not read, are checked all the same.  The
+    second-order slots of a dimension past d are bitwise +0.  Locations: (pb, slot, rb)."""
+    cp, AI = _t(cp), _t(AI)
+    n, d, dev = R["n"], R["d"], AI.device
+    _, scale, nug, D, _ = split_theta(th, d)
+    npb, nb = cp.shape[0], cp.shape[1]
+    nlive = -(-n // TS)
+    zt = _t(z, dev)
+    zz = zt[:, None] * zt[None, :]
+    g = R["ss"] * (0.5 * D * AI[:n, :n] - 0.5 * zz)
+    gabs = R["ss"] * (0.5 * D * AI[:n, :n].abs() + 0.5 * zz.abs())
+    W0 = gabs * R["c0"]
+    w0 = g * R["c0"]
+    K = 64.0 * n + 8.0
+    ke = K + R["e0"]
+    phi, dphi, ephi, edphi = R["phi"], R["dphi"], R["ephi"], R["edphi"]
+    refs, cores, names = [], [], []
+    for pb in range(npb):
+        bi, bj = tri_decode(pb)
+        for ii in range(HS_B):
+            for jj in range(HS_B):
+                li, lj, slot = bi * HS_B + ii, bj * HS_B + jj, ii * HS_B + jj
+                if li >= d or lj >= d:
+                    if not _zero_bits(cp[pb, :, slot]):
+                        return Check(math.inf, ("slot past d", pb, slot))
+                    continue
+                t = phi[li] * phi[lj]
+                val, mag = t, ke * t.abs() + ephi[li] * phi[lj].abs() + phi[li].abs() * ephi[lj]
+                if li == lj:
+                    val, mag = t + dphi[li], mag + ke * dphi[li].abs() + edphi[li]
+                refs.append(_bands(w0 * val, nb))
+                cores.append(_bands(W0 * mag, nb))
+                names.append((pb, slot))
+        if bj == 0:
+            for ii in range(HS_B):
+                li = bi * HS_B + ii
+                if li < d:
+                    refs.append(_bands(w0 * phi[li], nb))
+                    cores.append(_bands(W0 * (ke * phi[li].abs() + ephi[li]), nb))
+                    names.append((pb, 16 + ii))
+        if pb == 0:
+            refs.append(_bands(w0, nb))
+            cores.append(_bands(W0 * ke, nb))
+            names.append((0, 20))
+            refs.append(_bands(torch.diag(torch.diagonal(g)), nb))
+            cores.append(K * _bands(torch.diag(torch.diagonal(gabs)), nb))
+            names.append((0, 21))
+    got = torch.stack([cp[pb, :, slot] for pb, slot in names])
+    if bool((got[:, nlive:] != 0).any()):
+        return Check(math.inf, ("contract padding band",))
+    return _pworst("hess_contract", (got - torch.stack(refs)).abs()[:, :nlive], C * _U64 * torch.stack(cores)[:, :nlive], 64 * n,
+                   lambda pos: names[int(pos[0])] + (int(pos[1]),))
+
+
+def check_hess_vectors(uv, dot, YP, Q, AI, yv, Y, n) -> Check:
+    """u_i = AI y_i for all m vectors (hess_matvec_kernel; gamma_{n+1} |AI| |y_i|, all npad rows), the m^2 dot[i, j] = y_i . u_j
+    (hess_dot_kernel; gamma_{n+1} |y_i| . |u_j|), YP bitwise Y zero padded to ppad x npad (hess_pack_y_kernel) and Q = YP AI
+    entry by entry (OP_HESS_G; gamma_{n+1} |YP| |AI|), each from the fetched operands.  Locations: (what, ...)."""
+    uv, dot, YP, Q, AI, yv = _t(uv), _t(dot), _t(YP), _t(Q), _t(AI), _t(yv)
+    dev = AI.device
+    Yt = _t(Y, dev)
+    p = Yt.shape[0]
+    want = torch.zeros_like(YP)
+    want[:p, :n] = Yt
+    if not _same_bits(YP, want):
+        return Check(math.inf, ("YP",))
+    if bool((Q[p:, :] != 0).any()) or bool((Q[:, n:] != 0).any()) or bool((uv[:, n:] != 0).any()):
+        return Check(math.inf, ("Q / u padding",))
+    g = C * gamma(n + 1.0)
+    c1 = _pworst("hess_vectors", (uv - yv @ AI.T).abs()[:, :n], g * (yv.abs() @ AI.abs().T)[:, :n], n,
+                 lambda pos: ("u", int(pos[0]), int(pos[1]) // TS))
+    c2 = _pworst("hess_vectors", (dot - yv @ uv.T).abs(), g * (yv.abs() @ uv.abs().T), n,
+                 lambda pos: ("dot", int(pos[0]), int(pos[1])))
+    c3 = _pworst("hess_vectors", (Q - YP @ AI).abs()[:p, :n], g * (YP.abs() @ AI.abs())[:p, :n], n,
+                 lambda pos: ("Q", int(pos[0]), int(pos[1]) // TS))
+    return combine(c1, c2, c3)
+
+
+def hess_final_ref(tp, cp, dot, th, d):
+    """hess_final_kernel term by term in float64 numpy from the fetched tp (npair x nb), cp (npb x nb x 22), dot (m x m):
+    (hk (m x m, lower), the bound's sum of absolute terms |T| (m x m), 1/2 sum_rb |tp| (m x m))"""
+    tp, cp, dot = (np.asarray(_t(a).cpu(), np.float64) for a in (tp, cp, dot))
+    m = d + 2
+    _, scale, nug, D, _ = split_theta(th, d)
+    omw = 1.0 / (1.0 + nug)
+    w1 = omw * omw
+    ssum, sabs = cp.sum(axis=1), np.abs(cp).sum(axis=1)
+    hk, Ta, tra = np.zeros((m, m)), np.zeros((m, m)), np.zeros((m, m))
+    for i in range(m):
+        for j in range(i + 1):
+            if i < d:
+                pb, slot = (i // HS_B) * (i // HS_B + 1) // 2 + j // HS_B, (i % HS_B) * HS_B + j % HS_B
+                T, A = scale * omw * ssum[pb, slot], scale * omw * sabs[pb, slot]
+            elif j < d:
+                pb, slot = (j // HS_B) * (j // HS_B + 1) // 2, 16 + j % HS_B
+                cf = omw if i == d else -scale * w1
+                T, A = cf * ssum[pb, slot], abs(cf) * sabs[pb, slot]
+            else:
+                dd, da = ssum[0, 21] - ssum[0, 20], sabs[0, 21] + sabs[0, 20]
+                cf = 0.0 if i == d else (w1 if j == d else -2.0 * scale * w1 * omw)
+                T, A = cf * dd, abs(cf) * da
+            t = i * (i + 1) // 2 + j
+            hk[i, j] = (T - 0.5 * tp[t].sum()) + dot[i, j] / D
+            Ta[i, j], tra[i, j] = A, 0.5 * np.abs(tp[t]).sum()
+    return hk, Ta, tra
+
+
+def check_hess_out(out_row, YP, uv, Q, b, z, tp, cp, dot, th, n, d, p) -> Check:
+    """the row of `out` of one component, [hk (m x m) | hx (m x p) | hn (p x p)], from the fetched intermediates.
+      hx[i, a] = psi_a (Y_a . u_i) / (2 D) (hess_cross_kernel): the dot product and three roundings,
+          (n + 4) u |psi_a| |Y_a| . |u_i| / (2 D).
+      hn[a, b] = -(delta_ab psi_a Y_a . (b - z) + psi_a psi_b Y_a . (Y_b - Q_b)) / (4 D) (hess_noise_kernel) from YP, Q, b, z: the
+          differences are formed before the products, so the sums of absolute terms are |Y_a| . |Y_b - Q_b| and |Y_a| . |b - z|
+          -- the cancellation of I - A^-1 is not charged; gamma_{n+2} and the five roundings of the combination: n + 6.
+      hk[i, j] (hess_final_kernel) from tp, cp, dot: the band sums are nb roundings each; the coefficient of T at most 9 (omw two,
+          w1 four, the products), the difference of slots 21 and 20 one, T - tr / 2, dot / D and the sum three:
+          u [ (nb + 14) |T|_abs + (nb + 2) 1/2 sum_rb |tp| + 3 |dot| / D ],   |T|_abs = |coefficient| sum_rb |cp slot|.
+      Both triangles of hk are bitwise equal.  Locations: (block, i, j)."""
+    row = _t(out_row).reshape(-1)
+    dev = row.device
+    m = d + 2
+    _, scale, nug, D, psi = split_theta(th, d)
+    hk, hx, hn = row[:m * m].reshape(m, m), row[m * m:m * m + m * p].reshape(m, p), row[m * m + m * p:].reshape(p, p)
+    if not _same_bits(hk, hk.T):
+        return Check(math.inf, ("hk symmetry",))
+    YP, uv, Q = _t(YP, dev)[:p, :n], _t(uv, dev)[:, :n], _t(Q, dev)[:p, :n]
+    ps = _t(psi, dev)
+    c1 = _pworst("hess_out", (hx - (uv @ YP.T) * ps[None, :] / (2.0 * D)).abs(),
+                 C * _U64 * (n + 4.0) * (uv.abs() @ YP.abs().T) * ps.abs()[None, :] / (2.0 * D), n,
+                 lambda pos: ("hx", int(pos[0]), int(pos[1])))
+    bz = _t(b, dev) - _t(z, dev)
+    dif = YP - Q
+    pp = ps[:, None] * ps[None, :]
+    ref = -(torch.diag(ps * (YP @ bz)) + pp * (YP @ dif.T)) / (4.0 * D)
+    core = C * _U64 * (n + 6.0) * (torch.diag(ps.abs() * (YP.abs() @ bz.abs())) + pp.abs() * (YP.abs() @ dif.abs().T)) / (4.0 * D)
+    c2 = _pworst("hess_out", (hn - ref).abs(), core, n, lambda pos: ("hn", int(pos[0]), int(pos[1])))
+    nb = _t(tp).shape[1]
+    kref, Ta, tra = hess_final_ref(tp, cp, dot, th, d)
+    core = C * _U64 * ((nb + 14.0) * Ta + (nb + 2.0) * tra + 3.0 * np.abs(np.asarray(_t(dot).cpu())) / D)
+    il = np.tril_indices(m)
+    c3 = _pworst("hess_out", torch.as_tensor(np.abs(np.asarray(hk.cpu()) - kref)[il]), torch.as_tensor(core[il]), nb,
+                 lambda pos: ("hk", int(il[0][pos[0]]), int(il[1][pos[0]])))
+    return combine(c1, c2, c3)
+
+
+# ---- lcgp_predict_paramgrad --------------------------------------------------------------------------------------------
+# X, U, ghat, gvar, V are bitwise those of lcgp_predict_grad (check_cov_u, check_pgrad_v, check_predict cover them); xs, y_scale,
+# y_nug, E and the y_j go through check_hess_prep, check_hess_da and check_hess_y.
+def check_pp_y(yv, R, z) -> Check:
+    """y_j = d_jA z for every j < d of lcgp_predict_paramgrad: check_hess_y (the same two launches per dimension)"""
+    return check_hess_y(yv, R, z, "pp_y")
+
+
+def check_pp_t(T, V, E, n0, n) -> Check:
+    """the U slab after the call: T_{d-1} = V d_{d-1}A (OP_HESS_G) on the rows < n0, from the fetched V (n0 x >= n) and E:
+    gamma_{n+1} |V| |E|.  Locations: (row block, column block)."""
+    T, V, E = _t(T)[:n0, :n], _t(V)[:n0, :n], _t(E)[:n, :n]
+    return _pworst("pp_t", (T - V @ E).abs(), C * gamma(n + 1.0) * (V.abs() @ E.abs()), n)
+
+
+def check_pp_rowdot(rd, T, V, R, n0) -> Check:
+    """rd[j][i] = V_i (d_jA) V_i^T (pgrad_rowdot_kernel over T_j = V d_jA).  For j = d - 1 from the fetched T and V:
+    gamma_{n+1} |T_i| . |V_i|.  For the other j, whose T_j is overwritten, from V and the reference d_jA of xs: the product and
+    the dot, n + 1 each, and the evaluation of d_jA: u sum_bc |V_ib| (2 n + 2 + E0 + PHI + 7) |d_jA_bc| |V_ic|.
+    Locations: (j, 64-block of i)."""
+    n, d = R["n"], R["d"]
+    rd, V = _t(rd)[:, :n0], _t(V)[:n0, :n]
+    T = _t(T, V.device)[:n0, :n]
+    err, core = [], []
+    for j in range(d):
+        if j == d - 1:
+            ref, bnd = (T * V).sum(dim=1), C * gamma(n + 1.0) * (T.abs() * V.abs()).sum(dim=1)
+        else:
+            dA, e = R["dA"](j)
+            ref = ((V @ dA) * V).sum(dim=1)
+            bnd = C * _U64 * ((V.abs() @ ((2.0 * n + 2.0 + e) * dA.abs())) * V.abs()).sum(dim=1)
+        err.append((rd[j] - ref).abs())
+        core.append(bnd)
+    return _pworst("pp_rowdot", torch.stack(err), torch.stack(core), n * n, lambda pos: (int(pos[0]), int(pos[1]) // TS))
+
+
+def pp_sum_names(d):
+    return ["dz%d" % j for j in range(d)] + ["dv%d" % j for j in range(d)] + ["xz", "xv", "rz", "rv", "vv", "s2vv"] \
+        + ["vy%d" % j for j in range(d)] + ["vy_scale", "vy_nug"]
+
+
+def check_pp_sums(sums, x0, xs, z, V, yv, sr, th, kernel, same, n0, n) -> Check:
+    """pgrad_row_kernel: all 3 d + 8 sums of every row i < n0, [dz_j | dv_j | Xc.z, Xc.v, rz, rv, |v|^2, sum s^2 v^2 | v.y_t],
+    from x0, the library's xs, the fetched z, V (n0 x >= n), yv (m x npad), sr, theta.  x0 / ell is one IEEE division (the same
+    bits here); Xc = (scale / (1 + nug)) C0 s: the coefficient two, C0 E0, two products: E0 + 4.  Every sum is n fmas and the
+    workgroup sum in some order (n + 1 with the store) on the sum of its absolute terms:
+        dz_j, dv_j: Xc phi_j and its product:  (n + 2 + E0 + 4) |Xc phi_j w| + |Xc| ephi_j |w|,   w = z, v
+        Xc.z, Xc.v:  (n + 1 + E0 + 4) |Xc w|;     |v|^2, v.y_t:  n + 1;     sum s^2 v^2:  n + 3 (s s, its product with v)
+        rz, rv: ONE rounding of s z, s v at c* = i + same - 1 (the other 255 threads add exact zeros), and exactly 0 with same = 0.
+    Locations: (name of the sum, 64-block of i)."""
+    sums, V, yv, xs = _t(sums)[:n0], _t(V)[:n0, :n], _t(yv)[:, :n], _t(xs)[:, :n]
+    dev = sums.device
+    x0 = np.asarray(x0, np.float64)
+    d = x0.shape[1]
+    ell, scale, nug, D, _ = split_theta(th, d)
+    P = param_parts(_t((x0 / ell[None, :]).T.copy(), dev), xs, ell, kernel)
+    s = _t(np.ones(n) if sr is None else np.asarray(sr, np.float64), dev)
+    zt = _t(z, dev)
+    xc = (scale / (1.0 + nug)) * P["c0"] * s[None, :]
+    ex = P["e0"] + 4.0
+    za, va = zt.abs()[None, :], V.abs()
+    ref, core = [], []
+    for w, wa in ((zt[None, :], za), (V, va)):
+        for j in range(d):
+            t = xc * P["phi"][j]
+            ref.append((t * w).sum(dim=1))
+            core.append((((n + 2.0) + ex) * t.abs() * wa + xc.abs() * P["ephi"][j] * wa).sum(dim=1))
+    for w, wa in ((zt[None, :], za), (V, va)):
+        ref.append((xc * w).sum(dim=1))
+        core.append((((n + 1.0) + ex) * xc.abs() * wa).sum(dim=1))
+    rz, rv = torch.zeros(n0, dtype=torch.float64, device=dev), torch.zeros(n0, dtype=torch.float64, device=dev)
+    if same > 0:
+        cs = torch.arange(n0, device=dev) + same - 1
+        rz, rv = s[cs] * zt[cs], s[cs] * V[torch.arange(n0, device=dev), cs]
+    ref += [rz, rv, (V * V).sum(dim=1), (s * s * V * V).sum(dim=1)]
+    core += [rz.abs(), rv.abs(), (n + 1.0) * (V * V).sum(dim=1), (n + 3.0) * (s * s * V * V).sum(dim=1)]
+    ref += [(V * yv[j][None, :]).sum(dim=1) for j in range(d + 2)]
+    core += [(n + 1.0) * (va * yv[j].abs()[None, :]).sum(dim=1) for j in range(d + 2)]
+    ref, core = torch.stack(ref, dim=1), C * _U64 * torch.stack(core, dim=1)
+    if same <= 0 and not _zero_bits(sums[:, 2 * d + 2:2 * d + 4]):
+        return Check(math.inf, ("rz / rv with same = 0",))
+    names = pp_sum_names(d)
+    keep = [c for c in range(3 * d + 8) if same > 0 or c not in (2 * d + 2, 2 * d + 3)]
+    return _pworst("pp_sums", (sums - ref).abs()[:, keep], core[:, keep], n, lambda pos: (names[keep[int(pos[1])]], int(pos[0]) // TS))
+
+
+def check_pp_vy(YT, VY, V, Y, n0, n) -> Check:
+    """YT bitwise Y^T zero padded to npad x ppad (pgrad_pack_yt_kernel) and VY = V YT on the rows < n0 and columns < p
+    (OP_HESS_G): gamma_{n+1} |V| |YT|.  Locations: (row block, column block)."""
+    YT, VY, V = _t(YT), _t(VY), _t(V)[:n0, :n]
+    Yt = _t(Y, YT.device)
+    p = Yt.shape[0]
+    want = torch.zeros_like(YT)
+    want[:n, :p] = Yt.T
+    if not _same_bits(YT, want):
+        return Check(math.inf, ("YT",))
+    return _pworst("pp_vy", (VY[:n0, :p] - V @ YT[:n, :p]).abs(), C * gamma(n + 1.0) * (V.abs() @ YT[:n, :p].abs()), n)
+
+
+def check_pp_out(dghat, dgvar, dnoise, sums, rd, VY, th, d, p, n0) -> Check:
+    """pgrad_final_kernel term by term from the fetched sums (n0 x nsum), rd (d x >= n0), VY (>= n0 x >= p); omw = 1 / (1 + nug)
+    (two roundings), nt = nug omw (3), w1 = omw^2 (5); X.w = fma(scale nt, r_w, Xc.w) (5 on the nugget term):
+        dghat_j = dz_j - v.y_j:                          u (|dz_j| + |v.y_j|)
+        dgvar_j = -D (2 dv_j - rd_j):                    2 u D (2 |dv_j| + |rd_j|)
+        dghat_scale = X.z / scale - v.y_scale:           8 u (|X.z|_abs / scale + |v.y_scale|)
+        dgvar_scale = 1 - D (X.v + |v|^2) / scale:       9 u (1 + D (|X.v|_abs + |v|^2) / scale)
+        dghat_nug = fma(scale w1, rz, -Xc.z omw) - v.y_nug:          8 u (|scale w1 rz| + |Xc.z omw| + |v.y_nug|)
+        dgvar_nug = -D (2 A - B omw), A = fma(scale w1, rv, -Xc.v omw), B = D scale s2vv - (X.v - |v|^2):
+                                                         13 u D (2 |A|_abs + (D scale |s2vv| + |X.v|_abs + |v|^2) omw)
+        dghat_noise_a = -psi_a VY_a / 2:                 2 u |psi_a VY_a| / 2
+    with C = 4 on top.  Locations: (output, column, 64-block of i)."""
+    sums = _t(sums)[:n0]
+    dev = sums.device
+    m = d + 2
+    _, scale, nug, D, psi = split_theta(th, d)
+    omw = 1.0 / (1.0 + nug)
+    nt, w1 = nug * omw, omw * omw
+    rd, VY = _t(rd, dev)[:, :n0].T, _t(VY, dev)[:n0, :p]
+    dg, dv, dn = _t(dghat, dev).reshape(n0, m), _t(dgvar, dev).reshape(n0, m), _t(dnoise, dev).reshape(n0, p)
+    dz, dvs, vy = sums[:, :d], sums[:, d:2 * d], sums[:, 2 * d + 6:3 * d + 6]
+    xcz, xcv, rz, rv, vv, s2vv = (sums[:, 2 * d + c] for c in range(6))
+    vys, vyn = sums[:, 3 * d + 6], sums[:, 3 * d + 7]
+    xz, xv = scale * nt * rz + xcz, scale * nt * rv + xcv
+    xza, xva = abs(scale * nt) * rz.abs() + xcz.abs(), abs(scale * nt) * rv.abs() + xcv.abs()
+    A = scale * w1 * rv - xcv * omw
+    Aa = abs(scale * w1) * rv.abs() + xcv.abs() * omw
+    rg = torch.cat([dz - vy, (xz / scale - vys)[:, None], (scale * w1 * rz - xcz * omw - vyn)[:, None]], dim=1)
+    cg = torch.cat([dz.abs() + vy.abs(), 8.0 * (xza / scale + vys.abs())[:, None],
+                    8.0 * (abs(scale * w1) * rz.abs() + xcz.abs() * omw + vyn.abs())[:, None]], dim=1)
+    rv_ = torch.cat([-D * (2.0 * dvs - rd), (1.0 - D * (xv + vv) / scale)[:, None],
+                     (-D * (2.0 * A - (D * scale * s2vv - (xv - vv)) * omw))[:, None]], dim=1)
+    cv = torch.cat([2.0 * D * (2.0 * dvs.abs() + rd.abs()), 9.0 * (1.0 + D * (xva + vv.abs()) / scale)[:, None],
+                    13.0 * D * (2.0 * Aa + (D * scale * s2vv.abs() + xva + vv.abs()) * omw)[:, None]], dim=1)
+    ps = _t(psi, dev)
+    c1 = _pworst("pp_out", (dg - rg).abs(), C * _U64 * cg, 1, lambda pos: ("dghat", int(pos[1]), int(pos[0]) // TS))
+    c2 = _pworst("pp_out", (dv - rv_).abs(), C * _U64 * cv, 1, lambda pos: ("dgvar", int(pos[1]), int(pos[0]) // TS))
+    c3 = _pworst("pp_out", (dn + 0.5 * ps[None, :] * VY).abs(), C * _U64 * 2.0 * (0.5 * ps[None, :] * VY).abs(), 1,
+                 lambda pos: ("dghat_noise", int(pos[1]), int(pos[0]) // TS))
+    return combine(c1, c2, c3)

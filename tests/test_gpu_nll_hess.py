@@ -3,7 +3,9 @@ autograd reference of tests/nll_hess_ref.py (tied to the oracle by tests/test_nl
 
 Accuracy bound: 10 x max(eps_ref, 1e-12) = 1e-11 of the largest entry per block type, eps_ref ~ 2e-15 being the deviation of the
 CPU closed form from autograd (tests/test_nll_hess_host.py) and the factor 10 covering the different summation order of tiles.
-Observed on the MI355X (first run, the shapes below): kernel blocks <= 2.1e-15, border <= 6.6e-15, noise corner <= 8.6e-16."""
+Observed on the MI355X (first run, the shapes below): kernel blocks <= 2.1e-15, border <= 6.6e-15, noise corner <= 8.6e-16.
+The cases at d = 5 and d = 9 tie the block-pair and chunk arithmetic that d <= 2 never reaches end to end; entry by entry it is
+checked stage-wise in tests/test_gpu_param_bounds.py."""
 import ctypes as C
 import os
 import socket
@@ -28,7 +30,9 @@ Q = 3
 # (mode, kernel, n, d, diag_error_structure): n = 200 ragged last 64-tile; 128 exact tiles; 330 crosses a 128-tile edge
 CASES = [('full', 'matern32', 200, 2, None), ('full', 'se', 200, 2, None), ('full', 'matern52', 200, 2, None),
          ('rep', 'matern32', 200, 2, None), ('full', 'matern32', 128, 2, None), ('full', 'matern32', 330, 2, None),
-         ('full', 'matern32', 200, 1, None), ('full', 'matern32', 200, 2, [1, 3])]
+         ('full', 'matern32', 200, 1, None), ('full', 'matern32', 200, 2, [1, 3]),
+         # two and three blocks of four dimensions, m = d + 2 = 7 and 11 (two chunks of j in the trace reduction)
+         ('full', 'matern52', 130, 5, None), ('rep', 'se', 130, 9, None)]
 _cache = {}
 
 

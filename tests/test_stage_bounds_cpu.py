@@ -41,9 +41,18 @@ shares its series, switches and closed forms with the kernel -- meets the table 
 switch.  A wrong Matern-5/2 coefficient, ten series terms, the near-branch formula (erf differences for SE) in the far tail, a
 padding column that is not 1, the table row of the next dimension or component, a stale table chunk, x0 read under the mask, a
 prior left at scale or with the nugget, I2 of the wrong dimension or T_i . T_r dropped in gcov and float32-accurate rows each fail
-their stage.  Small table entries or one far tile of masked rows off by 1e-9, invisible to the normwise 1e-10, fail theirs."""
+their stage.  Small table entries or one far tile of masked rows off by 1e-9, invisible to the normwise 1e-10, fail theirs.
+
+The two parameter-space queries (lcgp_nll_hess, lcgp_predict_paramgrad) are emulated stage by stage in float64, every buffer of
+their scratch layouts, in the kernels' blocked order (4 x 4 dimension block pairs, HS_JC chunks of j, 64-bands, PP_DB blocks): the
+three kernels, full and rep, pass every check at d = 3 and d = 9 with at most 1 % of the bounds of any stage set by the floor, and
+the final outputs agree with the closed forms of tests/test_nll_hess_host.py (tied there to tests/nll_hess_ref.py) and
+tests/param_grad_ref.py at those files' bars.  Eleven defects of the Hessian path and six of the parameter-gradient path each fail
+the stage they belong to and none upstream; one ell-ell entry of hk and one small dgvar column off by 1e-6 relative pass today's
+normwise bars (1e-11, 1e-10) and fail check_hess_out / check_pp_out."""
 import numpy as np
 import pytest
+import scipy.linalg
 import torch
 
 from tests import stage_bounds as sb
@@ -2212,3 +2221,480 @@ def test_marginal_gap_small_table_entries_and_a_far_tile_are_invisible_normwise(
     assert eh < 1e-10 and ev < 1e-10
     c = sb.check_marg_cross(X, e["tab"], p["x0"], p["mask"], p["x"], p["sr"], p["th"][k], "matern32", "float64")
     assert c.ratio > 1.0 and c.where == (0, (MG_N - 1) // TS), c
+
+
+# ======================================================================================================================
+# the two parameter-space queries (lcgp_nll_hess, lcgp_predict_paramgrad), emulated stage by stage in float64: each stage from
+# the previous stage's stored result, in the kernels' blocked order (4 x 4 dimension block pairs, HS_JC chunks of j, 64-bands,
+# PP_DB blocks of dimensions).  n = 150: npad = 256, four bands, the third ragged, the fourth all padding.
+# ======================================================================================================================
+PH_N, PH_P, PH_N0 = 150, 3, 70
+PH_STAGES = ("hess_prep", "hess_mirror", "hess_da", "hess_y", "hess_g", "hess_trace", "hess_contract", "hess_vectors", "hess_out")
+PP_STAGES = ("hess_prep", "hess_da", "pp_y", "pp_t", "pp_rowdot", "pp_sums", "pp_vy", "pp_out")
+_PH_CACHE = {}
+
+
+def _ph_problem(d, kernel="matern32", rep=False, seed=21, n=PH_N):
+    """x in the unit box; lengthscales sqrt(d) exp(U(-1, 0.3)): sum_l S_l stays below ~10, so C0 is far from the cut-off and
+    from underflow and the only entries whose bound the floor sets are exact zeros (the diagonal of d_iA: phi(0) = 0).  D in
+    (0.2, 2): cond(A) <= 1 + D scale sum s^2 stays near that of the problems of the host files whose bars the ties below use"""
+    key = (d, kernel, rep, seed, n)
+    if key not in _PH_CACHE:
+        rng = np.random.default_rng(seed + d)
+        x, Y = rng.uniform(0.0, 1.0, (n, d)), rng.standard_normal((PH_P, n))
+        sr = np.sqrt(rng.integers(1, 6, n).astype(np.float64)) if rep else None
+        th = np.zeros((2, d + 3 + PH_P))
+        for k in range(2):
+            th[k, :d] = np.sqrt(d) * np.exp(rng.uniform(-1.0, 0.3, d))
+            th[k, d:d + 3] = rng.uniform(0.5, 2.0), 10.0 ** rng.uniform(-4.0, -2.0), rng.uniform(0.2, 2.0)
+            th[k, d + 3:] = rng.standard_normal(PH_P) / np.sqrt(PH_P)
+        x0 = rng.uniform(-0.1, 1.1, (PH_N0, d))
+        x0[:3] = x[:3]
+        _PH_CACHE[key] = dict(x=x, Y=Y, sr=sr, th=th, kernel=kernel, n=n, d=d, p=PH_P, x0=x0, fit={})
+    return _PH_CACHE[key]
+
+
+def _ph_phi(S, ell, kernel):
+    """hess_phi of lcgp_hip.hip"""
+    ie, S2 = 1.0 / ell, S * S
+    if kernel == "matern32":
+        r = 1.0 / (1.0 + S)
+        return S2 * r * ie, -S2 * (2.0 * S + 3.0) * (r * r) * (ie * ie)
+    if kernel == "se":
+        return S2 * ie, -3.0 * S2 * (ie * ie)
+    assert kernel == "matern52"
+    r = 1.0 / (S * S + (3.0 * S + 3.0))
+    N = S2 * (1.0 + S)
+    return N * r * ie, -(S2 * (3.0 * S + 2.0) * r + N * (3.0 - S2) * (r * r)) * (ie * ie)
+
+
+def _ph_c0(xa, xb, kernel):
+    """hess_c0 / the row loop of pgrad_row_kernel: C0 from scaled inputs (d x na), (d x nb)"""
+    poly, ssum = np.ones((xa.shape[1], xb.shape[1])), np.zeros((xa.shape[1], xb.shape[1]))
+    for l in range(xa.shape[0]):
+        df = xa[l][:, None] - xb[l][None, :]
+        sd = np.abs(df)
+        if kernel == "matern32":
+            poly, ssum = poly * sd + poly, ssum - sd
+        elif kernel == "se":
+            ssum = -0.5 * df * df + ssum
+        else:
+            poly, ssum = poly * (sd * (1.0 / 3.0) * sd + sd) + poly, ssum - sd
+    return np.exp(ssum) if kernel == "se" else poly * np.exp(ssum)
+
+
+def _ph_fit(P, k):
+    """the workspace of component k: A^-1 as the library stores it (lower triangle written, the upper one not), its fetched
+    (mirrored) form, b and z"""
+    if k not in P["fit"]:
+        n, d = P["n"], P["d"]
+        ell, scale, nug, D, psi = sb.split_theta(P["th"][k], d)
+        s = np.ones(n) if P["sr"] is None else P["sr"]
+        xs = (P["x"] / ell[None, :]).T
+        nt = nug / (1.0 + nug)
+        A = np.eye(n) + D * scale * np.outer(s, s) * ((1.0 - nt) * _ph_c0(xs, xs, P["kernel"]) + nt * np.eye(n))
+        low = np.tril(scipy.linalg.cho_solve((np.linalg.cholesky(A), True), np.eye(n)))
+        V = low + np.tril(low, -1).T
+        raw = low + np.triu(np.random.default_rng(5).standard_normal((n, n)), 1)
+        b = P["Y"].T @ psi
+        P["fit"][k] = dict(V=V, raw=raw, b=b, z=V @ b)
+    return P["fit"][k]
+
+
+def _ph_prep(P, k, npad, bug=None):
+    n, d = P["n"], P["d"]
+    f = _ph_fit(P, k)
+    ell, scale, nug, D, _ = sb.split_theta(P["th"][k], d)
+    s = np.ones(n) if P["sr"] is None else P["sr"]
+    xs, yv = np.zeros((d, npad)), np.zeros((d + 2, npad))
+    xs[:, :n] = (P["x"] / ell[None, :]).T
+    bz = f["b"] - f["z"]
+    yv[d, :n] = bz / scale
+    yv[d + 1, :n] = (D * scale * (1.0 if bug == "ynug_no_s2" else s * s) * f["z"] - bz) / (1.0 + nug)
+    return xs, yv
+
+
+def _ph_da(P, k, xs, i):
+    """hess_da_kernel: d_iA as a full npad x npad matrix, zero on the padding"""
+    n, d, npad = P["n"], P["d"], xs.shape[1]
+    ell, scale, nug, D, _ = sb.split_theta(P["th"][k], d)
+    s = np.ones(n) if P["sr"] is None else P["sr"]
+    E = np.zeros((npad, npad))
+    phi = _ph_phi(np.abs(xs[i, :n, None] - xs[i, None, :n]), ell[i], P["kernel"])[0]
+    E[:n, :n] = (D * scale / (1.0 + nug)) * np.outer(s, s) * _ph_c0(xs[:, :n], xs[:, :n], P["kernel"]) * phi
+    return E
+
+
+def _ph_final(tp, cp, dot, th, d, bug=None):
+    """hess_final_kernel"""
+    m, B = d + 2, sb.HS_B
+    _, scale, nug, D, _ = sb.split_theta(th, d)
+    omw = 1.0 / (1.0 + nug)
+    w1 = 1.0 / ((1.0 + nug) * (1.0 + nug))
+    slot_sum = lambda pb, slot: cp[pb, :, slot].sum()
+    hk = np.zeros((m, m))
+    for i in range(m):
+        for j in range(i + 1):
+            if i < d:
+                bi, bj = i // B, j // B
+                T = scale * omw * slot_sum(bi * (bi + 1) // 2 + bj, (i % B) * B + j % B)
+            elif j < d:
+                bj = j // B
+                s1 = slot_sum(bj if bug == "first_order_pair_bj" else bj * (bj + 1) // 2, 16 + j % B)
+                T = omw * s1 if i == d else -scale * w1 * s1
+            else:
+                dd = slot_sum(0, 21) - slot_sum(0, 20)
+                T = 0.0 if i == d else (w1 * dd if j == d else -2.0 * scale * w1 * omw * dd)
+            hk[i, j] = hk[j, i] = (T - 0.5 * tp[i * (i + 1) // 2 + j].sum()) + dot[i, j] / D
+    return hk
+
+
+def _ph_emulate(P, k, bug=None):
+    """lcgp_nll_hess on component k: every buffer of HessLay and the row of `out`.  `bug` plants one defect"""
+    n, d, p, kernel = P["n"], P["d"], P["p"], P["kernel"]
+    th = P["th"][k]
+    ell, scale, nug, D, psi = sb.split_theta(th, d)
+    L = sb.hess_layout(n, d, p, 1)
+    m, npad, nb, ppad, npair, npb = L["m"], L["npad"], L["nb"], L["ppad"], L["npair"], L["npb"]
+    f = _ph_fit(P, k)
+    s = np.ones(n) if P["sr"] is None else P["sr"]
+    spad = np.ones(npad)
+    spad[:n] = s
+    xs, yv = _ph_prep(P, k, npad, bug)
+    # hess_mirror_kernel
+    AI = np.eye(npad)
+    raw = f["raw"]
+    AI[:n, :n] = np.triu(raw) + np.triu(raw, 1).T if bug == "mirror_upper" else np.tril(raw) + np.tril(raw, -1).T
+    G = np.zeros((m, npad, npad))
+    v, dl = AI[:n, :n], np.eye(n)
+    G[d][:n, :n] = (dl - v) / scale
+    c = D * scale * (s * s)
+    G[d + 1][:n, :n] = ((c[:, None] if bug == "gnug_sa" else c[None, :]) * v + v - dl) / (1.0 + nug)
+    # per dimension: d_iA, y_i, G_i
+    for i in range(d):
+        E = _ph_da(P, k, xs, i)
+        yv[i] = E @ np.concatenate([f["z"], np.zeros(npad - n)])
+        G[i] = AI @ E
+    # hess_trace_kernel: one workgroup per (band, i, chunk of HS_JC values of j)
+    tp = np.full((npair, nb), np.nan)
+    njc, late = -(-m // sb.HS_JC), []
+    for i in range(m):
+        for jc in range(njc):
+            j0 = jc * sb.HS_JC
+            if j0 > i:
+                continue
+            for jj in range(sb.HS_JC):
+                j = j0 + jj
+                if j >= m or not (j <= i or (bug == "chunk2_all" and jc > 0)):
+                    continue
+                vals = (G[i] * G[j].T).reshape(nb, TS * npad).sum(axis=1)
+                idx = i * m + j if bug == "pair_im" else i * (i + 1) // 2 + j
+                if j > i:
+                    late.append((idx, vals))
+                elif idx < npair:
+                    tp[idx] = vals
+    for idx, vals in late:
+        if idx < npair:
+            tp[idx] = vals
+    # hess_contract_kernel: one workgroup per (band, block pair)
+    lim = npad if bug == "band_past_n" else n
+    zp = np.concatenate([f["z"], np.zeros(npad - n)])[:lim]
+    g = np.outer(spad[:lim], spad[:lim]) * (0.5 * D * AI[:lim, :lim] - 0.5 * np.outer(zp, zp))
+    w0 = g * _ph_c0(xs[:, :lim], xs[:, :lim], kernel)
+    ph = [_ph_phi(np.abs(xs[l, :lim, None] - xs[l, None, :lim]), ell[l], kernel) for l in range(d)]
+    if bug == "dphi_m32":
+        ph = [(ph[l][0], _ph_phi(np.abs(xs[l, :lim, None] - xs[l, None, :lim]), ell[l], "matern32")[1]) for l in range(d)]
+
+    def bands(M):
+        out = np.zeros(npad)
+        out[:lim] = M.sum(axis=1)
+        return out.reshape(nb, TS).sum(axis=1)
+
+    cp = np.full((npb, nb, sb.HS_SLOTS), np.nan)
+    B = sb.HS_B
+    for pb in range(npb):
+        bi, bj = sb.tri_decode(pb)
+        for ii in range(B):
+            li = bi * B + ii
+            pi = ph[li][0] if li < d else 0.0
+            cp[pb, :, 16 + ii] = bands(w0 * pi)
+            for jj in range(B):
+                lj = bj * B + jj
+                pj = ph[lj][0] if lj < d else 0.0
+                k2 = pi * pj
+                if li < d and ii == jj and (bi == bj or bug == "dphi_offdiag"):
+                    k2 = k2 + ph[li][1]
+                slot = jj * B + ii if (bug == "a2_transposed" and bi != bj) else ii * B + jj
+                cp[pb, :, slot] = bands(w0 * k2) if (li < d and lj < d) else 0.0
+        cp[pb, :, 20], cp[pb, :, 21] = bands(w0), bands(np.diag(np.diag(g)))
+    # u_i, dot, YP, Q
+    uv = yv @ AI.T
+    dot = yv @ uv.T
+    YP = np.zeros((ppad, npad))
+    YP[:p, :n] = P["Y"]
+    Q = YP @ AI
+    # the three output blocks
+    hx = (uv[:, :n] @ YP[:p, :n].T) * psi[None, :] / (2.0 * D)
+    sdot = YP[:p, :n] @ (YP[:p, :n] - Q[:p, :n]).T
+    tdot = np.zeros(p) if bug == "hn_no_diag" else YP[:p, :n] @ (f["b"] - f["z"])
+    hn = -(np.diag(psi * tdot) + np.outer(psi, psi) * sdot) / (4.0 * D)
+    hk = _ph_final(tp, cp, dot, th, d, bug)
+    out = np.concatenate([hk.reshape(-1), hx.reshape(-1), hn.reshape(-1)])
+    return dict(xs=xs, yv=yv, AI=AI, G=G, E=E, tp=tp, cp=cp, uv=uv, dot=dot, YP=YP, Q=Q, out=out)
+
+
+def _ph_checks(P, k, e, stages=PH_STAGES):
+    n, d, p, th, f = P["n"], P["d"], P["p"], P["th"][k], _ph_fit(P, k)
+    R = sb.hess_parts(e["xs"], P["sr"], th, P["kernel"], n)
+    fns = dict(hess_prep=lambda: sb.check_hess_prep(e["xs"], e["yv"], P["x"], P["sr"], th, f["b"], f["z"]),
+               hess_mirror=lambda: sb.check_hess_mirror(e["AI"], e["G"][d], e["G"][d + 1], f["V"], P["sr"], th, n, d),
+               hess_da=lambda: sb.check_hess_da(e["E"], R, d - 1),
+               hess_y=lambda: sb.check_hess_y(e["yv"], R, f["z"]),
+               hess_g=lambda: sb.check_hess_g(e["G"], e["AI"], e["E"], R),
+               hess_trace=lambda: sb.check_hess_trace(e["tp"], e["G"], n),
+               hess_contract=lambda: sb.check_hess_contract(e["cp"], e["AI"], R, f["z"], th),
+               hess_vectors=lambda: sb.check_hess_vectors(e["uv"], e["dot"], e["YP"], e["Q"], e["AI"], e["yv"], P["Y"], n),
+               hess_out=lambda: sb.check_hess_out(e["out"], e["YP"], e["uv"], e["Q"], f["b"], f["z"], e["tp"], e["cp"], e["dot"],
+                                                  th, n, d, p))
+    return {s: fns[s]() for s in stages}
+
+
+def _stage_only(order, checks, *failing):
+    """every stage listed in `failing` is above 1, every stage upstream of the first of them at or below 1"""
+    first = min(order.index(f) for f in failing)
+    for stage in order[:first]:
+        if stage in checks:
+            assert checks[stage].ratio <= 1.0, ("upstream", stage, checks[stage])
+    for stage in failing:
+        assert checks[stage].ratio > 1.0, (stage, checks[stage])
+
+
+def _floor_condition(log):
+    """at most 1 % of the entries of any stage have their bound set by the absolute floor"""
+    tot = {}
+    for stage, floored, entries in log:
+        a, b = tot.get(stage, (0, 0))
+        tot[stage] = (a + floored, b + entries)
+    for stage, (floored, entries) in tot.items():
+        assert floored <= 0.01 * entries, (stage, floored, entries)
+    return tot
+
+
+def _normwise_blocks(got, want):
+    return max(float(np.max(np.abs(g - w)) / np.max(np.abs(w))) for g, w in zip(got, want))
+
+
+@pytest.mark.parametrize("d", [3, 9])
+@pytest.mark.parametrize("rep", [False, True], ids=["full", "rep"])
+@pytest.mark.parametrize("kernel", KERNELS)
+def test_emulated_nll_hess_passes_every_stage(kernel, rep, d, monkeypatch):
+    """every stage at or below 1, the floor sets at most 1 % of the bounds of any stage, and the emulated output blocks agree
+    with the numpy closed form of tests/test_nll_hess_host.py -- which that file ties to the autograd Hessian of
+    tests/nll_hess_ref.py -- at its bar (EPS_REF = 1e-14 of the largest entry per block), on the same A^-1"""
+    import types
+    from tests import test_nll_hess_host as host
+    P = _ph_problem(d, kernel, rep)
+    log = []
+    monkeypatch.setattr(sb, "FLOOR_LOG", log)
+    for k in range(2):
+        e = _ph_emulate(P, k)
+        checks = _ph_checks(P, k, e)
+        print(kernel, rep, d, k, {s: "%.2e" % c.ratio for s, c in checks.items()})
+        for stage, c in checks.items():
+            assert c.ratio <= 1.0, (stage, c)
+        m, p = d + 2, P["p"]
+        got = e["out"][:m * m].reshape(m, m), e["out"][m * m:m * m + m * p].reshape(m, p), e["out"][m * m + m * p:].reshape(p, p)
+        # (the closed form takes the emulation's A^-1 -- the mirrored lower triangle, the input of both -- in place of its own
+        # solve: the two inverses differ by eps cond(A), which the noise corner's I - A^-1 magnifies past the bar)
+        monkeypatch.setattr(host, "sla", types.SimpleNamespace(cho_solve=lambda c, b, V=_ph_fit(P, k)["V"]: V))
+        assert _normwise_blocks(got, host.component_blocks(P["x"], P["Y"], P["sr"], P["th"][k], kernel)) <= host.EPS_REF
+    _floor_condition(log)
+
+
+HESS_DEFECTS = [("dphi_offdiag", "hess_contract"), ("a2_transposed", "hess_contract"), ("first_order_pair_bj", "hess_out"),
+                ("chunk2_all", "hess_trace"), ("pair_im", "hess_trace"), ("band_past_n", "hess_contract"),
+                ("gnug_sa", "hess_mirror"), ("ynug_no_s2", "hess_prep"), ("mirror_upper", "hess_mirror"),
+                ("hn_no_diag", "hess_out"), ("dphi_m32", "hess_contract")]
+
+
+@pytest.mark.parametrize("bug,stage", HESS_DEFECTS)
+def test_nll_hess_defect_fails_its_stage_and_none_upstream(bug, stage):
+    """d = 9 (three blocks of four dimensions, six block pairs, m = 11: two HS_JC chunks), the replicated path (s_a against s_b,
+    s^2 in y_nug); Matern-5/2 for the wrong d phi: dphi on an off-diagonal block pair, a2 transposed there, a first-order slot
+    read from pair bj (2 instead of 3 for the third block), a second chunk that also sums j > i, a trace pair written at
+    i m + j, a band past n included (the identity padding of AI reaches slots 20 and 21), G_nug with the row's s, y_nug without
+    s^2, the mirror from the unwritten triangle, hn without its diagonal term, the Matern-3/2 d phi under Matern-5/2"""
+    P = _ph_problem(9, "matern52" if bug == "dphi_m32" else "matern32", True)
+    checks = _ph_checks(P, 0, _ph_emulate(P, 0, bug))
+    print(bug, {s: "%.2e" % c.ratio for s, c in checks.items()})
+    _stage_only(PH_STAGES, checks, stage)
+
+
+def test_nll_hess_gap_small_ell_ell_entry_is_invisible_normwise():
+    """the smallest ell-ell entry of hk off by 1e-6 relative: max|H - H_ref| / max|H_ref| of the kernel block stays below the 1e-11
+    of tests/test_gpu_nll_hess.py, and check_hess_out fails at that entry"""
+    P = _ph_problem(9, "matern32", False)
+    d, m = 9, 11
+    e = _ph_emulate(P, 0)
+    hk = e["out"][:m * m].reshape(m, m).copy()
+    sub = np.abs(hk[:d, :d]) + np.triu(np.full((d, d), np.inf), 1)
+    i, j = np.unravel_index(int(np.argmin(sub)), sub.shape)
+    bad = hk.copy()
+    bad[i, j] = bad[j, i] = hk[i, j] * (1.0 + 1e-6)
+    nw = np.max(np.abs(bad - hk)) / np.max(np.abs(hk))
+    print("hk[%d, %d] = %.3e of max %.3e: normwise %.3e (bar 1e-11)" % (i, j, hk[i, j], np.max(np.abs(hk)), nw))
+    assert 0 < nw <= 1e-11
+    out = e["out"].copy()
+    out[:m * m] = bad.reshape(-1)
+    e2 = dict(e, out=out)
+    c = _ph_checks(P, 0, e2, stages=("hess_out",))["hess_out"]
+    assert c.ratio > 1.0 and c.where == ("hk", i, j), c
+
+
+# ---- lcgp_predict_paramgrad --------------------------------------------------------------------------------------------
+def _pp_x0(P, same, n0=PH_N0):
+    """same = 0: new inputs, the first three of them training inputs (phi = 0 at distance 0); same = lo + 1: rows lo .. lo + n0
+    of the training set, as a chunked caller passes them"""
+    return P["x0"][:n0] if same == 0 else P["x"][same - 1:same - 1 + n0]
+
+
+def _pp_emulate(P, k, same=0, bug=None, n0=PH_N0):
+    """lcgp_predict_paramgrad on component k: every buffer of PgradLay after the call and the three outputs"""
+    n, d, p, kernel = P["n"], P["d"], P["p"], P["kernel"]
+    th = P["th"][k]
+    ell, scale, nug, D, psi = sb.split_theta(th, d)
+    L = sb.pgrad_layout(n, d, p, 1, n0)
+    m, npad, ppad, n0r, nsum = L["m"], L["npad"], L["ppad"], L["n0r"], L["nsum"]
+    f = _ph_fit(P, k)
+    s = np.ones(n) if P["sr"] is None else P["sr"]
+    x0 = _pp_x0(P, same, n0)
+    xs, yv = _ph_prep(P, k, npad)
+    omw = 1.0 / (1.0 + nug)
+    nt, w1 = nug * omw, omw * omw
+    x0l = (x0 / ell[None, :]).T
+    xc = (scale / (1.0 + nug)) * _ph_c0(x0l, xs[:, :n], kernel) * s[None, :]
+    X = xc.copy()
+    rows = np.arange(n0)
+    if same > 0:
+        X[rows, rows + same - 1] += scale * nt * s[rows + same - 1]
+    V = np.zeros((n0r, npad))
+    V[:n0, :n] = X @ f["V"]                                  # (the library: U = X W^T, V = U W; an input of every check here)
+    zp = np.concatenate([f["z"], np.zeros(npad - n)])
+    rd = np.zeros((d, n0r))
+    per_dim = []
+    for j in range(d):
+        E = _ph_da(P, k, xs, j)
+        yv[j] = E @ zp
+        T = V @ E
+        per_dim.append((T * V).sum(axis=1))
+    for j in range(d):
+        rd[j] = per_dim[max(j - 1, 0)] if bug == "rd_prev" else per_dim[j]
+    v, z = V[:n0, :n], f["z"]
+    sums = np.zeros((n0r, nsum))
+    for j0 in range(0, d, sb.PP_DB):                          # one workgroup per (row, block of PP_DB dimensions)
+        for j in range(j0, min(j0 + sb.PP_DB, d)):
+            lj = ell[j - sb.PP_DB] if (bug == "stale_block" and j0 > 0) else ell[j]
+            t = xc * _ph_phi(np.abs(x0l[j][:, None] - xs[j][None, :n]), lj, kernel)[0]
+            sums[:n0, j], sums[:n0, d + j], sums[:n0, 2 * d + 6 + j] = (t * z).sum(axis=1), (t * v).sum(axis=1), (v * yv[j, :n]).sum(axis=1)
+        if j0 == 0:
+            s2 = 1.0 if bug == "s2vv_no_s2" else s * s
+            sums[:n0, 2 * d], sums[:n0, 2 * d + 1] = (xc * z).sum(axis=1), (xc * v).sum(axis=1)
+            sums[:n0, 2 * d + 4], sums[:n0, 2 * d + 5] = (v * v).sum(axis=1), (s2 * v * v).sum(axis=1)
+            sums[:n0, 3 * d + 6], sums[:n0, 3 * d + 7] = (v * yv[d, :n]).sum(axis=1), (v * yv[d + 1, :n]).sum(axis=1)
+            if same > 0:
+                cs = rows + same - 1 + (1 if bug == "cstar_off" else 0)
+                sums[:n0, 2 * d + 2], sums[:n0, 2 * d + 3] = s[cs] * z[cs], s[cs] * v[rows, cs]
+    YT = np.zeros((npad, ppad))
+    YT[:n, :p] = P["Y"].T
+    VY = V @ YT
+    # pgrad_final_kernel
+    S = sums[:n0]
+    dg, dv = np.zeros((n0, m)), np.zeros((n0, m))
+    dg[:, :d] = S[:, :d] - S[:, 2 * d + 6:3 * d + 6]
+    dv[:, :d] = -D * (2.0 * S[:, d:2 * d] - rd[:, :n0].T)
+    xcz, xcv, rz, rv, vv, s2vv = (S[:, 2 * d + c] for c in range(6))
+    xz, xv = scale * nt * rz + xcz, scale * nt * rv + xcv
+    dg[:, d] = xz / scale - S[:, 3 * d + 6]
+    dv[:, d] = 1.0 - D * (xv + vv) / scale
+    dg[:, d + 1] = (scale * w1 * rz - xcz * omw) - S[:, 3 * d + 7]
+    sg = -1.0 if bug == "nug_sign" else 1.0
+    dv[:, d + 1] = -D * (2.0 * (sg * scale * w1 * rv - xcv * omw) - (D * scale * s2vv - (xv - vv)) * omw)
+    ps = sb.split_theta(P["th"][1 - k], d)[4] if bug == "noise_psi_other" else psi
+    dn = -0.5 * ps[None, :] * VY[:n0, :p]
+    return dict(xs=xs, yv=yv, E=E, V=V, T=T, rd=rd, sums=sums, YT=YT, VY=VY, dg=dg, dv=dv, dn=dn, ghat=X @ z,
+                gvar=scale - D * (X * v).sum(axis=1))
+
+
+def _pp_checks(P, k, e, same, n0=PH_N0, stages=PP_STAGES):
+    n, d, p, th, f = P["n"], P["d"], P["p"], P["th"][k], _ph_fit(P, k)
+    R = sb.hess_parts(e["xs"], P["sr"], th, P["kernel"], n)
+    fns = dict(hess_prep=lambda: sb.check_hess_prep(e["xs"], e["yv"], P["x"], P["sr"], th, f["b"], f["z"]),
+               hess_da=lambda: sb.check_hess_da(e["E"], R, d - 1),
+               pp_y=lambda: sb.check_pp_y(e["yv"], R, f["z"]),
+               pp_t=lambda: sb.check_pp_t(e["T"], e["V"], e["E"], n0, n),
+               pp_rowdot=lambda: sb.check_pp_rowdot(e["rd"], e["T"], e["V"], R, n0),
+               pp_sums=lambda: sb.check_pp_sums(e["sums"], _pp_x0(P, same, n0), e["xs"], f["z"], e["V"], e["yv"], P["sr"], th,
+                                                P["kernel"], same, n0, n),
+               pp_vy=lambda: sb.check_pp_vy(e["YT"], e["VY"], e["V"], P["Y"], n0, n),
+               pp_out=lambda: sb.check_pp_out(e["dg"], e["dv"], e["dn"], e["sums"], e["rd"], e["VY"], th, d, p, n0))
+    return {s: fns[s]() for s in stages}
+
+
+@pytest.mark.parametrize("d", [3, 9])
+@pytest.mark.parametrize("rep", [False, True], ids=["full", "rep"])
+@pytest.mark.parametrize("kernel", KERNELS)
+def test_emulated_predict_paramgrad_passes_every_stage(kernel, rep, d, monkeypatch):
+    """new inputs (same = 0), the training set itself (same = 1) and a middle slice of it (same = 21): every stage at or below
+    1, the floor sets at most 1 % of the bounds of any stage, and the outputs agree with the dense restatement
+    tests/param_grad_ref.py:latent at the bar of tests/test_param_grad_host.py (1e-12 of the largest entry per output)"""
+    import types
+    from tests import param_grad_ref as pref
+    from tests.test_param_grad_host import EPS_REF
+    P = _ph_problem(d, kernel, rep)
+    log = []
+    monkeypatch.setattr(sb, "FLOOR_LOG", log)
+    for k, same in ((0, 0), (1, 1), (0, 21)):
+        e = _pp_emulate(P, k, same)
+        checks = _pp_checks(P, k, e, same)
+        print(kernel, rep, d, k, same, {s: "%.2e" % c.ratio for s, c in checks.items()})
+        for stage, c in checks.items():
+            assert c.ratio <= 1.0, (stage, c)
+        if same <= 1:
+            # (on the emulation's A^-1, as in the Hessian's tie: gvar = scale - D X.V cancels to eps cond(A) of its terms)
+            monkeypatch.setattr(pref, "sla", types.SimpleNamespace(cho_solve=lambda c, b, V=_ph_fit(P, k)["V"]: V))
+            want = pref.latent(_pp_x0(P, same), bool(same), P["x"], P["Y"], P["sr"], P["th"][k], kernel)
+            # (gvar, lcgp_predict_grad's output and none of this pass's stages, is left out: scale - D X.V cancels)
+            assert _normwise_blocks((e["ghat"], e["dg"], e["dv"], e["dn"]), want[:1] + want[2:]) <= EPS_REF
+    _floor_condition(log)
+
+
+PP_DEFECTS = [("cstar_off", "pp_sums", 9), ("rd_prev", "pp_rowdot", 9), ("s2vv_no_s2", "pp_sums", 9), ("stale_block", "pp_sums", 17),
+              ("noise_psi_other", "pp_out", 9), ("nug_sign", "pp_out", 9)]
+
+
+@pytest.mark.parametrize("bug,stage,d", PP_DEFECTS)
+def test_predict_paramgrad_defect_fails_its_stage_and_none_upstream(bug, stage, d):
+    """the replicated path, a middle slice of the training set (same = 21): c* one column off, rd of dimension j - 1, sum s^2 V^2
+    without s^2, the second PP_DB block (d = 17) with the first block's lengthscales, dghat_noise with psi of the other component,
+    d_nug gvar with the wrong sign on the nugget term"""
+    P = _ph_problem(d, "matern32", True)
+    checks = _pp_checks(P, 0, _pp_emulate(P, 0, 21, bug), 21)
+    print(bug, {s: "%.2e" % c.ratio for s, c in checks.items()})
+    _stage_only(PP_STAGES, checks, stage)
+
+
+def test_predict_paramgrad_gap_small_dgvar_column_is_invisible_normwise():
+    """one lengthscale 50 times longer than the others: its dgvar column is small, and off by 1e-6 relative it stays within the
+    1e-10 of max|err| / max|ref| of tests/test_gpu_param_grad.py while check_pp_out fails at that column"""
+    base = _ph_problem(9, "matern32", False)
+    P = dict(base, th=base["th"].copy(), fit={})
+    P["th"][:, 0] *= 50.0
+    e = _pp_emulate(P, 0, 0)
+    assert all(c.ratio <= 1.0 for c in _pp_checks(P, 0, e, 0).values())
+    bad = e["dv"].copy()
+    bad[:, 0] *= 1.0 + 1e-6
+    nw = np.max(np.abs(bad - e["dv"])) / np.max(np.abs(e["dv"]))
+    print("dgvar column 0: max %.3e of %.3e, normwise %.3e (bar 1e-10)" % (np.max(np.abs(e["dv"][:, 0])), np.max(np.abs(e["dv"])), nw))
+    assert 0 < nw <= 1e-10
+    c = _pp_checks(P, 0, dict(e, dv=bad), 0, stages=("pp_out",))["pp_out"]
+    assert c.ratio > 1.0 and c.where[:2] == ("dgvar", 0), c

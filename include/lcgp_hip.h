@@ -562,6 +562,9 @@ int lcgp_condition_predict_marginal(void* stream, int dtype, int kernel_id, int 
 int lcgp_condition_grad_state_bytes(int dtype, int n, int q_local, int m, size_t* bytes /*host out*/);
 int lcgp_condition_grad_prepare(void* stream, int dtype, int n, int d, int p, int q_local, const double* theta,
                                 const void* workspace, const void* state, int m, void* grad_state);
+/* w (q_local x m) and z' (q_local x n) of a grad state, in double, without their padding: the weights of the view's mean surface
+ * over the n + m centres are c sr_i z'_i and c w_a.  One launch; grad_state, w and z are device pointers. */
+int lcgp_condition_grad_fetch(void* stream, int n, int q_local, int m, const void* grad_state, double* w, double* z);
 int lcgp_condition_predict_grad_scratch_bytes(int dtype, int n, int q_local, int m, int n0, size_t* bytes /*host out*/);
 int lcgp_condition_predict_grad(void* stream, int dtype, int kernel_id, int n, int d, int p, int q_local,
                                 const void* x, const void* sr, const double* theta, const void* workspace,
@@ -1000,6 +1003,33 @@ int lcgp_sobol_matrix_pairs(void* stream, int dtype, int kernel_id, int n, int d
                             const double* ell /* q_local x d */, const double* box /* lo[d], hi[d] */,
                             const void* workspace, const int* ks /* nks, host */, int nks, void* scratch,
                             double* out /* nks x (2 d + 2) */);
+
+/* The matrix-weighted pass on a conditioned view: lcgp_sobol_matrix_pairs over the N = n + m centres
+ * xa = [x; xn] (training inputs first, then the view's m inputs) with the covariance correction of the view in A^-1's place.  For
+ * each LOCAL component k in `ks`, with W = L^-1 and A^-1 of the float64 workspace, U_n and L_S^-1 of the view's float64 state
+ * (lcgp_condition_prepare) and D_k from the theta rows, the weight of an element is
+ *     Q'[i, i'] = v[k, i] v[k, i'] (E[i, i'] + D_k A_k^-1[i, i'] [i < n and i' < n]),
+ *     E = Pt^T Pt,     Pt = [ -D_k T_n W | L_S^-1 ]  (m x N),     T_n = L_S^-1 U_n,
+ * the block inverse of the augmented matrix with the Schur complement S.  The split of D: D_k sits INSIDE the matrices (on A^-1
+ * and on the first block of Pt); v carries the rest, v[k, i] = c_k sr_i on the n training rows and c_k on the m new rows
+ * (c_k = scale_k (1 - nt_k)) -- unlike lcgp_sobol_matrix_pairs, whose v holds sqrt(D_k).  Row r of `out` is laid out as there:
+ * sum Q' (M_u - M_0) in columns 0 .. 2 d, S0 = sum Q' M_0 in column 2 d + 1, M over the N centres.
+ * One component at a time: -T_n and (-T_n) W on the tile kernel (OP_COND_U on a zeroed slab, OP_PRED_V), one transposing
+ * launch that scales and places the L_S^-T block (zeros on all padding), the lower 64 x 64 tiles of E (OP_PRED_COV, K = mpad),
+ * then ONE pair pass over the N x N plane whose tile weights are E plus, where both indices are below n, D_k A^-1 read in place.
+ * The workspace, the state and theta are only read.  float64 only (a float32 workspace or state is refused), d <= 126, n >= 1,
+ * m >= 1, nks >= 1; every argument is checked before the first launch.  No atomics, one stream: two calls agree bit for bit,
+ * nothing depends on the scratch content on entry or on which subset of ks is asked for.  xa (N x d), v (q_local x N), ell
+ * (q_local x d), box, theta, workspace, state, scratch and out are device pointers, ks is a HOST array.
+ * scratch: lcgp_condition_sobol_scratch_bytes(n, d, q_local, m, nks): the table (q_local d N doubles), the tile sums of one
+ * component, 2 mpad npad + Npad mpad + Npad^2 doubles for T_n, T_n W, P and E (Npad = N rounded up to 64), each 256-byte aligned. */
+int lcgp_condition_sobol_scratch_bytes(int n, int d, int q_local, int m, int nks, size_t* bytes /*host out*/);
+int lcgp_condition_sobol_matrix_pairs(void* stream, int dtype, int kernel_id, int n, int d, int p, int q_local,
+                                      const double* theta, const void* workspace, const void* state, int m,
+                                      const double* xa /* (n + m) x d, standardised */, const double* v /* q_local x (n + m) */,
+                                      const double* ell /* q_local x d */, const double* box /* lo[d], hi[d] */,
+                                      const int* ks /* nks, host */, int nks, void* scratch, size_t scratch_bytes,
+                                      double* out /* nks x (2 d + 2) */);
 
 #ifdef __cplusplus
 }

@@ -86,6 +86,7 @@ SIGNATURES = {
                                              C.c_size_t, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "lcgp_condition_grad_state_bytes": (_i, [_i, _i, _i, _i, C.POINTER(C.c_size_t)]),
     "lcgp_condition_grad_prepare": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp]),
+    "lcgp_condition_grad_fetch": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),
     "lcgp_condition_predict_grad_scratch_bytes": (_i, [_i, _i, _i, _i, _i, C.POINTER(C.c_size_t)]),
     "lcgp_condition_predict_grad": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, C.c_size_t,
                                          _vp, _vp, _vp, _vp, _i]),
@@ -136,6 +137,9 @@ SIGNATURES = {
     "lcgp_sobol_pairs": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, C.POINTER(_i), _i, _vp, _vp]),
     "lcgp_sobol_matrix_scratch_bytes": (_i, [_i, _i, _i, _i, C.POINTER(C.c_size_t)]),
     "lcgp_sobol_matrix_pairs": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, C.POINTER(_i), _i, _vp, _vp]),
+    "lcgp_condition_sobol_scratch_bytes": (_i, [_i, _i, _i, _i, _i, C.POINTER(C.c_size_t)]),
+    "lcgp_condition_sobol_matrix_pairs": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, C.POINTER(_i), _i,
+                                               _vp, C.c_size_t, _vp]),
 }
 
 _lib = None

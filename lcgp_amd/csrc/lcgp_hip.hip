@@ -4138,6 +4138,15 @@ __global__ __launch_bounds__(256) void cond_tmatvec_kernel(const T* __restrict__
     }
 }
 
+// w (q x m) and z' (q x n) of the grad state without their padding (lcgp_condition_grad_fetch)
+__global__ __launch_bounds__(256) void cond_grad_fetch_kernel(const double* __restrict__ wv, int mpad, int m,
+                                                              const double* __restrict__ zd, int npad, int n,
+                                                              double* __restrict__ w, double* __restrict__ z) {
+    const int k = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
+    if (i < m) w[(size_t)k * m + i] = wv[(size_t)k * mpad + i];
+    if (i < n) z[(size_t)k * n + i] = zd[(size_t)k * npad + i];
+}
+
 template <typename T>
 int do_condition_grad_prepare(hipStream_t st, const Ws& w, const double* theta, const void* state, int m, void* gstate) {
     const int dtype = sizeof(T) == 4 ? LCGP_F32 : LCGP_F64;
@@ -7305,19 +7314,39 @@ __device__ __forceinline__ double sobol_wave_sum(double v) {          // lane 0 
 
 // the matrix a matrix-weighted pair launch reads its weights from: component k's at base + k * mat, rows of npad doubles, the
 // lower triangle valid (the A^-1 slot of a float64 workspace); all zero in the launches of lcgp_sobol_pairs, which never read it
-struct SobolQ { const double* base; size_t mat; int npad; };
+struct SobolQ {
+    const double* base; size_t mat; int npad;
+    // SOBOL_VIEW only (lcgp_condition_sobol_matrix_pairs): the plane is (nt + m) x (nt + m); the second source E
+    // (ONE component's, rows of epad doubles, lower tiles valid) covers all of it, `base` its leading nt x nt block, times *dk
+    const double* e = nullptr; int epad = 0, nt = 0; const double* dk = nullptr;
+};
+
+// where the weight of an element comes from: the product of two vectors (lcgp_sobol_pairs), times an entry of A^-1
+// (lcgp_sobol_matrix_pairs), times E[i, i'] + D A^-1[i, i'] (i, i' < nt) on a conditioned view
+enum SobolWeight { SOBOL_VEC = 0, SOBOL_MAT = 1, SOBOL_VIEW = 2 };
 
 // tile (r, c), c <= r, of component k's matrix into qt[i * (TS + 1) + j], for the 256 threads of a workgroup: thread e reads
 // row e / 64, column e % 64, so a wavefront reads 64 consecutive doubles of one row.  In a diagonal tile only j <= i is read
 // and written to both (i, j) and (j, i): an element above the diagonal takes the mirrored entry.  Rows and columns beyond n
 // (never used by the element loop) are zero.  The caller's barrier follows.
+// SOBOL_VIEW: the element is E[gi, gj] (gi, gj < n = nt + m) plus D A^-1[gi, gj] where both indices are below nt; the boundary nt
+// may cut a tile, a diagonal one too: the sum is formed before the mirrored write, so the mirror holds for both sources.
+template <int MAT>
 __device__ __forceinline__ void sobol_stage_q(double* qt, const SobolQ& qm, int k, int n, int r, int c, int tid) {
     const double* src = qm.base + (size_t)k * qm.mat;
+    [[maybe_unused]] double dk = 0.0;
+    if constexpr (MAT == SOBOL_VIEW) dk = *qm.dk;
     for (int e = tid; e < TS * TS; e += 256) {
         const int i = e >> 6, j = e & 63;
         const int gi = r * TS + i, gj = c * TS + j;
         if (r == c && j > i) continue;
-        const double v = (gi < n && gj < n) ? src[(size_t)gi * qm.npad + gj] : 0.0;
+        double v;
+        if constexpr (MAT == SOBOL_VIEW) {
+            v = (gi < n && gj < n) ? qm.e[(size_t)gi * qm.epad + gj] : 0.0;
+            if (gi < qm.nt && gj < qm.nt) v = fma(dk, src[(size_t)gi * qm.npad + gj], v);
+        } else {
+            v = (gi < n && gj < n) ? src[(size_t)gi * qm.npad + gj] : 0.0;
+        }
         qt[i * (TS + 1) + j] = v;
         if (r == c) qt[j * (TS + 1) + i] = v;
     }
@@ -7358,7 +7387,7 @@ __global__ __launch_bounds__(256) void sobol_table_kernel(const double* __restri
 // w_i w_i' Q[i, i'] with Q the component's matrix in `qm` (A^-1 in place: qmat elements per component, rows of npad, its lower
 // triangle valid).  The tile of Q goes through LDS (sobol_stage_q); one more sum per tile, S0 = sum w_i w_i' Q M_0, follows the
 // 2 d + 1 others in part.  Nothing of MAT is instantiated in the instances without it.
-template <int KERN, int DD, bool MAT>
+template <int KERN, int DD, int MAT>
 __global__ __launch_bounds__(256) void sobol_pair_kernel(const double* __restrict__ x, int n, int d, const double* __restrict__ w,
                                                          const double* __restrict__ ell, const double* __restrict__ box,
                                                          const double* __restrict__ tab, SobolPairs pr, int ntile,
@@ -7394,7 +7423,7 @@ __global__ __launch_bounds__(256) void sobol_pair_kernel(const double* __restric
     const double* qs = nullptr;
     if constexpr (MAT) {
         __shared__ double qtile[TS * (TS + 1)];
-        sobol_stage_q(qtile, qm, k, n, r, c, tid);
+        sobol_stage_q<MAT>(qtile, qm, k, n, r, c, tid);
         qs = qtile;
     }
     __syncthreads();
@@ -7456,7 +7485,7 @@ __global__ __launch_bounds__(256) void sobol_pair_kernel(const double* __restric
 
 // launch 2 for d > 16: the same tiles, elements and sums, one input l at a time, its three products recomputed from the inputs
 // (O(d^2) pair averages per element), nothing staged
-template <int KERN, bool MAT>
+template <int KERN, int MAT>
 __global__ __launch_bounds__(256) void sobol_pair_wide_kernel(const double* __restrict__ x, int n, int d, const double* __restrict__ w,
                                                               const double* __restrict__ ell, const double* __restrict__ box,
                                                               const double* __restrict__ tab, SobolPairs pr, int ntile,
@@ -7473,7 +7502,7 @@ __global__ __launch_bounds__(256) void sobol_pair_wide_kernel(const double* __re
     const double* qs = nullptr;
     if constexpr (MAT) {                                   // (the one thing staged: every round reads the same weights)
         __shared__ double qtile[TS * (TS + 1)];
-        sobol_stage_q(qtile, qm, k, n, r, c, tid);
+        sobol_stage_q<MAT>(qtile, qm, k, n, r, c, tid);
         qs = qtile;
         __syncthreads();
     }
@@ -7517,7 +7546,7 @@ __global__ __launch_bounds__(256) void sobol_pair_wide_kernel(const double* __re
 // launch 3: out[pair, s] = the sum over the pair's tiles of part[pair, tile, s] in a fixed order (thread t adds tiles t, t + 256,
 // ..., then a tree over the threads), s = 0 .. 2 d; out[pair, 2 d + 1] = the box mean of component k where k = k', else 0.
 // grid (2 d + 2, pairs of the launch).  MAT: part holds 2 d + 2 sums per tile and out[pair, 2 d + 1] is the last one's sum, S0.
-template <bool MAT>
+template <int MAT>
 __global__ __launch_bounds__(256) void sobol_reduce_kernel(const double* __restrict__ part, int ntile, int d, SobolPairs pr,
                                                            const double* __restrict__ means, double* __restrict__ out) {
     __shared__ double red[256];
@@ -7550,15 +7579,38 @@ inline size_t sobol_part_doubles(int n, int d, int npairs, int per_tile_extra = 
     return (size_t)(npairs < SOBOL_BATCH ? npairs : SOBOL_BATCH) * ntile * ntile * (2 * d + 1 + per_tile_extra);
 }
 
-// MAT = false: lcgp_sobol_pairs (qm unused).  MAT = true: lcgp_sobol_matrix_pairs, `pairs` holds (k, k) of local components,
+// launches 2 and 3 for the nb <= SOBOL_BATCH pairs in pr: the pair tiles into part, their sums into out (nb rows).  The
+// reduction of SOBOL_VIEW is SOBOL_MAT's (2 d + 2 sums per tile either way).
+template <int MAT>
+int sobol_pair_launches(hipStream_t st, int kern, int n, int d, const double* x, const double* w, const double* ell,
+                        const double* box, const double* tab, const double* means, const SobolPairs& pr, int nb, double* part,
+                        double* out, const SobolQ& qm) {
+    const int ntile = (n + TS - 1) / TS;
+    const dim3 grid(ntile, ntile, nb);
+    for_kern(kern, [&](auto kn) {
+        constexpr int K = decltype(kn)::value;
+        if (d <= 8)
+            hipLaunchKernelGGL((sobol_pair_kernel<K, 8, MAT>), grid, dim3(256), 0, st, x, n, d, w, ell, box, tab, pr, ntile, part, qm);
+        else if (d <= 16)
+            hipLaunchKernelGGL((sobol_pair_kernel<K, 16, MAT>), grid, dim3(256), 0, st, x, n, d, w, ell, box, tab, pr, ntile, part, qm);
+        else
+            hipLaunchKernelGGL((sobol_pair_wide_kernel<K, MAT>), grid, dim3(256), 0, st, x, n, d, w, ell, box, tab, pr, ntile, part, qm);
+    });
+    CHECK_LAUNCH("sobol_pair_kernel");
+    constexpr int RED = MAT == SOBOL_VIEW ? (int)SOBOL_MAT : MAT;
+    hipLaunchKernelGGL((sobol_reduce_kernel<RED>), dim3(2 * d + 2, nb), dim3(256), 0, st, part, ntile, d, pr, means, out);
+    CHECK_LAUNCH("sobol_reduce_kernel");
+    return 0;
+}
+
+// SOBOL_VEC: lcgp_sobol_pairs (qm unused).  SOBOL_MAT: lcgp_sobol_matrix_pairs, `pairs` holds (k, k) of local components,
 // w their row vectors v and out[pair, 2 d + 1] is S0
-template <bool MAT>
+template <int MAT>
 int do_sobol_pairs(hipStream_t st, int kern, int n, int d, int q_all, const double* x, const double* w, const double* ell,
                    const double* box, const int* pairs, int npairs, void* scratch, double* out, SobolQ qm) {
     double* tab = (double*)scratch;
     double* means = tab + (size_t)q_all * d * n;
     double* part = means + q_all;
-    const int ntile = (n + TS - 1) / TS;
     for_kern(kern, [&](auto kn) {
         hipLaunchKernelGGL((sobol_table_kernel<decltype(kn)::value>), dim3(q_all), dim3(256), 0, st, x, n, d, w, ell, box, tab, means);
     });
@@ -7570,20 +7622,130 @@ int do_sobol_pairs(hipStream_t st, int kern, int n, int d, int q_all, const doub
             pr.k[i] = i < nb ? pairs[2 * (p0 + i)] : 0;
             pr.kp[i] = i < nb ? pairs[2 * (p0 + i) + 1] : 0;
         }
-        const dim3 grid(ntile, ntile, nb);
-        for_kern(kern, [&](auto kn) {
-            constexpr int K = decltype(kn)::value;
-            if (d <= 8)
-                hipLaunchKernelGGL((sobol_pair_kernel<K, 8, MAT>), grid, dim3(256), 0, st, x, n, d, w, ell, box, tab, pr, ntile, part, qm);
-            else if (d <= 16)
-                hipLaunchKernelGGL((sobol_pair_kernel<K, 16, MAT>), grid, dim3(256), 0, st, x, n, d, w, ell, box, tab, pr, ntile, part, qm);
-            else
-                hipLaunchKernelGGL((sobol_pair_wide_kernel<K, MAT>), grid, dim3(256), 0, st, x, n, d, w, ell, box, tab, pr, ntile, part, qm);
-        });
-        CHECK_LAUNCH("sobol_pair_kernel");
-        hipLaunchKernelGGL((sobol_reduce_kernel<MAT>), dim3(2 * d + 2, nb), dim3(256), 0, st, part, ntile, d, pr, means,
-                           out + (size_t)p0 * (2 * d + 2));
-        CHECK_LAUNCH("sobol_reduce_kernel");
+        int rc = sobol_pair_launches<MAT>(st, kern, n, d, x, w, ell, box, tab, means, pr, nb, part, out + (size_t)p0 * (2 * d + 2), qm);
+        if (rc) return rc;
+    }
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------
+// The matrix-weighted pass on a conditioned view (lcgp_condition_sobol_matrix_pairs).  Over the N = n + m centres
+// [x; xn] the view's covariance correction is c^2 times
+//     [[D sr sr^T o A^-1, 0], [0, 0]] + P P^T,     P = [ -D sr o (W^T T_n^T) ; L_S^-T ]  (N x m),   T_n = L_S^-1 U_n
+// (the block inverse of the augmented matrix with the Schur complement S of 4.13).  The caller's row vectors carry c sr_i on the
+// training rows and c on the new ones, so the weight of an element is v_i v_i' (E[i, i'] + D A^-1[i, i'] [i, i' < n]) with
+//     E = Pt^T Pt,     Pt = [ D (-T_n W) | L_S^-1 ]   (m x N; sr left to v).
+// One component at a time: -T_n by OP_COND_U on a zeroed slab (R := the dense L_S^-1, K = mpad), (-T_n) W by OP_PRED_V, the
+// transposition with the scaling by D and the L_S^-T block (cond_sobol_p_kernel), the lower tiles of E by OP_PRED_COV on a
+// zeroed E with its -D_k read from a word holding -1, and ONE pair pass over the N x N plane (SOBOL_VIEW).
+// ---------------------------------------------------------------------------------------------------
+struct CondSobolLay {
+    int N, Npad, npad, mpad;
+    size_t off_tab, off_means, off_part, off_neg, off_T, off_G, off_P, off_E, total;       // bytes
+};
+
+inline CondSobolLay cond_sobol_carve(int n, int d, int q, int m) {
+    CondSobolLay L;
+    L.N = n + m;
+    L.Npad = round_up(L.N, TS);
+    L.npad = round_up(n, 2 * TS);
+    L.mpad = cov_pad(m);
+    const size_t dbl = sizeof(double);
+    size_t o = 0;
+    L.off_tab = o; o = align256(o + (size_t)q * d * L.N * dbl);
+    L.off_means = o; o = align256(o + (size_t)q * dbl);
+    L.off_part = o; o = align256(o + sobol_part_doubles(L.N, d, 1, 1) * dbl);
+    L.off_neg = o; o = align256(o + dbl);
+    L.off_T = o; o = align256(o + (size_t)L.mpad * L.npad * dbl);
+    L.off_G = o; o = align256(o + (size_t)L.mpad * L.npad * dbl);
+    L.off_P = o; o = align256(o + (size_t)L.Npad * L.mpad * dbl);
+    L.off_E = o; o = align256(o + (size_t)L.Npad * L.Npad * dbl);
+    L.total = o;
+    return L;
+}
+
+// P[i, a] (Npad x mpad, row-major) from G = (-T_n) W (mpad x npad) and the dense L_S^-1 (mpad x mpad): D G[a, i] for i < n,
+// L_S^-1[a, i - n] for n <= i < n + m, zero for i >= n + m and for a >= m.  64 x 64 tiles through LDS: reads run along i, writes
+// along a.  Block (0, 0) also leaves the -1 that OP_PRED_COV takes for its -D_k.
+__global__ __launch_bounds__(256) void cond_sobol_p_kernel(const double* __restrict__ G, int npad, const double* __restrict__ Wi,
+                                                           int mpad, int n, int m, const double* __restrict__ dk,
+                                                           double* __restrict__ P, double* __restrict__ neg) {
+    __shared__ double tile[TS][TS + 1];
+    const int i0 = blockIdx.x * TS, a0 = blockIdx.y * TS, tid = threadIdx.x;
+    const double D = *dk;
+    for (int e = tid; e < TS * TS; e += 256) {
+        const int a = a0 + (e >> 6), i = i0 + (e & 63);
+        double v = 0.0;
+        if (a < m) {
+            if (i < n) v = D * G[(size_t)a * npad + i];
+            else if (i < n + m) v = Wi[(size_t)a * mpad + (i - n)];
+        }
+        tile[e >> 6][e & 63] = v;
+    }
+    __syncthreads();
+    for (int e = tid; e < TS * TS; e += 256) {
+        const int i = i0 + (e >> 6), a = a0 + (e & 63);
+        P[(size_t)i * mpad + a] = tile[e & 63][e >> 6];
+    }
+    if (blockIdx.x == 0 && blockIdx.y == 0 && tid == 0) *neg = -1.0;
+}
+
+int do_condition_sobol(hipStream_t st, const Ws& w, const double* theta, const void* state, int m, const double* xa,
+                       const double* v, const double* ell, const double* box, const int* ks, int nks, void* scratch, double* out) {
+    const CondLay L = cond_carve(LCGP_F64, w.n, w.q, m);
+    const CondSobolLay S = cond_sobol_carve(w.n, w.d, w.q, m);
+    const int N = S.N, Npad = S.Npad, mpad = S.mpad, npad = w.npad, d = w.d, tw = w.d + 3 + w.p;
+    char* sc = (char*)scratch;
+    double* tab = (double*)(sc + S.off_tab);
+    double* means = (double*)(sc + S.off_means);
+    double* part = (double*)(sc + S.off_part);
+    double* neg = (double*)(sc + S.off_neg);
+    double* Tn = (double*)(sc + S.off_T);
+    double* Gm = (double*)(sc + S.off_G);
+    double* Pm = (double*)(sc + S.off_P);
+    double* Em = (double*)(sc + S.off_E);
+    for_kern(w.kern, [&](auto kn) {
+        hipLaunchKernelGGL((sobol_table_kernel<decltype(kn)::value>), dim3(w.q), dim3(256), 0, st, xa, N, d, v, ell, box, tab, means);
+    });
+    CHECK_LAUNCH("sobol_table_kernel");
+    const size_t slab = (size_t)mpad * npad;
+    for (int r = 0; r < nks; ++r) {
+        const int k = ks[r];
+        const double* Un = (const double*)((const char*)state + L.off_U) + (size_t)k * slab;
+        const double* Wi = (const double*)((const char*)state + L.off_W) + (size_t)k * mpad * mpad;
+        const double* Wk = (const double*)(w.base + w.off_W) + (size_t)k * w.mat;
+        const double* dk = theta + (size_t)k * tw + d + 2;
+        hipError_t e = hipMemsetAsync(Tn, 0, slab * sizeof(double), st);
+        if (e != hipSuccess) return fail("hipMemsetAsync", e);
+        GemmArgs g;                                        // -T_n = 0 - L_S^-1 U_n
+        g.A = Wi; g.B = Un; g.C = Tn;
+        g.sA = (size_t)mpad * mpad; g.sB = g.sC = slab; g.ldA = mpad; g.ldB = g.ldC = npad;
+        g.nb = w.nb; g.p0 = mpad / TS; g.p1 = mpad / TS; g.p2 = g.p3 = 0;
+        int rc = launch_gemm<double, OP_COND_U, 64>(st, g, g.p0 * g.nb, 1);
+        if (rc) return rc;
+        rc = launch_pred<double, OP_PRED_V>(st, Tn, Wk, Gm, slab, w.mat, npad, mpad, w.nb, 1, 0, true);       // (-T_n) W
+        if (rc) return rc;
+        hipLaunchKernelGGL(cond_sobol_p_kernel, dim3(Npad / TS, mpad / TS), dim3(256), 0, st, (const double*)Gm, npad, Wi, mpad,
+                           w.n, m, dk, Pm, neg);
+        CHECK_LAUNCH("cond_sobol_p_kernel");
+        e = hipMemsetAsync(Em, 0, (size_t)Npad * Npad * sizeof(double), st);
+        if (e != hipSuccess) return fail("hipMemsetAsync", e);
+        GemmArgs h;                                        // E += P P^T on the lower tiles (alpha = -(-1))
+        h.A = Pm; h.B = Pm; h.C = Em;
+        h.sA = h.sB = (size_t)Npad * mpad; h.sC = (size_t)Npad * Npad; h.ldA = h.ldB = mpad; h.ldC = Npad;
+        h.p1 = 0; h.p2 = 0; h.p3 = 0;
+        h.theta = neg;
+        const int t64 = Npad / TS;
+        h.nb = t64; h.p0 = mpad / TS;
+        rc = launch_gemm<double, OP_PRED_COV, 64>(st, h, t64 * (t64 + 1) / 2, 1);
+        if (rc) return rc;
+        SobolPairs pr;
+        for (int i = 0; i < SOBOL_BATCH; ++i) pr.k[i] = pr.kp[i] = k;
+        SobolQ qm{(const double*)(w.base + w.off_V), w.mat, npad};
+        qm.e = Em; qm.epad = Npad; qm.nt = w.n; qm.dk = dk;
+        rc = sobol_pair_launches<SOBOL_VIEW>(st, w.kern, N, d, xa, v, ell, box, tab, means, pr, 1, part,
+                                             out + (size_t)r * (2 * d + 2), qm);
+        if (rc) return rc;
     }
     return 0;
 }
@@ -8179,6 +8341,19 @@ int lcgp_condition_grad_prepare(void* stream, int dtype, int n, int d, int p, in
     hipStream_t st = (hipStream_t)stream;
     return dtype == LCGP_F64 ? do_condition_grad_prepare<double>(st, w, theta, state, m, grad_state)
                              : do_condition_grad_prepare<float>(st, w, theta, state, m, grad_state);
+}
+
+int lcgp_condition_grad_fetch(void* stream, int n, int q_local, int m, const void* grad_state, double* w, double* z) {
+    if (n < 1 || q_local < 1 || q_local > 65535) return bad("n must be >= 1, q_local in [1, 65535]");
+    if (m < 1) return bad("m < 1");
+    if (!grad_state || !w || !z) return bad("NULL pointer");
+    const CondGradLay G = cond_grad_carve(n, q_local, m);
+    const int big = n > m ? n : m;
+    hipLaunchKernelGGL(cond_grad_fetch_kernel, dim3((big + 255) / 256, q_local), dim3(256), 0, (hipStream_t)stream,
+                       (const double*)((const char*)grad_state + G.off_w), (int)cov_pad(m), m,
+                       (const double*)((const char*)grad_state + G.off_z), round_up(n, 2 * TS), n, w, z);
+    CHECK_LAUNCH("cond_grad_fetch_kernel");
+    return 0;
 }
 
 int lcgp_condition_predict_grad_scratch_bytes(int dtype, int n, int q_local, int m, int n0, size_t* bytes) {
@@ -8856,7 +9031,7 @@ int lcgp_sobol_pairs(void* stream, int kernel_id, int n, int d, int q_all, const
     if (!x || !w || !ell || !box || !pairs || !scratch || !out) return bad("NULL pointer");
     for (int i = 0; i < 2 * npairs; ++i)
         if (pairs[i] < 0 || pairs[i] >= q_all) return bad("pairs must hold component indices in [0, q_all)");
-    return do_sobol_pairs<false>((hipStream_t)stream, kernel_id, n, d, q_all, x, w, ell, box, pairs, npairs, scratch, out,
+    return do_sobol_pairs<SOBOL_VEC>((hipStream_t)stream, kernel_id, n, d, q_all, x, w, ell, box, pairs, npairs, scratch, out,
                                  SobolQ{nullptr, 0, 0});
 }
 
@@ -8885,7 +9060,42 @@ int lcgp_sobol_matrix_pairs(void* stream, int dtype, int kernel_id, int n, int d
     }
     Ws w = carve(dtype, n, d, p, q_local, (void*)workspace);
     const SobolQ qm{(const double*)(w.base + w.off_V), w.mat, w.npad};
-    return do_sobol_pairs<true>((hipStream_t)stream, kernel_id, n, d, q_local, x, v, ell, box, pairs.data(), nks, scratch, out, qm);
+    return do_sobol_pairs<SOBOL_MAT>((hipStream_t)stream, kernel_id, n, d, q_local, x, v, ell, box, pairs.data(), nks, scratch, out, qm);
+}
+
+static int cond_sobol_check(int n, int d, int q_local, int m, int nks) {
+    if (m < 1) return bad("m < 1");
+    if (n > INT_MAX - m) return bad("n + m overflows");
+    int rc = sobol_check(n + m, d, q_local, 1);
+    if (rc) return rc;
+    if (nks < 1) return bad("nks < 1");
+    return 0;
+}
+
+int lcgp_condition_sobol_scratch_bytes(int n, int d, int q_local, int m, int nks, size_t* bytes) {
+    if (n < 1) return bad("n < 1");
+    int rc = cond_sobol_check(n, d, q_local, m, nks);
+    if (rc) return rc;
+    if (!bytes) return bad("bytes is NULL");
+    *bytes = cond_sobol_carve(n, d, q_local, m).total;
+    return 0;
+}
+
+int lcgp_condition_sobol_matrix_pairs(void* stream, int dtype, int kernel_id, int n, int d, int p, int q_local, const double* theta,
+                                      const void* workspace, const void* state, int m, const double* xa, const double* v,
+                                      const double* ell, const double* box, const int* ks, int nks, void* scratch,
+                                      size_t scratch_bytes, double* out) {
+    if (dtype != LCGP_F64) return bad("lcgp_condition_sobol_matrix_pairs reads a float64 workspace and a float64 state");
+    int rc = check_common(dtype, n, d, p, q_local, kernel_id);
+    if (rc) return rc;
+    if ((rc = cond_sobol_check(n, d, q_local, m, nks))) return rc;
+    if (!theta || !workspace || !state || !xa || !v || !ell || !box || !ks || !scratch || !out) return bad("NULL pointer");
+    for (int i = 0; i < nks; ++i)
+        if (ks[i] < 0 || ks[i] >= q_local) return bad("ks must hold local component indices in [0, q_local)");
+    if (scratch_bytes < cond_sobol_carve(n, d, q_local, m).total) return bad("scratch too small (lcgp_condition_sobol_scratch_bytes)");
+    Ws w = carve(dtype, n, d, p, q_local, (void*)workspace);
+    w.kern = kernel_id;
+    return do_condition_sobol((hipStream_t)stream, w, theta, state, m, xa, v, ell, box, ks, nks, scratch, out);
 }
 
 }  // extern "C"

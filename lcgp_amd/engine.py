@@ -565,6 +565,58 @@ class HotPathEngine:
             res = out.cpu().numpy()
         return res[:, :2 * d + 1].copy(), res[:, 2 * d + 1].copy()
 
+    def condition_sobol_matrix_sums(self, state, v, ell, box, ks):
+        """sobol_matrix_sums on the view `state` (lcgp_condition_sobol_matrix_pairs): over the N = n + m centres
+        [x; xn], weighted by Q'[i, i'] = v[k, i] v[k, i'] (E[i, i'] + D_k A_k^-1[i, i'] where both are training inputs), E the
+        rank-m term of the view.  v (q_local, N) holds c sr on the training rows and c on the new ones (D lives inside the
+        matrices), ell (q_local, d), box (2, d) standardised, ks local component indices.  Returns host arrays (sums (len(ks),
+        2 d + 1), s0 (len(ks),)).  The float64 workspace, the view's state and its grad state are only read; E of one component
+        at a time lives in the engine's scratch."""
+        torch = self.torch
+        assert self.dtype == _hip.F64, "condition_sobol_matrix_sums reads the A^-1 and the view state of a float64 engine"
+        if self._theta_last is None:
+            raise RuntimeError("condition_sobol_matrix_sums() needs a preceding evaluate() at the current parameters")
+        n, d, m = self.n, self.d, state['m']
+        N = n + m
+        v = np.ascontiguousarray(v, np.float64)
+        ell = np.ascontiguousarray(ell, np.float64)
+        box = np.ascontiguousarray(box, np.float64)
+        ks = np.ascontiguousarray(ks, np.int32).reshape(-1)
+        nks = ks.shape[0]
+        assert v.shape == (self.q_local, N) and ell.shape == (self.q_local, d) and box.shape == (2, d)
+        if not np.all(box[1] > box[0]):
+            raise ValueError("condition_sobol_matrix_sums: the box needs hi > lo in every dimension")
+        with torch.cuda.device(self.device):
+            self._condition_grad_state(state)
+            xa = torch.cat([self.x, state['xn']]).contiguous()           # (float64: the engine's dtype)
+            dev = [torch.as_tensor(a).to(self.device) for a in (v, ell, box)]
+            npad_all = -(-N // 64) * 64
+            scratch = self._grow_scratch(self._nbytes("lcgp_condition_sobol_scratch_bytes", n, d, self.q_local, m, nks),
+                                         ("the matrix-weighted Sobol pair sums of a conditioned view",
+                                          "one component's %d x %d matrix E and %d tile sums" % (npad_all, npad_all, (npad_all // 64) ** 2),
+                                          "condition on fewer new inputs at a time"))
+            out = torch.empty((nks, 2 * d + 2), dtype=torch.float64, device=self.device)
+            _hip.check(self.lib.lcgp_condition_sobol_matrix_pairs(
+                self._stream(), self.dtype, self.kernel_id, n, d, self.p, self.q_local, self._p(self.theta_dev),
+                self._p(self.workspace), self._p(state['state']), m, self._p(xa), *[self._p(t) for t in dev],
+                ks.ctypes.data_as(C.POINTER(C.c_int)), nks, self._p(scratch), scratch.numel(), self._p(out)),
+                "lcgp_condition_sobol_matrix_pairs")
+            res = out.cpu().numpy()
+        return res[:, :2 * d + 1].copy(), res[:, 2 * d + 1].copy()
+
+    def condition_mean_vectors(self, state):
+        """(z' (q_local, n), w (q_local, m)) of the view `state` on the host: its mean surface is X_0 z' + c^x(x0, xn) w (the grad
+        state of lcgp_condition_grad_prepare, built on first use)"""
+        torch = self.torch
+        m = state['m']
+        with torch.cuda.device(self.device):
+            gs = self._condition_grad_state(state)
+            w = torch.empty((self.q_local, m), dtype=torch.float64, device=self.device)
+            z = torch.empty((self.q_local, self.n), dtype=torch.float64, device=self.device)
+            _hip.check(self.lib.lcgp_condition_grad_fetch(self._stream(), self.n, self.q_local, m, self._p(gs), self._p(w),
+                                                          self._p(z)), "lcgp_condition_grad_fetch")
+            return z.cpu().numpy(), w.cpu().numpy()
+
     def predict_device(self, x0s, same=False):
         """ghat, gvar (q_local, n0): the two halves of predict_block()"""
         out = self.predict_block(x0s, same)

@@ -338,9 +338,15 @@ class ConditionedLCGP:
     predict(x0) equals, to rounding, predict(x0) of a model built on the augmented data at the same parameters.  The view
     goes stale when the base model's parameters change or the model is evaluated elsewhere: using it then raises RuntimeError."""
 
-    def __init__(self, base, x_new, engine, state):
+    def __init__(self, base, x_new, engine, state, ys=None, counts=None, float64=None):
         self.base, self.x_new, self.m = base, x_new, int(x_new.shape[0])
         self._engine, self._state = engine, state
+        # what the float64 queries (sobol_indices, integrated_variance) rebuild a float32 view from: the standardised outputs
+        # (p, m) and the counts (None: ones) condition() formed; float64: whether `state` is a float64 engine's (None: the base
+        # model's dtype says)
+        self._ys, self._counts = ys, counts
+        self._float64 = (base._dtype == 'float64') if float64 is None else bool(float64)
+        self._companion = None       # (state on the base model's float64 engine, built on first use) of a float32 view
         # (the view of a float32 model may live on its float64 engine, which does not follow the model's later evaluations:
         # the parameter vector itself is part of the check)
         self._u = base._get_flat().copy()
@@ -518,6 +524,84 @@ class ConditionedLCGP:
         """LCGP.main_effects() of the conditioned model: the main-effect curves after the view's new runs, from one
         predict_marginal() pass of this view.  Arguments, defaults, checks and the MainEffects returned are the model's."""
         return self.base._main_effects(self.predict_marginal, grid, box, outputs, effect_var)
+
+    def _float64_state(self):
+        """(engine, state) of this view in float64 (engine None on a rank without components): its own where that is a float64
+        engine's; otherwise a companion state on the base model's float64 engine (one evaluation there when its factorisation
+        is not current), built once from the same new inputs, standardised outputs and counts and kept with the view.  The
+        view is stale when either engine no longer holds the parameters of its state."""
+        self._require_current()
+        if self._float64:
+            return self._engine, self._state
+        base = self.base
+        if self._ys is None:
+            raise RuntimeError('this ConditionedLCGP was built without the outputs of its new runs: a float32 view needs them for '
+                               'its float64 queries; call condition() again')
+        eng = base._ensure_aux64()
+        if self._companion is None:
+            xs = base._standardise_x0(_np(self.x_new))[0]
+            self._companion = (base._agree(lambda: base._condition_state(eng, xs, self._ys, self._counts),
+                                           failure='the conditioning matrix S_k of latent component(s) %s is not numerically positive '
+                                                   'definite in float64 (info %s)', what='the float64 state of the view'),)
+        state = self._companion[0]
+        if eng is not None and not eng.is_current(state['theta']):
+            raise RuntimeError('this ConditionedLCGP is stale: its float64 state belongs to other parameters; call condition() again')
+        return eng, state
+
+    def _mean_weights(self, eng, state):
+        """(xa (N, d), w (q, N)): the N = n + m centres [x; xn] (standardised) and the weights of every component's mean surface
+        over them, c sr_i z'_i on the training inputs and c w_a on the new ones.  Every rank gathers all q rows."""
+        base = self.base
+        n, m = int(base.n), self.m
+        rows = np.zeros((len(base._local_ks), n + m), F64)
+        if eng is not None:
+            rows[:, :n], rows[:, n:] = eng.condition_mean_vectors(state)
+        allv = _dist.gather_rows(rows, int(base.q), base._group, None if eng is None else eng.device)
+        sr = np.sqrt(_np(base.r)) if base.submethod == 'rep' else np.ones(n, F64)
+        scale_k, nug = base.lLmb0.numpy(), base.lnugGPs.numpy()
+        c = scale_k * (1.0 - nug / (1.0 + nug))
+        w = c[:, None] * np.concatenate([sr[None, :] * allv[:, :n], allv[:, n:]], axis=1)
+        return np.vstack([base._x_train(), base._standardise_x0(_np(self.x_new))[0]]), w
+
+    def _sobol_matrix(self, bs, eng, state):
+        """LCGP._sobol_matrix with the view's covariance correction Q' over the n + m centres (lcgp_condition_sobol_matrix_pairs)"""
+        base = self.base
+        n, m = int(base.n), self.m
+
+        def local_sums(loc, c, Dk, sr, ell):
+            v = c[loc][:, None] * np.concatenate([np.broadcast_to(sr[None, :], (len(loc), n)), np.ones((len(loc), m), F64)], axis=1)
+            return eng.condition_sobol_matrix_sums(state, v, ell[loc], bs, np.arange(len(loc)))
+
+        return base._sobol_matrix(bs, eng, local_sums)
+
+    def sobol_indices(self, box=None, outputs=None, latent=False, uncertainty=False):
+        """LCGP.sobol_indices() of the conditioned model: the SobolIndices GIVEN the base model's data and this view's new runs,
+        equal to rounding to those of a model built on the augmented data at the same parameters; nothing of size n is
+        factorised.  The mean surface is a kernel expansion over the n + m centres [x; x_new], so the plug-in
+        part is lcgp_sobol_pairs on them; uncertainty=True adds one matrix-weighted pass over the (n + m)^2 pairs per
+        component, weighted by A^-1 in place plus the view's rank-m term (lcgp_condition_sobol_matrix_pairs).  Arguments,
+        defaults, checks, errors, shapes and the fields are the model's; the default box is the base model's (main_effects()).
+        Always float64: the view of a float32 model builds a float64 state once on the base model's float64 engine and keeps
+        it.  Any number of ranks, the result does not depend on it.  RuntimeError when the view is stale."""
+        base = self.base
+        outputs = base._sobol_rows(outputs, latent)
+        bs = base._marginal_box(box)
+        eng, state = self._float64_state()
+        xa, w = self._mean_weights(eng, state)
+        V, mean = base._sobol_mean(eng, xa, w, bs, latent)
+        return base._sobol_result(V, mean, outputs, latent, (lambda: self._sobol_matrix(bs, eng, state)) if uncertainty else None)
+
+    def integrated_variance(self, box=None, outputs=None, latent=False):
+        """LCGP.integrated_variance() of the conditioned model: (p_sel,) the exact IMSPE after the view's new runs, what a
+        sequential design is judged by, without a model on the augmented data.  The matrix-weighted pass of
+        sobol_indices(uncertainty=True) alone and bitwise that call's integrated_variance; never above the base model's.
+        RuntimeError when the view is stale."""
+        base = self.base
+        outputs = base._sobol_rows(outputs, latent)
+        bs = base._marginal_box(box)
+        eng, state = self._float64_state()
+        _, iv, _ = self._sobol_matrix(bs, eng, state)
+        return _t(base._latent_variance_to_rows(iv, latent)[outputs])
 
     def _design_arguments(self, xc_s, match):
         """what the design queries check beyond the base model's: the view is current, and on the rep path no candidate equals
@@ -1909,13 +1993,8 @@ class LCGP:
                    'the current parameters (info %s)')
 
         def begin(e):
-            if e is None:
-                return None
-            rows = e._theta_last
-            # the latent observation of each new input: the entry of b_k the evaluation would form for it, over D_k sr_i
-            # (one product per component: a row's sum must not depend on how many components the rank holds)
-            t = np.stack([(row[d + 3:] @ ys) / row[d + 2] for row in rows])
-            return e.condition_begin(xu_s, t, r)
+            return self._condition_state(e, xu_s, ys, r)
+        float64 = self._dtype == 'float64' or bool(self._last_eval_float64)      # (the same on every rank)
         try:
             state = self._agree(lambda: begin(eng), failure=failure, what='the conditioned view')
         except np.linalg.LinAlgError:
@@ -1933,7 +2012,20 @@ class LCGP:
             finally:
                 self._aux_engine, self._last_eval_float64, self._gc_last, self._float64_only = keep
             state = self._agree(lambda: begin(eng), failure=failure + ', in float64 either', what='the conditioned view')
-        return ConditionedLCGP(self, _t(xu), eng, state)
+            float64 = True
+        return ConditionedLCGP(self, _t(xu), eng, state, ys=ys, counts=r, float64=float64)
+
+    def _condition_state(self, e, xu_s, ys, r):
+        """this rank's state of a view on the engine e (None: a rank without components) for the standardised new inputs xu_s,
+        their standardised outputs ys (p, m) and counts r (None: ones)"""
+        if e is None:
+            return None
+        d = int(self.d)
+        rows = e._theta_last
+        # the latent observation of each new input: the entry of b_k the evaluation would form for it, over D_k sr_i
+        # (one product per component: a row's sum must not depend on how many components the rank holds)
+        t = np.stack([(row[d + 3:] @ ys) / row[d + 2] for row in rows])
+        return e.condition_begin(xu_s, t, r)
 
     # =============================================================================================
     # closed-form cross-validation at fixed parameters (beyond the reference)
@@ -2782,15 +2874,24 @@ class LCGP:
         input the data say nothing about gets a plug-in index of exactly zero.  One more pass over the pairs k = k' (on the rank
         that owns the component, weighted by its A^-1 in place: lcgp_sobol_matrix_pairs) and one more reduction; the fields
         above are bitwise the same with and without it."""
-        d, p, q = int(self.d), int(self.p), int(self.q)
         outputs = self._sobol_rows(outputs, latent)
         bs = self._marginal_box(box)
         eng = self._ensure_aux64()
         n = int(self.n)
         sr = np.sqrt(_np(self.r)) if self.submethod == 'rep' else np.ones(n, F64)
         z = self._fetch_all(lambda e, i: e.fetch_vector(1, i), n)
-        ell, scale_k, nug = self.lLmb.numpy(), self.lLmb0.numpy(), self.lnugGPs.numpy()
+        scale_k, nug = self.lLmb0.numpy(), self.lnugGPs.numpy()
         w = (scale_k * (1.0 - nug / (1.0 + nug)))[:, None] * sr[None, :] * z
+        V, mean = self._sobol_mean(eng, self._x_train(), w, bs, latent)
+        return self._sobol_result(V, mean, outputs, latent, (lambda: self._sobol_matrix(bs)) if uncertainty else None)
+
+    def _sobol_mean(self, eng, xc, w, bs, latent):
+        """The variances of the conditional means and the box mean of a mean surface given as a kernel expansion: centres xc
+        (N, d) standardised, weights w (q, N) of ALL components, on the float64 engine eng (None on a rank without components).
+        Returns (V (rows, 2 d + 1), mean (rows,)) for all p outputs (latent: the q components), columns as lcgp_sobol_pairs
+        orders the subsets.  The pairs are dealt round-robin over the ranks that hold an engine; one reduction assembles them."""
+        d, q = int(self.d), int(self.q)
+        ell = self.lLmb.numpy()
         pairs = np.array([(k, k) for k in range(q)] if latent else [(k, kp) for k in range(q) for kp in range(k, q)], np.int32)
         rank, world = _dist.rank_world(self._group)
         mine = np.arange(rank, len(pairs), min(world, q)) if eng is not None else np.zeros(0, int)
@@ -2798,7 +2899,7 @@ class LCGP:
 
         def share():
             if len(mine):
-                full[mine, :2 * d + 1], full[mine, 2 * d + 1] = eng.sobol_pairs(self._x_train(), w, ell, bs, pairs[mine])
+                full[mine, :2 * d + 1], full[mine, 2 * d + 1] = eng.sobol_pairs(xc, w, ell, bs, pairs[mine])
 
         self._agree(share, what='the Sobol pair sums')
         if _dist.use_collectives(self._group):
@@ -2815,6 +2916,13 @@ class LCGP:
             W, _, scale, offset = self._output_map()
             V = np.einsum('ka,la,klu->au', W, W, D) * (scale ** 2)[:, None]
             mean = offset + scale * (W.T @ means)
+        return V, mean
+
+    def _sobol_result(self, V, mean, outputs, latent, matrix):
+        """the SobolIndices of the rows `outputs` of _sobol_mean's (V, mean); matrix: None, or a callable that returns
+        _sobol_matrix's tuple (uncertainty=True: the expectations and the integrated variance are added)"""
+        d = int(self.d)
+        uncertainty = matrix is not None
         V, mean = V[outputs], mean[outputs]
         var = V[:, 2 * d]
         with np.errstate(divide='ignore', invalid='ignore'):
@@ -2823,7 +2931,7 @@ class LCGP:
         plug = (_t(first), _t(total), _t(var.copy()), _t(mean.copy()), _t(V[:, :d].copy()), _t(V[:, d:2 * d].copy()))
         if not uncertainty:
             return SobolIndices(*plug)
-        corr, iv, _ = self._sobol_matrix(bs)
+        corr, iv, _ = matrix()
         E = V + self._latent_variance_to_rows(corr, latent)[outputs]
         ev = E[:, 2 * d]
         with np.errstate(divide='ignore', invalid='ignore'):
@@ -2859,16 +2967,20 @@ class LCGP:
         W, _, scale, _ = self._output_map()
         return np.tensordot((W ** 2).T, lat, axes=(1, 0)) * (scale ** 2).reshape((-1,) + (1,) * (lat.ndim - 1))
 
-    def _sobol_matrix(self, bs):
+    def _sobol_matrix(self, bs, eng=None, local_sums=None):
         """What the posterior covariance of the continuous surface adds, per latent component, over the standardised box bs
         (DESIGN.md 4.23): (C (q, 2 d + 1), IV (q,), overall_var (q,)) with
             C_u = c (prod_{l not in u} I2_l - prod_l I2_l) - sum Q (M_u - M_0)      E[V_u] - V_u(mean), u as in sobol_indices
             IV  = c - S0 - sum Q (M_all - M_0)                                        the box mean of the posterior variance
             overall_var = c prod_l I2_l - S0                                          the variance of the box mean
         c = scale (1 - nt), Q = D c^2 sr sr^T o A^-1.  Every rank evaluates the components it holds on its float64 engine
-        (lcgp_sobol_matrix_pairs), fills their rows of a zero array, and one reduction completes it."""
+        (lcgp_sobol_matrix_pairs), fills their rows of a zero array, and one reduction completes it.
+        A conditioned view passes its float64 engine and local_sums(loc, c, Dk, sr, ell) -> (sums, s0) of the local
+        components loc with ITS matrix Q' over n + m centres; the prior terms and the three lines above are
+        the same."""
         d, q, n = int(self.d), int(self.q), int(self.n)
-        eng = self._ensure_aux64()
+        if local_sums is None:
+            eng = self._ensure_aux64()
         sr = np.sqrt(_np(self.r)) if self.submethod == 'rep' else np.ones(n, F64)
         ell, scale_k, nug = self.lLmb.numpy(), self.lLmb0.numpy(), self.lnugGPs.numpy()
         c = scale_k * (1.0 - nug / (1.0 + nug))
@@ -2878,6 +2990,9 @@ class LCGP:
         def share():
             if eng is not None:
                 loc = [int(k) for k in self._local_ks]
+                if local_sums is not None:
+                    full[loc, :2 * d + 1], full[loc, 2 * d + 1] = local_sums(loc, c, Dk, sr, ell)
+                    return
                 v = (c[loc] * np.sqrt(Dk[loc]))[:, None] * sr[None, :]
                 full[loc, :2 * d + 1], full[loc, 2 * d + 1] = eng.sobol_matrix_sums(self._x_train(), v, ell[loc], bs,
                                                                                     np.arange(len(loc)))

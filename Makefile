@@ -7,13 +7,14 @@ LIB = lcgp_amd/liblcgp_hip.so
 SRC = lcgp_amd/csrc/lcgp_hip.hip
 HDR = include/lcgp_hip.h
 SCHED = lcgp_amd/csrc/fill_sched.h
+SUBSET = lcgp_amd/csrc/sobol_subset.h
 # the same digest lcgp_amd/_hip.py::source_hash() computes: the binary carries it (lcgp_source_hash()), so a
 # stale library is detected by content, not by mtime
-HASH = $(shell cat $(SRC) $(HDR) $(SCHED) | sha256sum | cut -c1-16)
+HASH = $(shell cat $(SRC) $(HDR) $(SCHED) $(SUBSET) | sha256sum | cut -c1-16)
 
 all: $(LIB) tests/native/test_kernels
 
-$(LIB): $(SRC) $(HDR) $(SCHED)
+$(LIB): $(SRC) $(HDR) $(SCHED) $(SUBSET)
 	$(HIPCC) $(CXXFLAGS) -fPIC -shared '-DLCGP_SRC_HASH="LCGP_SRC_HASH=$(HASH)"' -o $@ $(SRC)
 
 tests/native/test_kernels: tests/native/test_kernels.cpp $(LIB) $(HDR)

@@ -42,6 +42,7 @@
 #define LCGP_HIP_H
 
 #include <stddef.h>
+#include <stdint.h>
 
 #ifdef __cplusplus
 extern "C" {
@@ -1030,6 +1031,56 @@ int lcgp_condition_sobol_matrix_pairs(void* stream, int dtype, int kernel_id, in
                                       const double* ell /* q_local x d */, const double* box /* lo[d], hi[d] */,
                                       const int* ks /* nks, host */, int nks, void* scratch, size_t scratch_bytes,
                                       double* out /* nks x (2 d + 2) */);
+
+/* Closed variances of a caller's list of input subsets: the pair sums of lcgp_sobol_pairs, of
+ * lcgp_sobol_matrix_pairs and of lcgp_condition_sobol_matrix_pairs for ANY subsets u of the inputs instead of the 2 d + 1 fixed
+ * ones -- what second-order indices, indices of groups of inputs and Shapley effects are made of.  A subset is a bit mask: bit l
+ * of masks[s] is set when input l is in u; the empty mask and the full mask are allowed, a mask may repeat.  With a_l, J_l and
+ *     M_u[i, i'] = prod_l (bit_l ? J_l[i, i'] : a_l[i] a'_l[i']),   l ascending   (a select per factor, never a division)
+ * of lcgp_sobol_pairs, column s of a row of `out` holds for u = masks[s]
+ *     lcgp_sobol_subset_pairs                    D_u = sum_{i, i'} w[k, i] w[k', i'] (M_u - M_0)[i, i']     (k, k') = pairs[r]
+ *     lcgp_sobol_matrix_subset_pairs             sum_{i, i'} Q[i, i'] (M_u - M_0)[i, i']                     k = ks[r], Q as there
+ *     lcgp_condition_sobol_matrix_subset_pairs   sum_{i, i'} Q'[i, i'] (M_u - M_0)[i, i']  over N = n + m centres, Q' as there
+ * with M_0 the same product for the empty mask, so that the empty mask gives exactly 0.0.  The other arguments, their checks, the
+ * tiles (a pair k = k' over the lower ones, the strictly lower ones twice), the element loop, the pair integrals and the
+ * preparation launches are those of the three functions above, whose results do not change; no row carries a box mean or S0.
+ * The expensive part of an element, its d pair integrals, does not depend on u: one launch accumulates
+ * lcgp_sobol_subset_chunk(d) masks over them (32 for every d <= 16), and more masks are further launches that form the
+ * integrals again: ceil(nsub / chunk) pair launches and as many reductions per batch of 64 pairs.  The tile sums go through the
+ * scratch and are added in a fixed order: no atomics, two calls agree bit for bit, nothing depends on the scratch content on
+ * entry, and the sum of a mask depends neither on the other masks of the call nor on its place among them.
+ * Refused before the first launch (lcgp_last_error says why): NULL pointers, d > 16 (no wider variant: use the functions above
+ * for the fixed subsets), a mask with a bit at or above d, nsub < 1, n < 1, and a float32 workspace for the matrix forms.
+ * masks is a HOST array.  lcgp_sobol_subset_chunk returns the chunk, or a negative value for d outside [1, 16].
+ * scratch: lcgp_sobol_subset_scratch_bytes(n, d, q_all, npairs, nsub) =
+ *     8 (q_all d n + q_all + min(npairs, 64) ceil(n / 64)^2 chunk(d))
+ * for both lcgp_sobol_subset_pairs and lcgp_sobol_matrix_subset_pairs (q_all = q_local, npairs = nks there); it does not grow
+ * with nsub.  The table of the a_l comes first, then the q_all box means sum_i w[k, i] prod_l a_l[i] of the components, which a
+ * caller may read there after the call, then the tile sums of one launch.
+ * lcgp_condition_sobol_subset_scratch_bytes(n, d, q_local, m, nks, nsub): the layout of lcgp_condition_sobol_scratch_bytes with
+ * ceil(N / 64)^2 chunk(d) tile sums in the place of its ceil(N / 64)^2 (2 d + 2). */
+int lcgp_sobol_subset_chunk(int d);
+int lcgp_sobol_subset_scratch_bytes(int n, int d, int q_all, int npairs, int nsub, size_t* bytes /*host out*/);
+int lcgp_sobol_subset_pairs(void* stream, int kernel_id, int n, int d, int q_all,
+                            const double* x /* n x d, standardised */, const double* w /* q_all x n */,
+                            const double* ell /* q_all x d */, const double* box /* lo[d], hi[d] */,
+                            const int* pairs /* npairs x 2, host */, int npairs,
+                            const uint64_t* masks /* nsub, host */, int nsub, void* scratch,
+                            double* out /* npairs x nsub */);
+int lcgp_sobol_matrix_subset_pairs(void* stream, int dtype, int kernel_id, int n, int d, int p, int q_local,
+                                   const double* x /* n x d, standardised */, const double* v /* q_local x n */,
+                                   const double* ell /* q_local x d */, const double* box /* lo[d], hi[d] */,
+                                   const void* workspace, const int* ks /* nks, host */, int nks,
+                                   const uint64_t* masks /* nsub, host */, int nsub, void* scratch,
+                                   double* out /* nks x nsub */);
+int lcgp_condition_sobol_subset_scratch_bytes(int n, int d, int q_local, int m, int nks, int nsub, size_t* bytes /*host out*/);
+int lcgp_condition_sobol_matrix_subset_pairs(void* stream, int dtype, int kernel_id, int n, int d, int p, int q_local,
+                                             const double* theta, const void* workspace, const void* state, int m,
+                                             const double* xa /* (n + m) x d, standardised */,
+                                             const double* v /* q_local x (n + m) */, const double* ell /* q_local x d */,
+                                             const double* box /* lo[d], hi[d] */, const int* ks /* nks, host */, int nks,
+                                             const uint64_t* masks /* nsub, host */, int nsub, void* scratch,
+                                             size_t scratch_bytes, double* out /* nks x nsub */);
 
 #ifdef __cplusplus
 }

@@ -16,6 +16,7 @@ LIB_PATH = os.environ.get("LCGP_HIP_LIB") or os.path.join(_HERE, "liblcgp_hip.so
 SRC_PATH = os.path.join(_HERE, "csrc", "lcgp_hip.hip")
 HDR_PATH = os.path.join(_ROOT, "include", "lcgp_hip.h")
 SCHED_PATH = os.path.join(_HERE, "csrc", "fill_sched.h")
+SUBSET_PATH = os.path.join(_HERE, "csrc", "sobol_subset.h")
 
 F64, F32 = 0, 1
 # include/lcgp_hip.h: LCGP_KERNEL_MATERN32 (the reference's) / LCGP_KERNEL_SE / LCGP_KERNEL_MATERN52 (extensions, parity unpinned)
@@ -140,6 +141,14 @@ SIGNATURES = {
     "lcgp_condition_sobol_scratch_bytes": (_i, [_i, _i, _i, _i, _i, C.POINTER(C.c_size_t)]),
     "lcgp_condition_sobol_matrix_pairs": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, C.POINTER(_i), _i,
                                                _vp, C.c_size_t, _vp]),
+    "lcgp_sobol_subset_chunk": (_i, [_i]),
+    "lcgp_sobol_subset_scratch_bytes": (_i, [_i, _i, _i, _i, _i, C.POINTER(C.c_size_t)]),
+    "lcgp_sobol_subset_pairs": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, C.POINTER(_i), _i, C.POINTER(C.c_uint64), _i, _vp, _vp]),
+    "lcgp_sobol_matrix_subset_pairs": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, C.POINTER(_i), _i,
+                                            C.POINTER(C.c_uint64), _i, _vp, _vp]),
+    "lcgp_condition_sobol_subset_scratch_bytes": (_i, [_i, _i, _i, _i, _i, _i, C.POINTER(C.c_size_t)]),
+    "lcgp_condition_sobol_matrix_subset_pairs": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp,
+                                                      C.POINTER(_i), _i, C.POINTER(C.c_uint64), _i, _vp, C.c_size_t, _vp]),
 }
 
 _lib = None
@@ -150,7 +159,7 @@ def source_hash() -> str:
     LCGP_SRC_HASH and returned by lcgp_source_hash(), so source and binary can be compared on any box."""
     import hashlib
     h = hashlib.sha256()
-    for path in (SRC_PATH, HDR_PATH, SCHED_PATH):
+    for path in (SRC_PATH, HDR_PATH, SCHED_PATH, SUBSET_PATH):
         with open(path, "rb") as f:
             h.update(f.read())
     return h.hexdigest()[:16]

@@ -22,6 +22,7 @@
 
 #include "../../include/lcgp_hip.h"
 #include "fill_sched.h"
+#include "sobol_subset.h"
 
 #define LCGP_VERSION 610
 
@@ -7629,6 +7630,187 @@ int do_sobol_pairs(hipStream_t st, int kern, int n, int d, int q_all, const doub
 }
 
 // ---------------------------------------------------------------------------------------------------
+// The same pass for a caller's list of input subsets (lcgp_sobol_subset_pairs and its two matrix-weighted forms):
+// second-order indices, indices of groups, Shapley effects.  What an element costs -- its d pair averages J_l -- does not depend
+// on the subset, so one launch accumulates a CHUNK of SC subsets over the J_l it has formed; further chunks are further launches
+// that form them again.  A subset travels as a bit mask (bit l: input l is in u), the chunk as a kernel argument: uniform over
+// the launch, so every select below is on a scalar condition.
+// ---------------------------------------------------------------------------------------------------
+template <int SC>
+struct SobolMasks { unsigned m[SC]; };
+
+// launch 2 of the subset pass: sobol_pair_kernel's staging, tiles and element loop (the rolled J loop through the thread's LDS
+// column); per element and mask s < ns the product P_u = prod_l (bit_l ? J_l : A_l), l ascending (sobol_subset.h: a select per
+// factor, no division, nothing contracted), and acc[s] += wgt (P_u - M_0) with M_0 the same product of the A_l alone -- the empty
+// mask adds exactly 0.  The weight enters in one place; a pair k = k' visits the lower tiles and counts the strictly lower ones
+// twice; rows and columns beyond n are skipped.  The SC accumulators are registers (the mask loop is unrolled: no runtime index
+// into them); slot s sees the same instructions whatever the other slots hold, so a mask's sum does not depend on its place in
+// the list.  The block sums go to part[pair, tile, s], s < SC (wave shuffles, then the four waves in order): no atomics.
+template <int KERN, int DD, int MAT>
+__global__ __launch_bounds__(256) void sobol_subset_kernel(const double* __restrict__ x, int n, int d, const double* __restrict__ w,
+                                                           const double* __restrict__ ell, const double* __restrict__ box,
+                                                           const double* __restrict__ tab, SobolPairs pr, int ntile,
+                                                           double* __restrict__ part, SobolQ qm,
+                                                           SobolMasks<sobol_subset_chunk(DD)> mk, int ns) {
+    constexpr int SC = sobol_subset_chunk(DD);
+    __shared__ double xr[TS][DD + 1], xc[TS][DD + 1], ar[TS][DD + 1], ac[TS][DD + 1];
+    __shared__ double wr[TS], wc[TS];
+    __shared__ double Js[DD][256];
+    __shared__ SobolDim cst[DD];
+    __shared__ double red[4][SC];
+    const int r = blockIdx.x, c = blockIdx.y, z = blockIdx.z;
+    const int k = pr.k[z], kp = pr.kp[z];
+    if (k == kp && c > r) return;
+    const int tid = threadIdx.x;
+    for (int e = tid; e < TS * DD; e += 256) {
+        const int i = e / DD, l = e - i * DD;
+        const int gi = r * TS + i, gj = c * TS + i;
+        const bool vi = gi < n && l < d, vj = gj < n && l < d;
+        xr[i][l] = vi ? x[(size_t)gi * d + l] : 0.0;
+        xc[i][l] = vj ? x[(size_t)gj * d + l] : 0.0;
+        ar[i][l] = vi ? tab[((size_t)k * d + l) * n + gi] : 1.0;
+        ac[i][l] = vj ? tab[((size_t)kp * d + l) * n + gj] : 1.0;
+    }
+    if (tid < TS) {
+        const int gi = r * TS + tid, gj = c * TS + tid;
+        wr[tid] = gi < n ? w[(size_t)k * n + gi] : 0.0;
+        wc[tid] = gj < n ? w[(size_t)kp * n + gj] : 0.0;
+    }
+    if (tid < DD) {
+        if (tid < d) cst[tid] = sobol_dim<KERN>(ell[(size_t)k * d + tid], ell[(size_t)kp * d + tid], box[tid], box[d + tid]);
+    }
+#pragma unroll
+    for (int l = 0; l < DD; ++l) Js[l][tid] = 1.0;         // (dimensions d .. DD - 1 stay neutral)
+    const double* qs = nullptr;
+    if constexpr (MAT) {
+        __shared__ double qtile[TS * (TS + 1)];
+        sobol_stage_q<MAT>(qtile, qm, k, n, r, c, tid);
+        qs = qtile;
+    }
+    __syncthreads();
+    const double twice = (k == kp && c < r) ? 2.0 : 1.0;
+    const int tx = tid & 15, ty = tid >> 4;
+    double acc[SC];
+#pragma unroll
+    for (int s = 0; s < SC; ++s) acc[s] = 0.0;
+#pragma unroll 1
+    for (int e = 0; e < 16; ++e) {
+        const int i = ty * 4 + (e >> 2), j = tx + 16 * (e & 3);
+        if (r * TS + i >= n || c * TS + j >= n) continue;
+#pragma unroll 1
+        for (int l = 0; l < d; ++l) Js[l][tid] = sobol_J<KERN>(xr[i][l], xc[j][l], cst[l]);
+        // the weight of the element: ONE place (a matrix entry can take the product's place)
+        double wgt = twice * (wr[i] * wc[j]);
+        if constexpr (MAT) wgt *= qs[i * (TS + 1) + j];
+        double J[DD], A[DD];
+#pragma unroll
+        for (int l = 0; l < DD; ++l) {
+            J[l] = Js[l][tid];
+            A[l] = ar[i][l] * ac[j][l];
+        }
+        const double m0 = sobol_subset_product<DD>(0u, J, A);
+#pragma unroll
+        for (int s = 0; s < SC; ++s)
+            if (s < ns) acc[s] = fma(wgt, sobol_subset_diff<DD>(mk.m[s], J, A, m0), acc[s]);
+    }
+    const int wave = tid >> 6, lane = tid & 63;
+#pragma unroll
+    for (int s = 0; s < SC; ++s) {
+        const double f = sobol_wave_sum(acc[s]);
+        if (lane == 0) red[wave][s] = f;
+    }
+    __syncthreads();
+    if (tid < SC)
+        part[(((size_t)z * ntile + r) * ntile + c) * SC + tid] = (red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid]);
+}
+
+// launch 3 of the subset pass: sobol_reduce_kernel's scheme over the columns of one chunk.  out[pair, s0 + s] = the sum over
+// the pair's tiles of part[pair, tile, s] in a fixed order (thread t adds tiles t, t + 256, ..., then a tree over the threads);
+// rows of `out` are ld doubles apart.  grid (masks of the chunk, pairs of the launch); sc = the columns per tile in part.
+__global__ __launch_bounds__(256) void sobol_subset_reduce_kernel(const double* __restrict__ part, int ntile, int sc, SobolPairs pr,
+                                                                  double* __restrict__ out, size_t ld) {
+    __shared__ double red[256];
+    const int s = blockIdx.x, z = blockIdx.y, tid = threadIdx.x;
+    const int k = pr.k[z], kp = pr.kp[z];
+    double acc = 0.0;
+    for (int t = tid; t < ntile * ntile; t += 256) {
+        const int r = t / ntile, c = t - r * ntile;
+        if (k == kp && c > r) continue;
+        acc += part[((size_t)z * ntile * ntile + t) * sc + s];
+    }
+    red[tid] = acc;
+    __syncthreads();
+    for (int o = 128; o >= 1; o >>= 1) {
+        if (tid < o) red[tid] += red[tid + o];
+        __syncthreads();
+    }
+    if (tid == 0) out[(size_t)z * ld + s] = red[0];
+}
+
+inline size_t sobol_subset_part_doubles(int n, int d, int npairs) {
+    const size_t ntile = (n + TS - 1) / TS;
+    return (size_t)(npairs < SOBOL_BATCH ? npairs : SOBOL_BATCH) * ntile * ntile * sobol_subset_chunk(d);
+}
+
+// launches 2 and 3 for the nb <= SOBOL_BATCH pairs in pr and ALL nsub masks, a chunk at a time: out[pair, s] (nb rows of nsub)
+template <int MAT, int DD>
+int sobol_subset_launches_dd(hipStream_t st, int kern, int n, int d, const double* x, const double* w, const double* ell,
+                             const double* box, const double* tab, const SobolPairs& pr, int nb, double* part, double* out,
+                             const SobolQ& qm, const uint64_t* masks, int nsub) {
+    constexpr int SC = sobol_subset_chunk(DD);
+    const int ntile = (n + TS - 1) / TS;
+    const dim3 grid(ntile, ntile, nb);
+    for (int s0 = 0; s0 < nsub; s0 += SC) {
+        const int ns = nsub - s0 < SC ? nsub - s0 : SC;
+        SobolMasks<SC> mk;
+        for (int s = 0; s < SC; ++s) mk.m[s] = s < ns ? (unsigned)masks[s0 + s] : 0u;
+        for_kern(kern, [&](auto kn) {
+            hipLaunchKernelGGL((sobol_subset_kernel<decltype(kn)::value, DD, MAT>), grid, dim3(256), 0, st, x, n, d, w, ell, box, tab,
+                               pr, ntile, part, qm, mk, ns);
+        });
+        CHECK_LAUNCH("sobol_subset_kernel");
+        hipLaunchKernelGGL(sobol_subset_reduce_kernel, dim3(ns, nb), dim3(256), 0, st, (const double*)part, ntile, SC, pr, out + s0,
+                           (size_t)nsub);
+        CHECK_LAUNCH("sobol_subset_reduce_kernel");
+    }
+    return 0;
+}
+
+template <int MAT>
+int sobol_subset_launches(hipStream_t st, int kern, int n, int d, const double* x, const double* w, const double* ell,
+                          const double* box, const double* tab, const SobolPairs& pr, int nb, double* part, double* out,
+                          const SobolQ& qm, const uint64_t* masks, int nsub) {
+    if (d <= 8) return sobol_subset_launches_dd<MAT, 8>(st, kern, n, d, x, w, ell, box, tab, pr, nb, part, out, qm, masks, nsub);
+    return sobol_subset_launches_dd<MAT, 16>(st, kern, n, d, x, w, ell, box, tab, pr, nb, part, out, qm, masks, nsub);
+}
+
+// do_sobol_pairs for a list of masks: the table and the means once (they stay in the scratch: tab, then means), then the pairs
+// in batches of SOBOL_BATCH, each over every chunk of masks.  out is npairs x nsub.
+template <int MAT>
+int do_sobol_subset_pairs(hipStream_t st, int kern, int n, int d, int q_all, const double* x, const double* w, const double* ell,
+                          const double* box, const int* pairs, int npairs, const uint64_t* masks, int nsub, void* scratch,
+                          double* out, SobolQ qm) {
+    double* tab = (double*)scratch;
+    double* means = tab + (size_t)q_all * d * n;
+    double* part = means + q_all;
+    for_kern(kern, [&](auto kn) {
+        hipLaunchKernelGGL((sobol_table_kernel<decltype(kn)::value>), dim3(q_all), dim3(256), 0, st, x, n, d, w, ell, box, tab, means);
+    });
+    CHECK_LAUNCH("sobol_table_kernel");
+    for (int p0 = 0; p0 < npairs; p0 += SOBOL_BATCH) {
+        const int nb = npairs - p0 < SOBOL_BATCH ? npairs - p0 : SOBOL_BATCH;
+        SobolPairs pr;
+        for (int i = 0; i < SOBOL_BATCH; ++i) {
+            pr.k[i] = i < nb ? pairs[2 * (p0 + i)] : 0;
+            pr.kp[i] = i < nb ? pairs[2 * (p0 + i) + 1] : 0;
+        }
+        int rc = sobol_subset_launches<MAT>(st, kern, n, d, x, w, ell, box, tab, pr, nb, part, out + (size_t)p0 * nsub, qm, masks, nsub);
+        if (rc) return rc;
+    }
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------
 // The matrix-weighted pass on a conditioned view (lcgp_condition_sobol_matrix_pairs).  Over the N = n + m centres
 // [x; xn] the view's covariance correction is c^2 times
 //     [[D sr sr^T o A^-1, 0], [0, 0]] + P P^T,     P = [ -D sr o (W^T T_n^T) ; L_S^-T ]  (N x m),   T_n = L_S^-1 U_n
@@ -7644,7 +7826,8 @@ struct CondSobolLay {
     size_t off_tab, off_means, off_part, off_neg, off_T, off_G, off_P, off_E, total;       // bytes
 };
 
-inline CondSobolLay cond_sobol_carve(int n, int d, int q, int m) {
+// subset: the tile sums are those of one chunk of masks (lcgp_condition_sobol_matrix_subset_pairs), everything else the same
+inline CondSobolLay cond_sobol_carve(int n, int d, int q, int m, bool subset = false) {
     CondSobolLay L;
     L.N = n + m;
     L.Npad = round_up(L.N, TS);
@@ -7654,7 +7837,7 @@ inline CondSobolLay cond_sobol_carve(int n, int d, int q, int m) {
     size_t o = 0;
     L.off_tab = o; o = align256(o + (size_t)q * d * L.N * dbl);
     L.off_means = o; o = align256(o + (size_t)q * dbl);
-    L.off_part = o; o = align256(o + sobol_part_doubles(L.N, d, 1, 1) * dbl);
+    L.off_part = o; o = align256(o + (subset ? sobol_subset_part_doubles(L.N, d, 1) : sobol_part_doubles(L.N, d, 1, 1)) * dbl);
     L.off_neg = o; o = align256(o + dbl);
     L.off_T = o; o = align256(o + (size_t)L.mpad * L.npad * dbl);
     L.off_G = o; o = align256(o + (size_t)L.mpad * L.npad * dbl);
@@ -7690,10 +7873,13 @@ __global__ __launch_bounds__(256) void cond_sobol_p_kernel(const double* __restr
     if (blockIdx.x == 0 && blockIdx.y == 0 && tid == 0) *neg = -1.0;
 }
 
+// masks: NULL = the 2 d + 1 subsets of 4.22 (rows of 2 d + 2 in out); else the nsub masks of 4.25 (rows of nsub): the same
+// preparation of E, only the pair launches differ
 int do_condition_sobol(hipStream_t st, const Ws& w, const double* theta, const void* state, int m, const double* xa,
-                       const double* v, const double* ell, const double* box, const int* ks, int nks, void* scratch, double* out) {
+                       const double* v, const double* ell, const double* box, const int* ks, int nks, void* scratch, double* out,
+                       const uint64_t* masks = nullptr, int nsub = 0) {
     const CondLay L = cond_carve(LCGP_F64, w.n, w.q, m);
-    const CondSobolLay S = cond_sobol_carve(w.n, w.d, w.q, m);
+    const CondSobolLay S = cond_sobol_carve(w.n, w.d, w.q, m, masks != nullptr);
     const int N = S.N, Npad = S.Npad, mpad = S.mpad, npad = w.npad, d = w.d, tw = w.d + 3 + w.p;
     char* sc = (char*)scratch;
     double* tab = (double*)(sc + S.off_tab);
@@ -7743,8 +7929,12 @@ int do_condition_sobol(hipStream_t st, const Ws& w, const double* theta, const v
         for (int i = 0; i < SOBOL_BATCH; ++i) pr.k[i] = pr.kp[i] = k;
         SobolQ qm{(const double*)(w.base + w.off_V), w.mat, npad};
         qm.e = Em; qm.epad = Npad; qm.nt = w.n; qm.dk = dk;
-        rc = sobol_pair_launches<SOBOL_VIEW>(st, w.kern, N, d, xa, v, ell, box, tab, means, pr, 1, part,
-                                             out + (size_t)r * (2 * d + 2), qm);
+        if (masks)
+            rc = sobol_subset_launches<SOBOL_VIEW>(st, w.kern, N, d, xa, v, ell, box, tab, pr, 1, part, out + (size_t)r * nsub, qm,
+                                                   masks, nsub);
+        else
+            rc = sobol_pair_launches<SOBOL_VIEW>(st, w.kern, N, d, xa, v, ell, box, tab, means, pr, 1, part,
+                                                 out + (size_t)r * (2 * d + 2), qm);
         if (rc) return rc;
     }
     return 0;
@@ -9096,6 +9286,102 @@ int lcgp_condition_sobol_matrix_pairs(void* stream, int dtype, int kernel_id, in
     Ws w = carve(dtype, n, d, p, q_local, (void*)workspace);
     w.kern = kernel_id;
     return do_condition_sobol((hipStream_t)stream, w, theta, state, m, xa, v, ell, box, ks, nks, scratch, out);
+}
+
+// ---- closed variances of a caller's input subsets ----
+int lcgp_sobol_subset_chunk(int d) {
+    if (d < 1 || d > SOBOL_SUBSET_DMAX) return bad("the subset pass takes d in [1, 16]");
+    return sobol_subset_chunk(d);
+}
+
+static int sobol_subset_check(int n, int d, int q_all, int npairs, int nsub) {
+    if (d > SOBOL_SUBSET_DMAX) return bad("the subset pass takes d in [1, 16] (a mask addresses 16 inputs; no d > 16 variant)");
+    int rc = sobol_check(n, d, q_all, npairs);
+    if (rc) return rc;
+    if (nsub < 1) return bad("nsub < 1");
+    return 0;
+}
+
+static int sobol_masks_check(const uint64_t* masks, int nsub, int d) {
+    for (int s = 0; s < nsub; ++s)
+        if (masks[s] >> d) return bad("a mask has a bit at or above d");
+    return 0;
+}
+
+int lcgp_sobol_subset_scratch_bytes(int n, int d, int q_all, int npairs, int nsub, size_t* bytes) {
+    int rc = sobol_subset_check(n, d, q_all, npairs, nsub);
+    if (rc) return rc;
+    if (!bytes) return bad("bytes is NULL");
+    *bytes = ((size_t)q_all * d * n + q_all + sobol_subset_part_doubles(n, d, npairs)) * sizeof(double);
+    return 0;
+}
+
+int lcgp_sobol_subset_pairs(void* stream, int kernel_id, int n, int d, int q_all, const double* x, const double* w,
+                            const double* ell, const double* box, const int* pairs, int npairs, const uint64_t* masks, int nsub,
+                            void* scratch, double* out) {
+    if (kernel_id != LCGP_KERNEL_MATERN32 && kernel_id != LCGP_KERNEL_SE && kernel_id != LCGP_KERNEL_MATERN52)
+        return bad("kernel_id must be 0 (Matern-3/2), 1 (squared exponential) or 2 (Matern-5/2)");
+    int rc = sobol_subset_check(n, d, q_all, npairs, nsub);
+    if (rc) return rc;
+    if (!x || !w || !ell || !box || !pairs || !masks || !scratch || !out) return bad("NULL pointer");
+    for (int i = 0; i < 2 * npairs; ++i)
+        if (pairs[i] < 0 || pairs[i] >= q_all) return bad("pairs must hold component indices in [0, q_all)");
+    if ((rc = sobol_masks_check(masks, nsub, d))) return rc;
+    return do_sobol_subset_pairs<SOBOL_VEC>((hipStream_t)stream, kernel_id, n, d, q_all, x, w, ell, box, pairs, npairs, masks, nsub,
+                                            scratch, out, SobolQ{nullptr, 0, 0});
+}
+
+int lcgp_sobol_matrix_subset_pairs(void* stream, int dtype, int kernel_id, int n, int d, int p, int q_local, const double* x,
+                                   const double* v, const double* ell, const double* box, const void* workspace, const int* ks,
+                                   int nks, const uint64_t* masks, int nsub, void* scratch, double* out) {
+    if (dtype != LCGP_F64) return bad("lcgp_sobol_matrix_subset_pairs reads a float64 workspace");
+    int rc = check_common(dtype, n, d, p, q_local, kernel_id);
+    if (rc) return rc;
+    if ((rc = sobol_subset_check(n, d, q_local, 1, nsub))) return rc;
+    if (nks < 1) return bad("nks < 1");
+    if (!x || !v || !ell || !box || !workspace || !ks || !masks || !scratch || !out) return bad("NULL pointer");
+    std::vector<int> pairs(2 * (size_t)nks);
+    for (int i = 0; i < nks; ++i) {
+        if (ks[i] < 0 || ks[i] >= q_local) return bad("ks must hold local component indices in [0, q_local)");
+        pairs[2 * i] = pairs[2 * i + 1] = ks[i];
+    }
+    if ((rc = sobol_masks_check(masks, nsub, d))) return rc;
+    Ws w = carve(dtype, n, d, p, q_local, (void*)workspace);
+    const SobolQ qm{(const double*)(w.base + w.off_V), w.mat, w.npad};
+    return do_sobol_subset_pairs<SOBOL_MAT>((hipStream_t)stream, kernel_id, n, d, q_local, x, v, ell, box, pairs.data(), nks, masks,
+                                            nsub, scratch, out, qm);
+}
+
+int lcgp_condition_sobol_subset_scratch_bytes(int n, int d, int q_local, int m, int nks, int nsub, size_t* bytes) {
+    if (n < 1) return bad("n < 1");
+    if (d > SOBOL_SUBSET_DMAX) return bad("the subset pass takes d in [1, 16] (a mask addresses 16 inputs; no d > 16 variant)");
+    int rc = cond_sobol_check(n, d, q_local, m, nks);
+    if (rc) return rc;
+    if (nsub < 1) return bad("nsub < 1");
+    if (!bytes) return bad("bytes is NULL");
+    *bytes = cond_sobol_carve(n, d, q_local, m, true).total;
+    return 0;
+}
+
+int lcgp_condition_sobol_matrix_subset_pairs(void* stream, int dtype, int kernel_id, int n, int d, int p, int q_local,
+                                             const double* theta, const void* workspace, const void* state, int m, const double* xa,
+                                             const double* v, const double* ell, const double* box, const int* ks, int nks,
+                                             const uint64_t* masks, int nsub, void* scratch, size_t scratch_bytes, double* out) {
+    if (dtype != LCGP_F64) return bad("lcgp_condition_sobol_matrix_subset_pairs reads a float64 workspace and a float64 state");
+    int rc = check_common(dtype, n, d, p, q_local, kernel_id);
+    if (rc) return rc;
+    if (d > SOBOL_SUBSET_DMAX) return bad("the subset pass takes d in [1, 16] (a mask addresses 16 inputs; no d > 16 variant)");
+    if ((rc = cond_sobol_check(n, d, q_local, m, nks))) return rc;
+    if (nsub < 1) return bad("nsub < 1");
+    if (!theta || !workspace || !state || !xa || !v || !ell || !box || !ks || !masks || !scratch || !out) return bad("NULL pointer");
+    for (int i = 0; i < nks; ++i)
+        if (ks[i] < 0 || ks[i] >= q_local) return bad("ks must hold local component indices in [0, q_local)");
+    if ((rc = sobol_masks_check(masks, nsub, d))) return rc;
+    if (scratch_bytes < cond_sobol_carve(n, d, q_local, m, true).total)
+        return bad("scratch too small (lcgp_condition_sobol_subset_scratch_bytes)");
+    Ws w = carve(dtype, n, d, p, q_local, (void*)workspace);
+    w.kern = kernel_id;
+    return do_condition_sobol((hipStream_t)stream, w, theta, state, m, xa, v, ell, box, ks, nks, scratch, out, masks, nsub);
 }
 
 }  // extern "C"

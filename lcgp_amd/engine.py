@@ -604,6 +604,125 @@ class HotPathEngine:
             res = out.cpu().numpy()
         return res[:, :2 * d + 1].copy(), res[:, 2 * d + 1].copy()
 
+    # ---- the same three passes for a caller's list of input subsets ----
+    def _subset_masks(self, masks, d, what):
+        """the checked uint64 masks (bit l set: input l is in the subset) of a subset pass over d inputs"""
+        masks = np.ascontiguousarray(masks, np.uint64).reshape(-1)
+        if d > 16:
+            raise ValueError("%s: the subset pass takes at most 16 inputs (d = %d)" % (what, d))
+        if masks.shape[0] < 1 or np.any(masks >> np.uint64(d)):
+            raise ValueError("%s: needs at least one mask, and no mask may have a bit at or above d = %d" % (what, d))
+        return masks
+
+    def sobol_subset_pairs(self, x, w, ell, box, pairs, masks):
+        """sobol_pairs for a list of subsets of the inputs (lcgp_sobol_subset_pairs): masks (nsub,) bit masks, bit
+        l set when input l is in the subset u; the other arguments as there.  Returns host arrays (D (npairs, nsub), means
+        (npairs,)): D[r, s] = D_u of the pair for u = masks[s] (the empty mask: exactly 0); means as sobol_pairs returns them.
+        lcgp_sobol_subset_chunk(d) masks per launch; d <= 16."""
+        torch = self.torch
+        x = np.ascontiguousarray(x, np.float64)
+        w = np.ascontiguousarray(w, np.float64)
+        ell = np.ascontiguousarray(ell, np.float64)
+        box = np.ascontiguousarray(box, np.float64)
+        pairs = np.ascontiguousarray(pairs, np.int32)
+        n, d = x.shape
+        q_all, npairs = w.shape[0], pairs.shape[0]
+        assert w.shape == (q_all, n) and ell.shape == (q_all, d) and box.shape == (2, d) and pairs.shape == (npairs, 2)
+        masks = self._subset_masks(masks, d, "sobol_subset_pairs")
+        nsub = masks.shape[0]
+        if not np.all(box[1] > box[0]):
+            raise ValueError("sobol_subset_pairs: the box needs hi > lo in every dimension")
+        with torch.cuda.device(self.device):
+            dev = [torch.as_tensor(a).to(self.device) for a in (x, w, ell, box)]
+            scratch = self._grow_scratch(self._nbytes("lcgp_sobol_subset_scratch_bytes", n, d, q_all, npairs, nsub),
+                                         ("the Sobol subset sums", "%d tile sums of %d pairs at a time" % ((-(-n // 64)) ** 2, min(npairs, 64)),
+                                          "use fewer training inputs"))
+            out = torch.empty((npairs, nsub), dtype=torch.float64, device=self.device)
+            _hip.check(self.lib.lcgp_sobol_subset_pairs(self._stream(), self.kernel_id, n, d, q_all, *[self._p(t) for t in dev],
+                                                        pairs.ctypes.data_as(C.POINTER(C.c_int)), npairs,
+                                                        masks.ctypes.data_as(C.POINTER(C.c_uint64)), nsub, self._p(scratch),
+                                                        self._p(out)),
+                       "lcgp_sobol_subset_pairs")
+            res = out.cpu().numpy()
+            # (the box means of the components follow the table in the scratch: include/lcgp_hip.h)
+            comp = scratch[8 * q_all * d * n:8 * (q_all * d * n + q_all)].view(torch.float64).cpu().numpy()
+        means = np.where(pairs[:, 0] == pairs[:, 1], comp[pairs[:, 0]], 0.0)
+        return res, means
+
+    def sobol_matrix_subset_sums(self, x, v, ell, box, ks, masks):
+        """sobol_matrix_sums for a list of subsets of the inputs (lcgp_sobol_matrix_subset_pairs): masks (nsub,)
+        as in sobol_subset_pairs, the other arguments as there.  Returns the host array sums (len(ks), nsub) = sum Q (M_u - M_0)
+        for u = masks[s]; no S0 (the corrections of the subsets do not need it)."""
+        torch = self.torch
+        assert self.dtype == _hip.F64, "sobol_matrix_subset_sums reads the A^-1 of a float64 engine"
+        if self._theta_last is None:
+            raise RuntimeError("sobol_matrix_subset_sums() needs a preceding evaluate() at the current parameters")
+        x = np.ascontiguousarray(x, np.float64)
+        v = np.ascontiguousarray(v, np.float64)
+        ell = np.ascontiguousarray(ell, np.float64)
+        box = np.ascontiguousarray(box, np.float64)
+        ks = np.ascontiguousarray(ks, np.int32).reshape(-1)
+        n, d = x.shape
+        nks = ks.shape[0]
+        assert n == self.n and d == self.d and v.shape == (self.q_local, n) and ell.shape == (self.q_local, d) and box.shape == (2, d)
+        masks = self._subset_masks(masks, d, "sobol_matrix_subset_sums")
+        nsub = masks.shape[0]
+        if not np.all(box[1] > box[0]):
+            raise ValueError("sobol_matrix_subset_sums: the box needs hi > lo in every dimension")
+        with torch.cuda.device(self.device):
+            dev = [torch.as_tensor(a).to(self.device) for a in (x, v, ell, box)]
+            scratch = self._grow_scratch(self._nbytes("lcgp_sobol_subset_scratch_bytes", n, d, self.q_local, nks, nsub),
+                                         ("the matrix-weighted Sobol subset sums",
+                                          "%d tile sums of %d components at a time" % ((-(-n // 64)) ** 2, min(nks, 64)),
+                                          "use fewer training inputs"))
+            out = torch.empty((nks, nsub), dtype=torch.float64, device=self.device)
+            _hip.check(self.lib.lcgp_sobol_matrix_subset_pairs(
+                self._stream(), self.dtype, self.kernel_id, n, d, self.p, self.q_local, *[self._p(t) for t in dev],
+                self._p(self.workspace), ks.ctypes.data_as(C.POINTER(C.c_int)), nks, masks.ctypes.data_as(C.POINTER(C.c_uint64)),
+                nsub, self._p(scratch), self._p(out)),
+                "lcgp_sobol_matrix_subset_pairs")
+            res = out.cpu().numpy()
+        return res
+
+    def condition_sobol_matrix_subset_sums(self, state, v, ell, box, ks, masks):
+        """condition_sobol_matrix_sums for a list of subsets of the inputs (lcgp_condition_sobol_matrix_subset_pairs; DESIGN.md
+        4.25): masks (nsub,) as in sobol_subset_pairs, the other arguments as there.  Returns the host array sums (len(ks), nsub)
+        = sum Q' (M_u - M_0) over the N = n + m centres.  E is prepared once per component, whatever the number of masks."""
+        torch = self.torch
+        assert self.dtype == _hip.F64, "condition_sobol_matrix_subset_sums reads the A^-1 and the view state of a float64 engine"
+        if self._theta_last is None:
+            raise RuntimeError("condition_sobol_matrix_subset_sums() needs a preceding evaluate() at the current parameters")
+        n, d, m = self.n, self.d, state['m']
+        N = n + m
+        v = np.ascontiguousarray(v, np.float64)
+        ell = np.ascontiguousarray(ell, np.float64)
+        box = np.ascontiguousarray(box, np.float64)
+        ks = np.ascontiguousarray(ks, np.int32).reshape(-1)
+        nks = ks.shape[0]
+        assert v.shape == (self.q_local, N) and ell.shape == (self.q_local, d) and box.shape == (2, d)
+        masks = self._subset_masks(masks, d, "condition_sobol_matrix_subset_sums")
+        nsub = masks.shape[0]
+        if not np.all(box[1] > box[0]):
+            raise ValueError("condition_sobol_matrix_subset_sums: the box needs hi > lo in every dimension")
+        with torch.cuda.device(self.device):
+            self._condition_grad_state(state)
+            xa = torch.cat([self.x, state['xn']]).contiguous()           # (float64: the engine's dtype)
+            dev = [torch.as_tensor(a).to(self.device) for a in (v, ell, box)]
+            npad_all = -(-N // 64) * 64
+            scratch = self._grow_scratch(self._nbytes("lcgp_condition_sobol_subset_scratch_bytes", n, d, self.q_local, m, nks, nsub),
+                                         ("the matrix-weighted Sobol subset sums of a conditioned view",
+                                          "one component's %d x %d matrix E and %d tile sums" % (npad_all, npad_all, (npad_all // 64) ** 2),
+                                          "condition on fewer new inputs at a time"))
+            out = torch.empty((nks, nsub), dtype=torch.float64, device=self.device)
+            _hip.check(self.lib.lcgp_condition_sobol_matrix_subset_pairs(
+                self._stream(), self.dtype, self.kernel_id, n, d, self.p, self.q_local, self._p(self.theta_dev),
+                self._p(self.workspace), self._p(state['state']), m, self._p(xa), *[self._p(t) for t in dev],
+                ks.ctypes.data_as(C.POINTER(C.c_int)), nks, masks.ctypes.data_as(C.POINTER(C.c_uint64)), nsub, self._p(scratch),
+                scratch.numel(), self._p(out)),
+                "lcgp_condition_sobol_matrix_subset_pairs")
+            res = out.cpu().numpy()
+        return res
+
     def condition_mean_vectors(self, state):
         """(z' (q_local, n), w (q_local, m)) of the view `state` on the host: its mean surface is X_0 z' + c^x(x0, xn) w (the grad
         state of lcgp_condition_grad_prepare, built on first use)"""

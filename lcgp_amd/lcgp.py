@@ -17,6 +17,7 @@ Deliberate differences from the reference, all documented in DESIGN.md:
 """
 from __future__ import annotations
 
+import math
 import zlib
 
 import numpy as np
@@ -316,7 +317,11 @@ class SobolIndices:
     uncertainty at the fitted parameters: expected_variance (p_sel,) = E[V], expected_first_variance = E[V_l] and
     expected_closed_variance = E[V_~l] (p_sel, d), each the plug-in value plus a correction >= 0; first_expected = E[V_l] /
     E[V] and total_expected = 1 - E[V_~l] / E[V], ratios of expectations (NaN where E[V] is exactly 0); and
-    integrated_variance (p_sel,), the posterior variance of the continuous surface averaged over the box."""
+    integrated_variance (p_sel,), the posterior variance of the continuous surface averaged over the box.
+    With order=2 also (None otherwise) the second-order terms: second_variance (p_sel, d, d), the variance
+    V_lm = V^c_{lm} - V_l - V_m of the interaction of inputs l and m alone, and second = V_lm / V; both symmetric with a NaN
+    diagonal.  With order=2 and uncertainty=True: expected_second_variance = E[V^c_{lm}] - E[V_l] - E[V_m] and second_expected,
+    its ratio to E[V]."""
 
     def __init__(self, first, total, variance, mean, first_variance, closed_variance, expected_variance=None,
                  expected_first_variance=None, expected_closed_variance=None, first_expected=None, total_expected=None,
@@ -326,9 +331,46 @@ class SobolIndices:
         self.expected_variance, self.integrated_variance = expected_variance, integrated_variance
         self.expected_first_variance, self.expected_closed_variance = expected_first_variance, expected_closed_variance
         self.first_expected, self.total_expected = first_expected, total_expected
+        self.second = self.second_variance = self.expected_second_variance = self.second_expected = None
 
     def __repr__(self):
         return 'SobolIndices(outputs=%d, d=%d)' % tuple(self.first.shape)
+
+
+class SobolSubsets:
+    """sobol_subsets(): for the list `subsets` (tuples of input indices, as asked for) closed_variance (p_sel, S), the closed
+    variance V^c_u = Var_{x_u} E[f | x_u] of the posterior mean surface over the box under the uniform measure -- what the
+    inputs in u explain together, their interactions among themselves included -- and closed = V^c_u / V (NaN where V is
+    exactly 0); variance (p_sel,) = V and mean (p_sel,), as in SobolIndices.  The empty subset has V^c exactly 0, the full one V.
+    The total index of a group u is 1 - closed of its complement.  Rounding is not clamped.
+    With uncertainty=True also (None otherwise) the posterior expectations expected_closed_variance = E[V^c_u] (p_sel, S),
+    expected_variance = E[V] (p_sel,) and closed_expected = E[V^c_u] / E[V], a ratio of expectations."""
+
+    def __init__(self, subsets, closed_variance, closed, variance, mean, expected_closed_variance=None, closed_expected=None,
+                 expected_variance=None):
+        self.subsets, self.closed_variance, self.closed, self.variance, self.mean = subsets, closed_variance, closed, variance, mean
+        self.expected_closed_variance, self.closed_expected = expected_closed_variance, closed_expected
+        self.expected_variance = expected_variance
+
+    def __repr__(self):
+        return 'SobolSubsets(outputs=%d, subsets=%d)' % tuple(self.closed_variance.shape)
+
+
+class ShapleyEffects:
+    """shapley_effects(): effects (p_sel, d), the Shapley effect of every input on every selected output: the average over all
+    orders in which the inputs can be added of the closed variance input l adds, sum_{u without l} |u|! (d - |u| - 1)! / d!
+    (V^c_{u + l} - V^c_u).  Unlike first and total indices the effects of an output add up to its variance V (variance,
+    (p_sel,)), interactions shared equally among their inputs, and first_variance <= effect <= V - closed_variance of the
+    others; shares = effects / V (NaN where V is exactly 0).  From the closed variances of all 2^d subsets, exact.
+    With uncertainty=True also (None otherwise) effects_expected, the same sum over the posterior expectations E[V^c_u], which
+    add up to expected_variance = E[V], and shares_expected = effects_expected / E[V]."""
+
+    def __init__(self, effects, shares, variance, effects_expected=None, shares_expected=None, expected_variance=None):
+        self.effects, self.shares, self.variance = effects, shares, variance
+        self.effects_expected, self.shares_expected, self.expected_variance = effects_expected, shares_expected, expected_variance
+
+    def __repr__(self):
+        return 'ShapleyEffects(outputs=%d, d=%d)' % tuple(self.effects.shape)
 
 
 class ConditionedLCGP:
@@ -574,7 +616,42 @@ class ConditionedLCGP:
 
         return base._sobol_matrix(bs, eng, local_sums)
 
-    def sobol_indices(self, box=None, outputs=None, latent=False, uncertainty=False):
+    def _sobol_context(self, box):
+        """LCGP._sobol_context of the conditioned model: the centres [x; x_new], the view's mean weights and its matrix Q'"""
+        base = self.base
+        bs = base._marginal_box(box)
+        eng, state = self._float64_state()
+        xa, w = self._mean_weights(eng, state)
+        n, m = int(base.n), self.m
+
+        def matrix(masks):
+            def local_sums(loc, c, Dk, sr, ell):
+                v = c[loc][:, None] * np.concatenate([np.broadcast_to(sr[None, :], (len(loc), n)), np.ones((len(loc), m), F64)], axis=1)
+                return eng.condition_sobol_matrix_subset_sums(state, v, ell[loc], bs, np.arange(len(loc)), masks)
+            return base._sobol_subset_matrix(bs, masks, eng, local_sums)
+
+        return eng, xa, w, bs, matrix
+
+    def sobol_subsets(self, subsets, box=None, outputs=None, latent=False, uncertainty=False):
+        """LCGP.sobol_subsets() of the conditioned model: the SobolSubsets GIVEN the base model's data and this
+        view's new runs, equal to rounding to those of a model built on the augmented data at the same parameters.  The
+        plug-in part is the vector pass on the n + m centres, uncertainty=True adds the matrix-weighted pass with the view's
+        Q' (lcgp_condition_sobol_matrix_subset_pairs; E is formed once per component).  Arguments, checks, errors and fields
+        are the model's.  RuntimeError when the view is stale."""
+        base = self.base
+        outputs = base._sobol_rows(outputs, latent)
+        subsets, masks = base._subset_masks(subsets)
+        return base._sobol_subsets_result(self._sobol_context(box), subsets, masks, outputs, latent, uncertainty)
+
+    def shapley_effects(self, box=None, outputs=None, latent=False, uncertainty=False):
+        """LCGP.shapley_effects() of the conditioned model; arguments, checks, errors and fields are the
+        model's.  RuntimeError when the view is stale."""
+        base = self.base
+        outputs = base._sobol_rows(outputs, latent)
+        base._shapley_check()
+        return base._shapley_result(self._sobol_context(box), outputs, latent, uncertainty)
+
+    def sobol_indices(self, box=None, outputs=None, latent=False, uncertainty=False, order=1):
         """LCGP.sobol_indices() of the conditioned model: the SobolIndices GIVEN the base model's data and this view's new runs,
         equal to rounding to those of a model built on the augmented data at the same parameters; nothing of size n is
         factorised.  The mean surface is a kernel expansion over the n + m centres [x; x_new], so the plug-in
@@ -582,14 +659,19 @@ class ConditionedLCGP:
         component, weighted by A^-1 in place plus the view's rank-m term (lcgp_condition_sobol_matrix_pairs).  Arguments,
         defaults, checks, errors, shapes and the fields are the model's; the default box is the base model's (main_effects()).
         Always float64: the view of a float32 model builds a float64 state once on the base model's float64 engine and keeps
-        it.  Any number of ranks, the result does not depend on it.  RuntimeError when the view is stale."""
+        it.  Any number of ranks, the result does not depend on it.  RuntimeError when the view is stale.
+        order=2 adds the second-order fields by one more pass over the d (d - 1) / 2 pair masks."""
         base = self.base
+        base._sobol_order(order)
         outputs = base._sobol_rows(outputs, latent)
         bs = base._marginal_box(box)
         eng, state = self._float64_state()
         xa, w = self._mean_weights(eng, state)
         V, mean = base._sobol_mean(eng, xa, w, bs, latent)
-        return base._sobol_result(V, mean, outputs, latent, (lambda: self._sobol_matrix(bs, eng, state)) if uncertainty else None)
+        res = base._sobol_result(V, mean, outputs, latent, (lambda: self._sobol_matrix(bs, eng, state)) if uncertainty else None)
+        if order == 2:
+            base._sobol_second(res, self._sobol_context(box), outputs, latent, uncertainty)
+        return res
 
     def integrated_variance(self, box=None, outputs=None, latent=False):
         """LCGP.integrated_variance() of the conditioned model: (p_sel,) the exact IMSPE after the view's new runs, what a
@@ -2856,7 +2938,7 @@ class LCGP:
     # =============================================================================================
     # Sobol indices of the posterior mean surface in closed form (beyond the reference)
     # =============================================================================================
-    def sobol_indices(self, box=None, outputs=None, latent=False, uncertainty=False):
+    def sobol_indices(self, box=None, outputs=None, latent=False, uncertainty=False, order=1):
         """First-order and total Sobol indices of every output with respect to every input: the share of the output's variance
         over `box` ((2, d) raw scale, default the training inputs' bounding box; uniform measure) that input l explains alone
         (first) and together with all its interactions (total).  They are those of the posterior mean surface at the fitted
@@ -2873,7 +2955,13 @@ class LCGP:
         total_expected, integrated_variance): with few runs the plug-in indices understate the variance, and an
         input the data say nothing about gets a plug-in index of exactly zero.  One more pass over the pairs k = k' (on the rank
         that owns the component, weighted by its A^-1 in place: lcgp_sobol_matrix_pairs) and one more reduction; the fields
-        above are bitwise the same with and without it."""
+        above are bitwise the same with and without it.
+        order=2: the SobolIndices also carries the second-order terms second_variance[l, m] = V^c_{lm} - V_l - V_m and second
+        = second_variance / V, (p_sel, d, d), symmetric with a NaN diagonal -- which inputs interact -- and with
+        uncertainty=True their expectations expected_second_variance and second_expected: one more pass over the d (d - 1) / 2
+        pair masks (lcgp_sobol_subset_pairs; d <= 16).  order=1 (the default) leaves them None and every other
+        field bitwise what it is without the argument; any other order raises ValueError."""
+        self._sobol_order(order)
         outputs = self._sobol_rows(outputs, latent)
         bs = self._marginal_box(box)
         eng = self._ensure_aux64()
@@ -2883,7 +2971,215 @@ class LCGP:
         scale_k, nug = self.lLmb0.numpy(), self.lnugGPs.numpy()
         w = (scale_k * (1.0 - nug / (1.0 + nug)))[:, None] * sr[None, :] * z
         V, mean = self._sobol_mean(eng, self._x_train(), w, bs, latent)
-        return self._sobol_result(V, mean, outputs, latent, (lambda: self._sobol_matrix(bs)) if uncertainty else None)
+        res = self._sobol_result(V, mean, outputs, latent, (lambda: self._sobol_matrix(bs)) if uncertainty else None)
+        if order == 2:
+            self._sobol_second(res, (eng, self._x_train(), w, bs, lambda masks: self._sobol_subset_matrix(bs, masks)), outputs,
+                               latent, uncertainty)
+        return res
+
+    # =============================================================================================
+    # Closed variances of arbitrary input subsets: groups, second-order indices, Shapley effects
+    # =============================================================================================
+    def sobol_subsets(self, subsets, box=None, outputs=None, latent=False, uncertainty=False):
+        """The closed variance V^c_u = Var_{x_u} E[f | x_u] of every subset u in `subsets` (a sequence of sequences of input
+        indices; the empty and the full set are allowed) for every selected output: what a group of inputs explains together,
+        exact for the product kernels as sobol_indices is (same box, measure, outputs= and latent=).  Returns a SobolSubsets
+        (subsets, closed_variance (p_sel, S), closed = V^c_u / V, variance, mean).  The call appends the full set itself, so V
+        and the ratios come from the same pass: lcgp_sobol_subset_pairs, lcgp_sobol_subset_chunk(d) subsets per launch over
+        the pair integrals of an element, further subsets in further launches.  Float64 always; the pairs of components are
+        dealt over the ranks as in sobol_indices and the result does not depend on their number.
+        uncertainty=True adds expected_closed_variance = V^c_u + C_u, closed_expected and expected_variance (4.23's formula
+        holds for any u; one matrix-weighted pass on the owner of each component and one more reduction).
+        ValueError: an index outside [0, d), an index repeated inside a subset, d > 16."""
+        outputs = self._sobol_rows(outputs, latent)
+        subsets, masks = self._subset_masks(subsets)
+        return self._sobol_subsets_result(self._sobol_context(box), subsets, masks, outputs, latent, uncertainty)
+
+    def shapley_effects(self, box=None, outputs=None, latent=False, uncertainty=False):
+        """Shapley effects of every input on every selected output: an attribution of the output's variance V over the box to
+        the inputs whose shares ADD UP to V, interactions (and, with correlated effects, overlaps) shared equally -- between
+        the first-order and the total variance of each input.  They need the closed variances of all 2^d subsets, which
+        sampling cannot afford and the closed form gets from 2^d / lcgp_sobol_subset_chunk(d) passes.  Returns a
+        ShapleyEffects (effects (p_sel, d), shares = effects / V, variance); the weights |u|! (d - |u| - 1)! / d! are applied
+        on the host in float64.  box, outputs, latent and the ranks as in sobol_subsets.  uncertainty=True adds
+        effects_expected, shares_expected and expected_variance from the posterior expectations E[V^c_u].
+        ValueError: d > 10 (more than 1024 subsets)."""
+        outputs = self._sobol_rows(outputs, latent)
+        self._shapley_check()
+        return self._shapley_result(self._sobol_context(box), outputs, latent, uncertainty)
+
+    @staticmethod
+    def _sobol_order(order):
+        if order not in (1, 2) or isinstance(order, bool):
+            raise ValueError('order must be 1 (first-order and total indices) or 2 (also the second-order indices), not %r' % (order,))
+
+    def _shapley_check(self):
+        if int(self.d) > 10:
+            raise ValueError('shapley_effects needs the closed variances of all 2^d subsets: d = %d > 10 is refused (more than '
+                             '1024 subsets)' % int(self.d))
+
+    def _subset_masks(self, subsets):
+        """the checked subsets as a list of tuples (in the order given) and their bit masks (uint64; bit l: input l is in u)"""
+        d = int(self.d)
+        if d > 16:
+            raise ValueError('the subset pass takes at most 16 inputs (d = %d); sobol_indices() has no such limit' % d)
+        if isinstance(subsets, (str, bytes)) or not hasattr(subsets, '__iter__'):
+            raise ValueError('subsets must be a sequence of sequences of input indices')
+        out, masks = [], []
+        for u in subsets:
+            if isinstance(u, (str, bytes)) or not hasattr(u, '__iter__'):
+                raise ValueError('subsets must be a sequence of sequences of input indices')
+            u = tuple(int(l) for l in u)
+            if any(l < 0 or l >= d for l in u):
+                raise ValueError('a subset holds an input index outside [0, %d): %r' % (d, u))
+            if len(set(u)) != len(u):
+                raise ValueError('a subset repeats an input index: %r' % (u,))
+            out.append(u)
+            masks.append(sum(1 << l for l in u))
+        return out, np.array(masks, np.uint64)
+
+    def _sobol_context(self, box):
+        """what a subset pass works on: (float64 engine or None, centres (N, d) standardised, weights w (q, N) of the mean
+        surface of ALL components, the standardised box, matrix(masks) -> C (q, nsub) of _sobol_subset_matrix)"""
+        bs = self._marginal_box(box)
+        eng = self._ensure_aux64()
+        n = int(self.n)
+        sr = np.sqrt(_np(self.r)) if self.submethod == 'rep' else np.ones(n, F64)
+        z = self._fetch_all(lambda e, i: e.fetch_vector(1, i), n)
+        scale_k, nug = self.lLmb0.numpy(), self.lnugGPs.numpy()
+        w = (scale_k * (1.0 - nug / (1.0 + nug)))[:, None] * sr[None, :] * z
+        return eng, self._x_train(), w, bs, lambda masks: self._sobol_subset_matrix(bs, masks)
+
+    def _sobol_subset_mean(self, eng, xc, w, bs, latent, masks):
+        """_sobol_mean for the subsets `masks`: (V (rows, nsub), mean (rows,)) for all p outputs (latent: the q components).  The
+        pairs are dealt round-robin over the ranks that hold an engine; one reduction assembles them."""
+        q, nsub = int(self.q), len(masks)
+        ell = self.lLmb.numpy()
+        pairs = np.array([(k, k) for k in range(q)] if latent else [(k, kp) for k in range(q) for kp in range(k, q)], np.int32)
+        rank, world = _dist.rank_world(self._group)
+        mine = np.arange(rank, len(pairs), min(world, q)) if eng is not None else np.zeros(0, int)
+        full = np.zeros((len(pairs), nsub + 1), F64)
+
+        def share():
+            if len(mine):
+                full[mine, :nsub], full[mine, nsub] = eng.sobol_subset_pairs(xc, w, ell, bs, pairs[mine], masks)
+
+        self._agree(share, what='the Sobol subset sums')
+        if _dist.use_collectives(self._group):
+            full = _dist.all_reduce_sum(full.reshape(-1), self._group, None if eng is None else eng.device).reshape(full.shape)
+        D = np.zeros((q, q, nsub), F64)
+        means = np.zeros(q, F64)
+        for (k, kp), row in zip(pairs, full):
+            D[k, kp] = D[kp, k] = row[:nsub]
+            if k == kp:
+                means[k] = row[nsub]
+        if latent:
+            return D[np.arange(q), np.arange(q)], means
+        W, _, scale, offset = self._output_map()
+        return np.einsum('ka,la,klu->au', W, W, D) * (scale ** 2)[:, None], offset + scale * (W.T @ means)
+
+    def _sobol_subset_matrix(self, bs, masks, eng=None, local_sums=None):
+        """_sobol_matrix's first line for the subsets `masks`, per latent component: C (q, nsub) with
+            C_u = c (prod_{l not in u} I2_l - prod_l I2_l) - sum Q (M_u - M_0)            E[V^c_u] - V^c_u(mean)
+        (4.23's formula holds for any u).  Every rank evaluates the components it holds (lcgp_sobol_matrix_subset_pairs) and one
+        reduction completes the array; a conditioned view passes its engine and local_sums(loc, c, Dk, sr, ell) -> sums."""
+        d, q, n, nsub = int(self.d), int(self.q), int(self.n), len(masks)
+        if local_sums is None:
+            eng = self._ensure_aux64()
+        sr = np.sqrt(_np(self.r)) if self.submethod == 'rep' else np.ones(n, F64)
+        ell, scale_k, nug = self.lLmb.numpy(), self.lLmb0.numpy(), self.lnugGPs.numpy()
+        c = scale_k * (1.0 - nug / (1.0 + nug))
+        Dk = _np(self.diag_D).reshape(-1)
+        full = np.zeros((q, nsub), F64)
+
+        def share():
+            if eng is not None:
+                loc = [int(k) for k in self._local_ks]
+                if local_sums is not None:
+                    full[loc] = local_sums(loc, c, Dk, sr, ell)
+                    return
+                v = (c[loc] * np.sqrt(Dk[loc]))[:, None] * sr[None, :]
+                full[loc] = eng.sobol_matrix_subset_sums(self._x_train(), v, ell[loc], bs, np.arange(len(loc)), masks)
+
+        self._agree(share, what='the matrix-weighted Sobol subset sums')
+        if _dist.use_collectives(self._group):
+            full = _dist.all_reduce_sum(full.reshape(-1), self._group, None if eng is None else eng.device).reshape(full.shape)
+        width = bs[1] - bs[0]
+        inside = ((np.asarray(masks, np.uint64)[:, None] >> np.arange(d, dtype=np.uint64)[None, :]) & np.uint64(1)).astype(bool)
+        prior = np.ones((q, nsub), F64)                        # prod of I2 over the inputs NOT in u, l ascending
+        i2all = np.ones(q, F64)
+        for k in range(q):
+            for l in range(d):
+                i2 = _box_double_average(self.kernel, float(width[l] / ell[k, l]))
+                prior[k] = np.where(inside[:, l], prior[k], prior[k] * i2)
+                i2all[k] *= i2
+        return c[:, None] * (prior - i2all[:, None]) - full
+
+    def _sobol_subset_pass(self, ctx, masks, latent, uncertainty):
+        """(V (rows, nsub), mean (rows,), E (rows, nsub) or None) of ALL rows (the p outputs; latent: the q components)"""
+        eng, xc, w, bs, matrix = ctx
+        V, mean = self._sobol_subset_mean(eng, xc, w, bs, latent, masks)
+        E = V + self._latent_variance_to_rows(matrix(masks), latent) if uncertainty else None
+        return V, mean, E
+
+    @staticmethod
+    def _ratio(num, den):
+        """num / den along the first axis, NaN where den is exactly 0"""
+        den = den.reshape((-1,) + (1,) * (num.ndim - 1))
+        with np.errstate(divide='ignore', invalid='ignore'):
+            return np.where(den == 0.0, np.nan, num / den)
+
+    def _sobol_subsets_result(self, ctx, subsets, masks, outputs, latent, uncertainty):
+        d = int(self.d)
+        masks = np.concatenate([masks, np.array([(1 << d) - 1], np.uint64)])           # (the full set: V from the same pass)
+        V, mean, E = self._sobol_subset_pass(ctx, masks, latent, uncertainty)
+        V, mean = V[outputs], mean[outputs]
+        plug = (subsets, _t(V[:, :-1].copy()), _t(self._ratio(V[:, :-1], V[:, -1])), _t(V[:, -1].copy()), _t(mean.copy()))
+        if not uncertainty:
+            return SobolSubsets(*plug)
+        E = E[outputs]
+        return SobolSubsets(*plug, _t(E[:, :-1].copy()), _t(self._ratio(E[:, :-1], E[:, -1])), _t(E[:, -1].copy()))
+
+    def _sobol_second(self, res, ctx, outputs, latent, uncertainty):
+        """fills the second-order fields of the SobolIndices res from one pass over the pair masks"""
+        d = int(self.d)
+        il, im = np.triu_indices(d, 1)
+        masks = np.array([(1 << int(l)) | (1 << int(m)) for l, m in zip(il, im)], np.uint64)
+
+        def spread(Vc, first, var):
+            sv = np.full((len(outputs), d, d), np.nan, F64)
+            if len(masks):
+                sv[:, il, im] = sv[:, im, il] = Vc - first[:, il] - first[:, im]
+            return _t(sv), _t(self._ratio(sv, var))
+
+        V = E = np.zeros((len(outputs), 0), F64)
+        if len(masks):
+            V, _, E = self._sobol_subset_pass(ctx, masks, latent, uncertainty)
+            V, E = V[outputs], (E[outputs] if uncertainty else None)
+        res.second_variance, res.second = spread(V, _np(res.first_variance), _np(res.variance))
+        if uncertainty:
+            res.expected_second_variance, res.second_expected = spread(E, _np(res.expected_first_variance), _np(res.expected_variance))
+
+    def _shapley_result(self, ctx, outputs, latent, uncertainty):
+        d = int(self.d)
+        masks = np.arange(1 << d, dtype=np.uint64)             # (mask s IS the index of its column)
+        V, _, E = self._sobol_subset_pass(ctx, masks, latent, uncertainty)
+        size = np.array([bin(s).count('1') for s in range(1 << d)])
+        fact = [float(math.factorial(j)) for j in range(d + 1)]
+        wt = np.array([fact[j] * fact[d - j - 1] / fact[d] if j < d else 0.0 for j in range(d + 1)], F64)
+
+        def effects(Vc):
+            Vc = Vc[outputs]
+            eff = np.zeros((len(outputs), d), F64)
+            for l in range(d):
+                without = np.array([s for s in range(1 << d) if not (s >> l) & 1])
+                eff[:, l] = (Vc[:, without | (1 << l)] - Vc[:, without]) @ wt[size[without]]
+            var = Vc[:, -1]
+            return _t(eff), _t(self._ratio(eff, var)), _t(var.copy())
+
+        if not uncertainty:
+            return ShapleyEffects(*effects(V))
+        return ShapleyEffects(*effects(V), *effects(E))
 
     def _sobol_mean(self, eng, xc, w, bs, latent):
         """The variances of the conditional means and the box mean of a mean surface given as a kernel expansion: centres xc

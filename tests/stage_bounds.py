@@ -8,7 +8,12 @@ the packed Hessians; lcgp_predict_gradcov: dghat, Gamma and its weighted sum M) 
 with the averaged prior, the view's stages and gcov) and of the two parameter-space queries (lcgp_nll_hess: xs and the two
 closed-form vectors, the mirrored A^-1 with G_scale and G_nug, d_iA, y_i, G_i, the trace partials, the contraction slots, u_i / dot
 / YP / Q, the three output blocks; lcgp_predict_paramgrad: y_j, T, the row dots, the 3 d + 8 row sums, YT and V YT, the three
-outputs -- with hess_layout / pgrad_layout restating the scratch layouts).
+outputs -- with hess_layout / pgrad_layout restating the scratch layouts) and of the Sobol pair and subset passes (lcgp_sobol_pairs,
+lcgp_sobol_subset_pairs: the table and the box means, every element on its own against mpmath through one-hot weights, every tile
+sum, the rows of every batch and the reduction; lcgp_sobol_matrix_pairs with A^-1 as the weight matrix and the S0 column;
+lcgp_condition_sobol_matrix_pairs: P, the lower tiles of E = P P^T, then the tiles with Q' = E + D A^-1 -- sobol_layout /
+sobol_subset_layout / cond_sobol_layout restating the scratch; float64 only, in numpy on the host: its references are mpmath and
+tests/sobol_ref.py).
 
 Every check compares one stage of the library with a plain float64 reference computed from THE LIBRARY'S OWN INPUT TO THAT
 STAGE (the fetched A for the Cholesky, the fetched L for L^-1, ...), so no bound carries a condition number.  Entries are
@@ -2304,3 +2309,543 @@ def check_pp_out(dghat, dgvar, dnoise, sums, rd, VY, th, d, p, n0) -> Check:
     c3 = _pworst("pp_out", (dn + 0.5 * ps[None, :] * VY).abs(), C * _U64 * 2.0 * (0.5 * ps[None, :] * VY).abs(), 1,
                  lambda pos: ("dghat_noise", int(pos[1]), int(pos[0]) // TS))
     return combine(c1, c2, c3)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# Sobol pair sums (lcgp_sobol_pairs, lcgp_sobol_subset_pairs): sobol_table_kernel (the table is marg_I1:
+# check_marg_table's bound; the box means) -> sobol_pair_kernel / sobol_pair_wide_kernel / sobol_subset_kernel (the tile sums
+# part[pair, r, c, s]) -> sobol_reduce_kernel / sobol_subset_reduce_kernel (out).  Float64 only.
+#
+#   sobol_means    means[k] against sum_i w_ki prod_l tab from the LIBRARY'S table: gamma_(d + n) on the absolute sum
+#   sobol_element  one-hot weights w_k = e_(i_k): the row of pair (k, k') is (M_u - M_0)[i_k, i_k'] of ONE element, every other
+#                  element enters as fma(0, finite, acc); each column against mpmath (sobol_exact_J, marg_exact)
+#   sobol_tile     every part[pair, r, c, s] against twice sum_tile wgt (M_u - M_0) from the library's table, the caller's w
+#                  and J of tests/sobol_ref.py (which sobol_element's constants tie to mpmath)
+#   sobol_reduce   out against the sum of the library's own part
+#
+# The bound of an element is relative to M_u + M_0, not to M_u - M_0: the kernel forms the two products and subtracts them, so
+# what it can promise is u E_u M_u + u E_0 M_0 (E: the error constants of the factors and the multiplications), and the
+# difference of two nearly equal products keeps that absolute error.  Constants:
+#   a_l     the relative form of marg_table_bound (the 1-D average, against mpmath), per element
+#   J_l SE  derived below from sobol_dim / sobol_J (_sobol_se_bound), with the input-conditioning terms
+#   J_l Matern  SOBOL_KJ: no short derivation covers the 30-term chain, the two recurrences and the three segments, so the
+#           constant is the worst error of the REFERENCE tests/sobol_ref.pair_integral against mpmath over sobol_cases, in units
+#           of u relative to J, per kernel and per branch class (outer / middle segment x series / forward recurrence), measured
+#           on the CPU (profiles/stage_bounds_sobol.txt, "reference against mpmath"; tests/test_sobol_bounds_cpu.py re-measures
+#           and asserts the figures do not exceed the constants).  With the file's C = 4 that is four times the reference's error.
+#           The device's own ratios go to the same file and set nothing.
+#   products  M_0 is d multiplications (pa of sobol_pair_kernel, m0 of the wide kernel, sobol_subset_product(0): factors d .. DD - 1
+#           are exactly 1).  M_u: sobol_pair_kernel forms a prefix of l, the factor, a suffix of d - 1 - l and their product:
+#           d + 1 for a single input or its complement, d for all inputs; the wide kernel d; sobol_subset_product d.  All are at
+#           most |u| + d, the count used.  One rounding for a_l a'_l per input, one for the difference, one for the fma.
+# ----------------------------------------------------------------------------------------------------------------------
+SOBOL_BATCH = 64                # lcgp_hip.hip: pairs per launch
+SOBOL_CHUNK = 32                # sobol_subset.h sobol_subset_chunk(): masks per launch, both instances
+SOBOL_SERIES_BELOW = 4.0        # lcgp_hip.hip: gamma L below it the 30-term series, from it on the forward recurrence
+SOBOL_DPS = 40
+# worst |pair_integral - exact| / (u exact) over sobol_cases on the two boxes [0, 1] and [0.3, 0.75], per (kernel, segment kind,
+# branch), rounded up to an integer; the measured figures stand in profiles/stage_bounds_sobol.txt ("reference against mpmath").
+# They are far above the handful of roundings of the formulas because they are relative to J and hold the input conditioning:
+# with a length scale of 0.01 box widths the anchored exponent s0a + s0b reaches 50 to 100, and every rounding of a scaled
+# distance moves e^(-s0) by s0 u.  No derived count is smaller over this table, so the measured ones stand.
+SOBOL_KJ = {("matern32", "outer", "series"): 8.0, ("matern32", "outer", "forward"): 68.0,
+            ("matern32", "middle", "series"): 183.0, ("matern32", "middle", "forward"): 26.0,
+            ("matern52", "outer", "series"): 10.0, ("matern52", "outer", "forward"): 63.0,
+            ("matern52", "middle", "series"): 190.0, ("matern52", "middle", "forward"): 27.0}
+# The same measurement in units of u (1 + s0), s0 = s0a + s0b the anchored exponent of the element's DOMINANT segment (the smallest
+# among its non-empty segments; (1 + s) e^-s falls with s, so the other segments' conditioning is covered): the derived
+# conditioning term taken out, what is left is a constant of a few u in every class.  Both are measured bounds of the reference;
+# an element's constant is the smaller of the two, so it is never above the flat one and an order of magnitude below it where the
+# exponent is small -- which is where a wrong branch of sobol_moments shows (profiles/stage_bounds_sobol.txt, same section).
+SOBOL_KJ0 = {("matern32", "outer", "series"): 7.0, ("matern32", "outer", "forward"): 3.0,
+             ("matern32", "middle", "series"): 3.0, ("matern32", "middle", "forward"): 3.0,
+             ("matern52", "outer", "series"): 6.0, ("matern52", "outer", "forward"): 3.0,
+             ("matern52", "middle", "series"): 5.0, ("matern52", "middle", "forward"): 3.0}
+# sum of a tile: 16 serial fmas per thread, six shuffle levels (sobol_wave_sum), two additions of the four waves
+SOBOL_TILE_DEPTH = 24.0
+_SOBOL_CACHE = {}
+
+
+def sobol_layout(n, d, q_all, npairs, extra=0):
+    """do_sobol_pairs' scratch: tab (q_all, d, n), means (q_all), part (min(npairs, 64), ntile, ntile, 2 d + 1 + extra) doubles
+    (extra = 1: the matrix-weighted entries' S0); `total` in bytes (= lcgp_sobol_scratch_bytes / lcgp_sobol_matrix_scratch_bytes)"""
+    ntile = (n + TS - 1) // TS
+    nb = min(npairs, SOBOL_BATCH)
+    cols = 2 * d + 1 + extra
+    lay = dict(tab=0, means=q_all * d * n, part=q_all * d * n + q_all, ntile=ntile, nb=nb, cols=cols)
+    lay["total"] = 8 * (lay["part"] + nb * ntile * ntile * cols)
+    return lay
+
+
+def sobol_subset_layout(n, d, q_all, npairs):
+    """do_sobol_subset_pairs' scratch: tab, means, part (min(npairs, 64), ntile, ntile, SOBOL_CHUNK)"""
+    ntile = (n + TS - 1) // TS
+    nb = min(npairs, SOBOL_BATCH)
+    lay = dict(tab=0, means=q_all * d * n, part=q_all * d * n + q_all, ntile=ntile, nb=nb, cols=SOBOL_CHUNK)
+    lay["total"] = 8 * (lay["part"] + nb * ntile * ntile * SOBOL_CHUNK)
+    return lay
+
+
+def sobol_std_masks(d):
+    """the 2 d + 1 columns of lcgp_sobol_pairs as bit masks: {l}, all but l, all"""
+    full = (1 << d) - 1
+    return [1 << l for l in range(d)] + [full ^ (1 << l) for l in range(d)] + [full]
+
+
+def _np(a):
+    return np.asarray(a.detach().cpu() if isinstance(a, torch.Tensor) else a, np.float64)
+
+
+def _mp_moment(n, g, L):
+    """int_0^L tau^n e^(-g tau) dtau in mpmath for either sign of g: the series in g L below 1 (no cancellation), the closed
+    form with guard digits from there on"""
+    x = g * L
+    if abs(x) < 1:
+        s, t, j = mp.mpf(0), mp.mpf(1), 0
+        while True:
+            term = t / (n + 1 + j)
+            s += term
+            j += 1
+            t = t * (-x) / j
+            if abs(t) < mp.mpf(10) ** (-(SOBOL_DPS + 25)) or j > 400:
+                break
+        return L ** (n + 1) * s
+    with mp.extradps(30):
+        e = mp.exp(-x)
+        part = sum(x ** j / mp.factorial(j) for j in range(n + 1))
+        return +(mp.factorial(n) / g ** (n + 1) * (1 - e * part))
+
+
+def sobol_exact_J(kernel, u, a, v, b, lo, hi):
+    """J = (1 / (hi - lo)) int_lo^hi kappa(|t - u| / a) kappa(|t - v| / b) dt in mpmath (SOBOL_DPS digits) for float64 scalars
+    taken as exact.  SE: the erf form, tails through erfc (_marg_mp).  Matern: the box split at the clipped centres; on a piece
+    [p, r] neither t - u nor t - v changes sign, the integrand is a polynomial in tau = t - p times e^(-g tau) with g of either
+    sign -- always anchored at the LEFT end, no switch on g L, no recurrence: nothing shared with sobol_J but the split."""
+    _known(kernel)
+    key = (kernel, float(u), float(a), float(v), float(b), float(lo), float(hi))
+    got = _SOBOL_CACHE.get(key)
+    if got is not None:
+        return got
+    with mp.workdps(SOBOL_DPS + 15):
+        u_, a_, v_, b_, lo_, hi_ = (mp.mpf(float(t)) for t in (u, a, v, b, lo, hi))
+        w = hi_ - lo_
+        if kernel == "se":
+            s2 = a_ * a_ + b_ * b_
+            sig = a_ * b_ / mp.sqrt(s2)
+            mu = (u_ * b_ * b_ + v_ * a_ * a_) / s2
+            z1, z2 = (mu - lo_) / sig, (hi_ - mu) / sig
+            if z1 >= 0 and z2 >= 0:
+                r = _marg_mp("se", "F", z1) + _marg_mp("se", "F", z2)
+            else:
+                r = _marg_mp("se", "Fc", min(abs(z1), abs(z2))) - _marg_mp("se", "Fc", max(abs(z1), abs(z2)))
+            got = mp.exp(-(u_ - v_) ** 2 / (2 * s2)) * sig * r / w
+        else:
+            cuts = sorted({lo_, hi_, min(max(u_, lo_), hi_), min(max(v_, lo_), hi_)})
+            tot = mp.mpf(0)
+            for p, r in zip(cuts[:-1], cuts[1:]):
+                mid = (p + r) / 2
+                polys, g, e0 = [], mp.mpf(0), mp.mpf(0)
+                for c, ell in ((u_, a_), (v_, b_)):
+                    sg = 1 if mid > c else -1
+                    s0, al = abs(p - c) / ell, sg / ell         # s(tau) = s0 + al tau >= 0 on the piece
+                    polys.append([1 + s0, al] if kernel == "matern32" else [1 + s0 + s0 * s0 / 3, al * (1 + 2 * s0 / 3), al * al / 3])
+                    g += al
+                    e0 += s0
+                q = [mp.mpf(0)] * (len(polys[0]) + len(polys[1]) - 1)
+                for i, ca in enumerate(polys[0]):
+                    for j, cb in enumerate(polys[1]):
+                        q[i + j] += ca * cb
+                tot += mp.exp(-e0) * sum(qn * _mp_moment(n, g, r - p) for n, qn in enumerate(q))
+            got = tot / w
+    _SOBOL_CACHE[key] = got
+    return got
+
+
+def _sobol_matern_parts(u, a, v, b, lo, hi):
+    """sobol_J's Matern branch variables in the library's float64 operations (arrays): the swap, the reciprocals, the clipped
+    centres, per segment its length L and g L"""
+    u, a, v, b, lo, hi = np.broadcast_arrays(*(np.asarray(t, np.float64) for t in (u, a, v, b, lo, hi)))
+    swap = u > v
+    ra, rb = np.where(swap, 1.0 / b, 1.0 / a), np.where(swap, 1.0 / a, 1.0 / b)
+    uu, vv = np.where(swap, v, u), np.where(swap, u, v)
+    cu, cv = np.minimum(np.maximum(uu, lo), hi), np.minimum(np.maximum(vv, lo), hi)
+    L = np.stack([cu - lo, cv - cu, hi - cv])
+    g1 = np.where(rb <= ra, ra + (-rb), (-ra) + rb)
+    g = np.stack([ra + rb, g1, ra + rb])
+    # s0 = s0a + s0b at each segment's anchor, as sobol_J passes them to sobol_segment (left: the anchor of the middle segment);
+    # smin, the smallest among the non-empty segments, is the exponent SOBOL_KJ0 is normalised by: keep both in step with sobol_J
+    left = rb <= ra
+    s0 = np.stack([np.abs(uu - cu) * ra + np.abs(vv - cu) * rb,
+                   np.where(left, np.abs(cu - uu) * ra + np.abs(vv - cu) * rb, np.abs(cv - uu) * ra + np.abs(vv - cv) * rb),
+                   np.abs(cv - uu) * ra + np.abs(cv - vv) * rb])
+    smin = np.min(np.where(L > 0.0, s0, np.inf), axis=0)
+    return dict(swap=swap, ra=ra, rb=rb, u=uu, v=vv, cu=cu, cv=cv, L=L, g=g, x=g * L, s0=s0, smin=smin)
+
+
+def _sobol_se_parts(u, a, v, b, lo, hi):
+    """sobol_dim / sobol_J's SE variables in the library's float64 operations"""
+    u, a, v, b, lo, hi = np.broadcast_arrays(*(np.asarray(t, np.float64) for t in (u, a, v, b, lo, hi)))
+    s2 = a * a + b * b
+    c0, c1 = -0.5 / s2, a * b / np.sqrt(s2)
+    c2, c3, c4 = 1.0 / c1, b * b / s2, a * a / s2
+    df = u - v
+    arg = -(c0 * df * df)
+    with np.errstate(under="ignore"):
+        pref = np.exp(-arg)
+    mu = c3 * u + c4 * v
+    z1, z2 = (mu - lo) * c2, (hi - mu) * c2
+    b1, b2 = np.abs(z1), np.abs(z2)
+    inside = (z1 >= 0.0) & (z2 >= 0.0)
+    return dict(c1=c1, c2=c2, c3=c3, c4=c4, arg=arg, pref=pref, mu=mu, z1=z1, z2=z2, b1=b1, b2=b2, inside=inside,
+                bn=np.minimum(b1, b2), bf=np.maximum(b1, b2), rw=1.0 / (hi - lo), u=u, v=v)
+
+
+def sobol_classes(kernel, u, a, v, b, lo, hi):
+    """the branch classes of sobol_J / sobol_moments an element (u, a, v, b, lo, hi) falls into: name -> bool array.  Computed
+    with the library's own float64 operations, so it follows the switches to the last bit."""
+    _known(kernel)
+    u, a, v, b, lo, hi = np.broadcast_arrays(*(np.asarray(t, np.float64) for t in (u, a, v, b, lo, hi)))
+    if kernel == "se":
+        p = _sobol_se_parts(u, a, v, b, lo, hi)
+        return {"inside": p["inside"], "outside_bn_le_1": ~p["inside"] & (p["bn"] <= 1.0),
+                "outside_bn_gt_1": ~p["inside"] & (p["bn"] > 1.0), "centre_on_end": (p["z1"] == 0.0) | (p["z2"] == 0.0),
+                "prefactor_below_1e-300": p["pref"] < 1e-300}
+    p = _sobol_matern_parts(u, a, v, b, lo, hi)
+    L, x, g = p["L"], p["x"], p["g"]
+    out = {}
+    for s in range(3):
+        out["seg%d_length0" % s] = L[s] == 0.0
+        out["seg%d_series" % s] = (L[s] > 0.0) & (x[s] < SOBOL_SERIES_BELOW)
+        out["seg%d_forward" % s] = (L[s] > 0.0) & (x[s] >= SOBOL_SERIES_BELOW)
+    mid = L[1] > 0.0
+    out["mid_gamma0"] = mid & (g[1] == 0.0)
+    out["mid_just_below_4"] = mid & (x[1] < 4.0) & (x[1] > 4.0 - 1e-3)
+    out["mid_just_above_4"] = mid & (x[1] >= 4.0) & (x[1] < 4.0 + 1e-3)
+    out["mid_rb_le_ra"] = mid & (p["rb"] <= p["ra"])
+    out["mid_rb_gt_ra"] = mid & (p["rb"] > p["ra"])
+    out["swap"] = p["swap"]
+    out["equal_centres"] = u == v
+    out["centre_on_end"] = (u == lo) | (u == hi) | (v == lo) | (v == hi)
+    ul, ur, vl, vr = u < lo, u > hi, v < lo, v > hi
+    one = (ul | ur) ^ (vl | vr)
+    out["one_outside_left"] = one & (ul | vl)
+    out["one_outside_right"] = one & (ur | vr)
+    out["both_outside_opposite"] = (ul & vr) | (ur & vl)
+    out["both_outside_same"] = (ul & vl) | (ur & vr)
+    out["scales_1e-12_apart"] = (a != b) & (np.abs(b / a - 1.0) < 1e-11)
+    return out
+
+
+def sobol_cases(kernel, lo, hi):
+    """the 1-D case table of the element stage for the box [lo, hi]: rows (u, a, v, b), a few hundred, every class of
+    sobol_classes at least 8 times per kernel over the two boxes of the tests (asserted by the CPU tests)"""
+    _known(kernel)
+    w = hi - lo
+    at = lambda f: lo + f * w                              # noqa: E731
+    S = [0.01 * w, w, 30.0 * w]
+    rows = []
+    centres = [(.2, .7), (.7, .2), (.5, .5), (0., .6), (.3, 1.), (-.3, .4), (.4, 1.3), (-.2, 1.3), (-.5, -.1), (1.1, 1.6),
+               (.6, -.25), (1., 0.)]
+    for a in S:
+        for b in S:
+            for fu, fv in centres:
+                rows.append((at(fu), a, at(fv), b))
+    if kernel == "se":
+        for a in [0.01 * w, 0.1 * w, w, 3.0 * w, 30.0 * w]:        # a = b: c3 = c4 = 1/2, the product's centre lies on the end
+            rows += [(lo, a, lo, a), (hi, a, hi, a)]
+        for a in [0.0165 * w, 0.017 * w, 0.0175 * w, 0.01 * w]:    # e^(-df^2 / (2 s2)) below 1e-300 (the last: 0)
+            rows += [(at(.05), a, at(.95), a), (at(.97), a, at(.06), a * 1.01), (at(-.02), a, at(.9), a)]
+        for a, b in [(w, w), (3 * w, w), (w, 30 * w), (.3 * w, .3 * w)]:   # the centre outside within one sigma
+            rows += [(at(-.1), a, at(-.15), b), (at(1.05), a, at(1.1), b)]
+    else:
+        # the middle segment around gamma L = 4: L = w / 2, 1 / a = 20 / w, gamma = 8 (1 + dl) / w
+        for dl in (0.0, 3e-16, -3e-16, 1e-6, -1e-6, 1e-5, -1e-5, 5e-5, -5e-5, 1e-4, -1e-4, 2e-4, -2e-4):
+            a, b = 0.05 * w, w / (12.0 - 8.0 * dl)
+            rows += [(at(.25), a, at(.75), b), (at(.25), b, at(.75), a), (at(.75), a, at(.25), b)]
+        # gamma L from 0.05 to 0.3 at moderate scales (s0 small: SOBOL_KJ0 applies), where a forward recurrence taken too early
+        # loses most: the middle segment (1 / b = 1 / a + gamma) and, with both centres near an end, an outer one
+        for gl in (0.05, 0.1, 0.2, 0.3):
+            for fu, fv, ia in ((0., .7, 8.), (.3, 1., 8.), (0., 1., 3.), (.1, .8, 5.)):
+                a, b = w / ia, w / (ia + gl / (fv - fu))
+                rows += [(at(fu), a, at(fv), b), (at(fv), a, at(fu), b)]
+            rows += [(at(gl / 4.0), 5.0 * w, at(gl / 4.0), 5.0 * w), (at(1.0 - gl / 2.0), 10.0 * w, at(1.0 - gl / 2.0), 10.0 * w)]
+        for a in S + [0.1 * w]:                                    # b = a (1 + 1e-12), and gamma = 0 exactly
+            for fu, fv in ((.2, .7), (.9, .1), (-.1, .5)):
+                rows += [(at(fu), a, at(fv), a * (1.0 + 1e-12)), (at(fu), a, at(fv), a)]
+    return np.array(rows, np.float64)
+
+
+def _sobol_se_bound(u, a, v, b, lo, hi):
+    """the absolute error of sobol_J<SE> in units of u, without C, counted from sobol_dim and sobol_J:
+      s2 = a a + b b (2 relative), c0 = -1/2 / s2 (+1), c1 = a b / sqrt(s2) (1 + 2 + 1: 4, kept at 5), c2 = 1 / c1 (6),
+      c3 = b b / s2, c4 = a a / s2 (4 each), rw = 1 / (hi - lo) (2)
+      pref = exp(c0 df df): the argument carries c0 (3), df twice (2), two products (2): 7, kept at 8, each moving pref by
+          |argument| u -- the input conditioning of e^(-z^2 / 2) -- plus the call's MARG_ULP
+      mu = fma(c3, u, c4 v): (4 + 1) u on each term, one for the sum: |d mu| <= 6 u (|c3 u| + |c4 v|), which enters z = (mu - end) c2
+          as an ABSOLUTE 6 u (|c3 u| + |c4 v|) c2 -- large against z where sigma is small against the centres: input conditioning
+      z = (mu - end) c2: the difference, c2, the product: 8 u |z| more; marg_F<SE> / marg_Fc<SE>: _marg_terms and 2 u b kappa(b)
+          for its own b s product; F' = kappa, Fc' = -kappa
+      r = the sum or difference of the two (1 on |A1| + |A2|), J = pref c1 r rw: three products
+    so |dJ| <= u [ J (MARG_ULP + 8 |arg| + 5 + 2 + 3) + pref c1 rw (K1 A1 + K2 A2 + A1 + A2 + sum_i kappa(b_i) (dz_i + 2 b_i)) ]"""
+    p = _sobol_se_parts(u, a, v, b, lo, hi)
+    far = ~p["inside"] & (p["bn"] > 1.0)
+    b1, b2 = p["b1"], p["b2"]
+    with np.errstate(under="ignore", over="ignore", invalid="ignore"):
+        t1 = np.where(far, _marg_terms("se", "Fc", b1), _marg_terms("se", "F", b1))
+        t2 = np.where(far, _marg_terms("se", "Fc", b2), _marg_terms("se", "F", b2))
+        k = MARG_ULP + MARG_ROUNDINGS["se", "F"]
+        A1, A2 = t1 / k, t2 / k
+        r = np.where(p["inside"], A1 + A2, np.abs(A1 - A2))
+        dmu = 6.0 * (np.abs(p["c3"] * p["u"]) + np.abs(p["c4"] * p["v"])) * p["c2"]
+        inner = t1 + t2 + A1 + A2 + _kappa("se", b1) * (dmu + 10.0 * b1) + _kappa("se", b2) * (dmu + 10.0 * b2)
+        front = p["pref"] * p["c1"] * p["rw"]
+        return front * r * (MARG_ULP + 8.0 * p["arg"] + 10.0) + front * inner
+
+
+def sobol_j_bound(kernel, u, a, v, b, lo, hi, J):
+    """the absolute error bound of ONE pair average J (arrays; J its value, float64) in units of u, without C: SE derived
+    (_sobol_se_bound), Matern SOBOL_KJ of the worst branch among the element's non-empty segments, relative to J"""
+    _known(kernel)
+    if kernel == "se":
+        return _sobol_se_bound(u, a, v, b, lo, hi)
+    p = _sobol_matern_parts(u, a, v, b, lo, hi)
+    K, K0 = np.zeros(np.shape(p["x"][0])), np.zeros(np.shape(p["x"][0]))
+    for s, kind in ((0, "outer"), (1, "middle"), (2, "outer")):
+        live = p["L"][s] > 0.0
+        series = p["x"][s] < SOBOL_SERIES_BELOW
+        K = np.maximum(K, np.where(live, np.where(series, SOBOL_KJ[kernel, kind, "series"], SOBOL_KJ[kernel, kind, "forward"]), 0.0))
+        K0 = np.maximum(K0, np.where(live, np.where(series, SOBOL_KJ0[kernel, kind, "series"], SOBOL_KJ0[kernel, kind, "forward"]), 0.0))
+    with np.errstate(invalid="ignore"):
+        return np.minimum(K, K0 * (1.0 + np.where(np.isfinite(p["smin"]), p["smin"], 0.0))) * np.abs(J)
+
+
+def sobol_j_measure(kernel, got, rows, lo, hi):
+    """the error of `got` (float64 J per row of `rows` = (u, a, v, b)) against sobol_exact_J in units of u relative to the exact
+    value (NaN where the exact value is below 1e-290: the floor's entries), and the exact values as float64"""
+    rel, ex = np.full(len(rows), np.nan), np.zeros(len(rows))
+    for i, (u, a, v, b) in enumerate(np.asarray(rows, np.float64).tolist()):
+        e = sobol_exact_J(kernel, u, a, v, b, lo, hi)
+        ex[i] = float(e)
+        if ex[i] > 1e-290:
+            with mp.workdps(SOBOL_DPS):
+                rel[i] = float(abs(mp.mpf(float(got[i])) - e) / e) / _U64 if math.isfinite(got[i]) else math.inf
+    return rel, ex
+
+
+def check_sobol_means(means, tab, w) -> Check:
+    """means[k] = sum_i w_ki prod_l tab[k, l, i] (sobol_table_kernel: d - 1 products and one fma per term, 64-lane shuffles, four
+    waves) against the same sum from the library's table: |error| <= C gamma_(d + n) sum_i |w_ki| prod_l tab + floor"""
+    mv, tb, wv = _np(means), _np(tab), _np(w)
+    q, d, n = tb.shape
+    pr = np.prod(tb, axis=1)
+    ref, sab = np.sum(wv * pr, axis=1), np.sum(np.abs(wv) * np.abs(pr), axis=1)
+    return worst(_t(np.abs(mv - ref)), _t(C * gamma(d + n) * sab + floor("float64", d + n)))
+
+
+def sobol_element_exact(kernel, U, A, V, B, box):
+    """per element e (rows of U, A, V, B: (m, d) centres and length scales of the two components) and input l the exact J and
+    the two 1-D averages, as object arrays (m, d) of mpmath numbers"""
+    U, A, V, B, box = (np.asarray(t, np.float64) for t in (U, A, V, B, box))
+    m, d = U.shape
+    Jx, ax, bx = (np.empty((m, d), object) for _ in range(3))
+    for e in range(m):
+        for l in range(d):
+            lo, hi = box[0, l], box[1, l]
+            Jx[e, l] = sobol_exact_J(kernel, U[e, l], A[e, l], V[e, l], B[e, l], lo, hi)
+            ax[e, l] = marg_exact(kernel, U[e, l:l + 1], lo, hi, A[e, l])[0]
+            bx[e, l] = marg_exact(kernel, V[e, l:l + 1], lo, hi, B[e, l])[0]
+    return Jx, ax, bx
+
+
+def check_sobol_element(rows, kernel, U, A, V, B, box, masks, detail=None) -> Check:
+    """rows (m, len(masks)): the library's (M_u - M_0) of ONE element per row (one-hot weights) for the subsets `masks` (bit l:
+    input l is in u), against the exact value from mpmath:
+        |error| <= C u [ M_u (sum_(l in u) K_J,l + sum_(l not in u) (k_a,l + k_a',l + 1) + |u| + d)
+                         + M_0 (sum_l (k_a,l + k_a',l + 1) + d) + |M_u - M_0| + (M_u + M_0) ] + floor
+    K_J u J the bound of sobol_j_bound, k_a u a that of marg_table_bound; the last two terms are the difference's and the fma's
+    rounding.  The empty mask must give exactly 0.0.  detail: a list that receives (row, column, |error| / (u (M_u + M_0)))."""
+    _known(kernel)
+    got = _np(rows)
+    U, A, V, B, box = (np.asarray(t, np.float64) for t in (U, A, V, B, box))
+    m, d = U.shape
+    assert got.shape == (m, len(masks)), (got.shape, m, len(masks))
+    Jx, ax, bx = sobol_element_exact(kernel, U, A, V, B, box)
+    Jf, af, bf = (np.array(t.tolist(), np.float64).reshape(m, d) for t in (Jx, ax, bx))
+    KJ, ka = np.zeros((m, d)), np.zeros((m, d))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        for l in range(d):
+            lo, hi = box[0, l], box[1, l]
+            kj = sobol_j_bound(kernel, U[:, l], A[:, l], V[:, l], B[:, l], lo, hi, Jf[:, l]) / Jf[:, l]
+            KJ[:, l] = np.where(Jf[:, l] > 0.0, kj, 0.0)
+            for e in range(m):
+                t = (marg_table_bound(kernel, U[e, l:l + 1], lo, hi, A[e, l])[0] / af[e, l] if af[e, l] > 0.0 else 0.0) + \
+                    (marg_table_bound(kernel, V[e, l:l + 1], lo, hi, B[e, l])[0] / bf[e, l] if bf[e, l] > 0.0 else 0.0)
+                ka[e, l] = t / _U64 + 1.0
+    KJ = np.where(np.isfinite(KJ), KJ, 0.0)
+    best = Check(0.0, ())
+    fl = floor("float64", 2 * d)
+    with mp.workdps(SOBOL_DPS):
+        for e in range(m):
+            m0x = mp.fprod(ax[e, l] * bx[e, l] for l in range(d))
+            e0 = float(np.sum(ka[e])) + d
+            for s, mask in enumerate(masks):
+                if mask == 0:
+                    r = 0.0 if (got[e, s] == 0.0 and not np.signbit(got[e, s])) else math.inf
+                else:
+                    mux = mp.fprod(Jx[e, l] if (mask >> l) & 1 else ax[e, l] * bx[e, l] for l in range(d))
+                    eu = sum(KJ[e, l] if (mask >> l) & 1 else ka[e, l] for l in range(d)) + bin(mask).count("1") + d
+                    mu_f, m0_f, ex = float(mux), float(m0x), mux - m0x
+                    err = float(abs(mp.mpf(float(got[e, s])) - ex)) if math.isfinite(got[e, s]) else math.inf
+                    bound = C * _U64 * (mu_f * eu + m0_f * e0 + float(abs(ex)) + mu_f + m0_f) + fl
+                    r = err / bound
+                    if detail is not None and mu_f + m0_f > 1e-290:
+                        detail.append((e, s, err / (_U64 * (mu_f + m0_f))))
+                if not r <= best.ratio:
+                    best = Check(float(r) if r == r else math.inf, (e, s))
+    return best
+
+
+def sobol_tile_reference(kernel, x, w, ell, box, tab, k, kp, masks, Q=None, rows=None, cols=None):
+    """per tile (r, c) and subset: ref = twice sum_tile wgt (M_u - M_0) and the bound's sum  u (E + SOBOL_TILE_DEPTH) |wgt| (M_u +
+    M_0), elementwise E as in check_sobol_element without the a terms (the table is the library's own): (ref, bnd) of shape (ntile,
+    ntile, len(masks) [+ 1 with Q: S0 = sum wgt M_0]).  J from tests/sobol_ref.pair_integral.  rows / cols: tile indices to form
+    (default: all; for a pair k = k' only c <= r is formed, the rest stays NaN)."""
+    from tests import sobol_ref
+    x, w, ell, box, tab = (_np(t) for t in (x, w, ell, box, tab))
+    n, d = x.shape
+    ntile = (n + TS - 1) // TS
+    ncol = len(masks) + (1 if Q is not None else 0)
+    ref, bnd = np.full((ntile, ntile, ncol), np.nan), np.full((ntile, ntile, ncol), np.nan)
+    for r in (range(ntile) if rows is None else rows):
+        for c in (range(ntile) if cols is None else cols):
+            if k == kp and c > r:
+                continue
+            ri, cj = slice(r * TS, min(n, (r + 1) * TS)), slice(c * TS, min(n, (c + 1) * TS))
+            twice = 2.0 if (k == kp and c < r) else 1.0
+            wgt = twice * (w[k, ri][:, None] * w[kp, cj][None, :])
+            if Q is not None:
+                wgt = wgt * _np(Q)[ri, cj]
+            J = np.empty(wgt.shape + (d,))
+            KJ = np.empty(wgt.shape + (d,))
+            for l in range(d):
+                args = (x[ri, l][:, None], ell[k, l], x[cj, l][None, :], ell[kp, l], box[0, l], box[1, l])
+                J[..., l] = sobol_ref.pair_integral(kernel, box[0, l], box[1, l], args[0], args[1], args[2], args[3])
+                with np.errstate(divide="ignore", invalid="ignore"):
+                    kj = sobol_j_bound(kernel, *args, J[..., l]) / J[..., l]
+                KJ[..., l] = np.where(np.isfinite(kj), kj, 0.0)
+            Aa = tab[k][:, ri].T[:, None, :] * tab[kp][:, cj].T[None, :, :]
+            M0 = np.prod(Aa, axis=-1)
+            for s, mask in enumerate(masks):
+                bits = np.array([(mask >> l) & 1 for l in range(d)], bool)
+                Mu = np.prod(np.where(bits, J, Aa), axis=-1)
+                E = np.sum(np.where(bits, KJ, 1.0), axis=-1) + float(bits.sum()) + d + 2.0
+                E0 = 2.0 * d + 2.0
+                ref[r, c, s] = np.sum(wgt * (Mu - M0))
+                bnd[r, c, s] = _U64 * np.sum(np.abs(wgt) * ((E + SOBOL_TILE_DEPTH) * Mu + (E0 + SOBOL_TILE_DEPTH) * M0))
+            if Q is not None:
+                ref[r, c, -1] = np.sum(wgt * M0)
+                bnd[r, c, -1] = _U64 * np.sum(np.abs(wgt) * (E0 + SOBOL_TILE_DEPTH) * M0)
+    return ref, bnd
+
+
+def check_sobol_tile(part, ref, bnd) -> Check:
+    """part (ntile, ntile, cols) of one pair against sobol_tile_reference: |error| <= C bnd + floor wherever ref is formed (not
+    NaN).  Location: (row tile, column tile, column)."""
+    pv = _np(part)
+    have = ~np.isnan(ref)
+    if not have.any():
+        return Check(0.0, ())
+    r = np.where(have, np.abs(pv - np.where(have, ref, 0.0)) / (C * np.where(have, bnd, 1.0) + floor("float64", TS * TS)), 0.0)
+    r = np.where(np.isnan(r), math.inf, r)
+    i = np.unravel_index(int(np.argmax(r)), r.shape)
+    return Check(float(r[i]), tuple(int(t) for t in i))
+
+
+def check_sobol_reduce(out_row, part, same) -> Check:
+    """out_row (cols) against the sum over the tiles of the library's own part (ntile, ntile, cols), in float64 on the host; for a
+    pair k = k' (`same`) only the tiles c <= r -- whatever the others hold must not reach the sum:
+        |error| <= C gamma_(ntile^2) sum |part| + floor
+    (sobol_reduce_kernel / sobol_subset_reduce_kernel: a serial sum per thread, then a tree over 256 threads: any order)"""
+    ov, pv = _np(out_row), _np(part)
+    nt = pv.shape[0]
+    keep = np.tril(np.ones((nt, nt), bool)) if same else np.ones((nt, nt), bool)
+    sel = pv[keep]
+    ref, sab = sel.sum(axis=0), np.abs(sel).sum(axis=0)
+    r = np.abs(ov - ref) / (C * gamma(nt * nt) * sab + floor("float64", nt * nt))
+    r = np.where(np.isnan(r), math.inf, r)
+    i = int(np.argmax(r))
+    return Check(float(r[i]), (i,))
+
+
+def check_sobol_rows(out_row, ref, bnd) -> Check:
+    """out_row (cols) of ANY batch against the tile references of sobol_tile_reference summed over the tiles it forms (NaN: none):
+        |error| <= C (sum bnd + gamma_(ntile^2) sum |ref|) + floor
+    the tile stage's bound and the reduction's together -- the one check that sees the rows of batches whose tile sums the next
+    batch has overwritten (the p0 loop and the row offsets of do_sobol_pairs / do_sobol_subset_pairs)"""
+    ov = _np(out_row)
+    nt = ref.shape[0]
+    r0, b0 = np.nansum(ref, axis=(0, 1)), np.nansum(bnd, axis=(0, 1))
+    sab = np.nansum(np.abs(ref), axis=(0, 1))
+    r = np.abs(ov[:r0.shape[0]] - r0) / (C * (b0 + gamma(nt * nt) * sab) + floor("float64", nt * nt * TS * TS))
+    r = np.where(np.isnan(r), math.inf, r)
+    i = int(np.argmax(r))
+    return Check(float(r[i]), (i,))
+
+
+# the matrix-weighted entries (lcgp_sobol_matrix_pairs: SOBOL_MAT) use sobol_layout(extra=1) and sobol_tile_reference(Q=...): the
+# weight of an element is v_i v_i' Q[i, i'] (one more product: covered by the + 2 of E), one more sum per tile, S0.  The view
+# (lcgp_condition_sobol_matrix_pairs: SOBOL_VIEW) prepares, per component, P and E in the scratch at cond_sobol_carve's offsets.
+def cond_sobol_layout(n, d, q, m, subset=False):
+    """cond_sobol_carve of lcgp_hip.hip: the offsets in doubles of tab (q, d, N), means, part (ONE pair: ntile^2 tiles of 2 d + 2
+    sums, or of SOBOL_CHUNK for the subset form), neg (the word holding -1), T (mpad x npad), G (mpad x npad), P (Npad x mpad),
+    E (Npad x Npad), each aligned to 256 bytes, and `total` in bytes"""
+    N = n + m
+    Npad, npad, mpad = -(-N // TS) * TS, _pad128(n), _pad128(m)
+    nt = Npad // TS
+    lay = _carve([("tab", q * d * N), ("means", q), ("part", nt * nt * (SOBOL_CHUNK if subset else 2 * d + 2)), ("neg", 1),
+                  ("t", mpad * npad), ("g", mpad * npad), ("p", Npad * mpad), ("e", Npad * Npad)])
+    lay.update(N=N, Npad=Npad, npad=npad, mpad=mpad, ntile=nt)
+    return lay
+
+
+def check_sobol_p(P, G, Wd, D, n, m) -> Check:
+    """P (Npad x mpad) of cond_sobol_p_kernel: D G[a, i] for i < n (one rounding: |error| <= C u |D G| + floor), BITWISE the dense
+    L_S^-1[a, i - n] for n <= i < n + m, bitwise zero on the rows from n + m on and on the columns from m on"""
+    Pv, Gv, Wv = _np(P), _np(G), _np(Wd)
+    if not (_same_bits(_t(Pv[n:n + m, :m].copy()), _t(Wv[:m, :m].T.copy())) and _zero_bits(_t(Pv[n + m:].copy()))
+            and _zero_bits(_t(Pv[:, m:].copy()))):
+        return Check(math.inf, ("copy",))
+    ref = float(D) * Gv[:m, :n].T
+    return worst(_t(np.abs(Pv[:n, :m] - ref)), _t(C * _U64 * np.abs(ref) + floor("float64", 1)), lower=False)
+
+
+def check_sobol_e(E, P, m) -> Check:
+    """the lower 64-tiles of E = P P^T (OP_PRED_COV on a zeroed E with alpha = -(-1)) against the library's own P:
+    |error| <= C gamma_(m + 1) |P| |P|^T + floor on the lower triangle; the strictly upper tiles stay bitwise zero"""
+    Ev, Pv = _np(E), _np(P)
+    Np = Ev.shape[0]
+    low = np.kron(np.tril(np.ones((Np // TS, Np // TS))), np.ones((TS, TS))) > 0
+    if np.any(Ev[~low].view(np.int64) != 0):
+        return Check(math.inf, ("upper",))
+    ref, sab = Pv @ Pv.T, np.abs(Pv) @ np.abs(Pv).T
+    err = np.tril(np.abs(Ev - ref))                        # (sobol_stage_q reads a diagonal tile's lower triangle only)
+    return worst(_t(err), _t(C * gamma(m + 1) * sab + floor("float64", m)), lower=False)
+
+
+def sobol_view_q(E, Ainv, D, nt, N):
+    """Q' (N x N) as sobol_stage_q<SOBOL_VIEW> reads it: E from its lower triangle, mirrored, plus D A^-1 where both indices are
+    below nt (one fma: within C)"""
+    Ev = _np(E)[:N, :N]
+    Q = np.tril(Ev) + np.tril(Ev, -1).T
+    Q[:nt, :nt] += float(D) * _np(Ainv)[:nt, :nt]
+    return Q
+
+
+def check_sobol_t(T, Wd, Un, m) -> Check:
+    """T = 0 - L_S^-1 U_n (mpad x npad; OP_COND_U on a zeroed slab with R := the dense L_S^-1, K = mpad) against the float64 product
+    of the state's own dense L_S^-1 (mpad x mpad) and U_n (mpad x npad): an inner product of m terms (the padding adds stored
+    zeros) and the subtraction from zero, |error| <= C gamma_(m + 1) |L_S^-1| |U_n| + floor.  G = T W, the launch that follows, is
+    check_pgrad_v's (OP_PRED_V with W = L^-1)."""
+    Tv, Wv, Uv = _np(T), _np(Wd), _np(Un)
+    ref, sab = -(Wv @ Uv), np.abs(Wv) @ np.abs(Uv)
+    return worst(_t(np.abs(Tv - ref)), _t(C * gamma(m + 1) * sab + floor("float64", m)), lower=False)

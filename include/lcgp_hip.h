@@ -1082,6 +1082,43 @@ int lcgp_condition_sobol_matrix_subset_pairs(void* stream, int dtype, int kernel
                                              const uint64_t* masks /* nsub, host */, int nsub, void* scratch,
                                              size_t scratch_bytes, double* out /* nks x nsub */);
 
+/* Exact box ALC (no counterpart in the reference): for every candidate, how much the box-integrated posterior
+ * variance IV_k of lcgp_sobol_matrix_pairs would drop if the simulator ran `replicates` more times there, at fixed parameters --
+ * lcgp_variance_reduction with the weighted sum over a reference set replaced by the exact integral over `box` (uniform measure).
+ * float64 only.  Runs behind lcgp_nll_grad at the same theta and only READS its workspace.  Per local component k, standardised
+ * inputs, c = scale (1 - nt), X_c the candidate's cross-covariance row as lcgp_variance_reduction forms it (`match`: per candidate
+ * the training input it replicates, whose column carries the nugget term, or -1; NULL = none; a DEVICE array), V_c = X_c A^-1,
+ * b_c = D c sr o V_c, J_l the pair average of lcgp_sobol_pairs with both length scales ell_kl:
+ *     M[i, i'] = prod_l J_l(x_il, x_i'l)        m_c[i] = prod_l J_l(x_cl, x_il)        m_cc = prod_l J_l(x_cl, x_cl)
+ *     R_k(c) = [ c^2 m_cc - 2 c b_c . m_c + b_c^T M b_c ] / (max(scale - D |U_c|^2, 0) + 1 / (D replicates))
+ * = IV_k before minus IV_k after the runs.  The three terms cancel: their absolute sum is tens to hundreds of c where R is 1e-5
+ * to 1e-3 of c, so R carries an ABSOLUTE error of a few ulps of that sum; it is not clamped and may come out slightly negative
+ * where the gain is at rounding level.  Candidates may lie outside the box.
+ * The call handles the components k0 .. k0 + q_group - 1 of the workspace (carved for q_local) and writes their rows of `out`
+ * (q_local rows of n_cand, `out_stride` apart, 0 = n_cand): a caller bounds the scratch by processing the local components in
+ * groups and the candidates in chunks.  form_m != 0: (sr sr^T) o M of the group's components is materialised at the head of the
+ * scratch first (box_matrix_kernel: 64 x 64 tiles with column tile <= row tile, written with their mirror, zero on the padding);
+ * form_m = 0: the scratch still holds it from the preceding call with the same k0, q_group and box -- the place of M does not
+ * depend on n_cand, so the chunks of one candidate set share it.
+ * Launches behind it: X, U = X W^T, gvar and V = U W by the launches of lcgp_predict_grad; T = V M on the fp64 MFMA tile kernel
+ * (OP_HESS_G, 128 x 128 tiles); one wave per candidate for T_c . V_c; box_cross_kernel, one workgroup per (candidate, component),
+ * which forms m_c[i] in registers, sums sr_i V_ci m_c[i] over the row and combines.  Nothing of size n_cand x n x d and no
+ * n_cand x n array of integrals is written.  V is formed on 64-row tiles below 128 candidates and on 128-row tiles from 128 on
+ * (the two sum in different orders): a caller that wants results independent of its chunking never passes fewer than 128
+ * candidates while it has them.  Every sum has a fixed order, no atomics: bitwise reproducible, independent of q_local, of k0 /
+ * q_group and of the scratch content on entry.
+ * Refused before the first launch: a float32 workspace, NULL pointers (sr and match may be NULL), d > 126, n < 1, n_cand < 1 or
+ * > 65535, replicates < 1.
+ * scratch: lcgp_box_alc_scratch_bytes(dtype, n, d, q_group, n_cand) = q_group (npad^2 + 2 n0pad npad + 3 n0pad) doubles (npad = n
+ * and n0pad = n_cand rounded up to 128), each part rounded up to 256 bytes. */
+int lcgp_box_alc_scratch_bytes(int dtype, int n, int d, int q_group, int n_cand, size_t* bytes /*host out*/);
+int lcgp_box_alc(void* stream, int dtype, int kernel_id, int n, int d, int p, int q_local,
+                 const void* x, const void* sr, const double* theta, const void* workspace,
+                 int k0, int q_group, const double* box /* lo[d], hi[d], standardised */,
+                 int n_cand, const void* x_cand /* n_cand x d, standardised */, const int* match /* n_cand, or NULL */,
+                 int replicates, int form_m, void* scratch,
+                 double* out /* q_local rows of n_cand, `out_stride` apart */, int out_stride);
+
 #ifdef __cplusplus
 }
 #endif

@@ -149,6 +149,8 @@ SIGNATURES = {
     "lcgp_condition_sobol_subset_scratch_bytes": (_i, [_i, _i, _i, _i, _i, _i, C.POINTER(C.c_size_t)]),
     "lcgp_condition_sobol_matrix_subset_pairs": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp,
                                                       C.POINTER(_i), _i, C.POINTER(C.c_uint64), _i, _vp, C.c_size_t, _vp]),
+    "lcgp_box_alc_scratch_bytes": (_i, [_i, _i, _i, _i, _i, C.POINTER(C.c_size_t)]),
+    "lcgp_box_alc": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _vp, _vp, _i, _i, _vp, _vp, _i]),
 }
 
 _lib = None

@@ -7940,6 +7940,192 @@ int do_condition_sobol(hipStream_t st, const Ws& w, const double* theta, const v
     return 0;
 }
 
+// ---------------------------------------------------------------------------------------------------
+// Exact box ALC (lcgp_hip.h: lcgp_box_alc; no counterpart in the reference): how much the box-integrated
+// posterior variance IV_k of 4.23 drops if the simulator ran r more times at a candidate.  With c = scale (1 - nt), X_c the
+// candidate's cross row (nugget entry at `match`), V_c = X_c A^-1, b_c = D c sr o V_c, J_l the pair average of sobol_J with both
+// length scales equal, M[i, i'] = prod_l J_l(x_il, x_i'l), m_c[i] = prod_l J_l(x_cl, x_il), m_cc = prod_l J_l(x_cl, x_cl):
+//     R(c) = [ c^2 m_cc - 2 c b_c . m_c + b_c^T M b_c ] / (max(scale - D |U_c|^2, 0) + 1 / (D r))
+// The three terms cancel to a few parts in 1e5 of each: errors are stated against their absolute sum, never against R.
+// Ms = (sr sr^T) o M is materialised once per group of components (box_matrix_kernel), X, U, gvar and V come from the launches of
+// lcgp_predict_grad, T = V Ms from the tile kernel (OP_HESS_G) and T_c . V_c from pgrad_rowdot_kernel; box_cross_kernel sweeps the
+// candidate's row for sum_i sr_i V_ci m_c[i] and combines.  Every row of every product depends on its candidate only and every sum
+// has a fixed order: bitwise independent of the chunking, of the grouping and of the scratch content.
+// ---------------------------------------------------------------------------------------------------
+struct BoxLay {
+    int npad, nb, n0p, n0r;
+    size_t mat, slab;
+    size_t off_m, off_x, off_u, off_gh, off_gv, off_rd, total;
+};
+
+// Ms first: its place does not depend on n_cand, so that the passes over the chunks of one candidate set share it
+inline BoxLay box_carve(int n, int qg, int n0) {
+    BoxLay L;
+    L.npad = round_up(n, 2 * TS);
+    L.nb = L.npad / TS;
+    L.n0p = predict_pad(n0);                // rows of X / U / V the launches of lcgp_predict form
+    L.n0r = round_up(n0, 2 * TS);           // rows of a slab: V Ms runs on 128 x 128 tiles
+    L.mat = (size_t)L.npad * L.npad;
+    L.slab = (size_t)L.n0r * L.npad;
+    size_t o = 0;
+    const size_t e = sizeof(double);
+    L.off_m = o; o = align256(o + (size_t)qg * L.mat * e);
+    L.off_x = o; o = align256(o + (size_t)qg * L.slab * e);
+    L.off_u = o; o = align256(o + (size_t)qg * L.slab * e);
+    L.off_gh = o; o = align256(o + (size_t)qg * L.n0r * e);
+    L.off_gv = o; o = align256(o + (size_t)qg * L.n0r * e);
+    L.off_rd = o; o = align256(o + (size_t)qg * L.n0r * e);
+    L.total = o;
+    return L;
+}
+
+// Ms_k = (sr sr^T) o M_k as a full npad x npad matrix, zero on the padding: one 64 x 64 tile (r, c), c <= r, per workgroup, 16
+// elements per thread one after the other (a rolled loop over d around sobol_J: the code of one J is long), through LDS to the
+// tile and to its mirror, both written in whole rows.  In a diagonal tile only j <= i is evaluated.
+template <int KERN>
+__global__ __launch_bounds__(256) void box_matrix_kernel(double* __restrict__ Ms, size_t mat, int n, int npad, int d,
+                                                         const double* __restrict__ x, const double* __restrict__ sr,
+                                                         const double* __restrict__ theta, int tw, const double* __restrict__ box) {
+    __shared__ double tl[TS][TS + 1];
+    __shared__ SobolDim cst[DWIDE];
+    const int r = blockIdx.x, c = blockIdx.y, k = blockIdx.z;
+    if (c > r) return;
+    const int tid = threadIdx.x;
+    const double* th = theta + (size_t)k * tw;
+    if (tid < d) cst[tid] = sobol_dim<KERN>(th[tid], th[tid], box[tid], box[d + tid]);
+    __syncthreads();
+    const int tx = tid & 15, ty = tid >> 4;
+#pragma unroll 1
+    for (int e = 0; e < 16; ++e) {
+        const int i = ty * 4 + (e >> 2), j = tx + 16 * (e & 3);
+        const int gi = r * TS + i, gj = c * TS + j;
+        if (r == c && j > i) continue;
+        double v = 0.0;
+        if (gi < n && gj < n) {
+            const double* xi = x + (size_t)gi * d;
+            const double* xj = x + (size_t)gj * d;
+            v = sr ? sr[gi] * sr[gj] : 1.0;
+#pragma unroll 1
+            for (int l = 0; l < d; ++l) v *= sobol_J<KERN>(xi[l], xj[l], cst[l]);
+        }
+        tl[i][j] = v;
+    }
+    __syncthreads();
+    double* Mk = Ms + (size_t)k * mat;
+    for (int e = tid; e < TS * TS; e += 256) {
+        const int i = e >> 6, j = e & 63;
+        if (r == c) {
+            Mk[(size_t)(r * TS + i) * npad + c * TS + j] = j <= i ? tl[i][j] : tl[j][i];
+        } else {
+            Mk[(size_t)(r * TS + i) * npad + c * TS + j] = tl[i][j];
+            Mk[(size_t)(c * TS + i) * npad + r * TS + j] = tl[j][i];
+        }
+    }
+}
+
+// One workgroup per (candidate, component): s1 = sum_i sr_i V[c, i] m_c[i] over the row (m_c[i] a rolled loop over d around
+// sobol_J, nothing of size n_cand x n reaches memory; butterflies inside a wave, then the four waves in order), m_cc, and with
+// rd = T_c . V_c (pgrad_rowdot_kernel) and gvar (pred_reduce_kernel) the score
+//     R = c^2 [ m_cc - 2 D s1 + D^2 rd ] / (max(gvar, 0) + 1 / (D r))
+// into out[k, c].  Not clamped: a gain at rounding level may come out slightly negative.
+template <int KERN>
+__global__ __launch_bounds__(256) void box_cross_kernel(const double* __restrict__ x0, const double* __restrict__ x,
+                                                        const double* __restrict__ sr, int n, int npad, int d,
+                                                        const double* __restrict__ theta, int tw, const double* __restrict__ box,
+                                                        const double* __restrict__ V, size_t slab, const double* __restrict__ rd,
+                                                        const double* __restrict__ gvar, int n0r, int nrep, int ldo,
+                                                        double* __restrict__ out) {
+    __shared__ double x0l[DWIDE];
+    __shared__ SobolDim cst[DWIDE];
+    __shared__ double sh[4];
+    const int i0 = blockIdx.x, k = blockIdx.y, tid = threadIdx.x;
+    const double* th = theta + (size_t)k * tw;
+    if (tid < d) {
+        x0l[tid] = x0[(size_t)i0 * d + tid];
+        cst[tid] = sobol_dim<KERN>(th[tid], th[tid], box[tid], box[d + tid]);
+    }
+    __syncthreads();
+    const double* vr = V + (size_t)k * slab + (size_t)i0 * npad;
+    double acc = 0.0;
+    for (int i = tid; i < n; i += 256) {
+        const double* xi = x + (size_t)i * d;
+        double m = sr ? sr[i] : 1.0;
+#pragma unroll 1
+        for (int l = 0; l < d; ++l) m *= sobol_J<KERN>(x0l[l], xi[l], cst[l]);
+        acc = fma(vr[i], m, acc);
+    }
+    const double s1 = hess_block_sum(acc, sh, tid);
+    if (tid != 0) return;
+    double mcc = 1.0;
+#pragma unroll 1
+    for (int l = 0; l < d; ++l) mcc *= sobol_J<KERN>(x0l[l], x0l[l], cst[l]);
+    const double scale = th[d], nug = th[d + 1], D = th[d + 2];
+    const double cc = scale / (1.0 + nug);                // scale (1 - nt)
+    const double t0 = cc * cc * mcc, t1 = 2.0 * cc * (D * cc * s1), t2 = (D * cc) * (D * cc) * rd[(size_t)k * n0r + i0];
+    const double den = fmax(gvar[(size_t)k * n0r + i0], 0.0) + 1.0 / (D * (double)nrep);
+    out[(size_t)k * ldo + i0] = ((t0 - t1) + t2) / den;
+}
+
+// enqueues the pass for the components [k0, k0 + qg) of the workspace and n0 candidates; form_m = 0: Ms of these components is
+// still in the scratch from the preceding call (same k0, qg, box)
+int do_box_alc(hipStream_t st, const Ws& w, const void* x, const void* sr, const double* theta, int k0, int qg, const double* box,
+               int n0, const void* x0, const int* match, int nrep, int form_m, char* scratch, double* out, int ldo) {
+    const int n = w.n, d = w.d, npad = w.npad, tw = d + 3 + w.p;
+    const BoxLay L = box_carve(n, qg, n0);
+    double* Ms = (double*)(scratch + L.off_m);
+    double* X = (double*)(scratch + L.off_x);          // X, then V
+    double* U = (double*)(scratch + L.off_u);          // U, then T
+    double* GH = (double*)(scratch + L.off_gh);
+    double* GV = (double*)(scratch + L.off_gv);
+    double* RD = (double*)(scratch + L.off_rd);
+    const double* W = (const double*)(w.base + w.off_W) + (size_t)k0 * w.mat;
+    const double* zv = (const double*)(w.base + w.off_z) + (size_t)k0 * npad;
+    const double* th = theta + (size_t)k0 * tw;
+    const double* xd = (const double*)x;
+    const double* srd = (const double*)sr;
+    const double* x0d = (const double*)x0;
+    if (form_m) {
+        for_kern(w.kern, [&](auto kern) {
+            hipLaunchKernelGGL((box_matrix_kernel<decltype(kern)::value>), dim3(w.nb, w.nb, qg), dim3(256), 0, st, Ms, L.mat, n, npad,
+                               d, xd, srd, th, tw, box);
+        });
+        CHECK_LAUNCH("box_matrix_kernel");
+    }
+    // X (nugget entry at match), U = X W^T, gvar, V = U W: the launches of lcgp_predict_grad on the group's components
+    ThetaArg dummy;
+    memset(&dummy, 0, sizeof(dummy));
+    for_kern(w.kern, [&](auto kern) {
+        hipLaunchKernelGGL((cross_kernel<double, decltype(kern)::value>), dim3(w.nb, L.n0p / TS, qg), dim3(256), 0, st, X, npad, n0, n, d,
+                           x0d, xd, dummy, th, 0, srd, L.n0p, npad, tw, L.slab, match);
+    });
+    CHECK_LAUNCH("cross_kernel");
+    int rc = launch_pred<double, OP_PRED_U>(st, X, W, U, L.slab, w.mat, npad, L.n0p, w.nb, qg);
+    if (rc) return rc;
+    hipLaunchKernelGGL((pred_reduce_kernel<double>), dim3(n0, qg), dim3(64), 0, st, (const double*)X, (const double*)U, L.slab, L.slab,
+                       npad, n, zv, npad, th, tw, d, L.n0r, GH, GV);
+    CHECK_LAUNCH("pred_reduce_kernel");
+    // OP_PRED_V sums in another order on 128-row tiles: below 128 candidates 64-row tiles whatever the padding,
+    // from 128 on the caller never passes fewer, so that a row's V does not depend on the chunking
+    rc = launch_pred<double, OP_PRED_V>(st, U, W, X, L.slab, w.mat, npad, L.n0p, w.nb, qg, 0, n0 < 2 * TS);
+    if (rc) return rc;
+    const double* V = X;
+    // T = V Ms (rows beyond n0p of a slab are never written: their products are never read), then T_c . V_c
+    GemmArgs g;
+    g.A = V; g.B = Ms; g.C = U; g.ldA = g.ldB = g.ldC = npad;
+    g.sA = L.slab; g.sB = L.mat; g.sC = L.slab;
+    g.nb = L.nb / 2; g.p0 = L.n0r / (2 * TS); g.p1 = L.nb / 2; g.p2 = g.p3 = 0;
+    rc = launch_gemm<double, OP_HESS_G, 128>(st, g, g.p0 * g.nb, qg);
+    if (rc) return rc;
+    hipLaunchKernelGGL(pgrad_rowdot_kernel, dim3(n0, qg), dim3(64), 0, st, (const double*)U, V, L.slab, npad, n, RD, (size_t)L.n0r);
+    CHECK_LAUNCH("pgrad_rowdot_kernel");
+    for_kern(w.kern, [&](auto kern) {
+        hipLaunchKernelGGL((box_cross_kernel<decltype(kern)::value>), dim3(n0, qg), dim3(256), 0, st, x0d, xd, srd, n, npad, d, th, tw,
+                           box, V, L.slab, (const double*)RD, (const double*)GV, L.n0r, nrep, ldo, out + (size_t)k0 * ldo);
+    });
+    CHECK_LAUNCH("box_cross_kernel");
+    return 0;
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------------
@@ -9382,6 +9568,38 @@ int lcgp_condition_sobol_matrix_subset_pairs(void* stream, int dtype, int kernel
     Ws w = carve(dtype, n, d, p, q_local, (void*)workspace);
     w.kern = kernel_id;
     return do_condition_sobol((hipStream_t)stream, w, theta, state, m, xa, v, ell, box, ks, nks, scratch, out, masks, nsub);
+}
+
+static int check_box_alc(int dtype, int n_cand) {
+    if (dtype != LCGP_F64) return bad("lcgp_box_alc reads a float64 workspace (its three terms cancel): evaluate on a float64 workspace");
+    if (n_cand < 1) return bad("n_cand must be >= 1");
+    if (n_cand > 65535) return bad("n_cand must be <= 65535: pass the candidates in chunks");
+    return 0;
+}
+
+int lcgp_box_alc_scratch_bytes(int dtype, int n, int d, int q_group, int n_cand, size_t* bytes) {
+    int rc = check_common(dtype, n, d, 1, q_group);
+    if (rc) return rc;
+    if ((rc = check_box_alc(dtype, n_cand))) return rc;
+    if (!bytes) return bad("bytes is NULL");
+    *bytes = box_carve(n, q_group, n_cand).total;
+    return 0;
+}
+
+int lcgp_box_alc(void* stream, int dtype, int kernel_id, int n, int d, int p, int q_local, const void* x, const void* sr,
+                 const double* theta, const void* workspace, int k0, int q_group, const double* box, int n_cand,
+                 const void* x_cand, const int* match, int replicates, int form_m, void* scratch, double* out, int out_stride) {
+    int rc = check_common(dtype, n, d, p, q_local, kernel_id);
+    if (rc) return rc;
+    if ((rc = check_box_alc(dtype, n_cand))) return rc;
+    if (k0 < 0 || q_group < 1 || k0 + q_group > q_local) return bad("k0 / q_group must select components inside [0, q_local)");
+    if (!x || !theta || !workspace || !box || !x_cand || !scratch || !out) return bad("NULL pointer");
+    if (replicates < 1) return bad("replicates must be >= 1");
+    if (out_stride != 0 && out_stride < n_cand) return bad("out_stride must be 0 (= n_cand) or >= n_cand");
+    Ws w = carve(dtype, n, d, p, q_local, (void*)workspace);
+    w.kern = kernel_id;
+    return do_box_alc((hipStream_t)stream, w, x, sr, theta, k0, q_group, box, n_cand, x_cand, match, replicates, form_m,
+                      (char*)scratch, out, out_stride ? out_stride : n_cand);
 }
 
 }  // extern "C"

@@ -1138,6 +1138,56 @@ class HotPathEngine:
                                                     n_cand), entry)
             return out
 
+    def box_alc_block(self, x_cand_s, box_s, match, r, q_group=None):
+        """(q_local, n_cand) float64 DEVICE tensor R_k(c), the drop of the box-integrated posterior variance IV_k if the simulator
+        ran r more times at candidate c (lcgp_box_alc), from the factorisation of the last evaluate() -- which is
+        only read.  x_cand_s (n_cand, d) standardised candidates, box_s (2, d) = [lo; hi] standardised, match as in
+        variance_reduction_block.  float64 engines only.  The candidates go in chunks of PREDICT_CHUNK rows (never fewer than 128
+        while there are that many: point_passes), the local components in groups halved until the scratch fits in the free device
+        memory (q_group: at most that many, for tests): one npad^2 matrix and two chunk_pad x npad slabs per component processed
+        at once; the matrix of a group is formed once and serves all chunks.  Results are bitwise independent of the chunking, of
+        the grouping and of the scratch content.  Raises ValueError when even one component does not fit."""
+        torch = self.torch
+        if self._theta_last is None:
+            raise RuntimeError("integrated_variance_reduction() needs a preceding evaluate() at the current parameters")
+        if self.dtype != _hip.F64:
+            raise RuntimeError("the exact box ALC is float64 only: evaluate on a float64 engine")
+        x_cand_s = np.ascontiguousarray(x_cand_s, np.float64)
+        box_s = np.ascontiguousarray(box_s, np.float64)
+        n0, d = x_cand_s.shape[0], self.d
+        assert x_cand_s.ndim == 2 and x_cand_s.shape[1] == d and n0 >= 1 and box_s.shape == (2, d)
+        if not np.all(box_s[1] > box_s[0]):
+            raise ValueError("box_alc_block: the box needs hi > lo in every dimension")
+        match = None if match is None else np.ascontiguousarray(match, np.int32)
+        if match is not None and not np.any(match >= 0):
+            match = None
+        chunk = min(n0, max(PREDICT_CHUNK, 128) if n0 >= 128 else PREDICT_CHUNK)
+        with torch.cuda.device(self.device):
+            free, _ = torch.cuda.mem_get_info(self.device)
+            free += torch.cuda.memory_reserved(self.device) - torch.cuda.memory_allocated(self.device)
+            free += 0 if self._scratch is None else self._scratch.numel()
+            group = self.q_local if q_group is None else max(1, min(int(q_group), self.q_local))
+            while True:
+                nbytes = self._nbytes("lcgp_box_alc_scratch_bytes", self.dtype, self.n, d, group, chunk)
+                if group == 1 or nbytes <= free:
+                    break
+                group = (group + 1) // 2
+            scp = self._p(self._grow_scratch(nbytes, ("the exact box ALC of %d candidates per pass" % chunk,
+                                                      "one n x n matrix and two of %d x n per component" % chunk,
+                                                      "use fewer training inputs per GPU or lower lcgp_amd.engine.PREDICT_CHUNK")))
+            xcd = torch.as_tensor(x_cand_s).to(self.device).contiguous()
+            boxd = torch.as_tensor(box_s).to(self.device).contiguous()
+            md = None if match is None else torch.as_tensor(match).to(self.device)
+            out = torch.empty((self.q_local, n0), dtype=torch.float64, device=self.device)
+            head = self._head()
+            for k0 in range(0, self.q_local, group):
+                for i, (lo, rows, _) in enumerate(point_passes(n0, chunk, True)):
+                    _hip.check(self.lib.lcgp_box_alc(
+                        *head, k0, min(group, self.q_local - k0), self._p(boxd), rows, C.c_void_p(xcd.data_ptr() + 8 * lo * d),
+                        C.c_void_p(0) if md is None else C.c_void_p(md.data_ptr() + 4 * lo), int(r), 1 if i == 0 else 0, scp,
+                        C.c_void_p(out.data_ptr() + 8 * lo), n0), "lcgp_box_alc")
+            return out
+
     def variance_reduction_grad_block(self, x_cand_s, x_ref_s, w, r):
         return self._vr_grad_block(None, x_cand_s, x_ref_s, w, r)
 

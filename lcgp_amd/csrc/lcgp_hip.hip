@@ -8135,6 +8135,184 @@ int do_box_alc(hipStream_t st, const Ws& w, const void* x, const void* sr, const
 #define LCGP_SRC_HASH "unknown"
 #endif
 
+namespace {
+
+// ---- what the entries share ("Writing an entry": how an entry and its twin on a conditioned view are written) ----
+// opens an entry: check_common, then the carved workspace with its kernel and the stream (nothing is read or enqueued)
+int open_entry(void* stream, int dtype, int kernel_id, int n, int d, int p, int q_local, const void* workspace, Ws& w,
+               hipStream_t& st) {
+    int rc = check_common(dtype, n, d, p, q_local, kernel_id);
+    if (rc) return rc;
+    w = carve(dtype, n, d, p, q_local, (void*)workspace);
+    w.kern = kernel_id;
+    st = (hipStream_t)stream;
+    return 0;
+}
+
+// f(double{}) or f(float{}): the one place a dtype becomes a template argument (f: a generic lambda calling do_x<decltype(t)>)
+template <typename F>
+int by_dtype(int dtype, F&& f) {
+    return dtype == LCGP_F64 ? f(double{}) : f(float{});
+}
+
+// the conditioned view a twin entry runs on (a null ViewArg*: the fitted model) and the size of the caller's scratch, which
+// only the view entries are told and test last
+struct ViewArg {
+    const void* state;
+    int m;
+    const void* xn;
+    const void* grad_state;
+    size_t scratch_bytes;
+};
+
+int check_view(int m) {
+    if (m < 1) return bad("m < 1");
+    return 0;
+}
+
+VrView view_of(int dtype, int n, int q_local, const ViewArg& v) {
+    const CondLay L = cond_carve(dtype, n, q_local, v.m);
+    VrView cv;
+    cv.Un = (const char*)v.state + L.off_U; cv.Wi = (const char*)v.state + L.off_W; cv.xn = v.xn;
+    cv.m = v.m; cv.mpad = L.mpad;
+    return cv;
+}
+
+// match_host / match go together; the host copy is scanned here (n_cand entries: -1 or a training index)
+int check_match(int n, int n_cand, const int* match_host, const int* match) {
+    if ((match_host == nullptr) != (match == nullptr)) return bad("match_host and match must both be NULL or both be given");
+    if (match_host)
+        for (int i = 0; i < n_cand; ++i)
+            if (match_host[i] < -1 || match_host[i] >= n) return bad("match must be -1 or a training index in [0, n)");
+    return 0;
+}
+
+// ---- the per-point queries: lcgp_predict, lcgp_predict_grad, lcgp_predict_hess, lcgp_predict_gradcov and their twins ----
+enum PointKind { PT_VALUE, PT_GRAD, PT_HESS, PT_GRADCOV };
+
+// o: the entry's output pointers in its own order (PT_GRADCOV: dghat, gamma, M; wt its weights); same: lcgp_predict only
+int point_checked(PointKind kind, void* stream, int dtype, int kernel_id, int n, int d, int p, int q_local, const void* x,
+                  const void* sr, const double* theta, const void* workspace, const ViewArg* v, int n0, const void* x0, int same,
+                  void* scratch, double* const (&o)[6], const double* wt, int out_stride) {
+    Ws w;
+    hipStream_t st;
+    int rc = open_entry(stream, dtype, kernel_id, n, d, p, q_local, workspace, w, st);
+    if (rc) return rc;
+    if (v && (rc = check_view(v->m))) return rc;
+    if (n0 < 1) return bad("n0 < 1");
+    if (kind >= PT_HESS && (long long)n0 * d > LCGP_HESS_MAX_ROWS)
+        return bad("n0 * d must be <= LCGP_HESS_MAX_ROWS: pass the new inputs in chunks");
+    bool null = !x || !theta || !workspace || !x0 || !scratch;
+    if (v) null = null || !v->state || !v->xn || (kind != PT_VALUE && !v->grad_state);
+    for (int i = 0; i < (kind == PT_GRADCOV ? 1 : 2 * (kind + 1)); ++i) null = null || !o[i];
+    if (null) return bad("NULL pointer");
+    if (kind == PT_GRADCOV) {
+        if (!o[1] && !wt) return bad("NULL pointer: gamma may only be NULL when w is given");
+        if ((wt != nullptr) != (o[2] != nullptr)) return bad("w and M go together: both or neither");
+    }
+    if (out_stride != 0 && out_stride < n0) return bad("out_stride must be 0 (= n0) or >= n0");
+    if (v) {
+        static const char* const small[] = {
+            "scratch is smaller than lcgp_condition_scratch_bytes(dtype, n, q_local, m, n0)",
+            "scratch is smaller than lcgp_condition_predict_grad_scratch_bytes(dtype, n, q_local, m, n0)",
+            "scratch is smaller than lcgp_condition_predict_hess_scratch_bytes(dtype, n, d, q_local, m, n0)",
+            "scratch is smaller than lcgp_condition_predict_gradcov_scratch_bytes(dtype, n, d, q_local, m, n0)"};
+        const size_t need = (kind != PT_GRADCOV ? cond_predict_scratch(dtype, n, q_local, v->m, n0) : 0) +
+                            (kind >= PT_HESS ? cond_rows_scratch(dtype, n, d, q_local, v->m, n0) : 0);
+        if (v->scratch_bytes < need) return bad(small[kind]);
+    }
+    const int ldo = out_stride ? out_stride : n0;
+    return by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        if (kind == PT_VALUE)
+            return v ? do_condition_predict<T>(st, w, x, sr, theta, v->state, v->m, v->xn, n0, x0, scratch, o[0], o[1], ldo)
+                     : do_predict<T>(st, w, x, sr, theta, n0, x0, same, scratch, o[0], o[1], ldo);
+        if (kind == PT_GRAD)
+            return v ? do_condition_predict_grad<T>(st, w, x, sr, theta, v->state, v->m, v->xn, v->grad_state, n0, x0, scratch, o[0],
+                                                    o[1], o[2], o[3], ldo)
+                     : do_predict_grad<T>(st, w, x, sr, theta, n0, x0, scratch, o[0], o[1], o[2], o[3], ldo);
+        if (kind == PT_HESS)
+            return v ? do_condition_predict_hess<T>(st, w, x, sr, theta, v->state, v->m, v->xn, v->grad_state, n0, x0, scratch, o[0],
+                                                    o[1], o[2], o[3], o[4], o[5], ldo)
+                     : do_predict_hess<T>(st, w, x, sr, theta, n0, x0, scratch, o[0], o[1], o[2], o[3], o[4], o[5], ldo);
+        return v ? do_condition_predict_gradcov<T>(st, w, x, sr, theta, v->state, v->m, v->xn, v->grad_state, n0, x0, scratch, o[0],
+                                                   o[1], wt, o[2], ldo)
+                 : do_predict_gradcov<T>(st, w, x, sr, theta, n0, x0, scratch, o[0], o[1], wt, o[2], ldo);
+    });
+}
+
+// lcgp_predict_hess_scratch_bytes / lcgp_predict_gradcov_scratch_bytes and their twins (m: the view's new inputs)
+int rows_bytes(bool hess, int dtype, int n, int d, int q_local, const int* m, int n0, size_t* bytes) {
+    if (dtype != LCGP_F64 && dtype != LCGP_F32) return bad("dtype must be 0 (f64) or 1 (f32)");
+    if (m ? (n < 1 || q_local < 1) : (n < 1 || n0 < 1 || q_local < 1))
+        return bad(m ? "n, q_local must be >= 1" : "n, n0, q_local must be >= 1");
+    if (d < 1 || d > DWIDE) return bad("d must be in [1, 126]");
+    if (m && *m < 1) return bad("m < 1");
+    if (m && n0 < 1) return bad("n0 < 1");
+    if ((long long)n0 * d > LCGP_HESS_MAX_ROWS) return bad("n0 * d must be <= LCGP_HESS_MAX_ROWS: pass the new inputs in chunks");
+    if (!bytes) return bad("bytes is NULL");
+    if (m)
+        *bytes = (hess ? cond_predict_scratch(dtype, n, q_local, *m, n0) : 0) + cond_rows_scratch(dtype, n, d, q_local, *m, n0);
+    else
+        *bytes = 2 * (size_t)q_local * ((hess ? predict_pad(n0) : 0) + (size_t)hess_rows_pad(n0, d)) * round_up(n, 2 * TS) *
+                 (dtype == LCGP_F64 ? 8 : 4);
+    return 0;
+}
+
+// ---- lcgp_predict_cov and its twin ----
+int cov_checked(void* stream, int dtype, int kernel_id, int n, int d, int p, int q_local, const void* x, const void* sr,
+                const double* theta, const void* workspace, const ViewArg* v, int n0, const void* x0, int same, void* scratch,
+                void* cov_workspace, double jitter) {
+    Ws w;
+    hipStream_t st;
+    int rc = open_entry(stream, dtype, kernel_id, n, d, p, q_local, workspace, w, st);
+    if (rc) return rc;
+    if (v && (rc = check_view(v->m))) return rc;
+    if (n0 < 1) return bad("n0 < 1");
+    if (!v && (same < 0 || (same > 0 && same - 1 + n0 > n))) return bad("same must be 0 or 1 + the row offset of x0 within x");
+    if (!(jitter >= 0.0) || !__builtin_isfinite(jitter)) return bad("jitter must be finite and >= 0");
+    if (!x || !theta || !workspace || (v && (!v->state || !v->xn)) || !x0 || !scratch || !cov_workspace) return bad("NULL pointer");
+    if (v && v->scratch_bytes < cond_cov_carve(dtype, n, q_local, v->m, n0).total)
+        return bad("scratch is smaller than lcgp_condition_predict_cov_scratch_bytes(dtype, n, q_local, m, n0)");
+    const Ws cw = carve(dtype, n0, d, p, q_local, cov_workspace);
+    return by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return v ? do_condition_predict_cov<T>(st, w, x, sr, theta, view_of(dtype, n, q_local, *v), n0, x0, (char*)scratch, cw, jitter)
+                 : do_predict_cov<T>(st, w, x, sr, theta, n0, x0, same, scratch, cw, jitter);
+    });
+}
+
+// ---- lcgp_predict_marginal (v == nullptr) and lcgp_condition_predict_marginal, which also runs without a state (m == 0) ----
+int marginal_checked(void* stream, int dtype, int kernel_id, int n, int d, int p, int q_local, const void* x, const void* sr,
+                     const double* theta, const void* workspace, const ViewArg* v, int n0, const void* x0,
+                     const unsigned char* mask, const double* box, void* scratch, double* ghat, double* gvar, int out_stride,
+                     const MargRef& ref) {
+    Ws w;
+    hipStream_t st;
+    int rc = open_entry(stream, dtype, kernel_id, n, d, p, q_local, workspace, w, st);
+    if (rc) return rc;
+    if (v && (v->state ? v->m < 1 : v->m != 0)) return bad("m must be >= 1 with a state and 0 without one");
+    if (n0 < 1) return bad("n0 < 1");
+    if (!x || !theta || !workspace || !x0 || !mask || !box || !scratch || !ghat || !gvar) return bad("NULL pointer");
+    if (v && v->state && !v->xn) return bad("NULL pointer");
+    if (ref.out && (ref.row < 0 || ref.row >= n0)) return bad("ref_row must be a row of the pass");
+    if (ref.in && (!ref.x || !ref.mask || !ref.gcov)) return bad("ref_in needs ref_x, ref_mask and gcov");
+    if (out_stride != 0 && out_stride < n0) return bad("out_stride must be 0 (= n0) or >= n0");
+    if (v) {
+        size_t need = 0;
+        if ((rc = lcgp_condition_predict_marginal_scratch_bytes(dtype, n, d, q_local, v->m, n0, &need))) return rc;
+        if (v->scratch_bytes < need)
+            return bad("scratch is smaller than lcgp_condition_predict_marginal_scratch_bytes(dtype, n, d, q_local, m, n0)");
+    }
+    const int ldo = out_stride ? out_stride : n0;
+    return by_dtype(dtype, [&](auto t) {
+        return do_predict_marginal<decltype(t)>(st, w, x, sr, theta, v ? v->state : nullptr, v ? v->m : 0, v ? v->xn : nullptr, n0, x0,
+                                                mask, box, scratch, ghat, gvar, ldo, ref);
+    });
+}
+
+}  // namespace
+
 extern "C" {
 
 int lcgp_version(void) { return LCGP_VERSION; }
@@ -8180,9 +8358,7 @@ int lcgp_covmat(void* stream, int dtype, int kernel_id, int n1, int n2, int d, c
     for (int j = 0; j < d; ++j) th.v[j] = ell[j];
     th.v[d] = scale;
     th.v[d + 1] = nug;
-    hipStream_t st = (hipStream_t)stream;
-    return dtype == LCGP_F64 ? do_matern<double>(st, kernel_id, n1, n2, d, x1, x2, th, same, out)
-                             : do_matern<float>(st, kernel_id, n1, n2, d, x1, x2, th, same, out);
+    return by_dtype(dtype, [&](auto t) { return do_matern<decltype(t)>((hipStream_t)stream, kernel_id, n1, n2, d, x1, x2, th, same, out); });
 }
 int lcgp_matern32(void* stream, int dtype, int n1, int n2, int d, const void* x1, const void* x2, const double* ell,
                   double scale, double nug, int same, void* out) {
@@ -8191,28 +8367,26 @@ int lcgp_matern32(void* stream, int dtype, int n1, int n2, int d, const void* x1
 
 int lcgp_kernel_build(void* stream, int dtype, int kernel_id, int n, int d, int p, int q_local, const void* x, const void* sr,
                       const double* theta, void* workspace) {
-    int rc = check_common(dtype, n, d, p, q_local, kernel_id);
+    Ws w;
+    hipStream_t st;
+    int rc = open_entry(stream, dtype, kernel_id, n, d, p, q_local, workspace, w, st);
     if (rc) return rc;
     if (!x || !theta || !workspace) return bad("NULL pointer");
-    Ws w = carve(dtype, n, d, p, q_local, workspace);
-    w.kern = kernel_id;
-    return dtype == LCGP_F64 ? do_build<double>((hipStream_t)stream, w, x, sr, theta)
-                             : do_build<float>((hipStream_t)stream, w, x, sr, theta);
+    return by_dtype(dtype, [&](auto t) { return do_build<decltype(t)>(st, w, x, sr, theta); });
 }
 
 int lcgp_potrf_logdet(void* stream, int dtype, int n, int d, int p, int q_local, void* workspace, double* half_logdet,
                       int* info, const lcgp_sched* sched, const void* plan) {
     const void* plan_host = plan;
-    int rc = check_common(dtype, n, d, p, q_local);
+    Ws w;
+    hipStream_t st;
+    int rc = open_entry(stream, dtype, 0, n, d, p, q_local, workspace, w, st);
     if (rc) return rc;
     if (!workspace) return bad("NULL workspace");
     lcgp_sched sc;
     if ((rc = resolve_sched(sched, sc))) return rc;
     if (plan_host && (rc = check_plan(plan_host, dtype, n, q_local, false))) return rc;
-    Ws w = carve(dtype, n, d, p, q_local, workspace);
-    hipStream_t st = (hipStream_t)stream;
-    rc = dtype == LCGP_F64 ? do_potrf<double>(st, w, sc, false, false, nullptr, plan_host)
-                           : do_potrf<float>(st, w, sc, false, false, nullptr, plan_host);
+    rc = by_dtype(dtype, [&](auto t) { return do_potrf<decltype(t)>(st, w, sc, false, false, nullptr, plan_host); });
     if (rc) return rc;
     if (half_logdet || info) {
         hipLaunchKernelGGL(copy_stats_kernel, dim3((q_local + 63) / 64), dim3(64), 0, st,
@@ -8223,34 +8397,30 @@ int lcgp_potrf_logdet(void* stream, int dtype, int n, int d, int p, int q_local,
     return 0;
 }
 
+// lcgp_potri (stage 0), lcgp_trtri (1), lcgp_lauum (2)
+static int inverse_stage(int stage, void* stream, int dtype, int n, int d, int p, int q_local, void* workspace,
+                         const lcgp_sched* sched) {
+    Ws w;
+    hipStream_t st;
+    int rc = open_entry(stream, dtype, 0, n, d, p, q_local, workspace, w, st);
+    if (rc) return rc;
+    if (!workspace) return bad("NULL workspace");
+    lcgp_sched sc;
+    if ((rc = resolve_sched(sched, sc))) return rc;
+    return by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return stage == 0 ? do_potri<T>(st, w, sc) : stage == 1 ? do_trtri<T>(st, w, sc) : do_lauum<T>(st, w, sc);
+    });
+}
+
 int lcgp_potri(void* stream, int dtype, int n, int d, int p, int q_local, void* workspace, const lcgp_sched* sched) {
-    int rc = check_common(dtype, n, d, p, q_local);
-    if (rc) return rc;
-    if (!workspace) return bad("NULL workspace");
-    lcgp_sched sc;
-    if ((rc = resolve_sched(sched, sc))) return rc;
-    Ws w = carve(dtype, n, d, p, q_local, workspace);
-    return dtype == LCGP_F64 ? do_potri<double>((hipStream_t)stream, w, sc) : do_potri<float>((hipStream_t)stream, w, sc);
+    return inverse_stage(0, stream, dtype, n, d, p, q_local, workspace, sched);
 }
-
 int lcgp_trtri(void* stream, int dtype, int n, int d, int p, int q_local, void* workspace, const lcgp_sched* sched) {
-    int rc = check_common(dtype, n, d, p, q_local);
-    if (rc) return rc;
-    if (!workspace) return bad("NULL workspace");
-    lcgp_sched sc;
-    if ((rc = resolve_sched(sched, sc))) return rc;
-    Ws w = carve(dtype, n, d, p, q_local, workspace);
-    return dtype == LCGP_F64 ? do_trtri<double>((hipStream_t)stream, w, sc) : do_trtri<float>((hipStream_t)stream, w, sc);
+    return inverse_stage(1, stream, dtype, n, d, p, q_local, workspace, sched);
 }
-
 int lcgp_lauum(void* stream, int dtype, int n, int d, int p, int q_local, void* workspace, const lcgp_sched* sched) {
-    int rc = check_common(dtype, n, d, p, q_local);
-    if (rc) return rc;
-    if (!workspace) return bad("NULL workspace");
-    lcgp_sched sc;
-    if ((rc = resolve_sched(sched, sc))) return rc;
-    Ws w = carve(dtype, n, d, p, q_local, workspace);
-    return dtype == LCGP_F64 ? do_lauum<double>((hipStream_t)stream, w, sc) : do_lauum<float>((hipStream_t)stream, w, sc);
+    return inverse_stage(2, stream, dtype, n, d, p, q_local, workspace, sched);
 }
 
 int lcgp_lauum_clock(void* stream, int dtype, int n, int d, int p, int q_local, const void* workspace,
@@ -8306,7 +8476,9 @@ int lcgp_nll_grad(void* stream, int dtype, int kernel_id, int n, int d, int p, i
                   const void* sr, const double* theta, void* workspace, double* out, const lcgp_sched* sched,
                   const void* plan) {
     const void* plan_host = plan;
-    int rc = check_common(dtype, n, d, p, q_local, kernel_id);
+    Ws w;
+    hipStream_t st;
+    int rc = open_entry(stream, dtype, kernel_id, n, d, p, q_local, workspace, w, st);
     if (rc) return rc;
     if (!x || !Y || !theta || !workspace || !out) return bad("NULL pointer");
     lcgp_sched sc;
@@ -8317,10 +8489,7 @@ int lcgp_nll_grad(void* stream, int dtype, int kernel_id, int n, int d, int p, i
     } else if ((rc = resolve_sched(sched, sc))) {
         return rc;
     }
-    Ws w = carve(dtype, n, d, p, q_local, workspace);
-    w.kern = kernel_id;
-    return dtype == LCGP_F64 ? do_nll_grad<double>((hipStream_t)stream, w, sc, x, Y, sr, theta, out, plan_host)
-                             : do_nll_grad<float>((hipStream_t)stream, w, sc, x, Y, sr, theta, out, plan_host);
+    return by_dtype(dtype, [&](auto t) { return do_nll_grad<decltype(t)>(st, w, sc, x, Y, sr, theta, out, plan_host); });
 }
 
 int lcgp_nll_hess_width(int d, int p) { return hess_out_width(d, p); }
@@ -8342,14 +8511,14 @@ int lcgp_nll_hess_scratch_bytes(int dtype, int n, int d, int p, int q_group, siz
 
 int lcgp_nll_hess(void* stream, int dtype, int kernel_id, int n, int d, int p, int q_local, const void* x, const void* Y,
                   const void* sr, const double* theta, const void* workspace, int k0, int q_group, void* scratch, double* out) {
-    int rc = check_common(dtype, n, d, p, q_local, kernel_id);
+    Ws w;
+    hipStream_t st;
+    int rc = open_entry(stream, dtype, kernel_id, n, d, p, q_local, workspace, w, st);
     if (rc) return rc;
     if ((rc = check_nll_hess(dtype))) return rc;
     if (k0 < 0 || q_group < 1 || k0 + q_group > q_local) return bad("k0 / q_group must select components inside [0, q_local)");
     if (!x || !Y || !theta || !workspace || !scratch || !out) return bad("NULL pointer");
-    Ws w = carve(dtype, n, d, p, q_local, (void*)workspace);
-    w.kern = kernel_id;
-    return do_nll_hess((hipStream_t)stream, w, x, (const double*)Y, sr, theta, k0, q_group, (char*)scratch, out);
+    return do_nll_hess(st, w, x, (const double*)Y, sr, theta, k0, q_group, (char*)scratch, out);
 }
 
 static int check_predict_paramgrad(int dtype, int n0) {
@@ -8372,7 +8541,9 @@ int lcgp_predict_paramgrad(void* stream, int dtype, int kernel_id, int n, int d,
                            const void* sr, const double* theta, const void* workspace, int k0, int q_group, int n0, const void* x0,
                            int same, void* scratch, double* ghat, double* gvar, double* dghat, double* dgvar, double* dghat_noise,
                            int out_stride) {
-    int rc = check_common(dtype, n, d, p, q_local, kernel_id);
+    Ws w;
+    hipStream_t st;
+    int rc = open_entry(stream, dtype, kernel_id, n, d, p, q_local, workspace, w, st);
     if (rc) return rc;
     if ((rc = check_predict_paramgrad(dtype, n0))) return rc;
     if (k0 < 0 || q_group < 1 || k0 + q_group > q_local) return bad("k0 / q_group must select components inside [0, q_local)");
@@ -8380,9 +8551,7 @@ int lcgp_predict_paramgrad(void* stream, int dtype, int kernel_id, int n, int d,
         return bad("NULL pointer");
     if (out_stride != 0 && out_stride < n0) return bad("out_stride must be 0 (= n0) or >= n0");
     if (same < 0 || (same > 0 && (long long)same - 1 + n0 > n)) return bad("same: the rows of x0 must be training inputs same - 1 .. same - 2 + n0");
-    Ws w = carve(dtype, n, d, p, q_local, (void*)workspace);
-    w.kern = kernel_id;
-    return do_predict_paramgrad((hipStream_t)stream, w, x, (const double*)Y, sr, theta, k0, q_group, n0, x0, same, (char*)scratch,
+    return do_predict_paramgrad(st, w, x, (const double*)Y, sr, theta, k0, q_group, n0, x0, same, (char*)scratch,
                                 ghat, gvar, dghat, dgvar, dghat_noise, out_stride ? out_stride : n0);
 }
 
@@ -8431,17 +8600,9 @@ int lcgp_pack_partial(void* stream, int d, int p, int q_local, int q_total, cons
 int lcgp_predict(void* stream, int dtype, int kernel_id, int n, int d, int p, int q_local, const void* x, const void* sr,
                  const double* theta, const void* workspace, int n0, const void* x0, int same, void* scratch,
                  double* ghat, double* gvar, int out_stride) {
-    int rc = check_common(dtype, n, d, p, q_local, kernel_id);
-    if (rc) return rc;
-    if (n0 < 1) return bad("n0 < 1");
-    if (!x || !theta || !workspace || !x0 || !scratch || !ghat || !gvar) return bad("NULL pointer");
-    if (out_stride != 0 && out_stride < n0) return bad("out_stride must be 0 (= n0) or >= n0");
-    const int ldo = out_stride ? out_stride : n0;
-    Ws w = carve(dtype, n, d, p, q_local, (void*)workspace);
-    w.kern = kernel_id;
-    hipStream_t st = (hipStream_t)stream;
-    return dtype == LCGP_F64 ? do_predict<double>(st, w, x, sr, theta, n0, x0, same, scratch, ghat, gvar, ldo)
-                             : do_predict<float>(st, w, x, sr, theta, n0, x0, same, scratch, ghat, gvar, ldo);
+    double* const o[6] = {ghat, gvar};
+    return point_checked(PT_VALUE, stream, dtype, kernel_id, n, d, p, q_local, x, sr, theta, workspace, nullptr, n0, x0, same, scratch,
+                         o, nullptr, out_stride);
 }
 
 int lcgp_predict_marginal_scratch_bytes(int dtype, int n, int d, int q_local, int n0, size_t* bytes) {
@@ -8455,19 +8616,8 @@ int lcgp_predict_marginal_scratch_bytes(int dtype, int n, int d, int q_local, in
 int lcgp_predict_marginal(void* stream, int dtype, int kernel_id, int n, int d, int p, int q_local, const void* x, const void* sr,
                           const double* theta, const void* workspace, int n0, const void* x0, const unsigned char* mask,
                           const double* box, void* scratch, double* ghat, double* gvar, int out_stride) {
-    int rc = check_common(dtype, n, d, p, q_local, kernel_id);
-    if (rc) return rc;
-    if (n0 < 1) return bad("n0 < 1");
-    if (!x || !theta || !workspace || !x0 || !mask || !box || !scratch || !ghat || !gvar) return bad("NULL pointer");
-    if (out_stride != 0 && out_stride < n0) return bad("out_stride must be 0 (= n0) or >= n0");
-    const int ldo = out_stride ? out_stride : n0;
-    Ws w = carve(dtype, n, d, p, q_local, (void*)workspace);
-    w.kern = kernel_id;
-    hipStream_t st = (hipStream_t)stream;
-    const MargRef none;
-    return dtype == LCGP_F64
-               ? do_predict_marginal<double>(st, w, x, sr, theta, nullptr, 0, nullptr, n0, x0, mask, box, scratch, ghat, gvar, ldo, none)
-               : do_predict_marginal<float>(st, w, x, sr, theta, nullptr, 0, nullptr, n0, x0, mask, box, scratch, ghat, gvar, ldo, none);
+    return marginal_checked(stream, dtype, kernel_id, n, d, p, q_local, x, sr, theta, workspace, nullptr, n0, x0, mask, box, scratch,
+                            ghat, gvar, out_stride, MargRef());
 }
 
 int lcgp_predict_grad_scratch_bytes(int dtype, int n, int q_local, int n0, size_t* bytes) {
@@ -8477,76 +8627,33 @@ int lcgp_predict_grad_scratch_bytes(int dtype, int n, int q_local, int n0, size_
 int lcgp_predict_grad(void* stream, int dtype, int kernel_id, int n, int d, int p, int q_local, const void* x, const void* sr,
                       const double* theta, const void* workspace, int n0, const void* x0, void* scratch,
                       double* ghat, double* gvar, double* dghat, double* dgvar, int out_stride) {
-    int rc = check_common(dtype, n, d, p, q_local, kernel_id);
-    if (rc) return rc;
-    if (n0 < 1) return bad("n0 < 1");
-    if (!x || !theta || !workspace || !x0 || !scratch || !ghat || !gvar || !dghat || !dgvar) return bad("NULL pointer");
-    if (out_stride != 0 && out_stride < n0) return bad("out_stride must be 0 (= n0) or >= n0");
-    const int ldo = out_stride ? out_stride : n0;
-    Ws w = carve(dtype, n, d, p, q_local, (void*)workspace);
-    w.kern = kernel_id;
-    hipStream_t st = (hipStream_t)stream;
-    return dtype == LCGP_F64 ? do_predict_grad<double>(st, w, x, sr, theta, n0, x0, scratch, ghat, gvar, dghat, dgvar, ldo)
-                             : do_predict_grad<float>(st, w, x, sr, theta, n0, x0, scratch, ghat, gvar, dghat, dgvar, ldo);
+    double* const o[6] = {ghat, gvar, dghat, dgvar};
+    return point_checked(PT_GRAD, stream, dtype, kernel_id, n, d, p, q_local, x, sr, theta, workspace, nullptr, n0, x0, 0, scratch, o,
+                         nullptr, out_stride);
 }
 
 int lcgp_predict_hess_scratch_bytes(int dtype, int n, int d, int q_local, int n0, size_t* bytes) {
-    if (dtype != LCGP_F64 && dtype != LCGP_F32) return bad("dtype must be 0 (f64) or 1 (f32)");
-    if (n < 1 || n0 < 1 || q_local < 1) return bad("n, n0, q_local must be >= 1");
-    if (d < 1 || d > DWIDE) return bad("d must be in [1, 126]");
-    if ((long long)n0 * d > LCGP_HESS_MAX_ROWS) return bad("n0 * d must be <= LCGP_HESS_MAX_ROWS: pass the new inputs in chunks");
-    if (!bytes) return bad("bytes is NULL");
-    const size_t npad = round_up(n, 2 * TS), n0pad = predict_pad(n0), rows_pad = hess_rows_pad(n0, d);
-    *bytes = 2 * (size_t)q_local * (n0pad + rows_pad) * npad * (dtype == LCGP_F64 ? 8 : 4);
-    return 0;
+    return rows_bytes(true, dtype, n, d, q_local, nullptr, n0, bytes);
 }
 
 int lcgp_predict_hess(void* stream, int dtype, int kernel_id, int n, int d, int p, int q_local, const void* x, const void* sr,
                       const double* theta, const void* workspace, int n0, const void* x0, void* scratch,
                       double* ghat, double* gvar, double* dghat, double* dgvar, double* d2ghat, double* d2gvar, int out_stride) {
-    int rc = check_common(dtype, n, d, p, q_local, kernel_id);
-    if (rc) return rc;
-    if (n0 < 1) return bad("n0 < 1");
-    if ((long long)n0 * d > LCGP_HESS_MAX_ROWS) return bad("n0 * d must be <= LCGP_HESS_MAX_ROWS: pass the new inputs in chunks");
-    if (!x || !theta || !workspace || !x0 || !scratch || !ghat || !gvar || !dghat || !dgvar || !d2ghat || !d2gvar)
-        return bad("NULL pointer");
-    if (out_stride != 0 && out_stride < n0) return bad("out_stride must be 0 (= n0) or >= n0");
-    const int ldo = out_stride ? out_stride : n0;
-    Ws w = carve(dtype, n, d, p, q_local, (void*)workspace);
-    w.kern = kernel_id;
-    hipStream_t st = (hipStream_t)stream;
-    return dtype == LCGP_F64
-               ? do_predict_hess<double>(st, w, x, sr, theta, n0, x0, scratch, ghat, gvar, dghat, dgvar, d2ghat, d2gvar, ldo)
-               : do_predict_hess<float>(st, w, x, sr, theta, n0, x0, scratch, ghat, gvar, dghat, dgvar, d2ghat, d2gvar, ldo);
+    double* const o[6] = {ghat, gvar, dghat, dgvar, d2ghat, d2gvar};
+    return point_checked(PT_HESS, stream, dtype, kernel_id, n, d, p, q_local, x, sr, theta, workspace, nullptr, n0, x0, 0, scratch, o,
+                         nullptr, out_stride);
 }
 
 int lcgp_predict_gradcov_scratch_bytes(int dtype, int n, int d, int q_local, int n0, size_t* bytes) {
-    if (dtype != LCGP_F64 && dtype != LCGP_F32) return bad("dtype must be 0 (f64) or 1 (f32)");
-    if (n < 1 || n0 < 1 || q_local < 1) return bad("n, n0, q_local must be >= 1");
-    if (d < 1 || d > DWIDE) return bad("d must be in [1, 126]");
-    if ((long long)n0 * d > LCGP_HESS_MAX_ROWS) return bad("n0 * d must be <= LCGP_HESS_MAX_ROWS: pass the new inputs in chunks");
-    if (!bytes) return bad("bytes is NULL");
-    *bytes = 2 * (size_t)q_local * hess_rows_pad(n0, d) * round_up(n, 2 * TS) * (dtype == LCGP_F64 ? 8 : 4);
-    return 0;
+    return rows_bytes(false, dtype, n, d, q_local, nullptr, n0, bytes);
 }
 
 int lcgp_predict_gradcov(void* stream, int dtype, int kernel_id, int n, int d, int p, int q_local, const void* x, const void* sr,
                          const double* theta, const void* workspace, int n0, const void* x0, void* scratch, double* dghat,
                          double* gamma, const double* w, double* M, int out_stride) {
-    int rc = check_common(dtype, n, d, p, q_local, kernel_id);
-    if (rc) return rc;
-    if (n0 < 1) return bad("n0 < 1");
-    if ((long long)n0 * d > LCGP_HESS_MAX_ROWS) return bad("n0 * d must be <= LCGP_HESS_MAX_ROWS: pass the new inputs in chunks");
-    if (!x || !theta || !workspace || !x0 || !scratch || !dghat) return bad("NULL pointer");
-    if (!gamma && !w) return bad("NULL pointer: gamma may only be NULL when w is given");
-    if ((w != nullptr) != (M != nullptr)) return bad("w and M go together: both or neither");
-    if (out_stride != 0 && out_stride < n0) return bad("out_stride must be 0 (= n0) or >= n0");
-    const int ldo = out_stride ? out_stride : n0;
-    Ws ws = carve(dtype, n, d, p, q_local, (void*)workspace);
-    ws.kern = kernel_id;
-    hipStream_t st = (hipStream_t)stream;
-    return dtype == LCGP_F64 ? do_predict_gradcov<double>(st, ws, x, sr, theta, n0, x0, scratch, dghat, gamma, w, M, ldo)
-                             : do_predict_gradcov<float>(st, ws, x, sr, theta, n0, x0, scratch, dghat, gamma, w, M, ldo);
+    double* const o[6] = {dghat, gamma, M};
+    return point_checked(PT_GRADCOV, stream, dtype, kernel_id, n, d, p, q_local, x, sr, theta, workspace, nullptr, n0, x0, 0, scratch,
+                         o, w, out_stride);
 }
 
 int lcgp_predict_cov_scratch_bytes(int dtype, int n, int q_local, int n0, size_t* bytes) {
@@ -8569,32 +8676,21 @@ int lcgp_sample_scratch_bytes(int dtype, int n0, int q_local, int S, size_t* byt
 int lcgp_predict_cov(void* stream, int dtype, int kernel_id, int n, int d, int p, int q_local, const void* x, const void* sr,
                      const double* theta, const void* workspace, int n0, const void* x0, int same, void* scratch,
                      void* cov_workspace, double jitter) {
-    int rc = check_common(dtype, n, d, p, q_local, kernel_id);
-    if (rc) return rc;
-    if (n0 < 1) return bad("n0 < 1");
-    if (same < 0 || (same > 0 && same - 1 + n0 > n)) return bad("same must be 0 or 1 + the row offset of x0 within x");
-    if (!(jitter >= 0.0) || !__builtin_isfinite(jitter)) return bad("jitter must be finite and >= 0");
-    if (!x || !theta || !workspace || !x0 || !scratch || !cov_workspace) return bad("NULL pointer");
-    Ws w = carve(dtype, n, d, p, q_local, (void*)workspace);
-    w.kern = kernel_id;
-    Ws cw = carve(dtype, n0, d, p, q_local, cov_workspace);
-    hipStream_t st = (hipStream_t)stream;
-    return dtype == LCGP_F64 ? do_predict_cov<double>(st, w, x, sr, theta, n0, x0, same, scratch, cw, jitter)
-                             : do_predict_cov<float>(st, w, x, sr, theta, n0, x0, same, scratch, cw, jitter);
+    return cov_checked(stream, dtype, kernel_id, n, d, p, q_local, x, sr, theta, workspace, nullptr, n0, x0, same, scratch,
+                       cov_workspace, jitter);
 }
 
 int lcgp_sample_latent(void* stream, int dtype, int n0, int d, int p, int q_local, int S, void* cov_workspace, const void* eps,
                        const double* ghat, int ldg, void* scratch, double* out) {
-    int rc = check_common(dtype, n0, d, p, q_local);
+    Ws cw;
+    hipStream_t st;
+    int rc = open_entry(stream, dtype, 0, n0, d, p, q_local, cov_workspace, cw, st);
     if (rc) return rc;
     if (S < 1 || S > LCGP_SAMPLE_MAX) return bad("S must be in [1, 32768]");
     if (ldg != 0 && ldg < n0) return bad("ldg must be 0 (= n0) or >= n0");
     if (!cov_workspace || !eps || !ghat || !scratch || !out) return bad("NULL pointer");
-    Ws cw = carve(dtype, n0, d, p, q_local, cov_workspace);
-    hipStream_t st = (hipStream_t)stream;
     const int ld = ldg ? ldg : n0;
-    return dtype == LCGP_F64 ? do_sample<double>(st, cw, S, eps, ghat, ld, scratch, out)
-                             : do_sample<float>(st, cw, S, eps, ghat, ld, scratch, out);
+    return by_dtype(dtype, [&](auto t) { return do_sample<decltype(t)>(st, cw, S, eps, ghat, ld, scratch, out); });
 }
 
 int lcgp_condition_scratch_bytes(int dtype, int n, int q_local, int m, int n0, size_t* bytes) {
@@ -8622,37 +8718,27 @@ int lcgp_condition_state_bytes(int dtype, int n, int d, int q_local, int m, size
 int lcgp_condition_prepare(void* stream, int dtype, int kernel_id, int n, int d, int p, int q_local, const void* x, const void* sr,
                            const double* theta, const void* workspace, int m, const void* xn, const double* t, const double* r,
                            void* scratch, size_t scratch_bytes, void* cond_workspace, void* state, int* info) {
-    int rc = check_common(dtype, n, d, p, q_local, kernel_id);
+    Ws w;
+    hipStream_t st;
+    int rc = open_entry(stream, dtype, kernel_id, n, d, p, q_local, workspace, w, st);
     if (rc) return rc;
     if (m < 1) return bad("m < 1");
     if (!x || !theta || !workspace || !xn || !t || !scratch || !cond_workspace || !state || !info) return bad("NULL pointer");
     if (scratch_bytes < cond_prepare_scratch(dtype, n, q_local, m))
         return bad("scratch is smaller than lcgp_condition_scratch_bytes(dtype, n, q_local, m, 0)");
-    Ws w = carve(dtype, n, d, p, q_local, (void*)workspace);
-    w.kern = kernel_id;
-    Ws cw = carve(dtype, m, d, p, q_local, cond_workspace);
-    hipStream_t st = (hipStream_t)stream;
-    return dtype == LCGP_F64 ? do_condition_prepare<double>(st, w, x, sr, theta, m, xn, t, r, scratch, cw, state, info)
-                             : do_condition_prepare<float>(st, w, x, sr, theta, m, xn, t, r, scratch, cw, state, info);
+    const Ws cw = carve(dtype, m, d, p, q_local, cond_workspace);
+    return by_dtype(dtype, [&](auto t_) {
+        return do_condition_prepare<decltype(t_)>(st, w, x, sr, theta, m, xn, t, r, scratch, cw, state, info);
+    });
 }
 
 int lcgp_condition_predict(void* stream, int dtype, int kernel_id, int n, int d, int p, int q_local, const void* x, const void* sr,
                            const double* theta, const void* workspace, const void* state, int m, const void* xn, int n0,
                            const void* x0, void* scratch, size_t scratch_bytes, double* ghat, double* gvar, int out_stride) {
-    int rc = check_common(dtype, n, d, p, q_local, kernel_id);
-    if (rc) return rc;
-    if (m < 1) return bad("m < 1");
-    if (n0 < 1) return bad("n0 < 1");
-    if (!x || !theta || !workspace || !state || !xn || !x0 || !scratch || !ghat || !gvar) return bad("NULL pointer");
-    if (out_stride != 0 && out_stride < n0) return bad("out_stride must be 0 (= n0) or >= n0");
-    if (scratch_bytes < cond_predict_scratch(dtype, n, q_local, m, n0))
-        return bad("scratch is smaller than lcgp_condition_scratch_bytes(dtype, n, q_local, m, n0)");
-    const int ldo = out_stride ? out_stride : n0;
-    Ws w = carve(dtype, n, d, p, q_local, (void*)workspace);
-    w.kern = kernel_id;
-    hipStream_t st = (hipStream_t)stream;
-    return dtype == LCGP_F64 ? do_condition_predict<double>(st, w, x, sr, theta, state, m, xn, n0, x0, scratch, ghat, gvar, ldo)
-                             : do_condition_predict<float>(st, w, x, sr, theta, state, m, xn, n0, x0, scratch, ghat, gvar, ldo);
+    const ViewArg v{state, m, xn, nullptr, scratch_bytes};
+    double* const o[6] = {ghat, gvar};
+    return point_checked(PT_VALUE, stream, dtype, kernel_id, n, d, p, q_local, x, sr, theta, workspace, &v, n0, x0, 0, scratch, o,
+                         nullptr, out_stride);
 }
 
 int lcgp_condition_predict_marginal_scratch_bytes(int dtype, int n, int d, int q_local, int m, int n0, size_t* bytes) {
@@ -8673,29 +8759,11 @@ int lcgp_condition_predict_marginal(void* stream, int dtype, int kernel_id, int 
                                     void* scratch, size_t scratch_bytes, double* ghat, double* gvar, int out_stride, int ref_row,
                                     void* ref_out, const void* ref_in, const void* ref_x, const unsigned char* ref_mask,
                                     double* gcov) {
-    int rc = check_common(dtype, n, d, p, q_local, kernel_id);
-    if (rc) return rc;
-    if (state ? m < 1 : m != 0) return bad("m must be >= 1 with a state and 0 without one");
-    if (n0 < 1) return bad("n0 < 1");
-    if (!x || !theta || !workspace || !x0 || !mask || !box || !scratch || !ghat || !gvar) return bad("NULL pointer");
-    if (state && !xn) return bad("NULL pointer");
-    if (ref_out && (ref_row < 0 || ref_row >= n0)) return bad("ref_row must be a row of the pass");
-    if (ref_in && (!ref_x || !ref_mask || !gcov)) return bad("ref_in needs ref_x, ref_mask and gcov");
-    if (out_stride != 0 && out_stride < n0) return bad("out_stride must be 0 (= n0) or >= n0");
-    size_t need = 0;
-    rc = lcgp_condition_predict_marginal_scratch_bytes(dtype, n, d, q_local, m, n0, &need);
-    if (rc) return rc;
-    if (scratch_bytes < need)
-        return bad("scratch is smaller than lcgp_condition_predict_marginal_scratch_bytes(dtype, n, d, q_local, m, n0)");
-    const int ldo = out_stride ? out_stride : n0;
-    Ws w = carve(dtype, n, d, p, q_local, (void*)workspace);
-    w.kern = kernel_id;
-    hipStream_t st = (hipStream_t)stream;
+    const ViewArg v{state, m, xn, nullptr, scratch_bytes};
     MargRef ref;
     ref.row = ref_row; ref.out = ref_out; ref.in = ref_in; ref.x = ref_x; ref.mask = ref_mask; ref.gcov = gcov;
-    return dtype == LCGP_F64
-               ? do_predict_marginal<double>(st, w, x, sr, theta, state, m, xn, n0, x0, mask, box, scratch, ghat, gvar, ldo, ref)
-               : do_predict_marginal<float>(st, w, x, sr, theta, state, m, xn, n0, x0, mask, box, scratch, ghat, gvar, ldo, ref);
+    return marginal_checked(stream, dtype, kernel_id, n, d, p, q_local, x, sr, theta, workspace, &v, n0, x0, mask, box, scratch, ghat,
+                            gvar, out_stride, ref);
 }
 
 int lcgp_condition_grad_state_bytes(int dtype, int n, int q_local, int m, size_t* bytes) {
@@ -8709,14 +8777,13 @@ int lcgp_condition_grad_state_bytes(int dtype, int n, int q_local, int m, size_t
 
 int lcgp_condition_grad_prepare(void* stream, int dtype, int n, int d, int p, int q_local, const double* theta,
                                 const void* workspace, const void* state, int m, void* grad_state) {
-    int rc = check_common(dtype, n, d, p, q_local);
+    Ws w;
+    hipStream_t st;
+    int rc = open_entry(stream, dtype, 0, n, d, p, q_local, workspace, w, st);
     if (rc) return rc;
     if (m < 1) return bad("m < 1");
     if (!theta || !workspace || !state || !grad_state) return bad("NULL pointer");
-    Ws w = carve(dtype, n, d, p, q_local, (void*)workspace);
-    hipStream_t st = (hipStream_t)stream;
-    return dtype == LCGP_F64 ? do_condition_grad_prepare<double>(st, w, theta, state, m, grad_state)
-                             : do_condition_grad_prepare<float>(st, w, theta, state, m, grad_state);
+    return by_dtype(dtype, [&](auto t) { return do_condition_grad_prepare<decltype(t)>(st, w, theta, state, m, grad_state); });
 }
 
 int lcgp_condition_grad_fetch(void* stream, int n, int q_local, int m, const void* grad_state, double* w, double* z) {
@@ -8746,42 +8813,14 @@ int lcgp_condition_predict_grad(void* stream, int dtype, int kernel_id, int n, i
                                 const void* sr, const double* theta, const void* workspace, const void* state, int m,
                                 const void* xn, const void* grad_state, int n0, const void* x0, void* scratch, size_t scratch_bytes,
                                 double* ghat, double* gvar, double* dghat, double* dgvar, int out_stride) {
-    int rc = check_common(dtype, n, d, p, q_local, kernel_id);
-    if (rc) return rc;
-    if (m < 1) return bad("m < 1");
-    if (n0 < 1) return bad("n0 < 1");
-    if (!x || !theta || !workspace || !state || !xn || !grad_state || !x0 || !scratch || !ghat || !gvar || !dghat || !dgvar)
-        return bad("NULL pointer");
-    if (out_stride != 0 && out_stride < n0) return bad("out_stride must be 0 (= n0) or >= n0");
-    if (scratch_bytes < cond_predict_scratch(dtype, n, q_local, m, n0))
-        return bad("scratch is smaller than lcgp_condition_predict_grad_scratch_bytes(dtype, n, q_local, m, n0)");
-    const int ldo = out_stride ? out_stride : n0;
-    Ws w = carve(dtype, n, d, p, q_local, (void*)workspace);
-    w.kern = kernel_id;
-    hipStream_t st = (hipStream_t)stream;
-    return dtype == LCGP_F64
-               ? do_condition_predict_grad<double>(st, w, x, sr, theta, state, m, xn, grad_state, n0, x0, scratch, ghat, gvar, dghat,
-                                                   dgvar, ldo)
-               : do_condition_predict_grad<float>(st, w, x, sr, theta, state, m, xn, grad_state, n0, x0, scratch, ghat, gvar, dghat,
-                                                  dgvar, ldo);
-}
-
-static int check_cond_rows(int dtype, int n, int d, int q_local, int m, int n0) {
-    if (dtype != LCGP_F64 && dtype != LCGP_F32) return bad("dtype must be 0 (f64) or 1 (f32)");
-    if (n < 1 || q_local < 1) return bad("n, q_local must be >= 1");
-    if (d < 1 || d > DWIDE) return bad("d must be in [1, 126]");
-    if (m < 1) return bad("m < 1");
-    if (n0 < 1) return bad("n0 < 1");
-    if ((long long)n0 * d > LCGP_HESS_MAX_ROWS) return bad("n0 * d must be <= LCGP_HESS_MAX_ROWS: pass the new inputs in chunks");
-    return 0;
+    const ViewArg v{state, m, xn, grad_state, scratch_bytes};
+    double* const o[6] = {ghat, gvar, dghat, dgvar};
+    return point_checked(PT_GRAD, stream, dtype, kernel_id, n, d, p, q_local, x, sr, theta, workspace, &v, n0, x0, 0, scratch, o,
+                         nullptr, out_stride);
 }
 
 int lcgp_condition_predict_hess_scratch_bytes(int dtype, int n, int d, int q_local, int m, int n0, size_t* bytes) {
-    int rc = check_cond_rows(dtype, n, d, q_local, m, n0);
-    if (rc) return rc;
-    if (!bytes) return bad("bytes is NULL");
-    *bytes = cond_predict_scratch(dtype, n, q_local, m, n0) + cond_rows_scratch(dtype, n, d, q_local, m, n0);
-    return 0;
+    return rows_bytes(true, dtype, n, d, q_local, &m, n0, bytes);
 }
 
 int lcgp_condition_predict_hess(void* stream, int dtype, int kernel_id, int n, int d, int p, int q_local, const void* x,
@@ -8789,70 +8828,36 @@ int lcgp_condition_predict_hess(void* stream, int dtype, int kernel_id, int n, i
                                 const void* xn, const void* grad_state, int n0, const void* x0, void* scratch, size_t scratch_bytes,
                                 double* ghat, double* gvar, double* dghat, double* dgvar, double* d2ghat, double* d2gvar,
                                 int out_stride) {
-    int rc = check_common(dtype, n, d, p, q_local, kernel_id);
-    if (rc) return rc;
-    rc = check_cond_rows(dtype, n, d, q_local, m, n0);
-    if (rc) return rc;
-    if (!x || !theta || !workspace || !state || !xn || !grad_state || !x0 || !scratch || !ghat || !gvar || !dghat || !dgvar ||
-        !d2ghat || !d2gvar)
-        return bad("NULL pointer");
-    if (out_stride != 0 && out_stride < n0) return bad("out_stride must be 0 (= n0) or >= n0");
-    if (scratch_bytes < cond_predict_scratch(dtype, n, q_local, m, n0) + cond_rows_scratch(dtype, n, d, q_local, m, n0))
-        return bad("scratch is smaller than lcgp_condition_predict_hess_scratch_bytes(dtype, n, d, q_local, m, n0)");
-    const int ldo = out_stride ? out_stride : n0;
-    Ws w = carve(dtype, n, d, p, q_local, (void*)workspace);
-    w.kern = kernel_id;
-    hipStream_t st = (hipStream_t)stream;
-    return dtype == LCGP_F64
-               ? do_condition_predict_hess<double>(st, w, x, sr, theta, state, m, xn, grad_state, n0, x0, scratch, ghat, gvar, dghat,
-                                                   dgvar, d2ghat, d2gvar, ldo)
-               : do_condition_predict_hess<float>(st, w, x, sr, theta, state, m, xn, grad_state, n0, x0, scratch, ghat, gvar, dghat,
-                                                  dgvar, d2ghat, d2gvar, ldo);
+    const ViewArg v{state, m, xn, grad_state, scratch_bytes};
+    double* const o[6] = {ghat, gvar, dghat, dgvar, d2ghat, d2gvar};
+    return point_checked(PT_HESS, stream, dtype, kernel_id, n, d, p, q_local, x, sr, theta, workspace, &v, n0, x0, 0, scratch, o,
+                         nullptr, out_stride);
 }
 
 int lcgp_condition_predict_gradcov_scratch_bytes(int dtype, int n, int d, int q_local, int m, int n0, size_t* bytes) {
-    int rc = check_cond_rows(dtype, n, d, q_local, m, n0);
-    if (rc) return rc;
-    if (!bytes) return bad("bytes is NULL");
-    *bytes = cond_rows_scratch(dtype, n, d, q_local, m, n0);
-    return 0;
+    return rows_bytes(false, dtype, n, d, q_local, &m, n0, bytes);
 }
 
 int lcgp_condition_predict_gradcov(void* stream, int dtype, int kernel_id, int n, int d, int p, int q_local, const void* x,
                                    const void* sr, const double* theta, const void* workspace, const void* state, int m,
                                    const void* xn, const void* grad_state, int n0, const void* x0, void* scratch,
                                    size_t scratch_bytes, double* dghat, double* gamma, const double* w, double* M, int out_stride) {
-    int rc = check_common(dtype, n, d, p, q_local, kernel_id);
-    if (rc) return rc;
-    rc = check_cond_rows(dtype, n, d, q_local, m, n0);
-    if (rc) return rc;
-    if (!x || !theta || !workspace || !state || !xn || !grad_state || !x0 || !scratch || !dghat) return bad("NULL pointer");
-    if (!gamma && !w) return bad("NULL pointer: gamma may only be NULL when w is given");
-    if ((w != nullptr) != (M != nullptr)) return bad("w and M go together: both or neither");
-    if (out_stride != 0 && out_stride < n0) return bad("out_stride must be 0 (= n0) or >= n0");
-    if (scratch_bytes < cond_rows_scratch(dtype, n, d, q_local, m, n0))
-        return bad("scratch is smaller than lcgp_condition_predict_gradcov_scratch_bytes(dtype, n, d, q_local, m, n0)");
-    const int ldo = out_stride ? out_stride : n0;
-    Ws ws = carve(dtype, n, d, p, q_local, (void*)workspace);
-    ws.kern = kernel_id;
-    hipStream_t st = (hipStream_t)stream;
-    return dtype == LCGP_F64
-               ? do_condition_predict_gradcov<double>(st, ws, x, sr, theta, state, m, xn, grad_state, n0, x0, scratch, dghat, gamma, w,
-                                                      M, ldo)
-               : do_condition_predict_gradcov<float>(st, ws, x, sr, theta, state, m, xn, grad_state, n0, x0, scratch, dghat, gamma, w,
-                                                     M, ldo);
+    const ViewArg v{state, m, xn, grad_state, scratch_bytes};
+    double* const o[6] = {dghat, gamma, M};
+    return point_checked(PT_GRADCOV, stream, dtype, kernel_id, n, d, p, q_local, x, sr, theta, workspace, &v, n0, x0, 0, scratch, o,
+                         w, out_stride);
 }
 
 int lcgp_loo(void* stream, int dtype, int n, int d, int p, int q_local, const void* sr, const double* theta,
              const void* workspace, double* ghat, double* gvar, int out_stride) {
-    int rc = check_common(dtype, n, d, p, q_local);
+    Ws w;
+    hipStream_t st;
+    int rc = open_entry(stream, dtype, 0, n, d, p, q_local, workspace, w, st);
     if (rc) return rc;
     if (!theta || !workspace || !ghat || !gvar) return bad("NULL pointer");
     if (out_stride != 0 && out_stride < n) return bad("out_stride must be 0 (= n) or >= n");
-    Ws w = carve(dtype, n, d, p, q_local, (void*)workspace);
-    hipStream_t st = (hipStream_t)stream;
     const int ldo = out_stride ? out_stride : n;
-    return dtype == LCGP_F64 ? do_loo<double>(st, w, sr, theta, ghat, gvar, ldo) : do_loo<float>(st, w, sr, theta, ghat, gvar, ldo);
+    return by_dtype(dtype, [&](auto t) { return do_loo<decltype(t)>(st, w, sr, theta, ghat, gvar, ldo); });
 }
 
 int lcgp_cv_workspace_bytes(int dtype, int n, int d, int p, int q_local, int F, const int* folds_host, size_t* bytes) {
@@ -8867,193 +8872,219 @@ int lcgp_cv_workspace_bytes(int dtype, int n, int d, int p, int q_local, int F, 
 
 int lcgp_cv_gather(void* stream, int dtype, int n, int d, int p, int q_local, const void* workspace, int F,
                    const int* folds_host, const int* folds, void* cv_workspace) {
-    int rc = check_common(dtype, n, d, p, q_local);
+    Ws w;
+    hipStream_t st;
+    int rc = open_entry(stream, dtype, 0, n, d, p, q_local, workspace, w, st);
     if (rc) return rc;
     int mmax = 0;
     if ((rc = check_folds(n, q_local, F, folds_host, &mmax))) return rc;
     if (!workspace || !folds || !cv_workspace) return bad("NULL pointer");
-    Ws w = carve(dtype, n, d, p, q_local, (void*)workspace);
-    Ws cw = carve(dtype, mmax, d, p, q_local * F, cv_workspace);
-    hipStream_t st = (hipStream_t)stream;
-    return dtype == LCGP_F64 ? do_cv_gather<double>(st, w, folds, F, cw) : do_cv_gather<float>(st, w, folds, F, cw);
+    const Ws cw = carve(dtype, mmax, d, p, q_local * F, cv_workspace);
+    return by_dtype(dtype, [&](auto t) { return do_cv_gather<decltype(t)>(st, w, folds, F, cw); });
 }
 
 int lcgp_cv_apply(void* stream, int dtype, int n, int d, int p, int q_local, const void* sr, const double* theta,
                   const void* workspace, int F, const int* folds_host, const int* folds, const void* cv_workspace,
                   double* ghat, double* gvar, int out_stride) {
-    int rc = check_common(dtype, n, d, p, q_local);
+    Ws w;
+    hipStream_t st;
+    int rc = open_entry(stream, dtype, 0, n, d, p, q_local, workspace, w, st);
     if (rc) return rc;
     int mmax = 0;
     if ((rc = check_folds(n, q_local, F, folds_host, &mmax))) return rc;
     if (!theta || !workspace || !folds || !cv_workspace || !ghat || !gvar) return bad("NULL pointer");
     if (out_stride != 0 && out_stride < n) return bad("out_stride must be 0 (= n) or >= n");
-    Ws w = carve(dtype, n, d, p, q_local, (void*)workspace);
-    Ws cw = carve(dtype, mmax, d, p, q_local * F, (void*)cv_workspace);
-    hipStream_t st = (hipStream_t)stream;
+    const Ws cw = carve(dtype, mmax, d, p, q_local * F, (void*)cv_workspace);
     const int ldo = out_stride ? out_stride : n;
-    return dtype == LCGP_F64 ? do_cv_apply<double>(st, w, sr, theta, folds, F, cw, ghat, gvar, ldo)
-                             : do_cv_apply<float>(st, w, sr, theta, folds, F, cw, ghat, gvar, ldo);
+    return by_dtype(dtype, [&](auto t) { return do_cv_apply<decltype(t)>(st, w, sr, theta, folds, F, cw, ghat, gvar, ldo); });
+}
+
+// ---- variance reduction, its gradient (grad: the entry of lcgp_variance_reduction_grad, which takes no match) and their twins
+// on a conditioned view (lcgp_hip.h: lcgp_condition_vr_*): the base model's code on widened rows (VrView) ----
+static size_t vr_need(bool grad, int dtype, int n, int d, int q_local, int mpad, int n_ref, int n_cand) {
+    return vr_carve(dtype, n, q_local, n_ref, n_cand, mpad).total +
+           (grad ? vrg_carve(dtype, n, d, q_local, n_ref, n_cand, mpad).total : 0);
+}
+
+// m: the view's new inputs, NULL on the fitted model; the candidates of one gradient call are rows of a launch grid
+static int vr_bytes(bool grad, int dtype, int n, int d, int q_local, const int* m, int n_ref, int n_cand, size_t* bytes) {
+    int rc = check_common(dtype, n, d, 1, q_local);
+    if (rc) return rc;
+    if (m && (rc = check_view(*m))) return rc;
+    if ((rc = check_vr(n_ref, n_cand))) return rc;
+    if (grad && n_cand > 65535 - 2 * TS) return bad("n_cand must be <= 65407 per call (pass the candidates in chunks)");
+    if (!bytes) return bad("bytes is NULL");
+    *bytes = vr_need(grad, dtype, n, d, q_local, m ? cov_pad(*m) : 0, n_ref, n_cand);
+    return 0;
+}
+
+static int vr_prepare_checked(void* stream, int dtype, int kernel_id, int n, int d, int p, int q_local, const void* x, const void* sr,
+                              const double* theta, const void* workspace, const ViewArg* v, int n_ref, const void* x_ref,
+                              void* scratch) {
+    Ws w;
+    hipStream_t st;
+    int rc = open_entry(stream, dtype, kernel_id, n, d, p, q_local, workspace, w, st);
+    if (rc) return rc;
+    if (v && (rc = check_view(v->m))) return rc;
+    if ((rc = check_vr(n_ref, 1))) return rc;
+    if (!x || !theta || !workspace || (v && (!v->state || !v->xn)) || !x_ref || !scratch) return bad("NULL pointer");
+    if (v && v->scratch_bytes < vr_need(false, dtype, n, d, q_local, cov_pad(v->m), n_ref, 1))
+        return bad("scratch is smaller than lcgp_condition_vr_scratch_bytes(dtype, n, q_local, m, n_ref, 1)");
+    VrView cv;
+    if (v) cv = view_of(dtype, n, q_local, *v);
+    return by_dtype(dtype, [&](auto t) {
+        return do_vr_prepare<decltype(t)>(st, w, x, sr, theta, n_ref, x_ref, (char*)scratch, v ? &cv : nullptr);
+    });
+}
+
+static int vr_checked(bool grad, void* stream, int dtype, int kernel_id, int n, int d, int p, int q_local, const void* x,
+                      const void* sr, const double* theta, const void* workspace, const ViewArg* v, int n_ref, const void* x_ref,
+                      const double* w_ref, int n_cand, const void* x_cand, const int* match_host, const int* match, int cand_row0,
+                      int r, void* scratch, double* out, int out_stride, double* dout) {
+    Ws w;
+    hipStream_t st;
+    int rc = open_entry(stream, dtype, kernel_id, n, d, p, q_local, workspace, w, st);
+    if (rc) return rc;
+    if (v && (rc = check_view(v->m))) return rc;
+    if ((rc = check_vr(n_ref, n_cand))) return rc;
+    if (grad && n_cand > 65535 - 2 * TS) return bad("n_cand must be <= 65407 per call (pass the candidates in chunks)");
+    if (r < 1) return bad("r must be >= 1");
+    if (cand_row0 < -1) return bad("cand_row0 must be -1 or a row of the reference set");
+    if (cand_row0 >= 0) {
+        if ((long long)cand_row0 + n_cand > n_ref) return bad("cand_row0 + n_cand must be <= n_ref");
+        if (x_cand || match_host || match)
+            return bad(grad ? "cand_row0 >= 0: x_cand must be NULL" : "cand_row0 >= 0: x_cand and match must be NULL");
+    } else if (!x_cand) {
+        return bad("NULL pointer");
+    }
+    if ((rc = check_match(n, n_cand, match_host, match))) return rc;
+    if (!x || !theta || !workspace || (v && (!v->state || !v->xn)) || !x_ref || !w_ref || !scratch || !out || (grad && !dout))
+        return bad("NULL pointer");
+    if (out_stride != 0 && out_stride < n_cand) return bad("out_stride must be 0 (= n_cand) or >= n_cand");
+    if (v && v->scratch_bytes < vr_need(grad, dtype, n, d, q_local, cov_pad(v->m), n_ref, n_cand))
+        return bad(grad ? "scratch is smaller than lcgp_condition_vr_grad_scratch_bytes(dtype, n, d, q_local, m, n_ref, n_cand)"
+                        : "scratch is smaller than lcgp_condition_vr_scratch_bytes(dtype, n, q_local, m, n_ref, n_cand)");
+    const int ldo = out_stride ? out_stride : n_cand;
+    VrView cv;
+    if (v) cv = view_of(dtype, n, q_local, *v);
+    const VrView* pcv = v ? &cv : nullptr;
+    return by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return grad ? do_vr_grad<T>(st, w, x, sr, theta, n_ref, x_ref, w_ref, n_cand, x_cand, cand_row0, r, (char*)scratch, out, ldo,
+                                    dout, pcv)
+                    : do_vr<T>(st, w, x, sr, theta, n_ref, x_ref, w_ref, n_cand, x_cand, match, cand_row0, r, (char*)scratch, out,
+                               ldo, pcv);
+    });
 }
 
 int lcgp_variance_reduction_scratch_bytes(int dtype, int n, int q_local, int n_ref, int n_cand, size_t* bytes) {
-    int rc = check_common(dtype, n, 1, 1, q_local);
-    if (rc) return rc;
-    if ((rc = check_vr(n_ref, n_cand))) return rc;
-    if (!bytes) return bad("bytes is NULL");
-    *bytes = vr_carve(dtype, n, q_local, n_ref, n_cand).total;
-    return 0;
+    return vr_bytes(false, dtype, n, 1, q_local, nullptr, n_ref, n_cand, bytes);
 }
 
 int lcgp_variance_reduction_prepare(void* stream, int dtype, int kernel_id, int n, int d, int p, int q_local, const void* x,
                                     const void* sr, const double* theta, const void* workspace, int n_ref, const void* x_ref,
                                     void* scratch) {
-    int rc = check_common(dtype, n, d, p, q_local, kernel_id);
-    if (rc) return rc;
-    if ((rc = check_vr(n_ref, 1))) return rc;
-    if (!x || !theta || !workspace || !x_ref || !scratch) return bad("NULL pointer");
-    Ws w = carve(dtype, n, d, p, q_local, (void*)workspace);
-    w.kern = kernel_id;
-    hipStream_t st = (hipStream_t)stream;
-    return dtype == LCGP_F64 ? do_vr_prepare<double>(st, w, x, sr, theta, n_ref, x_ref, (char*)scratch)
-                             : do_vr_prepare<float>(st, w, x, sr, theta, n_ref, x_ref, (char*)scratch);
+    return vr_prepare_checked(stream, dtype, kernel_id, n, d, p, q_local, x, sr, theta, workspace, nullptr, n_ref, x_ref, scratch);
 }
 
 int lcgp_variance_reduction(void* stream, int dtype, int kernel_id, int n, int d, int p, int q_local, const void* x, const void* sr,
                             const double* theta, const void* workspace, int n_ref, const void* x_ref, const double* w_ref,
                             int n_cand, const void* x_cand, const int* match_host, const int* match, int cand_row0, int r,
                             void* scratch, double* out, int out_stride) {
-    int rc = check_common(dtype, n, d, p, q_local, kernel_id);
-    if (rc) return rc;
-    if ((rc = check_vr(n_ref, n_cand))) return rc;
-    if (r < 1) return bad("r must be >= 1");
-    if (cand_row0 < -1) return bad("cand_row0 must be -1 or a row of the reference set");
-    if (cand_row0 >= 0) {
-        if ((long long)cand_row0 + n_cand > n_ref) return bad("cand_row0 + n_cand must be <= n_ref");
-        if (x_cand || match_host || match) return bad("cand_row0 >= 0: x_cand and match must be NULL");
-    } else if (!x_cand) {
-        return bad("NULL pointer");
-    }
-    if ((match_host == nullptr) != (match == nullptr)) return bad("match_host and match must both be NULL or both be given");
-    if (match_host)
-        for (int i = 0; i < n_cand; ++i)
-            if (match_host[i] < -1 || match_host[i] >= n) return bad("match must be -1 or a training index in [0, n)");
-    if (!x || !theta || !workspace || !x_ref || !w_ref || !scratch || !out) return bad("NULL pointer");
-    if (out_stride != 0 && out_stride < n_cand) return bad("out_stride must be 0 (= n_cand) or >= n_cand");
-    const int ldo = out_stride ? out_stride : n_cand;
-    Ws w = carve(dtype, n, d, p, q_local, (void*)workspace);
-    w.kern = kernel_id;
-    hipStream_t st = (hipStream_t)stream;
-    return dtype == LCGP_F64 ? do_vr<double>(st, w, x, sr, theta, n_ref, x_ref, w_ref, n_cand, x_cand, match, cand_row0, r,
-                                             (char*)scratch, out, ldo)
-                             : do_vr<float>(st, w, x, sr, theta, n_ref, x_ref, w_ref, n_cand, x_cand, match, cand_row0, r,
-                                            (char*)scratch, out, ldo);
-}
-
-// the candidates of one call are rows of a launch grid
-static int check_vr_grad(int n_cand) {
-    if (n_cand > 65535 - 2 * TS) return bad("n_cand must be <= 65407 per call (pass the candidates in chunks)");
-    return 0;
+    return vr_checked(false, stream, dtype, kernel_id, n, d, p, q_local, x, sr, theta, workspace, nullptr, n_ref, x_ref, w_ref, n_cand,
+                      x_cand, match_host, match, cand_row0, r, scratch, out, out_stride, nullptr);
 }
 
 int lcgp_variance_reduction_grad_scratch_bytes(int dtype, int n, int d, int q_local, int n_ref, int n_cand, size_t* bytes) {
-    int rc = check_common(dtype, n, d, 1, q_local);
-    if (rc) return rc;
-    if ((rc = check_vr(n_ref, n_cand))) return rc;
-    if ((rc = check_vr_grad(n_cand))) return rc;
-    if (!bytes) return bad("bytes is NULL");
-    *bytes = vr_carve(dtype, n, q_local, n_ref, n_cand).total + vrg_carve(dtype, n, d, q_local, n_ref, n_cand).total;
-    return 0;
+    return vr_bytes(true, dtype, n, d, q_local, nullptr, n_ref, n_cand, bytes);
 }
 
 int lcgp_variance_reduction_grad(void* stream, int dtype, int kernel_id, int n, int d, int p, int q_local, const void* x,
                                  const void* sr, const double* theta, const void* workspace, int n_ref, const void* x_ref,
                                  const double* w_ref, int n_cand, const void* x_cand, int cand_row0, int r, void* scratch,
                                  double* out, int out_stride, double* dout) {
-    int rc = check_common(dtype, n, d, p, q_local, kernel_id);
-    if (rc) return rc;
-    if ((rc = check_vr(n_ref, n_cand))) return rc;
-    if ((rc = check_vr_grad(n_cand))) return rc;
-    if (r < 1) return bad("r must be >= 1");
-    if (cand_row0 < -1) return bad("cand_row0 must be -1 or a row of the reference set");
-    if (cand_row0 >= 0) {
-        if ((long long)cand_row0 + n_cand > n_ref) return bad("cand_row0 + n_cand must be <= n_ref");
-        if (x_cand) return bad("cand_row0 >= 0: x_cand must be NULL");
-    } else if (!x_cand) {
-        return bad("NULL pointer");
-    }
-    if (!x || !theta || !workspace || !x_ref || !w_ref || !scratch || !out || !dout) return bad("NULL pointer");
-    if (out_stride != 0 && out_stride < n_cand) return bad("out_stride must be 0 (= n_cand) or >= n_cand");
-    const int ldo = out_stride ? out_stride : n_cand;
-    Ws w = carve(dtype, n, d, p, q_local, (void*)workspace);
-    w.kern = kernel_id;
-    hipStream_t st = (hipStream_t)stream;
-    return dtype == LCGP_F64 ? do_vr_grad<double>(st, w, x, sr, theta, n_ref, x_ref, w_ref, n_cand, x_cand, cand_row0, r,
-                                                  (char*)scratch, out, ldo, dout)
-                             : do_vr_grad<float>(st, w, x, sr, theta, n_ref, x_ref, w_ref, n_cand, x_cand, cand_row0, r,
-                                                 (char*)scratch, out, ldo, dout);
+    return vr_checked(true, stream, dtype, kernel_id, n, d, p, q_local, x, sr, theta, workspace, nullptr, n_ref, x_ref, w_ref, n_cand,
+                      x_cand, nullptr, nullptr, cand_row0, r, scratch, out, out_stride, dout);
 }
 
-int lcgp_select_scratch_bytes(int dtype, int n, int d, int q_local, int n_ref, int n_cand, int size, size_t* bytes) {
-    int rc = check_common(dtype, n, d, 1, q_local);
+// ---- greedy selection and its twins on a conditioned view (lcgp_hip.h: lcgp_select_* / lcgp_condition_select_*) ----
+// What the five entries test first, on the fitted model (m == NULL) and on a view of *m new inputs; *L receives the layout.  A view
+// entry is told the size of its scratch and tests it here, so its scratch pointer too; the model entries test theirs with their
+// other pointers, behind their own arguments.
+static int open_sel(int dtype, int n, int d, int p, int q_local, int kernel_id, const int* m, int n_ref, int n_cand, int size,
+                    const void* scratch, size_t scratch_bytes, SelLay* L) {
+    int rc = check_common(dtype, n, d, p, q_local, kernel_id);
     if (rc) return rc;
+    if (m && (rc = check_view(*m))) return rc;
     if ((rc = check_sel(n_ref, n_cand, size))) return rc;
-    if (!bytes) return bad("bytes is NULL");
-    *bytes = sel_carve(dtype, n, d, q_local, n_ref, n_cand, size).total;
+    if (m && !scratch) return bad("NULL pointer");
+    *L = sel_carve(dtype, n, d, q_local, n_ref, n_cand, size, m ? cov_pad(*m) : 0);
+    if (m && scratch_bytes < L->total)
+        return bad("scratch is smaller than lcgp_condition_select_scratch_bytes(dtype, n, d, q_local, m, n_ref, n_cand, size)");
     return 0;
 }
 
-int lcgp_select_begin(void* stream, int dtype, int kernel_id, int n, int d, int p, int q_local, const void* x, const void* sr,
-                      const double* theta, const void* workspace, int n_ref, const void* x_ref, const double* w_ref, int n_cand,
-                      const void* x_cand, const int* match_host, const int* match, int r, int size, int pass_rows, void* scratch) {
-    int rc = check_common(dtype, n, d, p, q_local, kernel_id);
-    if (rc) return rc;
-    if ((rc = check_sel(n_ref, n_cand, size))) return rc;
-    if (r < 1) return bad("r must be >= 1");
-    if (pass_rows < 1 || pass_rows > VR_XBLK) return bad("pass_rows must be in [1, 2048]");
-    if ((match_host == nullptr) != (match == nullptr)) return bad("match_host and match must both be NULL or both be given");
-    if (match_host)
-        for (int i = 0; i < n_cand; ++i)
-            if (match_host[i] < -1 || match_host[i] >= n) return bad("match must be -1 or a training index in [0, n)");
-    if (!x || !theta || !workspace || !x_ref || !w_ref || !x_cand || !scratch) return bad("NULL pointer");
-    Ws w = carve(dtype, n, d, p, q_local, (void*)workspace);
-    w.kern = kernel_id;
-    hipStream_t st = (hipStream_t)stream;
-    return dtype == LCGP_F64 ? do_sel_begin<double>(st, w, x, sr, theta, n_ref, x_ref, w_ref, n_cand, x_cand, match, r, size,
-                                                    pass_rows, (char*)scratch)
-                             : do_sel_begin<float>(st, w, x, sr, theta, n_ref, x_ref, w_ref, n_cand, x_cand, match, r, size,
-                                                   pass_rows, (char*)scratch);
-}
-
-int lcgp_select_score(void* stream, int dtype, int n, int d, int q_local, int n_ref, int n_cand, int size, int step,
-                      const double* omega, void* scratch, double* out) {
+static int sel_bytes(int dtype, int n, int d, int q_local, const int* m, int n_ref, int n_cand, int size, size_t* bytes) {
     int rc = check_common(dtype, n, d, 1, q_local);
     if (rc) return rc;
+    if (m && (rc = check_view(*m))) return rc;
     if ((rc = check_sel(n_ref, n_cand, size))) return rc;
+    if (!bytes) return bad("bytes is NULL");
+    *bytes = sel_carve(dtype, n, d, q_local, n_ref, n_cand, size, m ? cov_pad(*m) : 0).total;
+    return 0;
+}
+
+static int sel_begin(void* stream, int dtype, int kernel_id, int n, int d, int p, int q_local, const void* x, const void* sr,
+                     const double* theta, const void* workspace, const ViewArg* v, int n_ref, const void* x_ref, const double* w_ref,
+                     int n_cand, const void* x_cand, const int* match_host, const int* match, int r, int size, int pass_rows,
+                     void* scratch) {
+    SelLay L;
+    int rc = open_sel(dtype, n, d, p, q_local, kernel_id, v ? &v->m : nullptr, n_ref, n_cand, size, scratch, v ? v->scratch_bytes : 0, &L);
+    if (rc) return rc;
+    if (r < 1) return bad("r must be >= 1");
+    if (pass_rows < 1 || pass_rows > VR_XBLK) return bad("pass_rows must be in [1, 2048]");
+    if ((rc = check_match(n, n_cand, match_host, match))) return rc;
+    if (!x || !theta || !workspace || (v && (!v->state || !v->xn)) || !x_ref || !w_ref || !x_cand || !scratch)
+        return bad("NULL pointer");
+    Ws w = carve(dtype, n, d, p, q_local, (void*)workspace);
+    w.kern = kernel_id;
+    VrView cv;
+    if (v) cv = view_of(dtype, n, q_local, *v);
+    return by_dtype(dtype, [&](auto t) {
+        return do_sel_begin<decltype(t)>((hipStream_t)stream, w, x, sr, theta, n_ref, x_ref, w_ref, n_cand, x_cand, match, r, size,
+                                         pass_rows, (char*)scratch, v ? &cv : nullptr);
+    });
+}
+
+static int sel_score(void* stream, int dtype, int n, int d, int q_local, const int* m, int n_ref, int n_cand, int size, int step,
+                     const double* omega, void* scratch, size_t scratch_bytes, double* out) {
+    SelLay L;
+    int rc = open_sel(dtype, n, d, 1, q_local, 0, m, n_ref, n_cand, size, scratch, scratch_bytes, &L);
+    if (rc) return rc;
     if (step < 0 || step >= size) return bad("step must be in [0, size)");
     if (!omega || !scratch) return bad("NULL pointer");
-    const SelLay L = sel_carve(dtype, n, d, q_local, n_ref, n_cand, size);
     char* sc = (char*)scratch;
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(sel_score_kernel, dim3(1), dim3(1024), 0, st, (const double*)(sc + L.off_R), q_local, n_cand, omega,
-                       (const int*)(sc + L.off_mask), out, (int*)(sc + L.off_picks) + step);
+    hipLaunchKernelGGL(sel_score_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, (const double*)(sc + L.off_R), q_local, n_cand,
+                       omega, (const int*)(sc + L.off_mask), out, (int*)(sc + L.off_picks) + step);
     CHECK_LAUNCH("sel_score_kernel");
     return 0;
 }
 
-int lcgp_select_picks(int dtype, int n, int d, int q_local, int n_ref, int n_cand, int size, void* scratch, int** picks) {
-    int rc = check_common(dtype, n, d, 1, q_local);
+static int sel_picks(int dtype, int n, int d, int q_local, const int* m, int n_ref, int n_cand, int size, void* scratch,
+                     size_t scratch_bytes, int** picks) {
+    SelLay L;
+    int rc = open_sel(dtype, n, d, 1, q_local, 0, m, n_ref, n_cand, size, scratch, scratch_bytes, &L);
     if (rc) return rc;
-    if ((rc = check_sel(n_ref, n_cand, size))) return rc;
     if (!scratch || !picks) return bad("NULL pointer");
-    *picks = (int*)((char*)scratch + sel_carve(dtype, n, d, q_local, n_ref, n_cand, size).off_picks);
+    *picks = (int*)((char*)scratch + L.off_picks);
     return 0;
 }
 
-int lcgp_select_condition(void* stream, int dtype, int kernel_id, int n, int d, int p, int q_local, const double* theta,
-                          int n_ref, int n_cand, int size, int r, int step, const int* pick, void* scratch) {
-    int rc = check_common(dtype, n, d, p, q_local, kernel_id);
+static int sel_condition(void* stream, int dtype, int kernel_id, int n, int d, int p, int q_local, const double* theta, const int* m,
+                         int n_ref, int n_cand, int size, int r, int step, const int* pick, void* scratch, size_t scratch_bytes) {
+    SelLay L;
+    int rc = open_sel(dtype, n, d, p, q_local, kernel_id, m, n_ref, n_cand, size, scratch, scratch_bytes, &L);
     if (rc) return rc;
-    if ((rc = check_sel(n_ref, n_cand, size))) return rc;
     if (r < 1) return bad("r must be >= 1");
     if (step < 0 || step >= size) return bad("step must be in [0, size)");
     if (!theta || !pick || !scratch) return bad("NULL pointer");
@@ -9061,146 +9092,85 @@ int lcgp_select_condition(void* stream, int dtype, int kernel_id, int n, int d, 
     memset(&w, 0, sizeof(w));
     w.n = n; w.npad = round_up(n, 2 * TS); w.d = d; w.p = p; w.q = q_local; w.kern = kernel_id;
     w.esz = dtype == LCGP_F64 ? 8 : 4;
-    hipStream_t st = (hipStream_t)stream;
-    return dtype == LCGP_F64 ? do_sel_condition<double>(st, w, theta, n_ref, n_cand, size, r, step, pick, (char*)scratch)
-                             : do_sel_condition<float>(st, w, theta, n_ref, n_cand, size, r, step, pick, (char*)scratch);
+    return by_dtype(dtype, [&](auto t) {
+        return do_sel_condition<decltype(t)>((hipStream_t)stream, w, theta, n_ref, n_cand, size, r, step, pick, (char*)scratch,
+                                             m ? cov_pad(*m) : 0);
+    });
 }
 
-int lcgp_select_state(void* stream, int dtype, int n, int d, int q_local, int n_ref, int n_cand, int size, int which,
-                      const void* scratch, double* out) {
-    int rc = check_common(dtype, n, d, 1, q_local);
+static int sel_state(void* stream, int dtype, int n, int d, int q_local, const int* m, int n_ref, int n_cand, int size, int which,
+                     const void* scratch, size_t scratch_bytes, double* out) {
+    SelLay L;
+    int rc = open_sel(dtype, n, d, 1, q_local, 0, m, n_ref, n_cand, size, scratch, scratch_bytes, &L);
     if (rc) return rc;
-    if ((rc = check_sel(n_ref, n_cand, size))) return rc;
     if (which != 0 && which != 1) return bad("which must be 0 (R) or 1 (h)");
     if (!scratch || !out) return bad("NULL pointer");
-    const SelLay L = sel_carve(dtype, n, d, q_local, n_ref, n_cand, size);
     hipError_t e = hipMemcpyAsync(out, (const char*)scratch + (which ? L.off_h : L.off_R), (size_t)q_local * n_cand * sizeof(double),
                                   hipMemcpyDeviceToDevice, (hipStream_t)stream);
     return e == hipSuccess ? 0 : fail("hipMemcpyAsync", e);
 }
 
-// ---- variance reduction and greedy selection on a conditioned view (lcgp_hip.h: lcgp_condition_vr_* / lcgp_condition_select_*) ----
-// the base model's code on widened rows (VrView); every entry checks its arguments and scratch_bytes before anything is enqueued
-static int check_view(int m) {
-    if (m < 1) return bad("m < 1");
-    return 0;
+int lcgp_select_scratch_bytes(int dtype, int n, int d, int q_local, int n_ref, int n_cand, int size, size_t* bytes) {
+    return sel_bytes(dtype, n, d, q_local, nullptr, n_ref, n_cand, size, bytes);
 }
 
-static VrView view_of(int dtype, int n, int q_local, const void* state, int m, const void* xn) {
-    const CondLay L = cond_carve(dtype, n, q_local, m);
-    VrView v;
-    v.Un = (const char*)state + L.off_U; v.Wi = (const char*)state + L.off_W; v.xn = xn;
-    v.m = m; v.mpad = L.mpad;
-    return v;
+int lcgp_select_begin(void* stream, int dtype, int kernel_id, int n, int d, int p, int q_local, const void* x, const void* sr,
+                      const double* theta, const void* workspace, int n_ref, const void* x_ref, const double* w_ref, int n_cand,
+                      const void* x_cand, const int* match_host, const int* match, int r, int size, int pass_rows, void* scratch) {
+    return sel_begin(stream, dtype, kernel_id, n, d, p, q_local, x, sr, theta, workspace, nullptr, n_ref, x_ref, w_ref, n_cand, x_cand,
+                     match_host, match, r, size, pass_rows, scratch);
+}
+
+int lcgp_select_score(void* stream, int dtype, int n, int d, int q_local, int n_ref, int n_cand, int size, int step,
+                      const double* omega, void* scratch, double* out) {
+    return sel_score(stream, dtype, n, d, q_local, nullptr, n_ref, n_cand, size, step, omega, scratch, 0, out);
+}
+
+int lcgp_select_picks(int dtype, int n, int d, int q_local, int n_ref, int n_cand, int size, void* scratch, int** picks) {
+    return sel_picks(dtype, n, d, q_local, nullptr, n_ref, n_cand, size, scratch, 0, picks);
+}
+
+int lcgp_select_condition(void* stream, int dtype, int kernel_id, int n, int d, int p, int q_local, const double* theta,
+                          int n_ref, int n_cand, int size, int r, int step, const int* pick, void* scratch) {
+    return sel_condition(stream, dtype, kernel_id, n, d, p, q_local, theta, nullptr, n_ref, n_cand, size, r, step, pick, scratch, 0);
+}
+
+int lcgp_select_state(void* stream, int dtype, int n, int d, int q_local, int n_ref, int n_cand, int size, int which,
+                      const void* scratch, double* out) {
+    return sel_state(stream, dtype, n, d, q_local, nullptr, n_ref, n_cand, size, which, scratch, 0, out);
 }
 
 int lcgp_condition_vr_scratch_bytes(int dtype, int n, int q_local, int m, int n_ref, int n_cand, size_t* bytes) {
-    int rc = check_common(dtype, n, 1, 1, q_local);
-    if (rc) return rc;
-    if ((rc = check_view(m))) return rc;
-    if ((rc = check_vr(n_ref, n_cand))) return rc;
-    if (!bytes) return bad("bytes is NULL");
-    *bytes = vr_carve(dtype, n, q_local, n_ref, n_cand, cov_pad(m)).total;
-    return 0;
+    return vr_bytes(false, dtype, n, 1, q_local, &m, n_ref, n_cand, bytes);
 }
 
 int lcgp_condition_vr_prepare(void* stream, int dtype, int kernel_id, int n, int d, int p, int q_local, const void* x, const void* sr,
                               const double* theta, const void* workspace, const void* state, int m, const void* xn, int n_ref,
                               const void* x_ref, void* scratch, size_t scratch_bytes) {
-    int rc = check_common(dtype, n, d, p, q_local, kernel_id);
-    if (rc) return rc;
-    if ((rc = check_view(m))) return rc;
-    if ((rc = check_vr(n_ref, 1))) return rc;
-    if (!x || !theta || !workspace || !state || !xn || !x_ref || !scratch) return bad("NULL pointer");
-    if (scratch_bytes < vr_carve(dtype, n, q_local, n_ref, 1, cov_pad(m)).total)
-        return bad("scratch is smaller than lcgp_condition_vr_scratch_bytes(dtype, n, q_local, m, n_ref, 1)");
-    Ws w = carve(dtype, n, d, p, q_local, (void*)workspace);
-    w.kern = kernel_id;
-    const VrView cv = view_of(dtype, n, q_local, state, m, xn);
-    hipStream_t st = (hipStream_t)stream;
-    return dtype == LCGP_F64 ? do_vr_prepare<double>(st, w, x, sr, theta, n_ref, x_ref, (char*)scratch, &cv)
-                             : do_vr_prepare<float>(st, w, x, sr, theta, n_ref, x_ref, (char*)scratch, &cv);
+    const ViewArg v{state, m, xn, nullptr, scratch_bytes};
+    return vr_prepare_checked(stream, dtype, kernel_id, n, d, p, q_local, x, sr, theta, workspace, &v, n_ref, x_ref, scratch);
 }
 
 int lcgp_condition_vr(void* stream, int dtype, int kernel_id, int n, int d, int p, int q_local, const void* x, const void* sr,
                       const double* theta, const void* workspace, const void* state, int m, const void* xn, int n_ref,
                       const void* x_ref, const double* w_ref, int n_cand, const void* x_cand, const int* match_host, const int* match,
                       int cand_row0, int r, void* scratch, size_t scratch_bytes, double* out, int out_stride) {
-    int rc = check_common(dtype, n, d, p, q_local, kernel_id);
-    if (rc) return rc;
-    if ((rc = check_view(m))) return rc;
-    if ((rc = check_vr(n_ref, n_cand))) return rc;
-    if (r < 1) return bad("r must be >= 1");
-    if (cand_row0 < -1) return bad("cand_row0 must be -1 or a row of the reference set");
-    if (cand_row0 >= 0) {
-        if ((long long)cand_row0 + n_cand > n_ref) return bad("cand_row0 + n_cand must be <= n_ref");
-        if (x_cand || match_host || match) return bad("cand_row0 >= 0: x_cand and match must be NULL");
-    } else if (!x_cand) {
-        return bad("NULL pointer");
-    }
-    if ((match_host == nullptr) != (match == nullptr)) return bad("match_host and match must both be NULL or both be given");
-    if (match_host)
-        for (int i = 0; i < n_cand; ++i)
-            if (match_host[i] < -1 || match_host[i] >= n) return bad("match must be -1 or a training index in [0, n)");
-    if (!x || !theta || !workspace || !state || !xn || !x_ref || !w_ref || !scratch || !out) return bad("NULL pointer");
-    if (out_stride != 0 && out_stride < n_cand) return bad("out_stride must be 0 (= n_cand) or >= n_cand");
-    if (scratch_bytes < vr_carve(dtype, n, q_local, n_ref, n_cand, cov_pad(m)).total)
-        return bad("scratch is smaller than lcgp_condition_vr_scratch_bytes(dtype, n, q_local, m, n_ref, n_cand)");
-    const int ldo = out_stride ? out_stride : n_cand;
-    Ws w = carve(dtype, n, d, p, q_local, (void*)workspace);
-    w.kern = kernel_id;
-    const VrView cv = view_of(dtype, n, q_local, state, m, xn);
-    hipStream_t st = (hipStream_t)stream;
-    return dtype == LCGP_F64 ? do_vr<double>(st, w, x, sr, theta, n_ref, x_ref, w_ref, n_cand, x_cand, match, cand_row0, r,
-                                             (char*)scratch, out, ldo, &cv)
-                             : do_vr<float>(st, w, x, sr, theta, n_ref, x_ref, w_ref, n_cand, x_cand, match, cand_row0, r,
-                                            (char*)scratch, out, ldo, &cv);
+    const ViewArg v{state, m, xn, nullptr, scratch_bytes};
+    return vr_checked(false, stream, dtype, kernel_id, n, d, p, q_local, x, sr, theta, workspace, &v, n_ref, x_ref, w_ref, n_cand,
+                      x_cand, match_host, match, cand_row0, r, scratch, out, out_stride, nullptr);
 }
 
-// ---- gradient of the variance reduction on a conditioned view (lcgp_hip.h: lcgp_condition_vr_grad) ----
 int lcgp_condition_vr_grad_scratch_bytes(int dtype, int n, int d, int q_local, int m, int n_ref, int n_cand, size_t* bytes) {
-    int rc = check_common(dtype, n, d, 1, q_local);
-    if (rc) return rc;
-    if ((rc = check_view(m))) return rc;
-    if ((rc = check_vr(n_ref, n_cand))) return rc;
-    if ((rc = check_vr_grad(n_cand))) return rc;
-    if (!bytes) return bad("bytes is NULL");
-    const int mpad = cov_pad(m);
-    *bytes = vr_carve(dtype, n, q_local, n_ref, n_cand, mpad).total + vrg_carve(dtype, n, d, q_local, n_ref, n_cand, mpad).total;
-    return 0;
+    return vr_bytes(true, dtype, n, d, q_local, &m, n_ref, n_cand, bytes);
 }
 
 int lcgp_condition_vr_grad(void* stream, int dtype, int kernel_id, int n, int d, int p, int q_local, const void* x, const void* sr,
                            const double* theta, const void* workspace, const void* state, int m, const void* xn, int n_ref,
                            const void* x_ref, const double* w_ref, int n_cand, const void* x_cand, int cand_row0, int r,
                            void* scratch, size_t scratch_bytes, double* out, int out_stride, double* dout) {
-    int rc = check_common(dtype, n, d, p, q_local, kernel_id);
-    if (rc) return rc;
-    if ((rc = check_view(m))) return rc;
-    if ((rc = check_vr(n_ref, n_cand))) return rc;
-    if ((rc = check_vr_grad(n_cand))) return rc;
-    if (r < 1) return bad("r must be >= 1");
-    if (cand_row0 < -1) return bad("cand_row0 must be -1 or a row of the reference set");
-    if (cand_row0 >= 0) {
-        if ((long long)cand_row0 + n_cand > n_ref) return bad("cand_row0 + n_cand must be <= n_ref");
-        if (x_cand) return bad("cand_row0 >= 0: x_cand must be NULL");
-    } else if (!x_cand) {
-        return bad("NULL pointer");
-    }
-    if (!x || !theta || !workspace || !state || !xn || !x_ref || !w_ref || !scratch || !out || !dout) return bad("NULL pointer");
-    if (out_stride != 0 && out_stride < n_cand) return bad("out_stride must be 0 (= n_cand) or >= n_cand");
-    const int mpad = cov_pad(m);
-    if (scratch_bytes < vr_carve(dtype, n, q_local, n_ref, n_cand, mpad).total + vrg_carve(dtype, n, d, q_local, n_ref, n_cand, mpad).total)
-        return bad("scratch is smaller than lcgp_condition_vr_grad_scratch_bytes(dtype, n, d, q_local, m, n_ref, n_cand)");
-    const int ldo = out_stride ? out_stride : n_cand;
-    Ws w = carve(dtype, n, d, p, q_local, (void*)workspace);
-    w.kern = kernel_id;
-    const VrView cv = view_of(dtype, n, q_local, state, m, xn);
-    hipStream_t st = (hipStream_t)stream;
-    return dtype == LCGP_F64 ? do_vr_grad<double>(st, w, x, sr, theta, n_ref, x_ref, w_ref, n_cand, x_cand, cand_row0, r,
-                                                  (char*)scratch, out, ldo, dout, &cv)
-                             : do_vr_grad<float>(st, w, x, sr, theta, n_ref, x_ref, w_ref, n_cand, x_cand, cand_row0, r,
-                                                 (char*)scratch, out, ldo, dout, &cv);
+    const ViewArg v{state, m, xn, nullptr, scratch_bytes};
+    return vr_checked(true, stream, dtype, kernel_id, n, d, p, q_local, x, sr, theta, workspace, &v, n_ref, x_ref, w_ref, n_cand,
+                      x_cand, nullptr, nullptr, cand_row0, r, scratch, out, out_stride, dout);
 }
 
 // ---- joint posterior covariance of a conditioned view (lcgp_hip.h) ----
@@ -9217,45 +9187,13 @@ int lcgp_condition_predict_cov_scratch_bytes(int dtype, int n, int q_local, int 
 int lcgp_condition_predict_cov(void* stream, int dtype, int kernel_id, int n, int d, int p, int q_local, const void* x,
                                const void* sr, const double* theta, const void* workspace, const void* state, int m, const void* xn,
                                int n0, const void* x0, void* scratch, size_t scratch_bytes, void* cov_workspace, double jitter) {
-    int rc = check_common(dtype, n, d, p, q_local, kernel_id);
-    if (rc) return rc;
-    if ((rc = check_view(m))) return rc;
-    if (n0 < 1) return bad("n0 < 1");
-    if (!(jitter >= 0.0) || !__builtin_isfinite(jitter)) return bad("jitter must be finite and >= 0");
-    if (!x || !theta || !workspace || !state || !xn || !x0 || !scratch || !cov_workspace) return bad("NULL pointer");
-    if (scratch_bytes < cond_cov_carve(dtype, n, q_local, m, n0).total)
-        return bad("scratch is smaller than lcgp_condition_predict_cov_scratch_bytes(dtype, n, q_local, m, n0)");
-    Ws w = carve(dtype, n, d, p, q_local, (void*)workspace);
-    w.kern = kernel_id;
-    Ws cw = carve(dtype, n0, d, p, q_local, cov_workspace);
-    const VrView cv = view_of(dtype, n, q_local, state, m, xn);
-    hipStream_t st = (hipStream_t)stream;
-    return dtype == LCGP_F64 ? do_condition_predict_cov<double>(st, w, x, sr, theta, cv, n0, x0, (char*)scratch, cw, jitter)
-                             : do_condition_predict_cov<float>(st, w, x, sr, theta, cv, n0, x0, (char*)scratch, cw, jitter);
-}
-
-// the checks the five selection entries on a view share; *L receives the layout
-static int check_view_sel(int dtype, int n, int d, int p, int q_local, int kernel_id, int m, int n_ref, int n_cand, int size,
-                          const void* scratch, size_t scratch_bytes, SelLay* L) {
-    int rc = check_common(dtype, n, d, p, q_local, kernel_id);
-    if (rc) return rc;
-    if ((rc = check_view(m))) return rc;
-    if ((rc = check_sel(n_ref, n_cand, size))) return rc;
-    if (!scratch) return bad("NULL pointer");
-    *L = sel_carve(dtype, n, d, q_local, n_ref, n_cand, size, cov_pad(m));
-    if (scratch_bytes < L->total)
-        return bad("scratch is smaller than lcgp_condition_select_scratch_bytes(dtype, n, d, q_local, m, n_ref, n_cand, size)");
-    return 0;
+    const ViewArg v{state, m, xn, nullptr, scratch_bytes};
+    return cov_checked(stream, dtype, kernel_id, n, d, p, q_local, x, sr, theta, workspace, &v, n0, x0, 0, scratch, cov_workspace,
+                       jitter);
 }
 
 int lcgp_condition_select_scratch_bytes(int dtype, int n, int d, int q_local, int m, int n_ref, int n_cand, int size, size_t* bytes) {
-    int rc = check_common(dtype, n, d, 1, q_local);
-    if (rc) return rc;
-    if ((rc = check_view(m))) return rc;
-    if ((rc = check_sel(n_ref, n_cand, size))) return rc;
-    if (!bytes) return bad("bytes is NULL");
-    *bytes = sel_carve(dtype, n, d, q_local, n_ref, n_cand, size, cov_pad(m)).total;
-    return 0;
+    return sel_bytes(dtype, n, d, q_local, &m, n_ref, n_cand, size, bytes);
 }
 
 int lcgp_condition_select_begin(void* stream, int dtype, int kernel_id, int n, int d, int p, int q_local, const void* x,
@@ -9263,79 +9201,31 @@ int lcgp_condition_select_begin(void* stream, int dtype, int kernel_id, int n, i
                                 int n_ref, const void* x_ref, const double* w_ref, int n_cand, const void* x_cand,
                                 const int* match_host, const int* match, int r, int size, int pass_rows, void* scratch,
                                 size_t scratch_bytes) {
-    SelLay L;
-    int rc = check_view_sel(dtype, n, d, p, q_local, kernel_id, m, n_ref, n_cand, size, scratch, scratch_bytes, &L);
-    if (rc) return rc;
-    if (r < 1) return bad("r must be >= 1");
-    if (pass_rows < 1 || pass_rows > VR_XBLK) return bad("pass_rows must be in [1, 2048]");
-    if ((match_host == nullptr) != (match == nullptr)) return bad("match_host and match must both be NULL or both be given");
-    if (match_host)
-        for (int i = 0; i < n_cand; ++i)
-            if (match_host[i] < -1 || match_host[i] >= n) return bad("match must be -1 or a training index in [0, n)");
-    if (!x || !theta || !workspace || !state || !xn || !x_ref || !w_ref || !x_cand) return bad("NULL pointer");
-    Ws w = carve(dtype, n, d, p, q_local, (void*)workspace);
-    w.kern = kernel_id;
-    const VrView cv = view_of(dtype, n, q_local, state, m, xn);
-    hipStream_t st = (hipStream_t)stream;
-    return dtype == LCGP_F64 ? do_sel_begin<double>(st, w, x, sr, theta, n_ref, x_ref, w_ref, n_cand, x_cand, match, r, size,
-                                                    pass_rows, (char*)scratch, &cv)
-                             : do_sel_begin<float>(st, w, x, sr, theta, n_ref, x_ref, w_ref, n_cand, x_cand, match, r, size,
-                                                   pass_rows, (char*)scratch, &cv);
+    const ViewArg v{state, m, xn, nullptr, scratch_bytes};
+    return sel_begin(stream, dtype, kernel_id, n, d, p, q_local, x, sr, theta, workspace, &v, n_ref, x_ref, w_ref, n_cand, x_cand,
+                     match_host, match, r, size, pass_rows, scratch);
 }
 
 int lcgp_condition_select_score(void* stream, int dtype, int n, int d, int q_local, int m, int n_ref, int n_cand, int size, int step,
                                 const double* omega, void* scratch, size_t scratch_bytes, double* out) {
-    SelLay L;
-    int rc = check_view_sel(dtype, n, d, 1, q_local, 0, m, n_ref, n_cand, size, scratch, scratch_bytes, &L);
-    if (rc) return rc;
-    if (step < 0 || step >= size) return bad("step must be in [0, size)");
-    if (!omega) return bad("NULL pointer");
-    char* sc = (char*)scratch;
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(sel_score_kernel, dim3(1), dim3(1024), 0, st, (const double*)(sc + L.off_R), q_local, n_cand, omega,
-                       (const int*)(sc + L.off_mask), out, (int*)(sc + L.off_picks) + step);
-    CHECK_LAUNCH("sel_score_kernel");
-    return 0;
+    return sel_score(stream, dtype, n, d, q_local, &m, n_ref, n_cand, size, step, omega, scratch, scratch_bytes, out);
 }
 
 int lcgp_condition_select_picks(int dtype, int n, int d, int q_local, int m, int n_ref, int n_cand, int size, void* scratch,
                                 size_t scratch_bytes, int** picks) {
-    SelLay L;
-    int rc = check_view_sel(dtype, n, d, 1, q_local, 0, m, n_ref, n_cand, size, scratch, scratch_bytes, &L);
-    if (rc) return rc;
-    if (!picks) return bad("NULL pointer");
-    *picks = (int*)((char*)scratch + L.off_picks);
-    return 0;
+    return sel_picks(dtype, n, d, q_local, &m, n_ref, n_cand, size, scratch, scratch_bytes, picks);
 }
 
 int lcgp_condition_select_condition(void* stream, int dtype, int kernel_id, int n, int d, int p, int q_local, const double* theta,
                                     int m, int n_ref, int n_cand, int size, int r, int step, const int* pick, void* scratch,
                                     size_t scratch_bytes) {
-    SelLay L;
-    int rc = check_view_sel(dtype, n, d, p, q_local, kernel_id, m, n_ref, n_cand, size, scratch, scratch_bytes, &L);
-    if (rc) return rc;
-    if (r < 1) return bad("r must be >= 1");
-    if (step < 0 || step >= size) return bad("step must be in [0, size)");
-    if (!theta || !pick) return bad("NULL pointer");
-    Ws w;
-    memset(&w, 0, sizeof(w));
-    w.n = n; w.npad = round_up(n, 2 * TS); w.d = d; w.p = p; w.q = q_local; w.kern = kernel_id;
-    w.esz = dtype == LCGP_F64 ? 8 : 4;
-    hipStream_t st = (hipStream_t)stream;
-    return dtype == LCGP_F64 ? do_sel_condition<double>(st, w, theta, n_ref, n_cand, size, r, step, pick, (char*)scratch, cov_pad(m))
-                             : do_sel_condition<float>(st, w, theta, n_ref, n_cand, size, r, step, pick, (char*)scratch, cov_pad(m));
+    return sel_condition(stream, dtype, kernel_id, n, d, p, q_local, theta, &m, n_ref, n_cand, size, r, step, pick, scratch,
+                         scratch_bytes);
 }
 
 int lcgp_condition_select_state(void* stream, int dtype, int n, int d, int q_local, int m, int n_ref, int n_cand, int size, int which,
                                 const void* scratch, size_t scratch_bytes, double* out) {
-    SelLay L;
-    int rc = check_view_sel(dtype, n, d, 1, q_local, 0, m, n_ref, n_cand, size, scratch, scratch_bytes, &L);
-    if (rc) return rc;
-    if (which != 0 && which != 1) return bad("which must be 0 (R) or 1 (h)");
-    if (!out) return bad("NULL pointer");
-    hipError_t e = hipMemcpyAsync(out, (const char*)scratch + (which ? L.off_h : L.off_R), (size_t)q_local * n_cand * sizeof(double),
-                                  hipMemcpyDeviceToDevice, (hipStream_t)stream);
-    return e == hipSuccess ? 0 : fail("hipMemcpyAsync", e);
+    return sel_state(stream, dtype, n, d, q_local, &m, n_ref, n_cand, size, which, scratch, scratch_bytes, out);
 }
 
 int lcgp_calib_rows(void* stream, int q, int d, int n0, const double* ghat, const double* gvar, const double* dghat,
@@ -9411,6 +9301,15 @@ int lcgp_sobol_pairs(void* stream, int kernel_id, int n, int d, int q_all, const
                                  SobolQ{nullptr, 0, 0});
 }
 
+// ks: local component indices, scanned here; pairs (the entries on the fitted model) receives the pairs (k, k)
+static int check_ks(const int* ks, int nks, int q_local, std::vector<int>* pairs = nullptr) {
+    for (int i = 0; i < nks; ++i) {
+        if (ks[i] < 0 || ks[i] >= q_local) return bad("ks must hold local component indices in [0, q_local)");
+        if (pairs) pairs->insert(pairs->end(), 2, ks[i]);
+    }
+    return 0;
+}
+
 int lcgp_sobol_matrix_scratch_bytes(int n, int d, int q_local, int nks, size_t* bytes) {
     int rc = sobol_check(n, d, q_local, 1);
     if (rc) return rc;
@@ -9429,11 +9328,8 @@ int lcgp_sobol_matrix_pairs(void* stream, int dtype, int kernel_id, int n, int d
     if ((rc = sobol_check(n, d, q_local, 1))) return rc;
     if (nks < 1) return bad("nks < 1");
     if (!x || !v || !ell || !box || !workspace || !ks || !scratch || !out) return bad("NULL pointer");
-    std::vector<int> pairs(2 * (size_t)nks);
-    for (int i = 0; i < nks; ++i) {
-        if (ks[i] < 0 || ks[i] >= q_local) return bad("ks must hold local component indices in [0, q_local)");
-        pairs[2 * i] = pairs[2 * i + 1] = ks[i];
-    }
+    std::vector<int> pairs;
+    if ((rc = check_ks(ks, nks, q_local, &pairs))) return rc;
     Ws w = carve(dtype, n, d, p, q_local, (void*)workspace);
     const SobolQ qm{(const double*)(w.base + w.off_V), w.mat, w.npad};
     return do_sobol_pairs<SOBOL_MAT>((hipStream_t)stream, kernel_id, n, d, q_local, x, v, ell, box, pairs.data(), nks, scratch, out, qm);
@@ -9466,8 +9362,7 @@ int lcgp_condition_sobol_matrix_pairs(void* stream, int dtype, int kernel_id, in
     if (rc) return rc;
     if ((rc = cond_sobol_check(n, d, q_local, m, nks))) return rc;
     if (!theta || !workspace || !state || !xa || !v || !ell || !box || !ks || !scratch || !out) return bad("NULL pointer");
-    for (int i = 0; i < nks; ++i)
-        if (ks[i] < 0 || ks[i] >= q_local) return bad("ks must hold local component indices in [0, q_local)");
+    if ((rc = check_ks(ks, nks, q_local))) return rc;
     if (scratch_bytes < cond_sobol_carve(n, d, q_local, m).total) return bad("scratch too small (lcgp_condition_sobol_scratch_bytes)");
     Ws w = carve(dtype, n, d, p, q_local, (void*)workspace);
     w.kern = kernel_id;
@@ -9526,11 +9421,8 @@ int lcgp_sobol_matrix_subset_pairs(void* stream, int dtype, int kernel_id, int n
     if ((rc = sobol_subset_check(n, d, q_local, 1, nsub))) return rc;
     if (nks < 1) return bad("nks < 1");
     if (!x || !v || !ell || !box || !workspace || !ks || !masks || !scratch || !out) return bad("NULL pointer");
-    std::vector<int> pairs(2 * (size_t)nks);
-    for (int i = 0; i < nks; ++i) {
-        if (ks[i] < 0 || ks[i] >= q_local) return bad("ks must hold local component indices in [0, q_local)");
-        pairs[2 * i] = pairs[2 * i + 1] = ks[i];
-    }
+    std::vector<int> pairs;
+    if ((rc = check_ks(ks, nks, q_local, &pairs))) return rc;
     if ((rc = sobol_masks_check(masks, nsub, d))) return rc;
     Ws w = carve(dtype, n, d, p, q_local, (void*)workspace);
     const SobolQ qm{(const double*)(w.base + w.off_V), w.mat, w.npad};
@@ -9560,8 +9452,7 @@ int lcgp_condition_sobol_matrix_subset_pairs(void* stream, int dtype, int kernel
     if ((rc = cond_sobol_check(n, d, q_local, m, nks))) return rc;
     if (nsub < 1) return bad("nsub < 1");
     if (!theta || !workspace || !state || !xa || !v || !ell || !box || !ks || !masks || !scratch || !out) return bad("NULL pointer");
-    for (int i = 0; i < nks; ++i)
-        if (ks[i] < 0 || ks[i] >= q_local) return bad("ks must hold local component indices in [0, q_local)");
+    if ((rc = check_ks(ks, nks, q_local))) return rc;
     if ((rc = sobol_masks_check(masks, nsub, d))) return rc;
     if (scratch_bytes < cond_sobol_carve(n, d, q_local, m, true).total)
         return bad("scratch too small (lcgp_condition_sobol_subset_scratch_bytes)");

@@ -53,6 +53,48 @@ _POINT_QUERIES = {
 }
 
 
+# the design queries: the (scratch query, entries ...) of the fitted model and of a conditioned view (the selection: the
+# prefix of its family).  A view's entries take the view behind the workspace, m behind q_local in the dims of the scratch
+# query and the scratch size behind the scratch (_design_open).
+_DESIGN_QUERIES = {
+    'vr': (("lcgp_variance_reduction_scratch_bytes", "lcgp_variance_reduction_prepare", "lcgp_variance_reduction"),
+           ("lcgp_condition_vr_scratch_bytes", "lcgp_condition_vr_prepare", "lcgp_condition_vr")),
+    'vr_grad': (("lcgp_variance_reduction_grad_scratch_bytes", "lcgp_variance_reduction_prepare", "lcgp_variance_reduction_grad"),
+                ("lcgp_condition_vr_grad_scratch_bytes", "lcgp_condition_vr_prepare", "lcgp_condition_vr_grad")),
+    'select': (("lcgp_select_scratch_bytes", "lcgp_select_"), ("lcgp_condition_select_scratch_bytes", "lcgp_condition_select_")),
+}
+
+# the Sobol passes (_sobol_pass): (entry, scratch query) of the 2 d + 1 standard subsets and of a caller's masks, then what the
+# memory refusal names ("pair" / "subset" goes in)
+_SOBOL_PASSES = {
+    'pairs': (("lcgp_sobol_pairs", "lcgp_sobol_scratch_bytes"), ("lcgp_sobol_subset_pairs", "lcgp_sobol_subset_scratch_bytes"),
+              "the Sobol %s sums"),
+    'matrix': (("lcgp_sobol_matrix_pairs", "lcgp_sobol_matrix_scratch_bytes"),
+               ("lcgp_sobol_matrix_subset_pairs", "lcgp_sobol_subset_scratch_bytes"), "the matrix-weighted Sobol %s sums"),
+    'view': (("lcgp_condition_sobol_matrix_pairs", "lcgp_condition_sobol_scratch_bytes"),
+             ("lcgp_condition_sobol_matrix_subset_pairs", "lcgp_condition_sobol_subset_scratch_bytes"),
+             "the matrix-weighted Sobol %s sums of a conditioned view"),
+}
+
+
+def _checked_box(box, what):
+    """box (2, d) = [lo; hi] after the check that it has a volume; `what` names the caller in the refusal"""
+    if not np.all(box[1] > box[0]):
+        raise ValueError("%s: the box needs hi > lo in every dimension" % what)
+    return box
+
+
+def _match_or_none(match):
+    """match as contiguous int32, or None when there is none or no candidate replicates a training input"""
+    match = None if match is None else np.ascontiguousarray(match, np.int32)
+    return match if match is not None and np.any(match >= 0) else None
+
+
+def _split_sums(res):
+    """(sums, s0): all but the last column of a pass over the standard subsets, and the last"""
+    return res[:, :-1].copy(), res[:, -1].copy()
+
+
 class HotPathEngine:
     """Holds x (n,d), Y (p,n), optional sr (n) and the workspace for the local components on one GPU.
 
@@ -348,15 +390,8 @@ class HotPathEngine:
         assert x0s.ndim == 2 and x0s.shape[1] == d and n0 >= 1
         chunk = min(n0, PREDICT_CHUNK)
         with torch.cuda.device(self.device):
-            free, _ = torch.cuda.mem_get_info(self.device)
-            free += torch.cuda.memory_reserved(self.device) - torch.cuda.memory_allocated(self.device)
-            free += 0 if self._scratch is None else self._scratch.numel()
-            group = self.q_local if q_group is None else max(1, min(int(q_group), self.q_local))
-            while True:
-                nbytes = self._nbytes("lcgp_predict_paramgrad_scratch_bytes", self.dtype, self.n, d, self.p, group, chunk)
-                if group == 1 or nbytes <= free:
-                    break
-                group = (group + 1) // 2
+            group, nbytes = self._fit_group("lcgp_predict_paramgrad_scratch_bytes", self.dtype, self.n, d, self.p, None, chunk,
+                                            q_group=q_group)
             scp = self._p(self._grow_scratch(nbytes, ("the parameter derivatives of %d new inputs per pass" % chunk,
                                                       "one n x n matrix and two of %d x n per component" % chunk,
                                                       "use fewer training inputs per GPU or lower lcgp_amd.engine.PREDICT_CHUNK")))
@@ -453,8 +488,7 @@ class HotPathEngine:
         mask = np.ascontiguousarray(np.asarray(mask) != 0, np.uint8)
         box = np.ascontiguousarray(box, np.float64)
         assert np.shape(x0s) == (n0, d) and mask.shape == (n0, d) and box.shape == (2, d) and n0 >= 1
-        if not np.all(box[1] > box[0]):
-            raise ValueError("predict_marginal_block: the box needs hi > lo in every dimension")
+        _checked_box(box, "predict_marginal_block")
         chunk = min(n0, max(128, PREDICT_CHUNK))
         m, view, kp = self._view_args(state)
         with torch.cuda.device(self.device):
@@ -507,28 +541,7 @@ class HotPathEngine:
         (npairs,)): row r = D_u of the pair for u = {l} (l = 0 .. d - 1), all but l, all inputs; means[r] = the box mean of
         component k where the pair is (k, k), 0 elsewhere.  Nothing of the factorisation is read; the tile sums go through the
         engine's scratch and are added in a fixed order (two calls agree bit for bit)."""
-        torch = self.torch
-        x = np.ascontiguousarray(x, np.float64)
-        w = np.ascontiguousarray(w, np.float64)
-        ell = np.ascontiguousarray(ell, np.float64)
-        box = np.ascontiguousarray(box, np.float64)
-        pairs = np.ascontiguousarray(pairs, np.int32)
-        n, d = x.shape
-        q_all, npairs = w.shape[0], pairs.shape[0]
-        assert w.shape == (q_all, n) and ell.shape == (q_all, d) and box.shape == (2, d) and pairs.shape == (npairs, 2)
-        if not np.all(box[1] > box[0]):
-            raise ValueError("sobol_pairs: the box needs hi > lo in every dimension")
-        with torch.cuda.device(self.device):
-            dev = [torch.as_tensor(a).to(self.device) for a in (x, w, ell, box)]
-            scratch = self._grow_scratch(self._nbytes("lcgp_sobol_scratch_bytes", n, d, q_all, npairs),
-                                         ("the Sobol pair sums", "%d tile sums of %d pairs at a time" % ((-(-n // 64)) ** 2, min(npairs, 64)),
-                                          "use fewer training inputs"))
-            out = torch.empty((npairs, 2 * d + 2), dtype=torch.float64, device=self.device)
-            _hip.check(self.lib.lcgp_sobol_pairs(self._stream(), self.kernel_id, n, d, q_all, *[self._p(t) for t in dev],
-                                                 pairs.ctypes.data_as(C.POINTER(C.c_int)), npairs, self._p(scratch), self._p(out)),
-                       "lcgp_sobol_pairs")
-            res = out.cpu().numpy()
-        return res[:, :2 * d + 1].copy(), res[:, 2 * d + 1].copy()
+        return _split_sums(self._sobol_pass("sobol_pairs", 'pairs', x, w, ell, box, pairs)[0])
 
     def sobol_matrix_sums(self, x, v, ell, box, ks):
         """The pair sums of sobol_pairs for the pairs (k, k) of the LOCAL components ks, weighted by the matrix
@@ -537,33 +550,7 @@ class HotPathEngine:
         local components, box (2, d) standardised, ks local component indices.  Returns host arrays (sums (len(ks), 2 d + 1),
         s0 (len(ks),)): sum Q (M_u - M_0) for u = {l}, all but l, all inputs, and S0 = sum Q M_0.  A^-1 is read in place from the
         float64 workspace of the last evaluate(); the tile sums go through the engine's scratch in a fixed order."""
-        torch = self.torch
-        assert self.dtype == _hip.F64, "sobol_matrix_sums reads the A^-1 of a float64 engine"
-        if self._theta_last is None:
-            raise RuntimeError("sobol_matrix_sums() needs a preceding evaluate() at the current parameters")
-        x = np.ascontiguousarray(x, np.float64)
-        v = np.ascontiguousarray(v, np.float64)
-        ell = np.ascontiguousarray(ell, np.float64)
-        box = np.ascontiguousarray(box, np.float64)
-        ks = np.ascontiguousarray(ks, np.int32).reshape(-1)
-        n, d = x.shape
-        nks = ks.shape[0]
-        assert n == self.n and d == self.d and v.shape == (self.q_local, n) and ell.shape == (self.q_local, d) and box.shape == (2, d)
-        if not np.all(box[1] > box[0]):
-            raise ValueError("sobol_matrix_sums: the box needs hi > lo in every dimension")
-        with torch.cuda.device(self.device):
-            dev = [torch.as_tensor(a).to(self.device) for a in (x, v, ell, box)]
-            scratch = self._grow_scratch(self._nbytes("lcgp_sobol_matrix_scratch_bytes", n, d, self.q_local, nks),
-                                         ("the matrix-weighted Sobol pair sums",
-                                          "%d tile sums of %d components at a time" % ((-(-n // 64)) ** 2, min(nks, 64)),
-                                          "use fewer training inputs"))
-            out = torch.empty((nks, 2 * d + 2), dtype=torch.float64, device=self.device)
-            _hip.check(self.lib.lcgp_sobol_matrix_pairs(self._stream(), self.dtype, self.kernel_id, n, d, self.p, self.q_local,
-                                                        *[self._p(t) for t in dev], self._p(self.workspace),
-                                                        ks.ctypes.data_as(C.POINTER(C.c_int)), nks, self._p(scratch), self._p(out)),
-                       "lcgp_sobol_matrix_pairs")
-            res = out.cpu().numpy()
-        return res[:, :2 * d + 1].copy(), res[:, 2 * d + 1].copy()
+        return _split_sums(self._sobol_pass("sobol_matrix_sums", 'matrix', x, v, ell, box, ks)[0])
 
     def condition_sobol_matrix_sums(self, state, v, ell, box, ks):
         """sobol_matrix_sums on the view `state` (lcgp_condition_sobol_matrix_pairs): over the N = n + m centres
@@ -572,37 +559,70 @@ class HotPathEngine:
         matrices), ell (q_local, d), box (2, d) standardised, ks local component indices.  Returns host arrays (sums (len(ks),
         2 d + 1), s0 (len(ks),)).  The float64 workspace, the view's state and its grad state are only read; E of one component
         at a time lives in the engine's scratch."""
+        return _split_sums(self._sobol_pass("condition_sobol_matrix_sums", 'view', None, v, ell, box, ks, state=state)[0])
+
+    def _sobol_pass(self, caller, kind, x, wv, ell, box, idx, masks=None, state=None):
+        """One Sobol pass (_SOBOL_PASSES[kind]) for the public method `caller`: the conversions and checks, the inputs on the
+        device, the engine's scratch grown for it, the call and the fetch.  'pairs': the weights wv (q_all, n) of all components
+        and idx = pairs (npairs, 2); 'matrix' / 'view': the row vectors wv of the local components, idx = ks, and the float64
+        factorisation of the last evaluate(); 'view' takes its centres [x; xn] from the view `state`, not x.  masks: the pass over
+        a caller's subsets (an output column per mask) instead of the 2 d + 1 standard ones and the mean term.  Returns the
+        host array of the sums and the scratch."""
         torch = self.torch
-        assert self.dtype == _hip.F64, "condition_sobol_matrix_sums reads the A^-1 and the view state of a float64 engine"
-        if self._theta_last is None:
-            raise RuntimeError("condition_sobol_matrix_sums() needs a preceding evaluate() at the current parameters")
-        n, d, m = self.n, self.d, state['m']
-        N = n + m
-        v = np.ascontiguousarray(v, np.float64)
+        entry, sizer = _SOBOL_PASSES[kind][0 if masks is None else 1]
+        if kind != 'pairs':
+            assert self.dtype == _hip.F64, "%s reads the A^-1 %sof a float64 engine" % (caller, "and the view state " if state else "")
+            if self._theta_last is None:
+                raise RuntimeError("%s() needs a preceding evaluate() at the current parameters" % caller)
+        if state is None:
+            x = np.ascontiguousarray(x, np.float64)
+            (n, d), m = x.shape, 0
+        else:
+            n, d, m = self.n, self.d, state['m']
+        wv = np.ascontiguousarray(wv, np.float64)
         ell = np.ascontiguousarray(ell, np.float64)
         box = np.ascontiguousarray(box, np.float64)
-        ks = np.ascontiguousarray(ks, np.int32).reshape(-1)
-        nks = ks.shape[0]
-        assert v.shape == (self.q_local, N) and ell.shape == (self.q_local, d) and box.shape == (2, d)
-        if not np.all(box[1] > box[0]):
-            raise ValueError("condition_sobol_matrix_sums: the box needs hi > lo in every dimension")
+        idx = np.ascontiguousarray(idx, np.int32)
+        if kind == 'pairs':
+            q, nidx = wv.shape[0], idx.shape[0]
+            assert idx.shape == (nidx, 2)
+        else:
+            idx = idx.reshape(-1)
+            q, nidx = self.q_local, idx.shape[0]
+            assert n == self.n and d == self.d
+        assert wv.shape == (q, n + m) and ell.shape == (q, d) and box.shape == (2, d)
+        tail = ()
+        if masks is not None:
+            masks = self._subset_masks(masks, d, caller)
+            tail = (masks.ctypes.data_as(C.POINTER(C.c_uint64)), masks.shape[0])
+        _checked_box(box, caller)
+        tiles = -(-(n + m) // 64)
+        what = _SOBOL_PASSES[kind][2] % ("pair" if masks is None else "subset")
+        if state is None:
+            refusal = (what, "%d tile sums of %d %s at a time" % (tiles ** 2, min(nidx, 64), "pairs" if kind == 'pairs' else "components"),
+                       "use fewer training inputs")
+        else:
+            refusal = (what, "one component's %d x %d matrix E and %d tile sums" % (64 * tiles, 64 * tiles, tiles ** 2),
+                       "condition on fewer new inputs at a time")
         with torch.cuda.device(self.device):
-            self._condition_grad_state(state)
-            xa = torch.cat([self.x, state['xn']]).contiguous()           # (float64: the engine's dtype)
-            dev = [torch.as_tensor(a).to(self.device) for a in (v, ell, box)]
-            npad_all = -(-N // 64) * 64
-            scratch = self._grow_scratch(self._nbytes("lcgp_condition_sobol_scratch_bytes", n, d, self.q_local, m, nks),
-                                         ("the matrix-weighted Sobol pair sums of a conditioned view",
-                                          "one component's %d x %d matrix E and %d tile sums" % (npad_all, npad_all, (npad_all // 64) ** 2),
-                                          "condition on fewer new inputs at a time"))
-            out = torch.empty((nks, 2 * d + 2), dtype=torch.float64, device=self.device)
-            _hip.check(self.lib.lcgp_condition_sobol_matrix_pairs(
-                self._stream(), self.dtype, self.kernel_id, n, d, self.p, self.q_local, self._p(self.theta_dev),
-                self._p(self.workspace), self._p(state['state']), m, self._p(xa), *[self._p(t) for t in dev],
-                ks.ctypes.data_as(C.POINTER(C.c_int)), nks, self._p(scratch), scratch.numel(), self._p(out)),
-                "lcgp_condition_sobol_matrix_pairs")
-            res = out.cpu().numpy()
-        return res[:, :2 * d + 1].copy(), res[:, 2 * d + 1].copy()
+            if state is None:
+                model = () if kind == 'pairs' else (self.dtype,)
+                head = (self._stream(),) + model + (self.kernel_id, n, d) + (() if kind == 'pairs' else (self.p,)) + (q,)
+                dev = [torch.as_tensor(a).to(self.device) for a in (x, wv, ell, box)]
+                head += tuple(self._p(t) for t in dev) + (() if kind == 'pairs' else (self._p(self.workspace),))
+                dims = (n, d, q, nidx)
+            else:
+                self._condition_grad_state(state)
+                xa = torch.cat([self.x, state['xn']]).contiguous()           # (float64: the engine's dtype)
+                dev = [torch.as_tensor(a).to(self.device) for a in (wv, ell, box)]
+                head = (self._stream(), self.dtype, self.kernel_id, n, d, self.p, q, self._p(self.theta_dev), self._p(self.workspace),
+                        self._p(state['state']), m, self._p(xa)) + tuple(self._p(t) for t in dev)
+                dims = (n, d, q, m, nidx)
+            scratch = self._grow_scratch(self._nbytes(sizer, *dims, *tail[1:]), refusal)
+            out = torch.empty((nidx, 2 * d + 2 if masks is None else tail[1]), dtype=torch.float64, device=self.device)
+            scs = (self._p(scratch),) if state is None else (self._p(scratch), scratch.numel())
+            _hip.check(getattr(self.lib, entry)(*head, idx.ctypes.data_as(C.POINTER(C.c_int)), nidx, *tail, *scs, self._p(out)), entry)
+            return out.cpu().numpy(), scratch
 
     # ---- the same three passes for a caller's list of input subsets (DESIGN.md 4.25) ----
     def _subset_masks(self, masks, d, what):
@@ -619,33 +639,12 @@ class HotPathEngine:
         l set when input l is in the subset u; the other arguments as there.  Returns host arrays (D (npairs, nsub), means
         (npairs,)): D[r, s] = D_u of the pair for u = masks[s] (the empty mask: exactly 0); means as sobol_pairs returns them.
         lcgp_sobol_subset_chunk(d) masks per launch; d <= 16."""
-        torch = self.torch
-        x = np.ascontiguousarray(x, np.float64)
-        w = np.ascontiguousarray(w, np.float64)
-        ell = np.ascontiguousarray(ell, np.float64)
-        box = np.ascontiguousarray(box, np.float64)
-        pairs = np.ascontiguousarray(pairs, np.int32)
-        n, d = x.shape
-        q_all, npairs = w.shape[0], pairs.shape[0]
-        assert w.shape == (q_all, n) and ell.shape == (q_all, d) and box.shape == (2, d) and pairs.shape == (npairs, 2)
-        masks = self._subset_masks(masks, d, "sobol_subset_pairs")
-        nsub = masks.shape[0]
-        if not np.all(box[1] > box[0]):
-            raise ValueError("sobol_subset_pairs: the box needs hi > lo in every dimension")
-        with torch.cuda.device(self.device):
-            dev = [torch.as_tensor(a).to(self.device) for a in (x, w, ell, box)]
-            scratch = self._grow_scratch(self._nbytes("lcgp_sobol_subset_scratch_bytes", n, d, q_all, npairs, nsub),
-                                         ("the Sobol subset sums", "%d tile sums of %d pairs at a time" % ((-(-n // 64)) ** 2, min(npairs, 64)),
-                                          "use fewer training inputs"))
-            out = torch.empty((npairs, nsub), dtype=torch.float64, device=self.device)
-            _hip.check(self.lib.lcgp_sobol_subset_pairs(self._stream(), self.kernel_id, n, d, q_all, *[self._p(t) for t in dev],
-                                                        pairs.ctypes.data_as(C.POINTER(C.c_int)), npairs,
-                                                        masks.ctypes.data_as(C.POINTER(C.c_uint64)), nsub, self._p(scratch),
-                                                        self._p(out)),
-                       "lcgp_sobol_subset_pairs")
-            res = out.cpu().numpy()
+        res, scratch = self._sobol_pass("sobol_subset_pairs", 'pairs', x, w, ell, box, pairs, masks)
+        pairs = np.asarray(pairs, np.int32)
+        (n, d), q_all = np.shape(x), np.shape(w)[0]
+        with self.torch.cuda.device(self.device):
             # (the box means of the components follow the table in the scratch: include/lcgp_hip.h)
-            comp = scratch[8 * q_all * d * n:8 * (q_all * d * n + q_all)].view(torch.float64).cpu().numpy()
+            comp = scratch[8 * q_all * d * n:8 * (q_all * d * n + q_all)].view(self.torch.float64).cpu().numpy()
         means = np.where(pairs[:, 0] == pairs[:, 1], comp[pairs[:, 0]], 0.0)
         return res, means
 
@@ -653,75 +652,13 @@ class HotPathEngine:
         """sobol_matrix_sums for a list of subsets of the inputs (lcgp_sobol_matrix_subset_pairs): masks (nsub,)
         as in sobol_subset_pairs, the other arguments as there.  Returns the host array sums (len(ks), nsub) = sum Q (M_u - M_0)
         for u = masks[s]; no S0 (the corrections of the subsets do not need it)."""
-        torch = self.torch
-        assert self.dtype == _hip.F64, "sobol_matrix_subset_sums reads the A^-1 of a float64 engine"
-        if self._theta_last is None:
-            raise RuntimeError("sobol_matrix_subset_sums() needs a preceding evaluate() at the current parameters")
-        x = np.ascontiguousarray(x, np.float64)
-        v = np.ascontiguousarray(v, np.float64)
-        ell = np.ascontiguousarray(ell, np.float64)
-        box = np.ascontiguousarray(box, np.float64)
-        ks = np.ascontiguousarray(ks, np.int32).reshape(-1)
-        n, d = x.shape
-        nks = ks.shape[0]
-        assert n == self.n and d == self.d and v.shape == (self.q_local, n) and ell.shape == (self.q_local, d) and box.shape == (2, d)
-        masks = self._subset_masks(masks, d, "sobol_matrix_subset_sums")
-        nsub = masks.shape[0]
-        if not np.all(box[1] > box[0]):
-            raise ValueError("sobol_matrix_subset_sums: the box needs hi > lo in every dimension")
-        with torch.cuda.device(self.device):
-            dev = [torch.as_tensor(a).to(self.device) for a in (x, v, ell, box)]
-            scratch = self._grow_scratch(self._nbytes("lcgp_sobol_subset_scratch_bytes", n, d, self.q_local, nks, nsub),
-                                         ("the matrix-weighted Sobol subset sums",
-                                          "%d tile sums of %d components at a time" % ((-(-n // 64)) ** 2, min(nks, 64)),
-                                          "use fewer training inputs"))
-            out = torch.empty((nks, nsub), dtype=torch.float64, device=self.device)
-            _hip.check(self.lib.lcgp_sobol_matrix_subset_pairs(
-                self._stream(), self.dtype, self.kernel_id, n, d, self.p, self.q_local, *[self._p(t) for t in dev],
-                self._p(self.workspace), ks.ctypes.data_as(C.POINTER(C.c_int)), nks, masks.ctypes.data_as(C.POINTER(C.c_uint64)),
-                nsub, self._p(scratch), self._p(out)),
-                "lcgp_sobol_matrix_subset_pairs")
-            res = out.cpu().numpy()
-        return res
+        return self._sobol_pass("sobol_matrix_subset_sums", 'matrix', x, v, ell, box, ks, masks)[0]
 
     def condition_sobol_matrix_subset_sums(self, state, v, ell, box, ks, masks):
         """condition_sobol_matrix_sums for a list of subsets of the inputs (lcgp_condition_sobol_matrix_subset_pairs; DESIGN.md
         4.25): masks (nsub,) as in sobol_subset_pairs, the other arguments as there.  Returns the host array sums (len(ks), nsub)
         = sum Q' (M_u - M_0) over the N = n + m centres.  E is prepared once per component, whatever the number of masks."""
-        torch = self.torch
-        assert self.dtype == _hip.F64, "condition_sobol_matrix_subset_sums reads the A^-1 and the view state of a float64 engine"
-        if self._theta_last is None:
-            raise RuntimeError("condition_sobol_matrix_subset_sums() needs a preceding evaluate() at the current parameters")
-        n, d, m = self.n, self.d, state['m']
-        N = n + m
-        v = np.ascontiguousarray(v, np.float64)
-        ell = np.ascontiguousarray(ell, np.float64)
-        box = np.ascontiguousarray(box, np.float64)
-        ks = np.ascontiguousarray(ks, np.int32).reshape(-1)
-        nks = ks.shape[0]
-        assert v.shape == (self.q_local, N) and ell.shape == (self.q_local, d) and box.shape == (2, d)
-        masks = self._subset_masks(masks, d, "condition_sobol_matrix_subset_sums")
-        nsub = masks.shape[0]
-        if not np.all(box[1] > box[0]):
-            raise ValueError("condition_sobol_matrix_subset_sums: the box needs hi > lo in every dimension")
-        with torch.cuda.device(self.device):
-            self._condition_grad_state(state)
-            xa = torch.cat([self.x, state['xn']]).contiguous()           # (float64: the engine's dtype)
-            dev = [torch.as_tensor(a).to(self.device) for a in (v, ell, box)]
-            npad_all = -(-N // 64) * 64
-            scratch = self._grow_scratch(self._nbytes("lcgp_condition_sobol_subset_scratch_bytes", n, d, self.q_local, m, nks, nsub),
-                                         ("the matrix-weighted Sobol subset sums of a conditioned view",
-                                          "one component's %d x %d matrix E and %d tile sums" % (npad_all, npad_all, (npad_all // 64) ** 2),
-                                          "condition on fewer new inputs at a time"))
-            out = torch.empty((nks, nsub), dtype=torch.float64, device=self.device)
-            _hip.check(self.lib.lcgp_condition_sobol_matrix_subset_pairs(
-                self._stream(), self.dtype, self.kernel_id, n, d, self.p, self.q_local, self._p(self.theta_dev),
-                self._p(self.workspace), self._p(state['state']), m, self._p(xa), *[self._p(t) for t in dev],
-                ks.ctypes.data_as(C.POINTER(C.c_int)), nks, masks.ctypes.data_as(C.POINTER(C.c_uint64)), nsub, self._p(scratch),
-                scratch.numel(), self._p(out)),
-                "lcgp_condition_sobol_matrix_subset_pairs")
-            res = out.cpu().numpy()
-        return res
+        return self._sobol_pass("condition_sobol_matrix_subset_sums", 'view', None, v, ell, box, ks, masks, state)[0]
 
     def condition_mean_vectors(self, state):
         """(z' (q_local, n), w (q_local, m)) of the view `state` on the host: its mean surface is X_0 z' + c^x(x0, xn) w (the grad
@@ -753,6 +690,21 @@ class HotPathEngine:
         if nbytes > free:
             raise ValueError("%s needs %.2f GB of device memory (%s), %.2f GB are free: %s"
                              % (what, nbytes / 1e9, detail, free / 1e9, advice))
+
+    def _fit_group(self, sizer, *dims, q_group=None):
+        """(group, nbytes): how many local components a grouped query processes at once and the scratch `sizer` wants for them
+        (dims: its arguments, None where the group goes).  All of them, or at most q_group, halved until the scratch fits in the
+        free device memory -- the engine's own scratch counts as free -- or one component is left.  Inside the device context."""
+        torch = self.torch
+        free, _ = torch.cuda.mem_get_info(self.device)
+        free += torch.cuda.memory_reserved(self.device) - torch.cuda.memory_allocated(self.device)
+        free += 0 if self._scratch is None else self._scratch.numel()
+        group = self.q_local if q_group is None else max(1, min(int(q_group), self.q_local))
+        while True:
+            nbytes = self._nbytes(sizer, *[group if a is None else a for a in dims])
+            if group == 1 or nbytes <= free:
+                return group, nbytes
+            group = (group + 1) // 2
 
     def _cov_refusal(self, what):
         """the free-memory check's text for the joint covariance's buffers"""
@@ -1077,6 +1029,38 @@ class HotPathEngine:
         m = state['m']
         return m, (self._p(state['state']), m, self._p(state['xn'])), npad + -(-m // 128) * 128
 
+    def _design_inputs(self, caller, x_cand_s, x_ref_s, w, match=None):
+        """The host half of a design query: the check that an evaluation stands behind `caller`, then (x_cand_s, x_ref_s, match,
+        shared): the checked float64 candidates (n_cand, d) and reference set (n_ref, d) with its n_ref weights w, match as
+        _match_or_none leaves it; shared: x_ref_s was None, the reference set IS the candidate set"""
+        if self._theta_last is None:
+            raise RuntimeError("%s() needs a preceding evaluate() at the current parameters" % caller)
+        x_cand_s = np.ascontiguousarray(x_cand_s, np.float64)
+        assert x_cand_s.ndim == 2 and x_cand_s.shape[1] == self.d and x_cand_s.shape[0] >= 1
+        match = _match_or_none(match)
+        shared = x_ref_s is None
+        x_ref_s = x_cand_s if shared else np.ascontiguousarray(x_ref_s, np.float64)
+        assert x_ref_s.ndim == 2 and x_ref_s.shape[1] == self.d and x_ref_s.shape[0] >= 1 and len(w) == x_ref_s.shape[0]
+        return x_cand_s, x_ref_s, match, shared
+
+    def _design_open(self, query, view_args, lead, trail, refusal, x_ref_s, x_cand_s, w, match):
+        """The device half of a design query (_DESIGN_QUERIES) on the fitted model or on a view (view_args = _view_args(state)),
+        inside the device context: the engine's scratch grown to what the family's scratch query returns for lead + (m on a view)
+        + trail (refusal: what, detail, advice of the free-memory check), then the inputs on the device.  Returns (the family's
+        other entry names, the dims, (scratch[, scratch_bytes]) as the entries take them, the head with the view, (xr, xc, wd,
+        md)); x_cand_s / match = None: no xc / md."""
+        torch = self.torch
+        m, view, _ = view_args
+        sizer, *names = _DESIGN_QUERIES[query][1 if view else 0]
+        dims = lead + ((m,) if view else ()) + trail
+        scratch = self._grow_scratch(self._nbytes(sizer, *dims), refusal)
+        xr = torch.as_tensor(x_ref_s).to(self.device, self.tdtype).contiguous()
+        xc = None if x_cand_s is None else torch.as_tensor(x_cand_s).to(self.device, self.tdtype).contiguous()
+        wd = torch.as_tensor(np.ascontiguousarray(w, np.float64)).to(self.device)
+        md = None if match is None else torch.as_tensor(match).to(self.device)
+        scs = (self._p(scratch), scratch.numel()) if view else (self._p(scratch),)
+        return names, dims, scs, self._head() + view, (xr, xc, wd, md)
+
     def variance_reduction_block(self, x_cand_s, x_ref_s, w, match, r):
         return self._vr_block(None, x_cand_s, x_ref_s, w, match, r)
 
@@ -1093,40 +1077,20 @@ class HotPathEngine:
         input a candidate replicates (its cross row carries the nugget term there).  U of the reference set is formed once per
         call; candidates go in chunks of PREDICT_CHUNK; with x_ref_s = None and no match one U serves both.  Raises ValueError
         when the scratch does not fit in the free device memory."""
-        torch = self.torch
-        if self._theta_last is None:
-            raise RuntimeError("variance_reduction() needs a preceding evaluate() at the current parameters")
-        x_cand_s = np.ascontiguousarray(x_cand_s, np.float64)
-        n_cand, d = x_cand_s.shape[0], self.d
-        assert x_cand_s.ndim == 2 and x_cand_s.shape[1] == d and n_cand >= 1
-        match = None if match is None else np.ascontiguousarray(match, np.int32)
-        if match is not None and not np.any(match >= 0):
-            match = None
-        shared = x_ref_s is None and match is None
-        x_ref_s = x_cand_s if x_ref_s is None else np.ascontiguousarray(x_ref_s, np.float64)
-        n_ref = x_ref_s.shape[0]
-        assert x_ref_s.ndim == 2 and x_ref_s.shape[1] == d and n_ref >= 1 and len(w) == n_ref
+        torch, d = self.torch, self.d
+        x_cand_s, x_ref_s, match, shared = self._design_inputs("variance_reduction", x_cand_s, x_ref_s, w, match)
+        shared = shared and match is None
+        n_cand, n_ref = x_cand_s.shape[0], x_ref_s.shape[0]
         chunk = min(n_cand, PREDICT_CHUNK)
-        m, view, kp = self._view_args(state)
+        va = self._view_args(state)
         with torch.cuda.device(self.device):
-            if state is None:
-                nbytes = self._nbytes("lcgp_variance_reduction_scratch_bytes", self.dtype, self.n, self.q_local, n_ref, chunk)
-                detail = "%d components of (n_ref + %d candidates) x n" % (self.q_local, chunk)
-            else:
-                nbytes = self._nbytes("lcgp_condition_vr_scratch_bytes", self.dtype, self.n, self.q_local, m, n_ref, chunk)
-                detail = "%d components of (n_ref + %d candidates) x K', K' = npad + mpad = %d" % (self.q_local, chunk, kp)
-            scratch = self._grow_scratch(nbytes, ("the variance reduction over %d reference points" % n_ref, detail,
-                                                  "pass fewer reference points"))
-            xr = torch.as_tensor(x_ref_s).to(self.device, self.tdtype).contiguous()
-            xc = None if shared else torch.as_tensor(x_cand_s).to(self.device, self.tdtype).contiguous()
-            wd = torch.as_tensor(np.ascontiguousarray(w, np.float64)).to(self.device)
-            md = None if match is None else torch.as_tensor(match).to(self.device)
+            detail = ("%d components of (n_ref + %d candidates) x n" % (self.q_local, chunk) if state is None else
+                      "%d components of (n_ref + %d candidates) x K', K' = npad + mpad = %d" % (self.q_local, chunk, va[2]))
+            (prepare, entry), _, scs, head, (xr, xc, wd, md) = self._design_open(
+                'vr', va, (self.dtype, self.n, self.q_local), (n_ref, chunk),
+                ("the variance reduction over %d reference points" % n_ref, detail, "pass fewer reference points"),
+                x_ref_s, None if shared else x_cand_s, w, match)
             out = torch.empty((self.q_local, n_cand), dtype=torch.float64, device=self.device)
-            # (the entries on a view take the view behind the workspace and the scratch size behind the scratch)
-            prepare, entry = (("lcgp_variance_reduction_prepare", "lcgp_variance_reduction") if state is None else
-                              ("lcgp_condition_vr_prepare", "lcgp_condition_vr"))
-            scs = (self._p(scratch),) if state is None else (self._p(scratch), scratch.numel())
-            head = self._head() + view
             _hip.check(getattr(self.lib, prepare)(*head, n_ref, self._p(xr), *scs), prepare)
             for lo in range(0, n_cand, chunk):
                 rows = min(chunk, n_cand - lo)
@@ -1156,22 +1120,11 @@ class HotPathEngine:
         box_s = np.ascontiguousarray(box_s, np.float64)
         n0, d = x_cand_s.shape[0], self.d
         assert x_cand_s.ndim == 2 and x_cand_s.shape[1] == d and n0 >= 1 and box_s.shape == (2, d)
-        if not np.all(box_s[1] > box_s[0]):
-            raise ValueError("box_alc_block: the box needs hi > lo in every dimension")
-        match = None if match is None else np.ascontiguousarray(match, np.int32)
-        if match is not None and not np.any(match >= 0):
-            match = None
+        _checked_box(box_s, "box_alc_block")
+        match = _match_or_none(match)
         chunk = min(n0, max(PREDICT_CHUNK, 128) if n0 >= 128 else PREDICT_CHUNK)
         with torch.cuda.device(self.device):
-            free, _ = torch.cuda.mem_get_info(self.device)
-            free += torch.cuda.memory_reserved(self.device) - torch.cuda.memory_allocated(self.device)
-            free += 0 if self._scratch is None else self._scratch.numel()
-            group = self.q_local if q_group is None else max(1, min(int(q_group), self.q_local))
-            while True:
-                nbytes = self._nbytes("lcgp_box_alc_scratch_bytes", self.dtype, self.n, d, group, chunk)
-                if group == 1 or nbytes <= free:
-                    break
-                group = (group + 1) // 2
+            group, nbytes = self._fit_group("lcgp_box_alc_scratch_bytes", self.dtype, self.n, d, None, chunk, q_group=q_group)
             scp = self._p(self._grow_scratch(nbytes, ("the exact box ALC of %d candidates per pass" % chunk,
                                                       "one n x n matrix and two of %d x n per component" % chunk,
                                                       "use fewer training inputs per GPU or lower lcgp_amd.engine.PREDICT_CHUNK")))
@@ -1204,38 +1157,21 @@ class HotPathEngine:
         w held constant (also with x_ref_s = None, where the reference set is a copy of the candidates)
         (lcgp_variance_reduction_prepare once, lcgp_variance_reduction_grad per chunk of PREDICT_CHUNK candidates; on a view
         their lcgp_condition_vr_* siblings).  Raises ValueError when the scratch does not fit in the free device memory."""
-        torch = self.torch
-        if self._theta_last is None:
-            raise RuntimeError("variance_reduction_grad() needs a preceding evaluate() at the current parameters")
-        x_cand_s = np.ascontiguousarray(x_cand_s, np.float64)
-        n_cand, d = x_cand_s.shape[0], self.d
-        assert x_cand_s.ndim == 2 and x_cand_s.shape[1] == d and n_cand >= 1
-        shared = x_ref_s is None
-        x_ref_s = x_cand_s if shared else np.ascontiguousarray(x_ref_s, np.float64)
-        n_ref = x_ref_s.shape[0]
-        assert x_ref_s.ndim == 2 and x_ref_s.shape[1] == d and n_ref >= 1 and len(w) == n_ref
+        torch, d = self.torch, self.d
+        x_cand_s, x_ref_s, _, shared = self._design_inputs("variance_reduction_grad", x_cand_s, x_ref_s, w)
+        n_cand, n_ref = x_cand_s.shape[0], x_ref_s.shape[0]
         chunk = min(n_cand, PREDICT_CHUNK)
-        m, view, kp = self._view_args(state)
+        va = self._view_args(state)
         with torch.cuda.device(self.device):
-            if state is None:
-                nbytes = self._nbytes("lcgp_variance_reduction_grad_scratch_bytes", self.dtype, self.n, d, self.q_local, n_ref, chunk)
-                detail = "%d components of n_ref x n and %d candidates x (n_ref + 3 n)" % (self.q_local, chunk)
-            else:
-                nbytes = self._nbytes("lcgp_condition_vr_grad_scratch_bytes", self.dtype, self.n, d, self.q_local, m, n_ref, chunk)
-                detail = ("%d components of n_ref x K' and %d candidates x (n_ref + 2 K' + 2 n), K' = npad + mpad = %d"
-                          % (self.q_local, chunk, kp))
-            scratch = self._grow_scratch(nbytes, ("the variance reduction gradient over %d reference points" % n_ref, detail,
-                                                  "pass fewer reference points"))
-            xr = torch.as_tensor(x_ref_s).to(self.device, self.tdtype).contiguous()
-            xc = None if shared else torch.as_tensor(x_cand_s).to(self.device, self.tdtype).contiguous()
-            wd = torch.as_tensor(np.ascontiguousarray(w, np.float64)).to(self.device)
+            detail = ("%d components of n_ref x n and %d candidates x (n_ref + 3 n)" % (self.q_local, chunk) if state is None else
+                      "%d components of n_ref x K' and %d candidates x (n_ref + 2 K' + 2 n), K' = npad + mpad = %d"
+                      % (self.q_local, chunk, va[2]))
+            (prepare, entry), _, scs, head, (xr, xc, wd, _) = self._design_open(
+                'vr_grad', va, (self.dtype, self.n, d, self.q_local), (n_ref, chunk),
+                ("the variance reduction gradient over %d reference points" % n_ref, detail, "pass fewer reference points"),
+                x_ref_s, None if shared else x_cand_s, w, None)
             out = torch.empty((self.q_local, n_cand), dtype=torch.float64, device=self.device)
             dout = torch.empty((self.q_local, n_cand, d), dtype=torch.float64, device=self.device)
-            # (the entries on a view take the view behind the workspace and the scratch size behind the scratch)
-            prepare, entry = (("lcgp_variance_reduction_prepare", "lcgp_variance_reduction_grad") if state is None else
-                              ("lcgp_condition_vr_prepare", "lcgp_condition_vr_grad"))
-            scs = (self._p(scratch),) if state is None else (self._p(scratch), scratch.numel())
-            head = self._head() + view
             _hip.check(getattr(self.lib, prepare)(*head, n_ref, self._p(xr), *scs), prepare)
             for lo in range(0, n_cand, chunk):
                 rows = min(chunk, n_cand - lo)
@@ -1260,42 +1196,27 @@ class HotPathEngine:
         engine's scratch (candidates in passes of PREDICT_CHUNK rows) and the step-0 state R = variance_reduction_block(...) bitwise.
         Arguments as variance_reduction_block.  Raises ValueError when the scratch does not fit in the free device memory.  The
         state lives in the engine's scratch: no other query may run between select_begin and the last select_condition."""
-        torch = self.torch
-        if self._theta_last is None:
-            raise RuntimeError("select_batch() needs a preceding evaluate() at the current parameters")
-        x_cand_s = np.ascontiguousarray(x_cand_s, np.float64)
-        n_cand, d = x_cand_s.shape[0], self.d
-        assert x_cand_s.ndim == 2 and x_cand_s.shape[1] == d and 1 <= size <= n_cand
-        match = None if match is None else np.ascontiguousarray(match, np.int32)
-        if match is not None and not np.any(match >= 0):
-            match = None
-        x_ref_s = x_cand_s if x_ref_s is None else np.ascontiguousarray(x_ref_s, np.float64)
-        n_ref = x_ref_s.shape[0]
-        assert x_ref_s.ndim == 2 and x_ref_s.shape[1] == d and n_ref >= 1 and len(w) == n_ref
+        x_cand_s, x_ref_s, match, _ = self._design_inputs("select_batch", x_cand_s, x_ref_s, w, match)
+        n_cand, n_ref = x_cand_s.shape[0], x_ref_s.shape[0]
+        assert 1 <= size <= n_cand
         self._sel = None
-        m, view, kp = self._view_args(state)
-        with torch.cuda.device(self.device):
-            # (dims: what every entry of the family takes; on a view m goes behind q_local)
-            dims = (self.dtype, self.n, d, self.q_local) + ((m,) if view else ()) + (n_ref, n_cand, int(size))
-            pre = "lcgp_condition_select_" if view else "lcgp_select_"
-            nbytes = self._nbytes(pre + "scratch_bytes", *dims)
+        va = m, view, kp = self._view_args(state)
+        with self.torch.cuda.device(self.device):
             detail = ("%d components of (%d reference points + %d candidates) x %s, all resident"
                       % (self.q_local, n_ref, n_cand, "K', K' = npad + mpad = %d" % kp if view else "n"))
-            scratch = self._grow_scratch(nbytes, ("the batch selection over %d candidates" % n_cand, detail, "pass fewer candidates"))
-            xr = torch.as_tensor(x_ref_s).to(self.device, self.tdtype).contiguous()
-            xc = torch.as_tensor(x_cand_s).to(self.device, self.tdtype).contiguous()
-            wd = torch.as_tensor(np.ascontiguousarray(w, np.float64)).to(self.device)
-            md = None if match is None else torch.as_tensor(match).to(self.device)
-            scs = (self._p(scratch), scratch.numel()) if view else (self._p(scratch),)
+            # (dims: what every entry of the family takes; on a view m goes behind q_local)
+            (pre,), dims, scs, head, (xr, xc, wd, md) = self._design_open(
+                'select', va, (self.dtype, self.n, self.d, self.q_local), (n_ref, n_cand, int(size)),
+                ("the batch selection over %d candidates" % n_cand, detail, "pass fewer candidates"), x_ref_s, x_cand_s, w, match)
             _hip.check(getattr(self.lib, pre + "begin")(
-                *self._head(), *view, n_ref, self._p(xr), self._p(wd), n_cand, self._p(xc),
+                *head, n_ref, self._p(xr), self._p(wd), n_cand, self._p(xc),
                 C.c_void_p(0) if match is None else C.c_void_p(match.ctypes.data),
                 C.c_void_p(0) if md is None else self._p(md), int(r), int(size),
                 min(PREDICT_CHUNK, 2048), *scs), pre + "begin")
             picks = C.c_void_p(0)
             _hip.check(getattr(self.lib, pre + "picks")(*dims, *scs, C.byref(picks)), pre + "picks")
-            self._sel = dict(dims=dims, scratch=scratch, scs=scs, pre=pre, m=m, n_ref=n_ref, n_cand=n_cand, size=int(size), r=int(r),
-                             step=0, picks=picks.value, keep=(xr, xc, wd, md, state))
+            self._sel = dict(dims=dims, scratch=self._scratch, scs=scs, pre=pre, m=m, n_ref=n_ref, n_cand=n_cand, size=int(size),
+                             r=int(r), step=0, picks=picks.value, keep=(xr, xc, wd, md, state))
 
     def select_rows(self):
         """(q_local, n_cand) float64 DEVICE tensor: R_k(c) of the model conditioned on the picks made so far"""
@@ -1379,15 +1300,7 @@ class HotPathEngine:
             raise RuntimeError("the Hessian of the objective is float64 only: evaluate on a float64 engine")
         with torch.cuda.device(self.device):
             width = self.lib.lcgp_nll_hess_width(self.d, self.p)
-            free, _ = torch.cuda.mem_get_info(self.device)
-            free += torch.cuda.memory_reserved(self.device) - torch.cuda.memory_allocated(self.device)
-            free += 0 if self._scratch is None else self._scratch.numel()
-            group = self.q_local
-            while True:
-                nbytes = self._nbytes("lcgp_nll_hess_scratch_bytes", self.dtype, self.n, self.d, self.p, group)
-                if group == 1 or nbytes <= free:
-                    break
-                group = (group + 1) // 2
+            group, nbytes = self._fit_group("lcgp_nll_hess_scratch_bytes", self.dtype, self.n, self.d, self.p, None)
             scp = self._p(self._grow_scratch(nbytes, ("the Hessian of the objective", "%d matrices of n x n per component"
                                                       % (self.d + 4), "use fewer training inputs per GPU")))
             out = torch.empty((self.q_local, width), dtype=torch.float64, device=self.device)

@@ -3081,60 +3081,15 @@ class LCGP:
         w = (scale_k * (1.0 - nug / (1.0 + nug)))[:, None] * sr[None, :] * z
         return eng, self._x_train(), w, bs, lambda masks: self._sobol_subset_matrix(bs, masks)
 
-    def _sobol_subset_mean(self, eng, xc, w, bs, latent, masks):
-        """_sobol_mean for the subsets `masks`: (V (rows, nsub), mean (rows,)) for all p outputs (latent: the q components).  The
-        pairs are dealt round-robin over the ranks that hold an engine; one reduction assembles them."""
-        q, nsub = int(self.q), len(masks)
-        ell = self.lLmb.numpy()
-        pairs = np.array([(k, k) for k in range(q)] if latent else [(k, kp) for k in range(q) for kp in range(k, q)], np.int32)
-        rank, world = _dist.rank_world(self._group)
-        mine = np.arange(rank, len(pairs), min(world, q)) if eng is not None else np.zeros(0, int)
-        full = np.zeros((len(pairs), nsub + 1), F64)
-
-        def share():
-            if len(mine):
-                full[mine, :nsub], full[mine, nsub] = eng.sobol_subset_pairs(xc, w, ell, bs, pairs[mine], masks)
-
-        self._agree(share, what='the Sobol subset sums')
-        if _dist.use_collectives(self._group):
-            full = _dist.all_reduce_sum(full.reshape(-1), self._group, None if eng is None else eng.device).reshape(full.shape)
-        D = np.zeros((q, q, nsub), F64)
-        means = np.zeros(q, F64)
-        for (k, kp), row in zip(pairs, full):
-            D[k, kp] = D[kp, k] = row[:nsub]
-            if k == kp:
-                means[k] = row[nsub]
-        if latent:
-            return D[np.arange(q), np.arange(q)], means
-        W, _, scale, offset = self._output_map()
-        return np.einsum('ka,la,klu->au', W, W, D) * (scale ** 2)[:, None], offset + scale * (W.T @ means)
-
     def _sobol_subset_matrix(self, bs, masks, eng=None, local_sums=None):
         """_sobol_matrix's first line for the subsets `masks`, per latent component: C (q, nsub) with
             C_u = c (prod_{l not in u} I2_l - prod_l I2_l) - sum Q (M_u - M_0)            E[V^c_u] - V^c_u(mean)
         (4.23's formula holds for any u).  Every rank evaluates the components it holds (lcgp_sobol_matrix_subset_pairs) and one
         reduction completes the array; a conditioned view passes its engine and local_sums(loc, c, Dk, sr, ell) -> sums."""
-        d, q, n, nsub = int(self.d), int(self.q), int(self.n), len(masks)
-        if local_sums is None:
-            eng = self._ensure_aux64()
-        sr = np.sqrt(_np(self.r)) if self.submethod == 'rep' else np.ones(n, F64)
-        ell, scale_k, nug = self.lLmb.numpy(), self.lLmb0.numpy(), self.lnugGPs.numpy()
-        c = scale_k * (1.0 - nug / (1.0 + nug))
-        Dk = _np(self.diag_D).reshape(-1)
-        full = np.zeros((q, nsub), F64)
-
-        def share():
-            if eng is not None:
-                loc = [int(k) for k in self._local_ks]
-                if local_sums is not None:
-                    full[loc] = local_sums(loc, c, Dk, sr, ell)
-                    return
-                v = (c[loc] * np.sqrt(Dk[loc]))[:, None] * sr[None, :]
-                full[loc] = eng.sobol_matrix_subset_sums(self._x_train(), v, ell[loc], bs, np.arange(len(loc)), masks)
-
-        self._agree(share, what='the matrix-weighted Sobol subset sums')
-        if _dist.use_collectives(self._group):
-            full = _dist.all_reduce_sum(full.reshape(-1), self._group, None if eng is None else eng.device).reshape(full.shape)
+        d, q, nsub = int(self.d), int(self.q), len(masks)
+        c, ell, full = self._sobol_matrix_shares(
+            nsub, False, 'the matrix-weighted Sobol subset sums', eng, local_sums,
+            lambda eng, v, ell, ks: eng.sobol_matrix_subset_sums(self._x_train(), v, ell, bs, ks, masks))
         width = bs[1] - bs[0]
         inside = ((np.asarray(masks, np.uint64)[:, None] >> np.arange(d, dtype=np.uint64)[None, :]) & np.uint64(1)).astype(bool)
         prior = np.ones((q, nsub), F64)                        # prod of I2 over the inputs NOT in u, l ascending
@@ -3149,7 +3104,7 @@ class LCGP:
     def _sobol_subset_pass(self, ctx, masks, latent, uncertainty):
         """(V (rows, nsub), mean (rows,), E (rows, nsub) or None) of ALL rows (the p outputs; latent: the q components)"""
         eng, xc, w, bs, matrix = ctx
-        V, mean = self._sobol_subset_mean(eng, xc, w, bs, latent, masks)
+        V, mean = self._sobol_mean(eng, xc, w, bs, latent, masks)
         E = V + self._latent_variance_to_rows(matrix(masks), latent) if uncertainty else None
         return V, mean, E
 
@@ -3212,31 +3167,34 @@ class LCGP:
             return ShapleyEffects(*effects(V))
         return ShapleyEffects(*effects(V), *effects(E))
 
-    def _sobol_mean(self, eng, xc, w, bs, latent):
+    def _sobol_mean(self, eng, xc, w, bs, latent, masks=None):
         """The variances of the conditional means and the box mean of a mean surface given as a kernel expansion: centres xc
         (N, d) standardised, weights w (q, N) of ALL components, on the float64 engine eng (None on a rank without components).
         Returns (V (rows, 2 d + 1), mean (rows,)) for all p outputs (latent: the q components), columns as lcgp_sobol_pairs
-        orders the subsets.  The pairs are dealt round-robin over the ranks that hold an engine; one reduction assembles them."""
-        d, q = int(self.d), int(self.q)
+        orders the subsets; with masks (V (rows, nsub), mean) for those subsets (lcgp_sobol_subset_pairs).  The pairs are dealt
+        round-robin over the ranks that hold an engine; one reduction assembles them."""
+        q = int(self.q)
+        width = 2 * int(self.d) + 1 if masks is None else len(masks)
         ell = self.lLmb.numpy()
         pairs = np.array([(k, k) for k in range(q)] if latent else [(k, kp) for k in range(q) for kp in range(k, q)], np.int32)
         rank, world = _dist.rank_world(self._group)
         mine = np.arange(rank, len(pairs), min(world, q)) if eng is not None else np.zeros(0, int)
-        full = np.zeros((len(pairs), 2 * d + 2), F64)
+        full = np.zeros((len(pairs), width + 1), F64)
 
         def share():
             if len(mine):
-                full[mine, :2 * d + 1], full[mine, 2 * d + 1] = eng.sobol_pairs(xc, w, ell, bs, pairs[mine])
+                full[mine, :width], full[mine, width] = (eng.sobol_pairs(xc, w, ell, bs, pairs[mine]) if masks is None else
+                                                         eng.sobol_subset_pairs(xc, w, ell, bs, pairs[mine], masks))
 
-        self._agree(share, what='the Sobol pair sums')
+        self._agree(share, what='the Sobol pair sums' if masks is None else 'the Sobol subset sums')
         if _dist.use_collectives(self._group):
             full = _dist.all_reduce_sum(full.reshape(-1), self._group, None if eng is None else eng.device).reshape(full.shape)
-        D = np.zeros((q, q, 2 * d + 1), F64)
+        D = np.zeros((q, q, width), F64)
         means = np.zeros(q, F64)
         for (k, kp), row in zip(pairs, full):
-            D[k, kp] = D[kp, k] = row[:2 * d + 1]
+            D[k, kp] = D[kp, k] = row[:width]
             if k == kp:
-                means[k] = row[2 * d + 1]
+                means[k] = row[width]
         if latent:
             V, mean = D[np.arange(q), np.arange(q)], means
         else:
@@ -3294,6 +3252,38 @@ class LCGP:
         W, _, scale, _ = self._output_map()
         return np.tensordot((W ** 2).T, lat, axes=(1, 0)) * (scale ** 2).reshape((-1,) + (1,) * (lat.ndim - 1))
 
+    def _sobol_matrix_shares(self, width, with_s0, what, eng, local_sums, engine_sums):
+        """What _sobol_matrix and _sobol_subset_matrix begin with: (c (q,), ell (q, d), full (q, width; with_s0: S0 in one more
+        column)), the matrix-weighted sums of all components.  Every rank evaluates the components it holds -- engine_sums(eng,
+        v, ell, ks) on the fitted model's float64 engine, local_sums(loc, c, Dk, sr, ell) on the engine eng of a conditioned
+        view -- fills their rows of a zero array, and one reduction completes it (`what` names the pass if the ranks disagree)."""
+        q, n = int(self.q), int(self.n)
+        if local_sums is None:
+            eng = self._ensure_aux64()
+        sr = np.sqrt(_np(self.r)) if self.submethod == 'rep' else np.ones(n, F64)
+        ell, scale_k, nug = self.lLmb.numpy(), self.lLmb0.numpy(), self.lnugGPs.numpy()
+        c = scale_k * (1.0 - nug / (1.0 + nug))
+        Dk = _np(self.diag_D).reshape(-1)
+        full = np.zeros((q, width + with_s0), F64)
+
+        def share():
+            if eng is not None:
+                loc = [int(k) for k in self._local_ks]
+                if local_sums is not None:
+                    got = local_sums(loc, c, Dk, sr, ell)
+                else:
+                    v = (c[loc] * np.sqrt(Dk[loc]))[:, None] * sr[None, :]
+                    got = engine_sums(eng, v, ell[loc], np.arange(len(loc)))
+                if with_s0:
+                    full[loc, :width], full[loc, width] = got
+                else:
+                    full[loc] = got
+
+        self._agree(share, what=what)
+        if _dist.use_collectives(self._group):
+            full = _dist.all_reduce_sum(full.reshape(-1), self._group, None if eng is None else eng.device).reshape(full.shape)
+        return c, ell, full
+
     def _sobol_matrix(self, bs, eng=None, local_sums=None):
         """What the posterior covariance of the continuous surface adds, per latent component, over the standardised box bs
         (DESIGN.md 4.23): (C (q, 2 d + 1), IV (q,), overall_var (q,)) with
@@ -3305,28 +3295,10 @@ class LCGP:
         A conditioned view passes its float64 engine and local_sums(loc, c, Dk, sr, ell) -> (sums, s0) of the local
         components loc with ITS matrix Q' over n + m centres; the prior terms and the three lines above are
         the same."""
-        d, q, n = int(self.d), int(self.q), int(self.n)
-        if local_sums is None:
-            eng = self._ensure_aux64()
-        sr = np.sqrt(_np(self.r)) if self.submethod == 'rep' else np.ones(n, F64)
-        ell, scale_k, nug = self.lLmb.numpy(), self.lLmb0.numpy(), self.lnugGPs.numpy()
-        c = scale_k * (1.0 - nug / (1.0 + nug))
-        Dk = _np(self.diag_D).reshape(-1)
-        full = np.zeros((q, 2 * d + 2), F64)
-
-        def share():
-            if eng is not None:
-                loc = [int(k) for k in self._local_ks]
-                if local_sums is not None:
-                    full[loc, :2 * d + 1], full[loc, 2 * d + 1] = local_sums(loc, c, Dk, sr, ell)
-                    return
-                v = (c[loc] * np.sqrt(Dk[loc]))[:, None] * sr[None, :]
-                full[loc, :2 * d + 1], full[loc, 2 * d + 1] = eng.sobol_matrix_sums(self._x_train(), v, ell[loc], bs,
-                                                                                    np.arange(len(loc)))
-
-        self._agree(share, what='the matrix-weighted Sobol pair sums')
-        if _dist.use_collectives(self._group):
-            full = _dist.all_reduce_sum(full.reshape(-1), self._group, None if eng is None else eng.device).reshape(full.shape)
+        d, q = int(self.d), int(self.q)
+        c, ell, full = self._sobol_matrix_shares(
+            2 * d + 1, True, 'the matrix-weighted Sobol pair sums', eng, local_sums,
+            lambda eng, v, ell, ks: eng.sobol_matrix_sums(self._x_train(), v, ell, bs, ks))
         width = bs[1] - bs[0]
         prior = np.zeros((q, 2 * d + 1), F64)                  # prod of I2 over the inputs NOT in u (u = all: the empty product)
         i2all = np.ones(q, F64)
